@@ -8,20 +8,26 @@ A "call" is one read taken through both.  Reads are sharded per GPU (weak scalin
 collective on the data path); the process group is only used for the barrier and the
 max-over-ranks clock.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--whitelist W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--whitelist W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 from a plain `python bench.py` starts torch.distributed.run itself, as a child process and
 before this process has touched a GPU, and exits with the child's code.
 
 `--config 3` / `--config 5` time the other GPU configurations of BASELINE.json instead (K3 graph edges over 500K
-distinct barcodes at threshold 1 / 2) and print a line of the same shape with their own unit and roofline block.
+distinct barcodes at threshold 1 / 2) and print a line of the same shape with their own unit.
 
 Before the W warm-up steps the step runs untimed for a quarter of a second (`config.clock_ramp`; `--no-ramp` skips it): a
 step lasts a millisecond, and a handful of warm-up steps is over before the GPU has left its idle clocks.
 
-After the timed region the run is checked: the library's status word (queue overflow, bad base) and a sample of the
-final records and calls against the CPU oracle; a mismatch exits non-zero and prints no line.
+A plain run does only what the headline needs: inputs, warm-up, the K timed steps, the library's status word (queue
+overflow, bad base; a failure exits non-zero and prints no line), `--dump-outputs`, the line.  `--full` adds everything
+else: the per-kernel table and roofline block, a sample of the final records and calls checked against the CPU oracle (a
+mismatch exits non-zero and prints no line), the CPU baseline and, for the headline at one GPU, the graph passes of
+configs 3 and 5 in the same line.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's share) as DIR/<name>.npy in float32 / float64,
+at most DUMP_BYTES in all; the inputs are seeded, so two builds given the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -41,6 +47,39 @@ from badger_amd import _native, synth  # noqa: E402
 from badger_amd import dist as bdist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES = 60 << 20       # --dump-outputs: array data of one run (the .npy headers come on top, still under 64 MB)
+
+
+def dump_outputs(out_dir, cols, seed=0):
+    """Write cols (name -> (array of one row per item, float dtype), all of one length) as out_dir/<name>.npy.  When they
+    would take more than DUMP_BYTES, a fixed sample of the rows (numpy.default_rng(seed), kept in order) is written
+    instead, with the sampled row numbers as row_index.npy."""
+    n = len(next(iter(cols.values()))[0])
+    row_bytes = sum(np.dtype(dt).itemsize for _, dt in cols.values())
+    rows = None
+    if n * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(seed).choice(n, DUMP_BYTES // (row_bytes + 8), replace=False))
+        cols = dict(((k, (a[rows], dt)) for k, (a, dt) in cols.items()), row_index=(rows, np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (a, dt) in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(dt))
+
+
+def dump_calls(out_dir, recs, best_idx, best_ed, n_ties):
+    """config 2: every read's record (32-bit fields as float64, the byte fields as float32; `reserved` is always 0) and
+    its call against the whitelist (index -1 / distance 255: none)"""
+    r = recs.cpu().numpy().view(_native.REC_DTYPE).reshape(-1)
+    cols = {f: (r[f], np.float64 if r.dtype[f].itemsize == 4 else np.float32) for f in r.dtype.names if f != "reserved"}
+    cols.update(best_idx=(best_idx.cpu().numpy(), np.float64), best_ed=(best_ed.cpu().numpy(), np.float32),
+                n_ties=(n_ties.cpu().numpy().view(np.uint16), np.float32))
+    dump_outputs(out_dir, cols)
+
+
+def dump_edges(out_dir, e):
+    """configs 3 / 5: the rank's share of the edge list sorted by (a, b) - the device lists them in no fixed order"""
+    e = e[np.lexsort((e[:, 1], e[:, 0]))]
+    dump_outputs(out_dir, {"edge_a": (e[:, 0], np.float64), "edge_b": (e[:, 1], np.float64), "edge_dist": (e[:, 2], np.float32)})
+    np.save(os.path.join(out_dir, "edge_count.npy"), np.array([len(e)], dtype=np.float64))
 
 
 def cores_visible():
@@ -244,12 +283,12 @@ GRAPH_PATHS = {"k_graph_probe": ("neighbourhood probes", "blocks of equal rows")
                "k_graph_scan": ("all-pairs sweep", "row blocks of equal pair counts")}
 
 
-def measure_graph(args, rank, world, dev, ctx, thr, n, wl, steps, warmup, ramp, cpu_check):
+def measure_graph(args, rank, world, dev, ctx, thr, n, wl, steps, warmup, ramp, cpu_check, full=True, dump_dir=None):
     """One graph configuration of BASELINE.json (config 3: thr 1, config 5: thr 2): K3 over n distinct observed barcodes,
     every rank its share of the edge list (bdg_graph_edges_part_dev, no collective).  Returns the block of figures rank 0
-    prints: time per pass, rows/s, edges, every kernel of the pass (whatever its name: nothing on this path is a library
-    call any more), the roofline block of the one that takes longest, the whole pass against the HBM roofline, and - at one
-    GPU - the CPU oracle on the same rows, whose whole edge list is the checker."""
+    prints: time per pass, rows/s, edges; with `full` also every kernel of the pass (whatever its name: nothing on this
+    path is a library call any more), the roofline block of the one that takes longest, the whole pass against the HBM
+    roofline, a check of the edges and - at one GPU - the CPU oracle on the same rows, whose whole edge list is the checker."""
     from oracle import pyoracle as orc
     from badger_amd.barcode_graph import qgram_threshold
     ranks = observed_barcodes(n, wl)
@@ -266,18 +305,29 @@ def measure_graph(args, rank, world, dev, ctx, thr, n, wl, steps, warmup, ramp, 
     ramp_steps = clock_ramp(step, dev) if ramp else 0
     for _ in range(max(1, warmup)):
         step()
-    ctx.profile(True)
-    ctx.profile_reset()
+    if full:
+        ctx.profile(True)
+        ctx.profile_reset()
     elapsed = bdist.timed(step, steps, dev)
-    prof = ctx.profile_read()
-    ctx.profile(False)
+    if full:
+        prof = ctx.profile_read()
+        ctx.profile(False)
     ctx.graph_status()                                 # (what the asynchronous calls could not return)
     ne = int(d_n[0])
     if ne > cap:
         raise SystemExit("edge capacity too small: %d > %d" % (ne, cap))
+    e = d_edges[:ne].cpu().numpy().view(np.uint32)
+    if dump_dir and rank == 0:
+        dump_edges(dump_dir, e)
+    if not full:
+        ne_all = int(bdist.all_sum(ne, dev))
+        return None if rank != 0 else {
+            "threshold": thr, "rows": n, "qgram_T": T, "ms_per_pass": elapsed / steps * 1e3, "rows_per_s": n / (elapsed / steps),
+            "steps": steps, "warmup": warmup, "edges_rank0": ne, "edges_all_ranks": ne_all,
+            "parallelism": "one share of the edge list per GPU (bdg_graph_edges_part_dev), no collectives",
+            "clock_ramp": "%d untimed passes before the %d warm-up passes" % (ramp_steps, warmup)}
     # check (every rank, its own share): no edge twice, and 3,000 sampled edges are edges by the oracle's S and dmin with the
     # distance they carry; the whole list is compared with the oracle's below (one GPU) or by its length (several)
-    e = d_edges[:ne].cpu().numpy().view(np.uint32)
     rng = np.random.default_rng(7 + rank)
     status = "ok"
     key = e[:, 0].astype(np.uint64) << np.uint64(32) | e[:, 1].astype(np.uint64)
@@ -370,21 +420,22 @@ def bench_graph(args, rank, world, dev, local_dev):
     wl = synth.make_whitelist(args.whitelist)
     ctx = _native.Context(local_dev)
     ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    blk = measure_graph(args, rank, world, dev, ctx, thr, n, wl, args.steps, args.warmup, not args.no_ramp, not args.no_cpu_baseline)
+    blk = measure_graph(args, rank, world, dev, ctx, thr, n, wl, args.steps, args.warmup, not args.no_ramp,
+                        args.full and not args.no_cpu_baseline, args.full, args.dump_outputs)
     if rank == 0:
         line = {
             "metric": "graph rows/sec, threshold=%d, %d distinct barcodes" % (thr, n), "value": blk["rows_per_s"],
             "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": blk["ms_per_pass"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u32", "data": "synthetic",
-            "config": {"workload": "BASELINE config %d: barcode_graph edges, threshold %d, %d distinct observed barcodes (%s)"
-                                   % (args.config, thr, n, blk["path"]),
+            "config": {"workload": "BASELINE config %d: barcode_graph edges, threshold %d, %d distinct observed barcodes%s"
+                                   % (args.config, thr, n, " (%s)" % blk["path"] if "path" in blk else ""),
                        "rows": n, "edges_rank0": blk["edges_rank0"], "edges_all_ranks": blk["edges_all_ranks"], "qgram_T": blk["qgram_T"],
                        "parallelism": blk["parallelism"], "clock_ramp": blk["clock_ramp"]},
-            "roofline": blk["roofline"], "whole_pass": blk["whole_pass"],
-            "kernels_ms_per_step": blk["kernels_ms_per_pass"],
-            "parity_sample": blk["parity_sample"],
         }
+        if args.full:
+            line.update({"roofline": blk["roofline"], "whole_pass": blk["whole_pass"],
+                         "kernels_ms_per_step": blk["kernels_ms_per_pass"], "parity_sample": blk["parity_sample"]})
         if "cpu_baseline" in blk:
             line["cpu_baseline"] = blk["cpu_baseline"]
         print(json.dumps(line))
@@ -401,8 +452,13 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 5),
                     help="BASELINE.json config: 2 = the headline (K1 + K2), 3 = graph thr 1, 5 = graph thr 2")
     ap.add_argument("--rows", type=int, default=500000, help="distinct barcodes for --config 3 / 5")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-graph", action="store_true", help="headline only: skip the graph passes (configs 3 and 5) behind the config-2 measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel table and roofline block, oracle check of a sample of the output, CPU "
+                         "baseline and (config 2, one GPU) the graph passes of configs 3 and 5 in the same line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's share) as DIR/<name>.npy, float32 / float64, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-graph", action="store_true", help="--full without the graph passes (configs 3 and 5) behind the config-2 measurement")
     ap.add_argument("--graph-algo", type=int, default=0, help="--config 3 / 5: bdg_graph_set_algo (0: the library's choice)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="no batch pipelining.  By default (bdg_set_overlap) the whitelist match of batch i runs on a second stream beside "
@@ -413,6 +469,8 @@ def main():
                     help="the multi-rank plumbing without GPUs (self-launch, rendezvous, row / read split, barrier, max-over-ranks clock, "
                          "rank 0's line) with a stub in place of the step; prints a line marked \"rehearsal\": true - never a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, local_rank, world = bdist.env_rank()
     if world != args.gpus:
@@ -500,12 +558,13 @@ def bench_calls(args, rank, world, dev, local_dev):
         ctx.extract_batch_dev(bases, off_u, n, total_bytes, 12, recs_b[b])
         ctx.nearest16_recs_dev(recs_b[b], n, 2, idx_b[b], ed_b[b], ties_b[b])      # every record's barcode against the whitelist
 
-    # Warm-up with every kernel timed: it says which kernel dominates.  In the timed region only that kernel carries events
-    # (a pair of events per kernel costs the step ~6 % when all eight kernels have one); the per-kernel table of the line
-    # comes from a few more steps behind the timed region, all kernels timed again.
+    # --full: warm-up with every kernel timed: it says which kernel dominates.  In the timed region only that kernel carries
+    # events (a pair of events per kernel costs the step ~6 % when all eight kernels have one); the per-kernel table of the
+    # line comes from a few more steps behind the timed region, all kernels timed again.  A plain run times no kernel.
     ramp_steps = clock_ramp(step, dev) if not args.no_ramp else 0
-    ctx.profile(True)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile(True)
+        ctx.profile_reset()
     for _ in range(max(1, args.warmup)):
         step()
     rc, bad, nwin = ctx.extract_status()
@@ -516,29 +575,34 @@ def bench_calls(args, rank, world, dev, local_dev):
     if rc != 0:
         raise SystemExit("extract failed: rc=%d bad_read=%d" % (rc, bad))
     stats = ctx.extract_counters()
-    warm = ctx.profile_read()
-    dom = max((k for k, v in warm.items() if v[0]), key=lambda k: warm[k][1] / warm[k][0])
-    ctx.profile_only(dom)
-    ctx.profile_reset()
+    if args.full:
+        warm = ctx.profile_read()
+        dom = max((k for k, v in warm.items() if v[0]), key=lambda k: warm[k][1] / warm[k][0])
+        ctx.profile_only(dom)
+        ctx.profile_reset()
 
     # barrier + sync, K steps, sync (device-wide: both streams) + barrier, max over ranks; with batch pipelining the match of
     # the last warm-up step is queued before the clock starts and the match of the last timed step before it stops
     elapsed = bdist.timed(step, args.steps, dev, settle=None if args.no_overlap else ctx.synchronize)
-    prof = ctx.profile_read()                       # the dominant kernel, measured live over the timed region
-    ctx.profile_only(None)
-    ctx.profile_reset()
-    table_steps = min(5, args.steps)
-    for _ in range(table_steps):
-        step()
-    table = ctx.profile_read()
-    ctx.profile(False)
     last = (count[0] - 1) % nbuf
+    if args.dump_outputs and rank == 0:
+        dump_calls(args.dump_outputs, recs_b[last], idx_b[last], ed_b[last], ties_b[last])
+    if args.full:
+        prof = ctx.profile_read()                   # the dominant kernel, measured live over the timed region
+        ctx.profile_only(None)
+        ctx.profile_reset()
+        table_steps = min(5, args.steps)
+        for _ in range(table_steps):
+            step()
+        table = ctx.profile_read()
+        ctx.profile(False)
+        last = (count[0] - 1) % nbuf
     recs, best_idx, best_ed, n_ties = recs_b[last], idx_b[last], ed_b[last], ties_b[last]
 
-    # ---- the timed steps must have been clean, and their output right (every rank checks its own)
+    # ---- the timed steps must have been clean, and (--full) their output right (every rank checks its own)
     rc, bad, nwin = ctx.extract_status()
     status = "ok" if rc == 0 else "extract status after the timed region: rc=%d bad_read=%d" % (rc, bad)
-    if status == "ok":
+    if status == "ok" and args.full:
         status = parity_sample(ctx, bases, off_u, n, wl, recs, best_idx, best_ed, n_ties)
     fails = bdist.all_max(0.0 if status == "ok" else 1.0, dev)
     if status != "ok":
@@ -549,22 +613,8 @@ def bench_calls(args, rank, world, dev, local_dev):
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * n / (elapsed / args.steps)
-        # roofline of the dominant kernel: algorithmic bytes of the unit it serves / its own launch time
-        k1 = ("k_scan_reads", "k_sw_clusters", "k_sw_singles", "k_strict_filter", "k_finalize_reads")
-        per_launch_ms = {k: v[1] / max(1, v[0]) for k, v in prof.items() if v[0]}
-        table_ms = {k: v[1] / max(1, v[0]) for k, v in table.items() if v[0]}
         k1_bytes = total_bytes + 40 * n                # sum(L_i) + 8 (offset) + 32 (record) per read
         k2_bytes = 11 * n + 4 * len(wl)                # 4 (query) + 7 (idx, ed, ties) per call + whitelist once
-        alg = k1_bytes if dom in k1 else k2_bytes
-        achieved = alg / (per_launch_ms[dom] * 1e-3) / 1e9
-        pc = profile_counters(dom)
-        # SURVEY 8d (iii): the path is integer-issue bound, so say how close the kernel is to THAT ceiling:
-        # 1024 SIMDs, one wave64 VALU instruction per 4 clocks each, at the 2.4 GHz peak clock
-        issue_peak = 1024 * 2.4e9 / 4.0
-        valu = pc["valu"]
-        int_issue = None if valu is None else {"valu_insts_per_launch": valu, "achieved": valu / (per_launch_ms[dom] * 1e-3),
-                                               "peak": issue_peak, "unit": "wave-instr/s",
-                                               "frac": valu / (per_launch_ms[dom] * 1e-3) / issue_peak}
         line = {
             "metric": "barcode calls/sec vs 737K 10x whitelist", "value": value, "unit": "calls/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -576,12 +626,29 @@ def bench_calls(args, rank, world, dev, local_dev):
                        "parallelism": "reads sharded per GPU, no collectives",
                        "clock_ramp": "%d untimed steps (%.2f s) before the %d warm-up steps" % (ramp_steps, RAMP_S, args.warmup),
                        "batch_pipelining": "off" if args.no_overlap else "K2 of batch i on a second stream beside the alignment kernels of batch i+1, behind its scan (two record buffers)"},
+            # the whole step against the HBM roofline: the algorithmic bytes of K1 and K2 together / the step's time per GPU
+            "whole_step": {"algorithmic_bytes": k1_bytes + k2_bytes, "achieved": (k1_bytes + k2_bytes) / (ms_per_step * 1e-3) / 1e9, "unit": "GB/s",
+                           "frac_of_hbm_peak": (k1_bytes + k2_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+        }
+    if rank == 0 and args.full:
+        # roofline of the dominant kernel: algorithmic bytes of the unit it serves / its own launch time
+        k1 = ("k_scan_reads", "k_sw_clusters", "k_sw_singles", "k_strict_filter", "k_finalize_reads")
+        per_launch_ms = {k: v[1] / max(1, v[0]) for k, v in prof.items() if v[0]}
+        table_ms = {k: v[1] / max(1, v[0]) for k, v in table.items() if v[0]}
+        alg = k1_bytes if dom in k1 else k2_bytes
+        achieved = alg / (per_launch_ms[dom] * 1e-3) / 1e9
+        pc = profile_counters(dom)
+        # SURVEY 8d (iii): the path is integer-issue bound, so say how close the kernel is to THAT ceiling:
+        # 1024 SIMDs, one wave64 VALU instruction per 4 clocks each, at the 2.4 GHz peak clock
+        issue_peak = 1024 * 2.4e9 / 4.0
+        valu = pc["valu"]
+        int_issue = None if valu is None else {"valu_insts_per_launch": valu, "achieved": valu / (per_launch_ms[dom] * 1e-3),
+                                               "peak": issue_peak, "unit": "wave-instr/s",
+                                               "frac": valu / (per_launch_ms[dom] * 1e-3) / issue_peak}
+        line.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": pc["traffic"], "traffic_source": pc["source"],
                          "algorithmic_bytes_per_launch": alg, "kernel_ms": per_launch_ms[dom], "int_issue": int_issue},
-            # the whole step against the same roofline: the algorithmic bytes of K1 and K2 together / the step's time per GPU
-            "whole_step": {"algorithmic_bytes": k1_bytes + k2_bytes, "achieved": (k1_bytes + k2_bytes) / (ms_per_step * 1e-3) / 1e9, "unit": "GB/s",
-                           "frac_of_hbm_peak": (k1_bytes + k2_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
             "kernels_ms_per_step": {k: round(v, 4) for k, v in sorted(table_ms.items())},
             "kernels_ms_per_step_source": "%d steps behind the timed region with every kernel timed; roofline.kernel_ms is the dominant "
                                           "kernel's mean over the timed region itself, where only it carries events%s" % (
@@ -589,13 +656,13 @@ def bench_calls(args, rank, world, dev, local_dev):
                                               "k_strict_filter / k_finalize_reads of the next batch: those durations overlap and do not add up to the step "
                                               "(k_scan_reads runs alone)"),
             "parity_sample": "ok",
-        }
+        })
         if not args.no_cpu_baseline and world == 1:       # the CPU leg runs at N = 1 only (the host threads would fight the other ranks)
             line["cpu_baseline"] = cpu_baseline(bases, off_u, wl, (recs, best_idx, best_ed, n_ties))
             line["parity_sample"] = "ok (3 x 1000 records and calls after the timed region; " + line["cpu_baseline"].pop("checked") + ")"
-    # BASELINE configs 3 and 5 in the same line (one GPU): the graph passes at 500 K rows, thr 1 and thr 2, each with its
-    # kernel table, roofline block, CPU oracle on the same rows and the whole edge list compared
-    if world == 1 and not args.no_graph:
+    # --full: BASELINE configs 3 and 5 in the same line (one GPU): the graph passes at 500 K rows, thr 1 and thr 2, each with
+    # its kernel table, roofline block, CPU oracle on the same rows and the whole edge list compared
+    if args.full and world == 1 and not args.no_graph:
         for key, thr in (("graph_thr1", 1), ("graph_thr2", 2)):
             blk = measure_graph(args, rank, world, dev, ctx, thr, args.rows, wl, args.steps, args.warmup, not args.no_ramp, not args.no_cpu_baseline)
             line[key] = blk

@@ -103,3 +103,23 @@ def test_multi_rank_rehearsal_over_gloo():
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["units_all_ranks"] == 2000
+
+
+def test_dump_outputs_writes_floats_within_the_budget_and_samples_fixed_rows(tmp_path):
+    """--dump-outputs: every array as float32 / float64; an output larger than DUMP_BYTES is written as a sample of its rows
+    that is the same from run to run, with the row numbers beside it; a small one is written whole"""
+    import numpy as np
+    n = 2 * bench.DUMP_BYTES // 12
+    a = np.arange(n, dtype=np.uint32) * np.uint32(2654435761)
+    cols = {"wide": (a, np.float64), "narrow": (a & np.uint32(255), np.float32)}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), cols)
+    got = {f: np.load(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one")}
+    assert sorted(got) == ["narrow.npy", "row_index.npy", "wide.npy"]
+    assert sum(os.path.getsize(tmp_path / "one" / f) for f in got) < 64e6
+    rows = got["row_index.npy"].astype(np.int64)
+    assert got["wide.npy"].dtype == np.float64 and got["narrow.npy"].dtype == np.float32 and (np.diff(rows) > 0).all()
+    assert (got["wide.npy"] == a[rows]).all() and (got["narrow.npy"] == (a & 255)[rows]).all()
+    assert all((np.load(tmp_path / "two" / f) == v).all() for f, v in got.items())
+    bench.dump_outputs(str(tmp_path / "small"), {"x": (a[:1000], np.float64)})
+    assert os.listdir(tmp_path / "small") == ["x.npy"] and (np.load(tmp_path / "small" / "x.npy") == a[:1000]).all()

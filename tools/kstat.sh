@@ -1,8 +1,9 @@
 #!/bin/bash
 # usage: kstat.sh <tag>   (GPU box) kernel durations of a short bench run, parity ignored
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/kstat_$1; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/log.txt 2>&1
 f=$(find $OUT -name "*_kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv,sys

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Runs on the GPU box: a short bench line plus one PMC pass, then the instruction counts of k_scan_reads (iteration helper).
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/scanq
 rm -rf $OUT; mkdir -p $OUT
-python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])
