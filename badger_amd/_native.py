@@ -38,7 +38,7 @@ EXPORTS = [
     "bdg_graph_edges", "bdg_graph_edges_dev", "bdg_graph_edges_rows_dev", "bdg_graph_edges_part_dev", "bdg_graph_set_algo", "bdg_graph_status", "bdg_distinct_dev", "bdg_rows_of_dev",
     "bdg_extract_submit", "bdg_extract_collect", "bdg_extract_keep_records", "bdg_kept_records", "bdg_kept_records_to_host", "bdg_keep_observed", "bdg_touched_count_dev",
     "bdg_ingest_open", "bdg_ingest_open_mt", "bdg_ingest_open_ex", "bdg_ingest_next", "bdg_ingest_release", "bdg_ingest_error",
-    "bdg_ingest_reads", "bdg_ingest_close", "bdg_format_rows", "bdg_stage1_run",
+    "bdg_ingest_reads", "bdg_ingest_close", "bdg_format_rows", "bdg_format_rows_wl", "bdg_stage1_run",
     "bdg_cluster_dev", "bdg_assign_reads_dev", "bdg_idstore_new", "bdg_idstore_free", "bdg_idstore_count", "bdg_idstore_append",
     "bdg_idstore_get", "bdg_stage1_collect", "bdg_write_assignments", "bdg_import_stage1_tsv", "bdg_host_free",
 ]
@@ -63,7 +63,8 @@ class IngestOpts(C.Structure):
 class Stage1Opts(C.Structure):
     """bdg_stage1_opts"""
     _fields_ = [("umi_len", C.c_uint32), ("threads", C.c_uint32), ("format_threads", C.c_uint32), ("header_every", C.c_uint32),
-                ("chunk_reads", C.c_uint32), ("skip_secondary", C.c_int32), ("segment_bytes", C.c_uint64)]
+                ("chunk_reads", C.c_uint32), ("skip_secondary", C.c_int32), ("segment_bytes", C.c_uint64),
+                ("whitelist", C.c_uint32), ("max_bc_dist", C.c_uint32)]
 
 
 class Stage1Result(C.Structure):
@@ -72,7 +73,8 @@ class Stage1Result(C.Structure):
                 ("first_polyt", C.c_uint64), ("first_r1", C.c_uint64), ("bad_read", C.c_uint64),
                 ("chunks", C.c_uint64), ("out_bytes", C.c_uint64), ("seconds_total", C.c_double),
                 ("seconds_wait_parse", C.c_double), ("seconds_submit", C.c_double), ("seconds_wait_gpu", C.c_double),
-                ("seconds_wait_format", C.c_double), ("seconds_format", C.c_double), ("seconds_write", C.c_double)]
+                ("seconds_wait_format", C.c_double), ("seconds_format", C.c_double), ("seconds_write", C.c_double),
+                ("whitelist_barcodes", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -177,6 +179,8 @@ def load():
     L.bdg_ingest_close.restype = None
     L.bdg_format_rows.argtypes = [C.POINTER(IngestChunk), vp, vp, u64, C.POINTER(u64)]
     L.bdg_format_rows.restype = C.c_int64
+    L.bdg_format_rows_wl.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
+    L.bdg_format_rows_wl.restype = C.c_int64
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("bdg_free",):
@@ -513,13 +517,15 @@ def chunk_reads(ch):
 
 
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
-               chunk_reads=0, segment_bytes=0, format_threads=0):
+               chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
-    without a sequence."""
+    without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
+    whitelist columns (header must name them)."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
-    o = Stage1Opts(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes)
+    o = Stage1Opts(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
+                   1 if whitelist else 0, max_bc_dist)
     res = Stage1Result()
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"), C.byref(o), C.byref(res))
     if rc != 0:
@@ -645,6 +651,29 @@ def format_rows(ch, recs):
     got = L.bdg_format_rows(C.byref(ch), recs.ctypes.data, buf, int(need), counts)
     if got < 0 or got > need:
         raise BadgerHipError(int(got), "bdg_format_rows")
+    return buf.raw[:got], tuple(int(x) for x in counts)
+
+
+def format_rows_wl(ch, recs, best_idx, best_ed, n_ties, wl):
+    """format_rows with the three whitelist columns (bdg_format_rows_wl): the match's answer per record and the whitelist
+    (ranks, caller order).  Counts: (reads, barcodes, polyT, R1, whitelist barcodes)"""
+    L = load()
+    recs = np.ascontiguousarray(recs)
+    idx = np.ascontiguousarray(best_idx, dtype=np.uint32)
+    ed = np.ascontiguousarray(best_ed, dtype=np.uint8)
+    ties = np.ascontiguousarray(n_ties, dtype=np.uint16)
+    wl = np.ascontiguousarray(wl, dtype=np.uint32)
+    if not (len(recs) == len(idx) == len(ed) == len(ties) == ch.n):
+        raise ValueError("format_rows_wl: %d reads, %d records, %d / %d / %d calls" % (ch.n, len(recs), len(idx), len(ed), len(ties)))
+    counts = (C.c_uint64 * 5)()
+    args = (recs.ctypes.data, idx.ctypes.data, ed.ctypes.data, ties.ctypes.data, wl.ctypes.data, len(wl))
+    need = L.bdg_format_rows_wl(C.byref(ch), *args, None, 0, counts)
+    if need < 0:
+        raise BadgerHipError(int(need), "bdg_format_rows_wl")
+    buf = C.create_string_buffer(int(need) + 1)
+    got = L.bdg_format_rows_wl(C.byref(ch), *args, buf, int(need), counts)
+    if got < 0 or got > need:
+        raise BadgerHipError(int(got), "bdg_format_rows_wl")
     return buf.raw[:got], tuple(int(x) for x in counts)
 
 

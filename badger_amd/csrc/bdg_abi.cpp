@@ -19,6 +19,7 @@ int bdg_extract_judge_host(bdg_ctx*, const void*, uint64_t, uint64_t*, uint64_t*
 size_t bdg_extract_counter_bytes();
 int bdg_whitelist_load_impl(bdg_ctx*, const uint32_t*, uint32_t);
 int bdg_nearest16_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*);
+int bdg_nearest16_check(bdg_ctx*, uint32_t, uint32_t);
 int bdg_graph_launch(bdg_ctx*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, int32_t, bdg_edge*, uint64_t, uint64_t*, uint32_t part = 0, uint32_t nparts = 1);
 int bdg_graph_plan(const bdg_ctx*, uint32_t, uint32_t);
 int bdg_graph_join_flags(bdg_ctx*, uint32_t*);
@@ -259,11 +260,13 @@ void bdg_free(bdg_ctx* ctx)
     for (hipEvent_t e : ctx->ev_aux) if (e) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
                        &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_prefix, &ctx->w_bitmap, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
-                       &ctx->n_list, &ctx->n_counters, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs };
+                       &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
-        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs }) if (b->p) (void)hipFree(b->p);
+        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match }) if (b->p) (void)hipFree(b->p);
         if (sl.h_recs) (void)hipHostFree(sl.h_recs);
+        if (sl.h_match) (void)hipHostFree(sl.h_match);
+        if (sl.match_done) (void)hipEventDestroy(sl.match_done);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
         if (sl.h_counters) (void)hipHostFree(sl.h_counters);
         if (sl.done) (void)hipEventDestroy(sl.done);
@@ -291,13 +294,23 @@ int bdg_synchronize(bdg_ctx* ctx)
     return sync_all(ctx);
 }
 
+static int ensure_aux(bdg_ctx* ctx);
+
 int bdg_set_overlap(bdg_ctx* ctx, int on)
 {
     if (!ctx) return BDG_E_ARG;
     int rc = sync_all(ctx);
     if (rc) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (on && !ctx->aux_stream) {
+    if (on) { const int rca = ensure_aux(ctx); if (rca) return rca; }
+    ctx->aux_count = 0;
+    ctx->overlap = on != 0;
+    return BDG_OK;
+}
+
+static int ensure_aux(bdg_ctx* ctx)
+{
+    if (!ctx->aux_stream) {
         // (same priority as the main stream: measured against the lowest and the highest one, tools/ov_prio_probe.sh)
         BDG_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
         // (device-scope release: these events order kernels of two streams of one device; the default, a release to the
@@ -307,8 +320,6 @@ int bdg_set_overlap(bdg_ctx* ctx, int on)
         BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[0], hipEventDisableTiming | hipEventReleaseToDevice));
         BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[1], hipEventDisableTiming | hipEventReleaseToDevice));
     }
-    ctx->aux_count = 0;
-    ctx->overlap = on != 0;
     return BDG_OK;
 }
 
@@ -468,7 +479,7 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "slot still in flight: collect it first");
     if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (umi_len == 0 || umi_len > 64) return bdg_fail(ctx, BDG_E_ARG, "umi_len out of range");
-    sl.n = n; sl.umi_len = umi_len; sl.total = 0;
+    sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
     if (n == 0) { sl.busy = true; return BDG_OK; }
     for (uint32_t i = 0; i < n; ++i) {
         if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
@@ -524,6 +535,7 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
         // this chunk overflowed a queue: run it again (its input is still on the device) behind whatever is queued
         int rc2 = slot_enqueue(ctx, sl);
         if (rc2) return rc2;
+        sl.reran = true;
     }
     if (rc) return rc;
     memcpy(out, sl.h_recs, sizeof(bdg_extract_rec) * (size_t)sl.n);
@@ -543,6 +555,62 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
         BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(ctx->x_allrecs.p) + have, sl.d_recs.p, add, hipMemcpyDeviceToDevice, ctx->stream));
         ctx->x_allrecs_n += sl.n;
     }
+    return BDG_OK;
+}
+
+static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed)
+{
+    int rc;
+    if ((rc = ensure_aux(ctx))) return rc;
+    const size_t n = sl.n;
+    if ((rc = bdg_reserve(ctx, sl.d_match, 7 * n + 64))) return rc;
+    if ((rc = pinned_reserve(ctx, sl.h_match, sl.h_match_bytes, 7 * n + 64))) return rc;
+    if (!sl.match_done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.match_done, hipEventDisableTiming));
+    auto* d_idx = static_cast<uint32_t*>(sl.d_match.p);
+    auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n);
+    auto* d_ed = reinterpret_cast<uint8_t*>(d_ties + n);
+    BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, sl.done, 0));      // behind the chunk's extraction
+    ctx->launch_stream = ctx->aux_stream;
+    ctx->aux_pending = true;
+    rc = bdg_nearest16_launch(ctx, reinterpret_cast<const uint32_t*>(sl.d_recs.p) + 5, 8u, 1, sl.n, max_ed, d_idx, d_ed, d_ties);
+    ctx->launch_stream = nullptr;
+    if (rc) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_match, sl.d_match.p, 7 * n, hipMemcpyDeviceToHost, ctx->aux_stream));
+    BDG_HIP_TRY(ctx, hipEventRecord(sl.match_done, ctx->aux_stream));
+    sl.match_max_ed = max_ed;
+    sl.match_queued = true;
+    return BDG_OK;
+}
+
+int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed)
+{
+    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
+    if (sl.n == 0) return BDG_OK;
+    int rc = bdg_nearest16_check(ctx, sl.n, max_ed);
+    if (rc) return rc;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return queue_slot_match(ctx, sl, max_ed);
+}
+
+int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties)
+{
+    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    if (sl.n == 0) return BDG_OK;
+    if (!sl.match_queued) return bdg_fail(ctx, BDG_E_ARG, "no match queued for this slot");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if (sl.reran && (rc = queue_slot_match(ctx, sl, sl.match_max_ed))) return rc;     // the records changed: match them again
+    sl.reran = false;
+    BDG_HIP_TRY(ctx, hipEventSynchronize(sl.match_done));
+    sl.match_queued = false;
+    const size_t n = sl.n;
+    const auto* h_idx = static_cast<const uint32_t*>(sl.h_match);
+    const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n);
+    const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + n);
+    memcpy(best_idx, h_idx, 4 * n); memcpy(n_ties, h_ties, 2 * n); memcpy(best_ed, h_ed, n);
     return BDG_OK;
 }
 
@@ -609,7 +677,7 @@ int bdg_whitelist_load(bdg_ctx* ctx, const uint32_t* wl, uint32_t nw)
 
 int bdg_nearest16_set_algo(bdg_ctx* ctx, int algo)
 {
-    if (!ctx || algo < 0 || algo > 2) return BDG_E_ARG;
+    if (!ctx || algo < 0 || algo > 3) return BDG_E_ARG;
     ctx->n16_algo = algo;
     return BDG_OK;
 }
@@ -643,9 +711,12 @@ int bdg_nearest16_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t
     if (ctx->overlap) {
         // not queued yet: it goes behind the next extraction's scan (or behind everything queued so far, at the next
         // synchronisation, whitelist change or match)
-        int rc = bdg_launch_deferred_match(ctx, false);
+        // everything the launch would reject is rejected HERE, at the call that asked for the match: a match that fails
+        // when it is finally queued would fail inside the next extraction
+        int rc = bdg_nearest16_check(ctx, n, max_ed);
         if (rc) return rc;
-        if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+        if ((rc = bdg_launch_deferred_match(ctx, false))) return rc;
+        if (n == 0) return BDG_OK;
         ctx->deferred.pending = true;
         ctx->deferred.q = reinterpret_cast<const uint32_t*>(d_recs) + 5; ctx->deferred.n = n; ctx->deferred.max_ed = max_ed;
         ctx->deferred.idx = d_best_idx; ctx->deferred.ed = d_best_ed; ctx->deferred.ties = d_n_ties;

@@ -72,6 +72,13 @@ struct bdg_ctx {
         hipEvent_t done = nullptr;
         uint32_t n = 0, umi_len = 0; uint64_t total = 0, qcap = 0;
         bool busy = false;
+        bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
+        // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
+        DevBuf d_match;                                      // best_idx u32 [n] | n_ties u16 [n] | best_ed u8 [n]
+        void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
+        hipEvent_t match_done = nullptr;
+        uint32_t match_max_ed = 0;
+        bool match_queued = false;
     } slots[BDG_SLOTS];
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
@@ -96,6 +103,7 @@ struct bdg_ctx {
     int n16_algo = 0;
     DevBuf n_list;       // uint32 [(8 + 1) * nq] level-2 query list (8 segments) + overflow list
     DevBuf n_counters;   // one 128-byte line per list segment + one for the overflow list
+    DevBuf n_coop;       // uint64 partials of the cooperative kernel: one per (query, slice, wave)
 
     // ---- graph workspace (graph_kernels.hip)
     int graph_algo = 0;
@@ -122,6 +130,11 @@ struct bdg_ctx {
 int bdg_reserve(bdg_ctx* ctx, DevBuf& b, size_t bytes);
 const void* bdg_extract_counters_now(const bdg_ctx* ctx);   // the counters of the extraction launched last (extract_kernels.hip)
 int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan);   // overlap mode: queue the waiting whitelist match now (bdg_abi.cpp)
+// Stage 1 with a whitelist (bdg_abi.cpp): queue the match of the chunk just submitted to `slot` on the auxiliary stream, behind
+// its extraction, so that it runs beside the next chunk's; after bdg_extract_collect of the slot, wait for it and take the
+// results (a chunk that collect had to run again is matched again first).
+extern "C" int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed);
+extern "C" int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties);
 
 // Event-bracketed launch bookkeeping.
 int  bdg_timer_id(bdg_ctx* ctx, const char* name);

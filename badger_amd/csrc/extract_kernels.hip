@@ -1456,7 +1456,9 @@ int bdg_extract_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_o
                            static_cast<const uint8_t*>(ctx->x_lut.p), static_cast<int32_t*>(ctx->x_polyt.p),
                            qa, qb, qcap, counters, keys);
     }
-    if (ctx->deferred.pending && (rc = bdg_launch_deferred_match(ctx, true))) return rc;      // overlap mode: the match of the batch before
+    // overlap mode: the match of the batch before.  Its error is returned once this batch is complete: between the scan and
+    // k_finalize_reads (which clears the other counter set for the next batch) there is no way out
+    const int rc_match = ctx->deferred.pending ? bdg_launch_deferred_match(ctx, true) : BDG_OK;
     {
         ScopedKernelTimer tm(ctx, "k_sw_clusters");
         hipLaunchKernelGGL(k_sw_clusters, dim3(256 * 8), dim3(256), 0, st, d_bases, total_rounded, d_off, n, pt,
@@ -1484,7 +1486,7 @@ int bdg_extract_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_o
                            next_counters);
     }
     BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    return rc_match;
 }
 
 namespace {

@@ -2,11 +2,13 @@
 // body of BarcodeGraph.postprocessing, reference barcode_graph.py:376-384, whose
 // distance is editdistance.eval on 16-character strings).
 //
-// Two device paths with identical results (ties -> lowest caller index, tie count):
+// Three device paths with identical results (ties -> lowest caller index, tie count):
 //   scan   k_nearest_scan: exhaustive.  One query per lane (its four 16-bit match
 //          vectors live in registers), whitelist tiles staged in LDS and broadcast to
 //          the wave, Myers/Hyyro bit-vector distance per pair.  Any max_ed.
-//   probe  k_nearest_pairs + k_nearest_delins (+ k_nearest_scan for the rare query whose hit list overflows), max_ed <= 2:
+//   coop   k_nearest_coop + k_nearest_coop_merge: exhaustive, one query per WAVE (the scan with query and entry swapped), the
+//          whitelist cut into slices over the chip.  Any max_ed; what automatic mode runs below COOP_NQ_MAX queries.
+//   probe  k_nearest_pairs + k_nearest_delins (+ k_nearest_coop for the rare query whose hit list overflows), max_ed <= 2:
 //          instead of the whitelist the places are visited where a neighbour can sit.  An entry within Hamming distance 2
 //          shares two whole 4-base blocks with the query: six tables of buckets keyed by a block pair (pass 1, which
 //          settles distance 0 and 1 and the two-substitution neighbours).  Equal-length strings at distance 2 that are
@@ -111,6 +113,183 @@ void k_nearest_scan(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
         best_idx[qi] = bidx; best_ed[qi] = (uint8_t)best; n_ties[qi] = (uint16_t)(ties > 0xFFFFu ? 0xFFFFu : ties);
     }
   }
+}
+
+// ---- wave-cooperative best-hit scan ---------------------------------------------
+// The exhaustive scan with the roles of query and entry swapped: a query is the same for the whole wave (scalar registers,
+// taken through readfirstlane), each lane evaluates a different whitelist entry (its two bit planes in vector registers), and
+// the wave's answer is a min reduction of the packed key (ed << 32 | caller index) plus a sum of the lane tie counts at that
+// distance.  k_nearest_scan needs one query per LANE to fill the chip (65,536 queries for one 256-lane block per CU); this
+// kernel fills it with one query, by cutting the whitelist into slices.
+// Work item = (group of COOP_QG queries, slice of the sorted whitelist); a block stages its slice in LDS tiles of
+// COOP_TILE entries, and every one of its 4 waves runs the group's queries over a quarter of each tile (lane t: entries t,
+// t + 256, ...).  Each wave writes one partial per (query, slice): no atomics, and k_nearest_coop_merge combines the
+// 4 * nslices partials of a query in a fixed order - the answer does not depend on the plan.
+// The grid is fixed and loops over the items; the query count may live in device memory (the probe path's overflow list),
+// and the plan (slices, slice length) is derived from it on the device by coop_plan, by both kernels alike.
+// Register budget: 96 VGPRs (5 waves per SIMD: what the 32 KiB tile allows anyway, 5 blocks per CU), no scratch; the
+// compiler takes 74 (tests/test_nearest_coop_gpu.py checks the budget).
+constexpr int COOP_QG = 8;                    // queries per work item (the tile is read once for all of them)
+constexpr int COOP_TILE = 4096;               // entries per LDS tile: {rank, caller index}, 32 KiB
+constexpr uint32_t COOP_GRID = 1024;          // blocks of the fixed grid (4 per CU)
+constexpr uint32_t COOP_TARGET_ITEMS = 1024;  // work items the plan aims at when the queries alone give fewer
+constexpr uint32_t COOP_MIN_SLICE = 256;      // entries: a slice gives every lane of the block at least one
+constexpr uint64_t COOP_PARTIALS = 1ull << 21;   // partials the workspace holds at least (8 bytes each)
+
+struct CoopPlan { uint32_t nslices, slice_len; };
+
+__host__ __device__ inline CoopPlan coop_plan(uint32_t nq, uint32_t nw, uint64_t partial_cap)
+{
+    const uint64_t ngroups = ((uint64_t)nq + COOP_QG - 1) / COOP_QG;
+    uint64_t ns = ngroups ? (COOP_TARGET_ITEMS + ngroups - 1) / ngroups : 1;
+    const uint64_t ns_nw = ((uint64_t)nw + COOP_MIN_SLICE - 1) / COOP_MIN_SLICE;
+    const uint64_t ns_mem = ngroups ? partial_cap / (ngroups * COOP_QG * 4) : 1;
+    ns = ns < ns_nw ? ns : ns_nw;
+    ns = ns < ns_mem ? ns : ns_mem;
+    ns = ns ? ns : 1;
+    const uint64_t len = (((uint64_t)nw + ns - 1) / ns + 63) / 64 * 64;
+    CoopPlan p;
+    p.slice_len = (uint32_t)(len ? len : 64);
+    p.nslices = (uint32_t)(((uint64_t)nw + p.slice_len - 1) / p.slice_len);    // no empty slice
+    if (!p.nslices) p.nslices = 1;
+    return p;
+}
+
+// the partials of every query fit the workspace (the host sizes it so that they always do; this keeps a bad size from
+// turning into writes out of bounds)
+__host__ __device__ inline bool coop_plan_fits(const CoopPlan& p, uint32_t nq, uint64_t partial_cap)
+{
+    return (uint64_t)nq * p.nslices * 4u <= partial_cap;
+}
+
+__global__ __launch_bounds__(256)
+void k_nearest_coop(const uint32_t* __restrict__ q, uint32_t qstride,
+                    const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq,
+                    const uint32_t* __restrict__ wl_sorted, const uint32_t* __restrict__ wl_orig, uint32_t nw,
+                    unsigned long long* __restrict__ partials, uint64_t partial_cap)
+{
+    __shared__ uint2 s_ent[COOP_TILE];
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t ngroups = (nq + COOP_QG - 1) / COOP_QG;
+    const uint64_t nitems = (uint64_t)ngroups * plan.nslices;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    constexpr uint32_t EVEN = 0x55555555u;
+    for (uint64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint32_t g = (uint32_t)(item / plan.nslices), s = (uint32_t)(item % plan.nslices);
+        const uint32_t nqg = nq - g * COOP_QG < (uint32_t)COOP_QG ? nq - g * COOP_QG : (uint32_t)COOP_QG;
+        // the group's queries, uniform over the wave: scalar registers (a missing tail query repeats the first, unwritten)
+        uint32_t qv[COOP_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_QG; ++i) {
+            const uint32_t slot = g * COOP_QG + ((uint32_t)i < nqg ? (uint32_t)i : 0u);
+            const uint32_t qi = qlist ? qlist[slot] : slot;
+            qv[i] = __builtin_amdgcn_readfirstlane(q[(size_t)qi * qstride]);
+        }
+        uint32_t best[COOP_QG], bidx[COOP_QG], ties[COOP_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_QG; ++i) { best[i] = 255u; bidx[i] = NONE_IDX; ties[i] = 0u; }
+        const uint32_t s0 = s * plan.slice_len;
+        const uint32_t s1 = nw - s0 < plan.slice_len ? nw : s0 + plan.slice_len;
+        for (uint32_t t0 = s0; t0 < s1; t0 += COOP_TILE) {
+            const uint32_t tn = s1 - t0 < (uint32_t)COOP_TILE ? s1 - t0 : (uint32_t)COOP_TILE;
+            __syncthreads();
+            for (uint32_t k = threadIdx.x; k < tn; k += 256u) s_ent[k] = make_uint2(wl_sorted[t0 + k], wl_orig[t0 + k]);
+            __syncthreads();
+            for (uint32_t k = threadIdx.x; k < tn; k += 256u) {
+                const uint2 e = s_ent[k];
+                // the entry is the pattern (its rows spread at bits 2i), the query the text read column by column
+                const uint32_t P0 = e.x & EVEN, P1 = (e.x >> 1) & EVEN;
+#pragma unroll
+                for (int i = 0; i < COOP_QG; ++i) {
+                    const uint32_t t = qv[i];
+                    uint32_t pv = 0xFFFFFFFFu, mv = 0u, score = 16u;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t m0 = (uint32_t)((int32_t)(t << (31 - 2 * j)) >> 31), m1 = (uint32_t)((int32_t)(t << (30 - 2 * j)) >> 31);
+                        const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);             // ~(P0 ^ m0) & EVEN
+                        const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);               // t1 & ~(P1 ^ m1)
+                        const uint32_t xv = eq | mv;
+                        const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);    // (((eq & pv) + pv) ^ pv) | eq
+                        uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                     // mv | ~(xh | pv)
+                        uint32_t mh = pv & xh;
+                        score += (ph >> 30) & 1u;
+                        score -= (mh >> 30) & 1u;
+                        ph = (ph << 2) | 1u;
+                        mh = mh << 2;
+                        pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                              // mh | ~(xv | ph)
+                        mv = ph & xv;
+                    }
+                    const bool better = score < best[i], same = score == best[i];
+                    bidx[i] = better ? e.y : ((same && e.y < bidx[i]) ? e.y : bidx[i]);
+                    ties[i] = better ? 1u : (same ? ties[i] + 1u : ties[i]);
+                    best[i] = better ? score : best[i];
+                }
+            }
+        }
+        // per query: wave minimum of (ed << 32 | index) in six butterfly steps, then the tie count at that distance
+#pragma unroll
+        for (int i = 0; i < COOP_QG; ++i) {
+            unsigned long long key = ((unsigned long long)best[i] << 32) | bidx[i];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) {
+                const unsigned long long o = __shfl_xor(key, m);
+                key = o < key ? o : key;
+            }
+            const uint32_t ed = (uint32_t)(key >> 32);
+            uint32_t tc = best[i] == ed ? ties[i] : 0u;
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) tc += __shfl_xor(tc, m);
+            if (lane == 0 && (uint32_t)i < nqg) {
+                const uint64_t at = ((uint64_t)(g * COOP_QG + i) * plan.nslices + s) * 4u + (uint32_t)wv;
+                partials[at] = ((unsigned long long)ed << 48) | ((unsigned long long)(tc > 0xFFFFu ? 0xFFFFu : tc) << 32) | (uint32_t)key;
+            }
+        }
+    }
+}
+
+// one wave per query: the 4 * nslices partials (lane k: k, k + 64, ...), reduced like the scan's lanes -> the answer
+// (max_ed and unusable records: as k_nearest_scan)
+__global__ __launch_bounds__(256)
+void k_nearest_coop_merge(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
+                          const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq, uint32_t nw,
+                          const unsigned long long* __restrict__ partials, uint64_t partial_cap, uint32_t max_ed,
+                          uint32_t* __restrict__ best_idx, uint8_t* __restrict__ best_ed, uint16_t* __restrict__ n_ties)
+{
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t np = plan.nslices * 4u;
+    const int lane = threadIdx.x & 63;
+    for (uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6); slot < nq; slot += gridDim.x * 4u) {     // wave-uniform
+        const unsigned long long* p = partials + (uint64_t)slot * np;
+        uint32_t best = 255u, bidx = NONE_IDX, ties = 0u;
+        for (uint32_t k = (uint32_t)lane; k < np; k += 64u) {
+            const unsigned long long v = p[k];
+            const uint32_t ed = (uint32_t)(v >> 48), tc = (uint32_t)(v >> 32) & 0xFFFFu, ix = (uint32_t)v;
+            if (ed < best) { best = ed; bidx = ix; ties = tc; }
+            else if (ed == best) { bidx = ix < bidx ? ix : bidx; ties += tc; }
+        }
+        unsigned long long key = ((unsigned long long)best << 32) | bidx;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned long long o = __shfl_xor(key, m);
+            key = o < key ? o : key;
+        }
+        uint32_t tc = best == (uint32_t)(key >> 32) ? ties : 0u;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) tc += __shfl_xor(tc, m);
+        if (lane == 0) {
+            uint32_t ed = (uint32_t)(key >> 32), ix = (uint32_t)key;
+            const uint32_t qi = qlist ? qlist[slot] : slot;
+            const bool usable = !recs || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
+            if (ed > max_ed || !usable) { ed = 255u; ix = NONE_IDX; tc = 0u; }
+            best_idx[qi] = ix; best_ed[qi] = (uint8_t)ed; n_ties[qi] = (uint16_t)(tc > 0xFFFFu ? 0xFFFFu : tc);
+        }
+    }
 }
 
 // ---- probe path ----------------------------------------------------------------
@@ -561,21 +740,69 @@ static int build_delins_index(bdg_ctx* ctx)
 // --high_sens pass (a few hundred thousand unassigned barcodes against ~5,000 centres, barcode_graph.py:370-385) stays far
 // below it; a whitelist-sized list (737 K entries) crosses it with 5,500 queries.
 constexpr uint64_t SCAN_PAIR_EVALS_MAX = 4000000000ull;
+// Below this many queries the exhaustive answer comes from the wave-cooperative kernel instead of k_nearest_scan: the scan
+// runs one query per lane, so it needs 65,536 queries to give each of the 256 CUs one block of 256; the cooperative kernel
+// fills the chip from one query on.  Measured against the 737,280-entry list, max_ed 3 (tools/nearest_coop_probe.py,
+// profiles/r05_nearest_coop.jsonl): the scan takes 404-413 ms for every nq from 1 to 65,536 (7.4 G pair evaluations/s at
+// 4,096, 119 G at 65,536); the cooperative kernel 0.081 ms for 1 query, 21.6 ms for 4,096 and 347 ms for 65,536 (137-140 G/s
+// from 512 queries on).  It is ahead at every nq measured; beyond 65,536 the scan's blocks keep adding CUs, so the cut stays there.
+constexpr uint32_t COOP_NQ_MAX = 65536;
+
+// The cooperative kernel and its merge for a query list (qlist: indices into q, or NULL) whose length is nq_host or, if
+// d_nq is given, *d_nq <= nq_cap (known on the device only).
+static int launch_coop(bdg_ctx* ctx, hipStream_t st, const uint32_t* d_q, uint32_t qstride, int recs, const uint32_t* qlist,
+                       uint32_t nq_host, const uint32_t* d_nq, uint32_t nq_cap, uint32_t max_ed,
+                       uint32_t* d_best_idx, uint8_t* d_best_ed, uint16_t* d_n_ties)
+{
+    // room for at least one slice of every query of the largest list possible (coop_plan never plans more than there is)
+    const uint64_t groups = ((uint64_t)nq_cap + COOP_QG - 1) / COOP_QG;
+    const uint64_t cap = std::max<uint64_t>(COOP_PARTIALS, groups * COOP_QG * 4u);
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_coop, sizeof(unsigned long long) * cap))) return rc;
+    const uint64_t have = ctx->n_coop.bytes / sizeof(unsigned long long);
+    auto* part = static_cast<unsigned long long*>(ctx->n_coop.p);
+    const auto* srt = static_cast<const uint32_t*>(ctx->w_sorted.p);
+    const auto* org = static_cast<const uint32_t*>(ctx->w_orig.p);
+    uint32_t grid = COOP_GRID;
+    if (!d_nq) {                       // a known count: no more blocks than items
+        const CoopPlan p = coop_plan(nq_host, ctx->w_n, have);
+        const uint64_t items = (((uint64_t)nq_host + COOP_QG - 1) / COOP_QG) * p.nslices;
+        grid = (uint32_t)std::min<uint64_t>(items, COOP_GRID);
+    }
+    hipLaunchKernelGGL(k_nearest_coop, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
+                       part, have);
+    const uint32_t mgrid = d_nq ? 256u : std::min<uint32_t>((nq_host + 3) / 4, 2048u);
+    hipLaunchKernelGGL(k_nearest_coop_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
+                       part, have, max_ed, d_best_idx, d_best_ed, d_n_ties);
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int bdg_nearest16_check(bdg_ctx* ctx, uint32_t nq, uint32_t max_ed)
+{
+    if (nq == 0) return BDG_OK;
+    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    if (ctx->n16_algo == 2 && max_ed > 2) return bdg_fail(ctx, BDG_E_ARG, "probe path needs max_ed <= 2");
+    return BDG_OK;
+}
 
 int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, int recs, uint32_t nq, uint32_t max_ed,
                          uint32_t* d_best_idx, uint8_t* d_best_ed, uint16_t* d_n_ties)
 {
     if (nq == 0) return BDG_OK;
-    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    { const int rcc = bdg_nearest16_check(ctx, nq, max_ed); if (rcc) return rcc; }
     hipStream_t st = ctx->launch_stream ? ctx->launch_stream : ctx->stream;
     const auto* srt = static_cast<const uint32_t*>(ctx->w_sorted.p);
     const auto* org = static_cast<const uint32_t*>(ctx->w_orig.p);
     // automatic: the probe path when it applies (max_ed <= 2) and either its index exists already or the job is large enough to
-    // pay for building it
+    // pay for building it; otherwise exhaustive, by the cooperative kernel while nq is too small for one query per lane
     const bool built = ctx->w_probe_ready && (max_ed < 2 || ctx->w_delins_ready);
     const bool probe = ctx->n16_algo == 2 || (ctx->n16_algo == 0 && max_ed <= 2 && (built || (uint64_t)ctx->w_n * nq > SCAN_PAIR_EVALS_MAX));
-    if (ctx->n16_algo == 2 && max_ed > 2) return bdg_fail(ctx, BDG_E_ARG, "probe path needs max_ed <= 2");
     if (!probe) {
+        if (ctx->n16_algo == 3 || (ctx->n16_algo == 0 && nq < COOP_NQ_MAX)) {
+            ScopedKernelTimer tm(ctx, "k_nearest_coop");
+            return launch_coop(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, d_best_idx, d_best_ed, d_n_ties);
+        }
         ScopedKernelTimer tm(ctx, "k_nearest_scan");
         hipLaunchKernelGGL(k_nearest_scan, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, (const uint32_t*)nullptr, nq,
                            (const uint32_t*)nullptr, srt, org, ctx->w_n, max_ed, d_best_idx, d_best_ed, d_n_ties);
@@ -607,12 +834,12 @@ int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, in
                                static_cast<const uint4*>(ctx->w_dv.p), static_cast<const uint32_t*>(ctx->w_dv.p) + 4 * npairs,
                                d_best_idx, d_best_ed, d_n_ties, list3, counters);
         }
-        // queries whose hit list overflowed (one lane found more than 4 distinct entries): exhaustive
-        // scan of just those; the list length stays on the device, so no host round trip
+        // queries whose hit list overflowed (one lane found more than 4 distinct entries): the cooperative kernel on just
+        // those (few: a whole grid per query); the list length stays on the device, so no host round trip
         {
-            ScopedKernelTimer tm(ctx, "k_nearest_scan_overflow");
-            hipLaunchKernelGGL(k_nearest_scan, dim3(64), dim3(256), 0, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3,
-                               srt, org, ctx->w_n, max_ed, d_best_idx, d_best_ed, d_n_ties);
+            ScopedKernelTimer tm(ctx, "k_nearest_coop_overflow");
+            if ((rc = launch_coop(ctx, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3, nq, max_ed, d_best_idx, d_best_ed, d_n_ties)))
+                return rc;
         }
     }
     BDG_HIP_TRY(ctx, hipGetLastError());

@@ -42,12 +42,20 @@ inline char* put_int(char* o, int v)
     return o;
 }
 
-struct RowStats { uint64_t reads = 0, bc = 0, pt = 0, r1 = 0, first_pt = ~0ull, first_r1 = ~0ull; };
+struct RowStats { uint64_t reads = 0, bc = 0, pt = 0, r1 = 0, first_pt = ~0ull, first_r1 = ~0ull, wl = 0; };
+
+// A chunk's whitelist calls (bdg_format_rows_wl): per read the match's answer, and the whitelist in the caller's order.
+struct WlCalls {
+    const uint32_t* idx; const uint8_t* ed; const uint16_t* ties;
+    const uint32_t* wl; uint32_t nw;
+};
+constexpr uint64_t WL_COLS_MAX = 1 + 16 + 1 + 3 + 1 + 5;    // "\t" barcode "\t" dist "\t" ties
 
 // upper bound of the text of a chunk's rows (+ the headers that fall inside it)
-uint64_t rows_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, uint64_t g0, uint32_t header_every, size_t header_len)
+uint64_t rows_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, uint64_t g0, uint32_t header_every, size_t header_len,
+                    const WlCalls* wc = nullptr)
 {
-    uint64_t need = 0;
+    uint64_t need = wc ? WL_COLS_MAX * ch->n : 0;
     for (uint32_t i = 0; i < ch->n; ++i) {
         const uint64_t L = ch->off[i + 1] - ch->off[i];
         need += (ch->id_off[i + 1] - ch->id_off[i]) + 64 + (recs[i].valid ? 16 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start)) : 2);
@@ -60,7 +68,7 @@ uint64_t rows_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, uin
 // rows of a chunk whose first read is read g0 of the input; header_every > 0: the header line goes in front of every read
 // whose index is a multiple of it
 char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* o, uint64_t g0, uint32_t header_every,
-                 const char* header, size_t header_len, RowStats& st)
+                 const char* header, size_t header_len, RowStats& st, const WlCalls* wc = nullptr)
 {
     constexpr uint32_t AHEAD = 12;              // a row needs one or two lines of its read's bases, nowhere near the last row's: ask early
     for (uint32_t i = 0; i < ch->n; ++i) {
@@ -97,6 +105,23 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
         *o++ = '\t';
         o = put_int(o, r.polyT); *o++ = '\t';
         o = put_int(o, r.valid ? r.r1_end : -1);
+        if (wc) {
+            // no usable barcode, or nothing within max_ed: "*", -1, 0; one entry at the nearest distance: that entry;
+            // several: "*" with the distance and how many
+            const bool usable = r.valid && (r.flags & BDG_FLAG_RANK_OK) && wc->ed[i] != 255u && wc->idx[i] < wc->nw;
+            *o++ = '\t';
+            if (usable && wc->ties[i] == 1) {
+                const uint32_t rk = wc->wl[wc->idx[i]];
+                for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(rk >> (2 * b)) & 3u];
+                ++st.wl;
+            } else {
+                *o++ = '*';
+            }
+            *o++ = '\t';
+            o = put_int(o, usable ? (int)wc->ed[i] : -1);
+            *o++ = '\t';
+            o = put_int(o, usable ? (int)wc->ties[i] : 0);
+        }
         *o++ = '\n';
         if (r.polyT != -1) { ++st.pt; if (st.first_pt == ~0ull) st.first_pt = g0 + i; }
         if (r.valid && r.r1_end != -1) { ++st.r1; if (st.first_r1 == ~0ull) st.first_r1 = g0 + i; }
@@ -115,6 +140,7 @@ struct Job {
     bdg_ingest_chunk ch;
     bdg_ctx* ctx = nullptr; uint32_t slot = 0;
     std::vector<bdg_extract_rec> recs;
+    std::vector<uint32_t> m_idx; std::vector<uint8_t> m_ed; std::vector<uint16_t> m_ties;    // whitelist calls
     std::vector<char> text; size_t text_len = 0;
     RowStats st;
 };
@@ -124,6 +150,7 @@ struct Pipeline {
     int fd = -1;
     std::string header;
     uint32_t header_every = 0;
+    const uint32_t* wl = nullptr; uint32_t nw = 0;             // whitelist in the caller's order (opts->whitelist)
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Job*> to_format;
@@ -145,11 +172,14 @@ struct Pipeline {
                 j = to_format.front(); to_format.pop_front();
             }
             const double t0 = now_s();
-            j->text.resize((size_t)rows_bound(&j->ch, j->recs.data(), j->g0, header_every, header.size()));
-            char* e = write_rows(&j->ch, j->recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st);
+            const WlCalls wc{ j->m_idx.data(), j->m_ed.data(), j->m_ties.data(), wl, nw };
+            const WlCalls* pw = wl ? &wc : nullptr;
+            j->text.resize((size_t)rows_bound(&j->ch, j->recs.data(), j->g0, header_every, header.size(), pw));
+            char* e = write_rows(&j->ch, j->recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
             j->text_len = (size_t)(e - j->text.data());
             bdg_ingest_release(ing, j->ch.id);
             std::vector<bdg_extract_rec>().swap(j->recs);
+            std::vector<uint32_t>().swap(j->m_idx); std::vector<uint8_t>().swap(j->m_ed); std::vector<uint16_t>().swap(j->m_ties);
             const double dt = now_s() - t0;
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -185,6 +215,7 @@ struct Pipeline {
                 if (bad) write_failed = true;
                 total.reads += j->st.reads; total.bc += j->st.bc; total.pt += j->st.pt; total.r1 += j->st.r1;
                 total.first_pt = std::min(total.first_pt, j->st.first_pt); total.first_r1 = std::min(total.first_r1, j->st.first_r1);
+                total.wl += j->st.wl;
                 t_write += dt; out_bytes += j->text_len;
             }
             delete j;
@@ -217,6 +248,21 @@ int64_t bdg_format_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs,
     return (int64_t)(e - out);
 }
 
+int64_t bdg_format_rows_wl(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const uint32_t* best_idx,
+                           const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                           char* out, uint64_t cap, uint64_t counts[5])
+{
+    if (!ch || (ch->n && (!recs || !ch->bases || !ch->off || !ch->ids || !ch->id_off || !best_idx || !best_ed || !n_ties))) return BDG_E_ARG;
+    if (nw && !wl) return BDG_E_ARG;
+    const WlCalls wc{ best_idx, best_ed, n_ties, wl, nw };
+    const uint64_t need = rows_bound(ch, recs, 0, 0, 0, &wc);
+    if (!out || need > cap) return (int64_t)need;
+    RowStats st;
+    char* e = write_rows(ch, recs, out, 0, 0, nullptr, 0, st, &wc);
+    if (counts) { counts[0] = ch->n; counts[1] = st.bc; counts[2] = st.pt; counts[3] = st.r1; counts[4] = st.wl; }
+    return (int64_t)(e - out);
+}
+
 int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                    const bdg_stage1_opts* o, bdg_stage1_result* res)
 {
@@ -225,6 +271,19 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     memset(res, 0, sizeof(*res));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (o->umi_len == 0 || o->umi_len > 64) return bdg_fail(c0, BDG_E_ARG, "umi_len out of range");
+    // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
+    std::vector<uint32_t> wl_caller;
+    if (o->whitelist) {
+        if (o->max_bc_dist > 16) return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
+        for (uint32_t c = 0; c < n_ctx; ++c) {
+            if (!ctxs[c]) return BDG_E_ARG;
+            if (ctxs[c]->w_n == 0) return bdg_fail(c0, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load) on context " + std::to_string(c));
+            if (ctxs[c]->w_n != c0->w_n || ctxs[c]->w_fp != c0->w_fp)
+                return bdg_fail(c0, BDG_E_ARG, "the contexts hold different whitelists");
+        }
+        wl_caller.resize(c0->w_n);
+        for (uint32_t i = 0; i < c0->w_n; ++i) wl_caller[c0->w_host_order[i]] = c0->w_host_sorted[i];
+    }
     const double t_start = now_s();
     uint32_t fthreads = o->format_threads ? std::min(o->format_threads, 32u) : 4u;
     if (!o->format_threads) if (const char* e = getenv("BADGER_AMD_FORMAT_THREADS")) { const long v = atol(e); if (v > 0 && v <= 32) fthreads = (uint32_t)v; }
@@ -242,6 +301,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (P.fd < 0) { bdg_ingest_close(P.ing); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
     P.header = header; P.header_every = o->header_every;
+    if (o->whitelist) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); }
     bool ok_io = true;
     if (!o->header_every) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
     std::vector<std::thread> fmt;
@@ -255,6 +315,10 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         j->recs.resize(j->ch.n);
         const double t0 = now_s();
         int r = bdg_extract_collect(j->ctx, j->slot, j->recs.data());
+        if (r == BDG_OK && o->whitelist) {
+            j->m_idx.resize(j->ch.n); j->m_ed.resize(j->ch.n); j->m_ties.resize(j->ch.n);
+            r = bdg_slot_match_collect(j->ctx, j->slot, j->m_idx.data(), j->m_ed.data(), j->m_ties.data());
+        }
         t_gpu_wait += now_s() - t0;
         if (r) {
             err = bdg_last_error(j->ctx);
@@ -287,9 +351,11 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         j->seq = k; j->g0 = g0; j->ch = ch; j->ctx = ctxs[k % n_ctx]; j->slot = (uint32_t)((k / n_ctx) % per_ctx);
         const double t1 = now_s();
         rc = bdg_extract_submit(j->ctx, j->slot, ch.bases, ch.off, ch.n, o->umi_len);
+        if (rc) { t_submit += now_s() - t1; err = bdg_last_error(j->ctx); bdg_ingest_release(P.ing, ch.id); delete j; break; }
+        inflight.push_back(j);                                   // (submitted: collected below even if its match cannot be queued)
+        if (o->whitelist) rc = bdg_slot_match(j->ctx, j->slot, o->max_bc_dist);
         t_submit += now_s() - t1;
-        if (rc) { err = bdg_last_error(j->ctx); bdg_ingest_release(P.ing, ch.id); delete j; break; }
-        inflight.push_back(j);
+        if (rc) { err = bdg_last_error(j->ctx); break; }
         g0 += ch.n; ++k;
     }
     while (!inflight.empty()) {
@@ -297,6 +363,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         if (rc == BDG_OK) rc = collect(j);
         else { j->recs.resize(j->ch.n); (void)bdg_extract_collect(j->ctx, j->slot, j->recs.data()); bdg_ingest_release(P.ing, j->ch.id); delete j; }   // wait for the GPU before the pinned buffers go
     }
+    if (o->whitelist) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_synchronize(ctxs[c]);    // (a match still queued after a failure)
     { std::lock_guard<std::mutex> lk(P.mu); P.closing = true; }
     P.cv.notify_all();
     for (auto& t : fmt) t.join();
@@ -313,7 +380,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     }
     res->reads = P.total.reads; res->barcodes = P.total.bc; res->polyt = P.total.pt; res->r1 = P.total.r1;
     res->first_polyt = P.total.first_pt; res->first_r1 = P.total.first_r1; res->bad_read = bad_read;
-    res->chunks = k; res->out_bytes = P.out_bytes;
+    res->chunks = k; res->out_bytes = P.out_bytes; res->whitelist_barcodes = P.total.wl;
     res->seconds_total = now_s() - t_start; res->seconds_wait_parse = t_parse_wait; res->seconds_wait_gpu = t_gpu_wait;
     res->seconds_wait_format = t_fmt_wait; res->seconds_submit = t_submit; res->seconds_format = P.t_format; res->seconds_write = P.t_write;
     if (rc) return bdg_fail(c0, rc, err);

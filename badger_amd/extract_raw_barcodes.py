@@ -17,6 +17,11 @@ What differs from the reference, by design:
     of reader threads (1: one sequential reader).  No pysam, no Bio.
   * new optional flag: --gpus N.  Chunk k goes to device k mod N; submission is asynchronous, so
     the N devices work at the same time; rows are written in input order.
+  * --barcodes / -b FILE (documented by Badger, never wired up by the reference, whose load_barcodes :343-347 nothing
+    calls): every read's barcode is matched against the whitelist on the GPU (nearest entry under Levenshtein distance,
+    at most --max_bc_dist, default 2 - the bound of the reference's own whitelist match, barcode_graph.py:383) and three
+    columns follow R1_end: whitelist_barcode, whitelist_dist, whitelist_ties (include/badger_hip.h, bdg_format_rows_wl),
+    plus a "Whitelist barcode" line in the .stats.  Without -b the files are what they were.
 """
 import argparse
 import gzip
@@ -34,7 +39,33 @@ from .barcode_extraction.barcode_callers import (ReadStats, TenXBarcodeExtractor
 logger = logging.getLogger("BarcodeGraph")
 
 READ_CHUNK_SIZE = 100000
+WHITELIST_COLUMNS = ("whitelist_barcode", "whitelist_dist", "whitelist_ties")
+MAX_BC_DIST_DEFAULT = 2
 BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
+
+
+# ----------------------------------------------------------------------------- whitelist
+def load_barcodes(path):
+    """The whitelist of --barcodes as ranks (numpy uint32), in file order: the first whitespace-separated token of every
+    non-empty line (the reference's load_barcodes, :343-347), plain or gzipped.  Every token must be 16 letters of ACGT
+    (ValueError naming the line otherwise); a repeated entry is dropped, the first one stays, so an entry's index is its
+    position among the distinct entries."""
+    import numpy as np
+    opener = gzip.open if path.endswith((".gz", ".gzip")) else open
+    seen, order = set(), []
+    with opener(path, "rt") as f:
+        for lineno, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            bc = tok[0]
+            if len(bc) != 16 or bc.strip("ACGT"):
+                raise ValueError("%s, line %d: %r is not a barcode of 16 letters from ACGT" % (path, lineno, bc[:40]))
+            if bc not in seen:
+                seen.add(bc)
+                order.append(bc)
+    from .common import rank_many
+    return rank_many(order, 16).astype(np.uint32)
 
 
 # ----------------------------------------------------------------------------- readers
@@ -303,26 +334,40 @@ def _detectors(mode, gpus):
     return [BARCODE_CALLING_MODES[mode](device=g) for g in range(gpus)]
 
 
-def _stats_lines(res):
+def _stats_lines(res, whitelist=False):
     """ReadStats.__str__ (barcode_callers.py:138-143) from the native run's counters: the attribute lines come in the order
-    in which the first read showing each was met (a dict's insertion order in the reference)."""
+    in which the first read showing each was met (a dict's insertion order in the reference).  With a whitelist, one more
+    line after them: the rows whose whitelist_barcode is not '*'."""
     lines = [("Total reads", res.reads), ("Barcode detected", res.barcodes), ("Reliable UMI", 0)]
     attrs = []
     if res.polyt:
         attrs.append((res.first_polyt, 0, "PolyT detected", res.polyt))
     if res.r1:
         attrs.append((res.first_r1, 1, "R1 detected", res.r1))       # one read adds "PolyT detected" before "R1 detected"
-    return lines + [(name, v) for _, _, name, v in sorted(attrs)]
+    lines += [(name, v) for _, _, name, v in sorted(attrs)]
+    if whitelist:
+        lines.append(("Whitelist barcode", res.whitelist_barcodes))
+    return lines
 
 
 def _run_native(args, header_every, threads, skip_secondary):
     if not is_native_input(args.input):
         logger.error("Unknown file format " + args.input)
         sys.exit(-1)
+    wl = None
+    if getattr(args, "barcodes", None):
+        wl = load_barcodes(args.barcodes)
+        logger.info("Loaded %d whitelist barcodes from %s" % (len(wl), args.barcodes))
     detectors = _detectors(args.mode, getattr(args, "gpus", 1))
     logger.info("Barcode caller created")
-    res = _native.stage1_run([d._ctx() for d in detectors], args.input, args.output, detectors[0].result_type().header(),
-                             detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary)
+    header = detectors[0].result_type().header()
+    if wl is not None:
+        for d in detectors:
+            d._ctx().whitelist_load(wl)
+        header += "\t" + "\t".join(WHITELIST_COLUMNS)
+    res = _native.stage1_run([d._ctx() for d in detectors], args.input, args.output, header,
+                             detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
+                             whitelist=wl is not None, max_bc_dist=_max_bc_dist(args))
     timing = os.environ.get("BADGER_AMD_STAGE1_TIMING")
     if timing:                                   # where the run's time went (tools/cli_throughput.py reads it)
         import json
@@ -336,7 +381,7 @@ def process_single_thread(args):
     logger.info("Processing " + args.input)
     res = _run_native(args, 0, 1, False)
     with open(args.output + ".stats", "w") as f:
-        for k, v in _stats_lines(res):
+        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None))):
             f.write("%s:\t%d\n" % (k, v))
             logger.info("%s:\t%d" % (k, v))
     logger.info("Finished barcode calling")
@@ -349,7 +394,7 @@ def process_in_parallel(args):
     logger.info("Processing " + args.input)
     res = _run_native(args, READ_CHUNK_SIZE, args.threads, True)
     with open(args.output + ".stats", "w") as out_stats:
-        for k, v in _stats_lines(res):
+        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None))):
             logger.info("%s: %d" % (k, v))
             out_stats.write("%s: %d\n" % (k, v))
     logger.info("Finished barcode calling")
@@ -428,7 +473,36 @@ def parse_args(sys_argv):
     p.add_argument("--threads", "-t", type=int, help="threads to use (16)", default=16)
     p.add_argument("--tmp_dir", type=str, help="folder for temporary files (unused: no temporary files are written)")
     p.add_argument("--gpus", type=int, default=1, help="number of MI355X devices of this node to shard chunks over")
-    return p.parse_args(sys_argv)
+    p.add_argument("--barcodes", "-b", type=_whitelist_file, metavar="FILE",
+                   help="barcode whitelist for the used protocol (plain or gzipped; one barcode per line)")
+    p.add_argument("--max_bc_dist", type=_bc_dist, default=None, metavar="D",
+                   help="largest edit distance of a whitelist call, 0 .. 16 (default %d); needs --barcodes" % MAX_BC_DIST_DEFAULT)
+    args = p.parse_args(sys_argv)
+    if args.max_bc_dist is not None and not args.barcodes:
+        p.error("--max_bc_dist needs --barcodes")
+    return args
+
+
+def _whitelist_file(path):
+    """--barcodes: a file that can be read, checked while the arguments are parsed (a usage error, before any device is opened)"""
+    if not os.path.isfile(path) or not os.access(path, os.R_OK):
+        raise argparse.ArgumentTypeError("cannot read whitelist %r" % path)
+    return path
+
+
+def _bc_dist(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 0 <= v <= 16:
+        raise argparse.ArgumentTypeError("%d is outside 0 .. 16" % v)
+    return v
+
+
+def _max_bc_dist(args):
+    v = getattr(args, "max_bc_dist", None)
+    return MAX_BC_DIST_DEFAULT if v is None else v
 
 
 def main(sys_argv):

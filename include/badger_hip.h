@@ -250,10 +250,20 @@ void bdg_ingest_close(bdg_ingest* g);
  * written then; call with out = NULL to size), or < 0.  counts (may be NULL): reads, barcodes detected, polyT
  * detected, R1 detected (ReadStats, barcode_callers.py:122-143). */
 int64_t bdg_format_rows(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, char* out, uint64_t cap, uint64_t counts[4]);
+/* The same rows with three more columns behind R1_end, the read's whitelist call (bdg_nearest16_recs_dev's answer for its
+ * record: best_idx / best_ed / n_ties, and the whitelist as the caller's ranks, wl[best_idx]):
+ *   whitelist_barcode  the entry, spelled out, when exactly one entry lies at the nearest distance; '*' otherwise
+ *   whitelist_dist     that distance; -1 when nothing lies within max_ed or the record has no usable barcode (no BDG_FLAG_RANK_OK)
+ *   whitelist_ties     the number of entries at that distance (saturating at 65535); 0 where whitelist_dist is -1
+ * counts[4] (counts may be NULL) = the rows whose whitelist_barcode is not '*'. */
+int64_t bdg_format_rows_wl(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const uint32_t* best_idx,
+                           const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                           char* out, uint64_t cap, uint64_t counts[5]);
 
 /* Stage 1 from file to file in native threads: readers -> GPU(s) -> row formatters -> one writer, rows in input order
  * (extract_raw_barcodes.py:162-173 process_single_thread, :176-261 process_in_parallel).  Chunk k goes to context k mod
- * n_ctx, two chunks in flight per context.  header: the column line without its newline.  Returns BDG_E_BADBASE (reference:
+ * n_ctx, two chunks in flight per context.  With opts->whitelist, each chunk's whitelist match is queued behind its
+ * extraction on the context's auxiliary stream (the one of bdg_set_overlap), where it runs beside the next chunk's.  header: the column line without its newline.  Returns BDG_E_BADBASE (reference:
  * KeyError), BDG_E_FORMAT (ValueError), BDG_E_NOSEQ (TypeError) with the rows of the chunks in front of the failure
  * written, like the reference's loop; the message is bdg_last_error(ctxs[0]). */
 typedef struct bdg_stage1_opts {
@@ -266,6 +276,9 @@ typedef struct bdg_stage1_opts {
     uint32_t chunk_reads;         /* reads per GPU batch at most (0 = 100000) */
     int32_t  skip_secondary;      /* bdg_ingest_opts.skip_secondary */
     uint64_t segment_bytes;       /* bdg_ingest_opts.segment_bytes */
+    uint32_t whitelist;           /* 1: match every read's barcode against the whitelist each context holds (bdg_whitelist_load, the same
+                                     list on all of them) and write the three columns of bdg_format_rows_wl; 0: the rows of bdg_format_rows */
+    uint32_t max_bc_dist;         /* whitelist: the max_ed of the match */
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -278,6 +291,7 @@ typedef struct bdg_stage1_result {
     double   seconds_wait_gpu;                /* ... waiting for a chunk's records */
     double   seconds_wait_format;             /* ... waiting for the formatters / the writer to take a chunk */
     double   seconds_format, seconds_write;   /* busy time of the formatter threads (summed) / of the writer */
+    uint64_t whitelist_barcodes;              /* opts->whitelist: rows with a whitelist_barcode (counts[4] of bdg_format_rows_wl) */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
@@ -301,7 +315,12 @@ int  bdg_nearest16_dev(bdg_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t 
 int  bdg_nearest16_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t n, uint32_t max_ed,
                             uint32_t* d_best_idx, uint8_t* d_best_ed, uint16_t* d_n_ties);
 /* algorithm: 0 = automatic, 1 = force the exhaustive Myers scan, 2 = force the
- * neighbourhood-probe path (max_ed <= 2 only). Results are identical. */
+ * neighbourhood-probe path (max_ed <= 2 only), 3 = force the wave-cooperative exhaustive
+ * kernel (any max_ed: one query per wave, the whitelist cut into slices over the chip; what
+ * automatic mode runs instead of the scan below a few thousand queries, and what the probe
+ * path's rare overflowing queries go to).  Results are identical.  bdg_nearest16_recs_dev
+ * rejects a call the algorithm cannot serve (algo 2 with max_ed > 2) or one without a
+ * whitelist at once, in overlap mode too. */
 int  bdg_nearest16_set_algo(bdg_ctx* ctx, int algo);
 /* Device memory held by the neighbourhood-probe index of the loaded whitelist, in bytes: 0 until a call takes the probe path
  * (automatic mode takes the exhaustive scan while nw * nq stays small, e.g. stage 2's --high_sens pass against ~5,000 centres:
