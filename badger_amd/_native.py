@@ -35,6 +35,8 @@ EXPORTS = [
     "bdg_extract_batch", "bdg_extract_batch_dev", "bdg_extract_status", "bdg_extract_counters", "bdg_extract_set_queue_capacity",
     "bdg_extract_set_strand_rule",
     "bdg_nearest16", "bdg_whitelist_load", "bdg_nearest16_dev", "bdg_nearest16_recs_dev", "bdg_nearest16_set_algo", "bdg_nearest16_index_bytes",
+    "bdg_nearest16_overflow_count",
+    "bdg_nearest16_topk", "bdg_nearest16_topk_dev", "bdg_nearest16_topk_recs_dev", "bdg_format_rows_wlk",
     "bdg_graph_edges", "bdg_graph_edges_dev", "bdg_graph_edges_rows_dev", "bdg_graph_edges_part_dev", "bdg_graph_set_algo", "bdg_graph_status", "bdg_distinct_dev", "bdg_rows_of_dev",
     "bdg_extract_submit", "bdg_extract_collect", "bdg_extract_keep_records", "bdg_kept_records", "bdg_kept_records_to_host", "bdg_keep_observed", "bdg_touched_count_dev",
     "bdg_ingest_open", "bdg_ingest_open_mt", "bdg_ingest_open_ex", "bdg_ingest_next", "bdg_ingest_release", "bdg_ingest_error",
@@ -60,11 +62,14 @@ class IngestOpts(C.Structure):
                 ("segment_bytes", C.c_uint64), ("skip_secondary", C.c_int32), ("reserved", C.c_uint32)]
 
 
+STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates is set (BDG_STAGE1_WL_CANDIDATES)
+
+
 class Stage1Opts(C.Structure):
     """bdg_stage1_opts"""
     _fields_ = [("umi_len", C.c_uint32), ("threads", C.c_uint32), ("format_threads", C.c_uint32), ("header_every", C.c_uint32),
                 ("chunk_reads", C.c_uint32), ("skip_secondary", C.c_int32), ("segment_bytes", C.c_uint64),
-                ("whitelist", C.c_uint32), ("max_bc_dist", C.c_uint32)]
+                ("whitelist", C.c_uint32), ("max_bc_dist", C.c_uint16), ("bc_candidates", C.c_uint16)]
 
 
 class Stage1Result(C.Structure):
@@ -136,6 +141,13 @@ def load():
     L.bdg_nearest16_set_algo.argtypes = [vp, C.c_int]
     L.bdg_nearest16_index_bytes.argtypes = [vp]
     L.bdg_nearest16_index_bytes.restype = C.c_uint64
+    L.bdg_nearest16_overflow_count.argtypes = [vp]
+    L.bdg_nearest16_overflow_count.restype = C.c_uint32
+    L.bdg_nearest16_topk.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp]
+    L.bdg_nearest16_topk_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+    L.bdg_nearest16_topk_recs_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+    L.bdg_format_rows_wlk.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, C.POINTER(u64)]
+    L.bdg_format_rows_wlk.restype = C.c_int64
     L.bdg_graph_edges.argtypes = [vp, vp, u32, u32, i32, vp, u64, C.POINTER(u64)]
     L.bdg_graph_edges_dev.argtypes = [vp, vp, u32, u32, i32, vp, u64, vp]
     L.bdg_graph_edges_rows_dev.argtypes = [vp, vp, u32, u32, u32, u32, i32, vp, u64, vp]
@@ -340,6 +352,32 @@ class Context:
         self._check(self.lib.bdg_nearest16_recs_dev(self.h, d_recs.data_ptr(), n, max_ed, d_idx.data_ptr(),
                                                     d_ed.data_ptr(), d_ties.data_ptr()))
 
+    def nearest16_topk(self, q, wl, max_ed, k):
+        """the k nearest entries within max_ed, ordered by (distance, caller index) (bdg_nearest16_topk): idx [nq, k],
+        ed [nq, k] (empty slots 0xFFFFFFFF / 255) and n_within [nq], as numpy arrays"""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        wl = np.ascontiguousarray(wl, dtype=np.uint32)
+        k = int(k)
+        idx = np.zeros((len(q), max(k, 0)), np.uint32)
+        ed = np.zeros((len(q), max(k, 0)), np.uint8)
+        n_within = np.zeros(len(q), np.uint16)
+        self._check(self.lib.bdg_nearest16_topk(self.h, q.ctypes.data, len(q), wl.ctypes.data, len(wl), max_ed, k,
+                                                idx.ctypes.data, ed.ctypes.data, n_within.ctypes.data))
+        return idx, ed, n_within
+
+    def nearest16_topk_dev(self, d_q, nq, max_ed, k, d_idx, d_ed, d_n_within):
+        """device form (torch tensors or DeviceArrays): d_idx / d_ed hold nq * k entries, d_n_within nq"""
+        self._check(self.lib.bdg_nearest16_topk_dev(self.h, _ptr(d_q), nq, max_ed, k, _ptr(d_idx), _ptr(d_ed), _ptr(d_n_within)))
+
+    def nearest16_topk_recs_dev(self, d_recs, n, max_ed, k, d_idx, d_ed, d_n_within):
+        """nearest16_topk of every record's barcode (records without a 16-base ACGT barcode: empty slots, n_within 0)"""
+        self._check(self.lib.bdg_nearest16_topk_recs_dev(self.h, _ptr(d_recs), n, max_ed, k, _ptr(d_idx), _ptr(d_ed),
+                                                         _ptr(d_n_within)))
+
+    def nearest16_overflow_count(self):
+        """queries the last probe-path call sent on to the cooperative kernel (waits for the context's streams)"""
+        return int(self.lib.bdg_nearest16_overflow_count(self.h))
+
     def nearest16_set_algo(self, algo):
         self._check(self.lib.bdg_nearest16_set_algo(self.h, algo))
 
@@ -517,15 +555,16 @@ def chunk_reads(ch):
 
 
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
-               chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2):
+               chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
-    whitelist columns (header must name them)."""
+    whitelist columns (header must name them); bc_candidates=K (1 .. 8) one more, whitelist_candidates."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
+    wl_mode = (1 | (STAGE1_WL_CANDIDATES if bc_candidates else 0)) if whitelist else 0
     o = Stage1Opts(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
-                   1 if whitelist else 0, max_bc_dist)
+                   wl_mode, max_bc_dist, bc_candidates)
     res = Stage1Result()
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"), C.byref(o), C.byref(res))
     if rc != 0:
@@ -674,6 +713,35 @@ def format_rows_wl(ch, recs, best_idx, best_ed, n_ties, wl):
     got = L.bdg_format_rows_wl(C.byref(ch), *args, buf, int(need), counts)
     if got < 0 or got > need:
         raise BadgerHipError(int(got), "bdg_format_rows_wl")
+    return buf.raw[:got], tuple(int(x) for x in counts)
+
+
+def format_rows_wlk(ch, recs, best_idx, best_ed, n_ties, cand_idx, cand_ed, wl):
+    """format_rows_wl with the whitelist_candidates column (bdg_format_rows_wlk): cand_idx / cand_ed [n, k] are the slots of
+    the top-k match per record.  Counts as format_rows_wl"""
+    L = load()
+    recs = np.ascontiguousarray(recs)
+    idx = np.ascontiguousarray(best_idx, dtype=np.uint32)
+    ed = np.ascontiguousarray(best_ed, dtype=np.uint8)
+    ties = np.ascontiguousarray(n_ties, dtype=np.uint16)
+    cidx = np.ascontiguousarray(cand_idx, dtype=np.uint32)
+    ced = np.ascontiguousarray(cand_ed, dtype=np.uint8)
+    wl = np.ascontiguousarray(wl, dtype=np.uint32)
+    if cidx.ndim != 2 or cidx.shape != ced.shape:
+        raise ValueError("format_rows_wlk: candidate arrays must both be [n, k], got %s / %s" % (cidx.shape, ced.shape))
+    if not (len(recs) == len(idx) == len(ed) == len(ties) == len(cidx) == ch.n):
+        raise ValueError("format_rows_wlk: %d reads, %d records, %d / %d / %d / %d calls"
+                         % (ch.n, len(recs), len(idx), len(ed), len(ties), len(cidx)))
+    counts = (C.c_uint64 * 5)()
+    args = (recs.ctypes.data, idx.ctypes.data, ed.ctypes.data, ties.ctypes.data, wl.ctypes.data, len(wl),
+            cidx.shape[1], cidx.ctypes.data, ced.ctypes.data)
+    need = L.bdg_format_rows_wlk(C.byref(ch), *args, None, 0, counts)
+    if need < 0:
+        raise BadgerHipError(int(need), "bdg_format_rows_wlk")
+    buf = C.create_string_buffer(int(need) + 1)
+    got = L.bdg_format_rows_wlk(C.byref(ch), *args, buf, int(need), counts)
+    if got < 0 or got > need:
+        raise BadgerHipError(int(got), "bdg_format_rows_wlk")
     return buf.raw[:got], tuple(int(x) for x in counts)
 
 

@@ -20,6 +20,9 @@ size_t bdg_extract_counter_bytes();
 int bdg_whitelist_load_impl(bdg_ctx*, const uint32_t*, uint32_t);
 int bdg_nearest16_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*);
 int bdg_nearest16_check(bdg_ctx*, uint32_t, uint32_t);
+int bdg_nearest16_topk_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*, uint16_t*);
+int bdg_nearest16_topk_check(bdg_ctx*, uint32_t, uint32_t, uint32_t);
+int bdg_nearest16_overflow_read(bdg_ctx*, uint32_t*);
 int bdg_graph_launch(bdg_ctx*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, int32_t, bdg_edge*, uint64_t, uint64_t*, uint32_t part = 0, uint32_t nparts = 1);
 int bdg_graph_plan(const bdg_ctx*, uint32_t, uint32_t);
 int bdg_graph_join_flags(bdg_ctx*, uint32_t*);
@@ -114,6 +117,18 @@ static int sync_all(bdg_ctx* ctx)
     if (rcd) return rcd;
     BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux_pending) { BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream)); ctx->aux_pending = false; }
+    return BDG_OK;
+}
+
+// The context's stream waits for everything queued on the auxiliary stream so far (a match queued there - deferred, or a
+// stage-1 slot match - uses the same match workspaces as one launched on the main stream: the two must not overlap).
+static int main_after_aux(bdg_ctx* ctx)
+{
+    if (!ctx->aux_stream || !ctx->aux_pending) return BDG_OK;
+    hipEvent_t e = ctx->ev_aux[ctx->aux_count & 1];
+    BDG_HIP_TRY(ctx, hipEventRecord(e, ctx->aux_stream));
+    ctx->aux_count++;
+    BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, e, 0));
     return BDG_OK;
 }
 
@@ -558,43 +573,58 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
     return BDG_OK;
 }
 
-static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed)
+static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed, uint32_t k)
 {
     int rc;
     if ((rc = ensure_aux(ctx))) return rc;
     const size_t n = sl.n;
-    if ((rc = bdg_reserve(ctx, sl.d_match, 7 * n + 64))) return rc;
-    if ((rc = pinned_reserve(ctx, sl.h_match, sl.h_match_bytes, 7 * n + 64))) return rc;
+    const size_t bytes = k ? (4 * k + 4 + k) * n : 7 * n;
+    if ((rc = bdg_reserve(ctx, sl.d_match, bytes + 64))) return rc;
+    if ((rc = pinned_reserve(ctx, sl.h_match, sl.h_match_bytes, bytes + 64))) return rc;
     if (!sl.match_done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.match_done, hipEventDisableTiming));
-    auto* d_idx = static_cast<uint32_t*>(sl.d_match.p);
-    auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n);
-    auto* d_ed = reinterpret_cast<uint8_t*>(d_ties + n);
     BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, sl.done, 0));      // behind the chunk's extraction
     ctx->launch_stream = ctx->aux_stream;
     ctx->aux_pending = true;
-    rc = bdg_nearest16_launch(ctx, reinterpret_cast<const uint32_t*>(sl.d_recs.p) + 5, 8u, 1, sl.n, max_ed, d_idx, d_ed, d_ties);
+    const auto* d_q = reinterpret_cast<const uint32_t*>(sl.d_recs.p) + 5;
+    auto* d_idx = static_cast<uint32_t*>(sl.d_match.p);
+    if (k) {
+        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n * k);
+        auto* d_nwithin = d_ties + n;
+        auto* d_ed = reinterpret_cast<uint8_t*>(d_nwithin + n);
+        rc = bdg_nearest16_topk_launch(ctx, d_q, 8u, 1, sl.n, max_ed, k, d_idx, d_ed, d_nwithin, d_ties);
+    } else {
+        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n);
+        auto* d_ed = reinterpret_cast<uint8_t*>(d_ties + n);
+        rc = bdg_nearest16_launch(ctx, d_q, 8u, 1, sl.n, max_ed, d_idx, d_ed, d_ties);
+    }
     ctx->launch_stream = nullptr;
     if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_match, sl.d_match.p, 7 * n, hipMemcpyDeviceToHost, ctx->aux_stream));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_match, sl.d_match.p, bytes, hipMemcpyDeviceToHost, ctx->aux_stream));
     BDG_HIP_TRY(ctx, hipEventRecord(sl.match_done, ctx->aux_stream));
     sl.match_max_ed = max_ed;
+    sl.match_k = k;
     sl.match_queued = true;
     return BDG_OK;
 }
 
-int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed)
+int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k)
 {
     if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
     bdg_ctx::Slot& sl = ctx->slots[slot];
     if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
-    if (sl.n == 0) return BDG_OK;
-    int rc = bdg_nearest16_check(ctx, sl.n, max_ed);
-    if (rc) return rc;
+    int rc = k ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, k) : bdg_nearest16_check(ctx, sl.n, max_ed);
+    if (rc || sl.n == 0) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return queue_slot_match(ctx, sl, max_ed);
+    return queue_slot_match(ctx, sl, max_ed, k);
 }
 
-int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties)
+int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed)
+{
+    return bdg_slot_match_topk(ctx, slot, max_ed, 0);
+}
+
+int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
+                                uint32_t* cand_idx, uint8_t* cand_ed)
 {
     if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
     bdg_ctx::Slot& sl = ctx->slots[slot];
@@ -602,16 +632,29 @@ int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint
     if (!sl.match_queued) return bdg_fail(ctx, BDG_E_ARG, "no match queued for this slot");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
-    if (sl.reran && (rc = queue_slot_match(ctx, sl, sl.match_max_ed))) return rc;     // the records changed: match them again
+    if (sl.reran && (rc = queue_slot_match(ctx, sl, sl.match_max_ed, sl.match_k))) return rc;     // the records changed: match them again
     sl.reran = false;
     BDG_HIP_TRY(ctx, hipEventSynchronize(sl.match_done));
     sl.match_queued = false;
-    const size_t n = sl.n;
+    const size_t n = sl.n, k = sl.match_k;
     const auto* h_idx = static_cast<const uint32_t*>(sl.h_match);
-    const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n);
-    const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + n);
-    memcpy(best_idx, h_idx, 4 * n); memcpy(n_ties, h_ties, 2 * n); memcpy(best_ed, h_ed, n);
+    if (k) {
+        if (!cand_idx || !cand_ed) return bdg_fail(ctx, BDG_E_ARG, "a top-k match needs the candidate arrays");
+        const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n * k);
+        const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + 2 * n);
+        memcpy(cand_idx, h_idx, 4 * n * k); memcpy(cand_ed, h_ed, n * k); memcpy(n_ties, h_ties, 2 * n);
+        for (size_t i = 0; i < n; ++i) { best_idx[i] = h_idx[i * k]; best_ed[i] = h_ed[i * k]; }
+    } else {
+        const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n);
+        const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + n);
+        memcpy(best_idx, h_idx, 4 * n); memcpy(n_ties, h_ties, 2 * n); memcpy(best_ed, h_ed, n);
+    }
     return BDG_OK;
+}
+
+int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties)
+{
+    return bdg_slot_match_collect_topk(ctx, slot, best_idx, best_ed, n_ties, nullptr, nullptr);
 }
 
 int bdg_extract_keep_records(bdg_ctx* ctx, int on)
@@ -751,6 +794,75 @@ int bdg_nearest16(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* 
     BDG_HIP_TRY(ctx, hipMemcpyAsync(best_idx, d_idx, bq, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipMemcpyAsync(n_ties, d_ties, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipMemcpyAsync(best_ed, d_ed, (size_t)nq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
+
+uint32_t bdg_nearest16_overflow_count(bdg_ctx* ctx)
+{
+    if (!ctx || hipSetDevice(ctx->device) != hipSuccess || sync_all(ctx) != BDG_OK) return 0;
+    uint32_t n = 0;
+    return bdg_nearest16_overflow_read(ctx, &n) == BDG_OK ? n : 0;
+}
+
+int bdg_nearest16_topk_dev(bdg_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t max_ed, uint32_t k,
+                           uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (nq && (!d_q || !d_idx || !d_ed || !d_n_within)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = bdg_nearest16_topk_check(ctx, nq, max_ed, k);
+    if (rc || nq == 0) return rc;
+    if ((rc = main_after_aux(ctx))) return rc;
+    return bdg_nearest16_topk_launch(ctx, d_q, 1u, 0, nq, max_ed, k, d_idx, d_ed, d_n_within, nullptr);
+}
+
+int bdg_nearest16_topk_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t n, uint32_t max_ed, uint32_t k,
+                                uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && (!d_recs || !d_idx || !d_ed || !d_n_within)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = bdg_nearest16_topk_check(ctx, n, max_ed, k);
+    if (rc) return rc;
+    if (n == 0) return BDG_OK;
+    // overlap mode: a best-hit match still waiting is queued first (on the auxiliary stream); the top-k match is not deferred
+    // but goes on the context's stream, behind the extraction that wrote the records AND behind every match queued on the
+    // auxiliary stream, whose workspaces (counters, query lists, partials) it reuses
+    if (ctx->overlap && (rc = bdg_launch_deferred_match(ctx, false))) return rc;
+    if ((rc = main_after_aux(ctx))) return rc;
+    return bdg_nearest16_topk_launch(ctx, reinterpret_cast<const uint32_t*>(d_recs) + 5, 8u, 1, n, max_ed, k, d_idx, d_ed, d_n_within, nullptr);
+}
+
+int bdg_nearest16_topk(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw,
+                       uint32_t max_ed, uint32_t k, uint32_t* idx, uint8_t* ed, uint16_t* n_within)
+{
+    if (!ctx) return BDG_E_ARG;
+    int rc = bdg_nearest16_topk_check(ctx, 0, max_ed, k);
+    if (rc) return rc;
+    if (nq == 0) return BDG_OK;
+    if (!q || !idx || !ed || !n_within || (nw && !wl)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (nw == 0) {
+        for (size_t i = 0; i < (size_t)nq * k; ++i) { idx[i] = 0xFFFFFFFFu; ed[i] = 0xFF; }
+        for (uint32_t i = 0; i < nq; ++i) n_within[i] = 0;
+        return BDG_OK;
+    }
+    if ((rc = bdg_whitelist_load_impl(ctx, wl, nw))) return rc;
+    if ((rc = main_after_aux(ctx))) return rc;
+    const size_t bq = sizeof(uint32_t) * (size_t)nq, nk = (size_t)nq * k;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, bq))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, 5 * nk + 2 * (size_t)nq + 64))) return rc;     // idx u32 [nq k] | n_within u16 | ed u8 [nq k]
+    hipStream_t st = ctx->stream;
+    auto* d_idx = static_cast<uint32_t*>(ctx->s_out0.p);
+    auto* d_nw = reinterpret_cast<uint16_t*>(d_idx + nk);
+    auto* d_ed = reinterpret_cast<uint8_t*>(d_nw + nq);
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, bq, hipMemcpyHostToDevice, st));
+    rc = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, k, d_idx, d_ed, d_nw, nullptr);
+    if (rc) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, 4 * nk, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_within, d_nw, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ed, d_ed, nk, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return BDG_OK;
 }

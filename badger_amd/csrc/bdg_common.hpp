@@ -74,10 +74,11 @@ struct bdg_ctx {
         bool busy = false;
         bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
         // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
-        DevBuf d_match;                                      // best_idx u32 [n] | n_ties u16 [n] | best_ed u8 [n]
+        DevBuf d_match;                                      // best_idx u32 [n] | n_ties u16 [n] | best_ed u8 [n]; top-k (match_k > 0):
+                                                             // idx u32 [n * k] | n_ties u16 [n] | n_within u16 [n] | ed u8 [n * k]
         void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
         hipEvent_t match_done = nullptr;
-        uint32_t match_max_ed = 0;
+        uint32_t match_max_ed = 0, match_k = 0;
         bool match_queued = false;
     } slots[BDG_SLOTS];
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
@@ -135,6 +136,11 @@ int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan);   // overlap mode
 // results (a chunk that collect had to run again is matched again first).
 extern "C" int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed);
 extern "C" int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties);
+// the same with the k nearest entries (k = 0: the best-hit match above): best_idx / best_ed are slot 0 of the k, n_ties the
+// best-hit call's tie count; cand_idx / cand_ed [n * k] the slots (bdg_nearest16_topk)
+extern "C" int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k);
+extern "C" int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
+                                           uint32_t* cand_idx, uint8_t* cand_ed);
 
 // Event-bracketed launch bookkeeping.
 int  bdg_timer_id(bdg_ctx* ctx, const char* name);

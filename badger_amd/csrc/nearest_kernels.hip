@@ -15,6 +15,7 @@
 //          not two substitutions apart are one deletion plus one insertion apart, i.e. share a 15-base deletion variant:
 //          a 2^30-bit map of the whitelist's variants, then the owners of a variant that is present (pass 2).  Details
 //          at PairTables / delmap_index below.
+// Top-k forms of coop and probe (the k nearest within max_ed by (ed, caller index), and how many lie within it): at "top-k" below.
 #include "bdg_common.hpp"
 #include "bdg_partition.hpp"
 
@@ -138,12 +139,13 @@ constexpr uint64_t COOP_PARTIALS = 1ull << 21;   // partials the workspace holds
 
 struct CoopPlan { uint32_t nslices, slice_len; };
 
-__host__ __device__ inline CoopPlan coop_plan(uint32_t nq, uint32_t nw, uint64_t partial_cap)
+// qg: queries per work item (COOP_QG; the top-k kernel's COOP_TOPK_QG); partial_cap counts partials
+__host__ __device__ inline CoopPlan coop_plan(uint32_t nq, uint32_t nw, uint64_t partial_cap, uint32_t qg = COOP_QG)
 {
-    const uint64_t ngroups = ((uint64_t)nq + COOP_QG - 1) / COOP_QG;
+    const uint64_t ngroups = ((uint64_t)nq + qg - 1) / qg;
     uint64_t ns = ngroups ? (COOP_TARGET_ITEMS + ngroups - 1) / ngroups : 1;
     const uint64_t ns_nw = ((uint64_t)nw + COOP_MIN_SLICE - 1) / COOP_MIN_SLICE;
-    const uint64_t ns_mem = ngroups ? partial_cap / (ngroups * COOP_QG * 4) : 1;
+    const uint64_t ns_mem = ngroups ? partial_cap / (ngroups * qg * 4) : 1;
     ns = ns < ns_nw ? ns : ns_nw;
     ns = ns < ns_mem ? ns : ns_mem;
     ns = ns ? ns : 1;
@@ -598,6 +600,427 @@ void k_nearest_delins(const uint2* __restrict__ list2,
     }
 }
 
+// ---- top-k ----------------------------------------------------------------------
+// The k nearest entries within max_ed (bdg_nearest16_topk): order (ed, caller index), k <= TOPK_MAX, plus how many entries
+// lie within max_ed and - for stage 1's whitelist_ties column - how many share the smallest distance.  An entry is a packed
+// key ed << 32 | caller index (64 bits: every nw a 32-bit index addresses); the keys of distinct entries differ, so "the k
+// smallest keys" is the order above.  Every list holds TOPK_MAX keys whatever k is (registers are indexed by constants
+// only), ascending, KEY_NONE in empty places; the first k are the answer.
+constexpr int TOPK_MAX = 8;
+constexpr unsigned long long KEY_NONE = ~0ull;
+
+// a key into an ascending list: the largest falls off the end (branch-free compare-and-swap down the list)
+__device__ __forceinline__ void topk_insert(unsigned long long (&l)[TOPK_MAX], unsigned long long key)
+{
+#pragma unroll
+    for (int j = 0; j < TOPK_MAX; ++j) {
+        const unsigned long long a = l[j];
+        const bool lt = key < a;
+        l[j] = lt ? key : a;
+        key = lt ? a : key;
+    }
+}
+
+// the k smallest keys over the 64 lanes' lists (k wave-uniform): lane j < k returns the j-th, the others KEY_NONE.  Round j
+// takes the wave minimum of the list heads; the one lane holding it pops it (keys are distinct).  The lists are consumed.
+__device__ __forceinline__ unsigned long long wave_topk(unsigned long long (&l)[TOPK_MAX], uint32_t k, int lane)
+{
+    unsigned long long mine = KEY_NONE;
+    for (uint32_t j = 0; j < k; ++j) {
+        unsigned long long m = l[0];
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const unsigned long long o = __shfl_xor(m, s);
+            m = o < m ? o : m;
+        }
+        if (m == KEY_NONE) break;
+        if ((uint32_t)lane == j) mine = m;
+        if (l[0] == m) {
+#pragma unroll
+            for (int t = 0; t < TOPK_MAX - 1; ++t) l[t] = l[t + 1];
+            l[TOPK_MAX - 1] = KEY_NONE;
+        }
+    }
+    return mine;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_xor(v, m); v = o < v ? o : v; }
+    return v;
+}
+
+// Wave-cooperative top-k (algo 3, any max_ed, and the probe path's overflow): k_nearest_coop with a key list per lane and
+// query instead of one best key.  Fewer queries per work item (a list is 16 registers).  A partial per (query, slice, wave)
+// is k + 1 words: the wave's k smallest keys, then n_within | ties << 32 (ties: entries at the partial's smallest distance,
+// which is key 0's).  Register budget: 96 VGPRs, no scratch (tests/test_nearest_topk.py).
+constexpr int COOP_TOPK_QG = 2;
+
+__global__ __launch_bounds__(256)
+void k_nearest_coop_topk(const uint32_t* __restrict__ q, uint32_t qstride,
+                         const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq,
+                         const uint32_t* __restrict__ wl_sorted, const uint32_t* __restrict__ wl_orig, uint32_t nw,
+                         uint32_t max_ed, uint32_t k, unsigned long long* __restrict__ partials, uint64_t partial_cap)
+{
+    __shared__ uint2 s_ent[COOP_TILE];
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t ngroups = (nq + COOP_TOPK_QG - 1) / COOP_TOPK_QG;
+    const uint64_t nitems = (uint64_t)ngroups * plan.nslices;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    constexpr uint32_t EVEN = 0x55555555u;
+    for (uint64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint32_t g = (uint32_t)(item / plan.nslices), s = (uint32_t)(item % plan.nslices);
+        const uint32_t nqg = nq - g * COOP_TOPK_QG < (uint32_t)COOP_TOPK_QG ? nq - g * COOP_TOPK_QG : (uint32_t)COOP_TOPK_QG;
+        uint32_t qv[COOP_TOPK_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+            const uint32_t slot = g * COOP_TOPK_QG + ((uint32_t)i < nqg ? (uint32_t)i : 0u);
+            const uint32_t qi = qlist ? qlist[slot] : slot;
+            qv[i] = __builtin_amdgcn_readfirstlane(q[(size_t)qi * qstride]);
+        }
+        unsigned long long lst[COOP_TOPK_QG][TOPK_MAX];
+        uint32_t cnt[COOP_TOPK_QG], best[COOP_TOPK_QG], ties[COOP_TOPK_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX; ++j) lst[i][j] = KEY_NONE;
+            cnt[i] = 0u; best[i] = 255u; ties[i] = 0u;
+        }
+        const uint32_t s0 = s * plan.slice_len;
+        const uint32_t s1 = nw - s0 < plan.slice_len ? nw : s0 + plan.slice_len;
+        for (uint32_t t0 = s0; t0 < s1; t0 += COOP_TILE) {
+            const uint32_t tn = s1 - t0 < (uint32_t)COOP_TILE ? s1 - t0 : (uint32_t)COOP_TILE;
+            __syncthreads();
+            for (uint32_t e = threadIdx.x; e < tn; e += 256u) s_ent[e] = make_uint2(wl_sorted[t0 + e], wl_orig[t0 + e]);
+            __syncthreads();
+            for (uint32_t e = threadIdx.x; e < tn; e += 256u) {
+                const uint2 en = s_ent[e];
+                const uint32_t P0 = en.x & EVEN, P1 = (en.x >> 1) & EVEN;
+#pragma unroll
+                for (int i = 0; i < COOP_TOPK_QG; ++i) {
+                    const uint32_t t = qv[i];
+                    uint32_t pv = 0xFFFFFFFFu, mv = 0u, score = 16u;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const uint32_t m0 = (uint32_t)((int32_t)(t << (31 - 2 * j)) >> 31), m1 = (uint32_t)((int32_t)(t << (30 - 2 * j)) >> 31);
+                        const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);             // ~(P0 ^ m0) & EVEN
+                        const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);               // t1 & ~(P1 ^ m1)
+                        const uint32_t xv = eq | mv;
+                        const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);    // (((eq & pv) + pv) ^ pv) | eq
+                        uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                     // mv | ~(xh | pv)
+                        uint32_t mh = pv & xh;
+                        score += (ph >> 30) & 1u;
+                        score -= (mh >> 30) & 1u;
+                        ph = (ph << 2) | 1u;
+                        mh = mh << 2;
+                        pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                              // mh | ~(xv | ph)
+                        mv = ph & xv;
+                    }
+                    if (score <= max_ed) {
+                        ++cnt[i];
+                        ties[i] = score < best[i] ? 1u : (score == best[i] ? ties[i] + 1u : ties[i]);
+                        best[i] = score < best[i] ? score : best[i];
+                        const unsigned long long key = ((unsigned long long)score << 32) | en.y;
+                        if (key < lst[i][TOPK_MAX - 1]) topk_insert(lst[i], key);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+            const uint32_t n = wave_sum(cnt[i]);
+            const uint32_t wb = wave_min(best[i]);
+            const uint32_t tc = wave_sum(best[i] == wb ? ties[i] : 0u);
+            const unsigned long long mine = wave_topk(lst[i], k, lane);
+            if ((uint32_t)i < nqg) {
+                unsigned long long* p = partials + (((uint64_t)(g * COOP_TOPK_QG + i) * plan.nslices + s) * 4u + (uint32_t)wv) * (k + 1u);
+                if ((uint32_t)lane < k) p[lane] = mine;
+                if (lane == 0) p[k] = ((unsigned long long)tc << 32) | n;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void topk_store(uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, size_t at, unsigned long long key)
+{
+    out_idx[at] = key == KEY_NONE ? NONE_IDX : (uint32_t)key;
+    out_ed[at] = key == KEY_NONE ? (uint8_t)255u : (uint8_t)(key >> 32);
+}
+
+// one wave per query: every lane merges the partials lane, lane + 64, ... into its list, then the wave's k smallest keys
+// (fixed order, no atomics); unusable records: every slot empty, counts 0
+__global__ __launch_bounds__(256)
+void k_nearest_coop_topk_merge(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
+                               const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq, uint32_t nw,
+                               const unsigned long long* __restrict__ partials, uint64_t partial_cap, uint32_t k,
+                               uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                               uint16_t* __restrict__ n_ties)
+{
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t np = plan.nslices * 4u;
+    const int lane = threadIdx.x & 63;
+    for (uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6); slot < nq; slot += gridDim.x * 4u) {     // wave-uniform
+        const unsigned long long* base = partials + (uint64_t)slot * np * (k + 1u);
+        unsigned long long lst[TOPK_MAX];
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
+        uint32_t n = 0u, best = 255u, ties = 0u;
+        for (uint32_t pi = (uint32_t)lane; pi < np; pi += 64u) {
+            const unsigned long long* p = base + (uint64_t)pi * (k + 1u);
+            const unsigned long long c = p[k];
+            n += (uint32_t)c;
+            const unsigned long long k0 = p[0];
+            if (k0 != KEY_NONE) {
+                const uint32_t ed = (uint32_t)(k0 >> 32), tc = (uint32_t)(c >> 32);
+                ties = ed < best ? tc : (ed == best ? ties + tc : ties);
+                best = ed < best ? ed : best;
+            }
+            for (uint32_t j = 0; j < k; ++j) {               // ascending: stop at the first key that cannot enter (KEY_NONE too)
+                const unsigned long long key = p[j];
+                if (key >= lst[TOPK_MAX - 1]) break;
+                topk_insert(lst, key);
+            }
+        }
+        n = wave_sum(n);
+        const uint32_t wb = wave_min(best);
+        const uint32_t tc = wave_sum(best == wb ? ties : 0u);
+        unsigned long long mine = wave_topk(lst, k, lane);
+        const uint32_t qi = qlist ? qlist[slot] : slot;
+        const bool usable = !recs || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
+        if (!usable) mine = KEY_NONE;
+        if ((uint32_t)lane < k) topk_store(out_idx, out_ed, (size_t)qi * k + (uint32_t)lane, mine);
+        if (lane == 0) {
+            n_within[qi] = (uint16_t)(!usable ? 0u : (n > 0xFFFFu ? 0xFFFFu : n));
+            if (n_ties) n_ties[qi] = (uint16_t)(!usable ? 0u : (tc > 0xFFFFu ? 0xFFFFu : tc));
+        }
+    }
+}
+
+// Probe top-k, pass 1: k_nearest_pairs without its early stops - all six tables, every entry within min(max_ed, 2)
+// substitutions (each counted in its canonical table only) - into the lane's key list.  With max_ed = 2 every usable query
+// goes on to pass 2: the entries one deletion + one insertion away are at distance 2 too, whatever pass 1 found.
+__global__ __launch_bounds__(256)
+void k_nearest_pairs_topk(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t nq, PairTables pt, uint32_t max_ed,
+                          uint32_t k, uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                          uint16_t* __restrict__ n_ties, uint2* __restrict__ list2, uint32_t* __restrict__ counters)
+{
+    __shared__ uint32_t s_wcnt[4], s_base;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool on = i < nq;
+    uint32_t qq = 0;
+    bool usable = on;
+    if (on) {
+        qq = q[(size_t)i * qstride];
+        if (recs) usable = ((q[(size_t)i * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
+    }
+    unsigned long long lst[TOPK_MAX];
+#pragma unroll
+    for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
+    uint32_t n = 0u, best = 255u, ties = 0u;
+    if (usable) {
+#pragma unroll 1
+        for (int p = 0; p < 6; ++p) {
+            const int bk = p < 3 ? (p == 0 ? 2 : 1) : 0;
+            const int bl = p < 3 ? (p == 2 ? 2 : 3) : (p == 3 ? 3 : (p == 4 ? 2 : 1));
+            const uint32_t qrest = ((qq >> (8 * bk)) & 0xFFu) | (((qq >> (8 * bl)) & 0xFFu) << 8);
+            uint32_t blk = (uint32_t)p * 65536u + pair_key(qq, p);
+            do {
+                const uint4* rb = reinterpret_cast<const uint4*>(pt.rank + (size_t)blk * 16u);
+                const uint4 q0 = rb[0], q1 = rb[1], q2 = rb[2], q3 = rb[3];
+                const uint32_t wr[16] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w };
+                const uint32_t cnt = wr[0] & 0xFFu;
+#pragma unroll
+                for (uint32_t u = 0; u < PAIR_BLOCK_ENTRIES; ++u) {
+                    const uint32_t e = (wr[1 + (u >> 1)] >> (16 * (u & 1u))) & 0xFFFFu;
+                    const uint32_t xr = e ^ qrest;
+                    const uint32_t h = __popc((xr | (xr >> 1)) & 0x5555u);
+                    if (u < cnt && h <= max_ed) {
+                        const uint32_t x = ((xr & 0xFFu) << (8 * bk)) | ((xr >> 8) << (8 * bl));
+                        if (canonical_pair(x) == p) {
+                            const uint32_t wo = pt.idx[(size_t)blk * 32u + u];
+                            ++n;
+                            ties = h < best ? 1u : (h == best ? ties + 1u : ties);
+                            best = h < best ? h : best;
+                            const unsigned long long key = ((unsigned long long)h << 32) | wo;
+                            if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
+                        }
+                    }
+                }
+                blk = wr[0] >> 8;
+            } while (blk);
+        }
+    }
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, (size_t)i * k + (uint32_t)j, lst[j]);
+        n_within[i] = (uint16_t)(n > 0xFFFFu ? 0xFFFFu : n);
+        if (n_ties) n_ties[i] = (uint16_t)(ties > 0xFFFFu ? 0xFFFFu : ties);
+    }
+    const bool need2 = usable && max_ed >= 2u;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(need2);
+    if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    const uint32_t seg = blockIdx.x % LSH;
+    if (threadIdx.x == 0) {
+        const uint32_t tot = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        s_base = tot ? atomicAdd(&counters[seg * 32], tot) : 0u;
+    }
+    __syncthreads();
+    if (need2) {
+        uint32_t at = s_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wv; ++w) at += s_wcnt[w];
+        list2[(size_t)seg * nq + at] = make_uint2(i, qq);
+    }
+}
+
+// Probe top-k, pass 2: k_nearest_delins's look-ups and overflow rule unchanged; the distinct entries a query's four lanes
+// found (all at distance 2, none of them pass 1's: those are within Hamming distance 2 and skipped) are merged into the k
+// slots pass 1 wrote, and added to its counts.
+__global__ __launch_bounds__(256)
+void k_nearest_delins_topk(const uint2* __restrict__ list2,
+                           uint32_t nq, const uint32_t* counters, const uint32_t* __restrict__ delmap,
+                           const uint4* __restrict__ dv_ent, const uint32_t* __restrict__ dv_dir, uint32_t k,
+                           uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                           uint16_t* __restrict__ n_ties, uint32_t* __restrict__ list3, uint32_t* counters_out)
+{
+    uint32_t n2 = 0;
+#pragma unroll
+    for (int s = 0; s < LSH; ++s) { const uint32_t c = counters[s * 32]; n2 = c > n2 ? c : n2; }
+    n2 *= LSH;
+    const int lane = threadIdx.x & 63, sub = lane & 3, grp = lane >> 2;
+    const uint32_t wave_slot0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 16u;
+    const uint32_t ngroups = gridDim.x * 64u;
+    const unsigned long long gmask = 0xFull << (4 * grp);
+    const uint32_t seg = (wave_slot0 + (uint32_t)grp) % LSH;
+    const uint32_t seg_cnt = counters[seg * 32];
+    const uint2* seg_list = list2 + (size_t)seg * nq;
+    auto fetch = [&](uint32_t s0) -> uint2 {
+        const uint32_t s = s0 + (uint32_t)grp;
+        return (s < n2 && s / LSH < seg_cnt) ? seg_list[s / LSH] : make_uint2(NONE_IDX, 0u);
+    };
+    auto variant = [&](uint32_t qq, int t) -> uint32_t {
+        const uint32_t lm = low_mask(4 * sub + t);
+        return ((qq & lm) | ((qq >> 2) & ~lm)) & 0x3FFFFFFFu;
+    };
+    const uint2* const my_map = reinterpret_cast<const uint2*>(delmap + (size_t)sub * DELMAP_WORDS);
+    auto map_word = [&](uint32_t qq) -> uint2 { return my_map[delmap_index(variant(qq, 0), sub) >> 6]; };
+    uint2 e1 = fetch(wave_slot0), e2 = fetch(wave_slot0 + ngroups);
+    uint2 w1 = e1.x != NONE_IDX ? map_word(e1.y) : make_uint2(0u, 0u);
+    for (uint32_t s0 = wave_slot0; s0 < n2; s0 += ngroups) {
+        const uint32_t qi = e1.x, qq = e1.y;
+        const unsigned long long word = ((unsigned long long)w1.y << 32) | w1.x;
+        const bool on = qi != NONE_IDX;
+        e1 = e2;
+        w1 = e1.x != NONE_IDX ? map_word(e1.y) : make_uint2(0u, 0u);
+        e2 = fetch(s0 + 2u * ngroups);
+        uint32_t found[4] = { 0, 0, 0, 0 }; int nf = 0; bool overflow = false;
+        auto take = [&](const uint4 en, uint32_t d) __attribute__((always_inline)) {
+            if (en.x != d) return;
+            if (hamming16(en.y ^ qq) <= 2u) return;
+            const uint32_t oo = en.z;
+            const bool dup = (nf > 0 && found[0] == oo) || (nf > 1 && found[1] == oo) ||
+                             (nf > 2 && found[2] == oo) || (nf > 3 && found[3] == oo);
+            if (!dup) {
+                if (nf < 4) { found[0] = nf == 0 ? oo : found[0]; found[1] = nf == 1 ? oo : found[1];
+                              found[2] = nf == 2 ? oo : found[2]; found[3] = nf == 3 ? oo : found[3]; ++nf; }
+                else overflow = true;
+            }
+        };
+        uint32_t dvar[4]; bool hit[4]; bool any_hit = false;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int i = 4 * sub + t;
+            dvar[t] = variant(qq, t);
+            const bool dup_del = i > 0 && (((qq >> (2 * i)) ^ (qq >> (2 * i - 2))) & 3u) == 0u;
+            hit[t] = on && !dup_del && ((word >> (delmap_index(dvar[t], sub) & 63u)) & 1ull);
+            any_hit = any_hit || hit[t];
+        }
+        if (__ballot(any_hit)) {
+            constexpr int DV_AHEAD = 3;
+            uint32_t lo[4], hi[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const uint32_t b = hit[t] ? (dvar[t] >> DV_DIR_SHIFT) : 0u;
+                lo[t] = dv_dir[b]; hi[t] = dv_dir[b + 1];
+                if (!hit[t]) hi[t] = lo[t] = 0u;
+            }
+            uint4 en[4][DV_AHEAD];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int e = 0; e < DV_AHEAD; ++e) en[t][e] = dv_ent[lo[t] + (uint32_t)e < hi[t] ? lo[t] + (uint32_t)e : 0u];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+#pragma unroll
+                for (int e = 0; e < DV_AHEAD; ++e) if (lo[t] + (uint32_t)e < hi[t]) take(en[t][e], dvar[t]);
+                for (uint32_t x = lo[t] + DV_AHEAD; x < hi[t]; ++x) take(dv_ent[x], dvar[t]);
+            }
+        }
+        // the distinct hits of the query's four lanes, one at a time in every lane of the group, into a fresh key list
+        const bool any_over = (__ballot(overflow) & gmask) != 0;
+        unsigned long long lst[TOPK_MAX];
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
+        uint32_t add = 0;
+        int pending = nf;
+        while (true) {
+            const unsigned long long bal_all = __ballot(pending > 0);
+            if (!bal_all) break;
+            const unsigned long long bal = bal_all & gmask;
+            const int src = bal ? __builtin_ctzll(bal) : lane;
+            const uint32_t v = __shfl(found[0], src);
+            if (bal) {
+                ++add;
+                const unsigned long long key = (2ull << 32) | v;
+                if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
+                const bool h0 = pending > 0 && found[0] == v, h1 = pending > 1 && found[1] == v;
+                const bool h2 = pending > 2 && found[2] == v, h3 = pending > 3 && found[3] == v;
+                if (h0) { found[0] = found[1]; found[1] = found[2]; found[2] = found[3]; }
+                else if (h1) { found[1] = found[2]; found[2] = found[3]; }
+                else if (h2) { found[2] = found[3]; }
+                if (h0 || h1 || h2 || h3) --pending;
+            }
+        }
+        if (on && sub == 0) {
+            if (any_over) list3[atomicAdd(&counters_out[CTR_N3], 1u)] = qi;
+            else if (add) {
+                const size_t at = (size_t)qi * k;
+                const uint32_t ed0 = out_ed[at];
+#pragma unroll
+                for (int j = 0; j < TOPK_MAX; ++j) {
+                    if ((uint32_t)j < k && out_ed[at + j] != 255u) {
+                        const unsigned long long key = ((unsigned long long)out_ed[at + j] << 32) | out_idx[at + j];
+                        if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, at + j, lst[j]);
+                const uint32_t n = n_within[qi] + add;
+                n_within[qi] = (uint16_t)(n > 0xFFFFu ? 0xFFFFu : n);
+                if (n_ties && ed0 >= 2u) {
+                    const uint32_t t = (ed0 == 2u ? n_ties[qi] : 0u) + add;
+                    n_ties[qi] = (uint16_t)(t > 0xFFFFu ? 0xFFFFu : t);
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -839,6 +1262,104 @@ int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, in
         {
             ScopedKernelTimer tm(ctx, "k_nearest_coop_overflow");
             if ((rc = launch_coop(ctx, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3, nq, max_ed, d_best_idx, d_best_ed, d_n_ties)))
+                return rc;
+        }
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+// ---- top-k dispatch -------------------------------------------------------------------------------------------------
+// The cooperative top-k kernel and its merge (query list as for launch_coop).  A partial takes k + 1 words.
+static int launch_coop_topk(bdg_ctx* ctx, hipStream_t st, const uint32_t* d_q, uint32_t qstride, int recs, const uint32_t* qlist,
+                            uint32_t nq_host, const uint32_t* d_nq, uint32_t nq_cap, uint32_t max_ed, uint32_t k,
+                            uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within, uint16_t* d_n_ties)
+{
+    const uint64_t groups = ((uint64_t)nq_cap + COOP_TOPK_QG - 1) / COOP_TOPK_QG;
+    const uint64_t cap = std::max<uint64_t>(COOP_PARTIALS, groups * COOP_TOPK_QG * 4u * (k + 1u));      // words
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_coop, sizeof(unsigned long long) * cap))) return rc;
+    const uint64_t have = ctx->n_coop.bytes / sizeof(unsigned long long) / (k + 1u);        // in partials
+    auto* part = static_cast<unsigned long long*>(ctx->n_coop.p);
+    const auto* srt = static_cast<const uint32_t*>(ctx->w_sorted.p);
+    const auto* org = static_cast<const uint32_t*>(ctx->w_orig.p);
+    uint32_t grid = COOP_GRID;
+    if (!d_nq) {
+        const CoopPlan p = coop_plan(nq_host, ctx->w_n, have, COOP_TOPK_QG);
+        const uint64_t items = (((uint64_t)nq_host + COOP_TOPK_QG - 1) / COOP_TOPK_QG) * p.nslices;
+        grid = (uint32_t)std::min<uint64_t>(items, COOP_GRID);
+    }
+    hipLaunchKernelGGL(k_nearest_coop_topk, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
+                       max_ed, k, part, have);
+    const uint32_t mgrid = d_nq ? 256u : std::min<uint32_t>((nq_host + 3) / 4, 2048u);
+    hipLaunchKernelGGL(k_nearest_coop_topk_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
+                       part, have, k, d_idx, d_ed, d_n_within, d_n_ties);
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+// how many queries the last probe-path call sent to the cooperative kernel (its overflow list's length; the caller has
+// synchronised)
+int bdg_nearest16_overflow_read(bdg_ctx* ctx, uint32_t* n)
+{
+    *n = 0;
+    if (!ctx->n_counters.p) return BDG_OK;
+    BDG_HIP_TRY(ctx, hipMemcpy(n, static_cast<const uint32_t*>(ctx->n_counters.p) + CTR_N3, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BDG_OK;
+}
+
+int bdg_nearest16_topk_check(bdg_ctx* ctx, uint32_t nq, uint32_t max_ed, uint32_t k)
+{
+    if (k == 0 || k > (uint32_t)TOPK_MAX) return bdg_fail(ctx, BDG_E_ARG, "k out of range (1 .. 8)");
+    if (ctx->n16_algo == 1) return bdg_fail(ctx, BDG_E_ARG, "the scan (algo 1) has no top-k form");
+    if (ctx->n16_algo == 2 && max_ed > 2) return bdg_fail(ctx, BDG_E_ARG, "probe path needs max_ed <= 2");
+    if (nq && ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    return BDG_OK;
+}
+
+// top-k of nq queries (plain array or records, as bdg_nearest16_launch): d_idx / d_ed [nq * k], d_n_within [nq]; d_n_ties
+// (may be null): entries at slot 0's distance, what the best-hit call reports.  Probe path for max_ed <= 2 (automatic, algo 2),
+// the cooperative kernel otherwise (algo 3, max_ed > 2).
+int bdg_nearest16_topk_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, int recs, uint32_t nq, uint32_t max_ed,
+                              uint32_t k, uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within, uint16_t* d_n_ties)
+{
+    { const int rcc = bdg_nearest16_topk_check(ctx, nq, max_ed, k); if (rcc) return rcc; }
+    if (nq == 0) return BDG_OK;
+    hipStream_t st = ctx->launch_stream ? ctx->launch_stream : ctx->stream;
+    const bool probe = ctx->n16_algo != 3 && max_ed <= 2;
+    if (!probe) {
+        ScopedKernelTimer tm(ctx, "k_nearest_coop_topk");
+        return launch_coop_topk(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, k, d_idx, d_ed, d_n_within, d_n_ties);
+    }
+    int rc;
+    if (!ctx->w_probe_ready && (rc = build_pair_tables(ctx))) return rc;
+    if (max_ed >= 2 && !ctx->w_delins_ready && (rc = build_delins_index(ctx))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_list, sizeof(uint32_t) * (2ull * LSH + 1ull) * nq))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_counters, NCTR_BYTES))) return rc;
+    auto* list2 = static_cast<uint2*>(ctx->n_list.p);
+    auto* list3 = reinterpret_cast<uint32_t*>(list2 + (size_t)LSH * nq);
+    auto* counters = static_cast<uint32_t*>(ctx->n_counters.p);
+    BDG_HIP_TRY(ctx, hipMemsetAsync(counters, 0, NCTR_BYTES, st));
+    PairTables pt{ static_cast<const uint32_t*>(ctx->w_pent.p), static_cast<const uint32_t*>(ctx->w_pent.p) + ctx->w_pwords,
+                   static_cast<const uint32_t*>(ctx->w_delmap.p), ctx->w_n };
+    {
+        ScopedKernelTimer tm(ctx, "k_nearest_pairs_topk");
+        hipLaunchKernelGGL(k_nearest_pairs_topk, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, nq, pt, max_ed, k,
+                           d_idx, d_ed, d_n_within, d_n_ties, list2, counters);
+    }
+    if (max_ed >= 2) {
+        {
+            ScopedKernelTimer tm(ctx, "k_nearest_delins_topk");
+            const uint32_t grid = std::min<uint32_t>((nq + 63) / 64, 256u * 8u);
+            const size_t npairs = 16ull * ctx->w_n;
+            hipLaunchKernelGGL(k_nearest_delins_topk, dim3(grid), dim3(256), 0, st, list2, nq, counters, pt.delmap,
+                               static_cast<const uint4*>(ctx->w_dv.p), static_cast<const uint32_t*>(ctx->w_dv.p) + 4 * npairs, k,
+                               d_idx, d_ed, d_n_within, d_n_ties, list3, counters);
+        }
+        {
+            ScopedKernelTimer tm(ctx, "k_nearest_coop_topk_overflow");
+            if ((rc = launch_coop_topk(ctx, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3, nq, max_ed, k,
+                                       d_idx, d_ed, d_n_within, d_n_ties)))
                 return rc;
         }
     }

@@ -44,18 +44,21 @@ inline char* put_int(char* o, int v)
 
 struct RowStats { uint64_t reads = 0, bc = 0, pt = 0, r1 = 0, first_pt = ~0ull, first_r1 = ~0ull, wl = 0; };
 
-// A chunk's whitelist calls (bdg_format_rows_wl): per read the match's answer, and the whitelist in the caller's order.
+// A chunk's whitelist calls (bdg_format_rows_wl): per read the match's answer, and the whitelist in the caller's order;
+// k > 0: also the k slots of the top-k match per read (bdg_format_rows_wlk)
 struct WlCalls {
     const uint32_t* idx; const uint8_t* ed; const uint16_t* ties;
     const uint32_t* wl; uint32_t nw;
+    uint32_t k = 0; const uint32_t* cidx = nullptr; const uint8_t* ced = nullptr;
 };
 constexpr uint64_t WL_COLS_MAX = 1 + 16 + 1 + 3 + 1 + 5;    // "\t" barcode "\t" dist "\t" ties
+constexpr uint64_t WL_CAND_MAX = 16 + 1 + 3 + 1;            // per slot: barcode ":" dist ","
 
 // upper bound of the text of a chunk's rows (+ the headers that fall inside it)
 uint64_t rows_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, uint64_t g0, uint32_t header_every, size_t header_len,
                     const WlCalls* wc = nullptr)
 {
-    uint64_t need = wc ? WL_COLS_MAX * ch->n : 0;
+    uint64_t need = wc ? (WL_COLS_MAX + (wc->k ? 2 + WL_CAND_MAX * wc->k : 0)) * ch->n : 0;
     for (uint32_t i = 0; i < ch->n; ++i) {
         const uint64_t L = ch->off[i + 1] - ch->off[i];
         need += (ch->id_off[i + 1] - ch->id_off[i]) + 64 + (recs[i].valid ? 16 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start)) : 2);
@@ -121,6 +124,23 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
             o = put_int(o, usable ? (int)wc->ed[i] : -1);
             *o++ = '\t';
             o = put_int(o, usable ? (int)wc->ties[i] : 0);
+            if (wc->k) {
+                // the k nearest within max_ed, BARCODE:DIST in slot order; '*' for none or no usable barcode
+                *o++ = '\t';
+                const char* const o0 = o;
+                if (r.valid && (r.flags & BDG_FLAG_RANK_OK)) {
+                    for (uint32_t j = 0; j < wc->k; ++j) {
+                        const size_t at = (size_t)i * wc->k + j;
+                        if (wc->ced[at] == 255u || wc->cidx[at] >= wc->nw) break;
+                        if (o != o0) *o++ = ',';
+                        const uint32_t rk = wc->wl[wc->cidx[at]];
+                        for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(rk >> (2 * b)) & 3u];
+                        *o++ = ':';
+                        o = put_int(o, (int)wc->ced[at]);
+                    }
+                }
+                if (o == o0) *o++ = '*';
+            }
         }
         *o++ = '\n';
         if (r.polyT != -1) { ++st.pt; if (st.first_pt == ~0ull) st.first_pt = g0 + i; }
@@ -141,6 +161,7 @@ struct Job {
     bdg_ctx* ctx = nullptr; uint32_t slot = 0;
     std::vector<bdg_extract_rec> recs;
     std::vector<uint32_t> m_idx; std::vector<uint8_t> m_ed; std::vector<uint16_t> m_ties;    // whitelist calls
+    std::vector<uint32_t> c_idx; std::vector<uint8_t> c_ed;                                   // top-k slots (bc_candidates)
     std::vector<char> text; size_t text_len = 0;
     RowStats st;
 };
@@ -151,6 +172,7 @@ struct Pipeline {
     std::string header;
     uint32_t header_every = 0;
     const uint32_t* wl = nullptr; uint32_t nw = 0;             // whitelist in the caller's order (opts->whitelist)
+    uint32_t k = 0;                                            // opts->bc_candidates
     std::mutex mu;
     std::condition_variable cv;
     std::deque<Job*> to_format;
@@ -172,7 +194,7 @@ struct Pipeline {
                 j = to_format.front(); to_format.pop_front();
             }
             const double t0 = now_s();
-            const WlCalls wc{ j->m_idx.data(), j->m_ed.data(), j->m_ties.data(), wl, nw };
+            const WlCalls wc{ j->m_idx.data(), j->m_ed.data(), j->m_ties.data(), wl, nw, k, j->c_idx.data(), j->c_ed.data() };
             const WlCalls* pw = wl ? &wc : nullptr;
             j->text.resize((size_t)rows_bound(&j->ch, j->recs.data(), j->g0, header_every, header.size(), pw));
             char* e = write_rows(&j->ch, j->recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
@@ -180,6 +202,7 @@ struct Pipeline {
             bdg_ingest_release(ing, j->ch.id);
             std::vector<bdg_extract_rec>().swap(j->recs);
             std::vector<uint32_t>().swap(j->m_idx); std::vector<uint8_t>().swap(j->m_ed); std::vector<uint16_t>().swap(j->m_ties);
+            std::vector<uint32_t>().swap(j->c_idx); std::vector<uint8_t>().swap(j->c_ed);
             const double dt = now_s() - t0;
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -263,6 +286,24 @@ int64_t bdg_format_rows_wl(const bdg_ingest_chunk* ch, const bdg_extract_rec* re
     return (int64_t)(e - out);
 }
 
+int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const uint32_t* best_idx,
+                            const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                            uint32_t k, const uint32_t* cand_idx, const uint8_t* cand_ed,
+                            char* out, uint64_t cap, uint64_t counts[5])
+{
+    if (!ch || k == 0 || k > 8) return BDG_E_ARG;
+    if (ch->n && (!recs || !ch->bases || !ch->off || !ch->ids || !ch->id_off || !best_idx || !best_ed || !n_ties || !cand_idx || !cand_ed))
+        return BDG_E_ARG;
+    if (nw && !wl) return BDG_E_ARG;
+    const WlCalls wc{ best_idx, best_ed, n_ties, wl, nw, k, cand_idx, cand_ed };
+    const uint64_t need = rows_bound(ch, recs, 0, 0, 0, &wc);
+    if (!out || need > cap) return (int64_t)need;
+    RowStats st;
+    char* e = write_rows(ch, recs, out, 0, 0, nullptr, 0, st, &wc);
+    if (counts) { counts[0] = ch->n; counts[1] = st.bc; counts[2] = st.pt; counts[3] = st.r1; counts[4] = st.wl; }
+    return (int64_t)(e - out);
+}
+
 int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                    const bdg_stage1_opts* o, bdg_stage1_result* res)
 {
@@ -274,7 +315,10 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
     std::vector<uint32_t> wl_caller;
     if (o->whitelist) {
-        if (o->max_bc_dist > 16) return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
+        // a caller that does not set BDG_STAGE1_WL_CANDIDATES knows bc_candidates as the upper half of a 32-bit max_bc_dist
+        if (o->max_bc_dist > 16 || (!(o->whitelist & BDG_STAGE1_WL_CANDIDATES) && o->bc_candidates))
+            return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
+        if (o->bc_candidates > 8) return bdg_fail(c0, BDG_E_ARG, "bc_candidates out of range (0 .. 8)");
         for (uint32_t c = 0; c < n_ctx; ++c) {
             if (!ctxs[c]) return BDG_E_ARG;
             if (ctxs[c]->w_n == 0) return bdg_fail(c0, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load) on context " + std::to_string(c));
@@ -301,7 +345,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (P.fd < 0) { bdg_ingest_close(P.ing); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
     P.header = header; P.header_every = o->header_every;
-    if (o->whitelist) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); }
+    if (o->whitelist) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
     bool ok_io = true;
     if (!o->header_every) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
     std::vector<std::thread> fmt;
@@ -317,7 +361,9 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         int r = bdg_extract_collect(j->ctx, j->slot, j->recs.data());
         if (r == BDG_OK && o->whitelist) {
             j->m_idx.resize(j->ch.n); j->m_ed.resize(j->ch.n); j->m_ties.resize(j->ch.n);
-            r = bdg_slot_match_collect(j->ctx, j->slot, j->m_idx.data(), j->m_ed.data(), j->m_ties.data());
+            j->c_idx.resize((size_t)j->ch.n * o->bc_candidates); j->c_ed.resize((size_t)j->ch.n * o->bc_candidates);
+            r = bdg_slot_match_collect_topk(j->ctx, j->slot, j->m_idx.data(), j->m_ed.data(), j->m_ties.data(),
+                                            j->c_idx.data(), j->c_ed.data());
         }
         t_gpu_wait += now_s() - t0;
         if (r) {
@@ -353,7 +399,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         rc = bdg_extract_submit(j->ctx, j->slot, ch.bases, ch.off, ch.n, o->umi_len);
         if (rc) { t_submit += now_s() - t1; err = bdg_last_error(j->ctx); bdg_ingest_release(P.ing, ch.id); delete j; break; }
         inflight.push_back(j);                                   // (submitted: collected below even if its match cannot be queued)
-        if (o->whitelist) rc = bdg_slot_match(j->ctx, j->slot, o->max_bc_dist);
+        if (o->whitelist) rc = bdg_slot_match_topk(j->ctx, j->slot, o->max_bc_dist, o->bc_candidates);
         t_submit += now_s() - t1;
         if (rc) { err = bdg_last_error(j->ctx); break; }
         g0 += ch.n; ++k;

@@ -22,6 +22,9 @@ What differs from the reference, by design:
     at most --max_bc_dist, default 2 - the bound of the reference's own whitelist match, barcode_graph.py:383) and three
     columns follow R1_end: whitelist_barcode, whitelist_dist, whitelist_ties (include/badger_hip.h, bdg_format_rows_wl),
     plus a "Whitelist barcode" line in the .stats.  Without -b the files are what they were.
+  * --bc_candidates K (1 .. 8, needs -b): one more column, whitelist_candidates - the K nearest entries within
+    --max_bc_dist by (distance, list order) as BARCODE:DIST joined by commas, '*' for none (bdg_nearest16_topk,
+    bdg_format_rows_wlk).  The other columns and the .stats do not change.
 """
 import argparse
 import gzip
@@ -40,6 +43,7 @@ logger = logging.getLogger("BarcodeGraph")
 
 READ_CHUNK_SIZE = 100000
 WHITELIST_COLUMNS = ("whitelist_barcode", "whitelist_dist", "whitelist_ties")
+CANDIDATES_COLUMN = "whitelist_candidates"
 MAX_BC_DIST_DEFAULT = 2
 BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
 
@@ -365,9 +369,12 @@ def _run_native(args, header_every, threads, skip_secondary):
         for d in detectors:
             d._ctx().whitelist_load(wl)
         header += "\t" + "\t".join(WHITELIST_COLUMNS)
+        if getattr(args, "bc_candidates", None):
+            header += "\t" + CANDIDATES_COLUMN
     res = _native.stage1_run([d._ctx() for d in detectors], args.input, args.output, header,
                              detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
-                             whitelist=wl is not None, max_bc_dist=_max_bc_dist(args))
+                             whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
+                             bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0)
     timing = os.environ.get("BADGER_AMD_STAGE1_TIMING")
     if timing:                                   # where the run's time went (tools/cli_throughput.py reads it)
         import json
@@ -477,9 +484,14 @@ def parse_args(sys_argv):
                    help="barcode whitelist for the used protocol (plain or gzipped; one barcode per line)")
     p.add_argument("--max_bc_dist", type=_bc_dist, default=None, metavar="D",
                    help="largest edit distance of a whitelist call, 0 .. 16 (default %d); needs --barcodes" % MAX_BC_DIST_DEFAULT)
+    p.add_argument("--bc_candidates", type=_bc_candidates, default=None, metavar="K",
+                   help="add a whitelist_candidates column: the K (1 .. 8) nearest whitelist entries within --max_bc_dist, "
+                        "as BARCODE:DIST by (distance, list order); needs --barcodes")
     args = p.parse_args(sys_argv)
     if args.max_bc_dist is not None and not args.barcodes:
         p.error("--max_bc_dist needs --barcodes")
+    if args.bc_candidates is not None and not args.barcodes:
+        p.error("--bc_candidates needs --barcodes")
     return args
 
 
@@ -497,6 +509,16 @@ def _bc_dist(text):
         raise argparse.ArgumentTypeError("not an integer: %r" % text)
     if not 0 <= v <= 16:
         raise argparse.ArgumentTypeError("%d is outside 0 .. 16" % v)
+    return v
+
+
+def _bc_candidates(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 1 <= v <= 8:
+        raise argparse.ArgumentTypeError("%d is outside 1 .. 8" % v)
     return v
 
 

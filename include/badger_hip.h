@@ -259,6 +259,13 @@ int64_t bdg_format_rows(const bdg_ingest_chunk* chunk, const bdg_extract_rec* re
 int64_t bdg_format_rows_wl(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const uint32_t* best_idx,
                            const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
                            char* out, uint64_t cap, uint64_t counts[5]);
+/* bdg_format_rows_wl plus one column, whitelist_candidates: the k slots of bdg_nearest16_topk per record (cand_idx /
+ * cand_ed [n * k]) as BARCODE:DIST joined by commas, in slot order; '*' when no slot is filled or the record has no usable
+ * barcode (not valid, or no BDG_FLAG_RANK_OK). */
+int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const uint32_t* best_idx,
+                            const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                            uint32_t k, const uint32_t* cand_idx, const uint8_t* cand_ed,
+                            char* out, uint64_t cap, uint64_t counts[5]);
 
 /* Stage 1 from file to file in native threads: readers -> GPU(s) -> row formatters -> one writer, rows in input order
  * (extract_raw_barcodes.py:162-173 process_single_thread, :176-261 process_in_parallel).  Chunk k goes to context k mod
@@ -266,6 +273,7 @@ int64_t bdg_format_rows_wl(const bdg_ingest_chunk* chunk, const bdg_extract_rec*
  * extraction on the context's auxiliary stream (the one of bdg_set_overlap), where it runs beside the next chunk's.  header: the column line without its newline.  Returns BDG_E_BADBASE (reference:
  * KeyError), BDG_E_FORMAT (ValueError), BDG_E_NOSEQ (TypeError) with the rows of the chunks in front of the failure
  * written, like the reference's loop; the message is bdg_last_error(ctxs[0]). */
+#define BDG_STAGE1_WL_CANDIDATES 0x100u    /* bdg_stage1_opts.whitelist: the caller sets bc_candidates */
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -277,8 +285,13 @@ typedef struct bdg_stage1_opts {
     int32_t  skip_secondary;      /* bdg_ingest_opts.skip_secondary */
     uint64_t segment_bytes;       /* bdg_ingest_opts.segment_bytes */
     uint32_t whitelist;           /* 1: match every read's barcode against the whitelist each context holds (bdg_whitelist_load, the same
-                                     list on all of them) and write the three columns of bdg_format_rows_wl; 0: the rows of bdg_format_rows */
-    uint32_t max_bc_dist;         /* whitelist: the max_ed of the match */
+                                     list on all of them) and write the three columns of bdg_format_rows_wl; 0: the rows of bdg_format_rows.
+                                     | BDG_STAGE1_WL_CANDIDATES: bc_candidates is read (without the flag it must be 0) */
+    uint16_t max_bc_dist;         /* whitelist: the max_ed of the match */
+    uint16_t bc_candidates;       /* whitelist with BDG_STAGE1_WL_CANDIDATES: 0 = off; K (1 .. 8): the match is bdg_nearest16_topk
+                                     with k = K and the rows get the column of bdg_format_rows_wlk.  It takes the upper half of what
+                                     was a 32-bit max_bc_dist, so the struct keeps its size; without the flag a nonzero upper half
+                                     is rejected as an out-of-range max_bc_dist, as it was before. */
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -322,10 +335,29 @@ int  bdg_nearest16_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_
  * rejects a call the algorithm cannot serve (algo 2 with max_ed > 2) or one without a
  * whitelist at once, in overlap mode too. */
 int  bdg_nearest16_set_algo(bdg_ctx* ctx, int algo);
+/* The k nearest entries (1 <= k <= 8) within max_ed, ordered by (distance, caller index): per query q, slots
+ * idx[q*k + j] / ed[q*k + j] for j < min(k, n_within[q]), the remaining slots idx 0xFFFFFFFF, ed 0xFF; n_within[q] = how
+ * many entries lie within max_ed (saturating at 65535).  Slot 0 is bdg_nearest16's (best_idx, best_ed); the slots at its
+ * distance number min(k, n_ties).  Paths as bdg_nearest16_set_algo: automatic and algo 2 take the probe path for
+ * max_ed <= 2 (every entry within max_ed enumerated; a query whose candidates overflow it goes to the cooperative kernel),
+ * algo 3 and automatic with max_ed > 2 the cooperative kernel.  BDG_E_ARG at the call for k = 0 or k > 8, algo 1 (the scan
+ * has no top-k form) and algo 2 with max_ed > 2, in overlap mode too. */
+int  bdg_nearest16_topk(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw,
+                        uint32_t max_ed, uint32_t k, uint32_t* idx, uint8_t* ed, uint16_t* n_within);
+/* device arrays, the whitelist of bdg_whitelist_load; asynchronous on the context's stream */
+int  bdg_nearest16_topk_dev(bdg_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t max_ed, uint32_t k,
+                            uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within);
+/* the barcodes of extraction records, as bdg_nearest16_recs_dev: a record without BDG_FLAG_RANK_OK gets every slot empty and
+ * n_within 0.  In overlap mode a best-hit match still waiting is queued first; this one is not deferred. */
+int  bdg_nearest16_topk_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t n, uint32_t max_ed, uint32_t k,
+                                 uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within);
 /* Device memory held by the neighbourhood-probe index of the loaded whitelist, in bytes: 0 until a call takes the probe path
  * (automatic mode takes the exhaustive scan while nw * nq stays small, e.g. stage 2's --high_sens pass against ~5,000 centres:
  * no index is ever built then); the deletion-variant part is added by the first probe call with max_ed = 2. */
 uint64_t bdg_nearest16_index_bytes(bdg_ctx* ctx);
+/* How many queries the last probe-path call (best-hit or top-k) sent on to the cooperative kernel because a lane of its second
+ * pass found more distinct entries than it holds; 0 when no probe call was made.  Waits for the context's streams. */
+uint32_t bdg_nearest16_overflow_count(bdg_ctx* ctx);
 
 /* ---- B-G: edit-distance graph ----------------------------------------- */
 /* ranks: distinct rank-packed 16-mers, any order.  Writes up to cap edges (a<b)
