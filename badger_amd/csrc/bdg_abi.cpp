@@ -274,7 +274,7 @@ void bdg_free(bdg_ctx* ctx)
     if (ctx->ev_scan) (void)hipEventDestroy(ctx->ev_scan);
     for (hipEvent_t e : ctx->ev_aux) if (e) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
-                       &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_prefix, &ctx->w_bitmap, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
+                       &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
                        &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {

@@ -88,18 +88,15 @@ struct bdg_ctx {
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending
     DevBuf w_orig;       // uint32 [nw] caller index of sorted entry
-    DevBuf w_prefix;     // uint32 [2^pbits + 1] offsets by top bits
-    DevBuf w_bitmap;     // uint32 [2^bbits / 32] membership of top bbits
     DevBuf w_pent;       // block-pair tables: rank blocks (w_pwords words), then caller-index blocks of the same shape
     size_t w_pwords = 0;
-    DevBuf w_delmap;     // 2^30 bits: every 15-mer deletion variant of the whitelist
-    DevBuf w_dv;         // the same variants as (variant, sorted-whitelist position) pairs sorted by variant, + directory
+    DevBuf w_delmap;     // four copies of 2^30 bits: every 15-mer deletion variant of the whitelist, each copy in its own bit order
+    DevBuf w_dv;         // the same variants as {variant, rank, caller index, 0} entries grouped by the directory bucket, + directory
     uint32_t w_n = 0;        // 0: no whitelist loaded (set last, after every table of the list is complete)
     uint64_t w_fp = 0;       // fingerprint of the caller's list: the same list again is not rebuilt
     bool w_probe_ready = false;                       // pair tables built (on first use of the probe path)
     bool w_delins_ready = false;                      // deletion-variant maps and entries built (first probe call with max_ed = 2)
     std::vector<uint32_t> w_host_sorted, w_host_order;  // host copy the probe index is built from
-    int w_pbits = 0, w_bbits = 0;
     bool w_identity = false;
     int n16_algo = 0;
     DevBuf n_list;       // uint32 [(8 + 1) * nq] level-2 query list (8 segments) + overflow list

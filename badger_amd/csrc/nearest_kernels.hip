@@ -25,29 +25,120 @@
 namespace {
 
 constexpr uint32_t NONE_IDX = 0xFFFFFFFFu;
+constexpr uint32_t EVEN = 0x55555555u;
 
-struct WlIndex {
-    const uint32_t* sorted;
-    const uint32_t* orig;
-    const uint32_t* prefix;
-    const uint32_t* bitmap;
-    uint32_t n;
-    int pshift;     // 32 - pbits
-    int bshift;     // 32 - bbits
-};
+// a count into a 16-bit output field
+__device__ __forceinline__ uint16_t sat16(uint32_t x) { return (uint16_t)(x > 0xFFFFu ? 0xFFFFu : x); }
 
-__device__ __forceinline__ bool wl_lookup(const WlIndex& ix, uint32_t key, uint32_t& orig)
+// queries: a plain array (qstride 1, recs 0) or the bc_rank field of extraction records (qstride 8 words); a record whose
+// barcode is not 16 ACGT bases (flags byte of the record) has no query and reports "nothing within max_ed"
+__device__ __forceinline__ bool query_usable(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t qi)
 {
-    const uint32_t b = key >> ix.bshift;
-    if (!((ix.bitmap[b >> 5] >> (b & 31u)) & 1u)) return false;
-    const uint32_t p = key >> ix.pshift;
-    const uint32_t lo = ix.prefix[p], hi = ix.prefix[p + 1];
-    for (uint32_t k = lo; k < hi; ++k) {
-        const uint32_t v = ix.sorted[k];
-        if (v == key) { orig = ix.orig[k]; return true; }
-        if (v > key) break;
+    return !recs || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
+}
+
+// wave reductions: six __shfl_xor butterfly steps, every lane gets the result
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_xor(v, m); v = o < v ? o : v; }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { const unsigned long long o = __shfl_xor(v, m); v = o < v ? o : v; }
+    return v;
+}
+
+// Levenshtein distance of two 16-mers: D[16][16] of Myers/Hyyro's bit-vector recurrence, the pattern (bit planes P0 / P1)
+// against the text t.  The vectors stay SPREAD - row i of the pattern at bit 2i, where its 2-bit codes are - and a column's
+// equality vector is two three-input operations on the pattern's two bit planes and the text's code bits (t is a scalar
+// where it is the same in every lane); the addition carries through odd bits that pv keeps set (graph_kernels.hip, dmin3:
+// the same statements).
+// A macro, not a function: a __forceinline__ helper is optimised on its own before it is inlined, and the kernels then
+// need more registers (this statement moved into a function took k_nearest_coop from 74 to 91 VGPRs, k_nearest_scan from 33
+// to 34).  Sets `score` (the caller's) to D[16][16].
+#define ED16_SPREAD(score, P0, P1, t)                                                                                  \
+    do {                                                                                                             \
+        uint32_t pv = 0xFFFFFFFFu, mv = 0u;                                                                          \
+        score = 16u;                                                                                                 \
+        _Pragma("unroll")                                                                                            \
+        for (int j = 0; j < 16; ++j) {                                                                               \
+            const uint32_t m0 = (uint32_t)((int32_t)((t) << (31 - 2 * j)) >> 31);                                    \
+            const uint32_t m1 = (uint32_t)((int32_t)((t) << (30 - 2 * j)) >> 31);                                    \
+            const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);       /* ~(P0 ^ m0) & EVEN */        \
+            const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);         /* t1 & ~(P1 ^ m1) */          \
+            const uint32_t xv = eq | mv;                                                                             \
+            const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE); /* (((eq&pv)+pv)^pv)|eq */ \
+            uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);               /* mv | ~(xh | pv) */          \
+            uint32_t mh = pv & xh;                                                                                   \
+            score += (ph >> 30) & 1u;                                                                                \
+            score -= (mh >> 30) & 1u;                                                                                \
+            ph = (ph << 2) | 1u;                                                                                     \
+            mh = mh << 2;                                                                                            \
+            pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                        /* mh | ~(xv | ph) */          \
+            mv = ph & xv;                                                                                            \
+        }                                                                                                            \
+    } while (0)
+
+// ---- top-k key lists ------------------------------------------------------------
+// The k nearest entries within max_ed (bdg_nearest16_topk): order (ed, caller index), k <= TOPK_MAX, plus how many entries
+// lie within max_ed and - for stage 1's whitelist_ties column - how many share the smallest distance.  An entry is a packed
+// key ed << 32 | caller index (64 bits: every nw a 32-bit index addresses); the keys of distinct entries differ, so "the k
+// smallest keys" is the order above.  Every list holds TOPK_MAX keys whatever k is (registers are indexed by constants
+// only), ascending, KEY_NONE in empty places; the first k are the answer.
+constexpr int TOPK_MAX = 8;
+constexpr unsigned long long KEY_NONE = ~0ull;
+
+// a key into an ascending list: the largest falls off the end (branch-free compare-and-swap down the list)
+__device__ __forceinline__ void topk_insert(unsigned long long (&l)[TOPK_MAX], unsigned long long key)
+{
+#pragma unroll
+    for (int j = 0; j < TOPK_MAX; ++j) {
+        const unsigned long long a = l[j];
+        const bool lt = key < a;
+        l[j] = lt ? key : a;
+        key = lt ? a : key;
     }
-    return false;
+}
+
+__device__ __forceinline__ void topk_clear(unsigned long long (&l)[TOPK_MAX])
+{
+#pragma unroll
+    for (int j = 0; j < TOPK_MAX; ++j) l[j] = KEY_NONE;
+}
+
+// the k smallest keys over the 64 lanes' lists (k wave-uniform): lane j < k returns the j-th, the others KEY_NONE.  Round j
+// takes the wave minimum of the list heads; the one lane holding it pops it (keys are distinct).  The lists are consumed.
+__device__ __forceinline__ unsigned long long wave_topk(unsigned long long (&l)[TOPK_MAX], uint32_t k, int lane)
+{
+    unsigned long long mine = KEY_NONE;
+    for (uint32_t j = 0; j < k; ++j) {
+        const unsigned long long m = wave_min64(l[0]);
+        if (m == KEY_NONE) break;
+        if ((uint32_t)lane == j) mine = m;
+        if (l[0] == m) {
+#pragma unroll
+            for (int t = 0; t < TOPK_MAX - 1; ++t) l[t] = l[t + 1];
+            l[TOPK_MAX - 1] = KEY_NONE;
+        }
+    }
+    return mine;
+}
+
+__device__ __forceinline__ void topk_store(uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, size_t at, unsigned long long key)
+{
+    out_idx[at] = key == KEY_NONE ? NONE_IDX : (uint32_t)key;
+    out_ed[at] = key == KEY_NONE ? (uint8_t)255u : (uint8_t)(key >> 32);
 }
 
 // ---- exhaustive scan -------------------------------------------------------
@@ -67,15 +158,10 @@ void k_nearest_scan(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
   for (uint32_t slot0 = blockIdx.x * 256u; slot0 < nq; slot0 += gridDim.x * 256u) {
     const uint32_t slot = slot0 + threadIdx.x;
     const bool active = slot < nq;
-    // queries: a plain array (qstride 1) or the bc_rank field of extraction records (qstride 8 words; a record whose
-    // barcode is not 16 ACGT bases has no query and reports "nothing within max_ed")
     const uint32_t qi = active ? (qlist ? qlist[slot] : slot) : 0u;
     const uint32_t qq = active ? q[(size_t)qi * qstride] : 0u;
-    const bool usable = !recs || !active || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
-    // The Myers vectors stay SPREAD - row i of the query at bit 2i, where its 2-bit codes are - and a column's equality vector
-    // is two three-input operations on the query's two bit planes and the entry's code bits (scalars: the entry is the same in
-    // every lane); the addition carries through odd bits that pv keeps set (graph_kernels.hip, dmin3: the same statements).
-    constexpr uint32_t EVEN = 0x55555555u;
+    const bool usable = !active || query_usable(q, qstride, recs, qi);
+    // the query is the pattern, each entry (the same in every lane) the text
     const uint32_t P0 = qq & EVEN, P1 = (qq >> 1) & EVEN;
     uint32_t best = 255u, bidx = NONE_IDX, ties = 0u;
     for (uint32_t t0 = 0; t0 < nw; t0 += SCAN_TILE) {
@@ -86,23 +172,8 @@ void k_nearest_scan(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
         for (uint32_t k = 0; k < tn; ++k) {
             const uint32_t t = __builtin_amdgcn_readfirstlane(s_rank[k]);
             const uint32_t o = __builtin_amdgcn_readfirstlane(s_orig[k]);
-            uint32_t pv = 0xFFFFFFFFu, mv = 0u, score = 16u;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const uint32_t m0 = (uint32_t)((int32_t)(t << (31 - 2 * j)) >> 31), m1 = (uint32_t)((int32_t)(t << (30 - 2 * j)) >> 31);
-                const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);             // ~(P0 ^ m0) & EVEN
-                const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);               // t1 & ~(P1 ^ m1)
-                const uint32_t xv = eq | mv;
-                const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);    // (((eq & pv) + pv) ^ pv) | eq
-                uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                     // mv | ~(xh | pv)
-                uint32_t mh = pv & xh;
-                score += (ph >> 30) & 1u;
-                score -= (mh >> 30) & 1u;
-                ph = (ph << 2) | 1u;
-                mh = mh << 2;
-                pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                              // mh | ~(xv | ph)
-                mv = ph & xv;
-            }
+            uint32_t score;
+            ED16_SPREAD(score, P0, P1, t);
             const bool better = score < best, same = score == best;
             bidx = better ? o : ((same && o < bidx) ? o : bidx);
             ties = better ? 1u : (same ? ties + 1u : ties);
@@ -111,12 +182,12 @@ void k_nearest_scan(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
     }
     if (active) {
         if (best > max_ed || !usable) { best = 255u; bidx = NONE_IDX; ties = 0u; }
-        best_idx[qi] = bidx; best_ed[qi] = (uint8_t)best; n_ties[qi] = (uint16_t)(ties > 0xFFFFu ? 0xFFFFu : ties);
+        best_idx[qi] = bidx; best_ed[qi] = (uint8_t)best; n_ties[qi] = sat16(ties);
     }
   }
 }
 
-// ---- wave-cooperative best-hit scan ---------------------------------------------
+// ---- wave-cooperative scan ------------------------------------------------------
 // The exhaustive scan with the roles of query and entry swapped: a query is the same for the whole wave (scalar registers,
 // taken through readfirstlane), each lane evaluates a different whitelist entry (its two bit planes in vector registers), and
 // the wave's answer is a min reduction of the packed key (ed << 32 | caller index) plus a sum of the lane tie counts at that
@@ -137,10 +208,17 @@ constexpr uint32_t COOP_TARGET_ITEMS = 1024;  // work items the plan aims at whe
 constexpr uint32_t COOP_MIN_SLICE = 256;      // entries: a slice gives every lane of the block at least one
 constexpr uint64_t COOP_PARTIALS = 1ull << 21;   // partials the workspace holds at least (8 bytes each)
 
+// Wave-cooperative top-k (algo 3, any max_ed, and the probe path's overflow): k_nearest_coop with a key list per lane and
+// query instead of one best key; its item loop repeats k_nearest_coop's on purpose (moved into a shared __forceinline__
+// function, the loop cost k_nearest_coop 3 VGPRs and 0.7 % of its time).  Fewer queries per work item (a list is 16 registers).  A partial per (query, slice, wave)
+// is k + 1 words: the wave's k smallest keys, then n_within | ties << 32 (ties: entries at the partial's smallest distance,
+// which is key 0's).  Register budget: 96 VGPRs, no scratch (tests/test_nearest_topk.py).
+constexpr int COOP_TOPK_QG = 2;
+
 struct CoopPlan { uint32_t nslices, slice_len; };
 
 // qg: queries per work item (COOP_QG; the top-k kernel's COOP_TOPK_QG); partial_cap counts partials
-__host__ __device__ inline CoopPlan coop_plan(uint32_t nq, uint32_t nw, uint64_t partial_cap, uint32_t qg = COOP_QG)
+__host__ __device__ inline CoopPlan coop_plan(uint32_t nq, uint32_t nw, uint64_t partial_cap, uint32_t qg)
 {
     const uint64_t ngroups = ((uint64_t)nq + qg - 1) / qg;
     uint64_t ns = ngroups ? (COOP_TARGET_ITEMS + ngroups - 1) / ngroups : 1;
@@ -173,12 +251,11 @@ void k_nearest_coop(const uint32_t* __restrict__ q, uint32_t qstride,
     __shared__ uint2 s_ent[COOP_TILE];
     const uint32_t nq = d_nq ? *d_nq : nq_host;
     if (nq == 0) return;
-    const CoopPlan plan = coop_plan(nq, nw, partial_cap);
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_QG);
     if (!coop_plan_fits(plan, nq, partial_cap)) return;
     const uint32_t ngroups = (nq + COOP_QG - 1) / COOP_QG;
     const uint64_t nitems = (uint64_t)ngroups * plan.nslices;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr uint32_t EVEN = 0x55555555u;
     for (uint64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
         const uint32_t g = (uint32_t)(item / plan.nslices), s = (uint32_t)(item % plan.nslices);
         const uint32_t nqg = nq - g * COOP_QG < (uint32_t)COOP_QG ? nq - g * COOP_QG : (uint32_t)COOP_QG;
@@ -207,23 +284,8 @@ void k_nearest_coop(const uint32_t* __restrict__ q, uint32_t qstride,
 #pragma unroll
                 for (int i = 0; i < COOP_QG; ++i) {
                     const uint32_t t = qv[i];
-                    uint32_t pv = 0xFFFFFFFFu, mv = 0u, score = 16u;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        const uint32_t m0 = (uint32_t)((int32_t)(t << (31 - 2 * j)) >> 31), m1 = (uint32_t)((int32_t)(t << (30 - 2 * j)) >> 31);
-                        const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);             // ~(P0 ^ m0) & EVEN
-                        const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);               // t1 & ~(P1 ^ m1)
-                        const uint32_t xv = eq | mv;
-                        const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);    // (((eq & pv) + pv) ^ pv) | eq
-                        uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                     // mv | ~(xh | pv)
-                        uint32_t mh = pv & xh;
-                        score += (ph >> 30) & 1u;
-                        score -= (mh >> 30) & 1u;
-                        ph = (ph << 2) | 1u;
-                        mh = mh << 2;
-                        pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                              // mh | ~(xv | ph)
-                        mv = ph & xv;
-                    }
+                    uint32_t score;
+                    ED16_SPREAD(score, P0, P1, t);
                     const bool better = score < best[i], same = score == best[i];
                     bidx[i] = better ? e.y : ((same && e.y < bidx[i]) ? e.y : bidx[i]);
                     ties[i] = better ? 1u : (same ? ties[i] + 1u : ties[i]);
@@ -231,22 +293,87 @@ void k_nearest_coop(const uint32_t* __restrict__ q, uint32_t qstride,
                 }
             }
         }
-        // per query: wave minimum of (ed << 32 | index) in six butterfly steps, then the tie count at that distance
+        // per query: wave minimum of (ed << 32 | index), then the tie count at that distance
 #pragma unroll
         for (int i = 0; i < COOP_QG; ++i) {
-            unsigned long long key = ((unsigned long long)best[i] << 32) | bidx[i];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) {
-                const unsigned long long o = __shfl_xor(key, m);
-                key = o < key ? o : key;
-            }
+            const unsigned long long key = wave_min64(((unsigned long long)best[i] << 32) | bidx[i]);
             const uint32_t ed = (uint32_t)(key >> 32);
-            uint32_t tc = best[i] == ed ? ties[i] : 0u;
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) tc += __shfl_xor(tc, m);
+            const uint32_t tc = wave_sum(best[i] == ed ? ties[i] : 0u);
             if (lane == 0 && (uint32_t)i < nqg) {
                 const uint64_t at = ((uint64_t)(g * COOP_QG + i) * plan.nslices + s) * 4u + (uint32_t)wv;
-                partials[at] = ((unsigned long long)ed << 48) | ((unsigned long long)(tc > 0xFFFFu ? 0xFFFFu : tc) << 32) | (uint32_t)key;
+                partials[at] = ((unsigned long long)ed << 48) | ((unsigned long long)sat16(tc) << 32) | (uint32_t)key;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256)
+void k_nearest_coop_topk(const uint32_t* __restrict__ q, uint32_t qstride,
+                         const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq,
+                         const uint32_t* __restrict__ wl_sorted, const uint32_t* __restrict__ wl_orig, uint32_t nw,
+                         uint32_t max_ed, uint32_t k, unsigned long long* __restrict__ partials, uint64_t partial_cap)
+{
+    __shared__ uint2 s_ent[COOP_TILE];
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t ngroups = (nq + COOP_TOPK_QG - 1) / COOP_TOPK_QG;
+    const uint64_t nitems = (uint64_t)ngroups * plan.nslices;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (uint64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const uint32_t g = (uint32_t)(item / plan.nslices), s = (uint32_t)(item % plan.nslices);
+        const uint32_t nqg = nq - g * COOP_TOPK_QG < (uint32_t)COOP_TOPK_QG ? nq - g * COOP_TOPK_QG : (uint32_t)COOP_TOPK_QG;
+        uint32_t qv[COOP_TOPK_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+            const uint32_t slot = g * COOP_TOPK_QG + ((uint32_t)i < nqg ? (uint32_t)i : 0u);
+            const uint32_t qi = qlist ? qlist[slot] : slot;
+            qv[i] = __builtin_amdgcn_readfirstlane(q[(size_t)qi * qstride]);
+        }
+        unsigned long long lst[COOP_TOPK_QG][TOPK_MAX];
+        uint32_t cnt[COOP_TOPK_QG], best[COOP_TOPK_QG], ties[COOP_TOPK_QG];
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX; ++j) lst[i][j] = KEY_NONE;
+            cnt[i] = 0u; best[i] = 255u; ties[i] = 0u;
+        }
+        const uint32_t s0 = s * plan.slice_len;
+        const uint32_t s1 = nw - s0 < plan.slice_len ? nw : s0 + plan.slice_len;
+        for (uint32_t t0 = s0; t0 < s1; t0 += COOP_TILE) {
+            const uint32_t tn = s1 - t0 < (uint32_t)COOP_TILE ? s1 - t0 : (uint32_t)COOP_TILE;
+            __syncthreads();
+            for (uint32_t e = threadIdx.x; e < tn; e += 256u) s_ent[e] = make_uint2(wl_sorted[t0 + e], wl_orig[t0 + e]);
+            __syncthreads();
+            for (uint32_t e = threadIdx.x; e < tn; e += 256u) {
+                const uint2 en = s_ent[e];
+                const uint32_t P0 = en.x & EVEN, P1 = (en.x >> 1) & EVEN;
+#pragma unroll
+                for (int i = 0; i < COOP_TOPK_QG; ++i) {
+                    const uint32_t t = qv[i];
+                    uint32_t score;
+                    ED16_SPREAD(score, P0, P1, t);
+                    if (score <= max_ed) {
+                        ++cnt[i];
+                        ties[i] = score < best[i] ? 1u : (score == best[i] ? ties[i] + 1u : ties[i]);
+                        best[i] = score < best[i] ? score : best[i];
+                        const unsigned long long key = ((unsigned long long)score << 32) | en.y;
+                        if (key < lst[i][TOPK_MAX - 1]) topk_insert(lst[i], key);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < COOP_TOPK_QG; ++i) {
+            const uint32_t n = wave_sum(cnt[i]);
+            const uint32_t wb = wave_min(best[i]);
+            const uint32_t tc = wave_sum(best[i] == wb ? ties[i] : 0u);
+            const unsigned long long mine = wave_topk(lst[i], k, lane);
+            if ((uint32_t)i < nqg) {
+                unsigned long long* p = partials + (((uint64_t)(g * COOP_TOPK_QG + i) * plan.nslices + s) * 4u + (uint32_t)wv) * (k + 1u);
+                if ((uint32_t)lane < k) p[lane] = mine;
+                if (lane == 0) p[k] = ((unsigned long long)tc << 32) | n;
             }
         }
     }
@@ -262,7 +389,7 @@ void k_nearest_coop_merge(const uint32_t* __restrict__ q, uint32_t qstride, int 
 {
     const uint32_t nq = d_nq ? *d_nq : nq_host;
     if (nq == 0) return;
-    const CoopPlan plan = coop_plan(nq, nw, partial_cap);
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_QG);
     if (!coop_plan_fits(plan, nq, partial_cap)) return;
     const uint32_t np = plan.nslices * 4u;
     const int lane = threadIdx.x & 63;
@@ -275,21 +402,65 @@ void k_nearest_coop_merge(const uint32_t* __restrict__ q, uint32_t qstride, int 
             if (ed < best) { best = ed; bidx = ix; ties = tc; }
             else if (ed == best) { bidx = ix < bidx ? ix : bidx; ties += tc; }
         }
-        unsigned long long key = ((unsigned long long)best << 32) | bidx;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned long long o = __shfl_xor(key, m);
-            key = o < key ? o : key;
-        }
-        uint32_t tc = best == (uint32_t)(key >> 32) ? ties : 0u;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) tc += __shfl_xor(tc, m);
+        const unsigned long long key = wave_min64(((unsigned long long)best << 32) | bidx);
+        uint32_t tc = wave_sum(best == (uint32_t)(key >> 32) ? ties : 0u);
         if (lane == 0) {
             uint32_t ed = (uint32_t)(key >> 32), ix = (uint32_t)key;
             const uint32_t qi = qlist ? qlist[slot] : slot;
-            const bool usable = !recs || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
+            const bool usable = query_usable(q, qstride, recs, qi);
             if (ed > max_ed || !usable) { ed = 255u; ix = NONE_IDX; tc = 0u; }
-            best_idx[qi] = ix; best_ed[qi] = (uint8_t)ed; n_ties[qi] = (uint16_t)(tc > 0xFFFFu ? 0xFFFFu : tc);
+            best_idx[qi] = ix; best_ed[qi] = (uint8_t)ed; n_ties[qi] = sat16(tc);
+        }
+    }
+}
+
+// one wave per query: every lane merges the partials lane, lane + 64, ... into its list, then the wave's k smallest keys
+// (fixed order, no atomics); unusable records: every slot empty, counts 0
+__global__ __launch_bounds__(256)
+void k_nearest_coop_topk_merge(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
+                               const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq, uint32_t nw,
+                               const unsigned long long* __restrict__ partials, uint64_t partial_cap, uint32_t k,
+                               uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                               uint16_t* __restrict__ n_ties)
+{
+    const uint32_t nq = d_nq ? *d_nq : nq_host;
+    if (nq == 0) return;
+    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
+    if (!coop_plan_fits(plan, nq, partial_cap)) return;
+    const uint32_t np = plan.nslices * 4u;
+    const int lane = threadIdx.x & 63;
+    for (uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6); slot < nq; slot += gridDim.x * 4u) {     // wave-uniform
+        const unsigned long long* base = partials + (uint64_t)slot * np * (k + 1u);
+        unsigned long long lst[TOPK_MAX];
+        topk_clear(lst);
+        uint32_t n = 0u, best = 255u, ties = 0u;
+        for (uint32_t pi = (uint32_t)lane; pi < np; pi += 64u) {
+            const unsigned long long* p = base + (uint64_t)pi * (k + 1u);
+            const unsigned long long c = p[k];
+            n += (uint32_t)c;
+            const unsigned long long k0 = p[0];
+            if (k0 != KEY_NONE) {
+                const uint32_t ed = (uint32_t)(k0 >> 32), tc = (uint32_t)(c >> 32);
+                ties = ed < best ? tc : (ed == best ? ties + tc : ties);
+                best = ed < best ? ed : best;
+            }
+            for (uint32_t j = 0; j < k; ++j) {               // ascending: stop at the first key that cannot enter (KEY_NONE too)
+                const unsigned long long key = p[j];
+                if (key >= lst[TOPK_MAX - 1]) break;
+                topk_insert(lst, key);
+            }
+        }
+        n = wave_sum(n);
+        const uint32_t wb = wave_min(best);
+        const uint32_t tc = wave_sum(best == wb ? ties : 0u);
+        unsigned long long mine = wave_topk(lst, k, lane);
+        const uint32_t qi = qlist ? qlist[slot] : slot;
+        const bool usable = query_usable(q, qstride, recs, qi);
+        if (!usable) mine = KEY_NONE;
+        if ((uint32_t)lane < k) topk_store(out_idx, out_ed, (size_t)qi * k + (uint32_t)lane, mine);
+        if (lane == 0) {
+            n_within[qi] = usable ? sat16(n) : (uint16_t)0u;
+            if (n_ties) n_ties[qi] = usable ? sat16(tc) : (uint16_t)0u;
         }
     }
 }
@@ -316,8 +487,7 @@ struct PairTables {
     // average) never chains, one of a 4.9 M list (75) takes 3 blocks.
     const uint32_t* rank;
     const uint32_t* idx;
-    const uint32_t* delmap;  // 2^30 bits
-    uint32_t nw;
+    const uint32_t* delmap;  // four copies of 2^30 bits (see delmap_index)
 };
 constexpr uint32_t PAIR_BLOCK_ENTRIES = 30;
 
@@ -344,72 +514,48 @@ __device__ __forceinline__ uint32_t hamming16(uint32_t x)
     return __popc((x | (x >> 1)) & 0x55555555u);
 }
 
+// Bucket p of the pair tables for query qq: fn(h, caller index) for every entry h substitutions from the query with
+// within(h) whose canonical table is p.  within() is asked at each entry (the best-hit walk lowers its limit as it finds
+// closer entries).
+template <class Within, class Fn>
+__device__ __forceinline__ void walk_bucket(const PairTables& pt, uint32_t qq, int p, Within within, Fn fn)
+{
+    // the two blocks outside the key: (k, l) = the complement of pair p's (i, j)
+    const int bk = p < 3 ? (p == 0 ? 2 : 1) : 0;
+    const int bl = p < 3 ? (p == 2 ? 2 : 3) : (p == 3 ? 3 : (p == 4 ? 2 : 1));
+    const uint32_t qrest = ((qq >> (8 * bk)) & 0xFFu) | (((qq >> (8 * bl)) & 0xFFu) << 8);
+    uint32_t blk = (uint32_t)p * 65536u + pair_key(qq, p);
+    do {
+        const uint4* rb = reinterpret_cast<const uint4*>(pt.rank + (size_t)blk * 16u);
+        const uint4 q0 = rb[0], q1 = rb[1], q2 = rb[2], q3 = rb[3];          // the whole sector, four independent loads
+        const uint32_t wr[16] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w };
+        const uint32_t cnt = wr[0] & 0xFFu;
+#pragma unroll
+        for (uint32_t u = 0; u < PAIR_BLOCK_ENTRIES; ++u) {
+            const uint32_t e = (wr[1 + (u >> 1)] >> (16 * (u & 1u))) & 0xFFFFu;
+            const uint32_t xr = e ^ qrest;                                     // differences in the two blocks outside the key
+            const uint32_t h = __popc((xr | (xr >> 1)) & 0x5555u);
+            if (u < cnt && within(h)) {
+                const uint32_t x = ((xr & 0xFFu) << (8 * bk)) | ((xr >> 8) << (8 * bl));   // query ^ entry (zero in the key blocks)
+                if (canonical_pair(x) == p) fn(h, pt.idx[(size_t)blk * 32u + u]);
+            }
+        }
+        blk = wr[0] >> 8;
+    } while (blk);
+}
+
 // list of the queries pass 2 must look at: LSH segments of nq slots, one counter (own 128-byte line) per segment; a block
 // reserves its slots with ONE atomic (same-address atomics complete ~11 ns apart, whoever issues them)
 constexpr int LSH = 8;
 constexpr int CTR_N3 = LSH * 32;           // uint32 index of the overflow-list counter
 constexpr size_t NCTR_BYTES = (LSH + 1) * 128;
 
-__global__ __launch_bounds__(256)
-void k_nearest_pairs(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t nq, PairTables pt, uint32_t max_ed,
-                     uint32_t* __restrict__ best_idx, uint8_t* __restrict__ best_ed, uint16_t* __restrict__ n_ties,
-                     uint2* __restrict__ list2, uint32_t* __restrict__ counters)
+// block-wide reservation in this block's list2 segment, then query i's entry if need2 (pass 2 gets the query with its
+// index: one load less on its chain)
+__device__ __forceinline__ void append_pass2(bool need2, uint32_t i, uint32_t qq, uint32_t nq, uint2* __restrict__ list2,
+                                             uint32_t* __restrict__ counters)
 {
     __shared__ uint32_t s_wcnt[4], s_base;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool on = i < nq;
-    bool need2 = false;
-    uint32_t qq = 0;
-    bool usable = on;
-    if (on) {
-        qq = q[(size_t)i * qstride];
-        if (recs) usable = ((q[(size_t)i * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;      // flags byte of the record
-    }
-    if (on && !usable) { best_idx[i] = NONE_IDX; best_ed[i] = 255; n_ties[i] = 0; }
-    if (usable) {
-        uint32_t best = 3u, bidx = NONE_IDX, ties = 0u;
-        auto scan_bucket = [&](int p) {
-            // the two blocks outside the key: (k, l) = the complement of pair p's (i, j)
-            const int bk = p < 3 ? (p == 0 ? 2 : 1) : (p < 5 ? 0 : 0);
-            const int bl = p < 3 ? (p == 2 ? 2 : 3) : (p == 3 ? 3 : (p == 4 ? 2 : 1));
-            const uint32_t qrest = ((qq >> (8 * bk)) & 0xFFu) | (((qq >> (8 * bl)) & 0xFFu) << 8);
-            uint32_t blk = (uint32_t)p * 65536u + pair_key(qq, p);
-            do {
-                const uint4* rb = reinterpret_cast<const uint4*>(pt.rank + (size_t)blk * 16u);
-                const uint4 q0 = rb[0], q1 = rb[1], q2 = rb[2], q3 = rb[3];          // the whole sector, four independent loads
-                const uint32_t wr[16] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w };
-                const uint32_t cnt = wr[0] & 0xFFu;
-#pragma unroll
-                for (uint32_t u = 0; u < PAIR_BLOCK_ENTRIES; ++u) {
-                    const uint32_t e = (wr[1 + (u >> 1)] >> (16 * (u & 1u))) & 0xFFFFu;
-                    const uint32_t xr = e ^ qrest;                                     // differences in the two blocks outside the key
-                    const uint32_t h = __popc((xr | (xr >> 1)) & 0x5555u);
-                    if (u < cnt && h <= 2u && h <= best) {
-                        const uint32_t x = ((xr & 0xFFu) << (8 * bk)) | ((xr >> 8) << (8 * bl));   // query ^ entry (zero in the key blocks)
-                        if (canonical_pair(x) == p) {
-                            const uint32_t wo = pt.idx[(size_t)blk * 32u + u];
-                            if (h < best) { best = h; bidx = wo; ties = 1u; }
-                            else { ties++; bidx = wo < bidx ? wo : bidx; }
-                        }
-                    }
-                }
-                blk = wr[0] >> 8;
-            } while (blk);
-        };
-        scan_bucket(0);
-        if (best != 0u) {                                  // an exact match sits in table (0,1) and nothing can tie with it
-            scan_bucket(5);
-            if (best > 1u) {                               // otherwise all entries within distance 1 have been seen
-#pragma unroll
-                for (int p = 1; p <= 4; ++p) scan_bucket(p);
-            }
-        }
-        if (best > max_ed) { best = 255u; bidx = NONE_IDX; ties = 0u; }
-        best_idx[i] = bidx; best_ed[i] = (uint8_t)(best == 3u ? 255u : best);
-        n_ties[i] = (uint16_t)(ties > 0xFFFFu ? 0xFFFFu : ties);
-        need2 = max_ed >= 2u && (best == 2u || best == 3u || best == 255u);
-    }
-    // block-wide reservation in this block's list segment
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long m = __ballot(need2);
     if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(m);
@@ -423,16 +569,92 @@ void k_nearest_pairs(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
     if (need2) {
         uint32_t at = s_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
         for (int w = 0; w < wv; ++w) at += s_wcnt[w];
-        list2[(size_t)seg * nq + at] = make_uint2(i, qq);                 // pass 2 gets the query with its index: one load less on its chain
+        list2[(size_t)seg * nq + at] = make_uint2(i, qq);
     }
+}
+
+__global__ __launch_bounds__(256)
+void k_nearest_pairs(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t nq, PairTables pt, uint32_t max_ed,
+                     uint32_t* __restrict__ best_idx, uint8_t* __restrict__ best_ed, uint16_t* __restrict__ n_ties,
+                     uint2* __restrict__ list2, uint32_t* __restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool on = i < nq;
+    bool need2 = false;
+    uint32_t qq = 0;
+    bool usable = on;
+    if (on) {
+        qq = q[(size_t)i * qstride];
+        usable = query_usable(q, qstride, recs, i);
+    }
+    if (on && !usable) { best_idx[i] = NONE_IDX; best_ed[i] = 255; n_ties[i] = 0; }
+    if (usable) {
+        uint32_t best = 3u, bidx = NONE_IDX, ties = 0u;
+        const auto within = [&](uint32_t h) { return h <= 2u && h <= best; };     // min(2, best)
+        const auto take = [&](uint32_t h, uint32_t wo) {
+            if (h < best) { best = h; bidx = wo; ties = 1u; }
+            else { ties++; bidx = wo < bidx ? wo : bidx; }
+        };
+        walk_bucket(pt, qq, 0, within, take);
+        if (best != 0u) {                                  // an exact match sits in table (0,1) and nothing can tie with it
+            walk_bucket(pt, qq, 5, within, take);
+            if (best > 1u) {                               // otherwise all entries within distance 1 have been seen
+#pragma unroll
+                for (int p = 1; p <= 4; ++p) walk_bucket(pt, qq, p, within, take);
+            }
+        }
+        if (best > max_ed) { best = 255u; bidx = NONE_IDX; ties = 0u; }
+        best_idx[i] = bidx; best_ed[i] = (uint8_t)(best == 3u ? 255u : best);
+        n_ties[i] = sat16(ties);
+        need2 = max_ed >= 2u && (best == 2u || best == 3u || best == 255u);
+    }
+    append_pass2(need2, i, qq, nq, list2, counters);
+}
+
+// Probe top-k, pass 1: k_nearest_pairs without its early stops - all six tables, every entry within min(max_ed, 2)
+// substitutions (each counted in its canonical table only) - into the lane's key list.  With max_ed = 2 every usable query
+// goes on to pass 2: the entries one deletion + one insertion away are at distance 2 too, whatever pass 1 found.
+__global__ __launch_bounds__(256)
+void k_nearest_pairs_topk(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t nq, PairTables pt, uint32_t max_ed,
+                          uint32_t k, uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                          uint16_t* __restrict__ n_ties, uint2* __restrict__ list2, uint32_t* __restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool on = i < nq;
+    uint32_t qq = 0;
+    bool usable = on;
+    if (on) {
+        qq = q[(size_t)i * qstride];
+        usable = query_usable(q, qstride, recs, i);
+    }
+    unsigned long long lst[TOPK_MAX];
+    topk_clear(lst);
+    uint32_t n = 0u, best = 255u, ties = 0u;
+    if (usable) {
+#pragma unroll 1
+        for (int p = 0; p < 6; ++p)
+            walk_bucket(pt, qq, p, [&](uint32_t h) { return h <= max_ed; }, [&](uint32_t h, uint32_t wo) {
+                ++n;
+                ties = h < best ? 1u : (h == best ? ties + 1u : ties);
+                best = h < best ? h : best;
+                const unsigned long long key = ((unsigned long long)h << 32) | wo;
+                if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
+            });
+    }
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, (size_t)i * k + (uint32_t)j, lst[j]);
+        n_within[i] = sat16(n);
+        if (n_ties) n_ties[i] = sat16(ties);
+    }
+    append_pass2(usable && max_ed >= 2u, i, qq, nq, list2, counters);
 }
 
 __device__ __forceinline__ uint32_t low_mask(int bases) { return bases >= 16 ? 0xFFFFFFFFu : ((1u << (2 * bases)) - 1u); }
 
 // Deletion variants of the whitelist, twice: as a 2^30-bit membership map (the cheap first question) and as (variant, entry)
-// pairs to be sorted by variant (the second: WHICH entries own a variant).  Deleting a base inside a run of equal bases
-// gives the same variant as deleting its left neighbour: only the first of a run is emitted (key 0xFFFFFFFF sorts the
-// others to the end).
+// pairs grouped by variant (the second: WHICH entries own a variant).  Deleting a base inside a run of equal bases gives the
+// same variant as deleting its left neighbour: only the first of a run is emitted.
 // directory over the top 25 of the 30 variant bits (128 MB): 0.35 entries per bucket.  A wave waits for the longest bucket among
 // its lanes' hits, one round trip to memory per entry: with 22 bits (2.8 entries per bucket) k_nearest_delins took 0.120 ms per
 // 1M calls, with 24 bits 0.089, 25 bits 0.084, 27 bits 0.080
@@ -478,12 +700,15 @@ void k_build_delmap(const uint32_t* __restrict__ wl, const uint32_t* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256)
-void k_nearest_delins(const uint2* __restrict__ list2,
-                      uint32_t nq, const uint32_t* counters, const uint32_t* __restrict__ delmap,
-                      const uint4* __restrict__ dv_ent, const uint32_t* __restrict__ dv_dir,
-                      uint32_t* __restrict__ best_idx, uint8_t* __restrict__ best_ed, uint16_t* __restrict__ n_ties,
-                      uint32_t* __restrict__ list3, uint32_t* counters_out)
+// Pass 2 of both probe forms, up to the distinct hits of each query.  For every query of list2 whose four lanes found at
+// most four distinct entries each: State st (fresh per query, in every lane), on_hit(st, v) for each distinct caller index v,
+// in every lane of the query's group, then on_query(st, qi, hits) in the group's lane 0 if there was a hit.  A query with more
+// goes to list3 (the cooperative kernel answers it).
+template <class State, class OnHit, class OnQuery>
+__device__ __forceinline__ void delins_walk(const uint2* __restrict__ list2, uint32_t nq, const uint32_t* counters,
+                                            const uint32_t* __restrict__ delmap, const uint4* __restrict__ dv_ent,
+                                            const uint32_t* __restrict__ dv_dir, uint32_t* __restrict__ list3,
+                                            uint32_t* counters_out, OnHit on_hit, OnQuery on_query)
 {
     uint32_t n2 = 0;                                                              // virtual length: LSH * longest segment
 #pragma unroll
@@ -519,8 +744,9 @@ void k_nearest_delins(const uint2* __restrict__ list2,
         w1 = e1.x != NONE_IDX ? map_word(e1.y) : make_uint2(0u, 0u);
         e2 = fetch(s0 + 2u * ngroups);
         // A variant that occurs in the whitelist: WHICH entries own it (they are the re-insertions of one base into the
-        // variant)?  directory -> the few sorted {variant, rank, caller index} entries of its bucket.  Entries within Hamming
-        // distance 2 were pass 1's.  Equal neighbours give equal variants: the first of a run stands for all.
+        // variant)?  directory -> the few {variant, rank, caller index} entries of its bucket, in no particular order (each
+        // is compared with the variant).  Entries within Hamming distance 2 were pass 1's.  Equal neighbours give equal
+        // variants: the first of a run stands for all.
         uint32_t found[4] = { 0, 0, 0, 0 }; int nf = 0; bool overflow = false;
         auto take = [&](const uint4 en, uint32_t d) __attribute__((always_inline)) {
             if (en.x != d) return;
@@ -568,414 +794,9 @@ void k_nearest_delins(const uint2* __restrict__ list2,
                 for (uint32_t k = lo[t] + DV_AHEAD; k < hi[t]; ++k) take(dv_ent[k], dvar[t]);
             }
         }
-        // merge inside the query's four lanes: distinct hits, lowest caller index
+        // merge inside the query's four lanes: the distinct hits, one at a time in every lane of the group
         const bool any_over = (__ballot(overflow) & gmask) != 0;
-        uint32_t add = 0, midx = NONE_IDX;
-        int pending = nf;
-        while (true) {
-            const unsigned long long bal_all = __ballot(pending > 0);
-            if (!bal_all) break;
-            const unsigned long long bal = bal_all & gmask;
-            const int src = bal ? __builtin_ctzll(bal) : lane;
-            const uint32_t v = __shfl(found[0], src);
-            if (bal) {
-                ++add; midx = v < midx ? v : midx;
-                const bool h0 = pending > 0 && found[0] == v, h1 = pending > 1 && found[1] == v;
-                const bool h2 = pending > 2 && found[2] == v, h3 = pending > 3 && found[3] == v;
-                if (h0) { found[0] = found[1]; found[1] = found[2]; found[2] = found[3]; }
-                else if (h1) { found[1] = found[2]; found[2] = found[3]; }
-                else if (h2) { found[2] = found[3]; }
-                if (h0 || h1 || h2 || h3) --pending;
-            }
-        }
-        if (on && sub == 0) {
-            if (any_over) list3[atomicAdd(&counters_out[CTR_N3], 1u)] = qi;
-            else if (add) {
-                const uint32_t cur_ed = best_ed[qi];
-                uint32_t t = add, bi = midx;
-                if (cur_ed == 2u) { t += n_ties[qi]; const uint32_t o2 = best_idx[qi]; bi = o2 < bi ? o2 : bi; }
-                best_idx[qi] = bi; best_ed[qi] = 2; n_ties[qi] = (uint16_t)(t > 0xFFFFu ? 0xFFFFu : t);
-            }
-        }
-    }
-}
-
-// ---- top-k ----------------------------------------------------------------------
-// The k nearest entries within max_ed (bdg_nearest16_topk): order (ed, caller index), k <= TOPK_MAX, plus how many entries
-// lie within max_ed and - for stage 1's whitelist_ties column - how many share the smallest distance.  An entry is a packed
-// key ed << 32 | caller index (64 bits: every nw a 32-bit index addresses); the keys of distinct entries differ, so "the k
-// smallest keys" is the order above.  Every list holds TOPK_MAX keys whatever k is (registers are indexed by constants
-// only), ascending, KEY_NONE in empty places; the first k are the answer.
-constexpr int TOPK_MAX = 8;
-constexpr unsigned long long KEY_NONE = ~0ull;
-
-// a key into an ascending list: the largest falls off the end (branch-free compare-and-swap down the list)
-__device__ __forceinline__ void topk_insert(unsigned long long (&l)[TOPK_MAX], unsigned long long key)
-{
-#pragma unroll
-    for (int j = 0; j < TOPK_MAX; ++j) {
-        const unsigned long long a = l[j];
-        const bool lt = key < a;
-        l[j] = lt ? key : a;
-        key = lt ? a : key;
-    }
-}
-
-// the k smallest keys over the 64 lanes' lists (k wave-uniform): lane j < k returns the j-th, the others KEY_NONE.  Round j
-// takes the wave minimum of the list heads; the one lane holding it pops it (keys are distinct).  The lists are consumed.
-__device__ __forceinline__ unsigned long long wave_topk(unsigned long long (&l)[TOPK_MAX], uint32_t k, int lane)
-{
-    unsigned long long mine = KEY_NONE;
-    for (uint32_t j = 0; j < k; ++j) {
-        unsigned long long m = l[0];
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const unsigned long long o = __shfl_xor(m, s);
-            m = o < m ? o : m;
-        }
-        if (m == KEY_NONE) break;
-        if ((uint32_t)lane == j) mine = m;
-        if (l[0] == m) {
-#pragma unroll
-            for (int t = 0; t < TOPK_MAX - 1; ++t) l[t] = l[t + 1];
-            l[TOPK_MAX - 1] = KEY_NONE;
-        }
-    }
-    return mine;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_min(uint32_t v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_xor(v, m); v = o < v ? o : v; }
-    return v;
-}
-
-// Wave-cooperative top-k (algo 3, any max_ed, and the probe path's overflow): k_nearest_coop with a key list per lane and
-// query instead of one best key.  Fewer queries per work item (a list is 16 registers).  A partial per (query, slice, wave)
-// is k + 1 words: the wave's k smallest keys, then n_within | ties << 32 (ties: entries at the partial's smallest distance,
-// which is key 0's).  Register budget: 96 VGPRs, no scratch (tests/test_nearest_topk.py).
-constexpr int COOP_TOPK_QG = 2;
-
-__global__ __launch_bounds__(256)
-void k_nearest_coop_topk(const uint32_t* __restrict__ q, uint32_t qstride,
-                         const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq,
-                         const uint32_t* __restrict__ wl_sorted, const uint32_t* __restrict__ wl_orig, uint32_t nw,
-                         uint32_t max_ed, uint32_t k, unsigned long long* __restrict__ partials, uint64_t partial_cap)
-{
-    __shared__ uint2 s_ent[COOP_TILE];
-    const uint32_t nq = d_nq ? *d_nq : nq_host;
-    if (nq == 0) return;
-    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
-    if (!coop_plan_fits(plan, nq, partial_cap)) return;
-    const uint32_t ngroups = (nq + COOP_TOPK_QG - 1) / COOP_TOPK_QG;
-    const uint64_t nitems = (uint64_t)ngroups * plan.nslices;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    constexpr uint32_t EVEN = 0x55555555u;
-    for (uint64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const uint32_t g = (uint32_t)(item / plan.nslices), s = (uint32_t)(item % plan.nslices);
-        const uint32_t nqg = nq - g * COOP_TOPK_QG < (uint32_t)COOP_TOPK_QG ? nq - g * COOP_TOPK_QG : (uint32_t)COOP_TOPK_QG;
-        uint32_t qv[COOP_TOPK_QG];
-#pragma unroll
-        for (int i = 0; i < COOP_TOPK_QG; ++i) {
-            const uint32_t slot = g * COOP_TOPK_QG + ((uint32_t)i < nqg ? (uint32_t)i : 0u);
-            const uint32_t qi = qlist ? qlist[slot] : slot;
-            qv[i] = __builtin_amdgcn_readfirstlane(q[(size_t)qi * qstride]);
-        }
-        unsigned long long lst[COOP_TOPK_QG][TOPK_MAX];
-        uint32_t cnt[COOP_TOPK_QG], best[COOP_TOPK_QG], ties[COOP_TOPK_QG];
-#pragma unroll
-        for (int i = 0; i < COOP_TOPK_QG; ++i) {
-#pragma unroll
-            for (int j = 0; j < TOPK_MAX; ++j) lst[i][j] = KEY_NONE;
-            cnt[i] = 0u; best[i] = 255u; ties[i] = 0u;
-        }
-        const uint32_t s0 = s * plan.slice_len;
-        const uint32_t s1 = nw - s0 < plan.slice_len ? nw : s0 + plan.slice_len;
-        for (uint32_t t0 = s0; t0 < s1; t0 += COOP_TILE) {
-            const uint32_t tn = s1 - t0 < (uint32_t)COOP_TILE ? s1 - t0 : (uint32_t)COOP_TILE;
-            __syncthreads();
-            for (uint32_t e = threadIdx.x; e < tn; e += 256u) s_ent[e] = make_uint2(wl_sorted[t0 + e], wl_orig[t0 + e]);
-            __syncthreads();
-            for (uint32_t e = threadIdx.x; e < tn; e += 256u) {
-                const uint2 en = s_ent[e];
-                const uint32_t P0 = en.x & EVEN, P1 = (en.x >> 1) & EVEN;
-#pragma unroll
-                for (int i = 0; i < COOP_TOPK_QG; ++i) {
-                    const uint32_t t = qv[i];
-                    uint32_t pv = 0xFFFFFFFFu, mv = 0u, score = 16u;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        const uint32_t m0 = (uint32_t)((int32_t)(t << (31 - 2 * j)) >> 31), m1 = (uint32_t)((int32_t)(t << (30 - 2 * j)) >> 31);
-                        const uint32_t t1 = __builtin_amdgcn_bitop3_b32(P0, m0, EVEN, 0x82);             // ~(P0 ^ m0) & EVEN
-                        const uint32_t eq = __builtin_amdgcn_bitop3_b32(t1, P1, m1, 0x90);               // t1 & ~(P1 ^ m1)
-                        const uint32_t xv = eq | mv;
-                        const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);    // (((eq & pv) + pv) ^ pv) | eq
-                        uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                     // mv | ~(xh | pv)
-                        uint32_t mh = pv & xh;
-                        score += (ph >> 30) & 1u;
-                        score -= (mh >> 30) & 1u;
-                        ph = (ph << 2) | 1u;
-                        mh = mh << 2;
-                        pv = __builtin_amdgcn_bitop3_b32(mh, xv, ph, 0xF1);                              // mh | ~(xv | ph)
-                        mv = ph & xv;
-                    }
-                    if (score <= max_ed) {
-                        ++cnt[i];
-                        ties[i] = score < best[i] ? 1u : (score == best[i] ? ties[i] + 1u : ties[i]);
-                        best[i] = score < best[i] ? score : best[i];
-                        const unsigned long long key = ((unsigned long long)score << 32) | en.y;
-                        if (key < lst[i][TOPK_MAX - 1]) topk_insert(lst[i], key);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < COOP_TOPK_QG; ++i) {
-            const uint32_t n = wave_sum(cnt[i]);
-            const uint32_t wb = wave_min(best[i]);
-            const uint32_t tc = wave_sum(best[i] == wb ? ties[i] : 0u);
-            const unsigned long long mine = wave_topk(lst[i], k, lane);
-            if ((uint32_t)i < nqg) {
-                unsigned long long* p = partials + (((uint64_t)(g * COOP_TOPK_QG + i) * plan.nslices + s) * 4u + (uint32_t)wv) * (k + 1u);
-                if ((uint32_t)lane < k) p[lane] = mine;
-                if (lane == 0) p[k] = ((unsigned long long)tc << 32) | n;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void topk_store(uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, size_t at, unsigned long long key)
-{
-    out_idx[at] = key == KEY_NONE ? NONE_IDX : (uint32_t)key;
-    out_ed[at] = key == KEY_NONE ? (uint8_t)255u : (uint8_t)(key >> 32);
-}
-
-// one wave per query: every lane merges the partials lane, lane + 64, ... into its list, then the wave's k smallest keys
-// (fixed order, no atomics); unusable records: every slot empty, counts 0
-__global__ __launch_bounds__(256)
-void k_nearest_coop_topk_merge(const uint32_t* __restrict__ q, uint32_t qstride, int recs,
-                               const uint32_t* __restrict__ qlist, uint32_t nq_host, const uint32_t* __restrict__ d_nq, uint32_t nw,
-                               const unsigned long long* __restrict__ partials, uint64_t partial_cap, uint32_t k,
-                               uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
-                               uint16_t* __restrict__ n_ties)
-{
-    const uint32_t nq = d_nq ? *d_nq : nq_host;
-    if (nq == 0) return;
-    const CoopPlan plan = coop_plan(nq, nw, partial_cap, COOP_TOPK_QG);
-    if (!coop_plan_fits(plan, nq, partial_cap)) return;
-    const uint32_t np = plan.nslices * 4u;
-    const int lane = threadIdx.x & 63;
-    for (uint32_t slot = blockIdx.x * 4u + (threadIdx.x >> 6); slot < nq; slot += gridDim.x * 4u) {     // wave-uniform
-        const unsigned long long* base = partials + (uint64_t)slot * np * (k + 1u);
-        unsigned long long lst[TOPK_MAX];
-#pragma unroll
-        for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
-        uint32_t n = 0u, best = 255u, ties = 0u;
-        for (uint32_t pi = (uint32_t)lane; pi < np; pi += 64u) {
-            const unsigned long long* p = base + (uint64_t)pi * (k + 1u);
-            const unsigned long long c = p[k];
-            n += (uint32_t)c;
-            const unsigned long long k0 = p[0];
-            if (k0 != KEY_NONE) {
-                const uint32_t ed = (uint32_t)(k0 >> 32), tc = (uint32_t)(c >> 32);
-                ties = ed < best ? tc : (ed == best ? ties + tc : ties);
-                best = ed < best ? ed : best;
-            }
-            for (uint32_t j = 0; j < k; ++j) {               // ascending: stop at the first key that cannot enter (KEY_NONE too)
-                const unsigned long long key = p[j];
-                if (key >= lst[TOPK_MAX - 1]) break;
-                topk_insert(lst, key);
-            }
-        }
-        n = wave_sum(n);
-        const uint32_t wb = wave_min(best);
-        const uint32_t tc = wave_sum(best == wb ? ties : 0u);
-        unsigned long long mine = wave_topk(lst, k, lane);
-        const uint32_t qi = qlist ? qlist[slot] : slot;
-        const bool usable = !recs || ((q[(size_t)qi * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
-        if (!usable) mine = KEY_NONE;
-        if ((uint32_t)lane < k) topk_store(out_idx, out_ed, (size_t)qi * k + (uint32_t)lane, mine);
-        if (lane == 0) {
-            n_within[qi] = (uint16_t)(!usable ? 0u : (n > 0xFFFFu ? 0xFFFFu : n));
-            if (n_ties) n_ties[qi] = (uint16_t)(!usable ? 0u : (tc > 0xFFFFu ? 0xFFFFu : tc));
-        }
-    }
-}
-
-// Probe top-k, pass 1: k_nearest_pairs without its early stops - all six tables, every entry within min(max_ed, 2)
-// substitutions (each counted in its canonical table only) - into the lane's key list.  With max_ed = 2 every usable query
-// goes on to pass 2: the entries one deletion + one insertion away are at distance 2 too, whatever pass 1 found.
-__global__ __launch_bounds__(256)
-void k_nearest_pairs_topk(const uint32_t* __restrict__ q, uint32_t qstride, int recs, uint32_t nq, PairTables pt, uint32_t max_ed,
-                          uint32_t k, uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
-                          uint16_t* __restrict__ n_ties, uint2* __restrict__ list2, uint32_t* __restrict__ counters)
-{
-    __shared__ uint32_t s_wcnt[4], s_base;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool on = i < nq;
-    uint32_t qq = 0;
-    bool usable = on;
-    if (on) {
-        qq = q[(size_t)i * qstride];
-        if (recs) usable = ((q[(size_t)i * qstride + 1] >> 24) & BDG_FLAG_RANK_OK) != 0;
-    }
-    unsigned long long lst[TOPK_MAX];
-#pragma unroll
-    for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
-    uint32_t n = 0u, best = 255u, ties = 0u;
-    if (usable) {
-#pragma unroll 1
-        for (int p = 0; p < 6; ++p) {
-            const int bk = p < 3 ? (p == 0 ? 2 : 1) : 0;
-            const int bl = p < 3 ? (p == 2 ? 2 : 3) : (p == 3 ? 3 : (p == 4 ? 2 : 1));
-            const uint32_t qrest = ((qq >> (8 * bk)) & 0xFFu) | (((qq >> (8 * bl)) & 0xFFu) << 8);
-            uint32_t blk = (uint32_t)p * 65536u + pair_key(qq, p);
-            do {
-                const uint4* rb = reinterpret_cast<const uint4*>(pt.rank + (size_t)blk * 16u);
-                const uint4 q0 = rb[0], q1 = rb[1], q2 = rb[2], q3 = rb[3];
-                const uint32_t wr[16] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w };
-                const uint32_t cnt = wr[0] & 0xFFu;
-#pragma unroll
-                for (uint32_t u = 0; u < PAIR_BLOCK_ENTRIES; ++u) {
-                    const uint32_t e = (wr[1 + (u >> 1)] >> (16 * (u & 1u))) & 0xFFFFu;
-                    const uint32_t xr = e ^ qrest;
-                    const uint32_t h = __popc((xr | (xr >> 1)) & 0x5555u);
-                    if (u < cnt && h <= max_ed) {
-                        const uint32_t x = ((xr & 0xFFu) << (8 * bk)) | ((xr >> 8) << (8 * bl));
-                        if (canonical_pair(x) == p) {
-                            const uint32_t wo = pt.idx[(size_t)blk * 32u + u];
-                            ++n;
-                            ties = h < best ? 1u : (h == best ? ties + 1u : ties);
-                            best = h < best ? h : best;
-                            const unsigned long long key = ((unsigned long long)h << 32) | wo;
-                            if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
-                        }
-                    }
-                }
-                blk = wr[0] >> 8;
-            } while (blk);
-        }
-    }
-    if (on) {
-#pragma unroll
-        for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, (size_t)i * k + (uint32_t)j, lst[j]);
-        n_within[i] = (uint16_t)(n > 0xFFFFu ? 0xFFFFu : n);
-        if (n_ties) n_ties[i] = (uint16_t)(ties > 0xFFFFu ? 0xFFFFu : ties);
-    }
-    const bool need2 = usable && max_ed >= 2u;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(need2);
-    if (lane == 0) s_wcnt[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    const uint32_t seg = blockIdx.x % LSH;
-    if (threadIdx.x == 0) {
-        const uint32_t tot = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        s_base = tot ? atomicAdd(&counters[seg * 32], tot) : 0u;
-    }
-    __syncthreads();
-    if (need2) {
-        uint32_t at = s_base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wv; ++w) at += s_wcnt[w];
-        list2[(size_t)seg * nq + at] = make_uint2(i, qq);
-    }
-}
-
-// Probe top-k, pass 2: k_nearest_delins's look-ups and overflow rule unchanged; the distinct entries a query's four lanes
-// found (all at distance 2, none of them pass 1's: those are within Hamming distance 2 and skipped) are merged into the k
-// slots pass 1 wrote, and added to its counts.
-__global__ __launch_bounds__(256)
-void k_nearest_delins_topk(const uint2* __restrict__ list2,
-                           uint32_t nq, const uint32_t* counters, const uint32_t* __restrict__ delmap,
-                           const uint4* __restrict__ dv_ent, const uint32_t* __restrict__ dv_dir, uint32_t k,
-                           uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
-                           uint16_t* __restrict__ n_ties, uint32_t* __restrict__ list3, uint32_t* counters_out)
-{
-    uint32_t n2 = 0;
-#pragma unroll
-    for (int s = 0; s < LSH; ++s) { const uint32_t c = counters[s * 32]; n2 = c > n2 ? c : n2; }
-    n2 *= LSH;
-    const int lane = threadIdx.x & 63, sub = lane & 3, grp = lane >> 2;
-    const uint32_t wave_slot0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 16u;
-    const uint32_t ngroups = gridDim.x * 64u;
-    const unsigned long long gmask = 0xFull << (4 * grp);
-    const uint32_t seg = (wave_slot0 + (uint32_t)grp) % LSH;
-    const uint32_t seg_cnt = counters[seg * 32];
-    const uint2* seg_list = list2 + (size_t)seg * nq;
-    auto fetch = [&](uint32_t s0) -> uint2 {
-        const uint32_t s = s0 + (uint32_t)grp;
-        return (s < n2 && s / LSH < seg_cnt) ? seg_list[s / LSH] : make_uint2(NONE_IDX, 0u);
-    };
-    auto variant = [&](uint32_t qq, int t) -> uint32_t {
-        const uint32_t lm = low_mask(4 * sub + t);
-        return ((qq & lm) | ((qq >> 2) & ~lm)) & 0x3FFFFFFFu;
-    };
-    const uint2* const my_map = reinterpret_cast<const uint2*>(delmap + (size_t)sub * DELMAP_WORDS);
-    auto map_word = [&](uint32_t qq) -> uint2 { return my_map[delmap_index(variant(qq, 0), sub) >> 6]; };
-    uint2 e1 = fetch(wave_slot0), e2 = fetch(wave_slot0 + ngroups);
-    uint2 w1 = e1.x != NONE_IDX ? map_word(e1.y) : make_uint2(0u, 0u);
-    for (uint32_t s0 = wave_slot0; s0 < n2; s0 += ngroups) {
-        const uint32_t qi = e1.x, qq = e1.y;
-        const unsigned long long word = ((unsigned long long)w1.y << 32) | w1.x;
-        const bool on = qi != NONE_IDX;
-        e1 = e2;
-        w1 = e1.x != NONE_IDX ? map_word(e1.y) : make_uint2(0u, 0u);
-        e2 = fetch(s0 + 2u * ngroups);
-        uint32_t found[4] = { 0, 0, 0, 0 }; int nf = 0; bool overflow = false;
-        auto take = [&](const uint4 en, uint32_t d) __attribute__((always_inline)) {
-            if (en.x != d) return;
-            if (hamming16(en.y ^ qq) <= 2u) return;
-            const uint32_t oo = en.z;
-            const bool dup = (nf > 0 && found[0] == oo) || (nf > 1 && found[1] == oo) ||
-                             (nf > 2 && found[2] == oo) || (nf > 3 && found[3] == oo);
-            if (!dup) {
-                if (nf < 4) { found[0] = nf == 0 ? oo : found[0]; found[1] = nf == 1 ? oo : found[1];
-                              found[2] = nf == 2 ? oo : found[2]; found[3] = nf == 3 ? oo : found[3]; ++nf; }
-                else overflow = true;
-            }
-        };
-        uint32_t dvar[4]; bool hit[4]; bool any_hit = false;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int i = 4 * sub + t;
-            dvar[t] = variant(qq, t);
-            const bool dup_del = i > 0 && (((qq >> (2 * i)) ^ (qq >> (2 * i - 2))) & 3u) == 0u;
-            hit[t] = on && !dup_del && ((word >> (delmap_index(dvar[t], sub) & 63u)) & 1ull);
-            any_hit = any_hit || hit[t];
-        }
-        if (__ballot(any_hit)) {
-            constexpr int DV_AHEAD = 3;
-            uint32_t lo[4], hi[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const uint32_t b = hit[t] ? (dvar[t] >> DV_DIR_SHIFT) : 0u;
-                lo[t] = dv_dir[b]; hi[t] = dv_dir[b + 1];
-                if (!hit[t]) hi[t] = lo[t] = 0u;
-            }
-            uint4 en[4][DV_AHEAD];
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int e = 0; e < DV_AHEAD; ++e) en[t][e] = dv_ent[lo[t] + (uint32_t)e < hi[t] ? lo[t] + (uint32_t)e : 0u];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-#pragma unroll
-                for (int e = 0; e < DV_AHEAD; ++e) if (lo[t] + (uint32_t)e < hi[t]) take(en[t][e], dvar[t]);
-                for (uint32_t x = lo[t] + DV_AHEAD; x < hi[t]; ++x) take(dv_ent[x], dvar[t]);
-            }
-        }
-        // the distinct hits of the query's four lanes, one at a time in every lane of the group, into a fresh key list
-        const bool any_over = (__ballot(overflow) & gmask) != 0;
-        unsigned long long lst[TOPK_MAX];
-#pragma unroll
-        for (int j = 0; j < TOPK_MAX; ++j) lst[j] = KEY_NONE;
+        State st;
         uint32_t add = 0;
         int pending = nf;
         while (true) {
@@ -986,8 +807,7 @@ void k_nearest_delins_topk(const uint2* __restrict__ list2,
             const uint32_t v = __shfl(found[0], src);
             if (bal) {
                 ++add;
-                const unsigned long long key = (2ull << 32) | v;
-                if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
+                on_hit(st, v);
                 const bool h0 = pending > 0 && found[0] == v, h1 = pending > 1 && found[1] == v;
                 const bool h2 = pending > 2 && found[2] == v, h3 = pending > 3 && found[3] == v;
                 if (h0) { found[0] = found[1]; found[1] = found[2]; found[2] = found[3]; }
@@ -998,27 +818,68 @@ void k_nearest_delins_topk(const uint2* __restrict__ list2,
         }
         if (on && sub == 0) {
             if (any_over) list3[atomicAdd(&counters_out[CTR_N3], 1u)] = qi;
-            else if (add) {
-                const size_t at = (size_t)qi * k;
-                const uint32_t ed0 = out_ed[at];
-#pragma unroll
-                for (int j = 0; j < TOPK_MAX; ++j) {
-                    if ((uint32_t)j < k && out_ed[at + j] != 255u) {
-                        const unsigned long long key = ((unsigned long long)out_ed[at + j] << 32) | out_idx[at + j];
-                        if (key < lst[TOPK_MAX - 1]) topk_insert(lst, key);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, at + j, lst[j]);
-                const uint32_t n = n_within[qi] + add;
-                n_within[qi] = (uint16_t)(n > 0xFFFFu ? 0xFFFFu : n);
-                if (n_ties && ed0 >= 2u) {
-                    const uint32_t t = (ed0 == 2u ? n_ties[qi] : 0u) + add;
-                    n_ties[qi] = (uint16_t)(t > 0xFFFFu ? 0xFFFFu : t);
-                }
-            }
+            else if (add) on_query(st, qi, add);
         }
     }
+}
+
+// best hit: the lowest caller index among the hits, merged with pass 1's answer if that is at distance 2 too
+struct DelinsBest {
+    uint32_t midx = NONE_IDX;
+};
+
+__global__ __launch_bounds__(256)
+void k_nearest_delins(const uint2* __restrict__ list2,
+                      uint32_t nq, const uint32_t* counters, const uint32_t* __restrict__ delmap,
+                      const uint4* __restrict__ dv_ent, const uint32_t* __restrict__ dv_dir,
+                      uint32_t* __restrict__ best_idx, uint8_t* __restrict__ best_ed, uint16_t* __restrict__ n_ties,
+                      uint32_t* __restrict__ list3, uint32_t* counters_out)
+{
+    delins_walk<DelinsBest>(list2, nq, counters, delmap, dv_ent, dv_dir, list3, counters_out,
+        [&](DelinsBest& st, uint32_t v) { st.midx = v < st.midx ? v : st.midx; },
+        [&](DelinsBest& st, uint32_t qi, uint32_t add) {
+            const uint32_t cur_ed = best_ed[qi];
+            uint32_t t = add, bi = st.midx;
+            if (cur_ed == 2u) { t += n_ties[qi]; const uint32_t o2 = best_idx[qi]; bi = o2 < bi ? o2 : bi; }
+            best_idx[qi] = bi; best_ed[qi] = 2; n_ties[qi] = sat16(t);
+        });
+}
+
+// Probe top-k, pass 2: k_nearest_delins's look-ups and overflow rule unchanged; the distinct entries a query's four lanes
+// found (all at distance 2, none of them pass 1's: those are within Hamming distance 2 and skipped) go into a fresh key
+// list, are merged with the k slots pass 1 wrote, and added to its counts.
+struct DelinsTopk {
+    unsigned long long lst[TOPK_MAX];
+    __device__ __forceinline__ DelinsTopk() { topk_clear(lst); }
+};
+
+__global__ __launch_bounds__(256)
+void k_nearest_delins_topk(const uint2* __restrict__ list2,
+                           uint32_t nq, const uint32_t* counters, const uint32_t* __restrict__ delmap,
+                           const uint4* __restrict__ dv_ent, const uint32_t* __restrict__ dv_dir, uint32_t k,
+                           uint32_t* __restrict__ out_idx, uint8_t* __restrict__ out_ed, uint16_t* __restrict__ n_within,
+                           uint16_t* __restrict__ n_ties, uint32_t* __restrict__ list3, uint32_t* counters_out)
+{
+    delins_walk<DelinsTopk>(list2, nq, counters, delmap, dv_ent, dv_dir, list3, counters_out,
+        [&](DelinsTopk& st, uint32_t v) {
+            const unsigned long long key = (2ull << 32) | v;
+            if (key < st.lst[TOPK_MAX - 1]) topk_insert(st.lst, key);
+        },
+        [&](DelinsTopk& st, uint32_t qi, uint32_t add) {
+            const size_t at = (size_t)qi * k;
+            const uint32_t ed0 = out_ed[at];
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX; ++j) {
+                if ((uint32_t)j < k && out_ed[at + j] != 255u) {
+                    const unsigned long long key = ((unsigned long long)out_ed[at + j] << 32) | out_idx[at + j];
+                    if (key < st.lst[TOPK_MAX - 1]) topk_insert(st.lst, key);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < TOPK_MAX; ++j) if ((uint32_t)j < k) topk_store(out_idx, out_ed, at + j, st.lst[j]);
+            n_within[qi] = sat16(n_within[qi] + add);
+            if (n_ties && ed0 >= 2u) n_ties[qi] = sat16((ed0 == 2u ? n_ties[qi] : 0u) + add);
+        });
 }
 
 }  // namespace
@@ -1055,27 +916,12 @@ int bdg_whitelist_load_impl(bdg_ctx* ctx, const uint32_t* wl, uint32_t nw)
     for (uint32_t i = 0; i < nw; ++i) srt[i] = wl[order[i]];
     for (uint32_t i = 1; i < nw; ++i)
         if (srt[i] == srt[i - 1]) return bdg_fail(ctx, BDG_E_ARG, "whitelist entries must be distinct");
-    int pbits = 8;
-    while (pbits < 20 && (1u << pbits) < nw) ++pbits;
-    const int bbits = pbits + 4 > 24 ? 24 : pbits + 4;
-    std::vector<uint32_t> prefix((size_t(1) << pbits) + 1, 0u), bitmap(size_t(1) << (bbits - 5), 0u);
-    for (uint32_t i = 0; i < nw; ++i) {
-        prefix[(srt[i] >> (32 - pbits)) + 1]++;
-        const uint32_t b = srt[i] >> (32 - bbits);
-        bitmap[b >> 5] |= 1u << (b & 31u);
-    }
-    for (size_t p = 0; p < (size_t(1) << pbits); ++p) prefix[p + 1] += prefix[p];
     int rc;
     if ((rc = bdg_reserve(ctx, ctx->w_sorted, sizeof(uint32_t) * nw))) return rc;
     if ((rc = bdg_reserve(ctx, ctx->w_orig, sizeof(uint32_t) * nw))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->w_prefix, sizeof(uint32_t) * prefix.size()))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->w_bitmap, sizeof(uint32_t) * bitmap.size()))) return rc;
     BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     BDG_HIP_TRY(ctx, hipMemcpy(ctx->w_sorted.p, srt.data(), sizeof(uint32_t) * nw, hipMemcpyHostToDevice));
     BDG_HIP_TRY(ctx, hipMemcpy(ctx->w_orig.p, order.data(), sizeof(uint32_t) * nw, hipMemcpyHostToDevice));
-    BDG_HIP_TRY(ctx, hipMemcpy(ctx->w_prefix.p, prefix.data(), sizeof(uint32_t) * prefix.size(), hipMemcpyHostToDevice));
-    BDG_HIP_TRY(ctx, hipMemcpy(ctx->w_bitmap.p, bitmap.data(), sizeof(uint32_t) * bitmap.size(), hipMemcpyHostToDevice));
-    ctx->w_pbits = pbits; ctx->w_bbits = bbits;
     ctx->w_host_sorted.swap(srt);
     ctx->w_host_order.swap(order);
     ctx->w_n = nw; ctx->w_fp = fp;            // the scan path is usable from here; the probe index is built on first use
@@ -1172,32 +1018,75 @@ constexpr uint64_t SCAN_PAIR_EVALS_MAX = 4000000000ull;
 constexpr uint32_t COOP_NQ_MAX = 65536;
 
 // The cooperative kernel and its merge for a query list (qlist: indices into q, or NULL) whose length is nq_host or, if
-// d_nq is given, *d_nq <= nq_cap (known on the device only).
+// d_nq is given, *d_nq <= nq_cap (known on the device only).  k = 0: best hit (d_idx / d_ed / d_n_ties as
+// bdg_nearest16_launch's, d_n_within unused); k >= 1: top-k (as bdg_nearest16_topk_launch's), a partial takes k + 1 words.
 static int launch_coop(bdg_ctx* ctx, hipStream_t st, const uint32_t* d_q, uint32_t qstride, int recs, const uint32_t* qlist,
-                       uint32_t nq_host, const uint32_t* d_nq, uint32_t nq_cap, uint32_t max_ed,
-                       uint32_t* d_best_idx, uint8_t* d_best_ed, uint16_t* d_n_ties)
+                       uint32_t nq_host, const uint32_t* d_nq, uint32_t nq_cap, uint32_t max_ed, uint32_t k,
+                       uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within, uint16_t* d_n_ties)
 {
+    const uint32_t qg = k ? COOP_TOPK_QG : COOP_QG;            // queries per work item
+    const uint32_t words = k ? k + 1u : 1u;                     // words per partial
     // room for at least one slice of every query of the largest list possible (coop_plan never plans more than there is)
-    const uint64_t groups = ((uint64_t)nq_cap + COOP_QG - 1) / COOP_QG;
-    const uint64_t cap = std::max<uint64_t>(COOP_PARTIALS, groups * COOP_QG * 4u);
+    const uint64_t groups = ((uint64_t)nq_cap + qg - 1) / qg;
+    const uint64_t cap = std::max<uint64_t>(COOP_PARTIALS, groups * qg * 4u * words);      // words
     int rc;
     if ((rc = bdg_reserve(ctx, ctx->n_coop, sizeof(unsigned long long) * cap))) return rc;
-    const uint64_t have = ctx->n_coop.bytes / sizeof(unsigned long long);
+    const uint64_t have = ctx->n_coop.bytes / sizeof(unsigned long long) / words;           // in partials
     auto* part = static_cast<unsigned long long*>(ctx->n_coop.p);
     const auto* srt = static_cast<const uint32_t*>(ctx->w_sorted.p);
     const auto* org = static_cast<const uint32_t*>(ctx->w_orig.p);
     uint32_t grid = COOP_GRID;
     if (!d_nq) {                       // a known count: no more blocks than items
-        const CoopPlan p = coop_plan(nq_host, ctx->w_n, have);
-        const uint64_t items = (((uint64_t)nq_host + COOP_QG - 1) / COOP_QG) * p.nslices;
+        const CoopPlan p = coop_plan(nq_host, ctx->w_n, have, qg);
+        const uint64_t items = (((uint64_t)nq_host + qg - 1) / qg) * p.nslices;
         grid = (uint32_t)std::min<uint64_t>(items, COOP_GRID);
     }
-    hipLaunchKernelGGL(k_nearest_coop, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
-                       part, have);
     const uint32_t mgrid = d_nq ? 256u : std::min<uint32_t>((nq_host + 3) / 4, 2048u);
-    hipLaunchKernelGGL(k_nearest_coop_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
-                       part, have, max_ed, d_best_idx, d_best_ed, d_n_ties);
+    if (k) {
+        hipLaunchKernelGGL(k_nearest_coop_topk, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
+                           max_ed, k, part, have);
+        hipLaunchKernelGGL(k_nearest_coop_topk_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
+                           part, have, k, d_idx, d_ed, d_n_within, d_n_ties);
+    } else {
+        hipLaunchKernelGGL(k_nearest_coop, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
+                           part, have);
+        hipLaunchKernelGGL(k_nearest_coop_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
+                           part, have, max_ed, d_idx, d_ed, d_n_ties);
+    }
     BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+// What the two probe-path launchers share: the index parts the call needs (built on first use), the query lists and their
+// counters (zeroed on st), and where pass 2 reads.
+struct ProbeSetup {
+    PairTables pt;
+    uint2* list2;                // LSH segments of nq {index, query} entries
+    uint32_t* list3;             // overflow list, nq indices
+    uint32_t* counters;
+    const uint4* dv_ent = nullptr;       // pass 2 (max_ed 2): the deletion variants' entries and their directory
+    const uint32_t* dv_dir = nullptr;
+    uint32_t grid2;              // pass 2's blocks
+};
+
+static int probe_setup(bdg_ctx* ctx, hipStream_t st, uint32_t nq, uint32_t max_ed, ProbeSetup& ps)
+{
+    int rc;
+    if (!ctx->w_probe_ready && (rc = build_pair_tables(ctx))) return rc;
+    if (max_ed >= 2 && !ctx->w_delins_ready && (rc = build_delins_index(ctx))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_list, sizeof(uint32_t) * (2ull * LSH + 1ull) * nq))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->n_counters, NCTR_BYTES))) return rc;
+    ps.list2 = static_cast<uint2*>(ctx->n_list.p);
+    ps.list3 = reinterpret_cast<uint32_t*>(ps.list2 + (size_t)LSH * nq);
+    ps.counters = static_cast<uint32_t*>(ctx->n_counters.p);
+    BDG_HIP_TRY(ctx, hipMemsetAsync(ps.counters, 0, NCTR_BYTES, st));
+    ps.pt = PairTables{ static_cast<const uint32_t*>(ctx->w_pent.p), static_cast<const uint32_t*>(ctx->w_pent.p) + ctx->w_pwords,
+                        static_cast<const uint32_t*>(ctx->w_delmap.p) };
+    if (max_ed >= 2) {
+        ps.dv_ent = static_cast<const uint4*>(ctx->w_dv.p);
+        ps.dv_dir = static_cast<const uint32_t*>(ctx->w_dv.p) + 4 * 16ull * ctx->w_n;       // behind the 16 * nw entries
+    }
+    ps.grid2 = std::min<uint32_t>((nq + 63) / 64, 256u * 8u);
     return BDG_OK;
 }
 
@@ -1224,7 +1113,7 @@ int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, in
     if (!probe) {
         if (ctx->n16_algo == 3 || (ctx->n16_algo == 0 && nq < COOP_NQ_MAX)) {
             ScopedKernelTimer tm(ctx, "k_nearest_coop");
-            return launch_coop(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, d_best_idx, d_best_ed, d_n_ties);
+            return launch_coop(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, 0u, d_best_idx, d_best_ed, nullptr, d_n_ties);
         }
         ScopedKernelTimer tm(ctx, "k_nearest_scan");
         hipLaunchKernelGGL(k_nearest_scan, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, (const uint32_t*)nullptr, nq,
@@ -1232,36 +1121,26 @@ int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, in
         BDG_HIP_TRY(ctx, hipGetLastError());
         return BDG_OK;
     }
+    ProbeSetup ps;
     int rc;
-    if (!ctx->w_probe_ready && (rc = build_pair_tables(ctx))) return rc;
-    if (max_ed >= 2 && !ctx->w_delins_ready && (rc = build_delins_index(ctx))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->n_list, sizeof(uint32_t) * (2ull * LSH + 1ull) * nq))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->n_counters, NCTR_BYTES))) return rc;
-    auto* list2 = static_cast<uint2*>(ctx->n_list.p);                          // LSH segments of nq {index, query} entries
-    auto* list3 = reinterpret_cast<uint32_t*>(list2 + (size_t)LSH * nq);       // overflow list, nq indices
-    auto* counters = static_cast<uint32_t*>(ctx->n_counters.p);
-    BDG_HIP_TRY(ctx, hipMemsetAsync(counters, 0, NCTR_BYTES, st));
-    PairTables pt{ static_cast<const uint32_t*>(ctx->w_pent.p), static_cast<const uint32_t*>(ctx->w_pent.p) + ctx->w_pwords,
-                   static_cast<const uint32_t*>(ctx->w_delmap.p), ctx->w_n };
+    if ((rc = probe_setup(ctx, st, nq, max_ed, ps))) return rc;
     {
         ScopedKernelTimer tm(ctx, "k_nearest_pairs");
-        hipLaunchKernelGGL(k_nearest_pairs, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, nq, pt, max_ed,
-                           d_best_idx, d_best_ed, d_n_ties, list2, counters);
+        hipLaunchKernelGGL(k_nearest_pairs, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, nq, ps.pt, max_ed,
+                           d_best_idx, d_best_ed, d_n_ties, ps.list2, ps.counters);
     }
     if (max_ed >= 2) {
         {
             ScopedKernelTimer tm(ctx, "k_nearest_delins");
-            const uint32_t grid = std::min<uint32_t>((nq + 63) / 64, 256u * 8u);
-            const size_t npairs = 16ull * ctx->w_n;
-            hipLaunchKernelGGL(k_nearest_delins, dim3(grid), dim3(256), 0, st, list2, nq, counters, pt.delmap,
-                               static_cast<const uint4*>(ctx->w_dv.p), static_cast<const uint32_t*>(ctx->w_dv.p) + 4 * npairs,
-                               d_best_idx, d_best_ed, d_n_ties, list3, counters);
+            hipLaunchKernelGGL(k_nearest_delins, dim3(ps.grid2), dim3(256), 0, st, ps.list2, nq, ps.counters, ps.pt.delmap,
+                               ps.dv_ent, ps.dv_dir, d_best_idx, d_best_ed, d_n_ties, ps.list3, ps.counters);
         }
         // queries whose hit list overflowed (one lane found more than 4 distinct entries): the cooperative kernel on just
         // those (few: a whole grid per query); the list length stays on the device, so no host round trip
         {
             ScopedKernelTimer tm(ctx, "k_nearest_coop_overflow");
-            if ((rc = launch_coop(ctx, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3, nq, max_ed, d_best_idx, d_best_ed, d_n_ties)))
+            if ((rc = launch_coop(ctx, st, d_q, qstride, recs, ps.list3, 0u, ps.counters + CTR_N3, nq, max_ed, 0u,
+                                  d_best_idx, d_best_ed, nullptr, d_n_ties)))
                 return rc;
         }
     }
@@ -1270,34 +1149,6 @@ int bdg_nearest16_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstride, in
 }
 
 // ---- top-k dispatch -------------------------------------------------------------------------------------------------
-// The cooperative top-k kernel and its merge (query list as for launch_coop).  A partial takes k + 1 words.
-static int launch_coop_topk(bdg_ctx* ctx, hipStream_t st, const uint32_t* d_q, uint32_t qstride, int recs, const uint32_t* qlist,
-                            uint32_t nq_host, const uint32_t* d_nq, uint32_t nq_cap, uint32_t max_ed, uint32_t k,
-                            uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within, uint16_t* d_n_ties)
-{
-    const uint64_t groups = ((uint64_t)nq_cap + COOP_TOPK_QG - 1) / COOP_TOPK_QG;
-    const uint64_t cap = std::max<uint64_t>(COOP_PARTIALS, groups * COOP_TOPK_QG * 4u * (k + 1u));      // words
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->n_coop, sizeof(unsigned long long) * cap))) return rc;
-    const uint64_t have = ctx->n_coop.bytes / sizeof(unsigned long long) / (k + 1u);        // in partials
-    auto* part = static_cast<unsigned long long*>(ctx->n_coop.p);
-    const auto* srt = static_cast<const uint32_t*>(ctx->w_sorted.p);
-    const auto* org = static_cast<const uint32_t*>(ctx->w_orig.p);
-    uint32_t grid = COOP_GRID;
-    if (!d_nq) {
-        const CoopPlan p = coop_plan(nq_host, ctx->w_n, have, COOP_TOPK_QG);
-        const uint64_t items = (((uint64_t)nq_host + COOP_TOPK_QG - 1) / COOP_TOPK_QG) * p.nslices;
-        grid = (uint32_t)std::min<uint64_t>(items, COOP_GRID);
-    }
-    hipLaunchKernelGGL(k_nearest_coop_topk, dim3(grid), dim3(256), 0, st, d_q, qstride, qlist, nq_host, d_nq, srt, org, ctx->w_n,
-                       max_ed, k, part, have);
-    const uint32_t mgrid = d_nq ? 256u : std::min<uint32_t>((nq_host + 3) / 4, 2048u);
-    hipLaunchKernelGGL(k_nearest_coop_topk_merge, dim3(mgrid), dim3(256), 0, st, d_q, qstride, recs, qlist, nq_host, d_nq, ctx->w_n,
-                       part, have, k, d_idx, d_ed, d_n_within, d_n_ties);
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
-}
-
 // how many queries the last probe-path call sent to the cooperative kernel (its overflow list's length; the caller has
 // synchronised)
 int bdg_nearest16_overflow_read(bdg_ctx* ctx, uint32_t* n)
@@ -1329,37 +1180,26 @@ int bdg_nearest16_topk_launch(bdg_ctx* ctx, const uint32_t* d_q, uint32_t qstrid
     const bool probe = ctx->n16_algo != 3 && max_ed <= 2;
     if (!probe) {
         ScopedKernelTimer tm(ctx, "k_nearest_coop_topk");
-        return launch_coop_topk(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, k, d_idx, d_ed, d_n_within, d_n_ties);
+        return launch_coop(ctx, st, d_q, qstride, recs, nullptr, nq, nullptr, nq, max_ed, k, d_idx, d_ed, d_n_within, d_n_ties);
     }
+    ProbeSetup ps;
     int rc;
-    if (!ctx->w_probe_ready && (rc = build_pair_tables(ctx))) return rc;
-    if (max_ed >= 2 && !ctx->w_delins_ready && (rc = build_delins_index(ctx))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->n_list, sizeof(uint32_t) * (2ull * LSH + 1ull) * nq))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->n_counters, NCTR_BYTES))) return rc;
-    auto* list2 = static_cast<uint2*>(ctx->n_list.p);
-    auto* list3 = reinterpret_cast<uint32_t*>(list2 + (size_t)LSH * nq);
-    auto* counters = static_cast<uint32_t*>(ctx->n_counters.p);
-    BDG_HIP_TRY(ctx, hipMemsetAsync(counters, 0, NCTR_BYTES, st));
-    PairTables pt{ static_cast<const uint32_t*>(ctx->w_pent.p), static_cast<const uint32_t*>(ctx->w_pent.p) + ctx->w_pwords,
-                   static_cast<const uint32_t*>(ctx->w_delmap.p), ctx->w_n };
+    if ((rc = probe_setup(ctx, st, nq, max_ed, ps))) return rc;
     {
         ScopedKernelTimer tm(ctx, "k_nearest_pairs_topk");
-        hipLaunchKernelGGL(k_nearest_pairs_topk, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, nq, pt, max_ed, k,
-                           d_idx, d_ed, d_n_within, d_n_ties, list2, counters);
+        hipLaunchKernelGGL(k_nearest_pairs_topk, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, qstride, recs, nq, ps.pt, max_ed, k,
+                           d_idx, d_ed, d_n_within, d_n_ties, ps.list2, ps.counters);
     }
     if (max_ed >= 2) {
         {
             ScopedKernelTimer tm(ctx, "k_nearest_delins_topk");
-            const uint32_t grid = std::min<uint32_t>((nq + 63) / 64, 256u * 8u);
-            const size_t npairs = 16ull * ctx->w_n;
-            hipLaunchKernelGGL(k_nearest_delins_topk, dim3(grid), dim3(256), 0, st, list2, nq, counters, pt.delmap,
-                               static_cast<const uint4*>(ctx->w_dv.p), static_cast<const uint32_t*>(ctx->w_dv.p) + 4 * npairs, k,
-                               d_idx, d_ed, d_n_within, d_n_ties, list3, counters);
+            hipLaunchKernelGGL(k_nearest_delins_topk, dim3(ps.grid2), dim3(256), 0, st, ps.list2, nq, ps.counters, ps.pt.delmap,
+                               ps.dv_ent, ps.dv_dir, k, d_idx, d_ed, d_n_within, d_n_ties, ps.list3, ps.counters);
         }
         {
             ScopedKernelTimer tm(ctx, "k_nearest_coop_topk_overflow");
-            if ((rc = launch_coop_topk(ctx, st, d_q, qstride, recs, list3, 0u, counters + CTR_N3, nq, max_ed, k,
-                                       d_idx, d_ed, d_n_within, d_n_ties)))
+            if ((rc = launch_coop(ctx, st, d_q, qstride, recs, ps.list3, 0u, ps.counters + CTR_N3, nq, max_ed, k,
+                                  d_idx, d_ed, d_n_within, d_n_ties)))
                 return rc;
         }
     }
