@@ -37,6 +37,7 @@ EXPORTS = [
     "bdg_nearest16", "bdg_whitelist_load", "bdg_nearest16_dev", "bdg_nearest16_recs_dev", "bdg_nearest16_set_algo", "bdg_nearest16_index_bytes",
     "bdg_nearest16_overflow_count",
     "bdg_nearest16_topk", "bdg_nearest16_topk_dev", "bdg_nearest16_topk_recs_dev", "bdg_format_rows_wlk",
+    "bdg_nearest16_correct",
     "bdg_graph_edges", "bdg_graph_edges_dev", "bdg_graph_edges_rows_dev", "bdg_graph_edges_part_dev", "bdg_graph_set_algo", "bdg_graph_status", "bdg_distinct_dev", "bdg_rows_of_dev",
     "bdg_extract_submit", "bdg_extract_collect", "bdg_extract_keep_records", "bdg_kept_records", "bdg_kept_records_to_host", "bdg_keep_observed", "bdg_touched_count_dev",
     "bdg_ingest_open", "bdg_ingest_open_mt", "bdg_ingest_open_ex", "bdg_ingest_next", "bdg_ingest_release", "bdg_ingest_error",
@@ -63,6 +64,10 @@ class IngestOpts(C.Structure):
 
 
 STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates is set (BDG_STAGE1_WL_CANDIDATES)
+STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist correction, the trailing fields are set (BDG_STAGE1_WL_CORRECT)
+# status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
+WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
+WLC_STATUS = ("none", "exact", "corrected", "ambiguous", "truncated")
 
 
 class Stage1Opts(C.Structure):
@@ -70,6 +75,11 @@ class Stage1Opts(C.Structure):
     _fields_ = [("umi_len", C.c_uint32), ("threads", C.c_uint32), ("format_threads", C.c_uint32), ("header_every", C.c_uint32),
                 ("chunk_reads", C.c_uint32), ("skip_secondary", C.c_int32), ("segment_bytes", C.c_uint64),
                 ("whitelist", C.c_uint32), ("max_bc_dist", C.c_uint16), ("bc_candidates", C.c_uint16)]
+
+
+class Stage1OptsCorrect(Stage1Opts):
+    """bdg_stage1_opts with the fields read only with STAGE1_WL_CORRECT (Stage1Opts is the struct of callers without them)"""
+    _fields_ = [("bc_edit_bits", C.c_uint32), ("bc_min_permille", C.c_uint32), ("corrected_path", C.c_char_p)]
 
 
 class Stage1Result(C.Structure):
@@ -80,6 +90,11 @@ class Stage1Result(C.Structure):
                 ("seconds_wait_parse", C.c_double), ("seconds_submit", C.c_double), ("seconds_wait_gpu", C.c_double),
                 ("seconds_wait_format", C.c_double), ("seconds_format", C.c_double), ("seconds_write", C.c_double),
                 ("whitelist_barcodes", C.c_uint64)]
+
+
+class Stage1ResultCorrect(Stage1Result):
+    """bdg_stage1_result with the field written only with STAGE1_WL_CORRECT"""
+    _fields_ = [("whitelist_corrected", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -146,6 +161,7 @@ def load():
     L.bdg_nearest16_topk.argtypes = [vp, vp, u32, vp, u32, u32, u32, vp, vp, vp]
     L.bdg_nearest16_topk_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
     L.bdg_nearest16_topk_recs_dev.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+    L.bdg_nearest16_correct.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32, vp, vp, vp, vp, vp]
     L.bdg_format_rows_wlk.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, u64, C.POINTER(u64)]
     L.bdg_format_rows_wlk.restype = C.c_int64
     L.bdg_graph_edges.argtypes = [vp, vp, u32, u32, i32, vp, u64, C.POINTER(u64)]
@@ -374,6 +390,19 @@ class Context:
         self._check(self.lib.bdg_nearest16_topk_recs_dev(self.h, _ptr(d_recs), n, max_ed, k, _ptr(d_idx), _ptr(d_ed),
                                                          _ptr(d_n_within)))
 
+    def nearest16_correct(self, q, wl, max_ed=2, edit_bits=5, min_permille=975):
+        """abundance-weighted correction of the nq queries as one run (bdg_nearest16_correct): idx (uint32), ed (int8),
+        support (uint32), permille (int16), status (uint8, WLC_*), numpy arrays of nq entries"""
+        q = np.ascontiguousarray(q, dtype=np.uint32)
+        wl = np.ascontiguousarray(wl, dtype=np.uint32)
+        n = len(q)
+        idx, sup = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        ed, pm, st = np.zeros(n, np.int8), np.zeros(n, np.int16), np.zeros(n, np.uint8)
+        self._check(self.lib.bdg_nearest16_correct(self.h, q.ctypes.data, n, wl.ctypes.data, len(wl), max_ed, edit_bits,
+                                                   min_permille, idx.ctypes.data, ed.ctypes.data, sup.ctypes.data,
+                                                   pm.ctypes.data, st.ctypes.data))
+        return idx, ed, sup, pm, st
+
     def nearest16_overflow_count(self):
         """queries the last probe-path call sent on to the cooperative kernel (waits for the context's streams)"""
         return int(self.lib.bdg_nearest16_overflow_count(self.h))
@@ -555,18 +584,27 @@ def chunk_reads(ch):
 
 
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
-               chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0):
+               chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
+               corrected_path=None, bc_edit_bits=5, bc_min_permille=975):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
-    whitelist columns (header must name them); bc_candidates=K (1 .. 8) one more, whitelist_candidates."""
+    whitelist columns (header must name them); bc_candidates=K (1 .. 8) one more, whitelist_candidates.  corrected_path (with
+    whitelist): whitelist correction (BDG_STAGE1_WL_CORRECT) into that file; the result then has whitelist_corrected."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
-    wl_mode = (1 | (STAGE1_WL_CANDIDATES if bc_candidates else 0)) if whitelist else 0
-    o = Stage1Opts(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
-                   wl_mode, max_bc_dist, bc_candidates)
-    res = Stage1Result()
-    rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"), C.byref(o), C.byref(res))
+    correct = whitelist and corrected_path is not None
+    wl_mode = (1 | (STAGE1_WL_CANDIDATES if bc_candidates else 0) | (STAGE1_WL_CORRECT if correct else 0)) if whitelist else 0
+    args = (umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
+            wl_mode, max_bc_dist, bc_candidates)
+    if correct:
+        o = Stage1OptsCorrect(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path))
+        res = Stage1ResultCorrect()
+    else:
+        o = Stage1Opts(*args)
+        res = Stage1Result()
+    rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"),
+                          C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
     if rc != 0:
         msg = L.bdg_last_error(contexts[0].h).decode()
         if rc == E_BADBASE:

@@ -275,7 +275,8 @@ void bdg_free(bdg_ctx* ctx)
     for (hipEvent_t e : ctx->ev_aux) if (e) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
                        &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
-                       &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs };
+                       &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs,
+                       &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
         for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match }) if (b->p) (void)hipFree(b->p);
@@ -573,6 +574,45 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
     return BDG_OK;
 }
 
+// lists of the correction store (Correct::lists) from read `at` on
+struct CorrLists { uint32_t* idx8; uint8_t* ed8; uint16_t* nw; };
+static CorrLists corr_lists(bdg_ctx* ctx, uint64_t at)
+{
+    auto* base = static_cast<uint8_t*>(ctx->corr.lists.p);
+    const uint64_t cap = ctx->corr.cap;
+    return CorrLists{ reinterpret_cast<uint32_t*>(base) + at * 8, base + 32 * cap + at * 8,
+                      reinterpret_cast<uint16_t*>(base + 40 * cap) + at };
+}
+
+// room for `need` reads of kept lists; what is kept moves along (behind the matches that wrote it, on the auxiliary stream)
+static int corr_grow(bdg_ctx* ctx, uint64_t need)
+{
+    bdg_ctx::Correct& c = ctx->corr;
+    if (need <= c.cap) return BDG_OK;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * c.cap), 1ull << 20);
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, 42 * cap + 64);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return bdg_fail(ctx, BDG_E_NOMEM, "hipMalloc(" + std::to_string(42 * cap + 64) + " bytes) for the kept candidate lists");
+    }
+    if (c.lists.p) {
+        const CorrLists o = corr_lists(ctx, 0);
+        auto* nb = static_cast<uint8_t*>(p);
+        hipStream_t st = ctx->aux_stream ? ctx->aux_stream : ctx->stream;
+        if (c.n) {
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb, o.idx8, 32 * c.n, hipMemcpyDeviceToDevice, st));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb + 32 * cap, o.ed8, 8 * c.n, hipMemcpyDeviceToDevice, st));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb + 40 * cap, o.nw, 2 * c.n, hipMemcpyDeviceToDevice, st));
+        }
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        BDG_HIP_TRY(ctx, hipFree(c.lists.p));
+    }
+    c.lists.p = p; c.lists.bytes = 42 * cap + 64; c.cap = cap;
+    return BDG_OK;
+}
+
 static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed, uint32_t k)
 {
     int rc;
@@ -587,7 +627,18 @@ static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed, ui
     ctx->aux_pending = true;
     const auto* d_q = reinterpret_cast<const uint32_t*>(sl.d_recs.p) + 5;
     auto* d_idx = static_cast<uint32_t*>(sl.d_match.p);
-    if (k) {
+    if (sl.match_corr) {
+        // correction: the k = 8 lists go to the run's store and stay there; the support kernel adds the chunk's exact hits and
+        // gathers the k slots the host asked for (k = 0: the best-hit layout below) into d_match.  A chunk matched again after
+        // its extraction was rerun adds nothing twice: the first match saw the overflow's placeholder records, none usable.
+        const CorrLists L = corr_lists(ctx, sl.corr_at);
+        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n * (k ? k : 1));
+        auto* d_nwithin = k ? d_ties + n : nullptr;
+        auto* d_ed = reinterpret_cast<uint8_t*>(k ? d_nwithin + n : d_ties + n);
+        rc = bdg_nearest16_topk_launch(ctx, d_q, 8u, 1, sl.n, max_ed, 8u, L.idx8, L.ed8, L.nw, d_ties);
+        if (!rc) rc = bdg_correct_support_launch(ctx, ctx->aux_stream, L.idx8, L.ed8, L.nw, sl.n, k,
+                                                 static_cast<uint32_t*>(ctx->corr.support.p), d_idx, d_ed, d_nwithin);
+    } else if (k) {
         auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n * k);
         auto* d_nwithin = d_ties + n;
         auto* d_ed = reinterpret_cast<uint8_t*>(d_nwithin + n);
@@ -612,9 +663,18 @@ int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k
     if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
     bdg_ctx::Slot& sl = ctx->slots[slot];
     if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
-    int rc = k ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, k) : bdg_nearest16_check(ctx, sl.n, max_ed);
+    const bool corr = ctx->corr.on;
+    if (corr && max_ed > 3) return bdg_fail(ctx, BDG_E_ARG, "whitelist correction needs max_ed <= 3");
+    int rc = corr ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, 8u)
+                  : k ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, k) : bdg_nearest16_check(ctx, sl.n, max_ed);
+    sl.match_corr = corr;
     if (rc || sl.n == 0) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (corr) {
+        if ((rc = corr_grow(ctx, ctx->corr.n + sl.n))) return rc;
+        sl.corr_at = ctx->corr.n;
+        ctx->corr.n += sl.n;
+    }
     return queue_slot_match(ctx, sl, max_ed, k);
 }
 
@@ -655,6 +715,70 @@ int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx,
 int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties)
 {
     return bdg_slot_match_collect_topk(ctx, slot, best_idx, best_ed, n_ties, nullptr, nullptr);
+}
+
+int bdg_correct_begin(bdg_ctx* ctx)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = sync_all(ctx);
+    if (rc) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->corr.support, 4 * (size_t)ctx->w_n))) return rc;
+    BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->corr.support.p, 0, 4 * (size_t)ctx->w_n, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->corr.n = 0;
+    ctx->corr.on = true;
+    return BDG_OK;
+}
+
+int bdg_correct_support_to_host(bdg_ctx* ctx, uint32_t* support)
+{
+    if (!ctx || !support || !ctx->corr.support.p) return BDG_E_ARG;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = sync_all(ctx);
+    if (rc) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpy(support, ctx->corr.support.p, 4 * (size_t)ctx->w_n, hipMemcpyDeviceToHost));
+    return BDG_OK;
+}
+
+int bdg_correct_support_from_host(bdg_ctx* ctx, const uint32_t* support)
+{
+    if (!ctx || !support || !ctx->corr.support.p) return BDG_E_ARG;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = sync_all(ctx);
+    if (rc) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpy(ctx->corr.support.p, support, 4 * (size_t)ctx->w_n, hipMemcpyHostToDevice));
+    return BDG_OK;
+}
+
+int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out)
+{
+    if (!ctx || (ctx->corr.n && !out) || !ctx->corr.support.p) return BDG_E_ARG;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = sync_all(ctx);
+    if (rc || ctx->corr.n == 0) return rc;
+    const uint64_t n = ctx->corr.n;
+    if ((rc = bdg_reserve(ctx, ctx->corr.out, 12 * n + 64))) return rc;
+    const CorrLists L = corr_lists(ctx, 0);
+    if ((rc = bdg_correct_resolve_launch(ctx, ctx->stream, L.idx8, L.ed8, L.nw, n, static_cast<const uint32_t*>(ctx->corr.support.p),
+                                         max_ed, bits, pmin, ctx->corr.out.p)))
+        return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->corr.out.p, 12 * n, hipMemcpyDeviceToHost, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return BDG_OK;
+}
+
+int bdg_correct_end(bdg_ctx* ctx)
+{
+    if (!ctx) return BDG_E_ARG;
+    ctx->corr.on = false;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = sync_all(ctx);
+    if (rc) return rc;
+    for (DevBuf* b : { &ctx->corr.lists, &ctx->corr.out }) if (b->p) { BDG_HIP_TRY(ctx, hipFree(b->p)); *b = DevBuf(); }
+    ctx->corr.n = ctx->corr.cap = 0;
+    return BDG_OK;
 }
 
 int bdg_extract_keep_records(bdg_ctx* ctx, int on)
@@ -864,6 +988,53 @@ int bdg_nearest16_topk(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint3
     BDG_HIP_TRY(ctx, hipMemcpyAsync(n_within, d_nw, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipMemcpyAsync(ed, d_ed, nk, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
+
+int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw, uint32_t max_ed,
+                          uint32_t edit_bits, uint32_t min_permille, uint32_t* idx, int8_t* ed, uint32_t* support,
+                          int16_t* permille, uint8_t* status)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (max_ed > 3) return bdg_fail(ctx, BDG_E_ARG, "max_ed out of range (0 .. 3)");
+    if (edit_bits < 1 || edit_bits > 8) return bdg_fail(ctx, BDG_E_ARG, "edit_bits out of range (1 .. 8)");
+    if (min_permille < 501 || min_permille > 1000) return bdg_fail(ctx, BDG_E_ARG, "min_permille out of range (501 .. 1000)");
+    int rc = bdg_nearest16_topk_check(ctx, 0, max_ed, 8u);
+    if (rc) return rc;
+    if (nq == 0) return BDG_OK;
+    if (!q || !idx || !ed || !support || !permille || !status || (nw && !wl)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (nw == 0) {
+        for (uint32_t i = 0; i < nq; ++i) { idx[i] = 0xFFFFFFFFu; ed[i] = -1; support[i] = 0; permille[i] = -1; status[i] = BDG_WLC_NONE; }
+        return BDG_OK;
+    }
+    if ((rc = bdg_whitelist_load_impl(ctx, wl, nw))) return rc;
+    if ((rc = bdg_correct_begin(ctx))) return rc;
+    std::vector<uint8_t> out((size_t)nq * 12);
+    auto run = [&]() -> int {
+        int r;
+        if ((r = corr_grow(ctx, nq))) return r;
+        ctx->corr.n = nq;
+        if ((r = bdg_reserve(ctx, ctx->s_in0, sizeof(uint32_t) * (size_t)nq))) return r;
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, sizeof(uint32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+        const CorrLists L = corr_lists(ctx, 0);
+        if ((r = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, 8u, L.idx8, L.ed8, L.nw, nullptr)))
+            return r;
+        if ((r = bdg_correct_support_launch(ctx, ctx->stream, L.idx8, L.ed8, L.nw, nq, 0u, static_cast<uint32_t*>(ctx->corr.support.p),
+                                            nullptr, nullptr, nullptr)))
+            return r;
+        return bdg_correct_resolve(ctx, max_ed, edit_bits, min_permille, out.data());
+    };
+    rc = run();
+    const int rce = bdg_correct_end(ctx);
+    if (rc) return rc;
+    if (rce) return rce;
+    const size_t n = nq;
+    memcpy(idx, out.data(), 4 * n);
+    memcpy(support, out.data() + 4 * n, 4 * n);
+    memcpy(permille, out.data() + 8 * n, 2 * n);
+    memcpy(ed, out.data() + 10 * n, n);
+    memcpy(status, out.data() + 11 * n, n);
     return BDG_OK;
 }
 

@@ -80,7 +80,17 @@ struct bdg_ctx {
         hipEvent_t match_done = nullptr;
         uint32_t match_max_ed = 0, match_k = 0;
         bool match_queued = false;
+        bool match_corr = false;                             // correction on: the match runs at k = 8 into corr.lists at corr_at,
+        uint64_t corr_at = 0;                                // and d_match holds the compact block of match_k slots (0: best hit)
     } slots[BDG_SLOTS];
+    // ---- whitelist correction of a stage-1 run (correct_kernels.hip, bdg_stage1_run with BDG_STAGE1_WL_CORRECT)
+    struct Correct {
+        bool on = false;
+        DevBuf lists;        // per read in submission order: idx u32 [cap * 8] | ed u8 [cap * 8] | n_within u16 [cap] (42 bytes)
+        uint64_t n = 0, cap = 0;
+        DevBuf support;      // u32 [w_n]: exact hits per entry over this context's chunks
+        DevBuf out;          // resolve: idx u32 | support u32 | permille i16 | dist i8 | status u8, [n] each (12 bytes per read)
+    } corr;
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
     DevBuf x_allrecs; uint64_t x_allrecs_n = 0;
@@ -138,6 +148,19 @@ extern "C" int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* bes
 extern "C" int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k);
 extern "C" int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
                                            uint32_t* cand_idx, uint8_t* cand_ed);
+// Whitelist correction over a run of slot matches (bdg_abi.cpp): begin (on) clears the support array and the kept lists and makes
+// every later bdg_slot_match_topk of the context a k = 8 match whose lists stay on the device, plus a support kernel; the host
+// still gets k slots.  support_to_host / support_from_host: the context's support array, to be summed over the contexts of a run.
+// resolve: the rule over every kept list, results (layout of Correct::out) to host memory; end frees the lists.
+extern "C" int bdg_correct_begin(bdg_ctx* ctx);
+extern "C" int bdg_correct_support_to_host(bdg_ctx* ctx, uint32_t* support);
+extern "C" int bdg_correct_support_from_host(bdg_ctx* ctx, const uint32_t* support);
+extern "C" int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
+extern "C" int bdg_correct_end(bdg_ctx* ctx);
+int bdg_correct_support_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
+                               uint32_t n, uint32_t K, uint32_t* support, uint32_t* h_idx, uint8_t* h_ed, uint16_t* h_nw);
+int bdg_correct_resolve_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
+                               uint64_t n, const uint32_t* support, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
 
 // Event-bracketed launch bookkeeping.
 int  bdg_timer_id(bdg_ctx* ctx, const char* name);

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -256,6 +257,14 @@ bool write_all(int fd, const char* p, size_t n)
     return true;
 }
 
+// the correction file of bdg_stage1_run (BDG_STAGE1_WL_CORRECT): res = n results in bdg_ctx::Correct::out's layout, in input
+// order; *called = rows of status exact or corrected
+bool write_corrected(const char* path, const bdg_idstore* ids, const uint8_t* res, uint64_t n, const uint32_t* wl, uint32_t nw,
+                     uint64_t* called);
+int correct_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, const bdg_idstore* ids,
+                const std::vector<uint32_t>& chunk_n, uint64_t n, const uint32_t* wl, uint32_t nw, bdg_stage1_result* res,
+                std::string& err);
+
 }  // namespace
 
 extern "C" {
@@ -309,7 +318,9 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
 {
     if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !out_path || !header || !o || !res) return BDG_E_ARG;
     bdg_ctx* const c0 = ctxs[0];
-    memset(res, 0, sizeof(*res));
+    const bool corr = o->whitelist && (o->whitelist & BDG_STAGE1_WL_CORRECT);
+    // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT)
+    memset(res, 0, corr ? sizeof(*res) : offsetof(bdg_stage1_result, whitelist_corrected));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (o->umi_len == 0 || o->umi_len > 64) return bdg_fail(c0, BDG_E_ARG, "umi_len out of range");
     // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
@@ -319,6 +330,12 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         if (o->max_bc_dist > 16 || (!(o->whitelist & BDG_STAGE1_WL_CANDIDATES) && o->bc_candidates))
             return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
         if (o->bc_candidates > 8) return bdg_fail(c0, BDG_E_ARG, "bc_candidates out of range (0 .. 8)");
+        if (o->whitelist & BDG_STAGE1_WL_CORRECT) {
+            if (o->max_bc_dist > 3) return bdg_fail(c0, BDG_E_ARG, "whitelist correction needs max_bc_dist <= 3");
+            if (o->bc_edit_bits < 1 || o->bc_edit_bits > 8) return bdg_fail(c0, BDG_E_ARG, "bc_edit_bits out of range (1 .. 8)");
+            if (o->bc_min_permille < 501 || o->bc_min_permille > 1000) return bdg_fail(c0, BDG_E_ARG, "bc_min_permille out of range (501 .. 1000)");
+            if (!o->corrected_path) return bdg_fail(c0, BDG_E_ARG, "no corrected_path");
+        }
         for (uint32_t c = 0; c < n_ctx; ++c) {
             if (!ctxs[c]) return BDG_E_ARG;
             if (ctxs[c]->w_n == 0) return bdg_fail(c0, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load) on context " + std::to_string(c));
@@ -327,6 +344,20 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         }
         wl_caller.resize(c0->w_n);
         for (uint32_t i = 0; i < c0->w_n; ++i) wl_caller[c0->w_host_order[i]] = c0->w_host_sorted[i];
+    }
+    // correction: every context keeps its reads' candidate lists and counts exact hits; the read ids are kept for the file
+    bdg_idstore* ids = nullptr;
+    std::vector<uint32_t> chunk_n;                               // reads per chunk, in input order (chunk k on context k mod n_ctx)
+    auto corr_end = [&]() {
+        for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_correct_end(ctxs[c]);
+        bdg_idstore_free(ids); ids = nullptr;
+    };
+    if (corr) {
+        for (uint32_t c = 0; c < n_ctx; ++c) {
+            const int r = bdg_correct_begin(ctxs[c]);
+            if (r) { const std::string m = bdg_last_error(ctxs[c]); corr_end(); return bdg_fail(c0, r, m); }
+        }
+        ids = bdg_idstore_new();
     }
     const double t_start = now_s();
     uint32_t fthreads = o->format_threads ? std::min(o->format_threads, 32u) : 4u;
@@ -341,9 +372,9 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     const uint64_t max_outstanding = 2 * fthreads + 2;           // collected chunks waiting for / in the formatters
     Pipeline P;
     int rc = bdg_ingest_open_ex(in_path, &io, &P.ing);
-    if (rc) return bdg_fail(c0, rc, std::string("cannot read ") + in_path + " (unknown extension or unreadable file)");
+    if (rc) { if (corr) corr_end(); return bdg_fail(c0, rc, std::string("cannot read ") + in_path + " (unknown extension or unreadable file)"); }
     P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (P.fd < 0) { bdg_ingest_close(P.ing); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
+    if (P.fd < 0) { bdg_ingest_close(P.ing); if (corr) corr_end(); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
     P.header = header; P.header_every = o->header_every;
     if (o->whitelist) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
     bool ok_io = true;
@@ -402,6 +433,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         if (o->whitelist) rc = bdg_slot_match_topk(j->ctx, j->slot, o->max_bc_dist, o->bc_candidates);
         t_submit += now_s() - t1;
         if (rc) { err = bdg_last_error(j->ctx); break; }
+        if (corr) { (void)bdg_idstore_append(ids, ch.ids, ch.id_off, ch.n); chunk_n.push_back(ch.n); }
         g0 += ch.n; ++k;
     }
     while (!inflight.empty()) {
@@ -429,6 +461,14 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     res->chunks = k; res->out_bytes = P.out_bytes; res->whitelist_barcodes = P.total.wl;
     res->seconds_total = now_s() - t_start; res->seconds_wait_parse = t_parse_wait; res->seconds_wait_gpu = t_gpu_wait;
     res->seconds_wait_format = t_fmt_wait; res->seconds_submit = t_submit; res->seconds_format = P.t_format; res->seconds_write = P.t_write;
+    if (corr) {
+        if (rc == BDG_OK && ok_io && !P.write_failed) {
+            int rcc = correct_run(ctxs, n_ctx, o, ids, chunk_n, g0, P.wl, P.nw, res, err);
+            if (rcc) rc = rcc;
+        }
+        corr_end();
+        res->seconds_total = now_s() - t_start;
+    }
     if (rc) return bdg_fail(c0, rc, err);
     if (!ok_io || P.write_failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + out_path);
     return BDG_OK;
@@ -441,6 +481,157 @@ struct bdg_idstore {
     std::vector<char> text;
     std::vector<uint64_t> off{ 0 };
 };
+
+namespace {
+
+// "<id>\t<fields>\n" for every read of the store under a header line, into fd, which is closed (false: a write failed).  A row's
+// length is known before it is written (field_len(i): the bytes put_fields(i, o) writes, at most field_max): the rows are cut
+// into ranges, every range knows its place in the file, and a thread formats and pwrite()s its range by itself
+template <class Len, class Put>
+bool write_id_rows(int fd, const char* header, const bdg_idstore* ids, uint64_t n, uint64_t field_max, Len field_len, Put put_fields)
+{
+    const uint64_t hl = strlen(header);
+    bool ok = write_all(fd, (std::string(header) + "\n").data(), hl + 1);
+    unsigned nt = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    if (const char* e = getenv("BADGER_AMD_WRITE_THREADS")) nt = (unsigned)std::max(1, atoi(e));
+    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, n >> 16));                 // 65,536 rows per thread at least
+    std::vector<uint64_t> lo(nt + 1), at(nt + 1);
+    for (unsigned k = 0; k <= nt; ++k) lo[k] = n * k / nt;
+    at[0] = hl + 1;
+    {
+        std::vector<uint64_t> bytes(nt, 0);
+        std::vector<std::thread> th;
+        auto size_of = [&](unsigned k) {
+            uint64_t b = ids->off[lo[k + 1]] - ids->off[lo[k]] + 2 * (lo[k + 1] - lo[k]);
+            for (uint64_t i = lo[k]; i < lo[k + 1]; ++i) b += field_len(i);
+            bytes[k] = b;
+        };
+        for (unsigned k = 1; k < nt; ++k) th.emplace_back(size_of, k);
+        size_of(0);
+        for (auto& t : th) t.join();
+        for (unsigned k = 0; k < nt; ++k) at[k + 1] = at[k] + bytes[k];
+    }
+    std::atomic<bool> good{ ok };
+    auto write_range = [&](unsigned k) {
+        std::vector<char> buf;
+        buf.reserve(size_t(8) << 20);
+        uint64_t pos = at[k];
+        auto flush = [&]() {
+            size_t done = 0;
+            while (done < buf.size()) {
+                const ssize_t w = pwrite(fd, buf.data() + done, buf.size() - done, (off_t)(pos + done));
+                if (w <= 0) { good = false; return; }
+                done += (size_t)w;
+            }
+            pos += buf.size(); buf.clear();
+        };
+        for (uint64_t i = lo[k]; i < lo[k + 1] && good; ++i) {
+            const size_t idl = (size_t)(ids->off[i + 1] - ids->off[i]);
+            const size_t a = buf.size();
+            buf.resize(a + idl + 2 + field_max);
+            char* o = buf.data() + a;
+            memcpy(o, ids->text.data() + ids->off[i], idl); o += idl;
+            *o++ = '\t';
+            o = put_fields(i, o);
+            *o++ = '\n';
+            buf.resize((size_t)(o - buf.data()));
+            if (buf.size() > (size_t(8) << 20) - 4096) flush();
+        }
+        if (good && !buf.empty()) flush();
+    };
+    if (ok) {
+        std::vector<std::thread> th;
+        for (unsigned k = 1; k < nt; ++k) th.emplace_back(write_range, k);
+        write_range(0);
+        for (auto& t : th) t.join();
+    }
+    ok = good;
+    if (::close(fd) != 0) ok = false;
+    return ok;
+}
+
+const char* const WLC_STATUS[] = { "none", "exact", "corrected", "ambiguous", "truncated" };
+
+uint32_t dec_len(uint32_t v) { uint32_t l = 1; while (v >= 10) { v /= 10; ++l; } return l; }
+
+bool write_corrected(const char* path, const bdg_idstore* ids, const uint8_t* res, uint64_t n, const uint32_t* wl, uint32_t nw,
+                     uint64_t* called)
+{
+    const auto* idx = reinterpret_cast<const uint32_t*>(res);
+    const uint32_t* sup = idx + n;
+    const auto* pm = reinterpret_cast<const int16_t*>(sup + n);
+    const auto* ed = reinterpret_cast<const int8_t*>(pm + n);
+    const uint8_t* st = reinterpret_cast<const uint8_t*>(ed + n);
+    uint64_t c = 0;
+    for (uint64_t i = 0; i < n; ++i) c += st[i] == BDG_WLC_EXACT || st[i] == BDG_WLC_CORRECTED;
+    *called = c;
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return false;
+    auto shown = [&](uint64_t i) { return (st[i] == BDG_WLC_EXACT || st[i] == BDG_WLC_CORRECTED) && idx[i] < nw; };
+    auto ilen = [](int v) { return v < 0 ? 1 + dec_len((uint32_t)-v) : dec_len((uint32_t)v); };
+    return write_id_rows(fd, "#read_id\tcorrected_barcode\tcorrected_dist\tsupport\tposterior\tstatus", ids, n, 16 + 4 + 10 + 5 + 9 + 4,
+        [&](uint64_t i) -> uint64_t {
+            return (shown(i) ? 16 : 1) + 4 + ilen(ed[i]) + dec_len(sup[i]) + ilen(pm[i]) + strlen(WLC_STATUS[st[i] <= 4 ? st[i] : 0]);
+        },
+        [&](uint64_t i, char* o) -> char* {
+            if (shown(i)) { const uint32_t r = wl[idx[i]]; for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(r >> (2 * b)) & 3u]; }
+            else *o++ = '*';
+            *o++ = '\t'; o = put_int(o, ed[i]);
+            *o++ = '\t';
+            { char t[12]; int k = 0; uint32_t u = sup[i]; do { t[k++] = (char)('0' + u % 10); u /= 10; } while (u); while (k) *o++ = t[--k]; }
+            *o++ = '\t'; o = put_int(o, pm[i]);
+            *o++ = '\t';
+            const char* s = WLC_STATUS[st[i] <= 4 ? st[i] : 0];
+            const size_t l = strlen(s); memcpy(o, s, l); o += l;
+            return o;
+        });
+}
+
+// after the last chunk of a run with BDG_STAGE1_WL_CORRECT: the support arrays of all contexts summed, every context's lists
+// resolved, the results put in input order (chunk j was context j mod n_ctx's), the file written
+int correct_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, const bdg_idstore* ids,
+                const std::vector<uint32_t>& chunk_n, uint64_t n, const uint32_t* wl, uint32_t nw, bdg_stage1_result* res,
+                std::string& err)
+{
+    int rc;
+    std::vector<uint32_t> sum(nw, 0), part(nw);
+    for (uint32_t c = 0; c < n_ctx; ++c) {
+        if ((rc = bdg_correct_support_to_host(ctxs[c], part.data()))) { err = bdg_last_error(ctxs[c]); return rc; }
+        for (uint32_t w = 0; w < nw; ++w) sum[w] += part[w];
+    }
+    std::vector<uint64_t> local(n_ctx, 0);
+    for (size_t j = 0; j < chunk_n.size(); ++j) local[j % n_ctx] += chunk_n[j];
+    std::vector<uint8_t> all(12 * n + 16), loc;
+    static const size_t FIELD[5] = { 4, 4, 2, 1, 1 };          // idx, support, permille, dist, status
+    for (uint32_t c = 0; c < n_ctx; ++c) {
+        if (ctxs[c]->corr.n != local[c]) { err = "kept candidate lists do not match the chunks"; return BDG_E_ARG; }
+        if ((rc = bdg_correct_support_from_host(ctxs[c], sum.data()))) { err = bdg_last_error(ctxs[c]); return rc; }
+        loc.resize(12 * local[c] + 16);
+        if ((rc = bdg_correct_resolve(ctxs[c], o->max_bc_dist, o->bc_edit_bits, o->bc_min_permille, loc.data()))) {
+            err = bdg_last_error(ctxs[c]); return rc;
+        }
+        uint64_t g = 0, l = 0;
+        for (size_t j = 0; j < chunk_n.size(); ++j) {
+            if (j % n_ctx == c) {
+                size_t fo_all = 0, fo_loc = 0;
+                for (size_t f = 0; f < 5; ++f) {
+                    memcpy(all.data() + fo_all + FIELD[f] * g, loc.data() + fo_loc + FIELD[f] * l, FIELD[f] * chunk_n[j]);
+                    fo_all += FIELD[f] * n; fo_loc += FIELD[f] * local[c];
+                }
+                l += chunk_n[j];
+            }
+            g += chunk_n[j];
+        }
+    }
+    uint64_t called = 0;
+    if (!write_corrected(o->corrected_path, ids, all.data(), n, wl, nw, &called)) {
+        err = std::string("write error on ") + o->corrected_path; return BDG_E_ARG;
+    }
+    res->whitelist_corrected = called;
+    return BDG_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -469,7 +660,7 @@ int bdg_idstore_get(const bdg_idstore* s, uint64_t i, const char** p, uint32_t* 
 int bdg_stage1_collect(bdg_ctx* ctx, const char* in_path, const bdg_stage1_opts* o, bdg_idstore* ids, bdg_stage1_result* res)
 {
     if (!ctx || !in_path || !o || !ids || !res) return BDG_E_ARG;
-    memset(res, 0, sizeof(*res));
+    memset(res, 0, offsetof(bdg_stage1_result, whitelist_corrected));   // (the caller's struct may end before that field)
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (o->umi_len == 0 || o->umi_len > 64) return bdg_fail(ctx, BDG_E_ARG, "umi_len out of range");
     const double t_start = now_s();
@@ -678,67 +869,14 @@ int bdg_write_assignments(const bdg_idstore* ids, const uint32_t* rank, const ui
     if (!ids || !path || (n && (!rank || !has)) || n != bdg_idstore_count(ids)) return BDG_E_ARG;
     const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (fd < 0) return BDG_E_ARG;
-    bool ok = write_all(fd, "readID\tbarcode\n", 15);
-    // a row's length is known before it is written (id + tab + 16 letters or '*' + newline): the rows are cut into ranges,
-    // every range knows its place in the file, and a thread formats and pwrite()s its range by itself
-    unsigned nt = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-    if (const char* e = getenv("BADGER_AMD_WRITE_THREADS")) nt = (unsigned)std::max(1, atoi(e));
-    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, n >> 16));                 // 65,536 rows per thread at least
-    std::vector<uint64_t> lo(nt + 1), at(nt + 1);
-    for (unsigned k = 0; k <= nt; ++k) lo[k] = n * k / nt;
-    at[0] = 15;
-    {
-        std::vector<uint64_t> bytes(nt, 0);
-        std::vector<std::thread> th;
-        auto size_of = [&](unsigned k) {
-            uint64_t b = ids->off[lo[k + 1]] - ids->off[lo[k]] + 2 * (lo[k + 1] - lo[k]);
-            for (uint64_t i = lo[k]; i < lo[k + 1]; ++i) b += has[i] ? 16 : 1;
-            bytes[k] = b;
-        };
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(size_of, k);
-        size_of(0);
-        for (auto& t : th) t.join();
-        for (unsigned k = 0; k < nt; ++k) at[k + 1] = at[k] + bytes[k];
-    }
-    std::atomic<bool> good{ ok };
-    auto write_range = [&](unsigned k) {
-        std::vector<char> buf;
-        buf.reserve(size_t(8) << 20);
-        uint64_t pos = at[k];
-        auto flush = [&]() {
-            size_t done = 0;
-            while (done < buf.size()) {
-                const ssize_t w = pwrite(fd, buf.data() + done, buf.size() - done, (off_t)(pos + done));
-                if (w <= 0) { good = false; return; }
-                done += (size_t)w;
-            }
-            pos += buf.size(); buf.clear();
-        };
-        for (uint64_t i = lo[k]; i < lo[k + 1] && good; ++i) {
-            const size_t idl = (size_t)(ids->off[i + 1] - ids->off[i]);
-            const size_t a = buf.size();
-            buf.resize(a + idl + 19);
-            char* o = buf.data() + a;
-            memcpy(o, ids->text.data() + ids->off[i], idl); o += idl;
-            *o++ = '\t';
-            if (has[i]) { const uint32_t r = rank[i]; for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(r >> (2 * b)) & 3u]; }   // unrank, common.py:27-38
-            else *o++ = '*';
-            *o++ = '\n';
-            buf.resize((size_t)(o - buf.data()));
-            if (buf.size() > (size_t(8) << 20) - 4096) flush();
-        }
-        if (good && !buf.empty()) flush();
-    };
-    if (ok) {
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < nt; ++k) th.emplace_back(write_range, k);
-        write_range(0);
-        for (auto& t : th) t.join();
-    }
-    ok = good;
-    if (::close(fd) != 0) ok = false;
+    const bool ok = write_id_rows(fd, "readID\tbarcode", ids, n, 17,
+                                  [&](uint64_t i) -> uint64_t { return has[i] ? 16 : 1; },
+                                  [&](uint64_t i, char* o) -> char* {
+                                      if (has[i]) { const uint32_t r = rank[i]; for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(r >> (2 * b)) & 3u]; }   // unrank, common.py:27-38
+                                      else *o++ = '*';
+                                      return o;
+                                  });
     return ok ? BDG_OK : BDG_E_ARG;
 }
-
 
 }  // extern "C"

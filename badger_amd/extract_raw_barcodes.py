@@ -25,6 +25,12 @@ What differs from the reference, by design:
   * --bc_candidates K (1 .. 8, needs -b): one more column, whitelist_candidates - the K nearest entries within
     --max_bc_dist by (distance, list order) as BARCODE:DIST joined by commas, '*' for none (bdg_nearest16_topk,
     bdg_format_rows_wlk).  The other columns and the .stats do not change.
+  * --bc_correct (needs -b, --max_bc_dist at most 3): abundance-weighted whitelist correction.  Each read's 8 nearest entries
+    are weighed by how many reads of the whole run hit each one exactly, 2^--bc_edit_bits less per edit; the call is made
+    when its share reaches --bc_min_posterior (default 0.975).  One row per read goes to <output>.corrected.tsv
+    (corrected_barcode, corrected_dist, support, posterior in permille, status; badger_amd/wl_correct.py restates the rule,
+    include/badger_hip.h bdg_nearest16_correct states it) and the .stats gets a "Whitelist corrected" line.  The main TSV
+    does not change.
 """
 import argparse
 import gzip
@@ -45,6 +51,10 @@ READ_CHUNK_SIZE = 100000
 WHITELIST_COLUMNS = ("whitelist_barcode", "whitelist_dist", "whitelist_ties")
 CANDIDATES_COLUMN = "whitelist_candidates"
 MAX_BC_DIST_DEFAULT = 2
+CORRECT_MAX_BC_DIST = 3
+CORRECTED_SUFFIX = ".corrected.tsv"
+BC_EDIT_BITS_DEFAULT = 5
+BC_MIN_POSTERIOR_DEFAULT = 0.975
 BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
 
 
@@ -338,10 +348,11 @@ def _detectors(mode, gpus):
     return [BARCODE_CALLING_MODES[mode](device=g) for g in range(gpus)]
 
 
-def _stats_lines(res, whitelist=False):
+def _stats_lines(res, whitelist=False, corrected=False):
     """ReadStats.__str__ (barcode_callers.py:138-143) from the native run's counters: the attribute lines come in the order
     in which the first read showing each was met (a dict's insertion order in the reference).  With a whitelist, one more
-    line after them: the rows whose whitelist_barcode is not '*'."""
+    line after them: the rows whose whitelist_barcode is not '*'; with --bc_correct one more: the rows called exact or
+    corrected."""
     lines = [("Total reads", res.reads), ("Barcode detected", res.barcodes), ("Reliable UMI", 0)]
     attrs = []
     if res.polyt:
@@ -351,6 +362,8 @@ def _stats_lines(res, whitelist=False):
     lines += [(name, v) for _, _, name, v in sorted(attrs)]
     if whitelist:
         lines.append(("Whitelist barcode", res.whitelist_barcodes))
+        if corrected:
+            lines.append(("Whitelist corrected", res.whitelist_corrected))
     return lines
 
 
@@ -374,12 +387,14 @@ def _run_native(args, header_every, threads, skip_secondary):
     res = _native.stage1_run([d._ctx() for d in detectors], args.input, args.output, header,
                              detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
                              whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
-                             bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0)
+                             bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
+                             **_correct_kwargs(args, wl is not None))
     timing = os.environ.get("BADGER_AMD_STAGE1_TIMING")
     if timing:                                   # where the run's time went (tools/cli_throughput.py reads it)
         import json
         with open(timing, "a") as f:
-            f.write(json.dumps({k: getattr(res, k) for k, _ in res._fields_}) + "\n")
+            fields = [k for c in reversed(type(res).__mro__) for k, _ in c.__dict__.get("_fields_", ())]   # (a subclass's own last)
+            f.write(json.dumps({k: getattr(res, k) for k in fields}) + "\n")
     return res
 
 
@@ -388,7 +403,7 @@ def process_single_thread(args):
     logger.info("Processing " + args.input)
     res = _run_native(args, 0, 1, False)
     with open(args.output + ".stats", "w") as f:
-        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None))):
+        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None)), _correcting(args)):
             f.write("%s:\t%d\n" % (k, v))
             logger.info("%s:\t%d" % (k, v))
     logger.info("Finished barcode calling")
@@ -401,7 +416,7 @@ def process_in_parallel(args):
     logger.info("Processing " + args.input)
     res = _run_native(args, READ_CHUNK_SIZE, args.threads, True)
     with open(args.output + ".stats", "w") as out_stats:
-        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None))):
+        for k, v in _stats_lines(res, bool(getattr(args, "barcodes", None)), _correcting(args)):
             logger.info("%s: %d" % (k, v))
             out_stats.write("%s: %d\n" % (k, v))
     logger.info("Finished barcode calling")
@@ -487,11 +502,26 @@ def parse_args(sys_argv):
     p.add_argument("--bc_candidates", type=_bc_candidates, default=None, metavar="K",
                    help="add a whitelist_candidates column: the K (1 .. 8) nearest whitelist entries within --max_bc_dist, "
                         "as BARCODE:DIST by (distance, list order); needs --barcodes")
+    p.add_argument("--bc_correct", action="store_true",
+                   help="abundance-weighted whitelist correction into <output>%s; needs --barcodes and --max_bc_dist <= %d"
+                        % (CORRECTED_SUFFIX, CORRECT_MAX_BC_DIST))
+    p.add_argument("--bc_min_posterior", type=_bc_posterior, default=None, metavar="X",
+                   help="--bc_correct: smallest posterior of a call, 0.501 .. 1.0 (default %g)" % BC_MIN_POSTERIOR_DEFAULT)
+    p.add_argument("--bc_edit_bits", type=_bc_edit_bits, default=None, metavar="B",
+                   help="--bc_correct: one edit makes a candidate 2^B times less likely, 1 .. 8 (default %d)" % BC_EDIT_BITS_DEFAULT)
     args = p.parse_args(sys_argv)
     if args.max_bc_dist is not None and not args.barcodes:
         p.error("--max_bc_dist needs --barcodes")
     if args.bc_candidates is not None and not args.barcodes:
         p.error("--bc_candidates needs --barcodes")
+    if args.bc_correct and not args.barcodes:
+        p.error("--bc_correct needs --barcodes")
+    if args.bc_correct and _max_bc_dist(args) > CORRECT_MAX_BC_DIST:
+        p.error("--bc_correct needs --max_bc_dist <= %d (the correction's weights are exact in 64 bits up to there)"
+                % CORRECT_MAX_BC_DIST)
+    for flag in ("bc_min_posterior", "bc_edit_bits"):
+        if getattr(args, flag) is not None and not args.bc_correct:
+            p.error("--%s needs --bc_correct" % flag)
     return args
 
 
@@ -520,6 +550,43 @@ def _bc_candidates(text):
     if not 1 <= v <= 8:
         raise argparse.ArgumentTypeError("%d is outside 1 .. 8" % v)
     return v
+
+
+def _bc_posterior(text):
+    """--bc_min_posterior as permille (501 .. 1000)"""
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not a number: %r" % text)
+    pm = int(round(v * 1000))
+    if not (0.501 <= v <= 1.0 and 501 <= pm <= 1000):
+        raise argparse.ArgumentTypeError("%s is outside 0.501 .. 1.0" % text)
+    return pm
+
+
+def _bc_edit_bits(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 1 <= v <= 8:
+        raise argparse.ArgumentTypeError("%d is outside 1 .. 8" % v)
+    return v
+
+
+def _correcting(args):
+    return bool(getattr(args, "barcodes", None)) and bool(getattr(args, "bc_correct", False))
+
+
+def _correct_kwargs(args, whitelist):
+    """stage1_run's correction arguments: none without -b or without --bc_correct"""
+    if not (whitelist and _correcting(args)):
+        return {}
+    pm = getattr(args, "bc_min_posterior", None)
+    bits = getattr(args, "bc_edit_bits", None)
+    return dict(corrected_path=args.output + CORRECTED_SUFFIX,
+                bc_min_permille=int(round(BC_MIN_POSTERIOR_DEFAULT * 1000)) if pm is None else pm,
+                bc_edit_bits=BC_EDIT_BITS_DEFAULT if bits is None else bits)
 
 
 def _max_bc_dist(args):

@@ -274,6 +274,13 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
  * KeyError), BDG_E_FORMAT (ValueError), BDG_E_NOSEQ (TypeError) with the rows of the chunks in front of the failure
  * written, like the reference's loop; the message is bdg_last_error(ctxs[0]). */
 #define BDG_STAGE1_WL_CANDIDATES 0x100u    /* bdg_stage1_opts.whitelist: the caller sets bc_candidates */
+/* bdg_stage1_opts.whitelist: abundance-weighted correction (bdg_nearest16_correct's rule over the whole run).  Only with this bit
+ * does the library read bc_edit_bits, bc_min_permille and corrected_path, or write bdg_stage1_result.whitelist_corrected;
+ * max_bc_dist must be 0 .. 3.  The match runs at k = 8 and every context keeps its reads' lists on the device until the last
+ * chunk (42 bytes per read); then the support arrays of all contexts are summed, every list is resolved, and corrected_path
+ * gets "#read_id\tcorrected_barcode\tcorrected_dist\tsupport\tposterior\tstatus" and one row per read in input order (one
+ * header, whatever header_every says).  The main TSV and its columns are the same bytes as without the bit. */
+#define BDG_STAGE1_WL_CORRECT    0x200u
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -292,6 +299,10 @@ typedef struct bdg_stage1_opts {
                                      with k = K and the rows get the column of bdg_format_rows_wlk.  It takes the upper half of what
                                      was a 32-bit max_bc_dist, so the struct keeps its size; without the flag a nonzero upper half
                                      is rejected as an out-of-range max_bc_dist, as it was before. */
+    /* read only with BDG_STAGE1_WL_CORRECT (a caller built against the 40-byte struct never sets it) */
+    uint32_t bc_edit_bits;        /* B of bdg_nearest16_correct, 1 .. 8 */
+    uint32_t bc_min_permille;     /* P of bdg_nearest16_correct, 501 .. 1000 */
+    const char* corrected_path;   /* the per-read correction file */
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -305,6 +316,7 @@ typedef struct bdg_stage1_result {
     double   seconds_wait_format;             /* ... waiting for the formatters / the writer to take a chunk */
     double   seconds_format, seconds_write;   /* busy time of the formatter threads (summed) / of the writer */
     uint64_t whitelist_barcodes;              /* opts->whitelist: rows with a whitelist_barcode (counts[4] of bdg_format_rows_wl) */
+    uint64_t whitelist_corrected;             /* written only with BDG_STAGE1_WL_CORRECT: rows of status exact or corrected */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
@@ -351,6 +363,27 @@ int  bdg_nearest16_topk_dev(bdg_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint
  * n_within 0.  In overlap mode a best-hit match still waiting is queued first; this one is not deferred. */
 int  bdg_nearest16_topk_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t n, uint32_t max_ed, uint32_t k,
                                  uint32_t* d_idx, uint8_t* d_ed, uint16_t* d_n_within);
+/* Abundance-weighted whitelist correction: the nq queries are one whole run.  Per query, L = its top-8 list within D = max_ed
+ * (bdg_nearest16_topk, k = 8) and n = its n_within.  The support s(w) of an entry = the queries whose L[0] is w at distance 0.
+ * Status (BDG_WLC_*):
+ *   none       n == 0                       idx 0xFFFFFFFF, ed -1,      support 0,        permille -1
+ *   exact      L[0].ed == 0                 idx L[0],      ed 0,       support s(L[0]),  permille 1000
+ *   truncated  n > 8 (candidates beyond L)  idx 0xFFFFFFFF, ed L[0].ed, support 0,        permille -1
+ *   otherwise, over j < n: W_j = (min(s(L[j]), 2^24 - 1) + 1) << (edit_bits * (D - L[j].ed)), S = sum W_j, j* = the first j of
+ *   the largest W_j, permille = floor(1000 W_j* / S):
+ *   corrected  1000 W_j* >= min_permille * S  idx L[j*], ed L[j*].ed, support s(L[j*]), permille
+ *   ambiguous  otherwise                     the same fields of L[j*]
+ * One edit makes an entry 2^edit_bits times less likely.  All of it is exact integer arithmetic (W <= 2^48).  BDG_E_ARG at
+ * the call for max_ed > 3, edit_bits outside 1 .. 8, min_permille outside 501 .. 1000 (so a call is always unique) and algo 1;
+ * algo 2 takes D <= 2 as for bdg_nearest16_topk.  Host arrays of nq entries each. */
+#define BDG_WLC_NONE      0
+#define BDG_WLC_EXACT     1
+#define BDG_WLC_CORRECTED 2
+#define BDG_WLC_AMBIGUOUS 3
+#define BDG_WLC_TRUNCATED 4
+int  bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw, uint32_t max_ed,
+                           uint32_t edit_bits, uint32_t min_permille, uint32_t* idx, int8_t* ed, uint32_t* support,
+                           int16_t* permille, uint8_t* status);
 /* Device memory held by the neighbourhood-probe index of the loaded whitelist, in bytes: 0 until a call takes the probe path
  * (automatic mode takes the exhaustive scan while nw * nq stays small, e.g. stage 2's --high_sens pass against ~5,000 centres:
  * no index is ever built then); the deletion-variant part is added by the first probe call with max_ed = 2. */
