@@ -44,6 +44,8 @@ EXPORTS = [
     "bdg_ingest_reads", "bdg_ingest_close", "bdg_format_rows", "bdg_format_rows_wl", "bdg_stage1_run",
     "bdg_cluster_dev", "bdg_assign_reads_dev", "bdg_idstore_new", "bdg_idstore_free", "bdg_idstore_count", "bdg_idstore_append",
     "bdg_idstore_get", "bdg_stage1_collect", "bdg_write_assignments", "bdg_import_stage1_tsv", "bdg_host_free",
+    "bdg_extract_keep_umis", "bdg_keep_observed_umis", "bdg_kept_umis", "bdg_umi_dedup_dev", "bdg_import_stage1_tsv_umi",
+    "bdg_write_molecules",
 ]
 
 
@@ -199,6 +201,12 @@ def load():
     L.bdg_import_stage1_tsv.argtypes = [C.c_char_p, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
     L.bdg_host_free.argtypes = [vp]
     L.bdg_host_free.restype = None
+    L.bdg_extract_keep_umis.argtypes = [vp, C.c_int]
+    L.bdg_keep_observed_umis.argtypes = [vp, vp, u64]
+    L.bdg_kept_umis.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bdg_umi_dedup_dev.argtypes = [vp, vp, vp, vp, u64, vp, u32, u32, u32, vp, vp]
+    L.bdg_import_stage1_tsv_umi.argtypes = [C.c_char_p, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    L.bdg_write_molecules.argtypes = [vp, vp, vp, vp, vp, u64, C.c_char_p]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -316,6 +324,27 @@ class Context:
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.lib.bdg_kept_records(self.h, C.byref(p), C.byref(n)))
         return p.value or 0, int(n.value)
+
+    def extract_keep_umis(self, on=True):
+        """with the kept records, every read's UMI packed into 32 bits on the device (bdg_extract_keep_umis)"""
+        self._check(self.lib.bdg_extract_keep_umis(self.h, 1 if on else 0))
+
+    def keep_observed_umis(self, codes):
+        """the UMI codes of a stage-1 TSV (import_stage1_tsv(..., umis=True)) beside the records keep_observed made"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        self._check(self.lib.bdg_keep_observed_umis(self.h, codes.ctypes.data, len(codes)))
+
+    def kept_umis(self):
+        """-> (device pointer, count) of the kept UMI codes"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.bdg_kept_umis(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, int(n.value)
+
+    def umi_dedup_dev(self, d_rank, d_has, d_umi, n, d_cells, n_cells, umi_len, umi_dist, d_molecule, d_cell_counts):
+        """per-cell UMI deduplication (bdg_umi_dedup_dev): per read the molecule's UMI code, per cell [reads, umi_reads,
+        umis, molecules]"""
+        self._check(self.lib.bdg_umi_dedup_dev(self.h, _ptr(d_rank), _ptr(d_has), _ptr(d_umi), n, _ptr(d_cells), n_cells,
+                                               umi_len, umi_dist, _ptr(d_molecule), _ptr(d_cell_counts)))
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""
@@ -704,6 +733,62 @@ def import_stage1_tsv(path, bc_len=16):
     L.bdg_host_free(pr)
     L.bdg_host_free(pu)
     return ids, rank, usable
+
+
+UMI_NONE = 0xFFFFFFFF
+
+
+def import_stage1_tsv_umis(path, bc_len=16):
+    """import_stage1_tsv plus the UMI column (bdg_import_stage1_tsv_umi) -> (IdStore, rank, usable, UMI codes uint32[n];
+    UMI_NONE where the field is missing or not an ACGT string of 1 .. 14 letters).  ValueError without a UMI column."""
+    L = load()
+    ids = IdStore()
+    pr, pu, pm, n, bad = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    rc = L.bdg_import_stage1_tsv_umi(os.fsencode(path), bc_len, ids.h, C.byref(pr), C.byref(pu), C.byref(pm), C.byref(n),
+                                     C.byref(bad))
+    if rc == E_BADBASE:
+        raise KeyError("the barcode in line %d of %s holds a letter outside ACGT" % (bad.value, path))
+    if rc == E_FORMAT:
+        raise ValueError("%s is empty or has no '#read_id' / 'barcode' / 'UMI' column" % path)
+    if rc != 0:
+        raise BadgerHipError(rc, "cannot read %s" % path)
+    k = int(n.value)
+    out = []
+    for q, t in ((pr, C.c_uint32), (pu, C.c_uint8), (pm, C.c_uint32)):
+        a = np.ctypeslib.as_array(C.cast(q, C.POINTER(t)), shape=(max(k, 1),))[:k].copy() if q.value and k else \
+            np.zeros(0, np.uint32 if t is C.c_uint32 else np.uint8)
+        out.append(a)
+        if q.value:
+            L.bdg_host_free(q)
+    return ids, out[0], out[1].astype(bool), out[2]
+
+
+def umi_code(s):
+    """the packed code of a UMI text (bdg_extract_keep_umis), UMI_NONE for anything but an ACGT string of 1 .. 14 letters"""
+    if not 0 < len(s) <= 14:
+        return UMI_NONE
+    v = 0
+    for c in s:
+        b = "ACGT".find(c)
+        if b < 0:
+            return UMI_NONE
+        v = v << 2 | b
+    return len(s) << 28 | v
+
+
+def write_molecules(ids, rank, has, umi, molecule, path):
+    """<out>_molecules.tsv (bdg_write_molecules)"""
+    L = load()
+    rank = np.ascontiguousarray(rank, dtype=np.uint32)
+    has = np.ascontiguousarray(has, dtype=np.uint8)
+    umi = np.ascontiguousarray(umi, dtype=np.uint32)
+    molecule = np.ascontiguousarray(molecule, dtype=np.uint32)
+    if not len(rank) == len(has) == len(umi) == len(molecule):
+        raise ValueError("write_molecules: arrays differ in length")
+    rc = L.bdg_write_molecules(ids.h, rank.ctypes.data, has.ctypes.data, umi.ctypes.data, molecule.ctypes.data, len(rank),
+                               os.fsencode(path))
+    if rc != 0:
+        raise BadgerHipError(rc, "bdg_write_molecules(%s): %d reads, %d ids" % (path, len(rank), len(ids)))
 
 
 def write_assignments(ids, rank, has, path):

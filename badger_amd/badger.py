@@ -2,7 +2,10 @@
 """Stage 2 CLI: barcode correction, same flags and output file as the reference's badger.py
 (reference badger.py:23-47,62-132), with the edit-distance graph built on the MI355X.
 
-    python -m badger_amd.badger -r out.tsv -d tenX_v3 -l whitelist.txt -c 5000 [-t 1] [-hs]
+    python -m badger_amd.badger -r out.tsv -d tenX_v3 -l whitelist.txt -c 5000 [-t 1] [-hs] [--umi_dedup [--umi_dist 1]]
+
+--umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
+<out>_molecules.tsv and <out>_cells.tsv.
 
 --stats and --ground_truth drive the reference's offline evaluation module (stats.py), which
 is outside the accelerated path; the flags are accepted and rejected with a message.
@@ -48,7 +51,17 @@ def parse_args(args):
                    help="devices the edge build is shared over (one share of the edge list each, no exchange between them); "
                         "default: as many as --threads asks for and the node has (the reference's -tr N fans compare_chunk "
                         "out over N processes, barcode_graph.py:164-189), at least 1")
-    return p.parse_args(args)
+    p.add_argument("--umi_dedup", action="store_true", default=False,
+                   help="also deduplicate UMIs inside each cell: writes <out>_molecules.tsv (per read: UMI and the molecule's "
+                        "representative UMI) and <out>_cells.tsv (per cell: reads, reads with a UMI, UMIs, molecules)")
+    p.add_argument("--umi_dist", type=int, default=None, choices=(0, 1),
+                   help="with --umi_dedup: largest edit distance between two UMIs of one molecule (default 1)")
+    a = p.parse_args(args)
+    if a.umi_dist is not None and not a.umi_dedup:
+        p.error("--umi_dist needs --umi_dedup")
+    if a.umi_dist is None:
+        a.umi_dist = 1
+    return a
 
 
 def edge_build_gpus(args):
@@ -152,13 +165,18 @@ def main(args):
     warm.join()
     st2 = Stage2(args.threshold, device=args.device)
     if args.reads.endswith("tsv"):
-        read_ids, obs_rank, usable = _native.import_stage1_tsv(args.reads, bc_len)      # (import_tsv below, natively)
+        if args.umi_dedup:
+            read_ids, obs_rank, usable, umis = _native.import_stage1_tsv_umis(args.reads, bc_len)
+        else:
+            read_ids, obs_rank, usable = _native.import_stage1_tsv(args.reads, bc_len)      # (import_tsv below, natively)
         logger.info("Imported barcodes from file")
         logger.info("Initializing Graph")
         # the observed barcodes go to the device as records (bdg_keep_observed): from here on the TSV route is the route of
         # read input - counting, edges, clustering and the per-read assignment run there
         ctx = _native.default_context(args.device)
         ctx.keep_observed(obs_rank, usable)
+        if args.umi_dedup:
+            ctx.keep_observed_umis(umis)                  # (the UMI codes beside the records)
         mark("import")
         st2.count_device(ctx)
         mark("count")
@@ -170,6 +188,7 @@ def main(args):
         # Like the reference (:112-117) one thread keeps every SAM / BAM record, several skip secondary / supplementary ones.
         ctx = _native.default_context(args.device)
         ctx.extract_keep_records(True)
+        ctx.extract_keep_umis(args.umi_dedup)             # (every chunk's UMIs packed beside its records)
         logger.info("Extracting from " + args.reads)
         read_ids = _native.IdStore()
         umi_len = BARCODE_CALLING_MODES[args.data_type](device=args.device).UMI_LEN_10X
@@ -179,6 +198,7 @@ def main(args):
             _native.stage1_collect(ctx, args.reads, umi_len, read_ids, threads=args.threads,
                                    skip_secondary=args.threads != 1)
         except BaseException:
+            ctx.extract_keep_umis(False)
             ctx.extract_keep_records(False)
             raise
         mark("extract")
@@ -196,7 +216,13 @@ def main(args):
     st2.cluster(true_barcodes, barcode_list, args.n_cells, bc_len, args.interval)
     mark("cluster")
     logger.info("Clustering done")
-    st2.output_file_from_device(read_ids, from_device, args.output, args.high_sens)
+    st2.output_file_from_device(read_ids, from_device, args.output, args.high_sens, keep_reads=args.umi_dedup)
+    if args.umi_dedup:
+        from .umi_dedup import UMI_LEN
+        molecules = st2.umi_dedup_from_device(read_ids, args.output, UMI_LEN[args.data_type], args.umi_dist)
+        mark("umi_dedup")
+        logger.info("Molecules: %d" % molecules)
+        from_device.extract_keep_umis(False)
     from_device.extract_keep_records(False)
     disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
     st2.release_device()

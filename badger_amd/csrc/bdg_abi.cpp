@@ -33,6 +33,9 @@ int bdg_rows_of_launch(bdg_ctx*, const uint32_t*, uint32_t, const uint32_t*, uin
 int bdg_cluster_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, int32_t*);
 int bdg_assign_reads_launch(bdg_ctx*, const bdg_extract_rec*, uint64_t, const uint32_t*, uint32_t, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*);
 int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, const uint32_t*, uint32_t, uint64_t*);
+int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
+int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t,
+                         uint32_t*, uint32_t*);
 
 static thread_local std::string g_err_noctx;
 
@@ -276,7 +279,7 @@ void bdg_free(bdg_ctx* ctx)
     DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
                        &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
                        &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs,
-                       &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
+                       &ctx->x_allumis, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
         for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match }) if (b->p) (void)hipFree(b->p);
@@ -569,6 +572,25 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
             ctx->x_allrecs = nb;
         }
         BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(ctx->x_allrecs.p) + have, sl.d_recs.p, add, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx->keep_umis) {
+            // the chunk's UMIs, packed from its bases while they are still here (grown like the records)
+            const size_t uhave = 4 * (size_t)ctx->x_allumis_n, uadd = 4 * (size_t)sl.n;
+            if (uhave + uadd > ctx->x_allumis.bytes) {
+                DevBuf nb;
+                size_t want = (uhave + uadd) * 2;
+                if (want < (size_t(8) << 20)) want = size_t(8) << 20;
+                if ((rc = bdg_reserve(ctx, nb, want))) return rc;
+                if (uhave) BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.p, ctx->x_allumis.p, uhave, hipMemcpyDeviceToDevice, ctx->stream));
+                BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                if (ctx->x_allumis.p) (void)hipFree(ctx->x_allumis.p);
+                ctx->x_allumis = nb;
+            }
+            if ((rc = bdg_umi_pack_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
+                                          static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n,
+                                          static_cast<uint32_t*>(ctx->x_allumis.p) + ctx->x_allumis_n)))
+                return rc;
+            ctx->x_allumis_n += sl.n;
+        }
         ctx->x_allrecs_n += sl.n;
     }
     return BDG_OK;
@@ -786,12 +808,63 @@ int bdg_extract_keep_records(bdg_ctx* ctx, int on)
     if (!ctx) return BDG_E_ARG;
     ctx->keep_records = on != 0;
     ctx->x_allrecs_n = 0;
+    ctx->x_allumis_n = 0;
     if (!on && ctx->x_allrecs.p) {
         BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         (void)hipFree(ctx->x_allrecs.p);
         ctx->x_allrecs = DevBuf();
     }
+    if (!on && ctx->x_allumis.p) {
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(ctx->x_allumis.p);
+        ctx->x_allumis = DevBuf();
+    }
     return BDG_OK;
+}
+
+int bdg_extract_keep_umis(bdg_ctx* ctx, int on)
+{
+    if (!ctx) return BDG_E_ARG;
+    ctx->keep_umis = on != 0;
+    ctx->x_allumis_n = 0;
+    return BDG_OK;
+}
+
+int bdg_keep_observed_umis(bdg_ctx* ctx, const uint32_t* codes, uint64_t n)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && !codes) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n != ctx->x_allrecs_n) return bdg_fail(ctx, BDG_E_ARG, "UMI codes and kept records differ in number");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->x_allumis_n = 0;
+    if (n == 0) return BDG_OK;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->x_allumis, 4 * (size_t)n))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->x_allumis.p, codes, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->x_allumis_n = n;
+    return BDG_OK;
+}
+
+int bdg_kept_umis(bdg_ctx* ctx, const uint32_t** d_umis, uint64_t* n)
+{
+    if (!ctx || !d_umis || !n) return BDG_E_ARG;
+    *d_umis = static_cast<const uint32_t*>(ctx->x_allumis.p);
+    *n = ctx->x_allumis_n;
+    return BDG_OK;
+}
+
+int bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
+                      const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
+                      uint32_t* d_molecule, uint32_t* d_cell_counts)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && (!d_rank || !d_has || !d_umi || !d_molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n_cells && (!d_cells || !d_cell_counts)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
+    if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_umi_dedup_launch(ctx, d_rank, d_has, d_umi, n, d_cells, n_cells, umi_len, umi_dist, d_molecule, d_cell_counts);
 }
 
 int bdg_keep_observed(bdg_ctx* ctx, const uint32_t* rank, const uint8_t* usable, uint64_t n)
@@ -800,7 +873,7 @@ int bdg_keep_observed(bdg_ctx* ctx, const uint32_t* rank, const uint8_t* usable,
     if (n && (!rank || !usable)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = bdg_extract_keep_records(ctx, 1);                       // (an empty array; what was kept before is dropped)
+    int rc = bdg_extract_keep_records(ctx, 1);                       // (an empty array; what was kept before is dropped, UMIs too)
     if (rc || n == 0) return rc;
     if ((rc = bdg_reserve(ctx, ctx->x_allrecs, sizeof(bdg_extract_rec) * n))) return rc;
     // the two host arrays through the scratch buffer (pageable memory: the copies return when the data has left it)

@@ -94,6 +94,10 @@ struct bdg_ctx {
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
     DevBuf x_allrecs; uint64_t x_allrecs_n = 0;
+    // with them (bdg_extract_keep_umis), every read's UMI packed into 32 bits (umi_kernels.hip), in the same order
+    bool keep_umis = false;
+    DevBuf x_allumis; uint64_t x_allumis_n = 0;
+    DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -719,10 +719,14 @@ int bdg_stage1_collect(bdg_ctx* ctx, const char* in_path, const bdg_stage1_opts*
 // "barcode" by the first line's names, repeated header rows skipped (:104,107), an empty / NA barcode is '*', a barcode of
 // bc_len + 1 letters loses its last one (:108-109).  usable[i] = the read has a barcode of bc_len letters; its rank
 // (common.py:21-25) or BDG_E_BADBASE for a letter outside ACGT (the reference's rank() raises KeyError).
-int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, uint32_t** rank_out, uint8_t** usable_out, uint64_t* n_out, uint64_t* bad_line)
+// umi_out != null: also the UMI column, per read its packed code (umi_kernels.hip: len << 28 | 2-bit letters, first letter
+// most significant) or 0xFFFFFFFF for a field that is missing or not an ACGT string of 1 .. 14 letters; no UMI column is BDG_E_FORMAT
+static int import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, uint32_t** rank_out, uint8_t** usable_out,
+                             uint32_t** umi_out, uint64_t* n_out, uint64_t* bad_line)
 {
     if (!path || !ids || !rank_out || !usable_out || !n_out || bc_len == 0 || bc_len > 16) return BDG_E_ARG;
     *rank_out = nullptr; *usable_out = nullptr; *n_out = 0;
+    if (umi_out) *umi_out = nullptr;
     if (bad_line) *bad_line = 0;
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return BDG_E_ARG;
@@ -737,7 +741,7 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
     const char* const end = begin + size;
 
     // the first line names the columns
-    int ci = -1, cb = -1;
+    int ci = -1, cb = -1, cu = -1;
     const char* body;
     {
         const char* nl = static_cast<const char*>(memchr(begin, '\n', size));
@@ -750,16 +754,18 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
             const size_t l = (size_t)((t ? t : le) - q);
             if (l == 8 && memcmp(q, "#read_id", 8) == 0 && ci < 0) ci = col;
             if (l == 7 && memcmp(q, "barcode", 7) == 0 && cb < 0) cb = col;
+            if (umi_out && l == 3 && memcmp(q, "UMI", 3) == 0 && cu < 0) cu = col;
             if (!t) break;
             q = t + 1;
         }
-        if (ci < 0 || cb < 0) { munmap(map, size); return BDG_E_FORMAT; }
+        if (ci < 0 || cb < 0 || (umi_out && cu < 0)) { munmap(map, size); return BDG_E_FORMAT; }
     }
 
     // the lines behind it, in ranges cut at line ends: one thread per range, results joined in file order
     struct Part {
         const char* lo; const char* hi;
         std::vector<uint32_t> ranks; std::vector<uint8_t> usable; std::vector<char> text; std::vector<uint32_t> idlen;
+        std::vector<uint32_t> umis;
         uint64_t lines = 0, bad = 0;                     // lines seen; 1-based line (inside the range) of the first bad letter
     };
     const size_t body_bytes = (size_t)(end - body);
@@ -788,14 +794,15 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
             const char* next = nl ? nl + 1 : pt.hi;
             if (le > p && le[-1] == '\r') --le;
             ++pt.lines;
-            const char* fs[2] = { nullptr, nullptr }; size_t fl[2] = { 0, 0 };
+            const char* fs[3] = { nullptr, nullptr, nullptr }; size_t fl[3] = { 0, 0, 0 };
             int col = 0;
             for (const char* q = p;; ++col) {
                 const char* t = static_cast<const char*>(memchr(q, '\t', (size_t)(le - q)));
                 const size_t l = (size_t)((t ? t : le) - q);
                 if (col == ci) { fs[0] = q; fl[0] = l; }
                 if (col == cb) { fs[1] = q; fl[1] = l; }
-                if (!t || (fs[0] && fs[1])) break;
+                if (col == cu) { fs[2] = q; fl[2] = l; }
+                if (!t || (fs[0] && fs[1] && (cu < 0 || fs[2]))) break;
                 q = t + 1;
             }
             const bool blank = le == p;
@@ -828,6 +835,23 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
             pt.text.insert(pt.text.end(), fs[0], fs[0] + fl[0]);
             pt.idlen.push_back((uint32_t)fl[0]);
             pt.ranks.push_back(r); pt.usable.push_back(ok);
+            if (umi_out) {
+                // (a missing field, or one pandas reads as missing, is no ACGT string either)
+                const char* u = fs[2]; size_t ul = u ? fl[2] : 0;
+                if (ul >= 2 && u[0] == '"' && u[ul - 1] == '"') { ++u; ul -= 2; }
+                uint32_t code = 0xFFFFFFFFu;
+                if (ul >= 1 && ul <= 14) {
+                    uint32_t v = 0; size_t j = 0;
+                    for (; j < ul; ++j) {
+                        uint32_t c;
+                        switch (u[j]) { case 'A': c = 0; break; case 'C': c = 1; break; case 'G': c = 2; break; case 'T': c = 3; break; default: c = 4; }
+                        if (c == 4) break;
+                        v = v << 2 | c;
+                    }
+                    if (j == ul) code = (uint32_t)ul << 28 | v;
+                }
+                pt.umis.push_back(code);
+            }
         }
     };
     {
@@ -845,13 +869,19 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
     }
     *rank_out = static_cast<uint32_t*>(malloc(sizeof(uint32_t) * (n ? n : 1)));
     *usable_out = static_cast<uint8_t*>(malloc(n ? n : 1));
-    if (!*rank_out || !*usable_out) { free(*rank_out); free(*usable_out); *rank_out = nullptr; *usable_out = nullptr; return BDG_E_NOMEM; }
+    if (umi_out) *umi_out = static_cast<uint32_t*>(malloc(sizeof(uint32_t) * (n ? n : 1)));
+    if (!*rank_out || !*usable_out || (umi_out && !*umi_out)) {
+        free(*rank_out); free(*usable_out); *rank_out = nullptr; *usable_out = nullptr;
+        if (umi_out) { free(*umi_out); *umi_out = nullptr; }
+        return BDG_E_NOMEM;
+    }
     ids->text.reserve(ids->text.size() + text_bytes);
     ids->off.reserve(ids->off.size() + n);
     size_t at = 0;
     for (Part& pt : parts) {
         const size_t m = pt.ranks.size();
         if (m) { memcpy(*rank_out + at, pt.ranks.data(), sizeof(uint32_t) * m); memcpy(*usable_out + at, pt.usable.data(), m); }
+        if (m && umi_out) memcpy(*umi_out + at, pt.umis.data(), sizeof(uint32_t) * m);
         at += m;
         uint64_t o = ids->text.size();
         ids->text.insert(ids->text.end(), pt.text.begin(), pt.text.end());
@@ -862,7 +892,49 @@ int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, u
     return BDG_OK;
 }
 
+int bdg_import_stage1_tsv(const char* path, uint32_t bc_len, bdg_idstore* ids, uint32_t** rank_out, uint8_t** usable_out, uint64_t* n_out, uint64_t* bad_line)
+{
+    return import_stage1_tsv(path, bc_len, ids, rank_out, usable_out, nullptr, n_out, bad_line);
+}
+
+int bdg_import_stage1_tsv_umi(const char* path, uint32_t bc_len, bdg_idstore* ids, uint32_t** rank_out, uint8_t** usable_out,
+                              uint32_t** umi_out, uint64_t* n_out, uint64_t* bad_line)
+{
+    if (!umi_out) return BDG_E_ARG;
+    return import_stage1_tsv(path, bc_len, ids, rank_out, usable_out, umi_out, n_out, bad_line);
+}
+
 void bdg_host_free(void* p) { free(p); }
+
+int bdg_write_molecules(const bdg_idstore* ids, const uint32_t* rank, const uint8_t* has, const uint32_t* umi, const uint32_t* molecule,
+                        uint64_t n, const char* path)
+{
+    if (!ids || !path || (n && (!rank || !has || !umi || !molecule)) || n != bdg_idstore_count(ids)) return BDG_E_ARG;
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return BDG_E_ARG;
+    // a read has a molecule exactly when its UMI was usable: both columns are '*' together
+    auto umi_len = [](uint32_t c) -> uint64_t { return c == 0xFFFFFFFFu ? 1 : c >> 28; };
+    auto put_umi = [](uint32_t c, char* o) -> char* {
+        if (c == 0xFFFFFFFFu) { *o++ = '*'; return o; }
+        const uint32_t L = c >> 28;
+        for (uint32_t j = 0; j < L; ++j) *o++ = "ACGT"[(c >> (2 * (L - 1 - j))) & 3u];
+        return o;
+    };
+    const bool ok = write_id_rows(fd, "readID\tbarcode\tUMI\tmolecule", ids, n, 16 + 1 + 15 + 1 + 15,
+                                  [&](uint64_t i) -> uint64_t {
+                                      const uint32_t m = molecule[i];
+                                      return (has[i] ? 16 : 1) + 2 + umi_len(m == 0xFFFFFFFFu ? m : umi[i]) + umi_len(m);
+                                  },
+                                  [&](uint64_t i, char* o) -> char* {
+                                      if (has[i]) { const uint32_t r = rank[i]; for (int b = 0; b < 16; ++b) *o++ = "ACGT"[(r >> (2 * b)) & 3u]; }
+                                      else *o++ = '*';
+                                      const uint32_t m = molecule[i];
+                                      *o++ = '\t'; o = put_umi(m == 0xFFFFFFFFu ? m : umi[i], o);
+                                      *o++ = '\t'; o = put_umi(m, o);
+                                      return o;
+                                  });
+    return ok ? BDG_OK : BDG_E_ARG;
+}
 
 int bdg_write_assignments(const bdg_idstore* ids, const uint32_t* rank, const uint8_t* has, uint64_t n, const char* path)
 {

@@ -1,0 +1,257 @@
+// Per-cell UMI deduplication on the device (stage 2's --umi_dedup; the rule in badger_amd/umi_dedup.py).
+//
+//   pack     k_umi_pack: per read of an extraction chunk, the UMI stage 1 would print (the strand's text sliced as
+//            bdg_format_rows slices it) packed into 32 bits while the chunk's bases are still on the device: len << 28 |
+//            2-bit letters, first letter most significant, UMI_NONE for no ACGT string of 1..14 letters.  The numeric order of
+//            the codes is the rule's UMI order (length, then A < C < G < T).
+//   insert   k_umi_insert: per read with a cell and a usable UMI, the key cell ordinal << 32 | code goes into an open-
+//            addressing table (one compare-and-swap claims a slot, an add counts the read), the read keeps its slot.  The
+//            table's slots are the distinct (cell, UMI) pairs with their read counts; no sort, no scan.
+//   parent   k_umi_parent: per distinct pair, every string at distance 1 (3L substitutions, the distinct deletions, the
+//            distinct insertions; only lengths inside the window) is looked up in the same table: a found neighbour that is a
+//            parent candidate competes on n << 32 | ~code, the highest wins.  A thread writes only its own slot's parent, so
+//            the result is the same in every run.  Work per pair is bounded (at most 3 * 14 + 14 + 4 * 15 probes) whatever
+//            the size of its cell.
+//   root     k_umi_root: every pair follows its parents to the root (rank rises strictly along the way).
+//   results  k_umi_reads: per read the root's code; k_umi_insert and k_umi_cells count reads, reads with a UMI, distinct
+//            UMIs and molecules per cell, summed inside the wave before the atomic (one hot cell is one address).
+#include "bdg_common.hpp"
+
+namespace {
+
+constexpr uint32_t UMI_NONE = 0xFFFFFFFFu;
+constexpr unsigned long long EMPTY = ~0ull;            // (a key's cell ordinal is below 2^32 - 1 and its code is not UMI_NONE)
+constexpr uint32_t MAX_LEN = 14;
+
+__device__ __forceinline__ uint32_t slot_of(unsigned long long k, uint32_t mask)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (uint32_t)k & mask;
+}
+
+// counts[key * 4 + field] += 1 for every lane whose key is not UMI_NONE: lanes with the same key are summed first, one
+// lane per distinct key adds.  Every lane of the wave calls.
+__device__ __forceinline__ void wave_count(uint32_t* __restrict__ counts, uint32_t key, uint32_t field)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long todo = __ballot(key != UMI_NONE);
+    while (todo) {
+        const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+        const uint32_t lk = __shfl(key, (int)leader);
+        const unsigned long long peers = __ballot(key == lk) & todo;
+        if (lane == leader) atomicAdd(&counts[(size_t)lk * 4u + field], (uint32_t)__popcll(peers));
+        todo &= ~peers;
+    }
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_pack(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, const bdg_extract_rec* __restrict__ recs,
+                uint32_t n, uint32_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bdg_extract_rec r = recs[i];
+    uint32_t code = UMI_NONE;
+    if (r.valid) {
+        const uint64_t o = off[i];
+        const int64_t L = (int64_t)(off[i + 1] - o);
+        const int64_t a = r.umi_start < 0 ? 0 : (r.umi_start > L ? L : r.umi_start);
+        const int64_t b = r.umi_end < 0 ? 0 : (r.umi_end > L ? L : r.umi_end);
+        const bool rev = (r.flags & BDG_FLAG_REV) != 0;
+        if (b > a && b - a <= (int64_t)MAX_LEN) {
+            uint32_t v = 0;
+            bool ok = true;
+            for (int64_t x = a; x < b; ++x) {
+                const uint8_t c = rev ? bases[o + (uint64_t)(L - 1 - x)] : bases[o + (uint64_t)x];
+                uint32_t l;
+                switch (c) { case 'A': l = 0; break; case 'C': l = 1; break; case 'G': l = 2; break; case 'T': l = 3; break; default: l = 4; }
+                if (l == 4u) { ok = false; break; }
+                v = v << 2 | (rev ? 3u - l : l);                 // (the reverse complement: A <-> T, C <-> G)
+            }
+            if (ok) code = (uint32_t)(b - a) << 28 | v;
+        }
+    }
+    out[i] = code;
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_clear(unsigned long long* __restrict__ keys, uint32_t* __restrict__ cnt, uint32_t P)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < P) { keys[s] = EMPTY; cnt[s] = 0u; }
+}
+
+// the read's cell ordinal (its assigned barcode's place among the cells, ascending ranks), UMI_NONE for none
+__device__ __forceinline__ uint32_t cell_of(uint32_t rank, const uint32_t* __restrict__ cells, uint32_t ncells)
+{
+    uint32_t lo = 0, hi = ncells;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (cells[mid] < rank) lo = mid + 1; else hi = mid; }
+    return lo < ncells && cells[lo] == rank ? lo : UMI_NONE;
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_insert(const uint32_t* __restrict__ rank, const uint8_t* __restrict__ has, const uint32_t* __restrict__ umi, uint64_t n,
+                  const uint32_t* __restrict__ cells, uint32_t ncells, uint32_t lo_len, uint32_t hi_len,
+                  unsigned long long* __restrict__ keys, uint32_t* __restrict__ cnt, uint32_t mask,
+                  uint32_t* __restrict__ read_slot, uint32_t* __restrict__ counts)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256ull + threadIdx.x;      // (every lane stays for the wave's counts)
+    uint32_t c = UMI_NONE, slot = UMI_NONE;
+    if (i < n) {
+        if (has[i]) c = cell_of(rank[i], cells, ncells);
+        const uint32_t code = umi[i], len = code >> 28;
+        if (c != UMI_NONE && code != UMI_NONE && len >= lo_len && len <= hi_len) {
+            const unsigned long long k = (unsigned long long)c << 32 | code;
+            uint32_t h = slot_of(k, mask);
+            for (;;) {                                                    // (never full: twice as many slots as reads)
+                const unsigned long long old = atomicCAS(&keys[h], EMPTY, k);
+                if (old == EMPTY || old == k) { atomicAdd(&cnt[h], 1u); slot = h; break; }
+                h = (h + 1u) & mask;
+            }
+        }
+        read_slot[i] = slot;
+    }
+    wave_count(counts, c, 0u);
+    wave_count(counts, slot != UMI_NONE ? c : UMI_NONE, 1u);
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_parent(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ cnt, uint32_t P, uint32_t mask,
+                  uint32_t lo_len, uint32_t hi_len, uint32_t dist, uint32_t* __restrict__ par)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= P) return;
+    const unsigned long long k = keys[s];
+    if (k == EMPTY) return;
+    const unsigned long long cell = k & 0xFFFFFFFF00000000ull;
+    const uint32_t code = (uint32_t)k, L = code >> 28, x = code & 0x0FFFFFFFu, n = cnt[s];
+    unsigned long long best = 0;
+    uint32_t bslot = s;
+    auto probe = [&](uint32_t c2) {
+        const unsigned long long k2 = cell | c2;
+        for (uint32_t h = slot_of(k2, mask);; h = (h + 1u) & mask) {
+            const unsigned long long e = keys[h];
+            if (e == EMPTY) return;
+            if (e != k2) continue;
+            const uint32_t m = cnt[h];
+            // a parent candidate: n(a) >= 2 n(b) - 1 and (n(a), a) above (n(b), b); the highest (n, smaller code) wins
+            if ((unsigned long long)m + 1ull >= 2ull * n && (m > n || (m == n && c2 < code))) {
+                const unsigned long long pr = (unsigned long long)m << 32 | (uint32_t)~c2;
+                if (pr > best) { best = pr; bslot = h; }
+            }
+            return;
+        }
+    };
+    if (dist >= 1u) {
+        for (uint32_t p = 0; p < L; ++p) {                               // substitutions
+            const uint32_t sh = 2u * (L - 1u - p), cur = (x >> sh) & 3u;
+            for (uint32_t b = 0; b < 4u; ++b)
+                if (b != cur) probe(L << 28 | (x & ~(3u << sh)) | b << sh);
+        }
+        if (L >= 2u && L - 1u >= lo_len) {                               // deletions, once per run of equal letters
+            for (uint32_t p = 0; p < L; ++p) {
+                const uint32_t sh = 2u * (L - 1u - p);
+                if (p > 0u && ((x >> sh) & 3u) == ((x >> (sh + 2u)) & 3u)) continue;
+                probe((L - 1u) << 28 | (x >> (sh + 2u)) << sh | (x & ((1u << sh) - 1u)));
+            }
+        }
+        if (L + 1u <= hi_len) {                                          // insertions before letter p (p = L: at the end)
+            for (uint32_t p = 0; p <= L; ++p) {
+                const uint32_t sh = 2u * (L - p);
+                const uint32_t head = x >> sh, tail = x & ((1u << sh) - 1u);
+                for (uint32_t b = 0; b < 4u; ++b) {
+                    if (p < L && ((x >> (sh - 2u)) & 3u) == b) continue;   // (the same string as inserting b after that letter)
+                    probe((L + 1u) << 28 | (head << 2 | b) << sh | tail);
+                }
+            }
+        }
+    }
+    par[s] = bslot;
+}
+
+// root[s]: the end of s's parent chain (the parents stay as they are: every thread reads the same array)
+__global__ __launch_bounds__(256)
+void k_umi_root(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ par, uint32_t P, uint32_t* __restrict__ root)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= P || keys[s] == EMPTY) return;
+    uint32_t r = s;
+    for (uint32_t p = par[r]; p != r; p = par[r]) r = p;
+    root[s] = r;
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_cells(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ root, uint32_t P, uint32_t* __restrict__ counts)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    uint32_t c = UMI_NONE;
+    bool is_root = false;
+    if (s < P) {
+        const unsigned long long k = keys[s];
+        if (k != EMPTY) { c = (uint32_t)(k >> 32); is_root = root[s] == s; }
+    }
+    wave_count(counts, c, 2u);
+    wave_count(counts, is_root ? c : UMI_NONE, 3u);
+}
+
+__global__ __launch_bounds__(256)
+void k_umi_reads(const uint32_t* __restrict__ read_slot, uint64_t n, const unsigned long long* __restrict__ keys,
+                 const uint32_t* __restrict__ root, uint32_t* __restrict__ mol)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256ull + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = read_slot[i];
+    mol[i] = s == UMI_NONE ? UMI_NONE : (uint32_t)keys[root[s]];
+}
+
+}  // namespace
+
+int bdg_umi_pack_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
+                        uint32_t* d_out)
+{
+    if (n == 0) return BDG_OK;
+    ScopedKernelTimer tm(ctx, "k_umi_pack");
+    hipLaunchKernelGGL(k_umi_pack, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_bases, d_off, d_recs, n, d_out);
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int bdg_umi_dedup_launch(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
+                         const uint32_t* d_cells, uint32_t ncells, uint32_t umi_len, uint32_t umi_dist,
+                         uint32_t* d_mol, uint32_t* d_counts)
+{
+    hipStream_t st = ctx->stream;
+    if (ncells) BDG_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 16 * (size_t)ncells, st));
+    if (n == 0) return BDG_OK;
+    // twice as many slots as reads (a power of two): a probe that misses ends after about two slots
+    uint64_t P = 1024;
+    while (P < 2 * n) P <<= 1;
+    if (P > (1ull << 31)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the UMI table takes (2^30)");
+    // workspace: keys u64 [P] | counts u32 [P] (then the roots) | parents u32 [P] | read slots u32 [n]
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->u_ws, 16 * (size_t)P + 4 * (size_t)n + 256))) return rc;
+    auto* keys = static_cast<unsigned long long*>(ctx->u_ws.p);
+    auto* cnt = reinterpret_cast<uint32_t*>(keys + P);
+    auto* par = cnt + P;
+    auto* read_slot = par + P;
+    const uint32_t lo_len = umi_len > 3u ? umi_len - 2u : 1u, hi_len = umi_len + 2u < MAX_LEN ? umi_len + 2u : MAX_LEN;
+    const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_insert");
+        hipLaunchKernelGGL(k_umi_clear, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P);
+        hipLaunchKernelGGL(k_umi_insert, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_umi, n, d_cells, ncells, lo_len, hi_len,
+                           keys, cnt, mask, read_slot, d_counts);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_parent");
+        hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, mask, lo_len, hi_len, umi_dist, par);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_results");
+        hipLaunchKernelGGL(k_umi_root, dim3(gp), dim3(256), 0, st, keys, par, (uint32_t)P, cnt);
+        hipLaunchKernelGGL(k_umi_cells, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, d_counts);
+        hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, read_slot, n, keys, cnt, d_mol);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}

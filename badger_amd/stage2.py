@@ -410,9 +410,10 @@ class Stage2:
         ids = read_ids if isinstance(read_ids, _native.IdStore) else _native.IdStore(read_ids)
         _native.write_assignments(ids, rank, got, out + "_output_file.tsv")
 
-    def output_file_from_device(self, ids, ctx, out, high_sens):
+    def output_file_from_device(self, ids, ctx, out, high_sens, keep_reads=False):
         """the same straight from the extraction records the context kept: per read, the position of its barcode among the
-        distinct ones and what that was corrected to, on the device (bdg_assign_reads_dev); the host only writes the file"""
+        distinct ones and what that was corrected to, on the device (bdg_assign_reads_dev); the host only writes the file.
+        keep_reads: the per-read cells stay on the device for umi_dedup_from_device."""
         assigned, has = self.assigned(high_sens)
         ptr, n = ctx.kept_records()
         dev = self._dev
@@ -423,9 +424,41 @@ class Stage2:
         if n:
             ctx.assign_reads_dev(ptr, n, dev["uniq"], len(self.uniq), d_assigned, d_has, d_rank, d_got)
         rank, got = d_rank.to_host(n), d_got.to_host(n)
-        for d in (d_assigned, d_has, d_rank, d_got):
+        for d in (d_assigned, d_has) + (() if keep_reads else (d_rank, d_got)):
             d.free()
+        if keep_reads:
+            self._reads = {"ctx": ctx, "d_rank": d_rank, "d_got": d_got, "rank": rank, "got": got,
+                           "cells": np.unique(assigned[has])}        # every barcode a read can be assigned to, ascending ranks
         _native.write_assignments(ids, rank, got, out + "_output_file.tsv")
+
+    def umi_dedup_from_device(self, ids, out, umi_len, umi_dist):
+        """--umi_dedup: the reads' molecules inside their cells (bdg_umi_dedup_dev over the cells output_file_from_device left
+        on the device and the UMI codes the context kept), <out>_molecules.tsv written natively, <out>_cells.tsv (one line per
+        cell with a read, ascending barcode).  Returns the number of molecules."""
+        r, self._reads = self._reads, None
+        ctx, cells = r["ctx"], np.ascontiguousarray(r["cells"], dtype=np.uint32)
+        ptr, n = ctx.kept_umis()
+        if n != len(r["rank"]):
+            raise RuntimeError("%d UMI codes kept for %d reads" % (n, len(r["rank"])))
+        nc = len(cells)
+        d_cells = _native.DeviceArray.from_host(ctx, cells)
+        d_mol = _native.DeviceArray(ctx, max(n, 1), np.uint32)
+        d_cnt = _native.DeviceArray(ctx, (max(nc, 1), 4), np.uint32)
+        ctx.umi_dedup_dev(r["d_rank"], r["d_got"], ptr, n, d_cells, nc, umi_len, umi_dist, d_mol, d_cnt)
+        mol, cnt = d_mol.to_host(n), d_cnt.to_host(nc)
+        umi = np.zeros(n, np.uint32)
+        if n:
+            ctx._check(ctx.lib.bdg_mem_to_host(ctx.h, umi.ctypes.data, ptr, umi.nbytes))
+        for d in (d_cells, d_mol, d_cnt, r["d_rank"], r["d_got"]):
+            d.free()
+        _native.write_molecules(ids, r["rank"], r["got"], umi, mol, out + "_molecules.tsv")
+        seen = np.flatnonzero(cnt[:, 0] > 0) if nc else np.zeros(0, np.intp)
+        names = unrank_many(cells[seen])
+        with open(out + "_cells.tsv", "w") as f:
+            f.write("barcode\treads\tumi_reads\tumis\tmolecules\n")
+            f.write("".join("%s\t%d\t%d\t%d\t%d\n" % ((names[j],) + tuple(int(x) for x in cnt[seen[j]]))
+                            for j in sorted(range(len(seen)), key=names.__getitem__)))
+        return int(cnt[:, 3].sum()) if nc else 0
 
     def release_device(self):
         dev = getattr(self, "_dev", None)

@@ -1,0 +1,235 @@
+"""--umi_dedup on the GPU: stage 2's <out>_molecules.tsv and <out>_cells.tsv equal what badger_amd/umi_dedup.py (the rule,
+in plain Python) makes of the same reads, from a stage-1 TSV and from reads (both routes give the same files), with one hot
+cell, over several contexts; and nothing that stage 2 wrote before moves."""
+import io
+import os
+import random
+from contextlib import redirect_stdout
+
+import pytest
+
+from badger_amd import badger, extract_raw_barcodes as erb
+from badger_amd import umi_dedup as ud
+
+pytestmark = pytest.mark.gpu
+
+HEADER = "#read_id\tbarcode\tUMI\tBC_score\tvalid_UMI\tstrand\tpolyT_start\tR1_end"
+R1 = "CTACACGACGCTCTTCCGATCT"
+_COMP = str.maketrans("ACGTN", "TGCAN")
+
+
+def _whitelist(tmp, n, seed):
+    rng = random.Random(seed)
+    wl = sorted({"".join(rng.choice("ACGT") for _ in range(16)) for _ in range(n)})
+    path = str(tmp / ("wl_%d.txt" % seed))
+    with open(path, "w") as f:
+        f.write("\n".join(wl) + "\n")
+    return wl, path
+
+
+def _noisy(u, rng, p_sub=0.03, p_ins=0.01, p_del=0.015, p_n=0.002):
+    out = []
+    for c in u:
+        x = rng.random()
+        if x < p_del:
+            continue
+        if x < p_del + p_sub:
+            c = rng.choice([b for b in "ACGT" if b != c])
+        elif x < p_del + p_sub + p_n:
+            c = "N"
+        out.append(c)
+        if rng.random() < p_ins:
+            out.append(rng.choice("ACGT"))
+    return "".join(out)
+
+
+def _planted(cells, n_reads, rng):
+    """(barcode, UMI) per read: molecules of 1 - 20 reads in the given cells, nanopore-like UMI errors, some barcodes one
+    substitution off, some reads outside every cell or without a barcode"""
+    out = []
+    while len(out) < n_reads:
+        cell = rng.choice(cells)
+        true = "".join(rng.choice("ACGT") for _ in range(12))
+        for _ in range(rng.randint(1, 20)):
+            bc = cell
+            x = rng.random()
+            if x < 0.05:
+                p = rng.randrange(16)
+                bc = bc[:p] + rng.choice([b for b in "ACGT" if b != bc[p]]) + bc[p + 1:]
+            elif x < 0.08:
+                bc = "".join(rng.choice("ACGT") for _ in range(16))
+            out.append((bc, _noisy(true, rng)))
+    return out[:n_reads]
+
+
+def _write_tsv(path, pairs, rng):
+    with open(path, "w") as f:
+        f.write(HEADER + "\n")
+        for i, (bc, umi) in enumerate(pairs):
+            if rng.random() < 0.02:
+                f.write("read_%d\t*\t*\t-1\tFalse\t.\t-1\t-1\n" % i)
+            else:
+                f.write("read_%d\t%s\t%s\t0\tFalse\t+\t%d\t%d\n" % (i, bc, umi, 60, 22))
+
+
+def _stage2(argv):
+    """stdout of an in-process run (the log lines go where the logger's handler was pointed first, not here)"""
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        badger.main(argv)
+    return buf.getvalue()
+
+
+def _files(prefix):
+    return tuple(open(prefix + s).read() for s in ("_output_file.tsv", "_molecules.tsv", "_cells.tsv"))
+
+
+def _check_rule(prefix, stage1_tsv, umi_dist, stdout):
+    mol, cel = ud.files_of(prefix + "_output_file.tsv", stage1_tsv, 12, umi_dist)
+    got_mol, got_cel = open(prefix + "_molecules.tsv").read(), open(prefix + "_cells.tsv").read()
+    if got_mol != mol:
+        bad = [(g, w) for g, w in zip(got_mol.split("\n"), mol.split("\n")) if g != w][:5]
+        raise AssertionError("molecules differ from the rule: %s" % bad)
+    assert got_cel == cel
+    total = sum(int(l.split("\t")[4]) for l in cel.split("\n")[1:] if l)
+    if stdout is not None:
+        assert "Molecules: %d" % total in stdout
+    return total
+
+
+@pytest.fixture(scope="module")
+def planted(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("umi")
+    rng = random.Random(11)
+    wl, wl_path = _whitelist(tmp, 2600, 11)
+    pairs = _planted(wl[:2000], 200000, rng)
+    tsv = str(tmp / "s1.tsv")
+    _write_tsv(tsv, pairs, rng)
+    return tmp, tsv, wl_path
+
+
+def test_device_equals_the_rule(planted):
+    tmp, tsv, wl = planted
+    for hs in (False, True):
+        for dist in ("0", "1"):
+            prefix = str(tmp / ("d%s_%d" % (dist, hs)))
+            argv = ["-r", tsv, "-d", "tenX_v3", "-l", wl, "-c", "2000", "-o", prefix, "--umi_dedup", "--umi_dist", dist]
+            out = _stage2(argv + (["-hs"] if hs else []))
+            total = _check_rule(prefix, tsv, int(dist), None)
+            assert total > 1000
+        # the flag leaves the assignment file and the printed count alone
+        plain = str(tmp / ("plain_%d" % hs))
+        out_plain = _stage2(["-r", tsv, "-d", "tenX_v3", "-l", wl, "-c", "2000", "-o", plain] + (["-hs"] if hs else []))
+        assert open(plain + "_output_file.tsv").read() == open(prefix + "_output_file.tsv").read()
+        assert out_plain.strip().split("\n")[-1] == out.strip().split("\n")[-1]
+        assert not os.path.exists(plain + "_molecules.tsv") and not os.path.exists(plain + "_cells.tsv")
+    # distance 1 merges what distance 0 keeps apart
+    c0 = open(str(tmp / "d0_0") + "_cells.tsv").read().split("\n")[1:-1]
+    c1 = open(str(tmp / "d1_0") + "_cells.tsv").read().split("\n")[1:-1]
+    assert sum(int(l.split("\t")[4]) for l in c1) < sum(int(l.split("\t")[4]) for l in c0)
+
+
+def test_contexts_on_one_device_give_the_same_files(planted, monkeypatch):
+    tmp, tsv, wl = planted
+    monkeypatch.setenv("BADGER_AMD_CONTEXTS_ON_ONE_DEVICE", "1")
+    outs = []
+    for gpus in ("1", "2"):
+        prefix = str(tmp / ("g%s" % gpus))
+        _stage2(["-r", tsv, "-d", "tenX_v3", "-l", wl, "-c", "2000", "-o", prefix, "--umi_dedup", "--gpus", gpus])
+        outs.append(_files(prefix))
+    assert outs[0] == outs[1]
+
+
+def _fastq(path, pairs, rng):
+    """reads carrying the planted barcodes and UMIs: junk + R1 + barcode + UMI + polyT + cDNA, half of them reverse
+    complemented; some end inside the UMI"""
+    with open(path, "w") as f:
+        for i, (bc, umi) in enumerate(pairs):
+            junk = "".join(rng.choice("ACGT") for _ in range(rng.randint(0, 40)))
+            cdna = "".join(rng.choice("ACGT") for _ in range(rng.randint(150, 300)))
+            if rng.random() < 0.03:
+                s = junk + R1 + bc + umi[:rng.randint(2, 9)]
+            else:
+                s = junk + R1 + bc + umi + "T" * 30 + cdna
+            if rng.random() < 0.5:
+                s = s.translate(_COMP)[::-1]
+            f.write("@read_%d\n%s\n+\n%s\n" % (i, s, "I" * len(s)))
+
+
+def test_reads_and_their_stage1_tsv_give_the_same_files(tmp_path):
+    rng = random.Random(5)
+    wl, wl_path = _whitelist(tmp_path, 400, 5)
+    pairs = _planted(wl[:300], 30000, rng)
+    fq = str(tmp_path / "reads.fastq")
+    _fastq(fq, pairs, rng)
+    tsv = str(tmp_path / "reads_s1.tsv")
+    erb.main(["--mode", "tenX_v3", "-i", fq, "-o", tsv, "-t", "1"])
+    got = {}
+    for name, reads, extra in (("tsv", tsv, []), ("fq", fq, []), ("fq_tr2", fq, ["-tr", "2"])):
+        prefix = str(tmp_path / name)
+        _stage2(["-r", reads, "-d", "tenX_v3", "-l", wl_path, "-c", "300", "-o", prefix, "--umi_dedup"] + extra)
+        got[name] = _files(prefix)
+        _check_rule(prefix, tsv, 1, None)
+    assert got["tsv"] == got["fq"] == got["fq_tr2"]
+    # the reads' UMIs include short ones (cut by the read's end) and ones holding N: both are '*'
+    rows = got["fq"][1].split("\n")[1:-1]
+    assert sum(1 for r in rows if r.split("\t")[2] == "*" and r.split("\t")[1] != "*") > 100
+
+
+def test_nothing_old_moves(tmp_path, golden_dir):
+    want = open(os.path.join(golden_dir, "c1_stage2_output_file.tsv")).read()
+    tail = open(os.path.join(golden_dir, "c1_stage2_stdout_tail.txt")).read().strip()
+    stage1 = os.path.join(golden_dir, "c1_expected.tsv")
+    files = []
+    for reads in ("c1_expected.tsv", "c1_reads.fa.gz"):
+        for flags in ([], ["--umi_dedup"]):
+            prefix = str(tmp_path / ("c1_%s_%d" % (reads[:5], len(flags))))
+            out = _stage2(["-r", os.path.join(golden_dir, reads), "-d", "tenX_v3", "-l", os.path.join(golden_dir, "c1_whitelist.txt"),
+                           "-c", "50", "-o", prefix] + flags)
+            assert open(prefix + "_output_file.tsv").read() == want, (reads, flags)
+            assert out.strip().split("\n")[-1] == tail
+            if flags:
+                _check_rule(prefix, stage1, 1, None)
+                files.append(_files(prefix))
+    assert files[0] == files[1]
+
+
+def test_command_line_with_umi_dedup_runs_without_torch(tmp_path, golden_dir):
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prefix = str(tmp_path / "s2")
+    r = subprocess.run([sys.executable, "-X", "importtime", "-m", "badger_amd.badger", "-r", os.path.join(golden_dir, "c1_reads.fa.gz"),
+                        "-d", "tenX_v3", "-l", os.path.join(golden_dir, "c1_whitelist.txt"), "-c", "50", "-o", prefix, "--umi_dedup"],
+                       cwd=root, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "| torch" not in r.stderr and "badger_amd.stage2" in r.stderr
+    assert open(prefix + "_output_file.tsv").read() == open(os.path.join(golden_dir, "c1_stage2_output_file.tsv")).read()
+    mol, cel = ud.files_of(prefix + "_output_file.tsv", os.path.join(golden_dir, "c1_expected.tsv"), 12, 1)
+    assert open(prefix + "_molecules.tsv").read() == mol and open(prefix + "_cells.tsv").read() == cel
+    total = sum(int(l.split("\t")[4]) for l in cel.split("\n")[1:] if l)
+    assert "Molecules: %d" % total in r.stdout
+
+
+def test_hot_cell(tmp_path):
+    """one cell of 300,000 reads and about 100,000 distinct UMIs beside two small ones"""
+    rng = random.Random(17)
+    wl, wl_path = _whitelist(tmp_path, 50, 17)
+    hot, small = wl[0], wl[1:3]
+    true = list({"".join(rng.choice("ACGT") for _ in range(12)) for _ in range(80000)})
+    pairs = []
+    for u in true:
+        pairs += [(hot, u)] * rng.randint(1, 5)
+    while len(pairs) < 300000:
+        u = rng.choice(true)
+        pairs.append((hot, _noisy(u, rng, 0.05, 0.02, 0.02, 0.0)))
+    rng.shuffle(pairs)
+    for c in small:
+        pairs += [(c, "".join(rng.choice("ACGT") for _ in range(12))) for _ in range(3000)]
+    tsv = str(tmp_path / "hot.tsv")
+    _write_tsv(tsv, pairs, rng)
+    prefix = str(tmp_path / "hot")
+    _stage2(["-r", tsv, "-d", "tenX_v3", "-l", wl_path, "-c", "3", "-o", prefix, "--umi_dedup"])
+    _check_rule(prefix, tsv, 1, None)
+    cells = {l.split("\t")[0]: [int(x) for x in l.split("\t")[1:]] for l in open(prefix + "_cells.tsv").read().split("\n")[1:-1]}
+    assert cells[hot][0] > 290000 and cells[hot][2] > 90000
