@@ -105,6 +105,18 @@ class BadgerHipError(RuntimeError):
         self.code = code
 
 
+def _raise_like_reference(rc, msg):
+    """a failed native reader / stage-1 call as what the reference raises there: KeyError for a base outside ACGTN,
+    ValueError for a malformed file, TypeError for a record without a sequence (len(None) in find_barcode_umi)"""
+    if rc == E_BADBASE:
+        raise KeyError(msg)
+    if rc == E_FORMAT:
+        raise ValueError(msg)
+    if rc == E_NOSEQ:
+        raise TypeError(msg)
+    raise BadgerHipError(rc, msg)
+
+
 _LIB = None
 PRELOAD_TORCH = os.environ.get("BADGER_AMD_PRELOAD_TORCH", "1") != "0"
 
@@ -572,12 +584,8 @@ class Ingest:
     def next(self):
         ch = IngestChunk()
         rc = self.lib.bdg_ingest_next(self.h, C.byref(ch))
-        if rc == E_FORMAT:
-            raise ValueError(self.lib.bdg_ingest_error(self.h).decode())
-        if rc == E_NOSEQ:
-            raise TypeError(self.lib.bdg_ingest_error(self.h).decode())      # the reference: len(None) in find_barcode_umi
         if rc != 0:
-            raise BadgerHipError(rc, self.lib.bdg_ingest_error(self.h).decode())
+            _raise_like_reference(rc, self.lib.bdg_ingest_error(self.h).decode())
         return ch
 
     def release(self, ch):
@@ -635,14 +643,7 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"),
                           C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
     if rc != 0:
-        msg = L.bdg_last_error(contexts[0].h).decode()
-        if rc == E_BADBASE:
-            raise KeyError(msg)
-        if rc == E_FORMAT:
-            raise ValueError(msg)
-        if rc == E_NOSEQ:
-            raise TypeError(msg)
-        raise BadgerHipError(rc, msg)
+        _raise_like_reference(rc, L.bdg_last_error(contexts[0].h).decode())
     return res
 
 
@@ -699,68 +700,46 @@ def stage1_collect(ctx, in_path, umi_len, ids, threads=0, skip_secondary=False, 
     res = Stage1Result()
     rc = L.bdg_stage1_collect(ctx.h, os.fsencode(in_path), C.byref(o), ids.h, C.byref(res))
     if rc != 0:
-        msg = L.bdg_last_error(ctx.h).decode()
-        if rc == E_BADBASE:
-            raise KeyError(msg)
-        if rc == E_FORMAT:
-            raise ValueError(msg)
-        if rc == E_NOSEQ:
-            raise TypeError(msg)
-        raise BadgerHipError(rc, msg)
+        _raise_like_reference(rc, L.bdg_last_error(ctx.h).decode())
     return res
-
-
-def import_stage1_tsv(path, bc_len=16):
-    """a stage-1 TSV the way badger.py:91-111 reads it -> (IdStore of the read ids, rank uint32[n], usable bool[n])"""
-    L = load()
-    ids = IdStore()
-    pr, pu, n, bad = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-    rc = L.bdg_import_stage1_tsv(os.fsencode(path), bc_len, ids.h, C.byref(pr), C.byref(pu), C.byref(n), C.byref(bad))
-    if rc == E_BADBASE:
-        raise KeyError("the barcode in line %d of %s holds a letter outside ACGT" % (bad.value, path))
-    if rc == E_FORMAT:
-        raise ValueError("%s is empty or has no '#read_id' / 'barcode' column" % path)
-    if rc != 0:
-        raise BadgerHipError(rc, "cannot read %s" % path)
-    k = int(n.value)
-    if k == 0 or not pr.value or not pu.value:                # (a header and no rows)
-        for q in (pr, pu):
-            if q.value:
-                L.bdg_host_free(q)
-        return ids, np.zeros(0, np.uint32), np.zeros(0, bool)
-    rank = np.ctypeslib.as_array(C.cast(pr, C.POINTER(C.c_uint32)), shape=(max(k, 1),))[:k].copy()
-    usable = np.ctypeslib.as_array(C.cast(pu, C.POINTER(C.c_uint8)), shape=(max(k, 1),))[:k].astype(bool)
-    L.bdg_host_free(pr)
-    L.bdg_host_free(pu)
-    return ids, rank, usable
 
 
 UMI_NONE = 0xFFFFFFFF
 
 
-def import_stage1_tsv_umis(path, bc_len=16):
-    """import_stage1_tsv plus the UMI column (bdg_import_stage1_tsv_umi) -> (IdStore, rank, usable, UMI codes uint32[n];
-    UMI_NONE where the field is missing or not an ACGT string of 1 .. 14 letters).  ValueError without a UMI column."""
+def _import_stage1_tsv(path, bc_len, umis):
+    """-> [IdStore, rank uint32[n], usable bool[n]] + [UMI codes uint32[n]] with umis"""
     L = load()
     ids = IdStore()
-    pr, pu, pm, n, bad = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
-    rc = L.bdg_import_stage1_tsv_umi(os.fsencode(path), bc_len, ids.h, C.byref(pr), C.byref(pu), C.byref(pm), C.byref(n),
-                                     C.byref(bad))
+    n, bad = C.c_uint64(), C.c_uint64()
+    ptrs = [(C.c_void_p(), C.c_uint32), (C.c_void_p(), C.c_uint8)] + ([(C.c_void_p(), C.c_uint32)] if umis else [])
+    fn = L.bdg_import_stage1_tsv_umi if umis else L.bdg_import_stage1_tsv
+    rc = fn(os.fsencode(path), bc_len, ids.h, *[C.byref(q) for q, _ in ptrs], C.byref(n), C.byref(bad))
     if rc == E_BADBASE:
         raise KeyError("the barcode in line %d of %s holds a letter outside ACGT" % (bad.value, path))
     if rc == E_FORMAT:
-        raise ValueError("%s is empty or has no '#read_id' / 'barcode' / 'UMI' column" % path)
+        raise ValueError("%s is empty or has no '#read_id' / 'barcode'%s column" % (path, " / 'UMI'" if umis else ""))
     if rc != 0:
         raise BadgerHipError(rc, "cannot read %s" % path)
     k = int(n.value)
-    out = []
-    for q, t in ((pr, C.c_uint32), (pu, C.c_uint8), (pm, C.c_uint32)):
-        a = np.ctypeslib.as_array(C.cast(q, C.POINTER(t)), shape=(max(k, 1),))[:k].copy() if q.value and k else \
-            np.zeros(0, np.uint32 if t is C.c_uint32 else np.uint8)
-        out.append(a)
+    out = [ids]
+    for q, t in ptrs:                                         # (a header and no rows: no array, or one that is only freed)
+        out.append(np.ctypeslib.as_array(C.cast(q, C.POINTER(t)), shape=(k,)).copy() if q.value and k else np.zeros(0, t))
         if q.value:
             L.bdg_host_free(q)
-    return ids, out[0], out[1].astype(bool), out[2]
+    out[2] = out[2].astype(bool)
+    return out
+
+
+def import_stage1_tsv(path, bc_len=16):
+    """a stage-1 TSV the way badger.py:91-111 reads it -> (IdStore of the read ids, rank uint32[n], usable bool[n])"""
+    return tuple(_import_stage1_tsv(path, bc_len, False))
+
+
+def import_stage1_tsv_umis(path, bc_len=16):
+    """import_stage1_tsv plus the UMI column (bdg_import_stage1_tsv_umi) -> (IdStore, rank, usable, UMI codes uint32[n];
+    UMI_NONE where the field is missing or not an ACGT string of 1 .. 14 letters).  ValueError without a UMI column."""
+    return tuple(_import_stage1_tsv(path, bc_len, True))
 
 
 def umi_code(s):
@@ -801,71 +780,52 @@ def write_assignments(ids, rank, has, path):
         raise BadgerHipError(rc, "bdg_write_assignments(%s): %d reads, %d ids" % (path, len(rank), len(ids)))
 
 
+def _format_rows(fn, name, ch, args, n_counts):
+    """the native formatters' protocol: ask for the size, then format -> (bytes, counts); args: numpy arrays and numbers"""
+    argv = [a.ctypes.data if isinstance(a, np.ndarray) else a for a in args]
+    counts = (C.c_uint64 * n_counts)()
+    need = fn(C.byref(ch), *argv, None, 0, counts)
+    if need < 0:
+        raise BadgerHipError(int(need), name)
+    buf = C.create_string_buffer(int(need) + 1)
+    got = fn(C.byref(ch), *argv, buf, int(need), counts)
+    if got < 0 or got > need:
+        raise BadgerHipError(int(got), name)
+    return buf.raw[:got], tuple(int(x) for x in counts)
+
+
+def _wl_args(name, ch, recs, best_idx, best_ed, n_ties, wl, more=()):
+    """the leading arguments of the whitelist formatters, coerced and checked against the chunk"""
+    arrs = [np.ascontiguousarray(recs)] + [np.ascontiguousarray(a, dtype=t) for a, t in
+                                           ((best_idx, np.uint32), (best_ed, np.uint8), (n_ties, np.uint16))]
+    lens = [len(a) for a in arrs] + [len(a) for a in more]
+    if any(x != ch.n for x in lens):
+        raise ValueError("%s: %d reads, %d records, %s calls" % (name, ch.n, lens[0], " / ".join("%d" % x for x in lens[1:])))
+    wl = np.ascontiguousarray(wl, dtype=np.uint32)
+    return arrs + [wl, len(wl)]
+
+
 def format_rows(ch, recs):
     """TSV rows of a chunk as bytes (one "\n"-terminated line per read) + (reads, barcodes, polyT, R1) counts"""
-    L = load()
-    recs = np.ascontiguousarray(recs)
-    counts = (C.c_uint64 * 4)()
-    need = L.bdg_format_rows(C.byref(ch), recs.ctypes.data, None, 0, counts)
-    if need < 0:
-        raise BadgerHipError(int(need), "bdg_format_rows")
-    buf = C.create_string_buffer(int(need) + 1)
-    got = L.bdg_format_rows(C.byref(ch), recs.ctypes.data, buf, int(need), counts)
-    if got < 0 or got > need:
-        raise BadgerHipError(int(got), "bdg_format_rows")
-    return buf.raw[:got], tuple(int(x) for x in counts)
+    return _format_rows(load().bdg_format_rows, "bdg_format_rows", ch, [np.ascontiguousarray(recs)], 4)
 
 
 def format_rows_wl(ch, recs, best_idx, best_ed, n_ties, wl):
     """format_rows with the three whitelist columns (bdg_format_rows_wl): the match's answer per record and the whitelist
     (ranks, caller order).  Counts: (reads, barcodes, polyT, R1, whitelist barcodes)"""
-    L = load()
-    recs = np.ascontiguousarray(recs)
-    idx = np.ascontiguousarray(best_idx, dtype=np.uint32)
-    ed = np.ascontiguousarray(best_ed, dtype=np.uint8)
-    ties = np.ascontiguousarray(n_ties, dtype=np.uint16)
-    wl = np.ascontiguousarray(wl, dtype=np.uint32)
-    if not (len(recs) == len(idx) == len(ed) == len(ties) == ch.n):
-        raise ValueError("format_rows_wl: %d reads, %d records, %d / %d / %d calls" % (ch.n, len(recs), len(idx), len(ed), len(ties)))
-    counts = (C.c_uint64 * 5)()
-    args = (recs.ctypes.data, idx.ctypes.data, ed.ctypes.data, ties.ctypes.data, wl.ctypes.data, len(wl))
-    need = L.bdg_format_rows_wl(C.byref(ch), *args, None, 0, counts)
-    if need < 0:
-        raise BadgerHipError(int(need), "bdg_format_rows_wl")
-    buf = C.create_string_buffer(int(need) + 1)
-    got = L.bdg_format_rows_wl(C.byref(ch), *args, buf, int(need), counts)
-    if got < 0 or got > need:
-        raise BadgerHipError(int(got), "bdg_format_rows_wl")
-    return buf.raw[:got], tuple(int(x) for x in counts)
+    return _format_rows(load().bdg_format_rows_wl, "bdg_format_rows_wl", ch,
+                        _wl_args("format_rows_wl", ch, recs, best_idx, best_ed, n_ties, wl), 5)
 
 
 def format_rows_wlk(ch, recs, best_idx, best_ed, n_ties, cand_idx, cand_ed, wl):
     """format_rows_wl with the whitelist_candidates column (bdg_format_rows_wlk): cand_idx / cand_ed [n, k] are the slots of
     the top-k match per record.  Counts as format_rows_wl"""
-    L = load()
-    recs = np.ascontiguousarray(recs)
-    idx = np.ascontiguousarray(best_idx, dtype=np.uint32)
-    ed = np.ascontiguousarray(best_ed, dtype=np.uint8)
-    ties = np.ascontiguousarray(n_ties, dtype=np.uint16)
     cidx = np.ascontiguousarray(cand_idx, dtype=np.uint32)
     ced = np.ascontiguousarray(cand_ed, dtype=np.uint8)
-    wl = np.ascontiguousarray(wl, dtype=np.uint32)
     if cidx.ndim != 2 or cidx.shape != ced.shape:
         raise ValueError("format_rows_wlk: candidate arrays must both be [n, k], got %s / %s" % (cidx.shape, ced.shape))
-    if not (len(recs) == len(idx) == len(ed) == len(ties) == len(cidx) == ch.n):
-        raise ValueError("format_rows_wlk: %d reads, %d records, %d / %d / %d / %d calls"
-                         % (ch.n, len(recs), len(idx), len(ed), len(ties), len(cidx)))
-    counts = (C.c_uint64 * 5)()
-    args = (recs.ctypes.data, idx.ctypes.data, ed.ctypes.data, ties.ctypes.data, wl.ctypes.data, len(wl),
-            cidx.shape[1], cidx.ctypes.data, ced.ctypes.data)
-    need = L.bdg_format_rows_wlk(C.byref(ch), *args, None, 0, counts)
-    if need < 0:
-        raise BadgerHipError(int(need), "bdg_format_rows_wlk")
-    buf = C.create_string_buffer(int(need) + 1)
-    got = L.bdg_format_rows_wlk(C.byref(ch), *args, buf, int(need), counts)
-    if got < 0 or got > need:
-        raise BadgerHipError(int(got), "bdg_format_rows_wlk")
-    return buf.raw[:got], tuple(int(x) for x in counts)
+    return _format_rows(load().bdg_format_rows_wlk, "bdg_format_rows_wlk", ch,
+                        _wl_args("format_rows_wlk", ch, recs, best_idx, best_ed, n_ties, wl, more=(cidx,)) + [cidx.shape[1], cidx, ced], 5)
 
 
 _DEFAULT = {}

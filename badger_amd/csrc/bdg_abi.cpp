@@ -1,41 +1,15 @@
 // C ABI of libbadger_hip.so (include/badger_hip.h): context management, host-buffer
 // wrappers (H2D, launch, D2H) and the device-resident entry points.
-#include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
 #include "dj_codec.hpp"
+#include "host_util.hpp"
 
 #include <cstddef>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <chrono>
 #include <mutex>
-
-// launchers in the kernel translation units
-int bdg_extract_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint64_t, uint32_t, bdg_extract_rec*);
-int bdg_extract_status_impl(bdg_ctx*, uint64_t*, uint64_t*);
-int bdg_extract_counters_impl(bdg_ctx*, uint64_t*);
-int bdg_extract_judge_host(bdg_ctx*, const void*, uint64_t, uint64_t*, uint64_t*);
-size_t bdg_extract_counter_bytes();
-int bdg_whitelist_load_impl(bdg_ctx*, const uint32_t*, uint32_t);
-int bdg_nearest16_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*);
-int bdg_nearest16_check(bdg_ctx*, uint32_t, uint32_t);
-int bdg_nearest16_topk_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*, uint16_t*);
-int bdg_nearest16_topk_check(bdg_ctx*, uint32_t, uint32_t, uint32_t);
-int bdg_nearest16_overflow_read(bdg_ctx*, uint32_t*);
-int bdg_graph_launch(bdg_ctx*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, int32_t, bdg_edge*, uint64_t, uint64_t*, uint32_t part = 0, uint32_t nparts = 1);
-int bdg_graph_plan(const bdg_ctx*, uint32_t, uint32_t);
-int bdg_graph_join_flags(bdg_ctx*, uint32_t*);
-int bdg_graph_flags_error(bdg_ctx*, uint32_t);
-int bdg_distinct_launch(bdg_ctx*, const bdg_extract_rec*, uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*);
-int bdg_records_of_observed_launch(bdg_ctx*, const uint32_t*, const uint8_t*, uint64_t, bdg_extract_rec*);
-int bdg_rows_of_launch(bdg_ctx*, const uint32_t*, uint32_t, const uint32_t*, uint64_t, uint32_t, uint32_t*);
-int bdg_cluster_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, int32_t*);
-int bdg_assign_reads_launch(bdg_ctx*, const bdg_extract_rec*, uint64_t, const uint32_t*, uint32_t, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*);
-int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, const uint32_t*, uint32_t, uint64_t*);
-int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
-int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                         uint32_t*, uint32_t*);
 
 static thread_local std::string g_err_noctx;
 
@@ -90,7 +64,15 @@ void bdg_timer_end(bdg_ctx* ctx, int id)
     ctx->timers[id].launches++;
 }
 
-int bdg_nearest16_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*);
+// the barcode ranks of device records as a query of the nearest16 launchers: bc_rank of every record, the stride in words, and
+// "check the record's flags" (records without a 16-base ACGT barcode report no hit)
+struct RecsQuery { const uint32_t* q; uint32_t stride; int recs; };
+static RecsQuery recs_query(const void* d_recs)
+{
+    static_assert(sizeof(bdg_extract_rec) == 32 && offsetof(bdg_extract_rec, bc_rank) == 20 && offsetof(bdg_extract_rec, flags) == 27,
+                  "record layout the strided query reads");
+    return RecsQuery{ static_cast<const uint32_t*>(d_recs) + offsetof(bdg_extract_rec, bc_rank) / 4, sizeof(bdg_extract_rec) / 4, 1 };
+}
 
 int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan)
 {
@@ -107,7 +89,8 @@ int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan)
     BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, after, 0));
     ctx->launch_stream = ctx->aux_stream;
     ctx->aux_pending = true;
-    const int rc = bdg_nearest16_launch(ctx, d.q, 8u, 1, d.n, d.max_ed, d.idx, d.ed, d.ties);
+    const RecsQuery Q = recs_query(d.recs);
+    const int rc = bdg_nearest16_launch(ctx, Q.q, Q.stride, Q.recs, d.n, d.max_ed, d.idx, d.ed, d.ties);
     ctx->launch_stream = nullptr;
     BDG_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[ctx->aux_count & 1], ctx->aux_stream));
     ctx->aux_count++;
@@ -380,7 +363,7 @@ int bdg_extract_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* 
 {
     if (!ctx) return BDG_E_ARG;
     if (n && (!d_bases || !d_off || !d_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (umi_len == 0 || umi_len > 64) return bdg_fail(ctx, BDG_E_ARG, "umi_len out of range");
+    if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // overlap mode: the caller alternates between two record buffers, so this extraction may overwrite what the match before
     // the last one read: stay at most one match ahead
@@ -419,17 +402,24 @@ int bdg_extract_counters(bdg_ctx* ctx, uint64_t out[8])
     return bdg_extract_counters_impl(ctx, out);
 }
 
+// the first read whose offsets are out of order or that is too long for the kernels
+static int check_offsets(bdg_ctx* ctx, const uint64_t* off, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
+        if (off[i + 1] - off[i] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "read longer than 2^26 bases");
+    }
+    return BDG_OK;
+}
+
 int bdg_extract_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
                       uint32_t umi_len, bdg_extract_rec* out)
 {
     if (!ctx) return BDG_E_ARG;
     if (n == 0) return BDG_OK;
     if (!bases || !off || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (umi_len == 0 || umi_len > 64) return bdg_fail(ctx, BDG_E_ARG, "umi_len out of range");
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
-    for (uint32_t i = 0; i < n; ++i)
-        if (off[i + 1] - off[i] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "read longer than 2^26 bases");
+    if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
+    if (int rco = check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // ship only the byte range the offsets reference, rebased to 0
     const uint64_t lo = off[0], hi = off[n], total = hi - lo;
@@ -485,25 +475,22 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
 
 // where bdg_extract_submit's time goes (BADGER_AMD_INGEST_DEBUG; printed by bdg_stage1_run).  Summed only when that variable is
 // set, and atomically: the ABI lets different host threads drive different contexts, and they all pass here.
-std::atomic<double> g_submit_t[6];
+static std::atomic<double> g_submit_t[6];
+void bdg_submit_times(double t[5]) { for (int i = 0; i < 5; ++i) t[i] = g_submit_t[i].load(); }
 static const bool g_submit_debug = getenv("BADGER_AMD_INGEST_DEBUG") != nullptr;
 static inline void submit_add(int i, double v) { double o = g_submit_t[i].load(std::memory_order_relaxed); while (!g_submit_t[i].compare_exchange_weak(o, o + v, std::memory_order_relaxed)) {} }
-static inline double submit_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len)
 {
-    const double T0 = submit_now();
+    const double T0 = now_s();
     if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
     bdg_ctx::Slot& sl = ctx->slots[slot];
     if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "slot still in flight: collect it first");
     if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (umi_len == 0 || umi_len > 64) return bdg_fail(ctx, BDG_E_ARG, "umi_len out of range");
+    if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
     if (n == 0) { sl.busy = true; return BDG_OK; }
-    for (uint32_t i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
-        if (off[i + 1] - off[i] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "read longer than 2^26 bases");
-    }
+    if (int rco = check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t lo = off[0], total = off[n] - lo;
     sl.total = total;
@@ -519,20 +506,34 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
         }
     }
     if (!sl.done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    const double T1 = submit_now();
+    const double T1 = now_s();
     uint64_t* rel = static_cast<uint64_t*>(sl.h_off);
     for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
     hipStream_t st = ctx->stream;
-    const double T2 = submit_now();
+    const double T2 = now_s();
     // (one copy on one stream runs at the link's rate here: 56.6 GB/s for 32 MB from pinned memory, tools/hip_first_calls.py; two
     // halves on two streams, which gained 10 % in round 2, gain nothing any more)
     if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_bases.p, bases + lo, total, hipMemcpyHostToDevice, st));
     BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_off.p, rel, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
-    const double T3 = submit_now();
+    const double T3 = now_s();
     if ((rc = slot_enqueue(ctx, sl))) return rc;
     sl.busy = true;
-    const double T4 = submit_now();
+    const double T4 = now_s();
     if (g_submit_debug) { submit_add(0, T1 - T0); submit_add(1, T2 - T1); submit_add(2, T3 - T2); submit_add(3, T4 - T3); submit_add(4, 1.0); }
+    return BDG_OK;
+}
+
+// room for `add` bytes behind the `have` bytes a kept array (records, UMIs) holds: grown by copying, earlier chunks stay
+static int kept_grow(bdg_ctx* ctx, DevBuf& b, size_t have, size_t add, size_t min_bytes)
+{
+    if (have + add <= b.bytes) return BDG_OK;
+    DevBuf nb;
+    int rc;
+    if ((rc = bdg_reserve(ctx, nb, std::max((have + add) * 2, min_bytes)))) return rc;
+    if (have) BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.p, b.p, have, hipMemcpyDeviceToDevice, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (b.p) (void)hipFree(b.p);
+    b = nb;
     return BDG_OK;
 }
 
@@ -559,32 +560,13 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
     if (rc) return rc;
     memcpy(out, sl.h_recs, sizeof(bdg_extract_rec) * (size_t)sl.n);
     if (ctx->keep_records) {
-        // append the chunk's records to the device-side array (grown by copying: earlier chunks stay)
+        // append the chunk's records to the device-side array
         const size_t have = sizeof(bdg_extract_rec) * (size_t)ctx->x_allrecs_n, add = sizeof(bdg_extract_rec) * (size_t)sl.n;
-        if (have + add > ctx->x_allrecs.bytes) {
-            DevBuf nb;
-            size_t want = (have + add) * 2;
-            if (want < (size_t(64) << 20)) want = size_t(64) << 20;
-            if ((rc = bdg_reserve(ctx, nb, want))) return rc;
-            if (have) BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.p, ctx->x_allrecs.p, have, hipMemcpyDeviceToDevice, ctx->stream));
-            BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->x_allrecs.p) (void)hipFree(ctx->x_allrecs.p);
-            ctx->x_allrecs = nb;
-        }
+        if ((rc = kept_grow(ctx, ctx->x_allrecs, have, add, size_t(64) << 20))) return rc;
         BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(ctx->x_allrecs.p) + have, sl.d_recs.p, add, hipMemcpyDeviceToDevice, ctx->stream));
         if (ctx->keep_umis) {
-            // the chunk's UMIs, packed from its bases while they are still here (grown like the records)
-            const size_t uhave = 4 * (size_t)ctx->x_allumis_n, uadd = 4 * (size_t)sl.n;
-            if (uhave + uadd > ctx->x_allumis.bytes) {
-                DevBuf nb;
-                size_t want = (uhave + uadd) * 2;
-                if (want < (size_t(8) << 20)) want = size_t(8) << 20;
-                if ((rc = bdg_reserve(ctx, nb, want))) return rc;
-                if (uhave) BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.p, ctx->x_allumis.p, uhave, hipMemcpyDeviceToDevice, ctx->stream));
-                BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->x_allumis.p) (void)hipFree(ctx->x_allumis.p);
-                ctx->x_allumis = nb;
-            }
+            // the chunk's UMIs, packed from its bases while they are still here
+            if ((rc = kept_grow(ctx, ctx->x_allumis, 4 * (size_t)ctx->x_allumis_n, 4 * (size_t)sl.n, size_t(8) << 20))) return rc;
             if ((rc = bdg_umi_pack_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
                                           static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n,
                                           static_cast<uint32_t*>(ctx->x_allumis.p) + ctx->x_allumis_n)))
@@ -597,14 +579,7 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
 }
 
 // lists of the correction store (Correct::lists) from read `at` on
-struct CorrLists { uint32_t* idx8; uint8_t* ed8; uint16_t* nw; };
-static CorrLists corr_lists(bdg_ctx* ctx, uint64_t at)
-{
-    auto* base = static_cast<uint8_t*>(ctx->corr.lists.p);
-    const uint64_t cap = ctx->corr.cap;
-    return CorrLists{ reinterpret_cast<uint32_t*>(base) + at * 8, base + 32 * cap + at * 8,
-                      reinterpret_cast<uint16_t*>(base + 40 * cap) + at };
-}
+static CorrLists corr_lists(bdg_ctx* ctx, uint64_t at) { return corr_lists(ctx->corr.lists.p, ctx->corr.cap, at); }
 
 // room for `need` reads of kept lists; what is kept moves along (behind the matches that wrote it, on the auxiliary stream)
 static int corr_grow(bdg_ctx* ctx, uint64_t need)
@@ -613,25 +588,25 @@ static int corr_grow(bdg_ctx* ctx, uint64_t need)
     if (need <= c.cap) return BDG_OK;
     const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * c.cap), 1ull << 20);
     void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, 42 * cap + 64);
+    const size_t bytes = CORR_LISTS_READ_BYTES * cap + 64;
+    const hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return bdg_fail(ctx, BDG_E_NOMEM, "hipMalloc(" + std::to_string(42 * cap + 64) + " bytes) for the kept candidate lists");
+        return bdg_fail(ctx, BDG_E_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes) for the kept candidate lists");
     }
     if (c.lists.p) {
-        const CorrLists o = corr_lists(ctx, 0);
-        auto* nb = static_cast<uint8_t*>(p);
+        const CorrLists o = corr_lists(ctx, 0), nb = corr_lists(p, cap, 0);
         hipStream_t st = ctx->aux_stream ? ctx->aux_stream : ctx->stream;
         if (c.n) {
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb, o.idx8, 32 * c.n, hipMemcpyDeviceToDevice, st));
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb + 32 * cap, o.ed8, 8 * c.n, hipMemcpyDeviceToDevice, st));
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb + 40 * cap, o.nw, 2 * c.n, hipMemcpyDeviceToDevice, st));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.idx8, o.idx8, sizeof(uint32_t) * CORR_K * c.n, hipMemcpyDeviceToDevice, st));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.ed8, o.ed8, CORR_K * c.n, hipMemcpyDeviceToDevice, st));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.nw, o.nw, sizeof(uint16_t) * c.n, hipMemcpyDeviceToDevice, st));
         }
         BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
         BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         BDG_HIP_TRY(ctx, hipFree(c.lists.p));
     }
-    c.lists.p = p; c.lists.bytes = 42 * cap + 64; c.cap = cap;
+    c.lists.p = p; c.lists.bytes = bytes; c.cap = cap;
     return BDG_OK;
 }
 
@@ -639,36 +614,27 @@ static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed, ui
 {
     int rc;
     if ((rc = ensure_aux(ctx))) return rc;
-    const size_t n = sl.n;
-    const size_t bytes = k ? (4 * k + 4 + k) * n : 7 * n;
+    const size_t bytes = match_layout(nullptr, sl.n, k).bytes;
     if ((rc = bdg_reserve(ctx, sl.d_match, bytes + 64))) return rc;
     if ((rc = pinned_reserve(ctx, sl.h_match, sl.h_match_bytes, bytes + 64))) return rc;
     if (!sl.match_done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.match_done, hipEventDisableTiming));
     BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, sl.done, 0));      // behind the chunk's extraction
     ctx->launch_stream = ctx->aux_stream;
     ctx->aux_pending = true;
-    const auto* d_q = reinterpret_cast<const uint32_t*>(sl.d_recs.p) + 5;
-    auto* d_idx = static_cast<uint32_t*>(sl.d_match.p);
+    const RecsQuery Q = recs_query(sl.d_recs.p);
+    const MatchLayout M = match_layout(sl.d_match.p, sl.n, k);
     if (sl.match_corr) {
         // correction: the k = 8 lists go to the run's store and stay there; the support kernel adds the chunk's exact hits and
-        // gathers the k slots the host asked for (k = 0: the best-hit layout below) into d_match.  A chunk matched again after
+        // gathers the k slots the host asked for (k = 0: the best-hit layout) into d_match.  A chunk matched again after
         // its extraction was rerun adds nothing twice: the first match saw the overflow's placeholder records, none usable.
         const CorrLists L = corr_lists(ctx, sl.corr_at);
-        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n * (k ? k : 1));
-        auto* d_nwithin = k ? d_ties + n : nullptr;
-        auto* d_ed = reinterpret_cast<uint8_t*>(k ? d_nwithin + n : d_ties + n);
-        rc = bdg_nearest16_topk_launch(ctx, d_q, 8u, 1, sl.n, max_ed, 8u, L.idx8, L.ed8, L.nw, d_ties);
+        rc = bdg_nearest16_topk_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, CORR_K, L.idx8, L.ed8, L.nw, M.ties);
         if (!rc) rc = bdg_correct_support_launch(ctx, ctx->aux_stream, L.idx8, L.ed8, L.nw, sl.n, k,
-                                                 static_cast<uint32_t*>(ctx->corr.support.p), d_idx, d_ed, d_nwithin);
+                                                 static_cast<uint32_t*>(ctx->corr.support.p), M.idx, M.ed, M.n_within);
     } else if (k) {
-        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n * k);
-        auto* d_nwithin = d_ties + n;
-        auto* d_ed = reinterpret_cast<uint8_t*>(d_nwithin + n);
-        rc = bdg_nearest16_topk_launch(ctx, d_q, 8u, 1, sl.n, max_ed, k, d_idx, d_ed, d_nwithin, d_ties);
+        rc = bdg_nearest16_topk_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, k, M.idx, M.ed, M.n_within, M.ties);
     } else {
-        auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + n);
-        auto* d_ed = reinterpret_cast<uint8_t*>(d_ties + n);
-        rc = bdg_nearest16_launch(ctx, d_q, 8u, 1, sl.n, max_ed, d_idx, d_ed, d_ties);
+        rc = bdg_nearest16_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, M.idx, M.ed, M.ties);
     }
     ctx->launch_stream = nullptr;
     if (rc) return rc;
@@ -687,7 +653,7 @@ int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k
     if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
     const bool corr = ctx->corr.on;
     if (corr && max_ed > 3) return bdg_fail(ctx, BDG_E_ARG, "whitelist correction needs max_ed <= 3");
-    int rc = corr ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, 8u)
+    int rc = corr ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, CORR_K)
                   : k ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, k) : bdg_nearest16_check(ctx, sl.n, max_ed);
     sl.match_corr = corr;
     if (rc || sl.n == 0) return rc;
@@ -698,11 +664,6 @@ int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k
         ctx->corr.n += sl.n;
     }
     return queue_slot_match(ctx, sl, max_ed, k);
-}
-
-int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed)
-{
-    return bdg_slot_match_topk(ctx, slot, max_ed, 0);
 }
 
 int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
@@ -719,24 +680,16 @@ int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx,
     BDG_HIP_TRY(ctx, hipEventSynchronize(sl.match_done));
     sl.match_queued = false;
     const size_t n = sl.n, k = sl.match_k;
-    const auto* h_idx = static_cast<const uint32_t*>(sl.h_match);
+    const MatchLayout H = match_layout(sl.h_match, n, k);
+    if (k && (!cand_idx || !cand_ed)) return bdg_fail(ctx, BDG_E_ARG, "a top-k match needs the candidate arrays");
+    memcpy(n_ties, H.ties, sizeof(uint16_t) * n);
     if (k) {
-        if (!cand_idx || !cand_ed) return bdg_fail(ctx, BDG_E_ARG, "a top-k match needs the candidate arrays");
-        const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n * k);
-        const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + 2 * n);
-        memcpy(cand_idx, h_idx, 4 * n * k); memcpy(cand_ed, h_ed, n * k); memcpy(n_ties, h_ties, 2 * n);
-        for (size_t i = 0; i < n; ++i) { best_idx[i] = h_idx[i * k]; best_ed[i] = h_ed[i * k]; }
+        memcpy(cand_idx, H.idx, sizeof(uint32_t) * n * k); memcpy(cand_ed, H.ed, n * k);
+        for (size_t i = 0; i < n; ++i) { best_idx[i] = H.idx[i * k]; best_ed[i] = H.ed[i * k]; }
     } else {
-        const auto* h_ties = reinterpret_cast<const uint16_t*>(h_idx + n);
-        const auto* h_ed = reinterpret_cast<const uint8_t*>(h_ties + n);
-        memcpy(best_idx, h_idx, 4 * n); memcpy(n_ties, h_ties, 2 * n); memcpy(best_ed, h_ed, n);
+        memcpy(best_idx, H.idx, sizeof(uint32_t) * n); memcpy(best_ed, H.ed, n);
     }
     return BDG_OK;
-}
-
-int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties)
-{
-    return bdg_slot_match_collect_topk(ctx, slot, best_idx, best_ed, n_ties, nullptr, nullptr);
 }
 
 int bdg_correct_begin(bdg_ctx* ctx)
@@ -781,12 +734,12 @@ int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits, uint32_t p
     int rc = sync_all(ctx);
     if (rc || ctx->corr.n == 0) return rc;
     const uint64_t n = ctx->corr.n;
-    if ((rc = bdg_reserve(ctx, ctx->corr.out, 12 * n + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->corr.out, CORR_OUT_READ_BYTES * n + 64))) return rc;
     const CorrLists L = corr_lists(ctx, 0);
     if ((rc = bdg_correct_resolve_launch(ctx, ctx->stream, L.idx8, L.ed8, L.nw, n, static_cast<const uint32_t*>(ctx->corr.support.p),
                                          max_ed, bits, pmin, ctx->corr.out.p)))
         return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->corr.out.p, 12 * n, hipMemcpyDeviceToHost, ctx->stream));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->corr.out.p, CORR_OUT_READ_BYTES * n, hipMemcpyDeviceToHost, ctx->stream));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return BDG_OK;
 }
@@ -809,15 +762,10 @@ int bdg_extract_keep_records(bdg_ctx* ctx, int on)
     ctx->keep_records = on != 0;
     ctx->x_allrecs_n = 0;
     ctx->x_allumis_n = 0;
-    if (!on && ctx->x_allrecs.p) {
+    if (!on) for (DevBuf* b : { &ctx->x_allrecs, &ctx->x_allumis }) if (b->p) {
         BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->x_allrecs.p);
-        ctx->x_allrecs = DevBuf();
-    }
-    if (!on && ctx->x_allumis.p) {
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->x_allumis.p);
-        ctx->x_allumis = DevBuf();
+        (void)hipFree(b->p);
+        *b = DevBuf();
     }
     return BDG_OK;
 }
@@ -945,8 +893,6 @@ int bdg_nearest16_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t
 {
     if (!ctx) return BDG_E_ARG;
     if (n && (!d_recs || !d_best_idx || !d_best_ed || !d_n_ties)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    static_assert(sizeof(bdg_extract_rec) == 32 && offsetof(bdg_extract_rec, bc_rank) == 20 && offsetof(bdg_extract_rec, flags) == 27,
-                  "record layout the strided query reads");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->overlap) {
         // not queued yet: it goes behind the next extraction's scan (or behind everything queued so far, at the next
@@ -958,11 +904,12 @@ int bdg_nearest16_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t
         if ((rc = bdg_launch_deferred_match(ctx, false))) return rc;
         if (n == 0) return BDG_OK;
         ctx->deferred.pending = true;
-        ctx->deferred.q = reinterpret_cast<const uint32_t*>(d_recs) + 5; ctx->deferred.n = n; ctx->deferred.max_ed = max_ed;
+        ctx->deferred.recs = d_recs; ctx->deferred.n = n; ctx->deferred.max_ed = max_ed;
         ctx->deferred.idx = d_best_idx; ctx->deferred.ed = d_best_ed; ctx->deferred.ties = d_n_ties;
         return BDG_OK;
     }
-    return bdg_nearest16_launch(ctx, reinterpret_cast<const uint32_t*>(d_recs) + 5, 8u, 1, n, max_ed, d_best_idx, d_best_ed, d_n_ties);
+    const RecsQuery Q = recs_query(d_recs);
+    return bdg_nearest16_launch(ctx, Q.q, Q.stride, Q.recs, n, max_ed, d_best_idx, d_best_ed, d_n_ties);
 }
 
 int bdg_nearest16(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw,
@@ -980,17 +927,15 @@ int bdg_nearest16(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* 
     if (rc) return rc;
     const size_t bq = sizeof(uint32_t) * (size_t)nq;
     if ((rc = bdg_reserve(ctx, ctx->s_in0, bq))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, bq * 2 + 64))) return rc;     // idx u32 | ties u16 | ed u8
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, bq * 2 + 64))) return rc;
     hipStream_t st = ctx->stream;
-    auto* d_idx = static_cast<uint32_t*>(ctx->s_out0.p);
-    auto* d_ties = reinterpret_cast<uint16_t*>(d_idx + nq);
-    auto* d_ed = reinterpret_cast<uint8_t*>(d_ties + nq);
+    const MatchLayout M = match_layout(ctx->s_out0.p, nq, 0);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, bq, hipMemcpyHostToDevice, st));
-    rc = bdg_nearest16_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, d_idx, d_ed, d_ties);
+    rc = bdg_nearest16_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, M.idx, M.ed, M.ties);
     if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(best_idx, d_idx, bq, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_ties, d_ties, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(best_ed, d_ed, (size_t)nq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(best_idx, M.idx, bq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_ties, M.ties, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(best_ed, M.ed, (size_t)nq, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return BDG_OK;
 }
@@ -1028,7 +973,8 @@ int bdg_nearest16_topk_recs_dev(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uin
     // auxiliary stream, whose workspaces (counters, query lists, partials) it reuses
     if (ctx->overlap && (rc = bdg_launch_deferred_match(ctx, false))) return rc;
     if ((rc = main_after_aux(ctx))) return rc;
-    return bdg_nearest16_topk_launch(ctx, reinterpret_cast<const uint32_t*>(d_recs) + 5, 8u, 1, n, max_ed, k, d_idx, d_ed, d_n_within, nullptr);
+    const RecsQuery Q = recs_query(d_recs);
+    return bdg_nearest16_topk_launch(ctx, Q.q, Q.stride, Q.recs, n, max_ed, k, d_idx, d_ed, d_n_within, nullptr);
 }
 
 int bdg_nearest16_topk(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* wl, uint32_t nw,
@@ -1049,17 +995,15 @@ int bdg_nearest16_topk(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint3
     if ((rc = main_after_aux(ctx))) return rc;
     const size_t bq = sizeof(uint32_t) * (size_t)nq, nk = (size_t)nq * k;
     if ((rc = bdg_reserve(ctx, ctx->s_in0, bq))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, 5 * nk + 2 * (size_t)nq + 64))) return rc;     // idx u32 [nq k] | n_within u16 | ed u8 [nq k]
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, match_layout(nullptr, nq, k, false).bytes + 64))) return rc;
     hipStream_t st = ctx->stream;
-    auto* d_idx = static_cast<uint32_t*>(ctx->s_out0.p);
-    auto* d_nw = reinterpret_cast<uint16_t*>(d_idx + nk);
-    auto* d_ed = reinterpret_cast<uint8_t*>(d_nw + nq);
+    const MatchLayout M = match_layout(ctx->s_out0.p, nq, k, false);        // (no tie counts asked for)
     BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, bq, hipMemcpyHostToDevice, st));
-    rc = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, k, d_idx, d_ed, d_nw, nullptr);
+    rc = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, k, M.idx, M.ed, M.n_within, nullptr);
     if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, 4 * nk, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_within, d_nw, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ed, d_ed, nk, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(idx, M.idx, 4 * nk, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_within, M.n_within, sizeof(uint16_t) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ed, M.ed, nk, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return BDG_OK;
 }
@@ -1069,10 +1013,10 @@ int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const ui
                           int16_t* permille, uint8_t* status)
 {
     if (!ctx) return BDG_E_ARG;
-    if (max_ed > 3) return bdg_fail(ctx, BDG_E_ARG, "max_ed out of range (0 .. 3)");
-    if (edit_bits < 1 || edit_bits > 8) return bdg_fail(ctx, BDG_E_ARG, "edit_bits out of range (1 .. 8)");
-    if (min_permille < 501 || min_permille > 1000) return bdg_fail(ctx, BDG_E_ARG, "min_permille out of range (501 .. 1000)");
-    int rc = bdg_nearest16_topk_check(ctx, 0, max_ed, 8u);
+    static const char* const BAD_OPT[] = { "", "max_ed out of range (0 .. 3)", "edit_bits out of range (1 .. 8)",
+                                           "min_permille out of range (501 .. 1000)" };
+    if (const int bad = bdg_check_correct_opts(max_ed, edit_bits, min_permille)) return bdg_fail(ctx, BDG_E_ARG, BAD_OPT[bad]);
+    int rc = bdg_nearest16_topk_check(ctx, 0, max_ed, CORR_K);
     if (rc) return rc;
     if (nq == 0) return BDG_OK;
     if (!q || !idx || !ed || !support || !permille || !status || (nw && !wl)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
@@ -1083,7 +1027,7 @@ int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const ui
     }
     if ((rc = bdg_whitelist_load_impl(ctx, wl, nw))) return rc;
     if ((rc = bdg_correct_begin(ctx))) return rc;
-    std::vector<uint8_t> out((size_t)nq * 12);
+    std::vector<uint8_t> out((size_t)nq * CORR_OUT_READ_BYTES);
     auto run = [&]() -> int {
         int r;
         if ((r = corr_grow(ctx, nq))) return r;
@@ -1091,7 +1035,7 @@ int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const ui
         if ((r = bdg_reserve(ctx, ctx->s_in0, sizeof(uint32_t) * (size_t)nq))) return r;
         BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, sizeof(uint32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
         const CorrLists L = corr_lists(ctx, 0);
-        if ((r = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, 8u, L.idx8, L.ed8, L.nw, nullptr)))
+        if ((r = bdg_nearest16_topk_launch(ctx, static_cast<const uint32_t*>(ctx->s_in0.p), 1u, 0, nq, max_ed, CORR_K, L.idx8, L.ed8, L.nw, nullptr)))
             return r;
         if ((r = bdg_correct_support_launch(ctx, ctx->stream, L.idx8, L.ed8, L.nw, nq, 0u, static_cast<uint32_t*>(ctx->corr.support.p),
                                             nullptr, nullptr, nullptr)))
@@ -1102,12 +1046,7 @@ int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const ui
     const int rce = bdg_correct_end(ctx);
     if (rc) return rc;
     if (rce) return rce;
-    const size_t n = nq;
-    memcpy(idx, out.data(), 4 * n);
-    memcpy(support, out.data() + 4 * n, 4 * n);
-    memcpy(permille, out.data() + 8 * n, 2 * n);
-    memcpy(ed, out.data() + 10 * n, n);
-    memcpy(status, out.data() + 11 * n, n);
+    corr_out_copy(CorrOut{ idx, support, permille, ed, status }, 0, corr_out(out.data(), nq), 0, nq);
     return BDG_OK;
 }
 

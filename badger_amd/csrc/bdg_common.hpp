@@ -38,7 +38,7 @@ struct bdg_ctx {
     // The match is not queued when it is asked for but behind the NEXT extraction's scan (bdg_launch_deferred_match): beside
     // the scan (which streams the reads at the memory's rate) its gathers cost more than they hide, beside the alignment
     // kernels that follow (integer issue, almost no memory traffic) they are nearly free.
-    struct DeferredMatch { bool pending = false; const uint32_t* q = nullptr; uint32_t n = 0, max_ed = 0;
+    struct DeferredMatch { bool pending = false; const bdg_extract_rec* recs = nullptr; uint32_t n = 0, max_ed = 0;
                            uint32_t* idx = nullptr; uint8_t* ed = nullptr; uint16_t* ties = nullptr; } deferred;
     hipEvent_t ev_scan = nullptr;
     hipStream_t launch_stream = nullptr;    // where kernels (and their timing events) currently go: stream, or aux_stream
@@ -74,8 +74,7 @@ struct bdg_ctx {
         bool busy = false;
         bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
         // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
-        DevBuf d_match;                                      // best_idx u32 [n] | n_ties u16 [n] | best_ed u8 [n]; top-k (match_k > 0):
-                                                             // idx u32 [n * k] | n_ties u16 [n] | n_within u16 [n] | ed u8 [n * k]
+        DevBuf d_match;                                      // match_layout(n, match_k)
         void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
         hipEvent_t match_done = nullptr;
         uint32_t match_max_ed = 0, match_k = 0;
@@ -86,10 +85,10 @@ struct bdg_ctx {
     // ---- whitelist correction of a stage-1 run (correct_kernels.hip, bdg_stage1_run with BDG_STAGE1_WL_CORRECT)
     struct Correct {
         bool on = false;
-        DevBuf lists;        // per read in submission order: idx u32 [cap * 8] | ed u8 [cap * 8] | n_within u16 [cap] (42 bytes)
+        DevBuf lists;        // per read in submission order, room for cap reads: corr_lists()
         uint64_t n = 0, cap = 0;
         DevBuf support;      // u32 [w_n]: exact hits per entry over this context's chunks
-        DevBuf out;          // resolve: idx u32 | support u32 | permille i16 | dist i8 | status u8, [n] each (12 bytes per read)
+        DevBuf out;          // resolve: corr_out()
     } corr;
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
@@ -142,13 +141,12 @@ struct bdg_ctx {
 int bdg_reserve(bdg_ctx* ctx, DevBuf& b, size_t bytes);
 const void* bdg_extract_counters_now(const bdg_ctx* ctx);   // the counters of the extraction launched last (extract_kernels.hip)
 int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan);   // overlap mode: queue the waiting whitelist match now (bdg_abi.cpp)
+extern "C" void bdg_submit_times(double t[5]);   // where bdg_extract_submit's time went (bdg_abi.cpp, BADGER_AMD_INGEST_DEBUG)
 // Stage 1 with a whitelist (bdg_abi.cpp): queue the match of the chunk just submitted to `slot` on the auxiliary stream, behind
 // its extraction, so that it runs beside the next chunk's; after bdg_extract_collect of the slot, wait for it and take the
-// results (a chunk that collect had to run again is matched again first).
-extern "C" int bdg_slot_match(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed);
-extern "C" int bdg_slot_match_collect(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties);
-// the same with the k nearest entries (k = 0: the best-hit match above): best_idx / best_ed are slot 0 of the k, n_ties the
-// best-hit call's tie count; cand_idx / cand_ed [n * k] the slots (bdg_nearest16_topk)
+// results (a chunk that collect had to run again is matched again first).  With the k nearest entries (k = 0: the best-hit
+// match): best_idx / best_ed are slot 0 of the k, n_ties the best-hit call's tie count; cand_idx / cand_ed [n * k] the slots
+// (bdg_nearest16_topk)
 extern "C" int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k);
 extern "C" int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
                                            uint32_t* cand_idx, uint8_t* cand_ed);
@@ -161,10 +159,52 @@ extern "C" int bdg_correct_support_to_host(bdg_ctx* ctx, uint32_t* support);
 extern "C" int bdg_correct_support_from_host(bdg_ctx* ctx, const uint32_t* support);
 extern "C" int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
 extern "C" int bdg_correct_end(bdg_ctx* ctx);
-int bdg_correct_support_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
-                               uint32_t n, uint32_t K, uint32_t* support, uint32_t* h_idx, uint8_t* h_ed, uint16_t* h_nw);
-int bdg_correct_resolve_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
-                               uint64_t n, const uint32_t* support, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
+
+// ---- layouts of the blocks the host and the kernels share ----
+// The match results of n reads (Slot::d_match / h_match, the staging of bdg_nearest16 and bdg_nearest16_topk):
+//   idx u32 [n * max(k, 1)] | n_ties u16 [n] (if ties) | n_within u16 [n] (if k) | ed u8 [n * max(k, 1)]
+struct MatchLayout { uint32_t* idx; uint16_t* ties; uint16_t* n_within; uint8_t* ed; size_t bytes; };
+static inline MatchLayout match_layout(void* base, size_t n, size_t k, bool ties = true)
+{
+    const size_t slots = n * (k ? k : 1);
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);                  // (base may be null: the size alone is asked for)
+    const uintptr_t t = b + sizeof(uint32_t) * slots, w = t + (ties ? sizeof(uint16_t) * n : 0), e = w + (k ? sizeof(uint16_t) * n : 0);
+    return MatchLayout{ reinterpret_cast<uint32_t*>(b), ties ? reinterpret_cast<uint16_t*>(t) : nullptr,
+                        k ? reinterpret_cast<uint16_t*>(w) : nullptr, reinterpret_cast<uint8_t*>(e), (size_t)(e + slots - b) };
+}
+// Correct::lists with room for cap reads, from read `at` on: idx u32 [cap * 8] | ed u8 [cap * 8] | n_within u16 [cap]
+constexpr size_t CORR_K = 8, CORR_LISTS_READ_BYTES = CORR_K * (sizeof(uint32_t) + sizeof(uint8_t)) + sizeof(uint16_t);
+struct CorrLists { uint32_t* idx8; uint8_t* ed8; uint16_t* nw; };
+static inline CorrLists corr_lists(void* base, uint64_t cap, uint64_t at)
+{
+    uint32_t* const idx = static_cast<uint32_t*>(base);
+    uint8_t* const ed = reinterpret_cast<uint8_t*>(idx + CORR_K * cap);
+    return CorrLists{ idx + CORR_K * at, ed + CORR_K * at, reinterpret_cast<uint16_t*>(ed + CORR_K * cap) + at };
+}
+// Correct::out (and what bdg_correct_resolve hands to the host) for n reads:
+//   idx u32 [n] | support u32 [n] | permille i16 [n] | dist i8 [n] | status u8 [n]
+constexpr size_t CORR_OUT_READ_BYTES = 2 * sizeof(uint32_t) + sizeof(int16_t) + sizeof(int8_t) + sizeof(uint8_t);
+struct CorrOut { uint32_t* idx; uint32_t* support; int16_t* permille; int8_t* dist; uint8_t* status; };
+static inline CorrOut corr_out(void* base, size_t n)
+{
+    uint32_t* const idx = static_cast<uint32_t*>(base);
+    int16_t* const pm = reinterpret_cast<int16_t*>(idx + 2 * n);
+    int8_t* const dist = reinterpret_cast<int8_t*>(pm + n);
+    return CorrOut{ idx, idx + n, pm, dist, reinterpret_cast<uint8_t*>(dist + n) };
+}
+// the correction file of bdg_stage1_run (tsv_io.cpp): n results in input order; *called = rows of status exact or corrected
+bool bdg_write_corrected(const char* path, const bdg_idstore* ids, const CorrOut& res, uint64_t n, const uint32_t* wl, uint32_t nw,
+                         uint64_t* called);
+// m reads of `src` from read `from` on to read `at` of `dst`
+static inline void corr_out_copy(const CorrOut& dst, size_t at, const CorrOut& src, size_t from, size_t m)
+{
+    memcpy(dst.idx + at, src.idx + from, sizeof(uint32_t) * m);
+    memcpy(dst.support + at, src.support + from, sizeof(uint32_t) * m);
+    memcpy(dst.permille + at, src.permille + from, sizeof(int16_t) * m);
+    memcpy(dst.dist + at, src.dist + from, m);
+    memcpy(dst.status + at, src.status + from, m);
+}
+static_assert(CORR_LISTS_READ_BYTES == 42 && CORR_OUT_READ_BYTES == 12, "layouts correct_kernels.hip reads and writes");
 
 // Event-bracketed launch bookkeeping.
 int  bdg_timer_id(bdg_ctx* ctx, const char* name);
@@ -183,6 +223,18 @@ static inline int bdg_fail(bdg_ctx* ctx, int code, const std::string& msg)
 {
     if (ctx) ctx->err = msg;
     return code;
+}
+
+static inline int bdg_check_umi_len(bdg_ctx* ctx, uint32_t umi_len)
+{
+    return umi_len == 0 || umi_len > 64 ? bdg_fail(ctx, BDG_E_ARG, "umi_len out of range") : BDG_OK;
+}
+
+// the options of the whitelist correction: 0 = all in range, else which one is not: 1 = the distance (0 .. 3), 2 = the bits of
+// an edit (1 .. 8), 3 = the least posterior in permille (501 .. 1000); the callers have their own names for them
+static inline int bdg_check_correct_opts(uint32_t max_ed, uint32_t edit_bits, uint32_t min_permille)
+{
+    return max_ed > 3 ? 1 : (edit_bits < 1 || edit_bits > 8) ? 2 : (min_permille < 501 || min_permille > 1000) ? 3 : 0;
 }
 
 // ---- wave-wide data movement through DPP (gfx9 controls; behaviour on gfx950 checked by tools/ubench/dpp_check.hip) ----

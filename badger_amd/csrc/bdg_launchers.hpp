@@ -1,0 +1,39 @@
+// The launchers in the kernel translation units, as bdg_abi.cpp calls them.
+#pragma once
+
+#include "bdg_common.hpp"
+
+// extract_kernels.hip
+int bdg_extract_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint64_t, uint32_t, bdg_extract_rec*);
+int bdg_extract_status_impl(bdg_ctx*, uint64_t*, uint64_t*);
+int bdg_extract_counters_impl(bdg_ctx*, uint64_t*);
+int bdg_extract_judge_host(bdg_ctx*, const void*, uint64_t, uint64_t*, uint64_t*);
+size_t bdg_extract_counter_bytes();
+// nearest_kernels.hip (d_q, stride in words, records' flags checked, n, ...: see recs_query)
+int bdg_whitelist_load_impl(bdg_ctx*, const uint32_t*, uint32_t);
+int bdg_nearest16_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*);
+int bdg_nearest16_check(bdg_ctx*, uint32_t, uint32_t);
+int bdg_nearest16_topk_launch(bdg_ctx*, const uint32_t*, uint32_t, int, uint32_t, uint32_t, uint32_t, uint32_t*, uint8_t*, uint16_t*, uint16_t*);
+int bdg_nearest16_topk_check(bdg_ctx*, uint32_t, uint32_t, uint32_t);
+int bdg_nearest16_overflow_read(bdg_ctx*, uint32_t*);
+// correct_kernels.hip
+int bdg_correct_support_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
+                               uint32_t n, uint32_t K, uint32_t* support, uint32_t* h_idx, uint8_t* h_ed, uint16_t* h_nw);
+int bdg_correct_resolve_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
+                               uint64_t n, const uint32_t* support, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
+// graph_kernels.hip
+int bdg_graph_launch(bdg_ctx*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, int32_t, bdg_edge*, uint64_t, uint64_t*, uint32_t part = 0, uint32_t nparts = 1);
+int bdg_graph_plan(const bdg_ctx*, uint32_t, uint32_t);
+int bdg_graph_join_flags(bdg_ctx*, uint32_t*);
+int bdg_graph_flags_error(bdg_ctx*, uint32_t);
+// distinct_kernels.hip
+int bdg_distinct_launch(bdg_ctx*, const bdg_extract_rec*, uint32_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*);
+int bdg_records_of_observed_launch(bdg_ctx*, const uint32_t*, const uint8_t*, uint64_t, bdg_extract_rec*);
+int bdg_rows_of_launch(bdg_ctx*, const uint32_t*, uint32_t, const uint32_t*, uint64_t, uint32_t, uint32_t*);
+int bdg_cluster_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, int32_t*);
+int bdg_assign_reads_launch(bdg_ctx*, const bdg_extract_rec*, uint64_t, const uint32_t*, uint32_t, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*);
+int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, const uint32_t*, uint32_t, uint64_t*);
+// umi_kernels.hip
+int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
+int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t,
+                         uint32_t*, uint32_t*);
