@@ -18,6 +18,10 @@ REC_DTYPE = np.dtype([
     ("umi_end", "<i4"), ("bc_rank", "<u4"), ("r1_score", "i1"), ("strand", "i1"),
     ("valid", "u1"), ("flags", "u1"), ("reserved", "<u4")])
 EDGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4")])
+# bdg_trim_rec: the trimmed cDNA of a read (bdg_trim_batch; the rule in badger_amd/trim.py)
+TRIM_DTYPE = np.dtype([("cdna_start", "<i4"), ("cdna_end", "<i4"), ("tail_len", "<i2"), ("tso_score", "i1"), ("flags", "u1")])
+TRIM_EMIT, TRIM_TSO = 1, 2
+TSO_MIN_SCORE_DEFAULT = 20
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -46,6 +50,7 @@ EXPORTS = [
     "bdg_idstore_get", "bdg_stage1_collect", "bdg_write_assignments", "bdg_import_stage1_tsv", "bdg_host_free",
     "bdg_extract_keep_umis", "bdg_keep_observed_umis", "bdg_kept_umis", "bdg_umi_dedup_dev", "bdg_import_stage1_tsv_umi",
     "bdg_write_molecules",
+    "bdg_trim_batch", "bdg_trim_batch_dev", "bdg_extract_set_trim", "bdg_extract_collect_trim", "bdg_format_trimmed",
 ]
 
 
@@ -67,6 +72,7 @@ class IngestOpts(C.Structure):
 
 STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates is set (BDG_STAGE1_WL_CANDIDATES)
 STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist correction, the trailing fields are set (BDG_STAGE1_WL_CORRECT)
+STAGE1_TRIM = 0x400                 # bdg_stage1_opts.whitelist: trimmed reads, the fields behind the correction's are set (BDG_STAGE1_TRIM)
 # status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
 WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
 WLC_STATUS = ("none", "exact", "corrected", "ambiguous", "truncated")
@@ -84,6 +90,11 @@ class Stage1OptsCorrect(Stage1Opts):
     _fields_ = [("bc_edit_bits", C.c_uint32), ("bc_min_permille", C.c_uint32), ("corrected_path", C.c_char_p)]
 
 
+class Stage1OptsTrim(Stage1OptsCorrect):
+    """bdg_stage1_opts with the fields read only with STAGE1_TRIM"""
+    _fields_ = [("trimmed_path", C.c_char_p), ("tso_min_score", C.c_uint32), ("reserved_trim", C.c_uint32)]
+
+
 class Stage1Result(C.Structure):
     """bdg_stage1_result"""
     _fields_ = [("reads", C.c_uint64), ("barcodes", C.c_uint64), ("polyt", C.c_uint64), ("r1", C.c_uint64),
@@ -97,6 +108,11 @@ class Stage1Result(C.Structure):
 class Stage1ResultCorrect(Stage1Result):
     """bdg_stage1_result with the field written only with STAGE1_WL_CORRECT"""
     _fields_ = [("whitelist_corrected", C.c_uint64)]
+
+
+class Stage1ResultTrim(Stage1ResultCorrect):
+    """bdg_stage1_result with the counts written only with STAGE1_TRIM"""
+    _fields_ = [("trimmed_reads", C.c_uint64), ("trimmed_tso", C.c_uint64), ("trimmed_bases", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -219,6 +235,12 @@ def load():
     L.bdg_umi_dedup_dev.argtypes = [vp, vp, vp, vp, u64, vp, u32, u32, u32, vp, vp]
     L.bdg_import_stage1_tsv_umi.argtypes = [C.c_char_p, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
     L.bdg_write_molecules.argtypes = [vp, vp, vp, vp, vp, u64, C.c_char_p]
+    L.bdg_trim_batch.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_trim_batch_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_extract_set_trim.argtypes = [vp, C.c_int, u32]
+    L.bdg_extract_collect_trim.argtypes = [vp, u32, vp]
+    L.bdg_format_trimmed.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
+    L.bdg_format_trimmed.restype = C.c_int64
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -317,6 +339,33 @@ class Context:
         """wait for the chunk submitted to `slot` and return its records"""
         out = np.zeros(n, dtype=REC_DTYPE)
         self._check(self.lib.bdg_extract_collect(self.h, slot, out.ctypes.data))
+        return out
+
+    def trim_batch(self, bases, off, recs, tso_min_score=TSO_MIN_SCORE_DEFAULT):
+        """the trimmed cDNA of every read (bdg_trim_batch): reads as for extract_batch and their records -> TRIM_DTYPE array"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        n = len(off) - 1
+        if len(recs) != max(n, 0):
+            raise ValueError("trim_batch: %d reads, %d records" % (n, len(recs)))
+        out = np.zeros(max(n, 0), dtype=TRIM_DTYPE)
+        self._check(self.lib.bdg_trim_batch(self.h, bases.ctypes.data, off.ctypes.data, max(n, 0), recs.ctypes.data, tso_min_score,
+                                            out.ctypes.data))
+        return out
+
+    def trim_batch_dev(self, d_bases, d_off, n, d_recs, tso_min_score, d_out):
+        """device form, behind the extract_batch_dev call that wrote d_recs (bdg_trim_batch_dev); d_out: 12 bytes per read"""
+        self._check(self.lib.bdg_trim_batch_dev(self.h, _ptr(d_bases), _ptr(d_off), n, _ptr(d_recs), tso_min_score, _ptr(d_out)))
+
+    def extract_set_trim(self, on=True, tso_min_score=TSO_MIN_SCORE_DEFAULT):
+        """while on, extract_submit queues the chunk's trim behind its extraction; extract_collect_trim hands it over"""
+        self._check(self.lib.bdg_extract_set_trim(self.h, 1 if on else 0, tso_min_score))
+
+    def extract_collect_trim(self, slot, n):
+        """the trim results of the chunk just collected from `slot` (after extract_collect)"""
+        out = np.zeros(n, dtype=TRIM_DTYPE)
+        self._check(self.lib.bdg_extract_collect_trim(self.h, slot, out.ctypes.data))
         return out
 
     def extract_keep_records(self, on=True):
@@ -622,19 +671,27 @@ def chunk_reads(ch):
 
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
-               corrected_path=None, bc_edit_bits=5, bc_min_permille=975):
+               corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
     whitelist columns (header must name them); bc_candidates=K (1 .. 8) one more, whitelist_candidates.  corrected_path (with
-    whitelist): whitelist correction (BDG_STAGE1_WL_CORRECT) into that file; the result then has whitelist_corrected."""
+    whitelist): whitelist correction (BDG_STAGE1_WL_CORRECT) into that file; the result then has whitelist_corrected.
+    trimmed_path (with or without whitelist): the trimmed cDNA of every read as FASTA into that file (BDG_STAGE1_TRIM, TSO accepted
+    from tso_min_score on); the result then has trimmed_reads, trimmed_tso and trimmed_bases."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
     wl_mode = (1 | (STAGE1_WL_CANDIDATES if bc_candidates else 0) | (STAGE1_WL_CORRECT if correct else 0)) if whitelist else 0
+    if trimmed_path is not None:
+        wl_mode |= STAGE1_TRIM
     args = (umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
             wl_mode, max_bc_dist, bc_candidates)
-    if correct:
+    if trimmed_path is not None:
+        o = Stage1OptsTrim(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
+                           os.fsencode(trimmed_path), tso_min_score, 0)
+        res = Stage1ResultTrim()
+    elif correct:
         o = Stage1OptsCorrect(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path))
         res = Stage1ResultCorrect()
     else:
@@ -826,6 +883,24 @@ def format_rows_wlk(ch, recs, best_idx, best_ed, n_ties, cand_idx, cand_ed, wl):
         raise ValueError("format_rows_wlk: candidate arrays must both be [n, k], got %s / %s" % (cidx.shape, ced.shape))
     return _format_rows(load().bdg_format_rows_wlk, "bdg_format_rows_wlk", ch,
                         _wl_args("format_rows_wlk", ch, recs, best_idx, best_ed, n_ties, wl, more=(cidx,)) + [cidx.shape[1], cidx, ced], 5)
+
+
+def format_trimmed(ch, recs, trim, best_idx=None, n_ties=None, wl=None):
+    """the FASTA text of a chunk's trimmed reads (bdg_format_trimmed) + (records, with a TSO cut, bases) counts; with
+    best_idx / n_ties / wl (as for format_rows_wl) the headers carry CB where the row's whitelist_barcode is not '*'"""
+    recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+    trim = np.ascontiguousarray(trim, dtype=TRIM_DTYPE)
+    if len(recs) != ch.n or len(trim) != ch.n:
+        raise ValueError("format_trimmed: %d reads, %d records, %d trim results" % (ch.n, len(recs), len(trim)))
+    if wl is None:
+        args = [recs, trim, None, None, None, 0]
+    else:
+        idx, ties = np.ascontiguousarray(best_idx, dtype=np.uint32), np.ascontiguousarray(n_ties, dtype=np.uint16)
+        if len(idx) != ch.n or len(ties) != ch.n:
+            raise ValueError("format_trimmed: %d reads, %d / %d calls" % (ch.n, len(idx), len(ties)))
+        wl = np.ascontiguousarray(wl, dtype=np.uint32)
+        args = [recs, trim, idx, ties, wl, len(wl)]
+    return _format_rows(load().bdg_format_trimmed, "bdg_format_trimmed", ch, args, 3)
 
 
 _DEFAULT = {}

@@ -265,8 +265,9 @@ void bdg_free(bdg_ctx* ctx)
                        &ctx->x_allumis, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
-        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match }) if (b->p) (void)hipFree(b->p);
+        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match, &sl.d_trim }) if (b->p) (void)hipFree(b->p);
         if (sl.h_recs) (void)hipHostFree(sl.h_recs);
+        if (sl.h_trim) (void)hipHostFree(sl.h_trim);
         if (sl.h_match) (void)hipHostFree(sl.h_match);
         if (sl.match_done) (void)hipEventDestroy(sl.match_done);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
@@ -469,6 +470,13 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
     hipStream_t st = ctx->stream;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_recs, sl.d_recs.p, sizeof(bdg_extract_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_counters, bdg_extract_counters_now(ctx), bdg_extract_counter_bytes(), hipMemcpyDeviceToHost, st));
+    if (sl.trim) {
+        // the chunk's trim behind its extraction (a rerun passes here again: the trim of placeholder records is overwritten)
+        if ((rc = bdg_trim_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
+                                  static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n, sl.trim_min_score, static_cast<bdg_trim_rec*>(sl.d_trim.p))))
+            return rc;
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_trim, sl.d_trim.p, sizeof(bdg_trim_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
+    }
     BDG_HIP_TRY(ctx, hipEventRecord(sl.done, st));
     return BDG_OK;
 }
@@ -489,6 +497,7 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
+    sl.trim = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
     if (n == 0) { sl.busy = true; return BDG_OK; }
     if (int rco = check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -500,6 +509,10 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if ((rc = bdg_reserve(ctx, sl.d_recs, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
     if ((rc = pinned_reserve(ctx, sl.h_recs, sl.h_recs_bytes, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
     if ((rc = pinned_reserve(ctx, sl.h_off, sl.h_off_bytes, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if (sl.trim) {
+        if ((rc = bdg_reserve(ctx, sl.d_trim, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
+        if ((rc = pinned_reserve(ctx, sl.h_trim, sl.h_trim_bytes, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
+    }
     if (!sl.h_counters) {
         if (hipHostMalloc(&sl.h_counters, bdg_extract_counter_bytes(), hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError(); sl.h_counters = nullptr; return bdg_fail(ctx, BDG_E_NOMEM, "hipHostMalloc failed");
@@ -575,6 +588,74 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
         }
         ctx->x_allrecs_n += sl.n;
     }
+    return BDG_OK;
+}
+
+// ---- trimmed cDNA ---------------------------------------------------------------
+static int check_tso_min_score(bdg_ctx* ctx, uint32_t v)
+{
+    return v < 8 || v > 30 ? bdg_fail(ctx, BDG_E_ARG, "tso_min_score out of range (8 .. 30)") : BDG_OK;
+}
+
+int bdg_trim_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
+                       const bdg_extract_rec* d_recs, uint32_t tso_min_score, bdg_trim_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
+    if (n && (!d_bases || !d_off || !d_recs || !d_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (reinterpret_cast<uintptr_t>(d_recs) & 15u) return bdg_fail(ctx, BDG_E_ARG, "d_recs must be 16-byte aligned");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_trim_launch(ctx, d_bases, d_off, d_recs, n, tso_min_score, d_out);
+}
+
+int bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
+                   const bdg_extract_rec* recs, uint32_t tso_min_score, bdg_trim_rec* out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
+    if (n == 0) return BDG_OK;
+    if (!bases || !off || !recs || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rco = check_offsets(ctx, off, n)) return rco;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t lo = off[0], total = off[n] - lo;
+    const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, trim_bytes = sizeof(bdg_trim_rec) * (size_t)n;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, total + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_bytes + trim_bytes))) return rc;         // records | results
+    std::vector<uint64_t> rel((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
+    hipStream_t st = ctx->stream;
+    char* const d_recs = static_cast<char*>(ctx->s_out0.p);
+    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, total, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, rec_bytes, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_trim_launch(ctx, static_cast<const uint8_t*>(ctx->s_in0.p), static_cast<const uint64_t*>(ctx->s_in1.p),
+                              reinterpret_cast<const bdg_extract_rec*>(d_recs), n, tso_min_score, reinterpret_cast<bdg_trim_rec*>(d_recs + rec_bytes))))
+        return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_recs + rec_bytes, trim_bytes, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
+    return BDG_OK;
+}
+
+int bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (on) if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
+    ctx->trim_on = on != 0;
+    ctx->trim_min_score = on ? tso_min_score : 0;
+    return BDG_OK;
+}
+
+int bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out)
+{
+    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "collect the slot's records first (bdg_extract_collect)");
+    if (!sl.trim) return bdg_fail(ctx, BDG_E_ARG, "the slot's chunk was submitted without a trim (bdg_extract_set_trim)");
+    if (sl.n == 0) return BDG_OK;
+    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    memcpy(out, sl.h_trim, sizeof(bdg_trim_rec) * (size_t)sl.n);  // (the copy was queued in front of the event collect waited for)
     return BDG_OK;
 }
 

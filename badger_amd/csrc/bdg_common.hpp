@@ -73,6 +73,10 @@ struct bdg_ctx {
         uint32_t n = 0, umi_len = 0; uint64_t total = 0, qcap = 0;
         bool busy = false;
         bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
+        // trim of the chunk (bdg_extract_set_trim): behind the extraction on the same stream, results copied to h_trim
+        DevBuf d_trim;                                       // bdg_trim_rec [n]
+        void* h_trim = nullptr; size_t h_trim_bytes = 0;     // pinned
+        bool trim = false; uint32_t trim_min_score = 0;      // what the chunk was submitted with
         // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
         DevBuf d_match;                                      // match_layout(n, match_k)
         void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
@@ -90,6 +94,7 @@ struct bdg_ctx {
         DevBuf support;      // u32 [w_n]: exact hits per entry over this context's chunks
         DevBuf out;          // resolve: corr_out()
     } corr;
+    bool trim_on = false; uint32_t trim_min_score = 0;       // bdg_extract_set_trim: for the submits that follow
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
     DevBuf x_allrecs; uint64_t x_allrecs_n = 0;

@@ -2,6 +2,7 @@
 //   bdg_format_rows  one TSV row per read from the device's 32-byte records (TenXBarcodeDetectionResult.__str__,
 //                    barcode_callers.py:40-42,91-93,117-119); the barcode / UMI text is sliced from the chunk's bases, for
 //                    reverse-strand results from the reverse complement (barcode_extraction/common.py:34-39).
+//   bdg_format_trimmed  the trimmed cDNA of a chunk's reads as FASTA text, from the records and the trim results (--trimmed_reads).
 //   bdg_stage1_run   input file -> TSV, everything between in native threads: the readers of ingest.cpp fill pinned chunks,
 //                    this thread submits them to the GPU(s) (bdg_extract_submit / collect, chunk k on context k mod N, two
 //                    in flight per context), a few formatter threads turn records into rows and a writer thread writes them
@@ -134,6 +135,66 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
     return o;
 }
 
+struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0; };
+
+// upper bound of the FASTA text of a chunk's trimmed reads
+uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl)
+{
+    uint64_t need = 0;
+    for (uint32_t i = 0; i < ch->n; ++i) {
+        if (!(tr[i].flags & BDG_TRIM_EMIT)) continue;
+        const uint64_t L = ch->off[i + 1] - ch->off[i];
+        need += (ch->id_off[i + 1] - ch->id_off[i]) + 48 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start))
+                + (with_wl ? 22 : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);
+    }
+    return need;
+}
+
+// ">id\tCR:Z:barcode\tUR:Z:UMI\tST:A:strand[\tCB:Z:whitelist barcode]\n" cDNA in mRNA sense "\n" per read with BDG_TRIM_EMIT
+char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, const WlCalls* wc, char* o, TrimStats& st)
+{
+    for (uint32_t i = 0; i < ch->n; ++i) {
+        const bdg_trim_rec& t = tr[i];
+        if (!(t.flags & BDG_TRIM_EMIT)) continue;
+        const bdg_extract_rec& r = recs[i];
+        const uint8_t* seq = ch->bases + ch->off[i];
+        const int64_t L = (int64_t)(ch->off[i + 1] - ch->off[i]);
+        const char* id = ch->ids + ch->id_off[i];
+        size_t idl = (size_t)(ch->id_off[i + 1] - ch->id_off[i]);
+        for (size_t x = 0; x < idl; ++x) if (id[x] == ' ' || id[x] == '\t') { idl = x; break; }     // (the first word, like the reader's ids)
+        *o++ = '>';
+        memcpy(o, id, idl); o += idl;
+        const bool rev = (r.flags & BDG_FLAG_REV) != 0;
+        auto slice = [&](int64_t a, int64_t b) {                       // write_rows' slice: s[a:b] of the strand's text
+            a = std::min<int64_t>(std::max<int64_t>(a, 0), L); b = std::min<int64_t>(std::max<int64_t>(b, 0), L);
+            if (rev) for (int64_t x = a; x < b; ++x) *o++ = comp_base((char)seq[L - 1 - x]);
+            else if (b > a) { memcpy(o, seq + a, (size_t)(b - a)); o += b - a; }
+        };
+        memcpy(o, "\tCR:Z:", 6); o += 6;
+        slice(r.bc_start, (int64_t)r.bc_start + 16);
+        memcpy(o, "\tUR:Z:", 6); o += 6;
+        slice(r.umi_start, r.umi_end);
+        memcpy(o, "\tST:A:", 6); o += 6;
+        *o++ = r.strand > 0 ? '+' : (r.strand < 0 ? '-' : '.');
+        if (wc && r.valid && (r.flags & BDG_FLAG_RANK_OK) && wc->idx[i] < wc->nw && wc->ties[i] == 1) {   // the row's whitelist_barcode is not '*'
+            memcpy(o, "\tCB:Z:", 6); o += 6;
+            o = put_barcode16(o, wc->wl[wc->idx[i]]);
+        }
+        *o++ = '\n';
+        // revcomp(s[a:b]): for a reverse-strand record the read's own bytes, for a forward one their reverse complement
+        const int64_t a = std::min<int64_t>(std::max<int64_t>(t.cdna_start, 0), L), b = std::min<int64_t>(std::max<int64_t>(t.cdna_end, 0), L);
+        if (b > a) {
+            if (rev) { memcpy(o, seq + (L - b), (size_t)(b - a)); o += b - a; }
+            else for (int64_t x = b - 1; x >= a; --x) *o++ = comp_base((char)seq[x]);
+            st.bases += (uint64_t)(b - a);
+        }
+        *o++ = '\n';
+        ++st.reads;
+        if (t.flags & BDG_TRIM_TSO) ++st.tso;
+    }
+    return o;
+}
+
 // one chunk on its way through a GPU: its place in the input, the reader's view of it, the context and slot it runs on
 struct Fly { uint64_t seq = 0, g0 = 0; bdg_ingest_chunk ch; bdg_ctx* ctx = nullptr; uint32_t slot = 0; };
 
@@ -143,10 +204,14 @@ struct Job : Fly {
         std::vector<bdg_extract_rec> recs;
         std::vector<uint32_t> idx; std::vector<uint8_t> ed; std::vector<uint16_t> ties;       // whitelist calls
         std::vector<uint32_t> cidx; std::vector<uint8_t> ced;                                 // top-k slots (bc_candidates)
+        std::vector<bdg_trim_rec> trim;                                                       // BDG_STAGE1_TRIM
     } r;
     std::vector<char> text; size_t text_len = 0;
     RowStats st;
 };
+
+// the FASTA text of a chunk's trimmed reads on its way to the second writer
+struct TrimText { std::vector<char> text; size_t len = 0; TrimStats st; };
 
 struct Pipeline {
     bdg_ingest* ing = nullptr;
@@ -164,6 +229,12 @@ struct Pipeline {
     RowStats total;
     double t_format = 0, t_write = 0;
     uint64_t out_bytes = 0;
+    // BDG_STAGE1_TRIM: the formatters make a chunk's FASTA text beside its rows, a second writer appends it in input order
+    int fd_trim = -1;
+    std::map<uint64_t, TrimText*> trimmed;
+    uint64_t next_trim = 0;
+    bool trim_write_failed = false;
+    TrimStats trim_total;
 
     void format_loop()
     {
@@ -181,11 +252,18 @@ struct Pipeline {
             j->text.resize((size_t)rows_bound(&j->ch, j->r.recs.data(), header_every, header.size(), pw));
             char* e = write_rows(&j->ch, j->r.recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
             j->text_len = (size_t)(e - j->text.data());
+            TrimText* tt = nullptr;
+            if (fd_trim >= 0) {
+                tt = new TrimText;
+                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr));
+                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), pw, tt->text.data(), tt->st) - tt->text.data());
+            }
             bdg_ingest_release(ing, j->ch.id);
             j->r = Job::Results();                             // (their memory goes back now, not when the row text is written)
             const double dt = now_s() - t0;
             {
                 std::lock_guard<std::mutex> lk(mu);
+                if (tt) trimmed[j->seq] = tt;
                 formatted[j->seq] = j;
                 --outstanding;
                 t_format += dt;
@@ -216,6 +294,26 @@ struct Pipeline {
                 t_write += dt; out_bytes += j->text_len;
             }
             delete j;
+        }
+    }
+    void trim_write_loop()
+    {
+        for (;;) {
+            TrimText* t;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return (closing && to_format.empty() && outstanding == 0 && trimmed.empty()) || trimmed.count(next_trim); });
+                auto it = trimmed.find(next_trim);
+                if (it == trimmed.end()) return;
+                t = it->second; trimmed.erase(it); ++next_trim;
+            }
+            const bool bad = !write_all(fd_trim, t->text.data(), t->len);
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (bad) trim_write_failed = true;
+                trim_total.reads += t->st.reads; trim_total.tso += t->st.tso; trim_total.bases += t->st.bases;
+            }
+            delete t;
         }
     }
 };
@@ -375,19 +473,41 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
     return format_rows(ch, recs, &wc, out, cap, counts);
 }
 
+int64_t bdg_format_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                           const uint32_t* best_idx, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                           char* out, uint64_t cap, uint64_t counts[3])
+{
+    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
+    const bool with_wl = best_idx || n_ties || wl;
+    if (with_wl && ch->n && (!best_idx || !n_ties || (nw && !wl))) return BDG_E_ARG;
+    const WlCalls wc{ best_idx, nullptr, n_ties, wl, nw };
+    const uint64_t need = trimmed_bound(ch, recs, trim, with_wl);
+    if (!out || need > cap) return (int64_t)need;
+    TrimStats st;
+    char* e = write_trimmed(ch, recs, trim, with_wl ? &wc : nullptr, out, st);
+    if (counts) { counts[0] = st.reads; counts[1] = st.tso; counts[2] = st.bases; }
+    return (int64_t)(e - out);
+}
+
 int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                    const bdg_stage1_opts* o, bdg_stage1_result* res)
 {
     if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !out_path || !header || !o || !res) return BDG_E_ARG;
     bdg_ctx* const c0 = ctxs[0];
-    const bool corr = o->whitelist && (o->whitelist & BDG_STAGE1_WL_CORRECT);
-    // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT)
-    memset(res, 0, corr ? sizeof(*res) : offsetof(bdg_stage1_result, whitelist_corrected));
+    // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
+    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~BDG_STAGE1_TRIM) != 0;
+    const bool corr = wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT);
+    // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT, those behind it with BDG_STAGE1_TRIM)
+    memset(res, 0, trim ? sizeof(*res) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
+    if (trim) {
+        if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
+        if (o->tso_min_score < 8 || o->tso_min_score > 30) return bdg_fail(c0, BDG_E_ARG, "tso_min_score out of range (8 .. 30)");
+    }
     // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
     std::vector<uint32_t> wl_caller;
-    if (o->whitelist) {
+    if (wl_on) {
         // a caller that does not set BDG_STAGE1_WL_CANDIDATES knows bc_candidates as the upper half of a 32-bit max_bc_dist
         if (o->max_bc_dist > 16 || (!(o->whitelist & BDG_STAGE1_WL_CANDIDATES) && o->bc_candidates))
             return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
@@ -427,25 +547,40 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     if (const char* e = getenv("BADGER_AMD_INFLIGHT")) { const long v = atol(e); if (v >= 1 && v <= BDG_SLOTS) per_ctx = (uint32_t)v; }
     const uint64_t max_outstanding = 2 * fthreads + 2;           // collected chunks waiting for / in the formatters
     Pipeline P;
-    ChunkLoop L{ nullptr, ctxs, n_ctx, per_ctx, o->umi_len, res, o->whitelist ? o : nullptr, ids, false, false };
+    ChunkLoop L{ nullptr, ctxs, n_ctx, per_ctx, o->umi_len, res, wl_on ? o : nullptr, ids, false, false };
     int rc = open_reader(in_path, o, per_ctx * n_ctx + 2 * fthreads + 4, &P.ing, L.err);
     if (rc) { if (corr) corr_end(); return bdg_fail(c0, rc, L.err); }
     L.ing = P.ing;
     P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (P.fd < 0) { bdg_ingest_close(P.ing); if (corr) corr_end(); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
     P.header = header; P.header_every = o->header_every;
-    if (o->whitelist) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
+    if (wl_on) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
+    if (trim) {
+        P.fd_trim = ::open(o->trimmed_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        if (P.fd_trim < 0) {
+            ::close(P.fd); bdg_ingest_close(P.ing); if (corr) corr_end();
+            return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
+        }
+        for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 1, o->tso_min_score);   // (checked above; off again below)
+    }
     bool ok_io = true;
     if (!o->header_every) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
     std::vector<std::thread> fmt;
     for (uint32_t i = 0; i < fthreads; ++i) fmt.emplace_back(&Pipeline::format_loop, &P);
     std::thread writer(&Pipeline::write_loop, &P);
+    std::thread trim_writer;
+    if (trim) trim_writer = std::thread(&Pipeline::trim_write_loop, &P);
 
     double t_fmt_wait = 0;
     rc = L.run([&](const Fly& f, std::vector<bdg_extract_rec>& recs) -> int {   // with the match's answer, to the formatters
         Job* j = new Job(f);
         j->r.recs.swap(recs);
-        if (o->whitelist) {
+        if (trim) {
+            j->r.trim.resize(f.ch.n);
+            const int r = bdg_extract_collect_trim(f.ctx, f.slot, j->r.trim.data());
+            if (r) { delete j; return r; }
+        }
+        if (wl_on) {
             j->r.idx.resize(f.ch.n); j->r.ed.resize(f.ch.n); j->r.ties.resize(f.ch.n);
             j->r.cidx.resize((size_t)f.ch.n * o->bc_candidates); j->r.ced.resize((size_t)f.ch.n * o->bc_candidates);
             const double t0 = now_s();
@@ -465,11 +600,17 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         t_fmt_wait += now_s() - t1;
         return BDG_OK;
     });
-    if (o->whitelist) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_synchronize(ctxs[c]);    // (a match still queued after a failure)
+    if (wl_on) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_synchronize(ctxs[c]);    // (a match still queued after a failure)
+    if (trim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 0, 0);
     { std::lock_guard<std::mutex> lk(P.mu); P.closing = true; }
     P.cv.notify_all();
     for (auto& t : fmt) t.join();
     writer.join();
+    if (trim) {
+        trim_writer.join();
+        if (::close(P.fd_trim) != 0) P.trim_write_failed = true;
+        res->trimmed_reads = P.trim_total.reads; res->trimmed_tso = P.trim_total.tso; res->trimmed_bases = P.trim_total.bases;
+    }
     // rows of the chunks before a failure are in the file, like in the reference's loop
     if (rc == BDG_OK && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;
     if (::close(P.fd) != 0) ok_io = false;
@@ -496,6 +637,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     }
     if (rc) return bdg_fail(c0, rc, L.err);
     if (!ok_io || P.write_failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + out_path);
+    if (P.trim_write_failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + o->trimmed_path);
     return BDG_OK;
 }
 

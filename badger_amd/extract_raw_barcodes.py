@@ -31,6 +31,14 @@ What differs from the reference, by design:
     (corrected_barcode, corrected_dist, support, posterior in permille, status; badger_amd/wl_correct.py restates the rule,
     include/badger_hip.h bdg_nearest16_correct states it) and the .stats gets a "Whitelist corrected" line.  The main TSV
     does not change.
+  * --trimmed_reads PATH: the cDNA of every read with a barcode and a polyT tail as FASTA (qualities are dropped when the
+    reads are parsed: no FASTQ), cut behind the tail and in front of the template-switch oligo (found by a local alignment
+    of at least --tso_min_score, default 20, in the read's last 64 bases), in mRNA sense, one line per sequence, header
+    ">read_id\tCR:Z:barcode\tUR:Z:UMI\tST:A:strand[\tCB:Z:whitelist_barcode]" (CB with -b, where the TSV's whitelist_barcode is
+    not '*').  The rule is restated in badger_amd/trim.py and stated in include/badger_hip.h (bdg_trim_batch).  Records come
+    in input order; the TSV, the .stats and the .corrected.tsv do not change; the three counts go to the log.  Every input
+    this command line reads goes through the native pipeline, which is where the flag lives; the Python-driven
+    BarcodeCaller.process path (stage 2's read input) has no such output.
 """
 import argparse
 import gzip
@@ -55,6 +63,7 @@ CORRECT_MAX_BC_DIST = 3
 CORRECTED_SUFFIX = ".corrected.tsv"
 BC_EDIT_BITS_DEFAULT = 5
 BC_MIN_POSTERIOR_DEFAULT = 0.975
+TSO_MIN_SCORE_RANGE = (8, 30)
 BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
 
 
@@ -388,7 +397,10 @@ def _run_native(args, header_every, threads, skip_secondary):
                              detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
                              whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
                              bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
-                             **_correct_kwargs(args, wl is not None))
+                             **_correct_kwargs(args, wl is not None), **_trim_kwargs(args))
+    if getattr(args, "trimmed_reads", None):
+        logger.info("Trimmed reads: %d written to %s, %d with the TSO cut off, %d bases"
+                    % (res.trimmed_reads, args.trimmed_reads, res.trimmed_tso, res.trimmed_bases))
     timing = os.environ.get("BADGER_AMD_STAGE1_TIMING")
     if timing:                                   # where the run's time went (tools/cli_throughput.py reads it)
         import json
@@ -509,7 +521,17 @@ def parse_args(sys_argv):
                    help="--bc_correct: smallest posterior of a call, 0.501 .. 1.0 (default %g)" % BC_MIN_POSTERIOR_DEFAULT)
     p.add_argument("--bc_edit_bits", type=_bc_edit_bits, default=None, metavar="B",
                    help="--bc_correct: one edit makes a candidate 2^B times less likely, 1 .. 8 (default %d)" % BC_EDIT_BITS_DEFAULT)
+    p.add_argument("--trimmed_reads", type=str, default=None, metavar="PATH",
+                   help="write the trimmed, oriented cDNA of every read with a barcode and a polyT tail to PATH as FASTA (no "
+                        "qualities: they are dropped at parse time), barcode and UMI in the header (CR / UR / ST tags; CB with "
+                        "--barcodes: the per-read whitelist call - with --bc_correct too, since the corrected call needs the "
+                        "whole run: join it by read id from <output>%s)" % CORRECTED_SUFFIX)
+    p.add_argument("--tso_min_score", type=_tso_min_score, default=None, metavar="N",
+                   help="--trimmed_reads: smallest local-alignment score (match +1, mismatch / gap -1) at which the template-switch "
+                        "oligo is cut off, %d .. %d (default %d)" % (TSO_MIN_SCORE_RANGE + (_native.TSO_MIN_SCORE_DEFAULT,)))
     args = p.parse_args(sys_argv)
+    if args.tso_min_score is not None and not args.trimmed_reads:
+        p.error("--tso_min_score needs --trimmed_reads")
     if args.max_bc_dist is not None and not args.barcodes:
         p.error("--max_bc_dist needs --barcodes")
     if args.bc_candidates is not None and not args.barcodes:
@@ -552,6 +574,16 @@ def _bc_candidates(text):
     return v
 
 
+def _tso_min_score(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not TSO_MIN_SCORE_RANGE[0] <= v <= TSO_MIN_SCORE_RANGE[1]:
+        raise argparse.ArgumentTypeError("%d is outside %d .. %d" % ((v,) + TSO_MIN_SCORE_RANGE))
+    return v
+
+
 def _bc_posterior(text):
     """--bc_min_posterior as permille (501 .. 1000)"""
     try:
@@ -587,6 +619,15 @@ def _correct_kwargs(args, whitelist):
     return dict(corrected_path=args.output + CORRECTED_SUFFIX,
                 bc_min_permille=int(round(BC_MIN_POSTERIOR_DEFAULT * 1000)) if pm is None else pm,
                 bc_edit_bits=BC_EDIT_BITS_DEFAULT if bits is None else bits)
+
+
+def _trim_kwargs(args):
+    """stage1_run's trimming arguments: none without --trimmed_reads"""
+    path = getattr(args, "trimmed_reads", None)
+    if not path:
+        return {}
+    score = getattr(args, "tso_min_score", None)
+    return dict(trimmed_path=path, tso_min_score=_native.TSO_MIN_SCORE_DEFAULT if score is None else score)
 
 
 def _max_bc_dist(args):

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 R1 = "CTACACGACGCTCTTCCGATCT"          # reference barcode_callers.py:154
+TSO = "CCCATGTACTCTGCGTTGATACCACTGCTT"  # reference barcode_callers.py:156
 _CODE = {"A": 0, "C": 1, "G": 2, "T": 3}  # reference common.py:11-14 (rank encoding)
 _ASCII = np.frombuffer(b"ACGT", dtype=np.uint8)
 
@@ -98,10 +99,13 @@ def _table_lengths(seed):
 
 
 def make_reads(n, whitelist, seed=1, device="cpu", umi_len=12, n_cells=5000,
-               p_sub=0.03, p_ins=0.02, p_del=0.03, chunk=50000, with_truth=False):
+               p_sub=0.03, p_ins=0.02, p_del=0.03, chunk=50000, with_truth=False, tso=False, tso_tail=0):
     """-> (bases uint8[total] ASCII, off int64[n+1]) on `device` (+ truth dict).  The same (n, whitelist, seed) give
     the same bytes on every device: every random draw is a hash of (seed, purpose, index) in 64-bit integer arithmetic,
-    tables (cell choice, read lengths) are built with numpy on the host."""
+    tables (cell choice, read lengths) are built with numpy on the host.
+    tso: the cDNA ends in the template-switch oligo (TSO below), followed by tso_tail more random bases - the layout
+    junk + R1 + barcode + UMI + T*30 + cDNA + TSO [+ adapter bases]; a read too short for it is lengthened so that at least 20
+    bases of cDNA remain.  Off by default, and the default output is what it was."""
     dev = torch.device(device)
     wl_np = np.ascontiguousarray(whitelist).astype(np.int64)
     n_cells = min(n_cells, len(wl_np))
@@ -129,6 +133,8 @@ def make_reads(n, whitelist, seed=1, device="cpu", umi_len=12, n_cells=5000,
         total = len_tab[_lsr(_hash64(seed, 5, ridx), 48)]
         fixed = junk + len(R1) + 16 + umi_len + 30
         L = torch.maximum(total, fixed)
+        if tso:
+            L = torch.maximum(L, fixed + 20 + len(TSO) + int(tso_tail))
         rc = (_hash64(seed, 6, ridx) & 1) == 1
         off = torch.zeros(m + 1, dtype=torch.int64, device=dev)
         off[1:] = torch.cumsum(L, 0)
@@ -147,6 +153,10 @@ def make_reads(n, whitelist, seed=1, device="cpu", umi_len=12, n_cells=5000,
         t0 = 38 + umi_len
         in_t = (rel >= t0) & (rel < t0 + 30)
         codes[in_t] = 3
+        if tso:
+            tpos = pos - (L[rid] - len(TSO) - int(tso_tail))
+            in_tso = (tpos >= 0) & (tpos < len(TSO))
+            codes[in_tso] = torch.tensor([_CODE[c] for c in TSO], dtype=torch.uint8, device=dev)[tpos[in_tso]]
         # reverse-complement half of the reads
         src = torch.where(rc[rid], off[rid] + L[rid] - 1 - pos, torch.arange(N, device=dev))
         codes = torch.where(rc[rid], 3 - codes[src], codes)

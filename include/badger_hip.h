@@ -213,6 +213,47 @@ int  bdg_keep_observed_umis(bdg_ctx* ctx, const uint32_t* codes, uint64_t n);
 /* The kept UMI codes: device pointer (valid until the next collect / keep call) and count */
 int  bdg_kept_umis(bdg_ctx* ctx, const uint32_t** d_umis, uint64_t* n);
 
+/* ---- trimmed cDNA (stage 1's --trimmed_reads; the rule restated in badger_amd/trim.py) ------------------------------ */
+/* Per read, from its extraction record and its bases: where the cDNA lies between the polyT tail and the template-switch oligo
+ * (TSO).  s = the strand's text of length L (the reverse complement of the read for BDG_FLAG_REV records), p = rec.polyT.
+ * Eligible: rec.valid == 1, p >= 0, no BDG_FLAG_INCOMPLETE; every other read gets {-1, -1, 0, 0, 0}.
+ *   tail   from column p on a running score takes +1 for 'T' and -2 for anything else (N included); cdna_start is the column
+ *          behind the last strict maximum of it (p when there is none); the scan stops at the read's end or once the score
+ *          lies BDG_TRIM_TAIL_XDROP below its maximum (five non-T in a row always do that).
+ *   TSO    the pattern BDG_TRIM_TSO_SEQ is aligned locally (the alignment stage 1 uses for R1: match +1, mismatch -1, gap open =
+ *          extend = 1, N scores 0, SSW's end / begin tie rule) against w = s[max(cdna_start, L - BDG_TRIM_TSO_WINDOW) : L].
+ *          tso_score = the score (0 for an empty window).  At tso_score >= tso_min_score the cut goes to where the pattern's
+ *          first base would sit: cdna_end = max(cdna_start, window start + ref_begin - pattern_begin), flag BDG_TRIM_TSO;
+ *          otherwise cdna_end = L.
+ *   BDG_TRIM_EMIT is set when cdna_end > cdna_start.  tail_len = cdna_start - p, saturating at 32767.
+ * Coordinates are strand coordinates, like the extraction record's. */
+#define BDG_TRIM_TAIL_XDROP  10
+#define BDG_TRIM_TSO_WINDOW  64
+#define BDG_TRIM_TSO_SEQ     "CCCATGTACTCTGCGTTGATACCACTGCTT"   /* barcode_callers.py:156 */
+#define BDG_TRIM_TSO_MIN_SCORE_DEFAULT 20   /* tso_min_score: 8 .. 30 */
+#define BDG_TRIM_EMIT 1u      /* the read is eligible and its cDNA is not empty */
+#define BDG_TRIM_TSO  2u      /* the TSO was found: cdna_end is its cut */
+typedef struct bdg_trim_rec {
+    int32_t  cdna_start;
+    int32_t  cdna_end;
+    int16_t  tail_len;
+    int8_t   tso_score;
+    uint8_t  flags;       /* BDG_TRIM_* */
+} bdg_trim_rec;           /* 12 bytes */
+/* Device-resident: the bases, offsets and records of the bdg_extract_batch_dev call just made (same stream: the trim runs
+ * behind it); d_out [n].  Asynchronous.  BDG_E_ARG for tso_min_score outside 8 .. 30. */
+int  bdg_trim_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
+                        const bdg_extract_rec* d_recs, uint32_t tso_min_score, bdg_trim_rec* d_out);
+/* Host buffers: reads as for bdg_extract_batch, their records; copies in, runs, copies out. */
+int  bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
+                    const bdg_extract_rec* recs, uint32_t tso_min_score, bdg_trim_rec* out);
+/* The pipelined path: while on, bdg_extract_submit queues the trim of a chunk behind its extraction on the same stream, and
+ * bdg_extract_collect_trim(slot) - after bdg_extract_collect of that slot - hands over the chunk's n results.  A chunk that
+ * collect had to run again (queue overflow) has been trimmed again behind the rerun: the placeholder records of the failed
+ * pass give flags = 0 and are never seen.  Holds for the submits that follow. */
+int  bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score);
+int  bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out);
+
 /* ---- read ingest and row output (host side) --------------------------------------------- */
 /* [gzipped / BGZF] FASTA / FASTQ / SAM and BAM -> chunks of at most chunk_reads reads {concatenated bases, offsets, ids}
  * in pinned host memory (pinned = 0: pageable, for hosts without a GPU), in file order.  Replaces the reference's record
@@ -278,6 +319,17 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
                             const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
                             uint32_t k, const uint32_t* cand_idx, const uint8_t* cand_ed,
                             char* out, uint64_t cap, uint64_t counts[5]);
+/* The trimmed reads of a chunk as FASTA text: one record per read with BDG_TRIM_EMIT, in chunk order,
+ *   ">" read id "\tCR:Z:" barcode "\tUR:Z:" UMI "\tST:A:" + or - ["\tCB:Z:" whitelist_barcode] "\n" sequence "\n"
+ * barcode and UMI are the strings bdg_format_rows prints for the read; ST is '-' for a BDG_FLAG_REV record; CB is there only
+ * with whitelist arrays (best_idx / n_ties / wl / nw as for bdg_format_rows_wl, best_ed implied: best_idx < nw), and only where
+ * that row's whitelist_barcode is not '*'.  The sequence is the cDNA in mRNA sense on one line, revcomp(s[cdna_start:cdna_end]):
+ * for a BDG_FLAG_REV record the read's own bytes [L - cdna_end, L - cdna_start), for a forward one the reverse complement of
+ * read[cdna_start:cdna_end].  Sizing as bdg_format_rows.  counts (may be NULL): records written, of those with BDG_TRIM_TSO,
+ * bases written. */
+int64_t bdg_format_trimmed(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                           const uint32_t* best_idx, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
+                           char* out, uint64_t cap, uint64_t counts[3]);
 
 /* Stage 1 from file to file in native threads: readers -> GPU(s) -> row formatters -> one writer, rows in input order
  * (extract_raw_barcodes.py:162-173 process_single_thread, :176-261 process_in_parallel).  Chunk k goes to context k mod
@@ -293,6 +345,12 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
  * gets "#read_id\tcorrected_barcode\tcorrected_dist\tsupport\tposterior\tstatus" and one row per read in input order (one
  * header, whatever header_every says).  The main TSV and its columns are the same bytes as without the bit. */
 #define BDG_STAGE1_WL_CORRECT    0x200u
+/* bdg_stage1_opts.whitelist, with or without a whitelist (the low bits may be 0): the trimmed cDNA of every read goes to
+ * trimmed_path as FASTA (bdg_format_trimmed; CB with a whitelist), in input order, one file without headers whatever
+ * header_every says.  Only with this bit does the library read trimmed_path and tso_min_score or write the three
+ * bdg_stage1_result.trimmed_* counts; the caller's structs then reach to those fields.  The main TSV and every other output are
+ * the same bytes as without the bit. */
+#define BDG_STAGE1_TRIM          0x400u
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -315,6 +373,10 @@ typedef struct bdg_stage1_opts {
     uint32_t bc_edit_bits;        /* B of bdg_nearest16_correct, 1 .. 8 */
     uint32_t bc_min_permille;     /* P of bdg_nearest16_correct, 501 .. 1000 */
     const char* corrected_path;   /* the per-read correction file */
+    /* read only with BDG_STAGE1_TRIM */
+    const char* trimmed_path;     /* the FASTA file of trimmed reads */
+    uint32_t tso_min_score;       /* 8 .. 30 (BDG_TRIM_TSO_MIN_SCORE_DEFAULT) */
+    uint32_t reserved_trim;
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -328,7 +390,8 @@ typedef struct bdg_stage1_result {
     double   seconds_wait_format;             /* ... waiting for the formatters / the writer to take a chunk */
     double   seconds_format, seconds_write;   /* busy time of the formatter threads (summed) / of the writer */
     uint64_t whitelist_barcodes;              /* opts->whitelist: rows with a whitelist_barcode (counts[4] of bdg_format_rows_wl) */
-    uint64_t whitelist_corrected;             /* written only with BDG_STAGE1_WL_CORRECT: rows of status exact or corrected */
+    uint64_t whitelist_corrected;             /* written only with BDG_STAGE1_WL_CORRECT (or BDG_STAGE1_TRIM, then 0 without the correction): rows of status exact or corrected */
+    uint64_t trimmed_reads, trimmed_tso, trimmed_bases;   /* written only with BDG_STAGE1_TRIM: counts[3] of bdg_format_trimmed over the run */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);

@@ -1,0 +1,351 @@
+"""Trimmed reads without a GPU: the rule of badger_amd/trim.py (its alignment against the oracle's, hand-derived tails, exact
+recovery of both cuts on error-free reads, the batch form against the one-read form), the native FASTA formatter
+bdg_format_trimmed against a Python-built expectation, and the command line's argument checks."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from badger_amd import _native, common, extract_raw_barcodes as erb, synth, trim
+from oracle import pyoracle as orc
+
+TSO = trim.TSO
+R1 = synth.R1
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    import __graft_entry__
+    __graft_entry__.build()
+
+
+def _rand_seq(rng, n, alphabet="ACGT"):
+    return "".join(alphabet[c] for c in rng.integers(0, len(alphabet), size=n))
+
+
+def _mutate(rng, s, p=0.1):
+    out = []
+    for c in s:
+        u = rng.random()
+        if u < p / 3:
+            continue
+        if u < 2 * p / 3:
+            out.append("ACGT"[rng.integers(0, 4)])
+            continue
+        if u < p:
+            out.append("ACGT"[rng.integers(0, 4)])
+        out.append(c)
+    return "".join(out)
+
+
+# ---- 1. the alignment -------------------------------------------------------------------------------------------------
+def _windows(n, seed):
+    """windows of 0 .. 64 bases: no TSO, an exact one, a mutated one, a truncated one (head or tail missing), some with N"""
+    rng = np.random.default_rng(seed)
+    out = ["", "A", TSO, TSO[:10], "N" * 64, TSO + TSO, ("ACGT" * 16)]
+    while len(out) < n:
+        kind = int(rng.integers(0, 5))
+        L = int(rng.integers(0, 65))
+        if kind == 0:
+            w = _rand_seq(rng, L)
+        else:
+            t = TSO if kind == 1 else _mutate(rng, TSO, 0.15) if kind == 2 else TSO[:int(rng.integers(4, 30))] if kind == 3 \
+                else TSO[int(rng.integers(1, 26)):]
+            pre = _rand_seq(rng, int(rng.integers(0, max(1, 65 - len(t)))))
+            w = (pre + t + _rand_seq(rng, 64))[:max(L, 1)] if kind != 3 else (pre + t)[:64]
+        if rng.random() < 0.25 and w:
+            w = list(w)
+            for _ in range(int(rng.integers(1, 4))):
+                w[int(rng.integers(0, len(w)))] = "N"
+            w = "".join(w)
+        out.append(w)
+    return out
+
+
+def test_own_alignment_equals_the_oracles():
+    """all five outputs, over 3,000 seeded windows (the oracle's scan holds 64 rows and any number of columns: no limit
+    below 30 x 64)"""
+    seen_scores = set()
+    for w in _windows(3000, 17):
+        assert len(w) <= 64
+        got, want = trim.sw_align(TSO, w), orc.sw_align(TSO, w)
+        assert tuple(got) == tuple(want), (w, got, want)
+        seen_scores.add(got[4])
+    assert {0, 30} <= seen_scores and len(seen_scores) > 20
+
+
+def test_own_alignment_other_patterns():
+    rng = np.random.default_rng(3)
+    for _ in range(300):
+        pat = _rand_seq(rng, int(rng.integers(1, 31)), "ACGTN")
+        ref = _rand_seq(rng, int(rng.integers(0, 65)), "ACGTN")
+        assert tuple(trim.sw_align(pat, ref)) == tuple(orc.sw_align(pat, ref)), (pat, ref)
+
+
+# ---- 2. the tail ------------------------------------------------------------------------------------------------------
+def test_tail_known_answers():
+    pre = "GATCGATCGA"                                   # 10 bases in front of the tail, p = 10
+    p = len(pre)
+    # a clean T30 followed by ACGAC...: the tail ends behind its 30th T
+    assert trim.tail_end(pre + "T" * 30 + "ACGACGGATCAGCA", p) == p + 30
+    # one substitution inside (T12 C T17): +12, -2, +17: the maximum is at the end of the run
+    assert trim.tail_end(pre + "T" * 12 + "C" + "T" * 17 + "ACGACGGATCAGCA", p) == p + 30
+    # one insertion (31 columns), one deletion (29 columns)
+    assert trim.tail_end(pre + "T" * 20 + "G" + "T" * 10 + "ACGACGGATCAGCA", p) == p + 31
+    assert trim.tail_end(pre + "T" * 29 + "ACGACGGATCAGCA", p) == p + 29
+    # a tail running to the read's end; p at L - 1 on a T and on a non-T
+    assert trim.tail_end(pre + "T" * 25, p) == p + 25
+    assert trim.tail_end(pre + "T", p) == p + 1
+    assert trim.tail_end(pre + "G", p) == p
+    # a tail that starts on a non-T (find('TTT') failed and polyT is the window's start): -2, then +30 -> 28 > 0
+    assert trim.tail_end(pre + "G" + "T" * 30 + "ACGACGGATC", p) == p + 31
+    # ... and one that never recovers: G A C A (-8) T (-7) C (-9) A (-11, 10 or more below the maximum 0): an empty tail
+    assert trim.tail_end(pre + "GACATCAGGT", p) == p
+    # cDNA starting ATTTTTTT behind T30: 30, 28, then seven T -> 35 > 30: the rule extends over the A, to the end of the T run
+    assert trim.tail_end(pre + "T" * 30 + "ATTTTTTT" + "GACGACGACGACG", p) == p + 38
+    # ... but ATTG does not (30, 28, 29, 30: no strict maximum above 30)
+    assert trim.tail_end(pre + "T" * 30 + "ATTG" + "GACGACGACGACG", p) == p + 30
+    # five non-T in a row always end the tail, whatever follows
+    assert trim.tail_end(pre + "T" * 30 + "ACGAC" + "T" * 40, p) == p + 30
+    # N is "not T"
+    assert trim.tail_end(pre + "T" * 10 + "N" + "T" * 5 + "ACGACGGATC", p) == p + 16
+    # tail_len saturates
+    s = "T" * 40000
+    assert trim.trim_strand(s, 0)[:3] == (40000, 40000, 32767)
+
+
+def test_trim_strand_fields():
+    cdna = "GACGGCATCAGCATCGACTAGCATCAGCGACTACGACGGATATCGAGCAGCGAGGATCAGCAGCACGGA"
+    s = "GATCGATCGA" + "T" * 30 + cdna + TSO
+    st, en, tl, sc, fl = trim.trim_strand(s, 10)
+    assert (st, en, tl, sc, fl) == (40, 40 + len(cdna), 30, 30, trim.TRIM_EMIT | trim.TRIM_TSO)
+    # the read ends inside the TSO: 12 bases of it score 12; accepted at 8, not at 20
+    s2 = s[:40 + len(cdna) + 12]
+    assert trim.trim_strand(s2, 10, 8) == (40, 40 + len(cdna), 30, 12, trim.TRIM_EMIT | trim.TRIM_TSO)
+    assert trim.trim_strand(s2, 10, 20) == (40, len(s2), 30, 12, trim.TRIM_EMIT)
+    # a TSO whose first bases are missing: the cut goes to where its first base would sit
+    s3 = "GATCGATCGA" + "T" * 30 + cdna + TSO[3:]
+    assert trim.trim_strand(s3, 10) == (40, 40 + len(cdna) - 3, 30, 27, trim.TRIM_EMIT | trim.TRIM_TSO)
+    # nothing behind the tail: empty window, no TSO, nothing to emit
+    assert trim.trim_strand("GATCGATCGA" + "T" * 30, 10) == (40, 40, 30, 0, 0)
+    # the TSO directly behind the tail: an empty cDNA is not emitted
+    assert trim.trim_strand("GATCGATCGA" + "T" * 30 + TSO, 10) == (40, 40, 30, 30, trim.TRIM_TSO)
+    # not eligible
+    r = np.zeros(1, dtype=_native.REC_DTYPE)[0]
+    assert trim.trim_read(s, r) == (-1, -1, 0, 0, 0)
+    r["valid"], r["polyT"] = 1, -1
+    assert trim.trim_read(s, r) == (-1, -1, 0, 0, 0)
+    r["polyT"], r["flags"] = 10, _native.FLAG_INCOMPLETE
+    assert trim.trim_read(s, r) == (-1, -1, 0, 0, 0)
+    r["flags"] = 0
+    assert trim.trim_read(s, r) == (st, en, tl, sc, fl)
+    r["flags"] = _native.FLAG_REV
+    assert trim.trim_read(trim.revcomp(s), r) == (st, en, tl, sc, fl)
+
+
+# ---- 3. error-free reads ----------------------------------------------------------------------------------------------
+def _clean_reads(n, seed, umi_len):
+    """junk + R1 + barcode + UMI + T30 + cDNA + TSO without errors; the cDNA starts with >= 5 non-T bases and shares no 8-mer
+    with the TSO; every other read reverse-complemented.  -> reads, (true cdna_start, cdna_end) in strand coordinates"""
+    rng = np.random.default_rng(seed)
+    tso8 = {TSO[i:i + 8] for i in range(len(TSO) - 7)}
+    reads, truth = [], []
+    while len(reads) < n:
+        junk = _rand_seq(rng, int(rng.integers(0, 41)))
+        cdna = _rand_seq(rng, 5, "ACG") + _rand_seq(rng, int(rng.integers(15, 600)))
+        if any(cdna[i:i + 8] in tso8 for i in range(len(cdna) - 7)):
+            continue
+        head = junk + R1 + _rand_seq(rng, 16) + _rand_seq(rng, umi_len) + "T" * 30
+        s = head + cdna + TSO
+        reads.append(trim.revcomp(s) if len(reads) & 1 else s)
+        truth.append((len(head), len(head) + len(cdna)))
+    return reads, truth
+
+
+@pytest.mark.parametrize("umi_len", [10, 12])
+def test_error_free_reads_recover_both_cuts(umi_len):
+    reads, truth = _clean_reads(400, 23 + umi_len, umi_len)
+    bases, off = synth.list_to_reads(reads)
+    recs = orc.extract_batch(bases, off, umi_len, threads=4)
+    got = trim.trim_reads(reads, recs)
+    assert ((recs["flags"] & _native.FLAG_REV) != 0).tolist() == [bool(i & 1) for i in range(len(reads))]
+    for i, (t, (a, b)) in enumerate(zip(got, truth)):
+        assert trim.eligible(recs[i]), i
+        assert (int(t["cdna_start"]), int(t["cdna_end"])) == (a, b), (i, t, a, b)
+        assert int(t["flags"]) == trim.TRIM_EMIT | trim.TRIM_TSO and int(t["tso_score"]) == 30
+        want = reads[i] if i & 1 else trim.revcomp(reads[i])       # the cDNA in mRNA sense = the slice of revcomp(strand)
+        L = len(reads[i])
+        assert trim.trimmed_sequence(reads[i], recs[i], t) == want[L - b:L - a]
+    assert (trim.trim_batch(bases, off, recs) == got).all()
+
+
+# ---- the batch form is the one-read form --------------------------------------------------------------------------------
+def _mixed_reads(n, seed, umi_len=12):
+    """reads with the project's error model and a TSO, plus hand-made edge cases"""
+    wl = synth.make_whitelist(500)
+    b, o = synth.make_reads(n, wl, seed=seed, umi_len=umi_len, tso=True, tso_tail=(seed % 3) * 4)
+    reads = synth.reads_to_list(b, o)
+    rng = np.random.default_rng(seed)
+    head = "ACGGT" + R1 + "ACGTACGTACGTACGT" + "GATTACAGATTA"[:umi_len]
+    extra = [head + "T" * 30,                                           # ends with the tail
+             head + "T" * 17,                                           # ends inside the tail
+             head + "T" * 30 + "GACGACGGCATCAGCAGCGAC" + TSO[:14],      # ends inside the TSO
+             head + "T" * 30 + "GACGACG" + TSO,                         # fewer than 64 bases behind the tail
+             head + "T" * 30 + "GACNACGGCATNNGCAGCGACGAGCGAC" + TSO[:11] + "N" + TSO[12:],
+             "T" * 300, "T" * 16, "ACGTTGCA" * 40, "N" * 80,
+             head + "T" * 30 + _rand_seq(rng, 7000) + TSO]
+    extra += [trim.revcomp(x) for x in extra]
+    for k in range(20):                                                 # cut anywhere
+        s = reads[k]
+        extra.append(s[:int(rng.integers(16, len(s)))])
+        extra.append(s[int(rng.integers(0, len(s) - 16)):])
+    return reads + extra
+
+
+@pytest.mark.parametrize("umi_len,score", [(12, 20), (10, 8), (12, 30)])
+def test_batch_form_equals_one_read_form(umi_len, score):
+    reads = _mixed_reads(700, 5 + umi_len, umi_len)
+    bases, off = synth.list_to_reads(reads)
+    recs = orc.extract_batch(bases, off, umi_len, threads=4)
+    recs[3]["valid"] = 0                                                # invalid / placeholder records among them
+    recs[4]["flags"] |= _native.FLAG_INCOMPLETE
+    one = trim.trim_reads(reads, recs, score)
+    batch = trim.trim_batch(bases, off, recs, score)
+    bad = np.nonzero(one != batch)[0]
+    assert not len(bad), (bad[:5], one[bad[:5]], batch[bad[:5]])
+    # ... and with the oracle's alignment in place of its own
+    assert (trim.trim_reads(reads[:200], recs[:200], score, align=orc.sw_align) == one[:200]).all()
+    fl = one["flags"]
+    assert ((fl & trim.TRIM_TSO) != 0).sum() > 50 and (fl == trim.TRIM_EMIT).sum() > 0 and (one["cdna_start"] == -1).sum() > 2
+
+
+# ---- 4. the formatter ---------------------------------------------------------------------------------------------------
+class _Chunk:
+    """a bdg_ingest_chunk over numpy buffers (kept alive here)"""
+
+    def __init__(self, ids, seqs):
+        self.bases = np.frombuffer(("".join(seqs)).encode() + b"\0" * 64, dtype=np.uint8).copy()
+        self.off = np.cumsum([0] + [len(s) for s in seqs]).astype(np.uint64)
+        self.ids = np.frombuffer("".join(ids).encode() + b"\0", dtype=np.uint8).copy()
+        self.id_off = np.cumsum([0] + [len(i) for i in ids]).astype(np.uint64)
+        self.ch = _native.IngestChunk(0, len(seqs), self.bases.ctypes.data, self.off.ctypes.data, int(self.off[-1]),
+                                      self.ids.ctypes.data, self.id_off.ctypes.data)
+
+
+def _expected_fasta(ids, reads, recs, tr, rows, wl_col):
+    """the file's text from the TSV's own fields (barcode, UMI, strand[, whitelist_barcode]) and trim.py's cuts"""
+    out = []
+    for i in range(len(reads)):
+        if not tr[i]["flags"] & trim.TRIM_EMIT:
+            continue
+        f = rows[i].split("\t")
+        head = ">%s\tCR:Z:%s\tUR:Z:%s\tST:A:%s" % (ids[i].split(" ")[0], f[1], f[2], f[5])
+        if wl_col is not None and wl_col[i] != "*":
+            head += "\tCB:Z:" + wl_col[i]
+        a, b = int(tr[i]["cdna_start"]), int(tr[i]["cdna_end"])
+        s = trim.revcomp(reads[i]) if recs[i]["flags"] & _native.FLAG_REV else reads[i]
+        out.append(head + "\n" + trim.revcomp(s[a:b]) + "\n")
+    return "".join(out).encode()
+
+
+def test_format_trimmed_against_python():
+    reads = _mixed_reads(300, 41)
+    n = len(reads)
+    ids = ["read_%d" % i for i in range(n)]
+    ids[7] = "read_7 runid=abc ch=12"                                   # cut to its first word
+    ids[8] = "r8 x"
+    bases, off = synth.list_to_reads(reads)
+    recs = orc.extract_batch(bases, off, 12, threads=4)
+    tr = trim.trim_batch(bases, off, recs)
+    assert (tr["flags"] & trim.TRIM_EMIT).astype(bool).sum() > 200
+    ck = _Chunk(ids, reads)
+    rows = _native.format_rows(ck.ch, recs)[0].decode().split("\n")[:-1]
+    for k in (7, 8):
+        rows[k] = rows[k].replace(ids[k], ids[k].split(" ")[0], 1)
+    # without a whitelist
+    text, counts = _native.format_trimmed(ck.ch, recs, tr)
+    want = _expected_fasta(ids, reads, recs, tr, rows, None)
+    assert text == want
+    emit = (tr["flags"] & trim.TRIM_EMIT) != 0
+    assert counts == (int(emit.sum()), int((emit & ((tr["flags"] & trim.TRIM_TSO) != 0)).sum()),
+                      int((tr["cdna_end"][emit] - tr["cdna_start"][emit]).sum()))
+    assert text.count(b">") == counts[0] and b">read_7\tCR:Z:" in text and b"runid" not in text
+    assert all(len(l) for l in text.split(b"\n")[1:-1:2])               # one non-empty sequence line per record, no wrapping
+    # with whitelist arrays: unique calls, ties, misses
+    rng = np.random.default_rng(9)
+    wl = rng.integers(0, 1 << 32, size=40, dtype=np.uint64).astype(np.uint32)
+    idx = rng.integers(0, 40, size=n).astype(np.uint32)
+    ties = rng.integers(1, 4, size=n).astype(np.uint16)
+    ed = rng.integers(0, 3, size=n).astype(np.uint8)
+    miss = rng.random(n) < 0.2
+    idx[miss], ed[miss], ties[miss] = 0xFFFFFFFF, 255, 0
+    wl_rows = _native.format_rows_wl(ck.ch, recs, idx, ed, ties, wl)[0].decode().split("\n")[:-1]
+    wl_col = [r.split("\t")[8] for r in wl_rows]
+    assert sum(c != "*" for c in wl_col) > 50 and wl_col.count("*") > 50
+    text_wl, counts_wl = _native.format_trimmed(ck.ch, recs, tr, idx, ties, wl)
+    assert text_wl == _expected_fasta(ids, reads, recs, tr, rows, wl_col) and counts_wl == counts
+    assert text_wl.count(b"\tCB:Z:") == sum(1 for i in range(n) if emit[i] and wl_col[i] != "*")
+    # trim.py's own writer says the same
+    assert trim.fasta_text(ids, reads, recs, tr, wl_barcodes=wl_col).encode() == text_wl
+
+
+def test_format_trimmed_sizing_and_errors():
+    reads = _mixed_reads(60, 43)
+    ids = ["q%d" % i for i in range(len(reads))]
+    bases, off = synth.list_to_reads(reads)
+    recs = orc.extract_batch(bases, off, 12, threads=2)
+    tr = trim.trim_batch(bases, off, recs)
+    ck = _Chunk(ids, reads)
+    L = _native.load()
+    counts = (C.c_uint64 * 3)(7, 7, 7)
+    need = L.bdg_format_trimmed(C.byref(ck.ch), recs.ctypes.data, tr.ctypes.data, None, None, None, 0, None, 0, counts)
+    text = _native.format_trimmed(ck.ch, recs, tr)[0]
+    assert need >= len(text) > 0
+    buf = C.create_string_buffer(b"\xAA" * 64, 64)
+    small = L.bdg_format_trimmed(C.byref(ck.ch), recs.ctypes.data, tr.ctypes.data, None, None, None, 0, buf, 64, counts)
+    assert small == need and buf.raw == b"\xAA" * 64 and list(counts) == [7, 7, 7]       # too small: the size, nothing written
+    assert L.bdg_format_trimmed(C.byref(ck.ch), None, tr.ctypes.data, None, None, None, 0, None, 0, None) == _native.E_ARG
+    assert L.bdg_format_trimmed(C.byref(ck.ch), recs.ctypes.data, None, None, None, None, 0, None, 0, None) == _native.E_ARG
+    # nothing to emit: an empty text
+    none = np.zeros(len(reads), dtype=_native.TRIM_DTYPE)
+    assert _native.format_trimmed(ck.ch, recs, none) == (b"", (0, 0, 0))
+
+
+# ---- 5. arguments and layouts -------------------------------------------------------------------------------------------
+def _args(*extra):
+    return ["--mode", "tenX_v3", "-i", "reads.fa", "-o", "out.tsv"] + list(extra)
+
+
+def test_tso_min_score_needs_trimmed_reads():
+    with pytest.raises(SystemExit):
+        erb.parse_args(_args("--tso_min_score", "20"))
+
+
+@pytest.mark.parametrize("bad", ["7", "31", "0", "-3", "x", "20.5"])
+def test_tso_min_score_range(bad):
+    with pytest.raises(SystemExit):
+        erb.parse_args(_args("--trimmed_reads", "t.fa", "--tso_min_score", bad))
+
+
+def test_trim_flags_parse():
+    a = erb.parse_args(_args())
+    assert a.trimmed_reads is None and erb._trim_kwargs(a) == {}
+    a = erb.parse_args(_args("--trimmed_reads", "t.fa"))
+    assert erb._trim_kwargs(a) == dict(trimmed_path="t.fa", tso_min_score=20)
+    for v in (8, 30):
+        a = erb.parse_args(_args("--trimmed_reads", "t.fa", "--tso_min_score", str(v)))
+        assert erb._trim_kwargs(a) == dict(trimmed_path="t.fa", tso_min_score=v)
+
+
+def test_layouts():
+    """the record is 12 bytes; the structs of callers that do not know the new fields keep their size, the new fields trail"""
+    assert _native.TRIM_DTYPE.itemsize == 12 and _native.TRIM_DTYPE == trim.TRIM_DTYPE
+    assert C.sizeof(_native.Stage1Opts) == 40 and C.sizeof(_native.Stage1OptsCorrect) == 56
+    assert _native.Stage1OptsTrim.trimmed_path.offset == 56 and _native.Stage1OptsTrim.tso_min_score.offset == 64
+    assert C.sizeof(_native.Stage1ResultCorrect) == C.sizeof(_native.Stage1Result) + 8
+    assert _native.Stage1ResultTrim.trimmed_reads.offset == C.sizeof(_native.Stage1ResultCorrect)
+    assert _native.STAGE1_TRIM & (_native.STAGE1_WL_CANDIDATES | _native.STAGE1_WL_CORRECT | 0xFF) == 0
+    # the constants of the header, of the binding and of the rule agree
+    hdr = open(__import__("os").path.join(__import__("os").path.dirname(_native._HERE), "include", "badger_hip.h")).read()
+    assert '"%s"' % TSO in hdr and "BDG_TRIM_TAIL_XDROP  %d" % trim.TAIL_XDROP in hdr and "BDG_TRIM_TSO_WINDOW  %d" % trim.TSO_WINDOW in hdr
+    assert TSO == synth.TSO and common is not None
