@@ -42,7 +42,7 @@ EXPORTS = [
     "bdg_nearest16_overflow_count",
     "bdg_nearest16_topk", "bdg_nearest16_topk_dev", "bdg_nearest16_topk_recs_dev", "bdg_format_rows_wlk",
     "bdg_nearest16_correct",
-    "bdg_graph_edges", "bdg_graph_edges_dev", "bdg_graph_edges_rows_dev", "bdg_graph_edges_part_dev", "bdg_graph_set_algo", "bdg_graph_status", "bdg_distinct_dev", "bdg_rows_of_dev",
+    "bdg_graph_edges", "bdg_graph_edges_dev", "bdg_graph_edges_rows_dev", "bdg_graph_edges_part_dev", "bdg_graph_set_algo", "bdg_graph_set_knob", "bdg_graph_status", "bdg_distinct_dev", "bdg_rows_of_dev",
     "bdg_extract_submit", "bdg_extract_collect", "bdg_extract_keep_records", "bdg_kept_records", "bdg_kept_records_to_host", "bdg_keep_observed", "bdg_touched_count_dev",
     "bdg_ingest_open", "bdg_ingest_open_mt", "bdg_ingest_open_ex", "bdg_ingest_next", "bdg_ingest_release", "bdg_ingest_error",
     "bdg_ingest_reads", "bdg_ingest_close", "bdg_format_rows", "bdg_format_rows_wl", "bdg_stage1_run",
@@ -199,6 +199,7 @@ def load():
     L.bdg_graph_edges_rows_dev.argtypes = [vp, vp, u32, u32, u32, u32, i32, vp, u64, vp]
     L.bdg_graph_edges_part_dev.argtypes = [vp, vp, u32, u32, u32, u32, i32, vp, u64, vp]
     L.bdg_graph_set_algo.argtypes = [vp, C.c_int]
+    L.bdg_graph_set_knob.argtypes = [vp, C.c_int, C.c_int64]
     L.bdg_graph_status.argtypes = [vp]
     L.bdg_distinct_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
     L.bdg_rows_of_dev.argtypes = [vp, vp, u32, vp, u64, u32, vp]
@@ -535,6 +536,12 @@ class Context:
 
     def graph_set_algo(self, algo):
         self._check(self.lib.bdg_graph_set_algo(self.h, algo))
+
+    GRAPH_KNOBS = {"d1_min_rows": 0, "d2_min_rows": 1, "d2_rounds": 2, "dj_l2max": 3, "d2_pairs_blocks": 4}   # BDG_GRAPH_KNOB_*
+
+    def graph_set_knob(self, name, value):
+        """for tests and measurements (bdg_graph_set_knob): one of GRAPH_KNOBS, or its number; a negative value means automatic"""
+        self._check(self.lib.bdg_graph_set_knob(self.h, self.GRAPH_KNOBS[name] if isinstance(name, str) else name, value))
 
     def graph_status(self):
         """waits for the stream; raises if a deletion-variant join of the last *_dev graph call could not group its input"""

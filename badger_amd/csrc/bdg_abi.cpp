@@ -202,8 +202,13 @@ int bdg_init(int device_id, bdg_ctx** out)
         delete ctx; g_err_noctx = "hipStreamCreate failed"; return BDG_E_HIP;
     }
     ctx->stream = ctx->own_stream;
-    if (const char* e2 = getenv("BADGER_AMD_D2_MIN_ROWS")) ctx->g_d2_min_rows = (uint32_t)strtoul(e2, nullptr, 10);      // (for measurements)
-    if (const char* e1 = getenv("BADGER_AMD_D1_MIN_ROWS")) ctx->g_d1_min_rows = (uint32_t)strtoul(e1, nullptr, 10);
+    // the graph knobs' initial values (for measurements and tests; clamped into their ranges; bdg_graph_set_knob afterwards)
+    bdg_ctx::GraphKnobs& k = ctx->g_knobs;
+    if (const char* v = getenv("BADGER_AMD_D2_MIN_ROWS")) k.d2_min_rows = (uint32_t)strtoul(v, nullptr, 10);
+    if (const char* v = getenv("BADGER_AMD_D1_MIN_ROWS")) k.d1_min_rows = (uint32_t)strtoul(v, nullptr, 10);
+    if (const char* v = getenv("BADGER_AMD_D2_ROUNDS")) k.d2_rounds = std::max(1, atoi(v));
+    if (const char* v = getenv("BADGER_AMD_DJ_L2MAX")) k.dj_l2max = std::max(0, atoi(v));
+    if (const char* v = getenv("BADGER_AMD_D2_PAIRS_BLOCKS")) k.d2_pairs_blocks = (uint32_t)std::min(8, std::max(1, atoi(v)));
     *out = ctx;
     return BDG_OK;
 }
@@ -1137,6 +1142,24 @@ int bdg_graph_set_algo(bdg_ctx* ctx, int algo)
     if (!ctx || algo < 0 || algo > 6) return BDG_E_ARG;
     ctx->graph_algo = algo;
     return BDG_OK;
+}
+
+int bdg_graph_set_knob(bdg_ctx* ctx, int knob, int64_t value)
+{
+    if (!ctx) return BDG_E_ARG;
+    bdg_ctx::GraphKnobs& k = ctx->g_knobs;
+    const bdg_ctx::GraphKnobs automatic;
+    const bool aut = value < 0;
+    bool ok = true;
+    switch (knob) {
+    case BDG_GRAPH_KNOB_D1_MIN_ROWS:     if ((ok = value <= 0xFFFFFFFFll)) k.d1_min_rows = aut ? automatic.d1_min_rows : (uint32_t)value; break;
+    case BDG_GRAPH_KNOB_D2_MIN_ROWS:     if ((ok = value <= 0xFFFFFFFFll)) k.d2_min_rows = aut ? automatic.d2_min_rows : (uint32_t)value; break;
+    case BDG_GRAPH_KNOB_D2_ROUNDS:       if ((ok = value != 0 && value <= 0x7FFFFFFFll)) k.d2_rounds = aut ? automatic.d2_rounds : value; break;
+    case BDG_GRAPH_KNOB_DJ_L2MAX:        if ((ok = value <= 0x7FFFFFFFll)) k.dj_l2max = aut ? automatic.dj_l2max : value; break;
+    case BDG_GRAPH_KNOB_D2_PAIRS_BLOCKS: if ((ok = aut || (value >= 1 && value <= 8))) k.d2_pairs_blocks = aut ? automatic.d2_pairs_blocks : (uint32_t)value; break;
+    default: return bdg_fail(ctx, BDG_E_ARG, "bdg_graph_set_knob: no such knob");
+    }
+    return ok ? BDG_OK : bdg_fail(ctx, BDG_E_ARG, "bdg_graph_set_knob: value outside the knob's range");
 }
 
 int bdg_graph_status(bdg_ctx* ctx)

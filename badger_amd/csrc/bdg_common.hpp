@@ -121,16 +121,23 @@ struct bdg_ctx {
     DevBuf n_counters;   // one 128-byte line per list segment + one for the overflow list
     DevBuf n_coop;       // uint64 partials of the cooperative kernel: one per (query, slice, wave)
 
-    // ---- graph workspace (graph_kernels.hip)
+    // ---- graph workspace (graph_sweep.hip, graph_qjoin.hip, graph_deljoin.hip)
     int graph_algo = 0;
     DevBuf g_sig;        // uint32 [n] letter-count signatures
     DevBuf g_tmp0, g_tmp1, g_cnt;
     DevBuf g_qj;         // q-gram join: sorted (six-mer, row) entries, inverse positions, bucket and slice starts
-    uint32_t g_d1_min_rows = 100000;    // thr 1: from this many rows on the one-deletion join runs instead of the neighbourhood probes (BADGER_AMD_D1_MIN_ROWS)
-    uint32_t g_d2_min_rows = 10000;     // thr 2: from this many rows on the deletion-variant join runs instead of the q-gram join (BADGER_AMD_D2_MIN_ROWS)
+    // What a test or a measurement may turn: set from the environment once, when the context is made (bdg_init), and by
+    // bdg_graph_set_knob afterwards; the launchers only read the fields.  The values here are the automatic ones.
+    struct GraphKnobs {
+        uint32_t d1_min_rows = 100000;  // thr 1: from this many rows on the one-deletion join runs instead of the neighbourhood probes (BADGER_AMD_D1_MIN_ROWS)
+        uint32_t d2_min_rows = 10000;   // thr 2: from this many rows on the deletion-variant join runs instead of the q-gram join (BADGER_AMD_D2_MIN_ROWS)
+        int64_t d2_rounds = -1;         // deletion-variant joins: rounds the input is taken in, >= 1 (BADGER_AMD_D2_ROUNDS); -1: from the row count
+        int64_t dj_l2max = -1;          // ... log2 of the sub-buckets of a coarse bucket at most - only ever lowers it (BADGER_AMD_DJ_L2MAX); -1: no limit of its own
+        uint32_t d2_pairs_blocks = 4;   // ... blocks of k_d2_pairs_w per compute unit, 1 .. 8 (BADGER_AMD_D2_PAIRS_BLOCKS)
+    } g_knobs;
     int g_cus_distinct = 0;             // compute units (bdg_distinct_dev asks by itself when no graph call has)
     uint32_t* g_dj_geom = nullptr;      // deletion-variant joins: the device-side report of the last launch (bdg_graph_status)
-    int g_cus = 0, g_qj_per_cu = 0, g_qjw_per_cu = 0, g_qjw_variant = 0;   // compute units and resident blocks per unit of the join kernels (asked once)
+    int g_cus = 0, g_qj_per_cu = 0, g_qjw_per_cu = 0;   // compute units and resident blocks per unit of the q-gram join's kernels (asked once)
 };
 
 #define BDG_HIP_TRY(ctx, expr)                                                           \

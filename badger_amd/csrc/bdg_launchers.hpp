@@ -21,9 +21,14 @@ int bdg_correct_support_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx
                                uint32_t n, uint32_t K, uint32_t* support, uint32_t* h_idx, uint8_t* h_ed, uint16_t* h_nw);
 int bdg_correct_resolve_launch(bdg_ctx* ctx, hipStream_t st, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
                                uint64_t n, const uint32_t* support, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out);
-// graph_kernels.hip
+// graph_sweep.hip: the sweep, the probes, and the dispatch over the four families
 int bdg_graph_launch(bdg_ctx*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, int32_t, bdg_edge*, uint64_t, uint64_t*, uint32_t part = 0, uint32_t nparts = 1);
 int bdg_graph_plan(const bdg_ctx*, uint32_t, uint32_t);
+// graph_qjoin.hip (closed_form: path 4) and graph_deljoin.hip (one_deletion: path 6), as bdg_graph_launch calls them
+int bdg_graph_qjoin_launch(bdg_ctx*, const uint32_t* d_ranks, uint32_t n, uint32_t row_begin, uint32_t row_end, uint32_t thr, int32_t qgram_T,
+                           bdg_edge* d_out, uint64_t cap, unsigned long long* d_n_edges, bool closed_form);
+int bdg_graph_deljoin_launch(bdg_ctx*, const uint32_t* d_ranks, uint32_t n, uint32_t row_begin, uint32_t row_end, uint32_t thr, int32_t qgram_T,
+                             bdg_edge* d_out, uint64_t cap, unsigned long long* d_n_edges, uint32_t part, uint32_t nparts, bool one_deletion);
 int bdg_graph_join_flags(bdg_ctx*, uint32_t*);
 int bdg_graph_flags_error(bdg_ctx*, uint32_t);
 // distinct_kernels.hip

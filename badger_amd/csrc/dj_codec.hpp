@@ -1,4 +1,4 @@
-// Deletion-variant joins (graph_kernels.hip): what an index entry is.
+// Deletion-variant joins (graph_deljoin.hip): what an index entry is.
 //
 // A row (a 16-mer r) meets other rows in the groups of its deletion variants: the 14-mers r without two letters (thr <= 2)
 // or the 15-mers r without one (thr <= 1).  An entry must name the variant k and the row.  Instead of the pair (k, r) -

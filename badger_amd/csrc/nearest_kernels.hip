@@ -62,7 +62,7 @@ __device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
 // Levenshtein distance of two 16-mers: D[16][16] of Myers/Hyyro's bit-vector recurrence, the pattern (bit planes P0 / P1)
 // against the text t.  The vectors stay SPREAD - row i of the pattern at bit 2i, where its 2-bit codes are - and a column's
 // equality vector is two three-input operations on the pattern's two bit planes and the text's code bits (t is a scalar
-// where it is the same in every lane); the addition carries through odd bits that pv keeps set (graph_kernels.hip, dmin3:
+// where it is the same in every lane); the addition carries through odd bits that pv keeps set (graph_device.hpp, dmin3:
 // the same statements).
 // A macro, not a function: a __forceinline__ helper is optimised on its own before it is inlined, and the kernels then
 // need more registers (this statement moved into a function took k_nearest_coop from 74 to 91 VGPRs, k_nearest_scan from 33

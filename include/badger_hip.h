@@ -492,6 +492,19 @@ int  bdg_graph_edges_rows_dev(bdg_ctx* ctx, const uint32_t* d_ranks, uint32_t n,
  * in n where the q-gram join's is quadratic; any n - a large input is taken in rounds over shares of the 14-mers; a single
  * round never waits for the host), 6 the same over the 15-mers left by one deletion (thr <= 1).  All give identical edge lists. */
 int  bdg_graph_set_algo(bdg_ctx* ctx, int algo);
+/* FOR TESTS AND MEASUREMENTS ONLY: turns one of the context's graph knobs.  A context takes their first values from the
+ * environment when it is made (the variable beside each name) and never reads the environment again; a negative value puts
+ * the knob back to automatic (the built-in value).  No knob changes an edge list.  BDG_E_ARG for an unknown knob or a value
+ * outside the knob's range; the context stays usable. */
+enum {
+    BDG_GRAPH_KNOB_D1_MIN_ROWS = 0,      /* thr 1: rows from which the one-deletion join replaces the probes; automatic 100,000 (BADGER_AMD_D1_MIN_ROWS) */
+    BDG_GRAPH_KNOB_D2_MIN_ROWS = 1,      /* thr 2: rows from which the deletion-variant join replaces the q-gram join; automatic 10,000 (BADGER_AMD_D2_MIN_ROWS) */
+    BDG_GRAPH_KNOB_D2_ROUNDS = 2,        /* deletion-variant joins: rounds the input is taken in, >= 1; automatic: from the row count (BADGER_AMD_D2_ROUNDS) */
+    BDG_GRAPH_KNOB_DJ_L2MAX = 3,         /* ... log2 of the second bucket level at most, >= 0, only ever lowers it; 0 leaves every bucket to the
+                                          * block kernel; automatic: no limit of its own (BADGER_AMD_DJ_L2MAX) */
+    BDG_GRAPH_KNOB_D2_PAIRS_BLOCKS = 4   /* ... resident blocks of the wave consumer per compute unit, 1 .. 8; automatic 4 (BADGER_AMD_D2_PAIRS_BLOCKS) */
+};
+int  bdg_graph_set_knob(bdg_ctx* ctx, int knob, int64_t value);
 /* What the device-resident graph calls cannot return because they do not wait: waits for the context's stream, then
  * BDG_OK, or BDG_E_CAPACITY when a deletion-variant join of the last call met an input it could not group (more index
  * entries in one round than 32 bits address - only possible beyond 35 M rows; a bucket of variants beyond every split).

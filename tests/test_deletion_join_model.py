@@ -1,4 +1,4 @@
-"""The arithmetic of the deletion-variant joins (csrc/graph_kernels.hip: d2_key, d2_subseq, the run rule of the index
+"""The arithmetic of the deletion-variant joins (csrc/graph_deljoin.hip: d2_key, d2_subseq, the run rule of the index
 passes, d2_reports / d1_reports) restated in Python and checked on the CPU: every pair with dmin <= thr shares a group,
 and the reporting rule - three closed-form relations that between them cover every way to dmin <= 2 - names exactly one
 of the groups a pair shares, so the model's edge list is the oracle's, no edge missing and none twice; a second test throws
@@ -276,7 +276,7 @@ def test_counting_pass_places_are_exact():
 
 
 def test_spread_form_of_the_verifying_myers_pass():
-    """dmin3 (graph_kernels.hip) keeps its bit vectors spread over the even bits and lets the addition carry through odd bits
+    """dmin3 (graph_device.hpp) keeps its bit vectors spread over the even bits and lets the addition carry through odd bits
     that pv keeps set; tools/myers_spread_check.py restates exactly those statements on the host and compares 20,000 pairs with
     the edit-distance recurrence."""
     import os

@@ -120,7 +120,7 @@ def test_pair_balanced_blocks_balance_the_joins_work():
 
 def test_hashed_group_shares_balance_the_deletion_variant_join():
     """thr 2 on several GPUs: bdg_graph_edges_part_dev gives a rank the 14-mer groups whose multiplicative hash falls into
-    its part (graph_kernels.hip d2_part).  Restated here on bench.py's barcodes: index entries and meeting pairs per part
+    its part (graph_deljoin.hip d2_part).  Restated here on bench.py's barcodes: index entries and meeting pairs per part
     stay within 3 % of an even share for 2, 4 and 8 parts."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

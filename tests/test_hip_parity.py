@@ -496,39 +496,56 @@ def test_graph_vs_oracle(ctx, orc, algo, thr):
     ctx.graph_set_algo(0)
 
 
+class _GraphOnDevice:
+    """The sorted ranks on the device with room for cap edges.  run(call) makes one device-resident graph call -
+    call(d_ranks, n, d_out, cap, d_cnt) - waits for it and returns its edges as rows (a, b, dist); union_is compares
+    the calls' lists, taken together and sorted, with the oracle's three columns."""
+
+    def __init__(self, ctx, ranks, cap):
+        import torch
+        self.ctx, self.n, self.cap = ctx, len(ranks), cap
+        self.d_ranks = torch.from_numpy(ranks.view(np.int32)).cuda()
+        self.d_out = torch.zeros((cap, 3), dtype=torch.int32, device="cuda")
+        self.d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+    def run(self, call, fits=False):
+        call(self.d_ranks, self.n, self.d_out, self.cap, self.d_cnt)
+        self.ctx.synchronize()
+        k = int(self.d_cnt[0])
+        if fits:
+            assert k <= self.cap
+        return self.d_out[:k].cpu().numpy().view(np.uint32).copy()
+
+    @staticmethod
+    def union_is(got, want, more_than=-1):
+        e = np.concatenate(got)
+        e = e[np.lexsort((e[:, 1], e[:, 0]))]
+        return len(e) == len(want) and len(e) > more_than and \
+            (e[:, 0] == want["a"]).all() and (e[:, 1] == want["b"]).all() and (e[:, 2] == want["dist"]).all()
+
+
 @pytest.mark.parametrize("algo,thr", [(2, 1), (1, 1), (1, 2), (3, 2), (4, 2), (5, 2)])
 def test_graph_row_blocks_partition_the_edges(ctx, orc, algo, thr):
     """a GPU owns a block of rows of the sorted rank array and emits the edges whose smaller rank lies in
     it; the blocks of any partition give disjoint lists whose union is the full list (blocks cut inside 256-row tiles,
     empty blocks and one-row blocks included)."""
-    import torch
     from badger_amd import dist as bdist
     ranks = _observed_barcodes(300, 9000, 33)
     n = len(ranks)
     T = orc.qgram_threshold(thr)
     want = orc.graph_edges(ranks, thr, T, threads=8)
     want = want[np.lexsort((want["b"], want["a"]))]
-    d_ranks = torch.from_numpy(ranks.view(np.int32)).cuda()
-    cap = 4 * n + 1024
-    d_out = torch.zeros((cap, 3), dtype=torch.int32, device="cuda")
-    d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    dev = _GraphOnDevice(ctx, ranks, 4 * n + 1024)
     ctx.graph_set_algo(algo)
     cuts = [(0, 0), (0, 1), (1, 300), (300, 1000), (1000, 1000), (1000, n)]
     for blocks in (cuts, bdist.graph_row_blocks(n, 3, "pairs"), bdist.graph_row_blocks(n, 8, "rows")):
         got = []
         for lo, hi in blocks:
-            ctx.graph_edges_rows_dev(d_ranks, n, lo, hi, thr, T, d_out, cap, d_cnt)
-            ctx.synchronize()
-            k = int(d_cnt[0])
-            assert k <= cap
-            e = d_out[:k].cpu().numpy().view(np.uint32)
-            if k:
+            e = dev.run(lambda d_ranks, n, d_out, cap, d_cnt: ctx.graph_edges_rows_dev(d_ranks, n, lo, hi, thr, T, d_out, cap, d_cnt), fits=True)
+            if len(e):
                 assert (e[:, 0] >= ranks[lo]).all() and (e[:, 0] <= ranks[hi - 1]).all() and (e[:, 0] < e[:, 1]).all()
             got.append(e)
-        e = np.concatenate(got)
-        e = e[np.lexsort((e[:, 1], e[:, 0]))]
-        assert len(e) == len(want) and len(e) > 100
-        assert (e[:, 0] == want["a"]).all() and (e[:, 1] == want["b"]).all() and (e[:, 2] == want["dist"]).all()
+        assert dev.union_is(got, want, more_than=100)
     ctx.graph_set_algo(0)
 
 
@@ -537,61 +554,49 @@ def test_graph_parts_partition_the_edges(ctx, orc, algo, thr):
     """bdg_graph_edges_part_dev: the nparts shares of any cut are disjoint and their union is the oracle's list, whichever
     path serves the threshold (row blocks for the probes / the q-gram join / the sweep, shares of the 14-mer groups for the
     deletion-variant join); a part index outside the cut is an error."""
-    import torch
     ranks = _observed_barcodes(300, 9000, 35)
     n = len(ranks)
     T = orc.qgram_threshold(thr)
     want = orc.graph_edges(ranks, thr, T, threads=8)
     want = want[np.lexsort((want["b"], want["a"]))]
-    d_ranks = torch.from_numpy(ranks.view(np.int32)).cuda()
-    cap = 4 * n + 1024
-    d_out = torch.zeros((cap, 3), dtype=torch.int32, device="cuda")
-    d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    dev = _GraphOnDevice(ctx, ranks, 4 * n + 1024)
     ctx.graph_set_algo(algo)
     for nparts in (1, 3, 8):
-        got = []
-        for part in range(nparts):
-            ctx.graph_edges_part_dev(d_ranks, n, part, nparts, thr, T, d_out, cap, d_cnt)
-            ctx.synchronize()
-            k = int(d_cnt[0])
-            assert k <= cap
-            got.append(d_out[:k].cpu().numpy().view(np.uint32).copy())
+        got = [dev.run(lambda d_ranks, n, d_out, cap, d_cnt: ctx.graph_edges_part_dev(d_ranks, n, part, nparts, thr, T, d_out, cap, d_cnt), fits=True)
+               for part in range(nparts)]
         assert nparts == 1 or min(len(g) for g in got) > 0
-        e = np.concatenate(got)
-        e = e[np.lexsort((e[:, 1], e[:, 0]))]
-        assert len(e) == len(want) and len(e) > 100
-        assert (e[:, 0] == want["a"]).all() and (e[:, 1] == want["b"]).all() and (e[:, 2] == want["dist"]).all()
+        assert dev.union_is(got, want, more_than=100)
     with pytest.raises(_native.BadgerHipError):
-        ctx.graph_edges_part_dev(d_ranks, n, 3, 3, thr, T, d_out, cap, d_cnt)
+        ctx.graph_edges_part_dev(dev.d_ranks, n, 3, 3, thr, T, dev.d_out, dev.cap, dev.d_cnt)
     ctx.graph_set_algo(0)
 
 
-def test_graph_deletion_variant_join_in_rounds(ctx, orc, monkeypatch):
+def _parts_union_is(ctx, dev, nparts, thr, T, want, status=False):
+    """the union of the nparts shares of bdg_graph_edges_part_dev (status: bdg_graph_status asked after each) against want"""
+    got = []
+    for part in range(nparts):
+        got.append(dev.run(lambda d_ranks, n, d_out, cap, d_cnt: ctx.graph_edges_part_dev(d_ranks, n, part, nparts, thr, T, d_out, cap, d_cnt)))
+        if status:
+            ctx.graph_status()
+    return dev.union_is(got, want)
+
+
+def test_graph_deletion_variant_join_in_rounds(ctx, orc):
     """a large input is taken in several rounds over shares of the 14-mer groups (the cut that gives GPUs their parts):
     forced here on small inputs - 1, 3 and 7 rounds, alone and inside 2 parts - the list stays the oracle's"""
-    import torch
     for ranks in (_observed_barcodes(300, 9000, 37), _low_complexity_barcodes(4000, 44)):
-        n = len(ranks)
         T = orc.qgram_threshold(2)
         want = orc.graph_edges(ranks, 2, T, threads=8)
-        d_ranks = torch.from_numpy(ranks.view(np.int32)).cuda()
-        cap = len(want) + 1024
-        d_out = torch.zeros((cap, 3), dtype=torch.int32, device="cuda")
-        d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+        dev = _GraphOnDevice(ctx, ranks, len(want) + 1024)
         ctx.graph_set_algo(5)
-        for rounds in ("1", "3", "7"):
-            monkeypatch.setenv("BADGER_AMD_D2_ROUNDS", rounds)
-            for nparts in (1, 2):
-                got = []
-                for part in range(nparts):
-                    ctx.graph_edges_part_dev(d_ranks, n, part, nparts, 2, T, d_out, cap, d_cnt)
-                    ctx.synchronize()
-                    got.append(d_out[:int(d_cnt[0])].cpu().numpy().view(np.uint32).copy())
-                e = np.concatenate(got)
-                e = e[np.lexsort((e[:, 1], e[:, 0]))]
-                assert len(e) == len(want) and (e[:, 0] == want["a"]).all() and (e[:, 1] == want["b"]).all() and (e[:, 2] == want["dist"]).all(), (rounds, nparts)
-        monkeypatch.delenv("BADGER_AMD_D2_ROUNDS")
-        ctx.graph_set_algo(0)
+        try:
+            for rounds in ("1", "3", "7"):
+                ctx.graph_set_knob("d2_rounds", int(rounds))
+                for nparts in (1, 2):
+                    assert _parts_union_is(ctx, dev, nparts, 2, T, want), (rounds, nparts)
+        finally:
+            ctx.graph_set_knob("d2_rounds", -1)
+            ctx.graph_set_algo(0)
 
 
 def _low_complexity_barcodes(n, seed):
@@ -916,31 +921,61 @@ def test_rows_of_dev_and_device_arrays(ctx):
 
 
 @pytest.mark.parametrize("thr", [1, 2])
-def test_deletion_variant_join_with_oversize_buckets(ctx, orc, monkeypatch, thr):
-    """The joins' cold paths, forced: without the second bucket level (BADGER_AMD_DJ_L2MAX=0) a fine bucket is a whole coarse
+def test_deletion_variant_join_with_oversize_buckets(ctx, orc, thr):
+    """The joins' cold paths, forced: without the second bucket level (the knob dj_l2max = 0) a fine bucket is a whole coarse
     one - thousands of entries - so every bucket is beyond a wave's 256 entries and goes to the block kernel through the
     overflow list, and the larger ones beyond the block's 2048 are taken in shares of the low key bits.  Same edge lists as
     the oracle's, alone and in parts."""
-    import torch
     for ranks in (_observed_barcodes(300, 16000, 41), _low_complexity_barcodes(6000, 46)):
-        n = len(ranks)
         T = orc.qgram_threshold(thr)
         want = orc.graph_edges(ranks, thr, T, threads=8)
-        d_ranks = torch.from_numpy(ranks.view(np.int32)).cuda()
-        cap = len(want) + 1024
-        d_out = torch.zeros((cap, 3), dtype=torch.int32, device="cuda")
-        d_cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+        dev = _GraphOnDevice(ctx, ranks, len(want) + 1024)
         ctx.graph_set_algo(5 if thr == 2 else 6)
-        monkeypatch.setenv("BADGER_AMD_DJ_L2MAX", "0")
-        for nparts in (1, 3):
-            got = []
-            for part in range(nparts):
-                ctx.graph_edges_part_dev(d_ranks, n, part, nparts, thr, T, d_out, cap, d_cnt)
-                ctx.synchronize()
-                ctx.graph_status()
-                got.append(d_out[:int(d_cnt[0])].cpu().numpy().view(np.uint32).copy())
-            e = np.concatenate(got)
-            e = e[np.lexsort((e[:, 1], e[:, 0]))]
-            assert len(e) == len(want) and (e[:, 0] == want["a"]).all() and (e[:, 1] == want["b"]).all() and (e[:, 2] == want["dist"]).all(), nparts
-        monkeypatch.delenv("BADGER_AMD_DJ_L2MAX")
+        try:
+            ctx.graph_set_knob("dj_l2max", 0)
+            for nparts in (1, 3):
+                assert _parts_union_is(ctx, dev, nparts, thr, T, want, status=True), nparts
+        finally:
+            ctx.graph_set_knob("dj_l2max", -1)
+            ctx.graph_set_algo(0)
+
+
+def test_graph_set_knob_rejects_what_is_out_of_range(ctx):
+    """an unknown knob, 0 rounds, 9 pairs blocks: errors that leave the context as it was"""
+    for knob, value in ((99, 1), ("d2_rounds", 0), ("d2_pairs_blocks", 9)):
+        with pytest.raises(_native.BadgerHipError):
+            ctx.graph_set_knob(knob, value)
+    e = ctx.graph_edges(np.array([0, 1], np.uint32), 1, 5)
+    assert len(e) == 1 and tuple(e[0]) == (0, 1, 1)
+
+
+def test_graph_knobs_belong_to_their_context(ctx, orc):
+    """Two contexts differ in their knobs: while the first holds 7 rounds and no second bucket level, a second context's
+    deletion-variant join (algo 5, thr 2) gives the oracle's list with the automatic values, and so does the first under its
+    own; back at automatic the first reports and lists what a fresh context does."""
+    ranks = _observed_barcodes(300, 9000, 39)
+    T = orc.qgram_threshold(2)
+    want = orc.graph_edges(ranks, 2, T, threads=8)
+    assert len(want) > 100
+    other = _native.Context(0)
+    try:
+        ctx.graph_set_algo(5)
+        ctx.graph_set_knob("d2_rounds", 7)
+        ctx.graph_set_knob("dj_l2max", 0)
+        other.graph_set_algo(5)
+        fresh = other.graph_edges(ranks, 2, T)
+        assert len(fresh) == len(want) and (fresh == want).all()
+        turned = ctx.graph_edges(ranks, 2, T)
+        assert len(turned) == len(want) and (turned == want).all()
+        ctx.graph_set_knob("d2_rounds", -1)
+        ctx.graph_set_knob("dj_l2max", -1)
+        dev = _GraphOnDevice(ctx, ranks, len(want) + 1024)
+        back = dev.run(lambda d_ranks, n, d_out, cap, d_cnt: ctx.graph_edges_dev(d_ranks, n, 2, T, d_out, cap, d_cnt))
+        ctx.graph_status()
+        other.graph_status()
+        assert dev.union_is([back], want) and dev.union_is([back], fresh)
+    finally:
+        ctx.graph_set_knob("d2_rounds", -1)
+        ctx.graph_set_knob("dj_l2max", -1)
         ctx.graph_set_algo(0)
+        other.close()

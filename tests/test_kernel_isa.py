@@ -74,7 +74,7 @@ def test_deletion_variant_join_kernels_budget(tmp_path):
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
     out = str(tmp_path / "graph.s")
-    src = os.path.join(ROOT, "badger_amd", "csrc", "graph_kernels.hip")
+    src = os.path.join(ROOT, "badger_amd", "csrc", "graph_deljoin.hip")
     subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-Wno-unused-function",
                     "-Wno-inline-asm", "-Wno-unused-command-line-argument", "-I", os.path.join(ROOT, "include"), "-o", out, src],
                    check=True, timeout=900)

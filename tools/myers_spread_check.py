@@ -1,4 +1,4 @@
-"""Host model of dmin3 (graph_kernels.hip) in its spread form - row i at bit 2i, pv with every odd bit set so that the
+"""Host model of dmin3 (graph_device.hpp) in its spread form - row i at bit 2i, pv with every odd bit set so that the
 addition carries through - against the edit-distance recurrence: min(ed(a, b), ed(a, b[:-1]), ed(a[:-1], b)) on 20,000 pairs
 (equal, random, and a few edits apart).  python3 tools/myers_spread_check.py"""
 import random
