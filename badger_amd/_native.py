@@ -22,6 +22,10 @@ EDGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4")])
 TRIM_DTYPE = np.dtype([("cdna_start", "<i4"), ("cdna_end", "<i4"), ("tail_len", "<i2"), ("tso_score", "i1"), ("flags", "u1")])
 TRIM_EMIT, TRIM_TSO = 1, 2
 TSO_MIN_SCORE_DEFAULT = 20
+# bdg_chimera_rec: an internal adapter inside a read's cDNA (bdg_chimera_batch; the rule in badger_amd/chimera.py)
+CHIMERA_DTYPE = np.dtype([("cut", "<i4"), ("hit_pos", "<i4"), ("hit_ed", "u1"), ("hit_kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
+CHIMERA_HIT = 1
+CHIMERA_MAX_ED_DEFAULT, CHIMERA_MAX_ED_MAX = 3, 6
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -51,6 +55,7 @@ EXPORTS = [
     "bdg_extract_keep_umis", "bdg_keep_observed_umis", "bdg_kept_umis", "bdg_umi_dedup_dev", "bdg_import_stage1_tsv_umi",
     "bdg_write_molecules",
     "bdg_trim_batch", "bdg_trim_batch_dev", "bdg_extract_set_trim", "bdg_extract_collect_trim", "bdg_format_trimmed",
+    "bdg_chimera_batch", "bdg_chimera_batch_dev", "bdg_extract_set_chimera", "bdg_extract_collect_chimera", "bdg_format_trimmed_chimera",
 ]
 
 
@@ -72,6 +77,7 @@ class IngestOpts(C.Structure):
 
 STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates is set (BDG_STAGE1_WL_CANDIDATES)
 STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist correction, the trailing fields are set (BDG_STAGE1_WL_CORRECT)
+STAGE1_CHIMERA = 0x800              # bdg_stage1_opts.whitelist: with STAGE1_TRIM, chimeric reads are cut; chimera_max_ed is set (BDG_STAGE1_CHIMERA)
 STAGE1_TRIM = 0x400                 # bdg_stage1_opts.whitelist: trimmed reads, the fields behind the correction's are set (BDG_STAGE1_TRIM)
 # status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
 WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
@@ -95,6 +101,11 @@ class Stage1OptsTrim(Stage1OptsCorrect):
     _fields_ = [("trimmed_path", C.c_char_p), ("tso_min_score", C.c_uint32), ("reserved_trim", C.c_uint32)]
 
 
+class Stage1OptsChimera(Stage1OptsTrim):
+    """bdg_stage1_opts with the fields read only with STAGE1_CHIMERA"""
+    _fields_ = [("chimera_max_ed", C.c_uint32), ("reserved_chimera", C.c_uint32)]
+
+
 class Stage1Result(C.Structure):
     """bdg_stage1_result"""
     _fields_ = [("reads", C.c_uint64), ("barcodes", C.c_uint64), ("polyt", C.c_uint64), ("r1", C.c_uint64),
@@ -113,6 +124,11 @@ class Stage1ResultCorrect(Stage1Result):
 class Stage1ResultTrim(Stage1ResultCorrect):
     """bdg_stage1_result with the counts written only with STAGE1_TRIM"""
     _fields_ = [("trimmed_reads", C.c_uint64), ("trimmed_tso", C.c_uint64), ("trimmed_bases", C.c_uint64)]
+
+
+class Stage1ResultChimera(Stage1ResultTrim):
+    """bdg_stage1_result with the counts written only with STAGE1_CHIMERA"""
+    _fields_ = [("chimera_cut", C.c_uint64), ("chimera_dropped", C.c_uint64), ("chimera_bases", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -242,6 +258,12 @@ def load():
     L.bdg_extract_collect_trim.argtypes = [vp, u32, vp]
     L.bdg_format_trimmed.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.bdg_format_trimmed.restype = C.c_int64
+    L.bdg_chimera_batch.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp]
+    L.bdg_chimera_batch_dev.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp]
+    L.bdg_extract_set_chimera.argtypes = [vp, C.c_int, u32]
+    L.bdg_extract_collect_chimera.argtypes = [vp, u32, vp]
+    L.bdg_format_trimmed_chimera.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
+    L.bdg_format_trimmed_chimera.restype = C.c_int64
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -367,6 +389,35 @@ class Context:
         """the trim results of the chunk just collected from `slot` (after extract_collect)"""
         out = np.zeros(n, dtype=TRIM_DTYPE)
         self._check(self.lib.bdg_extract_collect_trim(self.h, slot, out.ctypes.data))
+        return out
+
+    def chimera_batch(self, bases, off, recs, trim, max_ed=CHIMERA_MAX_ED_DEFAULT):
+        """internal adapters inside every read's cDNA (bdg_chimera_batch): reads as for extract_batch, their records and trim
+        results -> CHIMERA_DTYPE array"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        trim = np.ascontiguousarray(trim, dtype=TRIM_DTYPE)
+        n = max(len(off) - 1, 0)
+        if len(recs) != n or len(trim) != n:
+            raise ValueError("chimera_batch: %d reads, %d records, %d trim results" % (n, len(recs), len(trim)))
+        out = np.zeros(n, dtype=CHIMERA_DTYPE)
+        self._check(self.lib.bdg_chimera_batch(self.h, bases.ctypes.data, off.ctypes.data, n, recs.ctypes.data, trim.ctypes.data,
+                                               max_ed, out.ctypes.data))
+        return out
+
+    def chimera_batch_dev(self, d_bases, d_off, n, d_recs, d_trim, max_ed, d_out):
+        """device form, behind the trim_batch_dev call that wrote d_trim (bdg_chimera_batch_dev); d_out: 12 bytes per read"""
+        self._check(self.lib.bdg_chimera_batch_dev(self.h, _ptr(d_bases), _ptr(d_off), n, _ptr(d_recs), _ptr(d_trim), max_ed, _ptr(d_out)))
+
+    def extract_set_chimera(self, on=True, max_ed=CHIMERA_MAX_ED_DEFAULT):
+        """while on (and the trim is on), extract_submit queues the chunk's chimera search behind its trim"""
+        self._check(self.lib.bdg_extract_set_chimera(self.h, 1 if on else 0, max_ed))
+
+    def extract_collect_chimera(self, slot, n):
+        """the chimera records of the chunk just collected from `slot` (after extract_collect)"""
+        out = np.zeros(n, dtype=CHIMERA_DTYPE)
+        self._check(self.lib.bdg_extract_collect_chimera(self.h, slot, out.ctypes.data))
         return out
 
     def extract_keep_records(self, on=True):
@@ -678,23 +729,32 @@ def chunk_reads(ch):
 
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
-               corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT):
+               corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT,
+               chimera_max_ed=None):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
     whitelist columns (header must name them); bc_candidates=K (1 .. 8) one more, whitelist_candidates.  corrected_path (with
     whitelist): whitelist correction (BDG_STAGE1_WL_CORRECT) into that file; the result then has whitelist_corrected.
     trimmed_path (with or without whitelist): the trimmed cDNA of every read as FASTA into that file (BDG_STAGE1_TRIM, TSO accepted
-    from tso_min_score on); the result then has trimmed_reads, trimmed_tso and trimmed_bases."""
+    from tso_min_score on); the result then has trimmed_reads, trimmed_tso and trimmed_bases.  chimera_max_ed (with trimmed_path):
+    reads are cut at their first internal adapter (BDG_STAGE1_CHIMERA); the result then has chimera_cut, chimera_dropped and
+    chimera_bases."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
     wl_mode = (1 | (STAGE1_WL_CANDIDATES if bc_candidates else 0) | (STAGE1_WL_CORRECT if correct else 0)) if whitelist else 0
     if trimmed_path is not None:
         wl_mode |= STAGE1_TRIM
+    if chimera_max_ed is not None:
+        wl_mode |= STAGE1_CHIMERA                   # (without a trimmed_path the library says E_ARG)
     args = (umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
             wl_mode, max_bc_dist, bc_candidates)
-    if trimmed_path is not None:
+    if chimera_max_ed is not None:
+        o = Stage1OptsChimera(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
+                              os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, 0, chimera_max_ed, 0)
+        res = Stage1ResultChimera()
+    elif trimmed_path is not None:
         o = Stage1OptsTrim(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
                            os.fsencode(trimmed_path), tso_min_score, 0)
         res = Stage1ResultTrim()
@@ -908,6 +968,24 @@ def format_trimmed(ch, recs, trim, best_idx=None, n_ties=None, wl=None):
         wl = np.ascontiguousarray(wl, dtype=np.uint32)
         args = [recs, trim, idx, ties, wl, len(wl)]
     return _format_rows(load().bdg_format_trimmed, "bdg_format_trimmed", ch, args, 3)
+
+
+def format_trimmed_chimera(ch, recs, trim, chim, best_idx=None, n_ties=None, wl=None):
+    """format_trimmed with the chunk's chimera records (bdg_format_trimmed_chimera) -> text, six counts"""
+    recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+    trim = np.ascontiguousarray(trim, dtype=TRIM_DTYPE)
+    chim = None if chim is None else np.ascontiguousarray(chim, dtype=CHIMERA_DTYPE)
+    if len(recs) != ch.n or len(trim) != ch.n or (chim is not None and len(chim) != ch.n):
+        raise ValueError("format_trimmed_chimera: %d reads, %d records, %d trim results" % (ch.n, len(recs), len(trim)))
+    if wl is None:
+        args = [recs, trim, chim, None, None, None, 0]
+    else:
+        idx, ties = np.ascontiguousarray(best_idx, dtype=np.uint32), np.ascontiguousarray(n_ties, dtype=np.uint16)
+        if len(idx) != ch.n or len(ties) != ch.n:
+            raise ValueError("format_trimmed_chimera: %d reads, %d / %d calls" % (ch.n, len(idx), len(ties)))
+        wl = np.ascontiguousarray(wl, dtype=np.uint32)
+        args = [recs, trim, chim, idx, ties, wl, len(wl)]
+    return _format_rows(load().bdg_format_trimmed_chimera, "bdg_format_trimmed_chimera", ch, args, 6 if chim is not None else 3)
 
 
 _DEFAULT = {}

@@ -270,9 +270,10 @@ void bdg_free(bdg_ctx* ctx)
                        &ctx->x_allumis, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
-        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match, &sl.d_trim }) if (b->p) (void)hipFree(b->p);
+        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match, &sl.d_trim, &sl.d_chim }) if (b->p) (void)hipFree(b->p);
         if (sl.h_recs) (void)hipHostFree(sl.h_recs);
         if (sl.h_trim) (void)hipHostFree(sl.h_trim);
+        if (sl.h_chim) (void)hipHostFree(sl.h_chim);
         if (sl.h_match) (void)hipHostFree(sl.h_match);
         if (sl.match_done) (void)hipEventDestroy(sl.match_done);
         if (sl.h_off) (void)hipHostFree(sl.h_off);
@@ -481,6 +482,13 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
                                   static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n, sl.trim_min_score, static_cast<bdg_trim_rec*>(sl.d_trim.p))))
             return rc;
         BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_trim, sl.d_trim.p, sizeof(bdg_trim_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
+        if (sl.chim) {                                           // ... and the search of the trimmed intervals behind the trim
+            if ((rc = bdg_chimera_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
+                                         static_cast<const bdg_extract_rec*>(sl.d_recs.p), static_cast<const bdg_trim_rec*>(sl.d_trim.p), sl.n,
+                                         sl.chim_max_ed, static_cast<bdg_chimera_rec*>(sl.d_chim.p))))
+                return rc;
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_chim, sl.d_chim.p, sizeof(bdg_chimera_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
+        }
     }
     BDG_HIP_TRY(ctx, hipEventRecord(sl.done, st));
     return BDG_OK;
@@ -503,6 +511,7 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
     sl.trim = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
+    sl.chim = ctx->trim_on && ctx->chim_on; sl.chim_max_ed = ctx->chim_max_ed;
     if (n == 0) { sl.busy = true; return BDG_OK; }
     if (int rco = check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -517,6 +526,10 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if (sl.trim) {
         if ((rc = bdg_reserve(ctx, sl.d_trim, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
         if ((rc = pinned_reserve(ctx, sl.h_trim, sl.h_trim_bytes, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
+    }
+    if (sl.chim) {
+        if ((rc = bdg_reserve(ctx, sl.d_chim, sizeof(bdg_chimera_rec) * (size_t)n))) return rc;
+        if ((rc = pinned_reserve(ctx, sl.h_chim, sl.h_chim_bytes, sizeof(bdg_chimera_rec) * (size_t)n))) return rc;
     }
     if (!sl.h_counters) {
         if (hipHostMalloc(&sl.h_counters, bdg_extract_counter_bytes(), hipHostMallocDefault) != hipSuccess) {
@@ -649,6 +662,7 @@ int bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score)
     if (on) if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
     ctx->trim_on = on != 0;
     ctx->trim_min_score = on ? tso_min_score : 0;
+    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; }     // (the search has nothing to search without the trim)
     return BDG_OK;
 }
 
@@ -661,6 +675,80 @@ int bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out)
     if (sl.n == 0) return BDG_OK;
     if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     memcpy(out, sl.h_trim, sizeof(bdg_trim_rec) * (size_t)sl.n);  // (the copy was queued in front of the event collect waited for)
+    return BDG_OK;
+}
+
+// ---- chimeric reads --------------------------------------------------------------
+static int check_chimera_max_ed(bdg_ctx* ctx, uint32_t v)
+{
+    return v > BDG_CHIMERA_MAX_ED_MAX ? bdg_fail(ctx, BDG_E_ARG, "chimera max_ed out of range (0 .. 6)") : BDG_OK;
+}
+
+int bdg_chimera_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
+                          const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim, uint32_t max_ed, bdg_chimera_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_chimera_max_ed(ctx, max_ed)) return rcs;
+    if (n && (!d_bases || !d_off || !d_recs || !d_trim || !d_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_trim) | reinterpret_cast<uintptr_t>(d_out)) & 3u) return bdg_fail(ctx, BDG_E_ARG, "d_trim and d_out must be 4-byte aligned");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_chimera_launch(ctx, d_bases, d_off, d_recs, d_trim, n, max_ed, d_out);
+}
+
+int bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
+                      const bdg_extract_rec* recs, const bdg_trim_rec* trim, uint32_t max_ed, bdg_chimera_rec* out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_chimera_max_ed(ctx, max_ed)) return rcs;
+    if (n == 0) return BDG_OK;
+    if (!bases || !off || !recs || !trim || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rco = check_offsets(ctx, off, n)) return rco;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t lo = off[0], total = off[n] - lo;
+    const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, trim_bytes = sizeof(bdg_trim_rec) * (size_t)n;
+    const size_t chim_bytes = sizeof(bdg_chimera_rec) * (size_t)n;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, total + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_bytes + trim_bytes + chim_bytes))) return rc;   // records | trim | results
+    std::vector<uint64_t> rel((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
+    hipStream_t st = ctx->stream;
+    char* const d_recs = static_cast<char*>(ctx->s_out0.p);
+    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, total, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, rec_bytes, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs + rec_bytes, trim, trim_bytes, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_chimera_launch(ctx, static_cast<const uint8_t*>(ctx->s_in0.p), static_cast<const uint64_t*>(ctx->s_in1.p),
+                                 reinterpret_cast<const bdg_extract_rec*>(d_recs), reinterpret_cast<const bdg_trim_rec*>(d_recs + rec_bytes), n,
+                                 max_ed, reinterpret_cast<bdg_chimera_rec*>(d_recs + rec_bytes + trim_bytes))))
+        return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_recs + rec_bytes + trim_bytes, chim_bytes, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
+    return BDG_OK;
+}
+
+int bdg_extract_set_chimera(bdg_ctx* ctx, int on, uint32_t max_ed)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (on) {
+        if (!ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "the chimera search needs the trim (bdg_extract_set_trim)");
+        if (int rcs = check_chimera_max_ed(ctx, max_ed)) return rcs;
+    }
+    ctx->chim_on = on != 0;
+    ctx->chim_max_ed = on ? max_ed : 0;
+    return BDG_OK;
+}
+
+int bdg_extract_collect_chimera(bdg_ctx* ctx, uint32_t slot, bdg_chimera_rec* out)
+{
+    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "collect the slot's records first (bdg_extract_collect)");
+    if (!sl.chim) return bdg_fail(ctx, BDG_E_ARG, "the slot's chunk was submitted without a chimera search (bdg_extract_set_chimera)");
+    if (sl.n == 0) return BDG_OK;
+    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    memcpy(out, sl.h_chim, sizeof(bdg_chimera_rec) * (size_t)sl.n);  // (the copy was queued in front of the event collect waited for)
     return BDG_OK;
 }
 

@@ -77,6 +77,10 @@ struct bdg_ctx {
         DevBuf d_trim;                                       // bdg_trim_rec [n]
         void* h_trim = nullptr; size_t h_trim_bytes = 0;     // pinned
         bool trim = false; uint32_t trim_min_score = 0;      // what the chunk was submitted with
+        // chimera search of the chunk (bdg_extract_set_chimera): behind the trim, results copied to h_chim
+        DevBuf d_chim;                                       // bdg_chimera_rec [n]
+        void* h_chim = nullptr; size_t h_chim_bytes = 0;     // pinned
+        bool chim = false; uint32_t chim_max_ed = 0;         // what the chunk was submitted with
         // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
         DevBuf d_match;                                      // match_layout(n, match_k)
         void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
@@ -95,6 +99,7 @@ struct bdg_ctx {
         DevBuf out;          // resolve: corr_out()
     } corr;
     bool trim_on = false; uint32_t trim_min_score = 0;       // bdg_extract_set_trim: for the submits that follow
+    bool chim_on = false; uint32_t chim_max_ed = 0;          // bdg_extract_set_chimera: likewise (only while trim_on)
     // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
     bool keep_records = false;
     DevBuf x_allrecs; uint64_t x_allrecs_n = 0;

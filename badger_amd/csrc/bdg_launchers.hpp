@@ -44,3 +44,5 @@ int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32
                          uint32_t*, uint32_t*);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
+// chimera_kernels.hip
+int bdg_chimera_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, const bdg_trim_rec*, uint32_t, uint32_t, bdg_chimera_rec*);

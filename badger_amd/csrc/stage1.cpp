@@ -135,27 +135,38 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
     return o;
 }
 
-struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0; };
+struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0; };
 
 // upper bound of the FASTA text of a chunk's trimmed reads
-uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl)
+uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl, bool with_ch = false)
 {
     uint64_t need = 0;
     for (uint32_t i = 0; i < ch->n; ++i) {
         if (!(tr[i].flags & BDG_TRIM_EMIT)) continue;
         const uint64_t L = ch->off[i + 1] - ch->off[i];
         need += (ch->id_off[i + 1] - ch->id_off[i]) + 48 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start))
-                + (with_wl ? 22 : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);
+                + (with_wl ? 22 : 0) + (with_ch ? 16 : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);   // (16: the CH field of a cut read)
     }
     return need;
 }
 
 // ">id\tCR:Z:barcode\tUR:Z:UMI\tST:A:strand[\tCB:Z:whitelist barcode]\n" cDNA in mRNA sense "\n" per read with BDG_TRIM_EMIT
-char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, const WlCalls* wc, char* o, TrimStats& st)
+// with cm (the chunk's chimera records): a read with a hit ends at its cut and says so in a last field "\tCH:Z:kind,edits";
+// one whose cut is its cDNA's first column is left out
+char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, const bdg_chimera_rec* cm,
+                    const WlCalls* wc, char* o, TrimStats& st)
 {
+    static const char* const kind_name[4] = { "TSO", "TSOrc", "R1", "R1rc" };
     for (uint32_t i = 0; i < ch->n; ++i) {
         const bdg_trim_rec& t = tr[i];
         if (!(t.flags & BDG_TRIM_EMIT)) continue;
+        const bool hit = cm && (cm[i].flags & BDG_CHIMERA_HIT);
+        const int32_t cend = hit ? cm[i].cut : t.cdna_end;
+        if (hit) {
+            st.cut_bases += (uint64_t)std::max(0, t.cdna_end - cend);
+            if (cend <= t.cdna_start) { ++st.dropped; continue; }
+            ++st.cut;
+        }
         const bdg_extract_rec& r = recs[i];
         const uint8_t* seq = ch->bases + ch->off[i];
         const int64_t L = (int64_t)(ch->off[i + 1] - ch->off[i]);
@@ -180,9 +191,18 @@ char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, con
             memcpy(o, "\tCB:Z:", 6); o += 6;
             o = put_barcode16(o, wc->wl[wc->idx[i]]);
         }
+        if (hit) {
+            memcpy(o, "\tCH:Z:", 6); o += 6;
+            const char* kn = kind_name[cm[i].hit_kind & 3u];
+            const size_t kl = strlen(kn);
+            memcpy(o, kn, kl); o += kl;
+            *o++ = ',';
+            if (cm[i].hit_ed >= 10) *o++ = (char)('0' + cm[i].hit_ed / 10 % 10);
+            *o++ = (char)('0' + cm[i].hit_ed % 10);
+        }
         *o++ = '\n';
         // revcomp(s[a:b]): for a reverse-strand record the read's own bytes, for a forward one their reverse complement
-        const int64_t a = std::min<int64_t>(std::max<int64_t>(t.cdna_start, 0), L), b = std::min<int64_t>(std::max<int64_t>(t.cdna_end, 0), L);
+        const int64_t a = std::min<int64_t>(std::max<int64_t>(t.cdna_start, 0), L), b = std::min<int64_t>(std::max<int64_t>(cend, 0), L);
         if (b > a) {
             if (rev) { memcpy(o, seq + (L - b), (size_t)(b - a)); o += b - a; }
             else for (int64_t x = b - 1; x >= a; --x) *o++ = comp_base((char)seq[x]);
@@ -205,6 +225,7 @@ struct Job : Fly {
         std::vector<uint32_t> idx; std::vector<uint8_t> ed; std::vector<uint16_t> ties;       // whitelist calls
         std::vector<uint32_t> cidx; std::vector<uint8_t> ced;                                 // top-k slots (bc_candidates)
         std::vector<bdg_trim_rec> trim;                                                       // BDG_STAGE1_TRIM
+        std::vector<bdg_chimera_rec> chim;                                                    // BDG_STAGE1_CHIMERA
     } r;
     std::vector<char> text; size_t text_len = 0;
     RowStats st;
@@ -255,8 +276,8 @@ struct Pipeline {
             TrimText* tt = nullptr;
             if (fd_trim >= 0) {
                 tt = new TrimText;
-                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr));
-                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), pw, tt->text.data(), tt->st) - tt->text.data());
+                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr, !j->r.chim.empty()));
+                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), j->r.chim.empty() ? nullptr : j->r.chim.data(), pw, tt->text.data(), tt->st) - tt->text.data());
             }
             bdg_ingest_release(ing, j->ch.id);
             j->r = Job::Results();                             // (their memory goes back now, not when the row text is written)
@@ -312,6 +333,7 @@ struct Pipeline {
                 std::lock_guard<std::mutex> lk(mu);
                 if (bad) trim_write_failed = true;
                 trim_total.reads += t->st.reads; trim_total.tso += t->st.tso; trim_total.bases += t->st.bases;
+                trim_total.cut += t->st.cut; trim_total.dropped += t->st.dropped; trim_total.cut_bases += t->st.cut_bases;
             }
             delete t;
         }
@@ -484,8 +506,25 @@ int64_t bdg_format_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* re
     const uint64_t need = trimmed_bound(ch, recs, trim, with_wl);
     if (!out || need > cap) return (int64_t)need;
     TrimStats st;
-    char* e = write_trimmed(ch, recs, trim, with_wl ? &wc : nullptr, out, st);
+    char* e = write_trimmed(ch, recs, trim, nullptr, with_wl ? &wc : nullptr, out, st);
     if (counts) { counts[0] = st.reads; counts[1] = st.tso; counts[2] = st.bases; }
+    return (int64_t)(e - out);
+}
+
+int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                                   const bdg_chimera_rec* chim, const uint32_t* best_idx, const uint16_t* n_ties,
+                                   const uint32_t* wl, uint32_t nw, char* out, uint64_t cap, uint64_t counts[6])
+{
+    if (!chim) return bdg_format_trimmed(ch, recs, trim, best_idx, n_ties, wl, nw, out, cap, counts);
+    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
+    const bool with_wl = best_idx || n_ties || wl;
+    if (with_wl && ch->n && (!best_idx || !n_ties || (nw && !wl))) return BDG_E_ARG;
+    const WlCalls wc{ best_idx, nullptr, n_ties, wl, nw };
+    const uint64_t need = trimmed_bound(ch, recs, trim, with_wl, true);
+    if (!out || need > cap) return (int64_t)need;
+    TrimStats st;
+    char* e = write_trimmed(ch, recs, trim, chim, with_wl ? &wc : nullptr, out, st);
+    if (counts) { counts[0] = st.reads; counts[1] = st.tso; counts[2] = st.bases; counts[3] = st.cut; counts[4] = st.dropped; counts[5] = st.cut_bases; }
     return (int64_t)(e - out);
 }
 
@@ -495,12 +534,15 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !out_path || !header || !o || !res) return BDG_E_ARG;
     bdg_ctx* const c0 = ctxs[0];
     // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
-    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~BDG_STAGE1_TRIM) != 0;
+    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA)) != 0;
+    const bool chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
+    if (chim && !trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_CHIMERA needs BDG_STAGE1_TRIM");
     const bool corr = wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT);
     // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT, those behind it with BDG_STAGE1_TRIM)
-    memset(res, 0, trim ? sizeof(*res) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
+    memset(res, 0, chim ? sizeof(*res) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
+    if (chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
     if (trim) {
         if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
         if (o->tso_min_score < 8 || o->tso_min_score > 30) return bdg_fail(c0, BDG_E_ARG, "tso_min_score out of range (8 .. 30)");
@@ -562,6 +604,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
             return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
         }
         for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 1, o->tso_min_score);   // (checked above; off again below)
+        if (chim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_chimera(ctxs[c], 1, o->chimera_max_ed);
     }
     bool ok_io = true;
     if (!o->header_every) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
@@ -579,6 +622,11 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
             j->r.trim.resize(f.ch.n);
             const int r = bdg_extract_collect_trim(f.ctx, f.slot, j->r.trim.data());
             if (r) { delete j; return r; }
+            if (chim && f.ch.n) {
+                j->r.chim.resize(f.ch.n);
+                const int r2 = bdg_extract_collect_chimera(f.ctx, f.slot, j->r.chim.data());
+                if (r2) { delete j; return r2; }
+            }
         }
         if (wl_on) {
             j->r.idx.resize(f.ch.n); j->r.ed.resize(f.ch.n); j->r.ties.resize(f.ch.n);
@@ -610,6 +658,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         trim_writer.join();
         if (::close(P.fd_trim) != 0) P.trim_write_failed = true;
         res->trimmed_reads = P.trim_total.reads; res->trimmed_tso = P.trim_total.tso; res->trimmed_bases = P.trim_total.bases;
+        if (chim) { res->chimera_cut = P.trim_total.cut; res->chimera_dropped = P.trim_total.dropped; res->chimera_bases = P.trim_total.cut_bases; }
     }
     // rows of the chunks before a failure are in the file, like in the reference's loop
     if (rc == BDG_OK && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;

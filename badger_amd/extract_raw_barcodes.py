@@ -39,6 +39,11 @@ What differs from the reference, by design:
     in input order; the TSV, the .stats and the .corrected.tsv do not change; the three counts go to the log.  Every input
     this command line reads goes through the native pipeline, which is where the flag lives; the Python-driven
     BarcodeCaller.process path (stage 2's read input) has no such output.
+  * --chimera_cut (with --trimmed_reads): a read whose cDNA holds an R1 adapter or a TSO, in either orientation, within
+    --chimera_max_ed edits (0 .. 6, default 3; two more for the longer TSO) is two molecules ligated end to end.  It is written
+    up to the first such column only, its header gains "\tCH:Z:<TSO|TSOrc|R1|R1rc>,<edits>", and it is left out when nothing
+    remains.  The rule is restated in badger_amd/chimera.py and stated in include/badger_hip.h (bdg_chimera_batch).  The TSV
+    and the .stats do not change; the three counts go to the log.
 """
 import argparse
 import gzip
@@ -64,6 +69,7 @@ CORRECTED_SUFFIX = ".corrected.tsv"
 BC_EDIT_BITS_DEFAULT = 5
 BC_MIN_POSTERIOR_DEFAULT = 0.975
 TSO_MIN_SCORE_RANGE = (8, 30)
+CHIMERA_MAX_ED_RANGE = (0, _native.CHIMERA_MAX_ED_MAX)
 BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
 
 
@@ -401,6 +407,8 @@ def _run_native(args, header_every, threads, skip_secondary):
     if getattr(args, "trimmed_reads", None):
         logger.info("Trimmed reads: %d written to %s, %d with the TSO cut off, %d bases"
                     % (res.trimmed_reads, args.trimmed_reads, res.trimmed_tso, res.trimmed_bases))
+    if getattr(args, "chimera_cut", False):
+        logger.info("Chimeric reads: %d cut, %d left out, %d bases cut off" % (res.chimera_cut, res.chimera_dropped, res.chimera_bases))
     timing = os.environ.get("BADGER_AMD_STAGE1_TIMING")
     if timing:                                   # where the run's time went (tools/cli_throughput.py reads it)
         import json
@@ -529,9 +537,19 @@ def parse_args(sys_argv):
     p.add_argument("--tso_min_score", type=_tso_min_score, default=None, metavar="N",
                    help="--trimmed_reads: smallest local-alignment score (match +1, mismatch / gap -1) at which the template-switch "
                         "oligo is cut off, %d .. %d (default %d)" % (TSO_MIN_SCORE_RANGE + (_native.TSO_MIN_SCORE_DEFAULT,)))
+    p.add_argument("--chimera_cut", action="store_true", default=False,
+                   help="--trimmed_reads: cut a read at the first R1 adapter or template-switch oligo found inside its cDNA, in either "
+                        "orientation (two molecules ligated end to end); the header gains a CH field, a read with nothing left is left out")
+    p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
+                   help="--chimera_cut: edits allowed in the 22-base adapter (two more in the 30-base oligo), %d .. %d (default %d)"
+                        % (CHIMERA_MAX_ED_RANGE + (_native.CHIMERA_MAX_ED_DEFAULT,)))
     args = p.parse_args(sys_argv)
     if args.tso_min_score is not None and not args.trimmed_reads:
         p.error("--tso_min_score needs --trimmed_reads")
+    if args.chimera_cut and not args.trimmed_reads:
+        p.error("--chimera_cut needs --trimmed_reads")
+    if args.chimera_max_ed is not None and not args.chimera_cut:
+        p.error("--chimera_max_ed needs --chimera_cut")
     if args.max_bc_dist is not None and not args.barcodes:
         p.error("--max_bc_dist needs --barcodes")
     if args.bc_candidates is not None and not args.barcodes:
@@ -584,6 +602,16 @@ def _tso_min_score(text):
     return v
 
 
+def _chimera_max_ed(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not CHIMERA_MAX_ED_RANGE[0] <= v <= CHIMERA_MAX_ED_RANGE[1]:
+        raise argparse.ArgumentTypeError("%d is outside %d .. %d" % ((v,) + CHIMERA_MAX_ED_RANGE))
+    return v
+
+
 def _bc_posterior(text):
     """--bc_min_posterior as permille (501 .. 1000)"""
     try:
@@ -627,7 +655,11 @@ def _trim_kwargs(args):
     if not path:
         return {}
     score = getattr(args, "tso_min_score", None)
-    return dict(trimmed_path=path, tso_min_score=_native.TSO_MIN_SCORE_DEFAULT if score is None else score)
+    kw = dict(trimmed_path=path, tso_min_score=_native.TSO_MIN_SCORE_DEFAULT if score is None else score)
+    if getattr(args, "chimera_cut", False):
+        ed = getattr(args, "chimera_max_ed", None)
+        kw["chimera_max_ed"] = _native.CHIMERA_MAX_ED_DEFAULT if ed is None else ed
+    return kw
 
 
 def _max_bc_dist(args):

@@ -254,6 +254,53 @@ int  bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uin
 int  bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score);
 int  bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out);
 
+/* ---- chimeric reads (stage 1's --chimera_cut; the rule restated in badger_amd/chimera.py) ---------------------------- */
+/* An R1 adapter or a TSO, in either orientation, inside what the trim calls cDNA is the junction of two molecules ligated end
+ * to end.  Per read, from its extraction record, its bdg_trim_rec and its strand text s (the read, or its reverse complement
+ * for BDG_FLAG_REV records; strand coordinates as everywhere).  Only a read with BDG_TRIM_EMIT takes part, every other read
+ * gets the "none" record {-1, -1, 0, 0, 0, 0}.  Integers only.
+ *   interval  [a, b) = [cdna_start, cdna_end).
+ *   patterns  kind 0: BDG_TRIM_TSO_SEQ as the trim aligns it, kind 1: its reverse complement (30 bases), kind 2:
+ *             BDG_CHIMERA_R1_SEQ, the R1 adapter stage 1 aligns, kind 3: its reverse complement (22 bases).
+ *   bound     with max_ed = E (0 .. BDG_CHIMERA_MAX_ED_MAX) k_P = E for the R1 kinds and E + 2 for the TSO kinds: the same edits
+ *             per base, rounded.
+ *   search    for pattern P and column j in [a, b): D_P(j) = the minimum over e in [j, b] of the unit-cost Levenshtein distance
+ *             of P and s[j:e) - the start fixed at j, the end free, the match wholly inside the interval.  A byte of s that
+ *             is not A, C, G or T equals no pattern letter.  (P, j) is a hit when D_P(j) <= k_P.
+ *   result    cut = the smallest j with a hit of any kind, -1 without one; hit_pos / hit_ed / hit_kind = the hit with the
+ *             smallest (D, j, kind) in that order, -1 / 0 / 0 without one; flags = BDG_CHIMERA_HIT with a hit.
+ * Both are plain minima over all (P, j): the answer depends neither on the order of evaluation nor on how the work is split.
+ * Over-trim: a start one column early costs one edit, so cut lies up to k_P - D columns left of the occurrence's true first
+ * base: the cut never keeps a foreign base and gives up at most 8 bases of cDNA (E = 6, an exact TSO).
+ * The library scans an interval in pieces of BDG_CHIMERA_SEGMENT columns, each from a fresh automaton started m + k columns
+ * early; a match of at most k edits spans at most m + k columns, so the pieces report what the whole scan reports. */
+#define BDG_CHIMERA_R1_SEQ   "CTACACGACGCTCTTCCGATCT"           /* barcode_callers.py:154 */
+#define BDG_CHIMERA_SEGMENT  256
+#define BDG_CHIMERA_MAX_ED_DEFAULT 3     /* the largest E with at most 1 false cut in 1,000 chimera-free reads */
+#define BDG_CHIMERA_MAX_ED_MAX 6
+#define BDG_CHIMERA_HIT 1u
+typedef struct bdg_chimera_rec {
+    int32_t  cut;
+    int32_t  hit_pos;
+    uint8_t  hit_ed;
+    uint8_t  hit_kind;    /* 0 TSO, 1 TSO reverse complement, 2 R1, 3 R1 reverse complement */
+    uint8_t  flags;       /* BDG_CHIMERA_* */
+    uint8_t  reserved;    /* 0 */
+} bdg_chimera_rec;        /* 12 bytes */
+/* Device-resident, behind the bdg_trim_batch_dev call that wrote d_trim (same stream); d_out [n].  Asynchronous.  BDG_E_ARG for
+ * max_ed > BDG_CHIMERA_MAX_ED_MAX.  Two calls on the same input write the same bytes. */
+int  bdg_chimera_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
+                           const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim, uint32_t max_ed, bdg_chimera_rec* d_out);
+/* Host buffers: reads as for bdg_extract_batch, their records and trim results; copies in, runs, copies out. */
+int  bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
+                       const bdg_extract_rec* recs, const bdg_trim_rec* trim, uint32_t max_ed, bdg_chimera_rec* out);
+/* The pipelined path: while on (only together with bdg_extract_set_trim: BDG_E_ARG otherwise), bdg_extract_submit queues the
+ * search and the copy of its 12 bytes per read behind the chunk's trim, and bdg_extract_collect_chimera(slot) - after
+ * bdg_extract_collect - hands them over.  A chunk run again after a queue overflow is searched again, as it is trimmed again.
+ * Turning the trim off turns this off too. */
+int  bdg_extract_set_chimera(bdg_ctx* ctx, int on, uint32_t max_ed);
+int  bdg_extract_collect_chimera(bdg_ctx* ctx, uint32_t slot, bdg_chimera_rec* out);
+
 /* ---- read ingest and row output (host side) --------------------------------------------- */
 /* [gzipped / BGZF] FASTA / FASTQ / SAM and BAM -> chunks of at most chunk_reads reads {concatenated bases, offsets, ids}
  * in pinned host memory (pinned = 0: pageable, for hosts without a GPU), in file order.  Replaces the reference's record
@@ -330,6 +377,14 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
 int64_t bdg_format_trimmed(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
                            const uint32_t* best_idx, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
                            char* out, uint64_t cap, uint64_t counts[3]);
+/* The same with the chimera records of the chunk (bdg_chimera_batch).  chim == NULL: the bytes and the three counts of
+ * bdg_format_trimmed.  Otherwise a read with BDG_CHIMERA_HIT is written as revcomp(s[cdna_start:cut)), its header gains a last
+ * field "\tCH:Z:" TSO | TSOrc | R1 | R1rc "," hit_ed, and it is left out when cut == cdna_start.  counts (may be NULL): the
+ * three of bdg_format_trimmed (over what is written), then reads cut, reads left out, cDNA bases cut off (cdna_end - cut over
+ * both). */
+int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                                   const bdg_chimera_rec* chim, const uint32_t* best_idx, const uint16_t* n_ties,
+                                   const uint32_t* wl, uint32_t nw, char* out, uint64_t cap, uint64_t counts[6]);
 
 /* Stage 1 from file to file in native threads: readers -> GPU(s) -> row formatters -> one writer, rows in input order
  * (extract_raw_barcodes.py:162-173 process_single_thread, :176-261 process_in_parallel).  Chunk k goes to context k mod
@@ -351,6 +406,11 @@ int64_t bdg_format_trimmed(const bdg_ingest_chunk* chunk, const bdg_extract_rec*
  * bdg_stage1_result.trimmed_* counts; the caller's structs then reach to those fields.  The main TSV and every other output are
  * the same bytes as without the bit. */
 #define BDG_STAGE1_TRIM          0x400u
+/* bdg_stage1_opts.whitelist, valid only together with BDG_STAGE1_TRIM (BDG_E_ARG otherwise): chimeric reads are cut at their
+ * first internal adapter (bdg_chimera_batch's rule, bdg_format_trimmed_chimera's text).  Only with this bit does the library
+ * read chimera_max_ed or write the three bdg_stage1_result.chimera_* counts.  The TSV and every other output but the trimmed
+ * file are the same bytes as without the bit. */
+#define BDG_STAGE1_CHIMERA       0x800u
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -377,6 +437,9 @@ typedef struct bdg_stage1_opts {
     const char* trimmed_path;     /* the FASTA file of trimmed reads */
     uint32_t tso_min_score;       /* 8 .. 30 (BDG_TRIM_TSO_MIN_SCORE_DEFAULT) */
     uint32_t reserved_trim;
+    /* read only with BDG_STAGE1_CHIMERA */
+    uint32_t chimera_max_ed;      /* 0 .. BDG_CHIMERA_MAX_ED_MAX (BDG_CHIMERA_MAX_ED_DEFAULT) */
+    uint32_t reserved_chimera;
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -392,6 +455,7 @@ typedef struct bdg_stage1_result {
     uint64_t whitelist_barcodes;              /* opts->whitelist: rows with a whitelist_barcode (counts[4] of bdg_format_rows_wl) */
     uint64_t whitelist_corrected;             /* written only with BDG_STAGE1_WL_CORRECT (or BDG_STAGE1_TRIM, then 0 without the correction): rows of status exact or corrected */
     uint64_t trimmed_reads, trimmed_tso, trimmed_bases;   /* written only with BDG_STAGE1_TRIM: counts[3] of bdg_format_trimmed over the run */
+    uint64_t chimera_cut, chimera_dropped, chimera_bases;   /* written only with BDG_STAGE1_CHIMERA: counts[3 .. 5] of bdg_format_trimmed_chimera */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
