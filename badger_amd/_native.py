@@ -481,10 +481,11 @@ class Context:
         self._check(self.lib.bdg_extract_set_strand_rule(self.h, rule))
 
     def extract_counters(self):
-        out = (C.c_uint64 * 8)()
+        out = (C.c_uint64 * 9)()
         self._check(self.lib.bdg_extract_counters(self.h, out))
-        names = ("hits", "clusters", "filter_in", "filter_skipped", "filter_kept", "requeued", "alignments", "filter_in_clusters")
-        return dict(zip(names, [int(x) for x in out[:8]]))
+        names = ("hits", "clusters", "filter_in", "filter_skipped", "filter_kept", "requeued", "alignments", "filter_in_clusters",
+                 "filter_searches")
+        return dict(zip(names, [int(x) for x in out[:9]]))
 
     # -- nearest ---------------------------------------------------------------
     def nearest16(self, q, wl, max_ed=2):

@@ -403,7 +403,7 @@ int bdg_extract_set_strand_rule(bdg_ctx* ctx, int rule)
     return BDG_OK;
 }
 
-int bdg_extract_counters(bdg_ctx* ctx, uint64_t out[8])
+int bdg_extract_counters(bdg_ctx* ctx, uint64_t out[9])
 {
     if (!ctx || !out) return BDG_E_ARG;
     return bdg_extract_counters_impl(ctx, out);

@@ -20,8 +20,8 @@
 //                    If the union cannot beat the first hit, no later hit of the cluster can replace it as "first
 //                    strictly best" (common.py:102-103) and they are skipped; otherwise they are re-queued (queue C).
 //   k_strict_filter  queue B only matters if an alignment reaches score 17, which implies semi-global edit distance <= 5:
-//                    Myers' 22-bit search per hit, after dropping read-strands the relaxed search has already decided;
-//                    survivors join queue C.
+//                    Myers' 22-bit search per group of two neighbouring hits (one pass over the union of their windows),
+//                    after dropping read-strands the relaxed search has already decided; survivors join queue C.
 //   k_sw_singles     the same alignment kernel over queue C: re-queued hits and filter survivors, one by one.
 //   k_finalize_reads one lane per read: delta checks, reverse pass for strict hits, polyT re-search, barcode/UMI
 //                    slicing, strand choice, 32-byte record.
@@ -51,7 +51,8 @@ enum { K_TASK = 0,      // next task of the shard (k_scan_reads)
        K_NC = 2, K_ND = 3,
        K_STAT = 4,      // S_* words below
        K_LINES = 5 };
-enum { S_BADREAD = 0 /* max of ~read index, 0 = none */, S_NWINDOWS = 1, S_NKEPT = 2, S_NHITS = 3, S_NSKIPPED = 4, S_NBHITS = 5, S_N = 6 };
+enum { S_BADREAD = 0 /* max of ~read index, 0 = none */, S_NWINDOWS = 1, S_NKEPT = 2, S_NHITS = 3, S_NSKIPPED = 4, S_NBHITS = 5,
+       S_NSEARCH = 6 /* Myers searches of k_strict_filter: one per group of hits */, S_N = 7 };
 constexpr int SH_WORDS = K_LINES * 16;                       // 64-bit words per shard
 constexpr size_t COUNTER_BYTES = (size_t)NSH * SH_WORDS * 8;
 
@@ -927,13 +928,23 @@ __device__ __forceinline__ uint64_t make_key(uint32_t acc, uint32_t pos)
 }
 
 // ---------------------------------------------------------------------------
-// k_strict_filter: one lane per queue-B cluster.  A local alignment of R1 with score >= 17
+// k_strict_filter: queue B's clusters.  A local alignment of R1 with score >= 17
 // (+1/-1/-1, N = 0) leaves at most 5 of the 22 pattern bases unmatched or mispaired, so R1
 // occurs in the window with semi-global edit distance <= 5.  Myers' 22-bit search decides that
-// at about a tenth of the cost of the alignment; only surviving hits join queue A.
+// at about a tenth of the cost of the alignment; only surviving hits join queue C.
+//
+// The hits of a cluster are mostly neighbours (a 7-mer of R1 matched, so two 6-mers did), and the windows of two
+// neighbours share 38 of their 39 bases.  So a lane searches a GROUP - a hit and, if the cluster holds it, the hit one
+// position on - once, over the union of the two windows: 40 bases, the ten words a single window needs anyway.  Every
+// alignment inside either window lies inside the union (free start, minimum over all end columns), so the union's result is
+// <= each hit's own: a group above 5 holds no hit the per-hit test would keep; a group at or below 5 forwards both hits,
+// the exact alignment of k_sw_singles decides, and a hit kept for its neighbour's sake scores below 17 there.
 // ---------------------------------------------------------------------------
+constexpr int FSPREAD = 2;                                                         // positions a group spans (4 was measured: DESIGN.md 4.4)
+constexpr int FW = ((R1_LEN - KMER) + (R1_LEN + 1) + (FSPREAD - 1) + 3) / 4;       // words of a group's window
 
-__device__ __forceinline__ uint32_t myers_search(uint32_t (&w)[10], int n, uint32_t comp)
+template <int NW>
+__device__ __forceinline__ uint32_t myers_search(uint32_t (&w)[NW], int n, uint32_t comp)
 {
     // Only bit 21 of the vectors is ever read and carries only move upwards, so bits 22..31 are left to hold anything.
     // A column is 20 vector instructions (round 4; the compiler's form of the textbook statements was 29): the equality mask
@@ -944,13 +955,13 @@ __device__ __forceinline__ uint32_t myers_search(uint32_t (&w)[10], int n, uint3
     uint32_t pv = 0x3FFFFFu, mv = 0u, score = R1_LEN, best = R1_LEN;
     const uint32_t flip = comp ? 0x04040404u : 0u;           // complement = 2-bit code ^ 2 = ASCII bit 2
 #pragma unroll
-    for (int d = 0; d < 10; ++d) {
+    for (int d = 0; d < NW; ++d) {
         const int left = n - 4 * d;                          // window bases in this word and behind it
         const uint32_t keep = left >= 4 ? 0xFFFFFFFFu : (left <= 0 ? 0u : (1u << (8 * left)) - 1u);
         w[d] = ((w[d] ^ flip) & keep) | (0x4E4E4E4Eu & ~keep);
     }
 #pragma nounroll
-    for (int d = 0; d < 10; ++d) {                           // rolled: keeps the kernel at 8 waves per SIMD, which the gathers need
+    for (int d = 0; d < NW; ++d) {                           // rolled: keeps the kernel at 8 waves per SIMD, which the gathers need
         const uint32_t cur = w[0];
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -972,7 +983,7 @@ __device__ __forceinline__ uint32_t myers_search(uint32_t (&w)[10], int n, uint3
             best = score < best ? score : best;
         }
 #pragma unroll
-        for (int i = 0; i < 9; ++i) w[i] = w[i + 1];
+        for (int i = 0; i < NW - 1; ++i) w[i] = w[i + 1];
     }
     return best;
 }
@@ -984,32 +995,39 @@ void k_strict_filter(const uint8_t* __restrict__ bases, uint64_t total_rounded,
                      unsigned long long* __restrict__ counters,
                      const unsigned long long* __restrict__ keys)
 {
-    __shared__ uint2 s_buf[4][192];          // live hits {read, (pos << 1) | strand}, compacted per wave (< 64 waiting + <= 128 new)
-    __shared__ uint2 s_out[4][128];          // survivors, flushed with one reservation
+    __shared__ uint2 s_buf[4][192];          // live groups {read, (first pos << 1) | strand}, compacted per wave (< 64 waiting + <= 128 new)
+    __shared__ uint8_t s_grp[4][192];        // ... and which of the FSPREAD positions from there on are hits (bit 0 always)
+    __shared__ uint2 s_out[4][64 * FSPREAD]; // surviving hits, flushed with one reservation
     __shared__ uint32_t s_cnt[NSH];
     const uint64_t nb = queue_counts(counters, K_NAB, 1, seg, s_cnt);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t shard = blockIdx.x % NSH;
     const uint64_t stride = (uint64_t)gridDim.x * 256ull;
-    uint32_t nkept = 0, nskip = 0, nbhits = 0, nbuf = 0, nout = 0;
+    uint32_t nkept = 0, nskip = 0, nbhits = 0, nsearch = 0, nbuf = 0, nout = 0;
 
-    auto process = [&](uint2 h, bool active) {
+    auto process = [&](uint2 h, uint32_t g, bool active) {
         uint64_t rs = 0; int64_t L = 0;
         if (active) { rs = off[h.x]; L = (int64_t)(off[h.x + 1] - rs); }
         const uint32_t strand = h.y & 1u;
-        const int64_t pos = (int64_t)(h.y >> 1);
+        const int64_t pos = (int64_t)(h.y >> 1), last = pos + (31 - __builtin_clz(g | 1u));
+        // strand positions: the windows of later hits reach further towards the strand's end, whichever strand it is
         const int64_t ws = pos - (R1_LEN - KMER) > 0 ? pos - (R1_LEN - KMER) : 0;
-        const int64_t we = pos + R1_LEN + 1 < L ? pos + R1_LEN + 1 : L;
-        uint32_t w[10];
-        load_block<10>(bases, total_rounded, rs, L, (int)strand, ws, +1, w);
-        const uint32_t k = myers_search(w, active ? (int)(we - ws) : 0, strand);
+        const int64_t we = last + R1_LEN + 1 < L ? last + R1_LEN + 1 : L;
+        uint32_t w[FW];
+        load_block<FW>(bases, total_rounded, rs, L, (int)strand, ws, +1, w);
+        const uint32_t k = myers_search<FW>(w, active ? (int)(we - ws) : 0, strand);
+        nsearch += (uint32_t)__popcll(__ballot(active));
         const bool keep = active && k <= 5u;
-        const unsigned long long m = __ballot(keep);
-        if (m) {
-            const uint32_t cnt = (uint32_t)__popcll(m);
-            if (nout + cnt > 128u) stage_flush(s_out[wv], nout, lane, qd, seg, shard, ctr(counters, shard, K_NC));
-            if (keep) s_out[wv][nout + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = h;
-            nout += cnt; nkept += cnt;
+        if (__ballot(keep)) {
+            const uint32_t cnt = keep ? (uint32_t)__popc(g) : 0u;
+            const uint32_t incl = wave_incl_scan(cnt);
+            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);           // <= 64 * FSPREAD
+            if (nout + tot > 64u * FSPREAD) stage_flush(s_out[wv], nout, lane, qd, seg, shard, ctr(counters, shard, K_NC));
+            uint32_t at = nout + incl - cnt;
+#pragma unroll
+            for (uint32_t j = 0; j < (uint32_t)FSPREAD; ++j)
+                if (keep && ((g >> j) & 1u)) s_out[wv][at++] = make_uint2(h.x, h.y + (j << 1));
+            nout += tot; nkept += tot;
         }
     };
 
@@ -1024,36 +1042,42 @@ void k_strict_filter(const uint8_t* __restrict__ bases, uint64_t total_rounded,
             const unsigned long long kr = keys[2ull * e.x + (e.y & 1u)];
             if (kr != 0 && (R1_LEN - 1 - (int)(kr & 31u)) <= 4) { nskip += __popc(mask); mask = 0u; }
         }
-        // live clusters hand over their hits, at most two per lane and round, to the compacted list
+        // live clusters hand over their hits as groups (the lowest hit left and the hits of the FSPREAD - 1 positions
+        // behind it), at most two groups per lane and round, to the compacted list
         while (__ballot(mask != 0u)) {
             const int j0 = mask ? __builtin_ctz(mask) : 0;
-            const uint32_t m1 = mask & (mask - 1u);
-            const int j1 = m1 ? __builtin_ctz(m1) : 0;
-            const uint32_t cnt = (mask ? 1u : 0u) + (m1 ? 1u : 0u);
-            mask = m1 & (m1 - 1u);
+            const uint32_t g0 = (mask >> j0) & ((1u << FSPREAD) - 1u);
+            mask &= ~(g0 << j0);
+            const int j1 = mask ? __builtin_ctz(mask) : 0;
+            const uint32_t g1 = (mask >> j1) & ((1u << FSPREAD) - 1u);
+            mask &= ~(g1 << j1);
+            const uint32_t cnt = (g0 ? 1u : 0u) + (g1 ? 1u : 0u);
             const uint32_t incl = wave_incl_scan(cnt);
             const uint32_t at = nbuf + incl - cnt;
-            if (cnt >= 1u) s_buf[wv][at] = make_uint2(e.x, e.y + ((uint32_t)j0 << 1));
-            if (cnt == 2u) s_buf[wv][at + 1u] = make_uint2(e.x, e.y + ((uint32_t)j1 << 1));
+            if (cnt >= 1u) { s_buf[wv][at] = make_uint2(e.x, e.y + ((uint32_t)j0 << 1)); s_grp[wv][at] = (uint8_t)g0; }
+            if (cnt == 2u) { s_buf[wv][at + 1u] = make_uint2(e.x, e.y + ((uint32_t)j1 << 1)); s_grp[wv][at + 1u] = (uint8_t)g1; }
             nbuf += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             __builtin_amdgcn_wave_barrier();
             while (nbuf >= 64u) {
                 nbuf -= 64u;
                 const uint2 h = s_buf[wv][nbuf + lane];
+                const uint32_t g = s_grp[wv][nbuf + lane];
                 __builtin_amdgcn_wave_barrier();
-                process(h, true);
+                process(h, g, true);
             }
         }
     }
     if (nbuf) {
         const bool on = (uint32_t)lane < nbuf;
         const uint2 h = on ? s_buf[wv][lane] : make_uint2(0u, 0u);
-        process(h, on);
+        const uint32_t g = on ? s_grp[wv][lane] : 0u;
+        process(h, g, on);
     }
     __builtin_amdgcn_wave_barrier();
     stage_flush(s_out[wv], nout, lane, qd, seg, shard, ctr(counters, shard, K_NC));
     unsigned long long* const stat = ctr(counters, shard, K_STAT);
     if (lane == 0 && nkept) atomicAdd(&stat[S_NKEPT], (unsigned long long)nkept);
+    if (lane == 0 && nsearch) atomicAdd(&stat[S_NSEARCH], (unsigned long long)nsearch);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) nskip += __shfl_xor(nskip, d);
     if (lane == 0 && nskip) atomicAdd(&stat[S_NSKIPPED], (unsigned long long)nskip);
@@ -1561,14 +1585,15 @@ int bdg_extract_status_impl(bdg_ctx* ctx, uint64_t* bad_read, uint64_t* n_window
     return judge_counters(ctx, cs, ctx->x_hits_cap_launched, bad_read, n_windows);
 }
 
-int bdg_extract_counters_impl(bdg_ctx* ctx, uint64_t out[8])
+int bdg_extract_counters_impl(bdg_ctx* ctx, uint64_t out[9])
 {
-    memset(out, 0, sizeof(uint64_t) * 8);
+    memset(out, 0, sizeof(uint64_t) * 9);
     if (!ctx->x_counters.p) return BDG_OK;
     CounterSums cs;
     int rc;
     if ((rc = read_counters(ctx, cs))) return rc;
     out[0] = cs.stat[S_NHITS]; out[1] = cs.a; out[2] = cs.stat[S_NBHITS]; out[3] = cs.stat[S_NSKIPPED];
     out[4] = cs.stat[S_NKEPT]; out[5] = cs.c - cs.stat[S_NKEPT]; out[6] = cs.stat[S_NWINDOWS]; out[7] = cs.b;    // queue C = re-queued + survivors
+    out[8] = cs.stat[S_NSEARCH];
     return BDG_OK;
 }

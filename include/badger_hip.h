@@ -172,8 +172,9 @@ int  bdg_extract_set_strand_rule(bdg_ctx* ctx, int rule);
 /* Pipeline statistics of the last extraction (synchronises): out[0] 6-mer hits, [1] clusters aligned
  * (queue A), [2] hits sent to the strict filter (queue B), [3] of those skipped because the
  * relaxed search had already succeeded, [4] filter survivors, [5] hits re-queued from clusters,
- * [6] alignments run, [7] clusters the hits of [2] arrived in. */
-int  bdg_extract_counters(bdg_ctx* ctx, uint64_t out[8]);
+ * [6] alignments run, [7] clusters the hits of [2] arrived in, [8] Myers searches the filter ran (one per
+ * group of neighbouring hits; [2] - [3] is what one search per hit would be). */
+int  bdg_extract_counters(bdg_ctx* ctx, uint64_t out[9]);
 
 /* Pipelined form of bdg_extract_batch for a stream of chunks (extract_raw_barcodes.py:131-159: chunks of 100,000
  * reads): submit() enqueues the H2D copy of a chunk (pinned host memory makes it asynchronous), the kernels and the
