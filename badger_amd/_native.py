@@ -56,6 +56,7 @@ EXPORTS = [
     "bdg_write_molecules",
     "bdg_trim_batch", "bdg_trim_batch_dev", "bdg_extract_set_trim", "bdg_extract_collect_trim", "bdg_format_trimmed",
     "bdg_chimera_batch", "bdg_chimera_batch_dev", "bdg_extract_set_chimera", "bdg_extract_collect_chimera", "bdg_format_trimmed_chimera",
+    "bdg_extract_keep_cdna", "bdg_kept_cdna", "bdg_molecule_reps_dev", "bdg_molecule_reps_set_aggregate", "bdg_format_trimmed_tags",
 ]
 
 
@@ -78,6 +79,7 @@ class IngestOpts(C.Structure):
 STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates is set (BDG_STAGE1_WL_CANDIDATES)
 STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist correction, the trailing fields are set (BDG_STAGE1_WL_CORRECT)
 STAGE1_CHIMERA = 0x800              # bdg_stage1_opts.whitelist: with STAGE1_TRIM, chimeric reads are cut; chimera_max_ed is set (BDG_STAGE1_CHIMERA)
+STAGE1_TAGS = 0x1000                # bdg_stage1_opts.whitelist: with STAGE1_TRIM, the trimmed file carries stage 2's tags; the tag_* fields are set (BDG_STAGE1_TAGS)
 STAGE1_TRIM = 0x400                 # bdg_stage1_opts.whitelist: trimmed reads, the fields behind the correction's are set (BDG_STAGE1_TRIM)
 # status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
 WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
@@ -106,6 +108,12 @@ class Stage1OptsChimera(Stage1OptsTrim):
     _fields_ = [("chimera_max_ed", C.c_uint32), ("reserved_chimera", C.c_uint32)]
 
 
+class Stage1OptsTags(Stage1OptsChimera):
+    """bdg_stage1_opts with the fields read only with STAGE1_TAGS"""
+    _fields_ = [("tag_cell_rank", C.c_void_p), ("tag_cell_has", C.c_void_p), ("tag_molecule", C.c_void_p),
+                ("tag_mol_reads", C.c_void_p), ("tag_keep", C.c_void_p), ("tag_reads", C.c_uint64)]
+
+
 class Stage1Result(C.Structure):
     """bdg_stage1_result"""
     _fields_ = [("reads", C.c_uint64), ("barcodes", C.c_uint64), ("polyt", C.c_uint64), ("r1", C.c_uint64),
@@ -129,6 +137,11 @@ class Stage1ResultTrim(Stage1ResultCorrect):
 class Stage1ResultChimera(Stage1ResultTrim):
     """bdg_stage1_result with the counts written only with STAGE1_CHIMERA"""
     _fields_ = [("chimera_cut", C.c_uint64), ("chimera_dropped", C.c_uint64), ("chimera_bases", C.c_uint64)]
+
+
+class Stage1ResultTags(Stage1ResultChimera):
+    """bdg_stage1_result with the counts written only with STAGE1_TAGS"""
+    _fields_ = [("tags_no_cell", C.c_uint64), ("tags_not_kept", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -264,6 +277,12 @@ def load():
     L.bdg_extract_collect_chimera.argtypes = [vp, u32, vp]
     L.bdg_format_trimmed_chimera.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.bdg_format_trimmed_chimera.restype = C.c_int64
+    L.bdg_extract_keep_cdna.argtypes = [vp, C.c_int]
+    L.bdg_kept_cdna.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
+    L.bdg_molecule_reps_dev.argtypes = [vp, vp, vp, vp, vp, u64, vp, u32, vp, vp]
+    L.bdg_molecule_reps_set_aggregate.argtypes = [vp, C.c_int]
+    L.bdg_format_trimmed_tags.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.bdg_format_trimmed_tags.restype = C.c_int64
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -452,6 +471,26 @@ class Context:
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self.lib.bdg_kept_umis(self.h, C.byref(p), C.byref(n)))
         return p.value or 0, int(n.value)
+
+    def extract_keep_cdna(self, on=True):
+        """with the kept records, every read's cDNA length on the device (bdg_extract_keep_cdna; only while the trim is on)"""
+        self._check(self.lib.bdg_extract_keep_cdna(self.h, 1 if on else 0))
+
+    def kept_cdna(self):
+        """-> (device pointer, count) of the kept cDNA lengths"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self.lib.bdg_kept_cdna(self.h, C.byref(p), C.byref(n)))
+        return p.value or 0, int(n.value)
+
+    def molecule_reps_dev(self, d_rank, d_has, d_molecule, d_cdna_len, n, d_cells, n_cells, d_rep, d_mol_reads):
+        """one representative read per molecule and every molecule's read count (bdg_molecule_reps_dev): d_rep uint8 [n],
+        d_mol_reads uint32 [n]"""
+        self._check(self.lib.bdg_molecule_reps_dev(self.h, _ptr(d_rank), _ptr(d_has), _ptr(d_molecule), _ptr(d_cdna_len), n,
+                                                   _ptr(d_cells), n_cells, _ptr(d_rep), _ptr(d_mol_reads)))
+
+    def molecule_reps_set_aggregate(self, on=True):
+        """for measurements and tests: False makes every lane of molecule_reps_dev issue its own atomics"""
+        self._check(self.lib.bdg_molecule_reps_set_aggregate(self.h, 1 if on else 0))
 
     def umi_dedup_dev(self, d_rank, d_has, d_umi, n, d_cells, n_cells, umi_len, umi_dist, d_molecule, d_cell_counts):
         """per-cell UMI deduplication (bdg_umi_dedup_dev): per read the molecule's UMI code, per cell [reads, umi_reads,
@@ -731,7 +770,7 @@ def chunk_reads(ch):
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
                corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT,
-               chimera_max_ed=None):
+               chimera_max_ed=None, tags=None):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
@@ -740,7 +779,9 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     trimmed_path (with or without whitelist): the trimmed cDNA of every read as FASTA into that file (BDG_STAGE1_TRIM, TSO accepted
     from tso_min_score on); the result then has trimmed_reads, trimmed_tso and trimmed_bases.  chimera_max_ed (with trimmed_path):
     reads are cut at their first internal adapter (BDG_STAGE1_CHIMERA); the result then has chimera_cut, chimera_dropped and
-    chimera_bases."""
+    chimera_bases.  tags (with trimmed_path, without whitelist; out_path may then be None: no TSV): a dict of per-read numpy arrays
+    over the whole input - cell_rank, cell_has and optionally molecule with mol_reads, and keep - whose answers go into the headers of
+    the trimmed file (BDG_STAGE1_TAGS, bdg_format_trimmed_tags); the result then has tags_no_cell and tags_not_kept."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
@@ -749,9 +790,22 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         wl_mode |= STAGE1_TRIM
     if chimera_max_ed is not None:
         wl_mode |= STAGE1_CHIMERA                   # (without a trimmed_path the library says E_ARG)
+    if tags is not None:
+        wl_mode |= STAGE1_TAGS                      # (without a trimmed_path the library says E_ARG)
     args = (umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
             wl_mode, max_bc_dist, bc_candidates)
-    if chimera_max_ed is not None:
+    if tags is not None:
+        held = [np.ascontiguousarray(tags["cell_rank"], dtype=np.uint32), np.ascontiguousarray(tags["cell_has"], dtype=np.uint8)]
+        held += [None if tags.get(k) is None else np.ascontiguousarray(tags[k], dtype=t)
+                 for k, t in (("molecule", np.uint32), ("mol_reads", np.uint32), ("keep", np.uint8))]
+        if len({len(a) for a in held if a is not None}) != 1 or (held[2] is None) != (held[3] is None):
+            raise ValueError("stage1_run: the tag arrays differ in length, or molecule comes without mol_reads")
+        o = Stage1OptsTags(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
+                           os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, 0,
+                           chimera_max_ed if chimera_max_ed is not None else 0, 0,
+                           *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]))
+        res = Stage1ResultTags()
+    elif chimera_max_ed is not None:
         o = Stage1OptsChimera(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
                               os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, 0, chimera_max_ed, 0)
         res = Stage1ResultChimera()
@@ -765,7 +819,7 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     else:
         o = Stage1Opts(*args)
         res = Stage1Result()
-    rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path), header.encode("ascii"),
+    rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path) if out_path is not None else None, header.encode("ascii"),
                           C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
     if rc != 0:
         _raise_like_reference(rc, L.bdg_last_error(contexts[0].h).decode())
@@ -987,6 +1041,20 @@ def format_trimmed_chimera(ch, recs, trim, chim, best_idx=None, n_ties=None, wl=
         wl = np.ascontiguousarray(wl, dtype=np.uint32)
         args = [recs, trim, chim, idx, ties, wl, len(wl)]
     return _format_rows(load().bdg_format_trimmed_chimera, "bdg_format_trimmed_chimera", ch, args, 6 if chim is not None else 3)
+
+
+def format_trimmed_tags(ch, recs, trim, chim, cell_rank, cell_has, molecule=None, mol_reads=None, keep=None):
+    """format_trimmed_chimera's records (chim may be None) of the reads with a cell (and, with keep, of those it keeps), their
+    headers carrying CB and - with molecule / mol_reads - UB and RN (bdg_format_trimmed_tags) -> text, (records, bases, reads left
+    out for having no cell, reads left out by keep)"""
+    recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+    trim = np.ascontiguousarray(trim, dtype=TRIM_DTYPE)
+    chim = None if chim is None else np.ascontiguousarray(chim, dtype=CHIMERA_DTYPE)
+    per_read = [np.ascontiguousarray(cell_rank, dtype=np.uint32), np.ascontiguousarray(cell_has, dtype=np.uint8)]
+    per_read += [None if a is None else np.ascontiguousarray(a, dtype=t) for a, t in ((molecule, np.uint32), (mol_reads, np.uint32), (keep, np.uint8))]
+    if any(a is not None and len(a) != ch.n for a in [recs, trim, chim] + per_read):
+        raise ValueError("format_trimmed_tags: an array does not hold %d reads" % ch.n)
+    return _format_rows(load().bdg_format_trimmed_tags, "bdg_format_trimmed_tags", ch, [recs, trim, chim] + per_read, 4)
 
 
 _DEFAULT = {}

@@ -3,9 +3,16 @@
 (reference badger.py:23-47,62-132), with the edit-distance graph built on the MI355X.
 
     python -m badger_amd.badger -r out.tsv -d tenX_v3 -l whitelist.txt -c 5000 [-t 1] [-hs] [--umi_dedup [--umi_dist 1]]
+    python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa [--chimera_cut] [--umi_dedup [--molecule_reads]]
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
+
+--tagged_reads PATH (read input only) writes what stage 1's --trimmed_reads [--chimera_cut] writes, for the reads this stage gave a
+cell: the trimmed cDNA with the corrected barcode as CB and, with --umi_dedup, the molecule as UB and its read count as RN in the
+header.  The input is read a second time for it (the extraction costs under a millisecond per million reads; no bases are kept).
+--molecule_reads keeps one read per molecule: the longest cDNA, the earliest read at equal lengths (the rule of molecule_reads.py,
+on the device).  Every other output is the same bytes with and without these flags.
 
 --stats and --ground_truth drive the reference's offline evaluation module (stats.py), which
 is outside the accelerated path; the flags are accepted and rejected with a message.
@@ -19,7 +26,7 @@ from traceback import print_exc
 
 from . import _native
 from .barcode_graph import BarcodeGraph
-from .extract_raw_barcodes import BARCODE_CALLING_MODES, is_native_input
+from .extract_raw_barcodes import BARCODE_CALLING_MODES, _chimera_max_ed, _tso_min_score, is_native_input
 
 logger = logging.getLogger("BarcodeGraph")
 
@@ -56,9 +63,37 @@ def parse_args(args):
                         "representative UMI) and <out>_cells.tsv (per cell: reads, reads with a UMI, UMIs, molecules)")
     p.add_argument("--umi_dist", type=int, default=None, choices=(0, 1),
                    help="with --umi_dedup: largest edit distance between two UMIs of one molecule (default 1)")
+    p.add_argument("--tagged_reads", type=str, default=None, metavar="PATH",
+                   help="read input only: the trimmed cDNA (stage 1's --trimmed_reads) of every read with a cell as FASTA, the header "
+                        "carrying the corrected barcode (CB) and, with --umi_dedup, the molecule (UB) and its read count (RN)")
+    p.add_argument("--tso_min_score", type=_tso_min_score, default=None, metavar="N",
+                   help="--tagged_reads: smallest alignment score at which the template-switch oligo is cut off, %d .. %d (default %d)"
+                        % (8, 30, _native.TSO_MIN_SCORE_DEFAULT))
+    p.add_argument("--chimera_cut", action="store_true", default=False,
+                   help="--tagged_reads: cut a read at the first adapter or template-switch oligo inside its cDNA (stage 1's --chimera_cut)")
+    p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
+                   help="--chimera_cut: edits allowed in the adapter, 0 .. %d (default %d)"
+                        % (_native.CHIMERA_MAX_ED_MAX, _native.CHIMERA_MAX_ED_DEFAULT))
+    p.add_argument("--molecule_reads", action="store_true", default=False,
+                   help="--tagged_reads with --umi_dedup: write one read per molecule, the one with the longest cDNA (the earliest "
+                        "at equal lengths)")
     a = p.parse_args(args)
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
+    if a.tagged_reads and a.reads.endswith("tsv"):
+        p.error("--tagged_reads needs read input (FASTA, FASTQ, SAM or BAM): a stage-1 TSV does not hold the reads' bases")
+    if a.tso_min_score is not None and not a.tagged_reads:
+        p.error("--tso_min_score needs --tagged_reads")
+    if a.chimera_cut and not a.tagged_reads:
+        p.error("--chimera_cut needs --tagged_reads")
+    if a.chimera_max_ed is not None and not a.chimera_cut:
+        p.error("--chimera_max_ed needs --chimera_cut")
+    if a.molecule_reads and not (a.umi_dedup and a.tagged_reads):
+        p.error("--molecule_reads needs --umi_dedup and --tagged_reads")
+    if a.tso_min_score is None:
+        a.tso_min_score = _native.TSO_MIN_SCORE_DEFAULT
+    if a.chimera_cut and a.chimera_max_ed is None:
+        a.chimera_max_ed = _native.CHIMERA_MAX_ED_DEFAULT
     if a.umi_dist is None:
         a.umi_dist = 1
     return a
@@ -189,6 +224,14 @@ def main(args):
         ctx = _native.default_context(args.device)
         ctx.extract_keep_records(True)
         ctx.extract_keep_umis(args.umi_dedup)             # (every chunk's UMIs packed beside its records)
+        # --tagged_reads with molecules: every chunk is trimmed (and searched for chimeras) here too, and only its reads' cDNA
+        # lengths stay, for the election of each molecule's read; the bases come back in the second pass
+        keep_cdna = bool(args.tagged_reads and args.umi_dedup)
+        if keep_cdna:
+            ctx.extract_set_trim(True, args.tso_min_score)
+            if args.chimera_cut:
+                ctx.extract_set_chimera(True, args.chimera_max_ed)
+            ctx.extract_keep_cdna(True)
         logger.info("Extracting from " + args.reads)
         read_ids = _native.IdStore()
         umi_len = BARCODE_CALLING_MODES[args.data_type](device=args.device).UMI_LEN_10X
@@ -198,9 +241,12 @@ def main(args):
             _native.stage1_collect(ctx, args.reads, umi_len, read_ids, threads=args.threads,
                                    skip_secondary=args.threads != 1)
         except BaseException:
+            ctx.extract_set_trim(False)
             ctx.extract_keep_umis(False)
             ctx.extract_keep_records(False)
             raise
+        if keep_cdna:
+            ctx.extract_set_trim(False)                   # (what was kept stays until the records go)
         mark("extract")
         logger.info("Finished barcode extraction")
         logger.info("Initializing Graph")
@@ -219,11 +265,21 @@ def main(args):
     st2.output_file_from_device(read_ids, from_device, args.output, args.high_sens, keep_reads=args.umi_dedup)
     if args.umi_dedup:
         from .umi_dedup import UMI_LEN
-        molecules = st2.umi_dedup_from_device(read_ids, args.output, UMI_LEN[args.data_type], args.umi_dist)
+        molecules = st2.umi_dedup_from_device(read_ids, args.output, UMI_LEN[args.data_type], args.umi_dist,
+                                              keep_molecules=bool(args.tagged_reads))
         mark("umi_dedup")
         logger.info("Molecules: %d" % molecules)
         from_device.extract_keep_umis(False)
+    tags = st2.read_tags_from_device(args.molecule_reads) if args.tagged_reads else None
     from_device.extract_keep_records(False)
+    if args.tagged_reads:
+        # the second pass: the same reader threads and the same skip_secondary as the first, so the same reads in the same order
+        res = _native.stage1_run([from_device], args.reads, None, "", umi_len, threads=args.threads,
+                                 skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads,
+                                 tso_min_score=args.tso_min_score, chimera_max_ed=args.chimera_max_ed, tags=tags)
+        mark("tagged_reads")
+        logger.info("Tagged reads: %d to %s, %d bases; left out: %d without a cell, %d not their molecule's read"
+                    % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))
     disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
     st2.release_device()
     mark("output")

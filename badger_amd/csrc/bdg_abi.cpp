@@ -267,7 +267,7 @@ void bdg_free(bdg_ctx* ctx)
     DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
                        &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
                        &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs,
-                       &ctx->x_allumis, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
+                       &ctx->x_allumis, &ctx->x_allcdna, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
     for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
     for (auto& sl : ctx->slots) {
         for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match, &sl.d_trim, &sl.d_chim }) if (b->p) (void)hipFree(b->p);
@@ -604,6 +604,16 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
                 return rc;
             ctx->x_allumis_n += sl.n;
         }
+        if (ctx->keep_cdna) {
+            // the chunk's cDNA lengths, from the trim and chimera records of the pass that counted (a rerun wrote them again)
+            if (!sl.trim) return bdg_fail(ctx, BDG_E_ARG, "cDNA lengths are kept but the slot's chunk was submitted without a trim");
+            if ((rc = kept_grow(ctx, ctx->x_allcdna, 4 * (size_t)ctx->x_allcdna_n, 4 * (size_t)sl.n, size_t(8) << 20))) return rc;
+            if ((rc = bdg_cdna_len_launch(ctx, static_cast<const bdg_trim_rec*>(sl.d_trim.p),
+                                          sl.chim ? static_cast<const bdg_chimera_rec*>(sl.d_chim.p) : nullptr, sl.n,
+                                          static_cast<uint32_t*>(ctx->x_allcdna.p) + ctx->x_allcdna_n)))
+                return rc;
+            ctx->x_allcdna_n += sl.n;
+        }
         ctx->x_allrecs_n += sl.n;
     }
     return BDG_OK;
@@ -662,7 +672,7 @@ int bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score)
     if (on) if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
     ctx->trim_on = on != 0;
     ctx->trim_min_score = on ? tso_min_score : 0;
-    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; }     // (the search has nothing to search without the trim)
+    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; ctx->keep_cdna = false; }   // (nothing to search or to measure without the trim)
     return BDG_OK;
 }
 
@@ -936,7 +946,8 @@ int bdg_extract_keep_records(bdg_ctx* ctx, int on)
     ctx->keep_records = on != 0;
     ctx->x_allrecs_n = 0;
     ctx->x_allumis_n = 0;
-    if (!on) for (DevBuf* b : { &ctx->x_allrecs, &ctx->x_allumis }) if (b->p) {
+    ctx->x_allcdna_n = 0;
+    if (!on) for (DevBuf* b : { &ctx->x_allrecs, &ctx->x_allumis, &ctx->x_allcdna }) if (b->p) {
         BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         (void)hipFree(b->p);
         *b = DevBuf();
@@ -949,6 +960,42 @@ int bdg_extract_keep_umis(bdg_ctx* ctx, int on)
     if (!ctx) return BDG_E_ARG;
     ctx->keep_umis = on != 0;
     ctx->x_allumis_n = 0;
+    return BDG_OK;
+}
+
+int bdg_extract_keep_cdna(bdg_ctx* ctx, int on)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (on && !ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "cDNA lengths need the trim (bdg_extract_set_trim)");
+    ctx->keep_cdna = on != 0;
+    ctx->x_allcdna_n = 0;
+    return BDG_OK;
+}
+
+int bdg_kept_cdna(bdg_ctx* ctx, const uint32_t** d_len, uint64_t* n)
+{
+    if (!ctx || !d_len || !n) return BDG_E_ARG;
+    *d_len = static_cast<const uint32_t*>(ctx->x_allcdna.p);
+    *n = ctx->x_allcdna_n;
+    return BDG_OK;
+}
+
+int bdg_molecule_reps_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_molecule,
+                          const uint32_t* d_cdna_len, uint64_t n, const uint32_t* d_cells, uint32_t n_cells,
+                          uint8_t* d_rep, uint32_t* d_mol_reads)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && (!d_rank || !d_has || !d_molecule || !d_cdna_len || !d_rep || !d_mol_reads)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n_cells && !d_cells) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_molecule_reps_launch(ctx, d_rank, d_has, d_molecule, d_cdna_len, n, d_cells, n_cells, d_rep, d_mol_reads);
+}
+
+int bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on)
+{
+    if (!ctx) return BDG_E_ARG;
+    ctx->mol_aggregate = on != 0;
     return BDG_OK;
 }
 

@@ -106,7 +106,12 @@ struct bdg_ctx {
     // with them (bdg_extract_keep_umis), every read's UMI packed into 32 bits (umi_kernels.hip), in the same order
     bool keep_umis = false;
     DevBuf x_allumis; uint64_t x_allumis_n = 0;
-    DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read
+    // ... and (bdg_extract_keep_cdna, only while trim_on) every read's cDNA length, from the chunk's trim and chimera records
+    bool keep_cdna = false;
+    DevBuf x_allcdna; uint64_t x_allcdna_n = 0;
+    DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read;
+                         // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
+    bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -42,6 +42,9 @@ int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_
 int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
 int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t,
                          uint32_t*, uint32_t*);
+int bdg_cdna_len_launch(bdg_ctx*, const bdg_trim_rec*, const bdg_chimera_rec*, uint32_t, uint32_t*);
+int bdg_molecule_reps_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t,
+                             uint8_t*, uint32_t*);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // chimera_kernels.hip

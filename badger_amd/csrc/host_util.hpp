@@ -35,6 +35,14 @@ inline char* put_barcode16(char* o, uint32_t rank)
     return o;
 }
 
+// the letters of a packed UMI code (len << 28 | 2-bit letters, first letter most significant; bdg_extract_keep_umis)
+inline char* put_umi_code(char* o, uint32_t c)
+{
+    const uint32_t L = c >> 28;
+    for (uint32_t j = 0; j < L; ++j) *o++ = "ACGT"[(c >> (2 * (L - 1 - j))) & 3u];
+    return o;
+}
+
 // 0 .. 3 for A, C, G, T; 4 for every other letter
 inline uint32_t acgt_code(char c)
 {

@@ -3,6 +3,7 @@
 //                    barcode_callers.py:40-42,91-93,117-119); the barcode / UMI text is sliced from the chunk's bases, for
 //                    reverse-strand results from the reverse complement (barcode_extraction/common.py:34-39).
 //   bdg_format_trimmed  the trimmed cDNA of a chunk's reads as FASTA text, from the records and the trim results (--trimmed_reads).
+//   bdg_format_trimmed_tags  the same with stage 2's cell, molecule and read count per read in the header (--tagged_reads).
 //   bdg_stage1_run   input file -> TSV, everything between in native threads: the readers of ingest.cpp fill pinned chunks,
 //                    this thread submits them to the GPU(s) (bdg_extract_submit / collect, chunk k on context k mod N, two
 //                    in flight per context), a few formatter threads turn records into rows and a writer thread writes them
@@ -135,17 +136,26 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
     return o;
 }
 
-struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0; };
+struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0, no_cell = 0, not_kept = 0; };
+
+// stage 2's answers for the reads of a chunk (bdg_format_trimmed_tags): the cell, the molecule's code and its read count (mol may
+// be null), a filter (may be null)
+struct Tags {
+    const uint32_t* rank; const uint8_t* has; const uint32_t* mol; const uint32_t* mol_reads; const uint8_t* keep;
+    Tags at(uint64_t g0) const { return Tags{ rank + g0, has + g0, mol ? mol + g0 : nullptr, mol_reads ? mol_reads + g0 : nullptr, keep ? keep + g0 : nullptr }; }
+};
+constexpr uint64_t TAG_COLS_MAX = (6 + 16) + (6 + 15) + (6 + 10);   // "\tCB:Z:" cell "\tUB:Z:" molecule "\tRN:i:" count
 
 // upper bound of the FASTA text of a chunk's trimmed reads
-uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl, bool with_ch = false)
+uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl, bool with_ch = false,
+                       bool with_tags = false)
 {
     uint64_t need = 0;
     for (uint32_t i = 0; i < ch->n; ++i) {
         if (!(tr[i].flags & BDG_TRIM_EMIT)) continue;
         const uint64_t L = ch->off[i + 1] - ch->off[i];
         need += (ch->id_off[i + 1] - ch->id_off[i]) + 48 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start))
-                + (with_wl ? 22 : 0) + (with_ch ? 16 : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);   // (16: the CH field of a cut read)
+                + (with_wl ? 22 : 0) + (with_ch ? 16 : 0) + (with_tags ? TAG_COLS_MAX : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);   // (16: the CH field of a cut read)
     }
     return need;
 }
@@ -153,8 +163,10 @@ uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, 
 // ">id\tCR:Z:barcode\tUR:Z:UMI\tST:A:strand[\tCB:Z:whitelist barcode]\n" cDNA in mRNA sense "\n" per read with BDG_TRIM_EMIT
 // with cm (the chunk's chimera records): a read with a hit ends at its cut and says so in a last field "\tCH:Z:kind,edits";
 // one whose cut is its cDNA's first column is left out
+// with tg (stage 2's answers): a read without a cell, or one the filter drops, is left out; the others get "\tCB:Z:cell" and, with
+// a molecule, "\tUB:Z:molecule\tRN:i:reads" in front of the CH field
 char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, const bdg_chimera_rec* cm,
-                    const WlCalls* wc, char* o, TrimStats& st)
+                    const WlCalls* wc, char* o, TrimStats& st, const Tags* tg = nullptr)
 {
     static const char* const kind_name[4] = { "TSO", "TSOrc", "R1", "R1rc" };
     for (uint32_t i = 0; i < ch->n; ++i) {
@@ -165,8 +177,12 @@ char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, con
         if (hit) {
             st.cut_bases += (uint64_t)std::max(0, t.cdna_end - cend);
             if (cend <= t.cdna_start) { ++st.dropped; continue; }
-            ++st.cut;
         }
+        if (tg) {
+            if (!tg->has[i]) { ++st.no_cell; continue; }
+            if (tg->keep && !tg->keep[i]) { ++st.not_kept; continue; }
+        }
+        if (hit) ++st.cut;
         const bdg_extract_rec& r = recs[i];
         const uint8_t* seq = ch->bases + ch->off[i];
         const int64_t L = (int64_t)(ch->off[i + 1] - ch->off[i]);
@@ -190,6 +206,16 @@ char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, con
         if (wc && r.valid && (r.flags & BDG_FLAG_RANK_OK) && wc->idx[i] < wc->nw && wc->ties[i] == 1) {   // the row's whitelist_barcode is not '*'
             memcpy(o, "\tCB:Z:", 6); o += 6;
             o = put_barcode16(o, wc->wl[wc->idx[i]]);
+        }
+        if (tg) {
+            memcpy(o, "\tCB:Z:", 6); o += 6;
+            o = put_barcode16(o, tg->rank[i]);
+            if (tg->mol && tg->mol[i] != 0xFFFFFFFFu) {
+                memcpy(o, "\tUB:Z:", 6); o += 6;
+                o = put_umi_code(o, tg->mol[i]);
+                memcpy(o, "\tRN:i:", 6); o += 6;
+                o = put_uint(o, tg->mol_reads[i]);
+            }
         }
         if (hit) {
             memcpy(o, "\tCH:Z:", 6); o += 6;
@@ -256,6 +282,8 @@ struct Pipeline {
     uint64_t next_trim = 0;
     bool trim_write_failed = false;
     TrimStats trim_total;
+    const Tags* tags = nullptr;                                // BDG_STAGE1_TAGS: per-read arrays over the whole input
+    bool no_tsv = false;                                       // ... with out_path == NULL: no rows are made
 
     void format_loop()
     {
@@ -270,14 +298,20 @@ struct Pipeline {
             const double t0 = now_s();
             const WlCalls wc{ j->r.idx.data(), j->r.ed.data(), j->r.ties.data(), wl, nw, k, j->r.cidx.data(), j->r.ced.data() };
             const WlCalls* pw = wl ? &wc : nullptr;
-            j->text.resize((size_t)rows_bound(&j->ch, j->r.recs.data(), header_every, header.size(), pw));
-            char* e = write_rows(&j->ch, j->r.recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
-            j->text_len = (size_t)(e - j->text.data());
+            if (!no_tsv) {
+                j->text.resize((size_t)rows_bound(&j->ch, j->r.recs.data(), header_every, header.size(), pw));
+                char* e = write_rows(&j->ch, j->r.recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
+                j->text_len = (size_t)(e - j->text.data());
+            } else {
+                j->st.reads = j->ch.n;
+            }
             TrimText* tt = nullptr;
             if (fd_trim >= 0) {
                 tt = new TrimText;
-                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr, !j->r.chim.empty()));
-                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), j->r.chim.empty() ? nullptr : j->r.chim.data(), pw, tt->text.data(), tt->st) - tt->text.data());
+                const Tags tg = tags ? tags->at(j->g0) : Tags{};
+                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr, !j->r.chim.empty(), tags != nullptr));
+                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), j->r.chim.empty() ? nullptr : j->r.chim.data(), pw, tt->text.data(), tt->st,
+                                                 tags ? &tg : nullptr) - tt->text.data());
             }
             bdg_ingest_release(ing, j->ch.id);
             j->r = Job::Results();                             // (their memory goes back now, not when the row text is written)
@@ -304,7 +338,7 @@ struct Pipeline {
                 j = it->second; formatted.erase(it); ++next_write;
             }
             const double t0 = now_s();
-            const bool bad = !write_all(fd, j->text.data(), j->text_len);
+            const bool bad = fd >= 0 && !write_all(fd, j->text.data(), j->text_len);
             const double dt = now_s() - t0;
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -334,6 +368,7 @@ struct Pipeline {
                 if (bad) trim_write_failed = true;
                 trim_total.reads += t->st.reads; trim_total.tso += t->st.tso; trim_total.bases += t->st.bases;
                 trim_total.cut += t->st.cut; trim_total.dropped += t->st.dropped; trim_total.cut_bases += t->st.cut_bases;
+                trim_total.no_cell += t->st.no_cell; trim_total.not_kept += t->st.not_kept;
             }
             delete t;
         }
@@ -528,18 +563,40 @@ int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* ch, const bdg_extract
     return (int64_t)(e - out);
 }
 
+int64_t bdg_format_trimmed_tags(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                                const bdg_chimera_rec* chim, const uint32_t* cell_rank, const uint8_t* cell_has,
+                                const uint32_t* molecule, const uint32_t* mol_reads, const uint8_t* keep,
+                                char* out, uint64_t cap, uint64_t counts[4])
+{
+    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
+    if (ch->n && (!cell_rank || !cell_has || (molecule && !mol_reads))) return BDG_E_ARG;
+    const uint64_t need = trimmed_bound(ch, recs, trim, false, chim != nullptr, true);
+    if (!out || need > cap) return (int64_t)need;
+    const Tags tg{ cell_rank, cell_has, molecule, mol_reads, keep };
+    TrimStats st;
+    char* e = write_trimmed(ch, recs, trim, chim, nullptr, out, st, &tg);
+    if (counts) { counts[0] = st.reads; counts[1] = st.bases; counts[2] = st.no_cell; counts[3] = st.not_kept; }
+    return (int64_t)(e - out);
+}
+
 int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                    const bdg_stage1_opts* o, bdg_stage1_result* res)
 {
-    if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !out_path || !header || !o || !res) return BDG_E_ARG;
+    if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !header || !o || !res) return BDG_E_ARG;
     bdg_ctx* const c0 = ctxs[0];
+    const bool tags = (o->whitelist & BDG_STAGE1_TAGS) != 0;
+    if (!out_path && !tags) return BDG_E_ARG;
     // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
-    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA)) != 0;
+    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS)) != 0;
     const bool chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
     if (chim && !trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_CHIMERA needs BDG_STAGE1_TRIM");
+    if (tags && !trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS needs BDG_STAGE1_TRIM");
+    if (tags && wl_on) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS takes no whitelist mode (the cell is the tag)");
+    if (tags && o->tag_reads && (!o->tag_cell_rank || !o->tag_cell_has || (o->tag_molecule && !o->tag_mol_reads)))
+        return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS: null array");
     const bool corr = wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT);
     // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT, those behind it with BDG_STAGE1_TRIM)
-    memset(res, 0, chim ? sizeof(*res) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
+    memset(res, 0, tags ? sizeof(*res) : chim ? offsetof(bdg_stage1_result, tags_no_cell) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
     if (chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
@@ -593,21 +650,25 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     int rc = open_reader(in_path, o, per_ctx * n_ctx + 2 * fthreads + 4, &P.ing, L.err);
     if (rc) { if (corr) corr_end(); return bdg_fail(c0, rc, L.err); }
     L.ing = P.ing;
-    P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (P.fd < 0) { bdg_ingest_close(P.ing); if (corr) corr_end(); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
+    const Tags all_tags = tags ? Tags{ o->tag_cell_rank, o->tag_cell_has, o->tag_molecule, o->tag_mol_reads, o->tag_keep } : Tags{};
+    if (tags) { P.tags = &all_tags; P.no_tsv = !out_path; }
+    if (!out_path) out_path = "(no TSV)";
+    if (!P.no_tsv) P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (P.fd < 0 && !P.no_tsv) { bdg_ingest_close(P.ing); if (corr) corr_end(); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
     P.header = header; P.header_every = o->header_every;
     if (wl_on) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
     if (trim) {
         P.fd_trim = ::open(o->trimmed_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
         if (P.fd_trim < 0) {
-            ::close(P.fd); bdg_ingest_close(P.ing); if (corr) corr_end();
+            if (P.fd >= 0) ::close(P.fd);
+            bdg_ingest_close(P.ing); if (corr) corr_end();
             return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
         }
         for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 1, o->tso_min_score);   // (checked above; off again below)
         if (chim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_chimera(ctxs[c], 1, o->chimera_max_ed);
     }
     bool ok_io = true;
-    if (!o->header_every) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
+    if (!o->header_every && !P.no_tsv) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
     std::vector<std::thread> fmt;
     for (uint32_t i = 0; i < fthreads; ++i) fmt.emplace_back(&Pipeline::format_loop, &P);
     std::thread writer(&Pipeline::write_loop, &P);
@@ -616,6 +677,9 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
 
     double t_fmt_wait = 0;
     rc = L.run([&](const Fly& f, std::vector<bdg_extract_rec>& recs) -> int {   // with the match's answer, to the formatters
+        // (the formatters index the tag arrays by the read's place in the input: no chunk may reach past them)
+        if (tags && f.g0 + f.ch.n > o->tag_reads)
+            return bdg_fail(f.ctx, BDG_E_ARG, "the input holds more reads than the " + std::to_string(o->tag_reads) + " the tag arrays hold");
         Job* j = new Job(f);
         j->r.recs.swap(recs);
         if (trim) {
@@ -659,10 +723,15 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         if (::close(P.fd_trim) != 0) P.trim_write_failed = true;
         res->trimmed_reads = P.trim_total.reads; res->trimmed_tso = P.trim_total.tso; res->trimmed_bases = P.trim_total.bases;
         if (chim) { res->chimera_cut = P.trim_total.cut; res->chimera_dropped = P.trim_total.dropped; res->chimera_bases = P.trim_total.cut_bases; }
+        if (tags) { res->tags_no_cell = P.trim_total.no_cell; res->tags_not_kept = P.trim_total.not_kept; }
     }
     // rows of the chunks before a failure are in the file, like in the reference's loop
-    if (rc == BDG_OK && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;
-    if (::close(P.fd) != 0) ok_io = false;
+    if (rc == BDG_OK && !P.no_tsv && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;
+    if (!P.no_tsv && ::close(P.fd) != 0) ok_io = false;
+    if (rc == BDG_OK && tags && L.g0 != o->tag_reads) {
+        rc = BDG_E_ARG;
+        L.err = "the input holds " + std::to_string(L.g0) + " reads, the tag arrays " + std::to_string(o->tag_reads);
+    }
     const double t_close0 = now_s();
     bdg_ingest_close(P.ing);
     if (getenv("BADGER_AMD_INGEST_DEBUG")) {

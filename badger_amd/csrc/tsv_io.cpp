@@ -347,9 +347,7 @@ int bdg_write_molecules(const bdg_idstore* ids, const uint32_t* rank, const uint
     auto umi_len = [](uint32_t c) -> uint64_t { return c == 0xFFFFFFFFu ? 1 : c >> 28; };
     auto put_umi = [](uint32_t c, char* o) -> char* {
         if (c == 0xFFFFFFFFu) { *o++ = '*'; return o; }
-        const uint32_t L = c >> 28;
-        for (uint32_t j = 0; j < L; ++j) *o++ = "ACGT"[(c >> (2 * (L - 1 - j))) & 3u];
-        return o;
+        return put_umi_code(o, c);
     };
     const bool ok = write_id_rows(fd, "readID\tbarcode\tUMI\tmolecule", ids, n, 16 + 1 + 15 + 1 + 15,
                                   [&](uint64_t i) -> uint64_t {

@@ -204,7 +204,168 @@ void k_umi_reads(const uint32_t* __restrict__ read_slot, uint64_t n, const unsig
     mol[i] = s == UMI_NONE ? UMI_NONE : (uint32_t)keys[root[s]];
 }
 
+// ---- one representative read per molecule (bdg_molecule_reps_dev; the rule in badger_amd/molecule_reads.py) ----
+//   length   k_cdna_len: per read of a collected chunk the cDNA bases bdg_format_trimmed_chimera would write, from the chunk's trim
+//            and chimera records while they are still on the device (bdg_extract_keep_cdna).
+//   insert   k_mol_insert: k_umi_insert's open-addressing form over the key cell ordinal << 32 | molecule code.  Per slot a read
+//            count and an election word cdna_len << 32 | (0xFFFFFFFF - i), taken by a 64-bit atomic maximum: the longest cDNA, the
+//            earliest read at equal lengths; a read without cDNA is counted and does not bid.  A large molecule is one address
+//            (§4.0), so the lanes of a wave that name the same key first combine their count and their maximum (the peers of
+//            wave_count); the leader of each group alone probes the table and issues one add and one maximum, and hands the slot
+//            to its peers.
+//   results  k_mol_reads: per read its slot's count, and rep where the slot's election word names the read.
+__global__ __launch_bounds__(256)
+void k_cdna_len(const bdg_trim_rec* __restrict__ trim, const bdg_chimera_rec* __restrict__ chim, uint32_t n, uint32_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bdg_trim_rec t = trim[i];
+    uint32_t len = 0;
+    if (t.flags & BDG_TRIM_EMIT) {
+        int32_t end = t.cdna_end;
+        if (chim) { const bdg_chimera_rec c = chim[i]; if (c.flags & BDG_CHIMERA_HIT) end = c.cut; }
+        if (end > t.cdna_start) len = (uint32_t)(end - t.cdna_start);
+    }
+    out[i] = len;
+}
+
+__global__ __launch_bounds__(256)
+void k_mol_clear(unsigned long long* __restrict__ keys, unsigned long long* __restrict__ elect, uint32_t* __restrict__ cnt, uint32_t P)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s < P) { keys[s] = EMPTY; elect[s] = 0ull; cnt[s] = 0u; }
+}
+
+// the slot of key k, claimed if nobody had (never full: twice as many slots as reads)
+__device__ __forceinline__ uint32_t mol_slot(unsigned long long* __restrict__ keys, unsigned long long k, uint32_t mask)
+{
+    for (uint32_t h = slot_of(k, mask);; h = (h + 1u) & mask) {
+        const unsigned long long old = atomicCAS(&keys[h], EMPTY, k);
+        if (old == EMPTY || old == k) return h;
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v)
+{
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long o = __shfl_xor(v, d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <bool AGGREGATE>
+__global__ __launch_bounds__(256)
+void k_mol_insert(const uint32_t* __restrict__ rank, const uint8_t* __restrict__ has, const uint32_t* __restrict__ mol,
+                  const uint32_t* __restrict__ cdna_len, uint64_t n, const uint32_t* __restrict__ cells, uint32_t ncells,
+                  unsigned long long* __restrict__ keys, unsigned long long* __restrict__ elect, uint32_t* __restrict__ cnt,
+                  uint32_t mask, uint32_t* __restrict__ read_slot)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256ull + threadIdx.x;      // (every lane stays for the wave's groups)
+    unsigned long long k = EMPTY, bid = 0;
+    if (i < n) {
+        const uint32_t code = mol[i];
+        const uint32_t c = has[i] && code != UMI_NONE ? cell_of(rank[i], cells, ncells) : UMI_NONE;
+        if (c != UMI_NONE) {
+            k = (unsigned long long)c << 32 | code;
+            const uint32_t len = cdna_len[i];
+            if (len) bid = (unsigned long long)len << 32 | (0xFFFFFFFFu - (uint32_t)i);
+        }
+    }
+    uint32_t slot = UMI_NONE;
+    if (!AGGREGATE) {
+        if (k != EMPTY) {
+            slot = mol_slot(keys, k, mask);
+            atomicAdd(&cnt[slot], 1u);
+            if (bid) atomicMax(&elect[slot], bid);
+        }
+    } else {
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t my_leader = lane, gcount = 0;
+        unsigned long long gmax = 0;
+        unsigned long long todo = __ballot(k != EMPTY);
+        while (todo) {
+            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+            const unsigned long long lk = __shfl(k, (int)leader);
+            const bool mine = k == lk;                                    // (EMPTY is no key: a lane outside todo never matches)
+            const unsigned long long peers = __ballot(mine);
+            unsigned long long m = bid;                                   // (alone: the leader's own bid)
+            if (peers & (peers - 1ull)) m = wave_max64(mine ? bid : 0ull);
+            if (mine) my_leader = leader;
+            if (lane == leader) { gcount = (uint32_t)__popcll(peers); gmax = m; }
+            todo &= ~peers;
+        }
+        if (k != EMPTY && my_leader == lane) {                            // the leaders of all groups probe side by side
+            slot = mol_slot(keys, k, mask);
+            atomicAdd(&cnt[slot], gcount);
+            if (gmax) atomicMax(&elect[slot], gmax);
+        }
+        slot = __shfl(slot, (int)my_leader);
+    }
+    if (i < n) read_slot[i] = slot;
+}
+
+__global__ __launch_bounds__(256)
+void k_mol_reads(const uint32_t* __restrict__ read_slot, const uint32_t* __restrict__ cdna_len, uint64_t n,
+                 const unsigned long long* __restrict__ elect, const uint32_t* __restrict__ cnt,
+                 uint8_t* __restrict__ rep, uint32_t* __restrict__ mol_reads)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256ull + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = read_slot[i];
+    uint32_t m = 0;
+    uint8_t r = 0;
+    if (s != UMI_NONE) {
+        m = cnt[s];
+        const uint32_t len = cdna_len[i];
+        r = len && elect[s] == ((unsigned long long)len << 32 | (0xFFFFFFFFu - (uint32_t)i));
+    }
+    mol_reads[i] = m;
+    rep[i] = r;
+}
+
 }  // namespace
+
+int bdg_cdna_len_launch(bdg_ctx* ctx, const bdg_trim_rec* d_trim, const bdg_chimera_rec* d_chim, uint32_t n, uint32_t* d_out)
+{
+    if (n == 0) return BDG_OK;
+    ScopedKernelTimer tm(ctx, "k_cdna_len");
+    hipLaunchKernelGGL(k_cdna_len, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_trim, d_chim, n, d_out);
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int bdg_molecule_reps_launch(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_mol, const uint32_t* d_len,
+                             uint64_t n, const uint32_t* d_cells, uint32_t ncells, uint8_t* d_rep, uint32_t* d_mol_reads)
+{
+    if (n == 0) return BDG_OK;
+    hipStream_t st = ctx->stream;
+    uint64_t P = 1024;                                                    // bdg_umi_dedup_launch's table: two slots per read
+    while (P < 2 * n) P <<= 1;
+    if (P > (1ull << 31)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the molecule table takes (2^30)");
+    // workspace: keys u64 [P] | election words u64 [P] | counts u32 [P] | read slots u32 [n]
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->u_ws, 20 * (size_t)P + 4 * (size_t)n + 256))) return rc;
+    auto* keys = static_cast<unsigned long long*>(ctx->u_ws.p);
+    auto* elect = keys + P;
+    auto* cnt = reinterpret_cast<uint32_t*>(elect + P);
+    auto* read_slot = cnt + P;
+    const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
+    {
+        ScopedKernelTimer tm(ctx, "k_mol_insert");
+        hipLaunchKernelGGL(k_mol_clear, dim3(gp), dim3(256), 0, st, keys, elect, cnt, (uint32_t)P);
+        if (ctx->mol_aggregate)
+            hipLaunchKernelGGL(k_mol_insert<true>, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_mol, d_len, n, d_cells, ncells, keys, elect, cnt, mask, read_slot);
+        else
+            hipLaunchKernelGGL(k_mol_insert<false>, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_mol, d_len, n, d_cells, ncells, keys, elect, cnt, mask, read_slot);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_mol_reads");
+        hipLaunchKernelGGL(k_mol_reads, dim3(gn), dim3(256), 0, st, read_slot, d_len, n, elect, cnt, d_rep, d_mol_reads);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
 
 int bdg_umi_pack_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
                         uint32_t* d_out)

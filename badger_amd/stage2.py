@@ -426,15 +426,17 @@ class Stage2:
         rank, got = d_rank.to_host(n), d_got.to_host(n)
         for d in (d_assigned, d_has) + (() if keep_reads else (d_rank, d_got)):
             d.free()
+        self._read_cells = (rank, got)                                # (for read_tags_from_device)
         if keep_reads:
             self._reads = {"ctx": ctx, "d_rank": d_rank, "d_got": d_got, "rank": rank, "got": got,
                            "cells": np.unique(assigned[has])}        # every barcode a read can be assigned to, ascending ranks
         _native.write_assignments(ids, rank, got, out + "_output_file.tsv")
 
-    def umi_dedup_from_device(self, ids, out, umi_len, umi_dist):
+    def umi_dedup_from_device(self, ids, out, umi_len, umi_dist, keep_molecules=False):
         """--umi_dedup: the reads' molecules inside their cells (bdg_umi_dedup_dev over the cells output_file_from_device left
         on the device and the UMI codes the context kept), <out>_molecules.tsv written natively, <out>_cells.tsv (one line per
-        cell with a read, ascending barcode).  Returns the number of molecules."""
+        cell with a read, ascending barcode).  Returns the number of molecules.  keep_molecules: the cells and molecules stay on
+        the device for read_tags_from_device."""
         r, self._reads = self._reads, None
         ctx, cells = r["ctx"], np.ascontiguousarray(r["cells"], dtype=np.uint32)
         ptr, n = ctx.kept_umis()
@@ -449,7 +451,10 @@ class Stage2:
         umi = np.zeros(n, np.uint32)
         if n:
             ctx._check(ctx.lib.bdg_mem_to_host(ctx.h, umi.ctypes.data, ptr, umi.nbytes))
-        for d in (d_cells, d_mol, d_cnt, r["d_rank"], r["d_got"]):
+        if keep_molecules:
+            self._molecules = {"ctx": ctx, "d_rank": r["d_rank"], "d_got": r["d_got"], "d_cells": d_cells, "nc": nc, "d_mol": d_mol,
+                               "mol": mol, "n": n}
+        for d in (d_cnt,) + (() if keep_molecules else (d_cells, d_mol, r["d_rank"], r["d_got"])):
             d.free()
         _native.write_molecules(ids, r["rank"], r["got"], umi, mol, out + "_molecules.tsv")
         seen = np.flatnonzero(cnt[:, 0] > 0) if nc else np.zeros(0, np.intp)
@@ -459,6 +464,29 @@ class Stage2:
             f.write("".join("%s\t%d\t%d\t%d\t%d\n" % ((names[j],) + tuple(int(x) for x in cnt[seen[j]]))
                             for j in sorted(range(len(seen)), key=names.__getitem__)))
         return int(cnt[:, 3].sum()) if nc else 0
+
+    def read_tags_from_device(self, molecule_reads=False):
+        """--tagged_reads: the per-read arrays of the second pass (_native.stage1_run's tags): every read's cell from
+        output_file_from_device and - after umi_dedup_from_device(keep_molecules=True) - its molecule and the molecule's read
+        count; each molecule's read elected on the device from the cDNA lengths the context kept (bdg_molecule_reps_dev), and
+        with molecule_reads the filter that keeps only those."""
+        rank, got = self._read_cells
+        tags = {"cell_rank": rank, "cell_has": got}
+        m, self._molecules = getattr(self, "_molecules", None), None
+        if m is None:
+            return tags
+        ctx, n = m["ctx"], m["n"]
+        ptr, n_len = ctx.kept_cdna()
+        if n_len != n:
+            raise RuntimeError("%d cDNA lengths kept for %d reads" % (n_len, n))
+        d_rep = _native.DeviceArray(ctx, max(n, 1), np.uint8)
+        d_cnt = _native.DeviceArray(ctx, max(n, 1), np.uint32)
+        if n:
+            ctx.molecule_reps_dev(m["d_rank"], m["d_got"], m["d_mol"], ptr, n, m["d_cells"], m["nc"], d_rep, d_cnt)
+        tags.update(molecule=m["mol"], mol_reads=d_cnt.to_host(n), keep=d_rep.to_host(n) if molecule_reads else None)
+        for d in (d_rep, d_cnt, m["d_rank"], m["d_got"], m["d_mol"], m["d_cells"]):
+            d.free()
+        return tags
 
     def release_device(self):
         dev = getattr(self, "_dev", None)

@@ -213,6 +213,16 @@ int  bdg_extract_keep_umis(bdg_ctx* ctx, int on);
 int  bdg_keep_observed_umis(bdg_ctx* ctx, const uint32_t* codes, uint64_t n);
 /* The kept UMI codes: device pointer (valid until the next collect / keep call) and count */
 int  bdg_kept_umis(bdg_ctx* ctx, const uint32_t** d_umis, uint64_t* n);
+/* cDNA lengths beside the kept records (stage 2's --tagged_reads with --umi_dedup).  on != 0 (only while bdg_extract_set_trim is on,
+ * BDG_E_ARG otherwise; with or without bdg_extract_set_chimera): while records are kept, every collected chunk also appends one
+ * uint32_t per read, the number of cDNA bases bdg_format_trimmed_chimera would write for it: 0 without BDG_TRIM_EMIT, otherwise
+ * end - cdna_start with end = cut for a read with BDG_CHIMERA_HIT and cdna_end otherwise (so 0 when cut == cdna_start).  A small
+ * kernel fills them from the chunk's bdg_trim_rec / bdg_chimera_rec on the device, behind them on the same stream, inside
+ * bdg_extract_collect: a chunk that collect ran again after a queue overflow gives the values of the rerun.  4 bytes per read.
+ * Starts an empty array; bdg_extract_keep_records(ctx, 0) frees it; turning the trim off turns this off. */
+int  bdg_extract_keep_cdna(bdg_ctx* ctx, int on);
+/* The kept cDNA lengths: device pointer (valid until the next collect / keep call) and count */
+int  bdg_kept_cdna(bdg_ctx* ctx, const uint32_t** d_len, uint64_t* n);
 
 /* ---- trimmed cDNA (stage 1's --trimmed_reads; the rule restated in badger_amd/trim.py) ------------------------------ */
 /* Per read, from its extraction record and its bases: where the cDNA lies between the polyT tail and the template-switch oligo
@@ -386,6 +396,18 @@ int64_t bdg_format_trimmed(const bdg_ingest_chunk* chunk, const bdg_extract_rec*
 int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
                                    const bdg_chimera_rec* chim, const uint32_t* best_idx, const uint16_t* n_ties,
                                    const uint32_t* wl, uint32_t nw, char* out, uint64_t cap, uint64_t counts[6]);
+/* bdg_format_trimmed_chimera without whitelist arrays, with stage 2's answers for the chunk's reads (arrays of chunk->n entries):
+ * cell_rank / cell_has the read's cell (bdg_assign_reads_dev), molecule (may be NULL) its molecule's UMI code (bdg_umi_dedup_dev,
+ * 0xFFFFFFFF: none), mol_reads (read only with molecule) the reads of that molecule (bdg_molecule_reps_dev), keep (may be NULL) a
+ * filter.  A record is written when bdg_format_trimmed_chimera would write it (chim may be NULL), cell_has[i] != 0, and keep is NULL
+ * or keep[i] != 0.  Header fields in order: CR / UR / ST as before, then "\tCB:Z:" the cell spelled out, then - where molecule is
+ * given and is not 0xFFFFFFFF - "\tUB:Z:" the molecule spelled out as bdg_write_molecules spells it "\tRN:i:" mol_reads, then the CH
+ * field last.  counts (may be NULL): records written, bases written, then - among the reads bdg_format_trimmed_chimera would
+ * write - reads left out for having no cell, and reads with a cell left out by keep.  Sizing as bdg_format_rows. */
+int64_t bdg_format_trimmed_tags(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
+                                const bdg_chimera_rec* chim, const uint32_t* cell_rank, const uint8_t* cell_has,
+                                const uint32_t* molecule, const uint32_t* mol_reads, const uint8_t* keep,
+                                char* out, uint64_t cap, uint64_t counts[4]);
 
 /* Stage 1 from file to file in native threads: readers -> GPU(s) -> row formatters -> one writer, rows in input order
  * (extract_raw_barcodes.py:162-173 process_single_thread, :176-261 process_in_parallel).  Chunk k goes to context k mod
@@ -412,6 +434,14 @@ int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* chunk, const bdg_extr
  * read chimera_max_ed or write the three bdg_stage1_result.chimera_* counts.  The TSV and every other output but the trimmed
  * file are the same bytes as without the bit. */
 #define BDG_STAGE1_CHIMERA       0x800u
+/* bdg_stage1_opts.whitelist, valid only together with BDG_STAGE1_TRIM and without a whitelist mode (BDG_E_ARG otherwise): the
+ * trimmed file is written through bdg_format_trimmed_tags from five per-read arrays in host memory, indexed by the read's place in
+ * the input (tag_cell_rank and tag_cell_has are required; tag_molecule with tag_mol_reads, and tag_keep, may be NULL), tag_reads
+ * entries each.  Only with this bit does the library read those fields or write bdg_stage1_result.tags_no_cell / tags_not_kept
+ * (trimmed_reads / trimmed_bases are counts[0] / counts[1] of bdg_format_trimmed_tags then; the caller's structs reach to the last
+ * field).  out_path may be NULL with this bit: no TSV is written.  The run fails with BDG_E_ARG, and says so, when the input
+ * yields another number of reads than tag_reads.  Stage 2's second pass over its input (--tagged_reads). */
+#define BDG_STAGE1_TAGS          0x1000u
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -441,6 +471,13 @@ typedef struct bdg_stage1_opts {
     /* read only with BDG_STAGE1_CHIMERA */
     uint32_t chimera_max_ed;      /* 0 .. BDG_CHIMERA_MAX_ED_MAX (BDG_CHIMERA_MAX_ED_DEFAULT) */
     uint32_t reserved_chimera;
+    /* read only with BDG_STAGE1_TAGS */
+    const uint32_t* tag_cell_rank;
+    const uint8_t*  tag_cell_has;
+    const uint32_t* tag_molecule;     /* may be NULL */
+    const uint32_t* tag_mol_reads;    /* NULL only with tag_molecule NULL */
+    const uint8_t*  tag_keep;         /* may be NULL */
+    uint64_t tag_reads;
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -457,6 +494,7 @@ typedef struct bdg_stage1_result {
     uint64_t whitelist_corrected;             /* written only with BDG_STAGE1_WL_CORRECT (or BDG_STAGE1_TRIM, then 0 without the correction): rows of status exact or corrected */
     uint64_t trimmed_reads, trimmed_tso, trimmed_bases;   /* written only with BDG_STAGE1_TRIM: counts[3] of bdg_format_trimmed over the run */
     uint64_t chimera_cut, chimera_dropped, chimera_bases;   /* written only with BDG_STAGE1_CHIMERA: counts[3 .. 5] of bdg_format_trimmed_chimera */
+    uint64_t tags_no_cell, tags_not_kept;   /* written only with BDG_STAGE1_TAGS: counts[2 .. 3] of bdg_format_trimmed_tags */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
@@ -626,6 +664,25 @@ int  bdg_touched_count_dev(bdg_ctx* ctx, const uint32_t* d_ea, const uint32_t* d
 int  bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
                        const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
                        uint32_t* d_molecule, uint32_t* d_cell_counts);
+/* One representative read per molecule, and every molecule's read count (the rule restated in badger_amd/molecule_reads.py;
+ * integers only).  Per read i (0 <= i < n): d_rank / d_has its cell (bdg_assign_reads_dev), d_molecule its molecule's code
+ * (bdg_umi_dedup_dev; 0xFFFFFFFF: none), d_cdna_len the cDNA bases bdg_format_trimmed_chimera would write for it (bdg_kept_cdna).
+ *   member    read i belongs to molecule (cell, molecule) when d_has[i] != 0, its rank is among d_cells (n_cells ascending ranks)
+ *             and d_molecule[i] != 0xFFFFFFFF.
+ *   count     d_mol_reads[i] = the number of reads of i's molecule, whatever their cdna_len; 0 for a read in no molecule.
+ *   election  the representative of a molecule is its read with the largest (cdna_len, -i) among its reads with cdna_len > 0: the
+ *             longest cDNA, the earliest read at equal lengths; a molecule without such a read has none.  d_rep[i] (uint8) = 1
+ *             for representatives, 0 elsewhere.
+ * Both are plain sums and maxima over sets: the order of evaluation cannot change them.  Works in the open-addressing table of
+ * bdg_umi_dedup_dev (the context's workspace, two slots per read: key, election word cdna_len << 32 | (0xFFFFFFFF - i) taken by a
+ * 64-bit atomic maximum, read count; n <= 2^30); lanes of a wave that name the same molecule combine count and maximum before one
+ * lane issues the atomics.  Asynchronous. */
+int  bdg_molecule_reps_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_molecule,
+                           const uint32_t* d_cdna_len, uint64_t n, const uint32_t* d_cells, uint32_t n_cells,
+                           uint8_t* d_rep, uint32_t* d_mol_reads);
+/* FOR MEASUREMENTS AND TESTS ONLY: on = 0 makes every lane of bdg_molecule_reps_dev issue its own atomics (the answers are the
+ * same; one large molecule is then one address hit once per read); on != 0 is the default. */
+int  bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on);
 
 /* ---- stage 2's read-side plumbing on the host (badger.py:112-121,129; barcode_graph.py:388-410) -------------- */
 /* Read ids of a run, kept natively (12 bytes per read instead of a Python string each). */
