@@ -1,15 +1,10 @@
-// C ABI of libbadger_hip.so (include/badger_hip.h): context management, host-buffer
-// wrappers (H2D, launch, D2H) and the device-resident entry points.
+// C ABI of libbadger_hip.so (include/badger_hip.h): context and memory, streams and profiling, the one-shot host-buffer
+// wrappers (H2D, launch, D2H) and the device-resident entry points.  The pipelined chunks are in bdg_chunks.cpp.
 #include "bdg_launchers.hpp"
 #include "dj_codec.hpp"
-#include "host_util.hpp"
-
-#include <cstddef>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <mutex>
 
 static thread_local std::string g_err_noctx;
 
@@ -64,16 +59,6 @@ void bdg_timer_end(bdg_ctx* ctx, int id)
     ctx->timers[id].launches++;
 }
 
-// the barcode ranks of device records as a query of the nearest16 launchers: bc_rank of every record, the stride in words, and
-// "check the record's flags" (records without a 16-base ACGT barcode report no hit)
-struct RecsQuery { const uint32_t* q; uint32_t stride; int recs; };
-static RecsQuery recs_query(const void* d_recs)
-{
-    static_assert(sizeof(bdg_extract_rec) == 32 && offsetof(bdg_extract_rec, bc_rank) == 20 && offsetof(bdg_extract_rec, flags) == 27,
-                  "record layout the strided query reads");
-    return RecsQuery{ static_cast<const uint32_t*>(d_recs) + offsetof(bdg_extract_rec, bc_rank) / 4, sizeof(bdg_extract_rec) / 4, 1 };
-}
-
 int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan)
 {
     if (!ctx->deferred.pending) return BDG_OK;
@@ -97,12 +82,37 @@ int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan)
     return rc;
 }
 
-static int sync_all(bdg_ctx* ctx)
+int bdg_sync_all(bdg_ctx* ctx)
 {
     const int rcd = bdg_launch_deferred_match(ctx, false);
     if (rcd) return rcd;
     BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->aux_pending) { BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->aux_stream)); ctx->aux_pending = false; }
+    return BDG_OK;
+}
+
+int bdg_ensure_aux(bdg_ctx* ctx)
+{
+    if (!ctx->aux_stream) {
+        // (same priority as the main stream: measured against the lowest and the highest one, tools/ov_prio_probe.sh)
+        BDG_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
+        // (device-scope release: these events order kernels of two streams of one device; the default, a release to the
+        // system, writes the caches back and kept the next kernel waiting 12 us behind the scan)
+        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming | hipEventReleaseToDevice));
+        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_scan, hipEventDisableTiming | hipEventReleaseToDevice));
+        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[0], hipEventDisableTiming | hipEventReleaseToDevice));
+        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[1], hipEventDisableTiming | hipEventReleaseToDevice));
+    }
+    return BDG_OK;
+}
+
+// the first read whose offsets are out of order or that is too long for the kernels
+int bdg_check_offsets(bdg_ctx* ctx, const uint64_t* off, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
+        if (off[i + 1] - off[i] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "read longer than 2^26 bases");
+    }
     return BDG_OK;
 }
 
@@ -120,7 +130,7 @@ static int main_after_aux(bdg_ctx* ctx)
 
 static int collect_timers(bdg_ctx* ctx)
 {
-    int rc0 = sync_all(ctx);
+    int rc0 = bdg_sync_all(ctx);
     if (rc0) return rc0;
     for (auto& t : ctx->timers) {
         for (auto& pr : t.pending) {
@@ -218,11 +228,12 @@ int bdg_mem_alloc(bdg_ctx* ctx, uint64_t bytes, void** d_out)
     if (!ctx || !d_out) return BDG_E_ARG;
     *d_out = nullptr;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); return bdg_fail(ctx, BDG_E_NOMEM, "device allocation failed"); }
-    hipError_t e = hipMemsetAsync(p, 0, bytes ? bytes : 1, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(p); return bdg_fail(ctx, BDG_E_HIP, hipGetErrorString(e)); }
-    *d_out = p;
+    DevBuf b;                                                    // (the caller's from the hand-over on: bdg_mem_free)
+    if (hipMalloc(&b.p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return bdg_fail(ctx, BDG_E_NOMEM, "device allocation failed"); }
+    hipError_t e = hipMemsetAsync(b.p, 0, bytes ? bytes : 1, ctx->stream);
+    if (e != hipSuccess) return bdg_fail(ctx, BDG_E_HIP, hipGetErrorString(e));
+    *d_out = b.p;
+    b.p = nullptr;
     return BDG_OK;
 }
 
@@ -231,7 +242,7 @@ int bdg_mem_free(bdg_ctx* ctx, void* d_ptr)
     if (!ctx) return BDG_E_ARG;
     if (!d_ptr) return BDG_OK;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);                                      // work that still uses the buffer, on either stream
+    int rc = bdg_sync_all(ctx);                                      // work that still uses the buffer, on either stream
     if (rc) return rc;
     BDG_HIP_TRY(ctx, hipFree(d_ptr));
     return BDG_OK;
@@ -264,26 +275,11 @@ void bdg_free(bdg_ctx* ctx)
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
     if (ctx->ev_scan) (void)hipEventDestroy(ctx->ev_scan);
     for (hipEvent_t e : ctx->ev_aux) if (e) (void)hipEventDestroy(e);
-    DevBuf* bufs[] = { &ctx->x_lut, &ctx->x_polyt, &ctx->x_keys, &ctx->x_hits, &ctx->x_counters, &ctx->s_in0,
-                       &ctx->s_in1, &ctx->s_out0, &ctx->w_sorted, &ctx->w_orig, &ctx->w_pent, &ctx->w_delmap, &ctx->w_dv,
-                       &ctx->n_list, &ctx->n_counters, &ctx->n_coop, &ctx->g_sig, &ctx->g_tmp0, &ctx->g_tmp1, &ctx->g_cnt, &ctx->g_qj, &ctx->x_allrecs,
-                       &ctx->x_allumis, &ctx->x_allcdna, &ctx->u_ws, &ctx->corr.lists, &ctx->corr.support, &ctx->corr.out };
-    for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
-    for (auto& sl : ctx->slots) {
-        for (DevBuf* b : { &sl.d_bases, &sl.d_off, &sl.d_recs, &sl.d_match, &sl.d_trim, &sl.d_chim }) if (b->p) (void)hipFree(b->p);
-        if (sl.h_recs) (void)hipHostFree(sl.h_recs);
-        if (sl.h_trim) (void)hipHostFree(sl.h_trim);
-        if (sl.h_chim) (void)hipHostFree(sl.h_chim);
-        if (sl.h_match) (void)hipHostFree(sl.h_match);
-        if (sl.match_done) (void)hipEventDestroy(sl.match_done);
-        if (sl.h_off) (void)hipHostFree(sl.h_off);
-        if (sl.h_counters) (void)hipHostFree(sl.h_counters);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
+    for (auto& sl : ctx->slots) for (hipEvent_t e : { sl.done, sl.match_done }) if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->timers) for (auto& pr : t.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                                  // (its buffers free themselves, on the device set above)
 }
 
 const char* bdg_last_error(bdg_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err_noctx.c_str(); }
@@ -291,7 +287,7 @@ const char* bdg_last_error(bdg_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err
 int bdg_set_stream(bdg_ctx* ctx, void* hip_stream)
 {
     if (!ctx) return BDG_E_ARG;
-    int rc = sync_all(ctx);
+    int rc = bdg_sync_all(ctx);
     if (rc) return rc;
     ctx->stream = static_cast<hipStream_t>(hip_stream);      // NULL is the device's default (null) stream
     return BDG_OK;
@@ -300,35 +296,18 @@ int bdg_set_stream(bdg_ctx* ctx, void* hip_stream)
 int bdg_synchronize(bdg_ctx* ctx)
 {
     if (!ctx) return BDG_E_ARG;
-    return sync_all(ctx);
+    return bdg_sync_all(ctx);
 }
-
-static int ensure_aux(bdg_ctx* ctx);
 
 int bdg_set_overlap(bdg_ctx* ctx, int on)
 {
     if (!ctx) return BDG_E_ARG;
-    int rc = sync_all(ctx);
+    int rc = bdg_sync_all(ctx);
     if (rc) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (on) { const int rca = ensure_aux(ctx); if (rca) return rca; }
+    if (on) { const int rca = bdg_ensure_aux(ctx); if (rca) return rca; }
     ctx->aux_count = 0;
     ctx->overlap = on != 0;
-    return BDG_OK;
-}
-
-static int ensure_aux(bdg_ctx* ctx)
-{
-    if (!ctx->aux_stream) {
-        // (same priority as the main stream: measured against the lowest and the highest one, tools/ov_prio_probe.sh)
-        BDG_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-        // (device-scope release: these events order kernels of two streams of one device; the default, a release to the
-        // system, writes the caches back and kept the next kernel waiting 12 us behind the scan)
-        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming | hipEventReleaseToDevice));
-        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_scan, hipEventDisableTiming | hipEventReleaseToDevice));
-        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[0], hipEventDisableTiming | hipEventReleaseToDevice));
-        BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[1], hipEventDisableTiming | hipEventReleaseToDevice));
-    }
     return BDG_OK;
 }
 
@@ -409,14 +388,37 @@ int bdg_extract_counters(bdg_ctx* ctx, uint64_t out[9])
     return bdg_extract_counters_impl(ctx, out);
 }
 
-// the first read whose offsets are out of order or that is too long for the kernels
-static int check_offsets(bdg_ctx* ctx, const uint64_t* off, uint32_t n)
+// What the host-buffer wrappers of reads share: the offsets checked, the byte range they reference shipped rebased to 0
+// (s_in0, s_in1; queued on the context's stream) and out_bytes of s_out0 reserved.  `rel` lives until the caller has synchronised.
+struct StagedReads { std::vector<uint64_t> rel; const uint8_t* d_bases; const uint64_t* d_off; void* d_out; uint64_t total; };
+static int stage_reads(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, size_t out_bytes, StagedReads& s)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, "offsets must be non-decreasing");
-        if (off[i + 1] - off[i] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "read longer than 2^26 bases");
-    }
+    if (int rco = bdg_check_offsets(ctx, off, n)) return rco;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t lo = off[0];
+    s.total = off[n] - lo;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, s.total + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, out_bytes))) return rc;
+    s.rel.resize((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) s.rel[i] = off[i] - lo;
+    if (s.total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, s.total, hipMemcpyHostToDevice, ctx->stream));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, s.rel.data(), sizeof(uint64_t) * s.rel.size(), hipMemcpyHostToDevice, ctx->stream));
+    s.d_bases = static_cast<const uint8_t*>(ctx->s_in0.p);
+    s.d_off = static_cast<const uint64_t*>(ctx->s_in1.p);
+    s.d_out = ctx->s_out0.p;
     return BDG_OK;
+}
+
+// s_out0 of the trim and chimera wrappers for n reads: records | trim | chimera (if chim)
+struct ReadsLayout { bdg_extract_rec* recs; bdg_trim_rec* trim; bdg_chimera_rec* chim; size_t bytes; };
+static ReadsLayout reads_layout(void* base, size_t n, bool chim)
+{
+    const uintptr_t r = reinterpret_cast<uintptr_t>(base);                  // (base may be null: the size alone is asked for)
+    const uintptr_t t = r + sizeof(bdg_extract_rec) * n, c = t + sizeof(bdg_trim_rec) * n;
+    return ReadsLayout{ reinterpret_cast<bdg_extract_rec*>(r), reinterpret_cast<bdg_trim_rec*>(t),
+                        chim ? reinterpret_cast<bdg_chimera_rec*>(c) : nullptr, (size_t)(c - r + (chim ? sizeof(bdg_chimera_rec) * n : 0)) };
 }
 
 int bdg_extract_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
@@ -426,205 +428,26 @@ int bdg_extract_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     if (n == 0) return BDG_OK;
     if (!bases || !off || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
-    if (int rco = check_offsets(ctx, off, n)) return rco;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // ship only the byte range the offsets reference, rebased to 0
-    const uint64_t lo = off[0], hi = off[n], total = hi - lo;
+    StagedReads S;
     int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, total + 64))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
-    std::vector<uint64_t> rel((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
+    if ((rc = stage_reads(ctx, bases, off, n, sizeof(bdg_extract_rec) * (size_t)n, S))) return rc;
     hipStream_t st = ctx->stream;
-    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, total, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, st));
     // A queue overflow grows the workspace from what the failed pass could count; the hits re-queued by clusters are only
     // known once queue A is complete, so a second overflow is possible: loop (each pass at least 1.5 x the last one).
     for (int attempt = 0; attempt < 8; ++attempt) {
-        rc = bdg_extract_launch(ctx, static_cast<const uint8_t*>(ctx->s_in0.p), static_cast<const uint64_t*>(ctx->s_in1.p),
-                                n, total, umi_len, static_cast<bdg_extract_rec*>(ctx->s_out0.p));
+        rc = bdg_extract_launch(ctx, S.d_bases, S.d_off, n, S.total, umi_len, static_cast<bdg_extract_rec*>(S.d_out));
         if (rc) return rc;
         uint64_t bad = 0, nwin = 0;
         rc = bdg_extract_status_impl(ctx, &bad, &nwin);
         if (rc != BDG_E_CAPACITY) break;
     }
     if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->s_out0.p, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, S.d_out, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return BDG_OK;
 }
 
-// ---- pipelined chunks ---------------------------------------------------------
-static int pinned_reserve(bdg_ctx* ctx, void*& p, size_t& have, size_t want)
-{
-    if (want <= have && p) return BDG_OK;
-    if (p) { int rc = sync_all(ctx); if (rc) return rc; (void)hipHostFree(p); p = nullptr; have = 0; }
-    want += want / 4 + 4096;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return bdg_fail(ctx, BDG_E_NOMEM, "hipHostMalloc failed"); }
-    have = want;
-    return BDG_OK;
-}
-
-static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
-{
-    int rc = bdg_extract_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
-                                sl.n, sl.total, sl.umi_len, static_cast<bdg_extract_rec*>(sl.d_recs.p));
-    if (rc) return rc;
-    sl.qcap = ctx->x_hits_cap_launched;
-    hipStream_t st = ctx->stream;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_recs, sl.d_recs.p, sizeof(bdg_extract_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_counters, bdg_extract_counters_now(ctx), bdg_extract_counter_bytes(), hipMemcpyDeviceToHost, st));
-    if (sl.trim) {
-        // the chunk's trim behind its extraction (a rerun passes here again: the trim of placeholder records is overwritten)
-        if ((rc = bdg_trim_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
-                                  static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n, sl.trim_min_score, static_cast<bdg_trim_rec*>(sl.d_trim.p))))
-            return rc;
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_trim, sl.d_trim.p, sizeof(bdg_trim_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
-        if (sl.chim) {                                           // ... and the search of the trimmed intervals behind the trim
-            if ((rc = bdg_chimera_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
-                                         static_cast<const bdg_extract_rec*>(sl.d_recs.p), static_cast<const bdg_trim_rec*>(sl.d_trim.p), sl.n,
-                                         sl.chim_max_ed, static_cast<bdg_chimera_rec*>(sl.d_chim.p))))
-                return rc;
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_chim, sl.d_chim.p, sizeof(bdg_chimera_rec) * (size_t)sl.n, hipMemcpyDeviceToHost, st));
-        }
-    }
-    BDG_HIP_TRY(ctx, hipEventRecord(sl.done, st));
-    return BDG_OK;
-}
-
-// where bdg_extract_submit's time goes (BADGER_AMD_INGEST_DEBUG; printed by bdg_stage1_run).  Summed only when that variable is
-// set, and atomically: the ABI lets different host threads drive different contexts, and they all pass here.
-static std::atomic<double> g_submit_t[6];
-void bdg_submit_times(double t[5]) { for (int i = 0; i < 5; ++i) t[i] = g_submit_t[i].load(); }
-static const bool g_submit_debug = getenv("BADGER_AMD_INGEST_DEBUG") != nullptr;
-static inline void submit_add(int i, double v) { double o = g_submit_t[i].load(std::memory_order_relaxed); while (!g_submit_t[i].compare_exchange_weak(o, o + v, std::memory_order_relaxed)) {} }
-
-int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len)
-{
-    const double T0 = now_s();
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "slot still in flight: collect it first");
-    if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
-    sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
-    sl.trim = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
-    sl.chim = ctx->trim_on && ctx->chim_on; sl.chim_max_ed = ctx->chim_max_ed;
-    if (n == 0) { sl.busy = true; return BDG_OK; }
-    if (int rco = check_offsets(ctx, off, n)) return rco;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t lo = off[0], total = off[n] - lo;
-    sl.total = total;
-    int rc;
-    if ((rc = bdg_reserve(ctx, sl.d_bases, total + 64))) return rc;
-    if ((rc = bdg_reserve(ctx, sl.d_off, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = bdg_reserve(ctx, sl.d_recs, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
-    if ((rc = pinned_reserve(ctx, sl.h_recs, sl.h_recs_bytes, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
-    if ((rc = pinned_reserve(ctx, sl.h_off, sl.h_off_bytes, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if (sl.trim) {
-        if ((rc = bdg_reserve(ctx, sl.d_trim, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
-        if ((rc = pinned_reserve(ctx, sl.h_trim, sl.h_trim_bytes, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
-    }
-    if (sl.chim) {
-        if ((rc = bdg_reserve(ctx, sl.d_chim, sizeof(bdg_chimera_rec) * (size_t)n))) return rc;
-        if ((rc = pinned_reserve(ctx, sl.h_chim, sl.h_chim_bytes, sizeof(bdg_chimera_rec) * (size_t)n))) return rc;
-    }
-    if (!sl.h_counters) {
-        if (hipHostMalloc(&sl.h_counters, bdg_extract_counter_bytes(), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); sl.h_counters = nullptr; return bdg_fail(ctx, BDG_E_NOMEM, "hipHostMalloc failed");
-        }
-    }
-    if (!sl.done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    const double T1 = now_s();
-    uint64_t* rel = static_cast<uint64_t*>(sl.h_off);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
-    hipStream_t st = ctx->stream;
-    const double T2 = now_s();
-    // (one copy on one stream runs at the link's rate here: 56.6 GB/s for 32 MB from pinned memory, tools/hip_first_calls.py; two
-    // halves on two streams, which gained 10 % in round 2, gain nothing any more)
-    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_bases.p, bases + lo, total, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_off.p, rel, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
-    const double T3 = now_s();
-    if ((rc = slot_enqueue(ctx, sl))) return rc;
-    sl.busy = true;
-    const double T4 = now_s();
-    if (g_submit_debug) { submit_add(0, T1 - T0); submit_add(1, T2 - T1); submit_add(2, T3 - T2); submit_add(3, T4 - T3); submit_add(4, 1.0); }
-    return BDG_OK;
-}
-
-// room for `add` bytes behind the `have` bytes a kept array (records, UMIs) holds: grown by copying, earlier chunks stay
-static int kept_grow(bdg_ctx* ctx, DevBuf& b, size_t have, size_t add, size_t min_bytes)
-{
-    if (have + add <= b.bytes) return BDG_OK;
-    DevBuf nb;
-    int rc;
-    if ((rc = bdg_reserve(ctx, nb, std::max((have + add) * 2, min_bytes)))) return rc;
-    if (have) BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.p, b.p, have, hipMemcpyDeviceToDevice, ctx->stream));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (b.p) (void)hipFree(b.p);
-    b = nb;
-    return BDG_OK;
-}
-
-int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
-{
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
-    sl.busy = false;
-    if (sl.n == 0) return BDG_OK;
-    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = BDG_OK;
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        BDG_HIP_TRY(ctx, hipEventSynchronize(sl.done));
-        uint64_t bad = 0, nwin = 0;
-        rc = bdg_extract_judge_host(ctx, sl.h_counters, sl.qcap, &bad, &nwin);
-        if (rc != BDG_E_CAPACITY) break;
-        // this chunk overflowed a queue: run it again (its input is still on the device) behind whatever is queued
-        int rc2 = slot_enqueue(ctx, sl);
-        if (rc2) return rc2;
-        sl.reran = true;
-    }
-    if (rc) return rc;
-    memcpy(out, sl.h_recs, sizeof(bdg_extract_rec) * (size_t)sl.n);
-    if (ctx->keep_records) {
-        // append the chunk's records to the device-side array
-        const size_t have = sizeof(bdg_extract_rec) * (size_t)ctx->x_allrecs_n, add = sizeof(bdg_extract_rec) * (size_t)sl.n;
-        if ((rc = kept_grow(ctx, ctx->x_allrecs, have, add, size_t(64) << 20))) return rc;
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(ctx->x_allrecs.p) + have, sl.d_recs.p, add, hipMemcpyDeviceToDevice, ctx->stream));
-        if (ctx->keep_umis) {
-            // the chunk's UMIs, packed from its bases while they are still here
-            if ((rc = kept_grow(ctx, ctx->x_allumis, 4 * (size_t)ctx->x_allumis_n, 4 * (size_t)sl.n, size_t(8) << 20))) return rc;
-            if ((rc = bdg_umi_pack_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p),
-                                          static_cast<const bdg_extract_rec*>(sl.d_recs.p), sl.n,
-                                          static_cast<uint32_t*>(ctx->x_allumis.p) + ctx->x_allumis_n)))
-                return rc;
-            ctx->x_allumis_n += sl.n;
-        }
-        if (ctx->keep_cdna) {
-            // the chunk's cDNA lengths, from the trim and chimera records of the pass that counted (a rerun wrote them again)
-            if (!sl.trim) return bdg_fail(ctx, BDG_E_ARG, "cDNA lengths are kept but the slot's chunk was submitted without a trim");
-            if ((rc = kept_grow(ctx, ctx->x_allcdna, 4 * (size_t)ctx->x_allcdna_n, 4 * (size_t)sl.n, size_t(8) << 20))) return rc;
-            if ((rc = bdg_cdna_len_launch(ctx, static_cast<const bdg_trim_rec*>(sl.d_trim.p),
-                                          sl.chim ? static_cast<const bdg_chimera_rec*>(sl.d_chim.p) : nullptr, sl.n,
-                                          static_cast<uint32_t*>(ctx->x_allcdna.p) + ctx->x_allcdna_n)))
-                return rc;
-            ctx->x_allcdna_n += sl.n;
-        }
-        ctx->x_allrecs_n += sl.n;
-    }
-    return BDG_OK;
-}
-
 // ---- trimmed cDNA ---------------------------------------------------------------
-static int check_tso_min_score(bdg_ctx* ctx, uint32_t v)
-{
-    return v < 8 || v > 30 ? bdg_fail(ctx, BDG_E_ARG, "tso_min_score out of range (8 .. 30)") : BDG_OK;
-}
-
 int bdg_trim_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
                        const bdg_extract_rec* d_recs, uint32_t tso_min_score, bdg_trim_rec* d_out)
 {
@@ -643,57 +466,19 @@ int bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint
     if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
     if (n == 0) return BDG_OK;
     if (!bases || !off || !recs || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (int rco = check_offsets(ctx, off, n)) return rco;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t lo = off[0], total = off[n] - lo;
-    const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, trim_bytes = sizeof(bdg_trim_rec) * (size_t)n;
+    StagedReads S;
     int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, total + 64))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_bytes + trim_bytes))) return rc;         // records | results
-    std::vector<uint64_t> rel((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
+    if ((rc = stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, false).bytes, S))) return rc;
     hipStream_t st = ctx->stream;
-    char* const d_recs = static_cast<char*>(ctx->s_out0.p);
-    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, total, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, rec_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = bdg_trim_launch(ctx, static_cast<const uint8_t*>(ctx->s_in0.p), static_cast<const uint64_t*>(ctx->s_in1.p),
-                              reinterpret_cast<const bdg_extract_rec*>(d_recs), n, tso_min_score, reinterpret_cast<bdg_trim_rec*>(d_recs + rec_bytes))))
-        return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_recs + rec_bytes, trim_bytes, hipMemcpyDeviceToHost, st));
+    const ReadsLayout L = reads_layout(S.d_out, n, false);
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(L.recs, recs, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_trim_launch(ctx, S.d_bases, S.d_off, L.recs, n, tso_min_score, L.trim))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, L.trim, sizeof(bdg_trim_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
     return BDG_OK;
 }
 
-int bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (on) if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
-    ctx->trim_on = on != 0;
-    ctx->trim_min_score = on ? tso_min_score : 0;
-    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; ctx->keep_cdna = false; }   // (nothing to search or to measure without the trim)
-    return BDG_OK;
-}
-
-int bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out)
-{
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "collect the slot's records first (bdg_extract_collect)");
-    if (!sl.trim) return bdg_fail(ctx, BDG_E_ARG, "the slot's chunk was submitted without a trim (bdg_extract_set_trim)");
-    if (sl.n == 0) return BDG_OK;
-    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    memcpy(out, sl.h_trim, sizeof(bdg_trim_rec) * (size_t)sl.n);  // (the copy was queued in front of the event collect waited for)
-    return BDG_OK;
-}
-
 // ---- chimeric reads --------------------------------------------------------------
-static int check_chimera_max_ed(bdg_ctx* ctx, uint32_t v)
-{
-    return v > BDG_CHIMERA_MAX_ED_MAX ? bdg_fail(ctx, BDG_E_ARG, "chimera max_ed out of range (0 .. 6)") : BDG_OK;
-}
-
 int bdg_chimera_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n,
                           const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim, uint32_t max_ed, bdg_chimera_rec* d_out)
 {
@@ -712,271 +497,16 @@ int bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     if (int rcs = check_chimera_max_ed(ctx, max_ed)) return rcs;
     if (n == 0) return BDG_OK;
     if (!bases || !off || !recs || !trim || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (int rco = check_offsets(ctx, off, n)) return rco;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t lo = off[0], total = off[n] - lo;
-    const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, trim_bytes = sizeof(bdg_trim_rec) * (size_t)n;
-    const size_t chim_bytes = sizeof(bdg_chimera_rec) * (size_t)n;
+    StagedReads S;
     int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, total + 64))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_bytes + trim_bytes + chim_bytes))) return rc;   // records | trim | results
-    std::vector<uint64_t> rel((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
+    if ((rc = stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, true).bytes, S))) return rc;
     hipStream_t st = ctx->stream;
-    char* const d_recs = static_cast<char*>(ctx->s_out0.p);
-    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, total, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, rel.data(), sizeof(uint64_t) * rel.size(), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, rec_bytes, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs + rec_bytes, trim, trim_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = bdg_chimera_launch(ctx, static_cast<const uint8_t*>(ctx->s_in0.p), static_cast<const uint64_t*>(ctx->s_in1.p),
-                                 reinterpret_cast<const bdg_extract_rec*>(d_recs), reinterpret_cast<const bdg_trim_rec*>(d_recs + rec_bytes), n,
-                                 max_ed, reinterpret_cast<bdg_chimera_rec*>(d_recs + rec_bytes + trim_bytes))))
-        return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_recs + rec_bytes + trim_bytes, chim_bytes, hipMemcpyDeviceToHost, st));
+    const ReadsLayout L = reads_layout(S.d_out, n, true);
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(L.recs, recs, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(L.trim, trim, sizeof(bdg_trim_rec) * (size_t)n, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_chimera_launch(ctx, S.d_bases, S.d_off, L.recs, L.trim, n, max_ed, L.chim))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, L.chim, sizeof(bdg_chimera_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
-    return BDG_OK;
-}
-
-int bdg_extract_set_chimera(bdg_ctx* ctx, int on, uint32_t max_ed)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (on) {
-        if (!ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "the chimera search needs the trim (bdg_extract_set_trim)");
-        if (int rcs = check_chimera_max_ed(ctx, max_ed)) return rcs;
-    }
-    ctx->chim_on = on != 0;
-    ctx->chim_max_ed = on ? max_ed : 0;
-    return BDG_OK;
-}
-
-int bdg_extract_collect_chimera(bdg_ctx* ctx, uint32_t slot, bdg_chimera_rec* out)
-{
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "collect the slot's records first (bdg_extract_collect)");
-    if (!sl.chim) return bdg_fail(ctx, BDG_E_ARG, "the slot's chunk was submitted without a chimera search (bdg_extract_set_chimera)");
-    if (sl.n == 0) return BDG_OK;
-    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    memcpy(out, sl.h_chim, sizeof(bdg_chimera_rec) * (size_t)sl.n);  // (the copy was queued in front of the event collect waited for)
-    return BDG_OK;
-}
-
-// lists of the correction store (Correct::lists) from read `at` on
-static CorrLists corr_lists(bdg_ctx* ctx, uint64_t at) { return corr_lists(ctx->corr.lists.p, ctx->corr.cap, at); }
-
-// room for `need` reads of kept lists; what is kept moves along (behind the matches that wrote it, on the auxiliary stream)
-static int corr_grow(bdg_ctx* ctx, uint64_t need)
-{
-    bdg_ctx::Correct& c = ctx->corr;
-    if (need <= c.cap) return BDG_OK;
-    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * c.cap), 1ull << 20);
-    void* p = nullptr;
-    const size_t bytes = CORR_LISTS_READ_BYTES * cap + 64;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return bdg_fail(ctx, BDG_E_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes) for the kept candidate lists");
-    }
-    if (c.lists.p) {
-        const CorrLists o = corr_lists(ctx, 0), nb = corr_lists(p, cap, 0);
-        hipStream_t st = ctx->aux_stream ? ctx->aux_stream : ctx->stream;
-        if (c.n) {
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.idx8, o.idx8, sizeof(uint32_t) * CORR_K * c.n, hipMemcpyDeviceToDevice, st));
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.ed8, o.ed8, CORR_K * c.n, hipMemcpyDeviceToDevice, st));
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(nb.nw, o.nw, sizeof(uint16_t) * c.n, hipMemcpyDeviceToDevice, st));
-        }
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        BDG_HIP_TRY(ctx, hipFree(c.lists.p));
-    }
-    c.lists.p = p; c.lists.bytes = bytes; c.cap = cap;
-    return BDG_OK;
-}
-
-static int queue_slot_match(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t max_ed, uint32_t k)
-{
-    int rc;
-    if ((rc = ensure_aux(ctx))) return rc;
-    const size_t bytes = match_layout(nullptr, sl.n, k).bytes;
-    if ((rc = bdg_reserve(ctx, sl.d_match, bytes + 64))) return rc;
-    if ((rc = pinned_reserve(ctx, sl.h_match, sl.h_match_bytes, bytes + 64))) return rc;
-    if (!sl.match_done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.match_done, hipEventDisableTiming));
-    BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->aux_stream, sl.done, 0));      // behind the chunk's extraction
-    ctx->launch_stream = ctx->aux_stream;
-    ctx->aux_pending = true;
-    const RecsQuery Q = recs_query(sl.d_recs.p);
-    const MatchLayout M = match_layout(sl.d_match.p, sl.n, k);
-    if (sl.match_corr) {
-        // correction: the k = 8 lists go to the run's store and stay there; the support kernel adds the chunk's exact hits and
-        // gathers the k slots the host asked for (k = 0: the best-hit layout) into d_match.  A chunk matched again after
-        // its extraction was rerun adds nothing twice: the first match saw the overflow's placeholder records, none usable.
-        const CorrLists L = corr_lists(ctx, sl.corr_at);
-        rc = bdg_nearest16_topk_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, CORR_K, L.idx8, L.ed8, L.nw, M.ties);
-        if (!rc) rc = bdg_correct_support_launch(ctx, ctx->aux_stream, L.idx8, L.ed8, L.nw, sl.n, k,
-                                                 static_cast<uint32_t*>(ctx->corr.support.p), M.idx, M.ed, M.n_within);
-    } else if (k) {
-        rc = bdg_nearest16_topk_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, k, M.idx, M.ed, M.n_within, M.ties);
-    } else {
-        rc = bdg_nearest16_launch(ctx, Q.q, Q.stride, Q.recs, sl.n, max_ed, M.idx, M.ed, M.ties);
-    }
-    ctx->launch_stream = nullptr;
-    if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_match, sl.d_match.p, bytes, hipMemcpyDeviceToHost, ctx->aux_stream));
-    BDG_HIP_TRY(ctx, hipEventRecord(sl.match_done, ctx->aux_stream));
-    sl.match_max_ed = max_ed;
-    sl.match_k = k;
-    sl.match_queued = true;
-    return BDG_OK;
-}
-
-int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k)
-{
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (!sl.busy) return bdg_fail(ctx, BDG_E_ARG, "nothing submitted to this slot");
-    const bool corr = ctx->corr.on;
-    if (corr && max_ed > 3) return bdg_fail(ctx, BDG_E_ARG, "whitelist correction needs max_ed <= 3");
-    int rc = corr ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, CORR_K)
-                  : k ? bdg_nearest16_topk_check(ctx, sl.n, max_ed, k) : bdg_nearest16_check(ctx, sl.n, max_ed);
-    sl.match_corr = corr;
-    if (rc || sl.n == 0) return rc;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (corr) {
-        if ((rc = corr_grow(ctx, ctx->corr.n + sl.n))) return rc;
-        sl.corr_at = ctx->corr.n;
-        ctx->corr.n += sl.n;
-    }
-    return queue_slot_match(ctx, sl, max_ed, k);
-}
-
-int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
-                                uint32_t* cand_idx, uint8_t* cand_ed)
-{
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
-    if (sl.n == 0) return BDG_OK;
-    if (!sl.match_queued) return bdg_fail(ctx, BDG_E_ARG, "no match queued for this slot");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if (sl.reran && (rc = queue_slot_match(ctx, sl, sl.match_max_ed, sl.match_k))) return rc;     // the records changed: match them again
-    sl.reran = false;
-    BDG_HIP_TRY(ctx, hipEventSynchronize(sl.match_done));
-    sl.match_queued = false;
-    const size_t n = sl.n, k = sl.match_k;
-    const MatchLayout H = match_layout(sl.h_match, n, k);
-    if (k && (!cand_idx || !cand_ed)) return bdg_fail(ctx, BDG_E_ARG, "a top-k match needs the candidate arrays");
-    memcpy(n_ties, H.ties, sizeof(uint16_t) * n);
-    if (k) {
-        memcpy(cand_idx, H.idx, sizeof(uint32_t) * n * k); memcpy(cand_ed, H.ed, n * k);
-        for (size_t i = 0; i < n; ++i) { best_idx[i] = H.idx[i * k]; best_ed[i] = H.ed[i * k]; }
-    } else {
-        memcpy(best_idx, H.idx, sizeof(uint32_t) * n); memcpy(best_ed, H.ed, n);
-    }
-    return BDG_OK;
-}
-
-int bdg_correct_begin(bdg_ctx* ctx)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->corr.support, 4 * (size_t)ctx->w_n))) return rc;
-    BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->corr.support.p, 0, 4 * (size_t)ctx->w_n, ctx->stream));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->corr.n = 0;
-    ctx->corr.on = true;
-    return BDG_OK;
-}
-
-int bdg_correct_support_to_host(bdg_ctx* ctx, uint32_t* support)
-{
-    if (!ctx || !support || !ctx->corr.support.p) return BDG_E_ARG;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpy(support, ctx->corr.support.p, 4 * (size_t)ctx->w_n, hipMemcpyDeviceToHost));
-    return BDG_OK;
-}
-
-int bdg_correct_support_from_host(bdg_ctx* ctx, const uint32_t* support)
-{
-    if (!ctx || !support || !ctx->corr.support.p) return BDG_E_ARG;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpy(ctx->corr.support.p, support, 4 * (size_t)ctx->w_n, hipMemcpyHostToDevice));
-    return BDG_OK;
-}
-
-int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits, uint32_t pmin, void* out)
-{
-    if (!ctx || (ctx->corr.n && !out) || !ctx->corr.support.p) return BDG_E_ARG;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);
-    if (rc || ctx->corr.n == 0) return rc;
-    const uint64_t n = ctx->corr.n;
-    if ((rc = bdg_reserve(ctx, ctx->corr.out, CORR_OUT_READ_BYTES * n + 64))) return rc;
-    const CorrLists L = corr_lists(ctx, 0);
-    if ((rc = bdg_correct_resolve_launch(ctx, ctx->stream, L.idx8, L.ed8, L.nw, n, static_cast<const uint32_t*>(ctx->corr.support.p),
-                                         max_ed, bits, pmin, ctx->corr.out.p)))
-        return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->corr.out.p, CORR_OUT_READ_BYTES * n, hipMemcpyDeviceToHost, ctx->stream));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return BDG_OK;
-}
-
-int bdg_correct_end(bdg_ctx* ctx)
-{
-    if (!ctx) return BDG_E_ARG;
-    ctx->corr.on = false;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = sync_all(ctx);
-    if (rc) return rc;
-    for (DevBuf* b : { &ctx->corr.lists, &ctx->corr.out }) if (b->p) { BDG_HIP_TRY(ctx, hipFree(b->p)); *b = DevBuf(); }
-    ctx->corr.n = ctx->corr.cap = 0;
-    return BDG_OK;
-}
-
-int bdg_extract_keep_records(bdg_ctx* ctx, int on)
-{
-    if (!ctx) return BDG_E_ARG;
-    ctx->keep_records = on != 0;
-    ctx->x_allrecs_n = 0;
-    ctx->x_allumis_n = 0;
-    ctx->x_allcdna_n = 0;
-    if (!on) for (DevBuf* b : { &ctx->x_allrecs, &ctx->x_allumis, &ctx->x_allcdna }) if (b->p) {
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(b->p);
-        *b = DevBuf();
-    }
-    return BDG_OK;
-}
-
-int bdg_extract_keep_umis(bdg_ctx* ctx, int on)
-{
-    if (!ctx) return BDG_E_ARG;
-    ctx->keep_umis = on != 0;
-    ctx->x_allumis_n = 0;
-    return BDG_OK;
-}
-
-int bdg_extract_keep_cdna(bdg_ctx* ctx, int on)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (on && !ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "cDNA lengths need the trim (bdg_extract_set_trim)");
-    ctx->keep_cdna = on != 0;
-    ctx->x_allcdna_n = 0;
-    return BDG_OK;
-}
-
-int bdg_kept_cdna(bdg_ctx* ctx, const uint32_t** d_len, uint64_t* n)
-{
-    if (!ctx || !d_len || !n) return BDG_E_ARG;
-    *d_len = static_cast<const uint32_t*>(ctx->x_allcdna.p);
-    *n = ctx->x_allcdna_n;
     return BDG_OK;
 }
 
@@ -999,30 +529,6 @@ int bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on)
     return BDG_OK;
 }
 
-int bdg_keep_observed_umis(bdg_ctx* ctx, const uint32_t* codes, uint64_t n)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (n && !codes) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n != ctx->x_allrecs_n) return bdg_fail(ctx, BDG_E_ARG, "UMI codes and kept records differ in number");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ctx->x_allumis_n = 0;
-    if (n == 0) return BDG_OK;
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->x_allumis, 4 * (size_t)n))) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->x_allumis.p, codes, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->x_allumis_n = n;
-    return BDG_OK;
-}
-
-int bdg_kept_umis(bdg_ctx* ctx, const uint32_t** d_umis, uint64_t* n)
-{
-    if (!ctx || !d_umis || !n) return BDG_E_ARG;
-    *d_umis = static_cast<const uint32_t*>(ctx->x_allumis.p);
-    *n = ctx->x_allumis_n;
-    return BDG_OK;
-}
-
 int bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
                       const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
                       uint32_t* d_molecule, uint32_t* d_cell_counts)
@@ -1034,45 +540,6 @@ int bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has
     if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return bdg_umi_dedup_launch(ctx, d_rank, d_has, d_umi, n, d_cells, n_cells, umi_len, umi_dist, d_molecule, d_cell_counts);
-}
-
-int bdg_keep_observed(bdg_ctx* ctx, const uint32_t* rank, const uint8_t* usable, uint64_t n)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (n && (!rank || !usable)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = bdg_extract_keep_records(ctx, 1);                       // (an empty array; what was kept before is dropped, UMIs too)
-    if (rc || n == 0) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->x_allrecs, sizeof(bdg_extract_rec) * n))) return rc;
-    // the two host arrays through the scratch buffer (pageable memory: the copies return when the data has left it)
-    if ((rc = bdg_reserve(ctx, ctx->g_tmp1, 5 * n + 16))) return rc;
-    uint32_t* const d_rank = static_cast<uint32_t*>(ctx->g_tmp1.p);
-    uint8_t* const d_usable = reinterpret_cast<uint8_t*>(d_rank + n);
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_rank, rank, 4 * n, hipMemcpyHostToDevice, ctx->stream));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_usable, usable, n, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = bdg_records_of_observed_launch(ctx, d_rank, d_usable, n, static_cast<bdg_extract_rec*>(ctx->x_allrecs.p)))) return rc;
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));             // (the scratch buffer is free for the next user)
-    ctx->x_allrecs_n = n;
-    return BDG_OK;
-}
-
-int bdg_kept_records_to_host(bdg_ctx* ctx, bdg_extract_rec* out, uint64_t cap)
-{
-    if (!ctx || (cap && !out)) return BDG_E_ARG;
-    const uint64_t n = ctx->x_allrecs_n < cap ? ctx->x_allrecs_n : cap;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n) BDG_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->x_allrecs.p, sizeof(bdg_extract_rec) * n, hipMemcpyDeviceToHost, ctx->stream));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return BDG_OK;
-}
-
-int bdg_kept_records(bdg_ctx* ctx, const bdg_extract_rec** d_recs, uint64_t* n)
-{
-    if (!ctx || !d_recs || !n) return BDG_E_ARG;
-    *d_recs = static_cast<const bdg_extract_rec*>(ctx->x_allrecs.p);
-    *n = ctx->x_allrecs_n;
-    return BDG_OK;
 }
 
 // ---- nearest ----------------------------------------------------------------
@@ -1163,7 +630,7 @@ int bdg_nearest16(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const uint32_t* 
 
 uint32_t bdg_nearest16_overflow_count(bdg_ctx* ctx)
 {
-    if (!ctx || hipSetDevice(ctx->device) != hipSuccess || sync_all(ctx) != BDG_OK) return 0;
+    if (!ctx || hipSetDevice(ctx->device) != hipSuccess || bdg_sync_all(ctx) != BDG_OK) return 0;
     uint32_t n = 0;
     return bdg_nearest16_overflow_read(ctx, &n) == BDG_OK ? n : 0;
 }
@@ -1251,7 +718,7 @@ int bdg_nearest16_correct(bdg_ctx* ctx, const uint32_t* q, uint32_t nq, const ui
     std::vector<uint8_t> out((size_t)nq * CORR_OUT_READ_BYTES);
     auto run = [&]() -> int {
         int r;
-        if ((r = corr_grow(ctx, nq))) return r;
+        if ((r = bdg_correct_grow(ctx, nq))) return r;
         ctx->corr.n = nq;
         if ((r = bdg_reserve(ctx, ctx->s_in0, sizeof(uint32_t) * (size_t)nq))) return r;
         BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, q, sizeof(uint32_t) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));

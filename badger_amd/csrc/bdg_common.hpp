@@ -13,10 +13,19 @@
 
 #include "../../include/badger_hip.h"
 
-struct DevBuf {
+// Memory its holder owns: move-only, freed when the holder goes (bdg_free deletes the context on its device).
+template <hipError_t (*Free)(void*)> struct OwnedBuf {
     void*  p = nullptr;
     size_t bytes = 0;
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    OwnedBuf& operator=(OwnedBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+    ~OwnedBuf() { reset(); }
+    void reset() { if (p) (void)Free(p); p = nullptr; bytes = 0; }
 };
+using DevBuf = OwnedBuf<hipFree>;          // device memory, grown by bdg_reserve
+using PinnedBuf = OwnedBuf<hipHostFree>;   // pinned host memory, grown by pinned_reserve (bdg_chunks.cpp)
+struct Mirror { DevBuf d; PinnedBuf h; };  // a device array and its pinned copy
 
 struct KTimer {
     std::string name;
@@ -60,35 +69,31 @@ struct bdg_ctx {
     uint64_t x_hits_cap_fixed = 0;     // bdg_extract_set_queue_capacity (0 = automatic)
     int x_strand_rule = 0;             // bdg_extract_set_strand_rule
     uint64_t x_hits_cap_launched = 0;  // capacity the last launch ran with
-    void* x_counters_host = nullptr;   // pinned mirror
     // host-buffer staging
     DevBuf s_in0, s_in1, s_out0;
     // pipelined chunks (bdg_extract_submit / collect)
     struct Slot {
-        DevBuf d_bases, d_off, d_recs;
-        void* h_recs = nullptr; size_t h_recs_bytes = 0;     // pinned
-        void* h_off = nullptr;  size_t h_off_bytes = 0;      // pinned, offsets rebased to 0
-        void* h_counters = nullptr;                          // pinned snapshot of the batch's counters
+        DevBuf d_bases, d_off;
+        PinnedBuf h_off;                                     // offsets rebased to 0
+        PinnedBuf h_counters;                                // snapshot of the batch's counters
+        Mirror recs;                                         // bdg_extract_rec [n]
         hipEvent_t done = nullptr;
         uint32_t n = 0, umi_len = 0; uint64_t total = 0, qcap = 0;
         bool busy = false;
         bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
-        // trim of the chunk (bdg_extract_set_trim): behind the extraction on the same stream, results copied to h_trim
-        DevBuf d_trim;                                       // bdg_trim_rec [n]
-        void* h_trim = nullptr; size_t h_trim_bytes = 0;     // pinned
-        bool trim = false; uint32_t trim_min_score = 0;      // what the chunk was submitted with
-        // chimera search of the chunk (bdg_extract_set_chimera): behind the trim, results copied to h_chim
-        DevBuf d_chim;                                       // bdg_chimera_rec [n]
-        void* h_chim = nullptr; size_t h_chim_bytes = 0;     // pinned
-        bool chim = false; uint32_t chim_max_ed = 0;         // what the chunk was submitted with
-        // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`, results copied to h_match
-        DevBuf d_match;                                      // match_layout(n, match_k)
-        void* h_match = nullptr; size_t h_match_bytes = 0;   // pinned, same layout
+        // trim of the chunk (bdg_extract_set_trim): behind the extraction on the same stream
+        Mirror trim;                                         // bdg_trim_rec [n]
+        bool trim_on = false; uint32_t trim_min_score = 0;   // what the chunk was submitted with
+        // chimera search of the chunk (bdg_extract_set_chimera): behind the trim
+        Mirror chim;                                         // bdg_chimera_rec [n]
+        bool chim_on = false; uint32_t chim_max_ed = 0;      // what the chunk was submitted with
+        // whitelist match of the chunk (bdg_stage1_run): on aux_stream behind `done`
+        Mirror match;                                        // match_layout(n, match_k)
         hipEvent_t match_done = nullptr;
         uint32_t match_max_ed = 0, match_k = 0;
         bool match_queued = false;
         bool match_corr = false;                             // correction on: the match runs at k = 8 into corr.lists at corr_at,
-        uint64_t corr_at = 0;                                // and d_match holds the compact block of match_k slots (0: best hit)
+        uint64_t corr_at = 0;                                // and match holds the compact block of match_k slots (0: best hit)
     } slots[BDG_SLOTS];
     // ---- whitelist correction of a stage-1 run (correct_kernels.hip, bdg_stage1_run with BDG_STAGE1_WL_CORRECT)
     struct Correct {
@@ -100,15 +105,10 @@ struct bdg_ctx {
     } corr;
     bool trim_on = false; uint32_t trim_min_score = 0;       // bdg_extract_set_trim: for the submits that follow
     bool chim_on = false; uint32_t chim_max_ed = 0;          // bdg_extract_set_chimera: likewise (only while trim_on)
-    // records of every collected chunk, kept on the device in submission order (bdg_extract_keep_records)
-    bool keep_records = false;
-    DevBuf x_allrecs; uint64_t x_allrecs_n = 0;
-    // with them (bdg_extract_keep_umis), every read's UMI packed into 32 bits (umi_kernels.hip), in the same order
-    bool keep_umis = false;
-    DevBuf x_allumis; uint64_t x_allumis_n = 0;
-    // ... and (bdg_extract_keep_cdna, only while trim_on) every read's cDNA length, from the chunk's trim and chimera records
-    bool keep_cdna = false;
-    DevBuf x_allcdna; uint64_t x_allcdna_n = 0;
+    // Arrays kept on the device over every collected chunk, in submission order: the records (bdg_extract_keep_records); with
+    // them every read's UMI packed into 32 bits (bdg_extract_keep_umis, umi_kernels.hip) and, only while trim_on, every read's
+    // cDNA length from the chunk's trim and chimera records (bdg_extract_keep_cdna)
+    struct Kept { bool on = false; DevBuf b; uint64_t n = 0; } kept_recs, kept_umis, kept_cdna;
     DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read;
                          // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
@@ -163,8 +163,8 @@ struct bdg_ctx {
 int bdg_reserve(bdg_ctx* ctx, DevBuf& b, size_t bytes);
 const void* bdg_extract_counters_now(const bdg_ctx* ctx);   // the counters of the extraction launched last (extract_kernels.hip)
 int bdg_launch_deferred_match(bdg_ctx* ctx, bool behind_scan);   // overlap mode: queue the waiting whitelist match now (bdg_abi.cpp)
-extern "C" void bdg_submit_times(double t[5]);   // where bdg_extract_submit's time went (bdg_abi.cpp, BADGER_AMD_INGEST_DEBUG)
-// Stage 1 with a whitelist (bdg_abi.cpp): queue the match of the chunk just submitted to `slot` on the auxiliary stream, behind
+extern "C" void bdg_submit_times(double t[5]);   // where bdg_extract_submit's time went (bdg_chunks.cpp, BADGER_AMD_INGEST_DEBUG)
+// Stage 1 with a whitelist (bdg_chunks.cpp): queue the match of the chunk just submitted to `slot` on the auxiliary stream, behind
 // its extraction, so that it runs beside the next chunk's; after bdg_extract_collect of the slot, wait for it and take the
 // results (a chunk that collect had to run again is matched again first).  With the k nearest entries (k = 0: the best-hit
 // match): best_idx / best_ed are slot 0 of the k, n_ties the best-hit call's tie count; cand_idx / cand_ed [n * k] the slots
@@ -172,7 +172,7 @@ extern "C" void bdg_submit_times(double t[5]);   // where bdg_extract_submit's t
 extern "C" int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k);
 extern "C" int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
                                            uint32_t* cand_idx, uint8_t* cand_ed);
-// Whitelist correction over a run of slot matches (bdg_abi.cpp): begin (on) clears the support array and the kept lists and makes
+// Whitelist correction over a run of slot matches (bdg_chunks.cpp): begin (on) clears the support array and the kept lists and makes
 // every later bdg_slot_match_topk of the context a k = 8 match whose lists stay on the device, plus a support kernel; the host
 // still gets k slots.  support_to_host / support_from_host: the context's support array, to be summed over the contexts of a run.
 // resolve: the rule over every kept list, results (layout of Correct::out) to host memory; end frees the lists.
@@ -183,7 +183,7 @@ extern "C" int bdg_correct_resolve(bdg_ctx* ctx, uint32_t max_ed, uint32_t bits,
 extern "C" int bdg_correct_end(bdg_ctx* ctx);
 
 // ---- layouts of the blocks the host and the kernels share ----
-// The match results of n reads (Slot::d_match / h_match, the staging of bdg_nearest16 and bdg_nearest16_topk):
+// The match results of n reads (Slot::match, the staging of bdg_nearest16 and bdg_nearest16_topk):
 //   idx u32 [n * max(k, 1)] | n_ties u16 [n] (if ties) | n_within u16 [n] (if k) | ed u8 [n * max(k, 1)]
 struct MatchLayout { uint32_t* idx; uint16_t* ties; uint16_t* n_within; uint8_t* ed; size_t bytes; };
 static inline MatchLayout match_layout(void* base, size_t n, size_t k, bool ties = true)

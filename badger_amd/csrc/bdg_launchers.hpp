@@ -1,7 +1,9 @@
-// The launchers in the kernel translation units, as bdg_abi.cpp calls them.
+// The launchers in the kernel translation units, as bdg_abi.cpp and bdg_chunks.cpp call them, and what those two share.
 #pragma once
 
 #include "bdg_common.hpp"
+
+#include <cstddef>
 
 // extract_kernels.hip
 int bdg_extract_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint64_t, uint32_t, bdg_extract_rec*);
@@ -49,3 +51,32 @@ int bdg_molecule_reps_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const ui
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // chimera_kernels.hip
 int bdg_chimera_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, const bdg_trim_rec*, uint32_t, uint32_t, bdg_chimera_rec*);
+
+// ---- host only: shared by bdg_abi.cpp and bdg_chunks.cpp ----
+int bdg_sync_all(bdg_ctx*);                                   // bdg_abi.cpp: a waiting deferred match queued, then both streams idle
+int bdg_ensure_aux(bdg_ctx*);                                 // bdg_abi.cpp: the auxiliary stream and its events exist
+int bdg_check_offsets(bdg_ctx*, const uint64_t*, uint32_t);   // bdg_abi.cpp: the first read out of order or too long for the kernels
+int bdg_correct_grow(bdg_ctx*, uint64_t need);                // bdg_chunks.cpp: room for `need` reads in the correction store
+
+// lists of the correction store (Correct::lists) from read `at` on
+static inline CorrLists corr_lists(bdg_ctx* ctx, uint64_t at) { return corr_lists(ctx->corr.lists.p, ctx->corr.cap, at); }
+
+// the barcode ranks of device records as a query of the nearest16 launchers: bc_rank of every record, the stride in words, and
+// "check the record's flags" (records without a 16-base ACGT barcode report no hit)
+struct RecsQuery { const uint32_t* q; uint32_t stride; int recs; };
+static inline RecsQuery recs_query(const void* d_recs)
+{
+    static_assert(sizeof(bdg_extract_rec) == 32 && offsetof(bdg_extract_rec, bc_rank) == 20 && offsetof(bdg_extract_rec, flags) == 27,
+                  "record layout the strided query reads");
+    return RecsQuery{ static_cast<const uint32_t*>(d_recs) + offsetof(bdg_extract_rec, bc_rank) / 4, sizeof(bdg_extract_rec) / 4, 1 };
+}
+
+static inline int check_tso_min_score(bdg_ctx* ctx, uint32_t v)
+{
+    return v < 8 || v > 30 ? bdg_fail(ctx, BDG_E_ARG, "tso_min_score out of range (8 .. 30)") : BDG_OK;
+}
+
+static inline int check_chimera_max_ed(bdg_ctx* ctx, uint32_t v)
+{
+    return v > BDG_CHIMERA_MAX_ED_MAX ? bdg_fail(ctx, BDG_E_ARG, "chimera max_ed out of range (0 .. 6)") : BDG_OK;
+}

@@ -1,4 +1,4 @@
-// Small host-side helpers shared by bdg_abi.cpp, stage1.cpp and tsv_io.cpp: the clock, text output of numbers and barcodes,
+// Small host-side helpers shared by bdg_chunks.cpp, stage1.cpp and tsv_io.cpp: the clock, text output of numbers and barcodes,
 // write(2) to the end.
 #pragma once
 
