@@ -22,6 +22,11 @@ EDGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("dist", "<u4")])
 TRIM_DTYPE = np.dtype([("cdna_start", "<i4"), ("cdna_end", "<i4"), ("tail_len", "<i2"), ("tso_score", "i1"), ("flags", "u1")])
 TRIM_EMIT, TRIM_TSO = 1, 2
 TSO_MIN_SCORE_DEFAULT = 20
+# the 5' layout (bdg_extract_set_layout; the rules in badger_amd/trim5p.py)
+LAYOUT_3P, LAYOUT_5P = 0, 1
+TRIM_SENSE, TRIM_ANCHOR, TRIM_NO_ANCHOR = 4, 8, 128
+TSO5_MAX_ED_DEFAULT, TSO5_MAX_ED_MAX = 2, 4
+TSO5_MIN_SCORE_DEFAULT, TSO5_MIN_SCORE_MAX = 16, 25
 # bdg_chimera_rec: an internal adapter inside a read's cDNA (bdg_chimera_batch; the rule in badger_amd/chimera.py)
 CHIMERA_DTYPE = np.dtype([("cut", "<i4"), ("hit_pos", "<i4"), ("hit_ed", "u1"), ("hit_kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
 CHIMERA_HIT = 1
@@ -41,7 +46,7 @@ EXPORTS = [
     "bdg_mem_alloc", "bdg_mem_free", "bdg_mem_to_host", "bdg_mem_from_host", "bdg_set_stream", "bdg_synchronize", "bdg_set_overlap",
     "bdg_profile_enable", "bdg_profile_only", "bdg_profile_reset", "bdg_profile_read",
     "bdg_extract_batch", "bdg_extract_batch_dev", "bdg_extract_status", "bdg_extract_counters", "bdg_extract_set_queue_capacity",
-    "bdg_extract_set_strand_rule",
+    "bdg_extract_set_strand_rule", "bdg_extract_set_layout", "bdg_trim_set_5p",
     "bdg_nearest16", "bdg_whitelist_load", "bdg_nearest16_dev", "bdg_nearest16_recs_dev", "bdg_nearest16_set_algo", "bdg_nearest16_index_bytes",
     "bdg_nearest16_overflow_count",
     "bdg_nearest16_topk", "bdg_nearest16_topk_dev", "bdg_nearest16_topk_recs_dev", "bdg_format_rows_wlk",
@@ -144,6 +149,11 @@ class Stage1ResultTags(Stage1ResultChimera):
     _fields_ = [("tags_no_cell", C.c_uint64), ("tags_not_kept", C.c_uint64)]
 
 
+class Stage1Result5p(Stage1ResultTags):
+    """bdg_stage1_result with the count written only with STAGE1_TRIM on contexts in LAYOUT_5P (whatever the other bits)"""
+    _fields_ = [("trimmed_no_anchor", C.c_uint64)]
+
+
 class BadgerHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libbadger_hip error %d: %s" % (code, msg))
@@ -208,6 +218,8 @@ def load():
     L.bdg_extract_counters.argtypes = [vp, C.POINTER(u64)]
     L.bdg_extract_set_queue_capacity.argtypes = [vp, u64]
     L.bdg_extract_set_strand_rule.argtypes = [vp, C.c_int]
+    L.bdg_extract_set_layout.argtypes = [vp, C.c_int]
+    L.bdg_trim_set_5p.argtypes = [vp, u32, u32]
     L.bdg_nearest16.argtypes = [vp, vp, u32, vp, u32, u32, vp, vp, vp]
     L.bdg_whitelist_load.argtypes = [vp, vp, u32]
     L.bdg_nearest16_dev.argtypes = [vp, vp, u32, u32, vp, vp, vp]
@@ -519,6 +531,15 @@ class Context:
         """STRAND_RULE_DEFAULT (find_barcode_umi) or STRAND_RULE_NO_POLYA (find_barcode_umi_no_polya) for the launches that follow"""
         self._check(self.lib.bdg_extract_set_strand_rule(self.h, rule))
 
+    def extract_set_layout(self, layout):
+        """LAYOUT_3P (the default) or LAYOUT_5P for the launches that follow, on every extraction path (bdg_extract_set_layout)"""
+        self._check(self.lib.bdg_extract_set_layout(self.h, layout))
+
+    def trim_set_5p(self, umi_len, tso5_max_ed=TSO5_MAX_ED_DEFAULT):
+        """what the 5' trimming rule takes beyond tso_min_score (bdg_trim_set_5p): the UMI length for trim_batch / trim_batch_dev,
+        the switch oligo's edit bound for those and for the pipelined trim"""
+        self._check(self.lib.bdg_trim_set_5p(self.h, umi_len, tso5_max_ed))
+
     def extract_counters(self):
         out = (C.c_uint64 * 9)()
         self._check(self.lib.bdg_extract_counters(self.h, out))
@@ -770,7 +791,7 @@ def chunk_reads(ch):
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
                corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT,
-               chimera_max_ed=None, tags=None):
+               chimera_max_ed=None, tags=None, tso5_max_ed=None):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
@@ -781,7 +802,9 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     reads are cut at their first internal adapter (BDG_STAGE1_CHIMERA); the result then has chimera_cut, chimera_dropped and
     chimera_bases.  tags (with trimmed_path, without whitelist; out_path may then be None: no TSV): a dict of per-read numpy arrays
     over the whole input - cell_rank, cell_has and optionally molecule with mol_reads, and keep - whose answers go into the headers of
-    the trimmed file (BDG_STAGE1_TAGS, bdg_format_trimmed_tags); the result then has tags_no_cell and tags_not_kept."""
+    the trimmed file (BDG_STAGE1_TAGS, bdg_format_trimmed_tags); the result then has tags_no_cell and tags_not_kept.
+    tso5_max_ed (with trimmed_path; the caller has put every context into LAYOUT_5P): the switch oligo's edit bound of the 5'
+    trimming rule; the result is then a Stage1Result5p whatever else is asked for, and has trimmed_no_anchor."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
@@ -801,17 +824,17 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         if len({len(a) for a in held if a is not None}) != 1 or (held[2] is None) != (held[3] is None):
             raise ValueError("stage1_run: the tag arrays differ in length, or molecule comes without mol_reads")
         o = Stage1OptsTags(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                           os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, 0,
+                           os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, tso5_max_ed or 0,
                            chimera_max_ed if chimera_max_ed is not None else 0, 0,
                            *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]))
         res = Stage1ResultTags()
     elif chimera_max_ed is not None:
         o = Stage1OptsChimera(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                              os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, 0, chimera_max_ed, 0)
+                              os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, tso5_max_ed or 0, chimera_max_ed, 0)
         res = Stage1ResultChimera()
     elif trimmed_path is not None:
         o = Stage1OptsTrim(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                           os.fsencode(trimmed_path), tso_min_score, 0)
+                           os.fsencode(trimmed_path), tso_min_score, tso5_max_ed or 0)
         res = Stage1ResultTrim()
     elif correct:
         o = Stage1OptsCorrect(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path))
@@ -819,6 +842,8 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     else:
         o = Stage1Opts(*args)
         res = Stage1Result()
+    if tso5_max_ed is not None and trimmed_path is not None:
+        res = Stage1Result5p()
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path) if out_path is not None else None, header.encode("ascii"),
                           C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
     if rc != 0:

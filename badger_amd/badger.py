@@ -14,6 +14,10 @@ header.  The input is read a second time for it (the extraction costs under a mi
 --molecule_reads keeps one read per molecule: the longest cDNA, the earliest read at equal lengths (the rule of molecule_reads.py,
 on the device).  Every other output is the same bytes with and without these flags.
 
+-d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
+(extract_raw_barcodes.py says what that changes), so --tagged_reads and --molecule_reads write the cDNA as stage 1's
+--trimmed_reads does in those modes; --tso5_max_ed and --tso_min_score mean what they mean there.
+
 --stats and --ground_truth drive the reference's offline evaluation module (stats.py), which
 is outside the accelerated path; the flags are accepted and rejected with a message.
 """
@@ -26,7 +30,8 @@ from traceback import print_exc
 
 from . import _native
 from .barcode_graph import BarcodeGraph
-from .extract_raw_barcodes import BARCODE_CALLING_MODES, _chimera_max_ed, _tso_min_score, is_native_input
+from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_5p_mode,
+                                   is_native_input, trim_5p_values)
 
 logger = logging.getLogger("BarcodeGraph")
 
@@ -68,7 +73,12 @@ def parse_args(args):
                         "carrying the corrected barcode (CB) and, with --umi_dedup, the molecule (UB) and its read count (RN)")
     p.add_argument("--tso_min_score", type=_tso_min_score, default=None, metavar="N",
                    help="--tagged_reads: smallest alignment score at which the template-switch oligo is cut off, %d .. %d (default %d)"
-                        % (8, 30, _native.TSO_MIN_SCORE_DEFAULT))
+                        % (8, 30, _native.TSO_MIN_SCORE_DEFAULT)
+                        + "; with -d tenX_5p_*: the RT primer's score, 8 .. %d (default %d)"
+                        % (_native.TSO5_MIN_SCORE_MAX, _native.TSO5_MIN_SCORE_DEFAULT))
+    p.add_argument("--tso5_max_ed", type=_tso5_max_ed, default=None, metavar="E",
+                   help="--tagged_reads with -d tenX_5p_*: edits allowed in the switch oligo behind the UMI, 0 .. %d (default %d)"
+                        % (_native.TSO5_MAX_ED_MAX, _native.TSO5_MAX_ED_DEFAULT))
     p.add_argument("--chimera_cut", action="store_true", default=False,
                    help="--tagged_reads: cut a read at the first adapter or template-switch oligo inside its cDNA (stage 1's --chimera_cut)")
     p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
@@ -84,14 +94,14 @@ def parse_args(args):
         p.error("--tagged_reads needs read input (FASTA, FASTQ, SAM or BAM): a stage-1 TSV does not hold the reads' bases")
     if a.tso_min_score is not None and not a.tagged_reads:
         p.error("--tso_min_score needs --tagged_reads")
+    check_5p_args(p, a.data_type, a.tso5_max_ed, a.tso_min_score, a.tagged_reads, "--tagged_reads")
     if a.chimera_cut and not a.tagged_reads:
         p.error("--chimera_cut needs --tagged_reads")
     if a.chimera_max_ed is not None and not a.chimera_cut:
         p.error("--chimera_max_ed needs --chimera_cut")
     if a.molecule_reads and not (a.umi_dedup and a.tagged_reads):
         p.error("--molecule_reads needs --umi_dedup and --tagged_reads")
-    if a.tso_min_score is None:
-        a.tso_min_score = _native.TSO_MIN_SCORE_DEFAULT
+    a.tso_min_score, a.tso5_max_ed = trim_5p_values(a.data_type, a.tso_min_score, a.tso5_max_ed)
     if a.chimera_cut and a.chimera_max_ed is None:
         a.chimera_max_ed = _native.CHIMERA_MAX_ED_DEFAULT
     if a.umi_dist is None:
@@ -176,7 +186,7 @@ def main(args):
     if args.data_type and args.data_type.startswith("tenX"):
         bc_len = 16
     else:
-        logger.error("Please specify the type of single cell data used. Options are tenX_v2 and tenX_v3.")
+        logger.error("Please specify the type of single cell data used. Options are tenX_v2, tenX_v3, tenX_5p_v2 and tenX_5p_v3.")
         sys.exit(-3)
     if args.stats or args.ground_truth is not None:
         logger.error("--stats / --ground_truth run the reference's offline evaluation module, which this build does not carry")
@@ -222,6 +232,11 @@ def main(args):
         # strings): counting and the edge build run there, the host only gets the per-read ranks for the output file.
         # Like the reference (:112-117) one thread keeps every SAM / BAM record, several skip secondary / supplementary ones.
         ctx = _native.default_context(args.device)
+        umi_len = BARCODE_CALLING_MODES[args.data_type](device=args.device).UMI_LEN_10X
+        layout = _native.LAYOUT_5P if is_5p_mode(args.data_type) else _native.LAYOUT_3P
+        if layout == _native.LAYOUT_5P:
+            ctx.trim_set_5p(umi_len, args.tso5_max_ed)
+        ctx.extract_set_layout(layout)                    # (for this pass; the context is shared and goes back to the 3' layout below)
         ctx.extract_keep_records(True)
         ctx.extract_keep_umis(args.umi_dedup)             # (every chunk's UMIs packed beside its records)
         # --tagged_reads with molecules: every chunk is trimmed (and searched for chimeras) here too, and only its reads' cDNA
@@ -234,17 +249,18 @@ def main(args):
             ctx.extract_keep_cdna(True)
         logger.info("Extracting from " + args.reads)
         read_ids = _native.IdStore()
-        umi_len = BARCODE_CALLING_MODES[args.data_type](device=args.device).UMI_LEN_10X
         try:
             # (-tr 1 is one sequential reader, compressed input as one gzip stream - the reference's single-thread shape,
             # as extract_raw_barcodes.process_single_thread asks for it)
             _native.stage1_collect(ctx, args.reads, umi_len, read_ids, threads=args.threads,
                                    skip_secondary=args.threads != 1)
         except BaseException:
+            ctx.extract_set_layout(_native.LAYOUT_3P)
             ctx.extract_set_trim(False)
             ctx.extract_keep_umis(False)
             ctx.extract_keep_records(False)
             raise
+        ctx.extract_set_layout(_native.LAYOUT_3P)
         if keep_cdna:
             ctx.extract_set_trim(False)                   # (what was kept stays until the records go)
         mark("extract")
@@ -274,9 +290,14 @@ def main(args):
     from_device.extract_keep_records(False)
     if args.tagged_reads:
         # the second pass: the same reader threads and the same skip_secondary as the first, so the same reads in the same order
-        res = _native.stage1_run([from_device], args.reads, None, "", umi_len, threads=args.threads,
-                                 skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads,
-                                 tso_min_score=args.tso_min_score, chimera_max_ed=args.chimera_max_ed, tags=tags)
+        from_device.extract_set_layout(layout)
+        try:
+            res = _native.stage1_run([from_device], args.reads, None, "", umi_len, threads=args.threads,
+                                     skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads,
+                                     tso_min_score=args.tso_min_score, chimera_max_ed=args.chimera_max_ed, tags=tags,
+                                     tso5_max_ed=args.tso5_max_ed)
+        finally:
+            from_device.extract_set_layout(_native.LAYOUT_3P)
         mark("tagged_reads")
         logger.info("Tagged reads: %d to %s, %d bases; left out: %d without a cell, %d not their molecule's read"
                     % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))

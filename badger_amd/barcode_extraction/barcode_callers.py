@@ -8,6 +8,7 @@ call per chunk of reads instead of one Python call per read).  All arithmetic ha
 the GPU; this module only slices strings and formats rows.
 """
 from collections import defaultdict
+from contextlib import contextmanager
 from dataclasses import dataclass
 from enum import Enum, unique
 
@@ -160,6 +161,8 @@ class TenXBarcodeExtractor:
     TERMINAL_MATCH_DELTA = 4
     STRICT_TERMINAL_MATCH_DELTA = 1
 
+    LAYOUT = _native.LAYOUT_3P        # the library layout the context is put into while this detector's reads run
+
     def __init__(self, protocol_version=TenXVersions.v3, device=0, instance=0):
         self.UMI_LEN_10X = self.UMI_LENGTHS[protocol_version]
         self.device = device
@@ -189,6 +192,7 @@ class TenXBarcodeExtractor:
         ctx = self._ctx()
         try:
             ctx.extract_set_strand_rule(strand_rule)
+            ctx.extract_set_layout(self.LAYOUT)
             return ctx.extract_batch(bases, off, self.UMI_LEN_10X)
         except _native.BadgerHipError as e:
             if e.code == _native.E_BADBASE:
@@ -196,6 +200,7 @@ class TenXBarcodeExtractor:
             raise
         finally:
             ctx.extract_set_strand_rule(_native.STRAND_RULE_DEFAULT)     # the context is shared: leave it as found
+            ctx.extract_set_layout(_native.LAYOUT_3P)
 
     def find_barcode_umi_batch(self, read_chunk):
         """read_chunk: list[(read_id, seq)] -> list[TenXBarcodeDetectionResult], input order."""
@@ -227,3 +232,28 @@ class TenXBarcodeExtractorV2(TenXBarcodeExtractor):
 class TenXBarcodeExtractorV3(TenXBarcodeExtractor):
     def __init__(self, device=0, instance=0):
         TenXBarcodeExtractor.__init__(self, TenXVersions.v3, device, instance)
+
+
+class TenX5pBarcodeExtractorV2(TenXBarcodeExtractorV2):
+    """10x 5' v2 (and v1 / v1.1): R1 - barcode - UMI (10) - TTTCTTATATGGG - cDNA (sense) - polyA - RT primer.  The R1 search is the
+    3' one; the records follow the 5' rule (include/badger_hip.h, bdg_extract_set_layout)."""
+    LAYOUT = _native.LAYOUT_5P
+
+
+class TenX5pBarcodeExtractorV3(TenXBarcodeExtractorV3):
+    """10x 5' v3: the same layout with a UMI of 12"""
+    LAYOUT = _native.LAYOUT_5P
+
+
+@contextmanager
+def contexts_in_layout(detectors):
+    """the detectors' contexts, each in its detector's layout for the time of the block (the contexts are shared: they are left in
+    LAYOUT_3P, as they were found)"""
+    ctxs = [d._ctx() for d in detectors]
+    try:
+        for d, c in zip(detectors, ctxs):
+            c.extract_set_layout(d.LAYOUT)
+        yield ctxs
+    finally:
+        for c in ctxs:
+            c.extract_set_layout(_native.LAYOUT_3P)

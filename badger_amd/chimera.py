@@ -21,7 +21,7 @@ that is not A, C, G or T equals no pattern letter.  (P, j) is a hit when D_P(j) 
 import numpy as np
 
 from ._native import FLAG_REV
-from .trim import TRIM_EMIT, TSO, _CODE, _strand_codes, revcomp
+from .trim import TRIM_EMIT, TRIM_SENSE, TSO, _CODE, _strand_codes, revcomp
 
 R1 = "CTACACGACGCTCTTCCGATCT"               # barcode_callers.py:154
 PATTERNS = (TSO, revcomp(TSO), R1, revcomp(R1))
@@ -227,7 +227,8 @@ def counts(trim, chim):
 
 def fasta_text(ids, reads, recs, trim, chim, rows=None, wl_barcodes=None):
     """the text bdg_format_trimmed_chimera writes: trim.fasta_text's record per read with TRIM_EMIT, but a read with a hit is
-    written as revcomp(s[cdna_start:cut)) with a last header field CH:Z:<kind>,<hit_ed>, and left out when cut == cdna_start"""
+    written as revcomp(s[cdna_start:cut)) - s[cdna_start:cut) itself with TRIM_SENSE - with a last header field
+    CH:Z:<kind>,<hit_ed>, and left out when cut == cdna_start"""
     out = []
     for i, (rid, read, rec, t, c) in enumerate(zip(ids, reads, recs, trim, chim)):
         if not int(t["flags"]) & TRIM_EMIT:
@@ -249,5 +250,5 @@ def fasta_text(ids, reads, recs, trim, chim, rows=None, wl_barcodes=None):
             head += "\tCB:Z:" + wl_barcodes[i]
         if hit:
             head += "\tCH:Z:%s,%d" % (KIND_NAMES[int(c["hit_kind"])], int(c["hit_ed"]))
-        out.append(head + "\n" + revcomp(s[a:b]) + "\n")
+        out.append(head + "\n" + (s[a:b] if int(t["flags"]) & TRIM_SENSE else revcomp(s[a:b])) + "\n")
     return "".join(out)

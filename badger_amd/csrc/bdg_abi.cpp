@@ -356,7 +356,7 @@ int bdg_extract_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* 
     // (the match of the batch before this one is still waiting - it goes behind this extraction's scan; the one before it is
     // the last one queued)
     if (ctx->overlap && ctx->aux_count >= 1) BDG_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux[(ctx->aux_count - 1) & 1], 0));
-    return bdg_extract_launch(ctx, d_bases, d_off, n, total_bytes, umi_len, d_out);
+    return bdg_extract_launch_layout(ctx, d_bases, d_off, n, total_bytes, umi_len, ctx->x_layout, d_out);
 }
 
 int bdg_extract_status(bdg_ctx* ctx, uint64_t* bad_read, uint64_t* n_windows)
@@ -379,6 +379,24 @@ int bdg_extract_set_strand_rule(bdg_ctx* ctx, int rule)
     if (!ctx) return BDG_E_ARG;
     if (rule != BDG_STRAND_RULE_DEFAULT && rule != BDG_STRAND_RULE_NO_POLYA) return bdg_fail(ctx, BDG_E_ARG, "unknown strand rule");
     ctx->x_strand_rule = rule;
+    return BDG_OK;
+}
+
+int bdg_extract_set_layout(bdg_ctx* ctx, int layout)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (layout != BDG_LAYOUT_3P && layout != BDG_LAYOUT_5P) return bdg_fail(ctx, BDG_E_ARG, "unknown layout");
+    ctx->x_layout = layout;
+    return BDG_OK;
+}
+
+int bdg_trim_set_5p(bdg_ctx* ctx, uint32_t umi_len, uint32_t tso5_max_ed)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
+    if (tso5_max_ed > BDG_TRIM5P_MAX_ED_MAX) return bdg_fail(ctx, BDG_E_ARG, "tso5_max_ed out of range (0 .. 4)");
+    ctx->trim5p_umi_len = umi_len;
+    ctx->trim5p_max_ed = tso5_max_ed;
     return BDG_OK;
 }
 
@@ -435,7 +453,7 @@ int bdg_extract_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     // A queue overflow grows the workspace from what the failed pass could count; the hits re-queued by clusters are only
     // known once queue A is complete, so a second overflow is possible: loop (each pass at least 1.5 x the last one).
     for (int attempt = 0; attempt < 8; ++attempt) {
-        rc = bdg_extract_launch(ctx, S.d_bases, S.d_off, n, S.total, umi_len, static_cast<bdg_extract_rec*>(S.d_out));
+        rc = bdg_extract_launch_layout(ctx, S.d_bases, S.d_off, n, S.total, umi_len, ctx->x_layout, static_cast<bdg_extract_rec*>(S.d_out));
         if (rc) return rc;
         uint64_t bad = 0, nwin = 0;
         rc = bdg_extract_status_impl(ctx, &bad, &nwin);
@@ -456,7 +474,7 @@ int bdg_trim_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_o
     if (n && (!d_bases || !d_off || !d_recs || !d_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (reinterpret_cast<uintptr_t>(d_recs) & 15u) return bdg_fail(ctx, BDG_E_ARG, "d_recs must be 16-byte aligned");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return bdg_trim_launch(ctx, d_bases, d_off, d_recs, n, tso_min_score, d_out);
+    return bdg_trim_launch_layout(ctx, d_bases, d_off, d_recs, n, ctx->x_layout, ctx->trim5p_umi_len, ctx->trim5p_max_ed, tso_min_score, d_out);
 }
 
 int bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n,
@@ -472,7 +490,7 @@ int bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint
     hipStream_t st = ctx->stream;
     const ReadsLayout L = reads_layout(S.d_out, n, false);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(L.recs, recs, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyHostToDevice, st));
-    if ((rc = bdg_trim_launch(ctx, S.d_bases, S.d_off, L.recs, n, tso_min_score, L.trim))) return rc;
+    if ((rc = bdg_trim_launch_layout(ctx, S.d_bases, S.d_off, L.recs, n, ctx->x_layout, ctx->trim5p_umi_len, ctx->trim5p_max_ed, tso_min_score, L.trim))) return rc;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(out, L.trim, sizeof(bdg_trim_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
     return BDG_OK;

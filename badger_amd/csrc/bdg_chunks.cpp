@@ -38,7 +38,7 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
     bdg_extract_rec* const d_recs = static_cast<bdg_extract_rec*>(sl.recs.d.p);
     bdg_trim_rec* const d_trim = static_cast<bdg_trim_rec*>(sl.trim.d.p);
     const size_t n = sl.n;
-    int rc = bdg_extract_launch(ctx, d_bases, d_off, sl.n, sl.total, sl.umi_len, d_recs);
+    int rc = bdg_extract_launch_layout(ctx, d_bases, d_off, sl.n, sl.total, sl.umi_len, sl.layout, d_recs);
     if (rc) return rc;
     sl.qcap = ctx->x_hits_cap_launched;
     hipStream_t st = ctx->stream;
@@ -46,7 +46,7 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
     BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_counters.p, bdg_extract_counters_now(ctx), bdg_extract_counter_bytes(), hipMemcpyDeviceToHost, st));
     if (sl.trim_on) {
         // the chunk's trim behind its extraction (a rerun passes here again: the trim of placeholder records is overwritten)
-        if ((rc = bdg_trim_launch(ctx, d_bases, d_off, d_recs, sl.n, sl.trim_min_score, d_trim))) return rc;
+        if ((rc = bdg_trim_launch_layout(ctx, d_bases, d_off, d_recs, sl.n, sl.layout, sl.umi_len, sl.tso5_max_ed, sl.trim_min_score, d_trim))) return rc;
         if ((rc = mirror_fetch(ctx, sl.trim, sizeof(bdg_trim_rec) * n, st))) return rc;
         if (sl.chim_on) {                                        // ... and the search of the trimmed intervals behind the trim
             if ((rc = bdg_chimera_launch(ctx, d_bases, d_off, d_recs, d_trim, sl.n, sl.chim_max_ed, static_cast<bdg_chimera_rec*>(sl.chim.d.p))))
@@ -181,6 +181,7 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
+    sl.layout = ctx->x_layout; sl.tso5_max_ed = ctx->trim5p_max_ed;
     sl.trim_on = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
     sl.chim_on = ctx->trim_on && ctx->chim_on; sl.chim_max_ed = ctx->chim_max_ed;
     if (n == 0) { sl.busy = true; return BDG_OK; }

@@ -68,6 +68,7 @@ struct bdg_ctx {
     uint64_t x_hits_cap = 0;
     uint64_t x_hits_cap_fixed = 0;     // bdg_extract_set_queue_capacity (0 = automatic)
     int x_strand_rule = 0;             // bdg_extract_set_strand_rule
+    int x_layout = BDG_LAYOUT_3P;      // bdg_extract_set_layout
     uint64_t x_hits_cap_launched = 0;  // capacity the last launch ran with
     // host-buffer staging
     DevBuf s_in0, s_in1, s_out0;
@@ -79,6 +80,7 @@ struct bdg_ctx {
         Mirror recs;                                         // bdg_extract_rec [n]
         hipEvent_t done = nullptr;
         uint32_t n = 0, umi_len = 0; uint64_t total = 0, qcap = 0;
+        int layout = BDG_LAYOUT_3P; uint32_t tso5_max_ed = 0;   // what the chunk was submitted with (a rerun keeps them)
         bool busy = false;
         bool reran = false;                                  // collect ran the chunk again (a queue overflowed)
         // trim of the chunk (bdg_extract_set_trim): behind the extraction on the same stream
@@ -105,6 +107,7 @@ struct bdg_ctx {
     } corr;
     bool trim_on = false; uint32_t trim_min_score = 0;       // bdg_extract_set_trim: for the submits that follow
     bool chim_on = false; uint32_t chim_max_ed = 0;          // bdg_extract_set_chimera: likewise (only while trim_on)
+    uint32_t trim5p_umi_len = 10, trim5p_max_ed = BDG_TRIM5P_MAX_ED_DEFAULT;   // bdg_trim_set_5p: read only in BDG_LAYOUT_5P
     // Arrays kept on the device over every collected chunk, in submission order: the records (bdg_extract_keep_records); with
     // them every read's UMI packed into 32 bits (bdg_extract_keep_umis, umi_kernels.hip) and, only while trim_on, every read's
     // cDNA length from the chunk's trim and chimera records (bdg_extract_keep_cdna)

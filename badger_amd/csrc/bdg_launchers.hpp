@@ -49,6 +49,9 @@ int bdg_molecule_reps_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const ui
                              uint8_t*, uint32_t*);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
+// trim5p_kernels.hip
+int bdg_layout5p_launch(bdg_ctx*, const uint64_t*, uint32_t, uint32_t, bdg_extract_rec*);
+int bdg_trim5p_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, uint32_t, uint32_t, bdg_trim_rec*);
 // chimera_kernels.hip
 int bdg_chimera_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, const bdg_trim_rec*, uint32_t, uint32_t, bdg_chimera_rec*);
 
@@ -73,7 +76,28 @@ static inline RecsQuery recs_query(const void* d_recs)
 
 static inline int check_tso_min_score(bdg_ctx* ctx, uint32_t v)
 {
+    if (ctx->x_layout == BDG_LAYOUT_5P)
+        return v < 8 || v > BDG_TRIM5P_PRIMER_LEN ? bdg_fail(ctx, BDG_E_ARG, "tso_min_score out of range (8 .. 25 in the 5' layout)") : BDG_OK;
     return v < 8 || v > 30 ? bdg_fail(ctx, BDG_E_ARG, "tso_min_score out of range (8 .. 30)") : BDG_OK;
+}
+
+// The extraction in a layout: bdg_extract_launch, and in BDG_LAYOUT_5P the record rule behind it on the same stream, in front of
+// whatever the caller queues next (copies, the trim, the whitelist match, the kept arrays).  Every extraction path calls this.
+static inline int bdg_extract_launch_layout(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint64_t total,
+                                            uint32_t umi_len, int layout, bdg_extract_rec* d_out)
+{
+    const int rc = bdg_extract_launch(ctx, d_bases, d_off, n, total, umi_len, d_out);
+    if (layout != BDG_LAYOUT_5P) return rc;
+    const int rc5 = bdg_layout5p_launch(ctx, d_off, n, umi_len, d_out);        // (also behind a batch whose deferred match failed: the records are complete)
+    return rc ? rc : rc5;
+}
+
+// the trim of a layout: k_trim_reads, or k_trim_reads_5p with the two values only it takes
+static inline int bdg_trim_launch_layout(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
+                                         int layout, uint32_t umi_len, uint32_t tso5_max_ed, uint32_t min_score, bdg_trim_rec* d_out)
+{
+    return layout == BDG_LAYOUT_5P ? bdg_trim5p_launch(ctx, d_bases, d_off, d_recs, n, umi_len, tso5_max_ed, min_score, d_out)
+                                   : bdg_trim_launch(ctx, d_bases, d_off, d_recs, n, min_score, d_out);
 }
 
 static inline int check_chimera_max_ed(bdg_ctx* ctx, uint32_t v)

@@ -12,6 +12,7 @@
 //                    one header on top (process_single_thread, :162-173), or a header in front of every READ_CHUNK_SIZE
 //                    reads plus one for the trailing, possibly empty chunk (process_in_parallel, :131-159,243-246).
 #include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
 #include "host_util.hpp"
 
 #include <fcntl.h>
@@ -136,7 +137,7 @@ char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* 
     return o;
 }
 
-struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0, no_cell = 0, not_kept = 0; };
+struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0, no_cell = 0, not_kept = 0, no_anchor = 0; };
 
 // stage 2's answers for the reads of a chunk (bdg_format_trimmed_tags): the cell, the molecule's code and its read count (mol may
 // be null), a filter (may be null)
@@ -171,6 +172,7 @@ char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, con
     static const char* const kind_name[4] = { "TSO", "TSOrc", "R1", "R1rc" };
     for (uint32_t i = 0; i < ch->n; ++i) {
         const bdg_trim_rec& t = tr[i];
+        if (t.flags & BDG_TRIM_NO_ANCHOR) ++st.no_anchor;                  // (5' layout: never with BDG_TRIM_EMIT)
         if (!(t.flags & BDG_TRIM_EMIT)) continue;
         const bool hit = cm && (cm[i].flags & BDG_CHIMERA_HIT);
         const int32_t cend = hit ? cm[i].cut : t.cdna_end;
@@ -227,10 +229,12 @@ char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, con
             *o++ = (char)('0' + cm[i].hit_ed % 10);
         }
         *o++ = '\n';
-        // revcomp(s[a:b]): for a reverse-strand record the read's own bytes, for a forward one their reverse complement
+        // revcomp(s[a:b]): for a reverse-strand record the read's own bytes, for a forward one their reverse complement;
+        // with BDG_TRIM_SENSE (5' layout) s[a:b] as it stands: the other way round
         const int64_t a = std::min<int64_t>(std::max<int64_t>(t.cdna_start, 0), L), b = std::min<int64_t>(std::max<int64_t>(cend, 0), L);
         if (b > a) {
-            if (rev) { memcpy(o, seq + (L - b), (size_t)(b - a)); o += b - a; }
+            if (t.flags & BDG_TRIM_SENSE) slice(a, b);
+            else if (rev) { memcpy(o, seq + (L - b), (size_t)(b - a)); o += b - a; }
             else for (int64_t x = b - 1; x >= a; --x) *o++ = comp_base((char)seq[x]);
             st.bases += (uint64_t)(b - a);
         }
@@ -368,7 +372,7 @@ struct Pipeline {
                 if (bad) trim_write_failed = true;
                 trim_total.reads += t->st.reads; trim_total.tso += t->st.tso; trim_total.bases += t->st.bases;
                 trim_total.cut += t->st.cut; trim_total.dropped += t->st.dropped; trim_total.cut_bases += t->st.cut_bases;
-                trim_total.no_cell += t->st.no_cell; trim_total.not_kept += t->st.not_kept;
+                trim_total.no_cell += t->st.no_cell; trim_total.not_kept += t->st.not_kept; trim_total.no_anchor += t->st.no_anchor;
             }
             delete t;
         }
@@ -595,14 +599,18 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     if (tags && o->tag_reads && (!o->tag_cell_rank || !o->tag_cell_has || (o->tag_molecule && !o->tag_mol_reads)))
         return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS: null array");
     const bool corr = wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT);
+    const int layout = c0->x_layout;                                   // bdg_extract_set_layout: the caller's, the same on every context
+    for (uint32_t c = 1; c < n_ctx; ++c) if (!ctxs[c] || ctxs[c]->x_layout != layout) return bdg_fail(c0, BDG_E_ARG, "the contexts differ in their layout");
+    const bool trim5p = trim && layout == BDG_LAYOUT_5P;
     // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT, those behind it with BDG_STAGE1_TRIM)
-    memset(res, 0, tags ? sizeof(*res) : chim ? offsetof(bdg_stage1_result, tags_no_cell) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
+    memset(res, 0, trim5p ? sizeof(*res) : tags ? offsetof(bdg_stage1_result, trimmed_no_anchor) : chim ? offsetof(bdg_stage1_result, tags_no_cell) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
     if (chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
     if (trim) {
         if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
-        if (o->tso_min_score < 8 || o->tso_min_score > 30) return bdg_fail(c0, BDG_E_ARG, "tso_min_score out of range (8 .. 30)");
+        if (int rcs = check_tso_min_score(c0, o->tso_min_score)) return rcs;
+        if (trim5p && o->reserved_trim > BDG_TRIM5P_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "tso5_max_ed out of range (0 .. 4)");
     }
     // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
     std::vector<uint32_t> wl_caller;
@@ -665,6 +673,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
             return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
         }
         for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 1, o->tso_min_score);   // (checked above; off again below)
+        if (trim5p) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_trim_set_5p(ctxs[c], o->umi_len, o->reserved_trim);
         if (chim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_chimera(ctxs[c], 1, o->chimera_max_ed);
     }
     bool ok_io = true;
@@ -724,6 +733,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         res->trimmed_reads = P.trim_total.reads; res->trimmed_tso = P.trim_total.tso; res->trimmed_bases = P.trim_total.bases;
         if (chim) { res->chimera_cut = P.trim_total.cut; res->chimera_dropped = P.trim_total.dropped; res->chimera_bases = P.trim_total.cut_bases; }
         if (tags) { res->tags_no_cell = P.trim_total.no_cell; res->tags_not_kept = P.trim_total.not_kept; }
+        if (trim5p) res->trimmed_no_anchor = P.trim_total.no_anchor;
     }
     // rows of the chunks before a failure are in the file, like in the reference's loop
     if (rc == BDG_OK && !P.no_tsv && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;

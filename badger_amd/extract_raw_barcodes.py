@@ -44,6 +44,16 @@ What differs from the reference, by design:
     up to the first such column only, its header gains "\tCH:Z:<TSO|TSOrc|R1|R1rc>,<edits>", and it is left out when nothing
     remains.  The rule is restated in badger_amd/chimera.py and stated in include/badger_hip.h (bdg_chimera_batch).  The TSV
     and the .stats do not change; the three counts go to the log.
+  * --mode tenX_5p_v2 (UMI 10; also 5' v1 / v1.1) and tenX_5p_v3 (UMI 12): 10x 5' libraries,
+    R1 - barcode - UMI - TTTCTTATATGGG - cDNA (sense) - polyA - RT primer.  The R1 and barcode search is the 3' one; behind it the
+    records follow the 5' rule (include/badger_hip.h, bdg_extract_set_layout; badger_amd/trim5p.py): the UMI is the umi_len bases
+    behind the barcode, the polyT column is -1 for every read, so "PolyT detected" in the .stats is 0 and its line is absent, and
+    the strand column says on which strand the layout was found.  --trimmed_reads then cuts behind the switch oligo (within
+    --tso5_max_ed edits, 0 .. 4, default 2; a read without it is not written and is counted in the log), in front of the RT
+    primer (--tso_min_score keeps its name and is the primer's score there, 8 .. 25, default 16) and in front of the polyA tail,
+    and writes the cDNA as it lies on the strand, which is mRNA sense.  Template-switch Gs beyond the oligo's three stay in the cDNA.
+    --chimera_cut works on that span with the same four patterns as in the 3' modes (the part kept is the one next to the barcode
+    in either layout); they are the 3' kits' adapters, and tuning them for 5' junctions is open.
 """
 import argparse
 import gzip
@@ -55,8 +65,8 @@ from traceback import print_exc
 
 from . import _native
 
-from .barcode_extraction.barcode_callers import (ReadStats, TenXBarcodeExtractorV2, TenXBarcodeExtractorV3,
-                                                 record_to_row)
+from .barcode_extraction.barcode_callers import (ReadStats, TenX5pBarcodeExtractorV2, TenX5pBarcodeExtractorV3, TenXBarcodeExtractorV2,
+                                                 TenXBarcodeExtractorV3, contexts_in_layout, record_to_row)
 
 logger = logging.getLogger("BarcodeGraph")
 
@@ -70,7 +80,13 @@ BC_EDIT_BITS_DEFAULT = 5
 BC_MIN_POSTERIOR_DEFAULT = 0.975
 TSO_MIN_SCORE_RANGE = (8, 30)
 CHIMERA_MAX_ED_RANGE = (0, _native.CHIMERA_MAX_ED_MAX)
-BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3}
+TSO5_MAX_ED_RANGE = (0, _native.TSO5_MAX_ED_MAX)
+BARCODE_CALLING_MODES = {"tenX_v2": TenXBarcodeExtractorV2, "tenX_v3": TenXBarcodeExtractorV3,
+                         "tenX_5p_v2": TenX5pBarcodeExtractorV2, "tenX_5p_v3": TenX5pBarcodeExtractorV3}
+
+
+def is_5p_mode(mode):
+    return getattr(BARCODE_CALLING_MODES.get(mode), "LAYOUT", _native.LAYOUT_3P) == _native.LAYOUT_5P
 
 
 # ----------------------------------------------------------------------------- whitelist
@@ -232,6 +248,8 @@ def run_fastx_pipeline(input_file, detectors, on_chunk, chunk_size=None, inflate
         on_chunk(rows, recs)
 
     total = 0
+    layout = contexts_in_layout(detectors)           # (holds for the submits below and for the chunks collect runs again)
+    layout.__enter__()
     try:
         k = 0
         while True:
@@ -253,6 +271,7 @@ def run_fastx_pipeline(input_file, detectors, on_chunk, chunk_size=None, inflate
                 det._ctx().extract_collect(slot, ch.n)
             except Exception:
                 pass
+        layout.__exit__(None, None, None)
         ing.close()
     return total
 
@@ -399,12 +418,16 @@ def _run_native(args, header_every, threads, skip_secondary):
         header += "\t" + "\t".join(WHITELIST_COLUMNS)
         if getattr(args, "bc_candidates", None):
             header += "\t" + CANDIDATES_COLUMN
-    res = _native.stage1_run([d._ctx() for d in detectors], args.input, args.output, header,
-                             detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
-                             whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
-                             bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
-                             **_correct_kwargs(args, wl is not None), **_trim_kwargs(args))
-    if getattr(args, "trimmed_reads", None):
+    with contexts_in_layout(detectors) as ctxs:
+        res = _native.stage1_run(ctxs, args.input, args.output, header,
+                                 detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
+                                 whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
+                                 bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
+                                 **_correct_kwargs(args, wl is not None), **_trim_kwargs(args))
+    if getattr(args, "trimmed_reads", None) and is_5p_mode(args.mode):
+        logger.info("Trimmed reads: %d written to %s, %d with the RT primer cut off, %d bases, %d left out without the switch oligo"
+                    % (res.trimmed_reads, args.trimmed_reads, res.trimmed_tso, res.trimmed_bases, res.trimmed_no_anchor))
+    elif getattr(args, "trimmed_reads", None):
         logger.info("Trimmed reads: %d written to %s, %d with the TSO cut off, %d bases"
                     % (res.trimmed_reads, args.trimmed_reads, res.trimmed_tso, res.trimmed_bases))
     if getattr(args, "chimera_cut", False):
@@ -536,7 +559,14 @@ def parse_args(sys_argv):
                         "whole run: join it by read id from <output>%s)" % CORRECTED_SUFFIX)
     p.add_argument("--tso_min_score", type=_tso_min_score, default=None, metavar="N",
                    help="--trimmed_reads: smallest local-alignment score (match +1, mismatch / gap -1) at which the template-switch "
-                        "oligo is cut off, %d .. %d (default %d)" % (TSO_MIN_SCORE_RANGE + (_native.TSO_MIN_SCORE_DEFAULT,)))
+                        "oligo is cut off, %d .. %d (default %d).  In the 5' modes the score of the RT primer at the read's far end, "
+                        "8 .. %d (default %d: the smallest score that fewer than 1 in 10,000 random 64-base windows reach - 4 of 100,000 do - and "
+                        "that 99.1 %%%% of primers planted at the synthetic reads' 8 %%%% error rate reach)"
+                        % (TSO_MIN_SCORE_RANGE + (_native.TSO_MIN_SCORE_DEFAULT, _native.TSO5_MIN_SCORE_MAX, _native.TSO5_MIN_SCORE_DEFAULT)))
+    p.add_argument("--tso5_max_ed", type=_tso5_max_ed, default=None, metavar="E",
+                   help="--trimmed_reads in a 5' mode: edits allowed in the 13-base switch oligo behind the UMI, %d .. %d (default %d: "
+                        "27 of 100,000 random sequences pass for it); a read without it is not written"
+                        % (TSO5_MAX_ED_RANGE + (_native.TSO5_MAX_ED_DEFAULT,)))
     p.add_argument("--chimera_cut", action="store_true", default=False,
                    help="--trimmed_reads: cut a read at the first R1 adapter or template-switch oligo found inside its cDNA, in either "
                         "orientation (two molecules ligated end to end); the header gains a CH field, a read with nothing left is left out")
@@ -546,6 +576,7 @@ def parse_args(sys_argv):
     args = p.parse_args(sys_argv)
     if args.tso_min_score is not None and not args.trimmed_reads:
         p.error("--tso_min_score needs --trimmed_reads")
+    check_5p_args(p, args.mode, args.tso5_max_ed, args.tso_min_score, args.trimmed_reads, "--trimmed_reads")
     if args.chimera_cut and not args.trimmed_reads:
         p.error("--chimera_cut needs --trimmed_reads")
     if args.chimera_max_ed is not None and not args.chimera_cut:
@@ -602,6 +633,35 @@ def _tso_min_score(text):
     return v
 
 
+def _tso5_max_ed(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not TSO5_MAX_ED_RANGE[0] <= v <= TSO5_MAX_ED_RANGE[1]:
+        raise argparse.ArgumentTypeError("%d is outside %d .. %d" % ((v,) + TSO5_MAX_ED_RANGE))
+    return v
+
+
+def check_5p_args(p, mode, tso5_max_ed, tso_min_score, reads_path, reads_flag):
+    """the dependent checks of the 5' flags, for both command lines: --tso5_max_ed needs the read output and a 5' mode; in a 5'
+    mode --tso_min_score is the primer's score and ends at its length"""
+    if tso5_max_ed is not None and not reads_path:
+        p.error("--tso5_max_ed needs %s" % reads_flag)
+    if tso5_max_ed is not None and not is_5p_mode(mode):
+        p.error("--tso5_max_ed needs a 5' mode (tenX_5p_v2, tenX_5p_v3)")
+    if tso_min_score is not None and is_5p_mode(mode) and tso_min_score > _native.TSO5_MIN_SCORE_MAX:
+        p.error("--tso_min_score is the RT primer's score in a 5' mode: %d .. %d" % (TSO_MIN_SCORE_RANGE[0], _native.TSO5_MIN_SCORE_MAX))
+
+
+def trim_5p_values(mode, tso_min_score, tso5_max_ed):
+    """(tso_min_score, tso5_max_ed) with the mode's defaults filled in; tso5_max_ed is None in a 3' mode"""
+    if is_5p_mode(mode):
+        return (_native.TSO5_MIN_SCORE_DEFAULT if tso_min_score is None else tso_min_score,
+                _native.TSO5_MAX_ED_DEFAULT if tso5_max_ed is None else tso5_max_ed)
+    return _native.TSO_MIN_SCORE_DEFAULT if tso_min_score is None else tso_min_score, None
+
+
 def _chimera_max_ed(text):
     try:
         v = int(text)
@@ -654,8 +714,10 @@ def _trim_kwargs(args):
     path = getattr(args, "trimmed_reads", None)
     if not path:
         return {}
-    score = getattr(args, "tso_min_score", None)
-    kw = dict(trimmed_path=path, tso_min_score=_native.TSO_MIN_SCORE_DEFAULT if score is None else score)
+    score, ed5 = trim_5p_values(getattr(args, "mode", None), getattr(args, "tso_min_score", None), getattr(args, "tso5_max_ed", None))
+    kw = dict(trimmed_path=path, tso_min_score=score)
+    if ed5 is not None:
+        kw["tso5_max_ed"] = ed5
     if getattr(args, "chimera_cut", False):
         ed = getattr(args, "chimera_max_ed", None)
         kw["chimera_max_ed"] = _native.CHIMERA_MAX_ED_DEFAULT if ed is None else ed

@@ -204,3 +204,60 @@ def list_to_reads(seqs):
         off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
     bases = np.frombuffer("".join(seqs).encode("ascii"), dtype=np.uint8).copy() if seqs else np.zeros(0, np.uint8)
     return bases, off
+
+
+TSO5 = "TTTCTTATATGGG"                    # the 5' kits' template-switch oligo, behind the UMI
+RT_PRIMER_RC = TSO[5:]                    # what a 5' read ends in: the RT primer's reverse complement
+
+
+def make_reads_5p(n, whitelist, seed=1, umi_len=10, n_cells=5000, p_sub=0.03, p_ins=0.02, p_del=0.03, tail=30, primer=True,
+                  clean_every=0, with_truth=False):
+    """10x 5' reads on the host -> (bases uint8[total] ASCII, off int64[n + 1]) (+ truth dict):
+      junk U[0,40] + R1 + barcode + UMI + TTTCTTATATGGG + cDNA + A*tail [+ RT primer, reverse complemented]
+    with the total length from make_reads' table, half of the reads reverse-complemented, then make_reads' iid per-base errors.
+    clean_every = k > 0: every k-th read stays error-free.  A generator of its own (numpy's, seeded): make_reads and its
+    bytes are untouched.  truth: barcode (rank), revcomp, umi (str), cdna (str, before errors)."""
+    rng = np.random.default_rng([int(seed), 0x5F5])
+    wl = np.ascontiguousarray(whitelist).astype(np.int64)
+    n_cells = min(n_cells, len(wl))
+    cells = wl[rng.permutation(len(wl))[:n_cells]]
+    w = np.exp(rng.standard_normal(n_cells))
+    cum = np.cumsum(w) / w.sum()
+    len_tab = _table_lengths(seed)
+    comp = np.array([3, 2, 1, 0], dtype=np.uint8)
+    enc = lambda s: np.array([_CODE[c] for c in s], dtype=np.uint8)             # noqa: E731
+    r1, tso5, prc = enc(R1), enc(TSO5), enc(RT_PRIMER_RC)
+    parts, lens = [], np.zeros(n, dtype=np.int64)
+    truth = {"barcode": np.zeros(n, np.int64), "revcomp": np.zeros(n, bool), "umi": [], "cdna": []}
+    for i in range(n):
+        bc = int(cells[min(int(np.searchsorted(cum, rng.random())), n_cells - 1)]) if rng.random() < 0.95 else int(rng.integers(0, 1 << 32))
+        junk = rng.integers(0, 4, size=int(rng.integers(0, 41)), dtype=np.uint8)
+        umi = rng.integers(0, 4, size=umi_len, dtype=np.uint8)
+        fixed = len(junk) + len(R1) + 16 + umi_len + len(TSO5) + tail + (len(prc) if primer else 0)
+        cdna = rng.integers(0, 4, size=max(int(len_tab[int(rng.integers(0, 65536))]) - fixed, 20), dtype=np.uint8)
+        bcc = np.array([(bc >> (2 * k)) & 3 for k in range(16)], dtype=np.uint8)
+        codes = np.concatenate([junk, r1, bcc, umi, tso5, cdna, np.zeros(tail, np.uint8), prc if primer else prc[:0]])
+        rc = bool(rng.integers(0, 2))
+        if rc:
+            codes = comp[codes[::-1]]
+        if not (clean_every and i % clean_every == 0):
+            u = rng.random(len(codes))
+            is_del, is_sub, is_ins = u < p_del, (u >= p_del) & (u < p_del + p_sub), (u >= p_del + p_sub) & (u < p_del + p_sub + p_ins)
+            codes = np.where(is_sub, (codes + rng.integers(1, 4, size=len(codes), dtype=np.uint8)) & 3, codes).astype(np.uint8)
+            cnt = (~is_del).astype(np.int64) + is_ins
+            at = np.cumsum(cnt) - cnt
+            out = np.empty(int(cnt.sum()), dtype=np.uint8)
+            keep = ~is_del
+            out[at[keep]] = codes[keep]
+            out[(at + keep)[is_ins]] = rng.integers(0, 4, size=int(is_ins.sum()), dtype=np.uint8)
+            codes = out
+        parts.append(codes)
+        lens[i] = len(codes)
+        truth["barcode"][i], truth["revcomp"][i] = bc, rc
+        if with_truth:
+            truth["umi"].append("".join("ACGT"[c] for c in umi))
+            truth["cdna"].append("".join("ACGT"[c] for c in cdna))
+    bases = _ASCII[np.concatenate(parts)] if n else np.zeros(0, np.uint8)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    return (bases, off, truth) if with_truth else (bases, off)

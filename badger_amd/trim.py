@@ -29,6 +29,7 @@ TSO_MIN_SCORE_DEFAULT = 20
 TSO_MIN_SCORE_RANGE = (8, 30)
 TRIM_EMIT = 1
 TRIM_TSO = 2
+TRIM_SENSE = 4       # 5' layout (trim5p.py): s[cdna_start:cdna_end] is mRNA sense as it stands
 TRIM_DTYPE = np.dtype([("cdna_start", "<i4"), ("cdna_end", "<i4"), ("tail_len", "<i2"), ("tso_score", "i1"), ("flags", "u1")])
 _COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
 
@@ -129,11 +130,14 @@ def trim_reads(reads, recs, tso_min_score=TSO_MIN_SCORE_DEFAULT, align=None):
 
 
 def trimmed_sequence(read, rec, t):
-    """the cDNA in mRNA sense, revcomp(s[cdna_start:cdna_end]): for a FLAG_REV record the read's own slice"""
+    """the cDNA in mRNA sense, revcomp(s[cdna_start:cdna_end]): for a FLAG_REV record the read's own slice.  With TRIM_SENSE
+    (5' layout) s[cdna_start:cdna_end] itself."""
     L, a, b = len(read), int(t["cdna_start"]), int(t["cdna_end"])
     a, b = min(max(a, 0), L), min(max(b, 0), L)
     if b <= a:
         return ""
+    if int(t["flags"]) & TRIM_SENSE:
+        return revcomp(read[L - b:L - a]) if int(rec["flags"]) & FLAG_REV else read[a:b]
     return read[L - b:L - a] if int(rec["flags"]) & FLAG_REV else revcomp(read[a:b])
 
 

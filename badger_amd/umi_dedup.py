@@ -18,7 +18,7 @@ and never depends on visiting order.
 """
 from collections import defaultdict
 
-UMI_LEN = {"tenX_v3": 12, "tenX_v2": 10}
+UMI_LEN = {"tenX_v3": 12, "tenX_v2": 10, "tenX_5p_v3": 12, "tenX_5p_v2": 10}
 UMI_MAX_LEN = 14                   # usable lengths are at most 12 + 2: the device code packs one into 32 bits (umi_code)
 NONE = 0xFFFFFFFF                  # the code of "no usable UMI"
 _ACGT = {"A": 0, "C": 1, "G": 2, "T": 3}

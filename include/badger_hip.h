@@ -169,6 +169,25 @@ int  bdg_extract_set_queue_capacity(bdg_ctx* ctx, uint64_t entries_per_segment);
 #define BDG_STRAND_RULE_DEFAULT  0
 #define BDG_STRAND_RULE_NO_POLYA 1
 int  bdg_extract_set_strand_rule(bdg_ctx* ctx, int rule);
+/* Which library layout the reads have.  A context setting like bdg_extract_set_trim: it holds for the launches that follow, on
+ * every extraction path (bdg_extract_batch, bdg_extract_batch_dev, bdg_extract_submit / bdg_extract_collect; a chunk that
+ * collect runs again after a queue overflow keeps the layout it was submitted with).  Any other value returns BDG_E_ARG.
+ * BDG_LAYOUT_3P (the default)  R1 - barcode - UMI - polyT - cDNA (antisense) - TSOrc: the reference's tenX_v2 / tenX_v3.  No
+ *                              further kernel runs; every output is what it was before this setting existed.
+ * BDG_LAYOUT_5P                R1 - barcode - UMI - BDG_TRIM5P_TSO_SEQ - cDNA (sense) - polyA - RT primer (10x 5' v1 .. v3).  The
+ *                              R1 search is the 3' one; one more kernel, behind it on the same stream and in front of everything
+ *                              that reads the records, rewrites each record as a pure function of the 3'-rule record and the
+ *                              read's length L:
+ *   valid == 1, no BDG_FLAG_INCOMPLETE   r1_end, bc_start, bc_rank, r1_score and flags stay; polyT = -1; umi_start = bc_start + 16;
+ *                                        umi_end = min(L, umi_start + umi_len); strand = -1 with BDG_FLAG_REV, else +1 (the layout
+ *                                        was found on the reverse complement, or on the read as given)
+ *   valid != 1, no BDG_FLAG_INCOMPLETE   polyT = -1, strand = 0, every other field stays
+ *   BDG_FLAG_INCOMPLETE (a placeholder)  left alone
+ * A UMI that ends in TT in front of the switch oligo's TTT no longer passes for a polyT and is no longer cut short.  "polyT
+ * detected" of the statistics is 0 in this layout. */
+#define BDG_LAYOUT_3P 0
+#define BDG_LAYOUT_5P 1
+int  bdg_extract_set_layout(bdg_ctx* ctx, int layout);
 /* Pipeline statistics of the last extraction (synchronises): out[0] 6-mer hits, [1] clusters aligned
  * (queue A), [2] hits sent to the strict filter (queue B), [3] of those skipped because the
  * relaxed search had already succeeded, [4] filter survivors, [5] hits re-queued from clusters,
@@ -264,6 +283,41 @@ int  bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uin
  * pass give flags = 0 and are never seen.  Holds for the submits that follow. */
 int  bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score);
 int  bdg_extract_collect_trim(bdg_ctx* ctx, uint32_t slot, bdg_trim_rec* out);
+
+/* ---- trimmed cDNA in the 5' layout (the rule restated in badger_amd/trim5p.py) --------------------------------------- */
+/* On a context in BDG_LAYOUT_5P, bdg_trim_batch, bdg_trim_batch_dev and the pipelined trim apply this rule instead of the one
+ * above, into the same bdg_trim_rec.  s, L as above; the record is the one the layout's kernel rewrote.  Integers only.
+ * Eligible: rec.valid == 1, no BDG_FLAG_INCOMPLETE, umi_end - umi_start == umi_len (the read holds its whole UMI; a record from
+ * elsewhere must also have 0 <= umi_start and umi_end <= L, which the layout's kernel always leaves); every other read gets
+ * {-1, -1, 0, 0, 0}.
+ *   anchor   the switch oligo BDG_TRIM5P_TSO_SEQ (13 letters) against the text s[max(umi_start, e - 3) : min(L, e + 19)],
+ *            e = umi_end: unit-cost edit distance, the pattern aligned whole, the text free at both ends, N equal to nothing.
+ *            d = the smallest distance over the text's end columns, at equal d the smallest end column.  Found when
+ *            d <= tso5_max_ed (0 .. BDG_TRIM5P_MAX_ED_MAX): cdna_start = that column + 1, flag BDG_TRIM_ANCHOR, d in
+ *            BDG_TRIM_ANCHOR_ED(flags).  Not found: {-1, -1, 0, 0, BDG_TRIM_NO_ANCHOR}: the read is not emitted, the writers
+ *            count it.  Template-switch Gs beyond the oligo's three stay in the cDNA.
+ *   far end  the RT primer's reverse complement = the last BDG_TRIM5P_PRIMER_LEN letters of BDG_TRIM_TSO_SEQ, aligned locally
+ *            (scores and tie rule of the TSO above) against w = s[max(cdna_start, L - BDG_TRIM_TSO_WINDOW) : L]; tso_score = its
+ *            score.  At tso_score >= tso_min_score (8 .. BDG_TRIM5P_PRIMER_LEN here) end0 = max(cdna_start, window start +
+ *            ref_begin - pattern_begin), flag BDG_TRIM_TSO; otherwise end0 = L.
+ *   polyA    the mirror of the tail above: from column end0 - 1 backwards a running score takes +1 for 'A' and -2 for anything
+ *            else; cdna_end = the column of the last strict maximum (end0 when there is none); the walk stops at cdna_start or
+ *            once the score lies BDG_TRIM_TAIL_XDROP below its maximum.  tail_len = end0 - cdna_end, saturating at 32767.
+ *   BDG_TRIM_EMIT when the anchor was found and cdna_end > cdna_start; an emitted record always carries BDG_TRIM_SENSE: the
+ *   strand's text between the two columns is mRNA sense (the writers print it as it stands, see bdg_format_trimmed). */
+#define BDG_TRIM5P_TSO_SEQ    "TTTCTTATATGGG"
+#define BDG_TRIM5P_PRIMER_LEN 25
+#define BDG_TRIM5P_MAX_ED_DEFAULT 2
+#define BDG_TRIM5P_MAX_ED_MAX 4
+#define BDG_TRIM5P_MIN_SCORE_DEFAULT 16   /* measured on the host model, DESIGN 4.15 */
+#define BDG_TRIM_SENSE     4u     /* s[cdna_start:cdna_end] is mRNA sense (5' layout) */
+#define BDG_TRIM_ANCHOR    8u     /* the switch oligo was found: cdna_start is the column behind it */
+#define BDG_TRIM_ANCHOR_ED(flags) (((flags) >> 4) & 7u)   /* its edit distance */
+#define BDG_TRIM_NO_ANCHOR 128u   /* an eligible read of the 5' layout without the oligo: not emitted */
+/* The two values the 5' rule needs beyond tso_min_score, for bdg_trim_batch / bdg_trim_batch_dev and - tso5_max_ed alone, the
+ * UMI length there is the submit's - for the pipelined trim.  Defaults 10 and BDG_TRIM5P_MAX_ED_DEFAULT.  BDG_E_ARG for a
+ * umi_len bdg_extract_batch rejects or tso5_max_ed > BDG_TRIM5P_MAX_ED_MAX.  Read only in BDG_LAYOUT_5P. */
+int  bdg_trim_set_5p(bdg_ctx* ctx, uint32_t umi_len, uint32_t tso5_max_ed);
 
 /* ---- chimeric reads (stage 1's --chimera_cut; the rule restated in badger_amd/chimera.py) ---------------------------- */
 /* An R1 adapter or a TSO, in either orientation, inside what the trim calls cDNA is the junction of two molecules ligated end
@@ -384,7 +438,8 @@ int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* r
  * that row's whitelist_barcode is not '*'.  The sequence is the cDNA in mRNA sense on one line, revcomp(s[cdna_start:cdna_end]):
  * for a BDG_FLAG_REV record the read's own bytes [L - cdna_end, L - cdna_start), for a forward one the reverse complement of
  * read[cdna_start:cdna_end].  Sizing as bdg_format_rows.  counts (may be NULL): records written, of those with BDG_TRIM_TSO,
- * bases written. */
+ * bases written.  A record with BDG_TRIM_SENSE (5' layout) is written as s[cdna_start:cdna_end] as it stands: the read's own bytes
+ * for a forward record, their reverse complement for a BDG_FLAG_REV one; the chimera and tags forms below inherit this. */
 int64_t bdg_format_trimmed(const bdg_ingest_chunk* chunk, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
                            const uint32_t* best_idx, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
                            char* out, uint64_t cap, uint64_t counts[3]);
@@ -466,8 +521,8 @@ typedef struct bdg_stage1_opts {
     const char* corrected_path;   /* the per-read correction file */
     /* read only with BDG_STAGE1_TRIM */
     const char* trimmed_path;     /* the FASTA file of trimmed reads */
-    uint32_t tso_min_score;       /* 8 .. 30 (BDG_TRIM_TSO_MIN_SCORE_DEFAULT) */
-    uint32_t reserved_trim;
+    uint32_t tso_min_score;       /* 8 .. 30 (BDG_TRIM_TSO_MIN_SCORE_DEFAULT); contexts in BDG_LAYOUT_5P: 8 .. 25, the far-end primer's score */
+    uint32_t reserved_trim;       /* contexts in BDG_LAYOUT_5P: tso5_max_ed, 0 .. BDG_TRIM5P_MAX_ED_MAX; not read otherwise */
     /* read only with BDG_STAGE1_CHIMERA */
     uint32_t chimera_max_ed;      /* 0 .. BDG_CHIMERA_MAX_ED_MAX (BDG_CHIMERA_MAX_ED_DEFAULT) */
     uint32_t reserved_chimera;
@@ -495,6 +550,8 @@ typedef struct bdg_stage1_result {
     uint64_t trimmed_reads, trimmed_tso, trimmed_bases;   /* written only with BDG_STAGE1_TRIM: counts[3] of bdg_format_trimmed over the run */
     uint64_t chimera_cut, chimera_dropped, chimera_bases;   /* written only with BDG_STAGE1_CHIMERA: counts[3 .. 5] of bdg_format_trimmed_chimera */
     uint64_t tags_no_cell, tags_not_kept;   /* written only with BDG_STAGE1_TAGS: counts[2 .. 3] of bdg_format_trimmed_tags */
+    uint64_t trimmed_no_anchor;   /* written only with BDG_STAGE1_TRIM on contexts in BDG_LAYOUT_5P (whatever the other bits: the caller's
+                                     struct then reaches to here): reads with BDG_TRIM_NO_ANCHOR */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
