@@ -815,35 +815,30 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         wl_mode |= STAGE1_CHIMERA                   # (without a trimmed_path the library says E_ARG)
     if tags is not None:
         wl_mode |= STAGE1_TAGS                      # (without a trimmed_path the library says E_ARG)
-    args = (umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
-            wl_mode, max_bc_dist, bc_candidates)
+    held = [None] * 5
     if tags is not None:
         held = [np.ascontiguousarray(tags["cell_rank"], dtype=np.uint32), np.ascontiguousarray(tags["cell_has"], dtype=np.uint8)]
         held += [None if tags.get(k) is None else np.ascontiguousarray(tags[k], dtype=t)
                  for k, t in (("molecule", np.uint32), ("mol_reads", np.uint32), ("keep", np.uint8))]
         if len({len(a) for a in held if a is not None}) != 1 or (held[2] is None) != (held[3] is None):
             raise ValueError("stage1_run: the tag arrays differ in length, or molecule comes without mol_reads")
-        o = Stage1OptsTags(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                           os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, tso5_max_ed or 0,
-                           chimera_max_ed if chimera_max_ed is not None else 0, 0,
-                           *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]))
-        res = Stage1ResultTags()
-    elif chimera_max_ed is not None:
-        o = Stage1OptsChimera(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                              os.fsencode(trimmed_path) if trimmed_path is not None else None, tso_min_score, tso5_max_ed or 0, chimera_max_ed, 0)
-        res = Stage1ResultChimera()
-    elif trimmed_path is not None:
-        o = Stage1OptsTrim(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path) if correct else None,
-                           os.fsencode(trimmed_path), tso_min_score, tso5_max_ed or 0)
-        res = Stage1ResultTrim()
-    elif correct:
-        o = Stage1OptsCorrect(*args, bc_edit_bits, bc_min_permille, os.fsencode(corrected_path))
-        res = Stage1ResultCorrect()
-    else:
-        o = Stage1Opts(*args)
-        res = Stage1Result()
+    # the whole struct, with zero or None in what the flags do not enable: the library reads those fields only under their bits
+    o = Stage1OptsTags(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
+                       wl_mode, max_bc_dist, bc_candidates, bc_edit_bits, bc_min_permille,
+                       os.fsencode(corrected_path) if correct else None, os.fsencode(trimmed_path) if trimmed_path is not None else None,
+                       tso_min_score, tso5_max_ed or 0, chimera_max_ed or 0, 0,
+                       *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]) if tags is not None else 0)
+    # the result is as short as the flags allow: the library writes a feature's counts only under its bit
     if tso5_max_ed is not None and trimmed_path is not None:
         res = Stage1Result5p()
+    elif tags is not None:
+        res = Stage1ResultTags()
+    elif chimera_max_ed is not None:
+        res = Stage1ResultChimera()
+    elif trimmed_path is not None:
+        res = Stage1ResultTrim()
+    else:
+        res = Stage1ResultCorrect() if correct else Stage1Result()
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path) if out_path is not None else None, header.encode("ascii"),
                           C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
     if rc != 0:

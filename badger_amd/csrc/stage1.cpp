@@ -1,9 +1,4 @@
-// Stage 1 as one native pipeline, and its row formatter:
-//   bdg_format_rows  one TSV row per read from the device's 32-byte records (TenXBarcodeDetectionResult.__str__,
-//                    barcode_callers.py:40-42,91-93,117-119); the barcode / UMI text is sliced from the chunk's bases, for
-//                    reverse-strand results from the reverse complement (barcode_extraction/common.py:34-39).
-//   bdg_format_trimmed  the trimmed cDNA of a chunk's reads as FASTA text, from the records and the trim results (--trimmed_reads).
-//   bdg_format_trimmed_tags  the same with stage 2's cell, molecule and read count per read in the header (--tagged_reads).
+// Stage 1 as one native pipeline; the text it writes is made by stage1_format.cpp:
 //   bdg_stage1_run   input file -> TSV, everything between in native threads: the readers of ingest.cpp fill pinned chunks,
 //                    this thread submits them to the GPU(s) (bdg_extract_submit / collect, chunk k on context k mod N, two
 //                    in flight per context), a few formatter threads turn records into rows and a writer thread writes them
@@ -14,6 +9,7 @@
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
 #include "host_util.hpp"
+#include "stage1_format.hpp"
 
 #include <fcntl.h>
 
@@ -22,359 +18,185 @@
 #include <condition_variable>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
 namespace {
 
-inline char comp_base(char c)
-{
-    switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return c; }   // N -> N
-}
-
-struct RowStats { uint64_t reads = 0, bc = 0, pt = 0, r1 = 0, first_pt = ~0ull, first_r1 = ~0ull, wl = 0; };
-
-// A chunk's whitelist calls (bdg_format_rows_wl): per read the match's answer, and the whitelist in the caller's order;
-// k > 0: also the k slots of the top-k match per read (bdg_format_rows_wlk)
-struct WlCalls {
-    const uint32_t* idx; const uint8_t* ed; const uint16_t* ties;
-    const uint32_t* wl; uint32_t nw;
-    uint32_t k = 0; const uint32_t* cidx = nullptr; const uint8_t* ced = nullptr;
-};
-constexpr uint64_t WL_COLS_MAX = 1 + 16 + 1 + 3 + 1 + 5;    // "\t" barcode "\t" dist "\t" ties
-constexpr uint64_t WL_CAND_MAX = 16 + 1 + 3 + 1;            // per slot: barcode ":" dist ","
-
-// upper bound of the text of a chunk's rows (+ the headers that fall inside it)
-uint64_t rows_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, uint32_t header_every, size_t header_len,
-                    const WlCalls* wc = nullptr)
-{
-    uint64_t need = wc ? (WL_COLS_MAX + (wc->k ? 2 + WL_CAND_MAX * wc->k : 0)) * ch->n : 0;
-    for (uint32_t i = 0; i < ch->n; ++i) {
-        const uint64_t L = ch->off[i + 1] - ch->off[i];
-        need += (ch->id_off[i + 1] - ch->id_off[i]) + 64 + (recs[i].valid ? 16 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start)) : 2);
-    }
-    if (header_every) need += (ch->n / header_every + 2) * (header_len + 1);
-    return need;
-}
-
-// rows of a chunk whose first read is read g0 of the input; header_every > 0: the header line goes in front of every read
-// whose index is a multiple of it
-char* write_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* o, uint64_t g0, uint32_t header_every,
-                 const char* header, size_t header_len, RowStats& st, const WlCalls* wc = nullptr)
-{
-    constexpr uint32_t AHEAD = 12;              // a row needs one or two lines of its read's bases, nowhere near the last row's: ask early
-    for (uint32_t i = 0; i < ch->n; ++i) {
-        if (header_every && (g0 + i) % header_every == 0) { memcpy(o, header, header_len); o += header_len; *o++ = '\n'; }
-        if (i + AHEAD < ch->n) {
-            const bdg_extract_rec& f = recs[i + AHEAD];
-            if (f.valid) {
-                const uint64_t a = ch->off[i + AHEAD], b = ch->off[i + AHEAD + 1];
-                const uint8_t* q = (f.flags & BDG_FLAG_REV) ? ch->bases + b - 1 - (uint64_t)std::min<int64_t>(f.umi_end, (int64_t)(b - a)) : ch->bases + a + (uint64_t)std::max(f.bc_start, 0);
-                __builtin_prefetch(q); __builtin_prefetch(q + 40);
-            }
-        }
-        const bdg_extract_rec& r = recs[i];
-        const uint8_t* seq = ch->bases + ch->off[i];
-        const int64_t L = (int64_t)(ch->off[i + 1] - ch->off[i]);
-        const size_t idl = (size_t)(ch->id_off[i + 1] - ch->id_off[i]);
-        memcpy(o, ch->ids + ch->id_off[i], idl); o += idl;
-        *o++ = '\t';
-        const bool rev = (r.flags & BDG_FLAG_REV) != 0;
-        auto slice = [&](int64_t a, int64_t b) {                       // Python slice s[a:b] of the strand's text (a, b >= 0)
-            a = std::min<int64_t>(std::max<int64_t>(a, 0), L); b = std::min<int64_t>(std::max<int64_t>(b, 0), L);
-            if (rev) for (int64_t x = a; x < b; ++x) *o++ = comp_base((char)seq[L - 1 - x]);
-            else if (b > a) { memcpy(o, seq + a, (size_t)(b - a)); o += b - a; }
-        };
-        if (r.valid) {
-            slice(r.bc_start, (int64_t)r.bc_start + 16); *o++ = '\t';
-            slice(r.umi_start, r.umi_end);
-            memcpy(o, "\t0\tFalse\t", 9); o += 9;
-            ++st.bc;
-        } else {
-            memcpy(o, "*\t*\t-1\tFalse\t", 13); o += 13;
-        }
-        *o++ = r.strand > 0 ? '+' : (r.strand < 0 ? '-' : '.');
-        *o++ = '\t';
-        o = put_int(o, r.polyT); *o++ = '\t';
-        o = put_int(o, r.valid ? r.r1_end : -1);
-        if (wc) {
-            // no usable barcode, or nothing within max_ed: "*", -1, 0; one entry at the nearest distance: that entry;
-            // several: "*" with the distance and how many
-            const bool usable = r.valid && (r.flags & BDG_FLAG_RANK_OK) && wc->ed[i] != 255u && wc->idx[i] < wc->nw;
-            *o++ = '\t';
-            if (usable && wc->ties[i] == 1) {
-                o = put_barcode16(o, wc->wl[wc->idx[i]]);
-                ++st.wl;
-            } else {
-                *o++ = '*';
-            }
-            *o++ = '\t';
-            o = put_int(o, usable ? (int)wc->ed[i] : -1);
-            *o++ = '\t';
-            o = put_int(o, usable ? (int)wc->ties[i] : 0);
-            if (wc->k) {
-                // the k nearest within max_ed, BARCODE:DIST in slot order; '*' for none or no usable barcode
-                *o++ = '\t';
-                const char* const o0 = o;
-                if (r.valid && (r.flags & BDG_FLAG_RANK_OK)) {
-                    for (uint32_t j = 0; j < wc->k; ++j) {
-                        const size_t at = (size_t)i * wc->k + j;
-                        if (wc->ced[at] == 255u || wc->cidx[at] >= wc->nw) break;
-                        if (o != o0) *o++ = ',';
-                        o = put_barcode16(o, wc->wl[wc->cidx[at]]);
-                        *o++ = ':';
-                        o = put_int(o, (int)wc->ced[at]);
-                    }
-                }
-                if (o == o0) *o++ = '*';
-            }
-        }
-        *o++ = '\n';
-        if (r.polyT != -1) { ++st.pt; if (st.first_pt == ~0ull) st.first_pt = g0 + i; }
-        if (r.valid && r.r1_end != -1) { ++st.r1; if (st.first_r1 == ~0ull) st.first_r1 = g0 + i; }
-    }
-    st.reads += ch->n;
-    return o;
-}
-
-struct TrimStats { uint64_t reads = 0, tso = 0, bases = 0, cut = 0, dropped = 0, cut_bases = 0, no_cell = 0, not_kept = 0, no_anchor = 0; };
-
-// stage 2's answers for the reads of a chunk (bdg_format_trimmed_tags): the cell, the molecule's code and its read count (mol may
-// be null), a filter (may be null)
-struct Tags {
-    const uint32_t* rank; const uint8_t* has; const uint32_t* mol; const uint32_t* mol_reads; const uint8_t* keep;
-    Tags at(uint64_t g0) const { return Tags{ rank + g0, has + g0, mol ? mol + g0 : nullptr, mol_reads ? mol_reads + g0 : nullptr, keep ? keep + g0 : nullptr }; }
-};
-constexpr uint64_t TAG_COLS_MAX = (6 + 16) + (6 + 15) + (6 + 10);   // "\tCB:Z:" cell "\tUB:Z:" molecule "\tRN:i:" count
-
-// upper bound of the FASTA text of a chunk's trimmed reads
-uint64_t trimmed_bound(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, bool with_wl, bool with_ch = false,
-                       bool with_tags = false)
-{
-    uint64_t need = 0;
-    for (uint32_t i = 0; i < ch->n; ++i) {
-        if (!(tr[i].flags & BDG_TRIM_EMIT)) continue;
-        const uint64_t L = ch->off[i + 1] - ch->off[i];
-        need += (ch->id_off[i + 1] - ch->id_off[i]) + 48 + std::min<uint64_t>(L, (uint64_t)std::max(0, recs[i].umi_end - recs[i].umi_start))
-                + (with_wl ? 22 : 0) + (with_ch ? 16 : 0) + (with_tags ? TAG_COLS_MAX : 0) + (uint64_t)std::max(0, tr[i].cdna_end - tr[i].cdna_start);   // (16: the CH field of a cut read)
-    }
-    return need;
-}
-
-// ">id\tCR:Z:barcode\tUR:Z:UMI\tST:A:strand[\tCB:Z:whitelist barcode]\n" cDNA in mRNA sense "\n" per read with BDG_TRIM_EMIT
-// with cm (the chunk's chimera records): a read with a hit ends at its cut and says so in a last field "\tCH:Z:kind,edits";
-// one whose cut is its cDNA's first column is left out
-// with tg (stage 2's answers): a read without a cell, or one the filter drops, is left out; the others get "\tCB:Z:cell" and, with
-// a molecule, "\tUB:Z:molecule\tRN:i:reads" in front of the CH field
-char* write_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* tr, const bdg_chimera_rec* cm,
-                    const WlCalls* wc, char* o, TrimStats& st, const Tags* tg = nullptr)
-{
-    static const char* const kind_name[4] = { "TSO", "TSOrc", "R1", "R1rc" };
-    for (uint32_t i = 0; i < ch->n; ++i) {
-        const bdg_trim_rec& t = tr[i];
-        if (t.flags & BDG_TRIM_NO_ANCHOR) ++st.no_anchor;                  // (5' layout: never with BDG_TRIM_EMIT)
-        if (!(t.flags & BDG_TRIM_EMIT)) continue;
-        const bool hit = cm && (cm[i].flags & BDG_CHIMERA_HIT);
-        const int32_t cend = hit ? cm[i].cut : t.cdna_end;
-        if (hit) {
-            st.cut_bases += (uint64_t)std::max(0, t.cdna_end - cend);
-            if (cend <= t.cdna_start) { ++st.dropped; continue; }
-        }
-        if (tg) {
-            if (!tg->has[i]) { ++st.no_cell; continue; }
-            if (tg->keep && !tg->keep[i]) { ++st.not_kept; continue; }
-        }
-        if (hit) ++st.cut;
-        const bdg_extract_rec& r = recs[i];
-        const uint8_t* seq = ch->bases + ch->off[i];
-        const int64_t L = (int64_t)(ch->off[i + 1] - ch->off[i]);
-        const char* id = ch->ids + ch->id_off[i];
-        size_t idl = (size_t)(ch->id_off[i + 1] - ch->id_off[i]);
-        for (size_t x = 0; x < idl; ++x) if (id[x] == ' ' || id[x] == '\t') { idl = x; break; }     // (the first word, like the reader's ids)
-        *o++ = '>';
-        memcpy(o, id, idl); o += idl;
-        const bool rev = (r.flags & BDG_FLAG_REV) != 0;
-        auto slice = [&](int64_t a, int64_t b) {                       // write_rows' slice: s[a:b] of the strand's text
-            a = std::min<int64_t>(std::max<int64_t>(a, 0), L); b = std::min<int64_t>(std::max<int64_t>(b, 0), L);
-            if (rev) for (int64_t x = a; x < b; ++x) *o++ = comp_base((char)seq[L - 1 - x]);
-            else if (b > a) { memcpy(o, seq + a, (size_t)(b - a)); o += b - a; }
-        };
-        memcpy(o, "\tCR:Z:", 6); o += 6;
-        slice(r.bc_start, (int64_t)r.bc_start + 16);
-        memcpy(o, "\tUR:Z:", 6); o += 6;
-        slice(r.umi_start, r.umi_end);
-        memcpy(o, "\tST:A:", 6); o += 6;
-        *o++ = r.strand > 0 ? '+' : (r.strand < 0 ? '-' : '.');
-        if (wc && r.valid && (r.flags & BDG_FLAG_RANK_OK) && wc->idx[i] < wc->nw && wc->ties[i] == 1) {   // the row's whitelist_barcode is not '*'
-            memcpy(o, "\tCB:Z:", 6); o += 6;
-            o = put_barcode16(o, wc->wl[wc->idx[i]]);
-        }
-        if (tg) {
-            memcpy(o, "\tCB:Z:", 6); o += 6;
-            o = put_barcode16(o, tg->rank[i]);
-            if (tg->mol && tg->mol[i] != 0xFFFFFFFFu) {
-                memcpy(o, "\tUB:Z:", 6); o += 6;
-                o = put_umi_code(o, tg->mol[i]);
-                memcpy(o, "\tRN:i:", 6); o += 6;
-                o = put_uint(o, tg->mol_reads[i]);
-            }
-        }
-        if (hit) {
-            memcpy(o, "\tCH:Z:", 6); o += 6;
-            const char* kn = kind_name[cm[i].hit_kind & 3u];
-            const size_t kl = strlen(kn);
-            memcpy(o, kn, kl); o += kl;
-            *o++ = ',';
-            if (cm[i].hit_ed >= 10) *o++ = (char)('0' + cm[i].hit_ed / 10 % 10);
-            *o++ = (char)('0' + cm[i].hit_ed % 10);
-        }
-        *o++ = '\n';
-        // revcomp(s[a:b]): for a reverse-strand record the read's own bytes, for a forward one their reverse complement;
-        // with BDG_TRIM_SENSE (5' layout) s[a:b] as it stands: the other way round
-        const int64_t a = std::min<int64_t>(std::max<int64_t>(t.cdna_start, 0), L), b = std::min<int64_t>(std::max<int64_t>(cend, 0), L);
-        if (b > a) {
-            if (t.flags & BDG_TRIM_SENSE) slice(a, b);
-            else if (rev) { memcpy(o, seq + (L - b), (size_t)(b - a)); o += b - a; }
-            else for (int64_t x = b - 1; x >= a; --x) *o++ = comp_base((char)seq[x]);
-            st.bases += (uint64_t)(b - a);
-        }
-        *o++ = '\n';
-        ++st.reads;
-        if (t.flags & BDG_TRIM_TSO) ++st.tso;
-    }
-    return o;
-}
+// undoes a step of bdg_stage1_run on every way out, unless the run's own end has done so (run())
+template <class F> struct Guard { F f; bool armed; void run() { if (armed) f(); armed = false; } ~Guard() { run(); } };
+template <class F> Guard(F, bool) -> Guard<F>;
 
 // one chunk on its way through a GPU: its place in the input, the reader's view of it, the context and slot it runs on
 struct Fly { uint64_t seq = 0, g0 = 0; bdg_ingest_chunk ch; bdg_ctx* ctx = nullptr; uint32_t slot = 0; };
 
+// a collected chunk on its way to the formatters, with what the device said about its reads
 struct Job : Fly {
     explicit Job(const Fly& f) : Fly(f) {}
-    struct Results {
-        std::vector<bdg_extract_rec> recs;
-        std::vector<uint32_t> idx; std::vector<uint8_t> ed; std::vector<uint16_t> ties;       // whitelist calls
-        std::vector<uint32_t> cidx; std::vector<uint8_t> ced;                                 // top-k slots (bc_candidates)
-        std::vector<bdg_trim_rec> trim;                                                       // BDG_STAGE1_TRIM
-        std::vector<bdg_chimera_rec> chim;                                                    // BDG_STAGE1_CHIMERA
-    } r;
-    std::vector<char> text; size_t text_len = 0;
-    RowStats st;
+    std::vector<bdg_extract_rec> recs;
+    std::vector<uint32_t> idx; std::vector<uint8_t> ed; std::vector<uint16_t> ties;       // whitelist calls
+    std::vector<uint32_t> cidx; std::vector<uint8_t> ced;                                 // top-k slots (bc_candidates)
+    std::vector<bdg_trim_rec> trim;                                                       // BDG_STAGE1_TRIM
+    std::vector<bdg_chimera_rec> chim;                                                    // BDG_STAGE1_CHIMERA
 };
 
-// the FASTA text of a chunk's trimmed reads on its way to the second writer
-struct TrimText { std::vector<char> text; size_t len = 0; TrimStats st; };
+// What a call of bdg_stage1_run asks for: the bits of opts->whitelist decoded and everything checked, once
+struct Stage1Plan {
+    // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
+    bool wl_on = false, corr = false, trim = false, chim = false, tags = false, trim5p = false, no_tsv = false;
+    // how much of the caller's result is the library's to clear and write (the fields behind whitelist_barcodes only with the
+    // bits that fill them); 0 until the flags and the layout have passed their checks: a call rejected there leaves the result alone
+    size_t result_bytes = 0;
+    uint32_t fthreads = 4, per_ctx = 2;         // formatter threads; chunks in flight per context (BDG_SLOTS >= 2)
+    std::vector<uint32_t> wl;                   // the whitelist in the caller's order, for the formatters
+    Tags all_tags{};                            // BDG_STAGE1_TAGS: the caller's per-read arrays over the whole input
+};
+
+// -> BDG_OK and the plan, or the code to return with its message in the first context
+int make_plan(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, const char* out_path, Stage1Plan& p)
+{
+    bdg_ctx* const c0 = ctxs[0];
+    p.tags = (o->whitelist & BDG_STAGE1_TAGS) != 0;
+    if (!out_path && !p.tags) return BDG_E_ARG;
+    p.trim = (o->whitelist & BDG_STAGE1_TRIM) != 0; p.chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
+    p.wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS)) != 0;
+    p.corr = p.wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT); p.no_tsv = !out_path;
+    if (p.chim && !p.trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_CHIMERA needs BDG_STAGE1_TRIM");
+    if (p.tags && !p.trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS needs BDG_STAGE1_TRIM");
+    if (p.tags && p.wl_on) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS takes no whitelist mode (the cell is the tag)");
+    if (p.tags && o->tag_reads && (!o->tag_cell_rank || !o->tag_cell_has || (o->tag_molecule && !o->tag_mol_reads))) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS: null array");
+    if (p.tags) p.all_tags = Tags{ o->tag_cell_rank, o->tag_cell_has, o->tag_molecule, o->tag_mol_reads, o->tag_keep };
+    // (bdg_extract_set_layout: the caller's, the same on every context)
+    for (uint32_t c = 1; c < n_ctx; ++c) if (!ctxs[c] || ctxs[c]->x_layout != c0->x_layout) return bdg_fail(c0, BDG_E_ARG, "the contexts differ in their layout");
+    p.trim5p = p.trim && c0->x_layout == BDG_LAYOUT_5P;
+    p.result_bytes = offsetof(bdg_stage1_result, whitelist_corrected);
+    if (p.corr) p.result_bytes = offsetof(bdg_stage1_result, trimmed_reads);
+    if (p.trim) p.result_bytes = offsetof(bdg_stage1_result, chimera_cut);
+    if (p.chim) p.result_bytes = offsetof(bdg_stage1_result, tags_no_cell);
+    if (p.tags) p.result_bytes = offsetof(bdg_stage1_result, trimmed_no_anchor);
+    if (p.trim5p) p.result_bytes = sizeof(bdg_stage1_result);
+    if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
+    if (p.chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
+    if (p.trim) {
+        if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
+        if (int rcs = check_tso_min_score(c0, o->tso_min_score)) return rcs;
+        if (p.trim5p && o->reserved_trim > BDG_TRIM5P_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "tso5_max_ed out of range (0 .. 4)");
+    }
+    if (p.wl_on) {
+        // a caller that does not set BDG_STAGE1_WL_CANDIDATES knows bc_candidates as the upper half of a 32-bit max_bc_dist
+        if (o->max_bc_dist > 16 || (!(o->whitelist & BDG_STAGE1_WL_CANDIDATES) && o->bc_candidates)) return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
+        if (o->bc_candidates > 8) return bdg_fail(c0, BDG_E_ARG, "bc_candidates out of range (0 .. 8)");
+        if (p.corr) {
+            static const char* const BAD_OPT[] = { "", "whitelist correction needs max_bc_dist <= 3", "bc_edit_bits out of range (1 .. 8)", "bc_min_permille out of range (501 .. 1000)" };
+            if (const int bad = bdg_check_correct_opts(o->max_bc_dist, o->bc_edit_bits, o->bc_min_permille)) return bdg_fail(c0, BDG_E_ARG, BAD_OPT[bad]);
+            if (!o->corrected_path) return bdg_fail(c0, BDG_E_ARG, "no corrected_path");
+        }
+        // from the first context; every context must hold the same list
+        for (uint32_t c = 0; c < n_ctx; ++c) {
+            if (ctxs[c]->w_n == 0) return bdg_fail(c0, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load) on context " + std::to_string(c));
+            if (ctxs[c]->w_n != c0->w_n || ctxs[c]->w_fp != c0->w_fp) return bdg_fail(c0, BDG_E_ARG, "the contexts hold different whitelists");
+        }
+        p.wl.resize(c0->w_n);
+        for (uint32_t i = 0; i < c0->w_n; ++i) p.wl[c0->w_host_order[i]] = c0->w_host_sorted[i];
+    }
+    if (o->format_threads) p.fthreads = std::min(o->format_threads, 32u);
+    else if (const char* e = getenv("BADGER_AMD_FORMAT_THREADS")) { const long v = atol(e); if (v > 0 && v <= 32) p.fthreads = (uint32_t)v; }
+    if (const char* e = getenv("BADGER_AMD_INFLIGHT")) { const long v = atol(e); if (v >= 1 && v <= BDG_SLOTS) p.per_ctx = (uint32_t)v; }
+    return BDG_OK;
+}
+
+// One output file.  The formatters put a chunk's text into `ready` under the chunk's number, the lane's writer appends the
+// texts in input order.  An fd still open when the lane goes is closed then.
+struct Lane {
+    int fd = -1; bool failed = false;
+    uint64_t next = 0; std::map<uint64_t, std::vector<char>> ready;
+    uint64_t bytes = 0; double seconds = 0;
+    bool close() { const int r = fd >= 0 ? ::close(fd) : 0; fd = -1; return r == 0; }
+    ~Lane() { close(); }
+};
 
 struct Pipeline {
-    bdg_ingest* ing = nullptr;
-    int fd = -1;
-    std::string header;
-    uint32_t header_every = 0;
-    const uint32_t* wl = nullptr; uint32_t nw = 0;             // whitelist in the caller's order (opts->whitelist)
-    uint32_t k = 0;                                            // opts->bc_candidates
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Job*> to_format;
-    std::map<uint64_t, Job*> formatted;
-    uint64_t next_write = 0, outstanding = 0;
-    bool closing = false, write_failed = false;
-    RowStats total;
-    double t_format = 0, t_write = 0;
-    uint64_t out_bytes = 0;
-    // BDG_STAGE1_TRIM: the formatters make a chunk's FASTA text beside its rows, a second writer appends it in input order
-    int fd_trim = -1;
-    std::map<uint64_t, TrimText*> trimmed;
-    uint64_t next_trim = 0;
-    bool trim_write_failed = false;
-    TrimStats trim_total;
-    const Tags* tags = nullptr;                                // BDG_STAGE1_TAGS: per-read arrays over the whole input
-    bool no_tsv = false;                                       // ... with out_path == NULL: no rows are made
+    const Stage1Plan& plan; const bdg_stage1_opts& o; bdg_ingest* ing; const std::string header;
+    std::mutex mu; std::condition_variable cv;
+    std::deque<std::unique_ptr<Job>> to_format;
+    uint64_t outstanding = 0; bool closing = false;
+    RowStats total; TrimStats trim_total; double t_format = 0;
+    Lane tsv, trim;                                            // trim: with BDG_STAGE1_TRIM a chunk's FASTA text is made beside its rows
+    std::vector<std::thread> threads;
 
+    void start(uint32_t fthreads)
+    {
+        for (uint32_t i = 0; i < fthreads; ++i) threads.emplace_back(&Pipeline::format_loop, this);
+        threads.emplace_back(&Pipeline::write_loop, this, std::ref(tsv));
+        if (plan.trim) threads.emplace_back(&Pipeline::write_loop, this, std::ref(trim));
+    }
+    // every queued chunk formatted and written, the threads gone: before that no lane may close its file
+    void finish()
+    {
+        { std::lock_guard<std::mutex> lk(mu); closing = true; }
+        cv.notify_all();
+        for (auto& t : threads) t.join();
+        threads.clear();
+    }
+    ~Pipeline() { finish(); }
     void format_loop()
     {
         for (;;) {
-            Job* j;
+            std::unique_ptr<Job> j;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return closing || !to_format.empty(); });
                 if (to_format.empty()) return;
-                j = to_format.front(); to_format.pop_front();
+                j = std::move(to_format.front()); to_format.pop_front();
             }
             const double t0 = now_s();
-            const WlCalls wc{ j->r.idx.data(), j->r.ed.data(), j->r.ties.data(), wl, nw, k, j->r.cidx.data(), j->r.ced.data() };
-            const WlCalls* pw = wl ? &wc : nullptr;
-            if (!no_tsv) {
-                j->text.resize((size_t)rows_bound(&j->ch, j->r.recs.data(), header_every, header.size(), pw));
-                char* e = write_rows(&j->ch, j->r.recs.data(), j->text.data(), j->g0, header_every, header.data(), header.size(), j->st, pw);
-                j->text_len = (size_t)(e - j->text.data());
-            } else {
-                j->st.reads = j->ch.n;
-            }
-            TrimText* tt = nullptr;
-            if (fd_trim >= 0) {
-                tt = new TrimText;
-                const Tags tg = tags ? tags->at(j->g0) : Tags{};
-                tt->text.resize((size_t)trimmed_bound(&j->ch, j->r.recs.data(), j->r.trim.data(), pw != nullptr, !j->r.chim.empty(), tags != nullptr));
-                tt->len = (size_t)(write_trimmed(&j->ch, j->r.recs.data(), j->r.trim.data(), j->r.chim.empty() ? nullptr : j->r.chim.data(), pw, tt->text.data(), tt->st,
-                                                 tags ? &tg : nullptr) - tt->text.data());
+            const WlCalls wc{ j->idx.data(), j->ed.data(), j->ties.data(), plan.wl.data(), (uint32_t)plan.wl.size(), o.bc_candidates, j->cidx.data(), j->ced.data() };
+            const WlCalls* pw = plan.wl_on ? &wc : nullptr;
+            std::vector<char> rows, fasta; RowStats rs; TrimStats ts;
+            if (!plan.no_tsv) {
+                rows.resize((size_t)rows_bound(&j->ch, j->recs.data(), o.header_every, header.size(), pw));
+                rows.resize((size_t)(write_rows(&j->ch, j->recs.data(), rows.data(), j->g0, o.header_every, header.data(), header.size(), rs, pw) - rows.data()));
+            } else rs.reads = j->ch.n;
+            if (plan.trim) {
+                const Tags tg = plan.tags ? plan.all_tags.at(j->g0) : Tags{};      // (the tag arrays cover the whole input)
+                const bdg_chimera_rec* cm = j->chim.empty() ? nullptr : j->chim.data();
+                fasta.resize((size_t)trimmed_bound(&j->ch, j->recs.data(), j->trim.data(), pw != nullptr, cm != nullptr, plan.tags));
+                fasta.resize((size_t)(write_trimmed(&j->ch, j->recs.data(), j->trim.data(), cm, pw, fasta.data(), ts, plan.tags ? &tg : nullptr) - fasta.data()));
             }
             bdg_ingest_release(ing, j->ch.id);
-            j->r = Job::Results();                             // (their memory goes back now, not when the row text is written)
+            const uint64_t seq = j->seq;
+            j.reset();                                         // (the results' memory goes back now, not when the text is written)
             const double dt = now_s() - t0;
             {
                 std::lock_guard<std::mutex> lk(mu);
-                if (tt) trimmed[j->seq] = tt;
-                formatted[j->seq] = j;
+                if (plan.trim) trim.ready[seq] = std::move(fasta);
+                tsv.ready[seq] = std::move(rows);
+                total += rs; trim_total += ts;
                 --outstanding;
                 t_format += dt;
             }
             cv.notify_all();
         }
     }
-    void write_loop()
+    // the writer of a lane: the texts in input order, to the end of the run whatever fails (a lane without a file drops them)
+    void write_loop(Lane& ln)
     {
         for (;;) {
-            Job* j;
+            std::vector<char> text;
             {
                 std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return (closing && to_format.empty() && outstanding == 0 && formatted.empty()) || formatted.count(next_write); });
-                auto it = formatted.find(next_write);
-                if (it == formatted.end()) return;
-                j = it->second; formatted.erase(it); ++next_write;
+                cv.wait(lk, [&] { return (closing && to_format.empty() && outstanding == 0 && ln.ready.empty()) || ln.ready.count(ln.next); });
+                auto it = ln.ready.find(ln.next);
+                if (it == ln.ready.end()) return;
+                text = std::move(it->second); ln.ready.erase(it); ++ln.next;
             }
             const double t0 = now_s();
-            const bool bad = fd >= 0 && !write_all(fd, j->text.data(), j->text_len);
+            const bool bad = ln.fd >= 0 && !write_all(ln.fd, text.data(), text.size());
             const double dt = now_s() - t0;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (bad) write_failed = true;
-                total.reads += j->st.reads; total.bc += j->st.bc; total.pt += j->st.pt; total.r1 += j->st.r1;
-                total.first_pt = std::min(total.first_pt, j->st.first_pt); total.first_r1 = std::min(total.first_r1, j->st.first_r1);
-                total.wl += j->st.wl;
-                t_write += dt; out_bytes += j->text_len;
-            }
-            delete j;
-        }
-    }
-    void trim_write_loop()
-    {
-        for (;;) {
-            TrimText* t;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return (closing && to_format.empty() && outstanding == 0 && trimmed.empty()) || trimmed.count(next_trim); });
-                auto it = trimmed.find(next_trim);
-                if (it == trimmed.end()) return;
-                t = it->second; trimmed.erase(it); ++next_trim;
-            }
-            const bool bad = !write_all(fd_trim, t->text.data(), t->len);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (bad) trim_write_failed = true;
-                trim_total.reads += t->st.reads; trim_total.tso += t->st.tso; trim_total.bases += t->st.bases;
-                trim_total.cut += t->st.cut; trim_total.dropped += t->st.dropped; trim_total.cut_bases += t->st.cut_bases;
-                trim_total.no_cell += t->st.no_cell; trim_total.not_kept += t->st.not_kept; trim_total.no_anchor += t->st.no_anchor;
-            }
-            delete t;
+            std::lock_guard<std::mutex> lk(mu);
+            if (bad) ln.failed = true;
+            ln.seconds += dt; ln.bytes += text.size();
         }
     }
 };
@@ -493,279 +315,118 @@ int correct_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, 
     return BDG_OK;
 }
 
-// the one body of bdg_format_rows, _wl (wc) and _wlk (wc->k): counts = 4 numbers, 5 with wc
-int64_t format_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const WlCalls* wc, char* out, uint64_t cap, uint64_t* counts)
-{
-    if (!ch || (ch->n && (!recs || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
-    if (wc && ch->n && (!wc->idx || !wc->ed || !wc->ties || (wc->k && (!wc->cidx || !wc->ced)))) return BDG_E_ARG;
-    if (wc && wc->nw && !wc->wl) return BDG_E_ARG;
-    const uint64_t need = rows_bound(ch, recs, 0, 0, wc);
-    if (!out || need > cap) return (int64_t)need;
-    RowStats st;
-    char* e = write_rows(ch, recs, out, 0, 0, nullptr, 0, st, wc);
-    if (counts) { counts[0] = ch->n; counts[1] = st.bc; counts[2] = st.pt; counts[3] = st.r1; if (wc) counts[4] = st.wl; }
-    return (int64_t)(e - out);
-}
-
 }  // namespace
 
 extern "C" {
-
-int64_t bdg_format_rows(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, char* out, uint64_t cap, uint64_t counts[4])
-{
-    return format_rows(ch, recs, nullptr, out, cap, counts);
-}
-
-int64_t bdg_format_rows_wl(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const uint32_t* best_idx,
-                           const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
-                           char* out, uint64_t cap, uint64_t counts[5])
-{
-    const WlCalls wc{ best_idx, best_ed, n_ties, wl, nw };
-    return format_rows(ch, recs, &wc, out, cap, counts);
-}
-
-int64_t bdg_format_rows_wlk(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const uint32_t* best_idx,
-                            const uint8_t* best_ed, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
-                            uint32_t k, const uint32_t* cand_idx, const uint8_t* cand_ed,
-                            char* out, uint64_t cap, uint64_t counts[5])
-{
-    if (k == 0 || k > 8) return BDG_E_ARG;
-    const WlCalls wc{ best_idx, best_ed, n_ties, wl, nw, k, cand_idx, cand_ed };
-    return format_rows(ch, recs, &wc, out, cap, counts);
-}
-
-int64_t bdg_format_trimmed(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
-                           const uint32_t* best_idx, const uint16_t* n_ties, const uint32_t* wl, uint32_t nw,
-                           char* out, uint64_t cap, uint64_t counts[3])
-{
-    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
-    const bool with_wl = best_idx || n_ties || wl;
-    if (with_wl && ch->n && (!best_idx || !n_ties || (nw && !wl))) return BDG_E_ARG;
-    const WlCalls wc{ best_idx, nullptr, n_ties, wl, nw };
-    const uint64_t need = trimmed_bound(ch, recs, trim, with_wl);
-    if (!out || need > cap) return (int64_t)need;
-    TrimStats st;
-    char* e = write_trimmed(ch, recs, trim, nullptr, with_wl ? &wc : nullptr, out, st);
-    if (counts) { counts[0] = st.reads; counts[1] = st.tso; counts[2] = st.bases; }
-    return (int64_t)(e - out);
-}
-
-int64_t bdg_format_trimmed_chimera(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
-                                   const bdg_chimera_rec* chim, const uint32_t* best_idx, const uint16_t* n_ties,
-                                   const uint32_t* wl, uint32_t nw, char* out, uint64_t cap, uint64_t counts[6])
-{
-    if (!chim) return bdg_format_trimmed(ch, recs, trim, best_idx, n_ties, wl, nw, out, cap, counts);
-    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
-    const bool with_wl = best_idx || n_ties || wl;
-    if (with_wl && ch->n && (!best_idx || !n_ties || (nw && !wl))) return BDG_E_ARG;
-    const WlCalls wc{ best_idx, nullptr, n_ties, wl, nw };
-    const uint64_t need = trimmed_bound(ch, recs, trim, with_wl, true);
-    if (!out || need > cap) return (int64_t)need;
-    TrimStats st;
-    char* e = write_trimmed(ch, recs, trim, chim, with_wl ? &wc : nullptr, out, st);
-    if (counts) { counts[0] = st.reads; counts[1] = st.tso; counts[2] = st.bases; counts[3] = st.cut; counts[4] = st.dropped; counts[5] = st.cut_bases; }
-    return (int64_t)(e - out);
-}
-
-int64_t bdg_format_trimmed_tags(const bdg_ingest_chunk* ch, const bdg_extract_rec* recs, const bdg_trim_rec* trim,
-                                const bdg_chimera_rec* chim, const uint32_t* cell_rank, const uint8_t* cell_has,
-                                const uint32_t* molecule, const uint32_t* mol_reads, const uint8_t* keep,
-                                char* out, uint64_t cap, uint64_t counts[4])
-{
-    if (!ch || (ch->n && (!recs || !trim || !ch->bases || !ch->off || !ch->ids || !ch->id_off))) return BDG_E_ARG;
-    if (ch->n && (!cell_rank || !cell_has || (molecule && !mol_reads))) return BDG_E_ARG;
-    const uint64_t need = trimmed_bound(ch, recs, trim, false, chim != nullptr, true);
-    if (!out || need > cap) return (int64_t)need;
-    const Tags tg{ cell_rank, cell_has, molecule, mol_reads, keep };
-    TrimStats st;
-    char* e = write_trimmed(ch, recs, trim, chim, nullptr, out, st, &tg);
-    if (counts) { counts[0] = st.reads; counts[1] = st.bases; counts[2] = st.no_cell; counts[3] = st.not_kept; }
-    return (int64_t)(e - out);
-}
 
 int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                    const bdg_stage1_opts* o, bdg_stage1_result* res)
 {
     if (!ctxs || n_ctx == 0 || !ctxs[0] || !in_path || !header || !o || !res) return BDG_E_ARG;
     bdg_ctx* const c0 = ctxs[0];
-    const bool tags = (o->whitelist & BDG_STAGE1_TAGS) != 0;
-    if (!out_path && !tags) return BDG_E_ARG;
-    // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
-    const bool trim = (o->whitelist & BDG_STAGE1_TRIM) != 0, wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS)) != 0;
-    const bool chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
-    if (chim && !trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_CHIMERA needs BDG_STAGE1_TRIM");
-    if (tags && !trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS needs BDG_STAGE1_TRIM");
-    if (tags && wl_on) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS takes no whitelist mode (the cell is the tag)");
-    if (tags && o->tag_reads && (!o->tag_cell_rank || !o->tag_cell_has || (o->tag_molecule && !o->tag_mol_reads)))
-        return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS: null array");
-    const bool corr = wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT);
-    const int layout = c0->x_layout;                                   // bdg_extract_set_layout: the caller's, the same on every context
-    for (uint32_t c = 1; c < n_ctx; ++c) if (!ctxs[c] || ctxs[c]->x_layout != layout) return bdg_fail(c0, BDG_E_ARG, "the contexts differ in their layout");
-    const bool trim5p = trim && layout == BDG_LAYOUT_5P;
-    // (the fields behind whitelist_barcodes are the caller's only with BDG_STAGE1_WL_CORRECT, those behind it with BDG_STAGE1_TRIM)
-    memset(res, 0, trim5p ? sizeof(*res) : tags ? offsetof(bdg_stage1_result, trimmed_no_anchor) : chim ? offsetof(bdg_stage1_result, tags_no_cell) : trim ? offsetof(bdg_stage1_result, chimera_cut) : corr ? offsetof(bdg_stage1_result, trimmed_reads) : offsetof(bdg_stage1_result, whitelist_corrected));
-    res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
-    if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
-    if (chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
-    if (trim) {
-        if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
-        if (int rcs = check_tso_min_score(c0, o->tso_min_score)) return rcs;
-        if (trim5p && o->reserved_trim > BDG_TRIM5P_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "tso5_max_ed out of range (0 .. 4)");
-    }
-    // the whitelist in the caller's order, for the formatters: from the first context; every context must hold the same list
-    std::vector<uint32_t> wl_caller;
-    if (wl_on) {
-        // a caller that does not set BDG_STAGE1_WL_CANDIDATES knows bc_candidates as the upper half of a 32-bit max_bc_dist
-        if (o->max_bc_dist > 16 || (!(o->whitelist & BDG_STAGE1_WL_CANDIDATES) && o->bc_candidates))
-            return bdg_fail(c0, BDG_E_ARG, "max_bc_dist out of range (0 .. 16)");
-        if (o->bc_candidates > 8) return bdg_fail(c0, BDG_E_ARG, "bc_candidates out of range (0 .. 8)");
-        if (o->whitelist & BDG_STAGE1_WL_CORRECT) {
-            static const char* const BAD_OPT[] = { "", "whitelist correction needs max_bc_dist <= 3", "bc_edit_bits out of range (1 .. 8)",
-                                                   "bc_min_permille out of range (501 .. 1000)" };
-            if (const int bad = bdg_check_correct_opts(o->max_bc_dist, o->bc_edit_bits, o->bc_min_permille)) return bdg_fail(c0, BDG_E_ARG, BAD_OPT[bad]);
-            if (!o->corrected_path) return bdg_fail(c0, BDG_E_ARG, "no corrected_path");
-        }
-        for (uint32_t c = 0; c < n_ctx; ++c) {
-            if (!ctxs[c]) return BDG_E_ARG;
-            if (ctxs[c]->w_n == 0) return bdg_fail(c0, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load) on context " + std::to_string(c));
-            if (ctxs[c]->w_n != c0->w_n || ctxs[c]->w_fp != c0->w_fp)
-                return bdg_fail(c0, BDG_E_ARG, "the contexts hold different whitelists");
-        }
-        wl_caller.resize(c0->w_n);
-        for (uint32_t i = 0; i < c0->w_n; ++i) wl_caller[c0->w_host_order[i]] = c0->w_host_sorted[i];
-    }
-    // correction: every context keeps its reads' candidate lists and counts exact hits; the read ids are kept for the file
+    auto every_ctx = [&](auto f) { for (uint32_t c = 0; c < n_ctx; ++c) f(ctxs[c]); };
+    // ---- plan
+    Stage1Plan plan; const int rc_plan = make_plan(ctxs, n_ctx, o, out_path, plan);
+    if (plan.result_bytes) { memset(res, 0, plan.result_bytes); res->first_polyt = res->first_r1 = res->bad_read = ~0ull; }
+    if (rc_plan) return rc_plan;
+    const bool wl_on = plan.wl_on, trim = plan.trim, chim = plan.chim, tags = plan.tags;
+    if (!out_path) out_path = "(no TSV)";
+    // ---- open: the correction on every context (each keeps its reads' candidate lists and counts exact hits, the read ids are
+    // kept for the file), the reader, the two files, the contexts' trim.  From here on every way out just returns
     bdg_idstore* ids = nullptr;
-    auto corr_end = [&]() {
-        for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_correct_end(ctxs[c]);
-        bdg_idstore_free(ids); ids = nullptr;
-    };
-    if (corr) {
-        for (uint32_t c = 0; c < n_ctx; ++c) {
-            const int r = bdg_correct_begin(ctxs[c]);
-            if (r) { const std::string m = bdg_last_error(ctxs[c]); corr_end(); return bdg_fail(c0, r, m); }
-        }
+    Guard corr_end{ [&] { every_ctx([](bdg_ctx* c) { (void)bdg_correct_end(c); }); bdg_idstore_free(ids); ids = nullptr; }, plan.corr };
+    if (plan.corr) {
+        for (uint32_t c = 0; c < n_ctx; ++c) if (const int r = bdg_correct_begin(ctxs[c])) return bdg_fail(c0, r, std::string(bdg_last_error(ctxs[c])));
         ids = bdg_idstore_new();
     }
     const double t_start = now_s();
-    uint32_t fthreads = o->format_threads ? std::min(o->format_threads, 32u) : 4u;
-    if (!o->format_threads) if (const char* e = getenv("BADGER_AMD_FORMAT_THREADS")) { const long v = atol(e); if (v > 0 && v <= 32) fthreads = (uint32_t)v; }
-    uint32_t per_ctx = 2;                                        // chunks in flight per context (BDG_SLOTS >= 2)
-    if (const char* e = getenv("BADGER_AMD_INFLIGHT")) { const long v = atol(e); if (v >= 1 && v <= BDG_SLOTS) per_ctx = (uint32_t)v; }
-    const uint64_t max_outstanding = 2 * fthreads + 2;           // collected chunks waiting for / in the formatters
-    Pipeline P;
-    ChunkLoop L{ nullptr, ctxs, n_ctx, per_ctx, o->umi_len, res, wl_on ? o : nullptr, ids, false, false };
-    int rc = open_reader(in_path, o, per_ctx * n_ctx + 2 * fthreads + 4, &P.ing, L.err);
-    if (rc) { if (corr) corr_end(); return bdg_fail(c0, rc, L.err); }
-    L.ing = P.ing;
-    const Tags all_tags = tags ? Tags{ o->tag_cell_rank, o->tag_cell_has, o->tag_molecule, o->tag_mol_reads, o->tag_keep } : Tags{};
-    if (tags) { P.tags = &all_tags; P.no_tsv = !out_path; }
-    if (!out_path) out_path = "(no TSV)";
-    if (!P.no_tsv) P.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (P.fd < 0 && !P.no_tsv) { bdg_ingest_close(P.ing); if (corr) corr_end(); return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path); }
-    P.header = header; P.header_every = o->header_every;
-    if (wl_on) { P.wl = wl_caller.data(); P.nw = (uint32_t)wl_caller.size(); P.k = o->bc_candidates; }
-    if (trim) {
-        P.fd_trim = ::open(o->trimmed_path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-        if (P.fd_trim < 0) {
-            if (P.fd >= 0) ::close(P.fd);
-            bdg_ingest_close(P.ing); if (corr) corr_end();
-            return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
-        }
-        for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 1, o->tso_min_score);   // (checked above; off again below)
-        if (trim5p) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_trim_set_5p(ctxs[c], o->umi_len, o->reserved_trim);
-        if (chim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_chimera(ctxs[c], 1, o->chimera_max_ed);
-    }
-    bool ok_io = true;
-    if (!o->header_every && !P.no_tsv) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1);
-    std::vector<std::thread> fmt;
-    for (uint32_t i = 0; i < fthreads; ++i) fmt.emplace_back(&Pipeline::format_loop, &P);
-    std::thread writer(&Pipeline::write_loop, &P);
-    std::thread trim_writer;
-    if (trim) trim_writer = std::thread(&Pipeline::trim_write_loop, &P);
-
+    const uint64_t max_outstanding = 2 * plan.fthreads + 2;      // collected chunks waiting for / in the formatters
+    ChunkLoop L{ nullptr, ctxs, n_ctx, plan.per_ctx, o->umi_len, res, wl_on ? o : nullptr, ids, false, false };
+    int rc = open_reader(in_path, o, plan.per_ctx * n_ctx + 2 * plan.fthreads + 4, &L.ing, L.err);
+    if (rc) return bdg_fail(c0, rc, L.err);
+    Guard close_reader{ [&] { bdg_ingest_close(L.ing); }, true };
+    Pipeline P{ plan, *o, L.ing, header };                       // (behind the reader: its threads are gone before the reader is)
+    if (!plan.no_tsv && (P.tsv.fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+        return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + out_path);
+    if (trim && (P.trim.fd = ::open(o->trimmed_path, O_WRONLY | O_CREAT | O_TRUNC, 0666)) < 0)
+        return bdg_fail(c0, BDG_E_ARG, std::string("cannot write ") + o->trimmed_path);
+    Guard trim_off{ [&] { every_ctx([](bdg_ctx* c) { (void)bdg_extract_set_trim(c, 0, 0); }); }, trim };
+    if (trim) every_ctx([&](bdg_ctx* c) {                        // (the values are checked in the plan)
+        (void)bdg_extract_set_trim(c, 1, o->tso_min_score);
+        if (plan.trim5p) (void)bdg_trim_set_5p(c, o->umi_len, o->reserved_trim);
+        if (chim) (void)bdg_extract_set_chimera(c, 1, o->chimera_max_ed);
+    });
+    // ---- start
+    const std::string header_line = P.header + "\n";
+    bool ok_io = o->header_every || plan.no_tsv || write_all(P.tsv.fd, header_line.data(), header_line.size());
+    P.start(plan.fthreads);
+    // ---- loop
     double t_fmt_wait = 0;
     rc = L.run([&](const Fly& f, std::vector<bdg_extract_rec>& recs) -> int {   // with the match's answer, to the formatters
         // (the formatters index the tag arrays by the read's place in the input: no chunk may reach past them)
         if (tags && f.g0 + f.ch.n > o->tag_reads)
             return bdg_fail(f.ctx, BDG_E_ARG, "the input holds more reads than the " + std::to_string(o->tag_reads) + " the tag arrays hold");
-        Job* j = new Job(f);
-        j->r.recs.swap(recs);
+        auto j = std::make_unique<Job>(f);
+        j->recs.swap(recs);
         if (trim) {
-            j->r.trim.resize(f.ch.n);
-            const int r = bdg_extract_collect_trim(f.ctx, f.slot, j->r.trim.data());
-            if (r) { delete j; return r; }
+            j->trim.resize(f.ch.n);
+            if (const int r = bdg_extract_collect_trim(f.ctx, f.slot, j->trim.data())) return r;
             if (chim && f.ch.n) {
-                j->r.chim.resize(f.ch.n);
-                const int r2 = bdg_extract_collect_chimera(f.ctx, f.slot, j->r.chim.data());
-                if (r2) { delete j; return r2; }
+                j->chim.resize(f.ch.n);
+                if (const int r = bdg_extract_collect_chimera(f.ctx, f.slot, j->chim.data())) return r;
             }
         }
         if (wl_on) {
-            j->r.idx.resize(f.ch.n); j->r.ed.resize(f.ch.n); j->r.ties.resize(f.ch.n);
-            j->r.cidx.resize((size_t)f.ch.n * o->bc_candidates); j->r.ced.resize((size_t)f.ch.n * o->bc_candidates);
+            j->idx.resize(f.ch.n); j->ed.resize(f.ch.n); j->ties.resize(f.ch.n);
+            j->cidx.resize((size_t)f.ch.n * o->bc_candidates); j->ced.resize((size_t)f.ch.n * o->bc_candidates);
             const double t0 = now_s();
-            const int r = bdg_slot_match_collect_topk(f.ctx, f.slot, j->r.idx.data(), j->r.ed.data(), j->r.ties.data(),
-                                                      j->r.cidx.data(), j->r.ced.data());
+            const int r = bdg_slot_match_collect_topk(f.ctx, f.slot, j->idx.data(), j->ed.data(), j->ties.data(), j->cidx.data(), j->ced.data());
             res->seconds_wait_gpu += now_s() - t0;
-            if (r) { delete j; return r; }
+            if (r) return r;
         }
         const double t1 = now_s();
         {
             std::unique_lock<std::mutex> lk(P.mu);
             P.cv.wait(lk, [&] { return P.outstanding < max_outstanding; });
             ++P.outstanding;
-            P.to_format.push_back(j);
+            P.to_format.push_back(std::move(j));
         }
         P.cv.notify_all();
         t_fmt_wait += now_s() - t1;
         return BDG_OK;
     });
-    if (wl_on) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_synchronize(ctxs[c]);    // (a match still queued after a failure)
-    if (trim) for (uint32_t c = 0; c < n_ctx; ++c) (void)bdg_extract_set_trim(ctxs[c], 0, 0);
-    { std::lock_guard<std::mutex> lk(P.mu); P.closing = true; }
-    P.cv.notify_all();
-    for (auto& t : fmt) t.join();
-    writer.join();
-    if (trim) {
-        trim_writer.join();
-        if (::close(P.fd_trim) != 0) P.trim_write_failed = true;
-        res->trimmed_reads = P.trim_total.reads; res->trimmed_tso = P.trim_total.tso; res->trimmed_bases = P.trim_total.bases;
-        if (chim) { res->chimera_cut = P.trim_total.cut; res->chimera_dropped = P.trim_total.dropped; res->chimera_bases = P.trim_total.cut_bases; }
-        if (tags) { res->tags_no_cell = P.trim_total.no_cell; res->tags_not_kept = P.trim_total.not_kept; }
-        if (trim5p) res->trimmed_no_anchor = P.trim_total.no_anchor;
-    }
+    // ---- join: the contexts as they were, the threads gone, the files closed (a close that fails is a write error)
+    if (wl_on) every_ctx([](bdg_ctx* c) { (void)bdg_synchronize(c); });    // (a match still queued after a failure)
+    trim_off.run();
+    P.finish();
+    if (!P.trim.close()) P.trim.failed = true;
     // rows of the chunks before a failure are in the file, like in the reference's loop
-    if (rc == BDG_OK && !P.no_tsv && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.fd, (P.header + "\n").data(), P.header.size() + 1) && ok_io;
-    if (!P.no_tsv && ::close(P.fd) != 0) ok_io = false;
-    if (rc == BDG_OK && tags && L.g0 != o->tag_reads) {
-        rc = BDG_E_ARG;
-        L.err = "the input holds " + std::to_string(L.g0) + " reads, the tag arrays " + std::to_string(o->tag_reads);
-    }
+    if (rc == BDG_OK && !plan.no_tsv && o->header_every && L.g0 % o->header_every == 0) ok_io = write_all(P.tsv.fd, header_line.data(), header_line.size()) && ok_io;
+    if (!P.tsv.close()) ok_io = false;
+    if (rc == BDG_OK && tags && L.g0 != o->tag_reads) { rc = BDG_E_ARG; L.err = "the input holds " + std::to_string(L.g0) + " reads, the tag arrays " + std::to_string(o->tag_reads); }
     const double t_close0 = now_s();
-    bdg_ingest_close(P.ing);
+    close_reader.run();
     if (getenv("BADGER_AMD_INGEST_DEBUG")) {
-        double t[5];
-        bdg_submit_times(t);
+        double t[5]; bdg_submit_times(t);
         fprintf(stderr, "stage1: reader closed in %.3f s; %d submits: reserve %.3f s, offsets %.3f s, copies %.3f s, launches + D2H %.3f s\n", now_s() - t_close0,
                 (int)t[4], t[0], t[1], t[2], t[3]);
     }
-    res->reads = P.total.reads; res->barcodes = P.total.bc; res->polyt = P.total.pt; res->r1 = P.total.r1;
-    res->first_polyt = P.total.first_pt; res->first_r1 = P.total.first_r1; res->bad_read = L.bad_read;
-    res->chunks = L.chunk_n.size(); res->out_bytes = P.out_bytes; res->whitelist_barcodes = P.total.wl;
+    // ---- report: the merged counts, one block per feature, then the correction over the whole run
+    const RowStats& T = P.total; const TrimStats& X = P.trim_total;
+    res->reads = T.reads; res->barcodes = T.bc; res->polyt = T.pt; res->r1 = T.r1;
+    res->first_polyt = T.first_pt; res->first_r1 = T.first_r1; res->bad_read = L.bad_read;
+    res->chunks = L.chunk_n.size(); res->out_bytes = P.tsv.bytes; res->whitelist_barcodes = T.wl;
+    res->seconds_wait_format = t_fmt_wait; res->seconds_format = P.t_format; res->seconds_write = P.tsv.seconds;
+    if (trim) { res->trimmed_reads = X.reads; res->trimmed_tso = X.tso; res->trimmed_bases = X.bases; }
+    if (chim) { res->chimera_cut = X.cut; res->chimera_dropped = X.dropped; res->chimera_bases = X.cut_bases; }
+    if (tags) { res->tags_no_cell = X.no_cell; res->tags_not_kept = X.not_kept; }
+    if (plan.trim5p) res->trimmed_no_anchor = X.no_anchor;
+    if (plan.corr && rc == BDG_OK && ok_io && !P.tsv.failed) rc = correct_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, plan.wl.data(), (uint32_t)plan.wl.size(), res, L.err);
+    corr_end.run();
     res->seconds_total = now_s() - t_start;
-    res->seconds_wait_format = t_fmt_wait; res->seconds_format = P.t_format; res->seconds_write = P.t_write;
-    if (corr) {
-        if (rc == BDG_OK && ok_io && !P.write_failed) {
-            int rcc = correct_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, P.wl, P.nw, res, L.err);
-            if (rcc) rc = rcc;
-        }
-        corr_end();
-        res->seconds_total = now_s() - t_start;
-    }
     if (rc) return bdg_fail(c0, rc, L.err);
-    if (!ok_io || P.write_failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + out_path);
-    if (P.trim_write_failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + o->trimmed_path);
+    if (!ok_io || P.tsv.failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + out_path);
+    if (P.trim.failed) return bdg_fail(c0, BDG_E_ARG, std::string("write error on ") + o->trimmed_path);
     return BDG_OK;
 }
 
@@ -782,8 +443,7 @@ int bdg_stage1_collect(bdg_ctx* ctx, const char* in_path, const bdg_stage1_opts*
     rc = L.run([&](const Fly& f, std::vector<bdg_extract_rec>&) -> int { bdg_ingest_release(L.ing, f.ch.id); return BDG_OK; });   // (the records stay on the device)
     bdg_ingest_close(L.ing);
     res->reads = L.g0; res->chunks = L.chunk_n.size(); res->bad_read = L.bad_read; res->seconds_total = now_s() - t_start;
-    if (rc) return bdg_fail(ctx, rc, L.err);
-    return BDG_OK;
+    return rc ? bdg_fail(ctx, rc, L.err) : BDG_OK;
 }
 
 }  // extern "C"

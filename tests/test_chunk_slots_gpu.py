@@ -7,24 +7,13 @@ import numpy as np
 import pytest
 
 from badger_amd import _native, synth
+from ingest_chunk import Chunk as _Chunk
 
 pytestmark = pytest.mark.gpu
 
 N, W, K, MAX_BC_DIST, TSO_MIN, CHIM_ED = 2000, 2000, 3, 2, 20, 3
 HEADER = ("#read_id\tbarcode\tUMI\tBC_score\tvalid_UMI\tstrand\tpolyT_start\tR1_end\twhitelist_barcode\twhitelist_dist\twhitelist_ties"
           "\twhitelist_candidates")
-
-
-class _Chunk:
-    """a bdg_ingest_chunk over numpy buffers (kept alive here)"""
-
-    def __init__(self, ids, bases, off):
-        self.bases = np.concatenate([bases, np.zeros(64, np.uint8)])
-        self.off = np.ascontiguousarray(off, dtype=np.uint64)
-        self.ids = np.frombuffer("".join(ids).encode() + b"\0", dtype=np.uint8).copy()
-        self.id_off = np.cumsum([0] + [len(i) for i in ids]).astype(np.uint64)
-        self.ch = _native.IngestChunk(0, len(ids), self.bases.ctypes.data, self.off.ctypes.data, int(self.off[-1]),
-                                      self.ids.ctypes.data, self.id_off.ctypes.data)
 
 
 @pytest.fixture(scope="module")

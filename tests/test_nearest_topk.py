@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from badger_amd import _native, common, extract_raw_barcodes as erb
+from ingest_chunk import Chunk as _Chunk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -78,16 +79,6 @@ def test_stage1_opts_carries_bc_candidates():
 
 
 # ---- the column ---------------------------------------------------------------------------------------------------------
-class _Chunk:
-    def __init__(self, ids, seqs):
-        self.bases = np.frombuffer(("".join(seqs)).encode() + b"\0" * 64, dtype=np.uint8).copy()
-        self.off = np.cumsum([0] + [len(s) for s in seqs]).astype(np.uint64)
-        self.ids = np.frombuffer("".join(ids).encode() + b"\0", dtype=np.uint8).copy()
-        self.id_off = np.cumsum([0] + [len(i) for i in ids]).astype(np.uint64)
-        self.ch = _native.IngestChunk(0, len(seqs), self.bases.ctypes.data, self.off.ctypes.data, int(self.off[-1]),
-                                      self.ids.ctypes.data, self.id_off.ctypes.data)
-
-
 NONE = 0xFFFFFFFF
 OK = _native.FLAG_BC16 | _native.FLAG_RANK_OK
 

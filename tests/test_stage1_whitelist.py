@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from badger_amd import _native, common, extract_raw_barcodes as erb
+from ingest_chunk import Chunk as _Chunk
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -90,18 +91,6 @@ def test_stats_line_only_with_a_whitelist():
 
 
 # ---- the formatter ------------------------------------------------------------------------------------------------------
-class _Chunk:
-    """a bdg_ingest_chunk over numpy buffers (kept alive here)"""
-
-    def __init__(self, ids, seqs):
-        self.bases = np.frombuffer(("".join(seqs)).encode() + b"\0" * 64, dtype=np.uint8).copy()
-        self.off = np.cumsum([0] + [len(s) for s in seqs]).astype(np.uint64)
-        self.ids = np.frombuffer("".join(ids).encode() + b"\0", dtype=np.uint8).copy()
-        self.id_off = np.cumsum([0] + [len(i) for i in ids]).astype(np.uint64)
-        self.ch = _native.IngestChunk(0, len(seqs), self.bases.ctypes.data, self.off.ctypes.data, int(self.off[-1]),
-                                      self.ids.ctypes.data, self.id_off.ctypes.data)
-
-
 def _wl_columns(rec, idx, ed, ties, wl):
     """the table of the whitelist columns, restated"""
     if not rec["valid"] or not (rec["flags"] & _native.FLAG_RANK_OK) or ed == 255:
