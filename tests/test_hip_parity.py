@@ -801,10 +801,11 @@ def test_nearest16_and_graph_fuzz_clustered(ctx, orc, seed):
         assert (ge == we).all() and (gi == wi).all() and (gt == wt).all(), (algo, _diff(gt, wt))
     ctx.nearest16_set_algo(0)
     ranks = np.unique(np.concatenate([wl, q]))
-    for algo, thr in ((1, 1), (2, 1), (1, 2)):
+    want = {thr: orc.graph_edges(ranks, thr, threads=8) for thr in (1, 2)}
+    for algo, thr in ((1, 1), (2, 1), (1, 2), (3, 1), (3, 2), (4, 1), (4, 2), (5, 1), (5, 2), (6, 1)):
         ctx.graph_set_algo(algo)
         e = ctx.graph_edges(ranks, thr, orc.qgram_threshold(thr))
-        w = orc.graph_edges(ranks, thr, threads=8)
+        w = want[thr]
         assert len(e) == len(w) and (e == w).all(), (algo, thr)
     ctx.graph_set_algo(0)
 
