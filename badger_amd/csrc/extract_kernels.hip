@@ -19,6 +19,10 @@
 //                    relaxed windows are column prefixes of the union: their results are snapshots of the running key).
 //                    If the union cannot beat the first hit, no later hit of the cluster can replace it as "first
 //                    strictly best" (common.py:102-103) and they are skipped; otherwise they are re-queued (queue C).
+//                    Of the union only that one bit is used, so the column loop is split: the words up to the end of the
+//                    wave's longest first window (at most 10 of the 14) build keys, and of those only the words that hold
+//                    some lane's last strict or relaxed column run the snapshot selects; the words behind them are
+//                    score-only (no row tag, no column key: one packed maximum of the cells).
 //   k_strict_filter  queue B only matters if an alignment reaches score 17, which implies semi-global edit distance <= 5:
 //                    Myers' 22-bit search per group of two neighbouring hits (one pass over the union of their windows),
 //                    after dropping read-strands the relaxed search has already decided; survivors join queue C.
@@ -761,6 +765,13 @@ __device__ __forceinline__ int wave_max(int v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+__device__ __forceinline__ uint32_t wave_or(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
 // ---------------------------------------------------------------------------
 // Smith-Waterman of R1 (rows) against the first characters of a window (columns), +1/-1/-1 linear gaps, N scores 0.
 // The result is the maximum over all cells of the SSW key
@@ -768,6 +779,8 @@ __device__ __forceinline__ int wave_max(int v)
 // i.e. the best score, its first column, and the smallest row in that column - the end cell SSW reports (see
 // oracle/badger_oracle.c, sw_scan); unpk() takes the 2048 off again (0: no cell with a positive score).  The running key after
 // column n1 - 1 / n2 - 1 is returned in snap1 / snap2: the result for the window made of the first n1 / n2 columns.
+// Columns behind the longest n1 of the wave cannot reach a snapshot; a caller that has such columns (k_sw_clusters: the rest
+// of the union) gets their best score alone, as a packed maximum of the cells (sw_word, SW_SCORE).
 //
 // TWO alignments per lane, one per 16-bit half, so that add / subtract / max run as packed 16-bit instructions on two cells
 // at once.  Cells hold G = (H + 1) << 10 as unsigned 16-bit: H - 1 is never negative in that form (G - 1024 >= 0) and nothing
@@ -829,76 +842,64 @@ __device__ __forceinline__ void sw_window(uint32_t (&w)[NW], int n, uint32_t com
     }
 }
 
-// win: the two windows (sw_window) of this lane in LDS but for their first dwords (firstA / firstB): dword d >= 1 of cluster A
-// at win[(d - 1) * 64], of cluster B at win[(NW - 1 + d - 1) * 64] (13 + 13 words a lane: with the re-queue staging a block of
-// k_sw_clusters stays below 32 KB, five blocks a compute unit).  The loop takes one dword of each per four columns; held in
-// registers the 2 x NW words had to be
-// moved down one place per round).  n1 / n2: the two window lengths whose running key is wanted, both clusters packed.
-// SINGLE: one alignment a lane (the low halves; the high halves see a window of 'N').  P0 / P1: the bit planes of the rows'
-// codes (R1_P0 / R1_P1, or a lane's own: the reverse pass of k_finalize_reads aligns R1[end_read .. 0]), rowmask: the rows
-// that exist.
-template <int NW, bool WITH_N, bool SINGLE>
-__device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firstA, uint32_t firstB, int ndw, uint32_t n1, uint32_t n2,
-                                              uint32_t P0, uint32_t P1, uint32_t rowmask,
-                                              uint32_t& snap1, uint32_t& snap2)
+// The four columns of word d come in three forms (BODY).  SW_KEYS: the SSW key of every column joins acc.  SW_SNAP: that,
+// and the running key after column n1 - 1 / n2 - 1 is kept in s1 / s2.  SW_SCORE: neither; the cells (G, before the floor)
+// only join the packed maximum tmax - what a caller needs that asks for the best score of these columns and not for where
+// it ends.  The cell recurrence and the equality words are the same in all three.
+enum { SW_KEYS = 0, SW_SNAP = 1, SW_SCORE = 2 };
+
+template <bool WITH_N, bool SINGLE, int BODY>
+__device__ __forceinline__ void sw_word(uint32_t (&hm)[R1_LEN], uint32_t curA, uint32_t curB, int d, uint32_t n1, uint32_t n2,
+                                        uint32_t P0, uint32_t P1, uint32_t rowmask,
+                                        uint32_t& acc, uint32_t& s1, uint32_t& s2, uint32_t& tmax)
 {
     constexpr uint32_t ONE2 = 0x04000400u;       // 1 << 10 in both halves
-    // Cells are kept as G - 1 = H in offset form, floored at 0 by the saturating subtract: every consumer of a cell (the
-    // cell to its right, below it, and diagonally below) needs exactly that, so one v_pk_sub_u16 clamp per cell replaces
-    // two subtractions and the max with 0.  (An unfloored cell only ever reaches the running key with score <= 0, where
-    // the key is never used.)
-    uint32_t hm[R1_LEN];
 #pragma unroll
-    for (int i = 0; i < R1_LEN; ++i) hm[i] = 0u;             // H = 0
-    uint32_t acc = 0, s1 = 0, s2 = 0;
-    uint32_t curA = firstA, curB = SINGLE ? 0x4E4E4E4Eu : firstB;
-#pragma nounroll
-    for (int d = 0; d < ndw; ++d) {
-        const int dn = d + 1 < NW ? d + 1 : NW - 1;           // (NW >= 2)
-        const uint32_t nextA = win[(dn - 1) * 64], nextB = SINGLE ? 0x4E4E4E4Eu : win[(NW - 1 + dn - 1) * 64];
+    for (int b = 0; b < 4; ++b) {
+        const int j = d * 4 + b;
+        // Equality words (row i = bit i; bits 22.. hold anything, no row reads them) from the two bit planes of R1's codes
+        // and the base's code bits spread over the word; ASCII bit 3 = 'N' or behind the window: matches nothing.
+        const uint32_t a0 = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 1, 1), a1 = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 2, 1);
+        const uint32_t an = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 3, 1);
+        const uint32_t b0 = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 1, 1), b1 = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 2, 1);
+        const uint32_t bn = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 3, 1);
+        const uint32_t eA = __builtin_amdgcn_bitop3_b32(a0, P0, __builtin_amdgcn_bitop3_b32(a1, P1, an, 0xBE), 0x41) & rowmask;
+        const uint32_t eB = SINGLE ? 0u : __builtin_amdgcn_bitop3_b32(b0, P0, __builtin_amdgcn_bitop3_b32(b1, P1, bn, 0xBE), 0x41);
+        const uint32_t M0 = __builtin_amdgcn_perm(eB, eA, 0x05040100u);  // rows 0..15 of both
+        const uint32_t M1 = __builtin_amdgcn_perm(eB, eA, 0x07060302u);  // rows 16..21 (and what lies above them)
+        const uint32_t M2 = M0 >> 4;                                     // rows 12..15 at bits 8..11 of both halves
+        // N scores 0.  Places behind a window's end are 'N' too: in the form without N they simply match nothing (-1, as
+        // before); here they score 0, which cannot lift a cell above the best one before them - and at equal score the
+        // earlier column wins.
+        const uint32_t dN = WITH_N ? ((an & 0x0400u) | (bn & 0x04000000u)) : 0u;
+        uint32_t diag_t = 0u;        // (H(-1, j-1) - 1) in offset form
+        uint32_t upm = 0u;           // (H(-1, j) - 1) likewise
+        uint32_t colkey = BODY == SW_SCORE ? tmax : 0u, kprev = 0u;      // (SW_SCORE: the running maximum itself)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int j = d * 4 + b;
-            // Equality words (row i = bit i; bits 22.. hold anything, no row reads them) from the two bit planes of R1's codes
-            // and the base's code bits spread over the word; ASCII bit 3 = 'N' or behind the window: matches nothing.
-            const uint32_t a0 = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 1, 1), a1 = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 2, 1);
-            const uint32_t an = (uint32_t)__builtin_amdgcn_sbfe((int)curA, 8 * b + 3, 1);
-            const uint32_t b0 = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 1, 1), b1 = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 2, 1);
-            const uint32_t bn = (uint32_t)__builtin_amdgcn_sbfe((int)curB, 8 * b + 3, 1);
-            const uint32_t eA = __builtin_amdgcn_bitop3_b32(a0, P0, __builtin_amdgcn_bitop3_b32(a1, P1, an, 0xBE), 0x41) & rowmask;
-            const uint32_t eB = SINGLE ? 0u : __builtin_amdgcn_bitop3_b32(b0, P0, __builtin_amdgcn_bitop3_b32(b1, P1, bn, 0xBE), 0x41);
-            const uint32_t M0 = __builtin_amdgcn_perm(eB, eA, 0x05040100u);  // rows 0..15 of both
-            const uint32_t M1 = __builtin_amdgcn_perm(eB, eA, 0x07060302u);  // rows 16..21 (and what lies above them)
-            const uint32_t M2 = M0 >> 4;                                     // rows 12..15 at bits 8..11 of both halves
-            // N scores 0.  Places behind a window's end are 'N' too: in the form without N they simply match nothing (-1, as
-            // before); here they score 0, which cannot lift a cell above the best one before them - and at equal score the
-            // earlier column wins.
-            const uint32_t dN = WITH_N ? ((an & 0x0400u) | (bn & 0x04000000u)) : 0u;
-            uint32_t diag_t = 0u;        // (H(-1, j-1) - 1) in offset form
-            uint32_t upm = 0u;           // (H(-1, j) - 1) likewise
-            uint32_t colkey = 0u, kprev = 0u;
-#pragma unroll
-            for (int i = 0; i < R1_LEN; ++i) {
-                const uint32_t tl = hm[i];                                               // H(i, j-1) - 1
-                // The row's match bit stays where it is in its word (bit p <= 11 of both halves) and is scaled to +2 by
-                // the multiplier of a packed multiply-add: one AND and one v_pk_mad_u16 where shift, AND and add were three.
-                const uint32_t src = i < 12 ? M0 : (i < 16 ? M2 : M1);
-                const int p = i < 12 ? i : (i < 16 ? i - 4 : i - 16);
-                uint32_t dg = pk_mad(src & (0x00010001u << p), 0x00010001u << (11 - p), diag_t);      // H(i-1,j-1) +/- 1
-                if (WITH_N) dg = pk_add(dg, dN);
-                const uint32_t g = pk_max3_below_7c00(dg, tl, upm);                      // max(diag, left-1, up-1); the floor comes next
-                const uint32_t gm = pk_sub_sat(g, ONE2);                                 // max(H, 0) - 1 in offset form
-                diag_t = tl;
-                hm[i] = gm;
-                upm = gm;
-                const uint32_t k = g | ((uint32_t)(31 - i) * 0x00010001u);
-                if (i & 1) colkey = pk_max3_below_7c00(colkey, kprev, k);
-                else kprev = k;
-            }
-            // the column's best cell as an SSW key: G up one bit, the column number in between
-            const uint32_t cj = (uint32_t)((63 - j) << 5) * 0x00010001u;
-            const uint32_t key = ((colkey & 0x7C007C00u) << 1) | (colkey & 0x001F001Fu) | cj;
-            acc = pk_max(acc, key);
+        for (int i = 0; i < R1_LEN; ++i) {
+            const uint32_t tl = hm[i];                                               // H(i, j-1) - 1
+            // The row's match bit stays where it is in its word (bit p <= 11 of both halves) and is scaled to +2 by
+            // the multiplier of a packed multiply-add: one AND and one v_pk_mad_u16 where shift, AND and add were three.
+            const uint32_t src = i < 12 ? M0 : (i < 16 ? M2 : M1);
+            const int p = i < 12 ? i : (i < 16 ? i - 4 : i - 16);
+            uint32_t dg = pk_mad(src & (0x00010001u << p), 0x00010001u << (11 - p), diag_t);      // H(i-1,j-1) +/- 1
+            if (WITH_N) dg = pk_add(dg, dN);
+            const uint32_t g = pk_max3_below_7c00(dg, tl, upm);                      // max(diag, left-1, up-1); the floor comes next
+            const uint32_t gm = pk_sub_sat(g, ONE2);                                 // max(H, 0) - 1 in offset form
+            diag_t = tl;
+            hm[i] = gm;
+            upm = gm;
+            // a column's maximum takes two rows per instruction; only a key carries the row
+            const uint32_t k = BODY == SW_SCORE ? g : g | ((uint32_t)(31 - i) * 0x00010001u);
+            if (i & 1) colkey = pk_max3_below_7c00(colkey, kprev, k);
+            else kprev = k;
+        }
+        if (BODY == SW_SCORE) { tmax = colkey; continue; }
+        // the column's best cell as an SSW key: G up one bit, the column number in between
+        const uint32_t cj = (uint32_t)((63 - j) << 5) * 0x00010001u;
+        const uint32_t key = ((colkey & 0x7C007C00u) << 1) | (colkey & 0x001F001Fu) | cj;
+        acc = pk_max(acc, key);
+        if (BODY == SW_SNAP) {
             // the running key after column n1 - 1 / n2 - 1: all ones in the half whose length is j + 1
             const uint32_t jj = (uint32_t)(j + 1) * 0x00010001u;
             const uint32_t m1 = pk_sub(pk_min(n1 ^ jj, 0x00010001u), 0x00010001u);
@@ -906,9 +907,68 @@ __device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firs
             s1 = (acc & m1) | (s1 & ~m1);
             s2 = (acc & m2) | (s2 & ~m2);
         }
-        curA = nextA; curB = nextB;
     }
-    snap1 = s1; snap2 = s2;
+}
+
+// win: the two windows (sw_window) of this lane in LDS but for their first dwords (firstA / firstB): dword d >= 1 of cluster A
+// at win[(d - 1) * 64], of cluster B at win[(NW - 1 + d - 1) * 64] (13 + 13 words a lane: with the re-queue staging a block of
+// k_sw_clusters stays below 32 KB, five blocks a compute unit).  The loop takes one dword of each per four columns (held in
+// registers the 2 x NW words had to be moved down one place per round).  n1 / n2: the two window lengths whose running key
+// is wanted, both clusters packed.
+// SINGLE: one alignment a lane (the low halves; the high halves see a window of 'N').  P0 / P1: the bit planes of the rows'
+// codes (R1_P0 / R1_P1, or a lane's own: the reverse pass of k_finalize_reads aligns R1[end_read .. 0]), rowmask: the rows
+// that exist.
+// ndh <= ndw: the HEAD words, whose columns can reach a key or a snapshot (every word up to the longest n1 of the wave), and
+// all words; SINGLE callers have head words only.  The words from ndh on are score-only: their packed cell maximum is
+// returned in tail_max (sw_tail_score turns a half of it into a score).  snap_words: bit d set when some lane's column
+// n1 - 1 or n2 - 1 lies in word d; the other head words run without the snapshot selects.  ndh, ndw and snap_words are the
+// same in every lane: the loops branch on scalars and stay rolled, one copy of each body.
+template <int NW, bool WITH_N, bool SINGLE>
+__device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firstA, uint32_t firstB, int ndh, int ndw, uint32_t snap_words,
+                                              uint32_t n1, uint32_t n2, uint32_t P0, uint32_t P1, uint32_t rowmask,
+                                              uint32_t& snap1, uint32_t& snap2, uint32_t& tail_max)
+{
+    // Cells are kept as G - 1 = H in offset form, floored at 0 by the saturating subtract: every consumer of a cell (the
+    // cell to its right, below it, and diagonally below) needs exactly that, so one v_pk_sub_u16 clamp per cell replaces
+    // two subtractions and the max with 0.  (An unfloored cell only ever reaches the running key with score <= 0, where
+    // the key is never used.)
+    uint32_t hm[R1_LEN];
+#pragma unroll
+    for (int i = 0; i < R1_LEN; ++i) hm[i] = 0u;             // H = 0
+    uint32_t acc = 0, s1 = 0, s2 = 0, tmax = 0;
+    uint32_t curA = firstA, curB = SINGLE ? 0x4E4E4E4Eu : firstB;
+    int d = 0;
+    while (d < ndh) {
+        // runs of words without and with snapshots, a plain loop each
+        const int dk = SINGLE ? ndh : min(ndh, d + (int)__builtin_ctz((snap_words >> d) | 0x10000u));
+#pragma nounroll
+        for (; d < dk; ++d) {
+            const int dn = d + 1 < NW ? d + 1 : NW - 1;           // (NW >= 2)
+            const uint32_t nextA = win[(dn - 1) * 64], nextB = SINGLE ? 0x4E4E4E4Eu : win[(NW - 1 + dn - 1) * 64];
+            sw_word<WITH_N, SINGLE, SW_KEYS>(hm, curA, curB, d, n1, n2, P0, P1, rowmask, acc, s1, s2, tmax);
+            curA = nextA; curB = nextB;
+        }
+        if (!SINGLE) {
+            const int ds = min(ndh, d + (int)__builtin_ctz(~(snap_words >> d)));
+#pragma nounroll
+            for (; d < ds; ++d) {
+                const int dn = d + 1 < NW ? d + 1 : NW - 1;
+                const uint32_t nextA = win[(dn - 1) * 64], nextB = win[(NW - 1 + dn - 1) * 64];
+                sw_word<WITH_N, SINGLE, SW_SNAP>(hm, curA, curB, d, n1, n2, P0, P1, rowmask, acc, s1, s2, tmax);
+                curA = nextA; curB = nextB;
+            }
+        }
+    }
+    if (!SINGLE) {
+#pragma nounroll
+        for (; d < ndw; ++d) {
+            const int dn = d + 1 < NW ? d + 1 : NW - 1;
+            const uint32_t nextA = win[(dn - 1) * 64], nextB = win[(NW - 1 + dn - 1) * 64];
+            sw_word<WITH_N, SINGLE, SW_SCORE>(hm, curA, curB, d, n1, n2, P0, P1, rowmask, acc, s1, s2, tmax);
+            curA = nextA; curB = nextB;
+        }
+    }
+    snap1 = s1; snap2 = s2; tail_max = tmax;
     return acc;
 }
 
@@ -917,6 +977,16 @@ __device__ __forceinline__ uint32_t unpk(uint32_t packed, int half)
 {
     const uint32_t k = half ? packed >> 16 : packed & 0xFFFFu;
     return k >= (uint32_t)ONE ? k - (uint32_t)ONE : 0u;
+}
+
+// A half of sw_block2's tail_max -> the best score of the tail's columns.  The tail keeps cells as G = (H + 1) << 10, and
+// before the floor: a cell with H <= 0 (G <= 1 << 10, an unfloored one among them) gives 0 here.  The only reader compares
+// the result with "> score_s", score_s >= 0, so such a cell can never turn the comparison true - the argument of the
+// unfloored cells of the running key (sw_block2).
+__device__ __forceinline__ uint32_t sw_tail_score(uint32_t tail_max, int half)
+{
+    const uint32_t g = (half ? tail_max >> 16 : tail_max & 0xFFFFu) >> 10;
+    return g ? g - 1u : 0u;
 }
 
 __device__ __forceinline__ uint64_t make_key(uint32_t acc, uint32_t pos)
@@ -1123,18 +1193,21 @@ __device__ __forceinline__ ClusterJob make_job(const QEnt e,
 }
 
 // keys of the first hit; returns the other hits of the cluster when the union beats it (they must be aligned one by one)
-__device__ __forceinline__ uint32_t finish_job(const ClusterJob& jb, uint32_t acc_s, uint32_t acc_r, uint32_t acc_u,
+// acc_h: the key over the head words (every column up to the wave's longest first window), score_t: the best score behind them;
+// of the union only the score is ever read
+__device__ __forceinline__ uint32_t finish_job(const ClusterJob& jb, bool relaxed, uint32_t acc_s, uint32_t acc_r, uint32_t acc_h, uint32_t score_t,
                                                uint32_t n_reads, unsigned long long* __restrict__ keys)
 {
     const uint32_t score_s = acc_s >> KEY_SHIFT;
     if (jb.active && score_s >= 17u)                                                    // barcode_callers.py:200
         atomicMax(&keys[2ull * n_reads + 2ull * jb.r + jb.strand], (unsigned long long)make_key(acc_s, (uint32_t)jb.pos));
-    if (jb.relaxed && (acc_r >> KEY_SHIFT) >= 9u)                                        // barcode_callers.py:191
+    if (relaxed && (acc_r >> KEY_SHIFT) >= 9u)                                           // barcode_callers.py:191
         atomicMax(&keys[2ull * jb.r + jb.strand], (unsigned long long)make_key(acc_r, (uint32_t)jb.pos));
     // Every window of the cluster lies inside the union, so no later hit scores above the union.
     // If the union does not beat the first hit, none of them can replace it (strictly greater is
     // required, common.py:102); otherwise align them one by one (queue C, second launch).
-    return (jb.active && (acc_u >> KEY_SHIFT) > score_s) ? (jb.mask & ~1u) : 0u;
+    const uint32_t score_h = acc_h >> KEY_SHIFT, score_u = score_h > score_t ? score_h : score_t;
+    return (jb.active && score_u > score_s) ? (jb.mask & ~1u) : 0u;
 }
 
 constexpr uint32_t REQ_CAP = 128;            // per-wave staging of re-queued hits (2 % of the clusters re-queue any)
@@ -1160,11 +1233,20 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __r
     for (uint64_t base = (uint64_t)blockIdx.x * 512ull + 2ull * (threadIdx.x & ~63); base < nq; base += stride) {
         const ClusterJob ja = make_job(queue_fetch(q, seg, s_cnt, base + 2ull * lane, nq), off, polyt);
         const ClusterJob jb = make_job(queue_fetch(q, seg, s_cnt, base + 2ull * lane + 1, nq), off, polyt);
+        nwin += (ja.active ? 1u : 0u) + (jb.active ? 1u : 0u);        // (here, not behind the alignment: the loop has no register to spare)
         uint32_t wa[CW], wb[CW];
         load_block<CW>(bases, total_rounded, ja.rs, ja.L, (int)ja.strand, ja.ws, +1, wa);
         load_block<CW>(bases, total_rounded, jb.rs, jb.L, (int)jb.strand, jb.ws, +1, wb);
         const bool anyN = __ballot((ja.active && block_has_N<CW>(wa)) || (jb.active && block_has_N<CW>(wb))) != 0;
-        const int ndw = (wave_max(ja.n_u > jb.n_u ? ja.n_u : jb.n_u) + 3) >> 2;
+        // One OR over the wave gives all three loop bounds: bit d of the low half for a lane whose column n_s - 1 or n_r - 1
+        // lies in word d (a length of 0 has none), of the high half for the last word of its union.  n_r <= n_s <= n_u, so
+        // the highest bit of each half is the wave's maximum: (max + 3) >> 2 words, as before.
+        auto last_word = [](int n) -> uint32_t { return n > 0 ? 1u << ((n - 1) >> 2) : 0u; };
+        const uint32_t words = wave_or(last_word(ja.n_s) | last_word(jb.n_s) | last_word(ja.n_r) | last_word(jb.n_r)
+                                       | ((last_word(ja.n_u) | last_word(jb.n_u)) << 16));
+        const uint32_t snap_words = words & 0xFFFFu;
+        const int ndh = snap_words ? 32 - __builtin_clz(snap_words) : 0;
+        const int ndw = (words >> 16) ? 32 - __builtin_clz(words >> 16) : 0;
         sw_window<CW>(wa, ja.n_u, ja.strand);
         sw_window<CW>(wb, jb.n_u, jb.strand);
         uint32_t* const win = &s_win[wv][0][lane];
@@ -1173,12 +1255,14 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __r
         __builtin_amdgcn_wave_barrier();
         uint32_t sn_s = 0, sn_r = 0;
         const uint32_t n_s2 = (uint32_t)ja.n_s | ((uint32_t)jb.n_s << 16), n_r2 = (uint32_t)ja.n_r | ((uint32_t)jb.n_r << 16);
-        const uint32_t acc = anyN ? sw_block2<CW, true, false>(win, wa[0], wb[0], ndw, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r)
-                                  : sw_block2<CW, false, false>(win, wa[0], wb[0], ndw, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r);
+        uint32_t tmax = 0;
+        const uint32_t acc = anyN ? sw_block2<CW, true, false>(win, wa[0], wb[0], ndh, ndw, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r, tmax)
+                                  : sw_block2<CW, false, false>(win, wa[0], wb[0], ndh, ndw, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r, tmax);
         __builtin_amdgcn_wave_barrier();
-        nwin += (ja.active ? 1u : 0u) + (jb.active ? 1u : 0u);
-        uint32_t rest_a = finish_job(ja, unpk(sn_s, 0), unpk(sn_r, 0), unpk(acc, 0), n_reads, keys);
-        uint32_t rest_b = finish_job(jb, unpk(sn_s, 1), unpk(sn_r, 1), unpk(acc, 1), n_reads, keys);
+        // (relaxed: a relaxed window is never empty, and n_r2 is in a register anyway; the two flags held across the loop
+        // were the registers it had no room for)
+        uint32_t rest_a = finish_job(ja, (n_r2 & 0xFFFFu) != 0u, unpk(sn_s, 0), unpk(sn_r, 0), unpk(acc, 0), sw_tail_score(tmax, 0), n_reads, keys);
+        uint32_t rest_b = finish_job(jb, (n_r2 >> 16) != 0u, unpk(sn_s, 1), unpk(sn_r, 1), unpk(acc, 1), sw_tail_score(tmax, 1), n_reads, keys);
         if (__ballot((rest_a | rest_b) != 0)) {
             const uint32_t cnt = __popc(rest_a) + __popc(rest_b);
             uint32_t incl = cnt;
@@ -1272,9 +1356,9 @@ __device__ __forceinline__ StrandRes finalize_strand(const uint8_t* __restrict__
         const int ndw = (wave_max(ncol) + 3) >> 2;
         const uint32_t p0r = __brev(R1_P0) >> (31 - end_read_s), p1r = __brev(R1_P1) >> (31 - end_read_s);
         const uint32_t rows = (2u << end_read_s) - 1u;
-        uint32_t sn1, sn2;
-        const uint32_t acc = anyN ? sw_block2<10, true, true>(win, w[0], 0u, ndw, 0u, 0u, p0r, p1r, rows, sn1, sn2)
-                                  : sw_block2<10, false, true>(win, w[0], 0u, ndw, 0u, 0u, p0r, p1r, rows, sn1, sn2);
+        uint32_t sn1, sn2, tmax = 0;                                       // (no snapshots, no tail: every word a head word)
+        const uint32_t acc = anyN ? sw_block2<10, true, true>(win, w[0], 0u, ndw, ndw, 0u, 0u, 0u, p0r, p1r, rows, sn1, sn2, tmax)
+                                  : sw_block2<10, false, true>(win, w[0], 0u, ndw, ndw, 0u, 0u, 0u, p0r, p1r, rows, sn1, sn2, tmax);
         __builtin_amdgcn_wave_barrier();
         if (need_rev) {
             const int rr = 31 - (int)(unpk(acc, 0) & 31u);             // (the pass always finds the forward score again: the key is never 0)
