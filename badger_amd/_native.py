@@ -31,6 +31,11 @@ TSO5_MIN_SCORE_DEFAULT, TSO5_MIN_SCORE_MAX = 16, 25
 CHIMERA_DTYPE = np.dtype([("cut", "<i4"), ("hit_pos", "<i4"), ("hit_ed", "u1"), ("hit_kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
 CHIMERA_HIT = 1
 CHIMERA_MAX_ED_DEFAULT, CHIMERA_MAX_ED_MAX = 3, 6
+# bdg_rescue_rec: the barcode of a read without a usable adapter (bdg_rescue_batch; the rule in badger_amd/rescue.py)
+RESCUE_DTYPE = np.dtype([("read", "<u4"), ("entry", "<u4"), ("support", "<u4"), ("polyT", "<i4"), ("bc_start", "<i4"),
+                         ("offset", "i1"), ("dist", "i1"), ("strand", "i1"), ("status", "u1"), ("umi", "S16")])
+RESCUE_NONE, RESCUE_RESCUED, RESCUE_AMBIGUOUS, RESCUE_TRUNCATED = 0, 1, 2, 3
+RESCUE_SLACK, RESCUE_MAX_ED_DEFAULT, RESCUE_MAX_ED_MAX, RESCUE_MIN_SUPPORT_DEFAULT, RESCUE_UMI_MAX = 2, 1, 2, 2, 14
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -62,6 +67,7 @@ EXPORTS = [
     "bdg_trim_batch", "bdg_trim_batch_dev", "bdg_extract_set_trim", "bdg_extract_collect_trim", "bdg_format_trimmed",
     "bdg_chimera_batch", "bdg_chimera_batch_dev", "bdg_extract_set_chimera", "bdg_extract_collect_chimera", "bdg_format_trimmed_chimera",
     "bdg_extract_keep_cdna", "bdg_kept_cdna", "bdg_molecule_reps_dev", "bdg_molecule_reps_set_aggregate", "bdg_format_trimmed_tags",
+    "bdg_rescue_batch", "bdg_rescue_batch_dev", "bdg_extract_set_rescue", "bdg_extract_rescue_resolve", "bdg_rescue_counts",
 ]
 
 
@@ -85,6 +91,7 @@ STAGE1_WL_CANDIDATES = 0x100        # bdg_stage1_opts.whitelist: bc_candidates i
 STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist correction, the trailing fields are set (BDG_STAGE1_WL_CORRECT)
 STAGE1_CHIMERA = 0x800              # bdg_stage1_opts.whitelist: with STAGE1_TRIM, chimeric reads are cut; chimera_max_ed is set (BDG_STAGE1_CHIMERA)
 STAGE1_TAGS = 0x1000                # bdg_stage1_opts.whitelist: with STAGE1_TRIM, the trimmed file carries stage 2's tags; the tag_* fields are set (BDG_STAGE1_TAGS)
+STAGE1_WL_RESCUE = 0x2000           # bdg_stage1_opts.whitelist: with STAGE1_WL_CORRECT, reads without a barcode are rescued; the rescue_* fields are set (BDG_STAGE1_WL_RESCUE)
 STAGE1_TRIM = 0x400                 # bdg_stage1_opts.whitelist: trimmed reads, the fields behind the correction's are set (BDG_STAGE1_TRIM)
 # status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
 WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
@@ -117,6 +124,11 @@ class Stage1OptsTags(Stage1OptsChimera):
     """bdg_stage1_opts with the fields read only with STAGE1_TAGS"""
     _fields_ = [("tag_cell_rank", C.c_void_p), ("tag_cell_has", C.c_void_p), ("tag_molecule", C.c_void_p),
                 ("tag_mol_reads", C.c_void_p), ("tag_keep", C.c_void_p), ("tag_reads", C.c_uint64)]
+
+
+class Stage1OptsRescue(Stage1OptsTags):
+    """bdg_stage1_opts with the fields read only with STAGE1_WL_RESCUE"""
+    _fields_ = [("rescue_max_ed", C.c_uint32), ("rescue_min_support", C.c_uint32), ("rescued_path", C.c_char_p)]
 
 
 class Stage1Result(C.Structure):
@@ -152,6 +164,12 @@ class Stage1ResultTags(Stage1ResultChimera):
 class Stage1Result5p(Stage1ResultTags):
     """bdg_stage1_result with the count written only with STAGE1_TRIM on contexts in LAYOUT_5P (whatever the other bits)"""
     _fields_ = [("trimmed_no_anchor", C.c_uint64)]
+
+
+class Stage1ResultRescue(Stage1Result5p):
+    """bdg_stage1_result with the counts written only with STAGE1_WL_RESCUE"""
+    _fields_ = [("rescue_eligible", C.c_uint64), ("rescue_rescued", C.c_uint64), ("rescue_ambiguous", C.c_uint64),
+                ("rescue_truncated", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -295,6 +313,11 @@ def load():
     L.bdg_molecule_reps_set_aggregate.argtypes = [vp, C.c_int]
     L.bdg_format_trimmed_tags.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.bdg_format_trimmed_tags.restype = C.c_int64
+    L.bdg_rescue_batch.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32)]
+    L.bdg_rescue_batch_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp, u32, u32, vp, C.POINTER(u32)]
+    L.bdg_extract_set_rescue.argtypes = [vp, C.c_int]
+    L.bdg_extract_rescue_resolve.argtypes = [vp, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.bdg_rescue_counts.argtypes = [vp, C.POINTER(u64)]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -450,6 +473,52 @@ class Context:
         out = np.zeros(n, dtype=CHIMERA_DTYPE)
         self._check(self.lib.bdg_extract_collect_chimera(self.h, slot, out.ctypes.data))
         return out
+
+    def rescue_batch(self, bases, off, recs, umi_len, support, max_ed=RESCUE_MAX_ED_DEFAULT, min_support=RESCUE_MIN_SUPPORT_DEFAULT):
+        """the barcodes of reads without a usable adapter (bdg_rescue_batch) against the loaded whitelist: reads as for
+        extract_batch, their records, support uint32 [entries] -> RESCUE_DTYPE array, one record per eligible read with a
+        candidate window, in read order"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+        support = np.ascontiguousarray(support, dtype=np.uint32)
+        n = max(len(off) - 1, 0)
+        if len(recs) != n:
+            raise ValueError("rescue_batch: %d reads, %d records" % (n, len(recs)))
+        out = np.zeros(n, dtype=RESCUE_DTYPE)
+        m = C.c_uint32(0)
+        self._check(self.lib.bdg_rescue_batch(self.h, bases.ctypes.data, off.ctypes.data, n, recs.ctypes.data, umi_len,
+                                              support.ctypes.data, max_ed, min_support, out.ctypes.data, C.byref(m)))
+        return out[:m.value].copy()
+
+    def rescue_batch_dev(self, d_bases, d_off, n, d_recs, umi_len, d_support, max_ed, min_support, d_out):
+        """device form, behind the extract_batch_dev call that wrote d_recs (bdg_rescue_batch_dev); d_out: room for n records of
+        40 bytes; waits and returns the number written (in no particular order)"""
+        m = C.c_uint32(0)
+        self._check(self.lib.bdg_rescue_batch_dev(self.h, _ptr(d_bases), _ptr(d_off), n, _ptr(d_recs), umi_len, _ptr(d_support),
+                                                  max_ed, min_support, _ptr(d_out), C.byref(m)))
+        return int(m.value)
+
+    def extract_set_rescue(self, on=True):
+        """while on, extract_submit stores the candidate windows of the chunk's reads without a barcode; on starts an empty store,
+        off frees it (bdg_extract_set_rescue)"""
+        self._check(self.lib.bdg_extract_set_rescue(self.h, 1 if on else 0))
+
+    def extract_rescue_resolve(self, d_support, max_ed=RESCUE_MAX_ED_DEFAULT, min_support=RESCUE_MIN_SUPPORT_DEFAULT):
+        """after the last extract_collect: everything stored matched and resolved (bdg_extract_rescue_resolve) -> RESCUE_DTYPE
+        array sorted by read; d_support: a device array, or None for the context's correction support"""
+        stored, _ = self.rescue_counts()
+        out = np.zeros(stored, dtype=RESCUE_DTYPE)
+        m = C.c_uint64(0)
+        self._check(self.lib.bdg_extract_rescue_resolve(self.h, None if d_support is None else _ptr(d_support), max_ed, min_support,
+                                                        out.ctypes.data if stored else None, stored, C.byref(m)))
+        return out[:m.value]
+
+    def rescue_counts(self):
+        """(stored reads, eligible reads) of the rescue store (bdg_rescue_counts; waits for the context's streams)"""
+        out = (C.c_uint64 * 2)()
+        self._check(self.lib.bdg_rescue_counts(self.h, out))
+        return int(out[0]), int(out[1])
 
     def extract_keep_records(self, on=True):
         """keep (a copy of) every collected chunk's records on the device, in order, for the stage-2 hand-off"""
@@ -791,7 +860,8 @@ def chunk_reads(ch):
 def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_every=0, skip_secondary=False,
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
                corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT,
-               chimera_max_ed=None, tags=None, tso5_max_ed=None):
+               chimera_max_ed=None, tags=None, tso5_max_ed=None, rescued_path=None, rescue_max_ed=RESCUE_MAX_ED_DEFAULT,
+               rescue_min_support=RESCUE_MIN_SUPPORT_DEFAULT):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
@@ -804,7 +874,9 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     over the whole input - cell_rank, cell_has and optionally molecule with mol_reads, and keep - whose answers go into the headers of
     the trimmed file (BDG_STAGE1_TAGS, bdg_format_trimmed_tags); the result then has tags_no_cell and tags_not_kept.
     tso5_max_ed (with trimmed_path; the caller has put every context into LAYOUT_5P): the switch oligo's edit bound of the 5'
-    trimming rule; the result is then a Stage1Result5p whatever else is asked for, and has trimmed_no_anchor."""
+    trimming rule; the result is then a Stage1Result5p whatever else is asked for, and has trimmed_no_anchor.  rescued_path (with
+    corrected_path): reads without a barcode are rescued against the run's support (BDG_STAGE1_WL_RESCUE) into that file; the result
+    is then a Stage1ResultRescue and has rescue_eligible, rescue_rescued, rescue_ambiguous and rescue_truncated."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
@@ -815,6 +887,8 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         wl_mode |= STAGE1_CHIMERA                   # (without a trimmed_path the library says E_ARG)
     if tags is not None:
         wl_mode |= STAGE1_TAGS                      # (without a trimmed_path the library says E_ARG)
+    if rescued_path is not None:
+        wl_mode |= STAGE1_WL_RESCUE                 # (without the correction the library says E_ARG)
     held = [None] * 5
     if tags is not None:
         held = [np.ascontiguousarray(tags["cell_rank"], dtype=np.uint32), np.ascontiguousarray(tags["cell_has"], dtype=np.uint8)]
@@ -822,14 +896,20 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
                  for k, t in (("molecule", np.uint32), ("mol_reads", np.uint32), ("keep", np.uint8))]
         if len({len(a) for a in held if a is not None}) != 1 or (held[2] is None) != (held[3] is None):
             raise ValueError("stage1_run: the tag arrays differ in length, or molecule comes without mol_reads")
-    # the whole struct, with zero or None in what the flags do not enable: the library reads those fields only under their bits
-    o = Stage1OptsTags(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
-                       wl_mode, max_bc_dist, bc_candidates, bc_edit_bits, bc_min_permille,
-                       os.fsencode(corrected_path) if correct else None, os.fsencode(trimmed_path) if trimmed_path is not None else None,
-                       tso_min_score, tso5_max_ed or 0, chimera_max_ed or 0, 0,
-                       *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]) if tags is not None else 0)
+    # the whole struct, with zero or None in what the flags do not enable: the library reads those fields only under their bits.
+    # The paths stay alive here, not in the struct: ctypes keeps what a c_char_p field points to under the field's index within its
+    # own class, so the third field of one subclass (rescued_path) would take the place of another's (corrected_path)
+    c_path, t_path, r_path = [os.fsencode(x) if on else None for x, on in
+                              ((corrected_path, correct), (trimmed_path, trimmed_path is not None), (rescued_path, rescued_path is not None))]
+    o = Stage1OptsRescue(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
+                         wl_mode, max_bc_dist, bc_candidates, bc_edit_bits, bc_min_permille, c_path, t_path,
+                         tso_min_score, tso5_max_ed or 0, chimera_max_ed or 0, 0,
+                         *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]) if tags is not None else 0,
+                         rescue_max_ed, rescue_min_support, r_path)
     # the result is as short as the flags allow: the library writes a feature's counts only under its bit
-    if tso5_max_ed is not None and trimmed_path is not None:
+    if rescued_path is not None:
+        res = Stage1ResultRescue()
+    elif tso5_max_ed is not None and trimmed_path is not None:
         res = Stage1Result5p()
     elif tags is not None:
         res = Stage1ResultTags()
@@ -841,6 +921,7 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         res = Stage1ResultCorrect() if correct else Stage1Result()
     rc = L.bdg_stage1_run(arr, len(contexts), os.fsencode(in_path), os.fsencode(out_path) if out_path is not None else None, header.encode("ascii"),
                           C.cast(C.pointer(o), C.POINTER(Stage1Opts)), C.cast(C.pointer(res), C.POINTER(Stage1Result)))
+    del c_path, t_path, r_path                     # (alive until here)
     if rc != 0:
         _raise_like_reference(rc, L.bdg_last_error(contexts[0].h).decode())
     return res

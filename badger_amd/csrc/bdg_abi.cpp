@@ -528,6 +528,39 @@ int bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     return BDG_OK;
 }
 
+// ---- barcode rescue (host buffers; the device form and the pipelined one are in bdg_chunks.cpp) ----
+int bdg_rescue_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_extract_rec* recs,
+                     uint32_t umi_len, const uint32_t* support, uint32_t max_ed, uint32_t min_support,
+                     bdg_rescue_rec* out, uint32_t* n_out)
+{
+    if (!ctx || !n_out) return BDG_E_ARG;
+    *n_out = 0;
+    if (int rcc = bdg_rescue_check(ctx, umi_len, max_ed)) return rcc;
+    if (ctx->resc.on) return bdg_fail(ctx, BDG_E_ARG, "the pipelined rescue is on: its store is in use (bdg_extract_set_rescue)");
+    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    if (n == 0) return BDG_OK;
+    if (!bases || !off || !recs || !support || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    StagedReads S;
+    int rc;
+    const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, sup_bytes = sizeof(uint32_t) * (size_t)ctx->w_n;
+    if ((rc = stage_reads(ctx, bases, off, n, rec_bytes + sup_bytes, S))) return rc;
+    hipStream_t st = ctx->stream;
+    bdg_extract_rec* const d_recs = static_cast<bdg_extract_rec*>(S.d_out);
+    uint32_t* const d_sup = reinterpret_cast<uint32_t*>(static_cast<char*>(S.d_out) + rec_bytes);
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, recs, rec_bytes, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_sup, support, sup_bytes, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
+    if ((rc = bdg_rescue_start(ctx))) return rc;
+    if (ctx->x_layout != BDG_LAYOUT_3P) return BDG_OK;          // (no read of the 5' layout is eligible)
+    if ((rc = bdg_rescue_store_reserve(ctx, n))) return rc;
+    ctx->resc.umi_len = umi_len;
+    if ((rc = bdg_rescue_store_batch(ctx, S.d_bases, S.d_off, d_recs, n, nullptr, umi_len, 0))) return rc;
+    uint64_t m = 0;
+    rc = bdg_rescue_finish(ctx, d_sup, max_ed, min_support, nullptr, out, n, &m);
+    *n_out = (uint32_t)m;
+    return rc;
+}
+
 int bdg_molecule_reps_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_molecule,
                           const uint32_t* d_cdna_len, uint64_t n, const uint32_t* d_cells, uint32_t n_cells,
                           uint8_t* d_rep, uint32_t* d_mol_reads)

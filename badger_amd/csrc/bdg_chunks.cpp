@@ -31,6 +31,116 @@ static int mirror_fetch(bdg_ctx* ctx, Mirror& m, size_t bytes, hipStream_t st)
     return BDG_OK;
 }
 
+
+// ---- the rescue store ------------------------------------------------------------------
+// room for `need` reads; what is stored moves along (behind the kernels that wrote it)
+int bdg_rescue_store_reserve(bdg_ctx* ctx, uint64_t need)
+{
+    bdg_ctx::Rescue& r = ctx->resc;
+    if (need <= r.cap) return BDG_OK;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * r.cap), 1ull << 10);
+    DevBuf nb;
+    const size_t bytes = RESC_STORE_READ_BYTES * cap + 64;
+    const hipError_t e = hipMalloc(&nb.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        nb.p = nullptr;
+        return bdg_fail(ctx, BDG_E_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes) for the rescue store");
+    }
+    nb.bytes = bytes;
+    if (r.store.p) {
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        uint32_t cnt = 0;
+        BDG_HIP_TRY(ctx, hipMemcpy(&cnt, r.counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
+        const uint64_t m = std::min<uint64_t>(cnt, r.cap);
+        const RescStore o = resc_store(r.store.p, r.cap), n = resc_store(nb.p, cap);
+        if (m) {
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(n.q, o.q, sizeof(uint32_t) * RESC_CAND * m, hipMemcpyDeviceToDevice, ctx->stream));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(n.pt, o.pt, sizeof(int32_t) * 2 * m, hipMemcpyDeviceToDevice, ctx->stream));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(n.read, o.read, sizeof(uint32_t) * m, hipMemcpyDeviceToDevice, ctx->stream));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(n.tail, o.tail, 2 * RESC_TAIL * m, hipMemcpyDeviceToDevice, ctx->stream));
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(n.mask, o.mask, sizeof(uint16_t) * m, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    r.store = std::move(nb);
+    r.cap = cap;
+    return BDG_OK;
+}
+
+int bdg_rescue_check(bdg_ctx* ctx, uint32_t umi_len, uint32_t max_ed)
+{
+    if (umi_len == 0 || umi_len > BDG_RESCUE_UMI_MAX) return bdg_fail(ctx, BDG_E_ARG, "rescue: umi_len out of range (1 .. 14)");
+    if (max_ed > BDG_RESCUE_MAX_ED_MAX) return bdg_fail(ctx, BDG_E_ARG, "rescue max_ed out of range (0 .. 2)");
+    return BDG_OK;
+}
+
+int bdg_rescue_start(bdg_ctx* ctx)
+{
+    bdg_ctx::Rescue& r = ctx->resc;
+    int rc = bdg_sync_all(ctx);
+    if (rc) return rc;
+    if ((rc = bdg_reserve(ctx, r.counters, RESC_CTR_BYTES))) return rc;
+    BDG_HIP_TRY(ctx, hipMemsetAsync(r.counters.p, 0, RESC_CTR_BYTES, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    r.known = r.ord = 0; r.umi_len = 0;
+    return BDG_OK;
+}
+
+int bdg_rescue_store_batch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
+                           const int32_t* polyt, uint32_t umi_len, uint32_t ord0)
+{
+    return bdg_rescue_windows_launch(ctx, d_bases, d_off, d_recs, n, polyt, umi_len, ord0, resc_store(ctx->resc.store.p, ctx->resc.cap),
+                                     ctx->resc.cap, static_cast<uint32_t*>(ctx->resc.counters.p));
+}
+
+static int rescue_read_counters(bdg_ctx* ctx, uint64_t* stored, uint64_t* eligible, bool* overflow)
+{
+    uint32_t c[RESC_CTR_BYTES / 4];
+    BDG_HIP_TRY(ctx, hipMemcpy(c, ctx->resc.counters.p, RESC_CTR_BYTES, hipMemcpyDeviceToHost));
+    *stored = c[0]; *overflow = c[1] != 0; *eligible = 0;
+    for (uint32_t k = 1; k <= RESC_ELIG_SHARDS; ++k) *eligible += c[RESC_CTR_WORDS * k];
+    return BDG_OK;
+}
+
+int bdg_rescue_finish(bdg_ctx* ctx, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support, bdg_rescue_rec* d_out,
+                      bdg_rescue_rec* out, uint64_t cap, uint64_t* n_out)
+{
+    bdg_ctx::Rescue& r = ctx->resc;
+    if (!r.counters.p) return bdg_fail(ctx, BDG_E_ARG, "no rescue store (bdg_extract_set_rescue)");
+    if (!d_support) d_support = static_cast<const uint32_t*>(ctx->corr.support.p);
+    if (!d_support) return bdg_fail(ctx, BDG_E_ARG, "rescue: no support array");
+    int rc = bdg_rescue_check(ctx, r.umi_len ? r.umi_len : 1, max_ed);
+    if (rc) return rc;
+    if ((rc = bdg_sync_all(ctx))) return rc;                         // (the match below reuses the workspaces of the slot matches)
+    uint64_t m = 0, elig = 0; bool ovf = false;
+    if ((rc = rescue_read_counters(ctx, &m, &elig, &ovf))) return rc;
+    if (ovf || m > r.cap) return bdg_fail(ctx, BDG_E_CAPACITY, "the rescue store overflowed");
+    *n_out = m;
+    if (m > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "rescue: " + std::to_string(m) + " records, room for " + std::to_string(cap));
+    if (m == 0) return BDG_OK;
+    if ((rc = bdg_nearest16_topk_check(ctx, (uint32_t)RESC_CAND, max_ed, CORR_K))) return rc;
+    // a piece of the store at a time: its ten lists per read (420 bytes) never outgrow 84 MB
+    const uint64_t piece = std::min<uint64_t>(m, 200000);
+    const size_t nq = piece * RESC_CAND;
+    if ((rc = bdg_reserve(ctx, r.lists, CORR_LISTS_READ_BYTES * nq + 64))) return rc;
+    if (!d_out && (rc = bdg_reserve(ctx, r.out, sizeof(bdg_rescue_rec) * piece))) return rc;
+    const CorrLists L = corr_lists(r.lists.p, nq, 0);
+    const RescStore S = resc_store(r.store.p, r.cap);
+    for (uint64_t j0 = 0; j0 < m; j0 += piece) {
+        const uint32_t mp = (uint32_t)std::min<uint64_t>(piece, m - j0);
+        if ((rc = bdg_nearest16_topk_launch(ctx, S.q + RESC_CAND * j0, 1u, 0, mp * (uint32_t)RESC_CAND, max_ed, CORR_K, L.idx8, L.ed8, L.nw, nullptr)))
+            return rc;
+        bdg_rescue_rec* const d = d_out ? d_out + j0 : static_cast<bdg_rescue_rec*>(r.out.p);
+        if ((rc = bdg_rescue_resolve_launch(ctx, S, j0, mp, L.idx8, L.ed8, L.nw, d_support, min_support, r.umi_len, d))) return rc;
+        if (!d_out) BDG_HIP_TRY(ctx, hipMemcpyAsync(out + j0, d, sizeof(bdg_rescue_rec) * mp, hipMemcpyDeviceToHost, ctx->stream));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // the store is filled by whichever wave comes first: input order is the order of `read`
+    if (!d_out) std::sort(out, out + m, [](const bdg_rescue_rec& a, const bdg_rescue_rec& b) { return a.read < b.read; });
+    return BDG_OK;
+}
+
 static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
 {
     const uint8_t* const d_bases = static_cast<const uint8_t*>(sl.d_bases.p);
@@ -53,6 +163,13 @@ static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
                 return rc;
             if ((rc = mirror_fetch(ctx, sl.chim, sizeof(bdg_chimera_rec) * n, st))) return rc;
         }
+    }
+    if (sl.resc_on) {
+        // the chunk's candidate windows behind its extraction, p from the scan's array, which the next extraction overwrites (a
+        // rerun passes here again: the failed pass's placeholder records are not eligible and stored nothing)
+        if ((rc = bdg_rescue_store_batch(ctx, d_bases, d_off, d_recs, sl.n, static_cast<const int32_t*>(ctx->x_polyt.p), sl.umi_len, sl.resc_ord0)))
+            return rc;
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.h_resc.p, ctx->resc.counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     BDG_HIP_TRY(ctx, hipEventRecord(sl.done, st));
     return BDG_OK;
@@ -184,7 +301,13 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     sl.layout = ctx->x_layout; sl.tso5_max_ed = ctx->trim5p_max_ed;
     sl.trim_on = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
     sl.chim_on = ctx->trim_on && ctx->chim_on; sl.chim_max_ed = ctx->chim_max_ed;
+    sl.resc_on = ctx->resc.on && sl.layout == BDG_LAYOUT_3P;             // (no read of the 5' layout is eligible)
     if (n == 0) { sl.busy = true; return BDG_OK; }
+    if (sl.resc_on) {
+        if (int rcr = bdg_rescue_check(ctx, umi_len, 0)) return rcr;
+        if (ctx->resc.umi_len && ctx->resc.umi_len != umi_len) return bdg_fail(ctx, BDG_E_ARG, "the rescue store holds reads of another umi_len");
+        if (ctx->resc.ord + n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads in one rescue store");
+    }
     if (int rco = bdg_check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t lo = off[0], total = off[n] - lo;
@@ -198,6 +321,14 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     if ((rc = mirror_reserve(ctx, sl.recs, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
     if (sl.trim_on && (rc = mirror_reserve(ctx, sl.trim, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
     if (sl.chim_on && (rc = mirror_reserve(ctx, sl.chim, sizeof(bdg_chimera_rec) * (size_t)n))) return rc;
+    if (sl.resc_on) {
+        // room for every read of this chunk and of the chunks still in flight behind what the last collect has seen
+        uint64_t need = ctx->resc.known + n;
+        for (const bdg_ctx::Slot& o : ctx->slots) if (&o != &sl && o.busy && o.resc_on) need += o.n;
+        if ((rc = pinned_reserve(ctx, sl.h_resc, sizeof(uint32_t)))) return rc;
+        if ((rc = bdg_rescue_store_reserve(ctx, need))) return rc;
+        sl.resc_ord0 = (uint32_t)ctx->resc.ord;                          // (the store's count moves on once the chunk is queued)
+    }
     if (!sl.done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     const double T1 = now_s();
     uint64_t* rel = static_cast<uint64_t*>(sl.h_off.p);
@@ -211,6 +342,7 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
     const double T3 = now_s();
     if ((rc = slot_enqueue(ctx, sl))) return rc;
     sl.busy = true;
+    if (sl.resc_on) { ctx->resc.ord += n; ctx->resc.umi_len = umi_len; }  // (a submit that failed leaves the ordinals where they were)
     const double T4 = now_s();
     if (g_submit_debug) { submit_add(0, T1 - T0); submit_add(1, T2 - T1); submit_add(2, T3 - T2); submit_add(3, T4 - T3); submit_add(4, 1.0); }
     return BDG_OK;
@@ -238,6 +370,7 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
     }
     if (rc) return rc;
     memcpy(out, sl.recs.h.p, sizeof(bdg_extract_rec) * (size_t)sl.n);
+    if (sl.resc_on) ctx->resc.known = *static_cast<const uint32_t*>(sl.h_resc.p);   // (chunks are collected in submission order)
     if (ctx->kept_recs.on) {
         const bdg_extract_rec* const d_recs = static_cast<const bdg_extract_rec*>(sl.recs.d.p);
         void* at;
@@ -302,6 +435,67 @@ int bdg_extract_collect_chimera(bdg_ctx* ctx, uint32_t slot, bdg_chimera_rec* ou
     const bdg_ctx::Slot& sl = ctx->slots[slot];
     return collect_result(ctx, sl, sl.chim, sizeof(bdg_chimera_rec), sl.chim_on,
                           "the slot's chunk was submitted without a chimera search (bdg_extract_set_chimera)", out);
+}
+
+
+// ---- barcode rescue --------------------------------------------------------------------
+int bdg_extract_set_rescue(bdg_ctx* ctx, int on)
+{
+    if (!ctx) return BDG_E_ARG;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (const bdg_ctx::Slot& sl : ctx->slots) if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "a chunk is in flight: collect it first");
+    ctx->resc.on = false;
+    int rc = bdg_rescue_start(ctx);
+    if (rc) return rc;
+    if (on) { ctx->resc.on = true; return BDG_OK; }
+    ctx->resc.store.reset(); ctx->resc.lists.reset(); ctx->resc.out.reset();
+    ctx->resc.cap = 0;
+    return BDG_OK;
+}
+
+int bdg_extract_rescue_resolve(bdg_ctx* ctx, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support,
+                               bdg_rescue_rec* out, uint64_t cap, uint64_t* n_out)
+{
+    if (!ctx || !n_out || (cap && !out)) return BDG_E_ARG;
+    if (!ctx->resc.on) return bdg_fail(ctx, BDG_E_ARG, "the rescue is off (bdg_extract_set_rescue)");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_rescue_finish(ctx, d_support, max_ed, min_support, nullptr, out, cap, n_out);
+}
+
+int bdg_rescue_counts(bdg_ctx* ctx, uint64_t out[2])
+{
+    if (!ctx || !out) return BDG_E_ARG;
+    out[0] = out[1] = 0;
+    if (!ctx->resc.counters.p) return BDG_OK;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = bdg_sync_all(ctx);
+    if (rc) return rc;
+    bool ovf = false;
+    return rescue_read_counters(ctx, &out[0], &out[1], &ovf);
+}
+
+int bdg_rescue_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs,
+                         uint32_t umi_len, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support,
+                         bdg_rescue_rec* d_out, uint32_t* n_out)
+{
+    if (!ctx || !n_out) return BDG_E_ARG;
+    *n_out = 0;
+    if (int rcc = bdg_rescue_check(ctx, umi_len, max_ed)) return rcc;
+    if (ctx->resc.on) return bdg_fail(ctx, BDG_E_ARG, "the pipelined rescue is on: its store is in use (bdg_extract_set_rescue)");
+    if (ctx->w_n == 0) return bdg_fail(ctx, BDG_E_ARG, "no whitelist loaded (bdg_whitelist_load)");
+    if (n && (!d_bases || !d_off || !d_recs || !d_support || !d_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (reinterpret_cast<uintptr_t>(d_recs) & 15u) return bdg_fail(ctx, BDG_E_ARG, "d_recs must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return bdg_fail(ctx, BDG_E_ARG, "d_out must be 4-byte aligned");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = bdg_rescue_start(ctx);
+    if (rc || n == 0 || ctx->x_layout != BDG_LAYOUT_3P) return rc;  // (no read of the 5' layout is eligible)
+    if ((rc = bdg_rescue_store_reserve(ctx, n))) return rc;
+    ctx->resc.umi_len = umi_len;
+    if ((rc = bdg_rescue_store_batch(ctx, d_bases, d_off, d_recs, n, nullptr, umi_len, 0))) return rc;
+    uint64_t m = 0;
+    rc = bdg_rescue_finish(ctx, d_support, max_ed, min_support, d_out, nullptr, n, &m);
+    *n_out = (uint32_t)m;
+    return rc;
 }
 
 // ---- slot match, correction store ------------------------------------------------------

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -96,6 +97,9 @@ struct bdg_ctx {
         bool match_queued = false;
         bool match_corr = false;                             // correction on: the match runs at k = 8 into corr.lists at corr_at,
         uint64_t corr_at = 0;                                // and match holds the compact block of match_k slots (0: best hit)
+        // rescue windows of the chunk (bdg_extract_set_rescue): behind the extraction, into the context's store
+        bool resc_on = false; uint32_t resc_ord0 = 0;        // what the chunk was submitted with: its first read's ordinal
+        PinnedBuf h_resc;                                    // the store's counter behind the chunk (u32)
     } slots[BDG_SLOTS];
     // ---- whitelist correction of a stage-1 run (correct_kernels.hip, bdg_stage1_run with BDG_STAGE1_WL_CORRECT)
     struct Correct {
@@ -105,6 +109,17 @@ struct bdg_ctx {
         DevBuf support;      // u32 [w_n]: exact hits per entry over this context's chunks
         DevBuf out;          // resolve: corr_out()
     } corr;
+    // ---- barcode rescue (rescue_kernels.hip; bdg_rescue_batch, bdg_extract_set_rescue, bdg_stage1_run with BDG_STAGE1_WL_RESCUE)
+    struct Rescue {
+        bool on = false;         // the pipelined form: submits store their chunk's windows
+        DevBuf store;            // resc_store() with room for cap reads
+        uint64_t cap = 0;
+        DevBuf counters;         // RESC_CTR_BYTES: the store's counter and overflow flag on one line, the eligible reads on eight
+        uint64_t known = 0;      // stored reads behind the chunk collected last; the chunks in flight add at most their reads
+        uint64_t ord = 0;        // reads submitted since the store was started
+        uint32_t umi_len = 0;    // of the reads in the store (0: none yet)
+        DevBuf lists, out;       // resolve, a piece of the store at a time: the ten top-8 lists of every read, the records
+    } resc;
     bool trim_on = false; uint32_t trim_min_score = 0;       // bdg_extract_set_trim: for the submits that follow
     bool chim_on = false; uint32_t chim_max_ed = 0;          // bdg_extract_set_chimera: likewise (only while trim_on)
     uint32_t trim5p_umi_len = 10, trim5p_max_ed = BDG_TRIM5P_MAX_ED_DEFAULT;   // bdg_trim_set_5p: read only in BDG_LAYOUT_5P
@@ -220,6 +235,8 @@ static inline CorrOut corr_out(void* base, size_t n)
 // the correction file of bdg_stage1_run (tsv_io.cpp): n results in input order; *called = rows of status exact or corrected
 bool bdg_write_corrected(const char* path, const bdg_idstore* ids, const CorrOut& res, uint64_t n, const uint32_t* wl, uint32_t nw,
                          uint64_t* called);
+// the file of rescued reads of bdg_stage1_run (tsv_io.cpp): m records sorted by `read` (an index into ids), none of status none
+bool bdg_write_rescued(const char* path, const bdg_idstore* ids, const bdg_rescue_rec* recs, uint64_t m, const uint32_t* wl, uint32_t nw);
 // m reads of `src` from read `from` on to read `at` of `dst`
 static inline void corr_out_copy(const CorrOut& dst, size_t at, const CorrOut& src, size_t from, size_t m)
 {
@@ -230,6 +247,23 @@ static inline void corr_out_copy(const CorrOut& dst, size_t at, const CorrOut& s
     memcpy(dst.status + at, src.status + from, m);
 }
 static_assert(CORR_LISTS_READ_BYTES == 42 && CORR_OUT_READ_BYTES == 12, "layouts correct_kernels.hip reads and writes");
+
+// Rescue::store with room for cap reads (the kernels' view): q u32 [cap * 10] (candidate c = strand * 5 + d + 2) | pt i32 [cap * 2]
+// | read u32 [cap] | tail u8 [cap * 32] (per strand the 16 bytes in front of p, from p - U - 2 on, zero-padded; 16-byte aligned)
+// | mask u16 [cap]
+constexpr size_t RESC_CAND = 10, RESC_TAIL = 16, RESC_STORE_READ_BYTES = 4 * RESC_CAND + 8 + 4 + 2 * RESC_TAIL + 2;
+constexpr uint32_t RESC_CTR_WORDS = 32, RESC_ELIG_SHARDS = 8, RESC_CTR_BYTES = 4 * RESC_CTR_WORDS * (1 + RESC_ELIG_SHARDS);
+struct RescStore { uint32_t* q; int32_t* pt; uint32_t* read; uint8_t* tail; uint16_t* mask; };
+static inline RescStore resc_store(void* base, uint64_t cap)
+{
+    // (the tail first: a hipMalloc'd base is 256-byte aligned and 32 * cap keeps the words behind it aligned)
+    uint8_t* const tail = static_cast<uint8_t*>(base);
+    uint32_t* const q = reinterpret_cast<uint32_t*>(tail + 2 * RESC_TAIL * cap);
+    int32_t* const pt = reinterpret_cast<int32_t*>(q + RESC_CAND * cap);
+    uint32_t* const read = reinterpret_cast<uint32_t*>(pt + 2 * cap);
+    return RescStore{ q, pt, read, tail, reinterpret_cast<uint16_t*>(read + cap) };
+}
+static_assert(RESC_STORE_READ_BYTES == 86, "device bytes per stored read (DESIGN 4.16)");
 
 // Event-bracketed launch bookkeeping.
 int  bdg_timer_id(bdg_ctx* ctx, const char* name);

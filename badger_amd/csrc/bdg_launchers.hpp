@@ -54,12 +54,26 @@ int bdg_layout5p_launch(bdg_ctx*, const uint64_t*, uint32_t, uint32_t, bdg_extra
 int bdg_trim5p_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, uint32_t, uint32_t, bdg_trim_rec*);
 // chimera_kernels.hip
 int bdg_chimera_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, const bdg_trim_rec*, uint32_t, uint32_t, bdg_chimera_rec*);
+// rescue_kernels.hip
+int bdg_rescue_windows_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, const int32_t* polyt, uint32_t umi_len,
+                              uint32_t ord0, const RescStore&, uint64_t cap, uint32_t* counters);
+int bdg_rescue_resolve_launch(bdg_ctx*, const RescStore&, uint64_t j0, uint32_t m, const uint32_t* idx8, const uint8_t* ed8, const uint16_t* nwi,
+                              const uint32_t* support, uint32_t min_support, uint32_t umi_len, bdg_rescue_rec* d_out);
 
 // ---- host only: shared by bdg_abi.cpp and bdg_chunks.cpp ----
 int bdg_sync_all(bdg_ctx*);                                   // bdg_abi.cpp: a waiting deferred match queued, then both streams idle
 int bdg_ensure_aux(bdg_ctx*);                                 // bdg_abi.cpp: the auxiliary stream and its events exist
 int bdg_check_offsets(bdg_ctx*, const uint64_t*, uint32_t);   // bdg_abi.cpp: the first read out of order or too long for the kernels
 int bdg_correct_grow(bdg_ctx*, uint64_t need);                // bdg_chunks.cpp: room for `need` reads in the correction store
+// bdg_chunks.cpp, the rescue store: start an empty one; store the windows of a batch (polyt: the scan's array of the batch, or null);
+// match and resolve what is stored (d_support null: the correction's array; records to d_out if set, else to `out` sorted by read)
+int bdg_rescue_start(bdg_ctx*);
+int bdg_rescue_store_reserve(bdg_ctx*, uint64_t need);
+int bdg_rescue_store_batch(bdg_ctx*, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
+                           const int32_t* polyt, uint32_t umi_len, uint32_t ord0);
+int bdg_rescue_finish(bdg_ctx*, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support, bdg_rescue_rec* d_out,
+                      bdg_rescue_rec* out, uint64_t cap, uint64_t* n_out);
+int bdg_rescue_check(bdg_ctx*, uint32_t umi_len, uint32_t max_ed);
 
 // lists of the correction store (Correct::lists) from read `at` on
 static inline CorrLists corr_lists(bdg_ctx* ctx, uint64_t at) { return corr_lists(ctx->corr.lists.p, ctx->corr.cap, at); }

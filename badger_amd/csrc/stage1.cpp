@@ -44,7 +44,7 @@ struct Job : Fly {
 // What a call of bdg_stage1_run asks for: the bits of opts->whitelist decoded and everything checked, once
 struct Stage1Plan {
     // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
-    bool wl_on = false, corr = false, trim = false, chim = false, tags = false, trim5p = false, no_tsv = false;
+    bool wl_on = false, corr = false, trim = false, chim = false, tags = false, trim5p = false, no_tsv = false, resc = false;
     // how much of the caller's result is the library's to clear and write (the fields behind whitelist_barcodes only with the
     // bits that fill them); 0 until the flags and the layout have passed their checks: a call rejected there leaves the result alone
     size_t result_bytes = 0;
@@ -62,6 +62,8 @@ int make_plan(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, co
     p.trim = (o->whitelist & BDG_STAGE1_TRIM) != 0; p.chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
     p.wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS)) != 0;
     p.corr = p.wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT); p.no_tsv = !out_path;
+    p.resc = (o->whitelist & BDG_STAGE1_WL_RESCUE) != 0;
+    if (p.resc && !p.corr) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_WL_RESCUE needs BDG_STAGE1_WL_CORRECT");
     if (p.chim && !p.trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_CHIMERA needs BDG_STAGE1_TRIM");
     if (p.tags && !p.trim) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS needs BDG_STAGE1_TRIM");
     if (p.tags && p.wl_on) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_TAGS takes no whitelist mode (the cell is the tag)");
@@ -75,9 +77,15 @@ int make_plan(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, co
     if (p.trim) p.result_bytes = offsetof(bdg_stage1_result, chimera_cut);
     if (p.chim) p.result_bytes = offsetof(bdg_stage1_result, tags_no_cell);
     if (p.tags) p.result_bytes = offsetof(bdg_stage1_result, trimmed_no_anchor);
-    if (p.trim5p) p.result_bytes = sizeof(bdg_stage1_result);
+    if (p.trim5p) p.result_bytes = offsetof(bdg_stage1_result, rescue_eligible);
+    if (p.resc) p.result_bytes = sizeof(bdg_stage1_result);
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
     if (p.chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
+    if (p.resc) {
+        if (c0->x_layout != BDG_LAYOUT_3P) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_WL_RESCUE needs the 3' layout");
+        if (int rcr = bdg_rescue_check(c0, o->umi_len, o->rescue_max_ed)) return rcr;
+        if (!o->rescued_path) return bdg_fail(c0, BDG_E_ARG, "no rescued_path");
+    }
     if (p.trim) {
         if (!o->trimmed_path) return bdg_fail(c0, BDG_E_ARG, "no trimmed_path");
         if (int rcs = check_tso_min_score(c0, o->tso_min_score)) return rcs;
@@ -315,6 +323,47 @@ int correct_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, 
     return BDG_OK;
 }
 
+// after correct_run of a run with BDG_STAGE1_WL_RESCUE (every context holds the summed support by then): every context's store
+// matched and resolved, the records put in input order (a context counts its own reads: chunk j was context j mod n_ctx's), the
+// file written
+int rescue_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, const bdg_idstore* ids, const std::vector<uint32_t>& chunk_n,
+               uint64_t n, const uint32_t* wl, uint32_t nw, bdg_stage1_result* res, std::string& err)
+{
+    if (n >= (1ull << 32)) { err = "more than 2^32 - 1 reads in a run with BDG_STAGE1_WL_RESCUE"; return BDG_E_ARG; }
+    std::vector<bdg_rescue_rec> all, loc;
+    uint64_t eligible = 0;
+    for (uint32_t c = 0; c < n_ctx; ++c) {
+        uint64_t cnt[2] = { 0, 0 }, m = 0;
+        int rc = bdg_rescue_counts(ctxs[c], cnt);
+        loc.resize(cnt[0]);
+        if (!rc) rc = bdg_extract_rescue_resolve(ctxs[c], nullptr, o->rescue_max_ed, o->rescue_min_support, loc.data(), loc.size(), &m);
+        if (rc) { err = bdg_last_error(ctxs[c]); return rc; }
+        eligible += cnt[1];
+        // the context's chunks: where each starts among its own reads, and in the input
+        std::vector<uint64_t> lstart, gstart;
+        uint64_t g = 0, l = 0;
+        for (size_t j = 0; j < chunk_n.size(); ++j) {
+            if (j % n_ctx == c) { lstart.push_back(l); gstart.push_back(g); l += chunk_n[j]; }
+            g += chunk_n[j];
+        }
+        for (uint64_t k = 0; k < m; ++k) {
+            bdg_rescue_rec r = loc[k];
+            if (r.status == BDG_RESCUE_NONE) continue;
+            if (r.read >= l) { err = "a rescue record names a read the context never saw"; return BDG_E_ARG; }
+            const size_t j = (size_t)(std::upper_bound(lstart.begin(), lstart.end(), (uint64_t)r.read) - lstart.begin()) - 1;
+            r.read = (uint32_t)(gstart[j] + (r.read - lstart[j]));
+            all.push_back(r);
+        }
+    }
+    std::sort(all.begin(), all.end(), [](const bdg_rescue_rec& a, const bdg_rescue_rec& b) { return a.read < b.read; });
+    uint64_t by_status[4] = { 0, 0, 0, 0 };
+    for (const bdg_rescue_rec& r : all) ++by_status[r.status & 3u];
+    if (!bdg_write_rescued(o->rescued_path, ids, all.data(), all.size(), wl, nw)) { err = std::string("write error on ") + o->rescued_path; return BDG_E_ARG; }
+    res->rescue_eligible = eligible; res->rescue_rescued = by_status[BDG_RESCUE_RESCUED];
+    res->rescue_ambiguous = by_status[BDG_RESCUE_AMBIGUOUS]; res->rescue_truncated = by_status[BDG_RESCUE_TRUNCATED];
+    return BDG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -339,6 +388,8 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
         for (uint32_t c = 0; c < n_ctx; ++c) if (const int r = bdg_correct_begin(ctxs[c])) return bdg_fail(c0, r, std::string(bdg_last_error(ctxs[c])));
         ids = bdg_idstore_new();
     }
+    Guard resc_off{ [&] { every_ctx([](bdg_ctx* c) { (void)bdg_extract_set_rescue(c, 0); }); }, plan.resc };
+    if (plan.resc) for (uint32_t c = 0; c < n_ctx; ++c) if (const int r = bdg_extract_set_rescue(ctxs[c], 1)) return bdg_fail(c0, r, std::string(bdg_last_error(ctxs[c])));
     const double t_start = now_s();
     const uint64_t max_outstanding = 2 * plan.fthreads + 2;      // collected chunks waiting for / in the formatters
     ChunkLoop L{ nullptr, ctxs, n_ctx, plan.per_ctx, o->umi_len, res, wl_on ? o : nullptr, ids, false, false };
@@ -422,6 +473,8 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     if (tags) { res->tags_no_cell = X.no_cell; res->tags_not_kept = X.not_kept; }
     if (plan.trim5p) res->trimmed_no_anchor = X.no_anchor;
     if (plan.corr && rc == BDG_OK && ok_io && !P.tsv.failed) rc = correct_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, plan.wl.data(), (uint32_t)plan.wl.size(), res, L.err);
+    if (plan.resc && rc == BDG_OK && ok_io && !P.tsv.failed) rc = rescue_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, plan.wl.data(), (uint32_t)plan.wl.size(), res, L.err);
+    resc_off.run();
     corr_end.run();
     res->seconds_total = now_s() - t_start;
     if (rc) return bdg_fail(c0, rc, L.err);

@@ -121,6 +121,50 @@ bool bdg_write_corrected(const char* path, const bdg_idstore* ids, const CorrOut
         });
 }
 
+bool bdg_write_rescued(const char* path, const bdg_idstore* ids, const bdg_rescue_rec* recs, uint64_t m, const uint32_t* wl, uint32_t nw)
+{
+    static const char* const STATUS[] = { "none", "rescued", "ambiguous", "truncated" };
+    const uint64_t n_ids = ids->off.size() - 1;
+    for (uint64_t k = 0; k < m; ++k) if (recs[k].read >= n_ids) return false;
+    // the ids of the rows, so that write_id_rows serves a file that names a part of the run's reads
+    bdg_idstore rows;
+    rows.off.reserve(m + 1);
+    for (uint64_t k = 0; k < m; ++k) {
+        const uint64_t a = ids->off[recs[k].read], b = ids->off[recs[k].read + 1];
+        rows.text.insert(rows.text.end(), ids->text.begin() + (ptrdiff_t)a, ids->text.begin() + (ptrdiff_t)b);
+        rows.off.push_back(rows.text.size());
+    }
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return false;
+    auto shown = [&](uint64_t k) { return recs[k].status == BDG_RESCUE_RESCUED && recs[k].entry < nw; };
+    auto ilen = [](int v) { return v < 0 ? 1 + dec_len((uint32_t)-v) : dec_len((uint32_t)v); };
+    auto umi_len = [&](uint64_t k) { return strnlen(recs[k].umi, sizeof(recs[k].umi)); };
+    return write_id_rows(fd, "#read_id\trescued_barcode\tdist\tsupport\tstrand\tpolyT_start\toffset\tUMI\tstatus", &rows, m,
+                         16 + 4 + 10 + 1 + 11 + 4 + 16 + 9 + 7,
+        [&](uint64_t k) -> uint64_t {
+            const bdg_rescue_rec& r = recs[k];
+            return (shown(k) ? 16 + umi_len(k) : 2) + 7 + ilen(r.dist) + dec_len(r.support) + 1 + ilen(r.polyT) + ilen(r.offset) + strlen(STATUS[r.status & 3u]);
+        },
+        [&](uint64_t k, char* o) -> char* {
+            const bdg_rescue_rec& r = recs[k];
+            const bool ok = shown(k);
+            if (ok) o = put_barcode16(o, wl[r.entry]);
+            else *o++ = '*';
+            *o++ = '\t'; o = put_int(o, r.dist);
+            *o++ = '\t'; o = put_uint(o, r.support);
+            *o++ = '\t'; *o++ = ok ? (r.strand > 0 ? '+' : '-') : '.';
+            *o++ = '\t'; o = put_int(o, r.polyT);
+            *o++ = '\t'; o = put_int(o, r.offset);
+            *o++ = '\t';
+            if (ok) { const size_t l = umi_len(k); memcpy(o, r.umi, l); o += l; }
+            else *o++ = '*';
+            *o++ = '\t';
+            const char* s = STATUS[r.status & 3u];
+            const size_t l = strlen(s); memcpy(o, s, l); o += l;
+            return o;
+        });
+}
+
 extern "C" {
 
 bdg_idstore* bdg_idstore_new(void) { return new bdg_idstore(); }

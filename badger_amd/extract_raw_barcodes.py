@@ -76,6 +76,7 @@ CANDIDATES_COLUMN = "whitelist_candidates"
 MAX_BC_DIST_DEFAULT = 2
 CORRECT_MAX_BC_DIST = 3
 CORRECTED_SUFFIX = ".corrected.tsv"
+RESCUED_SUFFIX = ".rescued.tsv"          # --bc_rescue: the barcodes found for reads whose row prints "*"
 BC_EDIT_BITS_DEFAULT = 5
 BC_MIN_POSTERIOR_DEFAULT = 0.975
 TSO_MIN_SCORE_RANGE = (8, 30)
@@ -423,7 +424,10 @@ def _run_native(args, header_every, threads, skip_secondary):
                                  detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
                                  whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
                                  bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
-                                 **_correct_kwargs(args, wl is not None), **_trim_kwargs(args))
+                                 **_correct_kwargs(args, wl is not None), **_trim_kwargs(args), **_rescue_kwargs(args, wl is not None))
+    if _rescuing(args):
+        logger.info("Rescued reads: %d eligible, %d rescued, %d ambiguous, %d truncated, written to %s"
+                    % (res.rescue_eligible, res.rescue_rescued, res.rescue_ambiguous, res.rescue_truncated, args.output + RESCUED_SUFFIX))
     if getattr(args, "trimmed_reads", None) and is_5p_mode(args.mode):
         logger.info("Trimmed reads: %d written to %s, %d with the RT primer cut off, %d bases, %d left out without the switch oligo"
                     % (res.trimmed_reads, args.trimmed_reads, res.trimmed_tso, res.trimmed_bases, res.trimmed_no_anchor))
@@ -573,7 +577,24 @@ def parse_args(sys_argv):
     p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
                    help="--chimera_cut: edits allowed in the 22-base adapter (two more in the 30-base oligo), %d .. %d (default %d)"
                         % (CHIMERA_MAX_ED_RANGE + (_native.CHIMERA_MAX_ED_DEFAULT,)))
+    p.add_argument("--bc_rescue", action="store_true", default=False,
+                   help="--bc_correct: look for a known barcode in reads without a usable adapter, at the place their polyT tail implies "
+                        "(16 bases, the UMI, the tail; both strands, %d bases of slack either way), among the whitelist entries this run "
+                        "saw exactly; into <output>%s; 3' modes only" % (_native.RESCUE_SLACK, RESCUED_SUFFIX))
+    p.add_argument("--rescue_max_ed", type=_rescue_max_ed, default=None, metavar="E",
+                   help="--bc_rescue: largest edit distance of a rescued barcode, 0 .. %d (default %d)"
+                        % (_native.RESCUE_MAX_ED_MAX, _native.RESCUE_MAX_ED_DEFAULT))
+    p.add_argument("--rescue_min_support", type=_rescue_min_support, default=None, metavar="M",
+                   help="--bc_rescue: exact hits a whitelist entry needs in this run to be a target (default %d)"
+                        % _native.RESCUE_MIN_SUPPORT_DEFAULT)
     args = p.parse_args(sys_argv)
+    if args.bc_rescue and not args.bc_correct:
+        p.error("--bc_rescue needs --bc_correct")
+    if args.bc_rescue and is_5p_mode(args.mode):
+        p.error("--bc_rescue serves the 3' modes only (a 5' read would be anchored on the switch oligo)")
+    for flag in ("rescue_max_ed", "rescue_min_support"):
+        if getattr(args, flag) is not None and not args.bc_rescue:
+            p.error("--%s needs --bc_rescue" % flag)
     if args.tso_min_score is not None and not args.trimmed_reads:
         p.error("--tso_min_score needs --trimmed_reads")
     check_5p_args(p, args.mode, args.tso5_max_ed, args.tso_min_score, args.trimmed_reads, "--trimmed_reads")
@@ -692,6 +713,40 @@ def _bc_edit_bits(text):
     if not 1 <= v <= 8:
         raise argparse.ArgumentTypeError("%d is outside 1 .. 8" % v)
     return v
+
+
+def _rescue_max_ed(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 0 <= v <= _native.RESCUE_MAX_ED_MAX:
+        raise argparse.ArgumentTypeError("%d is outside 0 .. %d" % (v, _native.RESCUE_MAX_ED_MAX))
+    return v
+
+
+def _rescue_min_support(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 0 <= v < 1 << 32:
+        raise argparse.ArgumentTypeError("%d is outside 0 .. 2^32 - 1" % v)
+    return v
+
+
+def _rescuing(args):
+    return _correcting(args) and bool(getattr(args, "bc_rescue", False))
+
+
+def _rescue_kwargs(args, whitelist):
+    """stage1_run's rescue arguments: none without --bc_rescue"""
+    if not (whitelist and _rescuing(args)):
+        return {}
+    ed, sup = getattr(args, "rescue_max_ed", None), getattr(args, "rescue_min_support", None)
+    return dict(rescued_path=args.output + RESCUED_SUFFIX,
+                rescue_max_ed=_native.RESCUE_MAX_ED_DEFAULT if ed is None else ed,
+                rescue_min_support=_native.RESCUE_MIN_SUPPORT_DEFAULT if sup is None else sup)
 
 
 def _correcting(args):

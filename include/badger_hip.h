@@ -366,6 +366,83 @@ int  bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, 
 int  bdg_extract_set_chimera(bdg_ctx* ctx, int on, uint32_t max_ed);
 int  bdg_extract_collect_chimera(bdg_ctx* ctx, uint32_t slot, bdg_chimera_rec* out);
 
+/* ---- barcode rescue (stage 1's --bc_rescue; the rule restated in badger_amd/rescue.py) -------------------------------- */
+/* A read without a usable R1 adapter (its row prints "*") may still hold its barcode where the polyT tail implies it: 16 bases,
+ * then the UMI, then the tail.  Per read, from its extraction record, its bases, umi_len U (1 .. BDG_RESCUE_UMI_MAX), the loaded
+ * whitelist and a support array s(w) over its entries (uint32 [nw], indexed like the whitelist the caller loaded: what
+ * --bc_correct counts, the run's exact hits per entry).  Integers only.
+ *   eligible    rec.valid == 0, no BDG_FLAG_INCOMPLETE, the context in BDG_LAYOUT_3P (in BDG_LAYOUT_5P no read is eligible).
+ *   candidates  both strand texts s of length L: the read and its reverse complement.  p = find_polyt_start(s) with the
+ *               reference's defaults (barcode_extraction/common.py:10-31: the first window of 16 letters holding >= 12 'T' among
+ *               the window starts 0 .. L - 17, moved on to the first "TTT" from there if there is one; -1 without such a window) -
+ *               the value k_scan_reads computes for every read and strand.  A strand with p >= 0 gives, for every offset d in
+ *               -BDG_RESCUE_SLACK .. +BDG_RESCUE_SLACK, the window s[b : b + 16], b = p - U - 16 + d; it is a candidate when
+ *               0 <= b, b + 16 <= L and its 16 letters are all ACGT; its query is the window's rank() (bdg_extract_rec.bc_rank's
+ *               packing).  At most 2 * (2 * BDG_RESCUE_SLACK + 1) = 10 candidates a read.
+ *   match       each candidate's top-8 list within D = max_ed (0 .. BDG_RESCUE_MAX_ED_MAX) and its n_within: bdg_nearest16_topk_dev
+ *               at k = 8.  Only list entries w with s(w) >= min_support count: the pairs (candidate, entry).
+ *   resolve     no pair: BDG_RESCUE_NONE.  Otherwise e = the smallest distance among the pairs; if a candidate holding a pair at
+ *               distance e has n_within > 8 (its list may hide an equal entry): BDG_RESCUE_TRUNCATED; else if the pairs at
+ *               distance e name more than one entry: BDG_RESCUE_AMBIGUOUS; else BDG_RESCUE_RESCUED with that entry, reported
+ *               from the candidate that holds it at distance e with the smallest |d|, then d < 0 before d > 0, then the forward
+ *               strand before the reverse one.
+ * A plain minimum and set tests over at most 80 pairs: the answer depends neither on the order the reads were stored in nor on
+ * the order the candidates were looked at. */
+#define BDG_RESCUE_SLACK 2
+#define BDG_RESCUE_MAX_ED_DEFAULT 1        /* on the host model no random read is rescued at 1, 2 to 6 of 2,000 at 2 (1,427 supported cells) */
+#define BDG_RESCUE_MAX_ED_MAX 2
+#define BDG_RESCUE_MIN_SUPPORT_DEFAULT 2
+#define BDG_RESCUE_UMI_MAX 14              /* the UMI text (U - d letters) fits bdg_rescue_rec.umi */
+#define BDG_RESCUE_NONE      0
+#define BDG_RESCUE_RESCUED   1
+#define BDG_RESCUE_AMBIGUOUS 2
+#define BDG_RESCUE_TRUNCATED 3
+/* One record per eligible read that has at least one candidate (every other read has none: its status is BDG_RESCUE_NONE by
+ * definition).  Only a BDG_RESCUE_RESCUED record fills entry .. strand and umi; the others carry entry 0xFFFFFFFF, support 0,
+ * polyT -1, bc_start -1, offset 0, strand 0, an empty umi, and dist = e (-1 for BDG_RESCUE_NONE). */
+typedef struct bdg_rescue_rec {
+    uint32_t read;       /* the read's ordinal: its index in the batch, or in the context's submission order (pipelined form) */
+    uint32_t entry;      /* whitelist entry, the caller's index */
+    uint32_t support;    /* s(entry) */
+    int32_t  polyT;      /* p of the reporting candidate's strand (strand coordinates, like everything here) */
+    int32_t  bc_start;   /* b: the barcode window is s[b : b + 16] */
+    int8_t   offset;     /* d */
+    int8_t   dist;       /* e */
+    int8_t   strand;     /* +1: the read as given, -1: its reverse complement, 0: not rescued */
+    uint8_t  status;     /* BDG_RESCUE_* */
+    char     umi[16];    /* s[b + 16 : p], U - d letters (U +- BDG_RESCUE_SLACK), zero-padded */
+} bdg_rescue_rec;        /* 40 bytes */
+/* Device-resident: the bases, offsets and records of the bdg_extract_batch_dev call just made (same stream), d_support [nw] on
+ * the device, d_out with room for n records.  Runs the three steps - k_rescue_windows (eligible reads compacted into the
+ * context's rescue store: ten queries, a validity mask, the ordinal, both p and the letters in front of them), the top-k match
+ * of the stored queries, k_rescue_resolve - and waits: *n_out (host) = the records written, one per stored read, in no
+ * particular order (the store is filled by whichever wave comes first; sort by `read`).  p is recomputed from the bases here,
+ * so the call serves records from anywhere - and is no fast path: one lane walks its whole read letter by letter on both
+ * strands (several extraction steps per batch); a pipeline takes the form below, which reads p from the scan.  BDG_E_ARG without a whitelist, for max_ed > BDG_RESCUE_MAX_ED_MAX, for umi_len
+ * outside 1 .. BDG_RESCUE_UMI_MAX, and while the pipelined form below is on (they share the store). */
+int  bdg_rescue_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs,
+                          uint32_t umi_len, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support,
+                          bdg_rescue_rec* d_out, uint32_t* n_out);
+/* Host buffers: reads as for bdg_extract_batch, their records, support [nw]; copies in, runs, copies out; the records come
+ * sorted by `read`. */
+int  bdg_rescue_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_extract_rec* recs,
+                      uint32_t umi_len, const uint32_t* support, uint32_t max_ed, uint32_t min_support,
+                      bdg_rescue_rec* out, uint32_t* n_out);
+/* The pipelined path.  on != 0 starts an empty store; while on, bdg_extract_submit queues k_rescue_windows behind the chunk's
+ * extraction on the same stream (p from the scan's own array; a chunk that collect runs again after a queue overflow passes
+ * again: the failed pass's placeholder records are not eligible and stored nothing), `read` counting the reads submitted since.
+ * The store stays on the device (86 bytes per stored read) until on = 0 frees it.  After the last collect,
+ * bdg_extract_rescue_resolve matches and resolves everything stored: d_support as above, or NULL for the context's own support
+ * array of a whitelist correction (bdg_stage1_run sums it over its contexts first); out with room for cap records, sorted by
+ * `read`; *n_out = the stored reads (BDG_E_CAPACITY, nothing written, when cap is smaller).  The store is kept: the call may
+ * be repeated with other values.  Waits for the context's streams. */
+int  bdg_extract_set_rescue(bdg_ctx* ctx, int on);
+int  bdg_extract_rescue_resolve(bdg_ctx* ctx, const uint32_t* d_support, uint32_t max_ed, uint32_t min_support,
+                                bdg_rescue_rec* out, uint64_t cap, uint64_t* n_out);
+/* Counts of the store (the pipelined run so far, or the last bdg_rescue_batch / bdg_rescue_batch_dev call): out[0] stored
+ * reads, out[1] eligible reads (with or without a candidate).  Waits for the context's streams. */
+int  bdg_rescue_counts(bdg_ctx* ctx, uint64_t out[2]);
+
 /* ---- read ingest and row output (host side) --------------------------------------------- */
 /* [gzipped / BGZF] FASTA / FASTQ / SAM and BAM -> chunks of at most chunk_reads reads {concatenated bases, offsets, ids}
  * in pinned host memory (pinned = 0: pageable, for hosts without a GPU), in file order.  Replaces the reference's record
@@ -497,6 +574,15 @@ int64_t bdg_format_trimmed_tags(const bdg_ingest_chunk* chunk, const bdg_extract
  * field).  out_path may be NULL with this bit: no TSV is written.  The run fails with BDG_E_ARG, and says so, when the input
  * yields another number of reads than tag_reads.  Stage 2's second pass over its input (--tagged_reads). */
 #define BDG_STAGE1_TAGS          0x1000u
+/* bdg_stage1_opts.whitelist, valid only together with BDG_STAGE1_WL_CORRECT (BDG_E_ARG otherwise; the contexts in BDG_LAYOUT_3P):
+ * every context stores the candidate windows of its reads without a barcode (bdg_extract_set_rescue); after the last chunk, once
+ * the support arrays of all contexts are summed and written back and the correction is resolved, the stores are matched and
+ * resolved against that support (bdg_extract_rescue_resolve) and rescued_path gets
+ * "#read_id\trescued_barcode\tdist\tsupport\tstrand\tpolyT_start\toffset\tUMI\tstatus" and one row per read of status rescued,
+ * ambiguous or truncated, in input order (barcode and UMI '*', strand '.' for a read that is not rescued).  Only with this bit
+ * does the library read rescue_max_ed, rescue_min_support and rescued_path or write the four bdg_stage1_result.rescue_* counts.
+ * Every other output is the same bytes as without the bit. */
+#define BDG_STAGE1_WL_RESCUE     0x2000u
 typedef struct bdg_stage1_opts {
     uint32_t umi_len;             /* 10 (tenX_v2) or 12 (tenX_v3) */
     uint32_t threads;             /* reader threads (bdg_ingest_opts.threads) */
@@ -533,6 +619,10 @@ typedef struct bdg_stage1_opts {
     const uint32_t* tag_mol_reads;    /* NULL only with tag_molecule NULL */
     const uint8_t*  tag_keep;         /* may be NULL */
     uint64_t tag_reads;
+    /* read only with BDG_STAGE1_WL_RESCUE */
+    uint32_t rescue_max_ed;       /* 0 .. BDG_RESCUE_MAX_ED_MAX (BDG_RESCUE_MAX_ED_DEFAULT) */
+    uint32_t rescue_min_support;  /* BDG_RESCUE_MIN_SUPPORT_DEFAULT */
+    const char* rescued_path;     /* the file of rescued reads */
 } bdg_stage1_opts;
 typedef struct bdg_stage1_result {
     uint64_t reads, barcodes, polyt, r1;      /* ReadStats: total, barcode detected, polyT detected, R1 detected */
@@ -552,6 +642,8 @@ typedef struct bdg_stage1_result {
     uint64_t tags_no_cell, tags_not_kept;   /* written only with BDG_STAGE1_TAGS: counts[2 .. 3] of bdg_format_trimmed_tags */
     uint64_t trimmed_no_anchor;   /* written only with BDG_STAGE1_TRIM on contexts in BDG_LAYOUT_5P (whatever the other bits: the caller's
                                      struct then reaches to here): reads with BDG_TRIM_NO_ANCHOR */
+    uint64_t rescue_eligible, rescue_rescued, rescue_ambiguous, rescue_truncated;   /* written only with BDG_STAGE1_WL_RESCUE (the
+                                     caller's struct then reaches to here): eligible reads, and the rows of each status */
 } bdg_stage1_result;
 int  bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, const char* out_path, const char* header,
                     const bdg_stage1_opts* opts, bdg_stage1_result* res);
