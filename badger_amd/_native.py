@@ -587,6 +587,14 @@ class Context:
             self._check(self.lib.bdg_kept_records_to_host(self.h, out.ctypes.data, n))
         return out
 
+    def kept_umis_to_host(self):
+        """the kept UMI codes as a numpy array (synchronises)"""
+        ptr, n = self.kept_umis()
+        out = np.zeros(n, dtype=np.uint32)
+        if n:
+            self._check(self.lib.bdg_mem_to_host(self.h, out.ctypes.data, ptr, out.nbytes))
+        return out
+
     def extract_status(self):
         bad, nwin = C.c_uint64(), C.c_uint64()
         rc = self.lib.bdg_extract_status(self.h, C.byref(bad), C.byref(nwin))

@@ -25,13 +25,16 @@ import argparse
 import logging
 import os
 import sys
+import threading
+import time
+from contextlib import nullcontext
 from io import StringIO
 from traceback import print_exc
 
 from . import _native
-from .barcode_graph import BarcodeGraph
-from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_5p_mode,
-                                   is_native_input, trim_5p_values)
+from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
+from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
+                                   trim_5p_values)
 
 logger = logging.getLogger("BarcodeGraph")
 
@@ -174,8 +177,54 @@ def load_true_barcodes(path):
     return set(vals)
 
 
+def from_stage1_tsv(args, ctx, bc_len, mark):
+    """a stage-1 TSV: its observed barcodes go to the device as records (bdg_keep_observed), the UMI codes beside them; from there
+    on the route is that of read input.  -> (read ids, nothing for a second pass)"""
+    if args.umi_dedup:
+        read_ids, obs_rank, usable, umis = _native.import_stage1_tsv_umis(args.reads, bc_len)
+    else:
+        read_ids, obs_rank, usable = _native.import_stage1_tsv(args.reads, bc_len)      # (import_tsv above, natively)
+    logger.info("Imported barcodes from file")
+    logger.info("Initializing Graph")
+    ctx.keep_observed(obs_rank, usable)
+    if args.umi_dedup:
+        ctx.keep_observed_umis(umis)
+    mark("import")
+    return read_ids, None
+
+
+def from_reads(args, ctx, bc_len, mark):
+    """FASTA / FASTQ / SAM / BAM: the records of every chunk stay on the device (stage 1 -> stage 2 hand-off without host strings),
+    the host only gets the read ids.  Like the reference (:112-117) one thread keeps every SAM / BAM record, several skip secondary /
+    supplementary ones.  -> (read ids, the detector whose layout and UMI length the second pass takes again)"""
+    detector = BARCODE_CALLING_MODES[args.data_type](device=args.device)
+    # --tagged_reads with molecules: every chunk is trimmed (and searched for chimeras) here too, and only its reads' cDNA
+    # lengths stay, for the election of each molecule's read; the bases come back in the second pass
+    trimming = (context_trimming(ctx, args.tso_min_score, args.chimera_max_ed, keep_cdna=True)
+                if args.tagged_reads and args.umi_dedup else nullcontext())
+    read_ids = _native.IdStore()
+    with contexts_in_layout([detector], args.tso5_max_ed), trimming:
+        logger.info("Extracting from " + args.reads)
+        # (-tr 1 is one sequential reader, compressed input as one gzip stream - the reference's single-thread shape,
+        # as extract_raw_barcodes.process_single_thread asks for it)
+        _native.stage1_collect(ctx, args.reads, detector.UMI_LEN_10X, read_ids, threads=args.threads, skip_secondary=args.threads != 1)
+    mark("extract")
+    logger.info("Finished barcode extraction")
+    logger.info("Initializing Graph")
+    return read_ids, detector
+
+
+def write_tagged_reads(args, detector, tags):
+    """the second pass: the same reader threads and the same skip_secondary as the first, so the same reads in the same order"""
+    with contexts_in_layout([detector], args.tso5_max_ed) as ctxs:
+        res = _native.stage1_run(ctxs, args.reads, None, "", detector.UMI_LEN_10X, threads=args.threads,
+                                 skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads, tso_min_score=args.tso_min_score,
+                                 chimera_max_ed=args.chimera_max_ed, tags=tags, tso5_max_ed=args.tso5_max_ed)
+    logger.info("Tagged reads: %d to %s, %d bases; left out: %d without a cell, %d not their molecule's read"
+                % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))
+
+
 def main(args):
-    import time
     t_marks = [("start", time.perf_counter())]
 
     def mark(name):
@@ -191,9 +240,8 @@ def main(args):
     if args.stats or args.ground_truth is not None:
         logger.error("--stats / --ground_truth run the reference's offline evaluation module, which this build does not carry")
         sys.exit(-4)
-    # the device context comes up (0.15 - 0.3 s of runtime start) while this thread reads the barcode lists
-    import threading
-    def _warm():
+
+    def _warm():                                  # the device context comes up (0.15 - 0.3 s) while this thread reads the barcode lists
         try:
             _native.default_context(args.device)
         except Exception:
@@ -206,103 +254,42 @@ def main(args):
         from .common import BarcodeRanks
         barcode_list = BarcodeRanks.from_file(args.barcode_list, bc_len)      # (the reference keeps a set of the lines, :82-88)
 
-    from .stage2 import Stage2, observed_from_strings
+    from .stage2 import Stage2
     warm.join()
-    st2 = Stage2(args.threshold, device=args.device)
     if args.reads.endswith("tsv"):
-        if args.umi_dedup:
-            read_ids, obs_rank, usable, umis = _native.import_stage1_tsv_umis(args.reads, bc_len)
-        else:
-            read_ids, obs_rank, usable = _native.import_stage1_tsv(args.reads, bc_len)      # (import_tsv below, natively)
-        logger.info("Imported barcodes from file")
-        logger.info("Initializing Graph")
-        # the observed barcodes go to the device as records (bdg_keep_observed): from here on the TSV route is the route of
-        # read input - counting, edges, clustering and the per-read assignment run there
-        ctx = _native.default_context(args.device)
-        ctx.keep_observed(obs_rank, usable)
-        if args.umi_dedup:
-            ctx.keep_observed_umis(umis)                  # (the UMI codes beside the records)
-        mark("import")
-        st2.count_device(ctx)
-        mark("count")
-        st2.build_edges(ctx, on_device=True, gpus=edge_build_gpus(args))
-        from_device = ctx
+        route = from_stage1_tsv
     elif is_native_input(args.reads):
-        # FASTA / FASTQ / SAM / BAM: the records of every chunk stay on the device (stage 1 -> stage 2 hand-off without host
-        # strings): counting and the edge build run there, the host only gets the per-read ranks for the output file.
-        # Like the reference (:112-117) one thread keeps every SAM / BAM record, several skip secondary / supplementary ones.
-        ctx = _native.default_context(args.device)
-        umi_len = BARCODE_CALLING_MODES[args.data_type](device=args.device).UMI_LEN_10X
-        layout = _native.LAYOUT_5P if is_5p_mode(args.data_type) else _native.LAYOUT_3P
-        if layout == _native.LAYOUT_5P:
-            ctx.trim_set_5p(umi_len, args.tso5_max_ed)
-        ctx.extract_set_layout(layout)                    # (for this pass; the context is shared and goes back to the 3' layout below)
-        ctx.extract_keep_records(True)
-        ctx.extract_keep_umis(args.umi_dedup)             # (every chunk's UMIs packed beside its records)
-        # --tagged_reads with molecules: every chunk is trimmed (and searched for chimeras) here too, and only its reads' cDNA
-        # lengths stay, for the election of each molecule's read; the bases come back in the second pass
-        keep_cdna = bool(args.tagged_reads and args.umi_dedup)
-        if keep_cdna:
-            ctx.extract_set_trim(True, args.tso_min_score)
-            if args.chimera_cut:
-                ctx.extract_set_chimera(True, args.chimera_max_ed)
-            ctx.extract_keep_cdna(True)
-        logger.info("Extracting from " + args.reads)
-        read_ids = _native.IdStore()
-        try:
-            # (-tr 1 is one sequential reader, compressed input as one gzip stream - the reference's single-thread shape,
-            # as extract_raw_barcodes.process_single_thread asks for it)
-            _native.stage1_collect(ctx, args.reads, umi_len, read_ids, threads=args.threads,
-                                   skip_secondary=args.threads != 1)
-        except BaseException:
-            ctx.extract_set_layout(_native.LAYOUT_3P)
-            ctx.extract_set_trim(False)
-            ctx.extract_keep_umis(False)
-            ctx.extract_keep_records(False)
-            raise
-        ctx.extract_set_layout(_native.LAYOUT_3P)
-        if keep_cdna:
-            ctx.extract_set_trim(False)                   # (what was kept stays until the records go)
-        mark("extract")
-        logger.info("Finished barcode extraction")
-        logger.info("Initializing Graph")
-        st2.count_device(ctx)
-        mark("count")
-        st2.build_edges(ctx, on_device=True, gpus=edge_build_gpus(args))
-        from_device = ctx
+        route = from_reads
     else:
         logger.error("Unknown file format " + args.reads)
         sys.exit(-1)
-    mark("reads_and_graph")
-    logger.info("Graph construction done")
-    st2.cluster(true_barcodes, barcode_list, args.n_cells, bc_len, args.interval)
-    mark("cluster")
-    logger.info("Clustering done")
-    st2.output_file_from_device(read_ids, from_device, args.output, args.high_sens, keep_reads=args.umi_dedup)
-    if args.umi_dedup:
-        from .umi_dedup import UMI_LEN
-        molecules = st2.umi_dedup_from_device(read_ids, args.output, UMI_LEN[args.data_type], args.umi_dist,
-                                              keep_molecules=bool(args.tagged_reads))
-        mark("umi_dedup")
-        logger.info("Molecules: %d" % molecules)
-        from_device.extract_keep_umis(False)
-    tags = st2.read_tags_from_device(args.molecule_reads) if args.tagged_reads else None
-    from_device.extract_keep_records(False)
-    if args.tagged_reads:
-        # the second pass: the same reader threads and the same skip_secondary as the first, so the same reads in the same order
-        from_device.extract_set_layout(layout)
-        try:
-            res = _native.stage1_run([from_device], args.reads, None, "", umi_len, threads=args.threads,
-                                     skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads,
-                                     tso_min_score=args.tso_min_score, chimera_max_ed=args.chimera_max_ed, tags=tags,
-                                     tso5_max_ed=args.tso5_max_ed)
-        finally:
-            from_device.extract_set_layout(_native.LAYOUT_3P)
-        mark("tagged_reads")
-        logger.info("Tagged reads: %d to %s, %d bases; left out: %d without a cell, %d not their molecule's read"
-                    % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))
-    disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
-    st2.release_device()
+    st2 = Stage2(args.threshold, device=args.device)
+    ctx = _native.default_context(args.device)      # shared inside the process: whatever happens below, it is left as it was found
+    try:
+        # both routes leave the reads' records on the device: counting, edges, clustering and the per-read assignment run there
+        with context_keeping(ctx, umis=args.umi_dedup):
+            read_ids, detector = route(args, ctx, bc_len, mark)
+            st2.count_device(ctx)
+            mark("count")
+            st2.build_edges(ctx, gpus=edge_build_gpus(args))
+            mark("reads_and_graph")
+            logger.info("Graph construction done")
+            st2.cluster(true_barcodes, barcode_list, args.n_cells, bc_len, args.interval)
+            mark("cluster")
+            logger.info("Clustering done")
+            st2.output_file_from_device(read_ids, ctx, args.output, args.high_sens)
+            if args.umi_dedup:
+                from .umi_dedup import UMI_LEN
+                molecules = st2.umi_dedup_from_device(read_ids, args.output, UMI_LEN[args.data_type], args.umi_dist)
+                mark("umi_dedup")
+                logger.info("Molecules: %d" % molecules)
+            tags = st2.read_tags_from_device(args.molecule_reads) if args.tagged_reads else None
+        if args.tagged_reads:
+            write_tagged_reads(args, detector, tags)
+            mark("tagged_reads")
+        disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
+    finally:
+        st2.release_device()
     mark("output")
     print(disconnected)                # "disconnected" count (reference :131-132)
     timing = os.environ.get("BADGER_AMD_STAGE2_TIMING")

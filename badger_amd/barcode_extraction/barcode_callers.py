@@ -246,14 +246,47 @@ class TenX5pBarcodeExtractorV3(TenXBarcodeExtractorV3):
 
 
 @contextmanager
-def contexts_in_layout(detectors):
+def contexts_in_layout(detectors, tso5_max_ed=None):
     """the detectors' contexts, each in its detector's layout for the time of the block (the contexts are shared: they are left in
-    LAYOUT_3P, as they were found)"""
+    LAYOUT_3P, as they were found).  tso5_max_ed (5' modes): with it the 5' trimming rule gets the detector's UMI length and that
+    edit bound (trim_set_5p) for the block, and a fresh context's values behind it"""
     ctxs = [d._ctx() for d in detectors]
     try:
         for d, c in zip(detectors, ctxs):
+            if tso5_max_ed is not None:
+                c.trim_set_5p(d.UMI_LEN_10X, tso5_max_ed)
             c.extract_set_layout(d.LAYOUT)
         yield ctxs
     finally:
         for c in ctxs:
             c.extract_set_layout(_native.LAYOUT_3P)
+            if tso5_max_ed is not None:
+                c.trim_set_5p(10, _native.TSO5_MAX_ED_DEFAULT)
+
+
+@contextmanager
+def context_keeping(ctx, umis=False):
+    """for the time of the block the context keeps every collected chunk's records on the device, with umis the packed UMIs beside
+    them (stage 2 reads both there); behind it the context keeps nothing, and everything kept - cDNA lengths too - is freed"""
+    try:
+        ctx.extract_keep_records(True)
+        ctx.extract_keep_umis(umis)
+        yield
+    finally:
+        ctx.extract_keep_umis(False)
+        ctx.extract_keep_records(False)
+
+
+@contextmanager
+def context_trimming(ctx, tso_min_score, chimera_max_ed=None, keep_cdna=False):
+    """for the time of the block every chunk the context extracts is trimmed too, with chimera_max_ed searched for internal
+    adapters, with keep_cdna its reads' cDNA lengths kept beside the records (they stay until the records go)"""
+    try:
+        ctx.extract_set_trim(True, tso_min_score)
+        if chimera_max_ed is not None:
+            ctx.extract_set_chimera(True, chimera_max_ed)
+        if keep_cdna:
+            ctx.extract_keep_cdna(True)
+        yield
+    finally:
+        ctx.extract_set_trim(False)                       # (the chimera search and the keeping of lengths go off with the trim)

@@ -14,6 +14,7 @@ level 2 "unclustered barcodes adjacent to level-1 members of exactly one centre"
 module against the dictionary mirror on random graphs, tests/test_cli_gpu.py against the reference's own output files.
 """
 import logging
+from collections import namedtuple
 from statistics import mean
 
 import numpy as np
@@ -75,6 +76,18 @@ def graph_contexts(gpus, first):
     return [first] + [_native.default_context(d) for d in others]
 
 
+class EdgeRows(namedtuple("EdgeRows", "ctx rows m")):
+    """the m edges on a device as positions in the distinct barcodes: `rows` is a (2, max(m, 1)) array, one row per end"""
+    a_ptr = property(lambda self: self.rows.data_ptr())
+    b_ptr = property(lambda self: self.rows.data_ptr() + 4 * max(self.m, 1))
+
+
+# per read: the cell it was given (on the device and on the host); `assigned`, `has`: per distinct barcode, what they came from
+ReadCells = namedtuple("ReadCells", "ctx d_rank d_got rank got assigned has")
+# per read: its molecule inside its cell (on the device and on the host), over the nc cells a read can be assigned to
+Molecules = namedtuple("Molecules", "d_cells nc d_mol mol")
+
+
 class Stage2:
     def __init__(self, threshold, device=0):
         self.threshold = threshold
@@ -85,19 +98,43 @@ class Stage2:
         self._ea = self._eb = np.zeros(0, np.uint32)  # edges as indices into uniq (on the host only if something asks for them)
         self.owner = np.zeros(0, np.int64)       # per distinct barcode: index of its centre, -1 conflict, -2 unclustered
         self.centers = []
+        self.edge_shares = []                    # (for logs and tests: how a --gpus N build cut the edge list)
+        self._place = None                       # count_host: (obs_rank, usable, every usable read's place in uniq)
+        # what lives on the device, each from the step that makes it until release_device(): every array in _owned
+        self._owned = []
+        self._d_uniq = None                      # uniq (count_device, or build_edges after count_host)
+        self._edges = None                       # EdgeRows (build_edges)
+        self._cells = None                       # ReadCells (output_file_from_device)
+        self._mol = None                         # Molecules (umi_dedup_from_device)
 
     def _ctx(self):
         return _native.default_context(self.device)
 
-    # the edges as positions in uniq.  After build_edges() they live on the device (self._dev); the host copy is made when
+    def _own(self, d):
+        self._owned.append(d)
+        return d
+
+    def _alloc(self, ctx, shape, dtype):
+        return self._own(_native.DeviceArray(ctx, shape, dtype))
+
+    def _upload(self, ctx, arr):
+        return self._own(_native.DeviceArray.from_host(ctx, arr))
+
+    def release_device(self):
+        """every device array this object made goes back, whichever step was reached; what is on the host stays"""
+        for d in self._owned:
+            d.free()
+        self._owned = []
+        self._d_uniq = self._edges = self._cells = self._mol = None
+
+    # the edges as positions in uniq.  After build_edges() they live on the device (self._edges); the host copy is made when
     # something reads it (the numpy clustering, tests) - the command line never does.
     def _edges_to_host(self):
-        dev = getattr(self, "_dev", None)
         if self._ea is None:
-            if dev is None:
+            if self._edges is None:
                 raise RuntimeError("the edges went back with the device buffers (release_device) before anything read them")
-            rows = dev["rows"].to_host()
-            self._ea, self._eb = rows[0, :dev["m"]], rows[1, :dev["m"]]
+            rows = self._edges.rows.to_host()
+            self._ea, self._eb = rows[0, :self._edges.m], rows[1, :self._edges.m]
 
     @property
     def ea(self):
@@ -122,6 +159,7 @@ class Stage2:
         """distinct barcodes of the usable reads, in read order (counts in first-occurrence order = argsort(first)).
         One sort of (rank << 32 | position) gives the distinct ranks, their first positions, their counts and - kept for
         per_read() - every usable read's place among the distinct ones."""
+        self.release_device()                                 # (what an earlier count left there is of other barcodes)
         r = obs_rank[usable]
         n = len(r)
         if n == 0 or n >= 1 << 32:
@@ -146,13 +184,12 @@ class Stage2:
 
     def count_device(self, ctx):
         """the same from the extraction records the context kept on the device (bdg_distinct_dev)"""
+        self.release_device()
         ptr, n = ctx.kept_records()
         m = max(n, 1)
         # device arrays through the library's own allocator (bdg_mem_alloc): the command line runs without torch
-        uniq = _native.DeviceArray(ctx, m, np.uint32)
-        cnt = _native.DeviceArray(ctx, m, np.uint32)
-        first = _native.DeviceArray(ctx, m, np.uint32)
-        dn = _native.DeviceArray(ctx, 2, np.uint32)
+        uniq, cnt, first = (self._alloc(ctx, m, np.uint32) for _ in range(3))
+        dn = self._alloc(ctx, 2, np.uint32)
         if n:
             ctx.distinct_dev(ptr, n, uniq, cnt, first, dn)
         nu, nbad = (int(x) for x in dn.to_host())
@@ -161,11 +198,14 @@ class Stage2:
         self.uniq = uniq.to_host(nu)
         self.count = cnt.to_host(nu).astype(np.int64)
         self.first = first.to_host(nu).astype(np.int64)
-        self._d_uniq = uniq                                    # stays on the device for the edge build
+        self._place = None
+        self._d_uniq = uniq                                    # stays on the device for the edge build and the assignment
+        for d in (cnt, first, dn):
+            d.free()
         return nu
 
     # ------------------------------------------------------------------ graph
-    def build_edges(self, ctx=None, on_device=False, gpus=1):
+    def build_edges(self, ctx=None, gpus=1):
         """edges as pairs of positions in uniq.  The distinct barcodes are on the device already after count_device();
         after count_host() they are sent there.  Either way the edge list is built there (bdg_graph_edges_dev), its ranks
         are turned into positions there (bdg_rows_of_dev) and only the positions come back.
@@ -174,73 +214,67 @@ class Stage2:
         union is the list, cut by the library), the shares' positions are put side by side on the first device, where the
         clustering runs.  No exchange between the devices."""
         nu = len(self.uniq)
-        T = qgram_threshold(self.threshold, 16)
         if nu < 2:
             self._ea = self._eb = np.zeros(0, np.uint32)
             return
         ctx = ctx or self._ctx()
-        d_uniq = self._d_uniq if on_device else _native.DeviceArray.from_host(ctx, self.uniq)
+        if self._d_uniq is None:
+            self._d_uniq = self._upload(ctx, self.uniq)
         if gpus > 1:
-            return self._build_edges_parts(ctx, d_uniq, nu, T, gpus)
-        cap = max(1024, 8 * nu)
-        while True:
-            d_edges = _native.DeviceArray(ctx, (cap, 3), np.uint32)
-            d_tot = _native.DeviceArray(ctx, 1, np.uint64)
-            ctx.graph_edges_dev(d_uniq, nu, self.threshold, T, d_edges, cap, d_tot)
-            tot = int(d_tot.to_host()[0])
-            ctx.graph_status()
-            if tot <= cap:
-                break
-            cap = tot
-            d_edges.free()
-        d_rows = _native.DeviceArray(ctx, (2, max(tot, 1)), np.uint32)
-        ctx.rows_of_dev(d_uniq, nu, d_edges, tot, 3, d_rows.data_ptr(), 0)
-        ctx.rows_of_dev(d_uniq, nu, d_edges, tot, 3, d_rows.data_ptr() + 4 * max(tot, 1), 1)
-        for d in (d_edges, d_tot):
-            d.free()
+            self._build_edges_parts(ctx, gpus)
+        else:
+            self._edges = self._edge_rows(ctx, self._d_uniq, max(1024, 8 * nu))
         # the positions and the distinct barcodes stay on the device: the clustering levels, the count badger.py prints and the
         # per-read assignment run there (50 M edges are 400 MB that the host would only hold)
         self._ea = self._eb = None
-        self._dev = {"ctx": ctx, "rows": d_rows, "m": tot, "uniq": d_uniq}
 
-    def _build_edges_parts(self, ctx, d_uniq, nu, T, gpus):
+    def _launch_edges(self, ctx, d_uniq, cap, part=0, nparts=1):
+        """room for cap edges and share `part` of `nparts` of the edge list queued into it on ctx -> (edges, their total)"""
+        nu, T = len(self.uniq), qgram_threshold(self.threshold, 16)
+        d_edges, d_tot = self._alloc(ctx, (cap, 3), np.uint32), self._alloc(ctx, 1, np.uint64)
+        if nparts == 1:
+            ctx.graph_edges_dev(d_uniq, nu, self.threshold, T, d_edges, cap, d_tot)
+        else:
+            ctx.graph_edges_part_dev(d_uniq, nu, part, nparts, self.threshold, T, d_edges, cap, d_tot)
+        return d_edges, d_tot
+
+    def _edge_rows(self, ctx, d_uniq, cap, part=0, nparts=1, launched=None):
+        """share `part` of `nparts` of the edge list over d_uniq as EdgeRows on ctx: `launched` (or a launch made here) waited
+        for, once more with room if the share is larger than cap, then the ranks of both ends turned into positions"""
+        while True:
+            d_edges, d_tot = launched or self._launch_edges(ctx, d_uniq, cap, part, nparts)
+            tot = int(d_tot.to_host()[0])
+            ctx.graph_status()
+            d_tot.free()
+            if tot <= cap:
+                break
+            d_edges.free()
+            cap, launched = tot, None
+        er = EdgeRows(ctx, self._alloc(ctx, (2, max(tot, 1)), np.uint32), tot)
+        ctx.rows_of_dev(d_uniq, len(self.uniq), d_edges, tot, 3, er.a_ptr, 0)
+        ctx.rows_of_dev(d_uniq, len(self.uniq), d_edges, tot, 3, er.b_ptr, 1)
+        d_edges.free()
+        return er
+
+    def _build_edges_parts(self, ctx, gpus):
         ctxs = [ctx] + [c for c in graph_contexts(gpus, ctx) if c is not ctx][:gpus - 1]
         n = len(ctxs)
-        cap = max(1024, 8 * nu // n + 4096)
+        cap = max(1024, 8 * len(self.uniq) // n + 4096)
         work = []
         for g, c in enumerate(ctxs):                         # every device starts on its share before anybody waits
-            du = d_uniq if c is ctx else _native.DeviceArray.from_host(c, self.uniq)
-            d_edges = _native.DeviceArray(c, (cap, 3), np.uint32)
-            d_tot = _native.DeviceArray(c, 1, np.uint64)
-            c.graph_edges_part_dev(du, nu, g, n, self.threshold, T, d_edges, cap, d_tot)
-            work.append([c, du, d_edges, d_tot, cap])
+            du = self._d_uniq if c is ctx else self._upload(c, self.uniq)
+            work.append((c, du, self._launch_edges(c, du, cap, g, n)))
         shares = []
-        for g, w in enumerate(work):
-            c, du, d_edges, d_tot, cp = w
-            tot = int(d_tot.to_host()[0])
-            c.graph_status()
-            while tot > cp:                                      # (a share larger than its room: once more with room)
-                d_edges.free()
-                cp = tot
-                d_edges = _native.DeviceArray(c, (cp, 3), np.uint32)
-                c.graph_edges_part_dev(du, nu, g, n, self.threshold, T, d_edges, cp, d_tot)
-                tot = int(d_tot.to_host()[0])
-                c.graph_status()
-            d_rows = _native.DeviceArray(c, (2, max(tot, 1)), np.uint32)
-            c.rows_of_dev(du, nu, d_edges, tot, 3, d_rows.data_ptr(), 0)
-            c.rows_of_dev(du, nu, d_edges, tot, 3, d_rows.data_ptr() + 4 * max(tot, 1), 1)
-            rows = d_rows.to_host()
-            shares.append((rows[0, :tot], rows[1, :tot]))
-            for d in (d_edges, d_tot, d_rows) + (() if c is ctx else (du,)):
-                d.free()
-        tot = sum(len(a) for a, _ in shares)
-        both = np.zeros((2, max(tot, 1)), np.uint32)
-        if tot:
-            both[0, :tot] = np.concatenate([a for a, _ in shares])
-            both[1, :tot] = np.concatenate([b for _, b in shares])
-        self._ea = self._eb = None
-        self._dev = {"ctx": ctx, "rows": _native.DeviceArray.from_host(ctx, both), "m": tot, "uniq": d_uniq}
-        self.edge_shares = [len(a) for a, _ in shares]          # (for logs and tests: how the list was cut)
+        for g, (c, du, launched) in enumerate(work):
+            er = self._edge_rows(c, du, cap, g, n, launched)
+            shares.append(er.rows.to_host()[:, :er.m])
+            er.rows.free()
+            if c is not ctx:
+                du.free()
+        self.edge_shares = [s.shape[1] for s in shares]
+        tot = sum(self.edge_shares)
+        both = np.concatenate(shares, axis=1) if tot else np.zeros((2, 1), np.uint32)
+        self._edges = EdgeRows(ctx, self._upload(ctx, both), tot)
 
     # ------------------------------------------------------------------ centres
     def get_cluster_centers(self, true_barcodes, bc_len, barcode_list, n_cells, interval):
@@ -299,16 +333,13 @@ class Stage2:
         present = ((pos < nu) & (self.uniq[np.minimum(pos, nu - 1)] == cr)) if nu else np.zeros(len(cr), bool)
         cidx = pos[present]                                               # centres that were observed (the others have no edges)
         owner[cidx] = cidx
-        dev = getattr(self, "_dev", None)
-        if dev is not None and self._ea is None:
+        e = self._edges
+        if e is not None and self._ea is None:
             # the edges are on the device: both levels there (bdg_cluster_dev), the same rule as the array code below
             print(1)
             print(2)                                                      # the reference prints the level numbers (:289)
-            ctx = dev["ctx"]
-            own32 = owner.astype(np.int32)
-            d_owner = _native.DeviceArray.from_host(ctx, own32)
-            m = dev["m"]
-            ctx.cluster_dev(dev["rows"].data_ptr(), dev["rows"].data_ptr() + 4 * max(m, 1), m, nu, d_owner)
+            d_owner = self._upload(e.ctx, owner.astype(np.int32))
+            e.ctx.cluster_dev(e.a_ptr, e.b_ptr, e.m, nu, d_owner)
             self.owner = d_owner.to_host(nu).astype(np.int64) if nu else owner
             d_owner.free()
             return
@@ -347,16 +378,13 @@ class Stage2:
         cr = np.unique(np.array(self.centers, dtype=np.uint32))                # a dict key exists once however often it is looked up
         pos = np.searchsorted(self.uniq, cr)
         present = ((pos < nu) & (self.uniq[np.minimum(pos, nu - 1)] == cr)) if nu else np.zeros(len(cr), bool)
-        dev = getattr(self, "_dev", None)
-        if dev is not None and self._ea is None:
+        e = self._edges
+        if e is not None and self._ea is None:
             # the edges are on the device: counted there (bdg_touched_count_dev)
-            ctx, m = dev["ctx"], dev["m"]
             cidx = np.ascontiguousarray(pos[present], dtype=np.uint32)
-            d_c = _native.DeviceArray.from_host(ctx, cidx) if len(cidx) else None
-            touched = ctx.touched_count_dev(dev["rows"].data_ptr(), dev["rows"].data_ptr() + 4 * max(m, 1), m, nu,
-                                            d_c.data_ptr() if d_c is not None else 0, len(cidx))
-            if d_c is not None:
-                d_c.free()
+            d_c = self._upload(e.ctx, cidx)
+            touched = e.ctx.touched_count_dev(e.a_ptr, e.b_ptr, e.m, nu, d_c, len(cidx))
+            d_c.free()
             return nu - (touched + int((~present).sum()))
         key = np.zeros(nu, bool)
         key[self.ea] = True
@@ -394,7 +422,7 @@ class Stage2:
         n = len(obs_rank)
         rank, got = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
         if usable.any():
-            kept = getattr(self, "_place", None)
+            kept = self._place
             if kept is not None and kept[0] is obs_rank and kept[1] is usable:
                 pos = kept[2]                                 # (count_host saw these very arrays)
             else:
@@ -410,53 +438,40 @@ class Stage2:
         ids = read_ids if isinstance(read_ids, _native.IdStore) else _native.IdStore(read_ids)
         _native.write_assignments(ids, rank, got, out + "_output_file.tsv")
 
-    def output_file_from_device(self, ids, ctx, out, high_sens, keep_reads=False):
-        """the same straight from the extraction records the context kept: per read, the position of its barcode among the
-        distinct ones and what that was corrected to, on the device (bdg_assign_reads_dev); the host only writes the file.
-        keep_reads: the per-read cells stay on the device for umi_dedup_from_device."""
+    def output_file_from_device(self, ids, ctx, out, high_sens):
+        """the same straight from the extraction records the context kept (after count_device(ctx)): per read, the position of
+        its barcode among the distinct ones and what that was corrected to, on the device (bdg_assign_reads_dev); the host only writes the file.
+        The per-read cells stay, on the device for umi_dedup_from_device and on the host for read_tags_from_device."""
         assigned, has = self.assigned(high_sens)
         ptr, n = ctx.kept_records()
-        dev = self._dev
-        d_assigned = _native.DeviceArray.from_host(ctx, assigned)
-        d_has = _native.DeviceArray.from_host(ctx, has.astype(np.uint8))
-        d_rank = _native.DeviceArray(ctx, max(n, 1), np.uint32)
-        d_got = _native.DeviceArray(ctx, max(n, 1), np.uint8)
+        d_assigned, d_has = self._upload(ctx, assigned), self._upload(ctx, has.astype(np.uint8))
+        d_rank, d_got = self._alloc(ctx, max(n, 1), np.uint32), self._alloc(ctx, max(n, 1), np.uint8)
         if n:
-            ctx.assign_reads_dev(ptr, n, dev["uniq"], len(self.uniq), d_assigned, d_has, d_rank, d_got)
-        rank, got = d_rank.to_host(n), d_got.to_host(n)
-        for d in (d_assigned, d_has) + (() if keep_reads else (d_rank, d_got)):
+            ctx.assign_reads_dev(ptr, n, self._d_uniq, len(self.uniq), d_assigned, d_has, d_rank, d_got)
+        self._cells = ReadCells(ctx, d_rank, d_got, d_rank.to_host(n), d_got.to_host(n), assigned, has)
+        for d in (d_assigned, d_has):
             d.free()
-        self._read_cells = (rank, got)                                # (for read_tags_from_device)
-        if keep_reads:
-            self._reads = {"ctx": ctx, "d_rank": d_rank, "d_got": d_got, "rank": rank, "got": got,
-                           "cells": np.unique(assigned[has])}        # every barcode a read can be assigned to, ascending ranks
-        _native.write_assignments(ids, rank, got, out + "_output_file.tsv")
+        _native.write_assignments(ids, self._cells.rank, self._cells.got, out + "_output_file.tsv")
 
-    def umi_dedup_from_device(self, ids, out, umi_len, umi_dist, keep_molecules=False):
+    def umi_dedup_from_device(self, ids, out, umi_len, umi_dist):
         """--umi_dedup: the reads' molecules inside their cells (bdg_umi_dedup_dev over the cells output_file_from_device left
         on the device and the UMI codes the context kept), <out>_molecules.tsv written natively, <out>_cells.tsv (one line per
-        cell with a read, ascending barcode).  Returns the number of molecules.  keep_molecules: the cells and molecules stay on
-        the device for read_tags_from_device."""
-        r, self._reads = self._reads, None
-        ctx, cells = r["ctx"], np.ascontiguousarray(r["cells"], dtype=np.uint32)
+        cell with a read, ascending barcode).  Returns the number of molecules.  The cells and molecules stay on the device for
+        read_tags_from_device."""
+        r = self._cells
+        ctx, cells = r.ctx, np.unique(r.assigned[r.has])     # every barcode a read can be assigned to, ascending ranks
         ptr, n = ctx.kept_umis()
-        if n != len(r["rank"]):
-            raise RuntimeError("%d UMI codes kept for %d reads" % (n, len(r["rank"])))
+        if n != len(r.rank):
+            raise RuntimeError("%d UMI codes kept for %d reads" % (n, len(r.rank)))
         nc = len(cells)
-        d_cells = _native.DeviceArray.from_host(ctx, cells)
-        d_mol = _native.DeviceArray(ctx, max(n, 1), np.uint32)
-        d_cnt = _native.DeviceArray(ctx, (max(nc, 1), 4), np.uint32)
-        ctx.umi_dedup_dev(r["d_rank"], r["d_got"], ptr, n, d_cells, nc, umi_len, umi_dist, d_mol, d_cnt)
-        mol, cnt = d_mol.to_host(n), d_cnt.to_host(nc)
-        umi = np.zeros(n, np.uint32)
-        if n:
-            ctx._check(ctx.lib.bdg_mem_to_host(ctx.h, umi.ctypes.data, ptr, umi.nbytes))
-        if keep_molecules:
-            self._molecules = {"ctx": ctx, "d_rank": r["d_rank"], "d_got": r["d_got"], "d_cells": d_cells, "nc": nc, "d_mol": d_mol,
-                               "mol": mol, "n": n}
-        for d in (d_cnt,) + (() if keep_molecules else (d_cells, d_mol, r["d_rank"], r["d_got"])):
-            d.free()
-        _native.write_molecules(ids, r["rank"], r["got"], umi, mol, out + "_molecules.tsv")
+        d_cells = self._upload(ctx, cells)
+        d_mol = self._alloc(ctx, max(n, 1), np.uint32)
+        d_cnt = self._alloc(ctx, (max(nc, 1), 4), np.uint32)
+        ctx.umi_dedup_dev(r.d_rank, r.d_got, ptr, n, d_cells, nc, umi_len, umi_dist, d_mol, d_cnt)
+        self._mol = Molecules(d_cells, nc, d_mol, d_mol.to_host(n))
+        cnt = d_cnt.to_host(nc)
+        d_cnt.free()
+        _native.write_molecules(ids, r.rank, r.got, ctx.kept_umis_to_host(), self._mol.mol, out + "_molecules.tsv")
         seen = np.flatnonzero(cnt[:, 0] > 0) if nc else np.zeros(0, np.intp)
         names = unrank_many(cells[seen])
         with open(out + "_cells.tsv", "w") as f:
@@ -467,31 +482,21 @@ class Stage2:
 
     def read_tags_from_device(self, molecule_reads=False):
         """--tagged_reads: the per-read arrays of the second pass (_native.stage1_run's tags): every read's cell from
-        output_file_from_device and - after umi_dedup_from_device(keep_molecules=True) - its molecule and the molecule's read
-        count; each molecule's read elected on the device from the cDNA lengths the context kept (bdg_molecule_reps_dev), and
-        with molecule_reads the filter that keeps only those."""
-        rank, got = self._read_cells
-        tags = {"cell_rank": rank, "cell_has": got}
-        m, self._molecules = getattr(self, "_molecules", None), None
+        output_file_from_device and - after umi_dedup_from_device - its molecule and the molecule's read count; each molecule's
+        read elected on the device from the cDNA lengths the context kept (bdg_molecule_reps_dev), and with molecule_reads the
+        filter that keeps only those."""
+        r, m = self._cells, self._mol
+        tags = {"cell_rank": r.rank, "cell_has": r.got}
         if m is None:
             return tags
-        ctx, n = m["ctx"], m["n"]
-        ptr, n_len = ctx.kept_cdna()
+        n = len(m.mol)
+        ptr, n_len = r.ctx.kept_cdna()
         if n_len != n:
             raise RuntimeError("%d cDNA lengths kept for %d reads" % (n_len, n))
-        d_rep = _native.DeviceArray(ctx, max(n, 1), np.uint8)
-        d_cnt = _native.DeviceArray(ctx, max(n, 1), np.uint32)
+        d_rep, d_cnt = self._alloc(r.ctx, max(n, 1), np.uint8), self._alloc(r.ctx, max(n, 1), np.uint32)
         if n:
-            ctx.molecule_reps_dev(m["d_rank"], m["d_got"], m["d_mol"], ptr, n, m["d_cells"], m["nc"], d_rep, d_cnt)
-        tags.update(molecule=m["mol"], mol_reads=d_cnt.to_host(n), keep=d_rep.to_host(n) if molecule_reads else None)
-        for d in (d_rep, d_cnt, m["d_rank"], m["d_got"], m["d_mol"], m["d_cells"]):
+            r.ctx.molecule_reps_dev(r.d_rank, r.d_got, m.d_mol, ptr, n, m.d_cells, m.nc, d_rep, d_cnt)
+        tags.update(molecule=m.mol, mol_reads=d_cnt.to_host(n), keep=d_rep.to_host(n) if molecule_reads else None)
+        for d in (d_rep, d_cnt):
             d.free()
         return tags
-
-    def release_device(self):
-        dev = getattr(self, "_dev", None)
-        if dev is not None:
-            dev["rows"].free()
-            if dev["uniq"] is not getattr(self, "_d_uniq", None):
-                dev["uniq"].free()
-            self._dev = None

@@ -10,7 +10,7 @@ import pytest
 
 from badger_amd import badger, synth
 from badger_amd.barcode_graph import BarcodeGraph
-from badger_amd.stage2 import Stage2, observed_from_strings, unrank_many
+from badger_amd.stage2 import EdgeRows, Stage2, observed_from_strings, unrank_many
 from oracle import pyoracle as orc
 
 
@@ -187,7 +187,8 @@ def test_device_clustering_and_assignment_equal_the_array_code(seed, thr, n_cell
     dev.ea = dev.eb = None                                    # (the edges exist on the device only, as after build_edges)
     m = len(ref.ea)
     d_rows = _native.DeviceArray.from_host(ctx, np.stack([ref.ea, ref.eb]).astype(np.uint32) if m else np.zeros((2, 1), np.uint32))
-    dev._dev = {"ctx": ctx, "rows": d_rows, "m": m, "uniq": _native.DeviceArray.from_host(ctx, dev.uniq)}
+    dev._edges = EdgeRows(ctx, dev._own(d_rows), m)
+    dev._d_uniq = dev._upload(ctx, dev.uniq)
     with redirect_stdout(io.StringIO()) as o:
         dev.cluster(None, None, max(4, n_cells // 2), 16, 25)
     assert o.getvalue() == "1\n2\n"
@@ -208,7 +209,7 @@ def test_device_clustering_and_assignment_equal_the_array_code(seed, thr, n_cell
     d_recs = _native.DeviceArray.from_host(ctx, recs.view(np.uint8).reshape(-1, 32))
     d_a, d_h = _native.DeviceArray.from_host(ctx, assigned), _native.DeviceArray.from_host(ctx, has.astype(np.uint8))
     d_r, d_g = _native.DeviceArray(ctx, len(recs), np.uint32), _native.DeviceArray(ctx, len(recs), np.uint8)
-    ctx.assign_reads_dev(d_recs, len(recs), dev._dev["uniq"], len(dev.uniq), d_a, d_h, d_r, d_g)
+    ctx.assign_reads_dev(d_recs, len(recs), dev._d_uniq, len(dev.uniq), d_a, d_h, d_r, d_g)
     got_rank, got_has = d_r.to_host(), d_g.to_host()
     assert (got_has == want_has).all() and (got_rank[want_has == 1] == want_rank[want_has == 1]).all() and want_has.sum() > 1000
     dev.release_device()

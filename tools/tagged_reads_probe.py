@@ -9,7 +9,8 @@
     python tools/tagged_reads_probe.py --cli [--cli_reads 1000000] [--pairs 3] [--parent DIR] --out ...
         the stage-2 command line on a FASTQ file, as alternating pairs of fresh processes: with --tagged_reads (and with
         --chimera_cut --umi_dedup --molecule_reads) against this build without them; and, with --parent DIR (a built checkout
-        of the parent commit), this build with the new flags off against the parent, beside parent against parent.
+        of the parent commit), this build with the new flags off against the parent, beside parent against parent
+        (--parent_flags: the same two pairs also without any flag and with all four).
 """
 import argparse
 import json
@@ -142,6 +143,11 @@ def cli_probe(args):
         parent = os.path.abspath(args.parent)
         pairs("parent", (parent, ["--umi_dedup"]), "flags_off", (ROOT, ["--umi_dedup"]), "stage2 CLI from FASTQ, --umi_dedup: this build with the new flags off against the parent commit's")
         pairs("parent_a", (parent, ["--umi_dedup"]), "parent_b", (parent, ["--umi_dedup"]), "stage2 CLI from FASTQ, --umi_dedup: the parent commit's build against itself")
+        if args.parent_flags:                                        # (a change that should move nothing: the same flags on both sides)
+            for label, extra in (("no flags", []), ("--umi_dedup --tagged_reads --chimera_cut --molecule_reads",
+                                                    ["--umi_dedup", "--tagged_reads", fa, "--chimera_cut", "--molecule_reads"])):
+                pairs("parent", (parent, extra), "this", (ROOT, extra), "stage2 CLI from FASTQ, %s: this build against the parent commit's" % label)
+                pairs("parent_a", (parent, extra), "parent_b", (parent, extra), "stage2 CLI from FASTQ, %s: the parent commit's build against itself" % label)
 
 
 def main():
@@ -154,6 +160,7 @@ def main():
     p.add_argument("--cli_reads", type=int, default=1000000)
     p.add_argument("--pairs", type=int, default=3)
     p.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    p.add_argument("--parent_flags", action="store_true", help="with --parent: the pairs also without flags and with all of them")
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
