@@ -4,6 +4,7 @@
 
     python -m badger_amd.badger -r out.tsv -d tenX_v3 -l whitelist.txt -c 5000 [-t 1] [-hs] [--umi_dedup [--umi_dist 1]]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa [--chimera_cut] [--umi_dedup [--molecule_reads]]
+    python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --umi_dedup --molecule_consensus consensus.fa
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -12,7 +13,9 @@
 cell: the trimmed cDNA with the corrected barcode as CB and, with --umi_dedup, the molecule as UB and its read count as RN in the
 header.  The input is read a second time for it (the extraction costs under a millisecond per million reads; no bases are kept).
 --molecule_reads keeps one read per molecule: the longest cDNA, the earliest read at equal lengths (the rule of molecule_reads.py,
-on the device).  Every other output is the same bytes with and without these flags.
+on the device).  --molecule_consensus PATH instead keeps every read in the tagged file and writes one consensus sequence per
+molecule from it (consensus.py: the reads of a molecule aligned to its longest read and voted column by column, on the device).
+Every other output is the same bytes with and without these flags.
 
 -d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
 (extract_raw_barcodes.py says what that changes), so --tagged_reads and --molecule_reads write the cDNA as stage 1's
@@ -32,6 +35,7 @@ from io import StringIO
 from traceback import print_exc
 
 from . import _native
+from .consensus import ANCHORS, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -90,6 +94,10 @@ def parse_args(args):
     p.add_argument("--molecule_reads", action="store_true", default=False,
                    help="--tagged_reads with --umi_dedup: write one read per molecule, the one with the longest cDNA (the earliest "
                         "at equal lengths)")
+    p.add_argument("--molecule_consensus", type=str, default=None, metavar="PATH",
+                   help="--tagged_reads with --umi_dedup: one consensus sequence per molecule as FASTA, the reads of the molecule "
+                        "voted on its longest read; the header is that read's with the number of voters as CN")
+    add_consensus_options(p)
     a = p.parse_args(args)
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
@@ -104,6 +112,14 @@ def parse_args(args):
         p.error("--chimera_max_ed needs --chimera_cut")
     if a.molecule_reads and not (a.umi_dedup and a.tagged_reads):
         p.error("--molecule_reads needs --umi_dedup and --tagged_reads")
+    if a.molecule_consensus and not (a.umi_dedup and a.tagged_reads):
+        p.error("--molecule_consensus needs --tagged_reads and --umi_dedup: it votes over the reads of each molecule in the tagged file")
+    if a.molecule_consensus and a.molecule_reads:
+        p.error("--molecule_consensus excludes --molecule_reads: one read per molecule leaves nothing to vote")
+    if (a.consensus_min_reads is not None or a.consensus_max_ed is not None) and not a.molecule_consensus:
+        p.error("--consensus_min_reads and --consensus_max_ed need --molecule_consensus")
+    a.consensus_min_reads = MIN_READS_DEFAULT if a.consensus_min_reads is None else a.consensus_min_reads
+    a.consensus_max_ed = MAX_ED_DEFAULT if a.consensus_max_ed is None else a.consensus_max_ed
     a.tso_min_score, a.tso5_max_ed = trim_5p_values(a.data_type, a.tso_min_score, a.tso5_max_ed)
     if a.chimera_cut and a.chimera_max_ed is None:
         a.chimera_max_ed = _native.CHIMERA_MAX_ED_DEFAULT
@@ -224,6 +240,19 @@ def write_tagged_reads(args, detector, tags):
                 % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))
 
 
+def consensus_anchor(data_type):
+    """the end the cDNA of a molecule's reads shares: the polyA cut in the 3' modes, the switch oligo in the 5' ones"""
+    return ANCHORS["start" if data_type.startswith("tenX_5p") else "end"]
+
+
+def write_molecule_consensus(args):
+    """behind write_tagged_reads, on the file it wrote"""
+    from .consensus import consensus_of_tagged, log_counts
+    counts = consensus_of_tagged(args.tagged_reads, args.molecule_consensus, consensus_anchor(args.data_type),
+                                 args.consensus_min_reads, args.consensus_max_ed, args.device)
+    log_counts(counts, args.molecule_consensus)
+
+
 def main(args):
     t_marks = [("start", time.perf_counter())]
 
@@ -287,6 +316,9 @@ def main(args):
         if args.tagged_reads:
             write_tagged_reads(args, detector, tags)
             mark("tagged_reads")
+            if args.molecule_consensus:
+                write_molecule_consensus(args)
+                mark("molecule_consensus")
         disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
     finally:
         st2.release_device()

@@ -1,0 +1,376 @@
+#!/usr/bin/env python3
+"""Per-molecule consensus cDNA (stage 2's --molecule_consensus).
+
+    python -m badger_amd.consensus -i tagged.fa -o consensus.fa [--anchor end|start] [--consensus_min_reads 3] [--consensus_max_ed 20]
+
+Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_consensus_dev, in numpy and integers
+only; the tests hold the device against it and it is not on the product path.  The DRIVER (consensus_of_tagged) is the product
+side: it reads a tagged FASTA as `badger.py --tagged_reads --umi_dedup` writes it, groups the reads by (CB, UB), elects each
+molecule's backbone and hands the groups to the device (bdg_consensus).
+
+The rule, in anchor-first coordinates (position p of a string of length L is index p for anchor=start, index L - 1 - p for
+anchor=end; the result is produced anchor-first and stored back in the input's sense).  Any byte other than ACGT behaves as N.
+    group       1 .. 16 sequences; the first is the backbone B (length Lb), the others are members.
+    alignment   of member M (length Lm) to B: unit-cost edit distance over cells (i, j), 0 <= i <= Lm, 0 <= j <= Lb, inside the
+                band -32 <= j - i <= 31; D[0][0] = 0; the diagonal costs 0 iff both bases are equal and in ACGT (N never matches);
+                vertical (a member base inserted) and horizontal (a backbone base deleted) cost 1.  ed = min_j D[Lm][j], span the
+                smallest j attaining it; no band cell in row Lm (Lm > Lb + 32): rejected by band.  Accepted iff
+                ed * 100 <= max_ed_pct * Lm.
+    traceback   from (Lm, span): diagonal if D[i-1][j-1] + cost == D[i][j], else vertical if D[i-1][j] + 1 == D[i][j], else
+                horizontal.
+    votes       per backbone position j: the backbone gives cov[j] += 1 and base[its code] if in ACGT; an accepted member gives
+                cov[j] += 1 for j < span, a diagonal step onto j votes its base (if ACGT), a horizontal step over j votes del[j],
+                the run of vertical steps in column j < Lb gives ins_n[j] += 1 and votes the run's base next to position j (its
+                last, anchor-first) in ins_base[j] if ACGT; a run in column Lb votes nothing.
+    call        j = 0 .. Lb - 1: if 2 * ins_n[j] > cov[j] the ins_base[j] base with the most votes (smallest code at a tie,
+                nothing without a vote); then nothing if 2 * del[j] > cov[j], else the base with the most base[j] votes (at a tie
+                the backbone's own if among the maxima, else the smallest code; without a vote the backbone's byte as it is).
+    lengths     a member longer than MAX_LEN is rejected by length; so is every member of a longer backbone, whose group
+                yields the backbone unchanged.
+Record per sequence (ed, span, flags): a backbone (0, Lb, BACKBONE); rejected by band or length (0, 0, flag).
+"""
+import argparse
+import logging
+import sys
+
+import numpy as np
+
+ANCHOR_START, ANCHOR_END = 0, 1
+ANCHORS = {"start": ANCHOR_START, "end": ANCHOR_END}
+MAX_LEN, MAX_GROUP = 8192, 16
+BAND_LO, BAND_HI, LANES = -32, 31, 64
+ACCEPTED, REJ_DIST, REJ_BAND, REJ_LEN, BACKBONE = 1, 2, 4, 8, 16
+MIN_READS_DEFAULT, MAX_ED_DEFAULT = 3, 20
+BATCH_BASES = 256 << 20             # bases per device call at most
+_INF = 1 << 20
+_CODE = np.full(256, 4, dtype=np.int8)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _i
+_LETTER = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+logger = logging.getLogger("BarcodeGraph")
+
+
+# ---------------------------------------------------------------- the checker ----
+def _as_bytes(s):
+    return s.encode() if isinstance(s, str) else bytes(s)
+
+
+def _align_batch(members, backbones):
+    """the banded alignment of members[k] to backbones[k] (uint8 arrays, anchor-first; every Lm <= Lb + 32), all pairs at once, a
+    row of the matrix per step and lane d of a row the diagonal j - i = d - 32 -> (ed [P], span [P], dbits, vbits [P, maxLm, 64]:
+    row i at index i - 1)"""
+    P = len(members)
+    Lm = np.array([len(m) for m in members], dtype=np.int64)
+    Lb = np.array([len(b) for b in backbones], dtype=np.int64)
+    rows = int(Lm.max()) if P else 0
+    Mc = np.full((P, max(rows, 1)), 5, dtype=np.int8)              # (a member's N is 5, a backbone's 4: they never match)
+    Bp = np.full((P, max(int(Lb.max()) if P else 0, rows) + LANES + 34, ), 4, dtype=np.int8)
+    for k in range(P):
+        c = _CODE[members[k]]
+        Mc[k, :len(c)] = np.where(c == 4, 5, c)
+        Bp[k, 33:33 + len(backbones[k])] = _CODE[backbones[k]]     # position p at column p + 33
+    d = np.arange(LANES, dtype=np.int64)
+    D = np.where((d >= 32) & (d - 32 <= Lb[:, None]), d - 32, _INF)
+    dbits = np.zeros((P, max(rows, 1), LANES), dtype=bool)
+    vbits = np.zeros((P, max(rows, 1), LANES), dtype=bool)
+    for t in range(rows):
+        i = t + 1
+        j = i + d - 32
+        valid = (j >= 0) & (j <= Lb[:, None])
+        cost = (Mc[:, t, None] != Bp[:, i:i + LANES]).astype(np.int64)      # cell (i, j) reads backbone position j - 1
+        up = np.concatenate([D[:, 1:], np.full((P, 1), _INF, dtype=np.int64)], axis=1)
+        c = np.where(valid, np.minimum(np.minimum(D + cost, up + 1), _INF), _INF)
+        Dn = np.minimum.accumulate(c - d, axis=1) + d                       # the horizontal steps inside the row
+        Dn = np.where(valid, np.minimum(Dn, _INF), _INF)
+        live = (i <= Lm)[:, None]
+        dbits[:, t, :] = live & valid & (j > 0) & (D + cost == Dn)
+        vbits[:, t, :] = live & valid & (up + 1 == Dn)
+        D = np.where(live, Dn, D)
+    key = D * LANES + d
+    best = key.min(axis=1) if P else np.zeros(0, np.int64)
+    return best // LANES, Lm + best % LANES - 32, dbits, vbits, Mc
+
+
+def consensus_groups(groups, anchor, max_ed_pct=MAX_ED_DEFAULT):
+    """the rule over groups (a list of lists of bytes / str / uint8 arrays, 1 .. 16 each)
+    -> list of (consensus bytes, n_voted, [(ed, span, flags) per sequence])"""
+    if anchor not in (ANCHOR_START, ANCHOR_END):
+        raise ValueError("unknown anchor")
+    if not 0 <= max_ed_pct <= 100:
+        raise ValueError("max_ed_pct out of range (0 .. 100)")
+    seqs = []
+    for g in groups:
+        if not 1 <= len(g) <= MAX_GROUP:
+            raise ValueError("a group holds 1 .. 16 sequences")
+        a = [np.frombuffer(_as_bytes(s), dtype=np.uint8) if not isinstance(s, np.ndarray) else s.astype(np.uint8) for s in g]
+        seqs.append([x[::-1] for x in a] if anchor == ANCHOR_END else a)
+    recs = [[None] * len(g) for g in seqs]
+    cnt_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    pairs = []                                                       # (group, index in the group)
+    for gi, g in enumerate(seqs):
+        Lb = len(g[0])
+        recs[gi][0] = (0, Lb, BACKBONE)
+        cnt_off[gi + 1] = cnt_off[gi] + (Lb if Lb <= MAX_LEN else 0)
+        for mi in range(1, len(g)):
+            Lm = len(g[mi])
+            if Lb > MAX_LEN or Lm > MAX_LEN:
+                recs[gi][mi] = (0, 0, REJ_LEN)
+            elif Lm > Lb - BAND_LO:
+                recs[gi][mi] = (0, 0, REJ_BAND)
+            else:
+                pairs.append((gi, mi))
+    N = int(cnt_off[-1])
+    base, ins_base = np.zeros((N, 4), np.int64), np.zeros((N, 4), np.int64)
+    dele, ins_n, cov_d = np.zeros(N, np.int64), np.zeros(N, np.int64), np.zeros(N + 1, np.int64)
+    # pairs in pieces of bounded direction-bit size, the longest first so that a piece holds similar lengths
+    pairs.sort(key=lambda p: -len(seqs[p[0]][p[1]]))
+    at = 0
+    while at < len(pairs):
+        rows = max(len(seqs[pairs[at][0]][pairs[at][1]]), 1)
+        take = max(1, (32 << 20) // (rows * LANES * 2))
+        piece = pairs[at:at + take]
+        at += take
+        M = [seqs[g][m] for g, m in piece]
+        B = [seqs[g][0] for g, _ in piece]
+        ed, span, dbits, vbits, Mc = _align_batch(M, B)
+        Lm = np.array([len(m) for m in M], dtype=np.int64)
+        Lb = np.array([len(b) for b in B], dtype=np.int64)
+        ok = ed * 100 <= max_ed_pct * Lm
+        for k, (g, m) in enumerate(piece):
+            recs[g][m] = (int(ed[k]), int(span[k]), ACCEPTED if ok[k] else REJ_DIST)
+        off = cnt_off[[g for g, _ in piece]]
+        np.add.at(cov_d, off[ok], 1)
+        np.add.at(cov_d, (off + span)[ok], -1)
+        # the traceback of every accepted pair, one step of each per round
+        i, j, last_v = Lm.copy(), span.copy(), np.full(len(piece), -1, dtype=np.int64)
+        live = np.flatnonzero(ok & ((i > 0) | (j > 0)))
+        while len(live):
+            li, lj = i[live], j[live]
+            r = np.maximum(li - 1, 0)
+            lane = np.clip(lj - li + 32, 0, LANES - 1)
+            mc = Mc[live, r].astype(np.int64)
+            diag = (li > 0) & (lj > 0) & dbits[live, r, lane]
+            vert = (li > 0) & ~diag & ((lj == 0) | vbits[live, r, lane])
+            hor = ~diag & ~vert
+            o = off[live]
+            s = diag & (mc < 4)
+            np.add.at(base, (o[s] + lj[s] - 1, mc[s]), 1)
+            np.add.at(dele, o[hor] + lj[hor] - 1, 1)
+            first = vert & (lj < Lb[live]) & (lj != last_v[live])            # the run's first step met: its last base anchor-first
+            np.add.at(ins_n, o[first] + lj[first], 1)
+            s = first & (mc < 4)
+            np.add.at(ins_base, (o[s] + lj[s], mc[s]), 1)
+            last_v[live[vert]] = lj[vert]
+            i[live] = li - (diag | vert)
+            j[live] = lj - (diag | hor)
+            live = live[(i[live] > 0) | (j[live] > 0)]
+    # the call, over every counted backbone position at once
+    cov = 1 + np.cumsum(cov_d[:-1])
+    bb = np.concatenate([g[0] for g in seqs if len(g[0]) <= MAX_LEN] + [np.zeros(0, np.uint8)])
+    bcode = _CODE[bb].astype(np.int64)
+    rows = np.arange(N)
+    own = bcode < 4
+    base[rows[own], bcode[own]] += 1
+    e_ins = (2 * ins_n > cov) & (ins_base.max(axis=1, initial=0) > 0)
+    c_ins = _LETTER[ins_base.argmax(axis=1)] if N else np.zeros(0, np.uint8)      # (argmax: the first, so the smallest code)
+    e_col = ~(2 * dele > cov)
+    top = base.max(axis=1, initial=0)
+    pick = base.argmax(axis=1) if N else np.zeros(0, np.int64)
+    own_wins = own & (base[rows, np.minimum(bcode, 3)] == top)
+    pick = np.where(own_wins, np.minimum(bcode, 3), pick)
+    c_col = np.where(top > 0, _LETTER[pick], bb)
+    emit = np.stack([e_ins, e_col], axis=1).ravel()
+    chars = np.stack([c_ins, c_col], axis=1).ravel()
+    out = []
+    for gi, g in enumerate(seqs):
+        voted = 1 + sum(1 for r in recs[gi][1:] if r[2] & ACCEPTED)
+        if len(g[0]) > MAX_LEN:
+            cons = g[0]
+        else:
+            lo, hi = 2 * cnt_off[gi], 2 * cnt_off[gi + 1]
+            cons = chars[lo:hi][emit[lo:hi]]
+        if anchor == ANCHOR_END:
+            cons = cons[::-1]
+        out.append((cons.tobytes(), voted, recs[gi]))
+    return out
+
+
+# ---------------------------------------------------------------- tagged FASTA: groups, election, text ----
+def _tag(fields, name):
+    for f in fields:
+        if f.startswith(name):
+            return f[len(name):]
+    return None
+
+
+def parse_tagged(text):
+    """a tagged FASTA (header line, sequence line) -> (headers [n] without '>', sequences [n] bytes, CB [n], UB [n]; None: no tag)"""
+    lines = text.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    if len(lines) % 2:
+        raise ValueError("tagged FASTA: a header without a sequence line")
+    heads, seqs, cb, ub = [], [], [], []
+    for h, s in zip(lines[::2], lines[1::2]):
+        if not h.startswith(b">"):
+            raise ValueError("tagged FASTA: header expected, got %r" % h[:40])
+        f = h[1:].split(b"\t")
+        heads.append(h[1:])
+        seqs.append(s)
+        cb.append(_tag(f[1:], b"CB:Z:"))
+        ub.append(_tag(f[1:], b"UB:Z:"))
+    return heads, seqs, cb, ub
+
+
+def elect(seqs, cb, ub):
+    """molecules of a tagged file -> (list of read-index lists, backbone first then the other reads in file order, at most 15 of
+    them; molecules in the file order of their backbones), reads left out for want of a CB or UB.  The backbone is the longest
+    sequence, the earliest in the file at equal lengths (the election of DESIGN 4.14)."""
+    n = len(seqs)
+    has = np.array([c is not None and u is not None for c, u in zip(cb, ub)], dtype=bool)
+    idx = np.flatnonzero(has)
+    if not len(idx):
+        return [], n
+    keys = np.array([cb[i] + b"\t" + ub[i] for i in idx])
+    _, group = np.unique(keys, return_inverse=True)
+    length = np.array([len(seqs[i]) for i in idx], dtype=np.int64)
+    order = np.lexsort((idx, -length, group))                      # per group: the longest first, the earliest at a tie
+    starts = np.flatnonzero(np.concatenate([[True], group[order][1:] != group[order][:-1]]))
+    backbone = idx[order][starts]                                   # per group
+    by_file = np.lexsort((idx, group))                              # per group its reads in file order
+    bounds = np.concatenate([np.flatnonzero(np.concatenate([[True], group[by_file][1:] != group[by_file][:-1]])), [len(idx)]])
+    in_file = idx[by_file].tolist()
+    mols = []
+    for g in np.argsort(backbone, kind="stable").tolist():          # (np.unique numbers the groups 0 ..: starts and bounds line up)
+        b = int(backbone[g])
+        mols.append([b] + [r for r in in_file[bounds[g]:bounds[g + 1]] if r != b][:MAX_GROUP - 1])
+    return mols, n - len(idx)
+
+
+def with_cn(head, n_voted):
+    """the backbone's header with CN:i:<n_voted> behind RN, in front of CH if there is one"""
+    at = head.find(b"\tCH:Z:")
+    tag = b"\tCN:i:%d" % n_voted
+    return head + tag if at < 0 else head[:at] + tag + head[at:]
+
+
+def consensus_text(text, anchor, min_reads, max_ed_pct, run_groups):
+    """the consensus file of a tagged file's bytes: run_groups(groups, anchor, max_ed_pct) is consensus_groups or the device's
+    equivalent -> (bytes, counts dict)"""
+    heads, seqs, cb, ub = parse_tagged(text)
+    mols, left_out = elect(seqs, cb, ub)
+    send = [m for m in mols if len(m) >= min_reads]
+    res = iter(run_groups([[seqs[i] for i in m] for m in send], anchor, max_ed_pct))
+    counts = dict(molecules=len(mols), voted=0, accepted=0, rej_dist=0, rej_band=0, rej_len=0, no_molecule=left_out)
+    out = []
+    for m in mols:
+        if len(m) < min_reads:
+            out.append(b">" + with_cn(heads[m[0]], 1) + b"\n" + seqs[m[0]] + b"\n")
+            continue
+        cons, voted, recs = next(res)
+        counts["voted"] += voted > 1
+        for _, _, fl in recs[1:]:
+            for name, bit in (("accepted", ACCEPTED), ("rej_dist", REJ_DIST), ("rej_band", REJ_BAND), ("rej_len", REJ_LEN)):
+                counts[name] += 1 if fl & bit else 0
+        out.append(b">" + with_cn(heads[m[0]], voted) + b"\n" + cons + b"\n")
+    return b"".join(out), counts
+
+
+# ---------------------------------------------------------------- the product side ----
+def device_groups(ctx):
+    """run_groups of consensus_text on the device: bdg_consensus over pieces of at most BATCH_BASES bases"""
+    def run(groups, anchor, max_ed_pct):
+        out, at = [], 0
+        while at < len(groups):
+            end, total = at, 0
+            while end < len(groups) and (end == at or total + sum(len(s) for s in groups[end]) <= BATCH_BASES):
+                total += sum(len(s) for s in groups[end])
+                end += 1
+            piece = groups[at:end]
+            flat = [s for g in piece for s in g]
+            bases = np.frombuffer(b"".join(flat), dtype=np.uint8)
+            seq_off = np.concatenate([[0], np.cumsum([len(s) for s in flat])]).astype(np.uint64)
+            grp_off = np.concatenate([[0], np.cumsum([len(g) for g in piece])]).astype(np.uint64)
+            o, o_off, o_len, voted, recs = ctx.consensus(bases, seq_off, grp_off, anchor, max_ed_pct)
+            for k in range(len(piece)):
+                a, b = int(grp_off[k]), int(grp_off[k + 1])
+                out.append((o[int(o_off[k]):int(o_off[k]) + int(o_len[k])].tobytes(), int(voted[k]),
+                            [(int(r["ed"]), int(r["span"]), int(r["flags"])) for r in recs[a:b]]))
+            at = end
+        return out
+    return run
+
+
+def consensus_of_tagged(path_in, path_out, anchor, min_reads=MIN_READS_DEFAULT, max_ed_pct=MAX_ED_DEFAULT, device=0):
+    """path_in: a tagged FASTA of `badger.py --tagged_reads --umi_dedup`; path_out: one record per molecule, in the file order of
+    the backbones -> counts"""
+    from . import _native
+    ctx = _native.default_context(device)
+    text, counts = consensus_text(open(path_in, "rb").read(), anchor, min_reads, max_ed_pct, device_groups(ctx))
+    with open(path_out, "wb") as f:
+        f.write(text)
+    return counts
+
+
+def log_counts(counts, path_out):
+    logger.info("Consensus: %d molecules to %s, %d with a vote; members: %d accepted, rejected %d by distance, %d by band, %d by "
+                "length; %d reads without a molecule left out"
+                % (counts["molecules"], path_out, counts["voted"], counts["accepted"], counts["rej_dist"], counts["rej_band"],
+                   counts["rej_len"], counts["no_molecule"]))
+
+
+def min_reads_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if x < 2:
+        raise argparse.ArgumentTypeError("--consensus_min_reads takes an integer of at least 2 (a molecule of one read has nothing to vote)")
+    return x
+
+
+def max_ed_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = -1
+    if not 0 <= x <= 100:
+        raise argparse.ArgumentTypeError("--consensus_max_ed takes a percentage, 0 .. 100")
+    return x
+
+
+def add_consensus_options(p):
+    p.add_argument("--consensus_min_reads", type=min_reads_arg, default=None, metavar="N",
+                   help="molecules of fewer reads are written as their longest read (default %d, at least 2)" % MIN_READS_DEFAULT)
+    p.add_argument("--consensus_max_ed", type=max_ed_arg, default=None, metavar="PCT",
+                   help="a read votes when its edit distance to the molecule's longest read is at most PCT percent of its length "
+                        "(default %d, 0 .. 100)" % MAX_ED_DEFAULT)
+
+
+def parse_args(argv):
+    p = argparse.ArgumentParser(description="per-molecule consensus of a tagged FASTA (badger.py --tagged_reads --umi_dedup)")
+    p.add_argument("-i", "--input", required=True, help="tagged FASTA: every read with CB, UB and RN")
+    p.add_argument("-o", "--output", required=True, help="consensus FASTA: one record per molecule")
+    p.add_argument("--anchor", choices=sorted(ANCHORS), default="end",
+                   help="the end the reads of a molecule share: end for 3' libraries (the polyA cut), start for 5' ones")
+    add_consensus_options(p)
+    p.add_argument("--device", type=int, default=0, help="MI355X device index")
+    a = p.parse_args(argv)
+    a.consensus_min_reads = MIN_READS_DEFAULT if a.consensus_min_reads is None else a.consensus_min_reads
+    a.consensus_max_ed = MAX_ED_DEFAULT if a.consensus_max_ed is None else a.consensus_max_ed
+    return a
+
+
+def main(argv):
+    a = parse_args(argv)
+    logger.setLevel(logging.INFO)
+    if not logger.handlers:
+        logger.addHandler(logging.StreamHandler(stream=sys.stdout))
+    log_counts(consensus_of_tagged(a.input, a.output, ANCHORS[a.anchor], a.consensus_min_reads, a.consensus_max_ed, a.device), a.output)
+
+
+if __name__ == "__main__":
+    from . import _native
+    _native.PRELOAD_TORCH = False            # nothing on this command line's path imports torch
+    main(sys.argv[1:])

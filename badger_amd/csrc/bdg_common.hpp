@@ -130,6 +130,11 @@ struct bdg_ctx {
     DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read;
                          // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
+    // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call
+    DevBuf c_meta;       // group of every sequence u32 | counter offset of every group u64
+    DevBuf c_cnt;        // vote counters, 8 bytes per backbone position of the call
+    DevBuf c_trace;      // direction bits, 16 bytes per member row and wave in flight
+    int c_cus = 0;       // compute units (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending
