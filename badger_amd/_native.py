@@ -40,6 +40,7 @@ RESCUE_SLACK, RESCUE_MAX_ED_DEFAULT, RESCUE_MAX_ED_MAX, RESCUE_MIN_SUPPORT_DEFAU
 CONSENSUS_DTYPE = np.dtype([("ed", "<u4"), ("span", "<u4"), ("flags", "<u4")])
 CONS_ANCHOR_START, CONS_ANCHOR_END = 0, 1
 CONS_MAX_LEN, CONS_MAX_GROUP = 8192, 16
+CONS_BAND_DEFAULT, CONS_BAND_MAX = 64, 256
 CONS_ACCEPTED, CONS_REJ_DIST, CONS_REJ_BAND, CONS_REJ_LEN, CONS_BACKBONE = 1, 2, 4, 8, 16
 FLAG_REV = 1
 FLAG_RANK_OK = 2
@@ -73,7 +74,7 @@ EXPORTS = [
     "bdg_chimera_batch", "bdg_chimera_batch_dev", "bdg_extract_set_chimera", "bdg_extract_collect_chimera", "bdg_format_trimmed_chimera",
     "bdg_extract_keep_cdna", "bdg_kept_cdna", "bdg_molecule_reps_dev", "bdg_molecule_reps_set_aggregate", "bdg_format_trimmed_tags",
     "bdg_rescue_batch", "bdg_rescue_batch_dev", "bdg_extract_set_rescue", "bdg_extract_rescue_resolve", "bdg_rescue_counts",
-    "bdg_consensus", "bdg_consensus_dev",
+    "bdg_consensus", "bdg_consensus_dev", "bdg_consensus_set_band",
 ]
 
 
@@ -326,6 +327,7 @@ def load():
     L.bdg_rescue_counts.argtypes = [vp, C.POINTER(u64)]
     L.bdg_consensus.argtypes = [vp, vp, vp, u64, vp, u32, C.c_int, u32, vp, vp, vp, vp, vp]
     L.bdg_consensus_dev.argtypes = [vp, vp, vp, u64, vp, u32, C.c_int, u32, vp, vp, vp, vp, vp]
+    L.bdg_consensus_set_band.argtypes = [vp, u32]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -356,6 +358,7 @@ class Context:
             raise BadgerHipError(rc, self.lib.bdg_last_error(None).decode())
         self.h = h
         self.device = int(device)
+        self.consensus_band = CONS_BAND_DEFAULT          # what consensus_set_band set last
 
     def close(self):
         if getattr(self, "h", None):
@@ -610,6 +613,12 @@ class Context:
         self._check(self.lib.bdg_consensus_dev(self.h, _ptr(d_bases), _ptr(d_seq_off), n_seqs, _ptr(d_grp_off), n_groups, int(anchor),
                                                int(max_ed_pct), _ptr(d_out_off), _ptr(d_out), _ptr(d_out_len), _ptr(d_n_voted),
                                                _ptr(d_recs)))
+
+    def consensus_set_band(self, band):
+        """the diagonals of the alignment's band for the consensus calls that follow: 64 (a new context's), 128 or 256
+        (bdg_consensus_set_band); consensus_band is the value in force"""
+        self._check(self.lib.bdg_consensus_set_band(self.h, int(band)))
+        self.consensus_band = int(band)
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""

@@ -5,6 +5,7 @@
     python -m badger_amd.badger -r out.tsv -d tenX_v3 -l whitelist.txt -c 5000 [-t 1] [-hs] [--umi_dedup [--umi_dist 1]]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa [--chimera_cut] [--umi_dedup [--molecule_reads]]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --umi_dedup --molecule_consensus consensus.fa
+                                [--consensus_band 64|128|256]
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -35,7 +36,7 @@ from io import StringIO
 from traceback import print_exc
 
 from . import _native
-from .consensus import ANCHORS, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
+from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -116,10 +117,11 @@ def parse_args(args):
         p.error("--molecule_consensus needs --tagged_reads and --umi_dedup: it votes over the reads of each molecule in the tagged file")
     if a.molecule_consensus and a.molecule_reads:
         p.error("--molecule_consensus excludes --molecule_reads: one read per molecule leaves nothing to vote")
-    if (a.consensus_min_reads is not None or a.consensus_max_ed is not None) and not a.molecule_consensus:
-        p.error("--consensus_min_reads and --consensus_max_ed need --molecule_consensus")
+    if (a.consensus_min_reads is not None or a.consensus_max_ed is not None or a.consensus_band is not None) and not a.molecule_consensus:
+        p.error("--consensus_min_reads, --consensus_max_ed and --consensus_band need --molecule_consensus")
     a.consensus_min_reads = MIN_READS_DEFAULT if a.consensus_min_reads is None else a.consensus_min_reads
     a.consensus_max_ed = MAX_ED_DEFAULT if a.consensus_max_ed is None else a.consensus_max_ed
+    a.consensus_band = BAND_DEFAULT if a.consensus_band is None else a.consensus_band
     a.tso_min_score, a.tso5_max_ed = trim_5p_values(a.data_type, a.tso_min_score, a.tso5_max_ed)
     if a.chimera_cut and a.chimera_max_ed is None:
         a.chimera_max_ed = _native.CHIMERA_MAX_ED_DEFAULT
@@ -249,7 +251,7 @@ def write_molecule_consensus(args):
     """behind write_tagged_reads, on the file it wrote"""
     from .consensus import consensus_of_tagged, log_counts
     counts = consensus_of_tagged(args.tagged_reads, args.molecule_consensus, consensus_anchor(args.data_type),
-                                 args.consensus_min_reads, args.consensus_max_ed, args.device)
+                                 args.consensus_min_reads, args.consensus_max_ed, args.device, args.consensus_band)
     log_counts(counts, args.molecule_consensus)
 
 

@@ -133,8 +133,9 @@ struct bdg_ctx {
     // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call
     DevBuf c_meta;       // group of every sequence u32 | counter offset of every group u64
     DevBuf c_cnt;        // vote counters, 8 bytes per backbone position of the call
-    DevBuf c_trace;      // direction bits, 16 bytes per member row and wave in flight
+    DevBuf c_trace;      // direction bits, 16 * c_band / 64 bytes per member row and wave in flight
     int c_cus = 0;       // compute units (asked once)
+    uint32_t c_band = BDG_CONS_BAND_DEFAULT;   // bdg_consensus_set_band: diagonals of the alignment's band, 64, 128 or 256
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -17,6 +17,13 @@
 //            is scalar work without a memory access.  Every step yields at most one vote; the votes of 64 steps are parked one
 //            per lane and issued as one vector atomic (a packed 32-bit add with a shifted increment, no return value).
 //            Members of one group run in different waves at once: the counters are only ever added to.
+//   wide     k_cons_align_wide<K>: the same wave for a band of W = 64 * K diagonals (bdg_consensus_set_band: K = 2, 4), K cells per
+//            lane.  Lane l holds the diagonals K * l .. K * l + K - 1 in K registers, so the upper neighbour of a cell is the
+//            lane's own next register and only the last one takes the next lane's first (one DPP shift, as at K = 1); the
+//            backbone's letters move the same way.  The horizontal steps are one pass: a running minimum of c - d over the lane's
+//            registers, one prefix over the lane totals (wave_incl_max, shifted by one lane to exclude the lane's own), K minima
+//            to apply it.  2 * K ballots per row, word r of a row the cells of register r: diagonal d is word d % K, bit d / K.
+//            The traceback loads 64 / K rows at once, lane l word l % K of row i - l / K: one contiguous 1 KiB load as at K = 1.
 //   call     k_cons_call: one block per group, one lane per backbone byte in the INPUT's sense.  Anchor-first order reversed is
 //            input order, so the place of a column's bases is an exclusive prefix over input indices for both anchors (for
 //            BDG_CONS_ANCHOR_END the column's base goes in front of its insertion); the prefix is bdgpart::block_excl_scan per
@@ -34,7 +41,7 @@
 namespace {
 
 constexpr int INF = 1 << 20;                       // above every distance (at most 2 * BDG_CONS_MAX_LEN), far below overflow
-constexpr uint32_t WAVES_PER_CU = 16;              // persistent waves: 16 * 256 CUs * 8192 rows * 16 B = 512 MiB of trace at most
+constexpr uint32_t WAVES_PER_CU = 16;              // persistent waves: 16 * 256 CUs * 8192 rows * 16 B = 512 MiB of trace at most (band 64; 2 GiB at 256)
 
 __device__ __forceinline__ uint32_t code_of(uint8_t c)
 {
@@ -149,6 +156,133 @@ void k_cons_align(const uint8_t* __restrict__ bases, const uint64_t* __restrict_
     }
 }
 
+// the band of 64 * K diagonals: lane l the diagonals d = K * l + r, r = 0 .. K - 1, diagonal d the cells j - i = d - 32 * K
+template <int K>
+__global__ __launch_bounds__(64)
+void k_cons_align_wide(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ grp_off,
+                       const uint32_t* __restrict__ seq_group, const uint64_t* __restrict__ cnt_off, uint32_t n_seqs, int anchor,
+                       uint32_t max_ed_pct, uint32_t* __restrict__ counters, ulonglong2* __restrict__ trace, uint32_t trace_rows,
+                       bdg_consensus_rec* __restrict__ recs)
+{
+    static_assert(K == 2 || K == 4, "64 * K diagonals: the end column's key keeps 8 bits of diagonal");
+    constexpr int H = 32 * K, LOG_K = K == 2 ? 1 : 2, WIN = 64 / K;           // WIN: rows of trace a wave holds in the traceback
+    const int lane = (int)threadIdx.x;
+    ulonglong2* const tr = trace + (size_t)blockIdx.x * trace_rows * K;      // row i, word r at tr[(i - 1) * K + r]
+    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
+        const uint32_t g = seq_group[q];
+        const uint64_t first = grp_off[g];
+        const uint64_t ob = seq_off[first], om = seq_off[q];
+        const uint64_t Lb64 = seq_off[first + 1] - ob, Lm64 = seq_off[q + 1] - om;
+        bdg_consensus_rec r;
+        if (q == first) { r.ed = 0u; r.span = (uint32_t)Lb64; r.flags = BDG_CONS_BACKBONE; }
+        else if (Lb64 > BDG_CONS_MAX_LEN || Lm64 > BDG_CONS_MAX_LEN) { r.ed = 0u; r.span = 0u; r.flags = BDG_CONS_REJ_LEN; }
+        else if (Lm64 > Lb64 + (uint64_t)H) { r.ed = 0u; r.span = 0u; r.flags = BDG_CONS_REJ_BAND; }
+        else {
+            const int Lb = (int)Lb64, Lm = (int)Lm64;                         // (Lm <= trace_rows: the host sized the trace by it)
+            const uint8_t* const B = bases + ob;
+            const uint8_t* const M = bases + om;
+            // ---- forward: row 0, then row t + 1 from row t
+            int D[K];
+            uint32_t bc[K];                                                   // row t + 1, diagonal d: backbone position t + d - H
+#pragma unroll
+            for (int x = 0; x < K; ++x) {
+                const int d = K * lane + x;
+                D[x] = d >= H && d - H <= Lb ? d - H : INF;
+                bc[x] = code_at(B, Lb, d - H, anchor);
+            }
+            uint32_t bch = 4u, mch = 4u;
+            for (int t = 0; t < Lm; ++t) {
+                if ((t & 63) == 0) mch = code_at(M, Lm, t + lane, anchor);
+                if (t >= 1) {
+                    if (((t - 1) & 63) == 0) bch = code_at(B, Lb, H - 1 + t + lane, anchor);
+                    uint32_t nx = wave_shl1(bc[0]);
+                    const uint32_t nb = lane_of(bch, (uint32_t)(t - 1) & 63u);   // position t + H - 1
+                    if (lane == 63) nx = nb;
+#pragma unroll
+                    for (int x = 0; x + 1 < K; ++x) bc[x] = bc[x + 1];
+                    bc[K - 1] = nx;
+                }
+                const uint32_t mc = lane_of(mch, (uint32_t)t & 63u);
+                int up_next = (int)wave_shl1((uint32_t)D[0]);
+                if (lane == 63) up_next = INF;
+                const int j0 = t + 1 + K * lane - H;                          // the column of the lane's first cell
+                int dc[K], uc[K], pm[K];                                      // through the diagonal, from above, the lane's running minimum of c - d
+                int run = INF;
+#pragma unroll
+                for (int x = 0; x < K; ++x) {
+                    const bool valid = j0 + x >= 0 && j0 + x <= Lb;
+                    dc[x] = D[x] + (mc < 4u && mc == bc[x] ? 0 : 1);
+                    uc[x] = (x + 1 < K ? D[x + 1] : up_next) + 1;
+                    int c = min(dc[x], uc[x]);                                // (j = 0: the lane's own value is the cell left of the matrix, INF)
+                    c = valid ? min(c, INF) : INF;
+                    run = min(run, c - (K * lane + x));
+                    pm[x] = run;
+                }
+                // the lanes in front: run is at most INF and at least -(64 * K - 1), so INF - run is a non-negative key; lane 0 reads 0
+                const int before = INF - (int)wave_shr1(wave_incl_max((uint32_t)(INF - run)));
+#pragma unroll
+                for (int x = 0; x < K; ++x) {
+                    const bool valid = j0 + x >= 0 && j0 + x <= Lb;
+                    int Dn = K * lane + x + min(pm[x], before);
+                    Dn = valid ? min(Dn, INF) : INF;
+                    const unsigned long long bd = __ballot(valid && j0 + x > 0 && dc[x] == Dn);
+                    const unsigned long long bv = __ballot(valid && uc[x] == Dn);
+                    if (lane == 0) tr[(size_t)t * K + x] = make_ulonglong2(bd, bv);
+                    D[x] = Dn;
+                }
+            }
+            // ---- the end column: the least value of row Lm, the smallest j at a tie
+            uint32_t key = (uint32_t)D[0] << 8 | (uint32_t)(K * lane);
+#pragma unroll
+            for (int x = 1; x < K; ++x) { const uint32_t o = (uint32_t)D[x] << 8 | (uint32_t)(K * lane + x); key = o < key ? o : key; }
+            for (int x = 1; x < 64; x <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)key, x); key = o < key ? o : key; }
+            key = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);
+            const int ed = (int)(key >> 8), span = Lm + (int)(key & 255u) - H;
+            const bool accepted = (uint64_t)ed * 100u <= (uint64_t)max_ed_pct * (uint64_t)Lm;
+            r.ed = (uint32_t)ed; r.span = (uint32_t)span; r.flags = accepted ? BDG_CONS_ACCEPTED : BDG_CONS_REJ_DIST;
+            if (accepted) {
+                // ---- traceback and votes (the rows lane 0 wrote are read by every lane: make them visible first)
+                __threadfence();
+                uint32_t* const w = counters + 2u * cnt_off[g];
+                int i = Lm, j = span, wtop = -1, last_vcol = -1;
+                unsigned long long wd = 0ull, wv = 0ull;
+                uint32_t wm = 4u, va = 0u, vi = 0u, nstep = 0u;
+                while (i > 0 || j > 0) {
+                    uint32_t a = 0u, inc = 0u;
+                    if (i == 0) { a = 2u * (uint32_t)(j - 1) + 1u; inc = 1u; --j; }
+                    else {
+                        if (wtop < i || wtop - i >= WIN) {                    // the next 64 / K rows, lane l word l % K of row i - l / K
+                            wtop = i;
+                            const int row = i - (lane >> LOG_K);
+                            if (row >= 1) {
+                                const ulonglong2 x = tr[(size_t)(row - 1) * K + (lane & (K - 1))];
+                                wd = x.x; wv = x.y; wm = code_at(M, Lm, row - 1, anchor);
+                            }
+                        }
+                        const int d = j - i + H;
+                        const uint32_t l0 = (uint32_t)(wtop - i) << LOG_K, l = l0 | ((uint32_t)d & (uint32_t)(K - 1));
+                        const unsigned long long bd = lane_of64(wd, l), bv = lane_of64(wv, l);
+                        const uint32_t mc = lane_of(wm, l0);
+                        const int bit = d >> LOG_K;
+                        if (j > 0 && ((bd >> bit) & 1ull)) {
+                            if (mc < 4u) { a = 2u * (uint32_t)(j - 1); inc = 1u << (8u * mc); }
+                            --i; --j;
+                        } else if (j == 0 || ((bv >> bit) & 1ull)) {
+                            if (j < Lb && j != last_vcol) { a = 2u * (uint32_t)j + 1u; inc = 1u << 8 | (mc < 4u ? 1u << (16u + 4u * mc) : 0u); }
+                            last_vcol = j;
+                            --i;
+                        } else { a = 2u * (uint32_t)(j - 1) + 1u; inc = 1u; --j; }
+                    }
+                    if ((uint32_t)lane == (nstep & 63u)) { va = a; vi = inc; }
+                    if ((++nstep & 63u) == 0u) { if (vi) atomicAdd(&w[va], vi); vi = 0u; }
+                }
+                if (vi) atomicAdd(&w[va], vi);
+            }
+        }
+        if (lane == 0) recs[q] = r;
+    }
+}
+
 __global__ __launch_bounds__(256)
 void k_cons_call(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint64_t* __restrict__ grp_off,
                  const uint64_t* __restrict__ cnt_off, int anchor, const uint32_t* __restrict__ counters,
@@ -221,6 +355,7 @@ struct ConsPlan {
     std::vector<uint32_t> seq_group;     // [n_seqs]
     std::vector<uint64_t> cnt_off;       // [n_groups + 1] backbone positions with counters in front of the group
     uint32_t trace_rows = 1;             // the longest member that is aligned
+    uint32_t band = BDG_CONS_BAND_DEFAULT;   // the context's at the time of the plan
 };
 
 int cons_plan(bdg_ctx* ctx, const uint64_t* seq_off, uint64_t n_seqs, const uint64_t* grp_off, uint32_t n_groups, int anchor,
@@ -234,6 +369,7 @@ int cons_plan(bdg_ctx* ctx, const uint64_t* seq_off, uint64_t n_seqs, const uint
         if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "consensus: sequence offsets must be non-decreasing");
         if (seq_off[q + 1] - seq_off[q] >= (1ull << 26)) return bdg_fail(ctx, BDG_E_ARG, "consensus: sequence longer than 2^26 bases");
     }
+    P.band = ctx->c_band;
     P.seq_group.resize(n_seqs);
     P.cnt_off.resize((size_t)n_groups + 1);
     uint64_t cnt = 0;
@@ -250,7 +386,7 @@ int cons_plan(bdg_ctx* ctx, const uint64_t* seq_off, uint64_t n_seqs, const uint
             cnt += Lb;
             for (uint64_t q = first + 1; q < first + size; ++q) {
                 const uint64_t Lm = seq_off[q + 1] - seq_off[q];
-                if (Lm <= BDG_CONS_MAX_LEN && Lm <= Lb + 32) P.trace_rows = std::max(P.trace_rows, (uint32_t)Lm);
+                if (Lm <= BDG_CONS_MAX_LEN && Lm <= Lb + P.band / 2) P.trace_rows = std::max(P.trace_rows, (uint32_t)Lm);
             }
         }
         for (uint64_t q = first; q < first + size; ++q) P.seq_group[q] = g;
@@ -271,12 +407,13 @@ int cons_launch(bdg_ctx* ctx, const ConsPlan& P, const uint8_t* d_bases, const u
     }
     const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->c_cus * WAVES_PER_CU);
     const uint64_t n_cnt = P.cnt_off[n_groups];
-    // workspaces: seq_group u32 [n_seqs] | cnt_off u64 [n_groups + 1];  counters 8 B per backbone position;  trace per wave
+    // workspaces: seq_group u32 [n_seqs] | cnt_off u64 [n_groups + 1];  counters 8 B per backbone position;  trace per wave,
+    // band / 64 words of 16 B per row
     const size_t sg_bytes = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u, co_bytes = sizeof(uint64_t) * ((size_t)n_groups + 1);
     int rc;
     if ((rc = bdg_reserve(ctx, ctx->c_meta, sg_bytes + co_bytes))) return rc;
     if ((rc = bdg_reserve(ctx, ctx->c_cnt, 8 * (size_t)n_cnt + 8))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->c_trace, sizeof(ulonglong2) * (size_t)waves * P.trace_rows))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->c_trace, sizeof(ulonglong2) * (P.band / 64u) * (size_t)waves * P.trace_rows))) return rc;
     auto* d_sg = static_cast<uint32_t*>(ctx->c_meta.p);
     auto* d_co = reinterpret_cast<uint64_t*>(static_cast<char*>(ctx->c_meta.p) + sg_bytes);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(d_sg, P.seq_group.data(), sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
@@ -285,7 +422,8 @@ int cons_launch(bdg_ctx* ctx, const ConsPlan& P, const uint8_t* d_bases, const u
     BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->c_cnt.p, 0, 8 * (size_t)n_cnt + 8, st));
     {
         ScopedKernelTimer tm(ctx, "k_cons_align");
-        hipLaunchKernelGGL(k_cons_align, dim3(waves), dim3(64), 0, st, d_bases, d_seq_off, d_grp_off, d_sg, d_co, (uint32_t)n_seqs, anchor,
+        const auto align = P.band == 64u ? k_cons_align : P.band == 128u ? k_cons_align_wide<2> : k_cons_align_wide<4>;
+        hipLaunchKernelGGL(align, dim3(waves), dim3(64), 0, st, d_bases, d_seq_off, d_grp_off, d_sg, d_co, (uint32_t)n_seqs, anchor,
                            max_ed_pct, static_cast<uint32_t*>(ctx->c_cnt.p), static_cast<ulonglong2*>(ctx->c_trace.p), P.trace_rows, d_recs);
     }
     {
@@ -300,6 +438,14 @@ int cons_launch(bdg_ctx* ctx, const ConsPlan& P, const uint8_t* d_bases, const u
 }  // namespace
 
 extern "C" {
+
+int bdg_consensus_set_band(bdg_ctx* ctx, uint32_t band)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (band != 64u && band != 128u && band != BDG_CONS_BAND_MAX) return bdg_fail(ctx, BDG_E_ARG, "consensus: the band is 64, 128 or 256 diagonals");
+    ctx->c_band = band;
+    return BDG_OK;
+}
 
 int bdg_consensus_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_seq_off, uint64_t n_seqs, const uint64_t* d_grp_off,
                       uint32_t n_groups, int anchor, uint32_t max_ed_pct, const uint64_t* d_out_off, uint8_t* d_out,

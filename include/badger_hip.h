@@ -838,9 +838,11 @@ int  bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on);
 #define BDG_CONS_ANCHOR_END   1      /* ... their last base (3' modes: in mRNA sense the cDNA ends at the polyA cut) */
 #define BDG_CONS_MAX_LEN      8192   /* longest sequence that is aligned */
 #define BDG_CONS_MAX_GROUP    16     /* sequences of a group at most: the backbone and 15 members */
+#define BDG_CONS_BAND_DEFAULT 64     /* diagonals of the alignment's band W (bdg_consensus_set_band): 64, 128 or ... */
+#define BDG_CONS_BAND_MAX     256    /* ... 256 */
 #define BDG_CONS_ACCEPTED     1u     /* bdg_consensus_rec.flags: the member voted */
 #define BDG_CONS_REJ_DIST     2u     /* ... ed * 100 > max_ed_pct * Lm */
-#define BDG_CONS_REJ_BAND     4u     /* ... no cell of the band in the member's last row (Lm > Lb + 32) */
+#define BDG_CONS_REJ_BAND     4u     /* ... no cell of the band in the member's last row (Lm > Lb + W / 2) */
 #define BDG_CONS_REJ_LEN      8u     /* ... the member, or its group's backbone, is longer than BDG_CONS_MAX_LEN */
 #define BDG_CONS_BACKBONE     16u    /* ... the group's first sequence */
 /* Per sequence.  A backbone: ed 0, span Lb.  A member rejected by band or by length: ed 0, span 0. */
@@ -851,11 +853,12 @@ typedef struct { uint32_t ed, span, flags; } bdg_consensus_rec;
  * anchor-first coordinates: position p of a string of length L is index p for BDG_CONS_ANCHOR_START and index L - 1 - p for
  * BDG_CONS_ANCHOR_END; the consensus is produced anchor-first and stored back in the input's sense.
  *   alignment   of member M (length Lm) to B: unit-cost edit distance over the cells (i, j), 0 <= i <= Lm, 0 <= j <= Lb, inside
- *               the band -32 <= j - i <= 31 (every other cell is +infinity).  D[0][0] = 0; the diagonal step costs 0 iff both
+ *               the band of W diagonals -H <= j - i <= H - 1, H = W / 2 (every other cell is +infinity; W is the context's
+ *               band, bdg_consensus_set_band: 64 unless set, so -32 <= j - i <= 31).  D[0][0] = 0; the diagonal step costs 0 iff both
  *               bases are equal and in ACGT (an N never matches, not even an N); a vertical step (a member base inserted) and a
  *               horizontal step (a backbone base deleted) cost 1.  The member is consumed whole, the backbone's far end is free:
- *               ed = min over j of D[Lm][j], span = the smallest j that attains it.  Without a band cell in row Lm the member is
- *               rejected (BDG_CONS_REJ_BAND).  It is accepted iff ed * 100 <= max_ed_pct * Lm.
+ *               ed = min over j of D[Lm][j], span = the smallest j that attains it.  Without a band cell in row Lm
+ *               (Lm > Lb + H) the member is rejected (BDG_CONS_REJ_BAND).  It is accepted iff ed * 100 <= max_ed_pct * Lm.
  *   traceback   from (Lm, span); at each cell: the diagonal if D[i-1][j-1] + cost == D[i][j], else the vertical step if
  *               D[i-1][j] + 1 == D[i][j], else the horizontal step.
  *   votes       per backbone position j < Lb the counters base[4], del, cov, ins_n, ins_base[4].  The backbone gives cov[j] += 1
@@ -873,8 +876,10 @@ typedef struct { uint32_t ed, span, flags; } bdg_consensus_rec;
  * Device arrays in and out: d_out takes group g's consensus from d_out_off[g] on, where the caller left at least 2 * Lb bytes
  * (d_out_off [n_groups + 1]); d_out_len [n_groups] its length, d_n_voted [n_groups] the backbone plus the accepted members,
  * d_recs [n_seqs] the records.  The call reads the three offset arrays back to check them and to size its workspaces (held by
- * the context: 8 bytes of counters per backbone base, 16 bytes of trace per member row and wave in flight), so it waits for
- * the stream once; the kernels are asynchronous.  BDG_E_ARG: a group of 0 or more than 16 sequences, offsets that are not
+ * the context: 8 bytes of counters per backbone base, 16 * W / 64 bytes of trace per member row and wave in flight - rows: the
+ * longest aligned member of the call, waves: 16 per compute unit at most, so up to 512 MiB at W = 64 and 2 GiB at W = 256 when a
+ * call holds 8,192-base members; BDG_E_NOMEM where the reserve fails), so it waits for the stream once; the kernels are
+ * asynchronous.  BDG_E_ARG: a group of 0 or more than 16 sequences, offsets that are not
  * monotone or do not cover [0, n_seqs], less than 2 * Lb output bytes for a group, an unknown anchor, max_ed_pct > 100. */
 int  bdg_consensus_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_seq_off, uint64_t n_seqs, const uint64_t* d_grp_off,
                        uint32_t n_groups, int anchor, uint32_t max_ed_pct, const uint64_t* d_out_off, uint8_t* d_out,
@@ -883,6 +888,10 @@ int  bdg_consensus_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_s
 int  bdg_consensus(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint64_t n_seqs, const uint64_t* grp_off,
                    uint32_t n_groups, int anchor, uint32_t max_ed_pct, const uint64_t* out_off, uint8_t* out,
                    uint32_t* out_len, uint32_t* n_voted, bdg_consensus_rec* recs);
+/* The band W of the alignment for the calls of bdg_consensus and bdg_consensus_dev that follow on this context: 64 (a new
+ * context's, BDG_CONS_BAND_DEFAULT), 128 or 256 diagonals.  Nothing else of the rule depends on it.  BDG_E_ARG for any other
+ * value; the band then stays what it was. */
+int  bdg_consensus_set_band(bdg_ctx* ctx, uint32_t band);
 
 /* ---- stage 2's read-side plumbing on the host (badger.py:112-121,129; barcode_graph.py:388-410) -------------- */
 /* Read ids of a run, kept natively (12 bytes per read instead of a Python string each). */

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Measurements of the per-molecule consensus, one JSON line each to --out (and stdout).
 
-    python tools/consensus_probe.py --device [--reads 1000000] --out profiles/r19_consensus.jsonl
+    python tools/consensus_probe.py --device [--reads 1000000] [--band 64 128 256] [--long_reads 100000] --out profiles/r20_consensus_band.jsonl
         bdg_consensus_dev alone, device-resident: reads in molecules of about 5 reads of about 900 bases (600 .. 1,200, the members
         cut by up to a quarter at the end away from the anchor, synth's error rates): wall time per call (with the call's own
-        read-back of the offsets and its planning on the host), and the two kernels from the library's event timers.
+        read-back of the offsets and its planning on the host), and the two kernels from the library's event timers, in every
+        --band asked for (bdg_consensus_set_band; 64 alone by default).  With --long_reads N a second workload behind it: N reads
+        in molecules of 3,000 .. 6,000 bases, where the band decides how many members vote (--reads 0 leaves the first one out).
     python tools/consensus_probe.py --cli [--cli_reads 1000000] [--pairs 3] [--parent DIR] --out ...
         the stage-2 command line on a FASTQ file in which every read of synth's error model comes with four siblings (the same
         read with 3 % substitutions between its ends, so that barcode and UMI stay), as alternating pairs of fresh processes:
@@ -76,14 +78,23 @@ def device_probe(args):
     from badger_amd import _native
     _native.PRELOAD_TORCH = False
     ctx = _native.default_context(0)
-    bases, seq_off, grp_off = molecules(args.reads)
+    if args.reads:
+        device_workload(args, _native, ctx, "molecules of 600 .. 1,200 bases", molecules(args.reads), (_native.CONS_ANCHOR_END, _native.CONS_ANCHOR_START))
+    if args.long_reads:
+        device_workload(args, _native, ctx, "molecules of 3,000 .. 6,000 bases", molecules(args.long_reads, seed=2, lo=3000, hi=6000, chunk=2000),
+                        (_native.CONS_ANCHOR_END,))
+
+
+def device_workload(args, _native, ctx, workload, arrays, anchors):
+    bases, seq_off, grp_off = arrays
     n_seqs, n_groups = len(seq_off) - 1, len(grp_off) - 1
     out_off = _native.consensus_out_offsets(seq_off, grp_off)
     d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, seq_off, grp_off, out_off)]
     d_out = _native.DeviceArray(ctx, int(out_off[-1]), np.uint8)
     d_len, d_voted = _native.DeviceArray(ctx, n_groups, np.uint32), _native.DeviceArray(ctx, n_groups, np.uint32)
     d_recs = _native.DeviceArray(ctx, n_seqs * 3, np.uint32)
-    for anchor in (_native.CONS_ANCHOR_END, _native.CONS_ANCHOR_START):
+    for band, anchor in ((b, a) for b in args.band for a in anchors):
+        ctx.consensus_set_band(band)
         call = lambda: ctx.consensus_dev(d[0], d[1], n_seqs, d[2], n_groups, anchor, 20, d[3], d_out, d_len, d_voted, d_recs)  # noqa: E731
         call()
         ctx.synchronize()
@@ -101,12 +112,13 @@ def device_probe(args):
         ctx.profile(False)
         recs = d_recs.to_host().view(_native.CONSENSUS_DTYPE)
         flags = recs["flags"]
-        emit(args.out, {"what": "bdg_consensus_dev, device-resident", "anchor": "end" if anchor else "start", "reads": n_seqs,
+        emit(args.out, {"what": "bdg_consensus_dev, device-resident", "workload": workload, "band": band, "anchor": "end" if anchor else "start", "reads": n_seqs,
                         "molecules": n_groups, "bases": int(seq_off[-1]), "accepted": int((flags & 1 != 0).sum()),
                         "rejected_by_distance": int((flags & 2 != 0).sum()), "rejected_by_band": int((flags & 4 != 0).sum()),
                         "consensus_bases": int(d_len.to_host().sum()), "call_ms_median": round(1e3 * float(np.median(times)), 3),
                         "call_ms_min": round(1e3 * min(times), 3), "kernel_ms": kt,
                         "kernel_ms_per_1M_reads": {k: round(v * 1e6 / n_seqs, 3) for k, v in kt.items()}})
+    ctx.consensus_set_band(_native.CONS_BAND_DEFAULT)
     for a in d + [d_out, d_len, d_voted, d_recs]:
         a.free()
 
@@ -183,6 +195,8 @@ def main():
     p.add_argument("--cli", action="store_true")
     p.add_argument("--reads", type=int, default=1000000)
     p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--band", type=int, nargs="+", choices=(64, 128, 256), default=[64], help="the bands to measure, each in turn")
+    p.add_argument("--long_reads", type=int, default=0, help="reads of the long-molecule workload (3,000 .. 6,000 bases); 0: none")
     p.add_argument("--cli_reads", type=int, default=1000000)
     p.add_argument("--pairs", type=int, default=3)
     p.add_argument("--parent", default=None, help="a built checkout of the parent commit")
