@@ -22,7 +22,9 @@
 //                    Of the union only that one bit is used, so the column loop is split: the words up to the end of the
 //                    wave's longest first window (at most 10 of the 14) build keys, and of those only the words that hold
 //                    some lane's last strict or relaxed column run the snapshot selects; the words behind them are
-//                    score-only (no row tag, no column key: one packed maximum of the cells).
+//                    score-only (no row tag, no column key: one packed maximum of the cells) - and run only for the clusters
+//                    that a bound on what those words can still add, taken from the cells the head leaves, does not
+//                    decide (one in a hundred): a block hands them to one of its waves through LDS (tail_bound2).
 //   k_strict_filter  queue B only matters if an alignment reaches score 17, which implies semi-global edit distance <= 5:
 //                    Myers' 22-bit search per group of two neighbouring hits (one pass over the union of their windows),
 //                    after dropping read-strands the relaxed search has already decided; survivors join queue C.
@@ -95,13 +97,17 @@ __device__ __forceinline__ QEnt queue_fetch(const QEnt* __restrict__ q, uint64_t
     return e;
 }
 // per-wave LDS staging of {read, (pos << 1) | strand} single-hit entries: one reservation per flush
+// (READLANE: the reservation reaches the lanes through the scalar unit - the same value, and no exchange address that a
+// kernel short of registers would hold across its loop)
+template <bool READLANE = false>
 __device__ __forceinline__ void stage_flush(uint2* buf, uint32_t& n, int lane, QEnt* __restrict__ q, uint64_t seg, uint32_t shard,
                                             unsigned long long* cnt)
 {
     if (n == 0) return;
     unsigned long long gb = 0;
     if (lane == 0) gb = atomicAdd(cnt, (unsigned long long)n);
-    gb = __shfl(gb, 0);
+    if (READLANE) gb = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(gb >> 32), 0) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)gb, 0);
+    else gb = __shfl(gb, 0);
     for (uint32_t i = (uint32_t)lane; i < n; i += 64u) {
         const unsigned long long idx = gb + i;
         if (idx < seg) { const uint2 e = buf[i]; q[shard * seg + idx] = make_uint4(e.x, e.y, 1u, 0u); }
@@ -765,6 +771,14 @@ __device__ __forceinline__ int wave_max(int v)
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+// wave_or with the lane number handed in: k_sw_clusters passes a copy the compiler cannot see through, so that the six
+// exchange addresses are made where they are used and not held in registers across the whole persistent loop.
+__device__ __forceinline__ uint32_t wave_or_at(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)v);
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
 __device__ __forceinline__ uint32_t wave_or(uint32_t v)
 {
 #pragma unroll
@@ -924,15 +938,14 @@ __device__ __forceinline__ void sw_word(uint32_t (&hm)[R1_LEN], uint32_t curA, u
 // n1 - 1 or n2 - 1 lies in word d; the other head words run without the snapshot selects.  ndh, ndw and snap_words are the
 // same in every lane: the loops branch on scalars and stay rolled, one copy of each body.
 template <int NW, bool WITH_N, bool SINGLE>
-__device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firstA, uint32_t firstB, int ndh, int ndw, uint32_t snap_words,
-                                              uint32_t n1, uint32_t n2, uint32_t P0, uint32_t P1, uint32_t rowmask,
-                                              uint32_t& snap1, uint32_t& snap2, uint32_t& tail_max)
+__device__ __forceinline__ uint32_t sw_head2(uint32_t (&hm)[R1_LEN], const uint32_t* win, uint32_t firstA, uint32_t firstB, int ndh, uint32_t snap_words,
+                                             uint32_t n1, uint32_t n2, uint32_t P0, uint32_t P1, uint32_t rowmask,
+                                             uint32_t& snap1, uint32_t& snap2)
 {
     // Cells are kept as G - 1 = H in offset form, floored at 0 by the saturating subtract: every consumer of a cell (the
     // cell to its right, below it, and diagonally below) needs exactly that, so one v_pk_sub_u16 clamp per cell replaces
     // two subtractions and the max with 0.  (An unfloored cell only ever reaches the running key with score <= 0, where
-    // the key is never used.)
-    uint32_t hm[R1_LEN];
+    // the key is never used.)  hm is left holding the cells of the head's last column, H << 10 in each half.
 #pragma unroll
     for (int i = 0; i < R1_LEN; ++i) hm[i] = 0u;             // H = 0
     uint32_t acc = 0, s1 = 0, s2 = 0, tmax = 0;
@@ -959,24 +972,25 @@ __device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firs
             }
         }
     }
-    if (!SINGLE) {
-#pragma nounroll
-        for (; d < ndw; ++d) {
-            const int dn = d + 1 < NW ? d + 1 : NW - 1;
-            const uint32_t nextA = win[(dn - 1) * 64], nextB = win[(NW - 1 + dn - 1) * 64];
-            sw_word<WITH_N, SINGLE, SW_SCORE>(hm, curA, curB, d, n1, n2, P0, P1, rowmask, acc, s1, s2, tmax);
-            curA = nextA; curB = nextB;
-        }
-    }
-    snap1 = s1; snap2 = s2; tail_max = tmax;
+    snap1 = s1; snap2 = s2;
     return acc;
 }
 
-// packed half -> sw_block key
-__device__ __forceinline__ uint32_t unpk(uint32_t packed, int half)
+// The score-only words behind a head: nt words of two alignments whose cells are in hm, alignment A from word dA of the
+// window at winA (word d >= 1 at winA[(d - 1) * 64], as sw_head2 lays them out), B likewise; a word from NW on is all 'N'.
+// The pointers and first words are a lane's own, so the two alignments need not be the ones the lane ran the head for
+// (k_sw_clusters' tail pass).  -> the packed maximum of the cells (sw_tail_score turns a half of it into a score)
+template <int NW, bool WITH_N>
+__device__ __forceinline__ uint32_t sw_tail2(uint32_t (&hm)[R1_LEN], const uint32_t* winA, const uint32_t* winB, int dA, int dB, int nt)
 {
-    const uint32_t k = half ? packed >> 16 : packed & 0xFFFFu;
-    return k >= (uint32_t)ONE ? k - (uint32_t)ONE : 0u;
+    uint32_t tmax = 0, acc = 0, s1 = 0, s2 = 0;
+#pragma nounroll
+    for (int t = 0; t < nt; ++t, ++dA, ++dB) {
+        const uint32_t wA = winA[(min(dA, NW - 1) - 1) * 64], wB = winB[(min(dB, NW - 1) - 1) * 64];
+        const uint32_t curA = dA < NW ? wA : 0x4E4E4E4Eu, curB = dB < NW ? wB : 0x4E4E4E4Eu;
+        sw_word<WITH_N, false, SW_SCORE>(hm, curA, curB, 0, 0u, 0u, R1_P0, R1_P1, 0xFFFFFFFFu, acc, s1, s2, tmax);
+    }
+    return tmax;
 }
 
 // A half of sw_block2's tail_max -> the best score of the tail's columns.  The tail keeps cells as G = (H + 1) << 10, and
@@ -987,6 +1001,70 @@ __device__ __forceinline__ uint32_t sw_tail_score(uint32_t tail_max, int half)
 {
     const uint32_t g = (half ? tail_max >> 16 : tail_max & 0xFFFFu) >> 10;
     return g ? g - 1u : 0u;
+}
+
+// The tail certificate.  Every window of the cluster lies inside the union, so no later hit scores above the union; if the
+// union does not beat the first hit, none of them can replace it (strictly greater is required, common.py:102), otherwise
+// they are aligned one by one (queue C, second launch).  After the head (last column c_h = 4 * ndh - 1, cells H[r], ext =
+// n_u - 1 - c_h columns left) an alignment that ends behind c_h either starts there, and scores at most min(ext, 22), or
+// crosses from a cell (r, c_h), and scores at most H[r] + min(21 - r, ext): a diagonal step adds at most 1 and uses up a
+// row and a column, an N adds 0.  With B the maximum of these bounds, a cluster with score_h <= score_s and B <= score_s
+// is decided (no), one with score_h > score_s is decided (yes), and only the others - one cluster in a hundred - are
+// OPEN and need the columns behind the head.  -> B << 10 in both halves
+__device__ __forceinline__ uint32_t tail_bound2(const uint32_t (&hm)[R1_LEN], uint32_t ext2 /* min(ext, 22) << 10, both halves */)
+{
+    uint32_t B = pk_max(ext2, hm[R1_LEN - 1]);
+#pragma unroll
+    for (int r = 0; r < R1_LEN - 1; ++r) B = pk_max(B, pk_add(hm[r], pk_min(ext2, (uint32_t)((R1_LEN - 1 - r) << 10) * 0x00010001u)));
+    return B;
+}
+
+// The words of a list entry (k_sw_clusters: the open clusters of a block, handed to its tail wave).
+constexpr int TE_HALF = 8, TE_SCORE = 9, TE_WORD = 14, TE_N = 18, TE_COLS = 19;      // owner thread in bits 0..7; bit 31: the entry is there
+__device__ __forceinline__ bool tail_entries_open(const uint32_t (&hm)[R1_LEN], uint32_t tmax, uint32_t m0, uint32_t m1, int done)
+{
+    // with `done` words behind the head aligned: does either entry still need columns?
+    const int rem0 = (int)((m0 >> TE_COLS) & 63u) - 4 * done, rem1 = (int)((m1 >> TE_COLS) & 63u) - 4 * done;
+    const uint32_t B2 = tail_bound2(hm, ((uint32_t)min(max(rem0, 0), R1_LEN) | ((uint32_t)min(max(rem1, 0), R1_LEN) << 16)) << 10);
+    const uint32_t s0 = (m0 >> TE_SCORE) & 31u, s1 = (m1 >> TE_SCORE) & 31u;
+    return (rem0 > 0 && sw_tail_score(tmax, 0) <= s0 && ((B2 & 0xFFFFu) >> 10) > s0)
+           || (rem1 > 0 && sw_tail_score(tmax, 1) <= s1 && (B2 >> 26) > s1);
+}
+// sw_tail2 for two list entries m0 / m1 (one that is not there has no columns), with the certificate again behind every
+// word: the pass ends when no entry of the wave is open any more - mostly after one or two words of the four.
+template <int NW, bool WITH_N>
+__device__ __forceinline__ uint32_t sw_tail_list(uint32_t (&hm)[R1_LEN], const uint32_t* winA, const uint32_t* winB, uint32_t m0, uint32_t m1)
+{
+    uint32_t tmax = 0, acc = 0, s1 = 0, s2 = 0;
+    int t = 0;
+#pragma nounroll
+    do {
+        const int d0 = (int)((m0 >> TE_WORD) & 15u) + t, d1 = (int)((m1 >> TE_WORD) & 15u) + t;
+        const uint32_t wA = winA[(min(d0, NW - 1) - 1) * 64], wB = winB[(min(d1, NW - 1) - 1) * 64];
+        const uint32_t curA = d0 < NW ? wA : 0x4E4E4E4Eu, curB = d1 < NW ? wB : 0x4E4E4E4Eu;
+        sw_word<WITH_N, false, SW_SCORE>(hm, curA, curB, 0, 0u, 0u, R1_P0, R1_P1, 0xFFFFFFFFu, acc, s1, s2, tmax);
+        ++t;
+    } while (__ballot(tail_entries_open(hm, tmax, m0, m1, t)) != 0ull);
+    return tmax;
+}
+
+// One alignment a lane (SINGLE callers: head words only, ndh == ndw), or the whole of two: head and score-only tail.
+template <int NW, bool WITH_N, bool SINGLE>
+__device__ __forceinline__ uint32_t sw_block2(const uint32_t* win, uint32_t firstA, uint32_t firstB, int ndh, int ndw, uint32_t snap_words,
+                                              uint32_t n1, uint32_t n2, uint32_t P0, uint32_t P1, uint32_t rowmask,
+                                              uint32_t& snap1, uint32_t& snap2, uint32_t& tail_max)
+{
+    uint32_t hm[R1_LEN];
+    const uint32_t acc = sw_head2<NW, WITH_N, SINGLE>(hm, win, firstA, firstB, ndh, snap_words, n1, n2, P0, P1, rowmask, snap1, snap2);
+    tail_max = SINGLE ? 0u : sw_tail2<NW, WITH_N>(hm, win, win + (NW - 1) * 64, ndh, ndh, ndw - ndh);
+    return acc;
+}
+
+// packed half -> sw_block key
+__device__ __forceinline__ uint32_t unpk(uint32_t packed, int half)
+{
+    const uint32_t k = half ? packed >> 16 : packed & 0xFFFFu;
+    return k >= (uint32_t)ONE ? k - (uint32_t)ONE : 0u;
 }
 
 __device__ __forceinline__ uint64_t make_key(uint32_t acc, uint32_t pos)
@@ -1192,25 +1270,29 @@ __device__ __forceinline__ ClusterJob make_job(const QEnt e,
     return jb;
 }
 
-// keys of the first hit; returns the other hits of the cluster when the union beats it (they must be aligned one by one)
-// acc_h: the key over the head words (every column up to the wave's longest first window), score_t: the best score behind them;
-// of the union only the score is ever read
-__device__ __forceinline__ uint32_t finish_job(const ClusterJob& jb, bool relaxed, uint32_t acc_s, uint32_t acc_r, uint32_t acc_h, uint32_t score_t,
-                                               uint32_t n_reads, unsigned long long* __restrict__ keys)
+// keys of the first hit (strict and relaxed); -> may the union beat it on the head's columns alone (score_h > score_s)?
+// acc_h: the key over the head words (every column up to the wave's longest first window); of the union only the score is
+// ever read
+__device__ __forceinline__ bool finish_job(const ClusterJob& jb, bool relaxed, uint32_t acc_s, uint32_t acc_r, uint32_t acc_h,
+                                           uint32_t n_reads, unsigned long long* __restrict__ keys)
 {
     const uint32_t score_s = acc_s >> KEY_SHIFT;
     if (jb.active && score_s >= 17u)                                                    // barcode_callers.py:200
         atomicMax(&keys[2ull * n_reads + 2ull * jb.r + jb.strand], (unsigned long long)make_key(acc_s, (uint32_t)jb.pos));
     if (relaxed && (acc_r >> KEY_SHIFT) >= 9u)                                           // barcode_callers.py:191
         atomicMax(&keys[2ull * jb.r + jb.strand], (unsigned long long)make_key(acc_r, (uint32_t)jb.pos));
-    // Every window of the cluster lies inside the union, so no later hit scores above the union.
-    // If the union does not beat the first hit, none of them can replace it (strictly greater is
-    // required, common.py:102); otherwise align them one by one (queue C, second launch).
-    const uint32_t score_h = acc_h >> KEY_SHIFT, score_u = score_h > score_t ? score_h : score_t;
-    return (jb.active && score_u > score_s) ? (jb.mask & ~1u) : 0u;
+    return jb.active && (acc_h >> KEY_SHIFT) > score_s;
 }
 
 constexpr uint32_t REQ_CAP = 128;            // per-wave staging of re-queued hits (2 % of the clusters re-queue any)
+
+// A block's open clusters are handed to ONE of its waves (the tail wave, another one every trip), which runs the
+// score-only columns for up to TAIL_CAP of them at once: 22 cells as halfwords, laid out so that a dword read gives a lane
+// of the tail wave its two clusters packed as the head leaves them, and a word of
+//   owner thread | half << 8 | score_s << 9 | first tail word << 14 | N in the owner's wave << 18
+//   | columns behind the head << 19 | 1 << 31 (the entry is there)                        (TE_* above).
+// The window words stay where the owner put them (s_win) and are read by the owner's address.
+constexpr uint32_t TAIL_CAP = 32;
 
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __restrict__ bases, uint64_t total_rounded,
@@ -1222,15 +1304,35 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __r
                    unsigned long long* __restrict__ keys)
 {
     __shared__ uint2 s_out[4][REQ_CAP];
-    __shared__ uint32_t s_win[4][2 * (CW - 1)][64];    // the two windows of every lane but for their first words (sw_block2)
+    __shared__ uint32_t s_win[4][2 * (CW - 1)][64];    // the two windows of every lane but for their first words (sw_head2)
     __shared__ uint32_t s_cnt[NSH];
-    const uint64_t nq = queue_counts(counters, kind, 0, seg, s_cnt);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ uint16_t s_cells[R1_LEN][TAIL_CAP];     // the open clusters of this trip: cells of the head's last column,
+    __shared__ uint32_t s_meta[TAIL_CAP];              // the word described above,
+    __shared__ uint32_t s_nopen;                       // places taken (a wave that does not fit leaves its places empty),
+    __shared__ uint32_t s_res[2];                      // and the tail wave's answer: bit e >> 1 of word e & 1 for entry e
+    // Queue C holds single hits: nothing to re-queue, no tail, no open cluster - and no barrier in the loop.
+    const bool coop = kind == K_NAB;
+    for (uint32_t i = threadIdx.x; i < R1_LEN * TAIL_CAP / 2; i += 256) reinterpret_cast<uint32_t*>(&s_cells[0][0])[i] = 0u;
+    if (threadIdx.x < TAIL_CAP) s_meta[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) { s_nopen = 0u; s_res[0] = 0u; s_res[1] = 0u; }
+    const uint64_t nq_v = queue_counts(counters, kind, 0, seg, s_cnt);      // (a block barrier: the list is clear behind it)
+    const uint64_t nq = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(nq_v >> 32)) << 32)
+                        | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)nq_v);
+    // The loop below is long and short of registers.  What a lane derives from its thread number (its lane, its wave, the
+    // addresses made of them) would be computed once and then held across all of it, so each part of the loop starts from a
+    // copy of the thread number that the compiler cannot see through, and makes what it needs where it needs it.
+    auto thread_no = []() -> uint32_t { uint32_t t = threadIdx.x; asm volatile("" : "+v"(t)); return t; };
     const uint32_t shard = blockIdx.x % NSH;
     unsigned long long* const nc = ctr(counters, shard, K_NC);
     const uint64_t stride = (uint64_t)gridDim.x * 512ull;           // two clusters per lane
     uint32_t nwin = 0, nout = 0;
-    for (uint64_t base = (uint64_t)blockIdx.x * 512ull + 2ull * (threadIdx.x & ~63); base < nq; base += stride) {
+    // The loop is block-uniform: the four waves of a block make the same number of trips (a wave whose share lies behind the
+    // queue's end sees holes), so that every thread reaches both barriers of every trip.
+    uint32_t tail_wave = blockIdx.x & 3u;
+    for (uint64_t base0 = (uint64_t)blockIdx.x * 512ull; base0 < nq; base0 += stride, tail_wave = (tail_wave + 1u) & 3u) {
+        const uint32_t t1 = thread_no();
+        const int lane = (int)(t1 & 63u), wv = (int)(t1 >> 6), lane_o = lane;
+        const uint64_t base = base0 + 2ull * (t1 & ~63u);
         const ClusterJob ja = make_job(queue_fetch(q, seg, s_cnt, base + 2ull * lane, nq), off, polyt);
         const ClusterJob jb = make_job(queue_fetch(q, seg, s_cnt, base + 2ull * lane + 1, nq), off, polyt);
         nwin += (ja.active ? 1u : 0u) + (jb.active ? 1u : 0u);        // (here, not behind the alignment: the loop has no register to spare)
@@ -1242,8 +1344,8 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __r
         // lies in word d (a length of 0 has none), of the high half for the last word of its union.  n_r <= n_s <= n_u, so
         // the highest bit of each half is the wave's maximum: (max + 3) >> 2 words, as before.
         auto last_word = [](int n) -> uint32_t { return n > 0 ? 1u << ((n - 1) >> 2) : 0u; };
-        const uint32_t words = wave_or(last_word(ja.n_s) | last_word(jb.n_s) | last_word(ja.n_r) | last_word(jb.n_r)
-                                       | ((last_word(ja.n_u) | last_word(jb.n_u)) << 16));
+        const uint32_t words = wave_or_at(last_word(ja.n_s) | last_word(jb.n_s) | last_word(ja.n_r) | last_word(jb.n_r)
+                                       | ((last_word(ja.n_u) | last_word(jb.n_u)) << 16), lane_o);
         const uint32_t snap_words = words & 0xFFFFu;
         const int ndh = snap_words ? 32 - __builtin_clz(snap_words) : 0;
         const int ndw = (words >> 16) ? 32 - __builtin_clz(words >> 16) : 0;
@@ -1255,53 +1357,126 @@ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_sw_clusters(const uint8_t* __r
         __builtin_amdgcn_wave_barrier();
         uint32_t sn_s = 0, sn_r = 0;
         const uint32_t n_s2 = (uint32_t)ja.n_s | ((uint32_t)jb.n_s << 16), n_r2 = (uint32_t)ja.n_r | ((uint32_t)jb.n_r << 16);
-        uint32_t tmax = 0;
-        const uint32_t acc = anyN ? sw_block2<CW, true, false>(win, wa[0], wb[0], ndh, ndw, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r, tmax)
-                                  : sw_block2<CW, false, false>(win, wa[0], wb[0], ndh, ndw, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r, tmax);
+        uint32_t hm[R1_LEN];
+        const uint32_t acc = anyN ? sw_head2<CW, true, false>(hm, win, wa[0], wb[0], ndh, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r)
+                                  : sw_head2<CW, false, false>(hm, win, wa[0], wb[0], ndh, snap_words, n_s2, n_r2, R1_P0, R1_P1, 0xFFFFFFFFu, sn_s, sn_r);
         __builtin_amdgcn_wave_barrier();
         // (relaxed: a relaxed window is never empty, and n_r2 is in a register anyway; the two flags held across the loop
         // were the registers it had no room for)
-        uint32_t rest_a = finish_job(ja, (n_r2 & 0xFFFFu) != 0u, unpk(sn_s, 0), unpk(sn_r, 0), unpk(acc, 0), sw_tail_score(tmax, 0), n_reads, keys);
-        uint32_t rest_b = finish_job(jb, (n_r2 >> 16) != 0u, unpk(sn_s, 1), unpk(sn_r, 1), unpk(acc, 1), sw_tail_score(tmax, 1), n_reads, keys);
+        bool better_a = finish_job(ja, (n_r2 & 0xFFFFu) != 0u, unpk(sn_s, 0), unpk(sn_r, 0), unpk(acc, 0), n_reads, keys);
+        bool better_b = finish_job(jb, (n_r2 >> 16) != 0u, unpk(sn_s, 1), unpk(sn_r, 1), unpk(acc, 1), n_reads, keys);
+        if (coop) {
+            // the certificate: which clusters with other hits to re-queue does the head leave open?
+            const uint32_t score_sa = unpk(sn_s, 0) >> KEY_SHIFT, score_sb = unpk(sn_s, 1) >> KEY_SHIFT;
+            const int ext_a = ja.n_u - 4 * ndh, ext_b = jb.n_u - 4 * ndh;
+            const uint32_t B2 = tail_bound2(hm, ((uint32_t)min(max(ext_a, 0), R1_LEN) | ((uint32_t)min(max(ext_b, 0), R1_LEN) << 16)) << 10);
+            const bool open_a = !better_a && (ja.mask & ~1u) != 0u && ext_a > 0 && ((B2 & 0xFFFFu) >> 10) > score_sa;
+            const bool open_b = !better_b && (jb.mask & ~1u) != 0u && ext_b > 0 && (B2 >> 26) > score_sb;
+            const unsigned long long bal_a = __ballot(open_a), bal_b = __ballot(open_b);
+            const uint32_t n_open = (uint32_t)__popcll(bal_a) + (uint32_t)__popcll(bal_b);
+            // A place in the list for each, one reservation a wave.  A wave whose clusters do not all fit runs its tail
+            // itself and leaves its places empty: an entry counts by the mark its writer sets (bit 31), not by the counter.
+            uint32_t slot = 0;
+            bool own_tail = false;
+            if (n_open) {
+                if (lane == 0) slot = atomicAdd(&s_nopen, n_open);
+                slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
+                own_tail = slot + n_open > TAIL_CAP;
+            }
+            const uint32_t slot_a = slot + lanes_below(bal_a), slot_b = slot + (uint32_t)__popcll(bal_a) + lanes_below(bal_b);
+            if (own_tail) {
+                const uint32_t tmax = sw_tail2<CW, true>(hm, win, win + (CW - 1) * 64, ndh, ndh, ndw - ndh);
+                better_a = better_a || (open_a && sw_tail_score(tmax, 0) > score_sa);
+                better_b = better_b || (open_b && sw_tail_score(tmax, 1) > score_sb);
+            } else if (n_open) {
+                const uint32_t meta = thread_no() | ((uint32_t)ndh << TE_WORD) | (anyN ? 1u << TE_N : 0u) | (1u << 31);
+                if (open_a) {
+#pragma unroll
+                    for (int r = 0; r < R1_LEN; ++r) s_cells[r][slot_a] = (uint16_t)hm[r];
+                    s_meta[slot_a] = meta | (score_sa << TE_SCORE) | ((uint32_t)ext_a << TE_COLS);
+                }
+                if (open_b) {
+#pragma unroll
+                    for (int r = 0; r < R1_LEN; ++r) s_cells[r][slot_b] = (uint16_t)(hm[r] >> 16);
+                    s_meta[slot_b] = meta | (1u << TE_HALF) | (score_sb << TE_SCORE) | ((uint32_t)ext_b << TE_COLS);
+                }
+            }
+            __syncthreads();
+            const uint32_t t3 = thread_no();
+            if ((t3 >> 6) == tail_wave) {
+                const int lane = (int)(t3 & 63u);
+                if (s_nopen) {
+                    if (lane == 0) s_nopen = 0u;                   // (the next trip's reservations come behind the second barrier)
+                    // entries 2 * lane and 2 * lane + 1, taken off the list; a lane without one aligns 'N' from cells that
+                    // are zero or stale
+                    const uint32_t e0 = 2u * (uint32_t)lane, e1 = e0 + 1u;
+                    uint32_t m0 = 0u, m1 = 0u;
+                    if (e0 < TAIL_CAP) { m0 = s_meta[e0]; m1 = s_meta[e1]; s_meta[e0] = m0 & 0x7FFFFFFFu; s_meta[e1] = m1 & 0x7FFFFFFFu; }
+                    if ((m0 >> 31) == 0u) m0 = (uint32_t)CW << TE_WORD;         // not there: no columns, words of 'N'
+                    if ((m1 >> 31) == 0u) m1 = (uint32_t)CW << TE_WORD;
+                    uint32_t tm[R1_LEN];
+#pragma unroll
+                    for (int r = 0; r < R1_LEN; ++r) tm[r] = lane < (int)TAIL_CAP / 2 ? reinterpret_cast<const uint32_t*>(&s_cells[r][0])[lane] : 0u;
+                    const uint32_t* const wA = &s_win[(m0 >> 6) & 3u][((m0 >> TE_HALF) & 1u) * (CW - 1)][m0 & 63u];
+                    const uint32_t* const wB = &s_win[(m1 >> 6) & 3u][((m1 >> TE_HALF) & 1u) * (CW - 1)][m1 & 63u];
+                    const bool tailN = __ballot(((m0 | m1) & (1u << TE_N)) != 0u) != 0ull;
+                    const uint32_t tmax = tailN ? sw_tail_list<CW, true>(tm, wA, wB, m0, m1) : sw_tail_list<CW, false>(tm, wA, wB, m0, m1);
+                    const unsigned long long yes0 = __ballot((m0 >> 31) != 0u && sw_tail_score(tmax, 0) > ((m0 >> TE_SCORE) & 31u));
+                    const unsigned long long yes1 = __ballot((m1 >> 31) != 0u && sw_tail_score(tmax, 1) > ((m1 >> TE_SCORE) & 31u));
+                    if (lane == 0) { s_res[0] = (uint32_t)yes0; s_res[1] = (uint32_t)yes1; }
+                }
+            }
+            __syncthreads();
+            if (!own_tail) {
+                better_a = better_a || (open_a && ((s_res[slot_a & 1u] >> (slot_a >> 1)) & 1u) != 0u);
+                better_b = better_b || (open_b && ((s_res[slot_b & 1u] >> (slot_b >> 1)) & 1u) != 0u);
+            }
+        }
+        uint32_t rest_a = better_a ? (ja.mask & ~1u) : 0u;
+        uint32_t rest_b = better_b ? (jb.mask & ~1u) : 0u;
+        const uint32_t t4 = thread_no();
+        const int lane4 = (int)(t4 & 63u), wv4 = (int)(t4 >> 6);
+        const uint32_t ya = ((uint32_t)ja.pos << 1) | ja.strand, yb = ((uint32_t)jb.pos << 1) | jb.strand;      // a re-queued hit j: y + 2 * j
         if (__ballot((rest_a | rest_b) != 0)) {
             const uint32_t cnt = __popc(rest_a) + __popc(rest_b);
             uint32_t incl = cnt;
 #pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-            const uint32_t total = __shfl(incl, 63);
-            if (nout + total > REQ_CAP) stage_flush(s_out[wv], nout, lane, qc, seg, shard, nc);
+            for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute((lane4 - d) << 2, (int)incl); if (lane4 >= d) incl += o; }
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            if (nout + total > REQ_CAP) stage_flush<true>(s_out[wv4], nout, lane4, qc, seg, shard, nc);
             if (total <= REQ_CAP) {
                 uint32_t idx = nout + incl - cnt;
                 while (rest_a) {
                     const int j = __builtin_ctz(rest_a); rest_a &= rest_a - 1;
-                    s_out[wv][idx++] = make_uint2(ja.r, ((uint32_t)(ja.pos + j) << 1) | ja.strand);
+                    s_out[wv4][idx++] = make_uint2(ja.r, ya + 2u * (uint32_t)j);
                 }
                 while (rest_b) {
                     const int j = __builtin_ctz(rest_b); rest_b &= rest_b - 1;
-                    s_out[wv][idx++] = make_uint2(jb.r, ((uint32_t)(jb.pos + j) << 1) | jb.strand);
+                    s_out[wv4][idx++] = make_uint2(jb.r, yb + 2u * (uint32_t)j);
                 }
                 nout += total;
                 __builtin_amdgcn_wave_barrier();
             } else {                       // more than the staging holds (dense repeats): straight to the queue
                 unsigned long long gb = 0;
-                if (lane == 63) gb = atomicAdd(nc, (unsigned long long)total);
-                gb = __shfl(gb, 63);
+                if (lane4 == 63) gb = atomicAdd(nc, (unsigned long long)total);
+                gb = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(gb >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)gb, 63);
                 unsigned long long idx = gb + incl - cnt;
                 while (rest_a) {
                     const int j = __builtin_ctz(rest_a); rest_a &= rest_a - 1;
-                    if (idx < seg) qc[shard * seg + idx] = make_uint4(ja.r, ((uint32_t)(ja.pos + j) << 1) | ja.strand, 1u, 0u);
+                    if (idx < seg) qc[shard * seg + idx] = make_uint4(ja.r, ya + 2u * (uint32_t)j, 1u, 0u);
                     ++idx;
                 }
                 while (rest_b) {
                     const int j = __builtin_ctz(rest_b); rest_b &= rest_b - 1;
-                    if (idx < seg) qc[shard * seg + idx] = make_uint4(jb.r, ((uint32_t)(jb.pos + j) << 1) | jb.strand, 1u, 0u);
+                    if (idx < seg) qc[shard * seg + idx] = make_uint4(jb.r, yb + 2u * (uint32_t)j, 1u, 0u);
                     ++idx;
                 }
             }
         }
     }
     __builtin_amdgcn_wave_barrier();
-    stage_flush(s_out[wv], nout, lane, qc, seg, shard, nc);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    stage_flush<true>(s_out[wv], nout, lane, qc, seg, shard, nc);
     // window count (statistics only)
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) nwin += __shfl_xor(nwin, d);
