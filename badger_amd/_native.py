@@ -31,6 +31,11 @@ TSO5_MIN_SCORE_DEFAULT, TSO5_MIN_SCORE_MAX = 16, 25
 CHIMERA_DTYPE = np.dtype([("cut", "<i4"), ("hit_pos", "<i4"), ("hit_ed", "u1"), ("hit_kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
 CHIMERA_HIT = 1
 CHIMERA_MAX_ED_DEFAULT, CHIMERA_MAX_ED_MAX = 3, 6
+# bdg_split_rec: a piece of a read cut at its internal junctions (bdg_split_batch; the rule in badger_amd/chimera_split.py)
+SPLIT_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("ed", "u1"), ("kind", "u1"), ("flags", "u1"), ("reserved", "u1")])
+SPLIT_CUT = 1
+SPLIT_MAX_ED_DEFAULT, SPLIT_MAX_ED_MAX = 3, 6
+SPLIT_MARGIN, SPLIT_CELL, SPLIT_REACH = 64, 32, 2
 # bdg_rescue_rec: the barcode of a read without a usable adapter (bdg_rescue_batch; the rule in badger_amd/rescue.py)
 RESCUE_DTYPE = np.dtype([("read", "<u4"), ("entry", "<u4"), ("support", "<u4"), ("polyT", "<i4"), ("bc_start", "<i4"),
                          ("offset", "i1"), ("dist", "i1"), ("strand", "i1"), ("status", "u1"), ("umi", "S16")])
@@ -72,6 +77,7 @@ EXPORTS = [
     "bdg_write_molecules",
     "bdg_trim_batch", "bdg_trim_batch_dev", "bdg_extract_set_trim", "bdg_extract_collect_trim", "bdg_format_trimmed",
     "bdg_chimera_batch", "bdg_chimera_batch_dev", "bdg_extract_set_chimera", "bdg_extract_collect_chimera", "bdg_format_trimmed_chimera",
+    "bdg_split_batch", "bdg_split_batch_dev",
     "bdg_extract_keep_cdna", "bdg_kept_cdna", "bdg_molecule_reps_dev", "bdg_molecule_reps_set_aggregate", "bdg_format_trimmed_tags",
     "bdg_rescue_batch", "bdg_rescue_batch_dev", "bdg_extract_set_rescue", "bdg_extract_rescue_resolve", "bdg_rescue_counts",
     "bdg_consensus", "bdg_consensus_dev", "bdg_consensus_set_band",
@@ -99,6 +105,7 @@ STAGE1_WL_CORRECT = 0x200           # bdg_stage1_opts.whitelist: whitelist corre
 STAGE1_CHIMERA = 0x800              # bdg_stage1_opts.whitelist: with STAGE1_TRIM, chimeric reads are cut; chimera_max_ed is set (BDG_STAGE1_CHIMERA)
 STAGE1_TAGS = 0x1000                # bdg_stage1_opts.whitelist: with STAGE1_TRIM, the trimmed file carries stage 2's tags; the tag_* fields are set (BDG_STAGE1_TAGS)
 STAGE1_WL_RESCUE = 0x2000           # bdg_stage1_opts.whitelist: with STAGE1_WL_CORRECT, reads without a barcode are rescued; the rescue_* fields are set (BDG_STAGE1_WL_RESCUE)
+STAGE1_SPLIT = 0x4000               # bdg_stage1_opts.whitelist: chimeric reads are split into their molecules first; split_max_ed is set (BDG_STAGE1_SPLIT)
 STAGE1_TRIM = 0x400                 # bdg_stage1_opts.whitelist: trimmed reads, the fields behind the correction's are set (BDG_STAGE1_TRIM)
 # status of bdg_nearest16_correct (BDG_WLC_*) and its name in the correction file
 WLC_NONE, WLC_EXACT, WLC_CORRECTED, WLC_AMBIGUOUS, WLC_TRUNCATED = 0, 1, 2, 3, 4
@@ -136,6 +143,11 @@ class Stage1OptsTags(Stage1OptsChimera):
 class Stage1OptsRescue(Stage1OptsTags):
     """bdg_stage1_opts with the fields read only with STAGE1_WL_RESCUE"""
     _fields_ = [("rescue_max_ed", C.c_uint32), ("rescue_min_support", C.c_uint32), ("rescued_path", C.c_char_p)]
+
+
+class Stage1OptsSplit(Stage1OptsRescue):
+    """bdg_stage1_opts with the fields read only with STAGE1_SPLIT"""
+    _fields_ = [("split_max_ed", C.c_uint32), ("reserved_split", C.c_uint32)]
 
 
 class Stage1Result(C.Structure):
@@ -177,6 +189,11 @@ class Stage1ResultRescue(Stage1Result5p):
     """bdg_stage1_result with the counts written only with STAGE1_WL_RESCUE"""
     _fields_ = [("rescue_eligible", C.c_uint64), ("rescue_rescued", C.c_uint64), ("rescue_ambiguous", C.c_uint64),
                 ("rescue_truncated", C.c_uint64)]
+
+
+class Stage1ResultSplit(Stage1ResultRescue):
+    """bdg_stage1_result with the counts written only with STAGE1_SPLIT"""
+    _fields_ = [("split_reads", C.c_uint64), ("split_pieces", C.c_uint64)]
 
 
 class BadgerHipError(RuntimeError):
@@ -314,6 +331,8 @@ def load():
     L.bdg_extract_collect_chimera.argtypes = [vp, u32, vp]
     L.bdg_format_trimmed_chimera.argtypes = [C.POINTER(IngestChunk), vp, vp, vp, vp, vp, vp, u32, vp, u64, C.POINTER(u64)]
     L.bdg_format_trimmed_chimera.restype = C.c_int64
+    L.bdg_split_batch.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, C.POINTER(u64)]
+    L.bdg_split_batch_dev.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, vp]
     L.bdg_extract_keep_cdna.argtypes = [vp, C.c_int]
     L.bdg_kept_cdna.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
     L.bdg_molecule_reps_dev.argtypes = [vp, vp, vp, vp, vp, u64, vp, u32, vp, vp]
@@ -474,6 +493,33 @@ class Context:
     def chimera_batch_dev(self, d_bases, d_off, n, d_recs, d_trim, max_ed, d_out):
         """device form, behind the trim_batch_dev call that wrote d_trim (bdg_chimera_batch_dev); d_out: 12 bytes per read"""
         self._check(self.lib.bdg_chimera_batch_dev(self.h, _ptr(d_bases), _ptr(d_off), n, _ptr(d_recs), _ptr(d_trim), max_ed, _ptr(d_out)))
+
+    def split_batch(self, bases, off, max_ed=SPLIT_MAX_ED_DEFAULT, cap=None):
+        """every read cut at its internal junctions (bdg_split_batch): reads as for extract_batch -> off' uint64 [n' + 1] over the
+        same bases, SPLIT_DTYPE [n'].  cap: room for that many pieces (default: what the bases can hold at most); with more
+        pieces than cap the library's E_CAPACITY is raised, its `n_pieces` the count."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(off) - 1, 0)
+        if cap is None:
+            cap = min(n + (int(off[n] - off[0]) // SPLIT_MARGIN if n else 0), 0xFFFFFFFF)
+        off_out = np.zeros(cap + 1, dtype=np.uint64)
+        pieces = np.zeros(cap, dtype=SPLIT_DTYPE)
+        count = C.c_uint64(0)
+        rc = self.lib.bdg_split_batch(self.h, bases.ctypes.data, off.ctypes.data, n, max_ed, off_out.ctypes.data, pieces.ctypes.data,
+                                      cap, C.byref(count))
+        if rc == E_CAPACITY:
+            err = BadgerHipError(rc, "bdg_split_batch: %d pieces, room for %d" % (count.value, cap))
+            err.n_pieces = count.value
+            raise err
+        self._check(rc)
+        return off_out[:count.value + 1].copy(), pieces[:count.value].copy()
+
+    def split_batch_dev(self, d_bases, d_off, n, max_ed, d_off_out, d_pieces, cap, d_n_pieces):
+        """device form, asynchronous (bdg_split_batch_dev): d_off_out 8 bytes per piece and 8 more, d_pieces 12 bytes per piece,
+        d_n_pieces 8 bytes"""
+        self._check(self.lib.bdg_split_batch_dev(self.h, _ptr(d_bases), _ptr(d_off), n, max_ed, _ptr(d_off_out), _ptr(d_pieces), cap,
+                                                 _ptr(d_n_pieces)))
 
     def extract_set_chimera(self, on=True, max_ed=CHIMERA_MAX_ED_DEFAULT):
         """while on (and the trim is on), extract_submit queues the chunk's chimera search behind its trim"""
@@ -921,7 +967,7 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
                chunk_reads=0, segment_bytes=0, format_threads=0, whitelist=False, max_bc_dist=2, bc_candidates=0,
                corrected_path=None, bc_edit_bits=5, bc_min_permille=975, trimmed_path=None, tso_min_score=TSO_MIN_SCORE_DEFAULT,
                chimera_max_ed=None, tags=None, tso5_max_ed=None, rescued_path=None, rescue_max_ed=RESCUE_MAX_ED_DEFAULT,
-               rescue_min_support=RESCUE_MIN_SUPPORT_DEFAULT):
+               rescue_min_support=RESCUE_MIN_SUPPORT_DEFAULT, split_max_ed=None):
     """bdg_stage1_run: input file -> TSV in native threads over the given contexts.  Returns the Stage1Result; raises what
     the reference raises: KeyError for a base outside ACGTN, ValueError for a malformed file, TypeError for a record
     without a sequence.  whitelist=True: every context holds the list (Context.whitelist_load) and the rows get the three
@@ -936,7 +982,9 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     tso5_max_ed (with trimmed_path; the caller has put every context into LAYOUT_5P): the switch oligo's edit bound of the 5'
     trimming rule; the result is then a Stage1Result5p whatever else is asked for, and has trimmed_no_anchor.  rescued_path (with
     corrected_path): reads without a barcode are rescued against the run's support (BDG_STAGE1_WL_RESCUE) into that file; the result
-    is then a Stage1ResultRescue and has rescue_eligible, rescue_rescued, rescue_ambiguous and rescue_truncated."""
+    is then a Stage1ResultRescue and has rescue_eligible, rescue_rescued, rescue_ambiguous and rescue_truncated.  split_max_ed (with
+    anything else, 3' layouts only): every read is first cut into its molecules (BDG_STAGE1_SPLIT) and each piece goes through the
+    run as a read of its own; the result is then a Stage1ResultSplit and has split_reads and split_pieces."""
     L = load()
     arr = (C.c_void_p * len(contexts))(*[c.h for c in contexts])
     correct = whitelist and corrected_path is not None
@@ -949,6 +997,8 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
         wl_mode |= STAGE1_TAGS                      # (without a trimmed_path the library says E_ARG)
     if rescued_path is not None:
         wl_mode |= STAGE1_WL_RESCUE                 # (without the correction the library says E_ARG)
+    if split_max_ed is not None:
+        wl_mode |= STAGE1_SPLIT
     held = [None] * 5
     if tags is not None:
         held = [np.ascontiguousarray(tags["cell_rank"], dtype=np.uint32), np.ascontiguousarray(tags["cell_has"], dtype=np.uint8)]
@@ -961,13 +1011,15 @@ def stage1_run(contexts, in_path, out_path, header, umi_len, threads=0, header_e
     # own class, so the third field of one subclass (rescued_path) would take the place of another's (corrected_path)
     c_path, t_path, r_path = [os.fsencode(x) if on else None for x, on in
                               ((corrected_path, correct), (trimmed_path, trimmed_path is not None), (rescued_path, rescued_path is not None))]
-    o = Stage1OptsRescue(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
+    o = Stage1OptsSplit(umi_len, threads, format_threads, header_every, chunk_reads, 1 if skip_secondary else 0, segment_bytes,
                          wl_mode, max_bc_dist, bc_candidates, bc_edit_bits, bc_min_permille, c_path, t_path,
                          tso_min_score, tso5_max_ed or 0, chimera_max_ed or 0, 0,
                          *[a.ctypes.data if a is not None and len(a) else None for a in held], len(held[0]) if tags is not None else 0,
-                         rescue_max_ed, rescue_min_support, r_path)
+                         rescue_max_ed, rescue_min_support, r_path, split_max_ed or 0, 0)
     # the result is as short as the flags allow: the library writes a feature's counts only under its bit
-    if rescued_path is not None:
+    if split_max_ed is not None:
+        res = Stage1ResultSplit()
+    elif rescued_path is not None:
         res = Stage1ResultRescue()
     elif tso5_max_ed is not None and trimmed_path is not None:
         res = Stage1Result5p()
@@ -1032,12 +1084,18 @@ class IdStore:
             pass
 
 
-def stage1_collect(ctx, in_path, umi_len, ids, threads=0, skip_secondary=False, chunk_reads=0, segment_bytes=0):
+def stage1_collect(ctx, in_path, umi_len, ids, threads=0, skip_secondary=False, chunk_reads=0, segment_bytes=0, split_max_ed=None):
     """bdg_stage1_collect: every read of the file through the context (records stay on the device if it keeps them), the
-    read ids into the IdStore.  Raises like stage1_run."""
+    read ids into the IdStore.  split_max_ed: the reads are cut into their molecules first, as stage1_run cuts them; the result
+    is then a Stage1ResultSplit.  Raises like stage1_run."""
     L = load()
-    o = Stage1Opts(umi_len, threads, 0, 0, chunk_reads, 1 if skip_secondary else 0, segment_bytes)
-    res = Stage1Result()
+    if split_max_ed is None:
+        o = Stage1Opts(umi_len, threads, 0, 0, chunk_reads, 1 if skip_secondary else 0, segment_bytes)
+        res = Stage1Result()
+    else:
+        o = Stage1OptsSplit(umi_len, threads, 0, 0, chunk_reads, 1 if skip_secondary else 0, segment_bytes, STAGE1_SPLIT)
+        o.split_max_ed = split_max_ed
+        res = Stage1ResultSplit()
     rc = L.bdg_stage1_collect(ctx.h, os.fsencode(in_path), C.byref(o), ids.h, C.byref(res))
     if rc != 0:
         _raise_like_reference(rc, L.bdg_last_error(ctx.h).decode())

@@ -10,6 +10,10 @@
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
 
+--chimera_split [--split_max_ed E] (read input only) cuts every read that holds several library molecules into its molecules
+before anything else looks at it, in both passes over the input (stage 1's --chimera_split): cells, molecules, tags and consensus
+count pieces.
+
 --tagged_reads PATH (read input only) writes what stage 1's --trimmed_reads [--chimera_cut] writes, for the reads this stage gave a
 cell: the trimmed cDNA with the corrected barcode as CB and, with --umi_dedup, the molecule as UB and its read count as RN in the
 header.  The input is read a second time for it (the extraction costs under a millisecond per million reads; no bases are kept).
@@ -38,7 +42,7 @@ from traceback import print_exc
 from . import _native
 from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
-from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
+from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
 
 logger = logging.getLogger("BarcodeGraph")
@@ -92,6 +96,12 @@ def parse_args(args):
     p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
                    help="--chimera_cut: edits allowed in the adapter, 0 .. %d (default %d)"
                         % (_native.CHIMERA_MAX_ED_MAX, _native.CHIMERA_MAX_ED_DEFAULT))
+    p.add_argument("--chimera_split", action="store_true", default=False,
+                   help="read input: split a read that holds several library molecules ligated end to end into its molecules, each a "
+                        "read of its own from there on, in both passes (stage 1's --chimera_split); 3' modes only")
+    p.add_argument("--split_max_ed", type=_split_max_ed, default=None, metavar="E",
+                   help="--chimera_split: edits allowed in the adapter, 0 .. %d (default %d)"
+                        % (_native.SPLIT_MAX_ED_MAX, _native.SPLIT_MAX_ED_DEFAULT))
     p.add_argument("--molecule_reads", action="store_true", default=False,
                    help="--tagged_reads with --umi_dedup: write one read per molecule, the one with the longest cDNA (the earliest "
                         "at equal lengths)")
@@ -111,6 +121,10 @@ def parse_args(args):
         p.error("--chimera_cut needs --tagged_reads")
     if a.chimera_max_ed is not None and not a.chimera_cut:
         p.error("--chimera_max_ed needs --chimera_cut")
+    if a.chimera_split and a.reads.endswith("tsv"):
+        p.error("--chimera_split needs read input (FASTA, FASTQ, SAM or BAM): the rows of a stage-1 TSV are pieces already, if "
+                "stage 1 ran with --chimera_split")
+    check_split_args(p, a.data_type, a.chimera_split, a.split_max_ed)
     if a.molecule_reads and not (a.umi_dedup and a.tagged_reads):
         p.error("--molecule_reads needs --umi_dedup and --tagged_reads")
     if a.molecule_consensus and not (a.umi_dedup and a.tagged_reads):
@@ -225,7 +239,10 @@ def from_reads(args, ctx, bc_len, mark):
         logger.info("Extracting from " + args.reads)
         # (-tr 1 is one sequential reader, compressed input as one gzip stream - the reference's single-thread shape,
         # as extract_raw_barcodes.process_single_thread asks for it)
-        _native.stage1_collect(ctx, args.reads, detector.UMI_LEN_10X, read_ids, threads=args.threads, skip_secondary=args.threads != 1)
+        res = _native.stage1_collect(ctx, args.reads, detector.UMI_LEN_10X, read_ids, threads=args.threads, skip_secondary=args.threads != 1,
+                                     **split_kwargs(args))
+    if args.chimera_split:
+        logger.info("Split reads: %d reads cut into %d pieces" % (res.split_reads, res.split_pieces))
     mark("extract")
     logger.info("Finished barcode extraction")
     logger.info("Initializing Graph")
@@ -237,7 +254,7 @@ def write_tagged_reads(args, detector, tags):
     with contexts_in_layout([detector], args.tso5_max_ed) as ctxs:
         res = _native.stage1_run(ctxs, args.reads, None, "", detector.UMI_LEN_10X, threads=args.threads,
                                  skip_secondary=args.threads != 1, trimmed_path=args.tagged_reads, tso_min_score=args.tso_min_score,
-                                 chimera_max_ed=args.chimera_max_ed, tags=tags, tso5_max_ed=args.tso5_max_ed)
+                                 chimera_max_ed=args.chimera_max_ed, tags=tags, tso5_max_ed=args.tso5_max_ed, **split_kwargs(args))
     logger.info("Tagged reads: %d to %s, %d bases; left out: %d without a cell, %d not their molecule's read"
                 % (res.trimmed_reads, args.tagged_reads, res.trimmed_bases, res.tags_no_cell, res.tags_not_kept))
 

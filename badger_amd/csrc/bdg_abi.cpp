@@ -275,7 +275,7 @@ void bdg_free(bdg_ctx* ctx)
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
     if (ctx->ev_scan) (void)hipEventDestroy(ctx->ev_scan);
     for (hipEvent_t e : ctx->ev_aux) if (e) (void)hipEventDestroy(e);
-    for (auto& sl : ctx->slots) for (hipEvent_t e : { sl.done, sl.match_done }) if (e) (void)hipEventDestroy(e);
+    for (auto& sl : ctx->slots) for (hipEvent_t e : { sl.done, sl.match_done, sl.split_done }) if (e) (void)hipEventDestroy(e);
     for (auto& t : ctx->timers) for (auto& pr : t.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -525,6 +525,53 @@ int bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     if ((rc = bdg_chimera_launch(ctx, S.d_bases, S.d_off, L.recs, L.trim, n, max_ed, L.chim))) return rc;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(out, L.chim, sizeof(bdg_chimera_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
+    return BDG_OK;
+}
+
+// ---- chimeric reads cut into their molecules ---------------------------------------
+int bdg_split_batch_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t max_ed,
+                        uint64_t* d_off_out, bdg_split_rec* d_pieces, uint32_t cap, uint64_t* d_n_pieces)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_split(ctx, max_ed)) return rcs;
+    if (!d_n_pieces || (n && (!d_bases || !d_off || !d_off_out || !d_pieces))) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_pieces) & 3u) || ((reinterpret_cast<uintptr_t>(d_n_pieces) | reinterpret_cast<uintptr_t>(d_off) | reinterpret_cast<uintptr_t>(d_off_out)) & 7u))
+        return bdg_fail(ctx, BDG_E_ARG, "d_pieces must be 4-byte, d_off, d_off_out and d_n_pieces 8-byte aligned");
+    if (cap < n) return bdg_fail(ctx, BDG_E_ARG, "cap is smaller than the number of reads");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return bdg_split_launch(ctx, d_bases, d_off, n, max_ed, ~0ull, d_off_out, d_pieces, cap, d_n_pieces);
+}
+
+// s_out0 of bdg_split_batch for room for cap pieces: the count (one line) | off' u64 [cap + 1] | pieces [cap]
+int bdg_split_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t max_ed,
+                    uint64_t* off_out, bdg_split_rec* pieces, uint32_t cap, uint64_t* n_pieces)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rcs = check_split(ctx, max_ed)) return rcs;
+    if (!n_pieces) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    *n_pieces = 0;
+    if (n == 0) { if (off && off_out) off_out[0] = off[0]; return BDG_OK; }
+    if (!bases || !off || !off_out || !pieces) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (cap < n) return bdg_fail(ctx, BDG_E_ARG, "cap is smaller than the number of reads");
+    StagedReads S;
+    int rc;
+    const size_t off_at = 256, pc_at = off_at + sizeof(uint64_t) * ((size_t)cap + 1);
+    if ((rc = stage_reads(ctx, bases, off, n, pc_at + sizeof(bdg_split_rec) * (size_t)cap, S))) return rc;
+    hipStream_t st = ctx->stream;
+    char* const d = static_cast<char*>(S.d_out);
+    uint64_t* const d_count = reinterpret_cast<uint64_t*>(d);
+    uint64_t* const d_off_out = reinterpret_cast<uint64_t*>(d + off_at);
+    // (a boundary needs BDG_SPLIT_MARGIN bases on either side: what the staging list can be asked to hold)
+    if ((rc = bdg_split_launch(ctx, S.d_bases, S.d_off, n, max_ed, S.total / BDG_SPLIT_MARGIN + 1, d_off_out,
+                               reinterpret_cast<bdg_split_rec*>(d + pc_at), cap, d_count))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_pieces, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (*n_pieces > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "more pieces than cap (see *n_pieces)");
+    const size_t np = (size_t)*n_pieces;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(off_out, d_off_out, sizeof(uint64_t) * (np + 1), hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(pieces, d + pc_at, sizeof(bdg_split_rec) * np, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                 // (rel and the caller's buffers may go now)
+    for (size_t p = 0; p <= np; ++p) off_out[p] += off[0];      // (the staged offsets are rebased to 0)
     return BDG_OK;
 }
 

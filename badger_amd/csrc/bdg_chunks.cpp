@@ -141,10 +141,26 @@ int bdg_rescue_finish(bdg_ctx* ctx, const uint32_t* d_support, uint32_t max_ed, 
     return BDG_OK;
 }
 
+// split_layout: Slot::split for room for cap pieces: the count (one line) | off' u64 [cap + 1] | pieces [cap]
+struct SplitLayout { uint64_t* count; uint64_t* off; bdg_split_rec* pieces; size_t bytes; };
+static SplitLayout split_layout(void* base, size_t cap)
+{
+    char* const b = static_cast<char*>(base);                                // (base may be null: the size alone is asked for)
+    const size_t off_at = 256, pc_at = off_at + sizeof(uint64_t) * (cap + 1);
+    return SplitLayout{ reinterpret_cast<uint64_t*>(b), reinterpret_cast<uint64_t*>(b + off_at), reinterpret_cast<bdg_split_rec*>(b + pc_at),
+                        pc_at + sizeof(bdg_split_rec) * cap };
+}
+
+// the offsets a slot's kernels read: the chunk's own, or the pieces' that bdg_slot_split_submit made of them
+static const uint64_t* slot_off(const bdg_ctx::Slot& sl)
+{
+    return sl.split_on ? split_layout(sl.split.p, sl.split_cap).off : static_cast<const uint64_t*>(sl.d_off.p);
+}
+
 static int slot_enqueue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
 {
     const uint8_t* const d_bases = static_cast<const uint8_t*>(sl.d_bases.p);
-    const uint64_t* const d_off = static_cast<const uint64_t*>(sl.d_off.p);
+    const uint64_t* const d_off = slot_off(sl);
     bdg_extract_rec* const d_recs = static_cast<bdg_extract_rec*>(sl.recs.d.p);
     bdg_trim_rec* const d_trim = static_cast<bdg_trim_rec*>(sl.trim.d.p);
     const size_t n = sl.n;
@@ -289,34 +305,49 @@ extern "C" {
 void bdg_submit_times(double t[5]) { for (int i = 0; i < 5; ++i) t[i] = g_submit_t[i].load(); }
 
 // ---- submit / collect -----------------------------------------------------------
-int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len)
+// The steps of a submit.  bdg_extract_submit runs them in one go; bdg_slot_split_submit puts the split between the chunk's
+// copies and everything that counts reads, which then counts pieces.
+// begin: what the chunk is submitted with
+static int submit_begin(bdg_ctx* ctx, bdg_ctx::Slot& sl, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len)
 {
-    const double T0 = now_s();
-    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
-    bdg_ctx::Slot& sl = ctx->slots[slot];
     if (sl.busy) return bdg_fail(ctx, BDG_E_ARG, "slot still in flight: collect it first");
     if (n && (!bases || !off)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
-    sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false;
+    sl.n = n; sl.umi_len = umi_len; sl.total = 0; sl.reran = false; sl.match_queued = false; sl.split_on = false;
     sl.layout = ctx->x_layout; sl.tso5_max_ed = ctx->trim5p_max_ed;
     sl.trim_on = ctx->trim_on; sl.trim_min_score = ctx->trim_min_score;
     sl.chim_on = ctx->trim_on && ctx->chim_on; sl.chim_max_ed = ctx->chim_max_ed;
     sl.resc_on = ctx->resc.on && sl.layout == BDG_LAYOUT_3P;             // (no read of the 5' layout is eligible)
-    if (n == 0) { sl.busy = true; return BDG_OK; }
-    if (sl.resc_on) {
-        if (int rcr = bdg_rescue_check(ctx, umi_len, 0)) return rcr;
-        if (ctx->resc.umi_len && ctx->resc.umi_len != umi_len) return bdg_fail(ctx, BDG_E_ARG, "the rescue store holds reads of another umi_len");
-        if (ctx->resc.ord + n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads in one rescue store");
-    }
+    return BDG_OK;
+}
+
+// what the rescue store asks of a chunk of n reads
+static int submit_check_rescue(bdg_ctx* ctx, const bdg_ctx::Slot& sl, uint32_t n, uint32_t umi_len)
+{
+    if (!sl.resc_on) return BDG_OK;
+    if (int rcr = bdg_rescue_check(ctx, umi_len, 0)) return rcr;
+    if (ctx->resc.umi_len && ctx->resc.umi_len != umi_len) return bdg_fail(ctx, BDG_E_ARG, "the rescue store holds reads of another umi_len");
+    if (ctx->resc.ord + n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads in one rescue store");
+    return BDG_OK;
+}
+
+// room for the chunk's bases and offsets on the device
+static int submit_reserve_input(bdg_ctx* ctx, bdg_ctx::Slot& sl, const uint64_t* off, uint32_t n)
+{
     if (int rco = bdg_check_offsets(ctx, off, n)) return rco;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t lo = off[0], total = off[n] - lo;
-    sl.total = total;
+    sl.total = off[n] - off[0];
     const size_t off_bytes = sizeof(uint64_t) * ((size_t)n + 1);
     int rc;
-    if ((rc = bdg_reserve(ctx, sl.d_bases, total + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, sl.d_bases, sl.total + 64))) return rc;
     if ((rc = bdg_reserve(ctx, sl.d_off, off_bytes))) return rc;
-    if ((rc = pinned_reserve(ctx, sl.h_off, off_bytes))) return rc;
+    return pinned_reserve(ctx, sl.h_off, off_bytes);
+}
+
+// room for the results of the n reads the kernels will see
+static int submit_reserve_results(bdg_ctx* ctx, bdg_ctx::Slot& sl, uint32_t n)
+{
+    int rc;
     if ((rc = pinned_reserve(ctx, sl.h_counters, bdg_extract_counter_bytes()))) return rc;
     if ((rc = mirror_reserve(ctx, sl.recs, sizeof(bdg_extract_rec) * (size_t)n))) return rc;
     if (sl.trim_on && (rc = mirror_reserve(ctx, sl.trim, sizeof(bdg_trim_rec) * (size_t)n))) return rc;
@@ -330,21 +361,105 @@ int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const 
         sl.resc_ord0 = (uint32_t)ctx->resc.ord;                          // (the store's count moves on once the chunk is queued)
     }
     if (!sl.done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    const double T1 = now_s();
+    return BDG_OK;
+}
+
+// the offsets rebased to 0, and both copies queued
+static int submit_copy_input(bdg_ctx* ctx, bdg_ctx::Slot& sl, const uint8_t* bases, const uint64_t* off, uint32_t n, double* t_rel)
+{
+    const uint64_t lo = off[0];
     uint64_t* rel = static_cast<uint64_t*>(sl.h_off.p);
     for (uint32_t i = 0; i <= n; ++i) rel[i] = off[i] - lo;
     hipStream_t st = ctx->stream;
-    const double T2 = now_s();
+    *t_rel = now_s();
     // (one copy on one stream runs at the link's rate here: 56.6 GB/s for 32 MB from pinned memory, tools/hip_first_calls.py; two
     // halves on two streams, which gained 10 % in round 2, gain nothing any more)
-    if (total) BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_bases.p, bases + lo, total, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_off.p, rel, off_bytes, hipMemcpyHostToDevice, st));
-    const double T3 = now_s();
-    if ((rc = slot_enqueue(ctx, sl))) return rc;
+    if (sl.total) BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_bases.p, bases + lo, sl.total, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(sl.d_off.p, rel, sizeof(uint64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    return BDG_OK;
+}
+
+// the kernels and the copies of their results queued: the slot is in flight
+static int submit_queue(bdg_ctx* ctx, bdg_ctx::Slot& sl)
+{
+    if (int rc = slot_enqueue(ctx, sl)) return rc;
     sl.busy = true;
-    if (sl.resc_on) { ctx->resc.ord += n; ctx->resc.umi_len = umi_len; }  // (a submit that failed leaves the ordinals where they were)
+    if (sl.resc_on) { ctx->resc.ord += sl.n; ctx->resc.umi_len = sl.umi_len; }  // (a submit that failed leaves the ordinals where they were)
+    return BDG_OK;
+}
+
+int bdg_extract_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len)
+{
+    const double T0 = now_s();
+    if (!ctx || slot >= BDG_SLOTS) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    int rc;
+    if ((rc = submit_begin(ctx, sl, bases, off, n, umi_len))) return rc;
+    if (n == 0) { sl.busy = true; return BDG_OK; }
+    if ((rc = submit_check_rescue(ctx, sl, n, umi_len))) return rc;
+    if ((rc = submit_reserve_input(ctx, sl, off, n))) return rc;
+    if ((rc = submit_reserve_results(ctx, sl, n))) return rc;
+    const double T1 = now_s();
+    double T2;
+    if ((rc = submit_copy_input(ctx, sl, bases, off, n, &T2))) return rc;
+    const double T3 = now_s();
+    if ((rc = submit_queue(ctx, sl))) return rc;
     const double T4 = now_s();
     if (g_submit_debug) { submit_add(0, T1 - T0); submit_add(1, T2 - T1); submit_add(2, T3 - T2); submit_add(3, T4 - T3); submit_add(4, 1.0); }
+    return BDG_OK;
+}
+
+// bdg_extract_submit with the chunk's reads cut into their molecules first (bdg_split_batch's rule at max_ed; bdg_stage1_run
+// with BDG_STAGE1_SPLIT).  The bases cross the link once: copy and split are queued, the piece count and the piece records come
+// back through the slot's pinned memory behind an event, then the chunk's kernels are queued on the resident bases with the
+// pieces' offsets, which never leave the device.  From here on the slot holds *n_pieces reads: collect them as such.  *pieces
+// (the slot's memory) stays valid until the slot is submitted to again.
+int bdg_slot_split_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len,
+                          uint32_t max_ed, uint32_t* n_pieces, const bdg_split_rec** pieces)
+{
+    if (!ctx || slot >= BDG_SLOTS || !n_pieces || !pieces) return BDG_E_ARG;
+    bdg_ctx::Slot& sl = ctx->slots[slot];
+    *n_pieces = 0; *pieces = nullptr;
+    int rc;
+    if ((rc = check_split(ctx, max_ed))) return rc;
+    if ((rc = submit_begin(ctx, sl, bases, off, n, umi_len))) return rc;
+    if (n == 0) { sl.busy = true; return BDG_OK; }
+    if ((rc = submit_reserve_input(ctx, sl, off, n))) return rc;
+    // a boundary needs BDG_SPLIT_MARGIN bases on either side: the pieces cannot outnumber this.  The host takes the count and,
+    // with it, as many records as a chunk with one read in eight cut once holds; the rare chunk with more fetches the rest
+    const uint64_t max_bounds = sl.total / BDG_SPLIT_MARGIN + 1, cap = n + max_bounds;
+    if (cap > 0xFFFFFFFFull) return bdg_fail(ctx, BDG_E_ARG, "a chunk of more than 2^32 - 1 pieces");
+    const size_t first = (size_t)std::min<uint64_t>(cap, (uint64_t)n + n / 8 + 1024);
+    if ((rc = bdg_reserve(ctx, sl.split, split_layout(nullptr, cap).bytes))) return rc;
+    sl.split_cap = cap;
+    if ((rc = pinned_reserve(ctx, sl.h_split, 16 + sizeof(bdg_split_rec) * first))) return rc;
+    if (!sl.split_done) BDG_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.split_done, hipEventDisableTiming));
+    double t_rel;
+    if ((rc = submit_copy_input(ctx, sl, bases, off, n, &t_rel))) return rc;
+    const SplitLayout S = split_layout(sl.split.p, cap);
+    hipStream_t st = ctx->stream;
+    if ((rc = bdg_split_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p), n, max_ed, max_bounds,
+                               S.off, S.pieces, (uint32_t)cap, S.count))) return rc;
+    char* const h = static_cast<char*>(sl.h_split.p);
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(h, S.count, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(h + 16, S.pieces, sizeof(bdg_split_rec) * first, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipEventRecord(sl.split_done, st));
+    BDG_HIP_TRY(ctx, hipEventSynchronize(sl.split_done));
+    const uint64_t np = *reinterpret_cast<const uint64_t*>(h);
+    if (np < n || np > cap) return bdg_fail(ctx, BDG_E_HIP, "the split reports a piece count outside its bounds");
+    if (np > first) {
+        // the rest of the records, while the stream holds nothing but the split: no kernel of the chunk is waited for
+        if ((rc = pinned_reserve(ctx, sl.h_split, 16 + sizeof(bdg_split_rec) * (size_t)np))) return rc;
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<char*>(sl.h_split.p) + 16, S.pieces, sizeof(bdg_split_rec) * (size_t)np, hipMemcpyDeviceToHost, st));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    // the second half: everything that counts reads counts pieces
+    sl.n = (uint32_t)np; sl.split_on = true;
+    if ((rc = submit_check_rescue(ctx, sl, sl.n, umi_len))) return rc;
+    if ((rc = submit_reserve_results(ctx, sl, sl.n))) return rc;
+    if ((rc = submit_queue(ctx, sl))) return rc;
+    *n_pieces = sl.n;
+    *pieces = reinterpret_cast<const bdg_split_rec*>(static_cast<const char*>(sl.h_split.p) + 16);
     return BDG_OK;
 }
 
@@ -380,7 +495,7 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
         if (ctx->kept_umis.on) {
             // the chunk's UMIs, packed from its bases while they are still here
             if ((rc = kept_append(ctx, ctx->kept_umis, 4, sl.n, size_t(8) << 20, &at))) return rc;
-            if ((rc = bdg_umi_pack_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), static_cast<const uint64_t*>(sl.d_off.p), d_recs, sl.n,
+            if ((rc = bdg_umi_pack_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), slot_off(sl), d_recs, sl.n,
                                           static_cast<uint32_t*>(at))))
                 return rc;
             ctx->kept_umis.n += sl.n;

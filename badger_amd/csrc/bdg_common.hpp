@@ -100,6 +100,11 @@ struct bdg_ctx {
         // rescue windows of the chunk (bdg_extract_set_rescue): behind the extraction, into the context's store
         bool resc_on = false; uint32_t resc_ord0 = 0;        // what the chunk was submitted with: its first read's ordinal
         PinnedBuf h_resc;                                    // the store's counter behind the chunk (u32)
+        // the chunk's reads cut into pieces first (bdg_slot_split_submit): n counts pieces, the kernels read the pieces' offsets
+        bool split_on = false;
+        DevBuf split; uint64_t split_cap = 0;                // split_layout(split_cap) in bdg_chunks.cpp: count | off' | pieces
+        PinnedBuf h_split;                                   // the count (16 bytes), then the piece records
+        hipEvent_t split_done = nullptr;
     } slots[BDG_SLOTS];
     // ---- whitelist correction of a stage-1 run (correct_kernels.hip, bdg_stage1_run with BDG_STAGE1_WL_CORRECT)
     struct Correct {
@@ -131,6 +136,8 @@ struct bdg_ctx {
                          // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
     // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call
+    // ---- chimera split (split_kernels.hip): grow-only, reused by every call
+    DevBuf sp_ws;        // counter | staged boundaries, 16 bytes each | piece count u32 per read | the scan's block sums
     DevBuf c_meta;       // group of every sequence u32 | counter offset of every group u64
     DevBuf c_cnt;        // vote counters, 8 bytes per backbone position of the call
     DevBuf c_trace;      // direction bits, 16 * c_band / 64 bytes per member row and wave in flight
@@ -196,6 +203,9 @@ extern "C" void bdg_submit_times(double t[5]);   // where bdg_extract_submit's t
 extern "C" int bdg_slot_match_topk(bdg_ctx* ctx, uint32_t slot, uint32_t max_ed, uint32_t k);
 extern "C" int bdg_slot_match_collect_topk(bdg_ctx* ctx, uint32_t slot, uint32_t* best_idx, uint8_t* best_ed, uint16_t* n_ties,
                                            uint32_t* cand_idx, uint8_t* cand_ed);
+// bdg_extract_submit behind a split of the chunk's reads into pieces (bdg_chunks.cpp; bdg_stage1_run with BDG_STAGE1_SPLIT)
+extern "C" int bdg_slot_split_submit(bdg_ctx* ctx, uint32_t slot, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t umi_len,
+                                     uint32_t max_ed, uint32_t* n_pieces, const bdg_split_rec** pieces);
 // Whitelist correction over a run of slot matches (bdg_chunks.cpp): begin (on) clears the support array and the kept lists and makes
 // every later bdg_slot_match_topk of the context a k = 8 match whose lists stay on the device, plus a support kernel; the host
 // still gets k slots.  support_to_host / support_from_host: the context's support array, to be summed over the contexts of a run.

@@ -54,6 +54,8 @@ int bdg_layout5p_launch(bdg_ctx*, const uint64_t*, uint32_t, uint32_t, bdg_extra
 int bdg_trim5p_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, uint32_t, uint32_t, bdg_trim_rec*);
 // chimera_kernels.hip
 int bdg_chimera_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, const bdg_trim_rec*, uint32_t, uint32_t, bdg_chimera_rec*);
+// split_kernels.hip (max_bounds: what the caller knows the boundaries cannot exceed; it only limits the staging list)
+int bdg_split_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint32_t, uint64_t max_bounds, uint64_t*, bdg_split_rec*, uint32_t, uint64_t*);
 // rescue_kernels.hip
 int bdg_rescue_windows_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, const int32_t* polyt, uint32_t umi_len,
                               uint32_t ord0, const RescStore&, uint64_t cap, uint32_t* counters);
@@ -117,4 +119,12 @@ static inline int bdg_trim_launch_layout(bdg_ctx* ctx, const uint8_t* d_bases, c
 static inline int check_chimera_max_ed(bdg_ctx* ctx, uint32_t v)
 {
     return v > BDG_CHIMERA_MAX_ED_MAX ? bdg_fail(ctx, BDG_E_ARG, "chimera max_ed out of range (0 .. 6)") : BDG_OK;
+}
+
+// the split's bound and layout: 3' only (the 5' kits end in a primer the patterns do not hold)
+static inline int check_split(bdg_ctx* ctx, uint32_t max_ed)
+{
+    if (max_ed > BDG_SPLIT_MAX_ED_MAX) return bdg_fail(ctx, BDG_E_ARG, "split max_ed out of range (0 .. 6)");
+    if (ctx->x_layout == BDG_LAYOUT_5P) return bdg_fail(ctx, BDG_E_ARG, "the chimera split knows the 3' layouts only (BDG_LAYOUT_3P)");
+    return BDG_OK;
 }

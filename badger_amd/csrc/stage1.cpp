@@ -28,8 +28,46 @@ namespace {
 template <class F> struct Guard { F f; bool armed; void run() { if (armed) f(); armed = false; } ~Guard() { run(); } };
 template <class F> Guard(F, bool) -> Guard<F>;
 
-// one chunk on its way through a GPU: its place in the input, the reader's view of it, the context and slot it runs on
-struct Fly { uint64_t seq = 0, g0 = 0; bdg_ingest_chunk ch; bdg_ctx* ctx = nullptr; uint32_t slot = 0; };
+// BDG_STAGE1_SPLIT: a chunk's reads cut into pieces.  The pieces tile the reads, so the view is the reader's chunk with other
+// offsets into the same bases, more reads, and ids rebuilt; whoever holds the chunk holds the view, and it goes when they go
+struct SplitView {
+    std::vector<uint64_t> off, id_off;          // n' + 1 each
+    std::vector<char> ids;
+    std::vector<uint32_t> read;                 // the input read of every piece, counted inside the chunk
+};
+
+// one chunk on its way through a GPU: its place in the input, the reader's view of it (with `view`: the pieces' view, which
+// g0 and ch.n then count), the context and slot it runs on; in0: the input reads in front of the chunk
+struct Fly { uint64_t seq = 0, g0 = 0, in0 = 0; bdg_ingest_chunk ch; bdg_ctx* ctx = nullptr; uint32_t slot = 0; std::shared_ptr<const SplitView> view; };
+
+// the view of chunk `ch` under its piece records: off' = off[read] + start; a read with one piece keeps its id, piece k (1-based) of
+// a read with more gets "/k" behind the id's first word (the text before the first blank or tab)
+std::shared_ptr<const SplitView> make_view(bdg_ingest_chunk& ch, const bdg_split_rec* pieces, uint32_t np)
+{
+    auto v = std::make_shared<SplitView>();
+    v->off.resize((size_t)np + 1); v->id_off.resize((size_t)np + 1); v->read.resize(np);
+    v->ids.reserve((size_t)(ch.id_off[ch.n] - ch.id_off[0]) + 64);
+    char num[16];
+    for (uint32_t p = 0, k = 0; p < np; ++p) {
+        const uint32_t r = pieces[p].read;
+        v->off[p] = ch.off[r] + pieces[p].start; v->read[p] = r;
+        v->id_off[p] = v->ids.size();
+        const char* id = ch.ids + ch.id_off[r];
+        const size_t len = (size_t)(ch.id_off[r + 1] - ch.id_off[r]);
+        const bool more = (p + 1 < np && pieces[p + 1].read == r) || (p && pieces[p - 1].read == r);
+        k = p && pieces[p - 1].read == r ? k + 1 : 1;
+        if (!more) { v->ids.insert(v->ids.end(), id, id + len); continue; }
+        size_t w = 0;
+        while (w < len && id[w] != ' ' && id[w] != '\t') ++w;
+        v->ids.insert(v->ids.end(), id, id + w);
+        const int m = snprintf(num, sizeof(num), "/%u", k);
+        v->ids.insert(v->ids.end(), num, num + m);
+        v->ids.insert(v->ids.end(), id + w, id + len);
+    }
+    v->off[np] = ch.off[ch.n]; v->id_off[np] = v->ids.size();
+    ch.n = np; ch.off = v->off.data(); ch.ids = v->ids.data(); ch.id_off = v->id_off.data();
+    return v;
+}
 
 // a collected chunk on its way to the formatters, with what the device said about its reads
 struct Job : Fly {
@@ -44,7 +82,7 @@ struct Job : Fly {
 // What a call of bdg_stage1_run asks for: the bits of opts->whitelist decoded and everything checked, once
 struct Stage1Plan {
     // BDG_STAGE1_TRIM shares the field with the whitelist's mode but needs no whitelist: `wl_on` is what o->whitelist was before it
-    bool wl_on = false, corr = false, trim = false, chim = false, tags = false, trim5p = false, no_tsv = false, resc = false;
+    bool wl_on = false, corr = false, trim = false, chim = false, tags = false, trim5p = false, no_tsv = false, resc = false, split = false;
     // how much of the caller's result is the library's to clear and write (the fields behind whitelist_barcodes only with the
     // bits that fill them); 0 until the flags and the layout have passed their checks: a call rejected there leaves the result alone
     size_t result_bytes = 0;
@@ -60,7 +98,8 @@ int make_plan(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, co
     p.tags = (o->whitelist & BDG_STAGE1_TAGS) != 0;
     if (!out_path && !p.tags) return BDG_E_ARG;
     p.trim = (o->whitelist & BDG_STAGE1_TRIM) != 0; p.chim = (o->whitelist & BDG_STAGE1_CHIMERA) != 0;
-    p.wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS)) != 0;
+    p.split = (o->whitelist & BDG_STAGE1_SPLIT) != 0;
+    p.wl_on = (o->whitelist & ~(BDG_STAGE1_TRIM | BDG_STAGE1_CHIMERA | BDG_STAGE1_TAGS | BDG_STAGE1_SPLIT)) != 0;
     p.corr = p.wl_on && (o->whitelist & BDG_STAGE1_WL_CORRECT); p.no_tsv = !out_path;
     p.resc = (o->whitelist & BDG_STAGE1_WL_RESCUE) != 0;
     if (p.resc && !p.corr) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_WL_RESCUE needs BDG_STAGE1_WL_CORRECT");
@@ -78,9 +117,11 @@ int make_plan(bdg_ctx* const* ctxs, uint32_t n_ctx, const bdg_stage1_opts* o, co
     if (p.chim) p.result_bytes = offsetof(bdg_stage1_result, tags_no_cell);
     if (p.tags) p.result_bytes = offsetof(bdg_stage1_result, trimmed_no_anchor);
     if (p.trim5p) p.result_bytes = offsetof(bdg_stage1_result, rescue_eligible);
-    if (p.resc) p.result_bytes = sizeof(bdg_stage1_result);
+    if (p.resc) p.result_bytes = offsetof(bdg_stage1_result, split_reads);
+    if (p.split) p.result_bytes = sizeof(bdg_stage1_result);
     if (int rcu = bdg_check_umi_len(c0, o->umi_len)) return rcu;
     if (p.chim && o->chimera_max_ed > BDG_CHIMERA_MAX_ED_MAX) return bdg_fail(c0, BDG_E_ARG, "chimera_max_ed out of range (0 .. 6)");
+    if (p.split) if (int rcs = check_split(c0, o->split_max_ed)) return rcs;
     if (p.resc) {
         if (c0->x_layout != BDG_LAYOUT_3P) return bdg_fail(c0, BDG_E_ARG, "BDG_STAGE1_WL_RESCUE needs the 3' layout");
         if (int rcr = bdg_rescue_check(c0, o->umi_len, o->rescue_max_ed)) return rcr;
@@ -237,6 +278,10 @@ struct ChunkLoop {
     std::vector<bdg_extract_rec> recs;         // records of the chunk collected last
     std::vector<uint32_t> chunk_n;             // reads per chunk, in input order
     std::string err; uint64_t bad_read = ~0ull, g0 = 0;
+    // BDG_STAGE1_SPLIT: every chunk is cut into pieces between its copy and its extraction, and from there on a piece is a read:
+    // g0 and chunk_n count pieces, in0 the input's reads
+    bool split = false; uint32_t split_max_ed = 0;
+    uint64_t in0 = 0, split_reads = 0, split_pieces = 0;
 
     // collected(fly, recs) -> rc: the chunk's records are in `recs`; with BDG_OK the chunk is the callee's to release
     template <class Collected>
@@ -252,7 +297,11 @@ struct ChunkLoop {
                 res->seconds_wait_gpu += now_s() - t0;
                 if (r == BDG_OK) r = collected(f, recs);
                 if (r) err = bdg_last_error(f.ctx);
-                if (r == BDG_E_BADBASE) { uint64_t b = ~0ull, w = 0; (void)bdg_extract_status(f.ctx, &b, &w); if (b != ~0ull) bad_read = f.g0 + b; }
+                if (r == BDG_E_BADBASE) {
+                    uint64_t b = ~0ull, w = 0; (void)bdg_extract_status(f.ctx, &b, &w);
+                    if (b != ~0ull) bad_read = !f.view ? f.g0 + b : f.in0 + (b < f.view->read.size() ? f.view->read[b] : 0u);   // (the INPUT read's number)
+                    if (b != ~0ull && f.view) err = "read " + std::to_string(bad_read - f.in0) + " of the chunk (a piece of it) holds a byte outside 'ACGTN'";
+                }
             }
             if (r || !full) bdg_ingest_release(ing, f.ch.id);
             return r;
@@ -268,17 +317,30 @@ struct ChunkLoop {
             if (inflight.size() >= (size_t)per_ctx * n_ctx && (rc = collect(true))) { bdg_ingest_release(ing, ch.id); break; }
             const uint64_t k = chunk_n.size();
             Fly f;
-            f.seq = k; f.g0 = g0; f.ch = ch; f.ctx = ctxs[k % n_ctx]; f.slot = (uint32_t)((k / n_ctx) % per_ctx);
+            f.seq = k; f.g0 = g0; f.in0 = in0; f.ch = ch; f.ctx = ctxs[k % n_ctx]; f.slot = (uint32_t)((k / n_ctx) % per_ctx);
             const double t1 = now_s();
-            if (ids && ids_first) (void)bdg_idstore_append(ids, ch.ids, ch.id_off, ch.n);
-            rc = bdg_extract_submit(f.ctx, f.slot, ch.bases, ch.off, ch.n, umi_len);
+            if (!split) {
+                if (ids && ids_first) (void)bdg_idstore_append(ids, ch.ids, ch.id_off, ch.n);
+                rc = bdg_extract_submit(f.ctx, f.slot, ch.bases, ch.off, ch.n, umi_len);
+            } else {
+                uint32_t np = 0; const bdg_split_rec* pieces = nullptr;
+                rc = bdg_slot_split_submit(f.ctx, f.slot, ch.bases, ch.off, ch.n, umi_len, split_max_ed, &np, &pieces);
+                if (!rc) {
+                    f.view = make_view(f.ch, pieces, np);       // (f.ch is the pieces' chunk from here on, ch the reader's)
+                    for (uint32_t p = 1; p < np; ++p) if (pieces[p].read == pieces[p - 1].read) {
+                        ++split_pieces;
+                        if (p < 2 || pieces[p - 2].read != pieces[p].read) { ++split_reads; ++split_pieces; }
+                    }
+                    if (ids && ids_first) (void)bdg_idstore_append(ids, f.ch.ids, f.ch.id_off, f.ch.n);
+                }
+            }
             if (rc) bdg_ingest_release(ing, ch.id);
             else inflight.push_back(f);                         // (submitted: collected below even if its match cannot be queued)
             if (!rc && match) rc = bdg_slot_match_topk(f.ctx, f.slot, match->max_bc_dist, match->bc_candidates);
             res->seconds_submit += now_s() - t1;
             if (rc) { err = bdg_last_error(f.ctx); break; }
-            if (ids && !ids_first) (void)bdg_idstore_append(ids, ch.ids, ch.id_off, ch.n);
-            chunk_n.push_back(ch.n); g0 += ch.n;
+            if (ids && !ids_first) (void)bdg_idstore_append(ids, f.ch.ids, f.ch.id_off, f.ch.n);
+            chunk_n.push_back(f.ch.n); g0 += f.ch.n; in0 += ch.n;
         }
         while (!inflight.empty()) { const int r = collect(rc == BDG_OK || collect_after_failure); if (rc == BDG_OK) rc = r; }
         return rc;
@@ -393,6 +455,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     const double t_start = now_s();
     const uint64_t max_outstanding = 2 * plan.fthreads + 2;      // collected chunks waiting for / in the formatters
     ChunkLoop L{ nullptr, ctxs, n_ctx, plan.per_ctx, o->umi_len, res, wl_on ? o : nullptr, ids, false, false };
+    L.split = plan.split; L.split_max_ed = plan.split ? o->split_max_ed : 0;
     int rc = open_reader(in_path, o, plan.per_ctx * n_ctx + 2 * plan.fthreads + 4, &L.ing, L.err);
     if (rc) return bdg_fail(c0, rc, L.err);
     Guard close_reader{ [&] { bdg_ingest_close(L.ing); }, true };
@@ -472,6 +535,7 @@ int bdg_stage1_run(bdg_ctx* const* ctxs, uint32_t n_ctx, const char* in_path, co
     if (chim) { res->chimera_cut = X.cut; res->chimera_dropped = X.dropped; res->chimera_bases = X.cut_bases; }
     if (tags) { res->tags_no_cell = X.no_cell; res->tags_not_kept = X.not_kept; }
     if (plan.trim5p) res->trimmed_no_anchor = X.no_anchor;
+    if (plan.split) { res->split_reads = L.split_reads; res->split_pieces = L.split_pieces; }
     if (plan.corr && rc == BDG_OK && ok_io && !P.tsv.failed) rc = correct_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, plan.wl.data(), (uint32_t)plan.wl.size(), res, L.err);
     if (plan.resc && rc == BDG_OK && ok_io && !P.tsv.failed) rc = rescue_run(ctxs, n_ctx, o, ids, L.chunk_n, L.g0, plan.wl.data(), (uint32_t)plan.wl.size(), res, L.err);
     resc_off.run();
@@ -489,13 +553,20 @@ int bdg_stage1_collect(bdg_ctx* ctx, const char* in_path, const bdg_stage1_opts*
     memset(res, 0, offsetof(bdg_stage1_result, whitelist_corrected));   // (the caller's struct may end before that field)
     res->first_polyt = res->first_r1 = res->bad_read = ~0ull;
     if (int rcu = bdg_check_umi_len(ctx, o->umi_len)) return rcu;
+    const bool split = (o->whitelist & BDG_STAGE1_SPLIT) != 0;             // (the one bit of opts->whitelist this call knows)
+    if (split) {
+        if (int rcs = check_split(ctx, o->split_max_ed)) return rcs;
+        res->split_reads = res->split_pieces = 0;
+    }
     const double t_start = now_s();
     ChunkLoop L{ nullptr, &ctx, 1, 2, o->umi_len, res, nullptr, ids, true, true };
+    L.split = split; L.split_max_ed = split ? o->split_max_ed : 0;
     int rc = open_reader(in_path, o, 4, &L.ing, L.err);
     if (rc) return bdg_fail(ctx, rc, L.err);
     rc = L.run([&](const Fly& f, std::vector<bdg_extract_rec>&) -> int { bdg_ingest_release(L.ing, f.ch.id); return BDG_OK; });   // (the records stay on the device)
     bdg_ingest_close(L.ing);
     res->reads = L.g0; res->chunks = L.chunk_n.size(); res->bad_read = L.bad_read; res->seconds_total = now_s() - t_start;
+    if (split) { res->split_reads = L.split_reads; res->split_pieces = L.split_pieces; }
     return rc ? bdg_fail(ctx, rc, L.err) : BDG_OK;
 }
 

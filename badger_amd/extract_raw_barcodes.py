@@ -44,6 +44,13 @@ What differs from the reference, by design:
     up to the first such column only, its header gains "\tCH:Z:<TSO|TSOrc|R1|R1rc>,<edits>", and it is left out when nothing
     remains.  The rule is restated in badger_amd/chimera.py and stated in include/badger_hip.h (bdg_chimera_batch).  The TSV
     and the .stats do not change; the three counts go to the log.
+  * --chimera_split: a read that holds several library molecules ligated end to end is cut into its molecules before anything else
+    looks at it, and every piece is a read from there on: its own row, its own barcode, UMI and trimmed record, under the id of its
+    read with /1, /2, .. behind the id's first word.  A junction is an R1 adapter or a TSO, in either orientation, within
+    --split_max_ed edits (0 .. 6, default 3; two more for the TSO), at least 64 bases from either end of the read.  Every output is
+    what the command gives without the flag on a file that holds the pieces as reads.  With --chimera_cut the cut then works on what
+    a piece still holds.  The rule is restated in badger_amd/chimera_split.py and stated in include/badger_hip.h (bdg_split_batch).
+    3' modes only.
   * --mode tenX_5p_v2 (UMI 10; also 5' v1 / v1.1) and tenX_5p_v3 (UMI 12): 10x 5' libraries,
     R1 - barcode - UMI - TTTCTTATATGGG - cDNA (sense) - polyA - RT primer.  The R1 and barcode search is the 3' one; behind it the
     records follow the 5' rule (include/badger_hip.h, bdg_extract_set_layout; badger_amd/trim5p.py): the UMI is the umi_len bases
@@ -424,7 +431,9 @@ def _run_native(args, header_every, threads, skip_secondary):
                                  detectors[0].UMI_LEN_10X, threads=threads, header_every=header_every, skip_secondary=skip_secondary,
                                  whitelist=wl is not None, max_bc_dist=_max_bc_dist(args),
                                  bc_candidates=(getattr(args, "bc_candidates", None) or 0) if wl is not None else 0,
-                                 **_correct_kwargs(args, wl is not None), **_trim_kwargs(args), **_rescue_kwargs(args, wl is not None))
+                                 **_correct_kwargs(args, wl is not None), **_trim_kwargs(args), **_rescue_kwargs(args, wl is not None), **split_kwargs(args))
+    if getattr(args, "chimera_split", False):
+        logger.info("Split reads: %d reads cut into %d pieces" % (res.split_reads, res.split_pieces))
     if _rescuing(args):
         logger.info("Rescued reads: %d eligible, %d rescued, %d ambiguous, %d truncated, written to %s"
                     % (res.rescue_eligible, res.rescue_rescued, res.rescue_ambiguous, res.rescue_truncated, args.output + RESCUED_SUFFIX))
@@ -577,6 +586,13 @@ def parse_args(sys_argv):
     p.add_argument("--chimera_max_ed", type=_chimera_max_ed, default=None, metavar="E",
                    help="--chimera_cut: edits allowed in the 22-base adapter (two more in the 30-base oligo), %d .. %d (default %d)"
                         % (CHIMERA_MAX_ED_RANGE + (_native.CHIMERA_MAX_ED_DEFAULT,)))
+    p.add_argument("--chimera_split", action="store_true", default=False,
+                   help="split a read that holds two or more library molecules ligated end to end into its molecules, at every R1 "
+                        "adapter or template-switch oligo found more than %d bases from either end; each piece goes through the run as "
+                        "a read of its own, with /1, /2, .. behind its read's id; 3' modes only" % _native.SPLIT_MARGIN)
+    p.add_argument("--split_max_ed", type=_split_max_ed, default=None, metavar="E",
+                   help="--chimera_split: edits allowed in the 22-base adapter (two more in the 30-base oligo), 0 .. %d (default %d)"
+                        % (_native.SPLIT_MAX_ED_MAX, _native.SPLIT_MAX_ED_DEFAULT))
     p.add_argument("--bc_rescue", action="store_true", default=False,
                    help="--bc_correct: look for a known barcode in reads without a usable adapter, at the place their polyT tail implies "
                         "(16 bases, the UMI, the tail; both strands, %d bases of slack either way), among the whitelist entries this run "
@@ -602,6 +618,7 @@ def parse_args(sys_argv):
         p.error("--chimera_cut needs --trimmed_reads")
     if args.chimera_max_ed is not None and not args.chimera_cut:
         p.error("--chimera_max_ed needs --chimera_cut")
+    check_split_args(p, args.mode, args.chimera_split, args.split_max_ed)
     if args.max_bc_dist is not None and not args.barcodes:
         p.error("--max_bc_dist needs --barcodes")
     if args.bc_candidates is not None and not args.barcodes:
@@ -691,6 +708,32 @@ def _chimera_max_ed(text):
     if not CHIMERA_MAX_ED_RANGE[0] <= v <= CHIMERA_MAX_ED_RANGE[1]:
         raise argparse.ArgumentTypeError("%d is outside %d .. %d" % ((v,) + CHIMERA_MAX_ED_RANGE))
     return v
+
+
+def _split_max_ed(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("not an integer: %r" % text)
+    if not 0 <= v <= _native.SPLIT_MAX_ED_MAX:
+        raise argparse.ArgumentTypeError("%d is outside 0 .. %d" % (v, _native.SPLIT_MAX_ED_MAX))
+    return v
+
+
+def check_split_args(p, mode, chimera_split, split_max_ed):
+    """the dependent checks of the split's flags, for both command lines"""
+    if split_max_ed is not None and not chimera_split:
+        p.error("--split_max_ed needs --chimera_split")
+    if chimera_split and is_5p_mode(mode):
+        p.error("--chimera_split serves the 3' modes only (a 5' read ends in the RT primer, which the split's patterns do not hold)")
+
+
+def split_kwargs(args):
+    """stage1_run's and stage1_collect's split argument: none without --chimera_split"""
+    if not getattr(args, "chimera_split", False):
+        return {}
+    ed = getattr(args, "split_max_ed", None)
+    return dict(split_max_ed=_native.SPLIT_MAX_ED_DEFAULT if ed is None else ed)
 
 
 def _bc_posterior(text):
