@@ -47,6 +47,11 @@ CONS_ANCHOR_START, CONS_ANCHOR_END = 0, 1
 CONS_MAX_LEN, CONS_MAX_GROUP = 8192, 16
 CONS_BAND_DEFAULT, CONS_BAND_MAX = 64, 256
 CONS_ACCEPTED, CONS_REJ_DIST, CONS_REJ_BAND, CONS_REJ_LEN, CONS_BACKBONE = 1, 2, 4, 8, 16
+# bdg_gene_rec: the gene call of a read by k-mer lookup (bdg_genes_assign; the rule in badger_amd/genes.py)
+GENE_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), ("n_keys", "<u4"), ("n_found", "<u4"), ("flags", "<u4")])
+GENES_K_MIN, GENES_K_MAX, GENES_K_DEFAULT, GENES_MIN_HITS_DEFAULT, GENES_MAX_FEATURES = 11, 31, 21, 3, 256
+GENES_AMBIGUOUS, GENES_NONE = 0xFFFFFFFE, 0xFFFFFFFF
+GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -81,6 +86,7 @@ EXPORTS = [
     "bdg_extract_keep_cdna", "bdg_kept_cdna", "bdg_molecule_reps_dev", "bdg_molecule_reps_set_aggregate", "bdg_format_trimmed_tags",
     "bdg_rescue_batch", "bdg_rescue_batch_dev", "bdg_extract_set_rescue", "bdg_extract_rescue_resolve", "bdg_rescue_counts",
     "bdg_consensus", "bdg_consensus_dev", "bdg_consensus_set_band",
+    "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
 ]
 
 
@@ -346,6 +352,10 @@ def load():
     L.bdg_rescue_counts.argtypes = [vp, C.POINTER(u64)]
     L.bdg_consensus.argtypes = [vp, vp, vp, u64, vp, u32, C.c_int, u32, vp, vp, vp, vp, vp]
     L.bdg_consensus_dev.argtypes = [vp, vp, vp, u64, vp, u32, C.c_int, u32, vp, vp, vp, vp, vp]
+    L.bdg_genes_index_build.argtypes = [vp, vp, vp, u32, vp, u32]
+    L.bdg_genes_index_stats.argtypes = [vp, vp]
+    L.bdg_genes_assign.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.bdg_genes_assign_dev.argtypes = [vp, vp, vp, u32, u32, vp]
     L.bdg_consensus_set_band.argtypes = [vp, u32]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
@@ -665,6 +675,36 @@ class Context:
         (bdg_consensus_set_band); consensus_band is the value in force"""
         self._check(self.lib.bdg_consensus_set_band(self.h, int(band)))
         self.consensus_band = int(band)
+
+    def genes_index_build(self, bases, seq_off, features, k=GENES_K_DEFAULT):
+        """the k-mer table of the sequences (bases uint8, seq_off uint64 [n + 1], features uint32 [n]) on the device, held by
+        the context in place of an earlier one (bdg_genes_index_build)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        features = np.ascontiguousarray(features, dtype=np.uint32)
+        if len(seq_off) != len(features) + 1:
+            raise ValueError("seq_off holds one entry more than features")
+        self._check(self.lib.bdg_genes_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data, int(k)))
+
+    def genes_index_stats(self):
+        """-> uint64 [6]: windows with a key, distinct keys, ambiguous keys, slots, longest run of occupied slots, keys stored
+        past a wrap of the table's end (bdg_genes_index_stats)"""
+        out = np.zeros(6, dtype=np.uint64)
+        self._check(self.lib.bdg_genes_index_stats(self.h, out.ctypes.data))
+        return out
+
+    def genes_assign(self, bases, off, min_hits=GENES_MIN_HITS_DEFAULT):
+        """the gene call of every read over host arrays (bdg_genes_assign) -> GENE_DTYPE [n]"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        out = np.zeros(n, dtype=GENE_DTYPE)
+        self._check(self.lib.bdg_genes_assign(self.h, bases.ctypes.data, off.ctypes.data, n, int(min_hits), out.ctypes.data))
+        return out
+
+    def genes_assign_dev(self, d_bases, d_off, n, min_hits, d_out):
+        """bdg_genes_assign_dev: the same over device arrays, asynchronous"""
+        self._check(self.lib.bdg_genes_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), int(min_hits), _ptr(d_out)))
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""

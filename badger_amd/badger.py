@@ -6,6 +6,7 @@
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa [--chimera_cut] [--umi_dedup [--molecule_reads]]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --umi_dedup --molecule_consensus consensus.fa
                                 [--consensus_band 64|128|256]
+    python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -20,6 +21,9 @@ header.  The input is read a second time for it (the extraction costs under a mi
 --molecule_reads keeps one read per molecule: the longest cDNA, the earliest read at equal lengths (the rule of molecule_reads.py,
 on the device).  --molecule_consensus PATH instead keeps every read in the tagged file and writes one consensus sequence per
 molecule from it (consensus.py: the reads of a molecule aligned to its longest read and voted column by column, on the device).
+--count_matrix DIR, with or without --umi_dedup and independent of --molecule_consensus, calls the gene of every read of the tagged
+file by k-mer lookup in --transcripts (genes.py: a table of the k-mers that belong to one gene only, on the device) and writes the
+features x barcodes matrix in MatrixMarket form with its two name files, plus reads.tsv with every read's call.
 Every other output is the same bytes with and without these flags.
 
 -d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
@@ -41,6 +45,7 @@ from traceback import print_exc
 
 from . import _native
 from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
+from .genes import K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HITS_DEFAULT, add_gene_options
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -109,7 +114,22 @@ def parse_args(args):
                    help="--tagged_reads with --umi_dedup: one consensus sequence per molecule as FASTA, the reads of the molecule "
                         "voted on its longest read; the header is that read's with the number of voters as CN")
     add_consensus_options(p)
+    p.add_argument("--count_matrix", type=str, default=None, metavar="DIR",
+                   help="--tagged_reads with --transcripts: the gene of every tagged read by k-mer lookup on the device and the "
+                        "features x barcodes matrix of the run (features.tsv, barcodes.tsv, matrix.mtx, reads.tsv in DIR); "
+                        "molecules are counted once with --umi_dedup, reads without it")
+    p.add_argument("--transcripts", type=str, default=None, metavar="FASTA",
+                   help="--count_matrix: transcript sequences in mRNA sense (.gz is read through gzip)")
+    p.add_argument("--tx2gene", type=str, default=None, metavar="TSV",
+                   help="--count_matrix: transcript<TAB>gene per line, counts are per gene (without it per transcript name)")
+    add_gene_options(p)
     a = p.parse_args(args)
+    if a.count_matrix and not (a.tagged_reads and a.transcripts):
+        p.error("--count_matrix needs --tagged_reads and --transcripts: it looks the tagged reads up in the transcripts")
+    if (a.transcripts or a.tx2gene or a.gene_k is not None or a.gene_min_hits is not None) and not a.count_matrix:
+        p.error("--transcripts, --tx2gene, --gene_k and --gene_min_hits need --count_matrix")
+    a.gene_k = GENE_K_DEFAULT if a.gene_k is None else a.gene_k
+    a.gene_min_hits = GENE_MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
@@ -272,6 +292,14 @@ def write_molecule_consensus(args):
     log_counts(counts, args.molecule_consensus)
 
 
+def write_count_matrix(args):
+    """behind write_tagged_reads, on the file it wrote"""
+    from .genes import count_matrix_of_tagged, log_counts
+    counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
+                                    args.gene_min_hits, args.device)
+    log_counts(counts, args.count_matrix)
+
+
 def main(args):
     t_marks = [("start", time.perf_counter())]
 
@@ -338,6 +366,9 @@ def main(args):
             if args.molecule_consensus:
                 write_molecule_consensus(args)
                 mark("molecule_consensus")
+            if args.count_matrix:
+                write_count_matrix(args)
+                mark("count_matrix")
         disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
     finally:
         st2.release_device()

@@ -143,6 +143,12 @@ struct bdg_ctx {
     DevBuf c_trace;      // direction bits, 16 * c_band / 64 bytes per member row and wave in flight
     int c_cus = 0;       // compute units (asked once)
     uint32_t c_band = BDG_CONS_BAND_DEFAULT;   // bdg_consensus_set_band: diagonals of the alignment's band, 64, 128 or 256
+    // ---- gene index (genes_kernels.hip): held like the whitelist, replaced by the next bdg_genes_index_build
+    DevBuf gn_table;     // gn_slots slots of {u64 key, u32 value, u32 pad}
+    uint64_t gn_slots = 0;                   // a power of two; 0: no index
+    uint32_t gn_k = 0;
+    uint64_t gn_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_genes_index_stats
+    int gn_cus = 0, gn_assign_per_cu = 0;    // compute units, and blocks of k_genes_assign resident on one (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

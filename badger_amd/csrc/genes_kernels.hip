@@ -1,0 +1,456 @@
+// Gene calls by k-mer lookup (include/badger_hip.h at bdg_genes_index_build states the rule; badger_amd/genes.py restates it;
+// DESIGN 4.19).  gfx950.
+//
+// Both kernels run one wave per sequence, persistent over the sequences, a lane per window.  A wave takes 64 positions at a
+// time: every lane loads its own byte (one coalesced 64-byte line per wave) and three ballots turn the 64 codes into three
+// 64-bit planes - low code bit, high code bit, "is N" (positions behind the sequence's end are N, so a window that would pass
+// the end has an N in it).  The planes are wave-uniform, they live in scalar registers; lane l's window is the bits
+// l .. l + k - 1 of a plane and the plane behind it, a shift and an or, and its key the two code planes interleaved.  No LDS
+// and no barrier on this path, and no byte is read by more than one lane.
+//
+// k_genes_insert   claims a key's slot with a 64-bit compare-and-swap on the key and settles the value without an order:
+//                  EMPTY -> f by compare-and-swap, another feature found there -> AMBIGUOUS.  A lane looks before it swaps:
+//                  a key already stored and a value that already reads f or AMBIGUOUS cost a load and no atomic, and a lane
+//                  whose left neighbour holds the same key (a homopolymer run: the all-A key of every polyA tail)
+//                  does nothing at all.
+// k_genes_assign   issues the first probe of GENES_CHUNKS x 64 windows before it looks at any of them (every probe of a large
+//                  table is a sector from HBM for a 16-byte slot), walks the longer chains of all of them in step, two slots a
+//                  round (a window that is not in the table walks to the next empty slot: the wave waits for the longest of its
+//                  chains, one trip to memory a round), and counts the values with a loop over the distinct values in the
+//                  wave: first live lane's value, ballot of its equals, popcount - one or two rounds for a read that lies in
+//                  one gene.  The counts go to a table of 256 (feature, count) entries in LDS that the whole wave searches,
+//                  four entries a lane: no LDS atomics.  The 257th feature sets CROWDED.  Best and second best are two wave
+//                  reductions with the tie rule.
+// k_genes_stats    the table's occupancy figures, none of which depends on the order of insertion.
+#include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
+
+#include <algorithm>
+
+namespace {
+
+constexpr unsigned long long KEY_EMPTY = ~0ull;              // no key of k <= 31 bases has bit 62 or 63 set
+constexpr unsigned long long HASH_MUL = 0x9E3779B97F4A7C15ull;
+constexpr uint32_t GENES_CHUNKS = 4;                         // chunks of 64 windows whose probes a wave has in flight
+constexpr uint32_t INSERT_WAVES_PER_CU = 16;                  // (k_genes_assign: as many as the device keeps resident, asked once)
+
+struct __align__(16) GeneSlot { unsigned long long key; uint32_t value, pad; };
+static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24, "layouts the header states");
+
+struct Planes { uint64_t lo, hi, nv; };
+
+__device__ __forceinline__ uint32_t base_code(uint32_t c)          // A 0, C 1, G 2, T 3, anything else 4
+{
+    return (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? ((c >> 1) ^ (c >> 2)) & 3u : 4u;
+}
+
+// this lane's byte of the positions p0 .. p0 + 63 of the sequence s; a position behind the end reads as N
+__device__ __forceinline__ uint32_t load_byte(const uint8_t* s, uint64_t len, uint64_t p0, uint32_t lane)
+{
+    const uint64_t p = p0 + lane;
+    return p < len ? s[p] : (uint32_t)'N';
+}
+
+// the planes of 64 positions from every lane's byte (bit i: lane i's position)
+__device__ __forceinline__ Planes planes_of(uint32_t byte)
+{
+    const uint32_t code = base_code(byte);
+    Planes P;
+    P.lo = __ballot((code & 1u) != 0);
+    P.hi = __ballot((code & 2u) != 0);
+    P.nv = __ballot((code & 4u) != 0);
+    return P;
+}
+
+__device__ __forceinline__ Planes load_planes(const uint8_t* s, uint64_t len, uint64_t p0, uint32_t lane)
+{
+    return planes_of(load_byte(s, len, p0, lane));
+}
+
+// bits lane .. lane + 31 of the 128 bits a1 : a0
+__device__ __forceinline__ uint32_t window32(uint64_t a0, uint64_t a1, uint32_t lane)
+{
+    return (uint32_t)(lane ? (a0 >> lane) | (a1 << (64u - lane)) : a0);
+}
+
+__device__ __forceinline__ uint64_t spread_bits(uint32_t x)        // bit i -> bit 2 i
+{
+    uint64_t v = x;
+    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
+    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
+    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    v = (v | (v << 2)) & 0x3333333333333333ull;
+    v = (v | (v << 1)) & 0x5555555555555555ull;
+    return v;
+}
+
+// the key of the window that starts at this lane's position of chunk A (B: the chunk behind it); KEY_EMPTY: it has none
+__device__ __forceinline__ unsigned long long window_key(const Planes& A, const Planes& B, uint32_t lane, uint32_t kmask)
+{
+    if (window32(A.nv, B.nv, lane) & kmask) return KEY_EMPTY;
+    return spread_bits(window32(A.lo, B.lo, lane) & kmask) | (spread_bits(window32(A.hi, B.hi, lane) & kmask) << 1);
+}
+
+__device__ __forceinline__ uint64_t home_slot(unsigned long long key, uint32_t shift) { return (key * HASH_MUL) >> shift; }
+
+__device__ __forceinline__ void insert_key(GeneSlot* table, uint64_t mask, uint32_t shift, unsigned long long key, uint32_t f)
+{
+    uint64_t s = home_slot(key, shift);
+    for (;;) {                                                      // (at most half of the slots are ever taken: it ends)
+        unsigned long long cur = __hip_atomic_load(&table[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == KEY_EMPTY) {
+            cur = atomicCAS(&table[s].key, KEY_EMPTY, key);
+            if (cur == KEY_EMPTY) cur = key;
+        }
+        if (cur == key) break;
+        s = (s + 1) & mask;
+    }
+    // the value only ever goes NONE -> a feature -> AMBIGUOUS
+    uint32_t v = __hip_atomic_load(&table[s].value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v == f || v == BDG_GENES_AMBIGUOUS) return;
+    if (v == BDG_GENES_NONE) {
+        v = atomicCAS(&table[s].value, BDG_GENES_NONE, f);
+        if (v == BDG_GENES_NONE || v == f) return;
+    }
+    if (v != BDG_GENES_AMBIGUOUS) __hip_atomic_store(&table[s].value, BDG_GENES_AMBIGUOUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(64)
+void k_genes_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ features,
+                    uint32_t n_seqs, uint32_t k, GeneSlot* table, uint64_t mask, uint32_t shift)
+{
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
+        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets)
+        if (len < k) continue;
+        const uint8_t* s = bases + b;
+        const uint32_t f = features[q];
+        Planes A = load_planes(s, len, 0, lane);
+        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
+            const Planes B = load_planes(s, len, p0 + 64, lane);
+            unsigned long long key = window_key(A, B, lane, kmask);
+            const unsigned long long left = __shfl_up(key, 1);
+            if (lane && left == key) key = KEY_EMPTY;               // its left neighbour inserts the same key for the same feature
+            if (key != KEY_EMPTY) insert_key(table, mask, shift, key, f);
+            A = B;
+        }
+    }
+}
+
+// out: distinct keys | ambiguous keys | longest run of occupied slots | keys in front of their home slot
+__global__ __launch_bounds__(256)
+void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t shift, unsigned long long* out)
+{
+    __shared__ unsigned long long sh[4];
+    if (threadIdx.x < 4) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t mask = slots - 1;
+    unsigned long long distinct = 0, amb = 0, run_max = 0, wrapped = 0;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long key = table[s].key;
+        if (key == KEY_EMPTY) continue;
+        ++distinct;
+        amb += table[s].value == BDG_GENES_AMBIGUOUS;
+        wrapped += home_slot(key, shift) > s;
+        if (table[(s - 1) & mask].key == KEY_EMPTY) {               // a run starts here (there is always an empty slot: it ends)
+            unsigned long long run = 1;
+            for (uint64_t t = (s + 1) & mask; table[t].key != KEY_EMPTY; t = (t + 1) & mask) ++run;
+            run_max = run > run_max ? run : run_max;
+        }
+    }
+    if (distinct) atomicAdd(&sh[0], distinct);
+    if (amb) atomicAdd(&sh[1], amb);
+    if (run_max) atomicMax(&sh[2], run_max);
+    if (wrapped) atomicAdd(&sh[3], wrapped);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (sh[0]) atomicAdd(&out[0], sh[0]);
+        if (sh[1]) atomicAdd(&out[1], sh[1]);
+        if (sh[2]) atomicMax(&out[2], sh[2]);
+        if (sh[3]) atomicAdd(&out[3], sh[3]);
+    }
+}
+
+__global__ __launch_bounds__(64)
+void k_genes_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k, uint32_t min_hits,
+                    const GeneSlot* __restrict__ table, uint64_t mask, uint32_t shift, bdg_gene_rec* __restrict__ out)
+{
+    __shared__ uint32_t t_feat[BDG_GENES_MAX_FEATURES], t_cnt[BDG_GENES_MAX_FEATURES];
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
+        const uint64_t b = off[r], e = off[r + 1], len = e > b ? e - b : 0;
+        const uint8_t* s = bases + b;
+        uint32_t n_ent = 0, n_keys = 0, n_found = 0;
+        bool crowded = false;
+        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64 * GENES_CHUNKS) {
+            uint32_t byte[GENES_CHUNKS + 1];
+            Planes P[GENES_CHUNKS + 1];
+#pragma unroll
+            for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = load_byte(s, len, p0 + 64 * c, lane);   // (all on their way, then the ballots)
+#pragma unroll
+            for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = planes_of(byte[c]);
+            unsigned long long key[GENES_CHUNKS];
+            ulonglong2 got[GENES_CHUNKS];
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) key[c] = window_key(P[c], P[c + 1], lane, kmask);
+            // every first probe is on its way before one is looked at (a lane without a key reads slot 0 and drops it: no branch
+            // around a load and no arithmetic between two of them)
+            uint64_t sl[GENES_CHUNKS];
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) sl[c] = key[c] != KEY_EMPTY ? home_slot(key[c], shift) : 0;
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) got[c] = *reinterpret_cast<const ulonglong2*>(table + sl[c]);
+            // the chains: a window whose home slot holds another key goes on, all four chunks in step and two slots a round,
+            // so that a round is one trip to memory for the wave - the longest chain among its 256 windows, halved, is what it
+            // waits for, not the sum over the chunks.  A lane that is done reads slot 0 and drops it (no branch around a load).
+            for (;;) {
+                bool open[GENES_CHUNKS], any = false;
+#pragma unroll
+                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) any |= open[c] = key[c] != KEY_EMPTY && got[c].x != KEY_EMPTY && got[c].x != key[c];
+                if (!__any(any)) break;
+                ulonglong2 t1[GENES_CHUNKS], t2[GENES_CHUNKS];
+#pragma unroll
+                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
+                    t1[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 1) & mask : 0));
+                    t2[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 2) & mask : 0));
+                }
+#pragma unroll
+                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
+                    if (!open[c]) continue;
+                    const bool ends = t1[c].x == KEY_EMPTY || t1[c].x == key[c];      // the chain ends at the first of the two
+                    got[c] = ends ? t1[c] : t2[c];
+                    sl[c] = (sl[c] + (ends ? 1 : 2)) & mask;
+                }
+            }
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
+                const bool has_key = key[c] != KEY_EMPTY;
+                const ulonglong2 g = got[c];
+                const bool found = has_key && g.x == key[c];
+                const uint32_t val = found ? (uint32_t)g.y : BDG_GENES_NONE;
+                n_keys += __popcll(__ballot(has_key));
+                n_found += __popcll(__ballot(found));
+                uint64_t live = crowded ? 0 : __ballot(val < BDG_GENES_AMBIGUOUS);
+                while (live) {                                      // one round per distinct feature among the 64 values
+                    const uint32_t f = __shfl(val, __ffsll((unsigned long long)live) - 1);
+                    const uint64_t same = __ballot(val == f);
+                    const uint32_t cnt = __popcll(same);
+                    live &= ~same;
+                    bool mine = false;
+                    uint32_t at = 0;
+                    for (uint32_t i = lane; i < n_ent; i += 64)
+                        if (t_feat[i] == f) { mine = true; at = i; }
+                    if (__ballot(mine)) {
+                        if (mine) t_cnt[at] += cnt;
+                    } else if (n_ent < BDG_GENES_MAX_FEATURES) {
+                        if (lane == 0) { t_feat[n_ent] = f; t_cnt[n_ent] = cnt; }
+                        ++n_ent;
+                    } else {
+                        crowded = true;
+                        live = 0;
+                    }
+                    __syncthreads();                                // (a block is one wave: this orders the LDS traffic)
+                }
+            }
+        }
+        // the largest count, the smallest feature at a tie; then the largest count of the others
+        uint32_t hits = 0, feature = BDG_GENES_NONE;
+        for (uint32_t i = lane; i < n_ent; i += 64) {
+            const uint32_t c = t_cnt[i], f = t_feat[i];
+            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }
+        }
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) {
+            const uint32_t c = __shfl_xor(hits, d), f = __shfl_xor(feature, d);
+            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }
+        }
+        uint32_t second = 0;
+        for (uint32_t i = lane; i < n_ent; i += 64)
+            if (t_feat[i] != feature) second = max(second, t_cnt[i]);
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));
+        __syncthreads();                                            // the table is read: the next read may fill it
+        if (lane == 0) {
+            bdg_gene_rec rec;
+            rec.n_keys = n_keys;
+            rec.n_found = n_found;
+            if (crowded) {
+                rec.feature = BDG_GENES_NONE; rec.hits = 0; rec.second = 0; rec.flags = BDG_GENE_CROWDED;
+            } else {
+                rec.feature = feature; rec.hits = hits; rec.second = second;
+                rec.flags = (hits >= min_hits && hits > second) ? BDG_GENE_ASSIGNED
+                          : (hits < min_hits ? BDG_GENE_LOW : 0u) | (hits == second && second > 0 ? BDG_GENE_TIE : 0u);
+            }
+            out[r] = rec;
+        }
+    }
+}
+
+int genes_cus(bdg_ctx* ctx)
+{
+    if (ctx->gn_cus == 0) {
+        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->gn_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        if (ctx->gn_cus <= 0) ctx->gn_cus = 1;
+    }
+    return BDG_OK;
+}
+
+int genes_check_assign(bdg_ctx* ctx, uint32_t min_hits)
+{
+    if (ctx->gn_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: no index built (bdg_genes_index_build)");
+    if (min_hits == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: min_hits must be at least 1");
+    return BDG_OK;
+}
+
+int genes_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits, bdg_gene_rec* d_out)
+{
+    if (int rc = genes_cus(ctx)) return rc;
+    if (ctx->gn_assign_per_cu == 0) {
+        // the reads are dealt out to the waves once: more blocks than are resident together would run as a second, thinner round
+        int per_cu = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_genes_assign, 64, 0));
+        ctx->gn_assign_per_cu = per_cu < 1 ? 1 : per_cu;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_assign_per_cu);
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
+    {
+        ScopedKernelTimer tm(ctx, "k_genes_assign");
+        hipLaunchKernelGGL(k_genes_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->gn_k, min_hits,
+                           static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, shift, d_out);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                          uint32_t k)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "genes: k out of range (11 .. 31)");
+    if (!seq_off || (n_seqs && !features)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "genes: sequence offsets must be non-decreasing");
+        if (features[q] >= BDG_GENES_AMBIGUOUS) return bdg_fail(ctx, BDG_E_ARG, "genes: feature id reserved (>= 0xFFFFFFFE)");
+    }
+    const uint64_t end = seq_off[n_seqs];
+    if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    // windows with a key: the table's size follows from them
+    uint64_t windows = 0;
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        uint64_t run = 0;
+        for (uint64_t p = seq_off[q]; p < seq_off[q + 1]; ++p) {
+            const uint8_t c = bases[p];
+            run = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? run + 1 : 0;
+            windows += run >= k;
+        }
+    }
+    uint64_t slots = 64;
+    while (slots < 2 * windows) slots <<= 1;
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(slots);
+
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (a queued assign call may still read the earlier table)
+    ctx->gn_table.reset();
+    ctx->gn_slots = 0;
+    ctx->gn_k = 0;
+    int rc;
+    if ((rc = genes_cus(ctx))) return rc;
+    // the sequences, their offsets and features and the four counters live for this call only
+    DevBuf d_bases, d_meta;
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), feat_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u;
+    if ((rc = bdg_reserve(ctx, ctx->gn_table, sizeof(GeneSlot) * (size_t)slots))) { ctx->gn_table.reset(); return rc; }
+    if ((rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + 4 * sizeof(uint64_t)))) {
+        ctx->gn_table.reset();
+        return rc;
+    }
+    auto* d_off = static_cast<uint64_t*>(d_meta.p);
+    auto* d_feat = reinterpret_cast<uint32_t*>(static_cast<char*>(d_meta.p) + off_b);
+    auto* d_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_meta.p) + off_b + feat_b);
+    unsigned long long h_stats[4] = { 0, 0, 0, 0 };
+    auto run = [&]() -> int {
+        if (end > seq_off[0])
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
+        if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_feat, features, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 4 * sizeof(uint64_t), st));
+        BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_table.p, 0xFF, sizeof(GeneSlot) * (size_t)slots, st));   // every key EMPTY, every value NONE
+        if (n_seqs) {
+            ScopedKernelTimer tm(ctx, "k_genes_insert");
+            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * INSERT_WAVES_PER_CU);
+            hipLaunchKernelGGL(k_genes_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_feat, n_seqs, k,
+                               static_cast<GeneSlot*>(ctx->gn_table.p), slots - 1, shift);
+        }
+        {
+            ScopedKernelTimer tm(ctx, "k_genes_stats");
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->gn_cus * 8);
+            hipLaunchKernelGGL(k_genes_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->gn_table.p), slots, shift, d_stats);
+        }
+        BDG_HIP_TRY(ctx, hipGetLastError());
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        return BDG_OK;
+    };
+    if ((rc = run())) {
+        (void)hipStreamSynchronize(st);                             // (the temporaries go with this frame)
+        ctx->gn_table.reset();
+        return rc;
+    }
+    const uint64_t stats[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
+    memcpy(ctx->gn_stats, stats, sizeof(stats));
+    ctx->gn_k = k;
+    ctx->gn_slots = slots;
+    return BDG_OK;
+}
+
+int bdg_genes_index_stats(bdg_ctx* ctx, uint64_t out[6])
+{
+    if (!ctx) return BDG_E_ARG;
+    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (ctx->gn_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: no index built (bdg_genes_index_build)");
+    memcpy(out, ctx->gn_stats, sizeof(ctx->gn_stats));
+    return BDG_OK;
+}
+
+int bdg_genes_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits, bdg_gene_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!d_off || !d_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_out);
+}
+
+int bdg_genes_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, bdg_gene_rec* out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!off || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    for (uint32_t r = 0; r < n; ++r)
+        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
+    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), rec_b = sizeof(bdg_gene_rec) * (size_t)n;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_b))) return rc;
+    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
+    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
+    auto* d_out = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
+    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
+    if ((rc = genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_out))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, rec_b, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
+
+}  // extern "C"

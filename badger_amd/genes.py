@@ -1,0 +1,383 @@
+#!/usr/bin/env python3
+"""Per-cell gene counts by k-mer lookup (stage 2's --count_matrix).
+
+    python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
+
+Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
+integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
+the product side: it reads a transcript FASTA, builds the k-mer table on the device (bdg_genes_index_build), hands the reads
+of a tagged FASTA as `badger.py --tagged_reads` writes it to the device (bdg_genes_assign), and turns the calls into molecules
+and the features x barcodes matrix on the host.
+
+The rule.  Any byte other than ACGT behaves as N; codes A 0, C 1, G 2, T 3.
+    key       a window of k consecutive bases (11 <= k <= 31) without an N: sum of code(base j) << 2j, j = 0 its first base.
+              Forward strand only: the cDNA this project writes is mRNA sense.
+    index     value(key) is f if every occurrence of the key, in every sequence, belongs to feature f, else AMBIGUOUS.
+    read      n_keys windows with a key, n_found of them in the index (ambiguous ones included); hits[f] the windows whose
+              value is f; hits the largest count, feature the smallest f attaining it, second the largest count among the
+              others (0 without one).  ASSIGNED iff hits >= min_hits and hits > second; else LOW if hits < min_hits and / or
+              TIE if hits == second > 0.  More than 256 distinct features: CROWDED alone, feature none, hits = second = 0.
+    table     open addressing, linear probing, the smallest power of two >= 2 * windows slots, at least 64; home slot
+              (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2 slots).  The set of occupied slots does not depend on the
+              order of insertion; the stats are functions of that set and the keys' home slots.
+    molecule  over a tagged file a read takes part if it has a CB.  The reads of one (CB, UB) pair form a molecule, a read
+              without UB is a molecule of its own.  A molecule's feature is the one named by strictly more of its ASSIGNED
+              reads than any other; a tie, or no assigned read, leaves it uncounted.
+    matrix    entry (feature, CB) = the molecules of that cell counted for that feature.
+"""
+import argparse
+import gzip
+import logging
+import os
+import sys
+
+import numpy as np
+
+K_MIN, K_MAX, K_DEFAULT, MIN_HITS_DEFAULT, MAX_FEATURES = 11, 31, 21, 3, 256
+AMBIGUOUS, NONE = 0xFFFFFFFE, 0xFFFFFFFF
+ASSIGNED, LOW, TIE, CROWDED = 1, 2, 4, 8
+FLAG_NAMES = ((ASSIGNED, "ASSIGNED"), (LOW, "LOW"), (TIE, "TIE"), (CROWDED, "CROWDED"))
+REC_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), ("n_keys", "<u4"), ("n_found", "<u4"), ("flags", "<u4")])
+HASH_MUL = np.uint64(0x9E3779B97F4A7C15)
+BATCH_BASES = 256 << 20             # bases per device call at most
+_CODE = np.full(256, 4, dtype=np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _i
+
+logger = logging.getLogger("BarcodeGraph")
+
+
+# ---------------------------------------------------------------- the checker ----
+def _as_array(s):
+    if isinstance(s, np.ndarray):
+        return s.astype(np.uint8, copy=False)
+    return np.frombuffer(s.encode() if isinstance(s, str) else bytes(s), dtype=np.uint8)
+
+
+def _check_k(k):
+    if not K_MIN <= k <= K_MAX:
+        raise ValueError("k out of range (11 .. 31)")
+
+
+def keys_of(seq, k):
+    """the keys of the windows of a sequence that have one, in the order of the windows -> uint64 array"""
+    _check_k(k)
+    code = _CODE[_as_array(seq)]
+    n = len(code) - k + 1
+    if n <= 0:
+        return np.zeros(0, dtype=np.uint64)
+    key = np.zeros(n, dtype=np.uint64)
+    bad = np.zeros(n, dtype=bool)
+    for j in range(k):
+        c = code[j:j + n]
+        bad |= c == 4
+        key |= (c & 3).astype(np.uint64) << np.uint64(2 * j)
+    return key[~bad]
+
+
+class Index:
+    """keys (uint64, ascending, distinct) and their values (uint32: a feature or AMBIGUOUS); windows: how many had a key"""
+
+    def __init__(self, keys, values, windows, k):
+        self.keys, self.values, self.windows, self.k = keys, values, int(windows), k
+
+    def slots(self):
+        n = 64
+        while n < 2 * self.windows:
+            n *= 2
+        return n
+
+    def lookup(self, keys):
+        """-> values of the keys, NONE where a key is not in the index"""
+        if not len(self.keys):
+            return np.full(len(keys), NONE, dtype=np.uint32)
+        at = np.minimum(np.searchsorted(self.keys, keys), len(self.keys) - 1)
+        return np.where(self.keys[at] == keys, self.values[at], np.uint32(NONE)).astype(np.uint32)
+
+    def stats(self, order=None):
+        """what bdg_genes_index_stats reports: windows with a key, distinct keys, ambiguous keys, slots, the longest run of
+        occupied slots (cyclic), keys stored in front of their home slot (past a wrap of the table's end).  order: the keys'
+        order of insertion (a permutation; ascending keys without one) - it moves single keys, never these figures: linear
+        probing fills the same slots in any order, and a run across the table's end takes up, in front of the end, exactly as
+        many of the keys at home there as it has slots there."""
+        slots = self.slots()
+        shift = np.uint64(64 - (slots.bit_length() - 1))
+        home = ((self.keys * HASH_MUL) >> shift).astype(np.int64)
+        used = [False] * slots
+        wrapped = 0
+        for h in (home if order is None else home[np.asarray(order)]).tolist():
+            s = h
+            while used[s]:
+                s = (s + 1) % slots
+            used[s] = True
+            wrapped += s < h
+        free = np.flatnonzero(~np.array(used))             # (at most half of the slots are taken)
+        runs = np.diff(np.concatenate([free, [free[0] + slots]])) - 1      # occupied slots between two free ones, round the end
+        return (self.windows, len(self.keys), int((self.values == AMBIGUOUS).sum()), slots, int(runs.max()), wrapped)
+
+
+def build_index(seqs, features, k):
+    """the index of the sequences (bytes / str / uint8 arrays) with a feature id each"""
+    _check_k(k)
+    if len(seqs) != len(features):
+        raise ValueError("a feature id per sequence")
+    if any(not 0 <= int(f) < AMBIGUOUS for f in features):
+        raise ValueError("feature id reserved or out of range")
+    parts = [keys_of(s, k) for s in seqs]
+    keys = np.concatenate(parts + [np.zeros(0, np.uint64)])
+    feat = np.concatenate([np.full(len(p), int(f), dtype=np.uint32) for p, f in zip(parts, features)] + [np.zeros(0, np.uint32)])
+    if not len(keys):
+        return Index(keys, feat, 0, k)
+    order = np.argsort(keys, kind="stable")
+    keys, feat = keys[order], feat[order]
+    first = np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1]]))
+    lo, hi = np.minimum.reduceat(feat, first), np.maximum.reduceat(feat, first)
+    return Index(keys[first], np.where(lo == hi, lo, np.uint32(AMBIGUOUS)).astype(np.uint32), len(keys), k)
+
+
+def assign_reads(index, reads, min_hits=MIN_HITS_DEFAULT):
+    """the rule over reads (bytes / str / uint8 arrays) -> REC_DTYPE [n]"""
+    if min_hits < 1:
+        raise ValueError("min_hits must be at least 1")
+    out = np.zeros(len(reads), dtype=REC_DTYPE)
+    for r, read in enumerate(reads):
+        val = index.lookup(keys_of(read, index.k))
+        feats, counts = np.unique(val[val < AMBIGUOUS], return_counts=True)
+        rec = out[r]
+        rec["n_keys"], rec["n_found"] = len(val), int((val != NONE).sum())
+        if len(feats) > MAX_FEATURES:
+            rec["feature"], rec["flags"] = NONE, CROWDED
+            continue
+        if not len(feats):
+            rec["feature"], rec["flags"] = NONE, LOW
+            continue
+        top = int(np.argmax(counts))                       # (the first maximum: the smallest feature)
+        hits = int(counts[top])
+        second = int(np.delete(counts, top).max(initial=0))
+        rec["feature"], rec["hits"], rec["second"] = feats[top], hits, second
+        rec["flags"] = ASSIGNED if hits >= min_hits and hits > second else (LOW if hits < min_hits else 0) | (TIE if hits == second > 0 else 0)
+    return out
+
+
+# ---------------------------------------------------------------- molecules and the matrix (host, product side) ----
+def flag_names(flags):
+    return ",".join(name for bit, name in FLAG_NAMES if flags & bit)
+
+
+def count_molecules(cb, ub, recs):
+    """cb, ub: per read bytes (ub None: a molecule of its own), recs REC_DTYPE [n] -> (cells sorted, {(feature, cell index):
+    molecules}, counts dict)"""
+    n = len(cb)
+    cells, cell_of = np.unique(np.array(cb, dtype=bytes) if n else np.zeros(0, "S1"), return_inverse=True)
+    mol_key = np.array([c + b"\t" + (u if u is not None else b"\t%d" % i) for i, (c, u) in enumerate(zip(cb, ub))], dtype=bytes) if n \
+        else np.zeros(0, "S1")
+    _, mol = np.unique(mol_key, return_inverse=True)
+    n_mol = int(mol.max()) + 1 if n else 0
+    mol_cell = np.zeros(n_mol, dtype=np.int64)
+    mol_cell[mol] = cell_of
+    flags = recs["flags"]
+    ok = (flags & ASSIGNED) != 0
+    # votes per (molecule, feature); per molecule the largest and whether another feature has as many
+    pair, votes = np.unique(np.stack([mol[ok], recs["feature"][ok].astype(np.int64)], axis=1), axis=0, return_counts=True) if ok.any() \
+        else (np.zeros((0, 2), np.int64), np.zeros(0, np.int64))
+    order = np.lexsort((pair[:, 1], -votes, pair[:, 0]))
+    pair, votes = pair[order], votes[order]
+    first = np.flatnonzero(np.concatenate([[True], pair[1:, 0] != pair[:-1, 0]])) if len(pair) else np.zeros(0, np.int64)
+    nxt = first + 1
+    tied = (nxt < len(pair)) & (pair[np.minimum(nxt, len(pair) - 1), 0] == pair[first, 0]) & (votes[np.minimum(nxt, len(pair) - 1)] == votes[first]) \
+        if len(pair) else np.zeros(0, bool)
+    won = first[~tied]
+    entries = {}
+    for m, f in pair[won].tolist():
+        key = (f, int(mol_cell[m]))
+        entries[key] = entries.get(key, 0) + 1
+    counts = dict(reads=n, assigned=int(ok.sum()), tie=int(((flags & TIE) != 0).sum()), low=int(((flags & LOW) != 0).sum()),
+                  crowded=int(((flags & CROWDED) != 0).sum()), molecules=n_mol, counted=len(won), tied=int(tied.sum()))
+    return [c for c in cells.tolist()], entries, counts
+
+
+def count_matrix_text(text, names, assign):
+    """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
+    assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
+    -> ({file name: bytes}, counts dict)"""
+    from .consensus import parse_tagged
+    heads, seqs, cb, ub = parse_tagged(text)
+    take = [i for i, c in enumerate(cb) if c is not None]
+    recs = assign([seqs[i] for i in take])
+    cells, entries, counts = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs)
+    counts["no_cell"] = len(cb) - len(take)
+    rows = ["read\tCB\tUB\tfeature\thits\tsecond\tn_keys\tn_found\tflags\n"]
+    for i, r in zip(take, recs.tolist()):
+        feature, hits, second, n_keys, n_found, flags = r
+        rows.append("%s\t%s\t%s\t%s\t%d\t%d\t%d\t%d\t%s\n" % (
+            heads[i].split(b"\t")[0].decode(), cb[i].decode(), ub[i].decode() if ub[i] is not None else "*",
+            names[feature] if feature != NONE else "*", hits, second, n_keys, n_found, flag_names(flags)))
+    mtx = ["%%MatrixMarket matrix coordinate integer general\n", "%d %d %d\n" % (len(names), len(cells), len(entries))]
+    mtx += ["%d %d %d\n" % (f + 1, c + 1, v) for (f, c), v in sorted(entries.items(), key=lambda e: (e[0][1], e[0][0]))]
+    files = {"features.tsv": "".join("%s\t%s\tGene Expression\n" % (x, x) for x in names).encode(),
+             "barcodes.tsv": b"".join(c + b"\n" for c in cells),
+             "matrix.mtx": "".join(mtx).encode(),
+             "reads.tsv": "".join(rows).encode()}
+    return files, counts
+
+
+# ---------------------------------------------------------------- transcripts ----
+def read_fasta(path):
+    """a (gzipped) FASTA, sequences over any number of lines, upper-cased -> (first words of the headers, sequences as bytes)"""
+    opener = gzip.open if path.endswith(".gz") else open
+    names, seqs, cur = [], [], None
+    with opener(path, "rb") as f:
+        for line in f:
+            line = line.rstrip(b"\r\n")
+            if line.startswith(b">"):
+                if cur is not None:
+                    seqs.append(b"".join(cur).upper())
+                words = line[1:].split()
+                if not words:
+                    raise ValueError("%s: a header without a name" % path)
+                names.append(words[0].decode())
+                cur = []
+            elif line:
+                if cur is None:
+                    raise ValueError("%s: sequence in front of the first header" % path)
+                cur.append(line)
+    if cur is not None:
+        seqs.append(b"".join(cur).upper())
+    return names, seqs
+
+
+def read_tx2gene(path):
+    out = {}
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line:
+                continue
+            cols = line.split("\t")
+            if len(cols) != 2 or not cols[0] or not cols[1]:
+                raise ValueError("%s line %d: two tab-separated columns expected (transcript, gene)" % (path, n))
+            out[cols[0]] = cols[1]
+    return out
+
+
+def features_of(tx_names, tx2gene=None):
+    """-> (feature names in first-appearance order, feature id per transcript uint32)"""
+    ids, names, feat = {}, [], np.zeros(len(tx_names), dtype=np.uint32)
+    for i, t in enumerate(tx_names):
+        if tx2gene is not None and t not in tx2gene:
+            raise ValueError("transcript %s is not in the --tx2gene map" % t)
+        g = tx2gene[t] if tx2gene is not None else t
+        if g not in ids:
+            ids[g] = len(names)
+            names.append(g)
+        feat[i] = ids[g]
+    return names, feat
+
+
+def _flatten(seqs):
+    return (np.frombuffer(b"".join(seqs), dtype=np.uint8),
+            np.concatenate([[0], np.cumsum([len(s) for s in seqs], dtype=np.int64)]).astype(np.uint64))
+
+
+# ---------------------------------------------------------------- the product side ----
+def device_assign(ctx, min_hits):
+    """assign of count_matrix_text on the device: bdg_genes_assign over pieces of at most BATCH_BASES bases"""
+    from . import _native
+
+    def run(seqs):
+        out, at = np.zeros(len(seqs), dtype=_native.GENE_DTYPE), 0
+        while at < len(seqs):
+            end, total = at, 0
+            while end < len(seqs) and (end == at or total + len(seqs[end]) <= BATCH_BASES):
+                total += len(seqs[end])
+                end += 1
+            out[at:end] = ctx.genes_assign(*_flatten(seqs[at:end]), min_hits)
+            at = end
+        return out
+    return run
+
+
+def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0):
+    """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
+    reads.tsv -> counts"""
+    from . import _native
+    tx_names, tx_seqs = read_fasta(transcripts)
+    names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
+    ctx = _native.default_context(device)
+    ctx.genes_index_build(*_flatten(tx_seqs), feat, k)
+    try:
+        stats = ctx.genes_index_stats()
+        files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits))
+    finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
+        ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
+    counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, data in files.items():
+        with open(os.path.join(out_dir, name), "wb") as f:
+            f.write(data)
+    return counts
+
+
+def log_counts(counts, out_dir):
+    logger.info("Genes: %d reads, %d assigned, %d tie, %d low, %d crowded; %d molecules, %d counted, %d tied; %d features of %d "
+                "transcripts, %d keys of %d bases (%d in more than one feature); matrix to %s"
+                % (counts["reads"], counts["assigned"], counts["tie"], counts["low"], counts["crowded"], counts["molecules"],
+                   counts["counted"], counts["tied"], counts.get("features", 0), counts.get("transcripts", 0), counts.get("keys", 0),
+                   counts.get("k", K_DEFAULT), counts.get("ambiguous", 0), out_dir))
+
+
+def gene_k_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if not K_MIN <= x <= K_MAX:
+        raise argparse.ArgumentTypeError("--gene_k takes an integer, 11 .. 31")
+    return x
+
+
+def gene_min_hits_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if x < 1:
+        raise argparse.ArgumentTypeError("--gene_min_hits takes an integer of at least 1")
+    return x
+
+
+def add_gene_options(p):
+    p.add_argument("--gene_k", type=gene_k_arg, default=None, metavar="K",
+                   help="bases of a key of the gene lookup (default %d, 11 .. 31)" % K_DEFAULT)
+    p.add_argument("--gene_min_hits", type=gene_min_hits_arg, default=None, metavar="H",
+                   help="a read is assigned to a gene when at least H of its keys belong to that gene alone, and more than to "
+                        "any other gene (default %d)" % MIN_HITS_DEFAULT)
+
+
+def parse_args(argv):
+    p = argparse.ArgumentParser(description="per-cell gene counts of a tagged FASTA (badger.py --tagged_reads) by k-mer lookup")
+    p.add_argument("-i", "--input", required=True, help="tagged FASTA: every read with CB, and UB where molecules are known")
+    p.add_argument("-t", "--transcripts", required=True, help="transcript FASTA (.gz is read through gzip), mRNA sense")
+    p.add_argument("--tx2gene", default=None, metavar="TSV",
+                   help="transcript<TAB>gene per line: counts are per gene (without it per transcript name)")
+    p.add_argument("-o", "--output", required=True, help="directory for features.tsv, barcodes.tsv, matrix.mtx and reads.tsv")
+    add_gene_options(p)
+    p.add_argument("--device", type=int, default=0, help="MI355X device index")
+    a = p.parse_args(argv)
+    a.gene_k = K_DEFAULT if a.gene_k is None else a.gene_k
+    a.gene_min_hits = MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
+    return a
+
+
+def main(argv):
+    a = parse_args(argv)
+    logger.setLevel(logging.INFO)
+    if not logger.handlers:
+        logger.addHandler(logging.StreamHandler(stream=sys.stdout))
+    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device), a.output)
+
+
+if __name__ == "__main__":
+    from . import _native
+    _native.PRELOAD_TORCH = False            # nothing on this command line's path imports torch
+    main(sys.argv[1:])

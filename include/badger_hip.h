@@ -965,6 +965,55 @@ int  bdg_consensus(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, 
  * value; the band then stays what it was. */
 int  bdg_consensus_set_band(bdg_ctx* ctx, uint32_t band);
 
+/* ---- gene calls by k-mer lookup (--count_matrix; checker: badger_amd/genes.py) ---- */
+#define BDG_GENES_K_MIN         11
+#define BDG_GENES_K_MAX         31
+#define BDG_GENES_K_DEFAULT     21
+#define BDG_GENES_MIN_HITS_DEFAULT 3
+#define BDG_GENES_MAX_FEATURES  256          /* distinct features a read may hit before it is CROWDED */
+#define BDG_GENES_AMBIGUOUS     0xFFFFFFFEu  /* value of a key that occurs in more than one feature */
+#define BDG_GENES_NONE          0xFFFFFFFFu  /* no feature (bdg_gene_rec.feature without any hit) */
+#define BDG_GENE_ASSIGNED       1u           /* bdg_gene_rec.flags: hits >= min_hits and hits > second */
+#define BDG_GENE_LOW            2u           /* ... hits < min_hits */
+#define BDG_GENE_TIE            4u           /* ... hits == second > 0 */
+#define BDG_GENE_CROWDED        8u           /* ... more than BDG_GENES_MAX_FEATURES distinct features hit; no other flag with it */
+typedef struct { uint32_t feature, hits, second, n_keys, n_found, flags; } bdg_gene_rec;
+/* THE RULE.  Bytes are ASCII; any byte other than ACGT (upper case) behaves as N.  Codes: A 0, C 1, G 2, T 3.
+ *   key      a window of k consecutive bases of one sequence, none of them N, has the key sum over j of code(base j) << 2j
+ *            (j = 0 the window's first base); a window with an N, or one that would pass the sequence's end, has none.
+ *            Forward strand only: the cDNA this library writes is in mRNA sense.
+ *   index    over n_seqs sequences, sequence q with the feature id features[q] < BDG_GENES_AMBIGUOUS: value(key) is f if every
+ *            occurrence of the key, in every sequence, belongs to feature f (twice in one sequence, or in two sequences of
+ *            one feature, is still one feature); otherwise BDG_GENES_AMBIGUOUS.
+ *   read     every window with a key is looked up: n_keys counts those windows, n_found the ones whose key is in the index
+ *            (ambiguous ones included); hits[f] is the number of windows whose value is f.  `hits` is the largest hits[f],
+ *            `feature` the smallest f that attains it, `second` the largest hits[f'] over f' != feature (0 if there is none).
+ *            flags: ASSIGNED iff hits >= min_hits and hits > second; otherwise LOW if hits < min_hits and / or TIE if
+ *            hits == second > 0, feature still the smallest maximum (BDG_GENES_NONE without any hit).  A read that hits
+ *            more than BDG_GENES_MAX_FEATURES distinct features: flags CROWDED alone, feature BDG_GENES_NONE,
+ *            hits = second = 0, n_keys and n_found as counted.  A read shorter than k has n_keys = 0.  No length limit.
+ * All of it is sums, maxima and a count of distinct values: no order of evaluation changes it.
+ *   table    open addressing with linear probing over 16-byte slots {u64 key, u32 value, u32 pad}; the capacity is the
+ *            smallest power of two >= 2 * (windows with a key), at least 64; the home slot of a key is
+ *            (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2 capacity).  Which slots are occupied does not depend on the
+ *            order of insertion, so neither do the stats below.
+ * bdg_genes_index_build takes host arrays (sequence q the bytes seq_off[q] .. seq_off[q + 1] - 1 of `bases`), builds the
+ * table on the device and waits for it.  The context holds it like the whitelist; it replaces an earlier one (also where
+ * the call fails behind its argument checks: the context then has none) and goes with bdg_free.  BDG_E_ARG for k outside
+ * 11 .. 31, a feature id >= BDG_GENES_AMBIGUOUS, offsets that decrease; BDG_E_NOMEM where the reserve fails. */
+int  bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                           uint32_t k);
+/* out: windows with a key | distinct keys | ambiguous keys | slots | the longest run of occupied slots (cyclic: a lookup
+ * reads at most one slot more than that - the longest probe chain the table can ask for) | keys stored in front of their home
+ * slot, that is past a wrap of the table's end.  BDG_E_ARG without an index. */
+int  bdg_genes_index_stats(bdg_ctx* ctx, uint64_t out[6]);
+/* Read r is the bytes d_off[r] .. d_off[r + 1] - 1 of d_bases (d_off [n + 1], non-decreasing: not checked); d_out [n].
+ * Asynchronous, on the context's stream.  BDG_E_ARG without an index or with min_hits == 0. */
+int  bdg_genes_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits,
+                          bdg_gene_rec* d_out);
+/* The same over host arrays; synchronous; also BDG_E_ARG for offsets that decrease. */
+int  bdg_genes_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, bdg_gene_rec* out);
+
 /* ---- stage 2's read-side plumbing on the host (badger.py:112-121,129; barcode_graph.py:388-410) -------------- */
 /* Read ids of a run, kept natively (12 bytes per read instead of a Python string each). */
 typedef struct bdg_idstore bdg_idstore;

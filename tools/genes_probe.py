@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Measurements of the gene calls by k-mer lookup, one JSON line each to --out (and stdout).
+
+    python tools/genes_probe.py --device [--reads 1000000] [--tx_bases 4000000 100000000] --out profiles/r22_genes.jsonl
+        bdg_genes_index_build and bdg_genes_assign_dev alone.  Per --tx_bases value a random transcriptome of that many bases in
+        transcripts of 2,000, a feature each: 4 M bases give a table of 134 MB, which the Infinity Cache holds, 100 M bases one
+        of 4.3 GB, which it does not.  The reads are 3' fragments of 300 .. 1,500 bases of random transcripts at synth's error
+        rates, every fifth read random, device-resident: wall time of the build (upload, the host's window count, the kernels)
+        and of an assign call, and the kernels from the library's event timers.
+    python tools/genes_probe.py --cli [--cli_reads 1000000] [--pairs 3] [--parent DIR] --out ...
+        the stage-2 command line on consensus_probe's FASTQ file (every read with four siblings), as alternating pairs of fresh
+        processes: --tagged_reads --umi_dedup with --count_matrix against without, the transcripts being the middles of the
+        first 20,000 reads in both senses; and, with --parent DIR (a built checkout of the parent commit), this build with the
+        flags off against the parent, beside parent against parent.
+"""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from umi_dedup_probe import emit  # noqa: E402
+
+ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+TX_LEN = 2000
+
+
+def fragments(tx, n_reads, seed=1, lo=300, hi=1500, chunk=50000):
+    """tx: codes of the transcripts [n_tx, TX_LEN] -> (bases uint8 ASCII, off uint64 [n + 1])"""
+    rng = np.random.default_rng(seed)
+    parts, lens = [], []
+    for r0 in range(0, n_reads, chunk):
+        m = min(chunk, n_reads - r0)
+        L = rng.integers(lo, hi + 1, m)
+        t = rng.integers(0, len(tx), m)
+        r_off = np.concatenate([[0], np.cumsum(L)])
+        rid = np.repeat(np.arange(m), L)
+        pos = np.arange(int(r_off[-1])) - r_off[rid]
+        codes = tx[t[rid], TX_LEN - L[rid] + pos]
+        random_read = (np.arange(r0, r0 + m) % 5 == 4)[rid]
+        codes = np.where(random_read, rng.integers(0, 4, len(codes), dtype=np.uint8), codes).astype(np.uint8)
+        u = rng.random(len(codes))
+        is_del, is_sub, is_ins = u < 0.03, (u >= 0.03) & (u < 0.06), (u >= 0.06) & (u < 0.08)
+        codes = np.where(is_sub, (codes + rng.integers(1, 4, len(codes), dtype=np.uint8)) & 3, codes).astype(np.uint8)
+        cnt = (~is_del).astype(np.int64) + is_ins
+        at = np.cumsum(cnt) - cnt
+        out = np.empty(int(cnt.sum()), dtype=np.uint8)
+        out[at[~is_del]] = codes[~is_del]
+        out[(at + ~is_del)[is_ins]] = rng.integers(0, 4, int(is_ins.sum()), dtype=np.uint8)
+        parts.append(ACGT[out])
+        lens.append(np.diff(np.concatenate([at, [int(cnt.sum())]])[r_off]))
+    return np.concatenate(parts), np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.uint64)
+
+
+def device_probe(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for tx_bases in args.tx_bases:
+        n_tx = max(tx_bases // TX_LEN, 1)
+        tx = np.random.default_rng(7).integers(0, 4, (n_tx, TX_LEN), dtype=np.uint8)
+        bases, off = fragments(tx, args.reads)
+        n = len(off) - 1
+        tx_ascii, tx_off = ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64)
+        feat = np.arange(n_tx, dtype=np.uint32)
+        ctx.genes_index_build(tx_ascii, tx_off, feat, args.k)             # (warm: the first allocation of this size)
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        ctx.genes_index_build(tx_ascii, tx_off, feat, args.k)
+        build_s = time.perf_counter() - t0
+        build_kt = {k: round(v[1], 4) for k, v in ctx.profile_read().items() if k.startswith("k_genes") and v[0]}
+        ctx.profile(False)
+        stats = [int(x) for x in ctx.genes_index_stats()]
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off)]
+        d_out = _native.DeviceArray(ctx, n * 6, np.uint32)
+        call = lambda: ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, d_out)  # noqa: E731
+        call()
+        ctx.synchronize()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            call()
+            ctx.synchronize()
+            times.append(time.perf_counter() - t0)
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(args.reps):
+            call()
+        ctx.synchronize()
+        kt = {k: round(v[1] / args.reps, 4) for k, v in ctx.profile_read().items() if k.startswith("k_genes") and v[0]}
+        ctx.profile(False)
+        recs = d_out.to_host().view(_native.GENE_DTYPE)
+        emit(args.out, {"what": "bdg_genes_index_build, bdg_genes_assign_dev, device-resident", "k": args.k, "min_hits": args.min_hits,
+                        "transcripts": n_tx, "transcript_bases": int(n_tx * TX_LEN), "table_bytes": 16 * stats[3],
+                        "stats": dict(zip(("windows", "keys", "ambiguous", "slots", "longest_run", "wrapped"), stats)),
+                        "build_wall_s": round(build_s, 3), "build_kernel_ms": build_kt,
+                        "reads": n, "read_bases": int(off[-1]), "windows_looked_up": int(recs["n_keys"].astype(np.int64).sum()),
+                        "found": int(recs["n_found"].astype(np.int64).sum()), "assigned": int((recs["flags"] & 1 != 0).sum()),
+                        "low": int((recs["flags"] & 2 != 0).sum()), "assign_call_ms_median": round(1e3 * float(np.median(times)), 3),
+                        "assign_call_ms_min": round(1e3 * min(times), 3), "assign_kernel_ms": kt,
+                        "assign_kernel_ms_per_1M_reads": {k: round(v * 1e6 / n, 3) for k, v in kt.items()}})
+        for a in d + [d_out]:
+            a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+
+
+def _transcripts_of(fq, path, n=20000):
+    """the middles of the first n reads of a FASTQ file, as they are and reverse-complemented, as a transcript FASTA"""
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    with open(fq, "rb") as f, open(path, "wb") as out:
+        for i in range(n):
+            f.readline()
+            s = f.readline().strip()
+            f.readline()
+            f.readline()
+            if len(s) < 520:
+                continue
+            mid = s[200:-200]
+            out.write(b">t%df\n%s\n>t%dr\n%s\n" % (i, mid, i, mid.translate(comp)[::-1]))
+
+
+def cli_probe(args):
+    from consensus_probe import _fastq
+    tmp = tempfile.mkdtemp(prefix="genes_probe_")
+    fq, wl = _fastq(args.cli_reads, tmp)
+    tx = os.path.join(tmp, "tx.fa")
+    _transcripts_of(fq, tx)
+    args_of = lambda out: ["-m", "badger_amd.badger", "-r", fq, "-d", "tenX_v3", "-l", wl, "-c", "5000", "-tr", "4", "-o", os.path.join(tmp, out)]  # noqa: E731
+
+    def run(cwd, out, extra):
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
+        if r.returncode != 0:
+            raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
+        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l]
+
+    def pairs(name_a, a, name_b, b, what):
+        walls, said = {name_a: [], name_b: []}, []
+        for _ in range(args.pairs):
+            for name, (cwd, extra) in ((name_a, a), (name_b, b)):
+                t, lines = run(cwd, name.replace(" ", "_"), extra)
+                walls[name].append(t)
+                said = lines or said
+        ma, mb = float(np.median(walls[name_a])), float(np.median(walls[name_b]))
+        emit(args.out, {"what": what, "reads": args.cli_reads, "pairs": args.pairs, "fastq_bytes": os.path.getsize(fq),
+                        name_a + "_s": [round(x, 3) for x in walls[name_a]], name_b + "_s": [round(x, 3) for x in walls[name_b]],
+                        "median_" + name_a + "_s": round(ma, 3), "median_" + name_b + "_s": round(mb, 3),
+                        "spread_" + name_a + "_s": round(max(walls[name_a]) - min(walls[name_a]), 3),
+                        "spread_" + name_b + "_s": round(max(walls[name_b]) - min(walls[name_b]), 3),
+                        "ratio_%s_over_%s" % (name_b, name_a): round(mb / ma, 3), "log": said})
+
+    fa = os.path.join(tmp, "tagged.fa")
+    tagged = ["--umi_dedup", "--tagged_reads", fa]
+    run(ROOT, "warm", tagged)                                          # (the file into the page cache, the runtime's caches)
+    pairs("tagged", (ROOT, tagged), "count_matrix", (ROOT, tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]),
+          "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: with --count_matrix against without")
+    if args.parent:
+        parent = os.path.abspath(args.parent)
+        pairs("parent", (parent, tagged), "flags_off", (ROOT, tagged), "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: this build with the flags off against the parent commit's")
+        pairs("parent_a", (parent, tagged), "parent_b", (parent, tagged), "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: the parent commit's build against itself")
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--device", action="store_true")
+    p.add_argument("--cli", action="store_true")
+    p.add_argument("--reads", type=int, default=1000000)
+    p.add_argument("--tx_bases", type=int, nargs="+", default=[4000000, 100000000], help="bases of each transcriptome to measure")
+    p.add_argument("--k", type=int, default=21)
+    p.add_argument("--min_hits", type=int, default=3)
+    p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--cli_reads", type=int, default=1000000)
+    p.add_argument("--pairs", type=int, default=3)
+    p.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    p.add_argument("--out", default=None)
+    args = p.parse_args()
+    if args.device:
+        device_probe(args)
+    if args.cli:
+        cli_probe(args)
+
+
+if __name__ == "__main__":
+    main()
