@@ -52,6 +52,11 @@ GENE_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), (
 GENES_K_MIN, GENES_K_MAX, GENES_K_DEFAULT, GENES_MIN_HITS_DEFAULT, GENES_MAX_FEATURES = 11, 31, 21, 3, 256
 GENES_AMBIGUOUS, GENES_NONE = 0xFFFFFFFE, 0xFFFFFFFF
 GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
+# bdg_iso_rec: the transcripts of its gene a read is compatible with (bdg_iso_assign; the rule in badger_amd/genes.py)
+ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("second", "<u4"), ("n_gene", "<u4"), ("flags", "<u4"),
+                      ("pad", "<u4")])
+ISO_LOCAL_MAX, ISO_MARGIN_DEFAULT = 63, 1
+ISO_UNIQUE, ISO_MULTI, ISO_NOGENE = 1, 2, 4
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -87,6 +92,7 @@ EXPORTS = [
     "bdg_rescue_batch", "bdg_rescue_batch_dev", "bdg_extract_set_rescue", "bdg_extract_rescue_resolve", "bdg_rescue_counts",
     "bdg_consensus", "bdg_consensus_dev", "bdg_consensus_set_band",
     "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
+    "bdg_genes_index_build_iso", "bdg_iso_assign", "bdg_iso_assign_dev",
 ]
 
 
@@ -356,6 +362,9 @@ def load():
     L.bdg_genes_index_stats.argtypes = [vp, vp]
     L.bdg_genes_assign.argtypes = [vp, vp, vp, u32, u32, vp]
     L.bdg_genes_assign_dev.argtypes = [vp, vp, vp, u32, u32, vp]
+    L.bdg_genes_index_build_iso.argtypes = [vp, vp, vp, u32, vp, vp, u32]
+    L.bdg_iso_assign.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
+    L.bdg_iso_assign_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
     L.bdg_consensus_set_band.argtypes = [vp, u32]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
@@ -705,6 +714,33 @@ class Context:
     def genes_assign_dev(self, d_bases, d_off, n, min_hits, d_out):
         """bdg_genes_assign_dev: the same over device arrays, asynchronous"""
         self._check(self.lib.bdg_genes_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), int(min_hits), _ptr(d_out)))
+
+    def genes_index_build_iso(self, bases, seq_off, features, local, k=GENES_K_DEFAULT):
+        """genes_index_build plus, per key, the mask of the local indices (uint8 [n], each <= 63) of the sequences that hold
+        it (bdg_genes_index_build_iso)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        features = np.ascontiguousarray(features, dtype=np.uint32)
+        local = np.ascontiguousarray(local, dtype=np.uint8)
+        if len(seq_off) != len(features) + 1 or len(local) != len(features):
+            raise ValueError("seq_off holds one entry more than features, local as many")
+        self._check(self.lib.bdg_genes_index_build_iso(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data,
+                                                       local.ctypes.data, int(k)))
+
+    def iso_assign(self, bases, off, min_hits=GENES_MIN_HITS_DEFAULT, margin=ISO_MARGIN_DEFAULT):
+        """the gene call and the compatible transcripts of every read over host arrays (bdg_iso_assign)
+        -> (GENE_DTYPE [n], ISO_DTYPE [n])"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        gene, iso = np.zeros(n, dtype=GENE_DTYPE), np.zeros(n, dtype=ISO_DTYPE)
+        self._check(self.lib.bdg_iso_assign(self.h, bases.ctypes.data, off.ctypes.data, n, int(min_hits), int(margin), gene.ctypes.data,
+                                            iso.ctypes.data))
+        return gene, iso
+
+    def iso_assign_dev(self, d_bases, d_off, n, d_gene_recs, margin, d_out):
+        """bdg_iso_assign_dev: the compatible transcripts over device arrays and the gene records of the same reads, asynchronous"""
+        self._check(self.lib.bdg_iso_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs), int(margin), _ptr(d_out)))
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""

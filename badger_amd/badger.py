@@ -7,6 +7,7 @@
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --umi_dedup --molecule_consensus consensus.fa
                                 [--consensus_band 64|128|256]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
+                                [--isoforms [--iso_margin 1]]
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -24,6 +25,10 @@ molecule from it (consensus.py: the reads of a molecule aligned to its longest r
 --count_matrix DIR, with or without --umi_dedup and independent of --molecule_consensus, calls the gene of every read of the tagged
 file by k-mer lookup in --transcripts (genes.py: a table of the k-mers that belong to one gene only, on the device) and writes the
 features x barcodes matrix in MatrixMarket form with its two name files, plus reads.tsv with every read's call.
+--isoforms (with --tx2gene) adds, in a second pass over the same reads on the device, the transcripts of its gene that every
+read is compatible with, and per molecule the intersection: transcripts.tsv, isoform_matrix.mtx (molecules that name one transcript),
+classes.tsv with class_matrix.mtx (transcript compatibility counts) and read_isoforms.tsv in DIR; the four files of the matrix
+stay the same bytes.
 Every other output is the same bytes with and without these flags.
 
 -d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
@@ -45,7 +50,7 @@ from traceback import print_exc
 
 from . import _native
 from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
-from .genes import K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HITS_DEFAULT, add_gene_options
+from .genes import K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HITS_DEFAULT, add_gene_options, check_iso_options
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -130,6 +135,7 @@ def parse_args(args):
         p.error("--transcripts, --tx2gene, --gene_k and --gene_min_hits need --count_matrix")
     a.gene_k = GENE_K_DEFAULT if a.gene_k is None else a.gene_k
     a.gene_min_hits = GENE_MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
+    check_iso_options(p, a, bool(a.count_matrix))
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
@@ -296,7 +302,7 @@ def write_count_matrix(args):
     """behind write_tagged_reads, on the file it wrote"""
     from .genes import count_matrix_of_tagged, log_counts
     counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
-                                    args.gene_min_hits, args.device)
+                                    args.gene_min_hits, args.device, args.iso_margin)
     log_counts(counts, args.count_matrix)
 
 

@@ -149,6 +149,8 @@ struct bdg_ctx {
     uint32_t gn_k = 0;
     uint64_t gn_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_genes_index_stats
     int gn_cus = 0, gn_assign_per_cu = 0;    // compute units, and blocks of k_genes_assign resident on one (asked once)
+    DevBuf gn_mask;      // u64 per slot: the transcripts of its gene that hold the slot's key (bdg_genes_index_build_iso only)
+    int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -22,6 +22,8 @@
 //                  four entries a lane: no LDS atomics.  The 257th feature sets CROWDED.  Best and second best are two wave
 //                  reductions with the tie rule.
 // k_genes_stats    the table's occupancy figures, none of which depends on the order of insertion.
+// k_iso_insert, k_iso_assign   the transcripts of its gene that hold a key, and a read's counts of them: below,
+//                  behind the gene kernels whose planes, keys and probe they share.
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
 
@@ -35,7 +37,7 @@ constexpr uint32_t GENES_CHUNKS = 4;                         // chunks of 64 win
 constexpr uint32_t INSERT_WAVES_PER_CU = 16;                  // (k_genes_assign: as many as the device keeps resident, asked once)
 
 struct __align__(16) GeneSlot { unsigned long long key; uint32_t value, pad; };
-static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24, "layouts the header states");
+static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24 && sizeof(bdg_iso_rec) == 32, "layouts the header states");
 
 struct Planes { uint64_t lo, hi, nv; };
 
@@ -171,6 +173,51 @@ void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t 
     }
 }
 
+// The probe of GENES_CHUNKS x 64 windows, stated once for k_genes_assign and k_iso_assign.  It declares, in the caller's scope,
+// key[c] (this lane's key of chunk c, KEY_EMPTY: none), got[c] (the slot its chain ends at: its key's, or an empty one) and
+// sl[c] (that slot's index).  Every first probe is on its way before one is looked at (a lane without a key reads slot 0 and
+// drops it: no branch around a load and no arithmetic between two of them).  The chains: a window whose home slot holds
+// another key goes on, all four chunks in step and two slots a round, so that a round is one trip to memory for the wave - the
+// longest chain among its 256 windows, halved, is what it waits for, not the sum over the chunks.  A lane that is done reads
+// slot 0 and drops it.  A macro and not a function: through an inlined function's array references the same statements cost
+// k_genes_assign 8 VGPRs more (84, a resident wave per SIMD fewer); as a macro its code is what it was, instruction for
+// instruction.
+#define GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)                                                                      \
+    uint32_t byte[GENES_CHUNKS + 1];                                                                                                     \
+    Planes P[GENES_CHUNKS + 1];                                                                                                          \
+    _Pragma("unroll")                                                                                                                    \
+    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = load_byte(s, len, p0 + 64 * c, lane);                                         \
+    _Pragma("unroll")                                                                                                                    \
+    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = planes_of(byte[c]);                                                              \
+    unsigned long long key[GENES_CHUNKS];                                                                                                \
+    ulonglong2 got[GENES_CHUNKS];                                                                                                        \
+    _Pragma("unroll")                                                                                                                    \
+    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) key[c] = window_key(P[c], P[c + 1], lane, kmask);                                        \
+    uint64_t sl[GENES_CHUNKS];                                                                                                           \
+    _Pragma("unroll")                                                                                                                    \
+    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) sl[c] = key[c] != KEY_EMPTY ? home_slot(key[c], shift) : 0;                              \
+    _Pragma("unroll")                                                                                                                    \
+    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) got[c] = *reinterpret_cast<const ulonglong2*>(table + sl[c]);                            \
+    for (;;) {                                                                                                                           \
+        bool open[GENES_CHUNKS], any = false;                                                                                            \
+        _Pragma("unroll")                                                                                                                \
+        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) any |= open[c] = key[c] != KEY_EMPTY && got[c].x != KEY_EMPTY && got[c].x != key[c]; \
+        if (!__any(any)) break;                                                                                                          \
+        ulonglong2 t1[GENES_CHUNKS], t2[GENES_CHUNKS];                                                                                   \
+        _Pragma("unroll")                                                                                                                \
+        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                    \
+            t1[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 1) & mask : 0));                                    \
+            t2[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 2) & mask : 0));                                    \
+        }                                                                                                                                \
+        _Pragma("unroll")                                                                                                                \
+        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                    \
+            if (!open[c]) continue;                                                                                                      \
+            const bool ends = t1[c].x == KEY_EMPTY || t1[c].x == key[c];                                                                 \
+            got[c] = ends ? t1[c] : t2[c];                                                                                               \
+            sl[c] = (sl[c] + (ends ? 1 : 2)) & mask;                                                                                     \
+        }                                                                                                                                \
+    }
+
 __global__ __launch_bounds__(64)
 void k_genes_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k, uint32_t min_hits,
                     const GeneSlot* __restrict__ table, uint64_t mask, uint32_t shift, bdg_gene_rec* __restrict__ out)
@@ -183,45 +230,7 @@ void k_genes_assign(const uint8_t* __restrict__ bases, const uint64_t* __restric
         uint32_t n_ent = 0, n_keys = 0, n_found = 0;
         bool crowded = false;
         for (uint64_t p0 = 0; p0 + k <= len; p0 += 64 * GENES_CHUNKS) {
-            uint32_t byte[GENES_CHUNKS + 1];
-            Planes P[GENES_CHUNKS + 1];
-#pragma unroll
-            for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = load_byte(s, len, p0 + 64 * c, lane);   // (all on their way, then the ballots)
-#pragma unroll
-            for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = planes_of(byte[c]);
-            unsigned long long key[GENES_CHUNKS];
-            ulonglong2 got[GENES_CHUNKS];
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) key[c] = window_key(P[c], P[c + 1], lane, kmask);
-            // every first probe is on its way before one is looked at (a lane without a key reads slot 0 and drops it: no branch
-            // around a load and no arithmetic between two of them)
-            uint64_t sl[GENES_CHUNKS];
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) sl[c] = key[c] != KEY_EMPTY ? home_slot(key[c], shift) : 0;
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) got[c] = *reinterpret_cast<const ulonglong2*>(table + sl[c]);
-            // the chains: a window whose home slot holds another key goes on, all four chunks in step and two slots a round,
-            // so that a round is one trip to memory for the wave - the longest chain among its 256 windows, halved, is what it
-            // waits for, not the sum over the chunks.  A lane that is done reads slot 0 and drops it (no branch around a load).
-            for (;;) {
-                bool open[GENES_CHUNKS], any = false;
-#pragma unroll
-                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) any |= open[c] = key[c] != KEY_EMPTY && got[c].x != KEY_EMPTY && got[c].x != key[c];
-                if (!__any(any)) break;
-                ulonglong2 t1[GENES_CHUNKS], t2[GENES_CHUNKS];
-#pragma unroll
-                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
-                    t1[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 1) & mask : 0));
-                    t2[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 2) & mask : 0));
-                }
-#pragma unroll
-                for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
-                    if (!open[c]) continue;
-                    const bool ends = t1[c].x == KEY_EMPTY || t1[c].x == key[c];      // the chain ends at the first of the two
-                    got[c] = ends ? t1[c] : t2[c];
-                    sl[c] = (sl[c] + (ends ? 1 : 2)) & mask;
-                }
-            }
+            GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)
 #pragma unroll
             for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
                 const bool has_key = key[c] != KEY_EMPTY;
@@ -286,6 +295,110 @@ void k_genes_assign(const uint8_t* __restrict__ bases, const uint64_t* __restric
     }
 }
 
+// ---- transcript compatibility (include/badger_hip.h at bdg_genes_index_build_iso states the rule) ----
+// k_iso_insert   runs behind k_genes_insert, when every key sits in its slot: a lane walks to its key's slot without writing
+//                and ors the sequence's bit into the 64-bit word beside that slot.  DESIGN 4.0 as in k_genes_insert: a lane
+//                whose left neighbour holds the same key does nothing, a word that already has the bit costs a load and no
+//                atomic, and of the lanes that are left the first of each group of equal keys (adjacent or not) ors for all.
+// k_iso_assign   a second pass over the reads that k_genes_assign gave a gene: the same probe, then the word of every window
+//                whose value is that gene - all four chunks' gathers before one is used.  Lane t owns cnt[t]; the loop over
+//                the distinct words of a chunk (first live lane's word, ballot of its equals, popcount) adds the count to
+//                every lane whose bit the word has: one round where the read lies in shared exons.  No LDS, no barrier.
+__global__ __launch_bounds__(64)
+void k_iso_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint8_t* __restrict__ local,
+                  uint32_t n_seqs, uint32_t k, const GeneSlot* table, unsigned long long* tx_mask, uint64_t mask, uint32_t shift)
+{
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
+        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets, and local[q] <= 63)
+        if (len < k) continue;
+        const uint8_t* s = bases + b;
+        const unsigned long long bit = 1ull << (local[q] & 63u);
+        Planes A = load_planes(s, len, 0, lane);
+        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
+            const Planes B = load_planes(s, len, p0 + 64, lane);
+            unsigned long long key = window_key(A, B, lane, kmask);
+            const unsigned long long left = __shfl_up(key, 1);
+            if (lane && left == key) key = KEY_EMPTY;
+            uint64_t at = 0;
+            bool need = false;
+            if (key != KEY_EMPTY) {
+                at = home_slot(key, shift);
+                unsigned long long cur;
+                while ((cur = table[at].key) != key && cur != KEY_EMPTY) at = (at + 1) & mask;   // (k_genes_insert stored it: found)
+                need = cur == key && !(__hip_atomic_load(&tx_mask[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit);
+            }
+            bool lead = false;
+            uint64_t live = __ballot(need);
+            while (live) {                                          // one round per distinct key that still lacks the bit
+                const uint32_t first = __ffsll((unsigned long long)live) - 1;
+                const unsigned long long kk = __shfl(key, first);
+                lead |= lane == first;
+                live &= ~__ballot(need && key == kk);
+            }
+            if (lead) atomicOr(&tx_mask[at], bit);
+            A = B;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64)
+void k_iso_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k,
+                  const bdg_gene_rec* __restrict__ genes, uint32_t margin, const GeneSlot* __restrict__ table,
+                  const unsigned long long* __restrict__ tx_mask, uint64_t mask, uint32_t shift, bdg_iso_rec* __restrict__ out)
+{
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
+        const uint32_t f = genes[r].feature;
+        if (!(genes[r].flags & BDG_GENE_ASSIGNED)) {                // none of its bases is read
+            if (lane == 0) {
+                bdg_iso_rec rec;
+                rec.compat = 0; rec.feature = BDG_GENES_NONE; rec.best = rec.second = rec.n_gene = 0; rec.flags = BDG_ISO_NOGENE; rec.pad = 0;
+                out[r] = rec;
+            }
+            continue;
+        }
+        const uint64_t b = off[r], e = off[r + 1], len = e > b ? e - b : 0;
+        const uint8_t* s = bases + b;
+        uint32_t cnt = 0, n_gene = 0;                               // cnt: of the transcript whose local index is this lane
+        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64 * GENES_CHUNKS) {
+            GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)
+            bool hit[GENES_CHUNKS];
+            unsigned long long m[GENES_CHUNKS];
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) hit[c] = key[c] != KEY_EMPTY && got[c].x == key[c] && (uint32_t)got[c].y == f;
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) m[c] = tx_mask[hit[c] ? sl[c] : 0];     // (a lane without a hit drops it)
+#pragma unroll
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
+                uint64_t live = __ballot(hit[c]);
+                n_gene += __popcll(live);
+                while (live) {                                      // one round per distinct word among the 64
+                    const unsigned long long mm = __shfl(m[c], __ffsll((unsigned long long)live) - 1);
+                    const uint64_t same = __ballot(hit[c] && m[c] == mm);
+                    cnt += (uint32_t)__popcll(same) * (uint32_t)((mm >> lane) & 1u);
+                    live &= ~same;
+                }
+            }
+        }
+        uint32_t best = cnt;
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d));
+        uint32_t second = cnt < best ? cnt : 0;
+#pragma unroll
+        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));
+        const uint64_t compat = __ballot(cnt > 0 && best - cnt < margin);
+        if (lane == 0) {
+            bdg_iso_rec rec;
+            rec.compat = compat; rec.feature = f; rec.best = best; rec.second = second; rec.n_gene = n_gene;
+            const uint32_t bits = __popcll(compat);
+            rec.flags = bits == 1 ? BDG_ISO_UNIQUE : bits > 1 ? BDG_ISO_MULTI : 0u;
+            rec.pad = 0;
+            out[r] = rec;
+        }
+    }
+}
+
 int genes_cus(bdg_ctx* ctx)
 {
     if (ctx->gn_cus == 0) {
@@ -322,19 +435,45 @@ int genes_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_
     return BDG_OK;
 }
 
-}  // namespace
+int iso_check_assign(bdg_ctx* ctx, uint32_t margin)
+{
+    if (ctx->gn_slots == 0 || !ctx->gn_mask.p) return bdg_fail(ctx, BDG_E_ARG, "isoforms: no index with masks built (bdg_genes_index_build_iso)");
+    if (margin == 0) return bdg_fail(ctx, BDG_E_ARG, "isoforms: margin must be at least 1");
+    return BDG_OK;
+}
 
-extern "C" {
+int iso_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes, uint32_t margin,
+                      bdg_iso_rec* d_out)
+{
+    if (int rc = genes_cus(ctx)) return rc;
+    if (ctx->gn_iso_per_cu == 0) {
+        int per_cu = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iso_assign, 64, 0));
+        ctx->gn_iso_per_cu = per_cu < 1 ? 1 : per_cu;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_iso_per_cu);
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
+    {
+        ScopedKernelTimer tm(ctx, "k_iso_assign");
+        hipLaunchKernelGGL(k_iso_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->gn_k, d_genes, margin,
+                           static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
+                           ctx->gn_slots - 1, shift, d_out);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
 
-int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
-                          uint32_t k)
+// bdg_genes_index_build, and with `local` bdg_genes_index_build_iso
+int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                      const uint8_t* local, bool with_masks, uint32_t k)
 {
     if (!ctx) return BDG_E_ARG;
     if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "genes: k out of range (11 .. 31)");
-    if (!seq_off || (n_seqs && !features)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (!seq_off || (n_seqs && !features) || (with_masks && n_seqs && !local)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     for (uint32_t q = 0; q < n_seqs; ++q) {
         if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "genes: sequence offsets must be non-decreasing");
         if (features[q] >= BDG_GENES_AMBIGUOUS) return bdg_fail(ctx, BDG_E_ARG, "genes: feature id reserved (>= 0xFFFFFFFE)");
+        if (with_masks && local[q] > BDG_ISO_LOCAL_MAX) return bdg_fail(ctx, BDG_E_ARG, "isoforms: local index above 63");
     }
     const uint64_t end = seq_off[n_seqs];
     if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
@@ -356,16 +495,23 @@ int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* se
     hipStream_t st = ctx->stream;
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (a queued assign call may still read the earlier table)
     ctx->gn_table.reset();
+    ctx->gn_mask.reset();
     ctx->gn_slots = 0;
     ctx->gn_k = 0;
     int rc;
     if ((rc = genes_cus(ctx))) return rc;
     // the sequences, their offsets and features and the four counters live for this call only
-    DevBuf d_bases, d_meta;
+    DevBuf d_bases, d_meta, d_local;
     const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), feat_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u;
     if ((rc = bdg_reserve(ctx, ctx->gn_table, sizeof(GeneSlot) * (size_t)slots))) { ctx->gn_table.reset(); return rc; }
     if ((rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + 4 * sizeof(uint64_t)))) {
         ctx->gn_table.reset();
+        return rc;
+    }
+    // the masks beside the table, and the local indices for this call, only where they are asked for
+    if (with_masks && ((rc = bdg_reserve(ctx, ctx->gn_mask, sizeof(uint64_t) * (size_t)slots)) || (rc = bdg_reserve(ctx, d_local, (size_t)n_seqs + 1)))) {
+        ctx->gn_table.reset();
+        ctx->gn_mask.reset();
         return rc;
     }
     auto* d_off = static_cast<uint64_t*>(d_meta.p);
@@ -385,6 +531,17 @@ int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* se
             hipLaunchKernelGGL(k_genes_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_feat, n_seqs, k,
                                static_cast<GeneSlot*>(ctx->gn_table.p), slots - 1, shift);
         }
+        if (with_masks) {
+            BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_mask.p, 0, sizeof(uint64_t) * (size_t)slots, st));
+            if (n_seqs) {
+                BDG_HIP_TRY(ctx, hipMemcpyAsync(d_local.p, local, (size_t)n_seqs, hipMemcpyHostToDevice, st));
+                ScopedKernelTimer tm(ctx, "k_iso_insert");
+                const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * INSERT_WAVES_PER_CU);
+                hipLaunchKernelGGL(k_iso_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off,
+                                   static_cast<const uint8_t*>(d_local.p), n_seqs, k, static_cast<const GeneSlot*>(ctx->gn_table.p),
+                                   static_cast<unsigned long long*>(ctx->gn_mask.p), slots - 1, shift);
+            }
+        }
         {
             ScopedKernelTimer tm(ctx, "k_genes_stats");
             const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->gn_cus * 8);
@@ -398,6 +555,7 @@ int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* se
     if ((rc = run())) {
         (void)hipStreamSynchronize(st);                             // (the temporaries go with this frame)
         ctx->gn_table.reset();
+        ctx->gn_mask.reset();
         return rc;
     }
     const uint64_t stats[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
@@ -405,6 +563,22 @@ int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* se
     ctx->gn_k = k;
     ctx->gn_slots = slots;
     return BDG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                          uint32_t k)
+{
+    return genes_index_build(ctx, bases, seq_off, n_seqs, features, nullptr, false, k);
+}
+
+int bdg_genes_index_build_iso(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                              const uint8_t* local, uint32_t k)
+{
+    return genes_index_build(ctx, bases, seq_off, n_seqs, features, local, true, k);
 }
 
 int bdg_genes_index_stats(bdg_ctx* ctx, uint64_t out[6])
@@ -449,6 +623,51 @@ int bdg_genes_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, ui
     BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
     if ((rc = genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_out))) return rc;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, rec_b, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
+
+int bdg_iso_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_gene_recs,
+                       uint32_t margin, bdg_iso_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = iso_check_assign(ctx, margin)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!d_off || !d_gene_recs || !d_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return iso_assign_launch(ctx, d_bases, d_off, n, d_gene_recs, margin, d_out);
+}
+
+int bdg_iso_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, uint32_t margin,
+                   bdg_gene_rec* gene_out, bdg_iso_rec* iso_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (int rc = iso_check_assign(ctx, margin)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!off || !gene_out || !iso_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    for (uint32_t r = 0; r < n; ++r)
+        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
+    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // one staging buffer for both records: the gene records, then the isoform records (32 bytes each, the start a multiple of 32)
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), gene_b = (sizeof(bdg_gene_rec) * (size_t)n + 31u) & ~(size_t)31u,
+                 iso_b = sizeof(bdg_iso_rec) * (size_t)n;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, gene_b + iso_b))) return rc;
+    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
+    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
+    auto* d_gene = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
+    auto* d_iso = reinterpret_cast<bdg_iso_rec*>(static_cast<char*>(ctx->s_out0.p) + gene_b);
+    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
+    if ((rc = genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_gene))) return rc;
+    if ((rc = iso_assign_launch(ctx, d_bases, d_off, n, d_gene, margin, d_iso))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(gene_out, d_gene, sizeof(bdg_gene_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(iso_out, d_iso, iso_b, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     return BDG_OK;
 }

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Per-cell gene counts by k-mer lookup (stage 2's --count_matrix).
+"""Per-cell gene counts by k-mer lookup (stage 2's --count_matrix), and with --isoforms the transcripts of its gene
+that every read and molecule is compatible with.
 
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
+                               [--isoforms [--iso_margin 1]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -24,6 +26,25 @@ The rule.  Any byte other than ACGT behaves as N; codes A 0, C 1, G 2, T 3.
               without UB is a molecule of its own.  A molecule's feature is the one named by strictly more of its ASSIGNED
               reads than any other; a tie, or no assigned read, leaves it uncounted.
     matrix    entry (feature, CB) = the molecules of that cell counted for that feature.
+
+The isoform rule, on top of it (include/badger_hip.h at bdg_genes_index_build_iso).  Integers, sums, ORs and maxima only.
+    local     local[q] of transcript q: its order of first appearance in the transcript file among the transcripts of its
+              feature, capped at 63 - bit 63 stands for the 64th transcript of the gene and every later one; a gene with more
+              than 64 transcripts is overflowing.
+    mask      mask(key): the OR of 1 << local[q] over every occurrence of the key in every sequence, whatever their features.
+              Only the mask of a key whose value is a feature is ever used.
+    read      with an ASSIGNED gene record of feature f (the same min_hits), over its windows whose value is f: n_gene their
+              number (the gene record's hits), cnt[t] those whose mask has bit t, best = max cnt, second the largest cnt below
+              best (0 without one), compat = {t: cnt[t] > 0 and best - cnt[t] < margin}, margin >= 1; UNIQUE with one bit,
+              MULTI with more.  Without an ASSIGNED gene: compat 0, feature NONE, best = second = n_gene = 0, NOGENE.
+    molecule  a molecule counted for feature f takes the AND of the compat sets of its reads that are ASSIGNED to f: not empty,
+              it is the molecule's class; empty, the molecule is a CONFLICT - counted for its gene, in neither isoform file.
+    files     transcripts.tsv: transcript, gene, local index, overflow 0|1, in file order.  isoform_matrix.mtx: transcripts x
+              barcodes, the molecules whose class is one bit that names one transcript (a lone bit 63 of an overflowing gene
+              names several and is not counted).  classes.tsv / class_matrix.mtx: every (gene, class) that occurs, by gene id,
+              then by the class's 64-bit value, "id, gene, transcripts" (bit 63 of an overflowing gene spelled out as all it
+              stands for), and classes x barcodes over every molecule with a class: transcript compatibility counts, what EM
+              tools take.  read_isoforms.tsv: per read with a CB.
 """
 import argparse
 import gzip
@@ -38,6 +59,12 @@ AMBIGUOUS, NONE = 0xFFFFFFFE, 0xFFFFFFFF
 ASSIGNED, LOW, TIE, CROWDED = 1, 2, 4, 8
 FLAG_NAMES = ((ASSIGNED, "ASSIGNED"), (LOW, "LOW"), (TIE, "TIE"), (CROWDED, "CROWDED"))
 REC_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), ("n_keys", "<u4"), ("n_found", "<u4"), ("flags", "<u4")])
+ISO_UNIQUE, ISO_MULTI, ISO_NOGENE = 1, 2, 4
+ISO_FLAG_NAMES = ((ISO_UNIQUE, "UNIQUE"), (ISO_MULTI, "MULTI"), (ISO_NOGENE, "NOGENE"))
+ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("second", "<u4"), ("n_gene", "<u4"), ("flags", "<u4"),
+                      ("pad", "<u4")])
+LOCAL_MAX, MARGIN_DEFAULT = 63, 1
+ISO_FILES = ("transcripts.tsv", "isoform_matrix.mtx", "classes.tsv", "class_matrix.mtx", "read_isoforms.tsv")
 HASH_MUL = np.uint64(0x9E3779B97F4A7C15)
 BATCH_BASES = 256 << 20             # bases per device call at most
 _CODE = np.full(256, 4, dtype=np.uint8)
@@ -78,8 +105,9 @@ def keys_of(seq, k):
 class Index:
     """keys (uint64, ascending, distinct) and their values (uint32: a feature or AMBIGUOUS); windows: how many had a key"""
 
-    def __init__(self, keys, values, windows, k):
+    def __init__(self, keys, values, windows, k, masks=None):
         self.keys, self.values, self.windows, self.k = keys, values, int(windows), k
+        self.masks = masks                                  # uint64 per key (build_index with local indices), or None
 
     def slots(self):
         n = 64
@@ -93,6 +121,13 @@ class Index:
             return np.full(len(keys), NONE, dtype=np.uint32)
         at = np.minimum(np.searchsorted(self.keys, keys), len(self.keys) - 1)
         return np.where(self.keys[at] == keys, self.values[at], np.uint32(NONE)).astype(np.uint32)
+
+    def lookup_masks(self, keys):
+        """-> masks of the keys, 0 where a key is not in the index"""
+        if not len(self.keys):
+            return np.zeros(len(keys), dtype=np.uint64)
+        at = np.minimum(np.searchsorted(self.keys, keys), len(self.keys) - 1)
+        return np.where(self.keys[at] == keys, self.masks[at], np.uint64(0)).astype(np.uint64)
 
     def stats(self, order=None):
         """what bdg_genes_index_stats reports: windows with a key, distinct keys, ambiguous keys, slots, the longest run of
@@ -116,23 +151,29 @@ class Index:
         return (self.windows, len(self.keys), int((self.values == AMBIGUOUS).sum()), slots, int(runs.max()), wrapped)
 
 
-def build_index(seqs, features, k):
-    """the index of the sequences (bytes / str / uint8 arrays) with a feature id each"""
+def build_index(seqs, features, k, local=None):
+    """the index of the sequences (bytes / str / uint8 arrays) with a feature id each; with local (an index <= 63 per
+    sequence) also the mask of every key"""
     _check_k(k)
-    if len(seqs) != len(features):
+    if len(seqs) != len(features) or (local is not None and len(local) != len(seqs)):
         raise ValueError("a feature id per sequence")
     if any(not 0 <= int(f) < AMBIGUOUS for f in features):
         raise ValueError("feature id reserved or out of range")
+    if local is not None and any(not 0 <= int(t) <= LOCAL_MAX for t in local):
+        raise ValueError("local index above 63")
     parts = [keys_of(s, k) for s in seqs]
     keys = np.concatenate(parts + [np.zeros(0, np.uint64)])
     feat = np.concatenate([np.full(len(p), int(f), dtype=np.uint32) for p, f in zip(parts, features)] + [np.zeros(0, np.uint32)])
+    bits = None if local is None else \
+        np.concatenate([np.full(len(p), 1 << int(t), dtype=np.uint64) for p, t in zip(parts, local)] + [np.zeros(0, np.uint64)])
     if not len(keys):
-        return Index(keys, feat, 0, k)
+        return Index(keys, feat, 0, k, bits)
     order = np.argsort(keys, kind="stable")
     keys, feat = keys[order], feat[order]
     first = np.flatnonzero(np.concatenate([[True], keys[1:] != keys[:-1]]))
     lo, hi = np.minimum.reduceat(feat, first), np.maximum.reduceat(feat, first)
-    return Index(keys[first], np.where(lo == hi, lo, np.uint32(AMBIGUOUS)).astype(np.uint32), len(keys), k)
+    masks = None if bits is None else np.bitwise_or.reduceat(bits[order], first)
+    return Index(keys[first], np.where(lo == hi, lo, np.uint32(AMBIGUOUS)).astype(np.uint32), len(keys), k, masks)
 
 
 def assign_reads(index, reads, min_hits=MIN_HITS_DEFAULT):
@@ -159,14 +200,55 @@ def assign_reads(index, reads, min_hits=MIN_HITS_DEFAULT):
     return out
 
 
+def local_indices(features):
+    """features: the feature id of every transcript in file order -> (local index per transcript uint8, whether its gene
+    is overflowing bool)"""
+    seen, local = {}, np.zeros(len(features), dtype=np.uint8)
+    for i, f in enumerate(np.asarray(features).tolist()):
+        local[i] = min(seen.get(f, 0), LOCAL_MAX)
+        seen[f] = seen.get(f, 0) + 1
+    return local, np.array([seen[f] > LOCAL_MAX + 1 for f in np.asarray(features).tolist()], dtype=bool)
+
+
+def iso_assign_reads(index, reads, gene_recs, margin=MARGIN_DEFAULT):
+    """the isoform rule over reads and their gene records (assign_reads over the same index) -> ISO_DTYPE [n]"""
+    if margin < 1:
+        raise ValueError("margin must be at least 1")
+    if index.masks is None:
+        raise ValueError("the index has no masks")
+    out = np.zeros(len(reads), dtype=ISO_DTYPE)
+    lanes = np.arange(64, dtype=np.uint64)
+    for r, read in enumerate(reads):
+        rec = out[r]
+        if not int(gene_recs["flags"][r]) & ASSIGNED:
+            rec["feature"], rec["flags"] = NONE, ISO_NOGENE
+            continue
+        f = int(gene_recs["feature"][r])
+        keys = keys_of(read, index.k)
+        m = index.lookup_masks(keys)[index.lookup(keys) == f]
+        cnt = ((m[:, None] >> lanes[None, :]) & np.uint64(1)).sum(axis=0).astype(np.int64)
+        best = int(cnt.max(initial=0))
+        compat = sum(1 << t for t in range(64) if cnt[t] > 0 and best - int(cnt[t]) < margin)
+        bits = bin(compat).count("1")
+        rec["compat"], rec["feature"], rec["best"], rec["n_gene"] = compat, f, best, len(m)
+        rec["second"] = int(cnt[cnt < best].max(initial=0))
+        rec["flags"] = ISO_UNIQUE if bits == 1 else ISO_MULTI if bits > 1 else 0
+    return out
+
+
 # ---------------------------------------------------------------- molecules and the matrix (host, product side) ----
 def flag_names(flags):
     return ",".join(name for bit, name in FLAG_NAMES if flags & bit)
 
 
-def count_molecules(cb, ub, recs):
+def iso_flag_names(flags):
+    return ",".join(name for bit, name in ISO_FLAG_NAMES if flags & bit)
+
+
+def count_molecules(cb, ub, recs, iso=None):
     """cb, ub: per read bytes (ub None: a molecule of its own), recs REC_DTYPE [n] -> (cells sorted, {(feature, cell index):
-    molecules}, counts dict)"""
+    molecules}, counts dict); with iso (ISO_DTYPE [n]) a fourth value: per counted molecule (feature, cell index, the AND of
+    the compat sets of its reads ASSIGNED to that feature - 0: CONFLICT), int64 [counted, 3] with the AND's bits as int64"""
     n = len(cb)
     cells, cell_of = np.unique(np.array(cb, dtype=bytes) if n else np.zeros(0, "S1"), return_inverse=True)
     mol_key = np.array([c + b"\t" + (u if u is not None else b"\t%d" % i) for i, (c, u) in enumerate(zip(cb, ub))], dtype=bytes) if n \
@@ -193,18 +275,92 @@ def count_molecules(cb, ub, recs):
         entries[key] = entries.get(key, 0) + 1
     counts = dict(reads=n, assigned=int(ok.sum()), tie=int(((flags & TIE) != 0).sum()), low=int(((flags & LOW) != 0).sum()),
                   crowded=int(((flags & CROWDED) != 0).sum()), molecules=n_mol, counted=len(won), tied=int(tied.sum()))
-    return [c for c in cells.tolist()], entries, counts
+    if iso is None:
+        return [c for c in cells.tolist()], entries, counts
+    # the reads that voted for their molecule's feature, grouped by molecule: the AND of their compat sets
+    mol_feat = np.full(n_mol, -1, dtype=np.int64)
+    mol_feat[pair[won, 0]] = pair[won, 1]
+    voter = np.flatnonzero(ok & (mol_feat[mol] == recs["feature"].astype(np.int64))) if n else np.zeros(0, np.int64)
+    voter = voter[np.argsort(mol[voter], kind="stable")]
+    start = np.flatnonzero(np.concatenate([[True], mol[voter][1:] != mol[voter][:-1]])) if len(voter) else np.zeros(0, np.int64)
+    cls = np.bitwise_and.reduceat(iso["compat"][voter], start) if len(voter) else np.zeros(0, np.uint64)
+    m = mol[voter][start]
+    return [c for c in cells.tolist()], entries, counts, np.stack([mol_feat[m], mol_cell[m], cls.view(np.int64)], axis=1)
 
 
-def count_matrix_text(text, names, assign):
+def _mtx(n_rows, n_cols, entries):
+    """{(row, column): count}, both from 0 -> the text of a MatrixMarket file, by column, then row"""
+    rows = ["%%MatrixMarket matrix coordinate integer general\n", "%d %d %d\n" % (n_rows, n_cols, len(entries))]
+    rows += ["%d %d %d\n" % (f + 1, c + 1, v) for (f, c), v in sorted(entries.items(), key=lambda e: (e[0][1], e[0][0]))]
+    return "".join(rows).encode()
+
+
+def isoform_files(names, tx_names, feat, heads, cb, ub, iso, cells, molecules):
+    """the five isoform files (ISO_FILES).  names: the features; tx_names, feat: every transcript and its feature id in file
+    order; heads, cb, ub, iso: per read with a CB; cells: the barcodes; molecules: count_molecules' fourth value
+    -> ({file name: bytes}, counts dict)"""
+    local, overflow = local_indices(feat)
+    # the transcripts a bit of a gene stands for, in file order
+    of_bit = {}
+    for q, (f, t) in enumerate(zip(np.asarray(feat).tolist(), local.tolist())):
+        of_bit.setdefault((f, t), []).append(q)
+
+    spelled = {}
+
+    def transcripts_of(f, compat):                                      # (few distinct sets per gene: each is spelled out once)
+        if (f, compat) not in spelled:
+            spelled[(f, compat)] = [q for t in range(64) if compat >> t & 1 for q in of_bit.get((f, t), ())]
+        return spelled[(f, compat)]
+
+    iso_entries, class_entries = {}, {}
+    mol = [(f, c, v & 0xFFFFFFFFFFFFFFFF) for f, c, v in molecules.tolist()]
+    classes = sorted({(f, v) for f, _, v in mol if v})
+    class_id = {fc: i for i, fc in enumerate(classes)}
+    n_unique = n_multi = 0
+    for f, c, v in mol:
+        if not v:
+            continue
+        class_entries[(class_id[(f, v)], c)] = class_entries.get((class_id[(f, v)], c), 0) + 1
+        tx = transcripts_of(f, v) if v & (v - 1) == 0 else ()
+        if len(tx) == 1:
+            iso_entries[(tx[0], c)] = iso_entries.get((tx[0], c), 0) + 1
+            n_unique += 1
+        else:
+            n_multi += 1
+    rows = ["read\tCB\tUB\tgene\tn_gene\tbest\tsecond\ttranscripts\tflags\n"]
+    for h, c, u, r in zip(heads, cb, ub, iso.tolist()):
+        compat, f, best, second, n_gene, flags, _ = r
+        rows.append("%s\t%s\t%s\t%s\t%d\t%d\t%d\t%s\t%s\n" % (
+            h.split(b"\t")[0].decode(), c.decode(), u.decode() if u is not None else "*", names[f] if f != NONE else "*", n_gene, best,
+            second, ",".join(tx_names[q] for q in transcripts_of(f, compat)) or "*", iso_flag_names(flags)))
+    files = {"transcripts.tsv": "".join("%s\t%s\t%d\t%d\n" % (t, names[f], l, o) for t, f, l, o in
+                                        zip(tx_names, np.asarray(feat).tolist(), local.tolist(), overflow.tolist())).encode(),
+             "isoform_matrix.mtx": _mtx(len(tx_names), len(cells), iso_entries),
+             "classes.tsv": "".join("%d\t%s\t%s\n" % (i + 1, names[f], ",".join(tx_names[q] for q in transcripts_of(f, v)))
+                                    for i, (f, v) in enumerate(classes)).encode(),
+             "class_matrix.mtx": _mtx(len(classes), len(cells), class_entries),
+             "read_isoforms.tsv": "".join(rows).encode()}
+    flags = iso["flags"]
+    counts = dict(iso_unique=int((flags & ISO_UNIQUE != 0).sum()), iso_multi=int((flags & ISO_MULTI != 0).sum()),
+                  iso_nogene=int((flags & ISO_NOGENE != 0).sum()), mol_unique=n_unique, mol_multi=n_multi,
+                  mol_conflict=sum(1 for _, _, v in mol if not v), classes=len(classes))
+    return files, counts
+
+
+def count_matrix_text(text, names, assign, isoforms=None):
     """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
     assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
-    -> ({file name: bytes}, counts dict)"""
+    -> ({file name: bytes}, counts dict).  With isoforms = (transcript names, their feature ids) assign returns the pair
+    (REC_DTYPE array, ISO_DTYPE array), and the files of isoform_files and its counts join the four, which stay as they are."""
     from .consensus import parse_tagged
     heads, seqs, cb, ub = parse_tagged(text)
     take = [i for i, c in enumerate(cb) if c is not None]
     recs = assign([seqs[i] for i in take])
-    cells, entries, counts = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs)
+    if isoforms is not None:
+        recs, iso = recs
+        cells, entries, counts, molecules = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs, iso)
+    else:
+        cells, entries, counts = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs)
     counts["no_cell"] = len(cb) - len(take)
     rows = ["read\tCB\tUB\tfeature\thits\tsecond\tn_keys\tn_found\tflags\n"]
     for i, r in zip(take, recs.tolist()):
@@ -212,12 +368,15 @@ def count_matrix_text(text, names, assign):
         rows.append("%s\t%s\t%s\t%s\t%d\t%d\t%d\t%d\t%s\n" % (
             heads[i].split(b"\t")[0].decode(), cb[i].decode(), ub[i].decode() if ub[i] is not None else "*",
             names[feature] if feature != NONE else "*", hits, second, n_keys, n_found, flag_names(flags)))
-    mtx = ["%%MatrixMarket matrix coordinate integer general\n", "%d %d %d\n" % (len(names), len(cells), len(entries))]
-    mtx += ["%d %d %d\n" % (f + 1, c + 1, v) for (f, c), v in sorted(entries.items(), key=lambda e: (e[0][1], e[0][0]))]
     files = {"features.tsv": "".join("%s\t%s\tGene Expression\n" % (x, x) for x in names).encode(),
              "barcodes.tsv": b"".join(c + b"\n" for c in cells),
-             "matrix.mtx": "".join(mtx).encode(),
+             "matrix.mtx": _mtx(len(names), len(cells), entries),
              "reads.tsv": "".join(rows).encode()}
+    if isoforms is not None:
+        more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], [heads[i] for i in take], [cb[i] for i in take],
+                                         [ub[i] for i in take], iso, cells, molecules)
+        files.update(more)
+        counts.update(iso_counts)
     return files, counts
 
 
@@ -280,34 +439,42 @@ def _flatten(seqs):
 
 
 # ---------------------------------------------------------------- the product side ----
-def device_assign(ctx, min_hits):
-    """assign of count_matrix_text on the device: bdg_genes_assign over pieces of at most BATCH_BASES bases"""
+def device_assign(ctx, min_hits, margin=None):
+    """assign of count_matrix_text on the device: bdg_genes_assign over pieces of at most BATCH_BASES bases; with a margin
+    bdg_iso_assign, and both records"""
     from . import _native
 
     def run(seqs):
-        out, at = np.zeros(len(seqs), dtype=_native.GENE_DTYPE), 0
+        out, iso, at = np.zeros(len(seqs), dtype=_native.GENE_DTYPE), np.zeros(len(seqs) if margin else 0, dtype=_native.ISO_DTYPE), 0
         while at < len(seqs):
             end, total = at, 0
             while end < len(seqs) and (end == at or total + len(seqs[end]) <= BATCH_BASES):
                 total += len(seqs[end])
                 end += 1
-            out[at:end] = ctx.genes_assign(*_flatten(seqs[at:end]), min_hits)
+            if margin:
+                out[at:end], iso[at:end] = ctx.iso_assign(*_flatten(seqs[at:end]), min_hits, margin)
+            else:
+                out[at:end] = ctx.genes_assign(*_flatten(seqs[at:end]), min_hits)
             at = end
-        return out
+        return (out, iso) if margin else out
     return run
 
 
-def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0):
+def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
-    reads.tsv -> counts"""
+    reads.tsv, and with iso_margin (--isoforms) the files of ISO_FILES -> counts"""
     from . import _native
     tx_names, tx_seqs = read_fasta(transcripts)
     names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
     ctx = _native.default_context(device)
-    ctx.genes_index_build(*_flatten(tx_seqs), feat, k)
+    if iso_margin:
+        ctx.genes_index_build_iso(*_flatten(tx_seqs), feat, local_indices(feat)[0], k)
+    else:
+        ctx.genes_index_build(*_flatten(tx_seqs), feat, k)
     try:
         stats = ctx.genes_index_stats()
-        files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits))
+        files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
+                                          (tx_names, feat) if iso_margin else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
@@ -324,6 +491,10 @@ def log_counts(counts, out_dir):
                 % (counts["reads"], counts["assigned"], counts["tie"], counts["low"], counts["crowded"], counts["molecules"],
                    counts["counted"], counts["tied"], counts.get("features", 0), counts.get("transcripts", 0), counts.get("keys", 0),
                    counts.get("k", K_DEFAULT), counts.get("ambiguous", 0), out_dir))
+    if "iso_unique" in counts:
+        logger.info("Isoforms: reads %d unique, %d multi, %d no gene; molecules %d unique, %d multi, %d conflict; %d classes"
+                    % (counts["iso_unique"], counts["iso_multi"], counts["iso_nogene"], counts["mol_unique"], counts["mol_multi"],
+                       counts["mol_conflict"], counts["classes"]))
 
 
 def gene_k_arg(v):
@@ -346,7 +517,34 @@ def gene_min_hits_arg(v):
     return x
 
 
+def iso_margin_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if x < 1:
+        raise argparse.ArgumentTypeError("--iso_margin takes an integer of at least 1")
+    return x
+
+
+def check_iso_options(p, a, with_matrix):
+    """the errors of --isoforms and --iso_margin, the same on both command lines; sets a.iso_margin to None without --isoforms"""
+    if a.iso_margin is not None and not a.isoforms:
+        p.error("--iso_margin needs --isoforms")
+    if a.isoforms and not with_matrix:
+        p.error("--isoforms needs --count_matrix: it refines the gene calls of the matrix")
+    if a.isoforms and not a.tx2gene:
+        p.error("--isoforms needs --tx2gene: without a gene map every gene has one transcript and there is nothing to tell apart")
+    a.iso_margin = (MARGIN_DEFAULT if a.iso_margin is None else a.iso_margin) if a.isoforms else None
+
+
 def add_gene_options(p):
+    p.add_argument("--isoforms", action="store_true",
+                   help="with --tx2gene: also the transcripts of its gene that every read and molecule is compatible with; "
+                        "writes %s beside the matrix" % ", ".join(ISO_FILES))
+    p.add_argument("--iso_margin", type=iso_margin_arg, default=None, metavar="M",
+                   help="--isoforms: a transcript stays compatible with a read while it has fewer than M of the gene's keys less "
+                        "than the best transcript (default %d)" % MARGIN_DEFAULT)
     p.add_argument("--gene_k", type=gene_k_arg, default=None, metavar="K",
                    help="bases of a key of the gene lookup (default %d, 11 .. 31)" % K_DEFAULT)
     p.add_argument("--gene_min_hits", type=gene_min_hits_arg, default=None, metavar="H",
@@ -360,12 +558,14 @@ def parse_args(argv):
     p.add_argument("-t", "--transcripts", required=True, help="transcript FASTA (.gz is read through gzip), mRNA sense")
     p.add_argument("--tx2gene", default=None, metavar="TSV",
                    help="transcript<TAB>gene per line: counts are per gene (without it per transcript name)")
-    p.add_argument("-o", "--output", required=True, help="directory for features.tsv, barcodes.tsv, matrix.mtx and reads.tsv")
+    p.add_argument("-o", "--output", required=True,
+                   help="directory for features.tsv, barcodes.tsv, matrix.mtx and reads.tsv (and the files of --isoforms)")
     add_gene_options(p)
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
     a = p.parse_args(argv)
     a.gene_k = K_DEFAULT if a.gene_k is None else a.gene_k
     a.gene_min_hits = MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
+    check_iso_options(p, a, True)
     return a
 
 
@@ -374,7 +574,8 @@ def main(argv):
     logger.setLevel(logging.INFO)
     if not logger.handlers:
         logger.addHandler(logging.StreamHandler(stream=sys.stdout))
-    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device), a.output)
+    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin),
+               a.output)
 
 
 if __name__ == "__main__":

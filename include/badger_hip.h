@@ -1014,6 +1014,39 @@ int  bdg_genes_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* 
 /* The same over host arrays; synchronous; also BDG_E_ARG for offsets that decrease. */
 int  bdg_genes_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, bdg_gene_rec* out);
 
+/* ---- transcript compatibility of the reads of a gene (--isoforms; checker: badger_amd/genes.py) ---- */
+#define BDG_ISO_LOCAL_MAX       63u          /* the largest local index: bit 63 of a mask */
+#define BDG_ISO_MARGIN_DEFAULT  1
+#define BDG_ISO_UNIQUE          1u           /* bdg_iso_rec.flags: compat has exactly one bit */
+#define BDG_ISO_MULTI           2u           /* ... more than one bit */
+#define BDG_ISO_NOGENE          4u           /* ... the read has no ASSIGNED gene record; no other flag with it */
+typedef struct { uint64_t compat; uint32_t feature, best, second, n_gene, flags, pad; } bdg_iso_rec;   /* 32 bytes */
+/* THE RULE, on top of the rule above.  Integers, sums, ORs and maxima only: no order of evaluation changes a result.
+ *   local    every sequence q has a local index local[q] <= 63 within its feature.  The host chooses it; the command line
+ *            takes the sequence's order of first appearance among the sequences of its feature, capped at 63, so that bit 63
+ *            stands for "the 64th transcript of this gene, or any later one" (such a gene is overflowing).
+ *   mask     mask(key) is the OR of 1 << local[q] over every occurrence of the key in every sequence q, whatever the
+ *            sequences' features are.  Only the mask of a key whose value is a feature (not AMBIGUOUS) is ever used.
+ *   read     it takes part if its gene record (bdg_genes_assign, the same min_hits) is ASSIGNED, to feature f.  Over its
+ *            windows whose value is f: n_gene their number (equal to the gene record's hits), cnt[t] the number of them
+ *            whose mask has bit t, best = max cnt[t], second the largest cnt[t] below best (0 if there is none), compat the
+ *            set of the t with cnt[t] > 0 and best - cnt[t] < margin, margin >= 1.  feature = f; flags UNIQUE if compat
+ *            has one bit, MULTI if more.  A read without an ASSIGNED gene record: compat = 0, feature BDG_GENES_NONE,
+ *            best = second = n_gene = 0, flags NOGENE; none of its bases is read.  pad is 0.
+ * bdg_genes_index_build_iso is bdg_genes_index_build plus the masks: the same table, the same stats, and a 64-bit word per
+ * slot beside it.  BDG_E_ARG also for a local index above 63.  An index built by bdg_genes_index_build has no masks, and
+ * building one drops the masks of an earlier index. */
+int  bdg_genes_index_build_iso(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
+                               const uint8_t* local, uint32_t k);
+/* Reads as for bdg_genes_assign_dev; d_gene_recs [n] what bdg_genes_assign_dev wrote for the same reads; d_out [n].
+ * Asynchronous, on the context's stream.  BDG_E_ARG with margin == 0 or on a context without masks. */
+int  bdg_iso_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_gene_recs,
+                        uint32_t margin, bdg_iso_rec* d_out);
+/* Both records over host arrays: bdg_genes_assign, then the above; synchronous; also BDG_E_ARG for min_hits == 0 and for
+ * offsets that decrease. */
+int  bdg_iso_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, uint32_t margin,
+                    bdg_gene_rec* gene_out, bdg_iso_rec* iso_out);
+
 /* ---- stage 2's read-side plumbing on the host (badger.py:112-121,129; barcode_graph.py:388-410) -------------- */
 /* Read ids of a run, kept natively (12 bytes per read instead of a Python string each). */
 typedef struct bdg_idstore bdg_idstore;

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Measurements of the gene calls by k-mer lookup, one JSON line each to --out (and stdout).
+"""Measurements of the gene calls by k-mer lookup and of the isoform pass on top of them, one
+JSON line each to --out (and stdout).
 
     python tools/genes_probe.py --device [--reads 1000000] [--tx_bases 4000000 100000000] --out profiles/r22_genes.jsonl
         bdg_genes_index_build and bdg_genes_assign_dev alone.  Per --tx_bases value a random transcriptome of that many bases in
@@ -12,6 +13,16 @@
         processes: --tagged_reads --umi_dedup with --count_matrix against without, the transcripts being the middles of the
         first 20,000 reads in both senses; and, with --parent DIR (a built checkout of the parent commit), this build with the
         flags off against the parent, beside parent against parent.
+    python tools/genes_probe.py --device --isoforms [--reads 1000000] [--tx_bases 4000000] --out profiles/r23_isoforms.jsonl
+        the same workload over genes of 2 .. 4 isoforms: every gene a random text of 2,000 bases, its first
+        isoform that text, every other one the text without 150 bases at a place of its own within the last 1,200, behind 150
+        bases of its own, so that every transcript has 2,000 bases; features are the genes.  bdg_genes_index_build_iso against
+        bdg_genes_index_build, and bdg_genes_assign_dev followed by bdg_iso_assign_dev: k_iso_insert and k_iso_assign beside
+        k_genes_insert and k_genes_assign from the event timers of the same run.
+    python tools/genes_probe.py --cli --isoforms ...
+        the command line with --count_matrix --isoforms against --count_matrix alone (the transcripts paired into genes of two
+        by a --tx2gene map: a read's middle and, as its second isoform, the same without its bases 100 .. 199), then the pairs
+        with --parent as above.
 """
 import argparse
 import os
@@ -112,6 +123,84 @@ def device_probe(args):
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
 
 
+def iso_transcriptome(n_tx, seed=7):
+    """-> (codes [n_tx', TX_LEN], feature of each uint32, local index of each uint8), n_tx' the first gene count that reaches n_tx"""
+    rng = np.random.default_rng(seed)
+    tx, feat, local, g = [], [], [], 0
+    while len(tx) < n_tx:
+        gene = rng.integers(0, 4, TX_LEN, dtype=np.uint8)
+        cuts = rng.permutation(7)[:int(rng.integers(1, 4))] * 150 + TX_LEN - 1200          # 1 .. 3 skipping isoforms
+        for i, c in enumerate([None] + cuts.tolist()):
+            tx.append(gene if c is None else np.concatenate([rng.integers(0, 4, 150, dtype=np.uint8), gene[:c], gene[c + 150:]]))
+            feat.append(g)
+            local.append(i)
+        g += 1
+    return np.stack(tx), np.array(feat, dtype=np.uint32), np.array(local, dtype=np.uint8)
+
+
+def device_probe_iso(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for tx_bases in args.tx_bases:
+        tx, feat, local = iso_transcriptome(max(tx_bases // TX_LEN, 1))
+        n_tx = len(tx)
+        bases, off = fragments(tx, args.reads)
+        n = len(off) - 1
+        tx_ascii, tx_off = ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64)
+        builds = {}
+        for name, build in (("plain", lambda: ctx.genes_index_build(tx_ascii, tx_off, feat, args.k)),
+                            ("iso", lambda: ctx.genes_index_build_iso(tx_ascii, tx_off, feat, local, args.k))):
+            build()                                                       # (warm: the first allocation of this size)
+            ctx.profile(True)
+            ctx.profile_reset()
+            t0 = time.perf_counter()
+            build()
+            wall = time.perf_counter() - t0
+            builds[name] = {"wall_s": round(wall, 3),
+                            "kernel_ms": {k: round(v[1], 4) for k, v in ctx.profile_read().items() if k.startswith(("k_genes", "k_iso")) and v[0]}}
+            ctx.profile(False)
+        stats = [int(x) for x in ctx.genes_index_stats()]
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off)]
+        d_gene, d_iso = _native.DeviceArray(ctx, n * 6, np.uint32), _native.DeviceArray(ctx, n * 8, np.uint32)
+
+        def call():
+            ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, d_gene)
+            ctx.iso_assign_dev(d[0], d[1], n, d_gene, args.margin, d_iso)
+        call()
+        ctx.synchronize()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            call()
+            ctx.synchronize()
+            times.append(time.perf_counter() - t0)
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(args.reps):
+            call()
+        ctx.synchronize()
+        kt = {k: round(v[1] / args.reps, 4) for k, v in ctx.profile_read().items() if k.startswith(("k_genes", "k_iso")) and v[0]}
+        ctx.profile(False)
+        gene, iso = d_gene.to_host().view(_native.GENE_DTYPE), d_iso.to_host().view(_native.ISO_DTYPE)
+        assigned = gene["flags"] & 1 != 0
+        emit(args.out, {"what": "bdg_genes_index_build_iso, bdg_genes_assign_dev + bdg_iso_assign_dev, device-resident", "k": args.k,
+                        "min_hits": args.min_hits, "margin": args.margin, "transcripts": n_tx, "genes": int(feat.max()) + 1,
+                        "transcript_bases": int(n_tx * TX_LEN), "table_bytes": 16 * stats[3], "mask_bytes": 8 * stats[3],
+                        "stats": dict(zip(("windows", "keys", "ambiguous", "slots", "longest_run", "wrapped"), stats)),
+                        "build": builds, "reads": n, "read_bases": int(off[-1]),
+                        "windows_looked_up": int(gene["n_keys"].astype(np.int64).sum()), "found": int(gene["n_found"].astype(np.int64).sum()),
+                        "assigned": int(assigned.sum()), "windows_of_the_gene": int(iso["n_gene"].astype(np.int64).sum()),
+                        "n_gene_is_hits": bool((iso["n_gene"] == np.where(assigned, gene["hits"], 0)).all()),
+                        "unique": int((iso["flags"] & 1 != 0).sum()), "multi": int((iso["flags"] & 2 != 0).sum()),
+                        "no_gene": int((iso["flags"] & 4 != 0).sum()),
+                        "both_calls_ms_median": round(1e3 * float(np.median(times)), 3), "both_calls_ms_min": round(1e3 * min(times), 3),
+                        "assign_kernel_ms": kt, "assign_kernel_ms_per_1M_reads": {k: round(v * 1e6 / n, 3) for k, v in kt.items()}})
+        for a in d + [d_gene, d_iso]:
+            a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+
+
 def _transcripts_of(fq, path, n=20000):
     """the middles of the first n reads of a FASTQ file, as they are and reverse-complemented, as a transcript FASTA"""
     comp = bytes.maketrans(b"ACGT", b"TGCA")
@@ -127,6 +216,16 @@ def _transcripts_of(fq, path, n=20000):
             out.write(b">t%df\n%s\n>t%dr\n%s\n" % (i, mid, i, mid.translate(comp)[::-1]))
 
 
+def _isoforms_of(tx, path_fa, path_map):
+    """every transcript of a FASTA (name line, sequence line) and, as a second isoform of its gene, the same without its bases
+    100 .. 199; the gene map beside it"""
+    with open(tx, "rb") as f, open(path_fa, "wb") as out, open(path_map, "wb") as m:
+        for name in f:
+            name, s = name[1:].strip(), f.readline().strip()
+            out.write(b">%s\n%s\n>%s.skip\n%s\n" % (name, s, name, s[:100] + s[200:]))
+            m.write(b"%s\tg_%s\n%s.skip\tg_%s\n" % (name, name, name, name))
+
+
 def cli_probe(args):
     from consensus_probe import _fastq
     tmp = tempfile.mkdtemp(prefix="genes_probe_")
@@ -140,7 +239,7 @@ def cli_probe(args):
         r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
-        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l]
+        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l]
 
     def pairs(name_a, a, name_b, b, what):
         walls, said = {name_a: [], name_b: []}, []
@@ -160,8 +259,15 @@ def cli_probe(args):
     fa = os.path.join(tmp, "tagged.fa")
     tagged = ["--umi_dedup", "--tagged_reads", fa]
     run(ROOT, "warm", tagged)                                          # (the file into the page cache, the runtime's caches)
-    pairs("tagged", (ROOT, tagged), "count_matrix", (ROOT, tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]),
-          "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: with --count_matrix against without")
+    if args.isoforms:
+        tx2, tx_map = os.path.join(tmp, "tx_iso.fa"), os.path.join(tmp, "tx2gene.tsv")
+        _isoforms_of(tx, tx2, tx_map)
+        matrix = tagged + ["--transcripts", tx2, "--tx2gene", tx_map, "--count_matrix", os.path.join(tmp, "matrix")]
+        pairs("count_matrix", (ROOT, matrix), "isoforms", (ROOT, matrix + ["--isoforms"]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --tx2gene: with --isoforms against without")
+    else:
+        pairs("tagged", (ROOT, tagged), "count_matrix", (ROOT, tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: with --count_matrix against without")
     if args.parent:
         parent = os.path.abspath(args.parent)
         pairs("parent", (parent, tagged), "flags_off", (ROOT, tagged), "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: this build with the flags off against the parent commit's")
@@ -176,6 +282,8 @@ def main():
     p.add_argument("--tx_bases", type=int, nargs="+", default=[4000000, 100000000], help="bases of each transcriptome to measure")
     p.add_argument("--k", type=int, default=21)
     p.add_argument("--min_hits", type=int, default=3)
+    p.add_argument("--isoforms", action="store_true", help="the isoform leg of --device and of --cli (DESIGN 4.20)")
+    p.add_argument("--margin", type=int, default=1)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--cli_reads", type=int, default=1000000)
     p.add_argument("--pairs", type=int, default=3)
@@ -183,7 +291,7 @@ def main():
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
-        device_probe(args)
+        (device_probe_iso if args.isoforms else device_probe)(args)
     if args.cli:
         cli_probe(args)
 
