@@ -57,6 +57,11 @@ ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("
                       ("pad", "<u4")])
 ISO_LOCAL_MAX, ISO_MARGIN_DEFAULT = 63, 1
 ISO_UNIQUE, ISO_MULTI, ISO_NOGENE = 1, 2, 4
+# bdg_em_class / bdg_em_info: a class of an EM problem and what became of the problem (bdg_em_tcc; the rule in badger_amd/genes.py)
+EM_CLASS_DTYPE = np.dtype([("mask", "<u8"), ("count", "<u4"), ("pad", "<u4")])
+EM_INFO_DTYPE = np.dtype([("iters", "<u4"), ("flags", "<u4"), ("lost", "<u4"), ("pad", "<u4")])
+EM_CLOSED, EM_CONVERGED, EM_MAXITER, EM_RANGE = 1, 2, 4, 8
+EM_EPS_DEFAULT, EM_MAX_ITER_DEFAULT = 1e-3, 1000
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -93,6 +98,7 @@ EXPORTS = [
     "bdg_consensus", "bdg_consensus_dev", "bdg_consensus_set_band",
     "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
     "bdg_genes_index_build_iso", "bdg_iso_assign", "bdg_iso_assign_dev",
+    "bdg_em_tcc", "bdg_em_tcc_dev",
 ]
 
 
@@ -365,6 +371,8 @@ def load():
     L.bdg_genes_index_build_iso.argtypes = [vp, vp, vp, u32, vp, vp, u32]
     L.bdg_iso_assign.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
     L.bdg_iso_assign_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_em_tcc.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
+    L.bdg_em_tcc_dev.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
     L.bdg_consensus_set_band.argtypes = [vp, u32]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
@@ -741,6 +749,32 @@ class Context:
     def iso_assign_dev(self, d_bases, d_off, n, d_gene_recs, margin, d_out):
         """bdg_iso_assign_dev: the compatible transcripts over device arrays and the gene records of the same reads, asynchronous"""
         self._check(self.lib.bdg_iso_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs), int(margin), _ptr(d_out)))
+
+    def em_tcc(self, classes, prob_off, out_off, eps=EM_EPS_DEFAULT, max_iter=EM_MAX_ITER_DEFAULT, start=None):
+        """EM over the compatibility counts of every problem, host arrays (bdg_em_tcc): classes EM_CLASS_DTYPE, problem p the
+        classes prob_off[p] .. prob_off[p + 1] - 1, its active lanes' values at out_off[p] onwards (start, if given, laid
+        out the same) -> (alpha float32 [out_off[-1]], EM_INFO_DTYPE [n])"""
+        classes = np.ascontiguousarray(classes, dtype=EM_CLASS_DTYPE)
+        prob_off = np.ascontiguousarray(prob_off, dtype=np.uint64)
+        out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+        n = len(prob_off) - 1
+        if n < 0 or len(out_off) != n + 1 or (n and int(prob_off[n]) > len(classes)):
+            raise ValueError("prob_off and out_off hold one entry more than there are problems, the classes reach to prob_off[-1]")
+        alpha, info = np.zeros(int(out_off[n]) if n else 0, dtype=np.float32), np.zeros(n, dtype=EM_INFO_DTYPE)
+        if start is not None:
+            start = np.ascontiguousarray(start, dtype=np.float32)
+            if len(start) != len(alpha):
+                raise ValueError("the start vector is laid out like the result")
+        self._check(self.lib.bdg_em_tcc(self.h, classes.ctypes.data, prob_off.ctypes.data, n, out_off.ctypes.data,
+                                        start.ctypes.data if start is not None and len(start) else None, float(eps), int(max_iter),
+                                        alpha.ctypes.data, info.ctypes.data))
+        return alpha, info
+
+    def em_tcc_dev(self, d_classes, d_prob_off, n, d_out_off, d_start, eps, max_iter, d_alpha, d_info):
+        """bdg_em_tcc_dev: the same over device arrays (d_start None: every active lane starts at 1), asynchronous"""
+        self._check(self.lib.bdg_em_tcc_dev(self.h, _ptr(d_classes), _ptr(d_prob_off), int(n), _ptr(d_out_off),
+                                            _ptr(d_start) if d_start is not None else None, float(eps), int(max_iter), _ptr(d_alpha),
+                                            _ptr(d_info)))
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""

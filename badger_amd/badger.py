@@ -7,7 +7,7 @@
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --umi_dedup --molecule_consensus consensus.fa
                                 [--consensus_band 64|128|256]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
-                                [--isoforms [--iso_margin 1]]
+                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -28,7 +28,8 @@ features x barcodes matrix in MatrixMarket form with its two name files, plus re
 --isoforms (with --tx2gene) adds, in a second pass over the same reads on the device, the transcripts of its gene that every
 read is compatible with, and per molecule the intersection: transcripts.tsv, isoform_matrix.mtx (molecules that name one transcript),
 classes.tsv with class_matrix.mtx (transcript compatibility counts) and read_isoforms.tsv in DIR; the four files of the matrix
-stay the same bytes.
+stay the same bytes.  --isoform_em runs expectation-maximisation over those counts on the device, one problem per (cell, gene):
+isoform_em_matrix.mtx (transcripts x barcodes, abundances in molecules) and isoform_em_pool.tsv (the genes' abundances over all cells).
 Every other output is the same bytes with and without these flags.
 
 -d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
@@ -302,7 +303,7 @@ def write_count_matrix(args):
     """behind write_tagged_reads, on the file it wrote"""
     from .genes import count_matrix_of_tagged, log_counts
     counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
-                                    args.gene_min_hits, args.device, args.iso_margin)
+                                    args.gene_min_hits, args.device, args.iso_margin, args.em)
     log_counts(counts, args.count_matrix)
 
 

@@ -151,6 +151,7 @@ struct bdg_ctx {
     int gn_cus = 0, gn_assign_per_cu = 0;    // compute units, and blocks of k_genes_assign resident on one (asked once)
     DevBuf gn_mask;      // u64 per slot: the transcripts of its gene that hold the slot's key (bdg_genes_index_build_iso only)
     int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
+    int em_cus = 0, em_per_cu = 0;           // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

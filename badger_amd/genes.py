@@ -3,7 +3,7 @@
 that every read and molecule is compatible with.
 
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
-                               [--isoforms [--iso_margin 1]]
+                               [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -45,6 +45,20 @@ The isoform rule, on top of it (include/badger_hip.h at bdg_genes_index_build_is
               then by the class's 64-bit value, "id, gene, transcripts" (bit 63 of an overflowing gene spelled out as all it
               stands for), and classes x barcodes over every molecule with a class: transcript compatibility counts, what EM
               tools take.  read_isoforms.tsv: per read with a CB.
+
+The EM rule, on those counts (include/badger_hip.h at bdg_em_tcc_dev; em_tcc below is its checker).  IEEE binary32,
+every operation rounded on its own, in the order given: the device and numpy agree bit for bit.
+    problem   the classes (mask, n) of one (cell, gene) in the order given; A the OR of the masks, lane t active if A has bit t,
+              N the sum of the n in integers.  N >= 2^24: RANGE, zeros.  Else no class or N == 0: CLOSED, zeros.  Else every mask
+              one bit: CLOSED, alpha_t the sum of the n of the mask 1 << t, an exact integer.
+    start     else alpha_t = 1 on the active lanes (or the start vector's value), +0 elsewhere; nothing is normalised.
+    iterate   new = +0, lost = 0; per class in order: x = alpha on the class's lanes, +0 elsewhere; for s in 32, 16, 8, 4, 2, 1:
+              x = x + x[lane ^ s]; d = x[0]; d > 0: new_t = new_t + (float32(n) * alpha_t) / d on the class's lanes, else
+              lost += n.  delta = max |new - alpha|; alpha = new; iters += 1.
+    stop      delta < eps: CONVERGED; else iters == max_iter: MAXITER.
+    files     isoform_em_matrix.mtx: transcripts x barcodes, "%.3f" of alpha, no entry for 0.000; isoform_em_pool.tsv: per
+              transcript the alpha of its gene's pooled problem (the counts summed over the cells).  Bit 63 of an overflowing
+              gene names several transcripts: its mass is in neither, the log line has it.
 """
 import argparse
 import gzip
@@ -65,6 +79,13 @@ ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("
                       ("pad", "<u4")])
 LOCAL_MAX, MARGIN_DEFAULT = 63, 1
 ISO_FILES = ("transcripts.tsv", "isoform_matrix.mtx", "classes.tsv", "class_matrix.mtx", "read_isoforms.tsv")
+EM_CLOSED, EM_CONVERGED, EM_MAXITER, EM_RANGE = 1, 2, 4, 8
+EM_CLASS_DTYPE = np.dtype([("mask", "<u8"), ("count", "<u4"), ("pad", "<u4")])
+EM_INFO_DTYPE = np.dtype([("iters", "<u4"), ("flags", "<u4"), ("lost", "<u4"), ("pad", "<u4")])
+EM_EPS_DEFAULT, EM_EPS_MIN, EM_EPS_MAX, EM_MAX_ITER_DEFAULT, EM_MAX_ITER_MAX, EM_INITS = 1e-3, 1e-6, 1.0, 1000, 100000, ("uniform", "pool")
+EM_N_MAX = 1 << 24                   # a problem's counts must sum to less: a count converts to float32 exactly
+EM_FILES = ("isoform_em_matrix.mtx", "isoform_em_pool.tsv")
+EM_BATCH_CLASSES = 4 << 20          # classes per device call at most
 HASH_MUL = np.uint64(0x9E3779B97F4A7C15)
 BATCH_BASES = 256 << 20             # bases per device call at most
 _CODE = np.full(256, 4, dtype=np.uint8)
@@ -236,6 +257,128 @@ def iso_assign_reads(index, reads, gene_recs, margin=MARGIN_DEFAULT):
     return out
 
 
+def _popcount(x):
+    return bin(int(x)).count("1")
+
+
+def em_tcc(problems, eps, max_iter, start=None, lanes=64):
+    """the EM rule.  problems: per problem a list of (mask, n); start: None or per problem the values of its active lanes in
+    ascending order; lanes: 64, or 32 / 16 for problems with A < 2^lanes - the butterfly a group of that many lanes does
+    -> (per problem the float32 values of its active lanes in ascending order, EM_INFO_DTYPE [n])"""
+    f32 = np.float32
+    if max_iter < 1 or not (np.isfinite(eps) and eps > 0):
+        raise ValueError("max_iter at least 1, eps finite and above 0")
+    eps = f32(eps)
+    lane = np.arange(lanes)
+    steps = [s for s in (32, 16, 8, 4, 2, 1) if s < lanes]
+    alphas, info = [], np.zeros(len(problems), dtype=EM_INFO_DTYPE)
+    for p, classes in enumerate(problems):
+        masks = [int(m) for m, _ in classes]
+        A, N = 0, sum(int(n) for _, n in classes)
+        for m in masks:
+            A |= m
+        if A >> lanes:
+            raise ValueError("a transcript beyond the lanes")
+        active = np.array([A >> t & 1 for t in range(lanes)], dtype=bool)
+        alpha = np.zeros(lanes, dtype=f32)
+        if N >= EM_N_MAX:
+            info[p]["flags"] = EM_RANGE
+        elif not classes or N == 0:
+            info[p]["flags"] = EM_CLOSED
+        elif all(_popcount(m) == 1 for m in masks):
+            total = np.zeros(lanes, dtype=np.int64)
+            for m, (_, n) in zip(masks, classes):
+                total[m.bit_length() - 1] += int(n)
+            alpha = total.astype(f32)
+            info[p]["flags"] = EM_CLOSED
+        else:
+            alpha[active] = f32(1) if start is None else np.asarray(start[p], dtype=f32)
+            # every class is a row: the butterfly and the terms of all rows at once, the sum over the classes row after row
+            member = np.array([[m >> t & 1 for t in range(lanes)] for m in masks], dtype=bool)
+            counts = np.array([int(n) for _, n in classes], dtype=np.int64)
+            nf = counts.astype(f32)[:, None]
+            iters = 0
+            while True:
+                x = np.where(member, alpha[None, :], f32(0))
+                for s in steps:
+                    x = x + x[:, lane ^ s]
+                d = x[:, :1]
+                ok = d > 0
+                term = np.where(member & ok, (nf * alpha[None, :]) / np.where(ok, d, f32(1)), f32(0))
+                new = np.add.accumulate(term, axis=0, dtype=f32)[-1]        # in the order of the classes; + 0.0 changes nothing
+                lost = int(counts[~ok[:, 0]].sum())
+                delta = np.max(np.abs(new - alpha))
+                alpha = new
+                iters += 1
+                if delta < eps or iters == max_iter:
+                    info[p]["iters"], info[p]["lost"] = iters, lost
+                    info[p]["flags"] = EM_CONVERGED if delta < eps else EM_MAXITER
+                    break
+        alphas.append(alpha[active])
+    return alphas, info
+
+
+def em_tcc_f64(problems, iters):
+    """the same update in float64 with plain sums, from 1 on the active lanes, for iters[p] iterations of problem p (an int:
+    for all): what em_tcc is held against -> per problem the float64 values of its active lanes in ascending order"""
+    out = []
+    for p, classes in enumerate(problems):
+        A = 0
+        for m, _ in classes:
+            A |= int(m)
+        lanes = [t for t in range(64) if A >> t & 1]
+        member = np.array([[int(m) >> t & 1 for t in lanes] for m, _ in classes], dtype=np.float64).reshape(len(classes), len(lanes))
+        n = np.array([int(c) for _, c in classes], dtype=np.float64)
+        alpha = np.ones(len(lanes))
+        for _ in range(int(iters if np.isscalar(iters) else iters[p])):
+            d = member @ alpha
+            alpha = alpha * ((n / d) @ member)
+        out.append(alpha)
+    return out
+
+
+def em_flatten(problems):
+    """problems as em_tcc takes them -> (classes EM_CLASS_DTYPE, prob_off uint64 [n + 1], out_off uint64 [n + 1]): the arrays of
+    bdg_em_tcc"""
+    classes = np.zeros(sum(len(c) for c in problems), dtype=EM_CLASS_DTYPE)
+    flat = [mc for c in problems for mc in c]
+    classes["mask"], classes["count"] = [int(m) for m, _ in flat], [int(n) for _, n in flat]
+    prob_off = np.concatenate([[0], np.cumsum([len(c) for c in problems], dtype=np.int64)]).astype(np.uint64)
+    return classes, prob_off, em_out_off(classes, prob_off)
+
+
+def em_out_off(classes, prob_off):
+    """-> out_off uint64 [n + 1]: the active lanes of the problems in front of each"""
+    return np.concatenate([[0], np.cumsum(_popcounts(em_active(classes, prob_off)), dtype=np.int64)]).astype(np.uint64)
+
+
+def em_active(classes, prob_off):
+    """-> A of every problem, uint64 [n]"""
+    n = len(prob_off) - 1
+    A = np.zeros(n, dtype=np.uint64)
+    has = np.flatnonzero(prob_off[1:] > prob_off[:-1])
+    if len(has):
+        A[has] = np.bitwise_or.reduceat(classes["mask"][:int(prob_off[n])], prob_off[:-1][has].astype(np.int64))
+    return A
+
+
+def _popcounts(x):
+    return np.unpackbits(np.ascontiguousarray(x, dtype="<u8").view(np.uint8).reshape(-1, 8), axis=1).sum(axis=1, dtype=np.int64)
+
+
+def em_lists(classes, prob_off):
+    """the arrays of bdg_em_tcc -> problems as em_tcc takes them"""
+    pairs = list(zip(classes["mask"].tolist(), classes["count"].tolist()))
+    return [pairs[int(a):int(b)] for a, b in zip(prob_off[:-1], prob_off[1:])]
+
+
+def checker_em(classes, prob_off, out_off, eps, max_iter, start=None):
+    """em_tcc with the call of Context.em_tcc: flat arrays in, (alpha float32 [out_off[-1]], EM_INFO_DTYPE [n]) out"""
+    parts = None if start is None else [start[int(a):int(b)] for a, b in zip(out_off[:-1], out_off[1:])]
+    alphas, info = em_tcc(em_lists(classes, prob_off), eps, max_iter, parts)
+    return np.concatenate(alphas + [np.zeros(0, np.float32)]).astype(np.float32), info
+
+
 # ---------------------------------------------------------------- molecules and the matrix (host, product side) ----
 def flag_names(flags):
     return ",".join(name for bit, name in FLAG_NAMES if flags & bit)
@@ -347,11 +490,126 @@ def isoform_files(names, tx_names, feat, heads, cb, ub, iso, cells, molecules):
     return files, counts
 
 
-def count_matrix_text(text, names, assign, isoforms=None):
+def _em_group(keys, cls):
+    """keys int64 [n, k] and the class of each row -> (the distinct keys in lexicographic order, classes EM_CLASS_DTYPE grouped
+    by key and ascending by the class's 64-bit value within it, prob_off)"""
+    if not len(cls):
+        return keys[:0], np.zeros(0, dtype=EM_CLASS_DTYPE), np.zeros(1, dtype=np.uint64)
+    order = np.lexsort((cls,) + tuple(keys[:, c] for c in range(keys.shape[1] - 1, -1, -1)))
+    keys, cls = keys[order], cls[order]
+    new_key = np.concatenate([[True], (keys[1:] != keys[:-1]).any(axis=1)])
+    first = np.flatnonzero(new_key | np.concatenate([[True], cls[1:] != cls[:-1]]))
+    classes = np.zeros(len(first), dtype=EM_CLASS_DTYPE)
+    classes["mask"], classes["count"] = cls[first], np.diff(np.concatenate([first, [len(cls)]]))
+    starts = np.flatnonzero(new_key[first])
+    return keys[first][starts], classes, np.concatenate([starts, [len(first)]]).astype(np.uint64)
+
+
+def em_problems(molecules, cells=None):
+    """molecules: count_molecules' fourth value; every molecule with a class (not a CONFLICT) counts once for its (cell, gene,
+    class) -> dict: cell_keys int64 [P, 2] (cell index, gene id) in that order, cell_classes, cell_off; pool_genes int64 [G]
+    ascending, pool_classes, pool_off - the pooled problem of a gene has its counts summed over the cells.  Classes ascend by
+    their 64-bit value.  (cells, the barcodes, is not needed: the cell indices of the molecules are theirs.)"""
+    mol = np.asarray(molecules, dtype=np.int64).reshape(-1, 3)
+    cls = np.ascontiguousarray(mol[:, 2]).view(np.uint64)
+    keep = cls != 0
+    mol, cls = mol[keep], cls[keep]
+    cell_keys, cell_classes, cell_off = _em_group(np.stack([mol[:, 1], mol[:, 0]], axis=1), cls)
+    pool_keys, pool_classes, pool_off = _em_group(mol[:, :1], cls)
+    return dict(cell_keys=cell_keys, cell_classes=cell_classes, cell_off=cell_off, pool_genes=pool_keys[:, 0], pool_classes=pool_classes,
+                pool_off=pool_off)
+
+
+def _em_lanes(A):
+    """A uint64 [n] -> (problem, lane) of every active lane, in the order of the output layout"""
+    bits = (A[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+    return np.nonzero(bits)
+
+
+def em_batches(prob_off, most=None):
+    """ranges of problems with at most `most` (EM_BATCH_CLASSES) classes each, a problem never cut -> [(first, end)]"""
+    most = EM_BATCH_CLASSES if most is None else most
+    out, at, n = [], 0, len(prob_off) - 1
+    while at < n:
+        end = int(np.searchsorted(prob_off, int(prob_off[at]) + most, side="right")) - 1
+        end = min(max(end, at + 1), n)
+        out.append((at, end))
+        at = end
+    return out
+
+
+def em_run(run, problems, eps, max_iter, init="uniform", most=None):
+    """the driver.  run(classes, prob_off, out_off, eps, max_iter, start) -> (alpha, info) is Context.em_tcc or checker_em.
+    The pooled problems first, in one call; then the cell problems in calls of bounded size, with init "pool" each from its
+    gene's pooled alpha on its own active lanes -> (pool alpha, pool info, cell alpha, cell info), alpha in the flat layout"""
+    pc, po = problems["pool_classes"], problems["pool_off"]
+    pool_alpha, pool_info = run(pc, po, em_out_off(pc, po), eps, max_iter, None)
+    cc, co = problems["cell_classes"], problems["cell_off"]
+    A = em_active(cc, co)
+    out_off = em_out_off(cc, co)
+    start = None
+    if init == "pool" and len(A):
+        full = np.zeros((len(problems["pool_genes"]), 64), dtype=np.float32)
+        gp, gl = _em_lanes(em_active(pc, po))
+        full[gp, gl] = pool_alpha
+        prob, lane = _em_lanes(A)
+        start = full[np.searchsorted(problems["pool_genes"], problems["cell_keys"][prob, 1]), lane]
+    alpha, info = np.zeros(int(out_off[-1]), dtype=np.float32), np.zeros(len(A), dtype=EM_INFO_DTYPE)
+    for a, b in em_batches(co, most):
+        c0, c1, o0, o1 = int(co[a]), int(co[b]), int(out_off[a]), int(out_off[b])
+        alpha[o0:o1], info[a:b] = run(cc[c0:c1], co[a:b + 1] - co[a], out_off[a:b + 1] - out_off[a], eps, max_iter,
+                                      None if start is None else start[o0:o1])
+    return pool_alpha, pool_info, alpha, info
+
+
+def em_files(names, tx_names, feat, cells, molecules, run, eps=EM_EPS_DEFAULT, max_iter=EM_MAX_ITER_DEFAULT, init="uniform"):
+    """the two files of --isoform_em (EM_FILES) and the counts of its log line; arguments as for isoform_files, run as for em_run
+    -> ({file name: bytes}, counts dict)"""
+    local, overflow = local_indices(feat)
+    feat_l = np.asarray(feat).tolist()
+    of_bit, spills = {}, set()
+    for q, (f, t, o) in enumerate(zip(feat_l, local.tolist(), overflow.tolist())):
+        of_bit.setdefault((f, t), q)                      # (only bit 63 of an overflowing gene has more than one)
+        if o and t == LOCAL_MAX:
+            spills.add(f)
+    problems = em_problems(molecules, cells)
+    pool_alpha, pool_info, alpha, info = em_run(run, problems, eps, max_iter, init)
+    overflow_mass = 0.0
+    entries = []
+    prob, lane = _em_lanes(em_active(problems["cell_classes"], problems["cell_off"]))
+    keys = problems["cell_keys"]
+    for p, t, v in zip(prob.tolist(), lane.tolist(), alpha.tolist()):
+        c, f = int(keys[p, 0]), int(keys[p, 1])
+        if t == LOCAL_MAX and f in spills:
+            overflow_mass += v
+            continue
+        text = "%.3f" % v
+        if text != "0.000":
+            entries.append((c, of_bit[(f, t)], text))
+    entries.sort()
+    rows = ["%%MatrixMarket matrix coordinate real general\n", "%d %d %d\n" % (len(tx_names), len(cells), len(entries))]
+    rows += ["%d %d %s\n" % (q + 1, c + 1, text) for c, q, text in entries]
+    pooled = {}
+    gp, gl = _em_lanes(em_active(problems["pool_classes"], problems["pool_off"]))
+    for g, t, v in zip(gp.tolist(), gl.tolist(), pool_alpha.tolist()):
+        pooled[(int(problems["pool_genes"][g]), t)] = v
+    pool_rows = ["transcript\tgene\tabundance\n"]
+    for name, f, t in zip(tx_names, feat_l, local.tolist()):
+        pool_rows.append("%s\t%s\t%s\n" % (name, names[f], "*" if t == LOCAL_MAX and f in spills else "%.3f" % pooled.get((f, t), 0.0)))
+    flags = info["flags"]
+    counts = dict(em_problems=len(info), em_pooled=len(pool_info), em_closed=int((flags == EM_CLOSED).sum()),
+                  em_converged=int((flags == EM_CONVERGED).sum()), em_maxiter=int((flags == EM_MAXITER).sum()),
+                  em_range=int((flags == EM_RANGE).sum()), em_iters=int(max(info["iters"].max(initial=0), pool_info["iters"].max(initial=0))),
+                  em_lost=int(info["lost"].sum(dtype=np.int64)), em_overflow=overflow_mass)
+    return {"isoform_em_matrix.mtx": "".join(rows).encode(), "isoform_em_pool.tsv": "".join(pool_rows).encode()}, counts
+
+
+def count_matrix_text(text, names, assign, isoforms=None, em=None):
     """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
     assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
     -> ({file name: bytes}, counts dict).  With isoforms = (transcript names, their feature ids) assign returns the pair
-    (REC_DTYPE array, ISO_DTYPE array), and the files of isoform_files and its counts join the four, which stay as they are."""
+    (REC_DTYPE array, ISO_DTYPE array), and the files of isoform_files and its counts join the four, which stay as they are.
+    With em = (run, eps, max_iter, init) beside isoforms (em_files) the two files of EM_FILES and their counts join those."""
     from .consensus import parse_tagged
     heads, seqs, cb, ub = parse_tagged(text)
     take = [i for i, c in enumerate(cb) if c is not None]
@@ -377,6 +635,10 @@ def count_matrix_text(text, names, assign, isoforms=None):
                                          [ub[i] for i in take], iso, cells, molecules)
         files.update(more)
         counts.update(iso_counts)
+        if em is not None:
+            more, em_counts = em_files(names, isoforms[0], isoforms[1], cells, molecules, *em)
+            files.update(more)
+            counts.update(em_counts)
     return files, counts
 
 
@@ -460,9 +722,18 @@ def device_assign(ctx, min_hits, margin=None):
     return run
 
 
-def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None):
+def device_em(ctx):
+    """run of em_run on the device: bdg_em_tcc"""
+    def run(classes, prob_off, out_off, eps, max_iter, start):
+        return ctx.em_tcc(classes, prob_off, out_off, eps, max_iter, start)
+    return run
+
+
+def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None,
+                           em=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
-    reads.tsv, and with iso_margin (--isoforms) the files of ISO_FILES -> counts"""
+    reads.tsv, with iso_margin (--isoforms) the files of ISO_FILES, and with em = (eps, max_iter, init) (--isoform_em) those of
+    EM_FILES -> counts"""
     from . import _native
     tx_names, tx_seqs = read_fasta(transcripts)
     names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
@@ -474,7 +745,8 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
     try:
         stats = ctx.genes_index_stats()
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
-                                          (tx_names, feat) if iso_margin else None)
+                                          (tx_names, feat) if iso_margin else None,
+                                          (device_em(ctx),) + tuple(em) if iso_margin and em else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
@@ -495,6 +767,11 @@ def log_counts(counts, out_dir):
         logger.info("Isoforms: reads %d unique, %d multi, %d no gene; molecules %d unique, %d multi, %d conflict; %d classes"
                     % (counts["iso_unique"], counts["iso_multi"], counts["iso_nogene"], counts["mol_unique"], counts["mol_multi"],
                        counts["mol_conflict"], counts["classes"]))
+    if "em_problems" in counts:
+        logger.info("Isoform EM: %d problems and %d pooled; %d closed form, %d converged, %d at the iteration cap, %d out of range; "
+                    "at most %d iterations; %d molecules lost, %.3f in the last bit of overflowing genes"
+                    % (counts["em_problems"], counts["em_pooled"], counts["em_closed"], counts["em_converged"], counts["em_maxiter"],
+                       counts["em_range"], counts["em_iters"], counts["em_lost"], counts["em_overflow"]))
 
 
 def gene_k_arg(v):
@@ -527,8 +804,35 @@ def iso_margin_arg(v):
     return x
 
 
+def em_eps_arg(v):
+    try:
+        x = float(v)
+    except ValueError:
+        x = 0.0
+    if not EM_EPS_MIN <= x <= EM_EPS_MAX:                 # (a NaN fails both comparisons)
+        raise argparse.ArgumentTypeError("--em_eps takes a number, 1e-6 .. 1")
+    return x
+
+
+def em_max_iter_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if not 1 <= x <= EM_MAX_ITER_MAX:
+        raise argparse.ArgumentTypeError("--em_max_iter takes an integer, 1 .. %d" % EM_MAX_ITER_MAX)
+    return x
+
+
 def check_iso_options(p, a, with_matrix):
-    """the errors of --isoforms and --iso_margin, the same on both command lines; sets a.iso_margin to None without --isoforms"""
+    """the errors of --isoforms, --iso_margin and the --isoform_em family, the same on both command lines; sets a.iso_margin to
+    None without --isoforms, and a.em to (eps, max_iter, init) with --isoform_em, else None"""
+    if (a.em_eps is not None or a.em_max_iter is not None or a.em_init is not None) and not a.isoform_em:
+        p.error("--em_eps, --em_max_iter and --em_init need --isoform_em")
+    if a.isoform_em and not a.isoforms:
+        p.error("--isoform_em needs --isoforms: it runs over the classes that --isoforms counts")
+    a.em = (EM_EPS_DEFAULT if a.em_eps is None else a.em_eps, EM_MAX_ITER_DEFAULT if a.em_max_iter is None else a.em_max_iter,
+            a.em_init or EM_INITS[0]) if a.isoform_em else None
     if a.iso_margin is not None and not a.isoforms:
         p.error("--iso_margin needs --isoforms")
     if a.isoforms and not with_matrix:
@@ -545,6 +849,15 @@ def add_gene_options(p):
     p.add_argument("--iso_margin", type=iso_margin_arg, default=None, metavar="M",
                    help="--isoforms: a transcript stays compatible with a read while it has fewer than M of the gene's keys less "
                         "than the best transcript (default %d)" % MARGIN_DEFAULT)
+    p.add_argument("--isoform_em", action="store_true",
+                   help="--isoforms: per-cell transcript abundances by EM over the class counts, on the device; writes %s beside "
+                        "the matrix" % ", ".join(EM_FILES))
+    p.add_argument("--em_eps", type=em_eps_arg, default=None, metavar="E",
+                   help="--isoform_em: a problem stops when no abundance moved by E molecules or more (default %g, 1e-6 .. 1)" % EM_EPS_DEFAULT)
+    p.add_argument("--em_max_iter", type=em_max_iter_arg, default=None, metavar="I",
+                   help="--isoform_em: iterations of a problem at most (default %d, 1 .. %d)" % (EM_MAX_ITER_DEFAULT, EM_MAX_ITER_MAX))
+    p.add_argument("--em_init", choices=EM_INITS, default=None,
+                   help="--isoform_em: a cell's problem starts uniform (default) or from its gene's abundances pooled over the cells")
     p.add_argument("--gene_k", type=gene_k_arg, default=None, metavar="K",
                    help="bases of a key of the gene lookup (default %d, 11 .. 31)" % K_DEFAULT)
     p.add_argument("--gene_min_hits", type=gene_min_hits_arg, default=None, metavar="H",
@@ -574,8 +887,8 @@ def main(argv):
     logger.setLevel(logging.INFO)
     if not logger.handlers:
         logger.addHandler(logging.StreamHandler(stream=sys.stdout))
-    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin),
-               a.output)
+    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
+                                      a.em), a.output)
 
 
 if __name__ == "__main__":

@@ -1047,6 +1047,50 @@ int  bdg_iso_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_
 int  bdg_iso_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, uint32_t margin,
                     bdg_gene_rec* gene_out, bdg_iso_rec* iso_out);
 
+/* ---- isoform abundances by EM over compatibility counts (--isoform_em; checker: badger_amd/genes.py em_tcc) ---- */
+#define BDG_EM_CLOSED           1u           /* bdg_em_info.flags: no iteration was needed (or there was nothing to do) */
+#define BDG_EM_CONVERGED        2u           /* ... delta < eps after `iters` iterations */
+#define BDG_EM_MAXITER          4u           /* ... iters == max_iter without delta < eps */
+#define BDG_EM_RANGE            8u           /* ... N >= 2^24: not run */
+#define BDG_EM_EPS_DEFAULT      1e-3f
+#define BDG_EM_MAX_ITER_DEFAULT 1000
+typedef struct { uint64_t mask; uint32_t count; uint32_t pad; } bdg_em_class;   /* 16 bytes */
+typedef struct { uint32_t iters, flags, lost, pad; } bdg_em_info;                /* 16 bytes; exactly one flag is set */
+/* THE RULE.  IEEE binary32, round to nearest even, denormals kept; every operation below is rounded on its own (no fused
+ * multiply-add), in the order given, so that a device and a host that follow it agree bit for bit.
+ *   problem  a list of classes (mask_j: u64, n_j: u32), j = 0 .. m - 1, in the order given (the command line passes them
+ *            ascending by mask; nothing here needs that, and equal masks are not merged).  A = the OR of the masks;
+ *            transcript (lane) t is active if bit t of A is set.  N = the sum of the n_j, in integers.
+ *            N >= 2^24: flags RANGE, every alpha_t = 0, 0 iterations (a count must convert to binary32 exactly).
+ *            Else m == 0 or N == 0: flags CLOSED, every alpha_t = 0, 0 iterations.
+ *   closed   else, if every mask has exactly one bit: alpha_t = (float)(sum of the n_j with mask_j == 1 << t), an exact
+ *            integer; flags CLOSED, 0 iterations.
+ *   start    else alpha_t = 1.0f for active t (with a start vector: its value for t), and +0.0 for every other t.  The update
+ *            is free of scale, nothing is normalised.
+ *   iterate  new_t = +0.0 for all t, lost = 0; then for j = 0 .. m - 1 in order:
+ *              x_l = alpha_l if bit l of mask_j is set, else +0.0, for the 64 lanes l;
+ *              for s = 32, 16, 8, 4, 2, 1 in this order: x_l = x_l + x_{l xor s}, all 64 lanes at once;
+ *              d_j = x_0;
+ *              if d_j > 0: for every t of mask_j, new_t = new_t + ((float)n_j * alpha_t) / d_j - a product, a quotient and a
+ *              sum, three roundings; otherwise (only a start vector with zeros gets there) lost = lost + n_j.
+ *            Then delta = max over t of |new_t - alpha_t|, alpha = new, iters = iters + 1.
+ *   stop     delta < eps: flags CONVERGED; else iters == max_iter: flags MAXITER; else iterate again.  `lost` is that of the
+ *            last iteration.  alpha_t is in molecules: the sum of the alpha_t is N - lost up to rounding.
+ * A consequence an implementation may use: with A < 2^16 the steps 32 and 16 add +0.0 to the lanes below 16, which is exact,
+ * so that a group of 16 lanes doing the steps 8, 4, 2, 1 has the same bits in d_j; likewise A < 2^32 and 32 lanes.
+ *
+ * Problem p is the classes d_prob_off[p] .. d_prob_off[p + 1] - 1 of d_classes; its active lanes' alpha go, in ascending
+ * order of t, to d_alpha[d_out_off[p]] onwards, so d_out_off[p + 1] - d_out_off[p] == popcount(A_p) is a precondition (not
+ * checked here); d_start is NULL or laid out like d_alpha; d_info [n_prob].  Asynchronous, on the context's stream.
+ * BDG_E_ARG for max_iter == 0 and for an eps that is not finite or not > 0.  n_prob == 0: BDG_OK, nothing is launched. */
+int  bdg_em_tcc_dev(bdg_ctx* ctx, const bdg_em_class* d_classes, const uint64_t* d_prob_off, uint32_t n_prob,
+                    const uint64_t* d_out_off, const float* d_start, float eps, uint32_t max_iter, float* d_alpha,
+                    bdg_em_info* d_info);
+/* The same over host arrays; synchronous; also BDG_E_ARG for problem offsets that decrease and for a problem whose out_off
+ * span is not popcount(A). */
+int  bdg_em_tcc(bdg_ctx* ctx, const bdg_em_class* classes, const uint64_t* prob_off, uint32_t n_prob, const uint64_t* out_off,
+                const float* start, float eps, uint32_t max_iter, float* alpha, bdg_em_info* info);
+
 /* ---- stage 2's read-side plumbing on the host (badger.py:112-121,129; barcode_graph.py:388-410) -------------- */
 /* Read ids of a run, kept natively (12 bytes per read instead of a Python string each). */
 typedef struct bdg_idstore bdg_idstore;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Measurements of the gene calls by k-mer lookup and of the isoform pass on top of them, one
-JSON line each to --out (and stdout).
+"""Measurements of the gene calls by k-mer lookup, of the isoform pass on top of them and of the EM
+over its class counts, one JSON line each to --out (and stdout).
 
     python tools/genes_probe.py --device [--reads 1000000] [--tx_bases 4000000 100000000] --out profiles/r22_genes.jsonl
         bdg_genes_index_build and bdg_genes_assign_dev alone.  Per --tx_bases value a random transcriptome of that many bases in
@@ -23,6 +23,14 @@ JSON line each to --out (and stdout).
         the command line with --count_matrix --isoforms against --count_matrix alone (the transcripts paired into genes of two
         by a --tx2gene map: a read's middle and, as its second isoform, the same without its bases 100 .. 199), then the pairs
         with --parent as above.
+    python tools/genes_probe.py --em [--em_problems 1000000] [--em_wide 100000] --out profiles/r24_isoform_em.jsonl
+        k_em_tcc alone, device-resident, at eps 1e-3 and 1,000 iterations at most: (cell, gene) problems as the
+        isoform workload above makes them - genes of 2 .. 4 isoforms, 1 .. 4 molecules a problem, one in four of them compatible
+        with more than their own transcript - and problems of 16 .. 64 transcripts with 20 .. 200 molecules in sets of 1 .. 4.
+        The share of closed-form problems, the iteration counts and the kernel from the library's event timer.
+    python tools/genes_probe.py --cli --isoforms --em ...
+        the command line with --isoforms --isoform_em against --isoforms alone, then, in this process, the EM step once more
+        over the tagged file of the run: how much of it is the device calls and how much host numpy.
 """
 import argparse
 import os
@@ -201,6 +209,116 @@ def device_probe_iso(args):
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
 
 
+def em_workload(n_prob, t_lo, t_hi, mol_lo, mol_hi, p_multi, extra_max, seed):
+    """n_prob problems: T transcripts (t_lo .. t_hi), mol_lo .. mol_hi molecules each of a random transcript of the problem;
+    with probability p_multi a molecule is also compatible with 1 .. extra_max other transcripts
+    -> (classes, prob_off, out_off) as bdg_em_tcc takes them"""
+    from badger_amd import genes as gn
+    rng = np.random.default_rng(seed)
+    T = rng.integers(t_lo, t_hi + 1, n_prob)
+    n_mol = rng.integers(mol_lo, mol_hi + 1, n_prob)
+    prob = np.repeat(np.arange(n_prob), n_mol)
+    Tm = T[prob]
+    cls = np.uint64(1) << (rng.random(len(prob)) * Tm).astype(np.uint64)
+    extras = np.where(rng.random(len(prob)) < p_multi, rng.integers(1, extra_max + 1, len(prob)), 0)
+    for e in range(extra_max):
+        more = np.uint64(1) << (rng.random(len(prob)) * Tm).astype(np.uint64)
+        cls = np.where(extras > e, cls | more, cls)
+    _, classes, off = gn._em_group(prob[:, None].astype(np.int64), cls)
+    return classes, off, gn.em_out_off(classes, off)
+
+
+def em_probe(args):
+    from badger_amd import _native
+    from badger_amd import genes as gn
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for what, n_prob, shape in (("cell problems of genes of 2 .. 4 isoforms", args.em_problems, (2, 4, 1, 4, 0.25, 2)),
+                                ("problems of 16 .. 64 transcripts", args.em_wide, (16, 64, 20, 200, 0.6, 3))):
+        classes, off, out_off = em_workload(n_prob, *shape, seed=24)
+        n_out = int(out_off[-1])
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (classes.view(np.uint32), off, out_off)]
+        d_alpha, d_info = _native.DeviceArray(ctx, max(n_out, 1), np.float32), _native.DeviceArray(ctx, n_prob * 4, np.uint32)
+        call = lambda: ctx.em_tcc_dev(d[0], d[1], n_prob, d[2], None, args.em_eps, args.em_max_iter, d_alpha, d_info)  # noqa: E731
+        call()
+        ctx.synchronize()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            call()
+            ctx.synchronize()
+            times.append(time.perf_counter() - t0)
+        ctx.profile(True)
+        ctx.profile_reset()
+        for _ in range(args.reps):
+            call()
+        ctx.synchronize()
+        kt = {k: round(v[1] / args.reps, 4) for k, v in ctx.profile_read().items() if k.startswith("k_em") and v[0]}
+        ctx.profile(False)
+        info, alpha = d_info.to_host().view(_native.EM_INFO_DTYPE), d_alpha.to_host()
+        it = info["iters"][info["flags"] != gn.EM_CLOSED].astype(np.int64)
+        per_prob = np.diff(off.astype(np.int64))
+        emit(args.out, {"what": "bdg_em_tcc_dev, device-resident: " + what, "form": "one problem per wave", "eps": args.em_eps,
+                        "max_iter": args.em_max_iter, "problems": n_prob, "classes": int(off[-1]), "classes_per_problem_max": int(per_prob.max()),
+                        "transcripts": n_out, "molecules": int(classes["count"].astype(np.int64).sum()),
+                        "closed": int((info["flags"] == gn.EM_CLOSED).sum()), "closed_share": round(float((info["flags"] == gn.EM_CLOSED).mean()), 4),
+                        "converged": int((info["flags"] == gn.EM_CONVERGED).sum()), "at_cap": int((info["flags"] == gn.EM_MAXITER).sum()),
+                        "iterations_total": int(it.sum()), "iterations_median": float(np.median(it)) if len(it) else 0.0,
+                        "iterations_max": int(it.max(initial=0)),
+                        "class_steps_total": int((info["iters"].astype(np.int64) * per_prob).sum()),
+                        "alpha_sum": round(float(alpha[:n_out].astype(np.float64).sum()), 3),
+                        "call_ms_median": round(1e3 * float(np.median(times)), 3), "call_ms_min": round(1e3 * min(times), 3), "kernel_ms": kt,
+                        "kernel_ms_per_1M_problems": {k: round(v * 1e6 / n_prob, 3) for k, v in kt.items()}})
+        for a in d + [d_alpha, d_info]:
+            a.free()
+
+
+def em_split_probe(args, tagged, tx, tx_map):
+    """the EM step of the command line once more, in this process: seconds in em_files, and of them in the device calls"""
+    from badger_amd import _native
+    from badger_amd import genes as gn
+    _native.PRELOAD_TORCH = False
+    spent = {"em_files_s": 0.0, "device_calls_s": 0.0, "device_calls": 0}
+    files_of, device_of = gn.em_files, gn.device_em
+
+    def timed_files(*a, **kw):
+        t0 = time.perf_counter()
+        try:
+            return files_of(*a, **kw)
+        finally:
+            spent["em_files_s"] += time.perf_counter() - t0
+
+    def timed_device(ctx):
+        run = device_of(ctx)
+
+        def call(*a):
+            t0 = time.perf_counter()
+            try:
+                return run(*a)
+            finally:
+                spent["device_calls_s"] += time.perf_counter() - t0
+                spent["device_calls"] += 1
+        return call
+    gn.em_files, gn.device_em = timed_files, timed_device
+    try:
+        ctx = _native.default_context(0)
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        counts = gn.count_matrix_of_tagged(tagged, tx, tx_map, os.path.join(os.path.dirname(tagged), "matrix_split"), iso_margin=1,
+                                           em=(args.em_eps, args.em_max_iter, "uniform"))
+        total = time.perf_counter() - t0
+        kt = {k: round(v[1], 4) for k, v in ctx.profile_read().items() if k.startswith("k_em") and v[0]}
+        ctx.profile(False)
+    finally:
+        gn.em_files, gn.device_em = files_of, device_of
+    emit(args.out, {"what": "count_matrix_of_tagged with --isoforms --isoform_em, in process: where the EM step's time goes",
+                    "whole_call_s": round(total, 3), "em_files_s": round(spent["em_files_s"], 3),
+                    "device_calls_s": round(spent["device_calls_s"], 3), "device_calls": spent["device_calls"],
+                    "host_numpy_s": round(spent["em_files_s"] - spent["device_calls_s"], 3), "kernel_ms": kt,
+                    "counts": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in counts.items() if k.startswith(("em_", "mol_", "classes"))}})
+
+
 def _transcripts_of(fq, path, n=20000):
     """the middles of the first n reads of a FASTQ file, as they are and reverse-complemented, as a transcript FASTA"""
     comp = bytes.maketrans(b"ACGT", b"TGCA")
@@ -239,7 +357,7 @@ def cli_probe(args):
         r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
-        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l]
+        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l]
 
     def pairs(name_a, a, name_b, b, what):
         walls, said = {name_a: [], name_b: []}, []
@@ -263,8 +381,13 @@ def cli_probe(args):
         tx2, tx_map = os.path.join(tmp, "tx_iso.fa"), os.path.join(tmp, "tx2gene.tsv")
         _isoforms_of(tx, tx2, tx_map)
         matrix = tagged + ["--transcripts", tx2, "--tx2gene", tx_map, "--count_matrix", os.path.join(tmp, "matrix")]
-        pairs("count_matrix", (ROOT, matrix), "isoforms", (ROOT, matrix + ["--isoforms"]),
-              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --tx2gene: with --isoforms against without")
+        if args.em:
+            pairs("isoforms", (ROOT, matrix + ["--isoforms"]), "isoform_em", (ROOT, matrix + ["--isoforms", "--isoform_em"]),
+                  "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --tx2gene --isoforms: with --isoform_em against without")
+            em_split_probe(args, fa, tx2, tx_map)
+        else:
+            pairs("count_matrix", (ROOT, matrix), "isoforms", (ROOT, matrix + ["--isoforms"]),
+                  "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --tx2gene: with --isoforms against without")
     else:
         pairs("tagged", (ROOT, tagged), "count_matrix", (ROOT, tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]),
               "stage2 CLI from FASTQ, --umi_dedup --tagged_reads: with --count_matrix against without")
@@ -284,6 +407,11 @@ def main():
     p.add_argument("--min_hits", type=int, default=3)
     p.add_argument("--isoforms", action="store_true", help="the isoform leg of --device and of --cli (DESIGN 4.20)")
     p.add_argument("--margin", type=int, default=1)
+    p.add_argument("--em", action="store_true", help="k_em_tcc alone; with --cli --isoforms the --isoform_em leg (DESIGN 4.21)")
+    p.add_argument("--em_problems", type=int, default=1000000)
+    p.add_argument("--em_wide", type=int, default=100000)
+    p.add_argument("--em_eps", type=float, default=1e-3)
+    p.add_argument("--em_max_iter", type=int, default=1000)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--cli_reads", type=int, default=1000000)
     p.add_argument("--pairs", type=int, default=3)
@@ -292,6 +420,8 @@ def main():
     args = p.parse_args()
     if args.device:
         (device_probe_iso if args.isoforms else device_probe)(args)
+    if args.em and not args.cli:
+        em_probe(args)
     if args.cli:
         cli_probe(args)
 
