@@ -21,7 +21,7 @@ that is not A, C, G or T equals no pattern letter.  (P, j) is a hit when D_P(j) 
 import numpy as np
 
 from ._native import FLAG_REV
-from .trim import TRIM_EMIT, TRIM_SENSE, TSO, _CODE, _strand_codes, revcomp
+from .trim import TRIM_EMIT, TRIM_SENSE, TSO, _CODE, revcomp
 
 R1 = "CTACACGACGCTCTTCCGATCT"               # barcode_callers.py:154
 PATTERNS = (TSO, revcomp(TSO), R1, revcomp(R1))
@@ -124,31 +124,31 @@ _PEQ = [np.array(_peq(p), dtype=np.uint64) for p in PATTERNS]
 _NOKEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
-def _scan(bases, o, L, rev, b, unit_read, ts, t0, te, kinds, ks_list, cut, key):
-    """Myers' search of `kinds` over units of the reads' scans.  Scan step t of a read visits strand column b - 1 - t; a unit
-    runs the steps [ts, te) from a fresh automaton and reports from step t0 on.  ks_list: per wanted max_ed the bounds per
-    kind; cut [len(ks_list), n] and key [len(ks_list), n] take minima of j and of (D << 40 | j << 2 | kind)."""
+def _scan(bases, a0, step, comp, pos0, pstep, ur, ts, t0, te, peqs, kmax, sink):
+    """Myers' search of the kinds in `peqs` (kind -> equality words) over units.  Scan step t of read r visits byte
+    a0[r] + step[r] * t, complemented where comp[r], and reports the position pos0[r] + pstep * t (step, comp: one per read or
+    one for all); a unit runs the steps [ts, te) of read ur from a fresh automaton and reports from t0 on.
+    sink(kind, reads, positions, distances) takes every report with a distance <= kmax[kind]."""
+    step, comp = np.broadcast_to(step, a0.shape), np.broadcast_to(comp, a0.shape)
     order = np.argsort(-(te - ts), kind="stable")
-    unit_read, ts, t0, te = unit_read[order], ts[order], t0[order], te[order]
+    ur, ts, t0, te = ur[order], ts[order], t0[order], te[order]
     length = te - ts
     nu = int((length > 0).sum())
-    kmax = {kd: max(ks[kd] for ks in ks_list) for kd in kinds}
-    st = {kd: [np.full(nu, (1 << len(PATTERNS[kd])) - 1, np.uint64), np.zeros(nu, np.uint64),
-               np.full(nu, len(PATTERNS[kd]), np.int64)] for kd in kinds}
+    st = {kd: [np.full(nu, (1 << len(PATTERNS[kd])) - 1, np.uint64), np.zeros(nu, np.uint64), np.full(nu, len(PATTERNS[kd]), np.int64)]
+          for kd in peqs}
     neg_len = -length[:nu]
     one = np.uint64(1)
-    for step in range(int(length[0]) if nu else 0):
-        cnt = int(np.searchsorted(neg_len, -step, side="left"))         # units with length > step: a prefix
-        r = unit_read[:cnt]
-        t = ts[:cnt] + step
-        x = b[r] - 1 - t
-        code = _strand_codes(bases, o[r], L[r], rev[r], x)
+    for s in range(int(length[0]) if nu else 0):
+        cnt = int(np.searchsorted(neg_len, -s, side="left"))            # units with length > s: a prefix
+        r = ur[:cnt]
+        t = ts[:cnt] + s
+        code = _CODE[bases[a0[r] + step[r] * t]]
+        code = np.where(comp[r] & (code < 4), 3 - code, code)
         rep = t >= t0[:cnt]
-        for kd in kinds:
-            m = len(PATTERNS[kd])
-            sh = np.uint64(m - 1)
+        for kd, peq in peqs.items():
+            sh = np.uint64(len(PATTERNS[kd]) - 1)
             pv, mv, sc = st[kd][0][:cnt], st[kd][1][:cnt], st[kd][2][:cnt]
-            eq = _PEQ[kd][code]
+            eq = peq[code]
             xv = eq | mv
             xh = (((eq & pv) + pv) ^ pv) | eq
             ph = mv | ~(xh | pv)
@@ -159,12 +159,20 @@ def _scan(bases, o, L, rev, b, unit_read, ts, t0, te, kinds, ks_list, cut, key):
             mv[:] = ph & xv
             hit = np.nonzero(rep & (sc <= kmax[kd]))[0]
             if len(hit):
-                d, j, rr = sc[hit], x[hit], r[hit]
-                k64 = (d.astype(np.uint64) << np.uint64(40)) | (j.astype(np.uint64) << np.uint64(2)) | np.uint64(kd)
-                for e, ks in enumerate(ks_list):
-                    ok = d <= ks[kd]
-                    np.minimum.at(cut[e], rr[ok], j[ok])
-                    np.minimum.at(key[e], rr[ok], k64[ok])
+                sink(kd, r[hit], pos0[r[hit]] + pstep * t[hit], sc[hit])
+
+
+def _units(ln, segment, warm):
+    """scan lengths per read -> the units (read, ts, t0, te): one per read with steps to scan, or with `segment` one per piece
+    of that many steps, started `warm` steps early"""
+    if segment is None:
+        ur = np.nonzero(ln > 0)[0]
+        z = np.zeros(len(ur), np.int64)
+        return ur, z, z, ln[ur]
+    nseg = (ln + segment - 1) // segment
+    ur = np.repeat(np.arange(len(ln)), nseg)
+    t0 = (np.arange(len(ur)) - np.repeat(np.cumsum(nseg) - nseg, nseg)) * segment
+    return ur, np.maximum(t0 - warm, 0), t0, np.minimum(t0 + segment, ln[ur])
 
 
 def chimera_batch_multi(bases, off, recs, trim, max_eds, segment=None):
@@ -175,27 +183,27 @@ def chimera_batch_multi(bases, off, recs, trim, max_eds, segment=None):
     off = np.ascontiguousarray(off).astype(np.int64)
     n = len(off) - 1
     ks_list = [[bound(kd, e) for kd in range(4)] for e in max_eds]
-    big = np.iinfo(np.int64).max
-    cut = np.full((len(max_eds), n), big, np.int64)
-    key = np.full((len(max_eds), n), _NOKEY, np.uint64)
+    kmax = [max(ks[kd] for ks in ks_list) for kd in range(4)]
+    cut = np.full((len(max_eds), n), np.iinfo(np.int64).max, np.int64)
+    key = np.full((len(max_eds), n), _NOKEY, np.uint64)              # minima of j and of (D << 40 | j << 2 | kind)
+
+    def sink(kd, r, j, d):
+        k64 = (d.astype(np.uint64) << np.uint64(40)) | (j.astype(np.uint64) << np.uint64(2)) | np.uint64(kd)
+        for e, ks in enumerate(ks_list):
+            ok = d <= ks[kd]
+            np.minimum.at(cut[e], r[ok], j[ok])
+            np.minimum.at(key[e], r[ok], k64[ok])
+
     o, L = off[:-1], np.diff(off)
     rev = (recs["flags"] & FLAG_REV) != 0
     a, b = trim["cdna_start"].astype(np.int64), trim["cdna_end"].astype(np.int64)
     ln = np.where((trim["flags"] & TRIM_EMIT) != 0, b - a, 0)
-    if segment is None:
-        idx = np.nonzero(ln > 0)[0]
-        z = np.zeros(len(idx), np.int64)
-        _scan(bases, o, L, rev, b, idx, z, z, ln[idx], (0, 1, 2, 3), ks_list, cut, key)
-    else:
-        assert len(max_eds) == 1
-        nseg = (ln + segment - 1) // segment
-        ur = np.repeat(np.arange(n), nseg)
-        g = np.arange(len(ur)) - np.repeat(np.cumsum(nseg) - nseg, nseg)
-        t0 = g * segment
-        te = np.minimum(t0 + segment, ln[ur])
-        for kinds in ((0, 1), (2, 3)):
-            warm = len(PATTERNS[kinds[0]]) + ks_list[0][kinds[0]]
-            _scan(bases, o, L, rev, b, ur, np.maximum(t0 - warm, 0), t0, te, kinds, ks_list, cut, key)
+    # scan step t visits strand column b - 1 - t: byte o + b - 1 - t as it is, or for a reverse-strand record o + L - b + t complemented
+    a0, step = np.where(rev, o + L - b, o + b - 1), np.where(rev, 1, -1)
+    assert segment is None or len(max_eds) == 1
+    for kinds in ((0, 1, 2, 3),) if segment is None else ((0, 1), (2, 3)):
+        ur, ts, t0, te = _units(ln, segment, len(PATTERNS[kinds[0]]) + kmax[kinds[0]])
+        _scan(bases, a0, step, rev, b - 1, -1, ur, ts, t0, te, {kd: _PEQ[kd] for kd in kinds}, kmax, sink)
     outs = []
     for e in range(len(max_eds)):
         out = np.zeros(n, dtype=CHIMERA_DTYPE)

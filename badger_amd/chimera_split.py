@@ -21,8 +21,7 @@ A molecule lies in a read as R1 .. TSO or as TSOrc .. R1rc: kinds 2 and 1 mark w
 """
 import numpy as np
 
-from .chimera import PATTERNS, _peq, bound, start_distances, start_distances_literal
-from .trim import _CODE
+from .chimera import PATTERNS, _peq, _scan, _units, bound, start_distances, start_distances_literal
 
 MARGIN = 64                                 # BDG_SPLIT_MARGIN
 CELL = 32                                   # BDG_SPLIT_CELL
@@ -51,23 +50,9 @@ def end_distances_literal(pattern, text):
 
 
 def end_distances(pattern, text):
-    """the same numbers by Myers' search over the text forwards (one word of m bits)"""
-    m = len(pattern)
-    peq, mask, top = _peq(pattern[::-1]), (1 << m) - 1, 1 << (m - 1)      # (_peq reverses: bit i = pattern[i] here)
-    pv, mv, score = mask, 0, m
-    out = []
-    for ch in text:
-        eq = peq[int(_CODE[ord(ch)])]
-        xv = eq | mv
-        xh = ((((eq & pv) + pv) ^ pv) | eq) & mask
-        ph = (mv | ~(xh | pv)) & mask
-        mh = pv & xh
-        score += (1 if ph & top else 0) - (1 if mh & top else 0)
-        ph, mh = (ph << 1) & mask, (mh << 1) & mask
-        pv = (mh | ~(xv | ph)) & mask
-        mv = ph & xv
-        out.append(score)
-    return out
+    """the same numbers by Myers' search over the text forwards: the mirror image of chimera.start_distances (the reversed
+    pattern over the reversed text, read backwards)"""
+    return start_distances(pattern[::-1], text[::-1])[::-1]
 
 
 # ----------------------------------------------------------------------------- one read, plain integers
@@ -125,41 +110,6 @@ _PEQ_FWD = {kd: np.array(_peq(PATTERNS[kd][::-1]), dtype=np.uint64) for kd in EN
 _NOKEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
-def _scan(bases, a0, step, pos0, ur, ts, t0, te, peqs, kmax, sink):
-    """Myers' search of the kinds in `peqs` over units.  Scan step t of read r visits byte a0[r] + step * t and reports the
-    position pos0[r] + step * t; a unit runs the steps [ts, te) of read ur from a fresh automaton and reports from t0 on.
-    sink(kind, reads, positions, distances) takes every report with a distance <= kmax[kind]."""
-    order = np.argsort(-(te - ts), kind="stable")
-    ur, ts, t0, te = ur[order], ts[order], t0[order], te[order]
-    length = te - ts
-    nu = int((length > 0).sum())
-    st = {kd: [np.full(nu, (1 << len(PATTERNS[kd])) - 1, np.uint64), np.zeros(nu, np.uint64), np.full(nu, len(PATTERNS[kd]), np.int64)]
-          for kd in peqs}
-    neg_len = -length[:nu]
-    one = np.uint64(1)
-    for s in range(int(length[0]) if nu else 0):
-        cnt = int(np.searchsorted(neg_len, -s, side="left"))            # units with length > s: a prefix
-        r = ur[:cnt]
-        t = ts[:cnt] + s
-        code = _CODE[bases[a0[r] + step * t]]
-        rep = t >= t0[:cnt]
-        for kd, peq in peqs.items():
-            sh = np.uint64(len(PATTERNS[kd]) - 1)
-            pv, mv, sc = st[kd][0][:cnt], st[kd][1][:cnt], st[kd][2][:cnt]
-            eq = peq[code]
-            xv = eq | mv
-            xh = (((eq & pv) + pv) ^ pv) | eq
-            ph = mv | ~(xh | pv)
-            mh = pv & xh
-            sc += ((ph >> sh) & one).astype(np.int64) - ((mh >> sh) & one).astype(np.int64)
-            ph, mh = ph << one, mh << one
-            pv[:] = mh | ~(xv | ph)
-            mv[:] = ph & xv
-            hit = np.nonzero(rep & (sc <= kmax[kd]))[0]
-            if len(hit):
-                sink(kd, r[hit], pos0[r[hit]] + step * t[hit], sc[hit])
-
-
 def batch_hits(bases, off, max_ed_max=MAX_ED_RANGE[1], segment=None):
     """every hit of every read at the bounds of max_ed_max, margins applied -> arrays (read, pos, D, kind)"""
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
@@ -175,18 +125,8 @@ def batch_hits(bases, off, max_ed_max=MAX_ED_RANGE[1], segment=None):
     ln = np.where(L >= 2 * MARGIN, L, 0)
     kmax = {kd: bound(kd, max_ed_max) for kd in range(4)}
     for peqs, a0, step, pos0 in ((_PEQ_REV, o + L - 1, -1, L - 1), (_PEQ_FWD, o, 1, np.ones(n, np.int64))):
-        if segment is None:
-            idx = np.nonzero(ln > 0)[0]
-            z = np.zeros(len(idx), np.int64)
-            _scan(bases, a0, step, pos0, idx, z, z, ln[idx], peqs, kmax, sink)
-        else:
-            nseg = (ln + segment - 1) // segment
-            ur = np.repeat(np.arange(n), nseg)
-            g = np.arange(len(ur)) - np.repeat(np.cumsum(nseg) - nseg, nseg)
-            t0 = g * segment
-            te = np.minimum(t0 + segment, ln[ur])
-            warm = max(len(PATTERNS[kd]) + kmax[kd] for kd in peqs)
-            _scan(bases, a0, step, pos0, ur, np.maximum(t0 - warm, 0), t0, te, peqs, kmax, sink)
+        ur, ts, t0, te = _units(ln, segment, max(len(PATTERNS[kd]) + kmax[kd] for kd in peqs))
+        _scan(bases, a0, step, False, pos0, step, ur, ts, t0, te, peqs, kmax, sink)
     cat = lambda v: np.concatenate(v) if v else np.zeros(0, np.int64)                     # noqa: E731
     return cat(acc[0]), cat(acc[1]), cat(acc[2]), cat(acc[3])
 

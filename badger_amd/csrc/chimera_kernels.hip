@@ -7,77 +7,27 @@
 //                b - 1 - t, and the automaton's score behind step t is D_P(b - 1 - t).  For a reverse-strand record "backwards
 //                in s" is forwards in the read's memory with ASCII bit 2 flipped (the complement's code bits), for a forward
 //                record it is backwards in memory: either way a contiguous run of bytes, read as aligned words.
-//     split      one lane per whole read would make a wave as slow as its longest read.  The unit of work is a segment of
-//                BDG_CHIMERA_SEGMENT scan steps.  The split is exact: a match with at most k edits spans at most m + k text
-//                columns, so the hit at step t >= t0 depends only on the steps (t - (m + k), t]; an automaton started fresh
-//                at or before step t0 - (m + k) therefore holds, at every step of the segment, the whole scan's score
-//                wherever that score is <= k, and never a smaller one (a fresh start takes starts away from the minimum, it
-//                adds none).  All four automata start WARM = 30 + 8 steps early, the m + k of the TSO at max_ed 6: an earlier
-//                start than a pattern needs changes nothing by the same argument.
+//     split      the unit of work is a segment of BDG_CHIMERA_SEGMENT scan steps, run from a fresh automaton started WARM
+//                steps early (exact: adapter_scan.hpp, which also holds the column and the walk over a unit's words).
 //     balance    the 64 reads of a wave put their segment counts through a prefix sum; in every round each lane takes the
 //                next unit (a binary search over the 64 sums in LDS finds its read), so all lanes run SEGMENT + WARM steps but
 //                for a read's last, shorter piece.
 //     automata   four words of 32 bits (30 / 30 / 22 / 22 rows), pv / mv / score each in registers; the three code bits of a base
 //                (ASCII bits 1, 2 and "is N" bit 3, spread over a word) are made once and shared; equality words come from the
-//                two bit planes of each pattern (compile-time constants).  Steps outside [start, end) of the unit inside its
-//                first and last word are turned into 'N', which no pattern letter equals: in front of a fresh automaton that
-//                leaves it fresh, behind the end nothing is reported.
+//                two bit planes of each pattern (compile-time constants).
 //     combine    hits are rare.  A hit takes two LDS atomic minima on its read's entries: the column (cut) and the packed key
 //                (D << 36 | j << 2 | kind).  All units of a read run in the wave that owns it, so no global atomics and no second
 //                pass: behind the rounds every lane writes its own read's 12 bytes.  The record is a function of the set of
 //                hits alone.
-#include "bdg_common.hpp"
+#include "adapter_scan.hpp"
 
 namespace {
 
-constexpr int SEG = BDG_CHIMERA_SEGMENT;
-constexpr int TSO_LEN = 30, R1_LEN = 22;
-constexpr int WARM = TSO_LEN + BDG_CHIMERA_MAX_ED_MAX + 2;     // m + k of the longest pattern at its largest bound
-constexpr char TSO[TSO_LEN + 1] = BDG_TRIM_TSO_SEQ;
-constexpr char R1[R1_LEN + 1] = BDG_CHIMERA_R1_SEQ;
-static_assert(sizeof(BDG_TRIM_TSO_SEQ) == TSO_LEN + 1 && sizeof(BDG_CHIMERA_R1_SEQ) == R1_LEN + 1, "each pattern in one 32-bit word");
-static_assert(SEG % 4 == 0 && SEG >= 64, "segments are whole words");
-
-// Bit i of a plane = ASCII bit `bit` of row i of the automaton.  The automaton runs the pattern reversed: row i of kind 0 / 2
-// is P[m - 1 - i]; the reverse complement reversed is the complement, row i = comp(P[i]), which flips ASCII bit 2 alone.
-constexpr uint32_t plane(const char* p, int m, int bit, bool rc)
-{
-    uint32_t w = 0;
-    for (int i = 0; i < m; ++i) {
-        const unsigned char c = (unsigned char)(rc ? p[i] ^ 4 : p[m - 1 - i]);
-        w |= (uint32_t)((c >> bit) & 1u) << i;
-    }
-    return w;
-}
+// kinds 0 / 2 run the pattern reversed, kinds 1 / 3 the complement (plane's rc)
 constexpr uint32_t T0_P0 = plane(TSO, TSO_LEN, 1, false), T0_P1 = plane(TSO, TSO_LEN, 2, false);
 constexpr uint32_t T1_P0 = plane(TSO, TSO_LEN, 1, true),  T1_P1 = plane(TSO, TSO_LEN, 2, true);
 constexpr uint32_t R2_P0 = plane(R1, R1_LEN, 1, false),   R2_P1 = plane(R1, R1_LEN, 2, false);
 constexpr uint32_t R3_P0 = plane(R1, R1_LEN, 1, true),    R3_P1 = plane(R1, R1_LEN, 2, true);
-
-// One column of Myers' search (D[0][j] = 0) for a pattern of M rows: k_strict_filter's form of the recurrence, every line
-// that joins three words one v_bitop3.  Only bit M - 1 is ever read and carries only move upwards: the bits above hold anything.
-template <int M>
-__device__ __forceinline__ void column(uint32_t m0, uint32_t m1, uint32_t mn, uint32_t P0, uint32_t P1,
-                                       uint32_t& pv, uint32_t& mv, int& score)
-{
-    const uint32_t off = __builtin_amdgcn_bitop3_b32(m1, P1, mn, 0xBE);                // (m1 ^ P1) | mn: where the base cannot match
-    const uint32_t eq = __builtin_amdgcn_bitop3_b32(m0, P0, off, 0x41);                // ~((m0 ^ P0) | off)
-    const uint32_t xv = eq | mv;
-    const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);     // (((eq & pv) + pv) ^ pv) | eq
-    const uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                 // mv | ~(xh | pv)
-    const uint32_t mh = pv & xh;
-    score += (int)((ph >> (M - 1)) & 1u);
-    score -= (int)((mh >> (M - 1)) & 1u);
-    const uint32_t ph1 = ph << 1, mh1 = mh << 1;
-    pv = __builtin_amdgcn_bitop3_b32(mh1, xv, ph1, 0xF1);                              // mh1 | ~(xv | ph1)
-    mv = ph1 & xv;
-}
-
-// the low min(max(k, 0), 4) bytes of a word
-__device__ __forceinline__ uint32_t low_bytes(int k)
-{
-    return k >= 4 ? 0xFFFFFFFFu : (k <= 0 ? 0u : (1u << (8 * k)) - 1u);
-}
 
 constexpr unsigned long long NO_KEY = ~0ull;
 
@@ -111,12 +61,7 @@ void k_chimera_search(const uint8_t* __restrict__ bases, const uint64_t* __restr
             }
         }
     }
-    uint32_t incl = ((uint32_t)len + (uint32_t)SEG - 1u) / (uint32_t)SEG;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
+    const uint32_t incl = wave_incl_scan(((uint32_t)len + (uint32_t)SEG - 1u) / (uint32_t)SEG);
     s_incl[lane] = incl; s_addr[lane] = addr; s_b[lane] = b; s_len[lane] = len; s_rev[lane] = rev;
     s_cut[lane] = 0xFFFFFFFFu; s_key[lane] = NO_KEY;
     __syncthreads();                                 // (a block is one wave)
@@ -124,53 +69,31 @@ void k_chimera_search(const uint8_t* __restrict__ bases, const uint64_t* __restr
     const int thr = max_ed;                          // the TSO's scores are kept 2 lower: one bound for all four
 
     for (uint32_t u = (uint32_t)lane; u < units; u += 64u) {
-        int r = 0;                                   // the first read whose inclusive sum lies above u
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) if (s_incl[r + s - 1] <= u) r += s;
+        const int r = read_above(s_incl, u);
         const uint32_t g = u - (r ? s_incl[r - 1] : 0u);
         const int ulen = s_len[r], ub = s_b[r];
-        const bool urev = s_rev[r] != 0;
-        const uint64_t a0 = s_addr[r];
         const int t0 = (int)(g * (uint32_t)SEG);
         const int te = t0 + SEG < ulen ? t0 + SEG : ulen;
-        const int ts = t0 > WARM ? t0 - WARM : 0;
-        // words in scan order: forwards in memory for a reverse-strand record, backwards (bytes swapped) for a forward one
-        const uint64_t as = urev ? a0 + (uint64_t)ts : a0 - (uint64_t)ts;
-        const int lead = urev ? (int)(as & 3u) : 3 - (int)(as & 3u);
-        const uint32_t* wp = reinterpret_cast<const uint32_t*>(as & ~(uint64_t)3);
-        const int wstep = urev ? 1 : -1;
-        const uint32_t flip = urev ? 0x04040404u : 0u;
         uint32_t pv0 = ~0u, pv1 = ~0u, pv2 = ~0u, pv3 = ~0u, mv0 = 0, mv1 = 0, mv2 = 0, mv3 = 0;
         int sc0 = TSO_LEN - 2, sc1 = TSO_LEN - 2, sc2 = R1_LEN, sc3 = R1_LEN;
-#pragma nounroll
-        for (int tw = ts - lead; tw < te; tw += 4, wp += wstep) {
-            uint32_t w = *wp;
-            if (!urev) w = __builtin_bswap32(w);
-            const uint32_t keep = low_bytes(te - tw) & ~low_bytes(ts - tw);
-            w = ((w ^ flip) & keep) | (0x4E4E4E4Eu & ~keep);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)w, 8 * k + 1, 1);      // 0 or ~0
-                const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)w, 8 * k + 2, 1);
-                const uint32_t mn = (uint32_t)__builtin_amdgcn_sbfe((int)w, 8 * k + 3, 1);      // 'N' alone among ACGTN
-                column<TSO_LEN>(m0, m1, mn, T0_P0, T0_P1, pv0, mv0, sc0);
-                column<TSO_LEN>(m0, m1, mn, T1_P0, T1_P1, pv1, mv1, sc1);
-                column<R1_LEN>(m0, m1, mn, R2_P0, R2_P1, pv2, mv2, sc2);
-                column<R1_LEN>(m0, m1, mn, R3_P0, R3_P1, pv3, mv3, sc3);
-                const int t = tw + k;
-                const int lo = min(min(sc0, sc1), min(sc2, sc3));
-                if (lo <= thr && (uint32_t)(t - t0) < (uint32_t)(te - t0)) {                   // rare
-                    const uint32_t j = (uint32_t)(ub - 1 - t);
-                    atomicMin(&s_cut[r], j);
-                    unsigned long long key = NO_KEY;
-                    if (sc0 <= thr) key = min(key, ((unsigned long long)(sc0 + 2) << 36) | ((unsigned long long)j << 2) | 0ull);
-                    if (sc1 <= thr) key = min(key, ((unsigned long long)(sc1 + 2) << 36) | ((unsigned long long)j << 2) | 1ull);
-                    if (sc2 <= thr) key = min(key, ((unsigned long long)sc2 << 36) | ((unsigned long long)j << 2) | 2ull);
-                    if (sc3 <= thr) key = min(key, ((unsigned long long)sc3 << 36) | ((unsigned long long)j << 2) | 3ull);
-                    atomicMin(&s_key[r], key);
-                }
+        // forwards in memory for a reverse-strand record, backwards for a forward one
+        scan_steps(s_addr[r], s_rev[r] != 0, t0 > WARM ? t0 - WARM : 0, te, [&](int t, uint32_t m0, uint32_t m1, uint32_t mn) {
+            column<TSO_LEN>(m0, m1, mn, T0_P0, T0_P1, pv0, mv0, sc0);
+            column<TSO_LEN>(m0, m1, mn, T1_P0, T1_P1, pv1, mv1, sc1);
+            column<R1_LEN>(m0, m1, mn, R2_P0, R2_P1, pv2, mv2, sc2);
+            column<R1_LEN>(m0, m1, mn, R3_P0, R3_P1, pv3, mv3, sc3);
+            const int lo = min(min(sc0, sc1), min(sc2, sc3));
+            if (lo <= thr && (uint32_t)(t - t0) < (uint32_t)(te - t0)) {                       // rare
+                const uint32_t j = (uint32_t)(ub - 1 - t);
+                atomicMin(&s_cut[r], j);
+                unsigned long long key = NO_KEY;
+                if (sc0 <= thr) key = min(key, ((unsigned long long)(sc0 + 2) << 36) | ((unsigned long long)j << 2) | 0ull);
+                if (sc1 <= thr) key = min(key, ((unsigned long long)(sc1 + 2) << 36) | ((unsigned long long)j << 2) | 1ull);
+                if (sc2 <= thr) key = min(key, ((unsigned long long)sc2 << 36) | ((unsigned long long)j << 2) | 2ull);
+                if (sc3 <= thr) key = min(key, ((unsigned long long)sc3 << 36) | ((unsigned long long)j << 2) | 3ull);
+                atomicMin(&s_key[r], key);
             }
-        }
+        });
     }
     __syncthreads();
     if (i < n) {

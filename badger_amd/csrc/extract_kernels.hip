@@ -1094,6 +1094,7 @@ constexpr int FW = ((R1_LEN - KMER) + (R1_LEN + 1) + (FSPREAD - 1) + 3) / 4;    
 template <int NW>
 __device__ __forceinline__ uint32_t myers_search(uint32_t (&w)[NW], int n, uint32_t comp)
 {
+    // (The recurrence is stated once more, for any row count, as column<M>() of adapter_scan.hpp.)
     // Only bit 21 of the vectors is ever read and carries only move upwards, so bits 22..31 are left to hold anything.
     // A column is 20 vector instructions (round 4; the compiler's form of the textbook statements was 29): the equality mask
     // comes from the two bit planes of R1's codes and the base's code bits spread over the word, with "matches nothing" - an

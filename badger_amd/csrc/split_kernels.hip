@@ -8,9 +8,9 @@
 //                comp(TSO[i]) and R1[m - 1 - i]): backwards over the bytes as they are they are kinds 1 and 2, forwards over
 //                the bytes with ASCII bit 2 flipped (the complement's code bits) they are kinds 0 and 3.
 //     split      a unit is the BDG_CHIMERA_SEGMENT columns [c0, c1) of a read in one direction; it reports the positions in
-//                [c0, c1) that the margins leave, from a fresh automaton started WARM steps early (exact: chimera_kernels.hip;
-//                the argument does not care for the direction).  A forward unit reports pos = t + 1 behind step t, so it runs
-//                the steps [c0 - 1, c1 - 1): every hit of a unit falls into the unit's own 8 cells.
+//                [c0, c1) that the margins leave, from a fresh automaton started WARM steps early (exact: adapter_scan.hpp,
+//                which also holds the column and describes the walk over a unit's words).  A forward unit reports pos = t + 1
+//                behind step t, so it runs the steps [c0 - 1, c1 - 1): every hit of a unit falls into the unit's own 8 cells.
 //     balance    the 64 reads' segment counts go through a prefix sum; in every round each lane takes the next unit.
 //     cells      a hit takes an LDS atomic minimum of D << 7 | (pos & 31) << 2 | kind on its cell's word.  The cells of a wave
 //                are numbered through its reads (8 per segment) and live in a ring of 1,024 words: a round scans 32 segments =
@@ -25,60 +25,23 @@
 //   the block scan of bdg_partition.hpp turns pcount into the pieces' places (three small launches).
 //   k_split_emit    a thread per read writes its first piece and off', a thread per staged boundary the piece it starts; the
 //                count always, nothing else when it exceeds cap.
-#include "bdg_common.hpp"
+#include "adapter_scan.hpp"
 #include "bdg_launchers.hpp"
 #include "bdg_partition.hpp"
 
 namespace {
 
-constexpr int SEG = BDG_CHIMERA_SEGMENT, MARGIN = BDG_SPLIT_MARGIN, CELL_SHIFT = 5, REACH = BDG_SPLIT_REACH;
+constexpr int MARGIN = BDG_SPLIT_MARGIN, CELL_SHIFT = 5, REACH = BDG_SPLIT_REACH;
 constexpr int CPS = SEG >> CELL_SHIFT;                        // cells per segment
 constexpr uint32_t ROUND_SEGS = 32, ROUND_CELLS = ROUND_SEGS * CPS, RING = 1024, EMPTY = 0xFFFFFFFFu;
-constexpr int TSO_LEN = 30, R1_LEN = 22;
-constexpr int WARM = TSO_LEN + BDG_CHIMERA_MAX_ED_MAX + 2;    // m + k of the longest pattern at its largest bound
-constexpr char TSO[TSO_LEN + 1] = BDG_TRIM_TSO_SEQ;
-constexpr char R1[R1_LEN + 1] = BDG_CHIMERA_R1_SEQ;
-static_assert(sizeof(BDG_TRIM_TSO_SEQ) == TSO_LEN + 1 && sizeof(BDG_CHIMERA_R1_SEQ) == R1_LEN + 1, "each pattern in one 32-bit word");
-static_assert((1 << CELL_SHIFT) == BDG_SPLIT_CELL && SEG % BDG_SPLIT_CELL == 0 && SEG % 4 == 0, "a segment is whole cells and whole words");
+static_assert((1 << CELL_SHIFT) == BDG_SPLIT_CELL && SEG % BDG_SPLIT_CELL == 0, "a segment is whole cells");
 static_assert(BDG_SPLIT_MAX_ED_MAX == BDG_CHIMERA_MAX_ED_MAX && BDG_SPLIT_MAX_ED_MAX + 2 < 16, "D in 4 bits of the cell word");
 static_assert(RING >= 2 * ROUND_CELLS + 4 * REACH && 64 * 4 == ROUND_CELLS && REACH == 2, "the ring holds a window and the round behind it; a lane selects 4 cells");
 static_assert(MARGIN >= BDG_SPLIT_CELL * REACH, "the first REACH cells of a read are empty: reads need no separator");
 
-// Bit i of a plane = ASCII bit `bit` of row i.  rc: row i = comp(p[i]) (flips ASCII bit 2 alone), otherwise p[m - 1 - i].
-constexpr uint32_t plane(const char* p, int m, int bit, bool rc)
-{
-    uint32_t w = 0;
-    for (int i = 0; i < m; ++i) {
-        const unsigned char c = (unsigned char)(rc ? p[i] ^ 4 : p[m - 1 - i]);
-        w |= (uint32_t)((c >> bit) & 1u) << i;
-    }
-    return w;
-}
+// the two automata: rows comp(TSO[i]) and R1[m - 1 - i]
 constexpr uint32_t A_P0 = plane(TSO, TSO_LEN, 1, true), A_P1 = plane(TSO, TSO_LEN, 2, true);
 constexpr uint32_t B_P0 = plane(R1, R1_LEN, 1, false),  B_P1 = plane(R1, R1_LEN, 2, false);
-
-// One column of Myers' search for a pattern of M rows: k_chimera_search's (k_strict_filter's) form.
-template <int M>
-__device__ __forceinline__ void column(uint32_t m0, uint32_t m1, uint32_t mn, uint32_t P0, uint32_t P1,
-                                       uint32_t& pv, uint32_t& mv, int& score)
-{
-    const uint32_t off = __builtin_amdgcn_bitop3_b32(m1, P1, mn, 0xBE);                // (m1 ^ P1) | mn
-    const uint32_t eq = __builtin_amdgcn_bitop3_b32(m0, P0, off, 0x41);                // ~((m0 ^ P0) | off)
-    const uint32_t xv = eq | mv;
-    const uint32_t xh = __builtin_amdgcn_bitop3_b32((eq & pv) + pv, pv, eq, 0xBE);     // (((eq & pv) + pv) ^ pv) | eq
-    const uint32_t ph = __builtin_amdgcn_bitop3_b32(mv, xh, pv, 0xF1);                 // mv | ~(xh | pv)
-    const uint32_t mh = pv & xh;
-    score += (int)((ph >> (M - 1)) & 1u);
-    score -= (int)((mh >> (M - 1)) & 1u);
-    const uint32_t ph1 = ph << 1, mh1 = mh << 1;
-    pv = __builtin_amdgcn_bitop3_b32(mh1, xv, ph1, 0xF1);                              // mh1 | ~(xv | ph1)
-    mv = ph1 & xv;
-}
-
-__device__ __forceinline__ uint32_t low_bytes(int k)
-{
-    return k >= 4 ? 0xFFFFFFFFu : (k <= 0 ? 0u : (1u << (8 * k)) - 1u);
-}
 
 // a cell word under the order (D, pos, kind) among cells `rel` apart
 __device__ __forceinline__ uint32_t full_key(uint32_t w, uint32_t rel) { return (w >> 7) << 20 | rel << 7 | (w & 127u); }
@@ -112,19 +75,12 @@ void k_split_scan(const uint8_t* __restrict__ bases, const uint64_t* __restrict_
     const uint32_t rounds = (segs + ROUND_SEGS - 1u) / ROUND_SEGS;
     const int thr = max_ed;                          // the TSO's scores are kept 2 lower: one bound for both
 
-    auto read_of = [&](uint32_t seg) {               // the first read whose inclusive sum lies above seg
-        int r = 0;
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1) if (s_incl[r + s - 1] <= seg) r += s;
-        return r;
-    };
-
     for (uint32_t round = 0; segs && round <= rounds; ++round) {
         const uint32_t u = round * 64u + (uint32_t)lane;
         if (round < rounds && u < units) {
             const uint32_t ws = u >> 1;
             const bool fwd = (u & 1u) != 0;
-            const int r = read_of(ws);
+            const int r = read_above(s_incl, ws);
             const uint32_t before = r ? s_incl[r - 1] : 0u;
             const int L = s_len[r];
             const int c0 = (int)((ws - before) * (uint32_t)SEG), c1 = L - c0 > SEG ? c0 + SEG : L;
@@ -134,7 +90,8 @@ void k_split_scan(const uint8_t* __restrict__ bases, const uint64_t* __restrict_
                 const uint64_t a0 = fwd ? s_addr[r] : s_addr[r] + (uint64_t)(L - 1);
                 const int t0 = fwd ? lo - 1 : L - hi, te = fwd ? hi - 1 : L - lo;
                 const int ts = t0 > WARM ? t0 - WARM : 0;
-                // words in scan order: forwards in memory with the complement's bits, or backwards (bytes swapped)
+                // the twin of adapter_scan.hpp's scan_steps(a0, fwd, ts, te, ..), kept in place: through the shared form this kernel
+                // measured 1 % slower (profiles/r25_adapter_scan.jsonl).  A change to either is a change to both.
                 const uint64_t as = fwd ? a0 + (uint64_t)ts : a0 - (uint64_t)ts;
                 const int lead = fwd ? (int)(as & 3u) : 3 - (int)(as & 3u);
                 const uint32_t* wp = reinterpret_cast<const uint32_t*>(as & ~(uint64_t)3);
@@ -180,7 +137,7 @@ void k_split_scan(const uint8_t* __restrict__ bases, const uint64_t* __restrict_
             if (c < 0 || c >= (int64_t)cells) continue;
             const uint32_t w = s_ring[(uint32_t)c & (RING - 1u)];
             if (w == EMPTY) continue;
-            const int r = read_of((uint32_t)c / (uint32_t)CPS);
+            const int r = read_above(s_incl, (uint32_t)c / (uint32_t)CPS);
             const int64_t first = (int64_t)(r ? s_incl[r - 1] : 0u) * CPS, last = (int64_t)s_incl[r] * CPS - 1;
             const uint32_t mine = full_key(w, REACH);
             bool wins = true;

@@ -105,6 +105,38 @@ def test_chimera_batch_dev_behind_extraction_and_trim():
     ctx.close()
 
 
+def test_every_byte_alignment_of_a_unit():
+    """the walk over a unit's words masks other bytes at every address mod 4 of the unit's first byte: the boundary cases (an
+    exact occurrence at every scan step from -(m + k) to +1 around a segment border, both strands) behind one more read of
+    0 .. 3 bases that takes no part, against the one-read rule"""
+    S = cc.case_set()
+    idx = [i for i, label in enumerate(S["labels"]) if label[0] == "boundary"]
+    assert 200 < len(idx) < 600
+    reads, recs, tr = [S["reads"][i] for i in idx], S["recs"][idx], S["trim"][idx]
+    kinds = np.array([S["labels"][i][1] for i in idx])
+    seen = {}
+
+    def distances(pat, text):                                          # (the rule's scan once for both bounds)
+        if (pat, text) not in seen:
+            seen[pat, text] = chimera.start_distances(pat, text)
+        return seen[pat, text]
+
+    want = {e: chimera.chimera_reads(reads, recs, tr, e, distances) for e in (E, 6)}
+    ctx = _native.Context(0)
+    for shift in range(4):
+        bases, off = synth.list_to_reads(["ACG"[:shift]] + reads)
+        assert int(off[1]) == shift
+        r = np.concatenate([np.zeros(1, recs.dtype), recs])
+        t = np.concatenate([np.zeros(1, tr.dtype), tr])                # (no TRIM_EMIT: the leading read is not searched)
+        for e in (E, 6):
+            w = np.concatenate([np.array([chimera.NONE], dtype=chimera.CHIMERA_DTYPE), want[e]])
+            planted = tr["cdna_start"] + 60                            # (the column of the occurrence's first base: chimera_cases)
+            assert (w["flags"][1:] == chimera.CHIMERA_HIT).all() and (w["hit_ed"][1:] == 0).all()
+            assert (w["hit_pos"][1:] == planted).all() and (w["hit_kind"][1:] == kinds).all() and (w["cut"][1:] <= planted).all()
+            _same(ctx.chimera_batch(bases, off, r, t, e), w, "shift %d max_ed %d" % (shift, e))
+    ctx.close()
+
+
 # ---- 2. the pipelined path ----------------------------------------------------------------------------------------------
 def _pipeline(ctx, bases, off, n, step, umi_len):
     recs, trims, chims, flying = [], [], [], []

@@ -115,6 +115,29 @@ def test_marks_on_either_side_of_a_segment_border(ctx):
     assert len(starts) >= len(reads) and set(range(250, 263)) | set(range(506, 519)) <= set(starts)
 
 
+def test_every_byte_alignment_of_a_unit(ctx):
+    """the walk over a unit's words masks other bytes at every address mod 4 of the unit's first byte: the reads of the test
+    above behind one more read of 0 .. 3 bases (shorter than 2 * MARGIN: no hit, one piece), against the one-read rule"""
+    rng = np.random.default_rng(4)
+    reads, marks = [], []                                               # marks: the (D, pos, kind) planted in each read
+    for pos in list(range(250, 263)) + list(range(506, 519)):
+        reads.append(cc.clean(rng, pos) + cc.mutate(rng, chimera.R1, 1, "sub") + cc.clean(rng, 700 - pos))
+        reads.append(cc.clean(rng, pos - 22) + cc.mutate(rng, chimera.PATTERNS[3], 1, "sub") + cc.clean(rng, 700 - pos))
+        reads.append(cc.clean(rng, pos) + chimera.PATTERNS[1] + cc.clean(rng, 700 - pos))
+        reads.append(cc.clean(rng, pos - 30) + chimera.TSO + cc.clean(rng, 700 - pos) + chimera.R1 + cc.clean(rng, 90))
+        marks += [[(1, pos, 2)], [(1, pos, 3)], [(0, pos, 1)], [(0, pos, 0), (0, 700, 2)]]
+    for s, planted in zip(reads, marks):
+        assert set(planted) <= set(cs.read_hits(s, 1)), planted
+    for e in (1, 6):
+        off0, rows0 = cs.split_reads(reads, e)
+        assert len(rows0) >= 2 * len(reads)
+        for shift in range(4):
+            rows = np.concatenate([np.zeros(1, cs.SPLIT_DTYPE), rows0])
+            rows["read"][1:] += 1
+            want = np.concatenate([np.zeros(1, np.uint64), off0 + np.uint64(shift)]), rows
+            _same(ctx.split_batch(*synth.list_to_reads(["ACG"[:shift]] + reads), e), want, ("shift", shift, e))
+
+
 @pytest.mark.parametrize("max_ed", EDS)
 def test_random_reads_equal_the_rule(ctx, max_ed):
     R = _random_set()
