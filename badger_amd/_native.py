@@ -49,6 +49,8 @@ CONS_BAND_DEFAULT, CONS_BAND_MAX = 64, 256
 CONS_ACCEPTED, CONS_REJ_DIST, CONS_REJ_BAND, CONS_REJ_LEN, CONS_BACKBONE = 1, 2, 4, 8, 16
 # bdg_gene_rec: the gene call of a read by k-mer lookup (bdg_genes_assign; the rule in badger_amd/genes.py)
 GENE_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), ("n_keys", "<u4"), ("n_found", "<u4"), ("flags", "<u4")])
+# bdg_gene_group_rec: a (cell, feature) group of bdg_umi_dedup_genes (the rule in badger_amd/umi_dedup.py dedup_per_gene)
+GENE_GROUP_DTYPE = np.dtype([("feature", "<u4"), ("cell", "<u4"), ("molecules", "<u4"), ("umis", "<u4"), ("umi_reads", "<u4"), ("own", "<u4")])
 GENES_K_MIN, GENES_K_MAX, GENES_K_DEFAULT, GENES_MIN_HITS_DEFAULT, GENES_MAX_FEATURES = 11, 31, 21, 3, 256
 GENES_AMBIGUOUS, GENES_NONE = 0xFFFFFFFE, 0xFFFFFFFF
 GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
@@ -99,7 +101,13 @@ EXPORTS = [
     "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
     "bdg_genes_index_build_iso", "bdg_iso_assign", "bdg_iso_assign_dev",
     "bdg_em_tcc", "bdg_em_tcc_dev",
+    "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate",
 ]
+
+
+def sort_gene_groups(groups):
+    """group records in the order the binding returns them: by cell, then feature"""
+    return groups[np.lexsort((groups["feature"], groups["cell"]))]
 
 
 class KernelTime(C.Structure):
@@ -374,6 +382,9 @@ def load():
     L.bdg_em_tcc.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
     L.bdg_em_tcc_dev.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
     L.bdg_consensus_set_band.argtypes = [vp, u32]
+    L.bdg_umi_dedup_genes.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, u32, vp]
+    L.bdg_umi_dedup_genes_dev.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, u32, vp]
+    L.bdg_umi_dedup_genes_set_aggregate.argtypes = [vp, C.c_int]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -662,6 +673,32 @@ class Context:
         umis, molecules]"""
         self._check(self.lib.bdg_umi_dedup_dev(self.h, _ptr(d_rank), _ptr(d_has), _ptr(d_umi), n, _ptr(d_cells), n_cells,
                                                umi_len, umi_dist, _ptr(d_molecule), _ptr(d_cell_counts)))
+
+    def umi_dedup_genes(self, cell, gene_recs, umi, umi_len, umi_dist=1, cap=None):
+        """molecules per (cell, feature) over host arrays (bdg_umi_dedup_genes): cell uint32 [n] ordinals (0xFFFFFFFF: none),
+        gene_recs GENE_DTYPE [n], umi uint32 [n] packed codes; cap: room for group records (default n, which always suffices)
+        -> (molecule uint32 [n], groups GENE_GROUP_DTYPE sorted by (cell, feature))"""
+        cell = np.ascontiguousarray(cell, dtype=np.uint32)
+        gene_recs = np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
+        umi = np.ascontiguousarray(umi, dtype=np.uint32)
+        n = len(cell)
+        if len(gene_recs) != n or len(umi) != n:
+            raise ValueError("a cell, a gene record and a UMI code per read")
+        cap = n if cap is None else int(cap)
+        mol, groups, count = np.zeros(n, dtype=np.uint32), np.zeros(cap, dtype=GENE_GROUP_DTYPE), np.zeros(1, dtype=np.uint32)
+        self._check(self.lib.bdg_umi_dedup_genes(self.h, cell.ctypes.data, gene_recs.ctypes.data, umi.ctypes.data, n, int(umi_len),
+                                                 int(umi_dist), mol.ctypes.data, groups.ctypes.data, cap, count.ctypes.data))
+        return mol, sort_gene_groups(groups[:int(count[0])])
+
+    def umi_dedup_genes_dev(self, d_cell, d_gene_recs, d_umi, n, umi_len, umi_dist, d_molecule, d_groups, cap, d_n_groups):
+        """bdg_umi_dedup_genes_dev: the same over device arrays; the records come in no particular order (sort_gene_groups);
+        waits for the stream once, for the number of groups"""
+        self._check(self.lib.bdg_umi_dedup_genes_dev(self.h, _ptr(d_cell), _ptr(d_gene_recs), _ptr(d_umi), int(n), int(umi_len),
+                                                     int(umi_dist), _ptr(d_molecule), _ptr(d_groups), int(cap), _ptr(d_n_groups)))
+
+    def umi_dedup_genes_set_aggregate(self, on=True):
+        """for measurements and tests: False makes every lane of umi_dedup_genes probe and count for itself"""
+        self._check(self.lib.bdg_umi_dedup_genes_set_aggregate(self.h, 1 if on else 0))
 
     def consensus(self, bases, seq_off, grp_off, anchor, max_ed_pct=20):
         """per-group consensus over host arrays (bdg_consensus): bases uint8, seq_off uint64 [n_seqs + 1], grp_off uint64

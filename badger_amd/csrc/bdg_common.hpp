@@ -134,7 +134,10 @@ struct bdg_ctx {
     struct Kept { bool on = false; DevBuf b; uint64_t n = 0; } kept_recs, kept_umis, kept_cdna;
     DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read;
                          // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
+                         // bdg_umi_dedup_genes_dev's: group keys u64 | UMI keys u64 | group counts u32 [4] | counts u32 | parents u32
+                         // per slot, read slots u32 per read
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
+    bool gene_aggregate = true;              // bdg_umi_dedup_genes_set_aggregate
     // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call
     // ---- chimera split (split_kernels.hip): grow-only, reused by every call
     DevBuf sp_ws;        // counter | staged boundaries, 16 bytes each | piece count u32 per read | the scan's block sums

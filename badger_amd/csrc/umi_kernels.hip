@@ -15,6 +15,10 @@
 //   root     k_umi_root: every pair follows its parents to the root (rank rises strictly along the way).
 //   results  k_umi_reads: per read the root's code; k_umi_insert and k_umi_cells count reads, reads with a UMI, distinct
 //            UMIs and molecules per cell, summed inside the wave before the atomic (one hot cell is one address).
+//
+// Further down: one representative read per molecule (bdg_molecule_reps_dev), and molecules per cell and gene
+// (bdg_umi_dedup_genes_dev, DESIGN §4.22: a group table over (cell, feature) in front of the table above, whose kernels from
+// k_umi_parent on then run unchanged with the group's id in the cell ordinal's place).
 #include "bdg_common.hpp"
 
 namespace {
@@ -324,6 +328,113 @@ void k_mol_reads(const uint32_t* __restrict__ read_slot, const uint32_t* __restr
     rep[i] = r;
 }
 
+// ---- molecules per cell and gene (bdg_umi_dedup_genes_dev; the rule in include/badger_hip.h, its checker umi_dedup.dedup_per_gene,
+// DESIGN §4.22) ----
+//   A (cell, feature, UMI) key has 96 bits and a compare-and-swap takes 64, so the key goes in two levels:
+//   groups   k_umi_insert_genes: per read that takes part, the key cell << 32 | feature finds or claims a slot of the group table; the
+//            slot index (below 2^31) is the group's id.  A housekeeping gene in one cell is one address (§4.0): the probe loads
+//            before it swaps - a key already stored costs a load and no atomic - and the lanes of a wave that name one group
+//            elect a leader (the peers of wave_count), who alone probes and hands the id to the others.
+//   UMIs     the same kernel then puts group id << 32 | code into k_umi_insert's table (look first here too).  From there on
+//            k_umi_parent, k_umi_root, k_umi_cells and k_umi_reads run as they are, "cell ordinal" read as "group id"; the counts
+//            [slots][4] per group are: own-molecule reads, reads with a usable UMI, distinct UMIs, roots.
+//   records  k_group_emit: the occupied group slots, compacted: one add to the cursor per wave (ballots and popcounts over its 16
+//            runs of 64 slots), a record per lane and run.
+__device__ __forceinline__ uint32_t find_or_claim(unsigned long long* keys, unsigned long long k, uint32_t mask)
+{
+    for (uint32_t h = slot_of(k, mask);; h = (h + 1u) & mask) {           // (never full: twice as many slots as reads)
+        // a slot goes from EMPTY to its key once and stays: a key read here is final, a stale EMPTY is settled by the swap
+        unsigned long long e = __atomic_load_n(&keys[h], __ATOMIC_RELAXED);
+        if (e == EMPTY) { e = atomicCAS(&keys[h], EMPTY, k); if (e == EMPTY) return h; }
+        if (e == k) return h;
+    }
+}
+
+template <bool AGGREGATE>
+__global__ __launch_bounds__(256)
+void k_umi_insert_genes(const uint32_t* __restrict__ cell, const bdg_gene_rec* __restrict__ recs, const uint32_t* __restrict__ umi,
+                        uint64_t n, uint32_t lo_len, uint32_t hi_len, unsigned long long* gkeys, uint32_t* __restrict__ gcounts,
+                        unsigned long long* keys, uint32_t* __restrict__ cnt, uint32_t mask, uint32_t* __restrict__ read_slot)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256ull + threadIdx.x;      // (every lane stays for the wave's groups and counts)
+    unsigned long long gk = EMPTY;
+    uint32_t code = UMI_NONE;
+    if (i < n) {
+        const uint32_t c = cell[i];
+        if (c != UMI_NONE && (recs[i].flags & BDG_GENE_ASSIGNED)) {
+            gk = (unsigned long long)c << 32 | recs[i].feature;
+            const uint32_t u = umi[i], len = u >> 28;
+            if (u != UMI_NONE && len >= lo_len && len <= hi_len) code = u;
+        }
+    }
+    uint32_t gid = UMI_NONE;
+    if (!AGGREGATE) {
+        if (gk != EMPTY) gid = find_or_claim(gkeys, gk, mask);
+    } else {
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t my_leader = lane;
+        unsigned long long todo = __ballot(gk != EMPTY);
+        while (todo) {
+            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+            const unsigned long long lk = __shfl(gk, (int)leader);
+            const bool mine = gk == lk;                                   // (EMPTY is no key: a lane outside todo never matches)
+            if (mine) my_leader = leader;
+            todo &= ~__ballot(mine);
+        }
+        if (gk != EMPTY && my_leader == lane) gid = find_or_claim(gkeys, gk, mask);   // the leaders of all groups probe side by side
+        gid = __shfl(gid, (int)my_leader);
+    }
+    uint32_t slot = UMI_NONE;
+    if (gid != UMI_NONE && code != UMI_NONE) {
+        slot = find_or_claim(keys, (unsigned long long)gid << 32 | code, mask);
+        atomicAdd(&cnt[slot], 1u);
+    }
+    if (i < n) read_slot[i] = slot;
+    const uint32_t own = slot == UMI_NONE ? gid : UMI_NONE, with_umi = slot != UMI_NONE ? gid : UMI_NONE;
+    if (AGGREGATE) {
+        wave_count(gcounts, own, 0u);
+        wave_count(gcounts, with_umi, 1u);
+    } else {
+        if (own != UMI_NONE) atomicAdd(&gcounts[(size_t)own * 4u], 1u);
+        if (with_umi != UMI_NONE) atomicAdd(&gcounts[(size_t)with_umi * 4u + 1u], 1u);
+    }
+}
+
+constexpr uint32_t EMIT_CHUNKS = 16;                                      // runs of 64 slots a wave of k_group_emit compacts behind one atomic
+
+__global__ __launch_bounds__(256)
+void k_group_emit(const unsigned long long* __restrict__ gkeys, const uint32_t* __restrict__ gcounts, uint32_t P,
+                  bdg_gene_group_rec* __restrict__ out, uint32_t cap, uint32_t* __restrict__ n_out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t first = ((uint64_t)blockIdx.x * 4ull + (threadIdx.x >> 6)) * (64ull * EMIT_CHUNKS);   // (the wave's first slot)
+    unsigned long long k[EMIT_CHUNKS];
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < EMIT_CHUNKS; ++c) {
+        const uint64_t s = first + 64ull * c + lane;
+        k[c] = s < P ? gkeys[s] : EMPTY;
+        total += (uint32_t)__popcll(__ballot(k[c] != EMPTY));
+    }
+    if (!total) return;                                                   // (the whole wave)
+    // the cursor is one address (§4.0): a wave asks once for all its records - a call of n reads issues n / 512 adds at most
+    uint32_t base = 0;
+    if (lane == 0u) base = atomicAdd(n_out, total);
+    base = __shfl(base, 0);
+#pragma unroll
+    for (uint32_t c = 0; c < EMIT_CHUNKS; ++c) {
+        const unsigned long long live = __ballot(k[c] != EMPTY);
+        const uint64_t at = (uint64_t)base + (uint32_t)__popcll(live & ((1ull << lane) - 1ull));
+        base += (uint32_t)__popcll(live);
+        if (k[c] == EMPTY || at >= cap) continue;                         // (past cap: counted, not written - the caller is told the number)
+        const uint32_t* g = gcounts + (size_t)(first + 64ull * c + lane) * 4u;
+        bdg_gene_group_rec r;
+        r.feature = (uint32_t)k[c]; r.cell = (uint32_t)(k[c] >> 32);
+        r.own = g[0]; r.umi_reads = g[1]; r.umis = g[2]; r.molecules = g[3] + g[0];
+        out[at] = r;
+    }
+}
+
 }  // namespace
 
 int bdg_cdna_len_launch(bdg_ctx* ctx, const bdg_trim_rec* d_trim, const bdg_chimera_rec* d_chim, uint32_t n, uint32_t* d_out)
@@ -414,5 +525,132 @@ int bdg_umi_dedup_launch(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_
         hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, read_slot, n, keys, cnt, d_mol);
     }
     BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+// ---- bdg_umi_dedup_genes_dev and its host twin ----
+static int umi_genes_check(bdg_ctx* ctx, uint64_t n, uint32_t umi_len, uint32_t umi_dist)
+{
+    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
+    if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
+    if (n > (1ull << 30)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the group and UMI tables take (2^30)");
+    return BDG_OK;
+}
+
+// the kernels, and *d_n_groups; asynchronous
+static int umi_genes_launch(bdg_ctx* ctx, const uint32_t* d_cell, const bdg_gene_rec* d_recs, const uint32_t* d_umi, uint64_t n,
+                            uint32_t umi_len, uint32_t umi_dist, uint32_t* d_mol, bdg_gene_group_rec* d_groups, uint32_t cap,
+                            uint32_t* d_n_groups)
+{
+    hipStream_t st = ctx->stream;
+    BDG_HIP_TRY(ctx, hipMemsetAsync(d_n_groups, 0, sizeof(uint32_t), st));
+    if (n == 0) return BDG_OK;
+    uint64_t P = 1024;                                                    // both tables: two slots per read, a power of two
+    while (P < 2 * n) P <<= 1;
+    // workspace: group keys u64 [P] | UMI keys u64 [P] | group counts u32 [P][4] | counts u32 [P] (then the roots) | parents u32 [P]
+    // | read slots u32 [n]
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->u_ws, 40 * (size_t)P + 4 * (size_t)n + 256))) return rc;
+    auto* gkeys = static_cast<unsigned long long*>(ctx->u_ws.p);
+    auto* keys = gkeys + P;
+    auto* gcounts = reinterpret_cast<uint32_t*>(keys + P);
+    auto* cnt = gcounts + 4 * P;
+    auto* par = cnt + P;
+    auto* read_slot = par + P;
+    const uint32_t lo_len = umi_len > 3u ? umi_len - 2u : 1u, hi_len = umi_len + 2u < MAX_LEN ? umi_len + 2u : MAX_LEN;
+    const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_insert_genes");
+        BDG_HIP_TRY(ctx, hipMemsetAsync(gkeys, 0xFF, 8 * (size_t)P, st));           // (EMPTY)
+        BDG_HIP_TRY(ctx, hipMemsetAsync(gcounts, 0, 16 * (size_t)P, st));
+        hipLaunchKernelGGL(k_umi_clear, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P);
+        if (ctx->gene_aggregate)
+            hipLaunchKernelGGL(k_umi_insert_genes<true>, dim3(gn), dim3(256), 0, st, d_cell, d_recs, d_umi, n, lo_len, hi_len, gkeys, gcounts,
+                               keys, cnt, mask, read_slot);
+        else
+            hipLaunchKernelGGL(k_umi_insert_genes<false>, dim3(gn), dim3(256), 0, st, d_cell, d_recs, d_umi, n, lo_len, hi_len, gkeys, gcounts,
+                               keys, cnt, mask, read_slot);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_parent");
+        hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, mask, lo_len, hi_len, umi_dist, par);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_results");
+        hipLaunchKernelGGL(k_umi_root, dim3(gp), dim3(256), 0, st, keys, par, (uint32_t)P, cnt);
+        hipLaunchKernelGGL(k_umi_cells, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, gcounts);
+        hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, read_slot, n, keys, cnt, d_mol);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_group_emit");
+        hipLaunchKernelGGL(k_group_emit, dim3((uint32_t)((P + 256ull * EMIT_CHUNKS - 1) / (256ull * EMIT_CHUNKS))), dim3(256), 0, st, gkeys, gcounts,
+                           (uint32_t)P, d_groups, cap, d_n_groups);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+static int umi_genes_cap_error(bdg_ctx* ctx, uint32_t need, uint32_t cap)
+{
+    return bdg_fail(ctx, BDG_E_ARG, "cap too small: " + std::to_string(need) + " groups, room for " + std::to_string(cap));
+}
+
+int bdg_umi_dedup_genes_dev(bdg_ctx* ctx, const uint32_t* d_cell, const bdg_gene_rec* d_gene_recs, const uint32_t* d_umi, uint64_t n,
+                            uint32_t umi_len, uint32_t umi_dist, uint32_t* d_molecule, bdg_gene_group_rec* d_groups, uint32_t cap,
+                            uint32_t* d_n_groups)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (!d_n_groups || (cap && !d_groups)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n && (!d_cell || !d_gene_recs || !d_umi || !d_molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = umi_genes_check(ctx, n, umi_len, umi_dist)) return rc;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = umi_genes_launch(ctx, d_cell, d_gene_recs, d_umi, n, umi_len, umi_dist, d_molecule, d_groups, cap, d_n_groups)) return rc;
+    uint32_t need = 0;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(&need, d_n_groups, sizeof(need), hipMemcpyDeviceToHost, ctx->stream));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return need > cap ? umi_genes_cap_error(ctx, need, cap) : BDG_OK;
+}
+
+int bdg_umi_dedup_genes(bdg_ctx* ctx, const uint32_t* cell, const bdg_gene_rec* gene_recs, const uint32_t* umi, uint64_t n,
+                        uint32_t umi_len, uint32_t umi_dist, uint32_t* molecule, bdg_gene_group_rec* groups, uint32_t cap,
+                        uint32_t* n_groups)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (!n_groups || (cap && !groups)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n && (!cell || !gene_recs || !umi || !molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = umi_genes_check(ctx, n, umi_len, umi_dist)) return rc;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // staging: cells u32 [n] | UMIs u32 [n];  gene records [n];  group count u32 (in 8 bytes) | group records [cap] | molecules u32 [n]
+    const size_t w_b = sizeof(uint32_t) * (size_t)n, rec_b = sizeof(bdg_gene_rec) * (size_t)n, grp_b = sizeof(bdg_gene_group_rec) * (size_t)cap;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, 2 * w_b + 8))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, rec_b + 8))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, 8 + grp_b + w_b))) return rc;
+    auto* d_cell = static_cast<uint32_t*>(ctx->s_in0.p);
+    auto* d_umi = d_cell + n;
+    auto* d_recs = static_cast<bdg_gene_rec*>(ctx->s_in1.p);
+    auto* d_n = static_cast<uint32_t*>(ctx->s_out0.p);
+    auto* d_groups = reinterpret_cast<bdg_gene_group_rec*>(d_n + 2);
+    auto* d_mol = reinterpret_cast<uint32_t*>(d_groups + cap);
+    if (n) {
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_cell, cell, w_b, hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_umi, umi, w_b, hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_recs, gene_recs, rec_b, hipMemcpyHostToDevice, st));
+    }
+    if ((rc = umi_genes_launch(ctx, d_cell, d_recs, d_umi, n, umi_len, umi_dist, d_mol, d_groups, cap, d_n))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(n_groups, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (*n_groups > cap) return umi_genes_cap_error(ctx, *n_groups, cap);
+    if (n) BDG_HIP_TRY(ctx, hipMemcpyAsync(molecule, d_mol, w_b, hipMemcpyDeviceToHost, st));
+    if (*n_groups) BDG_HIP_TRY(ctx, hipMemcpyAsync(groups, d_groups, sizeof(bdg_gene_group_rec) * (size_t)*n_groups, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
+
+int bdg_umi_dedup_genes_set_aggregate(bdg_ctx* ctx, int on)
+{
+    if (!ctx) return BDG_E_ARG;
+    ctx->gene_aggregate = on != 0;
     return BDG_OK;
 }

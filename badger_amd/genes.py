@@ -4,6 +4,7 @@ that every read and molecule is compatible with.
 
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
+                               [--umi_per_gene --umi_len L [--gene_umi_dist 0|1]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -26,6 +27,17 @@ The rule.  Any byte other than ACGT behaves as N; codes A 0, C 1, G 2, T 3.
               without UB is a molecule of its own.  A molecule's feature is the one named by strictly more of its ASSIGNED
               reads than any other; a tie, or no assigned read, leaves it uncounted.
     matrix    entry (feature, CB) = the molecules of that cell counted for that feature.
+
+With --umi_per_gene the molecules are made per cell and gene instead (include/badger_hip.h at bdg_umi_dedup_genes_dev; the
+checker is umi_dedup.dedup_per_gene and count_molecules_per_gene below), and UB is not looked at.
+    part      a read takes part when it has a CB and its gene record is ASSIGNED; its group is (CB, feature).
+    molecule  its UMI is the UR text of its header, usable under umi_dedup.usable(UMI, umi_len).  Inside one group the rule is
+              umi_dedup.cell_molecules as written; a molecule is (CB, feature, root UMI).  A read that takes part without a
+              usable UMI is a molecule of its own; a read that is not ASSIGNED is in no molecule.
+    matrix    entry (feature, CB) = the group's roots plus its own-molecule reads.  With --isoforms a molecule's class is the
+              AND of the compat sets of its reads: all of them are ASSIGNED to its feature by construction.
+    files     gene_molecules.tsv: read, CB, feature, UR, molecule (the root UMI's text, '*' for a molecule of its own) per read
+              that takes part.  features.tsv, barcodes.tsv, reads.tsv and read_isoforms.tsv are the same bytes as without.
 
 The isoform rule, on top of it (include/badger_hip.h at bdg_genes_index_build_iso).  Integers, sums, ORs and maxima only.
     local     local[q] of transcript q: its order of first appearance in the transcript file among the transcripts of its
@@ -87,6 +99,7 @@ EM_N_MAX = 1 << 24                   # a problem's counts must sum to less: a co
 EM_FILES = ("isoform_em_matrix.mtx", "isoform_em_pool.tsv")
 EM_BATCH_CLASSES = 4 << 20          # classes per device call at most
 HASH_MUL = np.uint64(0x9E3779B97F4A7C15)
+GENE_UMI_DIST_DEFAULT = 1
 BATCH_BASES = 256 << 20             # bases per device call at most
 _CODE = np.full(256, 4, dtype=np.uint8)
 for _i, _c in enumerate(b"ACGT"):
@@ -431,6 +444,105 @@ def count_molecules(cb, ub, recs, iso=None):
     return [c for c in cells.tolist()], entries, counts, np.stack([mol_feat[m], mol_cell[m], cls.view(np.int64)], axis=1)
 
 
+def _read_counts(recs, n):
+    flags = recs["flags"]
+    return dict(reads=n, assigned=int(((flags & ASSIGNED) != 0).sum()), tie=int(((flags & TIE) != 0).sum()),
+                low=int(((flags & LOW) != 0).sum()), crowded=int(((flags & CROWDED) != 0).sum()))
+
+
+def _ur_texts(heads):
+    """the UR text of every header of a tagged file (bytes, or None without the tag)"""
+    from .consensus import _tag
+    return [_tag(h.split(b"\t")[1:], b"UR:Z:") for h in heads]
+
+
+def count_molecules_per_gene(cb, ur, recs, umi_len, umi_dist=1, iso=None):
+    """the checker of --umi_per_gene.  cb, ur: per read bytes (ur None: no tag), recs REC_DTYPE [n] -> what count_molecules
+    returns: (cells sorted, {(feature, cell index): molecules}, counts dict) and with iso (ISO_DTYPE [n]) per molecule
+    (feature, cell index, the AND of the compat sets of its reads), int64 [molecules, 3] sorted by row.  counts also holds
+    groups, own (own-molecule reads) and no_part (reads in no molecule), and rows: per read None or the molecule text of
+    gene_molecules.tsv"""
+    from .umi_dedup import dedup_per_gene
+    n = len(cb)
+    cells = sorted(set(cb))
+    index = {c: i for i, c in enumerate(cells)}
+    feats = [int(f) if int(fl) & ASSIGNED else None for f, fl in zip(recs["feature"].tolist(), recs["flags"].tolist())]
+    rows, stats = dedup_per_gene(list(cb), feats, [None if u is None else u.decode("latin-1") for u in ur], umi_len, umi_dist)
+    entries = {(f, index[c]): s[0] for (c, f), s in stats.items()}
+    counts = _read_counts(recs, n)
+    total = sum(entries.values())
+    counts.update(molecules=total, counted=total, tied=0, groups=len(stats), own=sum(s[3] for s in stats.values()),
+                  no_part=sum(1 for r in rows if r is None), rows=rows)
+    if iso is None:
+        return cells, entries, counts
+    classes = {}
+    for i, (c, f, r) in enumerate(zip(cb, feats, rows)):
+        if r is None:
+            continue
+        key = (f, index[c], r if r != "*" else i)
+        classes[key] = classes.get(key, 0xFFFFFFFFFFFFFFFF) & int(iso["compat"][i])
+    mol = sorted((f, c, v) for (f, c, _), v in classes.items())
+    return cells, entries, counts, np.array(mol, dtype=np.uint64).astype(np.int64).reshape(-1, 3)
+
+
+def checker_dedup_genes(cell, gene_recs, umi, umi_len, umi_dist=1):
+    """dedup_per_gene with the call of Context.umi_dedup_genes: arrays in, (molecule uint32 [n], group records sorted by
+    (cell, feature)) out.  Not on the product path."""
+    from . import _native
+    from .umi_dedup import NONE as NO_UMI, dedup_per_gene, umi_code, umi_str
+    cell, umi = np.asarray(cell, dtype=np.uint32), np.asarray(umi, dtype=np.uint32)
+    feats = [int(f) if int(fl) & ASSIGNED else None for f, fl in zip(gene_recs["feature"].tolist(), gene_recs["flags"].tolist())]
+    rows, stats = dedup_per_gene([None if c == NONE else c for c in cell.tolist()], feats,
+                                 [None if u == NO_UMI else umi_str(u) for u in umi.tolist()], umi_len, umi_dist)
+    mol = np.array([NO_UMI if r is None or r == "*" else umi_code(r) for r in rows], dtype=np.uint32).reshape(len(cell))
+    groups = np.zeros(len(stats), dtype=_native.GENE_GROUP_DTYPE)
+    for g, ((c, f), s) in zip(groups, sorted(stats.items())):
+        g["cell"], g["feature"], g["molecules"], g["umis"], g["umi_reads"], g["own"] = c, f, s[0], s[1], s[2], s[3]
+    return mol, groups
+
+
+def molecules_per_gene(cb, ur, recs, run, umi_len, umi_dist=1, iso=None):
+    """the product side of --umi_per_gene: run(cell, gene_recs, umi, umi_len, umi_dist) -> (molecule codes, group records) is
+    Context.umi_dedup_genes (or checker_dedup_genes).  The matrix comes from the group records; the per-molecule list for the
+    isoform and EM files from grouping the reads by (cell, feature, molecule code), the AND on the host
+    -> what count_molecules_per_gene returns"""
+    from .umi_dedup import NONE as NO_UMI, umi_codes, umi_str
+    n = len(cb)
+    cells, cell_of = np.unique(np.array(cb, dtype=bytes) if n else np.zeros(0, "S1"), return_inverse=True)
+    mol, groups = run(cell_of.astype(np.uint32), recs, umi_codes(ur), umi_len, umi_dist)
+    entries = {(f, c): m for f, c, m in zip(groups["feature"].tolist(), groups["cell"].tolist(), groups["molecules"].tolist())}
+    part = (recs["flags"] & ASSIGNED) != 0
+    text = {c: umi_str(c) for c in np.unique(mol[part & (mol != NO_UMI)]).tolist()}
+    rows = [None if not p else "*" if m == NO_UMI else text[m] for p, m in zip(part.tolist(), mol.tolist())]
+    counts = _read_counts(recs, n)
+    total = int(groups["molecules"].sum(dtype=np.int64))
+    counts.update(molecules=total, counted=total, tied=0, groups=len(groups), own=int(groups["own"].sum(dtype=np.int64)),
+                  no_part=int((~part).sum()), rows=rows)
+    if iso is None:
+        return cells.tolist(), entries, counts
+    idx = np.flatnonzero(part)
+    code = mol[idx].astype(np.int64)
+    own = code == NO_UMI
+    code[own] = (1 << 32) + idx[own]                                  # (a molecule of its own: a code no other read has)
+    c, f = cell_of[idx].astype(np.int64), recs["feature"][idx].astype(np.int64)
+    order = np.lexsort((code, f, c))
+    c, f, code = c[order], f[order], code[order]
+    start = np.flatnonzero(np.concatenate([[True], (c[1:] != c[:-1]) | (f[1:] != f[:-1]) | (code[1:] != code[:-1])])) if len(idx) \
+        else np.zeros(0, np.int64)
+    cls = np.bitwise_and.reduceat(iso["compat"][idx][order], start) if len(idx) else np.zeros(0, np.uint64)
+    molecules = np.stack([f[start], c[start], cls.astype(np.uint64).view(np.int64)], axis=1).reshape(-1, 3)
+    return cells.tolist(), entries, counts, molecules[np.lexsort((molecules[:, 2].view(np.uint64), molecules[:, 1], molecules[:, 0]))]
+
+
+def gene_molecules_text(names, heads, cb, ur, recs, rows):
+    """gene_molecules.tsv: one row per read that takes part"""
+    out = ["read\tCB\tfeature\tUR\tmolecule\n"]
+    for h, c, u, f, r in zip(heads, cb, ur, recs["feature"].tolist(), rows):
+        if r is not None:
+            out.append("%s\t%s\t%s\t%s\t%s\n" % (h.split(b"\t")[0].decode(), c.decode(), names[f], u.decode("latin-1") if u is not None else "*", r))
+    return "".join(out).encode()
+
+
 def _mtx(n_rows, n_cols, entries):
     """{(row, column): count}, both from 0 -> the text of a MatrixMarket file, by column, then row"""
     rows = ["%%MatrixMarket matrix coordinate integer general\n", "%d %d %d\n" % (n_rows, n_cols, len(entries))]
@@ -604,21 +716,29 @@ def em_files(names, tx_names, feat, cells, molecules, run, eps=EM_EPS_DEFAULT, m
     return {"isoform_em_matrix.mtx": "".join(rows).encode(), "isoform_em_pool.tsv": "".join(pool_rows).encode()}, counts
 
 
-def count_matrix_text(text, names, assign, isoforms=None, em=None):
+def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None):
     """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
     assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
     -> ({file name: bytes}, counts dict).  With isoforms = (transcript names, their feature ids) assign returns the pair
     (REC_DTYPE array, ISO_DTYPE array), and the files of isoform_files and its counts join the four, which stay as they are.
-    With em = (run, eps, max_iter, init) beside isoforms (em_files) the two files of EM_FILES and their counts join those."""
+    With em = (run, eps, max_iter, init) beside isoforms (em_files) the two files of EM_FILES and their counts join those.
+    With per_gene = (run, umi_len, umi_dist) (--umi_per_gene; run as for molecules_per_gene) the molecules are made per cell and
+    gene from the headers' UR: matrix.mtx and the isoform and EM matrices follow them, gene_molecules.tsv joins the files, the
+    other files stay the same bytes."""
     from .consensus import parse_tagged
     heads, seqs, cb, ub = parse_tagged(text)
     take = [i for i, c in enumerate(cb) if c is not None]
     recs = assign([seqs[i] for i in take])
+    iso = None
     if isoforms is not None:
         recs, iso = recs
-        cells, entries, counts, molecules = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs, iso)
+    if per_gene is not None:
+        ur = _ur_texts([heads[i] for i in take])
+        made = molecules_per_gene([cb[i] for i in take], ur, recs, per_gene[0], per_gene[1], per_gene[2], iso)
     else:
-        cells, entries, counts = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs)
+        made = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs, iso)
+    cells, entries, counts = made[:3]
+    molecules = made[3] if isoforms is not None else None
     counts["no_cell"] = len(cb) - len(take)
     rows = ["read\tCB\tUB\tfeature\thits\tsecond\tn_keys\tn_found\tflags\n"]
     for i, r in zip(take, recs.tolist()):
@@ -630,6 +750,8 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None):
              "barcodes.tsv": b"".join(c + b"\n" for c in cells),
              "matrix.mtx": _mtx(len(names), len(cells), entries),
              "reads.tsv": "".join(rows).encode()}
+    if per_gene is not None:
+        files["gene_molecules.tsv"] = gene_molecules_text(names, [heads[i] for i in take], [cb[i] for i in take], ur, recs, counts.pop("rows"))
     if isoforms is not None:
         more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], [heads[i] for i in take], [cb[i] for i in take],
                                          [ub[i] for i in take], iso, cells, molecules)
@@ -730,10 +852,11 @@ def device_em(ctx):
 
 
 def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None,
-                           em=None):
+                           em=None, per_gene=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
     reads.tsv, with iso_margin (--isoforms) the files of ISO_FILES, and with em = (eps, max_iter, init) (--isoform_em) those of
-    EM_FILES -> counts"""
+    EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
+    (bdg_umi_dedup_genes) and gene_molecules.tsv -> counts"""
     from . import _native
     tx_names, tx_seqs = read_fasta(transcripts)
     names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
@@ -746,7 +869,8 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
         stats = ctx.genes_index_stats()
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
                                           (tx_names, feat) if iso_margin else None,
-                                          (device_em(ctx),) + tuple(em) if iso_margin and em else None)
+                                          (device_em(ctx),) + tuple(em) if iso_margin and em else None,
+                                          (ctx.umi_dedup_genes,) + tuple(per_gene) if per_gene else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
@@ -763,6 +887,9 @@ def log_counts(counts, out_dir):
                 % (counts["reads"], counts["assigned"], counts["tie"], counts["low"], counts["crowded"], counts["molecules"],
                    counts["counted"], counts["tied"], counts.get("features", 0), counts.get("transcripts", 0), counts.get("keys", 0),
                    counts.get("k", K_DEFAULT), counts.get("ambiguous", 0), out_dir))
+    if "groups" in counts:
+        logger.info("Molecules per gene: %d groups of cell and gene, %d molecules, %d of them reads without a usable UMI; %d reads "
+                    "in no molecule" % (counts["groups"], counts["molecules"], counts["own"], counts["no_part"]))
     if "iso_unique" in counts:
         logger.info("Isoforms: reads %d unique, %d multi, %d no gene; molecules %d unique, %d multi, %d conflict; %d classes"
                     % (counts["iso_unique"], counts["iso_multi"], counts["iso_nogene"], counts["mol_unique"], counts["mol_multi"],
@@ -824,6 +951,32 @@ def em_max_iter_arg(v):
     return x
 
 
+def gene_umi_dist_arg(v):
+    if v not in ("0", "1"):
+        raise argparse.ArgumentTypeError("--gene_umi_dist takes 0 or 1")
+    return int(v)
+
+
+def gene_umi_len_arg(v):
+    try:
+        x = int(v)
+    except ValueError:
+        x = 0
+    if not 3 <= x <= 12:
+        raise argparse.ArgumentTypeError("--umi_len takes an integer, 3 .. 12")
+    return x
+
+
+def check_per_gene_options(p, a, with_matrix):
+    """the errors of --umi_per_gene and --gene_umi_dist, the same on both command lines; sets a.gene_umi_dist to None without
+    --umi_per_gene, else to the distance"""
+    if a.gene_umi_dist is not None and not a.umi_per_gene:
+        p.error("--gene_umi_dist needs --umi_per_gene")
+    if a.umi_per_gene and not with_matrix:
+        p.error("--umi_per_gene needs --count_matrix: it makes the molecules that the matrix counts")
+    a.gene_umi_dist = (GENE_UMI_DIST_DEFAULT if a.gene_umi_dist is None else a.gene_umi_dist) if a.umi_per_gene else None
+
+
 def check_iso_options(p, a, with_matrix):
     """the errors of --isoforms, --iso_margin and the --isoform_em family, the same on both command lines; sets a.iso_margin to
     None without --isoforms, and a.em to (eps, max_iter, init) with --isoform_em, else None"""
@@ -858,6 +1011,12 @@ def add_gene_options(p):
                    help="--isoform_em: iterations of a problem at most (default %d, 1 .. %d)" % (EM_MAX_ITER_DEFAULT, EM_MAX_ITER_MAX))
     p.add_argument("--em_init", choices=EM_INITS, default=None,
                    help="--isoform_em: a cell's problem starts uniform (default) or from its gene's abundances pooled over the cells")
+    p.add_argument("--umi_per_gene", action="store_true",
+                   help="make the molecules of the matrix (and of --isoforms) per cell and gene: UMIs are collapsed inside (cell, "
+                        "gene), from the UR of the tagged reads, so that one UMI in two genes of a cell counts twice; writes "
+                        "gene_molecules.tsv beside the matrix")
+    p.add_argument("--gene_umi_dist", type=gene_umi_dist_arg, default=None, metavar="D",
+                   help="--umi_per_gene: largest edit distance between two UMIs of one molecule, 0 or 1 (default %d)" % GENE_UMI_DIST_DEFAULT)
     p.add_argument("--gene_k", type=gene_k_arg, default=None, metavar="K",
                    help="bases of a key of the gene lookup (default %d, 11 .. 31)" % K_DEFAULT)
     p.add_argument("--gene_min_hits", type=gene_min_hits_arg, default=None, metavar="H",
@@ -874,11 +1033,19 @@ def parse_args(argv):
     p.add_argument("-o", "--output", required=True,
                    help="directory for features.tsv, barcodes.tsv, matrix.mtx and reads.tsv (and the files of --isoforms)")
     add_gene_options(p)
+    p.add_argument("--umi_len", type=gene_umi_len_arg, default=None, metavar="L",
+                   help="--umi_per_gene: letters of the library's UMI, 3 .. 12 (a UMI is usable at L - 2 .. L + 2 letters)")
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
     a = p.parse_args(argv)
     a.gene_k = K_DEFAULT if a.gene_k is None else a.gene_k
     a.gene_min_hits = MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
     check_iso_options(p, a, True)
+    check_per_gene_options(p, a, True)
+    if a.umi_len is not None and not a.umi_per_gene:
+        p.error("--umi_len needs --umi_per_gene")
+    if a.umi_per_gene and a.umi_len is None:
+        p.error("--umi_per_gene needs --umi_len: the tagged file does not say how many letters the library's UMI has")
+    a.per_gene = (a.umi_len, a.gene_umi_dist) if a.umi_per_gene else None
     return a
 
 
@@ -888,7 +1055,7 @@ def main(argv):
     if not logger.handlers:
         logger.addHandler(logging.StreamHandler(stream=sys.stdout))
     log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
-                                      a.em), a.output)
+                                      a.em, a.per_gene), a.output)
 
 
 if __name__ == "__main__":

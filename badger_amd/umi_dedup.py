@@ -15,8 +15,13 @@ The rule
 UMI-tools' directional method walks the same graph breadth-first from the most abundant UMI and takes a child into the
 first component that reaches it; the best-parent form above gives the same answer wherever a child has one candidate parent
 and never depends on visiting order.
+
+dedup_per_gene is the same rule inside (cell, gene) instead of inside the cell (--count_matrix --umi_per_gene; the device's
+bdg_umi_dedup_genes_dev).
 """
 from collections import defaultdict
+
+import numpy as np
 
 UMI_LEN = {"tenX_v3": 12, "tenX_v2": 10, "tenX_5p_v3": 12, "tenX_5p_v2": 10}
 UMI_MAX_LEN = 14                   # usable lengths are at most 12 + 2: the device code packs one into 32 bits (umi_code)
@@ -37,6 +42,32 @@ def umi_code(s):
             return NONE
         v = v << 2 | b
     return len(s) << 28 | v
+
+
+_LETTER = np.full(256, 4, dtype=np.uint8)
+for _c, _b in _ACGT.items():
+    _LETTER[ord(_c)] = _b
+
+
+def umi_codes(texts):
+    """umi_code of every text (str or bytes; None counts as no text) at once -> uint32 [n]"""
+    n = len(texts)
+    out = np.full(n, NONE, dtype=np.uint32)
+    if not n:
+        return out
+    raw = [b"" if t is None else t.encode() if isinstance(t, str) else bytes(t) for t in texts]
+    lens = np.fromiter((len(r) for r in raw), dtype=np.int64, count=n)
+    letter = _LETTER[np.frombuffer(b"".join(raw), dtype=np.uint8)]
+    off = np.concatenate([[0], np.cumsum(lens)])
+    bad = np.concatenate([[0], np.cumsum(letter == 4)])
+    ok = (lens > 0) & (lens <= UMI_MAX_LEN) & (bad[off[1:]] == bad[off[:-1]])
+    at, L = off[:-1][ok], lens[ok]
+    v = np.zeros(len(at), dtype=np.uint32)
+    for j in range(int(L.max(initial=0))):
+        has = j < L
+        v[has] = v[has] << np.uint32(2) | letter[at[has] + j]
+    out[ok] = L.astype(np.uint32) << np.uint32(28) | v
+    return out
 
 
 def umi_str(code):
@@ -136,6 +167,46 @@ def dedup(cells, umis, umi_len, umi_dist=1):
             rows.append((u, mol[c][u]))
         else:
             rows.append(("*", "*"))
+    return rows, stats
+
+
+def dedup_per_gene(cells, features, umis, umi_len, umi_dist=1):
+    """Molecules per cell and gene (--umi_per_gene; the rule include/badger_hip.h states at bdg_umi_dedup_genes_dev).
+    Per read: its cell ('*' or None: none), its feature (None: its gene record is not ASSIGNED) and the UR text of its header
+    (None: no tag).  A read takes part when it has a cell and a feature; its group is (cell, feature).  Inside one group the
+    rule is cell_molecules over the group's usable UMIs, as written; a read that takes part without a usable UMI is a molecule
+    of its own; nothing merges across groups
+    -> (per read: None if it takes no part, '*' for a molecule of its own, else the text of its molecule's root UMI,
+        {(cell, feature): [molecules, umis, umi_reads, own]} for every group with a read; molecules = roots + own)"""
+    def part(c, f):
+        return c is not None and c != "*" and f is not None
+
+    per_group = defaultdict(lambda: defaultdict(int))
+    stats = {}
+    for c, f, u in zip(cells, features, umis):
+        if not part(c, f):
+            continue
+        s = stats.setdefault((c, f), [0, 0, 0, 0])
+        if u is not None and usable(u, umi_len):
+            per_group[(c, f)][u] += 1
+            s[2] += 1
+        else:
+            s[3] += 1
+    roots = {}
+    for g, counts in per_group.items():
+        roots[g] = cell_molecules(counts, umi_dist)
+        stats[g][1] = len(counts)
+        stats[g][0] = sum(1 for u in counts if roots[g][u] == u)
+    for s in stats.values():
+        s[0] += s[3]
+    rows = []
+    for c, f, u in zip(cells, features, umis):
+        if not part(c, f):
+            rows.append(None)
+        elif u is not None and usable(u, umi_len):
+            rows.append(roots[(c, f)][u])
+        else:
+            rows.append("*")
     return rows, stats
 
 

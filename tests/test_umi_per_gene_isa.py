@@ -1,0 +1,36 @@
+"""The compiler's resource counts of the per-gene UMI kernels for gfx950 (CPU tier: hipcc cross-compiles without a GPU).
+k_umi_insert_genes (both forms) and k_group_emit are memory-bound table kernels that count on many resident waves:
+neither may use scratch, and each stays at or below 64 VGPRs - the kernels they run beside in csrc/umi_kernels.hip report 6 to
+30.  Resource counts only."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from test_genes_isa import _resources
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.fixture(scope="module")
+def text(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not available")
+    out = str(tmp_path_factory.mktemp("isa") / "umi.s")
+    src = os.path.join(ROOT, "badger_amd", "csrc", "umi_kernels.hip")
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-Wno-unused-function",
+                    "-Wno-inline-asm", "-Wno-unused-command-line-argument", "-I", os.path.join(ROOT, "include"), "-o", out, src],
+                   check=True, timeout=600)
+    return open(out).read()
+
+
+@pytest.mark.parametrize("name", ("18k_umi_insert_genesILb1EE", "18k_umi_insert_genesILb0EE", "12k_group_emitE"))
+def test_per_gene_kernel_budget(text, name):
+    vgpr, agpr, scratch, lds = _resources(text, name)
+    print("%s: %d VGPRs, %d AGPRs, %d bytes of scratch, %d bytes of LDS" % (name, vgpr, agpr, scratch, lds))
+    assert scratch == 0, name + " spills"
+    assert lds == 0, (name, lds)
+    assert vgpr + agpr <= 64, (name, vgpr, agpr)
+
