@@ -608,38 +608,6 @@ int bdg_rescue_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, ui
     return rc;
 }
 
-int bdg_molecule_reps_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_molecule,
-                          const uint32_t* d_cdna_len, uint64_t n, const uint32_t* d_cells, uint32_t n_cells,
-                          uint8_t* d_rep, uint32_t* d_mol_reads)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (n && (!d_rank || !d_has || !d_molecule || !d_cdna_len || !d_rep || !d_mol_reads)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n_cells && !d_cells) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return bdg_molecule_reps_launch(ctx, d_rank, d_has, d_molecule, d_cdna_len, n, d_cells, n_cells, d_rep, d_mol_reads);
-}
-
-int bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on)
-{
-    if (!ctx) return BDG_E_ARG;
-    ctx->mol_aggregate = on != 0;
-    return BDG_OK;
-}
-
-int bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
-                      const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
-                      uint32_t* d_molecule, uint32_t* d_cell_counts)
-{
-    if (!ctx) return BDG_E_ARG;
-    if (n && (!d_rank || !d_has || !d_umi || !d_molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n_cells && (!d_cells || !d_cell_counts)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
-    if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return bdg_umi_dedup_launch(ctx, d_rank, d_has, d_umi, n, d_cells, n_cells, umi_len, umi_dist, d_molecule, d_cell_counts);
-}
-
 // ---- nearest ----------------------------------------------------------------
 int bdg_whitelist_load(bdg_ctx* ctx, const uint32_t* wl, uint32_t nw)
 {

@@ -132,10 +132,7 @@ struct bdg_ctx {
     // them every read's UMI packed into 32 bits (bdg_extract_keep_umis, umi_kernels.hip) and, only while trim_on, every read's
     // cDNA length from the chunk's trim and chimera records (bdg_extract_keep_cdna)
     struct Kept { bool on = false; DevBuf b; uint64_t n = 0; } kept_recs, kept_umis, kept_cdna;
-    DevBuf u_ws;         // bdg_umi_dedup_dev's table: keys u64 | counts u32 | parents u32 per slot, read slots u32 per read;
-                         // bdg_molecule_reps_dev's: keys u64 | election words u64 | counts u32 per slot, read slots u32 per read
-                         // bdg_umi_dedup_genes_dev's: group keys u64 | UMI keys u64 | group counts u32 [4] | counts u32 | parents u32
-                         // per slot, read slots u32 per read
+    DevBuf u_ws;         // the tables of umi_kernels.hip, laid out by its umi_table() and mol_table(); every call clears what it uses
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
     bool gene_aggregate = true;              // bdg_umi_dedup_genes_set_aggregate
     // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call

@@ -40,13 +40,9 @@ int bdg_rows_of_launch(bdg_ctx*, const uint32_t*, uint32_t, const uint32_t*, uin
 int bdg_cluster_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, int32_t*);
 int bdg_assign_reads_launch(bdg_ctx*, const bdg_extract_rec*, uint64_t, const uint32_t*, uint32_t, const uint32_t*, const uint8_t*, uint32_t*, uint8_t*);
 int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_t, uint32_t, const uint32_t*, uint32_t, uint64_t*);
-// umi_kernels.hip
+// umi_kernels.hip (which also holds the entry points of its tables: the bdg_umi_dedup*, bdg_molecule_reps* family)
 int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
-int bdg_umi_dedup_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t,
-                         uint32_t*, uint32_t*);
 int bdg_cdna_len_launch(bdg_ctx*, const bdg_trim_rec*, const bdg_chimera_rec*, uint32_t, uint32_t*);
-int bdg_molecule_reps_launch(bdg_ctx*, const uint32_t*, const uint8_t*, const uint32_t*, const uint32_t*, uint64_t, const uint32_t*, uint32_t,
-                             uint8_t*, uint32_t*);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // trim5p_kernels.hip

@@ -5,8 +5,8 @@
 //            2-bit letters, first letter most significant, UMI_NONE for no ACGT string of 1..14 letters.  The numeric order of
 //            the codes is the rule's UMI order (length, then A < C < G < T).
 //   insert   k_umi_insert: per read with a cell and a usable UMI, the key cell ordinal << 32 | code goes into an open-
-//            addressing table (one compare-and-swap claims a slot, an add counts the read), the read keeps its slot.  The
-//            table's slots are the distinct (cell, UMI) pairs with their read counts; no sort, no scan.
+//            addressing table (find_or_claim: one compare-and-swap claims a slot; an add counts the read), the read keeps its
+//            slot.  The table's slots are the distinct (cell, UMI) pairs with their read counts; no sort, no scan.
 //   parent   k_umi_parent: per distinct pair, every string at distance 1 (3L substitutions, the distinct deletions, the
 //            distinct insertions; only lengths inside the window) is looked up in the same table: a found neighbour that is a
 //            parent candidate competes on n << 32 | ~code, the highest wins.  A thread writes only its own slot's parent, so
@@ -14,11 +14,14 @@
 //            the size of its cell.
 //   root     k_umi_root: every pair follows its parents to the root (rank rises strictly along the way).
 //   results  k_umi_reads: per read the root's code; k_umi_insert and k_umi_cells count reads, reads with a UMI, distinct
-//            UMIs and molecules per cell, summed inside the wave before the atomic (one hot cell is one address).
+//            UMIs and molecules per cell, summed inside the wave before the atomic (wave_count: one hot cell is one address).
 //
 // Further down: one representative read per molecule (bdg_molecule_reps_dev), and molecules per cell and gene
 // (bdg_umi_dedup_genes_dev, DESIGN §4.22: a group table over (cell, feature) in front of the table above, whose kernels from
 // k_umi_parent on then run unchanged with the group's id in the cell ordinal's place).
+//
+// All three store keys through one probe (find_or_claim) and group the lanes of a wave by one walk (wave_groups); on the host one
+// size (table_slots), one layout of the workspace (umi_table, mol_table) and one launch of the kernels from k_umi_parent on.
 #include "bdg_common.hpp"
 
 namespace {
@@ -33,19 +36,49 @@ __device__ __forceinline__ uint32_t slot_of(unsigned long long k, uint32_t mask)
     return (uint32_t)k & mask;
 }
 
+// The slot of key k in an open-addressing table (linear probing from slot_of), claimed if nobody had.  Every table of this file
+// keeps two things and every probe relies on them: a slot goes from EMPTY to its key once and stays, and the table is at most
+// half full (table_slots), so a probe ends - at the key or at an EMPTY slot - after about two slots.  LOOK_FIRST loads before it
+// swaps: a key already stored costs a load and no atomic (a key read is final, a stale EMPTY is settled by the swap).
+template <bool LOOK_FIRST>
+__device__ __forceinline__ uint32_t find_or_claim(unsigned long long* keys, unsigned long long k, uint32_t mask)
+{
+    for (uint32_t h = slot_of(k, mask);; h = (h + 1u) & mask) {
+        unsigned long long e = LOOK_FIRST ? __atomic_load_n(&keys[h], __ATOMIC_RELAXED) : EMPTY;
+        if (e == EMPTY) { e = atomicCAS(&keys[h], EMPTY, k); if (e == EMPTY) return h; }
+        if (e == k) return h;
+    }
+}
+
+// The lanes of a wave that name one key, a group at a time: the lowest lane of the group is its leader.  Every lane of the wave
+// calls; `none` is no key - a lane that holds it belongs to no group, matches no leader (a leader's key is not `none`) and gets
+// its own lane back.  step(leader, leader's key, peers, mine) runs once per group on every lane, in wave-uniform control flow
+// (it may shuffle): peers is the group's lane mask, mine says whether this lane is in it.  -> this lane's leader.
+template <typename K, typename F>
+__device__ __forceinline__ uint32_t wave_groups(K key, K none, F&& step)
+{
+    uint32_t my_leader = threadIdx.x & 63u;
+    unsigned long long todo = __ballot(key != none);
+    while (todo) {
+        const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+        const K lk = __shfl(key, (int)leader);
+        const bool mine = key == lk;
+        const unsigned long long peers = __ballot(mine);
+        if (mine) my_leader = leader;
+        step(leader, lk, peers, mine);
+        todo &= ~peers;
+    }
+    return my_leader;
+}
+
 // counts[key * 4 + field] += 1 for every lane whose key is not UMI_NONE: lanes with the same key are summed first, one
 // lane per distinct key adds.  Every lane of the wave calls.
 __device__ __forceinline__ void wave_count(uint32_t* __restrict__ counts, uint32_t key, uint32_t field)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long todo = __ballot(key != UMI_NONE);
-    while (todo) {
-        const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-        const uint32_t lk = __shfl(key, (int)leader);
-        const unsigned long long peers = __ballot(key == lk) & todo;
+    wave_groups(key, UMI_NONE, [&](uint32_t leader, uint32_t lk, unsigned long long peers, bool) {
         if (lane == leader) atomicAdd(&counts[(size_t)lk * 4u + field], (uint32_t)__popcll(peers));
-        todo &= ~peers;
-    }
+    });
 }
 
 __global__ __launch_bounds__(256)
@@ -105,13 +138,8 @@ void k_umi_insert(const uint32_t* __restrict__ rank, const uint8_t* __restrict__
         if (has[i]) c = cell_of(rank[i], cells, ncells);
         const uint32_t code = umi[i], len = code >> 28;
         if (c != UMI_NONE && code != UMI_NONE && len >= lo_len && len <= hi_len) {
-            const unsigned long long k = (unsigned long long)c << 32 | code;
-            uint32_t h = slot_of(k, mask);
-            for (;;) {                                                    // (never full: twice as many slots as reads)
-                const unsigned long long old = atomicCAS(&keys[h], EMPTY, k);
-                if (old == EMPTY || old == k) { atomicAdd(&cnt[h], 1u); slot = h; break; }
-                h = (h + 1u) & mask;
-            }
+            slot = find_or_claim<false>(keys, (unsigned long long)c << 32 | code, mask);
+            atomicAdd(&cnt[slot], 1u);
         }
         read_slot[i] = slot;
     }
@@ -214,9 +242,9 @@ void k_umi_reads(const uint32_t* __restrict__ read_slot, uint64_t n, const unsig
 //   insert   k_mol_insert: k_umi_insert's open-addressing form over the key cell ordinal << 32 | molecule code.  Per slot a read
 //            count and an election word cdna_len << 32 | (0xFFFFFFFF - i), taken by a 64-bit atomic maximum: the longest cDNA, the
 //            earliest read at equal lengths; a read without cDNA is counted and does not bid.  A large molecule is one address
-//            (§4.0), so the lanes of a wave that name the same key first combine their count and their maximum (the peers of
-//            wave_count); the leader of each group alone probes the table and issues one add and one maximum, and hands the slot
-//            to its peers.
+//            (§4.0), so the lanes of a wave that name the same key first combine their count and their maximum (wave_groups);
+//            the leader of each group alone probes the table and issues one add and one maximum, and hands the slot to its
+//            peers.
 //   results  k_mol_reads: per read its slot's count, and rep where the slot's election word names the read.
 __global__ __launch_bounds__(256)
 void k_cdna_len(const bdg_trim_rec* __restrict__ trim, const bdg_chimera_rec* __restrict__ chim, uint32_t n, uint32_t* __restrict__ out)
@@ -238,15 +266,6 @@ void k_mol_clear(unsigned long long* __restrict__ keys, unsigned long long* __re
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s < P) { keys[s] = EMPTY; elect[s] = 0ull; cnt[s] = 0u; }
-}
-
-// the slot of key k, claimed if nobody had (never full: twice as many slots as reads)
-__device__ __forceinline__ uint32_t mol_slot(unsigned long long* __restrict__ keys, unsigned long long k, uint32_t mask)
-{
-    for (uint32_t h = slot_of(k, mask);; h = (h + 1u) & mask) {
-        const unsigned long long old = atomicCAS(&keys[h], EMPTY, k);
-        if (old == EMPTY || old == k) return h;
-    }
 }
 
 __device__ __forceinline__ unsigned long long wave_max64(unsigned long long v)
@@ -279,28 +298,21 @@ void k_mol_insert(const uint32_t* __restrict__ rank, const uint8_t* __restrict__
     uint32_t slot = UMI_NONE;
     if (!AGGREGATE) {
         if (k != EMPTY) {
-            slot = mol_slot(keys, k, mask);
+            slot = find_or_claim<false>(keys, k, mask);
             atomicAdd(&cnt[slot], 1u);
             if (bid) atomicMax(&elect[slot], bid);
         }
     } else {
         const uint32_t lane = threadIdx.x & 63u;
-        uint32_t my_leader = lane, gcount = 0;
+        uint32_t gcount = 0;
         unsigned long long gmax = 0;
-        unsigned long long todo = __ballot(k != EMPTY);
-        while (todo) {
-            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-            const unsigned long long lk = __shfl(k, (int)leader);
-            const bool mine = k == lk;                                    // (EMPTY is no key: a lane outside todo never matches)
-            const unsigned long long peers = __ballot(mine);
+        const uint32_t my_leader = wave_groups(k, EMPTY, [&](uint32_t leader, unsigned long long, unsigned long long peers, bool mine) {
             unsigned long long m = bid;                                   // (alone: the leader's own bid)
             if (peers & (peers - 1ull)) m = wave_max64(mine ? bid : 0ull);
-            if (mine) my_leader = leader;
             if (lane == leader) { gcount = (uint32_t)__popcll(peers); gmax = m; }
-            todo &= ~peers;
-        }
+        });
         if (k != EMPTY && my_leader == lane) {                            // the leaders of all groups probe side by side
-            slot = mol_slot(keys, k, mask);
+            slot = find_or_claim<false>(keys, k, mask);
             atomicAdd(&cnt[slot], gcount);
             if (gmax) atomicMax(&elect[slot], gmax);
         }
@@ -332,24 +344,14 @@ void k_mol_reads(const uint32_t* __restrict__ read_slot, const uint32_t* __restr
 // DESIGN §4.22) ----
 //   A (cell, feature, UMI) key has 96 bits and a compare-and-swap takes 64, so the key goes in two levels:
 //   groups   k_umi_insert_genes: per read that takes part, the key cell << 32 | feature finds or claims a slot of the group table; the
-//            slot index (below 2^31) is the group's id.  A housekeeping gene in one cell is one address (§4.0): the probe loads
-//            before it swaps - a key already stored costs a load and no atomic - and the lanes of a wave that name one group
-//            elect a leader (the peers of wave_count), who alone probes and hands the id to the others.
+//            slot index (below 2^31) is the group's id.  A housekeeping gene in one cell is one address (§4.0): the probe looks
+//            first (find_or_claim<true>), and the lanes of a wave that name one group elect a leader (wave_groups), who alone
+//            probes and hands the id to the others.
 //   UMIs     the same kernel then puts group id << 32 | code into k_umi_insert's table (look first here too).  From there on
 //            k_umi_parent, k_umi_root, k_umi_cells and k_umi_reads run as they are, "cell ordinal" read as "group id"; the counts
 //            [slots][4] per group are: own-molecule reads, reads with a usable UMI, distinct UMIs, roots.
 //   records  k_group_emit: the occupied group slots, compacted: one add to the cursor per wave (ballots and popcounts over its 16
 //            runs of 64 slots), a record per lane and run.
-__device__ __forceinline__ uint32_t find_or_claim(unsigned long long* keys, unsigned long long k, uint32_t mask)
-{
-    for (uint32_t h = slot_of(k, mask);; h = (h + 1u) & mask) {           // (never full: twice as many slots as reads)
-        // a slot goes from EMPTY to its key once and stays: a key read here is final, a stale EMPTY is settled by the swap
-        unsigned long long e = __atomic_load_n(&keys[h], __ATOMIC_RELAXED);
-        if (e == EMPTY) { e = atomicCAS(&keys[h], EMPTY, k); if (e == EMPTY) return h; }
-        if (e == k) return h;
-    }
-}
-
 template <bool AGGREGATE>
 __global__ __launch_bounds__(256)
 void k_umi_insert_genes(const uint32_t* __restrict__ cell, const bdg_gene_rec* __restrict__ recs, const uint32_t* __restrict__ umi,
@@ -369,24 +371,16 @@ void k_umi_insert_genes(const uint32_t* __restrict__ cell, const bdg_gene_rec* _
     }
     uint32_t gid = UMI_NONE;
     if (!AGGREGATE) {
-        if (gk != EMPTY) gid = find_or_claim(gkeys, gk, mask);
+        if (gk != EMPTY) gid = find_or_claim<true>(gkeys, gk, mask);
     } else {
         const uint32_t lane = threadIdx.x & 63u;
-        uint32_t my_leader = lane;
-        unsigned long long todo = __ballot(gk != EMPTY);
-        while (todo) {
-            const uint32_t leader = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-            const unsigned long long lk = __shfl(gk, (int)leader);
-            const bool mine = gk == lk;                                   // (EMPTY is no key: a lane outside todo never matches)
-            if (mine) my_leader = leader;
-            todo &= ~__ballot(mine);
-        }
-        if (gk != EMPTY && my_leader == lane) gid = find_or_claim(gkeys, gk, mask);   // the leaders of all groups probe side by side
+        const uint32_t my_leader = wave_groups(gk, EMPTY, [](uint32_t, unsigned long long, unsigned long long, bool) {});
+        if (gk != EMPTY && my_leader == lane) gid = find_or_claim<true>(gkeys, gk, mask);   // the leaders of all groups probe side by side
         gid = __shfl(gid, (int)my_leader);
     }
     uint32_t slot = UMI_NONE;
     if (gid != UMI_NONE && code != UMI_NONE) {
-        slot = find_or_claim(keys, (unsigned long long)gid << 32 | code, mask);
+        slot = find_or_claim<true>(keys, (unsigned long long)gid << 32 | code, mask);
         atomicAdd(&cnt[slot], 1u);
     }
     if (i < n) read_slot[i] = slot;
@@ -446,38 +440,6 @@ int bdg_cdna_len_launch(bdg_ctx* ctx, const bdg_trim_rec* d_trim, const bdg_chim
     return BDG_OK;
 }
 
-int bdg_molecule_reps_launch(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_mol, const uint32_t* d_len,
-                             uint64_t n, const uint32_t* d_cells, uint32_t ncells, uint8_t* d_rep, uint32_t* d_mol_reads)
-{
-    if (n == 0) return BDG_OK;
-    hipStream_t st = ctx->stream;
-    uint64_t P = 1024;                                                    // bdg_umi_dedup_launch's table: two slots per read
-    while (P < 2 * n) P <<= 1;
-    if (P > (1ull << 31)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the molecule table takes (2^30)");
-    // workspace: keys u64 [P] | election words u64 [P] | counts u32 [P] | read slots u32 [n]
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->u_ws, 20 * (size_t)P + 4 * (size_t)n + 256))) return rc;
-    auto* keys = static_cast<unsigned long long*>(ctx->u_ws.p);
-    auto* elect = keys + P;
-    auto* cnt = reinterpret_cast<uint32_t*>(elect + P);
-    auto* read_slot = cnt + P;
-    const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
-    {
-        ScopedKernelTimer tm(ctx, "k_mol_insert");
-        hipLaunchKernelGGL(k_mol_clear, dim3(gp), dim3(256), 0, st, keys, elect, cnt, (uint32_t)P);
-        if (ctx->mol_aggregate)
-            hipLaunchKernelGGL(k_mol_insert<true>, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_mol, d_len, n, d_cells, ncells, keys, elect, cnt, mask, read_slot);
-        else
-            hipLaunchKernelGGL(k_mol_insert<false>, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_mol, d_len, n, d_cells, ncells, keys, elect, cnt, mask, read_slot);
-    }
-    {
-        ScopedKernelTimer tm(ctx, "k_mol_reads");
-        hipLaunchKernelGGL(k_mol_reads, dim3(gn), dim3(256), 0, st, read_slot, d_len, n, elect, cnt, d_rep, d_mol_reads);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
-}
-
 int bdg_umi_pack_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, const bdg_extract_rec* d_recs, uint32_t n,
                         uint32_t* d_out)
 {
@@ -488,53 +450,146 @@ int bdg_umi_pack_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_
     return BDG_OK;
 }
 
-int bdg_umi_dedup_launch(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
-                         const uint32_t* d_cells, uint32_t ncells, uint32_t umi_len, uint32_t umi_dist,
-                         uint32_t* d_mol, uint32_t* d_counts)
+// ---- the host side of the family: the size, the workspace, the shared launches, then the entry points with their checks ----
+// The slots of a table for n reads: twice as many as reads, a power of two, 1,024 at least.  0: more reads than a table takes
+// (2^31 slots: a slot index is a 32-bit word in which UMI_NONE is no slot, and a group's id in the upper word of a key).
+static uint64_t table_slots(uint64_t n)
 {
-    hipStream_t st = ctx->stream;
-    if (ncells) BDG_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 16 * (size_t)ncells, st));
-    if (n == 0) return BDG_OK;
-    // twice as many slots as reads (a power of two): a probe that misses ends after about two slots
+    if (n > (1ull << 30)) return 0;
     uint64_t P = 1024;
     while (P < 2 * n) P <<= 1;
-    if (P > (1ull << 31)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the UMI table takes (2^30)");
-    // workspace: keys u64 [P] | counts u32 [P] (then the roots) | parents u32 [P] | read slots u32 [n]
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->u_ws, 16 * (size_t)P + 4 * (size_t)n + 256))) return rc;
-    auto* keys = static_cast<unsigned long long*>(ctx->u_ws.p);
+    return P;
+}
+
+// the usable UMI lengths around umi_len (umi_dedup.usable; a code holds 14 letters at most)
+struct LenWindow { uint32_t lo, hi; };
+static LenWindow len_window(uint32_t umi_len)
+{
+    return LenWindow{ umi_len > 3u ? umi_len - 2u : 1u, umi_len + 2u < MAX_LEN ? umi_len + 2u : MAX_LEN };
+}
+
+// bdg_ctx::u_ws, grown to hold it, as the UMI table of P slots for n reads behind `front` bytes of the caller's own:
+//   keys u64 [P] | counts u32 [P] (k_umi_root writes the roots over them) | parents u32 [P] | read slots u32 [n]
+struct UmiTable { unsigned long long* keys; uint32_t* cnt; uint32_t* par; uint32_t* read_slot; };
+static int umi_table(bdg_ctx* ctx, size_t front, uint64_t P, uint64_t n, UmiTable& T)
+{
+    if (int rc = bdg_reserve(ctx, ctx->u_ws, front + 16 * (size_t)P + 4 * (size_t)n + 256)) return rc;
+    auto* keys = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->u_ws.p) + front);
     auto* cnt = reinterpret_cast<uint32_t*>(keys + P);
-    auto* par = cnt + P;
-    auto* read_slot = par + P;
-    const uint32_t lo_len = umi_len > 3u ? umi_len - 2u : 1u, hi_len = umi_len + 2u < MAX_LEN ? umi_len + 2u : MAX_LEN;
+    T = UmiTable{ keys, cnt, cnt + P, cnt + 2 * P };
+    return BDG_OK;
+}
+// ... and as the molecule table: keys u64 [P] | election words u64 [P] | counts u32 [P] | read slots u32 [n]
+struct MolTable { unsigned long long* keys; unsigned long long* elect; uint32_t* cnt; uint32_t* read_slot; };
+static int mol_table(bdg_ctx* ctx, uint64_t P, uint64_t n, MolTable& T)
+{
+    if (int rc = bdg_reserve(ctx, ctx->u_ws, 20 * (size_t)P + 4 * (size_t)n + 256)) return rc;
+    auto* keys = static_cast<unsigned long long*>(ctx->u_ws.p);
+    auto* cnt = reinterpret_cast<uint32_t*>(keys + 2 * P);
+    T = MolTable{ keys, keys + P, cnt, cnt + P };
+    return BDG_OK;
+}
+
+// Behind an insert that filled T and every read's slot: parents, roots, the counts [ordinal][4] fields 2 and 3 (distinct UMIs,
+// roots) and every read's molecule.  "Ordinal" is what the insert put in the keys' upper word: a cell's, or a group's id.
+static void umi_tail_launch(bdg_ctx* ctx, const UmiTable& T, uint64_t P, uint64_t n, LenWindow w, uint32_t umi_dist, uint32_t* d_counts,
+                            uint32_t* d_mol)
+{
+    hipStream_t st = ctx->stream;
     const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
     {
-        ScopedKernelTimer tm(ctx, "k_umi_insert");
-        hipLaunchKernelGGL(k_umi_clear, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P);
-        hipLaunchKernelGGL(k_umi_insert, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_umi, n, d_cells, ncells, lo_len, hi_len,
-                           keys, cnt, mask, read_slot, d_counts);
-    }
-    {
         ScopedKernelTimer tm(ctx, "k_umi_parent");
-        hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, mask, lo_len, hi_len, umi_dist, par);
+        hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P, mask, w.lo, w.hi, umi_dist, T.par);
     }
     {
         ScopedKernelTimer tm(ctx, "k_umi_results");
-        hipLaunchKernelGGL(k_umi_root, dim3(gp), dim3(256), 0, st, keys, par, (uint32_t)P, cnt);
-        hipLaunchKernelGGL(k_umi_cells, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, d_counts);
-        hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, read_slot, n, keys, cnt, d_mol);
+        hipLaunchKernelGGL(k_umi_root, dim3(gp), dim3(256), 0, st, T.keys, T.par, (uint32_t)P, T.cnt);
+        hipLaunchKernelGGL(k_umi_cells, dim3(gp), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P, d_counts);
+        hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, T.read_slot, n, T.keys, T.cnt, d_mol);
+    }
+}
+
+// the numbers every dedup entry point takes; `tables` names in the message what n reads would not fit
+static int umi_check(bdg_ctx* ctx, uint64_t n, uint32_t umi_len, uint32_t umi_dist, const char* tables)
+{
+    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
+    if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
+    if (!table_slots(n)) return bdg_fail(ctx, BDG_E_ARG, std::string("more reads than the ") + tables + " (2^30)");
+    return BDG_OK;
+}
+
+int bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
+                      const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
+                      uint32_t* d_molecule, uint32_t* d_cell_counts)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && (!d_rank || !d_has || !d_umi || !d_molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n_cells && (!d_cells || !d_cell_counts)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = umi_check(ctx, n, umi_len, umi_dist, "UMI table takes")) return rc;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (n_cells) BDG_HIP_TRY(ctx, hipMemsetAsync(d_cell_counts, 0, 16 * (size_t)n_cells, st));
+    if (n == 0) return BDG_OK;
+    const uint64_t P = table_slots(n);
+    UmiTable T;
+    if (int rc = umi_table(ctx, 0, P, n, T)) return rc;
+    const LenWindow w = len_window(umi_len);
+    {
+        ScopedKernelTimer tm(ctx, "k_umi_insert");
+        hipLaunchKernelGGL(k_umi_clear, dim3((uint32_t)(P / 256)), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P);
+        hipLaunchKernelGGL(k_umi_insert, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, d_rank, d_has, d_umi, n, d_cells, n_cells, w.lo, w.hi,
+                           T.keys, T.cnt, (uint32_t)(P - 1), T.read_slot, d_cell_counts);
+    }
+    umi_tail_launch(ctx, T, P, n, w, umi_dist, d_cell_counts, d_molecule);
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int bdg_molecule_reps_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_molecule,
+                          const uint32_t* d_cdna_len, uint64_t n, const uint32_t* d_cells, uint32_t n_cells,
+                          uint8_t* d_rep, uint32_t* d_mol_reads)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n && (!d_rank || !d_has || !d_molecule || !d_cdna_len || !d_rep || !d_mol_reads)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n_cells && !d_cells) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n >= (1ull << 32)) return bdg_fail(ctx, BDG_E_ARG, "more than 2^32 - 1 reads");
+    const uint64_t P = table_slots(n);
+    if (!P) return bdg_fail(ctx, BDG_E_ARG, "more reads than the molecule table takes (2^30)");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) return BDG_OK;
+    hipStream_t st = ctx->stream;
+    MolTable T;
+    if (int rc = mol_table(ctx, P, n, T)) return rc;
+    const uint32_t mask = (uint32_t)(P - 1), gn = (uint32_t)((n + 255) / 256);
+    {
+        ScopedKernelTimer tm(ctx, "k_mol_insert");
+        hipLaunchKernelGGL(k_mol_clear, dim3((uint32_t)(P / 256)), dim3(256), 0, st, T.keys, T.elect, T.cnt, (uint32_t)P);
+        hipLaunchKernelGGL(ctx->mol_aggregate ? k_mol_insert<true> : k_mol_insert<false>, dim3(gn), dim3(256), 0, st, d_rank, d_has, d_molecule,
+                           d_cdna_len, n, d_cells, n_cells, T.keys, T.elect, T.cnt, mask, T.read_slot);
+    }
+    {
+        ScopedKernelTimer tm(ctx, "k_mol_reads");
+        hipLaunchKernelGGL(k_mol_reads, dim3(gn), dim3(256), 0, st, T.read_slot, d_cdna_len, n, T.elect, T.cnt, d_rep, d_mol_reads);
     }
     BDG_HIP_TRY(ctx, hipGetLastError());
     return BDG_OK;
 }
 
-// ---- bdg_umi_dedup_genes_dev and its host twin ----
-static int umi_genes_check(bdg_ctx* ctx, uint64_t n, uint32_t umi_len, uint32_t umi_dist)
+int bdg_molecule_reps_set_aggregate(bdg_ctx* ctx, int on)
 {
-    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
-    if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
-    if (n > (1ull << 30)) return bdg_fail(ctx, BDG_E_ARG, "more reads than the group and UMI tables take (2^30)");
+    if (!ctx) return BDG_E_ARG;
+    ctx->mol_aggregate = on != 0;
     return BDG_OK;
+}
+
+// ---- bdg_umi_dedup_genes_dev and its host twin ----
+// what both take: the pointers (device or host memory) and the numbers
+static int umi_genes_check(bdg_ctx* ctx, const void* cell, const void* gene_recs, const void* umi, uint64_t n, uint32_t umi_len,
+                           uint32_t umi_dist, const void* molecule, const void* groups, uint32_t cap, const void* n_groups)
+{
+    if (!n_groups || (cap && !groups)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n && (!cell || !gene_recs || !umi || !molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    return umi_check(ctx, n, umi_len, umi_dist, "group and UMI tables take");
 }
 
 // the kernels, and *d_n_groups; asynchronous
@@ -545,42 +600,22 @@ static int umi_genes_launch(bdg_ctx* ctx, const uint32_t* d_cell, const bdg_gene
     hipStream_t st = ctx->stream;
     BDG_HIP_TRY(ctx, hipMemsetAsync(d_n_groups, 0, sizeof(uint32_t), st));
     if (n == 0) return BDG_OK;
-    uint64_t P = 1024;                                                    // both tables: two slots per read, a power of two
-    while (P < 2 * n) P <<= 1;
-    // workspace: group keys u64 [P] | UMI keys u64 [P] | group counts u32 [P][4] | counts u32 [P] (then the roots) | parents u32 [P]
-    // | read slots u32 [n]
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->u_ws, 40 * (size_t)P + 4 * (size_t)n + 256))) return rc;
+    const uint64_t P = table_slots(n);                                    // (both tables)
+    UmiTable T;
+    if (int rc = umi_table(ctx, 24 * (size_t)P, P, n, T)) return rc;      // in front: group keys u64 [P] | group counts u32 [P][4]
     auto* gkeys = static_cast<unsigned long long*>(ctx->u_ws.p);
-    auto* keys = gkeys + P;
-    auto* gcounts = reinterpret_cast<uint32_t*>(keys + P);
-    auto* cnt = gcounts + 4 * P;
-    auto* par = cnt + P;
-    auto* read_slot = par + P;
-    const uint32_t lo_len = umi_len > 3u ? umi_len - 2u : 1u, hi_len = umi_len + 2u < MAX_LEN ? umi_len + 2u : MAX_LEN;
-    const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
+    auto* gcounts = reinterpret_cast<uint32_t*>(gkeys + P);
+    const LenWindow w = len_window(umi_len);
+    const uint32_t mask = (uint32_t)(P - 1), gn = (uint32_t)((n + 255) / 256);
     {
         ScopedKernelTimer tm(ctx, "k_umi_insert_genes");
         BDG_HIP_TRY(ctx, hipMemsetAsync(gkeys, 0xFF, 8 * (size_t)P, st));           // (EMPTY)
         BDG_HIP_TRY(ctx, hipMemsetAsync(gcounts, 0, 16 * (size_t)P, st));
-        hipLaunchKernelGGL(k_umi_clear, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P);
-        if (ctx->gene_aggregate)
-            hipLaunchKernelGGL(k_umi_insert_genes<true>, dim3(gn), dim3(256), 0, st, d_cell, d_recs, d_umi, n, lo_len, hi_len, gkeys, gcounts,
-                               keys, cnt, mask, read_slot);
-        else
-            hipLaunchKernelGGL(k_umi_insert_genes<false>, dim3(gn), dim3(256), 0, st, d_cell, d_recs, d_umi, n, lo_len, hi_len, gkeys, gcounts,
-                               keys, cnt, mask, read_slot);
+        hipLaunchKernelGGL(k_umi_clear, dim3((uint32_t)(P / 256)), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P);
+        hipLaunchKernelGGL(ctx->gene_aggregate ? k_umi_insert_genes<true> : k_umi_insert_genes<false>, dim3(gn), dim3(256), 0, st, d_cell, d_recs,
+                           d_umi, n, w.lo, w.hi, gkeys, gcounts, T.keys, T.cnt, mask, T.read_slot);
     }
-    {
-        ScopedKernelTimer tm(ctx, "k_umi_parent");
-        hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, mask, lo_len, hi_len, umi_dist, par);
-    }
-    {
-        ScopedKernelTimer tm(ctx, "k_umi_results");
-        hipLaunchKernelGGL(k_umi_root, dim3(gp), dim3(256), 0, st, keys, par, (uint32_t)P, cnt);
-        hipLaunchKernelGGL(k_umi_cells, dim3(gp), dim3(256), 0, st, keys, cnt, (uint32_t)P, gcounts);
-        hipLaunchKernelGGL(k_umi_reads, dim3(gn), dim3(256), 0, st, read_slot, n, keys, cnt, d_mol);
-    }
+    umi_tail_launch(ctx, T, P, n, w, umi_dist, gcounts, d_mol);
     {
         ScopedKernelTimer tm(ctx, "k_group_emit");
         hipLaunchKernelGGL(k_group_emit, dim3((uint32_t)((P + 256ull * EMIT_CHUNKS - 1) / (256ull * EMIT_CHUNKS))), dim3(256), 0, st, gkeys, gcounts,
@@ -600,9 +635,7 @@ int bdg_umi_dedup_genes_dev(bdg_ctx* ctx, const uint32_t* d_cell, const bdg_gene
                             uint32_t* d_n_groups)
 {
     if (!ctx) return BDG_E_ARG;
-    if (!d_n_groups || (cap && !d_groups)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n && (!d_cell || !d_gene_recs || !d_umi || !d_molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (int rc = umi_genes_check(ctx, n, umi_len, umi_dist)) return rc;
+    if (int rc = umi_genes_check(ctx, d_cell, d_gene_recs, d_umi, n, umi_len, umi_dist, d_molecule, d_groups, cap, d_n_groups)) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = umi_genes_launch(ctx, d_cell, d_gene_recs, d_umi, n, umi_len, umi_dist, d_molecule, d_groups, cap, d_n_groups)) return rc;
     uint32_t need = 0;
@@ -616,9 +649,7 @@ int bdg_umi_dedup_genes(bdg_ctx* ctx, const uint32_t* cell, const bdg_gene_rec* 
                         uint32_t* n_groups)
 {
     if (!ctx) return BDG_E_ARG;
-    if (!n_groups || (cap && !groups)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (n && (!cell || !gene_recs || !umi || !molecule)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (int rc = umi_genes_check(ctx, n, umi_len, umi_dist)) return rc;
+    if (int rc = umi_genes_check(ctx, cell, gene_recs, umi, n, umi_len, umi_dist, molecule, groups, cap, n_groups)) return rc;
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // staging: cells u32 [n] | UMIs u32 [n];  gene records [n];  group count u32 (in 8 bytes) | group records [cap] | molecules u32 [n]

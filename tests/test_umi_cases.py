@@ -139,3 +139,42 @@ def test_distinct_keys_and_shuffles():
     s, perm = c.shuffled(3)
     mol2, counts2 = uc.rule(s, 12, 1)
     assert (mol2 == mol[perm]).all() and (counts2 == counts).all() and not (perm == np.arange(c.n)).all()
+
+
+@pytest.mark.parametrize("n", uc.WAVE_SIZES)
+def test_wave_shapes_hold_what_they_claim(n):
+    waves = [range(a, min(a + uc.WAVE, n)) for a in range(0, n, uc.WAVE)]
+    keys = {s: uc.wave_keys(s, n) for s in uc.WAVE_SHAPES}
+    assert all(len(k) == n for k in keys.values())
+    per_wave = {s: [sorted({k[i] for i in w if k[i] is not None}) for w in waves] for s, k in keys.items()}
+    assert all(len(d) == 1 for d in per_wave["same"]) and len(set(keys["same"])) == 1
+    assert all(len(d) == len(w) for d, w in zip(per_wave["distinct"], waves)) and len(set(keys["distinct"])) == n
+    assert all(len(d) == min(2, len(w)) for d, w in zip(per_wave["alternate"], waves))
+    assert all(a != b for a, b in zip(keys["alternate"], keys["alternate"][1:]))
+    assert set(keys["none"]) == {None}
+    # ends: a key on lanes 0 and 63 and nowhere else; the two lanes share it in an even wave and differ in an odd one
+    for w, lanes in enumerate(waves):
+        held = [i - lanes[0] for i in lanes if keys["ends"][i] is not None]
+        assert held == [l for l in (0, 63) if l < len(lanes)]
+        if len(lanes) == uc.WAVE:
+            assert (keys["ends"][lanes[0]] == keys["ends"][lanes[63]]) == (w % 2 == 0)
+    assert len({k for k in keys["ends"] if k is not None}) == sum(len(d) for d in per_wave["ends"])   # (no key in two waves)
+    # straddle: one key; its holders are the last lanes of wave 0 - none of them lane 0 in a full wave - and the first of wave 1
+    held = [i for i in range(n) if keys["straddle"][i] is not None]
+    assert len({keys["straddle"][i] for i in held}) == 1
+    assert held == list(range(max(0, min(n, uc.WAVE) - 3), min(n, uc.WAVE + 3)))
+    if n > uc.WAVE:
+        assert held[0] == 61 and held[-1] == min(n, 67) - 1 and 64 in held
+    # as reads: equal keys are equal (cell, UMI) pairs and different keys different ones; a lane without a key takes no part
+    for shape in uc.WAVE_SHAPES:
+        for absent in ("cell", "umi"):
+            c = uc.wave_case(shape, n, absent)
+            pairs = {}
+            for i, k in enumerate(keys[shape]):
+                takes_part = c.cell_text[i] != "*" and ud.usable(c.umi_text[i], 12)
+                assert takes_part == (k is not None), (shape, absent, i)
+                if k is None:
+                    assert (c.cell_text[i] == "*") == (absent == "cell") and (c.umi[i] != ud.NONE or absent == "umi")
+                else:
+                    assert pairs.setdefault(k, (c.cell_text[i], c.umi_text[i])) == (c.cell_text[i], c.umi_text[i])
+            assert len(set(pairs.values())) == len(pairs)

@@ -34,3 +34,20 @@ def test_per_gene_kernel_budget(text, name):
     assert lds == 0, (name, lds)
     assert vgpr + agpr <= 64, (name, vgpr, agpr)
 
+
+
+# VGPRs of the kernels that took the shared probe (find_or_claim) and the shared wave grouping (wave_groups), as the compiler
+# reported them for the commit before the fold, each with its own copy of both loops
+BEFORE_THE_FOLD = {"12k_umi_insertE": 14, "12k_mol_insertILb1EE": 26, "12k_mol_insertILb0EE": 12, "11k_umi_cellsE": 10, "12k_umi_parentE": 30}
+
+
+@pytest.mark.parametrize("name", sorted(BEFORE_THE_FOLD))
+def test_shared_probe_and_grouping_cost_no_registers(text, name):
+    """k_umi_insert 14 VGPRs, k_mol_insert 26 with the aggregation and 12 without, k_umi_cells 10, k_umi_parent 30 before the
+    probe and the grouping were folded into one function each: none may use scratch or LDS, or more than two
+    VGPRs above that"""
+    vgpr, agpr, scratch, lds = _resources(text, name)
+    print("%s: %d VGPRs, %d AGPRs, %d bytes of scratch, %d bytes of LDS" % (name, vgpr, agpr, scratch, lds))
+    assert scratch == 0, name + " spills"
+    assert lds == 0, (name, lds)
+    assert vgpr + agpr <= BEFORE_THE_FOLD[name] + 2, (name, vgpr, agpr)

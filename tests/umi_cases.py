@@ -342,6 +342,53 @@ def distinct_keys(umi_len, n, seed, n_cells=4):
     return Case("distinct%d_%d" % (umi_len, n), cells, reads)
 
 
+# ---- wave shapes ------------------------------------------------------------------------------------------------------------
+WAVE = 64
+WAVE_SIZES = (1, 63, 64, 65, 257)
+WAVE_SHAPES = ("same", "distinct", "alternate", "ends", "none", "straddle")
+
+
+def wave_keys(shape, n):
+    """what the lanes of the insert kernels hold, read i being lane i % 64 of wave i // 64: a small integer per read (equal
+    integers are one key) or None for a lane without a key.  same: one key everywhere; distinct: every lane its own; alternate:
+    two keys in turn; ends: only lanes 0 and 63 of a wave have a key - one key in an even wave, two in an odd one; none: no
+    lane has a key; straddle: one key, held only by the last three lanes of wave 0 (of the reads, where they end before it
+    does) and the first three of wave 1"""
+    if shape == "same":
+        return [0] * n
+    if shape == "distinct":
+        return list(range(n))
+    if shape == "alternate":
+        return [i & 1 for i in range(n)]
+    if shape == "ends":
+        return [2 * (i // WAVE) + (i // WAVE & 1 and i % WAVE == 63) if i % WAVE in (0, 63) else None for i in range(n)]
+    if shape == "none":
+        return [None] * n
+    if shape == "straddle":
+        return [0 if min(n, WAVE) - 3 <= i < WAVE + 3 else None for i in range(n)]
+    raise ValueError(shape)
+
+
+def wave_umi(j):
+    """a 12-letter UMI of its own for every j below 4^12"""
+    return "".join("ACGT"[(j * 2654435761 % (1 << 24)) >> s & 3] for s in range(22, -2, -2))
+
+
+def wave_case(shape, n, absent):
+    """wave_keys as reads of bdg_umi_dedup_dev: key k is cell k % 3 with UMI wave_umi(k // 3); a lane without a key has no cell
+    (absent == "cell": has is 0, the rank is a cell's and the UMI usable) or a cell and no usable UMI (absent == "umi")"""
+    cells = [1000, 2000, 0xFFFFFFF0]
+    reads = []
+    for i, k in enumerate(wave_keys(shape, n)):
+        if k is not None:
+            reads.append((cells[k % 3], 1, wave_umi(k // 3)))
+        elif absent == "cell":
+            reads.append((cells[i % 3], 0, wave_umi(i)))
+        else:
+            reads.append((cells[i % 3], 1, "N" * 12 if i & 1 else wave_umi(i)[:9]))       # (no code, or a length outside the window)
+    return Case("wave_%s_%d_%s" % (shape, n, absent), cells, reads)
+
+
 GENERATORS = {
     "dense": dense,
     "runs": runs,
