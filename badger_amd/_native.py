@@ -3,6 +3,7 @@
 The product path: there is NO CPU fallback.  If the HIP library is missing, or no
 MI355X is visible, every entry point raises.
 """
+import contextlib
 import ctypes as C
 import importlib.util
 import os
@@ -46,6 +47,7 @@ CONSENSUS_DTYPE = np.dtype([("ed", "<u4"), ("span", "<u4"), ("flags", "<u4")])
 CONS_ANCHOR_START, CONS_ANCHOR_END = 0, 1
 CONS_MAX_LEN, CONS_MAX_GROUP = 8192, 16
 CONS_BAND_DEFAULT, CONS_BAND_MAX = 64, 256
+UMI_MAX_DIST_DEFAULT, UMI_MAX_DIST = 1, 2     # bdg_umi_set_max_dist
 CONS_ACCEPTED, CONS_REJ_DIST, CONS_REJ_BAND, CONS_REJ_LEN, CONS_BACKBONE = 1, 2, 4, 8, 16
 # bdg_gene_rec: the gene call of a read by k-mer lookup (bdg_genes_assign; the rule in badger_amd/genes.py)
 GENE_DTYPE = np.dtype([("feature", "<u4"), ("hits", "<u4"), ("second", "<u4"), ("n_keys", "<u4"), ("n_found", "<u4"), ("flags", "<u4")])
@@ -101,7 +103,7 @@ EXPORTS = [
     "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
     "bdg_genes_index_build_iso", "bdg_iso_assign", "bdg_iso_assign_dev",
     "bdg_em_tcc", "bdg_em_tcc_dev",
-    "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate",
+    "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
 ]
 
 
@@ -385,6 +387,7 @@ def load():
     L.bdg_umi_dedup_genes.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, u32, vp]
     L.bdg_umi_dedup_genes_dev.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, u32, vp]
     L.bdg_umi_dedup_genes_set_aggregate.argtypes = [vp, C.c_int]
+    L.bdg_umi_set_max_dist.argtypes = [vp, u32]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -416,6 +419,7 @@ class Context:
         self.h = h
         self.device = int(device)
         self.consensus_band = CONS_BAND_DEFAULT          # what consensus_set_band set last
+        self.umi_max_dist = UMI_MAX_DIST_DEFAULT         # what umi_set_max_dist set last
 
     def close(self):
         if getattr(self, "h", None):
@@ -695,6 +699,23 @@ class Context:
         waits for the stream once, for the number of groups"""
         self._check(self.lib.bdg_umi_dedup_genes_dev(self.h, _ptr(d_cell), _ptr(d_gene_recs), _ptr(d_umi), int(n), int(umi_len),
                                                      int(umi_dist), _ptr(d_molecule), _ptr(d_groups), int(cap), _ptr(d_n_groups)))
+
+    def umi_set_max_dist(self, max_dist):
+        """the largest umi_dist that umi_dedup_dev, umi_dedup_genes_dev and umi_dedup_genes take from here on: 1 (the default)
+        or 2 (bdg_umi_set_max_dist); umi_max_dist is the value in force"""
+        self._check(self.lib.bdg_umi_set_max_dist(self.h, int(max_dist)))
+        self.umi_max_dist = int(max_dist)
+
+    @contextlib.contextmanager
+    def umi_max_dist_of(self, max_dist):
+        """the context takes umi_dist up to max_dist for the time of the block; behind it, an exception included, it has the
+        setting it had"""
+        before = self.umi_max_dist
+        self.umi_set_max_dist(max_dist)
+        try:
+            yield self
+        finally:
+            self.umi_set_max_dist(before)
 
     def umi_dedup_genes_set_aggregate(self, on=True):
         """for measurements and tests: False makes every lane of umi_dedup_genes probe and count for itself"""

@@ -8,7 +8,7 @@
                                 [--consensus_band 64|128|256]
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
                                 [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
-                                [--umi_per_gene [--gene_umi_dist 0|1]]
+                                [--umi_per_gene [--gene_umi_dist 0|1 | --gene_umi_dist2]]
 
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
@@ -96,7 +96,9 @@ def parse_args(args):
                    help="also deduplicate UMIs inside each cell: writes <out>_molecules.tsv (per read: UMI and the molecule's "
                         "representative UMI) and <out>_cells.tsv (per cell: reads, reads with a UMI, UMIs, molecules)")
     p.add_argument("--umi_dist", type=int, default=None, choices=(0, 1),
-                   help="with --umi_dedup: largest edit distance between two UMIs of one molecule (default 1)")
+                   help="with --umi_dedup: largest edit distance between two UMIs of one molecule (default 1).  No 2 here: among "
+                        "the thousands of UMIs of a whole cell a 12-letter UMI has chance neighbours two edits away; distance 2 "
+                        "is taken inside (cell, gene) alone (--umi_per_gene --gene_umi_dist2)")
     p.add_argument("--tagged_reads", type=str, default=None, metavar="PATH",
                    help="read input only: the trimmed cDNA (stage 1's --trimmed_reads) of every read with a cell as FASTA, the header "
                         "carrying the corrected barcode (CB) and, with --umi_dedup, the molecule (UB) and its read count (RN)")

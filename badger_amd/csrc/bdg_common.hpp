@@ -135,6 +135,7 @@ struct bdg_ctx {
     DevBuf u_ws;         // the tables of umi_kernels.hip, laid out by its umi_table() and mol_table(); every call clears what it uses
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
     bool gene_aggregate = true;              // bdg_umi_dedup_genes_set_aggregate
+    uint32_t u_max_dist = 1;                 // bdg_umi_set_max_dist: the largest umi_dist the dedup entry points take, 1 or 2
     // ---- per-molecule consensus (consensus_kernels.hip): grow-only like u_ws, reused by every call
     // ---- chimera split (split_kernels.hip): grow-only, reused by every call
     DevBuf sp_ws;        // counter | staged boundaries, 16 bytes each | piece count u32 per read | the scan's block sums

@@ -11,7 +11,7 @@
 //            distinct insertions; only lengths inside the window) is looked up in the same table: a found neighbour that is a
 //            parent candidate competes on n << 32 | ~code, the highest wins.  A thread writes only its own slot's parent, so
 //            the result is the same in every run.  Work per pair is bounded (at most 3 * 14 + 14 + 4 * 15 probes) whatever
-//            the size of its cell.
+//            the size of its cell.  At distance 2 k_umi_parent2 stands in its place (a wave per pair).
 //   root     k_umi_root: every pair follows its parents to the root (rank rises strictly along the way).
 //   results  k_umi_reads: per read the root's code; k_umi_insert and k_umi_cells count reads, reads with a UMI, distinct
 //            UMIs and molecules per cell, summed inside the wave before the atomic (wave_count: one hot cell is one address).
@@ -429,6 +429,110 @@ void k_group_emit(const unsigned long long* __restrict__ gkeys, const uint32_t* 
     }
 }
 
+// ---- parents at distance 2 (bdg_umi_set_max_dist) ----
+// The idx-th string one edit from the string of L letters x (idx counts 3 L substitutions, then L deletions, then 4 (L + 1)
+// insertions before letter p, p = L: at the end), as a code; L may be 0 (the empty string has its four insertions, code 0).
+// UMI_NONE where idx is past the last edit, where the string's length is outside lo .. hi, and where an earlier idx gives the
+// same string (k_umi_parent's rules: a deletion inside a run of equal letters, an insertion of the letter that follows).
+__device__ __forceinline__ uint32_t edit_at(uint32_t L, uint32_t x, uint32_t idx, uint32_t lo, uint32_t hi)
+{
+    if (idx < 3u * L) {
+        const uint32_t p = idx / 3u, sh = 2u * (L - 1u - p), b = (((x >> sh) & 3u) + 1u + (idx - 3u * p)) & 3u;
+        return L >= lo && L <= hi ? L << 28 | (x & ~(3u << sh)) | b << sh : UMI_NONE;
+    }
+    idx -= 3u * L;
+    if (idx < L) {
+        const uint32_t sh = 2u * (L - 1u - idx);
+        const bool again = idx > 0u && ((x >> sh) & 3u) == ((x >> (sh + 2u)) & 3u);
+        return L - 1u >= lo && L - 1u <= hi && !again ? (L - 1u) << 28 | (x >> (sh + 2u)) << sh | (x & ((1u << sh) - 1u)) : UMI_NONE;
+    }
+    idx -= L;
+    if (idx < 4u * (L + 1u) && L + 1u >= lo && L + 1u <= hi) {              // (hi <= MAX_LEN: sh + 2 <= 28)
+        const uint32_t p = idx >> 2, b = idx & 3u, sh = 2u * (L - p);
+        const bool again = p < L && ((x >> (sh - 2u)) & 3u) == b;
+        return again ? UMI_NONE : (L + 1u) << 28 | ((x >> sh) << 2 | b) << sh | (x & ((1u << sh) - 1u));
+    }
+    return UMI_NONE;
+}
+
+constexpr uint32_t PROBES2 = 4;                                           // probes of k_umi_parent2 a lane has in flight
+
+// k_umi_parent at distance 2 (bdg_umi_set_max_dist), the wave working together: the same par[] from the same
+// table.  A wave takes the occupied ones among its 64 slots in turn (a ballot; the slot's key and count are read from its
+// lane).  The lanes share out the strings one edit from the slot's UMI (edit_at over all lengths 0 .. 14: at most 8 * 14 + 4
+// = 116, two rounds of 64) - an intermediate may be outside the window, absent from the table, or empty; one of 15 letters is never
+// needed, since the two edits of a pair of usable UMIs can be ordered with a deletion first (include/badger_hip.h).  Every lane
+// then walks the strings one edit from its intermediate whose length is in the window, and the intermediate itself, and looks
+// them up in the table, PROBES2 at a time.  A lane with nothing to look up (no intermediate, idx past its edits, a length
+// outside the window, a string met before) looks up the slot's own key: the candidate test refuses it, as it refuses the UMI
+// itself when two edits lead back to it, so no load stands behind a divergent branch and the loops are the wave's.  The probes
+// end as find_or_claim's do (a table at most half full).  Candidates compete on n << 32 | ~code as in k_umi_parent - a maximum,
+// so a string met twice changes nothing; one wave maximum picks the parent and one lane stores it: the same in every run.
+__global__ __launch_bounds__(256)
+void k_umi_parent2(const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ cnt, uint32_t P, uint32_t mask,
+                   uint32_t lo_len, uint32_t hi_len, uint32_t* __restrict__ par)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t s_mine = blockIdx.x * 256u + threadIdx.x, first = s_mine - lane;
+    const unsigned long long k_mine = s_mine < P ? keys[s_mine] : EMPTY;
+    const uint32_t n_mine = s_mine < P ? cnt[s_mine] : 0u;
+    for (unsigned long long todo = __ballot(k_mine != EMPTY); todo; todo &= todo - 1ull) {
+        const int src = __ffsll(todo) - 1;
+        // (src is the wave's: a lane read, no shuffle)
+        const uint32_t code = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)k_mine, src), L = code >> 28, x = code & 0x0FFFFFFFu;
+        const unsigned long long cell = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(k_mine >> 32), src) << 32;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)n_mine, src), s = first + (uint32_t)src;
+        const uint32_t n_mid = 8u * L + 4u, n_end = 8u * (L < MAX_LEN ? L + 1u : L) + 5u;   // (the longest intermediate's strings, and itself)
+        unsigned long long best = 0;
+        uint32_t bslot = s;
+        for (uint32_t base = 0; base < n_mid; base += 64u) {
+            const uint32_t mid = edit_at(L, x, base + lane, 0u, MAX_LEN);
+            const uint32_t L1 = mid >> 28, x1 = mid & 0x0FFFFFFFu;
+            for (uint32_t j = 0; j < n_end; j += PROBES2) {
+                uint32_t c2[PROBES2], h[PROBES2];
+                unsigned long long k2[PROBES2], e[PROBES2];
+#pragma unroll
+                for (uint32_t u = 0; u < PROBES2; ++u) {
+                    uint32_t c = UMI_NONE;
+                    if (mid != UMI_NONE) c = j + u ? edit_at(L1, x1, j + u - 1u, lo_len, hi_len) : (L1 >= lo_len && L1 <= hi_len ? mid : UMI_NONE);
+                    c2[u] = c != UMI_NONE ? c : code;
+                    k2[u] = cell | c2[u];
+                    h[u] = slot_of(k2[u], mask);
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < PROBES2; ++u) e[u] = keys[h[u]];
+                for (;;) {                                               // the chains, all in step: a lane that is done reads its slot again
+                    bool open = false;
+#pragma unroll
+                    for (uint32_t u = 0; u < PROBES2; ++u) {
+                        const bool on = e[u] != EMPTY && e[u] != k2[u];
+                        h[u] = on ? (h[u] + 1u) & mask : h[u];
+                        open |= on;
+                    }
+                    if (!__any(open)) break;
+#pragma unroll
+                    for (uint32_t u = 0; u < PROBES2; ++u) e[u] = keys[h[u]];
+                }
+                bool found = false;
+#pragma unroll
+                for (uint32_t u = 0; u < PROBES2; ++u) found |= e[u] == k2[u] && c2[u] != code;
+                if (!__any(found)) continue;                             // (the wave's branch; most rounds find nothing)
+#pragma unroll
+                for (uint32_t u = 0; u < PROBES2; ++u) {
+                    const uint32_t m = cnt[h[u]];
+                    // a parent candidate, as in k_umi_parent
+                    if (e[u] == k2[u] && (unsigned long long)m + 1ull >= 2ull * n && (m > n || (m == n && c2[u] < code))) {
+                        const unsigned long long pr = (unsigned long long)m << 32 | (uint32_t)~c2[u];
+                        if (pr > best) { best = pr; bslot = h[u]; }
+                    }
+                }
+            }
+        }
+        const unsigned long long top = wave_max64(best);                  // (0: no candidate, every lane holds s)
+        if (lane == (uint32_t)__ffsll(__ballot(best == top)) - 1u) par[s] = bslot;
+    }
+}
+
 }  // namespace
 
 int bdg_cdna_len_launch(bdg_ctx* ctx, const bdg_trim_rec* d_trim, const bdg_chimera_rec* d_chim, uint32_t n, uint32_t* d_out)
@@ -497,7 +601,10 @@ static void umi_tail_launch(bdg_ctx* ctx, const UmiTable& T, uint64_t P, uint64_
 {
     hipStream_t st = ctx->stream;
     const uint32_t mask = (uint32_t)(P - 1), gp = (uint32_t)(P / 256), gn = (uint32_t)((n + 255) / 256);
-    {
+    if (umi_dist >= 2u) {                                                 // (only behind bdg_umi_set_max_dist: umi_check)
+        ScopedKernelTimer tm(ctx, "k_umi_parent2");
+        hipLaunchKernelGGL(k_umi_parent2, dim3(gp), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P, mask, w.lo, w.hi, T.par);
+    } else {
         ScopedKernelTimer tm(ctx, "k_umi_parent");
         hipLaunchKernelGGL(k_umi_parent, dim3(gp), dim3(256), 0, st, T.keys, T.cnt, (uint32_t)P, mask, w.lo, w.hi, umi_dist, T.par);
     }
@@ -512,9 +619,17 @@ static void umi_tail_launch(bdg_ctx* ctx, const UmiTable& T, uint64_t P, uint64_
 // the numbers every dedup entry point takes; `tables` names in the message what n reads would not fit
 static int umi_check(bdg_ctx* ctx, uint64_t n, uint32_t umi_len, uint32_t umi_dist, const char* tables)
 {
-    if (umi_dist > 1) return bdg_fail(ctx, BDG_E_ARG, "umi_dist must be 0 or 1");
+    if (umi_dist > ctx->u_max_dist) return bdg_fail(ctx, BDG_E_ARG, ctx->u_max_dist > 1u ? "umi_dist must be 0, 1 or 2" : "umi_dist must be 0 or 1");
     if (umi_len < 3 || umi_len > 12) return bdg_fail(ctx, BDG_E_ARG, "umi_len must be 3 .. 12 (usable lengths are at most 14)");
     if (!table_slots(n)) return bdg_fail(ctx, BDG_E_ARG, std::string("more reads than the ") + tables + " (2^30)");
+    return BDG_OK;
+}
+
+int bdg_umi_set_max_dist(bdg_ctx* ctx, uint32_t max_dist)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (max_dist != 1u && max_dist != BDG_UMI_MAX_DIST) return bdg_fail(ctx, BDG_E_ARG, "umi: the largest distance is 1 or 2");
+    ctx->u_max_dist = max_dist;
     return BDG_OK;
 }
 

@@ -4,7 +4,7 @@ that every read and molecule is compatible with.
 
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
-                               [--umi_per_gene --umi_len L [--gene_umi_dist 0|1]]
+                               [--umi_per_gene --umi_len L [--gene_umi_dist 0|1 | --gene_umi_dist2]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -34,6 +34,7 @@ checker is umi_dedup.dedup_per_gene and count_molecules_per_gene below; DESIGN 4
     molecule  its UMI is the UR text of its header, usable under umi_dedup.usable(UMI, umi_len).  Inside one group the rule is
               umi_dedup.cell_molecules as written; a molecule is (CB, feature, root UMI).  A read that takes part without a
               usable UMI is a molecule of its own; a read that is not ASSIGNED is in no molecule.
+              --gene_umi_dist2 takes the rule at distance 2 (bdg_umi_set_max_dist, k_umi_parent2).
     matrix    entry (feature, CB) = the group's roots plus its own-molecule reads.  With --isoforms a molecule's class is the
               AND of the compat sets of its reads: all of them are ASSIGNED to its feature by construction.
     files     gene_molecules.tsv: read, CB, feature, UR, molecule (the root UMI's text, '*' for a molecule of its own) per read
@@ -844,6 +845,15 @@ def device_assign(ctx, min_hits, margin=None):
     return run
 
 
+def device_dedup_genes(ctx):
+    """run of molecules_per_gene on the device: bdg_umi_dedup_genes, the context taking distance 2 only for the time of a run
+    that asks for it (the context is shared inside the process)"""
+    def run(cell, gene_recs, umi, umi_len, umi_dist):
+        with ctx.umi_max_dist_of(max(1, umi_dist)):
+            return ctx.umi_dedup_genes(cell, gene_recs, umi, umi_len, umi_dist)
+    return run
+
+
 def device_em(ctx):
     """run of em_run on the device: bdg_em_tcc"""
     def run(classes, prob_off, out_off, eps, max_iter, start):
@@ -870,7 +880,7 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
                                           (tx_names, feat) if iso_margin else None,
                                           (device_em(ctx),) + tuple(em) if iso_margin and em else None,
-                                          (ctx.umi_dedup_genes,) + tuple(per_gene) if per_gene else None)
+                                          (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
@@ -968,13 +978,18 @@ def gene_umi_len_arg(v):
 
 
 def check_per_gene_options(p, a, with_matrix):
-    """the errors of --umi_per_gene and --gene_umi_dist, the same on both command lines; sets a.gene_umi_dist to None without
-    --umi_per_gene, else to the distance"""
+    """the errors of --umi_per_gene, --gene_umi_dist and --gene_umi_dist2, the same on both command lines; sets a.gene_umi_dist
+    to None without --umi_per_gene, else to the distance (2 with --gene_umi_dist2)"""
     if a.gene_umi_dist is not None and not a.umi_per_gene:
         p.error("--gene_umi_dist needs --umi_per_gene")
+    if a.gene_umi_dist2 and not a.umi_per_gene:
+        p.error("--gene_umi_dist2 needs --umi_per_gene: two edits are only told from chance inside a (cell, gene) group")
+    if a.gene_umi_dist2 and a.gene_umi_dist is not None:
+        p.error("--gene_umi_dist2 may not be combined with --gene_umi_dist: it is the distance 2")
     if a.umi_per_gene and not with_matrix:
         p.error("--umi_per_gene needs --count_matrix: it makes the molecules that the matrix counts")
-    a.gene_umi_dist = (GENE_UMI_DIST_DEFAULT if a.gene_umi_dist is None else a.gene_umi_dist) if a.umi_per_gene else None
+    a.gene_umi_dist = (2 if a.gene_umi_dist2 else GENE_UMI_DIST_DEFAULT if a.gene_umi_dist is None else a.gene_umi_dist) \
+        if a.umi_per_gene else None
 
 
 def check_iso_options(p, a, with_matrix):
@@ -1017,6 +1032,9 @@ def add_gene_options(p):
                         "gene_molecules.tsv beside the matrix")
     p.add_argument("--gene_umi_dist", type=gene_umi_dist_arg, default=None, metavar="D",
                    help="--umi_per_gene: largest edit distance between two UMIs of one molecule, 0 or 1 (default %d)" % GENE_UMI_DIST_DEFAULT)
+    p.add_argument("--gene_umi_dist2", action="store_true",
+                   help="--umi_per_gene: UMIs of one (cell, gene) group up to Levenshtein distance 2 are neighbours (long reads "
+                        "carry two errors in a 12-letter UMI too often for distance 1); not with --gene_umi_dist")
     p.add_argument("--gene_k", type=gene_k_arg, default=None, metavar="K",
                    help="bases of a key of the gene lookup (default %d, 11 .. 31)" % K_DEFAULT)
     p.add_argument("--gene_min_hits", type=gene_min_hits_arg, default=None, metavar="H",

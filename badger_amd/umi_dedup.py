@@ -5,7 +5,9 @@ The rule
     input per read: its cell (the barcode stage 2 assigned it, '*' for none) and its UMI (the text of stage 1's UMI column).
     A UMI is usable when it holds only ACGT, its length is within umi_len +- 2 and the read has a cell; any other read has
     no UMI (not an error).
-    Inside one cell, two different usable UMIs are neighbours when their Levenshtein distance is at most umi_dist (0 or 1).
+    Inside one cell, two different usable UMIs are neighbours when their Levenshtein distance is at most umi_dist (0, 1 or
+    2; the device takes 2 behind bdg_umi_set_max_dist, and the command lines only inside (cell, gene): --gene_umi_dist2,
+    DESIGN §4.24).
     n(u) = reads of the cell carrying u.  UMIs are ordered by (length, then A < C < G < T); (n, u) ranks above (n', u') when
     n > n', or n == n' and u comes first in that order.
     a is a parent candidate of b when they are neighbours, n(a) >= 2 n(b) - 1 (UMI-tools' directional condition) and
@@ -105,24 +107,60 @@ def _deletions(u):
     return {u[:i] + u[i + 1:] for i in range(len(u))}
 
 
+def _deletions2(u):
+    """u without one letter and without two, every distinct string once"""
+    one = _deletions(u)
+    return one.union(*[_deletions(v) for v in one])
+
+
+def within(a, b, d):
+    """Levenshtein distance of a and b is at most d: behind their common prefix the first letters differ, and one edit takes
+    a letter off a (a deletion), off b (an insertion) or off both (a substitution)"""
+    if abs(len(a) - len(b)) > d:
+        return False
+    if d == 0:
+        return a == b
+    i, n = 0, min(len(a), len(b))
+    while i < n and a[i] == b[i]:
+        i += 1
+    if i == n:
+        return True                                 # (one is a prefix of the other: the lengths have said it)
+    return within(a[i + 1:], b[i + 1:], d - 1) or within(a[i + 1:], b[i:], d - 1) or within(a[i:], b[i + 1:], d - 1)
+
+
 def cell_molecules(counts, umi_dist=1):
     """counts: {umi: reads} of one cell -> {umi: representative umi}.  Neighbours at distance 1 meet through deletion
     variants: two strings of one length at Hamming distance 1 share the string left by deleting the differing letter, a
-    string and one with a letter more share the shorter string itself."""
+    string and one with a letter more share the shorter string itself.  At distance 2 the same with up to two letters deleted
+    (the columns of an alignment with at most two edits, taken out of both strings, leave one string), each pair that meets
+    held against the Levenshtein recurrence once."""
     def above(a, b):
         return counts[a] > counts[b] or (counts[a] == counts[b] and order_key(a) < order_key(b))
 
+    if umi_dist not in (0, 1, 2):
+        raise ValueError("umi_dist is 0, 1 or 2")
     best = {}
     if umi_dist >= 1:
+        variants = _deletions if umi_dist == 1 else _deletions2
+        known = {}
+
+        def near(a, b):
+            if umi_dist == 1:
+                return within_one(a, b)
+            key = (a, b) if a < b else (b, a)
+            if key not in known:
+                known[key] = within(a, b, 2)
+            return known[key]
+
         groups = defaultdict(list)
         for u in counts:
             groups[u].append(u)
-            for v in _deletions(u):
+            for v in variants(u):
                 groups[v].append(u)
         for members in groups.values():
             for a in members:
                 for b in members:
-                    if a == b or not within_one(a, b):
+                    if a == b or not near(a, b):
                         continue
                     # a candidate parent of b?
                     if counts[a] >= 2 * counts[b] - 1 and above(a, b):

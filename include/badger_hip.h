@@ -881,10 +881,24 @@ int  bdg_touched_count_dev(bdg_ctx* ctx, const uint32_t* d_ea, const uint32_t* d
  * <= umi_dist (0 or 1); a UMI's parent is its highest (count, smaller UMI) neighbour with count >= 2 * its count - 1 that
  * ranks above it, the root of its parent chain is its molecule.  Out: d_molecule [n] the molecule's UMI code per read
  * (0xFFFFFFFF: no usable UMI), d_cell_counts [n_cells][4] per cell: reads, reads with a usable UMI, distinct UMIs, molecules.
- * Works in an open-addressing table of 16 bytes per slot, two slots per read (held by the context).  Asynchronous. */
+ * Works in an open-addressing table of 16 bytes per slot, two slots per read (held by the context).  Asynchronous.
+ * DISTANCE 2.  Behind bdg_umi_set_max_dist(ctx, 2) umi_dist may also be 2, and nothing moves but the neighbour relation: two
+ * different usable UMIs of a cell are then neighbours at Levenshtein distance <= 2; the parent candidates, the best parent, the
+ * root, the usable lengths and the outputs are as above, and umi_dist 0 and 1 give what they give on a fresh context.  A pair at
+ * distance 2 whose UMIs are both usable (1 .. 14 letters) is always linked by an edit script whose intermediate string has at
+ * most 14 letters: the two edits touch independent positions and can be done in either order, so where one is an insertion and
+ * the other a deletion the deletion goes first (two insertions end at 14 letters or fewer, so pass 13 or fewer).  An intermediate
+ * of 15 letters is never formed.  The intermediate may lie outside the usable window on either side, may be absent from the
+ * table, and may be empty. */
 int  bdg_umi_dedup_dev(bdg_ctx* ctx, const uint32_t* d_rank, const uint8_t* d_has, const uint32_t* d_umi, uint64_t n,
                        const uint32_t* d_cells, uint32_t n_cells, uint32_t umi_len, uint32_t umi_dist,
                        uint32_t* d_molecule, uint32_t* d_cell_counts);
+#define BDG_UMI_MAX_DIST 2
+/* The largest umi_dist that bdg_umi_dedup_dev, bdg_umi_dedup_genes_dev and bdg_umi_dedup_genes take from here on: 1 (a fresh
+ * context: umi_dist 2 is BDG_E_ARG) or 2 (umi_dist 0, 1 or 2; 3 stays BDG_E_ARG).  BDG_E_ARG for any other value, the setting
+ * then stays.  Distance 2 is meant for the small groups of (cell, gene): among the thousands of UMIs of a whole cell a 12-letter
+ * UMI has chance neighbours two edits away. */
+int  bdg_umi_set_max_dist(bdg_ctx* ctx, uint32_t max_dist);
 /* One representative read per molecule, and every molecule's read count (the rule restated in badger_amd/molecule_reads.py;
  * integers only).  Per read i (0 <= i < n): d_rank / d_has its cell (bdg_assign_reads_dev), d_molecule its molecule's code
  * (bdg_umi_dedup_dev; 0xFFFFFFFF: none), d_cdna_len the cDNA bases bdg_format_trimmed_chimera would write for it (bdg_kept_cdna).
@@ -1071,7 +1085,10 @@ typedef struct { uint32_t feature, cell, molecules, umis, umi_reads, own; } bdg_
  * n <= 2^30.  A key already stored costs a load and no atomic; the lanes of a wave that name one group combine before one lane
  * probes and adds.  The kernels are asynchronous; the call then waits for the stream once to read the number of groups:
  * BDG_E_ARG (the message names the number needed, *d_n_groups holds it) when cap is smaller - no record is written past cap.
- * BDG_E_ARG also for umi_dist > 1, umi_len outside 3 .. 12, n > 2^30 and null pointers. */
+ * BDG_E_ARG also for umi_dist > 1, umi_len outside 3 .. 12, n > 2^30 and null pointers.
+ * DISTANCE 2.  Behind bdg_umi_set_max_dist(ctx, 2) umi_dist may also be 2 (3 stays BDG_E_ARG): the neighbours of the molecule
+ * clause are then the different usable UMIs of the group at Levenshtein distance <= 2, as stated at bdg_umi_dedup_dev with the
+ * note on the intermediate string; every other clause stays, and umi_dist 0 and 1 give what they give on a fresh context. */
 int  bdg_umi_dedup_genes_dev(bdg_ctx* ctx, const uint32_t* d_cell, const bdg_gene_rec* d_gene_recs, const uint32_t* d_umi, uint64_t n,
                              uint32_t umi_len, uint32_t umi_dist, uint32_t* d_molecule, bdg_gene_group_rec* d_groups, uint32_t cap,
                              uint32_t* d_n_groups);

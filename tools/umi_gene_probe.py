@@ -6,6 +6,13 @@
         UMIs already on the device; every molecule is given a gene drawn from 2,000, one read in twenty no gene): wall time per
         call (after a warm-up, synchronised, median of --reps) and the per-kernel split from the library's event timers, both
         calls in the same run; then one hot group holding every read, with and without the aggregation inside the wave.
+    python tools/umi_gene_probe.py --dist 2 [--reads 1000000,12500000] [--reps 3] --out profiles/r26_umi_dist2.jsonl
+        k_umi_parent2 beside k_umi_parent on the same workload in one run: bdg_umi_dedup_genes_dev and
+        bdg_umi_dedup_dev at umi_dist 1 and, behind bdg_umi_set_max_dist(2), at umi_dist 2 - wall time per call, the two parent
+        kernels' times from the library's event timers, and the molecules each distance finds.
+    python tools/umi_gene_probe.py --cli --dist 2 [--pairs 3] [--parent DIR] --out profiles/r26_umi_dist2.jsonl
+        the --cli pairs below with --umi_per_gene on every side: --gene_umi_dist2 against without, and with --parent this
+        build without the flag against the parent's, and the parent's against itself.
     python tools/umi_gene_probe.py --cli [--cli_reads 1000000] [--pairs 3] [--parent DIR] --out ...
         the stage-2 command line from FASTQ with --umi_dedup --tagged_reads --count_matrix, as alternating pairs of fresh
         processes: with --umi_per_gene against without; and, with --parent DIR (a built checkout of the parent commit), this
@@ -104,6 +111,42 @@ def device_probe(args):
             a.free()
 
 
+def dist2_probe(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for n in [int(x) for x in args.reads.split(",")]:
+        cells, rank, has, umi = synthetic(n)
+        cell = np.where(has != 0, np.searchsorted(cells, rank), 0xFFFFFFFF).astype(np.uint32)
+        recs = gene_records(n, umi)
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (cells, rank, has, umi, cell, recs)]
+        d_mol = _native.DeviceArray(ctx, n, np.uint32)
+        d_cnt = _native.DeviceArray(ctx, (len(cells), 4), np.uint32)
+        d_groups = _native.DeviceArray(ctx, n, _native.GENE_GROUP_DTYPE)
+        d_n = _native.DeviceArray(ctx, 1, np.uint32)
+        row = {"what": "k_umi_parent2 (umi_dist 2) beside k_umi_parent (umi_dist 1), device-resident", "reads": n,
+               "cells": int(len(cells)), "genes": N_GENES, "reps": args.reps}
+        with ctx.umi_max_dist_of(2):
+            for dist in (1, 2):
+                per_gene = lambda: ctx.umi_dedup_genes_dev(d[4], d[5], d[3], n, 12, dist, d_mol, d_groups, n, d_n)      # noqa: E731
+                per_cell = lambda: ctx.umi_dedup_dev(d[1], d[2], d[3], n, d[0], len(cells), 12, dist, d_mol, d_cnt)      # noqa: E731
+                tg, kg = _time(ctx, per_gene, args.reps)
+                groups = d_groups.to_host(int(d_n.to_host()[0]))
+                tc, kc = _time(ctx, per_cell, args.reps)
+                cnt = d_cnt.to_host()
+                kernel = "k_umi_parent2" if dist == 2 else "k_umi_parent"
+                row["dist%d" % dist] = {
+                    "per_gene_ms_median": round(1e3 * float(np.median(tg)), 4), "per_cell_ms_median": round(1e3 * float(np.median(tc)), 4),
+                    "per_gene_" + kernel + "_ms": kg.get(kernel), "per_cell_" + kernel + "_ms": kc.get(kernel),
+                    "per_gene_" + kernel + "_ms_per_1M_reads": round(kg.get(kernel, 0.0) * 1e6 / n, 4),
+                    "per_gene_kernel_ms": kg, "per_cell_kernel_ms": kc, "groups": int(len(groups)),
+                    "umis": int(groups["umis"].sum(dtype=np.int64)), "per_gene_molecules": int(groups["molecules"].sum(dtype=np.int64)),
+                    "per_cell_molecules": int(cnt[:, 3].sum())}
+        emit(args.out, row)
+        for a in d + [d_mol, d_cnt, d_groups, d_n]:
+            a.free()
+
+
 def cli_probe(args):
     from consensus_probe import _fastq
     from genes_probe import _transcripts_of
@@ -137,6 +180,14 @@ def cli_probe(args):
 
     matrix = ["--umi_dedup", "--tagged_reads", os.path.join(tmp, "tagged.fa"), "--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]
     run(ROOT, "warm", matrix)                                          # (the file into the page cache, the runtime's caches)
+    if args.dist == 2:                                                 # --gene_umi_dist2 against --umi_per_gene alone, and that against the parent's
+        per_gene, what = matrix + ["--umi_per_gene"], "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --umi_per_gene: "
+        pairs("umi_per_gene", (ROOT, per_gene), "gene_umi_dist2", (ROOT, per_gene + ["--gene_umi_dist2"]), what + "with --gene_umi_dist2 against without")
+        if args.parent:
+            parent = os.path.abspath(args.parent)
+            pairs("parent", (parent, per_gene), "flag_off", (ROOT, per_gene), what + "this build without --gene_umi_dist2 against the parent commit's")
+            pairs("parent_a", (parent, per_gene), "parent_b", (parent, per_gene), what + "the parent commit's build against itself")
+        return
     pairs("flag_off", (ROOT, matrix), "umi_per_gene", (ROOT, matrix + ["--umi_per_gene"]),
           "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix: with --umi_per_gene against without")
     if args.parent:
@@ -151,6 +202,7 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--device", action="store_true")
     p.add_argument("--cli", action="store_true")
+    p.add_argument("--dist", type=int, default=None, choices=(2,), help="time k_umi_parent2 beside k_umi_parent")
     p.add_argument("--reads", default="1000000,12500000")
     p.add_argument("--reps", type=int, default=10)
     p.add_argument("--cli_reads", type=int, default=1000000)
@@ -160,6 +212,8 @@ def main():
     args = p.parse_args()
     if args.device:
         device_probe(args)
+    if args.dist and not args.cli:
+        dist2_probe(args)
     if args.cli:
         cli_probe(args)
 
