@@ -60,6 +60,8 @@ GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
 ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("second", "<u4"), ("n_gene", "<u4"), ("flags", "<u4"),
                       ("pad", "<u4")])
 ISO_LOCAL_MAX, ISO_MARGIN_DEFAULT = 63, 1
+# bdg_cdna_span: an interval of a read, as it stands or reverse-complemented (bdg_genes_assign_spans; the rule in badger_amd/genes.py)
+SPAN_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("rc", "<u4")])
 ISO_UNIQUE, ISO_MULTI, ISO_NOGENE = 1, 2, 4
 # bdg_em_class / bdg_em_info: a class of an EM problem and what became of the problem (bdg_em_tcc; the rule in badger_amd/genes.py)
 EM_CLASS_DTYPE = np.dtype([("mask", "<u8"), ("count", "<u4"), ("pad", "<u4")])
@@ -103,6 +105,8 @@ EXPORTS = [
     "bdg_genes_index_build", "bdg_genes_index_stats", "bdg_genes_assign", "bdg_genes_assign_dev",
     "bdg_genes_index_build_iso", "bdg_iso_assign", "bdg_iso_assign_dev",
     "bdg_em_tcc", "bdg_em_tcc_dev",
+    "bdg_genes_assign_spans", "bdg_genes_assign_spans_dev", "bdg_iso_assign_spans_dev", "bdg_cdna_spans_dev", "bdg_extract_keep_genes",
+    "bdg_kept_genes",
     "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
 ]
 
@@ -381,6 +385,12 @@ def load():
     L.bdg_genes_index_build_iso.argtypes = [vp, vp, vp, u32, vp, vp, u32]
     L.bdg_iso_assign.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
     L.bdg_iso_assign_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_genes_assign_spans.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp]
+    L.bdg_genes_assign_spans_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_iso_assign_spans_dev.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp]
+    L.bdg_cdna_spans_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
+    L.bdg_extract_keep_genes.argtypes = [vp, C.c_int, u32, u32]
+    L.bdg_kept_genes.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     L.bdg_em_tcc.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
     L.bdg_em_tcc_dev.argtypes = [vp, vp, vp, u32, vp, vp, C.c_float, u32, vp, vp]
     L.bdg_consensus_set_band.argtypes = [vp, u32]
@@ -808,6 +818,45 @@ class Context:
         """bdg_iso_assign_dev: the compatible transcripts over device arrays and the gene records of the same reads, asynchronous"""
         self._check(self.lib.bdg_iso_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs), int(margin), _ptr(d_out)))
 
+    def genes_assign_spans(self, bases, off, spans, min_hits=GENES_MIN_HITS_DEFAULT, margin=0):
+        """the gene call of a span of every read over host arrays, spans SPAN_DTYPE [n] (bdg_genes_assign_spans) -> GENE_DTYPE [n];
+        with a margin the compatible transcripts too -> (GENE_DTYPE [n], ISO_DTYPE [n])"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        spans = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+        n = len(off) - 1
+        if len(spans) != n:
+            raise ValueError("a span per read")
+        gene, iso = np.zeros(n, dtype=GENE_DTYPE), np.zeros(n if margin else 0, dtype=ISO_DTYPE)
+        self._check(self.lib.bdg_genes_assign_spans(self.h, bases.ctypes.data, off.ctypes.data, n, spans.ctypes.data, int(min_hits),
+                                                    int(margin), gene.ctypes.data, iso.ctypes.data if margin else None))
+        return (gene, iso) if margin else gene
+
+    def genes_assign_spans_dev(self, d_bases, d_off, n, d_spans, min_hits, d_out):
+        """bdg_genes_assign_spans_dev: the gene call of a span of every read over device arrays, asynchronous"""
+        self._check(self.lib.bdg_genes_assign_spans_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_spans), int(min_hits), _ptr(d_out)))
+
+    def iso_assign_spans_dev(self, d_bases, d_off, n, d_spans, d_gene_recs, margin, d_out):
+        """bdg_iso_assign_spans_dev: the compatible transcripts of the same spans and their gene records, asynchronous"""
+        self._check(self.lib.bdg_iso_assign_spans_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_spans), _ptr(d_gene_recs),
+                                                      int(margin), _ptr(d_out)))
+
+    def cdna_spans_dev(self, d_off, n, d_recs, d_trim, d_chim, d_out):
+        """bdg_cdna_spans_dev: every read's span from its extraction, trim and (d_chim None: no search ran) chimera records"""
+        self._check(self.lib.bdg_cdna_spans_dev(self.h, _ptr(d_off), int(n), _ptr(d_recs), _ptr(d_trim),
+                                                None if d_chim is None else _ptr(d_chim), _ptr(d_out)))
+
+    def extract_keep_genes(self, on=True, min_hits=GENES_MIN_HITS_DEFAULT, margin=0):
+        """with the kept records, every read's gene record and with a margin its isoform record, from the chunk's bases on the
+        device (bdg_extract_keep_genes; only while the trim is on and an index is held)"""
+        self._check(self.lib.bdg_extract_keep_genes(self.h, 1 if on else 0, int(min_hits), int(margin)))
+
+    def kept_genes(self):
+        """-> (device pointer of the gene records, of the isoform records or 0, count)"""
+        g, i, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(self.lib.bdg_kept_genes(self.h, C.byref(g), C.byref(i), C.byref(n)))
+        return g.value or 0, i.value or 0, int(n.value)
+
     def em_tcc(self, classes, prob_off, out_off, eps=EM_EPS_DEFAULT, max_iter=EM_MAX_ITER_DEFAULT, start=None):
         """EM over the compatibility counts of every problem, host arrays (bdg_em_tcc): classes EM_CLASS_DTYPE, problem p the
         classes prob_off[p] .. prob_off[p + 1] - 1, its active lanes' values at out_off[p] onwards (start, if given, laid
@@ -833,6 +882,13 @@ class Context:
         self._check(self.lib.bdg_em_tcc_dev(self.h, _ptr(d_classes), _ptr(d_prob_off), int(n), _ptr(d_out_off),
                                             _ptr(d_start) if d_start is not None else None, float(eps), int(max_iter), _ptr(d_alpha),
                                             _ptr(d_info)))
+
+    def device_to_host(self, ptr, n, dtype):
+        """n elements of a device array the context holds (a kept array) as a numpy array; waits for the context's stream"""
+        out = np.zeros(n, dtype=dtype)
+        if n:
+            self._check(self.lib.bdg_mem_to_host(self.h, out.ctypes.data, ptr, out.nbytes))
+        return out
 
     def kept_records_to_host(self):
         """the kept records as a numpy array (synchronises)"""

@@ -10,6 +10,9 @@
                                 [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                 [--umi_per_gene [--gene_umi_dist 0|1 | --gene_umi_dist2]]
 
+    python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR --matrix_from_reads
+                                [--tagged_reads tagged.fa] [the options of --count_matrix]
+
 --umi_dedup adds what the reference does not have: the reads' molecules per cell (the rule of umi_dedup.py, on the device),
 <out>_molecules.tsv and <out>_cells.tsv.
 
@@ -35,6 +38,10 @@ isoform_em_matrix.mtx (transcripts x barcodes, abundances in molecules) and isof
 UMIs are collapsed inside (cell, gene) from the reads' UR, so the same UMI - or two UMIs one edit apart - in two genes of one cell
 are two molecules; gene_molecules.tsv in DIR names every read's molecule.  The tagged file, <out>_molecules.tsv and <out>_cells.tsv
 keep describing the molecules per cell.
+--matrix_from_reads writes the same DIR from the one pass over the reads: every read's gene (and isoform) call is made on the device
+from its cDNA where it lies in the read, while its chunk is there (genes.py MatrixFromReads).  --tagged_reads is then optional, and
+a tagged file is written as without the flag but not read back; without it the input is read once.  One column differs: the UR of
+gene_molecules.tsv is the text of the UMI code the device keeps, '*' for a UMI that is no ACGT string of 1 .. 14 letters.
 Every other output is the same bytes with and without these flags.
 
 -d tenX_5p_v2 / tenX_5p_v3 (read input): 10x 5' libraries.  Both passes over the reads put the context into the 5' layout
@@ -136,9 +143,15 @@ def parse_args(args):
                    help="--count_matrix: transcript sequences in mRNA sense (.gz is read through gzip)")
     p.add_argument("--tx2gene", type=str, default=None, metavar="TSV",
                    help="--count_matrix: transcript<TAB>gene per line, counts are per gene (without it per transcript name)")
+    p.add_argument("--matrix_from_reads", action="store_true", default=False,
+                   help="--count_matrix with --transcripts, read input only: call every read's gene during the one pass over the "
+                        "reads, from its cDNA where it lies in the read on the device; the same files in DIR, no tagged file is "
+                        "needed, and one written with --tagged_reads is not read back")
     add_gene_options(p)
     a = p.parse_args(args)
-    if a.count_matrix and not (a.tagged_reads and a.transcripts):
+    if a.matrix_from_reads and not (a.count_matrix and a.transcripts):
+        p.error("--matrix_from_reads needs --count_matrix and --transcripts: it is another way to that matrix")
+    if a.count_matrix and not a.matrix_from_reads and not (a.tagged_reads and a.transcripts):
         p.error("--count_matrix needs --tagged_reads and --transcripts: it looks the tagged reads up in the transcripts")
     if (a.transcripts or a.tx2gene or a.gene_k is not None or a.gene_min_hits is not None) and not a.count_matrix:
         p.error("--transcripts, --tx2gene, --gene_k and --gene_min_hits need --count_matrix")
@@ -150,10 +163,17 @@ def parse_args(args):
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
         p.error("--tagged_reads needs read input (FASTA, FASTQ, SAM or BAM): a stage-1 TSV does not hold the reads' bases")
-    if a.tso_min_score is not None and not a.tagged_reads:
+    if a.matrix_from_reads and a.reads.endswith("tsv"):
+        p.error("--matrix_from_reads needs read input (FASTA, FASTQ, SAM or BAM): a stage-1 TSV does not hold the reads' bases, "
+                "which the gene calls are made from")
+    if a.matrix_from_reads and a.molecule_reads:
+        p.error("--matrix_from_reads excludes --molecule_reads: the tagged file would hold one read per molecule and the matrix "
+                "would count other reads than it holds")
+    trims = a.tagged_reads or a.matrix_from_reads                 # what trims the reads: the trim's options go with either
+    if a.tso_min_score is not None and not trims:
         p.error("--tso_min_score needs --tagged_reads")
-    check_5p_args(p, a.data_type, a.tso5_max_ed, a.tso_min_score, a.tagged_reads, "--tagged_reads")
-    if a.chimera_cut and not a.tagged_reads:
+    check_5p_args(p, a.data_type, a.tso5_max_ed, a.tso_min_score, trims, "--tagged_reads")
+    if a.chimera_cut and not trims:
         p.error("--chimera_cut needs --tagged_reads")
     if a.chimera_max_ed is not None and not a.chimera_cut:
         p.error("--chimera_max_ed needs --chimera_cut")
@@ -245,7 +265,7 @@ def load_true_barcodes(path):
     return set(vals)
 
 
-def from_stage1_tsv(args, ctx, bc_len, mark):
+def from_stage1_tsv(args, ctx, bc_len, mark, matrix=None):
     """a stage-1 TSV: its observed barcodes go to the device as records (bdg_keep_observed), the UMI codes beside them; from there
     on the route is that of read input.  -> (read ids, nothing for a second pass)"""
     if args.umi_dedup:
@@ -261,17 +281,20 @@ def from_stage1_tsv(args, ctx, bc_len, mark):
     return read_ids, None
 
 
-def from_reads(args, ctx, bc_len, mark):
+def from_reads(args, ctx, bc_len, mark, matrix=None):
     """FASTA / FASTQ / SAM / BAM: the records of every chunk stay on the device (stage 1 -> stage 2 hand-off without host strings),
     the host only gets the read ids.  Like the reference (:112-117) one thread keeps every SAM / BAM record, several skip secondary /
     supplementary ones.  -> (read ids, the detector whose layout and UMI length the second pass takes again)"""
     detector = BARCODE_CALLING_MODES[args.data_type](device=args.device)
     # --tagged_reads with molecules: every chunk is trimmed (and searched for chimeras) here too, and only its reads' cDNA
     # lengths stay, for the election of each molecule's read; the bases come back in the second pass
+    # --matrix_from_reads: likewise, and every read's gene call is made from its bases while the chunk is on the device
     trimming = (context_trimming(ctx, args.tso_min_score, args.chimera_max_ed, keep_cdna=True)
-                if args.tagged_reads and args.umi_dedup else nullcontext())
+                if matrix or (args.tagged_reads and args.umi_dedup) else nullcontext())
     read_ids = _native.IdStore()
     with contexts_in_layout([detector], args.tso5_max_ed), trimming:
+        if matrix:
+            matrix.keep()                                 # (goes off with the trim)
         logger.info("Extracting from " + args.reads)
         # (-tr 1 is one sequential reader, compressed input as one gzip stream - the reference's single-thread shape,
         # as extract_raw_barcodes.process_single_thread asks for it)
@@ -318,6 +341,18 @@ def write_count_matrix(args):
     log_counts(counts, args.count_matrix)
 
 
+def write_matrix_from_reads(args, matrix, st2, ctx, read_ids):
+    """--matrix_from_reads, behind the cell and molecule calls and while the context still keeps the pass's arrays"""
+    from .genes import log_counts
+    from .umi_dedup import UMI_LEN
+    cells, mol = st2.read_cells(), st2.read_molecules()
+    ptr, n = ctx.kept_cdna()
+    counts = matrix.write(args.count_matrix, read_ids, cells.rank, cells.got, mol.mol if mol is not None else None,
+                          ctx.kept_umis_to_host() if args.umi_per_gene else None, ctx.device_to_host(ptr, n, "<u4"), args.em,
+                          (UMI_LEN[args.data_type], args.gene_umi_dist) if args.umi_per_gene else None)
+    log_counts(counts, args.count_matrix)
+
+
 def main(args):
     t_marks = [("start", time.perf_counter())]
 
@@ -359,10 +394,15 @@ def main(args):
         sys.exit(-1)
     st2 = Stage2(args.threshold, device=args.device)
     ctx = _native.default_context(args.device)      # shared inside the process: whatever happens below, it is left as it was found
+    matrix = None
     try:
+        if args.matrix_from_reads:                  # the transcripts' table is on the device before the one pass over the reads
+            from .genes import MatrixFromReads
+            matrix = MatrixFromReads(ctx, args.transcripts, args.tx2gene, args.gene_k, args.gene_min_hits, args.iso_margin)
+            mark("gene_index")
         # both routes leave the reads' records on the device: counting, edges, clustering and the per-read assignment run there
-        with context_keeping(ctx, umis=args.umi_dedup):
-            read_ids, detector = route(args, ctx, bc_len, mark)
+        with context_keeping(ctx, umis=args.umi_dedup or (matrix is not None and args.umi_per_gene)):
+            read_ids, detector = route(args, ctx, bc_len, mark, matrix)
             st2.count_device(ctx)
             mark("count")
             st2.build_edges(ctx, gpus=edge_build_gpus(args))
@@ -378,18 +418,25 @@ def main(args):
                 mark("umi_dedup")
                 logger.info("Molecules: %d" % molecules)
             tags = st2.read_tags_from_device(args.molecule_reads) if args.tagged_reads else None
+            if matrix:
+                write_matrix_from_reads(args, matrix, st2, ctx, read_ids)
+                mark("count_matrix")
         if args.tagged_reads:
             write_tagged_reads(args, detector, tags)
             mark("tagged_reads")
             if args.molecule_consensus:
                 write_molecule_consensus(args)
                 mark("molecule_consensus")
-            if args.count_matrix:
+            if args.count_matrix and not matrix:
                 write_count_matrix(args)
                 mark("count_matrix")
         disconnected = st2.disconnected()  # (counted where the edges are, before they are given back)
     finally:
-        st2.release_device()
+        try:
+            st2.release_device()
+        finally:
+            if matrix:
+                matrix.close()
     mark("output")
     print(disconnected)                # "disconnected" count (reference :131-132)
     timing = os.environ.get("BADGER_AMD_STAGE2_TIMING")

@@ -509,6 +509,23 @@ int bdg_extract_collect(bdg_ctx* ctx, uint32_t slot, bdg_extract_rec* out)
                 return rc;
             ctx->kept_cdna.n += sl.n;
         }
+        if (ctx->kept_gene.on) {
+            // the chunk's gene (and isoform) records, from its bases while they are still in the slot and the records of the pass
+            // that counted; the pieces' offsets of a split chunk
+            if (!sl.trim_on) return bdg_fail(ctx, BDG_E_ARG, "gene records are kept but the slot's chunk was submitted without a trim");
+            const uint32_t margin = ctx->kept_gene_margin;
+            if ((rc = bdg_genes_keep_check(ctx, ctx->kept_gene_min_hits, margin))) return rc;
+            void* at_iso = nullptr;
+            if ((rc = kept_append(ctx, ctx->kept_gene, sizeof(bdg_gene_rec), sl.n, size_t(32) << 20, &at))) return rc;
+            if (margin && (rc = kept_append(ctx, ctx->kept_iso, sizeof(bdg_iso_rec), sl.n, size_t(32) << 20, &at_iso))) return rc;
+            if ((rc = bdg_genes_kept_launch(ctx, static_cast<const uint8_t*>(sl.d_bases.p), slot_off(sl), sl.n, d_recs,
+                                            static_cast<const bdg_trim_rec*>(sl.trim.d.p),
+                                            sl.chim_on ? static_cast<const bdg_chimera_rec*>(sl.chim.d.p) : nullptr,
+                                            ctx->kept_gene_min_hits, margin, static_cast<bdg_gene_rec*>(at), static_cast<bdg_iso_rec*>(at_iso))))
+                return rc;
+            ctx->kept_gene.n += sl.n;
+            if (margin) ctx->kept_iso.n += sl.n;
+        }
         ctx->kept_recs.n += sl.n;
     }
     return BDG_OK;
@@ -521,7 +538,7 @@ int bdg_extract_set_trim(bdg_ctx* ctx, int on, uint32_t tso_min_score)
     if (on) if (int rcs = check_tso_min_score(ctx, tso_min_score)) return rcs;
     ctx->trim_on = on != 0;
     ctx->trim_min_score = on ? tso_min_score : 0;
-    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; ctx->kept_cdna.on = false; }   // (nothing to search or to measure without the trim)
+    if (!on) { ctx->chim_on = false; ctx->chim_max_ed = 0; ctx->kept_cdna.on = ctx->kept_gene.on = false; }   // (nothing to search, measure or call without the trim)
     return BDG_OK;
 }
 
@@ -724,8 +741,8 @@ int bdg_extract_keep_records(bdg_ctx* ctx, int on)
 {
     if (!ctx) return BDG_E_ARG;
     kept_set(ctx->kept_recs, on);
-    ctx->kept_umis.n = ctx->kept_cdna.n = 0;
-    if (!on) for (bdg_ctx::Kept* k : { &ctx->kept_recs, &ctx->kept_umis, &ctx->kept_cdna }) if (k->b.p) {
+    ctx->kept_umis.n = ctx->kept_cdna.n = ctx->kept_gene.n = ctx->kept_iso.n = 0;
+    if (!on) for (bdg_ctx::Kept* k : { &ctx->kept_recs, &ctx->kept_umis, &ctx->kept_cdna, &ctx->kept_gene, &ctx->kept_iso }) if (k->b.p) {
         BDG_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         k->b.reset();
     }
@@ -744,6 +761,29 @@ int bdg_extract_keep_cdna(bdg_ctx* ctx, int on)
     if (!ctx) return BDG_E_ARG;
     if (on && !ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "cDNA lengths need the trim (bdg_extract_set_trim)");
     kept_set(ctx->kept_cdna, on);
+    return BDG_OK;
+}
+
+int bdg_extract_keep_genes(bdg_ctx* ctx, int on, uint32_t min_hits, uint32_t margin)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (on) {
+        if (int rc = bdg_genes_keep_check(ctx, min_hits, margin)) return rc;
+        if (!ctx->trim_on) return bdg_fail(ctx, BDG_E_ARG, "gene records need the trim (bdg_extract_set_trim)");
+    }
+    kept_set(ctx->kept_gene, on);
+    ctx->kept_iso.n = 0;
+    ctx->kept_gene_min_hits = on ? min_hits : 0;
+    ctx->kept_gene_margin = on ? margin : 0;
+    return BDG_OK;
+}
+
+int bdg_kept_genes(bdg_ctx* ctx, const bdg_gene_rec** d_gene, const bdg_iso_rec** d_iso, uint64_t* n)
+{
+    if (!ctx || !d_gene || !d_iso || !n) return BDG_E_ARG;
+    *d_gene = static_cast<const bdg_gene_rec*>(ctx->kept_gene.b.p);
+    *d_iso = ctx->kept_gene_margin ? static_cast<const bdg_iso_rec*>(ctx->kept_iso.b.p) : nullptr;
+    *n = ctx->kept_gene.n;
     return BDG_OK;
 }
 

@@ -132,6 +132,10 @@ struct bdg_ctx {
     // them every read's UMI packed into 32 bits (bdg_extract_keep_umis, umi_kernels.hip) and, only while trim_on, every read's
     // cDNA length from the chunk's trim and chimera records (bdg_extract_keep_cdna)
     struct Kept { bool on = false; DevBuf b; uint64_t n = 0; } kept_recs, kept_umis, kept_cdna;
+    // ... and, only while trim_on and an index is held, every read's gene record (and with a margin its isoform record) from the
+    // chunk's bases in the slot (bdg_extract_keep_genes; kept_gene.on covers both)
+    Kept kept_gene, kept_iso;
+    uint32_t kept_gene_min_hits = 0, kept_gene_margin = 0;
     DevBuf u_ws;         // the tables of umi_kernels.hip, laid out by its umi_table() and mol_table(); every call clears what it uses
     bool mol_aggregate = true;               // bdg_molecule_reps_set_aggregate
     bool gene_aggregate = true;              // bdg_umi_dedup_genes_set_aggregate
@@ -152,6 +156,8 @@ struct bdg_ctx {
     int gn_cus = 0, gn_assign_per_cu = 0;    // compute units, and blocks of k_genes_assign resident on one (asked once)
     DevBuf gn_mask;      // u64 per slot: the transcripts of its gene that hold the slot's key (bdg_genes_index_build_iso only)
     int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
+    int gn_assign_sp_per_cu = 0, gn_iso_sp_per_cu = 0;   // the same of k_genes_assign_spans and k_iso_assign_spans
+    DevBuf gn_spans;     // the spans of the chunk bdg_extract_collect computes kept gene records for (grow-only)
     int em_cus = 0, em_per_cu = 0;           // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)

@@ -43,6 +43,10 @@ int bdg_touched_count_launch(bdg_ctx*, const uint32_t*, const uint32_t*, uint64_
 // umi_kernels.hip (which also holds the entry points of its tables: the bdg_umi_dedup*, bdg_molecule_reps* family)
 int bdg_umi_pack_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t*);
 int bdg_cdna_len_launch(bdg_ctx*, const bdg_trim_rec*, const bdg_chimera_rec*, uint32_t, uint32_t*);
+// genes_kernels.hip: the kept gene (and, with a margin, isoform) records of a chunk from its bases and records
+int bdg_genes_keep_check(bdg_ctx*, uint32_t min_hits, uint32_t margin);
+int bdg_genes_kept_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, const bdg_extract_rec*, const bdg_trim_rec*, const bdg_chimera_rec*,
+                          uint32_t min_hits, uint32_t margin, bdg_gene_rec*, bdg_iso_rec*);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // trim5p_kernels.hip

@@ -24,6 +24,9 @@
 // k_genes_stats    the table's occupancy figures, none of which depends on the order of insertion.
 // k_iso_insert, k_iso_assign   the transcripts of its gene that hold a key, and a read's counts of them: below,
 //                  behind the gene kernels whose planes, keys and probe they share.
+// k_genes_assign_spans, k_iso_assign_spans   the two assign kernels over an interval of every read, as it stands or
+//                  reverse-complemented: the same bodies, only the byte a lane loads differs.  k_cdna_spans makes
+//                  the intervals from a chunk's extraction, trim and chimera records.
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
 
@@ -37,7 +40,8 @@ constexpr uint32_t GENES_CHUNKS = 4;                         // chunks of 64 win
 constexpr uint32_t INSERT_WAVES_PER_CU = 16;                  // (k_genes_assign: as many as the device keeps resident, asked once)
 
 struct __align__(16) GeneSlot { unsigned long long key; uint32_t value, pad; };
-static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24 && sizeof(bdg_iso_rec) == 32, "layouts the header states");
+static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24 && sizeof(bdg_iso_rec) == 32 && sizeof(bdg_cdna_span) == 12,
+              "layouts the header states");
 
 struct Planes { uint64_t lo, hi, nv; };
 
@@ -68,6 +72,46 @@ __device__ __forceinline__ Planes load_planes(const uint8_t* s, uint64_t len, ui
 {
     return planes_of(load_byte(s, len, p0, lane));
 }
+
+// Where the 64 bytes of a chunk come from, for the probe below.  Whole: the sequence as it lies, off[r] .. off[r + 1].  Span: an
+// interval of it, as it stands or reverse-complemented (include/badger_hip.h at bdg_cdna_span) - position p is the
+// byte begin + p, or under rc the byte end - 1 - p, whose code is complemented where the planes are made: 3 - code is both code
+// bits flipped, two scalar operations on wave-uniform planes.  Descending addresses inside a wave are one line like ascending
+// ones; a position behind the span's end is N, so nothing outside the span is read.
+struct Whole {
+    const uint8_t* s; uint64_t len;
+    static __device__ __forceinline__ Whole of(const uint8_t* bases, const uint64_t* off, const bdg_cdna_span*, uint32_t r)
+    {
+        const uint64_t b = off[r], e = off[r + 1];
+        return Whole{ bases + b, e > b ? e - b : 0 };
+    }
+    __device__ __forceinline__ uint32_t byte(uint64_t p0, uint32_t lane) const { return load_byte(s, len, p0, lane); }
+    __device__ __forceinline__ Planes planes(uint32_t b) const { return planes_of(b); }
+};
+
+struct Span {
+    const uint8_t* first; uint64_t len; bool rc;                   // first: the byte of position 0
+    static __device__ __forceinline__ Span of(const uint8_t* bases, const uint64_t* off, const bdg_cdna_span* spans, uint32_t r)
+    {
+        const uint64_t b = off[r], e = off[r + 1];
+        const int64_t L = e > b ? (int64_t)(e - b) : 0;
+        const bdg_cdna_span sp = spans[r];
+        const int64_t lo = min(max((int64_t)sp.begin, (int64_t)0), L), hi = min(max((int64_t)sp.end, (int64_t)0), L);
+        const bool rc = sp.rc != 0;
+        return Span{ bases + b + (rc ? hi - 1 : lo), hi > lo ? (uint64_t)(hi - lo) : 0, rc };
+    }
+    __device__ __forceinline__ uint32_t byte(uint64_t p0, uint32_t lane) const
+    {
+        const uint64_t p = p0 + lane;
+        return p < len ? first[rc ? -(int64_t)p : (int64_t)p] : (uint32_t)'N';
+    }
+    __device__ __forceinline__ Planes planes(uint32_t b) const
+    {
+        Planes P = planes_of(b);
+        if (rc) { P.lo = ~(P.lo | P.nv); P.hi = ~(P.hi | P.nv); }
+        return P;
+    }
+};
 
 // bits lane .. lane + 31 of the 128 bits a1 : a0
 __device__ __forceinline__ uint32_t window32(uint64_t a0, uint64_t a1, uint32_t lane)
@@ -173,7 +217,8 @@ void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t 
     }
 }
 
-// The probe of GENES_CHUNKS x 64 windows, stated once for k_genes_assign and k_iso_assign.  It declares, in the caller's scope,
+// The probe of GENES_CHUNKS x 64 windows, stated once for k_genes_assign and k_iso_assign and their span forms (rd: a Whole or
+// a Span).  It declares, in the caller's scope,
 // key[c] (this lane's key of chunk c, KEY_EMPTY: none), got[c] (the slot its chain ends at: its key's, or an empty one) and
 // sl[c] (that slot's index).  Every first probe is on its way before one is looked at (a lane without a key reads slot 0 and
 // drops it: no branch around a load and no arithmetic between two of them).  The chains: a window whose home slot holds
@@ -182,13 +227,13 @@ void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t 
 // slot 0 and drops it.  A macro and not a function: through an inlined function's array references the same statements cost
 // k_genes_assign 8 VGPRs more (84, a resident wave per SIMD fewer); as a macro its code is what it was, instruction for
 // instruction.
-#define GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)                                                                      \
+#define GENES_PROBE_CHUNKS(rd, p0, lane, kmask, table, mask, shift)                                                                          \
     uint32_t byte[GENES_CHUNKS + 1];                                                                                                     \
     Planes P[GENES_CHUNKS + 1];                                                                                                          \
     _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = load_byte(s, len, p0 + 64 * c, lane);                                         \
+    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = rd.byte(p0 + 64 * c, lane);                                                   \
     _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = planes_of(byte[c]);                                                              \
+    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = rd.planes(byte[c]);                                                              \
     unsigned long long key[GENES_CHUNKS];                                                                                                \
     ulonglong2 got[GENES_CHUNKS];                                                                                                        \
     _Pragma("unroll")                                                                                                                    \
@@ -218,81 +263,97 @@ void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t 
         }                                                                                                                                \
     }
 
+// The body of k_genes_assign (READ = Whole) and k_genes_assign_spans (READ = Span), stated once.  A macro and not an inlined
+// function template, for GENES_PROBE_CHUNKS' reason: called through a forceinline function the forward kernel comes out of the
+// compiler with another schedule (13 instructions fewer, the same registers); stamped into the kernel it is the parent's code,
+// instruction for instruction.  It names the kernel's parameters bases, off, spans, n, k, min_hits, table, mask,
+// shift and out.
+#define GENES_ASSIGN_BODY(READ)                                                                                                             \
+    __shared__ uint32_t t_feat[BDG_GENES_MAX_FEATURES], t_cnt[BDG_GENES_MAX_FEATURES];                                                      \
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;                                                                              \
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {                                                                                  \
+        const READ rd = READ::of(bases, off, spans, r);                                                                                     \
+        uint32_t n_ent = 0, n_keys = 0, n_found = 0;                                                                                        \
+        bool crowded = false;                                                                                                               \
+        for (uint64_t p0 = 0; p0 + k <= rd.len; p0 += 64 * GENES_CHUNKS) {                                                                  \
+            GENES_PROBE_CHUNKS(rd, p0, lane, kmask, table, mask, shift)                                                                     \
+            _Pragma("unroll")                                                                                                               \
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                   \
+                const bool has_key = key[c] != KEY_EMPTY;                                                                                   \
+                const ulonglong2 g = got[c];                                                                                                \
+                const bool found = has_key && g.x == key[c];                                                                                \
+                const uint32_t val = found ? (uint32_t)g.y : BDG_GENES_NONE;                                                                \
+                n_keys += __popcll(__ballot(has_key));                                                                                      \
+                n_found += __popcll(__ballot(found));                                                                                       \
+                uint64_t live = crowded ? 0 : __ballot(val < BDG_GENES_AMBIGUOUS);                                                          \
+                while (live) {   /* one round per distinct feature among the 64 values */                                                   \
+                    const uint32_t f = __shfl(val, __ffsll((unsigned long long)live) - 1);                                                  \
+                    const uint64_t same = __ballot(val == f);                                                                               \
+                    const uint32_t cnt = __popcll(same);                                                                                    \
+                    live &= ~same;                                                                                                          \
+                    bool mine = false;                                                                                                      \
+                    uint32_t at = 0;                                                                                                        \
+                    for (uint32_t i = lane; i < n_ent; i += 64)                                                                             \
+                        if (t_feat[i] == f) { mine = true; at = i; }                                                                        \
+                    if (__ballot(mine)) {                                                                                                   \
+                        if (mine) t_cnt[at] += cnt;                                                                                         \
+                    } else if (n_ent < BDG_GENES_MAX_FEATURES) {                                                                            \
+                        if (lane == 0) { t_feat[n_ent] = f; t_cnt[n_ent] = cnt; }                                                           \
+                        ++n_ent;                                                                                                            \
+                    } else {                                                                                                                \
+                        crowded = true;                                                                                                     \
+                        live = 0;                                                                                                           \
+                    }                                                                                                                       \
+                    __syncthreads();   /* (a block is one wave: this orders the LDS traffic) */                                             \
+                }                                                                                                                           \
+            }                                                                                                                               \
+        }                                                                                                                                   \
+        /* the largest count, the smallest feature at a tie; then the largest count of the others */                                        \
+        uint32_t hits = 0, feature = BDG_GENES_NONE;                                                                                        \
+        for (uint32_t i = lane; i < n_ent; i += 64) {                                                                                       \
+            const uint32_t c = t_cnt[i], f = t_feat[i];                                                                                     \
+            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }                                                          \
+        }                                                                                                                                   \
+        _Pragma("unroll")                                                                                                                   \
+        for (uint32_t d = 32; d; d >>= 1) {                                                                                                 \
+            const uint32_t c = __shfl_xor(hits, d), f = __shfl_xor(feature, d);                                                             \
+            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }                                                          \
+        }                                                                                                                                   \
+        uint32_t second = 0;                                                                                                                \
+        for (uint32_t i = lane; i < n_ent; i += 64)                                                                                         \
+            if (t_feat[i] != feature) second = max(second, t_cnt[i]);                                                                       \
+        _Pragma("unroll")                                                                                                                   \
+        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));                                            \
+        __syncthreads();   /* the table is read: the next read may fill it */                                                               \
+        if (lane == 0) {                                                                                                                    \
+            bdg_gene_rec rec;                                                                                                               \
+            rec.n_keys = n_keys;                                                                                                            \
+            rec.n_found = n_found;                                                                                                          \
+            if (crowded) {                                                                                                                  \
+                rec.feature = BDG_GENES_NONE; rec.hits = 0; rec.second = 0; rec.flags = BDG_GENE_CROWDED;                                   \
+            } else {                                                                                                                        \
+                rec.feature = feature; rec.hits = hits; rec.second = second;                                                                \
+                rec.flags = (hits >= min_hits && hits > second) ? BDG_GENE_ASSIGNED                                                         \
+                          : (hits < min_hits ? BDG_GENE_LOW : 0u) | (hits == second && second > 0 ? BDG_GENE_TIE : 0u);                     \
+            }                                                                                                                               \
+            out[r] = rec;                                                                                                                   \
+        }                                                                                                                                   \
+    }
+
 __global__ __launch_bounds__(64)
 void k_genes_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k, uint32_t min_hits,
                     const GeneSlot* __restrict__ table, uint64_t mask, uint32_t shift, bdg_gene_rec* __restrict__ out)
 {
-    __shared__ uint32_t t_feat[BDG_GENES_MAX_FEATURES], t_cnt[BDG_GENES_MAX_FEATURES];
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
-        const uint64_t b = off[r], e = off[r + 1], len = e > b ? e - b : 0;
-        const uint8_t* s = bases + b;
-        uint32_t n_ent = 0, n_keys = 0, n_found = 0;
-        bool crowded = false;
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64 * GENES_CHUNKS) {
-            GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
-                const bool has_key = key[c] != KEY_EMPTY;
-                const ulonglong2 g = got[c];
-                const bool found = has_key && g.x == key[c];
-                const uint32_t val = found ? (uint32_t)g.y : BDG_GENES_NONE;
-                n_keys += __popcll(__ballot(has_key));
-                n_found += __popcll(__ballot(found));
-                uint64_t live = crowded ? 0 : __ballot(val < BDG_GENES_AMBIGUOUS);
-                while (live) {                                      // one round per distinct feature among the 64 values
-                    const uint32_t f = __shfl(val, __ffsll((unsigned long long)live) - 1);
-                    const uint64_t same = __ballot(val == f);
-                    const uint32_t cnt = __popcll(same);
-                    live &= ~same;
-                    bool mine = false;
-                    uint32_t at = 0;
-                    for (uint32_t i = lane; i < n_ent; i += 64)
-                        if (t_feat[i] == f) { mine = true; at = i; }
-                    if (__ballot(mine)) {
-                        if (mine) t_cnt[at] += cnt;
-                    } else if (n_ent < BDG_GENES_MAX_FEATURES) {
-                        if (lane == 0) { t_feat[n_ent] = f; t_cnt[n_ent] = cnt; }
-                        ++n_ent;
-                    } else {
-                        crowded = true;
-                        live = 0;
-                    }
-                    __syncthreads();                                // (a block is one wave: this orders the LDS traffic)
-                }
-            }
-        }
-        // the largest count, the smallest feature at a tie; then the largest count of the others
-        uint32_t hits = 0, feature = BDG_GENES_NONE;
-        for (uint32_t i = lane; i < n_ent; i += 64) {
-            const uint32_t c = t_cnt[i], f = t_feat[i];
-            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }
-        }
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) {
-            const uint32_t c = __shfl_xor(hits, d), f = __shfl_xor(feature, d);
-            if (c > hits || (c == hits && f < feature)) { hits = c; feature = f; }
-        }
-        uint32_t second = 0;
-        for (uint32_t i = lane; i < n_ent; i += 64)
-            if (t_feat[i] != feature) second = max(second, t_cnt[i]);
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));
-        __syncthreads();                                            // the table is read: the next read may fill it
-        if (lane == 0) {
-            bdg_gene_rec rec;
-            rec.n_keys = n_keys;
-            rec.n_found = n_found;
-            if (crowded) {
-                rec.feature = BDG_GENES_NONE; rec.hits = 0; rec.second = 0; rec.flags = BDG_GENE_CROWDED;
-            } else {
-                rec.feature = feature; rec.hits = hits; rec.second = second;
-                rec.flags = (hits >= min_hits && hits > second) ? BDG_GENE_ASSIGNED
-                          : (hits < min_hits ? BDG_GENE_LOW : 0u) | (hits == second && second > 0 ? BDG_GENE_TIE : 0u);
-            }
-            out[r] = rec;
-        }
-    }
+    constexpr const bdg_cdna_span* spans = nullptr;
+    GENES_ASSIGN_BODY(Whole)
+}
+
+__global__ __launch_bounds__(64)
+void k_genes_assign_spans(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, const bdg_cdna_span* __restrict__ spans,
+                          uint32_t n, uint32_t k, uint32_t min_hits, const GeneSlot* __restrict__ table, uint64_t mask, uint32_t shift,
+                          bdg_gene_rec* __restrict__ out)
+{
+    GENES_ASSIGN_BODY(Span)
 }
 
 // ---- transcript compatibility (include/badger_hip.h at bdg_genes_index_build_iso states the rule) ----
@@ -342,61 +403,100 @@ void k_iso_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict_
     }
 }
 
+// The body of k_iso_assign (READ = Whole) and k_iso_assign_spans (READ = Span), a macro for the same reason.  It names the
+// kernel's parameters bases, off, spans, n, k, genes, margin, table, tx_mask, mask, shift and out.
+#define ISO_ASSIGN_BODY(READ)                                                                                                                  \
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;                                                                                 \
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {                                                                                     \
+        const uint32_t f = genes[r].feature;                                                                                                   \
+        if (!(genes[r].flags & BDG_GENE_ASSIGNED)) {   /* none of its bases is read */                                                         \
+            if (lane == 0) {                                                                                                                   \
+                bdg_iso_rec rec;                                                                                                               \
+                rec.compat = 0; rec.feature = BDG_GENES_NONE; rec.best = rec.second = rec.n_gene = 0; rec.flags = BDG_ISO_NOGENE; rec.pad = 0; \
+                out[r] = rec;                                                                                                                  \
+            }                                                                                                                                  \
+            continue;                                                                                                                          \
+        }                                                                                                                                      \
+        const READ rd = READ::of(bases, off, spans, r);                                                                                        \
+        uint32_t cnt = 0, n_gene = 0;   /* cnt: of the transcript whose local index is this lane */                                            \
+        for (uint64_t p0 = 0; p0 + k <= rd.len; p0 += 64 * GENES_CHUNKS) {                                                                     \
+            GENES_PROBE_CHUNKS(rd, p0, lane, kmask, table, mask, shift)                                                                        \
+            bool hit[GENES_CHUNKS];                                                                                                            \
+            unsigned long long m[GENES_CHUNKS];                                                                                                \
+            _Pragma("unroll")                                                                                                                  \
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) hit[c] = key[c] != KEY_EMPTY && got[c].x == key[c] && (uint32_t)got[c].y == f;         \
+            _Pragma("unroll")                                                                                                                  \
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) m[c] = tx_mask[hit[c] ? sl[c] : 0];   /* (a lane without a hit drops it) */            \
+            _Pragma("unroll")                                                                                                                  \
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                      \
+                uint64_t live = __ballot(hit[c]);                                                                                              \
+                n_gene += __popcll(live);                                                                                                      \
+                while (live) {   /* one round per distinct word among the 64 */                                                                \
+                    const unsigned long long mm = __shfl(m[c], __ffsll((unsigned long long)live) - 1);                                         \
+                    const uint64_t same = __ballot(hit[c] && m[c] == mm);                                                                      \
+                    cnt += (uint32_t)__popcll(same) * (uint32_t)((mm >> lane) & 1u);                                                           \
+                    live &= ~same;                                                                                                             \
+                }                                                                                                                              \
+            }                                                                                                                                  \
+        }                                                                                                                                      \
+        uint32_t best = cnt;                                                                                                                   \
+        _Pragma("unroll")                                                                                                                      \
+        for (uint32_t d = 32; d; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d));                                                     \
+        uint32_t second = cnt < best ? cnt : 0;                                                                                                \
+        _Pragma("unroll")                                                                                                                      \
+        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));                                               \
+        const uint64_t compat = __ballot(cnt > 0 && best - cnt < margin);                                                                      \
+        if (lane == 0) {                                                                                                                       \
+            bdg_iso_rec rec;                                                                                                                   \
+            rec.compat = compat; rec.feature = f; rec.best = best; rec.second = second; rec.n_gene = n_gene;                                   \
+            const uint32_t bits = __popcll(compat);                                                                                            \
+            rec.flags = bits == 1 ? BDG_ISO_UNIQUE : bits > 1 ? BDG_ISO_MULTI : 0u;                                                            \
+            rec.pad = 0;                                                                                                                       \
+            out[r] = rec;                                                                                                                      \
+        }                                                                                                                                      \
+    }
+
 __global__ __launch_bounds__(64)
 void k_iso_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k,
                   const bdg_gene_rec* __restrict__ genes, uint32_t margin, const GeneSlot* __restrict__ table,
                   const unsigned long long* __restrict__ tx_mask, uint64_t mask, uint32_t shift, bdg_iso_rec* __restrict__ out)
 {
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
-        const uint32_t f = genes[r].feature;
-        if (!(genes[r].flags & BDG_GENE_ASSIGNED)) {                // none of its bases is read
-            if (lane == 0) {
-                bdg_iso_rec rec;
-                rec.compat = 0; rec.feature = BDG_GENES_NONE; rec.best = rec.second = rec.n_gene = 0; rec.flags = BDG_ISO_NOGENE; rec.pad = 0;
-                out[r] = rec;
-            }
-            continue;
-        }
-        const uint64_t b = off[r], e = off[r + 1], len = e > b ? e - b : 0;
-        const uint8_t* s = bases + b;
-        uint32_t cnt = 0, n_gene = 0;                               // cnt: of the transcript whose local index is this lane
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64 * GENES_CHUNKS) {
-            GENES_PROBE_CHUNKS(s, len, p0, lane, kmask, table, mask, shift)
-            bool hit[GENES_CHUNKS];
-            unsigned long long m[GENES_CHUNKS];
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) hit[c] = key[c] != KEY_EMPTY && got[c].x == key[c] && (uint32_t)got[c].y == f;
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) m[c] = tx_mask[hit[c] ? sl[c] : 0];     // (a lane without a hit drops it)
-#pragma unroll
-            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
-                uint64_t live = __ballot(hit[c]);
-                n_gene += __popcll(live);
-                while (live) {                                      // one round per distinct word among the 64
-                    const unsigned long long mm = __shfl(m[c], __ffsll((unsigned long long)live) - 1);
-                    const uint64_t same = __ballot(hit[c] && m[c] == mm);
-                    cnt += (uint32_t)__popcll(same) * (uint32_t)((mm >> lane) & 1u);
-                    live &= ~same;
-                }
-            }
-        }
-        uint32_t best = cnt;
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) best = max(best, (uint32_t)__shfl_xor(best, d));
-        uint32_t second = cnt < best ? cnt : 0;
-#pragma unroll
-        for (uint32_t d = 32; d; d >>= 1) second = max(second, (uint32_t)__shfl_xor(second, d));
-        const uint64_t compat = __ballot(cnt > 0 && best - cnt < margin);
-        if (lane == 0) {
-            bdg_iso_rec rec;
-            rec.compat = compat; rec.feature = f; rec.best = best; rec.second = second; rec.n_gene = n_gene;
-            const uint32_t bits = __popcll(compat);
-            rec.flags = bits == 1 ? BDG_ISO_UNIQUE : bits > 1 ? BDG_ISO_MULTI : 0u;
-            rec.pad = 0;
-            out[r] = rec;
+    constexpr const bdg_cdna_span* spans = nullptr;
+    ISO_ASSIGN_BODY(Whole)
+}
+
+__global__ __launch_bounds__(64)
+void k_iso_assign_spans(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, const bdg_cdna_span* __restrict__ spans,
+                        uint32_t n, uint32_t k, const bdg_gene_rec* __restrict__ genes, uint32_t margin, const GeneSlot* __restrict__ table,
+                        const unsigned long long* __restrict__ tx_mask, uint64_t mask, uint32_t shift, bdg_iso_rec* __restrict__ out)
+{
+    ISO_ASSIGN_BODY(Span)
+}
+
+// The span of a read from its records (include/badger_hip.h at bdg_cdna_spans_dev): what write_trimmed prints as its cDNA.
+__global__ __launch_bounds__(256)
+void k_cdna_spans(const uint64_t* __restrict__ off, uint32_t n, const bdg_extract_rec* __restrict__ recs,
+                  const bdg_trim_rec* __restrict__ trim, const bdg_chimera_rec* __restrict__ chim, bdg_cdna_span* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const bdg_trim_rec t = trim[i];
+    bdg_cdna_span sp = { 0, 0, 0u };
+    if (t.flags & BDG_TRIM_EMIT) {
+        const int64_t a = t.cdna_start;
+        int64_t b = t.cdna_end;
+        if (chim) { const bdg_chimera_rec c = chim[i]; if (c.flags & BDG_CHIMERA_HIT) b = c.cut; }
+        if (b > a) {
+            const uint64_t o0 = off[i], o1 = off[i + 1];
+            const int64_t L = o1 > o0 ? (int64_t)(o1 - o0) : 0;
+            const bool rev = (recs[i].flags & BDG_FLAG_REV) != 0, sense = (t.flags & BDG_TRIM_SENSE) != 0;
+            const int64_t lo = rev ? L - b : a, hi = rev ? L - a : b;
+            sp.begin = (int32_t)min(max(lo, (int64_t)INT32_MIN), (int64_t)INT32_MAX);
+            sp.end = (int32_t)min(max(hi, (int64_t)INT32_MIN), (int64_t)INT32_MAX);
+            sp.rc = rev == sense ? 1u : 0u;
         }
     }
+    out[i] = sp;
 }
 
 int genes_cus(bdg_ctx* ctx)
@@ -459,6 +559,57 @@ int iso_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_of
                            static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
                            ctx->gn_slots - 1, shift, d_out);
     }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+// the span forms: the same grids, each kernel's own resident-wave figure
+int genes_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
+                              uint32_t min_hits, bdg_gene_rec* d_out)
+{
+    if (int rc = genes_cus(ctx)) return rc;
+    if (ctx->gn_assign_sp_per_cu == 0) {
+        int per_cu = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_genes_assign_spans, 64, 0));
+        ctx->gn_assign_sp_per_cu = per_cu < 1 ? 1 : per_cu;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_assign_sp_per_cu);
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
+    {
+        ScopedKernelTimer tm(ctx, "k_genes_assign_spans");
+        hipLaunchKernelGGL(k_genes_assign_spans, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, d_spans, n, ctx->gn_k, min_hits,
+                           static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, shift, d_out);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int iso_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
+                            const bdg_gene_rec* d_genes, uint32_t margin, bdg_iso_rec* d_out)
+{
+    if (int rc = genes_cus(ctx)) return rc;
+    if (ctx->gn_iso_sp_per_cu == 0) {
+        int per_cu = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iso_assign_spans, 64, 0));
+        ctx->gn_iso_sp_per_cu = per_cu < 1 ? 1 : per_cu;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_iso_sp_per_cu);
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
+    {
+        ScopedKernelTimer tm(ctx, "k_iso_assign_spans");
+        hipLaunchKernelGGL(k_iso_assign_spans, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, d_spans, n, ctx->gn_k, d_genes, margin,
+                           static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
+                           ctx->gn_slots - 1, shift, d_out);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+int cdna_spans_launch(bdg_ctx* ctx, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim,
+                      const bdg_chimera_rec* d_chim, bdg_cdna_span* d_out)
+{
+    ScopedKernelTimer tm(ctx, "k_cdna_spans");
+    hipLaunchKernelGGL(k_cdna_spans, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_off, n, d_recs, d_trim, d_chim, d_out);
     BDG_HIP_TRY(ctx, hipGetLastError());
     return BDG_OK;
 }
@@ -567,7 +718,101 @@ int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_of
 
 }  // namespace
 
+// bdg_extract_keep_genes (bdg_chunks.cpp): what the context must hold for it, and the records of a collected chunk - the spans
+// from the chunk's records into the context's scratch array, the gene pass, and with a margin the isoform pass, all behind the
+// chunk's kernels on the same stream
+int bdg_genes_keep_check(bdg_ctx* ctx, uint32_t min_hits, uint32_t margin)
+{
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (margin > 0 && !ctx->gn_mask.p) return bdg_fail(ctx, BDG_E_ARG, "isoforms: no index with masks built (bdg_genes_index_build_iso)");
+    return BDG_OK;
+}
+
+int bdg_genes_kept_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs,
+                          const bdg_trim_rec* d_trim, const bdg_chimera_rec* d_chim, uint32_t min_hits, uint32_t margin,
+                          bdg_gene_rec* d_gene, bdg_iso_rec* d_iso)
+{
+    int rc;
+    if ((rc = bdg_genes_keep_check(ctx, min_hits, margin))) return rc;
+    if (n == 0) return BDG_OK;
+    if ((rc = bdg_reserve(ctx, ctx->gn_spans, sizeof(bdg_cdna_span) * (size_t)n))) return rc;
+    auto* d_spans = static_cast<bdg_cdna_span*>(ctx->gn_spans.p);
+    if ((rc = cdna_spans_launch(ctx, d_off, n, d_recs, d_trim, d_chim, d_spans))) return rc;
+    if ((rc = genes_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, min_hits, d_gene))) return rc;
+    if (margin > 0 && (rc = iso_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, d_gene, margin, d_iso))) return rc;
+    return BDG_OK;
+}
+
 extern "C" {
+
+int bdg_genes_assign_spans_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
+                               uint32_t min_hits, bdg_gene_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!d_off || !d_spans || !d_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return genes_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, min_hits, d_out);
+}
+
+int bdg_iso_assign_spans_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
+                             const bdg_gene_rec* d_gene_recs, uint32_t margin, bdg_iso_rec* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = iso_check_assign(ctx, margin)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!d_off || !d_spans || !d_gene_recs || !d_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return iso_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, d_gene_recs, margin, d_out);
+}
+
+int bdg_cdna_spans_dev(bdg_ctx* ctx, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim,
+                       const bdg_chimera_rec* d_chim_or_null, bdg_cdna_span* d_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (n == 0) return BDG_OK;
+    if (!d_off || !d_recs || !d_trim || !d_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return cdna_spans_launch(ctx, d_off, n, d_recs, d_trim, d_chim_or_null, d_out);
+}
+
+int bdg_genes_assign_spans(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_cdna_span* spans,
+                           uint32_t min_hits, uint32_t margin, bdg_gene_rec* gene_out, bdg_iso_rec* iso_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    const bool both = margin > 0;                                   // (the isoform pass too: the index must have masks)
+    if (both) if (int rc = iso_check_assign(ctx, margin)) return rc;
+    if (n == 0) return BDG_OK;
+    if (!off || !spans || !gene_out || (both && !iso_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    for (uint32_t r = 0; r < n; ++r)
+        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
+    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // one input buffer behind the bases: the offsets, then the spans; one output buffer as in bdg_iso_assign
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), span_b = sizeof(bdg_cdna_span) * (size_t)n,
+                 gene_b = (sizeof(bdg_gene_rec) * (size_t)n + 31u) & ~(size_t)31u, iso_b = both ? sizeof(bdg_iso_rec) * (size_t)n : 0;
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + span_b))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, gene_b + iso_b))) return rc;
+    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
+    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
+    auto* d_spans = reinterpret_cast<bdg_cdna_span*>(static_cast<char*>(ctx->s_in1.p) + off_b);
+    auto* d_gene = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
+    auto* d_iso = reinterpret_cast<bdg_iso_rec*>(static_cast<char*>(ctx->s_out0.p) + gene_b);
+    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_spans, spans, span_b, hipMemcpyHostToDevice, st));
+    if ((rc = genes_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, min_hits, d_gene))) return rc;
+    if (both && (rc = iso_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, d_gene, margin, d_iso))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(gene_out, d_gene, sizeof(bdg_gene_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (both) BDG_HIP_TRY(ctx, hipMemcpyAsync(iso_out, d_iso, iso_b, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BDG_OK;
+}
 
 int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
                           uint32_t k)

@@ -10,7 +10,10 @@ Two things live here.  The CHECKER restates the rule that include/badger_hip.h s
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
 the product side: it reads a transcript FASTA, builds the k-mer table on the device (bdg_genes_index_build), hands the reads
 of a tagged FASTA as `badger.py --tagged_reads` writes it to the device (bdg_genes_assign), and turns the calls into molecules
-and the features x barcodes matrix on the host.
+and the features x barcodes matrix on the host.  MatrixFromReads is the second route to the same files (badger.py
+--matrix_from_reads): the gene calls are made during stage 2's one pass over the reads, from each read's cDNA where
+it lies in the read (span_sequence and spans_of_records restate that rule), and no tagged file is read.  Both routes end in
+count_matrix_records.
 
 The rule.  Any byte other than ACGT behaves as N; codes A 0, C 1, G 2, T 3.
     key       a window of k consecutive bases (11 <= k <= 31) without an N: sum of code(base j) << 2j, j = 0 its first base.
@@ -269,6 +272,56 @@ def iso_assign_reads(index, reads, gene_recs, margin=MARGIN_DEFAULT):
         rec["second"] = int(cnt[cnt < best].max(initial=0))
         rec["flags"] = ISO_UNIQUE if bits == 1 else ISO_MULTI if bits > 1 else 0
     return out
+
+
+# The span rule (include/badger_hip.h at bdg_cdna_span): a read's cDNA where it lies.  Read B of length L, begin and
+# end clamped to 0 .. L; X = B[begin:end] for rc == 0, else its reverse complement (A <-> T, C <-> G, anything else N); end <= begin
+# is the empty sequence.  The records of a span are the records of X.
+_COMP = np.full(256, ord("N"), dtype=np.uint8)
+for _a, _b in zip(b"ACGT", b"TGCA"):
+    _COMP[_a] = _b
+
+
+def span_sequence(read, begin, end, rc):
+    """the sequence X of a span of a read (bytes / str / uint8 array) -> bytes"""
+    b = _as_array(read)
+    lo, hi = min(max(int(begin), 0), len(b)), min(max(int(end), 0), len(b))
+    x = b[lo:hi] if hi > lo else b[:0]
+    return (_COMP[x[::-1]] if rc else x).tobytes()
+
+
+def span_sequences(reads, spans):
+    return [span_sequence(r, s["begin"], s["end"], s["rc"]) for r, s in zip(reads, spans)]
+
+
+def spans_of_records(lengths, recs, trim, chim=None):
+    """the span of every read from its records, the cDNA bdg_format_trimmed_chimera writes: lengths the reads' lengths, recs /
+    trim / chim the _native REC / TRIM / CHIMERA arrays (chim None: no search ran) -> _native.SPAN_DTYPE [n].  {0, 0, 0} without
+    TRIM_EMIT or with b <= a, where a = cdna_start and b = cut for a CHIMERA_HIT record, else cdna_end; the read's own bytes are
+    [L - b, L - a) for a FLAG_REV record and [a, b) otherwise; rc = 1 unless exactly one of FLAG_REV and TRIM_SENSE is set."""
+    from . import _native
+    out = np.zeros(len(lengths), dtype=_native.SPAN_DTYPE)
+    for i, L in enumerate(np.asarray(lengths).tolist()):
+        flags = int(trim["flags"][i])
+        if not flags & _native.TRIM_EMIT:
+            continue
+        a, b = int(trim["cdna_start"][i]), int(trim["cdna_end"][i])
+        if chim is not None and int(chim["flags"][i]) & _native.CHIMERA_HIT:
+            b = int(chim["cut"][i])
+        if b <= a:
+            continue
+        rev, sense = bool(int(recs["flags"][i]) & _native.FLAG_REV), bool(flags & _native.TRIM_SENSE)
+        lo, hi = (L - b, L - a) if rev else (a, b)
+        out[i] = (min(max(lo, -2 ** 31), 2 ** 31 - 1), min(max(hi, -2 ** 31), 2 ** 31 - 1), 1 if rev == sense else 0)
+    return out
+
+
+def assign_spans(index, reads, spans, min_hits=MIN_HITS_DEFAULT, margin=None):
+    """the rule over a span of every read: assign_reads of the spans' sequences -> REC_DTYPE [n], with a margin (and an index with
+    masks) also iso_assign_reads of them -> (REC_DTYPE [n], ISO_DTYPE [n])"""
+    seqs = span_sequences(reads, spans)
+    recs = assign_reads(index, seqs, min_hits)
+    return (recs, iso_assign_reads(index, seqs, recs, margin)) if margin else recs
 
 
 def _popcount(x):
@@ -733,29 +786,38 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None
     iso = None
     if isoforms is not None:
         recs, iso = recs
+    heads = [heads[i] for i in take]
+    return count_matrix_records([h.split(b"\t")[0] for h in heads], [cb[i] for i in take], [ub[i] for i in take],
+                                _ur_texts(heads) if per_gene is not None else None, recs, names, iso, isoforms, em, per_gene,
+                                len(cb) - len(take))
+
+
+def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, em=None, per_gene=None, no_cell=0):
+    """what count_matrix_text does behind the parse and the gene calls, for both routes to the matrix.  Per read that has a cell:
+    ids its name, cb its cell, ub its molecule or None (all bytes), ur its UMI text or None (looked at with per_gene only), recs
+    REC_DTYPE, iso ISO_DTYPE with isoforms; names, isoforms, em, per_gene as for count_matrix_text; no_cell: reads left out for
+    want of a cell, for the log -> ({file name: bytes}, counts dict)"""
     if per_gene is not None:
-        ur = _ur_texts([heads[i] for i in take])
-        made = molecules_per_gene([cb[i] for i in take], ur, recs, per_gene[0], per_gene[1], per_gene[2], iso)
+        made = molecules_per_gene(cb, ur, recs, per_gene[0], per_gene[1], per_gene[2], iso)
     else:
-        made = count_molecules([cb[i] for i in take], [ub[i] for i in take], recs, iso)
+        made = count_molecules(cb, ub, recs, iso)
     cells, entries, counts = made[:3]
     molecules = made[3] if isoforms is not None else None
-    counts["no_cell"] = len(cb) - len(take)
+    counts["no_cell"] = no_cell
     rows = ["read\tCB\tUB\tfeature\thits\tsecond\tn_keys\tn_found\tflags\n"]
-    for i, r in zip(take, recs.tolist()):
+    for name, c, u, r in zip(ids, cb, ub, recs.tolist()):
         feature, hits, second, n_keys, n_found, flags = r
         rows.append("%s\t%s\t%s\t%s\t%d\t%d\t%d\t%d\t%s\n" % (
-            heads[i].split(b"\t")[0].decode(), cb[i].decode(), ub[i].decode() if ub[i] is not None else "*",
+            name.decode(), c.decode(), u.decode() if u is not None else "*",
             names[feature] if feature != NONE else "*", hits, second, n_keys, n_found, flag_names(flags)))
     files = {"features.tsv": "".join("%s\t%s\tGene Expression\n" % (x, x) for x in names).encode(),
              "barcodes.tsv": b"".join(c + b"\n" for c in cells),
              "matrix.mtx": _mtx(len(names), len(cells), entries),
              "reads.tsv": "".join(rows).encode()}
     if per_gene is not None:
-        files["gene_molecules.tsv"] = gene_molecules_text(names, [heads[i] for i in take], [cb[i] for i in take], ur, recs, counts.pop("rows"))
+        files["gene_molecules.tsv"] = gene_molecules_text(names, ids, cb, ur, recs, counts.pop("rows"))
     if isoforms is not None:
-        more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], [heads[i] for i in take], [cb[i] for i in take],
-                                         [ub[i] for i in take], iso, cells, molecules)
+        more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], ids, cb, ub, iso, cells, molecules)
         files.update(more)
         counts.update(iso_counts)
         if em is not None:
@@ -868,13 +930,8 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
     EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
     (bdg_umi_dedup_genes) and gene_molecules.tsv -> counts"""
     from . import _native
-    tx_names, tx_seqs = read_fasta(transcripts)
-    names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
     ctx = _native.default_context(device)
-    if iso_margin:
-        ctx.genes_index_build_iso(*_flatten(tx_seqs), feat, local_indices(feat)[0], k)
-    else:
-        ctx.genes_index_build(*_flatten(tx_seqs), feat, k)
+    names, tx_names, feat = _build_index(ctx, transcripts, tx2gene, k, iso_margin)
     try:
         stats = ctx.genes_index_stats()
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
@@ -882,13 +939,89 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
                                           (device_em(ctx),) + tuple(em) if iso_margin and em else None,
                                           (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
-        ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
+        _drop_index(ctx, k)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
     os.makedirs(out_dir, exist_ok=True)
     for name, data in files.items():
         with open(os.path.join(out_dir, name), "wb") as f:
             f.write(data)
     return counts
+
+
+def _build_index(ctx, transcripts, tx2gene, k, iso_margin):
+    """the transcripts' k-mer table on the context (with masks for --isoforms) -> (feature names, transcript names, feature ids)"""
+    tx_names, tx_seqs = read_fasta(transcripts)
+    names, feat = features_of(tx_names, read_tx2gene(tx2gene) if tx2gene else None)
+    if iso_margin:
+        ctx.genes_index_build_iso(*_flatten(tx_seqs), feat, local_indices(feat)[0], k)
+    else:
+        ctx.genes_index_build(*_flatten(tx_seqs), feat, k)
+    return names, tx_names, feat
+
+
+def _drop_index(ctx, k):
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), k)
+
+
+class MatrixFromReads:
+    """--matrix_from_reads: the matrix from the one pass over the reads.  Made before that pass - the transcripts'
+    table goes to the device; keep() is called in front of the pass, inside the block that keeps records and trims - every collected
+    chunk's gene (and isoform) records stay on the device; write() behind the cell and molecule calls, while the kept arrays
+    live; close() leaves the shared context with the empty table, as count_matrix_of_tagged does."""
+
+    def __init__(self, ctx, transcripts, tx2gene, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, iso_margin=None):
+        self.ctx, self.k, self.min_hits, self.iso_margin = ctx, k, min_hits, iso_margin
+        try:
+            self.names, self.tx_names, self.feat = _build_index(ctx, transcripts, tx2gene, k, iso_margin)
+            self.stats = ctx.genes_index_stats()
+        except BaseException:
+            self.close()
+            raise
+
+    def keep(self):
+        """from here on every collected chunk's records stay (bdg_extract_keep_genes); turning the trim off ends it"""
+        self.ctx.extract_keep_genes(True, self.min_hits, self.iso_margin or 0)
+
+    def close(self):
+        _drop_index(self.ctx, self.k)
+
+    def write(self, out_dir, ids, cell_rank, cell_has, molecule, umi, cdna_len, em=None, per_gene=None):
+        """ids: the reads' names (an _native.IdStore or a list); per read cell_rank / cell_has its cell, molecule its molecule's
+        code inside the cell (None without --umi_dedup), umi its kept UMI code, cdna_len its kept cDNA length (numpy arrays).  The
+        reads that take part are those the tagged file would hold: a cell and a cDNA length above 0 -> counts"""
+        from . import _native
+        from .stage2 import unrank_many
+        from .umi_dedup import NONE as NO_UMI, umi_str
+        ctx = self.ctx
+        d_gene, d_iso, n = ctx.kept_genes()
+        if not (n == len(cell_rank) == len(cdna_len) == len(ids)) or (umi is not None and len(umi) != n):
+            raise RuntimeError("%d gene records kept for %d reads" % (n, len(cell_rank)))
+        take = np.flatnonzero((np.asarray(cell_has) != 0) & (np.asarray(cdna_len) > 0))
+        recs = ctx.device_to_host(d_gene, n, _native.GENE_DTYPE)[take]
+        iso = ctx.device_to_host(d_iso, n, _native.ISO_DTYPE)[take] if self.iso_margin else None
+        names = ids.to_list() if hasattr(ids, "to_list") else list(ids)
+        cells, which = np.unique(np.asarray(cell_rank)[take], return_inverse=True)
+        cell_text = [c.encode() for c in unrank_many(cells)]
+
+        def code_texts(codes):                              # (few distinct codes beside the reads: each is spelled once)
+            distinct, at = np.unique(codes, return_inverse=True)
+            text = [None if c == NO_UMI else umi_str(c).encode() for c in distinct.tolist()]
+            return [text[j] for j in at.tolist()]
+
+        ub = code_texts(np.asarray(molecule)[take]) if molecule is not None else [None] * len(take)
+        ur = code_texts(np.asarray(umi)[take]) if per_gene is not None else None
+        files, counts = count_matrix_records(
+            [names[i].encode() for i in take.tolist()], [cell_text[j] for j in which.tolist()], ub, ur, recs, self.names, iso,
+            (self.tx_names, self.feat) if self.iso_margin else None,
+            (device_em(ctx),) + tuple(em) if self.iso_margin and em else None,
+            (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None, int((np.asarray(cell_has) == 0).sum()))
+        counts.update(transcripts=len(self.tx_names), features=len(self.names), keys=int(self.stats[1]), ambiguous=int(self.stats[2]),
+                      k=self.k)
+        os.makedirs(out_dir, exist_ok=True)
+        for name, data in files.items():
+            with open(os.path.join(out_dir, name), "wb") as f:
+                f.write(data)
+        return counts
 
 
 def log_counts(counts, out_dir):

@@ -480,6 +480,14 @@ class Stage2:
                             for j in sorted(range(len(seen)), key=names.__getitem__)))
         return int(cnt[:, 3].sum()) if nc else 0
 
+    def read_cells(self):
+        """the per-read cells output_file_from_device left (ReadCells)"""
+        return self._cells
+
+    def read_molecules(self):
+        """the per-read molecules umi_dedup_from_device left (Molecules), None without it"""
+        return self._mol
+
     def read_tags_from_device(self, molecule_reads=False):
         """--tagged_reads: the per-read arrays of the second pass (_native.stage1_run's tags): every read's cell from
         output_file_from_device and - after umi_dedup_from_device - its molecule and the molecule's read count; each molecule's

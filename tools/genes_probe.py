@@ -31,6 +31,14 @@ over its class counts, one JSON line each to --out (and stdout).
     python tools/genes_probe.py --cli --isoforms --em ...
         the command line with --isoforms --isoform_em against --isoforms alone, then, in this process, the EM step once more
         over the tagged file of the run: how much of it is the device calls and how much host numpy.
+    python tools/genes_probe.py --device --spans [--reads 1000000] [--tx_bases 4000000 100000000] --out profiles/r27_matrix_from_reads.jsonl
+        the isoform workload once more: every fragment also lies inside a raw read, behind 100 random bases and in
+        front of 60, every second one reverse-complemented, with its span.  bdg_genes_assign_spans_dev and
+        bdg_iso_assign_spans_dev on the raw reads beside bdg_genes_assign_dev and bdg_iso_assign_dev on the fragments: the four
+        kernels from the event timers of the same run, and whether the records are the same.
+    python tools/genes_probe.py --cli --spans ...
+        the command line with --umi_dedup --count_matrix --matrix_from_reads against --umi_dedup --tagged_reads --count_matrix,
+        the pair once more with --isoforms --isoform_em --umi_per_gene, then the pairs with --parent as above.
 """
 import argparse
 import os
@@ -209,6 +217,90 @@ def device_probe_iso(args):
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
 
 
+def raw_reads(bases, off, seed=3, pre=100, suf=60, chunk=50000):
+    """every read of (bases, off) inside a raw read of its own: `pre` random bases, the read - every second one
+    reverse-complemented - and `suf` random bases -> (raw bases, raw off, spans SPAN_DTYPE)"""
+    from badger_amd import _native
+    rng = np.random.default_rng(seed)
+    n = len(off) - 1
+    L = np.diff(off.astype(np.int64))
+    raw_off = np.concatenate([[0], np.cumsum(L + pre + suf)])
+    raw = ACGT[rng.integers(0, 4, int(raw_off[-1]), dtype=np.uint8)]
+    comp = np.zeros(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    for r0 in range(0, n, chunk):
+        r1 = min(n, r0 + chunk)
+        a, b = int(off[r0]), int(off[r1])
+        rid = np.repeat(np.arange(r0, r1), L[r0:r1])
+        pos = np.arange(a, b) - off.astype(np.int64)[rid]
+        rc = (rid & 1) == 1
+        raw[raw_off[rid] + pre + np.where(rc, L[rid] - 1 - pos, pos)] = np.where(rc, comp[bases[a:b]], bases[a:b])
+    spans = np.zeros(n, dtype=_native.SPAN_DTYPE)
+    spans["begin"], spans["end"], spans["rc"] = pre, pre + L, np.arange(n) & 1
+    return raw, raw_off.astype(np.uint64), spans
+
+
+def device_probe_spans(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for tx_bases in args.tx_bases:
+        tx, feat, local = iso_transcriptome(max(tx_bases // TX_LEN, 1))
+        n_tx = len(tx)
+        bases, off = fragments(tx, args.reads)
+        raw, raw_off, spans = raw_reads(bases, off)
+        n = len(off) - 1
+        ctx.genes_index_build_iso(ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64), feat, local, args.k)
+        stats = [int(x) for x in ctx.genes_index_stats()]
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off, raw, raw_off, spans)]
+        out = [_native.DeviceArray(ctx, n * w, np.uint32) for w in (6, 8, 6, 8)]
+
+        def forward():
+            ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, out[0])
+            ctx.iso_assign_dev(d[0], d[1], n, out[0], args.margin, out[1])
+
+        def spanned():
+            ctx.genes_assign_spans_dev(d[2], d[3], n, d[4], args.min_hits, out[2])
+            ctx.iso_assign_spans_dev(d[2], d[3], n, d[4], out[2], args.margin, out[3])
+        walls = {}
+        for name, call in (("forward", forward), ("spans", spanned)):
+            call()
+            ctx.synchronize()
+            times = []
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                call()
+                ctx.synchronize()
+                times.append(time.perf_counter() - t0)
+            walls[name] = round(1e3 * float(np.median(times)), 3)
+        # the kernels, one call of each form after the other, every repetition timed on its own: medians
+        per = {}
+        for _ in range(args.reps):
+            ctx.profile(True)
+            ctx.profile_reset()
+            forward()
+            spanned()
+            ctx.synchronize()
+            for k, v in ctx.profile_read().items():
+                if k.startswith(("k_genes_assign", "k_iso_assign")) and v[0]:
+                    per.setdefault(k, []).append(v[1])
+            ctx.profile(False)
+        kt = {k: round(float(np.median(v)), 4) for k, v in per.items()}
+        host = [o.to_host() for o in out]
+        emit(args.out, {"what": "span kernels on raw reads beside the forward kernels on the materialised cDNA, device-resident",
+                        "k": args.k, "min_hits": args.min_hits, "margin": args.margin, "transcripts": n_tx, "transcript_bases": int(n_tx * TX_LEN),
+                        "table_bytes": 16 * stats[3], "mask_bytes": 8 * stats[3], "reads": n, "cdna_bases": int(off[-1]),
+                        "raw_bases": int(raw_off[-1]), "reverse_complemented": int(spans["rc"].sum()), "reps": args.reps,
+                        "gene_records_equal": bool((host[0] == host[2]).all()), "iso_records_equal": bool((host[1] == host[3]).all()),
+                        "assigned": int((host[0].view(_native.GENE_DTYPE)["flags"] & 1 != 0).sum()),
+                        "both_calls_ms_median": walls, "kernel_ms_median": kt,
+                        "spans_over_forward": {"genes": round(kt["k_genes_assign_spans"] / kt["k_genes_assign"], 4),
+                                               "iso": round(kt["k_iso_assign_spans"] / kt["k_iso_assign"], 4)}})
+        for a in d + out:
+            a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+
+
 def em_workload(n_prob, t_lo, t_hi, mol_lo, mol_hi, p_multi, extra_max, seed):
     """n_prob problems: T transcripts (t_lo .. t_hi), mol_lo .. mol_hi molecules each of a random transcript of the problem;
     with probability p_multi a molecule is also compatible with 1 .. extra_max other transcripts
@@ -377,7 +469,16 @@ def cli_probe(args):
     fa = os.path.join(tmp, "tagged.fa")
     tagged = ["--umi_dedup", "--tagged_reads", fa]
     run(ROOT, "warm", tagged)                                          # (the file into the page cache, the runtime's caches)
-    if args.isoforms:
+    if args.spans:
+        tx2, tx_map = os.path.join(tmp, "tx_iso.fa"), os.path.join(tmp, "tx2gene.tsv")
+        _isoforms_of(tx, tx2, tx_map)
+        for what, gene in (("", ["--transcripts", tx]),
+                           (" --tx2gene --isoforms --isoform_em --umi_per_gene",
+                            ["--transcripts", tx2, "--tx2gene", tx_map, "--isoforms", "--isoform_em", "--umi_per_gene"])):
+            matrix = ["--umi_dedup"] + gene + ["--count_matrix", os.path.join(tmp, "matrix")]
+            pairs("tagged_route", (ROOT, matrix + ["--tagged_reads", fa]), "from_reads", (ROOT, matrix + ["--matrix_from_reads"]),
+                  "stage2 CLI from FASTQ, --umi_dedup --count_matrix%s: --matrix_from_reads against --tagged_reads" % what)
+    elif args.isoforms:
         tx2, tx_map = os.path.join(tmp, "tx_iso.fa"), os.path.join(tmp, "tx2gene.tsv")
         _isoforms_of(tx, tx2, tx_map)
         matrix = tagged + ["--transcripts", tx2, "--tx2gene", tx_map, "--count_matrix", os.path.join(tmp, "matrix")]
@@ -407,6 +508,7 @@ def main():
     p.add_argument("--min_hits", type=int, default=3)
     p.add_argument("--isoforms", action="store_true", help="the isoform leg of --device and of --cli (DESIGN 4.20)")
     p.add_argument("--margin", type=int, default=1)
+    p.add_argument("--spans", action="store_true", help="the span kernels beside the forward ones (--device), --matrix_from_reads (--cli) (DESIGN 4.25)")
     p.add_argument("--em", action="store_true", help="k_em_tcc alone; with --cli --isoforms the --isoform_em leg (DESIGN 4.21)")
     p.add_argument("--em_problems", type=int, default=1000000)
     p.add_argument("--em_wide", type=int, default=100000)
@@ -419,7 +521,7 @@ def main():
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
-        (device_probe_iso if args.isoforms else device_probe)(args)
+        (device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
     if args.em and not args.cli:
         em_probe(args)
     if args.cli:
