@@ -56,6 +56,9 @@ GENE_GROUP_DTYPE = np.dtype([("feature", "<u4"), ("cell", "<u4"), ("molecules", 
 GENES_K_MIN, GENES_K_MAX, GENES_K_DEFAULT, GENES_MIN_HITS_DEFAULT, GENES_MAX_FEATURES = 11, 31, 21, 3, 256
 GENES_AMBIGUOUS, GENES_NONE = 0xFFFFFFFE, 0xFFFFFFFF
 GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
+# bdg_allele_rec: a read's windows that carry either allele of a known SNV (bdg_alleles_assign; the rule in badger_amd/alleles.py)
+ALLELE_DTYPE = np.dtype([("read", "<u4"), ("variant", "<u4"), ("ref_hits", "<u4"), ("alt_hits", "<u4")])
+ALLELES_K_DEFAULT, ALLELES_MAX_VARIANTS = 15, 256
 # bdg_iso_rec: the transcripts of its gene a read is compatible with (bdg_iso_assign; the rule in badger_amd/genes.py)
 ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("second", "<u4"), ("n_gene", "<u4"), ("flags", "<u4"),
                       ("pad", "<u4")])
@@ -108,6 +111,8 @@ EXPORTS = [
     "bdg_genes_assign_spans", "bdg_genes_assign_spans_dev", "bdg_iso_assign_spans_dev", "bdg_cdna_spans_dev", "bdg_extract_keep_genes",
     "bdg_kept_genes",
     "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
+    "bdg_alleles_index_build", "bdg_alleles_index_stats", "bdg_alleles_assign_dev", "bdg_alleles_assign",
+    "bdg_alleles_index_values",
 ]
 
 
@@ -398,6 +403,11 @@ def load():
     L.bdg_umi_dedup_genes_dev.argtypes = [vp, vp, vp, vp, u64, u32, u32, vp, vp, u32, vp]
     L.bdg_umi_dedup_genes_set_aggregate.argtypes = [vp, C.c_int]
     L.bdg_umi_set_max_dist.argtypes = [vp, u32]
+    L.bdg_alleles_index_build.argtypes = [vp, vp, vp, u32, vp, vp, u32, u32, u32]
+    L.bdg_alleles_index_stats.argtypes = [vp, vp, vp]
+    L.bdg_alleles_index_values.argtypes = [vp, C.POINTER(u32)]
+    L.bdg_alleles_assign_dev.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
+    L.bdg_alleles_assign.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -856,6 +866,62 @@ class Context:
         g, i, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._check(self.lib.bdg_kept_genes(self.h, C.byref(g), C.byref(i), C.byref(n)))
         return g.value or 0, i.value or 0, int(n.value)
+
+    def alleles_index_build(self, bases, seq_off, values, genes, n_features, k=ALLELES_K_DEFAULT):
+        """the allele table of the allele sequences (bases uint8, seq_off uint64 [n + 1], values uint32 [n]: 2 * variant + allele)
+        on the device, beside the genes table and in place of an earlier allele table; genes uint32 [n_variants] the feature id
+        of every variant's gene, each < n_features (bdg_alleles_index_build)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        genes = np.ascontiguousarray(genes, dtype=np.uint32)
+        if len(seq_off) != len(values) + 1:
+            raise ValueError("seq_off holds one entry more than values")
+        self._check(self.lib.bdg_alleles_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(values), values.ctypes.data,
+                                                     genes.ctypes.data, len(genes), int(n_features), int(k)))
+
+    def alleles_index_stats(self):
+        """-> (uint64 [6] as genes_index_stats, of the allele table; uint32 [2 * n_variants]: per value its keys that are not
+        ambiguous) (bdg_alleles_index_stats)"""
+        out = np.zeros(6, dtype=np.uint64)
+        n_values = C.c_uint32()                             # (asked of the context: whoever made the build, the buffer fits)
+        self._check(self.lib.bdg_alleles_index_values(self.h, C.byref(n_values)))
+        per_value = np.zeros(n_values.value, dtype=np.uint32)
+        self._check(self.lib.bdg_alleles_index_stats(self.h, out.ctypes.data, per_value.ctypes.data if len(per_value) else None))
+        return out, per_value
+
+    def alleles_assign_dev(self, d_bases, d_off, n, d_gene_recs, d_out, cap, d_counts):
+        """bdg_alleles_assign_dev: the allele records of the reads over device arrays, asynchronous; d_counts [2] uint64"""
+        self._check(self.lib.bdg_alleles_assign_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs),
+                                                    None if d_out is None else _ptr(d_out), int(cap), _ptr(d_counts)))
+
+    def alleles_assign(self, bases, off, gene_recs, cap=None, retry=True):
+        """the allele records of the reads over host arrays, gene_recs GENE_DTYPE [n] what genes_assign gave for them
+        (bdg_alleles_assign) -> (ALLELE_DTYPE sorted by (read, variant), crowded reads).  cap: room for that many records
+        (default: one per read); with more the call is made once more with the count the library returned - retry False raises
+        the library's E_CAPACITY instead, its `n_records` the count."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        gene_recs = np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
+        n = max(len(off) - 1, 0)
+        if len(gene_recs) != n:
+            raise ValueError("a gene record per read")
+        cap = n if cap is None else int(cap)
+        counts = np.zeros(2, dtype=np.uint64)
+        for attempt in range(2):
+            out = np.zeros(cap, dtype=ALLELE_DTYPE)
+            rc = self.lib.bdg_alleles_assign(self.h, bases.ctypes.data, off.ctypes.data, n, gene_recs.ctypes.data,
+                                             out.ctypes.data if cap else None, cap, counts.ctypes.data)
+            if rc == E_CAPACITY and retry and attempt == 0:
+                cap = int(counts[0])
+                continue
+            if rc == E_CAPACITY:
+                err = BadgerHipError(rc, "bdg_alleles_assign: %d records, room for %d" % (int(counts[0]), cap))
+                err.n_records = int(counts[0])
+                raise err
+            self._check(rc)
+            out = out[:int(counts[0])]
+            return out[np.lexsort((out["variant"], out["read"]))], int(counts[1])
 
     def em_tcc(self, classes, prob_off, out_off, eps=EM_EPS_DEFAULT, max_iter=EM_MAX_ITER_DEFAULT, start=None):
         """EM over the compatibility counts of every problem, host arrays (bdg_em_tcc): classes EM_CLASS_DTYPE, problem p the

@@ -9,6 +9,7 @@
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
                                 [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                 [--umi_per_gene [--gene_umi_dist 0|1 | --gene_umi_dist2]]
+                                [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]]
 
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR --matrix_from_reads
                                 [--tagged_reads tagged.fa] [the options of --count_matrix]
@@ -38,6 +39,10 @@ isoform_em_matrix.mtx (transcripts x barcodes, abundances in molecules) and isof
 UMIs are collapsed inside (cell, gene) from the reads' UR, so the same UMI - or two UMIs one edit apart - in two genes of one cell
 are two molecules; gene_molecules.tsv in DIR names every read's molecule.  The tagged file, <out>_molecules.tsv and <out>_cells.tsv
 keep describing the molecules per cell.
+--variants TSV (known single-base variants, id / transcript / 1-based pos / ref / alt per line) adds per-cell allele counts: a second
+table on the device holds the k-mers that cover each site, once per allele; a pass over the tagged reads counts each read's windows that
+carry either allele of a variant of the read's gene, and a vote over the molecules of matrix.mtx gives allele_ref.mtx and allele_alt.mtx
+(variants x barcodes) with variants.tsv and read_alleles.tsv in DIR (alleles.py).  Not yet with --matrix_from_reads.
 --matrix_from_reads writes the same DIR from the one pass over the reads: every read's gene (and isoform) call is made on the device
 from its cDNA where it lies in the read, while its chunk is there (genes.py MatrixFromReads).  --tagged_reads is then optional, and
 a tagged file is written as without the flag but not read back; without it the input is read once.  One column differs: the UR of
@@ -65,6 +70,7 @@ from . import _native
 from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT, add_consensus_options
 from .genes import (K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HITS_DEFAULT, add_gene_options, check_iso_options,
                     check_per_gene_options)
+from .alleles import add_allele_options, check_allele_options, log_counts as log_allele_counts
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -148,6 +154,7 @@ def parse_args(args):
                         "reads, from its cDNA where it lies in the read on the device; the same files in DIR, no tagged file is "
                         "needed, and one written with --tagged_reads is not read back")
     add_gene_options(p)
+    add_allele_options(p)
     a = p.parse_args(args)
     if a.matrix_from_reads and not (a.count_matrix and a.transcripts):
         p.error("--matrix_from_reads needs --count_matrix and --transcripts: it is another way to that matrix")
@@ -159,6 +166,7 @@ def parse_args(args):
     a.gene_min_hits = GENE_MIN_HITS_DEFAULT if a.gene_min_hits is None else a.gene_min_hits
     check_iso_options(p, a, bool(a.count_matrix))
     check_per_gene_options(p, a, bool(a.count_matrix))
+    check_allele_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
@@ -337,8 +345,9 @@ def write_count_matrix(args):
     from .umi_dedup import UMI_LEN
     counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
                                     args.gene_min_hits, args.device, args.iso_margin, args.em,
-                                    (UMI_LEN[args.data_type], args.gene_umi_dist) if args.umi_per_gene else None)
+                                    (UMI_LEN[args.data_type], args.gene_umi_dist) if args.umi_per_gene else None, args.alleles)
     log_counts(counts, args.count_matrix)
+    log_allele_counts(counts, args.count_matrix)
 
 
 def write_matrix_from_reads(args, matrix, st2, ctx, read_ids):

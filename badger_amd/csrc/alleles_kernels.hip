@@ -1,0 +1,395 @@
+// Allele counts at known SNVs by k-mer lookup (include/badger_hip.h at bdg_alleles_index_build states the rule;
+// badger_amd/alleles.py restates it).  gfx950.
+//
+// A second table of genes_kernels.hip's slots holds the keys that cover each site, once per allele; the slot's fourth word is
+// the feature id of the variant's gene.  The planes, the keys, insert_key and the probe are genes_probe.hpp's, shared with the
+// gene kernels: one wave per sequence, persistent, a lane per window, three ballots per 64 bases.
+//
+// k_alleles_insert  insert_key plus the gene word.  All writers of a key that stays unambiguous write the same word (a variant
+//                   has one gene), so it needs no order: a lane looks, and stores only where the word differs.  The word of an
+//                   ambiguous key is whichever writer came last and is never used.  As in k_genes_insert a lane whose left
+//                   neighbour holds the same key does nothing.
+// k_alleles_stats   the six occupancy figures of k_genes_stats, and per value 2 v + a the number of its keys that are not
+//                   ambiguous: one atomicAdd per such slot on the value's own counter (a few dozen keys per value: no hot
+//                   address).
+// k_alleles_assign  a read whose gene record is not ASSIGNED, or whose gene has no variant (a byte per feature), costs its gene
+//                   record and nothing else.  The others are walked like k_genes_assign walks them; nearly every window ends at
+//                   an empty home slot of a table the cache holds.  A found window counts when its value is an allele and the
+//                   slot's gene word is the read's gene - got[c] already holds both.  The loop over the distinct values among
+//                   the 64 adds each value's popcount to a table of 256 (variant, ref, alt) entries in LDS, four entries a lane
+//                   to search, no LDS atomics; the 257th variant makes the read crowded and ends its walk.
+//                   Emission: records are rare per window and common per read, and a returning atomic per read on the call's
+//                   one cursor is a hot address.  So a wave parks its reads' records in a staging area of
+//                   ALLELES_STAGE records in LDS and reserves room with one add per flush - when the next read's records do not
+//                   fit, and at its end - then writes them out, a lane per 16-byte record, consecutive.  The add happens
+//                   whether or not the records fit under cap: the count is exact, the stores are bounded.
+#include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
+#include "genes_probe.hpp"
+
+#include <algorithm>
+
+namespace {
+
+constexpr uint32_t ALLELES_INSERT_WAVES_PER_CU = 16;
+constexpr uint32_t ALLELES_STAGE = 256;                       // records a wave parks before it reserves room for them
+
+static_assert(sizeof(bdg_allele_rec) == 16 && sizeof(uint4) == 16 && ALLELES_STAGE >= BDG_ALLELES_MAX_VARIANTS,
+              "a record is one 16-byte store, and a read's records fit the empty staging area");
+
+__global__ __launch_bounds__(64)
+void k_alleles_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ values,
+                      const uint32_t* __restrict__ genes, uint32_t n_seqs, uint32_t k, GeneSlot* table, uint64_t mask, uint32_t shift)
+{
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
+        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets, values and genes)
+        if (len < k) continue;
+        const uint8_t* s = bases + b;
+        const uint32_t v = values[q], g = genes[v >> 1];
+        Planes A = load_planes(s, len, 0, lane);
+        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
+            const Planes B = load_planes(s, len, p0 + 64, lane);
+            unsigned long long key = window_key(A, B, lane, kmask);
+            const unsigned long long left = __shfl_up(key, 1);
+            if (lane && left == key) key = KEY_EMPTY;               // its left neighbour inserts the same key for the same value
+            if (key != KEY_EMPTY) {
+                const uint64_t at = insert_key(table, mask, shift, key, v);
+                if (__hip_atomic_load(&table[at].pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g)
+                    __hip_atomic_store(&table[at].pad, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            A = B;
+        }
+    }
+}
+
+// out: distinct keys | ambiguous keys | longest run of occupied slots | keys in front of their home slot; per_value [n_values]
+__global__ __launch_bounds__(256)
+void k_alleles_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t shift, unsigned long long* out, uint32_t* per_value,
+                     uint32_t n_values)
+{
+    __shared__ unsigned long long sh[4];
+    if (threadIdx.x < 4) sh[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t mask = slots - 1;
+    unsigned long long distinct = 0, amb = 0, run_max = 0, wrapped = 0;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long key = table[s].key;
+        if (key == KEY_EMPTY) continue;
+        ++distinct;
+        const uint32_t v = table[s].value;
+        amb += v == BDG_GENES_AMBIGUOUS;
+        if (v < n_values) atomicAdd(&per_value[v], 1u);
+        wrapped += home_slot(key, shift) > s;
+        if (table[(s - 1) & mask].key == KEY_EMPTY) {               // a run starts here (there is always an empty slot: it ends)
+            unsigned long long run = 1;
+            for (uint64_t t = (s + 1) & mask; table[t].key != KEY_EMPTY; t = (t + 1) & mask) ++run;
+            run_max = run > run_max ? run : run_max;
+        }
+    }
+    if (distinct) atomicAdd(&sh[0], distinct);
+    if (amb) atomicAdd(&sh[1], amb);
+    if (run_max) atomicMax(&sh[2], run_max);
+    if (wrapped) atomicAdd(&sh[3], wrapped);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (sh[0]) atomicAdd(&out[0], sh[0]);
+        if (sh[1]) atomicAdd(&out[1], sh[1]);
+        if (sh[2]) atomicMax(&out[2], sh[2]);
+        if (sh[3]) atomicAdd(&out[3], sh[3]);
+    }
+}
+
+// the wave's parked records go out: one add on the call's cursor, then a lane per record; a place at or behind cap is not written
+__device__ __forceinline__ void flush_stage(const uint4* stage, uint32_t n_staged, uint32_t lane, uint4* out, uint64_t cap,
+                                            unsigned long long* counts)
+{
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(&counts[0], (unsigned long long)n_staged);
+    base = __shfl(base, 0);
+    for (uint32_t i = lane; i < n_staged; i += 64)
+        if (base + i < cap) out[base + i] = stage[i];
+    __syncthreads();   // (a block is one wave: the area is read before it is filled again)
+}
+
+__global__ __launch_bounds__(64)
+void k_alleles_assign(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ off, uint32_t n, uint32_t k,
+                      const bdg_gene_rec* __restrict__ genes, const uint8_t* __restrict__ has, uint32_t n_features,
+                      const GeneSlot* __restrict__ table, uint64_t mask, uint32_t shift, uint4* __restrict__ out, uint64_t cap,
+                      unsigned long long* counts)
+{
+    __shared__ uint32_t t_var[BDG_ALLELES_MAX_VARIANTS], t_ref[BDG_ALLELES_MAX_VARIANTS], t_alt[BDG_ALLELES_MAX_VARIANTS];
+    __shared__ uint4 stage[ALLELES_STAGE];
+    constexpr const bdg_cdna_span* spans = nullptr;
+    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
+    uint32_t n_staged = 0, n_crowded = 0;
+    for (uint32_t r = blockIdx.x; r < n; r += gridDim.x) {
+        const uint32_t f = genes[r].feature;
+        if (!(genes[r].flags & BDG_GENE_ASSIGNED) || f >= n_features || !has[f]) continue;   // none of its bases is read
+        const Whole rd = Whole::of(bases, off, spans, r);
+        uint32_t n_ent = 0;
+        bool crowded = false;
+        for (uint64_t p0 = 0; p0 + k <= rd.len && !crowded; p0 += 64 * GENES_CHUNKS) {
+            GENES_PROBE_CHUNKS(rd, p0, lane, kmask, table, mask, shift)
+            _Pragma("unroll")
+            for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {
+                const ulonglong2 g = got[c];
+                const uint32_t val = (uint32_t)g.y;
+                const bool hit = key[c] != KEY_EMPTY && g.x == key[c] && val < BDG_GENES_AMBIGUOUS && (uint32_t)(g.y >> 32) == f;
+                uint64_t live = crowded ? 0 : __ballot(hit);
+                while (live) {   // one round per distinct value among the 64
+                    const uint32_t v = __shfl(val, __ffsll((unsigned long long)live) - 1);
+                    const uint64_t same = __ballot(hit && val == v);
+                    const uint32_t cnt = __popcll(same), var = v >> 1, alt = v & 1u;
+                    live &= ~same;
+                    bool mine = false;
+                    uint32_t at = 0;
+                    for (uint32_t i = lane; i < n_ent; i += 64)
+                        if (t_var[i] == var) { mine = true; at = i; }
+                    if (__ballot(mine)) {
+                        if (mine) { if (alt) t_alt[at] += cnt; else t_ref[at] += cnt; }
+                    } else if (n_ent < BDG_ALLELES_MAX_VARIANTS) {
+                        if (lane == 0) { t_var[n_ent] = var; t_ref[n_ent] = alt ? 0u : cnt; t_alt[n_ent] = alt ? cnt : 0u; }
+                        ++n_ent;
+                    } else {
+                        crowded = true;
+                        live = 0;
+                    }
+                    __syncthreads();   // (a block is one wave: this orders the LDS traffic)
+                }
+            }
+        }
+        if (crowded) { ++n_crowded; continue; }
+        if (n_ent == 0) continue;
+        if (n_staged + n_ent > ALLELES_STAGE) {
+            flush_stage(stage, n_staged, lane, out, cap, counts);
+            n_staged = 0;
+        }
+        for (uint32_t i = lane; i < n_ent; i += 64) stage[n_staged + i] = make_uint4(r, t_var[i], t_ref[i], t_alt[i]);
+        n_staged += n_ent;
+        __syncthreads();   // the table is read: the next read may fill it
+    }
+    if (n_staged) flush_stage(stage, n_staged, lane, out, cap, counts);
+    if (lane == 0 && n_crowded) atomicAdd(&counts[1], (unsigned long long)n_crowded);
+}
+
+int alleles_cus(bdg_ctx* ctx)
+{
+    if (ctx->gn_cus == 0) {
+        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->gn_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        if (ctx->gn_cus <= 0) ctx->gn_cus = 1;
+    }
+    return BDG_OK;
+}
+
+int alleles_check_assign(bdg_ctx* ctx)
+{
+    if (ctx->al_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "alleles: no index built (bdg_alleles_index_build)");
+    return BDG_OK;
+}
+
+// d_counts is set to zero, then the kernel (n > 0)
+int alleles_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes,
+                          bdg_allele_rec* d_out, uint64_t cap, uint64_t* d_counts)
+{
+    BDG_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ctx->stream));
+    if (n == 0) return BDG_OK;
+    if (int rc = alleles_cus(ctx)) return rc;
+    if (ctx->al_assign_per_cu == 0) {
+        int per_cu = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_alleles_assign, 64, 0));
+        ctx->al_assign_per_cu = per_cu < 1 ? 1 : per_cu;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->al_assign_per_cu);
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->al_slots);
+    {
+        ScopedKernelTimer tm(ctx, "k_alleles_assign");
+        hipLaunchKernelGGL(k_alleles_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->al_k, d_genes,
+                           static_cast<const uint8_t*>(ctx->al_has.p), ctx->al_features, static_cast<const GeneSlot*>(ctx->al_table.p),
+                           ctx->al_slots - 1, shift, reinterpret_cast<uint4*>(d_out), cap, reinterpret_cast<unsigned long long*>(d_counts));
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
+
+void alleles_drop(bdg_ctx* ctx)
+{
+    ctx->al_table.reset();
+    ctx->al_has.reset();
+    ctx->al_slots = 0;
+    ctx->al_k = 0;
+    ctx->al_features = 0;
+    ctx->al_keys_per_value.clear();
+}
+
+}  // namespace
+
+extern "C" {
+
+int bdg_alleles_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* values,
+                            const uint32_t* genes, uint32_t n_variants, uint32_t n_features, uint32_t k)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "alleles: k out of range (11 .. 31)");
+    if (!seq_off || (n_seqs && !values) || (n_variants && !genes)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (n_variants >= 0x7FFFFFFFu) return bdg_fail(ctx, BDG_E_ARG, "alleles: too many variants");
+    for (uint32_t v = 0; v < n_variants; ++v)
+        if (genes[v] >= n_features) return bdg_fail(ctx, BDG_E_ARG, "alleles: gene of a variant out of range (>= n_features)");
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "alleles: sequence offsets must be non-decreasing");
+        if (values[q] >= 2u * n_variants) return bdg_fail(ctx, BDG_E_ARG, "alleles: value out of range (>= 2 * n_variants)");
+    }
+    const uint64_t end = seq_off[n_seqs];
+    if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    // windows with a key: the table's size follows from them
+    uint64_t windows = 0;
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        uint64_t run = 0;
+        for (uint64_t p = seq_off[q]; p < seq_off[q + 1]; ++p) {
+            const uint8_t c = bases[p];
+            run = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? run + 1 : 0;
+            windows += run >= k;
+        }
+    }
+    uint64_t slots = 64;
+    while (slots < 2 * windows) slots <<= 1;
+    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(slots);
+    std::vector<uint8_t> has((size_t)n_features + 1, 0);
+    for (uint32_t v = 0; v < n_variants; ++v) has[genes[v]] = 1;
+
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (a queued assign call may still read the earlier table)
+    alleles_drop(ctx);
+    int rc;
+    if ((rc = alleles_cus(ctx))) return rc;
+    // the sequences, their offsets and values, the variants' genes and the counters live for this call only
+    DevBuf d_bases, d_meta;
+    const size_t n_values = 2 * (size_t)n_variants;
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), val_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u,
+                 gene_b = (sizeof(uint32_t) * (size_t)n_variants + 7u) & ~(size_t)7u, stat_b = 4 * sizeof(uint64_t),
+                 kpv_b = sizeof(uint32_t) * n_values;
+    if ((rc = bdg_reserve(ctx, ctx->al_table, sizeof(GeneSlot) * (size_t)slots)) || (rc = bdg_reserve(ctx, ctx->al_has, has.size())) ||
+        (rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + val_b + gene_b + stat_b + kpv_b + 8))) {
+        alleles_drop(ctx);
+        return rc;
+    }
+    char* meta = static_cast<char*>(d_meta.p);
+    auto* d_off = reinterpret_cast<uint64_t*>(meta);
+    auto* d_val = reinterpret_cast<uint32_t*>(meta + off_b);
+    auto* d_gene = reinterpret_cast<uint32_t*>(meta + off_b + val_b);
+    auto* d_stats = reinterpret_cast<unsigned long long*>(meta + off_b + val_b + gene_b);
+    auto* d_kpv = reinterpret_cast<uint32_t*>(meta + off_b + val_b + gene_b + stat_b);
+    unsigned long long h_stats[4] = { 0, 0, 0, 0 };
+    std::vector<uint32_t> kpv(n_values, 0);
+    auto run = [&]() -> int {
+        if (end > seq_off[0])
+            BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
+        if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_val, values, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
+        if (n_variants) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_gene, genes, sizeof(uint32_t) * (size_t)n_variants, hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->al_has.p, has.data(), has.size(), hipMemcpyHostToDevice, st));
+        BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, stat_b + kpv_b, st));
+        BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->al_table.p, 0xFF, sizeof(GeneSlot) * (size_t)slots, st));   // every key EMPTY, every value NONE
+        if (n_seqs) {
+            ScopedKernelTimer tm(ctx, "k_alleles_insert");
+            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * ALLELES_INSERT_WAVES_PER_CU);
+            hipLaunchKernelGGL(k_alleles_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_val, d_gene,
+                               n_seqs, k, static_cast<GeneSlot*>(ctx->al_table.p), slots - 1, shift);
+        }
+        {
+            ScopedKernelTimer tm(ctx, "k_alleles_stats");
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->gn_cus * 8);
+            hipLaunchKernelGGL(k_alleles_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->al_table.p), slots, shift,
+                               d_stats, d_kpv, (uint32_t)n_values);
+        }
+        BDG_HIP_TRY(ctx, hipGetLastError());
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+        if (n_values) BDG_HIP_TRY(ctx, hipMemcpyAsync(kpv.data(), d_kpv, kpv_b, hipMemcpyDeviceToHost, st));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        return BDG_OK;
+    };
+    if ((rc = run())) {
+        (void)hipStreamSynchronize(st);                             // (the temporaries go with this frame)
+        alleles_drop(ctx);
+        return rc;
+    }
+    const uint64_t stats[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
+    memcpy(ctx->al_stats, stats, sizeof(stats));
+    ctx->al_keys_per_value.swap(kpv);
+    ctx->al_k = k;
+    ctx->al_features = n_features;
+    ctx->al_slots = slots;
+    return BDG_OK;
+}
+
+int bdg_alleles_index_stats(bdg_ctx* ctx, uint64_t out[6], uint32_t* keys_per_value)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = alleles_check_assign(ctx)) return rc;
+    memcpy(out, ctx->al_stats, sizeof(ctx->al_stats));
+    if (keys_per_value && !ctx->al_keys_per_value.empty())
+        memcpy(keys_per_value, ctx->al_keys_per_value.data(), sizeof(uint32_t) * ctx->al_keys_per_value.size());
+    return BDG_OK;
+}
+
+int bdg_alleles_index_values(bdg_ctx* ctx, uint32_t* n_values)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (!n_values) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = alleles_check_assign(ctx)) return rc;
+    *n_values = (uint32_t)ctx->al_keys_per_value.size();
+    return BDG_OK;
+}
+
+int bdg_alleles_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_gene_recs,
+                           bdg_allele_rec* d_out, uint64_t cap, uint64_t* d_counts)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = alleles_check_assign(ctx)) return rc;
+    if (!d_counts || (cap && !d_out) || (n && (!d_off || !d_gene_recs))) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return bdg_fail(ctx, BDG_E_ARG, "alleles: d_out must be aligned to 16 bytes (a record is one store)");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return alleles_assign_launch(ctx, d_bases, d_off, n, d_gene_recs, d_out, cap, d_counts);
+}
+
+int bdg_alleles_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_gene_rec* gene_recs,
+                       bdg_allele_rec* out, uint64_t cap, uint64_t counts[2])
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = alleles_check_assign(ctx)) return rc;
+    if (!counts || (cap && !out) || (n && (!off || !gene_recs))) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    counts[0] = counts[1] = 0;
+    if (n == 0) return BDG_OK;
+    for (uint32_t r = 0; r < n; ++r)
+        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "alleles: read offsets must be non-decreasing");
+    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // one input buffer behind the bases: the offsets, then the gene records; one output buffer: the two counts, then the records
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), gene_b = sizeof(bdg_gene_rec) * (size_t)n, cnt_b = 2 * sizeof(uint64_t);
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + gene_b))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, cnt_b + sizeof(bdg_allele_rec) * (size_t)cap))) return rc;
+    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
+    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
+    auto* d_genes = reinterpret_cast<bdg_gene_rec*>(static_cast<char*>(ctx->s_in1.p) + off_b);
+    auto* d_counts = static_cast<uint64_t*>(ctx->s_out0.p);
+    auto* d_out = reinterpret_cast<bdg_allele_rec*>(static_cast<char*>(ctx->s_out0.p) + cnt_b);
+    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_genes, gene_recs, gene_b, hipMemcpyHostToDevice, st));
+    if ((rc = alleles_assign_launch(ctx, d_bases, d_off, n, d_genes, d_out, cap, d_counts))) return rc;
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, cnt_b, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (counts[0] > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "alleles: " + std::to_string(counts[0]) + " records, more than the capacity");
+    if (counts[0]) {
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(bdg_allele_rec) * (size_t)counts[0], hipMemcpyDeviceToHost, st));
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
+    return BDG_OK;
+}
+
+}  // extern "C"

@@ -158,7 +158,16 @@ struct bdg_ctx {
     int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
     int gn_assign_sp_per_cu = 0, gn_iso_sp_per_cu = 0;   // the same of k_genes_assign_spans and k_iso_assign_spans
     DevBuf gn_spans;     // the spans of the chunk bdg_extract_collect computes kept gene records for (grow-only)
-    int em_cus = 0, em_per_cu = 0;           // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
+    // ---- allele index (alleles_kernels.hip): a second table of the same slots with its own k, replaced by the next
+    // bdg_alleles_index_build; building one table does not touch the other
+    DevBuf al_table;     // al_slots slots of {u64 key, u32 value, u32 gene}
+    DevBuf al_has;       // u8 per feature: the gene has a variant
+    uint64_t al_slots = 0;                   // a power of two; 0: no allele index
+    uint32_t al_k = 0, al_features = 0;
+    uint64_t al_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_alleles_index_stats
+    std::vector<uint32_t> al_keys_per_value;       // ... [2 * n_variants]
+    int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
+    int em_cus = 0, em_per_cu = 0;          // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -27,68 +27,27 @@
 // k_genes_assign_spans, k_iso_assign_spans   the two assign kernels over an interval of every read, as it stands or
 //                  reverse-complemented: the same bodies, only the byte a lane loads differs.  k_cdna_spans makes
 //                  the intervals from a chunk's extraction, trim and chimera records.
+//
+// The slot, the planes, the keys, insert_key and the probe macro GENES_PROBE_CHUNKS are in genes_probe.hpp, which
+// alleles_kernels.hip includes too.
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
+#include "genes_probe.hpp"
 
 #include <algorithm>
 
 namespace {
 
-constexpr unsigned long long KEY_EMPTY = ~0ull;              // no key of k <= 31 bases has bit 62 or 63 set
-constexpr unsigned long long HASH_MUL = 0x9E3779B97F4A7C15ull;
-constexpr uint32_t GENES_CHUNKS = 4;                         // chunks of 64 windows whose probes a wave has in flight
 constexpr uint32_t INSERT_WAVES_PER_CU = 16;                  // (k_genes_assign: as many as the device keeps resident, asked once)
 
-struct __align__(16) GeneSlot { unsigned long long key; uint32_t value, pad; };
 static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24 && sizeof(bdg_iso_rec) == 32 && sizeof(bdg_cdna_span) == 12,
               "layouts the header states");
 
-struct Planes { uint64_t lo, hi, nv; };
-
-__device__ __forceinline__ uint32_t base_code(uint32_t c)          // A 0, C 1, G 2, T 3, anything else 4
-{
-    return (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? ((c >> 1) ^ (c >> 2)) & 3u : 4u;
-}
-
-// this lane's byte of the positions p0 .. p0 + 63 of the sequence s; a position behind the end reads as N
-__device__ __forceinline__ uint32_t load_byte(const uint8_t* s, uint64_t len, uint64_t p0, uint32_t lane)
-{
-    const uint64_t p = p0 + lane;
-    return p < len ? s[p] : (uint32_t)'N';
-}
-
-// the planes of 64 positions from every lane's byte (bit i: lane i's position)
-__device__ __forceinline__ Planes planes_of(uint32_t byte)
-{
-    const uint32_t code = base_code(byte);
-    Planes P;
-    P.lo = __ballot((code & 1u) != 0);
-    P.hi = __ballot((code & 2u) != 0);
-    P.nv = __ballot((code & 4u) != 0);
-    return P;
-}
-
-__device__ __forceinline__ Planes load_planes(const uint8_t* s, uint64_t len, uint64_t p0, uint32_t lane)
-{
-    return planes_of(load_byte(s, len, p0, lane));
-}
-
-// Where the 64 bytes of a chunk come from, for the probe below.  Whole: the sequence as it lies, off[r] .. off[r + 1].  Span: an
-// interval of it, as it stands or reverse-complemented (include/badger_hip.h at bdg_cdna_span) - position p is the
-// byte begin + p, or under rc the byte end - 1 - p, whose code is complemented where the planes are made: 3 - code is both code
-// bits flipped, two scalar operations on wave-uniform planes.  Descending addresses inside a wave are one line like ascending
-// ones; a position behind the span's end is N, so nothing outside the span is read.
-struct Whole {
-    const uint8_t* s; uint64_t len;
-    static __device__ __forceinline__ Whole of(const uint8_t* bases, const uint64_t* off, const bdg_cdna_span*, uint32_t r)
-    {
-        const uint64_t b = off[r], e = off[r + 1];
-        return Whole{ bases + b, e > b ? e - b : 0 };
-    }
-    __device__ __forceinline__ uint32_t byte(uint64_t p0, uint32_t lane) const { return load_byte(s, len, p0, lane); }
-    __device__ __forceinline__ Planes planes(uint32_t b) const { return planes_of(b); }
-};
-
+// Span: an interval of a sequence, as it stands or reverse-complemented (include/badger_hip.h at bdg_cdna_span),
+// beside genes_probe.hpp's Whole - position p is the byte begin + p, or under rc the byte end - 1 - p, whose code is complemented
+// where the planes are made: 3 - code is both code bits flipped, two scalar operations on wave-uniform planes.  Descending
+// addresses inside a wave are one line like ascending ones; a position behind the span's end is N, so nothing outside the span
+// is read.
 struct Span {
     const uint8_t* first; uint64_t len; bool rc;                   // first: the byte of position 0
     static __device__ __forceinline__ Span of(const uint8_t* bases, const uint64_t* off, const bdg_cdna_span* spans, uint32_t r)
@@ -112,54 +71,6 @@ struct Span {
         return P;
     }
 };
-
-// bits lane .. lane + 31 of the 128 bits a1 : a0
-__device__ __forceinline__ uint32_t window32(uint64_t a0, uint64_t a1, uint32_t lane)
-{
-    return (uint32_t)(lane ? (a0 >> lane) | (a1 << (64u - lane)) : a0);
-}
-
-__device__ __forceinline__ uint64_t spread_bits(uint32_t x)        // bit i -> bit 2 i
-{
-    uint64_t v = x;
-    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
-    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
-    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
-    v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & 0x5555555555555555ull;
-    return v;
-}
-
-// the key of the window that starts at this lane's position of chunk A (B: the chunk behind it); KEY_EMPTY: it has none
-__device__ __forceinline__ unsigned long long window_key(const Planes& A, const Planes& B, uint32_t lane, uint32_t kmask)
-{
-    if (window32(A.nv, B.nv, lane) & kmask) return KEY_EMPTY;
-    return spread_bits(window32(A.lo, B.lo, lane) & kmask) | (spread_bits(window32(A.hi, B.hi, lane) & kmask) << 1);
-}
-
-__device__ __forceinline__ uint64_t home_slot(unsigned long long key, uint32_t shift) { return (key * HASH_MUL) >> shift; }
-
-__device__ __forceinline__ void insert_key(GeneSlot* table, uint64_t mask, uint32_t shift, unsigned long long key, uint32_t f)
-{
-    uint64_t s = home_slot(key, shift);
-    for (;;) {                                                      // (at most half of the slots are ever taken: it ends)
-        unsigned long long cur = __hip_atomic_load(&table[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == KEY_EMPTY) {
-            cur = atomicCAS(&table[s].key, KEY_EMPTY, key);
-            if (cur == KEY_EMPTY) cur = key;
-        }
-        if (cur == key) break;
-        s = (s + 1) & mask;
-    }
-    // the value only ever goes NONE -> a feature -> AMBIGUOUS
-    uint32_t v = __hip_atomic_load(&table[s].value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (v == f || v == BDG_GENES_AMBIGUOUS) return;
-    if (v == BDG_GENES_NONE) {
-        v = atomicCAS(&table[s].value, BDG_GENES_NONE, f);
-        if (v == BDG_GENES_NONE || v == f) return;
-    }
-    if (v != BDG_GENES_AMBIGUOUS) __hip_atomic_store(&table[s].value, BDG_GENES_AMBIGUOUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __global__ __launch_bounds__(64)
 void k_genes_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ features,
@@ -216,52 +127,6 @@ void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t 
         if (sh[3]) atomicAdd(&out[3], sh[3]);
     }
 }
-
-// The probe of GENES_CHUNKS x 64 windows, stated once for k_genes_assign and k_iso_assign and their span forms (rd: a Whole or
-// a Span).  It declares, in the caller's scope,
-// key[c] (this lane's key of chunk c, KEY_EMPTY: none), got[c] (the slot its chain ends at: its key's, or an empty one) and
-// sl[c] (that slot's index).  Every first probe is on its way before one is looked at (a lane without a key reads slot 0 and
-// drops it: no branch around a load and no arithmetic between two of them).  The chains: a window whose home slot holds
-// another key goes on, all four chunks in step and two slots a round, so that a round is one trip to memory for the wave - the
-// longest chain among its 256 windows, halved, is what it waits for, not the sum over the chunks.  A lane that is done reads
-// slot 0 and drops it.  A macro and not a function: through an inlined function's array references the same statements cost
-// k_genes_assign 8 VGPRs more (84, a resident wave per SIMD fewer); as a macro its code is what it was, instruction for
-// instruction.
-#define GENES_PROBE_CHUNKS(rd, p0, lane, kmask, table, mask, shift)                                                                          \
-    uint32_t byte[GENES_CHUNKS + 1];                                                                                                     \
-    Planes P[GENES_CHUNKS + 1];                                                                                                          \
-    _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) byte[c] = rd.byte(p0 + 64 * c, lane);                                                   \
-    _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c <= GENES_CHUNKS; ++c) P[c] = rd.planes(byte[c]);                                                              \
-    unsigned long long key[GENES_CHUNKS];                                                                                                \
-    ulonglong2 got[GENES_CHUNKS];                                                                                                        \
-    _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) key[c] = window_key(P[c], P[c + 1], lane, kmask);                                        \
-    uint64_t sl[GENES_CHUNKS];                                                                                                           \
-    _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) sl[c] = key[c] != KEY_EMPTY ? home_slot(key[c], shift) : 0;                              \
-    _Pragma("unroll")                                                                                                                    \
-    for (uint32_t c = 0; c < GENES_CHUNKS; ++c) got[c] = *reinterpret_cast<const ulonglong2*>(table + sl[c]);                            \
-    for (;;) {                                                                                                                           \
-        bool open[GENES_CHUNKS], any = false;                                                                                            \
-        _Pragma("unroll")                                                                                                                \
-        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) any |= open[c] = key[c] != KEY_EMPTY && got[c].x != KEY_EMPTY && got[c].x != key[c]; \
-        if (!__any(any)) break;                                                                                                          \
-        ulonglong2 t1[GENES_CHUNKS], t2[GENES_CHUNKS];                                                                                   \
-        _Pragma("unroll")                                                                                                                \
-        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                    \
-            t1[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 1) & mask : 0));                                    \
-            t2[c] = *reinterpret_cast<const ulonglong2*>(table + (open[c] ? (sl[c] + 2) & mask : 0));                                    \
-        }                                                                                                                                \
-        _Pragma("unroll")                                                                                                                \
-        for (uint32_t c = 0; c < GENES_CHUNKS; ++c) {                                                                                    \
-            if (!open[c]) continue;                                                                                                      \
-            const bool ends = t1[c].x == KEY_EMPTY || t1[c].x == key[c];                                                                 \
-            got[c] = ends ? t1[c] : t2[c];                                                                                               \
-            sl[c] = (sl[c] + (ends ? 1 : 2)) & mask;                                                                                     \
-        }                                                                                                                                \
-    }
 
 // The body of k_genes_assign (READ = Whole) and k_genes_assign_spans (READ = Span), stated once.  A macro and not an inlined
 // function template, for GENES_PROBE_CHUNKS' reason: called through a forceinline function the forward kernel comes out of the

@@ -5,6 +5,7 @@ that every read and molecule is compatible with.
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                [--umi_per_gene --umi_len L [--gene_umi_dist 0|1 | --gene_umi_dist2]]
+                               [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -770,7 +771,7 @@ def em_files(names, tx_names, feat, cells, molecules, run, eps=EM_EPS_DEFAULT, m
     return {"isoform_em_matrix.mtx": "".join(rows).encode(), "isoform_em_pool.tsv": "".join(pool_rows).encode()}, counts
 
 
-def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None):
+def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None, alleles=None):
     """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
     assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
     -> ({file name: bytes}, counts dict).  With isoforms = (transcript names, their feature ids) assign returns the pair
@@ -778,7 +779,9 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None
     With em = (run, eps, max_iter, init) beside isoforms (em_files) the two files of EM_FILES and their counts join those.
     With per_gene = (run, umi_len, umi_dist) (--umi_per_gene; run as for molecules_per_gene) the molecules are made per cell and
     gene from the headers' UR: matrix.mtx and the isoform and EM matrices follow them, gene_molecules.tsv joins the files, the
-    other files stay the same bytes."""
+    other files stay the same bytes.
+    With alleles (--variants; an alleles.Caller) the four files of alleles.FILES and their counts join; every other file stays
+    the same bytes."""
     from .consensus import parse_tagged
     heads, seqs, cb, ub = parse_tagged(text)
     take = [i for i, c in enumerate(cb) if c is not None]
@@ -789,14 +792,15 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None
     heads = [heads[i] for i in take]
     return count_matrix_records([h.split(b"\t")[0] for h in heads], [cb[i] for i in take], [ub[i] for i in take],
                                 _ur_texts(heads) if per_gene is not None else None, recs, names, iso, isoforms, em, per_gene,
-                                len(cb) - len(take))
+                                len(cb) - len(take), None if alleles is None else lambda *a: alleles([seqs[i] for i in take], *a))
 
 
-def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, em=None, per_gene=None, no_cell=0):
+def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, em=None, per_gene=None, no_cell=0, alleles=None):
     """what count_matrix_text does behind the parse and the gene calls, for both routes to the matrix.  Per read that has a cell:
     ids its name, cb its cell, ub its molecule or None (all bytes), ur its UMI text or None (looked at with per_gene only), recs
     REC_DTYPE, iso ISO_DTYPE with isoforms; names, isoforms, em, per_gene as for count_matrix_text; no_cell: reads left out for
-    want of a cell, for the log -> ({file name: bytes}, counts dict)"""
+    want of a cell, for the log; alleles: the hook of --variants, called with (ids, cb, ub, recs, the barcodes, per read its
+    molecule text with per_gene or None) -> ({file name: bytes}, counts dict)"""
     if per_gene is not None:
         made = molecules_per_gene(cb, ur, recs, per_gene[0], per_gene[1], per_gene[2], iso)
     else:
@@ -814,8 +818,13 @@ def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, 
              "barcodes.tsv": b"".join(c + b"\n" for c in cells),
              "matrix.mtx": _mtx(len(names), len(cells), entries),
              "reads.tsv": "".join(rows).encode()}
+    rows = counts.pop("rows") if per_gene is not None else None
     if per_gene is not None:
-        files["gene_molecules.tsv"] = gene_molecules_text(names, ids, cb, ur, recs, counts.pop("rows"))
+        files["gene_molecules.tsv"] = gene_molecules_text(names, ids, cb, ur, recs, rows)
+    if alleles is not None:
+        more, allele_counts = alleles(ids, cb, ub, recs, cells, rows)
+        files.update(more)
+        counts.update(allele_counts)
     if isoforms is not None:
         more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], ids, cb, ub, iso, cells, molecules)
         files.update(more)
@@ -924,22 +933,27 @@ def device_em(ctx):
 
 
 def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None,
-                           em=None, per_gene=None):
+                           em=None, per_gene=None, variants=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
     reads.tsv, with iso_margin (--isoforms) the files of ISO_FILES, and with em = (eps, max_iter, init) (--isoform_em) those of
     EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
-    (bdg_umi_dedup_genes) and gene_molecules.tsv -> counts"""
-    from . import _native
+    (bdg_umi_dedup_genes) and gene_molecules.tsv, and with variants = (path, k, min_hits) (--variants) the allele table beside
+    the genes table and the files of alleles.FILES -> counts"""
+    from . import _native, alleles
     ctx = _native.default_context(device)
     names, tx_names, feat = _build_index(ctx, transcripts, tx2gene, k, iso_margin)
     try:
         stats = ctx.genes_index_stats()
+        caller = alleles.device_caller(ctx, variants[0], transcripts, names, feat, bool(tx2gene), variants[1], variants[2]) \
+            if variants else None
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
                                           (tx_names, feat) if iso_margin else None,
                                           (device_em(ctx),) + tuple(em) if iso_margin and em else None,
-                                          (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None)
+                                          (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None, caller)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         _drop_index(ctx, k)
+        if variants:
+            alleles.drop_index(ctx)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
     os.makedirs(out_dir, exist_ok=True)
     for name, data in files.items():
@@ -1184,6 +1198,8 @@ def parse_args(argv):
     p.add_argument("-o", "--output", required=True,
                    help="directory for features.tsv, barcodes.tsv, matrix.mtx and reads.tsv (and the files of --isoforms)")
     add_gene_options(p)
+    from .alleles import add_allele_options, check_allele_options
+    add_allele_options(p)
     p.add_argument("--umi_len", type=gene_umi_len_arg, default=None, metavar="L",
                    help="--umi_per_gene: letters of the library's UMI, 3 .. 12 (a UMI is usable at L - 2 .. L + 2 letters)")
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
@@ -1197,6 +1213,7 @@ def parse_args(argv):
     if a.umi_per_gene and a.umi_len is None:
         p.error("--umi_per_gene needs --umi_len: the tagged file does not say how many letters the library's UMI has")
     a.per_gene = (a.umi_len, a.gene_umi_dist) if a.umi_per_gene else None
+    check_allele_options(p, a, True)
     return a
 
 
@@ -1205,8 +1222,11 @@ def main(argv):
     logger.setLevel(logging.INFO)
     if not logger.handlers:
         logger.addHandler(logging.StreamHandler(stream=sys.stdout))
-    log_counts(count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
-                                      a.em, a.per_gene), a.output)
+    from .alleles import log_counts as log_allele_counts
+    counts = count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
+                                    a.em, a.per_gene, a.alleles)
+    log_counts(counts, a.output)
+    log_allele_counts(counts, a.output)
 
 
 if __name__ == "__main__":

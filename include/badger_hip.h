@@ -1140,6 +1140,54 @@ int  bdg_umi_dedup_genes(bdg_ctx* ctx, const uint32_t* cell, const bdg_gene_rec*
  * is the default. */
 int  bdg_umi_dedup_genes_set_aggregate(bdg_ctx* ctx, int on);
 
+/* ---- allele counts at known SNVs by k-mer lookup (--variants; checker: badger_amd/alleles.py) ---- */
+#define BDG_ALLELES_K_DEFAULT   15
+#define BDG_ALLELES_MAX_VARIANTS 256         /* distinct variants a read may hit before it is crowded */
+typedef struct { uint32_t read, variant, ref_hits, alt_hits; } bdg_allele_rec;   /* 16 bytes */
+/* THE RULE.  Bases, codes and keys as for bdg_genes_index_build, with the allele table's own k, 11 .. 31.
+ *   variant  a single-base site known in one or more transcripts of one gene, with a reference and an alternative letter;
+ *            variants are numbered from 0, value 2 v + a names allele a of variant v (a = 0: ref, 1: alt).
+ *   sequence for an occurrence of the site at the 0-based position p of a transcript T of length L and an allele a: the bases
+ *            T[max(0, p - k + 1) .. min(L, p + k) - 1] with T[p] replaced by the allele's letter - every window of k bases
+ *            that covers the site.  The caller makes these sequences; sequence q carries values[q] < 2 * n_variants.
+ *   index    the keys of the windows of the sequences that have one (no N).  value(key) is values[q] if every sequence that
+ *            holds the key has that value, otherwise BDG_GENES_AMBIGUOUS.  gene(key) is genes[value(key) >> 1], the feature id
+ *            of the variant's gene (genes: one entry per VARIANT, each < n_features); it is only ever used for a key whose
+ *            value is not ambiguous.  Consequences: isoforms that share a site share its keys and nothing becomes ambiguous;
+ *            of two sites fewer than k bases apart the windows that carry both reference letters are ambiguous, those that
+ *            carry one alternative letter vote for it, and those that carry both are in no table.
+ *   read     the reads and gene records of bdg_genes_assign.  A read takes part iff its gene record is ASSIGNED, to a feature
+ *            g < n_features that has at least one variant.  Over its windows, hits[value] += 1 for every window whose key is
+ *            stored with value < BDG_GENES_AMBIGUOUS and gene(key) == g.  Every variant v with hits[2 v] + hits[2 v + 1] > 0
+ *            yields one record { read, v, hits[2 v], hits[2 v + 1] }.  A read that hits more than BDG_ALLELES_MAX_VARIANTS
+ *            distinct variants yields no record and is counted as crowded.
+ *   result   the set of records (their order is not part of it), the number of records and the number of crowded reads.
+ * The table is a second one beside the genes table (the same slots, open addressing and home slot; gene(key) lives in the
+ * slot's fourth word): building one does not touch the other.  It replaces an earlier allele table and goes with bdg_free.
+ * n_seqs == 0 leaves a 64-slot empty table.  Synchronous.  BDG_E_ARG for k outside 11 .. 31, a value >= 2 * n_variants, a gene
+ * >= n_features, offsets that decrease, null pointers. */
+int  bdg_alleles_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* values,
+                             const uint32_t* genes, uint32_t n_variants, uint32_t n_features, uint32_t k);
+/* out: the six figures of bdg_genes_index_stats, of the allele table.  keys_per_value [2 * n_variants], or NULL: per value the
+ * number of its keys that are not ambiguous - 0 says that this allele of this variant can never be seen. */
+int  bdg_alleles_index_stats(bdg_ctx* ctx, uint64_t out[6], uint32_t* keys_per_value);
+/* *n_values = 2 * n_variants of the allele table the context holds now: the entries bdg_alleles_index_stats writes to
+ * keys_per_value, for a caller that did not make the build itself.  BDG_E_ARG without an allele index. */
+int  bdg_alleles_index_values(bdg_ctx* ctx, uint32_t* n_values);
+/* Reads as for bdg_genes_assign_dev; d_gene_recs [n] what it wrote for them.  d_out [cap] takes the records in no particular
+ * order, d_counts [2] = { records, crowded reads }, both set by the call.  The record count is exact whatever cap is; when it
+ * exceeds cap the first cap places of d_out hold some of the records and nothing else of the output is meaningful (the contract
+ * of bdg_split_batch_dev).  A read that does not take part costs its gene record and nothing else: none of its bases is read.
+ * d_out must be aligned to 16 bytes: a record goes out as one 16-byte store (what hipMalloc and bdg_mem_alloc return is).
+ * Asynchronous, on the context's stream.  BDG_E_ARG without an allele index, for null pointers (d_out may be NULL when
+ * cap == 0) and for a d_out that is not so aligned. */
+int  bdg_alleles_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_gene_recs,
+                            bdg_allele_rec* d_out, uint64_t cap, uint64_t* d_counts);
+/* The same over host arrays, synchronous.  counts [2] is always set; BDG_E_CAPACITY when counts[0] > cap (call again with
+ * that much room).  Also BDG_E_ARG for decreasing offsets. */
+int  bdg_alleles_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_gene_rec* gene_recs,
+                        bdg_allele_rec* out, uint64_t cap, uint64_t counts[2]);
+
 /* ---- isoform abundances by EM over compatibility counts (--isoform_em; checker: badger_amd/genes.py em_tcc) ---- */
 #define BDG_EM_CLOSED           1u           /* bdg_em_info.flags: no iteration was needed (or there was nothing to do) */
 #define BDG_EM_CONVERGED        2u           /* ... delta < eps after `iters` iterations */

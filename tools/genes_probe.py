@@ -39,6 +39,14 @@ over its class counts, one JSON line each to --out (and stdout).
     python tools/genes_probe.py --cli --spans ...
         the command line with --umi_dedup --count_matrix --matrix_from_reads against --umi_dedup --tagged_reads --count_matrix,
         the pair once more with --isoforms --isoform_em --umi_per_gene, then the pairs with --parent as above.
+    python tools/genes_probe.py --device --alleles [--reads 1000000] [--tx_bases 4000000] --out profiles/r28_alleles.jsonl
+        the first workload once more with 4 sites planted per transcript, then with sites on one transcript in ten:
+        bdg_alleles_index_build (k_alleles_insert, k_alleles_stats, the whole call) and bdg_alleles_assign_dev behind
+        bdg_genes_assign_dev on the same reads: k_alleles_assign beside k_genes_assign from the event timers of the same run,
+        the median of --reps runs each.
+    python tools/genes_probe.py --cli --alleles ...
+        the command line with --count_matrix --variants against --count_matrix alone (4 sites per transcript), then the pairs
+        with --parent as above.
 """
 import argparse
 import os
@@ -137,6 +145,95 @@ def device_probe(args):
         for a in d + [d_out]:
             a.free()
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+
+
+def device_probe_alleles(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    ak, sites_per_tx = 15, 4
+    for tx_bases in args.tx_bases:
+        n_tx = max(tx_bases // TX_LEN, 1)
+        rng = np.random.default_rng(7)
+        tx = rng.integers(0, 4, (n_tx, TX_LEN), dtype=np.uint8)
+        bases, off = fragments(tx, args.reads)
+        n = len(off) - 1
+        tx_ascii, tx_off = ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64)
+        ctx.genes_index_build(tx_ascii, tx_off, np.arange(n_tx, dtype=np.uint32), args.k)
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off)]
+        d_gene = _native.DeviceArray(ctx, n * 6, np.uint32)
+        for every in (1, 10):
+            # the allele sequences of sites_per_tx sites in the last 1,500 bases of every `every`-th transcript: 2 k - 1 bases each
+            which = np.arange(0, n_tx, every)
+            pos = TX_LEN - 1500 + np.sort(rng.integers(ak, 1500 - ak, (len(which), sites_per_tx)), axis=1)
+            t_of, p_of = np.repeat(which, sites_per_tx), pos.ravel()
+            win = tx[t_of[:, None], p_of[:, None] + np.arange(1 - ak, ak)[None, :]]
+            alt = win.copy()
+            alt[:, ak - 1] = (alt[:, ak - 1] + rng.integers(1, 4, len(alt), dtype=np.uint8)) & 3
+            seqs = ACGT[np.stack([win, alt], axis=1).reshape(-1, 2 * ak - 1)]
+            values = np.arange(2 * len(t_of), dtype=np.uint32)
+            seq_off = (np.arange(len(seqs) + 1) * (2 * ak - 1)).astype(np.uint64)
+            genes = t_of.astype(np.uint32)
+            build = lambda: ctx.alleles_index_build(seqs.ravel(), seq_off, values, genes, n_tx, ak)  # noqa: E731
+            build()
+            ctx.profile(True)
+            ctx.profile_reset()
+            t0 = time.perf_counter()
+            build()
+            build_s = time.perf_counter() - t0
+            build_kt = {k: round(v[1], 4) for k, v in ctx.profile_read().items() if k.startswith("k_alleles") and v[0]}
+            ctx.profile(False)
+            stats, per_value = ctx.alleles_index_stats()
+            cap = 8 * n
+            d_out, d_counts = _native.DeviceArray(ctx, cap * 4, np.uint32), _native.DeviceArray(ctx, 2, np.uint64)
+
+            def call():
+                ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, d_gene)
+                ctx.alleles_assign_dev(d[0], d[1], n, d_gene, d_out, cap, d_counts)
+            call()
+            ctx.synchronize()
+            per_run = {}
+            ctx.profile(True)
+            for _ in range(args.reps):
+                ctx.profile_reset()
+                call()
+                ctx.synchronize()
+                for k, v in ctx.profile_read().items():
+                    if k in ("k_genes_assign", "k_alleles_assign") and v[0]:
+                        per_run.setdefault(k, []).append(v[1])
+            ctx.profile(False)
+            counts = d_counts.to_host()
+            recs = d_out.to_host().view(_native.ALLELE_DTYPE)[:int(counts[0])]
+            gene_recs = d_gene.to_host().view(_native.GENE_DTYPE)
+            emit(args.out, {"what": "bdg_alleles_index_build, bdg_alleles_assign_dev behind bdg_genes_assign_dev, device-resident",
+                            "allele_k": ak, "gene_k": args.k, "transcripts": n_tx, "transcripts_with_sites": len(which),
+                            "variants": len(t_of), "table_bytes": 16 * int(stats[3]),
+                            "stats": dict(zip(("windows", "keys", "ambiguous", "slots", "longest_run", "wrapped"), [int(x) for x in stats])),
+                            "values_without_a_key": int((per_value == 0).sum()),
+                            "build_wall_s": round(build_s, 4), "build_kernel_ms": build_kt, "reads": n, "read_bases": int(off[-1]),
+                            "reads_assigned": int((gene_recs["flags"] & 1 != 0).sum()), "records": int(counts[0]), "crowded": int(counts[1]),
+                            "reads_with_a_record": int(len(np.unique(recs["read"]))), "ref_hits": int(recs["ref_hits"].sum(dtype=np.int64)),
+                            "alt_hits": int(recs["alt_hits"].sum(dtype=np.int64)), "reps": args.reps,
+                            "kernel_ms_median": {k: round(float(np.median(v)), 4) for k, v in per_run.items()},
+                            "kernel_ms_runs": {k: [round(x, 4) for x in v] for k, v in per_run.items()},
+                            "alleles_over_genes": round(float(np.median(per_run["k_alleles_assign"]) / np.median(per_run["k_genes_assign"])), 4)})
+            d_out.free()
+            d_counts.free()
+        for a in d + [d_gene]:
+            a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+    ctx.alleles_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0, ak)
+
+
+def _variants_of(tx, path, per_tx=4):
+    """per_tx sites, evenly spread, in every transcript of a FASTA (name line, sequence line) that has no N there"""
+    with open(tx, "rb") as f, open(path, "wb") as out:
+        for name in f:
+            name, s = name[1:].strip(), f.readline().strip().upper()
+            for j in range(per_tx):
+                p = (j + 1) * len(s) // (per_tx + 1)
+                if s[p:p + 1] in (b"A", b"C", b"G", b"T"):
+                    out.write(b"%s.%d\t%s\t%d\t%s\t%s\n" % (name, j, name, p + 1, s[p:p + 1], b"CGTA"[b"ACGT".index(s[p:p + 1]):][:1]))
 
 
 def iso_transcriptome(n_tx, seed=7):
@@ -449,7 +546,7 @@ def cli_probe(args):
         r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
-        return time.perf_counter() - t0, [l.split(" - ")[-1] for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l]
+        return time.perf_counter() - t0, [l.split(" - ")[-1].replace(tmp, "TMP") for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l or "Alleles: " in l]
 
     def pairs(name_a, a, name_b, b, what):
         walls, said = {name_a: [], name_b: []}, []
@@ -478,6 +575,12 @@ def cli_probe(args):
             matrix = ["--umi_dedup"] + gene + ["--count_matrix", os.path.join(tmp, "matrix")]
             pairs("tagged_route", (ROOT, matrix + ["--tagged_reads", fa]), "from_reads", (ROOT, matrix + ["--matrix_from_reads"]),
                   "stage2 CLI from FASTQ, --umi_dedup --count_matrix%s: --matrix_from_reads against --tagged_reads" % what)
+    elif args.alleles:
+        var = os.path.join(tmp, "variants.tsv")
+        _variants_of(tx, var)
+        matrix = tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]
+        pairs("count_matrix", (ROOT, matrix), "variants", (ROOT, matrix + ["--variants", var]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix: with --variants (4 sites per transcript) against without")
     elif args.isoforms:
         tx2, tx_map = os.path.join(tmp, "tx_iso.fa"), os.path.join(tmp, "tx2gene.tsv")
         _isoforms_of(tx, tx2, tx_map)
@@ -509,6 +612,7 @@ def main():
     p.add_argument("--isoforms", action="store_true", help="the isoform leg of --device and of --cli (DESIGN 4.20)")
     p.add_argument("--margin", type=int, default=1)
     p.add_argument("--spans", action="store_true", help="the span kernels beside the forward ones (--device), --matrix_from_reads (--cli) (DESIGN 4.25)")
+    p.add_argument("--alleles", action="store_true", help="the allele leg of --device and of --cli (DESIGN 4.26)")
     p.add_argument("--em", action="store_true", help="k_em_tcc alone; with --cli --isoforms the --isoform_em leg (DESIGN 4.21)")
     p.add_argument("--em_problems", type=int, default=1000000)
     p.add_argument("--em_wide", type=int, default=100000)
@@ -521,7 +625,7 @@ def main():
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
-        (device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
+        (device_probe_alleles if args.alleles else device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
     if args.em and not args.cli:
         em_probe(args)
     if args.cli:
