@@ -71,6 +71,12 @@ EM_CLASS_DTYPE = np.dtype([("mask", "<u8"), ("count", "<u4"), ("pad", "<u4")])
 EM_INFO_DTYPE = np.dtype([("iters", "<u4"), ("flags", "<u4"), ("lost", "<u4"), ("pad", "<u4")])
 EM_CLOSED, EM_CONVERGED, EM_MAXITER, EM_RANGE = 1, 2, 4, 8
 EM_EPS_DEFAULT, EM_MAX_ITER_DEFAULT = 1e-3, 1000
+# bdg_donor_entry / bdg_donor_rec: a cell's molecules at a variant and the cell's best hypotheses (bdg_donor_scores; the rule in
+# badger_amd/donors.py)
+DONOR_ENTRY_DTYPE = np.dtype([("variant", "<u4"), ("ref", "<u4"), ("alt", "<u4"), ("pad", "<u4")])
+DONOR_DTYPE = np.dtype([("best_score", "<i8"), ("second_score", "<i8"), ("doublet_score", "<i8"), ("donor1", "<u4"), ("donor2", "<u4"),
+                        ("pair", "<u4"), ("pad", "<u4")])
+DONORS_MAX, DONOR_NONE = 32, 0xFFFFFFFF
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -113,6 +119,7 @@ EXPORTS = [
     "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
     "bdg_alleles_index_build", "bdg_alleles_index_stats", "bdg_alleles_assign_dev", "bdg_alleles_assign",
     "bdg_alleles_index_values",
+    "bdg_donor_scores", "bdg_donor_scores_dev",
 ]
 
 
@@ -408,6 +415,8 @@ def load():
     L.bdg_alleles_index_values.argtypes = [vp, C.POINTER(u32)]
     L.bdg_alleles_assign_dev.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
     L.bdg_alleles_assign.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
+    L.bdg_donor_scores.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
+    L.bdg_donor_scores_dev.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -948,6 +957,34 @@ class Context:
         self._check(self.lib.bdg_em_tcc_dev(self.h, _ptr(d_classes), _ptr(d_prob_off), int(n), _ptr(d_out_off),
                                             _ptr(d_start) if d_start is not None else None, float(eps), int(max_iter), _ptr(d_alpha),
                                             _ptr(d_info)))
+
+    def donor_scores(self, entries, cell_off, geno, n_donors, tables, with_scores=False):
+        """the donor records of the cells over host arrays (bdg_donor_scores): entries DONOR_ENTRY_DTYPE, cell c the entries
+        cell_off[c] .. cell_off[c + 1] - 1, geno uint64 per variant (donor i's dosage in bits 2 i, 2 i + 1), tables int32 [10]
+        (A_0 .. A_4, B_0 .. B_4) -> DONOR_DTYPE [n_cells], and with with_scores the int64 matrix [n_cells, H] behind it"""
+        entries = np.ascontiguousarray(entries, dtype=DONOR_ENTRY_DTYPE)
+        cell_off = np.ascontiguousarray(cell_off, dtype=np.uint64)
+        geno = np.ascontiguousarray(geno, dtype=np.uint64)
+        tables = np.ascontiguousarray(tables, dtype=np.int32)
+        n, d = len(cell_off) - 1, int(n_donors)
+        if n < 0 or len(tables) != 10 or (n and int(cell_off.max()) > len(entries)):
+            raise ValueError("cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values")
+        recs = np.zeros(n, dtype=DONOR_DTYPE)
+        h = d + d * (d - 1) // 2 if 1 <= d <= DONORS_MAX else 0
+        scores = np.zeros((n, h), dtype=np.int64) if with_scores else None
+        self._check(self.lib.bdg_donor_scores(self.h, entries.ctypes.data if len(entries) else None, cell_off.ctypes.data, n,
+                                              geno.ctypes.data if len(geno) else None, len(geno), d, tables.ctypes.data,
+                                              recs.ctypes.data, scores.ctypes.data if with_scores and scores.size else None))
+        return (recs, scores) if with_scores else recs
+
+    def donor_scores_dev(self, d_entries, d_cell_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, d_scores=None):
+        """bdg_donor_scores_dev: the same over device arrays (tables a host array; d_scores None: no matrix), asynchronous"""
+        tables = np.ascontiguousarray(tables, dtype=np.int32)
+        if len(tables) != 10:
+            raise ValueError("ten table values")
+        self._check(self.lib.bdg_donor_scores_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_geno), int(n_variants),
+                                                  int(n_donors), tables.ctypes.data, _ptr(d_recs),
+                                                  _ptr(d_scores) if d_scores is not None else None))
 
     def device_to_host(self, ptr, n, dtype):
         """n elements of a device array the context holds (a kept array) as a numpy array; waits for the context's stream"""

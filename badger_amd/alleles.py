@@ -268,10 +268,12 @@ def read_alleles_text(variants, ids, cb, ub, recs, calls):
 
 class Caller:
     """the hook of genes.count_matrix_records.  assign(seqs, gene_recs) -> (REC_DTYPE, crowded) is assign_reads over an Index or
-    the device's equivalent (device_assign); keys_per_value as Index.stats / Context.alleles_index_stats give it"""
+    the device's equivalent (device_assign); keys_per_value as Index.stats / Context.alleles_index_stats give it; donors: None, or
+    the hook of --donor_genotypes (a donors.Demux), called with the barcodes and the two allele counts -> more files and counts"""
 
-    def __init__(self, variants, names, keys_per_value, assign, min_hits=MIN_HITS_DEFAULT):
+    def __init__(self, variants, names, keys_per_value, assign, min_hits=MIN_HITS_DEFAULT, donors=None):
         self.variants, self.names, self.keys_per_value, self.assign, self.min_hits = variants, names, keys_per_value, assign, min_hits
+        self.donors = donors
 
     def __call__(self, seqs, ids, cb, ub, gene_recs, cells, rows=None):
         """per read with a cell: its sequence, name, cell, molecule or None (bytes), gene record; cells: the barcodes in the order
@@ -287,6 +289,10 @@ class Caller:
                  "allele_ref.mtx": genes._mtx(len(self.variants), len(cells), ref),
                  "allele_alt.mtx": genes._mtx(len(self.variants), len(cells), alt),
                  "read_alleles.tsv": read_alleles_text(self.variants, ids, cb, ub, recs, calls)}
+        if self.donors is not None:
+            more, donor_counts = self.donors(cells, ref, alt)
+            files.update(more)
+            counts.update(donor_counts)
         return files, counts
 
 

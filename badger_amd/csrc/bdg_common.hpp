@@ -168,6 +168,7 @@ struct bdg_ctx {
     std::vector<uint32_t> al_keys_per_value;       // ... [2 * n_variants]
     int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
     int em_cus = 0, em_per_cu = 0;          // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
+    int donor_cus = 0, donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -1188,6 +1188,38 @@ int  bdg_alleles_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t
 int  bdg_alleles_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_gene_rec* gene_recs,
                         bdg_allele_rec* out, uint64_t cap, uint64_t counts[2]);
 
+/* ---- cells to donors from known genotypes (--donor_genotypes; checker: badger_amd/donors.py) ---- */
+#define BDG_DONORS_MAX          32
+#define BDG_DONORS_MAX_DEPTH    (1ull << 40)  /* the counts of one cell must sum to less */
+#define BDG_DONOR_NONE          0xFFFFFFFFu   /* bdg_donor_rec: no second donor, no pair (one donor) */
+typedef struct { uint32_t variant, ref, alt, pad; } bdg_donor_entry;                 /* 16 bytes */
+typedef struct { int64_t best_score, second_score, doublet_score; uint32_t donor1, donor2, pair, pad; } bdg_donor_rec;   /* 40 bytes */
+/* THE RULE.  Integers only, so that the order of the sums does not matter and a device and a host agree exactly.
+ *   donors   D of them, 1 .. BDG_DONORS_MAX.  geno [n_variants]: per variant one word, donor i's alt dosage 0, 1 or 2 in bits
+ *            2 i, 2 i + 1 (3 never occurs).
+ *   cell     c is the entries d_cell_off[c] .. d_cell_off[c + 1] - 1 of d_entries: (variant, ref, alt), the molecules counted
+ *            for either allele of the variant in the cell.
+ *   tables   ten int32, A_0 .. A_4 then B_0 .. B_4: the logarithms, times 2^16 and rounded, of the chance of a reference and of
+ *            an alternative molecule at the levels l = 0 .. 4 (alt fraction l / 4 behind the error rate); the caller makes them.
+ *   hypotheses  h < D: the singlet of donor h, level 2 g_h.  Then the pairs (a < b) in lexicographic order, level g_a + g_b.
+ *            H = D + D (D - 1) / 2.
+ *   score    S[c][h] = the sum over the cell's entries of ref * A_level + alt * B_level, in int64.
+ *   record   best_score, donor1: the highest singlet score, of equal ones the lowest donor.  second_score, donor2: the same over
+ *            the other donors; D == 1: INT64_MIN and BDG_DONOR_NONE.  doublet_score, pair: the highest pair score, of equal
+ *            ones the lowest h, pair = a | b << 16; D == 1: INT64_MIN and BDG_DONOR_NONE.  pad = 0.
+ * d_recs [n_cells]; d_scores NULL or [n_cells * H], row c the scores of cell c.  d_entries must be aligned to 16 bytes (an entry
+ * is one load).  An entry whose variant is not below n_variants counts with a genotype word of 0 here.  Asynchronous, on the
+ * context's stream; tables is host memory and read before the call returns.  BDG_E_ARG for D outside 1 .. 32, null pointers and
+ * entries not so aligned.  n_cells == 0: BDG_OK, nothing is launched. */
+int  bdg_donor_scores_dev(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells,
+                          const uint64_t* d_geno, uint32_t n_variants, uint32_t n_donors, const int32_t* tables,
+                          bdg_donor_rec* d_recs, int64_t* d_scores);
+/* The same over host arrays, synchronous.  Also BDG_E_ARG, before anything is launched, for cell offsets that decrease, an
+ * entry whose variant is not below n_variants, a genotype field of one of the D donors that holds 3, and a cell whose ref + alt
+ * sum to BDG_DONORS_MAX_DEPTH or more (below it every score stays inside int64: |A_l|, |B_l| < 2^20 for error rates >= 1e-4). */
+int  bdg_donor_scores(bdg_ctx* ctx, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, const uint64_t* geno,
+                      uint32_t n_variants, uint32_t n_donors, const int32_t* tables, bdg_donor_rec* recs, int64_t* scores);
+
 /* ---- isoform abundances by EM over compatibility counts (--isoform_em; checker: badger_amd/genes.py em_tcc) ---- */
 #define BDG_EM_CLOSED           1u           /* bdg_em_info.flags: no iteration was needed (or there was nothing to do) */
 #define BDG_EM_CONVERGED        2u           /* ... delta < eps after `iters` iterations */
