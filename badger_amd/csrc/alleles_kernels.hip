@@ -173,15 +173,6 @@ void k_alleles_assign(const uint8_t* __restrict__ bases, const uint64_t* __restr
     if (lane == 0 && n_crowded) atomicAdd(&counts[1], (unsigned long long)n_crowded);
 }
 
-int alleles_cus(bdg_ctx* ctx)
-{
-    if (ctx->gn_cus == 0) {
-        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->gn_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (ctx->gn_cus <= 0) ctx->gn_cus = 1;
-    }
-    return BDG_OK;
-}
-
 int alleles_check_assign(bdg_ctx* ctx)
 {
     if (ctx->al_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "alleles: no index built (bdg_alleles_index_build)");
@@ -194,22 +185,10 @@ int alleles_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* 
 {
     BDG_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ctx->stream));
     if (n == 0) return BDG_OK;
-    if (int rc = alleles_cus(ctx)) return rc;
-    if (ctx->al_assign_per_cu == 0) {
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_alleles_assign, 64, 0));
-        ctx->al_assign_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->al_assign_per_cu);
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->al_slots);
-    {
-        ScopedKernelTimer tm(ctx, "k_alleles_assign");
-        hipLaunchKernelGGL(k_alleles_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->al_k, d_genes,
-                           static_cast<const uint8_t*>(ctx->al_has.p), ctx->al_features, static_cast<const GeneSlot*>(ctx->al_table.p),
-                           ctx->al_slots - 1, shift, reinterpret_cast<uint4*>(d_out), cap, reinterpret_cast<unsigned long long*>(d_counts));
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    return bdg_resident_launch(ctx, k_alleles_assign, ctx->al_assign_per_cu, "k_alleles_assign", n, d_bases, d_off, n, ctx->al_k, d_genes,
+                               static_cast<const uint8_t*>(ctx->al_has.p), ctx->al_features, static_cast<const GeneSlot*>(ctx->al_table.p),
+                               ctx->al_slots - 1, kmer_shift(ctx->al_slots), reinterpret_cast<uint4*>(d_out), cap,
+                               reinterpret_cast<unsigned long long*>(d_counts));
 }
 
 void alleles_drop(bdg_ctx* ctx)
@@ -241,48 +220,29 @@ int bdg_alleles_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* 
     }
     const uint64_t end = seq_off[n_seqs];
     if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    // windows with a key: the table's size follows from them
-    uint64_t windows = 0;
-    for (uint32_t q = 0; q < n_seqs; ++q) {
-        uint64_t run = 0;
-        for (uint64_t p = seq_off[q]; p < seq_off[q + 1]; ++p) {
-            const uint8_t c = bases[p];
-            run = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? run + 1 : 0;
-            windows += run >= k;
-        }
-    }
-    uint64_t slots = 64;
-    while (slots < 2 * windows) slots <<= 1;
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(slots);
+    const uint64_t windows = kmer_windows(bases, seq_off, n_seqs, k), slots = kmer_slots(windows);
+    const uint32_t shift = kmer_shift(slots);
     std::vector<uint8_t> has((size_t)n_features + 1, 0);
     for (uint32_t v = 0; v < n_variants; ++v) has[genes[v]] = 1;
-
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (a queued assign call may still read the earlier table)
-    alleles_drop(ctx);
-    int rc;
-    if ((rc = alleles_cus(ctx))) return rc;
     // the sequences, their offsets and values, the variants' genes and the counters live for this call only
     DevBuf d_bases, d_meta;
     const size_t n_values = 2 * (size_t)n_variants;
     const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), val_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u,
                  gene_b = (sizeof(uint32_t) * (size_t)n_variants + 7u) & ~(size_t)7u, stat_b = 4 * sizeof(uint64_t),
                  kpv_b = sizeof(uint32_t) * n_values;
-    if ((rc = bdg_reserve(ctx, ctx->al_table, sizeof(GeneSlot) * (size_t)slots)) || (rc = bdg_reserve(ctx, ctx->al_has, has.size())) ||
-        (rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + val_b + gene_b + stat_b + kpv_b + 8))) {
-        alleles_drop(ctx);
-        return rc;
-    }
-    char* meta = static_cast<char*>(d_meta.p);
-    auto* d_off = reinterpret_cast<uint64_t*>(meta);
-    auto* d_val = reinterpret_cast<uint32_t*>(meta + off_b);
-    auto* d_gene = reinterpret_cast<uint32_t*>(meta + off_b + val_b);
-    auto* d_stats = reinterpret_cast<unsigned long long*>(meta + off_b + val_b + gene_b);
-    auto* d_kpv = reinterpret_cast<uint32_t*>(meta + off_b + val_b + gene_b + stat_b);
-    unsigned long long h_stats[4] = { 0, 0, 0, 0 };
     std::vector<uint32_t> kpv(n_values, 0);
-    auto run = [&]() -> int {
+    auto run = [&](unsigned long long* h_stats) -> int {
+        int rc;
+        if ((rc = bdg_reserve(ctx, ctx->al_has, has.size())) || (rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) ||
+            (rc = bdg_reserve(ctx, d_meta, off_b + val_b + gene_b + stat_b + kpv_b + 8)))
+            return rc;
+        char* meta = static_cast<char*>(d_meta.p);
+        auto* d_off = reinterpret_cast<uint64_t*>(meta);
+        auto* d_val = reinterpret_cast<uint32_t*>(meta + off_b);
+        auto* d_gene = reinterpret_cast<uint32_t*>(meta + off_b + val_b);
+        auto* d_stats = reinterpret_cast<unsigned long long*>(meta + off_b + val_b + gene_b);
+        auto* d_kpv = reinterpret_cast<uint32_t*>(meta + off_b + val_b + gene_b + stat_b);
         if (end > seq_off[0])
             BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
@@ -290,32 +250,23 @@ int bdg_alleles_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* 
         if (n_variants) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_gene, genes, sizeof(uint32_t) * (size_t)n_variants, hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->al_has.p, has.data(), has.size(), hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, stat_b + kpv_b, st));
-        BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->al_table.p, 0xFF, sizeof(GeneSlot) * (size_t)slots, st));   // every key EMPTY, every value NONE
         if (n_seqs) {
             ScopedKernelTimer tm(ctx, "k_alleles_insert");
-            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * ALLELES_INSERT_WAVES_PER_CU);
+            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * ALLELES_INSERT_WAVES_PER_CU);
             hipLaunchKernelGGL(k_alleles_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_val, d_gene,
                                n_seqs, k, static_cast<GeneSlot*>(ctx->al_table.p), slots - 1, shift);
         }
         {
             ScopedKernelTimer tm(ctx, "k_alleles_stats");
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->gn_cus * 8);
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->cus * 8);
             hipLaunchKernelGGL(k_alleles_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->al_table.p), slots, shift,
                                d_stats, d_kpv, (uint32_t)n_values);
         }
-        BDG_HIP_TRY(ctx, hipGetLastError());
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, stat_b, hipMemcpyDeviceToHost, st));
         if (n_values) BDG_HIP_TRY(ctx, hipMemcpyAsync(kpv.data(), d_kpv, kpv_b, hipMemcpyDeviceToHost, st));
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
         return BDG_OK;
     };
-    if ((rc = run())) {
-        (void)hipStreamSynchronize(st);                             // (the temporaries go with this frame)
-        alleles_drop(ctx);
-        return rc;
-    }
-    const uint64_t stats[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
-    memcpy(ctx->al_stats, stats, sizeof(stats));
+    if (int rc = kmer_table_build(ctx, ctx->al_table, windows, slots, ctx->al_stats, [&] { alleles_drop(ctx); }, run)) return rc;
     ctx->al_keys_per_value.swap(kpv);
     ctx->al_k = k;
     ctx->al_features = n_features;
@@ -362,26 +313,18 @@ int bdg_alleles_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, 
     if (!counts || (cap && !out) || (n && (!off || !gene_recs))) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     counts[0] = counts[1] = 0;
     if (n == 0) return BDG_OK;
-    for (uint32_t r = 0; r < n; ++r)
-        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "alleles: read offsets must be non-decreasing");
-    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // one input buffer behind the bases: the offsets, then the gene records; one output buffer: the two counts, then the records
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), gene_b = sizeof(bdg_gene_rec) * (size_t)n, cnt_b = 2 * sizeof(uint64_t);
+    // the gene records behind the offsets; one output buffer: the two counts, then the records (16 bytes each, the start a multiple of 16)
+    const size_t gene_b = sizeof(bdg_gene_rec) * (size_t)n, cnt_b = 2 * sizeof(uint64_t);
+    StagedReads S;
     int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + gene_b))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, cnt_b + sizeof(bdg_allele_rec) * (size_t)cap))) return rc;
-    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
-    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
-    auto* d_genes = reinterpret_cast<bdg_gene_rec*>(static_cast<char*>(ctx->s_in1.p) + off_b);
-    auto* d_counts = static_cast<uint64_t*>(ctx->s_out0.p);
-    auto* d_out = reinterpret_cast<bdg_allele_rec*>(static_cast<char*>(ctx->s_out0.p) + cnt_b);
-    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, cnt_b + sizeof(bdg_allele_rec) * (size_t)cap, S, gene_b, "alleles: read offsets must be non-decreasing")))
+        return rc;
+    hipStream_t st = ctx->stream;
+    auto* d_genes = static_cast<bdg_gene_rec*>(S.d_extra);
+    auto* d_counts = static_cast<uint64_t*>(S.d_out);
+    auto* d_out = reinterpret_cast<bdg_allele_rec*>(static_cast<char*>(S.d_out) + cnt_b);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(d_genes, gene_recs, gene_b, hipMemcpyHostToDevice, st));
-    if ((rc = alleles_assign_launch(ctx, d_bases, d_off, n, d_genes, d_out, cap, d_counts))) return rc;
+    if ((rc = alleles_assign_launch(ctx, S.d_bases, S.d_off, n, d_genes, d_out, cap, d_counts))) return rc;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, cnt_b, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
     if (counts[0] > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "alleles: " + std::to_string(counts[0]) + " records, more than the capacity");

@@ -116,6 +116,36 @@ int bdg_check_offsets(bdg_ctx* ctx, const uint64_t* off, uint32_t n)
     return BDG_OK;
 }
 
+// What the host-buffer wrappers of reads share (bdg_launchers.hpp; the gene and allele wrappers in their kernel files call it too)
+int bdg_stage_reads(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, size_t out_bytes, StagedReads& s,
+                    size_t extra_bytes, const char* order_msg)
+{
+    if (!order_msg) {
+        if (int rco = bdg_check_offsets(ctx, off, n)) return rco;
+    } else {
+        for (uint32_t i = 0; i < n; ++i)
+            if (off[i + 1] < off[i]) return bdg_fail(ctx, BDG_E_ARG, order_msg);
+    }
+    const uint64_t lo = off[0];
+    s.total = off[n] - lo;
+    if (s.total && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1);
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, s.total + 64))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + extra_bytes))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, out_bytes))) return rc;
+    s.rel.resize((size_t)n + 1);
+    for (uint32_t i = 0; i <= n; ++i) s.rel[i] = off[i] - lo;
+    if (s.total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, s.total, hipMemcpyHostToDevice, ctx->stream));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, s.rel.data(), off_b, hipMemcpyHostToDevice, ctx->stream));
+    s.d_bases = static_cast<const uint8_t*>(ctx->s_in0.p);
+    s.d_off = static_cast<const uint64_t*>(ctx->s_in1.p);
+    s.d_extra = static_cast<char*>(ctx->s_in1.p) + off_b;
+    s.d_out = ctx->s_out0.p;
+    return BDG_OK;
+}
+
 // The context's stream waits for everything queued on the auxiliary stream so far (a match queued there - deferred, or a
 // stage-1 slot match - uses the same match workspaces as one launched on the main stream: the two must not overlap).
 static int main_after_aux(bdg_ctx* ctx)
@@ -406,29 +436,6 @@ int bdg_extract_counters(bdg_ctx* ctx, uint64_t out[9])
     return bdg_extract_counters_impl(ctx, out);
 }
 
-// What the host-buffer wrappers of reads share: the offsets checked, the byte range they reference shipped rebased to 0
-// (s_in0, s_in1; queued on the context's stream) and out_bytes of s_out0 reserved.  `rel` lives until the caller has synchronised.
-struct StagedReads { std::vector<uint64_t> rel; const uint8_t* d_bases; const uint64_t* d_off; void* d_out; uint64_t total; };
-static int stage_reads(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, size_t out_bytes, StagedReads& s)
-{
-    if (int rco = bdg_check_offsets(ctx, off, n)) return rco;
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t lo = off[0];
-    s.total = off[n] - lo;
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, s.total + 64))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, sizeof(uint64_t) * ((size_t)n + 1)))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, out_bytes))) return rc;
-    s.rel.resize((size_t)n + 1);
-    for (uint32_t i = 0; i <= n; ++i) s.rel[i] = off[i] - lo;
-    if (s.total) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, bases + lo, s.total, hipMemcpyHostToDevice, ctx->stream));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, s.rel.data(), sizeof(uint64_t) * s.rel.size(), hipMemcpyHostToDevice, ctx->stream));
-    s.d_bases = static_cast<const uint8_t*>(ctx->s_in0.p);
-    s.d_off = static_cast<const uint64_t*>(ctx->s_in1.p);
-    s.d_out = ctx->s_out0.p;
-    return BDG_OK;
-}
-
 // s_out0 of the trim and chimera wrappers for n reads: records | trim | chimera (if chim)
 struct ReadsLayout { bdg_extract_rec* recs; bdg_trim_rec* trim; bdg_chimera_rec* chim; size_t bytes; };
 static ReadsLayout reads_layout(void* base, size_t n, bool chim)
@@ -448,7 +455,7 @@ int bdg_extract_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     if (int rcu = bdg_check_umi_len(ctx, umi_len)) return rcu;
     StagedReads S;
     int rc;
-    if ((rc = stage_reads(ctx, bases, off, n, sizeof(bdg_extract_rec) * (size_t)n, S))) return rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, sizeof(bdg_extract_rec) * (size_t)n, S))) return rc;
     hipStream_t st = ctx->stream;
     // A queue overflow grows the workspace from what the failed pass could count; the hits re-queued by clusters are only
     // known once queue A is complete, so a second overflow is possible: loop (each pass at least 1.5 x the last one).
@@ -486,7 +493,7 @@ int bdg_trim_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint
     if (!bases || !off || !recs || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     StagedReads S;
     int rc;
-    if ((rc = stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, false).bytes, S))) return rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, false).bytes, S))) return rc;
     hipStream_t st = ctx->stream;
     const ReadsLayout L = reads_layout(S.d_out, n, false);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(L.recs, recs, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -517,7 +524,7 @@ int bdg_chimera_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, u
     if (!bases || !off || !recs || !trim || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     StagedReads S;
     int rc;
-    if ((rc = stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, true).bytes, S))) return rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, reads_layout(nullptr, n, true).bytes, S))) return rc;
     hipStream_t st = ctx->stream;
     const ReadsLayout L = reads_layout(S.d_out, n, true);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(L.recs, recs, sizeof(bdg_extract_rec) * (size_t)n, hipMemcpyHostToDevice, st));
@@ -556,7 +563,7 @@ int bdg_split_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uin
     StagedReads S;
     int rc;
     const size_t off_at = 256, pc_at = off_at + sizeof(uint64_t) * ((size_t)cap + 1);
-    if ((rc = stage_reads(ctx, bases, off, n, pc_at + sizeof(bdg_split_rec) * (size_t)cap, S))) return rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, pc_at + sizeof(bdg_split_rec) * (size_t)cap, S))) return rc;
     hipStream_t st = ctx->stream;
     char* const d = static_cast<char*>(S.d_out);
     uint64_t* const d_count = reinterpret_cast<uint64_t*>(d);
@@ -590,7 +597,7 @@ int bdg_rescue_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, ui
     StagedReads S;
     int rc;
     const size_t rec_bytes = sizeof(bdg_extract_rec) * (size_t)n, sup_bytes = sizeof(uint32_t) * (size_t)ctx->w_n;
-    if ((rc = stage_reads(ctx, bases, off, n, rec_bytes + sup_bytes, S))) return rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, rec_bytes + sup_bytes, S))) return rc;
     hipStream_t st = ctx->stream;
     bdg_extract_rec* const d_recs = static_cast<bdg_extract_rec*>(S.d_out);
     uint32_t* const d_sup = reinterpret_cast<uint32_t*>(static_cast<char*>(S.d_out) + rec_bytes);

@@ -37,6 +37,7 @@ struct KTimer {
 
 struct bdg_ctx {
     int device = 0;
+    int cus = 0;                            // compute units of the device: bdg_cus() asks on first use
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     // bdg_set_overlap: the whitelist match of a batch's records runs on aux_stream, ordered behind the extraction that wrote
@@ -146,14 +147,13 @@ struct bdg_ctx {
     DevBuf c_meta;       // group of every sequence u32 | counter offset of every group u64
     DevBuf c_cnt;        // vote counters, 8 bytes per backbone position of the call
     DevBuf c_trace;      // direction bits, 16 * c_band / 64 bytes per member row and wave in flight
-    int c_cus = 0;       // compute units (asked once)
     uint32_t c_band = BDG_CONS_BAND_DEFAULT;   // bdg_consensus_set_band: diagonals of the alignment's band, 64, 128 or 256
     // ---- gene index (genes_kernels.hip): held like the whitelist, replaced by the next bdg_genes_index_build
     DevBuf gn_table;     // gn_slots slots of {u64 key, u32 value, u32 pad}
     uint64_t gn_slots = 0;                   // a power of two; 0: no index
     uint32_t gn_k = 0;
     uint64_t gn_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_genes_index_stats
-    int gn_cus = 0, gn_assign_per_cu = 0;    // compute units, and blocks of k_genes_assign resident on one (asked once)
+    int gn_assign_per_cu = 0;                // blocks of k_genes_assign resident on a compute unit (asked once)
     DevBuf gn_mask;      // u64 per slot: the transcripts of its gene that hold the slot's key (bdg_genes_index_build_iso only)
     int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
     int gn_assign_sp_per_cu = 0, gn_iso_sp_per_cu = 0;   // the same of k_genes_assign_spans and k_iso_assign_spans
@@ -167,8 +167,8 @@ struct bdg_ctx {
     uint64_t al_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_alleles_index_stats
     std::vector<uint32_t> al_keys_per_value;       // ... [2 * n_variants]
     int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
-    int em_cus = 0, em_per_cu = 0;          // em_kernels.hip: compute units, and blocks of k_em_tcc resident on one (asked once)
-    int donor_cus = 0, donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
+    int em_per_cu = 0;                      // em_kernels.hip: blocks of k_em_tcc resident on a compute unit (asked once)
+    int donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending
@@ -202,9 +202,8 @@ struct bdg_ctx {
         int64_t dj_l2max = -1;          // ... log2 of the sub-buckets of a coarse bucket at most - only ever lowers it (BADGER_AMD_DJ_L2MAX); -1: no limit of its own
         uint32_t d2_pairs_blocks = 4;   // ... blocks of k_d2_pairs_w per compute unit, 1 .. 8 (BADGER_AMD_D2_PAIRS_BLOCKS)
     } g_knobs;
-    int g_cus_distinct = 0;             // compute units (bdg_distinct_dev asks by itself when no graph call has)
     uint32_t* g_dj_geom = nullptr;      // deletion-variant joins: the device-side report of the last launch (bdg_graph_status)
-    int g_cus = 0, g_qj_per_cu = 0, g_qjw_per_cu = 0;   // compute units and resident blocks per unit of the q-gram join's kernels (asked once)
+    int g_qj_per_cu = 0, g_qjw_per_cu = 0;   // resident blocks per compute unit of the q-gram join's kernels (asked once)
 };
 
 #define BDG_HIP_TRY(ctx, expr)                                                           \
@@ -215,6 +214,16 @@ struct bdg_ctx {
             return e_ == hipErrorOutOfMemory ? BDG_E_NOMEM : BDG_E_HIP;                  \
         }                                                                                \
     } while (0)
+
+// The device's compute units, asked once per context: behind an OK ctx->cus is at least 1 (the resident grids are sized from it).
+static inline int bdg_cus(bdg_ctx* ctx)
+{
+    if (ctx->cus == 0) {
+        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        if (ctx->cus <= 0) ctx->cus = 1;
+    }
+    return BDG_OK;
+}
 
 // Grow-only device buffer.
 int bdg_reserve(bdg_ctx* ctx, DevBuf& b, size_t bytes);

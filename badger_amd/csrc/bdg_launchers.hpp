@@ -3,7 +3,29 @@
 
 #include "bdg_common.hpp"
 
+#include <algorithm>
 #include <cstddef>
+
+// The launch of a persistent kernel that runs one wave per item (blocks of 64): as many waves as stay resident together, the
+// items dealt out to them once - more blocks than that would run as a second, thinner round.  per_cu is the kernel's own cached
+// figure, blocks of it resident on a compute unit, asked on the first launch; `name` is its timer.  n > 0.
+template <class Kernel, class... Args>
+static inline int bdg_resident_launch(bdg_ctx* ctx, Kernel kernel, int& per_cu, const char* name, uint64_t n, Args... args)
+{
+    if (int rc = bdg_cus(ctx)) return rc;
+    if (per_cu == 0) {
+        int blocks = 0;
+        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, 64, 0));
+        per_cu = blocks < 1 ? 1 : blocks;
+    }
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->cus * (uint64_t)per_cu);
+    {
+        ScopedKernelTimer tm(ctx, name);
+        hipLaunchKernelGGL(kernel, dim3(waves), dim3(64), 0, ctx->stream, args...);
+    }
+    BDG_HIP_TRY(ctx, hipGetLastError());
+    return BDG_OK;
+}
 
 // extract_kernels.hip
 int bdg_extract_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, uint64_t, uint32_t, bdg_extract_rec*);
@@ -66,6 +88,13 @@ int bdg_rescue_resolve_launch(bdg_ctx*, const RescStore&, uint64_t j0, uint32_t 
 int bdg_sync_all(bdg_ctx*);                                   // bdg_abi.cpp: a waiting deferred match queued, then both streams idle
 int bdg_ensure_aux(bdg_ctx*);                                 // bdg_abi.cpp: the auxiliary stream and its events exist
 int bdg_check_offsets(bdg_ctx*, const uint64_t*, uint32_t);   // bdg_abi.cpp: the first read out of order or too long for the kernels
+// bdg_abi.cpp: what the host-buffer wrappers of reads share - the offsets checked (order_msg null: bdg_check_offsets; else only
+// their order, failing with that text), the byte range they reference shipped rebased to 0 (s_in0, and the offsets in s_in1;
+// queued on the context's stream), extra_bytes of s_in1 reserved behind the offsets (d_extra) and out_bytes of s_out0 (d_out).
+// `rel` lives until the caller has synchronised.
+struct StagedReads { std::vector<uint64_t> rel; const uint8_t* d_bases; const uint64_t* d_off; void* d_extra; void* d_out; uint64_t total; };
+int bdg_stage_reads(bdg_ctx*, const uint8_t* bases, const uint64_t* off, uint32_t n, size_t out_bytes, StagedReads&,
+                    size_t extra_bytes = 0, const char* order_msg = nullptr);
 int bdg_correct_grow(bdg_ctx*, uint64_t need);                // bdg_chunks.cpp: room for `need` reads in the correction store
 // bdg_chunks.cpp, the rescue store: start an empty one; store the windows of a batch (polyt: the scan's array of the batch, or null);
 // match and resolve what is stored (d_support null: the correction's array; records to d_out if set, else to `out` sorted by read)

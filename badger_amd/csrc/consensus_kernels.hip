@@ -401,11 +401,8 @@ int cons_launch(bdg_ctx* ctx, const ConsPlan& P, const uint8_t* d_bases, const u
                 uint8_t* d_out, uint32_t* d_out_len, uint32_t* d_n_voted, bdg_consensus_rec* d_recs)
 {
     hipStream_t st = ctx->stream;
-    if (ctx->c_cus == 0) {
-        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->c_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (ctx->c_cus <= 0) ctx->c_cus = 1;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->c_cus * WAVES_PER_CU);
+    if (int rcu = bdg_cus(ctx)) return rcu;
+    const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * WAVES_PER_CU);
     const uint64_t n_cnt = P.cnt_off[n_groups];
     // workspaces: seq_group u32 [n_seqs] | cnt_off u64 [n_groups + 1];  counters 8 B per backbone position;  trace per wave,
     // band / 64 words of 16 B per row

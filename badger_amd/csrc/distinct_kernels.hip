@@ -271,12 +271,8 @@ int bdg_distinct_launch(bdg_ctx* ctx, const bdg_extract_rec* d_recs, uint32_t n,
     hipStream_t st = ctx->stream;
     BDG_HIP_TRY(ctx, hipMemsetAsync(d_n, 0, 8, st));
     if (n == 0) return BDG_OK;
-    if (!ctx->g_cus) {
-        hipDeviceProp_t prop;
-        BDG_HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ctx->g_cus_distinct = prop.multiProcessorCount;
-    }
-    const uint32_t cus = (uint32_t)(ctx->g_cus ? ctx->g_cus : ctx->g_cus_distinct);
+    if (int rcu = bdg_cus(ctx)) return rcu;
+    const uint32_t cus = (uint32_t)ctx->cus;
     // geometry: coarse buckets by the rank's top l1 bits; below about a million records they are the fine buckets already
     // (no second level), beyond that the device picks the sub-bucket count from the number of usable records
     uint32_t l1 = 8;

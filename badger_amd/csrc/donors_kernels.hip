@@ -12,6 +12,7 @@
 //            scratch; no LDS, no atomics.  Three wave reductions with the rule's ties make the record.
 //            The launcher takes the smallest NR of 1, 2, 4, 9 that holds H = D + D (D - 1) / 2 hypotheses.
 #include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -152,41 +153,22 @@ int donor_check(bdg_ctx* ctx, uint32_t n_donors, const int32_t* tables)
     return BDG_OK;
 }
 
-template <int NR>
-int donor_launch_as(bdg_ctx* ctx, int which, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells,
-                    const uint64_t* d_geno, uint32_t n_variants, uint32_t D, const DonorTables& t, bdg_donor_rec* d_recs,
-                    int64_t* d_scores)
-{
-    if (ctx->donor_per_cu[which] == 0) {
-        // as many waves as stay resident: the cells are dealt out to them once
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_donor_scores<NR>, 64, 0));
-        ctx->donor_per_cu[which] = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n_cells, (uint64_t)ctx->donor_cus * (uint64_t)ctx->donor_per_cu[which]);
-    {
-        ScopedKernelTimer tm(ctx, "k_donor_scores");
-        hipLaunchKernelGGL(k_donor_scores<NR>, dim3(waves), dim3(64), 0, ctx->stream, d_entries, d_cell_off, n_cells, d_geno,
-                           n_variants, D, t, d_recs, d_scores);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
-}
-
 int donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells, const uint64_t* d_geno,
                  uint32_t n_variants, uint32_t D, const int32_t* tables, bdg_donor_rec* d_recs, int64_t* d_scores)
 {
-    if (ctx->donor_cus == 0) {
-        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->donor_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (ctx->donor_cus <= 0) ctx->donor_cus = 1;
-    }
     DonorTables t;
     for (int l = 0; l < 5; ++l) t.a[l] = tables[l], t.b[l] = tables[5 + l];
-    switch (donor_rounds_index(D)) {
-    case 0: return donor_launch_as<1>(ctx, 0, d_entries, d_cell_off, n_cells, d_geno, n_variants, D, t, d_recs, d_scores);
-    case 1: return donor_launch_as<2>(ctx, 1, d_entries, d_cell_off, n_cells, d_geno, n_variants, D, t, d_recs, d_scores);
-    case 2: return donor_launch_as<4>(ctx, 2, d_entries, d_cell_off, n_cells, d_geno, n_variants, D, t, d_recs, d_scores);
-    default: return donor_launch_as<9>(ctx, 3, d_entries, d_cell_off, n_cells, d_geno, n_variants, D, t, d_recs, d_scores);
+    // as many waves as stay resident: the cells are dealt out to them once (each instantiation has its own figure)
+    const int which = donor_rounds_index(D);
+    auto as = [&](auto kernel) {
+        return bdg_resident_launch(ctx, kernel, ctx->donor_per_cu[which], "k_donor_scores", n_cells, d_entries, d_cell_off, n_cells, d_geno,
+                                   n_variants, D, t, d_recs, d_scores);
+    };
+    switch (which) {
+    case 0: return as(k_donor_scores<1>);
+    case 1: return as(k_donor_scores<2>);
+    case 2: return as(k_donor_scores<4>);
+    default: return as(k_donor_scores<9>);
     }
 }
 

@@ -15,6 +15,7 @@
 // The arithmetic: every float operation of the rule is rounded on its own.  The file is compiled with contraction off
 // (the pragma below), division is the correctly rounded one (v_div_scale / v_div_fmas / v_div_fixup), denormals are kept.
 #include "bdg_common.hpp"
+#include "bdg_launchers.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -175,22 +176,9 @@ int em_check(bdg_ctx* ctx, float eps, uint32_t max_iter)
 int em_launch(bdg_ctx* ctx, const bdg_em_class* d_classes, const uint64_t* d_prob_off, uint32_t n_prob, const uint64_t* d_out_off,
               const float* d_start, float eps, uint32_t max_iter, float* d_alpha, bdg_em_info* d_info)
 {
-    if (ctx->em_cus == 0) {
-        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->em_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (ctx->em_cus <= 0) ctx->em_cus = 1;
-        // as many waves as stay resident: the problems are dealt out to them once
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_em_tcc, 64, 0));
-        ctx->em_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n_prob, (uint64_t)ctx->em_cus * (uint64_t)ctx->em_per_cu);
-    {
-        ScopedKernelTimer tm(ctx, "k_em_tcc");
-        hipLaunchKernelGGL(k_em_tcc, dim3(waves), dim3(64), 0, ctx->stream, d_classes, d_prob_off, n_prob, d_out_off, d_start, eps,
-                           max_iter, d_alpha, d_info);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    // as many waves as stay resident: the problems are dealt out to them once
+    return bdg_resident_launch(ctx, k_em_tcc, ctx->em_per_cu, "k_em_tcc", n_prob, d_classes, d_prob_off, n_prob, d_out_off, d_start, eps,
+                               max_iter, d_alpha, d_info);
 }
 
 }  // namespace

@@ -364,39 +364,10 @@ void k_cdna_spans(const uint64_t* __restrict__ off, uint32_t n, const bdg_extrac
     out[i] = sp;
 }
 
-int genes_cus(bdg_ctx* ctx)
-{
-    if (ctx->gn_cus == 0) {
-        BDG_HIP_TRY(ctx, hipDeviceGetAttribute(&ctx->gn_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        if (ctx->gn_cus <= 0) ctx->gn_cus = 1;
-    }
-    return BDG_OK;
-}
-
 int genes_check_assign(bdg_ctx* ctx, uint32_t min_hits)
 {
     if (ctx->gn_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: no index built (bdg_genes_index_build)");
     if (min_hits == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: min_hits must be at least 1");
-    return BDG_OK;
-}
-
-int genes_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits, bdg_gene_rec* d_out)
-{
-    if (int rc = genes_cus(ctx)) return rc;
-    if (ctx->gn_assign_per_cu == 0) {
-        // the reads are dealt out to the waves once: more blocks than are resident together would run as a second, thinner round
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_genes_assign, 64, 0));
-        ctx->gn_assign_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_assign_per_cu);
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
-    {
-        ScopedKernelTimer tm(ctx, "k_genes_assign");
-        hipLaunchKernelGGL(k_genes_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->gn_k, min_hits,
-                           static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, shift, d_out);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
     return BDG_OK;
 }
 
@@ -407,67 +378,35 @@ int iso_check_assign(bdg_ctx* ctx, uint32_t margin)
     return BDG_OK;
 }
 
+// The four assign launches: one wave per read as bdg_resident_launch deals them out, each kernel with its own resident figure.
+int genes_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits, bdg_gene_rec* d_out)
+{
+    return bdg_resident_launch(ctx, k_genes_assign, ctx->gn_assign_per_cu, "k_genes_assign", n, d_bases, d_off, n, ctx->gn_k, min_hits,
+                               static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
+}
+
 int iso_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes, uint32_t margin,
                       bdg_iso_rec* d_out)
 {
-    if (int rc = genes_cus(ctx)) return rc;
-    if (ctx->gn_iso_per_cu == 0) {
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iso_assign, 64, 0));
-        ctx->gn_iso_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_iso_per_cu);
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
-    {
-        ScopedKernelTimer tm(ctx, "k_iso_assign");
-        hipLaunchKernelGGL(k_iso_assign, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, n, ctx->gn_k, d_genes, margin,
-                           static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
-                           ctx->gn_slots - 1, shift, d_out);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    return bdg_resident_launch(ctx, k_iso_assign, ctx->gn_iso_per_cu, "k_iso_assign", n, d_bases, d_off, n, ctx->gn_k, d_genes, margin,
+                               static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
+                               ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
 }
 
-// the span forms: the same grids, each kernel's own resident-wave figure
 int genes_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
                               uint32_t min_hits, bdg_gene_rec* d_out)
 {
-    if (int rc = genes_cus(ctx)) return rc;
-    if (ctx->gn_assign_sp_per_cu == 0) {
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_genes_assign_spans, 64, 0));
-        ctx->gn_assign_sp_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_assign_sp_per_cu);
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
-    {
-        ScopedKernelTimer tm(ctx, "k_genes_assign_spans");
-        hipLaunchKernelGGL(k_genes_assign_spans, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, d_spans, n, ctx->gn_k, min_hits,
-                           static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, shift, d_out);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    return bdg_resident_launch(ctx, k_genes_assign_spans, ctx->gn_assign_sp_per_cu, "k_genes_assign_spans", n, d_bases, d_off, d_spans, n,
+                               ctx->gn_k, min_hits, static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1,
+                               kmer_shift(ctx->gn_slots), d_out);
 }
 
 int iso_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
                             const bdg_gene_rec* d_genes, uint32_t margin, bdg_iso_rec* d_out)
 {
-    if (int rc = genes_cus(ctx)) return rc;
-    if (ctx->gn_iso_sp_per_cu == 0) {
-        int per_cu = 0;
-        BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_iso_assign_spans, 64, 0));
-        ctx->gn_iso_sp_per_cu = per_cu < 1 ? 1 : per_cu;
-    }
-    const uint32_t waves = (uint32_t)std::min<uint64_t>(n, (uint64_t)ctx->gn_cus * (uint64_t)ctx->gn_iso_sp_per_cu);
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(ctx->gn_slots);
-    {
-        ScopedKernelTimer tm(ctx, "k_iso_assign_spans");
-        hipLaunchKernelGGL(k_iso_assign_spans, dim3(waves), dim3(64), 0, ctx->stream, d_bases, d_off, d_spans, n, ctx->gn_k, d_genes, margin,
-                           static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
-                           ctx->gn_slots - 1, shift, d_out);
-    }
-    BDG_HIP_TRY(ctx, hipGetLastError());
-    return BDG_OK;
+    return bdg_resident_launch(ctx, k_iso_assign_spans, ctx->gn_iso_sp_per_cu, "k_iso_assign_spans", n, d_bases, d_off, d_spans, n,
+                               ctx->gn_k, d_genes, margin, static_cast<const GeneSlot*>(ctx->gn_table.p),
+                               static_cast<const unsigned long long*>(ctx->gn_mask.p), ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
 }
 
 int cdna_spans_launch(bdg_ctx* ctx, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim,
@@ -493,57 +432,35 @@ int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_of
     }
     const uint64_t end = seq_off[n_seqs];
     if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    // windows with a key: the table's size follows from them
-    uint64_t windows = 0;
-    for (uint32_t q = 0; q < n_seqs; ++q) {
-        uint64_t run = 0;
-        for (uint64_t p = seq_off[q]; p < seq_off[q + 1]; ++p) {
-            const uint8_t c = bases[p];
-            run = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? run + 1 : 0;
-            windows += run >= k;
-        }
-    }
-    uint64_t slots = 64;
-    while (slots < 2 * windows) slots <<= 1;
-    const uint32_t shift = 64u - (uint32_t)__builtin_ctzll(slots);
-
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t windows = kmer_windows(bases, seq_off, n_seqs, k), slots = kmer_slots(windows);
+    const uint32_t shift = kmer_shift(slots);
     hipStream_t st = ctx->stream;
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (a queued assign call may still read the earlier table)
-    ctx->gn_table.reset();
-    ctx->gn_mask.reset();
-    ctx->gn_slots = 0;
-    ctx->gn_k = 0;
-    int rc;
-    if ((rc = genes_cus(ctx))) return rc;
+    auto drop = [&] {
+        ctx->gn_table.reset();
+        ctx->gn_mask.reset();
+        ctx->gn_slots = 0;
+        ctx->gn_k = 0;
+    };
     // the sequences, their offsets and features and the four counters live for this call only
     DevBuf d_bases, d_meta, d_local;
     const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), feat_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u;
-    if ((rc = bdg_reserve(ctx, ctx->gn_table, sizeof(GeneSlot) * (size_t)slots))) { ctx->gn_table.reset(); return rc; }
-    if ((rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + 4 * sizeof(uint64_t)))) {
-        ctx->gn_table.reset();
-        return rc;
-    }
-    // the masks beside the table, and the local indices for this call, only where they are asked for
-    if (with_masks && ((rc = bdg_reserve(ctx, ctx->gn_mask, sizeof(uint64_t) * (size_t)slots)) || (rc = bdg_reserve(ctx, d_local, (size_t)n_seqs + 1)))) {
-        ctx->gn_table.reset();
-        ctx->gn_mask.reset();
-        return rc;
-    }
-    auto* d_off = static_cast<uint64_t*>(d_meta.p);
-    auto* d_feat = reinterpret_cast<uint32_t*>(static_cast<char*>(d_meta.p) + off_b);
-    auto* d_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_meta.p) + off_b + feat_b);
-    unsigned long long h_stats[4] = { 0, 0, 0, 0 };
-    auto run = [&]() -> int {
+    auto run = [&](unsigned long long* h_stats) -> int {
+        int rc;
+        if ((rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + 4 * sizeof(uint64_t)))) return rc;
+        // the masks beside the table, and the local indices for this call, only where they are asked for
+        if (with_masks && ((rc = bdg_reserve(ctx, ctx->gn_mask, sizeof(uint64_t) * (size_t)slots)) || (rc = bdg_reserve(ctx, d_local, (size_t)n_seqs + 1))))
+            return rc;
+        auto* d_off = static_cast<uint64_t*>(d_meta.p);
+        auto* d_feat = reinterpret_cast<uint32_t*>(static_cast<char*>(d_meta.p) + off_b);
+        auto* d_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_meta.p) + off_b + feat_b);
         if (end > seq_off[0])
             BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
         if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_feat, features, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 4 * sizeof(uint64_t), st));
-        BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_table.p, 0xFF, sizeof(GeneSlot) * (size_t)slots, st));   // every key EMPTY, every value NONE
+        const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * INSERT_WAVES_PER_CU);
         if (n_seqs) {
             ScopedKernelTimer tm(ctx, "k_genes_insert");
-            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * INSERT_WAVES_PER_CU);
             hipLaunchKernelGGL(k_genes_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_feat, n_seqs, k,
                                static_cast<GeneSlot*>(ctx->gn_table.p), slots - 1, shift);
         }
@@ -552,7 +469,6 @@ int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_of
             if (n_seqs) {
                 BDG_HIP_TRY(ctx, hipMemcpyAsync(d_local.p, local, (size_t)n_seqs, hipMemcpyHostToDevice, st));
                 ScopedKernelTimer tm(ctx, "k_iso_insert");
-                const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->gn_cus * INSERT_WAVES_PER_CU);
                 hipLaunchKernelGGL(k_iso_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off,
                                    static_cast<const uint8_t*>(d_local.p), n_seqs, k, static_cast<const GeneSlot*>(ctx->gn_table.p),
                                    static_cast<unsigned long long*>(ctx->gn_mask.p), slots - 1, shift);
@@ -560,24 +476,49 @@ int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_of
         }
         {
             ScopedKernelTimer tm(ctx, "k_genes_stats");
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->gn_cus * 8);
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->cus * 8);
             hipLaunchKernelGGL(k_genes_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->gn_table.p), slots, shift, d_stats);
         }
-        BDG_HIP_TRY(ctx, hipGetLastError());
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         return BDG_OK;
     };
-    if ((rc = run())) {
-        (void)hipStreamSynchronize(st);                             // (the temporaries go with this frame)
-        ctx->gn_table.reset();
-        ctx->gn_mask.reset();
-        return rc;
-    }
-    const uint64_t stats[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
-    memcpy(ctx->gn_stats, stats, sizeof(stats));
+    if (int rc = kmer_table_build(ctx, ctx->gn_table, windows, slots, ctx->gn_stats, drop, run)) return rc;
     ctx->gn_k = k;
     ctx->gn_slots = slots;
+    return BDG_OK;
+}
+
+// The host-buffer calls bdg_genes_assign, bdg_iso_assign and bdg_genes_assign_spans: the gene pass, and with_iso the isoform
+// pass behind it, over whole reads or (spans set) over their spans.  The reads go through bdg_stage_reads, the spans behind the
+// offsets; one output buffer holds the gene records, then the isoform records (32 bytes each, the start a multiple of 32).
+int genes_assign_host(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_cdna_span* spans, bool with_spans,
+                      uint32_t min_hits, bool with_iso, uint32_t margin, bdg_gene_rec* gene_out, bdg_iso_rec* iso_out)
+{
+    if (!ctx) return BDG_E_ARG;
+    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
+    if (with_iso) if (int rc = iso_check_assign(ctx, margin)) return rc;   // (the index must have masks)
+    if (n == 0) return BDG_OK;
+    if (!off || (with_spans && !spans) || !gene_out || (with_iso && !iso_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    const size_t span_b = with_spans ? sizeof(bdg_cdna_span) * (size_t)n : 0, rec_b = sizeof(bdg_gene_rec) * (size_t)n,
+                 gene_b = (rec_b + 31u) & ~(size_t)31u, iso_b = with_iso ? sizeof(bdg_iso_rec) * (size_t)n : 0;
+    StagedReads S;
+    int rc;
+    if ((rc = bdg_stage_reads(ctx, bases, off, n, gene_b + iso_b, S, span_b, "genes: read offsets must be non-decreasing"))) return rc;
+    hipStream_t st = ctx->stream;
+    auto* d_spans = static_cast<bdg_cdna_span*>(S.d_extra);
+    auto* d_gene = static_cast<bdg_gene_rec*>(S.d_out);
+    auto* d_iso = reinterpret_cast<bdg_iso_rec*>(static_cast<char*>(S.d_out) + gene_b);
+    if (with_spans) {
+        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_spans, spans, span_b, hipMemcpyHostToDevice, st));
+        if ((rc = genes_assign_spans_launch(ctx, S.d_bases, S.d_off, n, d_spans, min_hits, d_gene))) return rc;
+        if (with_iso && (rc = iso_assign_spans_launch(ctx, S.d_bases, S.d_off, n, d_spans, d_gene, margin, d_iso))) return rc;
+    } else {
+        if ((rc = genes_assign_launch(ctx, S.d_bases, S.d_off, n, min_hits, d_gene))) return rc;
+        if (with_iso && (rc = iso_assign_launch(ctx, S.d_bases, S.d_off, n, d_gene, margin, d_iso))) return rc;
+    }
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(gene_out, d_gene, rec_b, hipMemcpyDeviceToHost, st));
+    if (with_iso) BDG_HIP_TRY(ctx, hipMemcpyAsync(iso_out, d_iso, iso_b, hipMemcpyDeviceToHost, st));
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));                     // (S.rel and the caller's buffers may go now)
     return BDG_OK;
 }
 
@@ -645,38 +586,7 @@ int bdg_cdna_spans_dev(bdg_ctx* ctx, const uint64_t* d_off, uint32_t n, const bd
 int bdg_genes_assign_spans(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, const bdg_cdna_span* spans,
                            uint32_t min_hits, uint32_t margin, bdg_gene_rec* gene_out, bdg_iso_rec* iso_out)
 {
-    if (!ctx) return BDG_E_ARG;
-    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
-    const bool both = margin > 0;                                   // (the isoform pass too: the index must have masks)
-    if (both) if (int rc = iso_check_assign(ctx, margin)) return rc;
-    if (n == 0) return BDG_OK;
-    if (!off || !spans || !gene_out || (both && !iso_out)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t r = 0; r < n; ++r)
-        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
-    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // one input buffer behind the bases: the offsets, then the spans; one output buffer as in bdg_iso_assign
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), span_b = sizeof(bdg_cdna_span) * (size_t)n,
-                 gene_b = (sizeof(bdg_gene_rec) * (size_t)n + 31u) & ~(size_t)31u, iso_b = both ? sizeof(bdg_iso_rec) * (size_t)n : 0;
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + span_b))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, gene_b + iso_b))) return rc;
-    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
-    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
-    auto* d_spans = reinterpret_cast<bdg_cdna_span*>(static_cast<char*>(ctx->s_in1.p) + off_b);
-    auto* d_gene = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
-    auto* d_iso = reinterpret_cast<bdg_iso_rec*>(static_cast<char*>(ctx->s_out0.p) + gene_b);
-    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_spans, spans, span_b, hipMemcpyHostToDevice, st));
-    if ((rc = genes_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, min_hits, d_gene))) return rc;
-    if (both && (rc = iso_assign_spans_launch(ctx, d_bases, d_off, n, d_spans, d_gene, margin, d_iso))) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(gene_out, d_gene, sizeof(bdg_gene_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
-    if (both) BDG_HIP_TRY(ctx, hipMemcpyAsync(iso_out, d_iso, iso_b, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return BDG_OK;
+    return genes_assign_host(ctx, bases, off, n, spans, true, min_hits, margin > 0, margin, gene_out, iso_out);   // (a margin: the isoform pass too)
 }
 
 int bdg_genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, const uint32_t* features,
@@ -712,29 +622,7 @@ int bdg_genes_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d
 
 int bdg_genes_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, bdg_gene_rec* out)
 {
-    if (!ctx) return BDG_E_ARG;
-    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
-    if (n == 0) return BDG_OK;
-    if (!off || !out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t r = 0; r < n; ++r)
-        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
-    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), rec_b = sizeof(bdg_gene_rec) * (size_t)n;
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_b))) return rc;
-    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
-    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
-    auto* d_out = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
-    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
-    if ((rc = genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_out))) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, rec_b, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return BDG_OK;
+    return genes_assign_host(ctx, bases, off, n, nullptr, false, min_hits, false, 0, out, nullptr);
 }
 
 int bdg_iso_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_gene_recs,
@@ -751,35 +639,7 @@ int bdg_iso_assign_dev(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_o
 int bdg_iso_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, uint32_t n, uint32_t min_hits, uint32_t margin,
                    bdg_gene_rec* gene_out, bdg_iso_rec* iso_out)
 {
-    if (!ctx) return BDG_E_ARG;
-    if (int rc = genes_check_assign(ctx, min_hits)) return rc;
-    if (int rc = iso_check_assign(ctx, margin)) return rc;
-    if (n == 0) return BDG_OK;
-    if (!off || !gene_out || !iso_out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t r = 0; r < n; ++r)
-        if (off[r + 1] < off[r]) return bdg_fail(ctx, BDG_E_ARG, "genes: read offsets must be non-decreasing");
-    if (off[n] > off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // one staging buffer for both records: the gene records, then the isoform records (32 bytes each, the start a multiple of 32)
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n + 1), gene_b = (sizeof(bdg_gene_rec) * (size_t)n + 31u) & ~(size_t)31u,
-                 iso_b = sizeof(bdg_iso_rec) * (size_t)n;
-    int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, (size_t)off[n] + 1))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, gene_b + iso_b))) return rc;
-    auto* d_bases = static_cast<uint8_t*>(ctx->s_in0.p);
-    auto* d_off = static_cast<uint64_t*>(ctx->s_in1.p);
-    auto* d_gene = static_cast<bdg_gene_rec*>(ctx->s_out0.p);
-    auto* d_iso = reinterpret_cast<bdg_iso_rec*>(static_cast<char*>(ctx->s_out0.p) + gene_b);
-    if (off[n] > off[0]) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_bases + off[0], bases + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, off, off_b, hipMemcpyHostToDevice, st));
-    if ((rc = genes_assign_launch(ctx, d_bases, d_off, n, min_hits, d_gene))) return rc;
-    if ((rc = iso_assign_launch(ctx, d_bases, d_off, n, d_gene, margin, d_iso))) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(gene_out, d_gene, sizeof(bdg_gene_rec) * (size_t)n, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(iso_out, d_iso, iso_b, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return BDG_OK;
+    return genes_assign_host(ctx, bases, off, n, nullptr, false, min_hits, true, margin, gene_out, iso_out);
 }
 
 }  // extern "C"

@@ -1,10 +1,13 @@
 // What genes_kernels.hip and alleles_kernels.hip share: the 16-byte slot of the k-mer tables, the ballot
 // planes of 64 positions, a window's key and home slot, the reader of a whole sequence, the insertion of a key and the probe of
-// GENES_CHUNKS x 64 windows.  Device code only, in the unnamed namespace of the file that includes it: every kernel that uses
-// it keeps its name and, stamped from the same statements, its code.  gfx950.
+// GENES_CHUNKS x 64 windows - device code in the unnamed namespace of the file that includes it: every kernel that uses it
+// keeps its name and, stamped from the same statements, its code.  Behind it the host side of a table: its size from the
+// sequences, the shift of a home slot, and the frame of a build.  gfx950.
 #pragma once
 
 #include "bdg_common.hpp"
+
+#include <cstring>
 
 namespace {
 
@@ -153,5 +156,66 @@ __device__ __forceinline__ uint64_t insert_key(GeneSlot* table, uint64_t mask, u
             sl[c] = (sl[c] + (ends ? 1 : 2)) & mask;                                                                                     \
         }                                                                                                                                \
     }
+
+// ---- host side: a table's size, and the frame of its build ----
+
+// windows with a key (k bases of ACGT) over the sequences: the table's size follows from them
+inline uint64_t kmer_windows(const uint8_t* bases, const uint64_t* seq_off, uint32_t n_seqs, uint32_t k)
+{
+    uint64_t windows = 0;
+    for (uint32_t q = 0; q < n_seqs; ++q) {
+        uint64_t run = 0;
+        for (uint64_t p = seq_off[q]; p < seq_off[q + 1]; ++p) {
+            const uint8_t c = bases[p];
+            run = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? run + 1 : 0;
+            windows += run >= k;
+        }
+    }
+    return windows;
+}
+
+// a power of two, at least 64 and at least twice the windows: at most half of the slots are ever taken
+inline uint64_t kmer_slots(uint64_t windows)
+{
+    uint64_t slots = 64;
+    while (slots < 2 * windows) slots <<= 1;
+    return slots;
+}
+
+// home_slot's shift for a table of `slots` slots: the top log2(slots) bits of the product
+inline uint32_t kmer_shift(uint64_t slots) { return 64u - (uint32_t)__builtin_ctzll(slots); }
+
+// The frame of a build.  The stream is drained (a queued assign call may still read the earlier table) and drop() clears what
+// the context holds of the table, so that whatever fails from here on leaves no index behind; `table` gets its slots, every key
+// EMPTY and every value NONE; run(h_stats) reserves and uploads what the build needs, queues its insert and stats kernels and
+// the copy of the stats kernel's four figures to h_stats (its temporaries are the caller's: they outlive this frame).  Behind
+// the frame's synchronize the six figures stand in `stats`; on a failure drop() runs again.  The caller publishes k and the
+// slots, which is what makes the index exist.
+template <class Drop, class Run>
+int kmer_table_build(bdg_ctx* ctx, DevBuf& table, uint64_t windows, uint64_t slots, uint64_t stats[6], Drop drop, Run run)
+{
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+    drop();
+    unsigned long long h_stats[4] = { 0, 0, 0, 0 };
+    auto build = [&]() -> int {
+        int rc;
+        if ((rc = bdg_cus(ctx)) || (rc = bdg_reserve(ctx, table, sizeof(GeneSlot) * (size_t)slots))) return rc;
+        BDG_HIP_TRY(ctx, hipMemsetAsync(table.p, 0xFF, sizeof(GeneSlot) * (size_t)slots, st));
+        if ((rc = run(h_stats))) return rc;
+        BDG_HIP_TRY(ctx, hipGetLastError());
+        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
+        return BDG_OK;
+    };
+    if (int rc = build()) {
+        (void)hipStreamSynchronize(st);                             // (the caller's temporaries go behind this)
+        drop();
+        return rc;
+    }
+    const uint64_t figures[6] = { windows, h_stats[0], h_stats[1], slots, h_stats[2], h_stats[3] };
+    memcpy(stats, figures, sizeof(figures));
+    return BDG_OK;
+}
 
 }  // namespace

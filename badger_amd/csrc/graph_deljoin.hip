@@ -707,7 +707,7 @@ int bdg_graph_deljoin_launch(bdg_ctx* ctx, const uint32_t* d_ranks, uint32_t n, 
     hipStream_t st = ctx->stream;
     const bdg_ctx::GraphKnobs& knobs = ctx->g_knobs;
     int rc;
-    if ((rc = bdg_graph_cus(ctx))) return rc;
+    if ((rc = bdg_cus(ctx))) return rc;
     const unsigned long long per_row_max = one_deletion ? 16ull : 120ull, per_row_est = one_deletion ? 12ull : 72ull;
     // rounds: so that a round expects at most D2_ROUND_ENTRIES entries.  Its buffers hold whatever it can emit - every
     // entry of every row - up to what 32 bits index; only beyond that (thr 2: from 35 M rows on) can a round's share of
@@ -736,7 +736,7 @@ int bdg_graph_deljoin_launch(bdg_ctx* ctx, const uint32_t* d_ranks, uint32_t n, 
         while (l2_max < 12u && l2_max < keybits - l1 && ((cap_ent / nsub + 1ull) >> (l1 + l2_max)) > 64ull) ++l2_max;
         if (knobs.dj_l2max >= 0) l2_max = (uint32_t)std::min((int64_t)l2_max, (int64_t)knobs.dj_l2max);      // (for tests: oversize buckets)
         const uint32_t target = 256u * 5u / 8u;      // entries a fine bucket should hold at most on average (80 .. 160 of the 256 a wave of k_d2_pairs_w takes)
-        uint32_t tiles_want = (uint32_t)ctx->g_cus * 8u;
+        uint32_t tiles_want = (uint32_t)ctx->cus * 8u;
         uint32_t rows_per_tile = ((n + tiles_want - 1u) / tiles_want + 63u) & ~63u;
         if (rows_per_tile < 64u) rows_per_tile = 64u;
         const uint32_t ntiles = (n + rows_per_tile - 1u) / rows_per_tile;
@@ -773,8 +773,8 @@ int bdg_graph_deljoin_launch(bdg_ctx* ctx, const uint32_t* d_ranks, uint32_t n, 
         }
         {
             ScopedKernelTimer tm(ctx, one_deletion ? "k_d1_pairs" : "k_d2_pairs");
-            const uint32_t wgrid = (uint32_t)ctx->g_cus * knobs.d2_pairs_blocks;      // (k_d2_pairs_w: 36 KB of LDS a block of 4 waves at 256 entries a wave)
-            const uint32_t bgrid = (uint32_t)ctx->g_cus;
+            const uint32_t wgrid = (uint32_t)ctx->cus * knobs.d2_pairs_blocks;        // (k_d2_pairs_w: 36 KB of LDS a block of 4 waves at 256 entries a wave)
+            const uint32_t bgrid = (uint32_t)ctx->cus;
             if (one_deletion) dj_pairs<1>(wgrid, bgrid, st, ovf, e_b, fstart, geom, l1, d_ranks, row_begin, row_end, thr, qgram_T, d_out, cap, d_n_edges);
             else dj_pairs<2>(wgrid, bgrid, st, ovf, e_b, fstart, geom, l1, d_ranks, row_begin, row_end, thr, qgram_T, d_out, cap, d_n_edges);
         }

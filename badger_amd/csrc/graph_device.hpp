@@ -206,14 +206,3 @@ __device__ __forceinline__ void verify_queued(PairQueue<2>& q, bool tail, uint32
 }
 
 }  // namespace gdev
-
-// once per context: the device's compute units (the joins size their resident grids from them)
-static inline int bdg_graph_cus(bdg_ctx* ctx)
-{
-    if (!ctx->g_cus) {
-        hipDeviceProp_t prop;
-        BDG_HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ctx->g_cus = prop.multiProcessorCount;
-    }
-    return BDG_OK;
-}

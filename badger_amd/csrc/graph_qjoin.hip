@@ -345,7 +345,7 @@ void k_graph_qjoin_w(const uint32_t* __restrict__ ranks, uint32_t n, uint32_t ro
 static int qj_props(bdg_ctx* ctx)
 {
     int rc;
-    if ((rc = bdg_graph_cus(ctx))) return rc;
+    if ((rc = bdg_cus(ctx))) return rc;
     if (!ctx->g_qjw_per_cu) {
         int per_cu = 0, per_cu_w = 0;
         BDG_HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_graph_qjoin, 256, 0));
@@ -396,14 +396,14 @@ int bdg_graph_qjoin_launch(bdg_ctx* ctx, const uint32_t* d_ranks, uint32_t n, ui
     if ((rc = qj_props(ctx))) return rc;
     if (closed_form) {
         ScopedKernelTimer tm(ctx, "k_graph_qjoin");
-        uint32_t grid = (uint32_t)ctx->g_qj_per_cu * (uint32_t)ctx->g_cus;          // resident grid, rows interleaved
+        uint32_t grid = (uint32_t)ctx->g_qj_per_cu * (uint32_t)ctx->cus;            // resident grid, rows interleaved
         if (grid > row_end - row_begin) grid = row_end - row_begin;
         hipLaunchKernelGGL(k_graph_qjoin, dim3(grid), dim3(256), 0, st, d_ranks, n, row_begin, row_end, v_out, pos_of, split, G,
                            thr, qgram_T, d_out, cap, d_n_edges);
     } else {
         ScopedKernelTimer tm(ctx, "k_graph_qjoin_w");
         const uint32_t waves = qgram_T < 2 ? 4u : 2u;
-        uint32_t grid = (uint32_t)ctx->g_qjw_per_cu * (uint32_t)ctx->g_cus;         // resident grid, one row per wave at a time, rows interleaved
+        uint32_t grid = (uint32_t)ctx->g_qjw_per_cu * (uint32_t)ctx->cus;           // resident grid, one row per wave at a time, rows interleaved
         const uint32_t want = (row_end - row_begin + waves - 1u) / waves;
         if (grid > want) grid = want;
         if (qgram_T < 2) qjw_launch<8192, 4, false>(grid, st, d_ranks, n, row_begin, row_end, v_out, pos_of, bucket_off, thr, qgram_T, d_out, cap, d_n_edges);
