@@ -77,6 +77,9 @@ DONOR_ENTRY_DTYPE = np.dtype([("variant", "<u4"), ("ref", "<u4"), ("alt", "<u4")
 DONOR_DTYPE = np.dtype([("best_score", "<i8"), ("second_score", "<i8"), ("doublet_score", "<i8"), ("donor1", "<u4"), ("donor2", "<u4"),
                         ("pair", "<u4"), ("pad", "<u4")])
 DONORS_MAX, DONOR_NONE = 32, 0xFFFFFFFF
+# bdg_cluster_restart: a restart of bdg_donor_cluster (its L, its iterations, whether the last one changed nothing)
+CLUSTER_RESTART_DTYPE = np.dtype([("score", "<i8"), ("iterations", "<u4"), ("converged", "<u4")])
+CLUSTER_NO_GENOTYPE = 3
 FLAG_REV = 1
 FLAG_RANK_OK = 2
 FLAG_BC16 = 4
@@ -120,6 +123,7 @@ EXPORTS = [
     "bdg_alleles_index_build", "bdg_alleles_index_stats", "bdg_alleles_assign_dev", "bdg_alleles_assign",
     "bdg_alleles_index_values",
     "bdg_donor_scores", "bdg_donor_scores_dev",
+    "bdg_donor_cluster_counts_dev", "bdg_donor_cluster_assign_dev", "bdg_donor_cluster_words_dev", "bdg_donor_cluster",
 ]
 
 
@@ -417,6 +421,10 @@ def load():
     L.bdg_alleles_assign.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
     L.bdg_donor_scores.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     L.bdg_donor_scores_dev.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
+    L.bdg_donor_cluster_counts_dev.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp]
+    L.bdg_donor_cluster_assign_dev.argtypes = [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+    L.bdg_donor_cluster_words_dev.argtypes = [vp, vp, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp]
+    L.bdg_donor_cluster.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, u32, u32, vp, vp, C.POINTER(u32), vp, vp, vp]
     L.bdg_ingest_next.argtypes = [vp, C.POINTER(IngestChunk)]
     L.bdg_ingest_release.argtypes = [vp, u32]
     L.bdg_ingest_error.argtypes = [vp]
@@ -985,6 +993,60 @@ class Context:
         self._check(self.lib.bdg_donor_scores_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_geno), int(n_variants),
                                                   int(n_donors), tables.ctypes.data, _ptr(d_recs),
                                                   _ptr(d_scores) if d_scores is not None else None))
+
+    def donor_cluster(self, entries, cell_off, n_variants, n_clusters, tables, z0, max_iter, with_scores=False):
+        """the fit of bdg_donor_cluster over host arrays: entries and cell_off as donor_scores takes them, over n_variants variants;
+        z0 uint32 [restarts, n_cells], the start assignments -> dict(z uint32 [n_cells], restarts CLUSTER_RESTART_DTYPE, chosen,
+        recs DONOR_DTYPE [n_cells], genotypes uint8 [K, n_variants] (CLUSTER_NO_GENOTYPE: no molecule), and with with_scores
+        scores int64 [n_cells, H])"""
+        entries = np.ascontiguousarray(entries, dtype=DONOR_ENTRY_DTYPE)
+        cell_off = np.ascontiguousarray(cell_off, dtype=np.uint64)
+        tables = np.ascontiguousarray(tables, dtype=np.int32)
+        z0 = np.ascontiguousarray(z0, dtype=np.uint32)
+        n, k, v = len(cell_off) - 1, int(n_clusters), int(n_variants)
+        if n < 0 or len(tables) != 10 or (n and int(cell_off.max()) > len(entries)) or z0.ndim != 2 or z0.shape[1] != n:
+            raise ValueError("cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values, "
+                             "z0 is restarts x cells")
+        ok = 1 <= k <= DONORS_MAX
+        z, recs = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=DONOR_DTYPE)
+        table, chosen = np.zeros(len(z0), dtype=CLUSTER_RESTART_DTYPE), C.c_uint32(0)
+        geno = np.zeros((k if ok else 0, v), dtype=np.uint8)
+        scores = np.zeros((n, k + k * (k - 1) // 2 if ok else 0), dtype=np.int64) if with_scores else None
+        self._check(self.lib.bdg_donor_cluster(self.h, entries.ctypes.data if len(entries) else None, cell_off.ctypes.data, n, v, k,
+                                               tables.ctypes.data, z0.ctypes.data if z0.size else None, len(z0), int(max_iter),
+                                               z.ctypes.data, table.ctypes.data, C.byref(chosen), recs.ctypes.data,
+                                               scores.ctypes.data if with_scores and scores.size else None,
+                                               geno.ctypes.data if geno.size else None))
+        out = dict(z=z, restarts=table, chosen=int(chosen.value), recs=recs, genotypes=geno)
+        if with_scores:
+            out["scores"] = scores
+        return out
+
+    def donor_cluster_counts_dev(self, d_entries, d_cell_off, n_cells, d_z, n_variants, n_clusters, d_counts):
+        """bdg_donor_cluster_counts_dev: the count table uint32 [V, K, 2] of the assignment d_z, asynchronous"""
+        self._check(self.lib.bdg_donor_cluster_counts_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_z),
+                                                          int(n_variants), int(n_clusters), _ptr(d_counts)))
+
+    def donor_cluster_assign_dev(self, d_entries, d_cell_off, n_cells, d_z, d_gp, n_variants, n_clusters, tables, d_counts, d_z_out,
+                                 d_sums, d_scores=None):
+        """bdg_donor_cluster_assign_dev: one iteration over the counts of d_z (tables a host array), asynchronous"""
+        tables = np.ascontiguousarray(tables, dtype=np.int32)
+        if len(tables) != 10:
+            raise ValueError("ten table values")
+        self._check(self.lib.bdg_donor_cluster_assign_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_z), _ptr(d_gp),
+                                                          int(n_variants), int(n_clusters), tables.ctypes.data, _ptr(d_counts),
+                                                          _ptr(d_z_out), _ptr(d_scores) if d_scores is not None else None, _ptr(d_sums)))
+
+    def donor_cluster_words_dev(self, d_entries, d_cell_off, n_cells, d_z, d_gp, n_variants, n_clusters, tables, d_counts, d_words,
+                                d_genotypes=None):
+        """bdg_donor_cluster_words_dev: the entries' words and the clusters' genotypes from the counts of d_z, asynchronous"""
+        tables = np.ascontiguousarray(tables, dtype=np.int32)
+        if len(tables) != 10:
+            raise ValueError("ten table values")
+        self._check(self.lib.bdg_donor_cluster_words_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_z), _ptr(d_gp),
+                                                         int(n_variants), int(n_clusters), tables.ctypes.data, _ptr(d_counts),
+                                                         _ptr(d_words) if d_words is not None else None,
+                                                         _ptr(d_genotypes) if d_genotypes is not None else None))
 
     def device_to_host(self, ptr, n, dtype):
         """n elements of a device array the context holds (a kept array) as a numpy array; waits for the context's stream"""

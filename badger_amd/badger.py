@@ -10,8 +10,8 @@
                                 [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                 [--umi_per_gene [--gene_umi_dist 0|1 | --gene_umi_dist2]]
                                 [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]
-                                 [--donor_genotypes donors.tsv [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10]
-                                  [--donor_min_llr 2.0]]]
+                                 [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
+                                  [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
 
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR --matrix_from_reads
                                 [--tagged_reads tagged.fa] [the options of --count_matrix]
@@ -49,6 +49,10 @@ carry either allele of a variant of the read's gene, and a vote over the molecul
 0, 1, 2 or . per donor) assigns every cell to a donor: the device scores each cell's allele counts under every donor and every pair
 of donors, and donors.tsv names per barcode the singlet's donor, the doublet's pair, or * for a cell with too few covered variants or
 too small a lead; donor_summary.tsv counts them (donors.py, which also runs alone over a matrix directory).
+--donors K (behind --variants, in --donor_genotypes' place) needs no genotypes: the device clusters the cells into K donors by
+leave-one-out hard EM over their allele counts, from --donor_restarts random starts of at most --donor_max_iter iterations, and the
+same call follows with the donors cluster0 .. cluster<K-1>; cluster_genotypes.tsv holds the inferred genotypes in the format of
+--donor_genotypes and donor_clusters.tsv the restarts.  Every other file of DIR stays the same bytes.
 --matrix_from_reads writes the same DIR from the one pass over the reads: every read's gene (and isoform) call is made on the device
 from its cDNA where it lies in the read, while its chunk is there (genes.py MatrixFromReads).  --tagged_reads is then optional, and
 a tagged file is written as without the flag but not read back; without it the input is read once.  One column differs: the UR of

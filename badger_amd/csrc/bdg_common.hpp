@@ -169,6 +169,7 @@ struct bdg_ctx {
     int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
     int em_per_cu = 0;                      // em_kernels.hip: blocks of k_em_tcc resident on a compute unit (asked once)
     int donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
+    int cluster_per_cu[3] = { 0, 0, 0 };    // demux_kernels.hip: the same of k_cluster_counts, k_cluster_assign and k_cluster_words
 
     // ---- whitelist index (nearest_kernels.hip)
     DevBuf w_sorted;     // uint32 [nw] ranks ascending

@@ -69,6 +69,9 @@ int bdg_cdna_len_launch(bdg_ctx*, const bdg_trim_rec*, const bdg_chimera_rec*, u
 int bdg_genes_keep_check(bdg_ctx*, uint32_t min_hits, uint32_t margin);
 int bdg_genes_kept_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, const bdg_extract_rec*, const bdg_trim_rec*, const bdg_chimera_rec*,
                           uint32_t min_hits, uint32_t margin, bdg_gene_rec*, bdg_iso_rec*);
+// donors_kernels.hip: k_donor_scores over device arrays (the word of entry e is d_words[e.variant], D donors; d_scores null: no matrix)
+int bdg_donor_launch(bdg_ctx*, const bdg_donor_entry*, const uint64_t*, uint32_t, const uint64_t* d_words, uint32_t n_words, uint32_t D,
+                     const int32_t* tables, bdg_donor_rec*, int64_t* d_scores);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // trim5p_kernels.hip

@@ -174,6 +174,13 @@ int donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t*
 
 }  // namespace
 
+// the launch as demux_kernels.hip calls it, for the final records of a fit
+int bdg_donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells, const uint64_t* d_words,
+                     uint32_t n_words, uint32_t D, const int32_t* tables, bdg_donor_rec* d_recs, int64_t* d_scores)
+{
+    return donor_launch(ctx, d_entries, d_cell_off, n_cells, d_words, n_words, D, tables, d_recs, d_scores);
+}
+
 extern "C" {
 
 int bdg_donor_scores_dev(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells,

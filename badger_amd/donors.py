@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Cells to donors from known genotypes (--donor_genotypes): which donor of a pool each cell comes from, and which
-cells are two donors in one droplet.
+"""Cells to donors from known genotypes (--donor_genotypes) or without them (--donors K): which donor of
+a pool each cell comes from, and which cells are two donors in one droplet.
 
-    python -m badger_amd.donors -d DIR --donor_genotypes donors.tsv [-o OUT_DIR] [--donor_error 0.01] [--doublet_rate 0.1]
+    python -m badger_amd.donors -d DIR (--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50]
+                                [--donor_seed 1]) [-o OUT_DIR] [--donor_error 0.01] [--doublet_rate 0.1]
                                 [--donor_min_variants 10] [--donor_min_llr 2.0]
 
 reads variants.tsv, barcodes.tsv, allele_ref.mtx and allele_alt.mtx of a matrix directory that --variants wrote and writes
@@ -35,6 +36,31 @@ The rule.  All integer, so the order of the sums does not matter.
     files     donors.tsv: one row per barcode of barcodes.tsv, cells without entries too.  The donor is A, A,B or *; scores and
               margin are %.3f of the value / 65536; * stands for an absent value.  donor_summary.tsv: per donor its singlets,
               then the doublets and the unassigned cells.
+
+Without genotypes (--donors K) the cells are clustered first: leave-one-out hard EM, all integer as above, which
+include/badger_hip.h states at bdg_donor_cluster_assign_dev.  The CHECKER is pooled_genotypes, cluster_counts, loo_genotypes,
+cluster_step, cluster_fit and entry_words; the DRIVER is ClusterDemux with device_cluster (bdg_donor_cluster).
+    entries   as above, over all V variants of the variants file; K clusters, 1 .. 32.
+    genotypes only the levels 0, 2 and 4 serve, as g = 0, 1, 2: A_g = tables[2 g], B_g = tables[5 + 2 g].  best(R, Al) is the g that
+              maximises R A_g + Al B_g, of equal values the lowest.
+    pooled    gp[v] = best(Rtot[v], Atot[v]) over the molecules of all cells at v; a variant whose molecules sum to 2^32 or more
+              is refused.
+    counts    of an assignment z (a cluster per cell): R[v][k], Al[v][k] the ref and alt molecules at v of the cells with z == k.
+    leave-one-out  for an entry (v, r, a) of cell c and cluster k: R' = R[v][k] - r, Al' = Al[v][k] - a if z[c] == k, else the counts
+              themselves; g(c, j, k) = gp[v] if R' + Al' == 0, else best(R', Al').
+    iteration S[c][k] = the sum over c's entries of r A_g + a B_g with g = g(c, j, k), in int64.  z'[c] is the k of the highest
+              S[c][k], of equal ones the lowest (a cell without entries: 0).  L = the sum over the cells of S[c][z'[c]], changed =
+              the number of cells with z' != z.
+    restart r z0[c] = splitmix64((seed << 40) ^ (r << 32) ^ c) mod K, with splitmix64(x): x += 0x9E3779B97F4A7C15, x = (x ^ x >> 30)
+              0xBF58476D1CE4E5B9, x = (x ^ x >> 27) 0x94D049BB133111EB, x ^ x >> 31, in uint64.  Iterate; stop behind the iteration
+              with changed == 0 or behind max_iter iterations (the rule is not monotone and may cycle).  The result is the last
+              iteration's z' and L.
+    fit       the restart with the highest L, of equal ones the first.
+    records   with z the fit's assignment, entry j gets the word that holds g(c, j, k) in bits 2 k, 2 k + 1; the records are the
+              rule's above, D = K, over the entries renumbered so that entry j's variant is j and these words.  call, donors_text
+              and summary_text run unchanged; the donors are cluster0 .. cluster<K-1>.
+    files     cluster_genotypes.tsv: G[k][v] = best(R[v][k], Al[v][k]) of the fit, . without a molecule, in the format of
+              --donor_genotypes.  donor_clusters.tsv: per restart its iterations, whether it stopped by itself, L and the choice.
 """
 import argparse
 import logging
@@ -53,6 +79,11 @@ ENTRY_DTYPE = np.dtype([("variant", "<u4"), ("ref", "<u4"), ("alt", "<u4"), ("pa
 REC_DTYPE = np.dtype([("best_score", "<i8"), ("second_score", "<i8"), ("doublet_score", "<i8"), ("donor1", "<u4"), ("donor2", "<u4"),
                       ("pair", "<u4"), ("pad", "<u4")])
 FILES = ("donors.tsv", "donor_summary.tsv")
+CLUSTER_FILES = ("cluster_genotypes.tsv", "donor_clusters.tsv")
+CLUSTERS_HEADER = "restart\titerations\tconverged\tL\tchosen\n"
+VARIANT_DEPTH_MAX, NO_GENOTYPE = 1 << 32, 3
+RESTARTS_DEFAULT, RESTARTS_MAX, MAX_ITER_DEFAULT, MAX_ITER_MAX, SEED_DEFAULT, SEED_MAX = 8, 1000, 50, 10000, 1, (1 << 23) - 1
+RESTART_DTYPE = np.dtype([("score", "<i8"), ("iterations", "<u4"), ("converged", "<u4")])
 DONORS_HEADER = "barcode\tstatus\tdonor\tvariants\tmolecules\tbest\tbest_score\tsecond\tsecond_score\tdoublet\tdoublet_score\tmargin\n"
 SUMMARY_HEADER = "donor\tcells\n"
 TOKENS = {"0": 0, "1": 1, "2": 2, ".": None, "0/0": 0, "0/1": 1, "1/0": 1, "1/1": 2, "./.": None,
@@ -175,6 +206,225 @@ def call(recs, n_entries, n_donors, doublet_rate=DOUBLET_RATE_DEFAULT, min_varia
         margin.append(m)
         status[c] = UNASSIGNED if int(n_entries[c]) < min_variants or (m is not None and m < floor) else kind[c]
     return status, kind, margin
+
+
+# ---------------------------------------------------------------- the checker without genotypes ----
+def _check_k(n_clusters):
+    if not 1 <= n_clusters <= D_MAX:
+        raise ValueError("the number of clusters must be 1 .. 32")
+
+
+def _used(entries, cell_off):
+    """the entries the offsets reference and the offsets from 0 (int64)"""
+    off = np.asarray(cell_off, dtype=np.uint64).astype(np.int64)
+    if len(off) < 1 or (np.diff(off) < 0).any():
+        raise ValueError("cell offsets must be non-decreasing")
+    return np.asarray(entries, dtype=ENTRY_DTYPE)[int(off[0]):int(off[-1])], off - off[0]
+
+
+def _geno_tables(tables):
+    t = np.asarray(tables, dtype=np.int64)
+    return t[0:LEVELS:2], t[LEVELS::2]
+
+
+def _best_genotype(r, a, tables):
+    """best(R, Al) of the rule, elementwise over int64 arrays"""
+    a_of, b_of = _geno_tables(tables)
+    return np.argmax(np.stack([r * a_of[g] + a * b_of[g] for g in range(3)]), axis=0).astype(np.uint8)   # (the first of equal ones)
+
+
+def check_cluster_inputs(entries, cell_off, n_variants, n_clusters):
+    """the argument errors of bdg_donor_cluster that the entries can cause, as ValueError -> (used entries, offsets from 0)"""
+    _check_k(n_clusters)
+    used, off = _used(entries, cell_off)
+    if len(used) and int(used["variant"].max()) >= n_variants:
+        raise ValueError("an entry's variant is not below n_variants")
+    depth = np.concatenate([[0], np.cumsum(used["ref"].astype(np.int64) + used["alt"].astype(np.int64))])
+    if len(off) > 1 and int((depth[off[1:]] - depth[off[:-1]]).max()) >= DEPTH_MAX:
+        raise ValueError("the counts of a cell sum to 2^40 or more")
+    return used, off
+
+
+def pooled_genotypes(entries, n_variants, tables):
+    """gp uint8 [n_variants] from all the entries given"""
+    entries = np.asarray(entries, dtype=ENTRY_DTYPE)
+    r_tot, a_tot = np.zeros(n_variants, dtype=np.int64), np.zeros(n_variants, dtype=np.int64)
+    np.add.at(r_tot, entries["variant"], entries["ref"].astype(np.int64))
+    np.add.at(a_tot, entries["variant"], entries["alt"].astype(np.int64))
+    if n_variants and int((r_tot + a_tot).max()) >= VARIANT_DEPTH_MAX:
+        raise ValueError("the counts of a variant sum to 2^32 or more")
+    return _best_genotype(r_tot, a_tot, tables)
+
+
+def cluster_counts(entries, cell_off, z, n_variants, n_clusters):
+    """-> (R, Al) int64 [n_variants, K] of the assignment z"""
+    used, off = _used(entries, cell_off)
+    k_of = np.repeat(np.asarray(z, dtype=np.int64), np.diff(off))
+    r, al = np.zeros((n_variants, n_clusters), dtype=np.int64), np.zeros((n_variants, n_clusters), dtype=np.int64)
+    np.add.at(r, (used["variant"], k_of), used["ref"].astype(np.int64))
+    np.add.at(al, (used["variant"], k_of), used["alt"].astype(np.int64))
+    return r, al
+
+
+def loo_genotypes(entries, cell_off, z, gp, n_clusters, tables):
+    """g(c, j, k) -> uint8 [entries, K]"""
+    used, off = _used(entries, cell_off)
+    r, al = cluster_counts(used, off, z, len(gp), n_clusters)
+    k_of, rows = np.repeat(np.asarray(z, dtype=np.int64), np.diff(off)), np.arange(len(used))
+    r1, al1 = r[used["variant"]], al[used["variant"]]
+    r1[rows, k_of] -= used["ref"].astype(np.int64)
+    al1[rows, k_of] -= used["alt"].astype(np.int64)
+    own = np.asarray(gp, dtype=np.uint8)[used["variant"]]
+    return np.where(r1 + al1 == 0, own[:, None], _best_genotype(r1, al1, tables)).astype(np.uint8)
+
+
+def cluster_step(entries, cell_off, z, gp, n_clusters, tables):
+    """one iteration -> (z' uint32 [cells], L, changed, S int64 [cells, K])"""
+    used, off = _used(entries, cell_off)
+    g = loo_genotypes(used, off, z, gp, n_clusters, tables)
+    a_of, b_of = _geno_tables(tables)
+    part = used["ref"].astype(np.int64)[:, None] * a_of[g] + used["alt"].astype(np.int64)[:, None] * b_of[g]
+    run = np.concatenate([np.zeros((1, n_clusters), dtype=np.int64), np.cumsum(part, axis=0)])
+    s = run[off[1:]] - run[off[:-1]]
+    z1 = np.argmax(s, axis=1).astype(np.uint32) if len(s) else np.zeros(0, dtype=np.uint32)   # (the first of equal ones)
+    return z1, int(s[np.arange(len(s)), z1].sum()), int((z1 != np.asarray(z, dtype=np.uint32)).sum()), s
+
+
+def splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return x ^ (x >> 31)
+
+
+def start_assignments(n_cells, n_clusters, restarts, seed):
+    """z0 uint32 [restarts, cells]: the rule's formula, vectorised in uint64 (which wraps as the formula does)"""
+    _check_k(n_clusters)
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        x = (u(seed << 40) ^ (np.arange(restarts, dtype=u)[:, None] << u(32)) ^ np.arange(n_cells, dtype=u)[None, :]) + u(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> u(30))) * u(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> u(27))) * u(0x94D049BB133111EB)
+        x = x ^ (x >> u(31))
+    return (x % u(n_clusters)).astype(np.uint32)
+
+
+def cluster_restarts(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter):
+    """the restarts from the rows of z0 and the choice among them -> dict(z, restarts RESTART_DTYPE, chosen, gp)"""
+    used, off = check_cluster_inputs(entries, cell_off, n_variants, n_clusters)
+    z0 = np.asarray(z0, dtype=np.uint32)
+    if z0.ndim != 2 or len(z0) < 1 or z0.shape[1] != len(off) - 1 or max_iter < 1:
+        raise ValueError("z0 is restarts x cells, at least one restart and one iteration")
+    if z0.size and int(z0.max()) >= n_clusters:
+        raise ValueError("a start cluster is not below the number of clusters")
+    gp = pooled_genotypes(used, n_variants, tables)
+    table, results = np.zeros(len(z0), dtype=RESTART_DTYPE), []
+    for r, z in enumerate(z0):
+        for it in range(1, max_iter + 1):
+            z, total, changed, _ = cluster_step(used, off, z, gp, n_clusters, tables)
+            if changed == 0:
+                break
+        table[r] = (total, it, int(changed == 0))
+        results.append(z)
+    chosen = int(np.argmax(table["score"]))                                                       # (the first of equal ones)
+    return dict(z=results[chosen], restarts=table, chosen=chosen, gp=gp)
+
+
+def cluster_fit(entries, cell_off, n_variants, n_clusters, tables, seed=SEED_DEFAULT, restarts=RESTARTS_DEFAULT, max_iter=MAX_ITER_DEFAULT):
+    """the fit from the rule's own starts"""
+    z0 = start_assignments(len(np.asarray(cell_off)) - 1, n_clusters, restarts, seed)
+    return cluster_restarts(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter)
+
+
+def entry_words(entries, cell_off, z, gp, n_clusters, tables):
+    """the 64-bit word per entry: g(c, j, k) in bits 2 k, 2 k + 1"""
+    g = loo_genotypes(entries, cell_off, z, gp, n_clusters, tables).astype(np.uint64)
+    words = np.zeros(len(g), dtype=np.uint64)
+    for k in range(n_clusters):
+        words |= g[:, k] << np.uint64(2 * k)
+    return words
+
+
+def cluster_genotypes(entries, cell_off, z, n_variants, n_clusters, tables):
+    """G uint8 [K, n_variants], NO_GENOTYPE where the cluster has no molecule"""
+    r, al = cluster_counts(entries, cell_off, z, n_variants, n_clusters)
+    return np.where(r + al == 0, NO_GENOTYPE, _best_genotype(r, al, tables)).astype(np.uint8).T.copy()
+
+
+def renumbered(entries):
+    """the entries with entry j's variant set to j"""
+    out = np.array(entries, dtype=ENTRY_DTYPE)
+    out["variant"] = np.arange(len(out), dtype=np.uint32)
+    return out
+
+
+def checker_cluster(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter):
+    """what bdg_donor_cluster returns, by the checker: dict(z, restarts, chosen, recs, genotypes)"""
+    fit = cluster_restarts(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter)
+    used, off = _used(entries, cell_off)
+    words = entry_words(used, off, fit["z"], fit["gp"], n_clusters, tables)
+    recs = checker_records(renumbered(used), off.astype(np.uint64), words, n_clusters, tables)
+    return dict(z=fit["z"], restarts=fit["restarts"], chosen=fit["chosen"], recs=recs,
+                genotypes=cluster_genotypes(used, off, fit["z"], n_variants, n_clusters, tables))
+
+
+def device_cluster(ctx):
+    """the same on the device: bdg_donor_cluster"""
+    return lambda entries, cell_off, n_variants, n_clusters, tables, z0, max_iter: \
+        ctx.donor_cluster(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter)
+
+
+def cluster_genotypes_text(variant_ids, genotypes):
+    names = ["cluster%d" % k for k in range(len(genotypes))]
+    token = "012."
+    rows = ["variant\t%s\n" % "\t".join(names)]
+    rows += ["%s\t%s\n" % (v, "\t".join(token[g] for g in col)) for v, col in zip(variant_ids, np.asarray(genotypes).T.tolist())]
+    return "".join(rows).encode()
+
+
+def clusters_text(restarts, chosen):
+    rows = [CLUSTERS_HEADER]
+    rows += ["%d\t%d\t%d\t%.3f\t%d\n" % (r, it, conv, score / SCALE, int(r == chosen)) for r, (score, it, conv) in enumerate(restarts.tolist())]
+    return "".join(rows).encode()
+
+
+class ClusterOptions(tuple):
+    """(K, restarts, max_iter, seed) of --donors: what stands in the place of the genotype file's path"""
+    __slots__ = ()
+
+    def __new__(cls, n_clusters, restarts=RESTARTS_DEFAULT, max_iter=MAX_ITER_DEFAULT, seed=SEED_DEFAULT):
+        return tuple.__new__(cls, (n_clusters, restarts, max_iter, seed))
+
+
+class ClusterDemux:
+    """the hook of alleles.Caller without genotypes, called as Demux is.  run(entries, cell_off, V, K, tables, z0, max_iter) ->
+    dict(z, restarts, chosen, recs, genotypes) is checker_cluster or the device's equivalent (device_cluster); fit = (K, restarts,
+    max_iter, seed); options as Demux takes them"""
+
+    def __init__(self, variant_ids, fit, run, options=(ERROR_DEFAULT, DOUBLET_RATE_DEFAULT, MIN_VARIANTS_DEFAULT, MIN_LLR_DEFAULT)):
+        self.variant_ids, self.fit, self.run, self.options = list(variant_ids), ClusterOptions(*fit), run, tuple(options)
+        _check_k(self.fit[0])
+
+    def __call__(self, cells, ref, alt):
+        n_clusters, restarts, max_iter, seed = self.fit
+        error, doublet_rate, min_variants, min_llr = self.options
+        n_variants = len(self.variant_ids)
+        names = ["cluster%d" % k for k in range(n_clusters)]
+        entries, cell_off = entries_of(ref, alt, len(cells), np.arange(n_variants))
+        out = self.run(entries, cell_off, n_variants, n_clusters, level_tables(error), start_assignments(len(cells), n_clusters, restarts, seed),
+                       max_iter)
+        recs = np.asarray(out["recs"]).view(REC_DTYPE).reshape(-1)
+        status, kind, margin = call(recs, np.diff(cell_off.astype(np.int64)), n_clusters, doublet_rate, min_variants, min_llr)
+        table, chosen = np.asarray(out["restarts"]), int(out["chosen"])
+        files = {"donors.tsv": donors_text(cells, names, entries, cell_off, recs, status, margin),
+                 "donor_summary.tsv": summary_text(names, recs, status),
+                 "cluster_genotypes.tsv": cluster_genotypes_text(self.variant_ids, out["genotypes"]),
+                 "donor_clusters.tsv": clusters_text(table, chosen)}
+        counts = dict(donors=n_clusters, donor_cells=len(cells), donor_singlets=int((status == SINGLET).sum()),
+                      donor_doublets=int((status == DOUBLET).sum()), donor_unassigned=int((status == UNASSIGNED).sum()),
+                      donor_entries=len(entries), donor_variants=int(len(np.unique(entries["variant"]))), donor_restarts=len(table),
+                      donor_chosen=chosen, donor_iterations=int(table["iterations"][chosen]), donor_converged=int(table["converged"][chosen]))
+        return files, counts
 
 
 # ---------------------------------------------------------------- the genotype file ----
@@ -329,12 +579,23 @@ class Demux:
 
 
 def device_demux(ctx, path, variant_ids, options):
-    """the genotypes of `path` over the variants of the variants file -> Demux on the device"""
+    """the genotypes of `path` over the variants of the variants file -> Demux on the device; path a ClusterOptions (--donors):
+    the ClusterDemux on the device over all the variants"""
+    if isinstance(path, ClusterOptions):
+        return ClusterDemux(variant_ids, path, device_cluster(ctx), options)
     return Demux(read_genotypes(path, variant_ids), device_records(ctx), options)
 
 
 def log_counts(counts, out_dir):
     if "donor_cells" not in counts:
+        return
+    if "donor_restarts" in counts:
+        logger.info("Donors: %d cells, %d singlets, %d doublets, %d unassigned; %d clusters from %d entries at %d covered variants, "
+                    "restart %d of %d chosen (%d iterations, %s); %s in %s"
+                    % (counts["donor_cells"], counts["donor_singlets"], counts["donor_doublets"], counts["donor_unassigned"],
+                       counts["donors"], counts["donor_entries"], counts["donor_variants"], counts["donor_chosen"], counts["donor_restarts"],
+                       counts["donor_iterations"], "stopped by itself" if counts["donor_converged"] else "ended by --donor_max_iter",
+                       ", ".join(FILES + CLUSTER_FILES), out_dir))
         return
     logger.info("Donors: %d cells, %d singlets, %d doublets, %d unassigned; %d donors, %d entries at %d usable variants (%d rows "
                 "skipped for an unknown id, %d dropped for a missing genotype, %d variants without a row); %s in %s"
@@ -371,32 +632,75 @@ def donor_min_variants_arg(v):
     return x
 
 
-def add_donor_options(p, required=False):
-    p.add_argument("--donor_genotypes", default=None, metavar="TSV", required=required,
+def _integer_arg(flag, lo, hi, text):
+    def parse(v):
+        try:
+            x = int(v)
+        except ValueError:
+            x = lo - 1
+        if not lo <= x <= hi:
+            raise argparse.ArgumentTypeError("%s takes an integer, %s" % (flag, text))
+        return x
+    return parse
+
+
+donors_arg = _integer_arg("--donors", 1, D_MAX, "1 .. %d" % D_MAX)
+donor_restarts_arg = _integer_arg("--donor_restarts", 1, RESTARTS_MAX, "1 .. %d" % RESTARTS_MAX)
+donor_max_iter_arg = _integer_arg("--donor_max_iter", 1, MAX_ITER_MAX, "1 .. %d" % MAX_ITER_MAX)
+donor_seed_arg = _integer_arg("--donor_seed", 0, SEED_MAX, "0 .. %d" % SEED_MAX)
+
+
+def add_donor_options(p):
+    p.add_argument("--donors", dest="donor_clusters", type=donors_arg, default=None, metavar="K",
+                   help="--variants, without genotypes: cluster the cells into K donors (1 .. %d) by their allele counts on the device "
+                        "(leave-one-out hard EM), then call singlets and doublets as --donor_genotypes does; writes %s beside the "
+                        "matrix; not with --donor_genotypes" % (D_MAX, ", ".join(FILES + CLUSTER_FILES)))
+    p.add_argument("--donor_restarts", type=donor_restarts_arg, default=None, metavar="N",
+                   help="--donors: random starts, the one with the best held-out score is kept (default %d, 1 .. %d)"
+                        % (RESTARTS_DEFAULT, RESTARTS_MAX))
+    p.add_argument("--donor_max_iter", type=donor_max_iter_arg, default=None, metavar="N",
+                   help="--donors: iterations of a start at most (default %d, 1 .. %d)" % (MAX_ITER_DEFAULT, MAX_ITER_MAX))
+    p.add_argument("--donor_seed", type=donor_seed_arg, default=None, metavar="N",
+                   help="--donors: seed of the starts (default %d, 0 .. %d)" % (SEED_DEFAULT, SEED_MAX))
+    p.add_argument("--donor_genotypes", default=None, metavar="TSV",
                    help="--variants: the donors' genotypes, header variant<TAB>donor names, then id<TAB>0|1|2|. per donor (also "
                         "0/0 0/1 1/1 ./.): every cell's donor, or pair of donors, from its allele counts on the device; writes %s "
                         "beside the matrix" % ", ".join(FILES))
     p.add_argument("--donor_error", type=donor_error_arg, default=None, metavar="E",
-                   help="--donor_genotypes: chance that a molecule shows the other allele (default %g, 1e-4 .. 0.25)" % ERROR_DEFAULT)
+                   help="--donor_genotypes or --donors: chance that a molecule shows the other allele (default %g, 1e-4 .. 0.25)" % ERROR_DEFAULT)
     p.add_argument("--doublet_rate", type=doublet_rate_arg, default=None, metavar="P",
-                   help="--donor_genotypes: share of the droplets that hold two donors, a prior (default %g)" % DOUBLET_RATE_DEFAULT)
+                   help="--donor_genotypes or --donors: share of the droplets that hold two donors, a prior (default %g)" % DOUBLET_RATE_DEFAULT)
     p.add_argument("--donor_min_variants", type=donor_min_variants_arg, default=None, metavar="N",
-                   help="--donor_genotypes: a cell with fewer covered variants is unassigned (default %d)" % MIN_VARIANTS_DEFAULT)
+                   help="--donor_genotypes or --donors: a cell with fewer covered variants is unassigned (default %d)" % MIN_VARIANTS_DEFAULT)
     p.add_argument("--donor_min_llr", type=donor_min_llr_arg, default=None, metavar="L",
-                   help="--donor_genotypes: a cell whose call leads the next best by less than L (natural log units) is unassigned "
+                   help="--donor_genotypes or --donors: a cell whose call leads the next best by less than L (natural log units) is unassigned "
                         "(default %g)" % MIN_LLR_DEFAULT)
 
 
-def check_donor_options(p, a, with_variants=True):
-    """the errors of --donor_genotypes and its four values, the same on every command line; sets a.donors to None without
-    --donor_genotypes, else to (path, (error, doublet rate, min variants, min llr))"""
+def check_donor_options(p, a, with_variants=True, required=False):
+    """the errors of --donor_genotypes, --donors and their values, the same on every command line; sets a.donors to None without
+    either, else to (path, (error, doublet rate, min variants, min llr)), with --donors a ClusterOptions in the path's place"""
     values = (a.donor_error, a.doublet_rate, a.donor_min_variants, a.donor_min_llr)
-    if any(v is not None for v in values) and not a.donor_genotypes:
+    fit = (a.donor_restarts, a.donor_max_iter, a.donor_seed)
+    if a.donor_clusters is not None and a.donor_genotypes:
+        p.error("--donors excludes --donor_genotypes: the donors are either inferred or given")
+    if required and a.donor_clusters is None and not a.donor_genotypes:
+        p.error("exactly one of --donor_genotypes and --donors is needed")
+    if any(v is not None for v in fit) and a.donor_clusters is None:
+        p.error("--donor_restarts, --donor_max_iter and --donor_seed need --donors")
+    if any(v is not None for v in values) and not a.donor_genotypes and a.donor_clusters is None:
         p.error("--donor_error, --doublet_rate, --donor_min_variants and --donor_min_llr need --donor_genotypes")
     if a.donor_genotypes and not with_variants:
         p.error("--donor_genotypes needs --variants: the donors are told apart by the allele counts")
+    if a.donor_clusters is not None and not with_variants:
+        p.error("--donors needs --variants: the donors are told apart by the allele counts")
     defaults = (ERROR_DEFAULT, DOUBLET_RATE_DEFAULT, MIN_VARIANTS_DEFAULT, MIN_LLR_DEFAULT)
-    a.donors = (a.donor_genotypes, tuple(d if v is None else v for v, d in zip(values, defaults))) if a.donor_genotypes else None
+    options = tuple(d if v is None else v for v, d in zip(values, defaults))
+    if a.donor_clusters is not None:
+        fit_defaults = (RESTARTS_DEFAULT, MAX_ITER_DEFAULT, SEED_DEFAULT)
+        a.donors = (ClusterOptions(a.donor_clusters, *(d if v is None else v for v, d in zip(fit, fit_defaults))), options)
+    else:
+        a.donors = (a.donor_genotypes, options) if a.donor_genotypes else None
 
 
 # ---------------------------------------------------------------- the stand-alone command line ----
@@ -439,13 +743,13 @@ def demux_directory(folder, demux_of, out_dir=None):
 
 
 def parse(args=None):
-    p = argparse.ArgumentParser(description="cells to donors from known genotypes, over the allele files of a matrix directory")
+    p = argparse.ArgumentParser(description="cells to donors, from known genotypes or by clustering, over the allele files of a matrix directory")
     p.add_argument("-d", "--directory", required=True, help="a matrix directory that --variants wrote")
     p.add_argument("-o", "--output", default=None, help="directory for %s (default: the matrix directory)" % ", ".join(FILES))
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
-    add_donor_options(p, required=True)
+    add_donor_options(p)
     a = p.parse_args(args)
-    check_donor_options(p, a)
+    check_donor_options(p, a, required=True)
     return a
 
 

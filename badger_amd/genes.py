@@ -6,8 +6,8 @@ that every read and molecule is compatible with.
                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                [--umi_per_gene --umi_len L [--gene_umi_dist 0|1 | --gene_umi_dist2]]
                                [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]
-                                [--donor_genotypes donors.tsv [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10]
-                                 [--donor_min_llr 2.0]]]
+                                [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
+                                 [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -941,7 +941,9 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
     EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
     (bdg_umi_dedup_genes) and gene_molecules.tsv, and with variants = (path, k, min_hits) (--variants) the allele table beside
     the genes table and the files of alleles.FILES, and with donors = (path, options) (--donor_genotypes, behind variants) the
-    donor of every cell from the allele counts on the device (bdg_donor_scores) and the files of donors.FILES -> counts"""
+    donor of every cell from the allele counts on the device (bdg_donor_scores) and the files of donors.FILES; with a
+    donors.ClusterOptions in the path's place (--donors) the donors are clusters fitted on the device (bdg_donor_cluster) and the
+    files of donors.CLUSTER_FILES come too -> counts"""
     from . import _native, alleles
     from . import donors as donors_step
     ctx = _native.default_context(device)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Measurements of the donor step (--donor_genotypes).  Every record is one JSON line on stdout and, with --out, in
-that file.
+"""Measurements of the donor step (--donor_genotypes; --donors K).  Every record is one JSON line on
+stdout and, with --out, in that file.
 
     python tools/donors_probe.py --device [--cells 10000] [--entries 300] [--donors 8 32] [--rounds 5] --out profiles/r29_donors.jsonl
         a synthetic pool on the device: per number of donors, bdg_donor_scores_dev over device-resident arrays in alternating
@@ -12,6 +12,13 @@ that file.
         the parent's against itself.
     python tools/donors_probe.py --bench --parent DIR [--pairs 3] --out ...
         bench.py --gpus 1 --steps 10 --warmup 3 in alternating fresh processes, this build and the parent's.
+    python tools/donors_probe.py --cluster [--cells 10000] [--entries 300] [--donors 8 32] [--rounds 5] --out profiles/r30_donor_clusters.jsonl
+        the clustering of --donors K on the same synthetic pool: per K one iteration over device-resident arrays (k_cluster_counts,
+        k_cluster_assign) and the final step (k_cluster_words, k_cluster_geno) from the event timers, k_donor_scores on the same
+        input in the same rounds, the numpy checker's iteration once, and a whole fit of 8 restarts (bdg_donor_cluster) from the
+        host clock.
+    python tools/donors_probe.py --cli --cluster_cli [--parent DIR] --out ...
+        --cli with its first comparison replaced: the stage-2 command with --donors 8 against --donor_genotypes (8 donors).
 """
 import argparse
 import json
@@ -89,6 +96,60 @@ def device_probe(args):
     ctx.close()
 
 
+def cluster_probe(args):
+    from badger_amd import _native
+    from badger_amd import donors as dn
+    ctx = _native.Context(0)
+    tables = dn.level_tables()
+    kernels = ("k_cluster_counts", "k_cluster_assign", "k_cluster_words", "k_cluster_geno", "k_donor_scores")
+    for k in args.donors:
+        entries, off, words = synthetic_pool(args.cells, args.entries, k)
+        n_variants, n = len(words), args.cells
+        z = dn.start_assignments(n, k, 1, 1)[0]
+        gp = dn.pooled_genotypes(entries, n_variants, tables)
+        d = [_native.DeviceArray.from_host(ctx, a) for a in (entries.view(np.uint32), off, z, gp, words)]
+        counts, z_out, sums = (_native.DeviceArray(ctx, b, np.uint8) for b in (8 * n_variants * k, 4 * n, 16))
+        d_words, geno = _native.DeviceArray(ctx, len(entries), np.uint64), _native.DeviceArray(ctx, n_variants * k, np.uint8)
+        recs = _native.DeviceArray(ctx, n * _native.DONOR_DTYPE.itemsize, np.uint8)
+        per_run = {name: [] for name in kernels}
+        ctx.profile(True)
+        for r in range(args.rounds + 1):                                  # (the first round warms up and is left out)
+            ctx.profile_reset()
+            ctx.donor_cluster_counts_dev(d[0], d[1], n, d[2], n_variants, k, counts)
+            ctx.donor_cluster_assign_dev(d[0], d[1], n, d[2], d[3], n_variants, k, tables, counts, z_out, sums)
+            ctx.donor_cluster_words_dev(d[0], d[1], n, d[2], d[3], n_variants, k, tables, counts, d_words, geno)
+            ctx.donor_scores_dev(d[0], d[1], n, d[4], n_variants, k, tables, recs)
+            ctx.synchronize()
+            times = ctx.profile_read()
+            if r:
+                for name in kernels:
+                    per_run[name].append(times[name][1])
+        ctx.profile(False)
+        got = (z_out.to_host().view(np.uint32), sums.to_host().view(np.int64).tolist(), d_words.to_host())
+        t0 = time.perf_counter()
+        z1, total, changed, _ = dn.cluster_step(entries, off, z, gp, k, tables)
+        checker_s = time.perf_counter() - t0
+        same = bool(got[0].tolist() == z1.tolist() and got[1] == [total, changed]
+                    and got[2].tolist() == dn.entry_words(entries, off, z, gp, k, tables).tolist())
+        for a in d + [counts, z_out, sums, d_words, geno, recs]:
+            a.free()
+        z0 = dn.start_assignments(n, k, 8, 1)
+        ctx.donor_cluster(entries, off, n_variants, k, tables, z0[:1], 2)        # (the staging buffers grow here)
+        t0 = time.perf_counter()
+        fit = ctx.donor_cluster(entries, off, n_variants, k, tables, z0, 50)
+        fit_s = time.perf_counter() - t0
+        med = {name: round(float(np.median(v)), 4) for name, v in per_run.items()}
+        emit(args.out, {"what": "one iteration of the clustering (counts with its clear, assign), the final step (words, genotypes) and "
+                                "k_donor_scores on the same input, device-resident; the numpy checker's iteration; a fit of 8 restarts",
+                        "cells": n, "entries_per_cell": args.entries, "clusters": k, "variants": n_variants,
+                        "kernel_ms": {name: [round(x, 4) for x in v] for name, v in per_run.items()}, "median_kernel_ms": med,
+                        "iteration_ms": round(med["k_cluster_counts"] + med["k_cluster_assign"], 4), "entry_bytes": int(entries.nbytes),
+                        "count_table_bytes": 8 * n_variants * k, "checker_iteration_s": round(checker_s, 3), "same_as_checker": same,
+                        "fit_restarts": 8, "fit_max_iter": 50, "fit_s": round(fit_s, 3), "fit_iterations": int(fit["restarts"]["iterations"].sum()),
+                        "fit_table": [list(x) for x in fit["restarts"].tolist()], "fit_chosen": fit["chosen"], "version": ctx_version()})
+    ctx.close()
+
+
 def ctx_version():
     from badger_amd import _native
     return _native.load().bdg_version().decode()
@@ -148,8 +209,12 @@ def cli_probe(args):
     tagged = ["--umi_dedup", "--tagged_reads", fa]
     run(ROOT, "warm", tagged)                                          # (the file into the page cache, the runtime's caches)
     matrix = tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix"), "--variants", var]
-    pairs("variants", (ROOT, matrix), "donors", (ROOT, matrix + ["--donor_genotypes", geno]),
-          "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --variants: with --donor_genotypes (8 donors) against without")
+    if args.cluster_cli:
+        pairs("genotypes", (ROOT, matrix + ["--donor_genotypes", geno]), "clusters", (ROOT, matrix + ["--donors", "8"]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --variants: with --donors 8 against --donor_genotypes (8 donors)")
+    else:
+        pairs("variants", (ROOT, matrix), "donors", (ROOT, matrix + ["--donor_genotypes", geno]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix --variants: with --donor_genotypes (8 donors) against without")
     if args.parent:
         parent = os.path.abspath(args.parent)
         pairs("parent", (parent, matrix), "flags_off", (ROOT, matrix),
@@ -182,6 +247,8 @@ def main():
     p.add_argument("--device", action="store_true")
     p.add_argument("--cli", action="store_true")
     p.add_argument("--bench", action="store_true")
+    p.add_argument("--cluster", action="store_true")
+    p.add_argument("--cluster_cli", action="store_true", help="--cli: --donors 8 against --donor_genotypes instead of --donor_genotypes against without")
     p.add_argument("--cells", type=int, default=10000)
     p.add_argument("--entries", type=int, default=300)
     p.add_argument("--donors", type=int, nargs="+", default=[8, 32])
@@ -195,6 +262,8 @@ def main():
         p.error("--bench needs --parent")
     if args.device:
         device_probe(args)
+    if args.cluster:
+        cluster_probe(args)
     if args.cli:
         cli_probe(args)
     if args.bench:
