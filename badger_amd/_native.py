@@ -970,13 +970,9 @@ class Context:
         """the donor records of the cells over host arrays (bdg_donor_scores): entries DONOR_ENTRY_DTYPE, cell c the entries
         cell_off[c] .. cell_off[c + 1] - 1, geno uint64 per variant (donor i's dosage in bits 2 i, 2 i + 1), tables int32 [10]
         (A_0 .. A_4, B_0 .. B_4) -> DONOR_DTYPE [n_cells], and with with_scores the int64 matrix [n_cells, H] behind it"""
-        entries = np.ascontiguousarray(entries, dtype=DONOR_ENTRY_DTYPE)
-        cell_off = np.ascontiguousarray(cell_off, dtype=np.uint64)
+        entries, cell_off, tables, n = _donor_inputs(entries, cell_off, tables)
         geno = np.ascontiguousarray(geno, dtype=np.uint64)
-        tables = np.ascontiguousarray(tables, dtype=np.int32)
-        n, d = len(cell_off) - 1, int(n_donors)
-        if n < 0 or len(tables) != 10 or (n and int(cell_off.max()) > len(entries)):
-            raise ValueError("cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values")
+        d = int(n_donors)
         recs = np.zeros(n, dtype=DONOR_DTYPE)
         h = d + d * (d - 1) // 2 if 1 <= d <= DONORS_MAX else 0
         scores = np.zeros((n, h), dtype=np.int64) if with_scores else None
@@ -987,9 +983,7 @@ class Context:
 
     def donor_scores_dev(self, d_entries, d_cell_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, d_scores=None):
         """bdg_donor_scores_dev: the same over device arrays (tables a host array; d_scores None: no matrix), asynchronous"""
-        tables = np.ascontiguousarray(tables, dtype=np.int32)
-        if len(tables) != 10:
-            raise ValueError("ten table values")
+        tables = _tables10(tables)
         self._check(self.lib.bdg_donor_scores_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_geno), int(n_variants),
                                                   int(n_donors), tables.ctypes.data, _ptr(d_recs),
                                                   _ptr(d_scores) if d_scores is not None else None))
@@ -999,14 +993,9 @@ class Context:
         z0 uint32 [restarts, n_cells], the start assignments -> dict(z uint32 [n_cells], restarts CLUSTER_RESTART_DTYPE, chosen,
         recs DONOR_DTYPE [n_cells], genotypes uint8 [K, n_variants] (CLUSTER_NO_GENOTYPE: no molecule), and with with_scores
         scores int64 [n_cells, H])"""
-        entries = np.ascontiguousarray(entries, dtype=DONOR_ENTRY_DTYPE)
-        cell_off = np.ascontiguousarray(cell_off, dtype=np.uint64)
-        tables = np.ascontiguousarray(tables, dtype=np.int32)
         z0 = np.ascontiguousarray(z0, dtype=np.uint32)
-        n, k, v = len(cell_off) - 1, int(n_clusters), int(n_variants)
-        if n < 0 or len(tables) != 10 or (n and int(cell_off.max()) > len(entries)) or z0.ndim != 2 or z0.shape[1] != n:
-            raise ValueError("cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values, "
-                             "z0 is restarts x cells")
+        entries, cell_off, tables, n = _donor_inputs(entries, cell_off, tables, z0)
+        k, v = int(n_clusters), int(n_variants)
         ok = 1 <= k <= DONORS_MAX
         z, recs = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=DONOR_DTYPE)
         table, chosen = np.zeros(len(z0), dtype=CLUSTER_RESTART_DTYPE), C.c_uint32(0)
@@ -1030,9 +1019,7 @@ class Context:
     def donor_cluster_assign_dev(self, d_entries, d_cell_off, n_cells, d_z, d_gp, n_variants, n_clusters, tables, d_counts, d_z_out,
                                  d_sums, d_scores=None):
         """bdg_donor_cluster_assign_dev: one iteration over the counts of d_z (tables a host array), asynchronous"""
-        tables = np.ascontiguousarray(tables, dtype=np.int32)
-        if len(tables) != 10:
-            raise ValueError("ten table values")
+        tables = _tables10(tables)
         self._check(self.lib.bdg_donor_cluster_assign_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_z), _ptr(d_gp),
                                                           int(n_variants), int(n_clusters), tables.ctypes.data, _ptr(d_counts),
                                                           _ptr(d_z_out), _ptr(d_scores) if d_scores is not None else None, _ptr(d_sums)))
@@ -1040,9 +1027,7 @@ class Context:
     def donor_cluster_words_dev(self, d_entries, d_cell_off, n_cells, d_z, d_gp, n_variants, n_clusters, tables, d_counts, d_words,
                                 d_genotypes=None):
         """bdg_donor_cluster_words_dev: the entries' words and the clusters' genotypes from the counts of d_z, asynchronous"""
-        tables = np.ascontiguousarray(tables, dtype=np.int32)
-        if len(tables) != 10:
-            raise ValueError("ten table values")
+        tables = _tables10(tables)
         self._check(self.lib.bdg_donor_cluster_words_dev(self.h, _ptr(d_entries), _ptr(d_cell_off), int(n_cells), _ptr(d_z), _ptr(d_gp),
                                                          int(n_variants), int(n_clusters), tables.ctypes.data, _ptr(d_counts),
                                                          _ptr(d_words) if d_words is not None else None,
@@ -1248,6 +1233,23 @@ def consensus_out_offsets(seq_off, grp_off):
     lb = (seq_off[first + 1] - seq_off[first]) if len(seq_off) > 1 else np.zeros(len(first), np.int64)
     lb = np.where(grp_off[1:] > grp_off[:-1], np.maximum(lb, 0), 0)
     return np.concatenate([[0], np.cumsum(2 * lb)]).astype(np.uint64)
+
+
+def _tables10(tables, others_ok=True, text="ten table values"):
+    """the table values of the donor calls as the library reads them; a call that refuses more in one text gives that text"""
+    tables = np.ascontiguousarray(tables, dtype=np.int32)
+    if len(tables) != 10 or not others_ok:
+        raise ValueError(text)
+    return tables
+
+
+def _donor_inputs(entries, cell_off, tables, z0=None):
+    """what donor_scores and donor_cluster (with its z0) take alike, as the library reads it, and the number of cells"""
+    entries, cell_off = np.ascontiguousarray(entries, dtype=DONOR_ENTRY_DTYPE), np.ascontiguousarray(cell_off, dtype=np.uint64)
+    n = len(cell_off) - 1
+    ok = n >= 0 and not (n and int(cell_off.max()) > len(entries)) and (z0 is None or (z0.ndim == 2 and z0.shape[1] == n))
+    text = "cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values"
+    return entries, cell_off, _tables10(tables, ok, text if z0 is None else text + ", z0 is restarts x cells"), n
 
 
 def _ptr(x, byte_offset=0):

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <functional>
+#include <vector>
 
 // The launch of a persistent kernel that runs one wave per item (blocks of 64): as many waves as stay resident together, the
 // items dealt out to them once - more blocks than that would run as a second, thinner round.  per_cu is the kernel's own cached
@@ -72,6 +74,21 @@ int bdg_genes_kept_launch(bdg_ctx*, const uint8_t*, const uint64_t*, uint32_t, c
 // donors_kernels.hip: k_donor_scores over device arrays (the word of entry e is d_words[e.variant], D donors; d_scores null: no matrix)
 int bdg_donor_launch(bdg_ctx*, const bdg_donor_entry*, const uint64_t*, uint32_t, const uint64_t* d_words, uint32_t n_words, uint32_t D,
                      const int32_t* tables, bdg_donor_rec*, int64_t* d_scores);
+// donors_kernels.hip, what the entry points of the donor calls and of the clustering (demux_kernels.hip) share:
+// "<where>: the number of <what> must be 1 .. 32", the tables there (with_tables), device entries aligned to 16 bytes (host
+// entries: pass null)
+int bdg_donor_count_check(bdg_ctx*, const char* where, const char* what, uint32_t n, bool with_tables, const int32_t* tables, const void* d_entries);
+// the refusals that host entries and offsets can cause, in this order: offsets out of order, referenced entries without a pointer,
+// what `between` returns (the caller's own refusals that stand here, given the number of referenced entries), a variant not below
+// n_variants, a cell's counts at 2^40; ref_tot set: every variant's molecules added to ref_tot[v], alt_tot[v]
+int bdg_donor_entries_check(bdg_ctx*, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, uint32_t n_variants,
+                            uint64_t* ref_tot = nullptr, uint64_t* alt_tot = nullptr, const std::function<int(uint64_t)>& between = nullptr);
+// the staged call, as bdg_stage_reads is for reads: the entries the (checked) offsets reference to s_in0, the offsets rebased to
+// 0 to s_in1 (queued on the context's stream), extra_bytes of s_in1 reserved behind the offsets (d_extra) and out_bytes of s_out0
+// (d_out).  n_cells > 0; `rel` lives until the caller has synchronised.
+struct StagedDonors { std::vector<uint64_t> rel; bdg_donor_entry* d_entries; const uint64_t* d_off; void* d_extra; void* d_out; };
+int bdg_stage_donors(bdg_ctx*, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, size_t out_bytes, StagedDonors&,
+                     size_t extra_bytes = 0);
 // trim_kernels.hip
 int bdg_trim_launch(bdg_ctx*, const uint8_t*, const uint64_t*, const bdg_extract_rec*, uint32_t, uint32_t, bdg_trim_rec*);
 // trim5p_kernels.hip

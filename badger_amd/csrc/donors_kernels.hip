@@ -13,15 +13,18 @@
 //            The launcher takes the smallest NR of 1, 2, 4, 9 that holds H = D + D (D - 1) / 2 hypotheses.
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
+#include "donor_device.hpp"
 
 #include <algorithm>
 #include <climits>
+#include <string>
 
 namespace {
 
-static_assert(sizeof(bdg_donor_entry) == 16 && sizeof(bdg_donor_rec) == 40, "layouts the header states");
+static_assert(sizeof(bdg_donor_rec) == 40, "layout the header states");
 
 struct DonorTables { int32_t a[5], b[5]; };
+struct ScoreEntry { uint32_t wlo, whi, ref, alt; };      // what a lane keeps of its entry: the two halves of the genotype word, the counts
 
 constexpr uint32_t DONOR_NONE = 0xFFFFFFFFu;
 
@@ -33,22 +36,6 @@ __device__ __forceinline__ void donor_pair(uint32_t h, uint32_t D, uint32_t& a, 
     a = 0;
     while (row && rem >= row) { rem -= row; --row; ++a; }
     b = a + 1 + rem;
-}
-
-// the higher score, of equal scores the lower index, over the wave: every lane leaves with the winner
-__device__ __forceinline__ void wave_best(int64_t& s, uint32_t& i)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const int64_t os = (int64_t)__shfl_xor((long long)s, d);
-        const uint32_t oi = (uint32_t)__shfl_xor((int)i, d);
-        if (os > s || (os == s && oi < i)) s = os, i = oi;
-    }
-}
-
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t j)      // lane j's v, j wave-uniform
-{
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
 }
 
 // the two-bit field at bit position s (0 .. 62, even) of the word lo | hi << 32
@@ -79,16 +66,15 @@ void k_donor_scores(const bdg_donor_entry* __restrict__ entries, const uint64_t*
 #pragma unroll
         for (int r = 0; r < NR; ++r) acc[r] = 0;
         for (uint64_t at = 0; at < m; at += 64) {
-            uint32_t wlo = 0, whi = 0, ref = 0, alt = 0;
-            if (at + lane < m) {
-                const uint4 e = *reinterpret_cast<const uint4*>(entries + e0 + at + lane);
-                const uint64_t w = e.x < n_variants ? geno[e.x] : 0;     // (the host call refuses such an entry)
-                wlo = (uint32_t)w, whi = (uint32_t)(w >> 32), ref = e.y, alt = e.z;
-            }
+            // lane j: entry j of the chunk and the genotype word of its variant, 0 for a variant the words do not reach
+            const ScoreEntry e = chunk_entry<ScoreEntry>(entries, e0, at, m, lane, n_variants, [=](uint32_t v, uint32_t r, uint32_t a, bool known) {
+                const uint64_t w = known ? geno[v] : 0;
+                return ScoreEntry{ (uint32_t)w, (uint32_t)(w >> 32), r, a };
+            });
             const uint32_t in_chunk = m - at < 64 ? (uint32_t)(m - at) : 64u;
             for (uint32_t j = 0; j < in_chunk; ++j) {
-                const uint32_t lo = lane_u32(wlo, j), hi = lane_u32(whi, j);
-                const int64_t nr = (int64_t)lane_u32(ref, j), na = (int64_t)lane_u32(alt, j);
+                const uint32_t lo = lane_u32(e.wlo, j), hi = lane_u32(e.whi, j);
+                const int64_t nr = (int64_t)lane_u32(e.ref, j), na = (int64_t)lane_u32(e.alt, j);
                 const int64_t c0 = nr * t.a[0] + na * t.b[0], c1 = nr * t.a[1] + na * t.b[1], c2 = nr * t.a[2] + na * t.b[2],
                               c3 = nr * t.a[3] + na * t.b[3], c4 = nr * t.a[4] + na * t.b[4];
 #pragma unroll
@@ -146,15 +132,11 @@ int donor_rounds_index(uint32_t D)          // which of the four instantiations 
     return H <= 64 ? 0 : H <= 128 ? 1 : H <= 256 ? 2 : 3;
 }
 
-int donor_check(bdg_ctx* ctx, uint32_t n_donors, const int32_t* tables)
-{
-    if (n_donors < 1 || n_donors > BDG_DONORS_MAX) return bdg_fail(ctx, BDG_E_ARG, "donors: the number of donors must be 1 .. 32");
-    if (!tables) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    return BDG_OK;
-}
+}  // namespace
 
-int donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells, const uint64_t* d_geno,
-                 uint32_t n_variants, uint32_t D, const int32_t* tables, bdg_donor_rec* d_recs, int64_t* d_scores)
+// the launch, for the entry points below and for demux_kernels.hip (the final records of a fit)
+int bdg_donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells, const uint64_t* d_geno,
+                     uint32_t n_variants, uint32_t D, const int32_t* tables, bdg_donor_rec* d_recs, int64_t* d_scores)
 {
     DonorTables t;
     for (int l = 0; l < 5; ++l) t.a[l] = tables[l], t.b[l] = tables[5 + l];
@@ -172,13 +154,56 @@ int donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t*
     }
 }
 
-}  // namespace
-
-// the launch as demux_kernels.hip calls it, for the final records of a fit
-int bdg_donor_launch(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const uint64_t* d_cell_off, uint32_t n_cells, const uint64_t* d_words,
-                     uint32_t n_words, uint32_t D, const int32_t* tables, bdg_donor_rec* d_recs, int64_t* d_scores)
+// What the entry points of the two files share (bdg_launchers.hpp).
+int bdg_donor_count_check(bdg_ctx* ctx, const char* where, const char* what, uint32_t n, bool with_tables, const int32_t* tables,
+                          const void* d_entries)
 {
-    return donor_launch(ctx, d_entries, d_cell_off, n_cells, d_words, n_words, D, tables, d_recs, d_scores);
+    if (n < 1 || n > BDG_DONORS_MAX) return bdg_fail(ctx, BDG_E_ARG, std::string(where) + ": the number of " + what + " must be 1 .. 32");
+    if (with_tables && !tables) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (reinterpret_cast<uintptr_t>(d_entries) & 15u) return bdg_fail(ctx, BDG_E_ARG, std::string(where) + ": the entries must be aligned to 16 bytes");
+    return BDG_OK;
+}
+
+int bdg_donor_entries_check(bdg_ctx* ctx, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, uint32_t n_variants,
+                            uint64_t* ref_tot, uint64_t* alt_tot, const std::function<int(uint64_t)>& between)
+{
+    for (uint32_t c = 0; c < n_cells; ++c)
+        if (cell_off[c + 1] < cell_off[c]) return bdg_fail(ctx, BDG_E_ARG, "donors: cell offsets must be non-decreasing");
+    const uint64_t n_entries = n_cells ? cell_off[n_cells] - cell_off[0] : 0;
+    if (n_entries && !entries) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = between ? between(n_entries) : BDG_OK) return rc;
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        uint64_t sum = 0;
+        for (uint64_t j = cell_off[c]; j < cell_off[c + 1]; ++j) {
+            const bdg_donor_entry& e = entries[j];
+            if (e.variant >= n_variants) return bdg_fail(ctx, BDG_E_ARG, "donors: an entry's variant is not below n_variants");
+            sum += (uint64_t)e.ref + (uint64_t)e.alt;
+            if (sum >= BDG_DONORS_MAX_DEPTH) return bdg_fail(ctx, BDG_E_ARG, "donors: the counts of a cell sum to 2^40 or more");
+            if (ref_tot) ref_tot[e.variant] += e.ref, alt_tot[e.variant] += e.alt;
+        }
+    }
+    return BDG_OK;
+}
+
+int bdg_stage_donors(bdg_ctx* ctx, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, size_t out_bytes, StagedDonors& s,
+                     size_t extra_bytes)
+{
+    const uint64_t first = cell_off[0], n_entries = cell_off[n_cells] - first;
+    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t ent_b = sizeof(bdg_donor_entry) * (size_t)n_entries, off_b = sizeof(uint64_t) * ((size_t)n_cells + 1);
+    int rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in0, ent_b + 16))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + extra_bytes + 16))) return rc;
+    if ((rc = bdg_reserve(ctx, ctx->s_out0, out_bytes + 16))) return rc;
+    s.rel.resize((size_t)n_cells + 1);
+    for (uint32_t c = 0; c <= n_cells; ++c) s.rel[c] = cell_off[c] - first;
+    if (ent_b) BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in0.p, entries + first, ent_b, hipMemcpyHostToDevice, ctx->stream));
+    BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->s_in1.p, s.rel.data(), off_b, hipMemcpyHostToDevice, ctx->stream));
+    s.d_entries = static_cast<bdg_donor_entry*>(ctx->s_in0.p);
+    s.d_off = static_cast<const uint64_t*>(ctx->s_in1.p);
+    s.d_extra = static_cast<char*>(ctx->s_in1.p) + off_b;
+    s.d_out = ctx->s_out0.p;
+    return BDG_OK;
 }
 
 extern "C" {
@@ -188,58 +213,39 @@ int bdg_donor_scores_dev(bdg_ctx* ctx, const bdg_donor_entry* d_entries, const u
                          bdg_donor_rec* d_recs, int64_t* d_scores)
 {
     if (!ctx) return BDG_E_ARG;
-    if (int rc = donor_check(ctx, n_donors, tables)) return rc;
+    // (without cells nothing is read: the entries may then be anything)
+    if (int rc = bdg_donor_count_check(ctx, "donors", "donors", n_donors, true, tables, n_cells ? d_entries : nullptr)) return rc;
     if (n_cells == 0) return BDG_OK;
     if (!d_cell_off || !d_recs) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (reinterpret_cast<uintptr_t>(d_entries) & 15u) return bdg_fail(ctx, BDG_E_ARG, "donors: the entries must be aligned to 16 bytes");
     BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return donor_launch(ctx, d_entries, d_cell_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, d_scores);
+    return bdg_donor_launch(ctx, d_entries, d_cell_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, d_scores);
 }
 
 int bdg_donor_scores(bdg_ctx* ctx, const bdg_donor_entry* entries, const uint64_t* cell_off, uint32_t n_cells, const uint64_t* geno,
                      uint32_t n_variants, uint32_t n_donors, const int32_t* tables, bdg_donor_rec* recs, int64_t* scores)
 {
     if (!ctx) return BDG_E_ARG;
-    if (int rc = donor_check(ctx, n_donors, tables)) return rc;
+    if (int rc = bdg_donor_count_check(ctx, "donors", "donors", n_donors, true, tables, nullptr)) return rc;
     if (n_variants && !geno) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     for (uint32_t v = 0; v < n_variants; ++v)
         for (uint32_t d = 0; d < n_donors; ++d)
             if (((geno[v] >> (2 * d)) & 3u) == 3u) return bdg_fail(ctx, BDG_E_ARG, "donors: a genotype field holds 3");
     if (n_cells == 0) return BDG_OK;
     if (!cell_off || !recs) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t c = 0; c < n_cells; ++c)
-        if (cell_off[c + 1] < cell_off[c]) return bdg_fail(ctx, BDG_E_ARG, "donors: cell offsets must be non-decreasing");
-    const uint64_t n_entries = cell_off[n_cells];
-    if (n_entries && !entries) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t c = 0; c < n_cells; ++c) {
-        uint64_t sum = 0;
-        for (uint64_t j = cell_off[c]; j < cell_off[c + 1]; ++j) {
-            if (entries[j].variant >= n_variants) return bdg_fail(ctx, BDG_E_ARG, "donors: an entry's variant is not below n_variants");
-            sum += (uint64_t)entries[j].ref + (uint64_t)entries[j].alt;
-            if (sum >= BDG_DONORS_MAX_DEPTH) return bdg_fail(ctx, BDG_E_ARG, "donors: the counts of a cell sum to 2^40 or more");
-        }
-    }
-    BDG_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // staging: the entries | the offsets, then the genotype words | the records, then the score matrix
-    const uint64_t H = (uint64_t)n_donors + (uint64_t)n_donors * (n_donors - 1) / 2;
-    const size_t ent_b = sizeof(bdg_donor_entry) * (size_t)n_entries, off_b = sizeof(uint64_t) * ((size_t)n_cells + 1),
-                 gen_b = sizeof(uint64_t) * (size_t)n_variants, rec_b = sizeof(bdg_donor_rec) * (size_t)n_cells,
-                 sc_b = scores ? sizeof(int64_t) * (size_t)n_cells * (size_t)H : 0;
     int rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in0, ent_b + 16))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_in1, off_b + gen_b + 16))) return rc;
-    if ((rc = bdg_reserve(ctx, ctx->s_out0, rec_b + sc_b + 16))) return rc;
-    auto* d_entries = static_cast<bdg_donor_entry*>(ctx->s_in0.p);
-    auto* d_cell_off = static_cast<uint64_t*>(ctx->s_in1.p);
-    auto* d_geno = d_cell_off + n_cells + 1;
-    auto* d_recs = static_cast<bdg_donor_rec*>(ctx->s_out0.p);
-    auto* d_scores = reinterpret_cast<int64_t*>(d_recs + n_cells);
-    if (ent_b) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_entries, entries, ent_b, hipMemcpyHostToDevice, st));
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(d_cell_off, cell_off, off_b, hipMemcpyHostToDevice, st));
+    if ((rc = bdg_donor_entries_check(ctx, entries, cell_off, n_cells, n_variants))) return rc;
+    // the genotype words behind the offsets; one output buffer: the records, then the score matrix
+    const uint64_t H = (uint64_t)n_donors + (uint64_t)n_donors * (n_donors - 1) / 2;
+    const size_t gen_b = sizeof(uint64_t) * (size_t)n_variants, rec_b = sizeof(bdg_donor_rec) * (size_t)n_cells,
+                 sc_b = scores ? sizeof(int64_t) * (size_t)n_cells * (size_t)H : 0;
+    StagedDonors S;
+    if ((rc = bdg_stage_donors(ctx, entries, cell_off, n_cells, rec_b + sc_b, S, gen_b))) return rc;
+    hipStream_t st = ctx->stream;
+    auto* d_geno = static_cast<uint64_t*>(S.d_extra);
+    auto* d_recs = static_cast<bdg_donor_rec*>(S.d_out);
+    auto* d_scores = scores ? reinterpret_cast<int64_t*>(d_recs + n_cells) : nullptr;
     if (gen_b) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_geno, geno, gen_b, hipMemcpyHostToDevice, st));
-    if ((rc = donor_launch(ctx, d_entries, d_cell_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, scores ? d_scores : nullptr)))
-        return rc;
+    if ((rc = bdg_donor_launch(ctx, S.d_entries, S.d_off, n_cells, d_geno, n_variants, n_donors, tables, d_recs, d_scores))) return rc;
     BDG_HIP_TRY(ctx, hipMemcpyAsync(recs, d_recs, rec_b, hipMemcpyDeviceToHost, st));
     if (sc_b) BDG_HIP_TRY(ctx, hipMemcpyAsync(scores, d_scores, sc_b, hipMemcpyDeviceToHost, st));
     BDG_HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -112,23 +112,33 @@ def hypotheses(n_donors):
     return [(h, h) for h in range(n_donors)] + [(a, b) for a in range(n_donors) for b in range(a + 1, n_donors)]
 
 
-def check_inputs(entries, cell_off, geno, n_donors):
-    """the argument errors of bdg_donor_scores, as ValueError"""
-    _check_d(n_donors)
+def _used(entries, cell_off):
+    """the entries the offsets reference and the offsets from 0 (int64)"""
     off = np.asarray(cell_off, dtype=np.uint64).astype(np.int64)
     if len(off) < 1 or (np.diff(off) < 0).any():
         raise ValueError("cell offsets must be non-decreasing")
+    return np.asarray(entries, dtype=ENTRY_DTYPE)[int(off[0]):int(off[-1])], off - off[0]
+
+
+def _check_entries(used, off, n_variants):
+    """what the entries themselves can violate, over _used's pair, which it returns"""
+    if len(used) and int(used["variant"].max()) >= n_variants:
+        raise ValueError("an entry's variant is not below n_variants")
+    depth = np.concatenate([[0], np.cumsum(used["ref"].astype(np.int64) + used["alt"].astype(np.int64))])
+    if len(off) > 1 and int((depth[off[1:]] - depth[off[:-1]]).max()) >= DEPTH_MAX:
+        raise ValueError("the counts of a cell sum to 2^40 or more")
+    return used, off
+
+
+def check_inputs(entries, cell_off, geno, n_donors):
+    """the argument errors of bdg_donor_scores, as ValueError"""
+    _check_d(n_donors)
+    used, off = _used(entries, cell_off)
     geno = np.asarray(geno, dtype=np.uint64)
     for d in range(n_donors):
         if (((geno >> np.uint64(2 * d)) & np.uint64(3)) == 3).any():
             raise ValueError("a genotype field holds 3")
-    used = entries[int(off[0]):int(off[-1])] if len(off) > 1 else entries[:0]
-    if len(used) and int(used["variant"].max()) >= len(geno):
-        raise ValueError("an entry's variant is not below n_variants")
-    depth = used["ref"].astype(np.int64) + used["alt"].astype(np.int64)
-    for c in range(len(off) - 1):
-        if int(depth[int(off[c] - off[0]):int(off[c + 1] - off[0])].sum()) >= DEPTH_MAX:
-            raise ValueError("the counts of a cell sum to 2^40 or more")
+    _check_entries(used, off, len(geno))
 
 
 def scores(entries, cell_off, geno, n_donors, tables):
@@ -214,14 +224,6 @@ def _check_k(n_clusters):
         raise ValueError("the number of clusters must be 1 .. 32")
 
 
-def _used(entries, cell_off):
-    """the entries the offsets reference and the offsets from 0 (int64)"""
-    off = np.asarray(cell_off, dtype=np.uint64).astype(np.int64)
-    if len(off) < 1 or (np.diff(off) < 0).any():
-        raise ValueError("cell offsets must be non-decreasing")
-    return np.asarray(entries, dtype=ENTRY_DTYPE)[int(off[0]):int(off[-1])], off - off[0]
-
-
 def _geno_tables(tables):
     t = np.asarray(tables, dtype=np.int64)
     return t[0:LEVELS:2], t[LEVELS::2]
@@ -236,13 +238,7 @@ def _best_genotype(r, a, tables):
 def check_cluster_inputs(entries, cell_off, n_variants, n_clusters):
     """the argument errors of bdg_donor_cluster that the entries can cause, as ValueError -> (used entries, offsets from 0)"""
     _check_k(n_clusters)
-    used, off = _used(entries, cell_off)
-    if len(used) and int(used["variant"].max()) >= n_variants:
-        raise ValueError("an entry's variant is not below n_variants")
-    depth = np.concatenate([[0], np.cumsum(used["ref"].astype(np.int64) + used["alt"].astype(np.int64))])
-    if len(off) > 1 and int((depth[off[1:]] - depth[off[:-1]]).max()) >= DEPTH_MAX:
-        raise ValueError("the counts of a cell sum to 2^40 or more")
-    return used, off
+    return _check_entries(*_used(entries, cell_off), n_variants)
 
 
 def pooled_genotypes(entries, n_variants, tables):
@@ -291,21 +287,21 @@ def cluster_step(entries, cell_off, z, gp, n_clusters, tables):
 
 
 def splitmix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return x ^ (x >> 31)
+    """the rule's generator of a uint64 array, elementwise, or of a Python int: in uint64, which wraps as the formula does"""
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        y = np.asarray(x, dtype=u) + u(0x9E3779B97F4A7C15)
+        y = (y ^ (y >> u(30))) * u(0xBF58476D1CE4E5B9)
+        y = (y ^ (y >> u(27))) * u(0x94D049BB133111EB)
+        y = y ^ (y >> u(31))
+    return y if isinstance(x, np.ndarray) else int(y)
 
 
 def start_assignments(n_cells, n_clusters, restarts, seed):
-    """z0 uint32 [restarts, cells]: the rule's formula, vectorised in uint64 (which wraps as the formula does)"""
+    """z0 uint32 [restarts, cells] by the rule's formula"""
     _check_k(n_clusters)
     u = np.uint64
-    with np.errstate(over="ignore"):
-        x = (u(seed << 40) ^ (np.arange(restarts, dtype=u)[:, None] << u(32)) ^ np.arange(n_cells, dtype=u)[None, :]) + u(0x9E3779B97F4A7C15)
-        x = (x ^ (x >> u(30))) * u(0xBF58476D1CE4E5B9)
-        x = (x ^ (x >> u(27))) * u(0x94D049BB133111EB)
-        x = x ^ (x >> u(31))
+    x = splitmix64(u(seed << 40) ^ (np.arange(restarts, dtype=u)[:, None] << u(32)) ^ np.arange(n_cells, dtype=u)[None, :])
     return (x % u(n_clusters)).astype(np.uint32)
 
 
@@ -370,14 +366,16 @@ def checker_cluster(entries, cell_off, n_variants, n_clusters, tables, z0, max_i
 
 def device_cluster(ctx):
     """the same on the device: bdg_donor_cluster"""
-    return lambda entries, cell_off, n_variants, n_clusters, tables, z0, max_iter: \
-        ctx.donor_cluster(entries, cell_off, n_variants, n_clusters, tables, z0, max_iter)
+    return ctx.donor_cluster
+
+
+def cluster_names(n_clusters):
+    return ["cluster%d" % k for k in range(n_clusters)]
 
 
 def cluster_genotypes_text(variant_ids, genotypes):
-    names = ["cluster%d" % k for k in range(len(genotypes))]
     token = "012."
-    rows = ["variant\t%s\n" % "\t".join(names)]
+    rows = ["variant\t%s\n" % "\t".join(cluster_names(len(genotypes)))]
     rows += ["%s\t%s\n" % (v, "\t".join(token[g] for g in col)) for v, col in zip(variant_ids, np.asarray(genotypes).T.tolist())]
     return "".join(rows).encode()
 
@@ -407,23 +405,16 @@ class ClusterDemux:
 
     def __call__(self, cells, ref, alt):
         n_clusters, restarts, max_iter, seed = self.fit
-        error, doublet_rate, min_variants, min_llr = self.options
         n_variants = len(self.variant_ids)
-        names = ["cluster%d" % k for k in range(n_clusters)]
         entries, cell_off = entries_of(ref, alt, len(cells), np.arange(n_variants))
-        out = self.run(entries, cell_off, n_variants, n_clusters, level_tables(error), start_assignments(len(cells), n_clusters, restarts, seed),
-                       max_iter)
-        recs = np.asarray(out["recs"]).view(REC_DTYPE).reshape(-1)
-        status, kind, margin = call(recs, np.diff(cell_off.astype(np.int64)), n_clusters, doublet_rate, min_variants, min_llr)
+        out = self.run(entries, cell_off, n_variants, n_clusters, level_tables(self.options[0]),
+                       start_assignments(len(cells), n_clusters, restarts, seed), max_iter)
+        files, counts = called(cells, cluster_names(n_clusters), entries, cell_off, out["recs"], self.options)
         table, chosen = np.asarray(out["restarts"]), int(out["chosen"])
-        files = {"donors.tsv": donors_text(cells, names, entries, cell_off, recs, status, margin),
-                 "donor_summary.tsv": summary_text(names, recs, status),
-                 "cluster_genotypes.tsv": cluster_genotypes_text(self.variant_ids, out["genotypes"]),
-                 "donor_clusters.tsv": clusters_text(table, chosen)}
-        counts = dict(donors=n_clusters, donor_cells=len(cells), donor_singlets=int((status == SINGLET).sum()),
-                      donor_doublets=int((status == DOUBLET).sum()), donor_unassigned=int((status == UNASSIGNED).sum()),
-                      donor_entries=len(entries), donor_variants=int(len(np.unique(entries["variant"]))), donor_restarts=len(table),
-                      donor_chosen=chosen, donor_iterations=int(table["iterations"][chosen]), donor_converged=int(table["converged"][chosen]))
+        files.update({"cluster_genotypes.tsv": cluster_genotypes_text(self.variant_ids, out["genotypes"]),
+                      "donor_clusters.tsv": clusters_text(table, chosen)})
+        counts.update(donor_variants=int(len(np.unique(entries["variant"]))), donor_restarts=len(table), donor_chosen=chosen,
+                      donor_iterations=int(table["iterations"][chosen]), donor_converged=int(table["converged"][chosen]))
         return files, counts
 
 
@@ -545,6 +536,19 @@ def summary_text(donors, recs, status):
 
 
 # ---------------------------------------------------------------- the step ----
+def called(cells, donors, entries, cell_off, recs, options):
+    """what Demux and ClusterDemux make of the records of their run: the calls -> (the two files of FILES, the counts both have)"""
+    _, doublet_rate, min_variants, min_llr = options
+    recs = np.asarray(recs).view(REC_DTYPE).reshape(-1)
+    status, kind, margin = call(recs, np.diff(cell_off.astype(np.int64)), len(donors), doublet_rate, min_variants, min_llr)
+    files = {"donors.tsv": donors_text(cells, donors, entries, cell_off, recs, status, margin),
+             "donor_summary.tsv": summary_text(donors, recs, status)}
+    counts = dict(donors=len(donors), donor_cells=len(cells), donor_singlets=int((status == SINGLET).sum()),
+                  donor_doublets=int((status == DOUBLET).sum()), donor_unassigned=int((status == UNASSIGNED).sum()),
+                  donor_entries=len(entries))
+    return files, counts
+
+
 def checker_records(entries, cell_off, geno, n_donors, tables):
     """the records by the checker: what the device's are held against"""
     return records(scores(entries, cell_off, geno, n_donors, tables), n_donors)
@@ -552,7 +556,7 @@ def checker_records(entries, cell_off, geno, n_donors, tables):
 
 def device_records(ctx):
     """the records on the device: bdg_donor_scores"""
-    return lambda entries, cell_off, geno, n_donors, tables: ctx.donor_scores(entries, cell_off, geno, n_donors, tables)
+    return ctx.donor_scores
 
 
 class Demux:
@@ -565,16 +569,10 @@ class Demux:
     def __call__(self, cells, ref, alt):
         """cells: the barcodes in the order of barcodes.tsv; ref, alt: {(variant, cell): molecules} -> ({file name: bytes}, counts)"""
         g = self.genotypes
-        error, doublet_rate, min_variants, min_llr = self.options
         entries, cell_off = entries_of(ref, alt, len(cells), g.index)
-        recs = np.asarray(self.run(entries, cell_off, g.words, len(g), level_tables(error))).view(REC_DTYPE).reshape(-1)
-        status, kind, margin = call(recs, np.diff(cell_off.astype(np.int64)), len(g), doublet_rate, min_variants, min_llr)
-        files = {"donors.tsv": donors_text(cells, g.donors, entries, cell_off, recs, status, margin),
-                 "donor_summary.tsv": summary_text(g.donors, recs, status)}
-        counts = dict(donors=len(g), donor_cells=len(cells), donor_singlets=int((status == SINGLET).sum()),
-                      donor_doublets=int((status == DOUBLET).sum()), donor_unassigned=int((status == UNASSIGNED).sum()),
-                      donor_entries=len(entries), donor_variants=len(g.usable), donor_skipped=g.skipped, donor_dropped=g.dropped,
-                      donor_absent=g.absent)
+        recs = self.run(entries, cell_off, g.words, len(g), level_tables(self.options[0]))
+        files, counts = called(cells, g.donors, entries, cell_off, recs, self.options)
+        counts.update(donor_variants=len(g.usable), donor_skipped=g.skipped, donor_dropped=g.dropped, donor_absent=g.absent)
         return files, counts
 
 
@@ -589,65 +587,42 @@ def device_demux(ctx, path, variant_ids, options):
 def log_counts(counts, out_dir):
     if "donor_cells" not in counts:
         return
+    head = "Donors: %d cells, %d singlets, %d doublets, %d unassigned; " \
+           % (counts["donor_cells"], counts["donor_singlets"], counts["donor_doublets"], counts["donor_unassigned"])
     if "donor_restarts" in counts:
-        logger.info("Donors: %d cells, %d singlets, %d doublets, %d unassigned; %d clusters from %d entries at %d covered variants, "
-                    "restart %d of %d chosen (%d iterations, %s); %s in %s"
-                    % (counts["donor_cells"], counts["donor_singlets"], counts["donor_doublets"], counts["donor_unassigned"],
-                       counts["donors"], counts["donor_entries"], counts["donor_variants"], counts["donor_chosen"], counts["donor_restarts"],
+        logger.info(head + "%d clusters from %d entries at %d covered variants, restart %d of %d chosen (%d iterations, %s); %s in %s"
+                    % (counts["donors"], counts["donor_entries"], counts["donor_variants"], counts["donor_chosen"], counts["donor_restarts"],
                        counts["donor_iterations"], "stopped by itself" if counts["donor_converged"] else "ended by --donor_max_iter",
                        ", ".join(FILES + CLUSTER_FILES), out_dir))
-        return
-    logger.info("Donors: %d cells, %d singlets, %d doublets, %d unassigned; %d donors, %d entries at %d usable variants (%d rows "
-                "skipped for an unknown id, %d dropped for a missing genotype, %d variants without a row); %s in %s"
-                % (counts["donor_cells"], counts["donor_singlets"], counts["donor_doublets"], counts["donor_unassigned"],
-                   counts["donors"], counts["donor_entries"], counts["donor_variants"], counts["donor_skipped"], counts["donor_dropped"],
-                   counts["donor_absent"], ", ".join(FILES), out_dir))
+    else:
+        logger.info(head + "%d donors, %d entries at %d usable variants (%d rows skipped for an unknown id, %d dropped for a missing "
+                    "genotype, %d variants without a row); %s in %s"
+                    % (counts["donors"], counts["donor_entries"], counts["donor_variants"], counts["donor_skipped"], counts["donor_dropped"],
+                       counts["donor_absent"], ", ".join(FILES), out_dir))
 
 
 # ---------------------------------------------------------------- options ----
-def _number_arg(flag, lo, hi, text, open_ends=False):
+def _range_arg(flag, cast, lo, hi, text, open_ends=False):
+    """the argparse type of a value that cast (float or int) reads, lo .. hi, or between the two with open ends"""
     def parse(v):
         try:
-            x = float(v)
+            x = cast(v)
         except ValueError:
-            x = float("nan")
-        if not (lo < x < hi if open_ends else lo <= x <= hi):
-            raise argparse.ArgumentTypeError("%s takes a number, %s" % (flag, text))
+            x = None
+        if x is None or not (lo < x < hi if open_ends else lo <= x <= hi):                    # (nan compares false)
+            raise argparse.ArgumentTypeError("%s takes %s, %s" % (flag, "a number" if cast is float else "an integer", text))
         return x
     return parse
 
 
-donor_error_arg = _number_arg("--donor_error", ERROR_MIN, ERROR_MAX, "1e-4 .. 0.25")
-doublet_rate_arg = _number_arg("--doublet_rate", 0.0, 1.0, "above 0 and below 1", True)
-donor_min_llr_arg = _number_arg("--donor_min_llr", 0.0, MIN_LLR_MAX, "0 .. 1e6")
-
-
-def donor_min_variants_arg(v):
-    try:
-        x = int(v)
-    except ValueError:
-        x = -1
-    if not 0 <= x <= MIN_VARIANTS_MAX:
-        raise argparse.ArgumentTypeError("--donor_min_variants takes an integer, 0 .. %d" % MIN_VARIANTS_MAX)
-    return x
-
-
-def _integer_arg(flag, lo, hi, text):
-    def parse(v):
-        try:
-            x = int(v)
-        except ValueError:
-            x = lo - 1
-        if not lo <= x <= hi:
-            raise argparse.ArgumentTypeError("%s takes an integer, %s" % (flag, text))
-        return x
-    return parse
-
-
-donors_arg = _integer_arg("--donors", 1, D_MAX, "1 .. %d" % D_MAX)
-donor_restarts_arg = _integer_arg("--donor_restarts", 1, RESTARTS_MAX, "1 .. %d" % RESTARTS_MAX)
-donor_max_iter_arg = _integer_arg("--donor_max_iter", 1, MAX_ITER_MAX, "1 .. %d" % MAX_ITER_MAX)
-donor_seed_arg = _integer_arg("--donor_seed", 0, SEED_MAX, "0 .. %d" % SEED_MAX)
+donor_error_arg = _range_arg("--donor_error", float, ERROR_MIN, ERROR_MAX, "1e-4 .. 0.25")
+doublet_rate_arg = _range_arg("--doublet_rate", float, 0.0, 1.0, "above 0 and below 1", True)
+donor_min_llr_arg = _range_arg("--donor_min_llr", float, 0.0, MIN_LLR_MAX, "0 .. 1e6")
+donor_min_variants_arg = _range_arg("--donor_min_variants", int, 0, MIN_VARIANTS_MAX, "0 .. %d" % MIN_VARIANTS_MAX)
+donors_arg = _range_arg("--donors", int, 1, D_MAX, "1 .. %d" % D_MAX)
+donor_restarts_arg = _range_arg("--donor_restarts", int, 1, RESTARTS_MAX, "1 .. %d" % RESTARTS_MAX)
+donor_max_iter_arg = _range_arg("--donor_max_iter", int, 1, MAX_ITER_MAX, "1 .. %d" % MAX_ITER_MAX)
+donor_seed_arg = _range_arg("--donor_seed", int, 0, SEED_MAX, "0 .. %d" % SEED_MAX)
 
 
 def add_donor_options(p):

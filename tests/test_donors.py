@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import demux_cases as mc
 import donor_cases as dc
 from badger_amd import alleles as al
 from badger_amd import badger
@@ -104,6 +105,38 @@ def test_argument_errors():
         dn.scores(at_bound, off_b, dc.pack(genotypes), 2, t)
     at_bound["alt"][0] -= 1
     assert dn.scores(at_bound, off_b, dc.pack(genotypes), 2, t).shape == (1, 3)
+
+
+def test_both_input_checks_refuse_alike():
+    """what check_inputs and check_cluster_inputs share: the same text for the same violation, and the bound of a cell held by the
+    cell that reaches it alone, behind unused leading entries and beside cells just below it"""
+    geno = dc.pack([[0, 1], [2, 0]])
+    entries, off = dc.flatten([[(0, 1, 0)], [(1, 0, 1)]])
+    half = 1 << 31
+    below = [(v % 2, half, half - (v == 7)) for v in range(256)]
+    deep, off_d = dc.flatten([[(9, half, half)], below, [], [(v % 2, half, half) for v in range(256)], below])
+    texts = []
+    for e, o, n_variants in ((entries, off[::-1].copy(), 2), (entries, np.zeros(0, np.uint64), 2), (entries, off, 1), (deep, off_d[1:], 2)):
+        with pytest.raises(ValueError) as a:
+            dn.check_inputs(e, o, geno[:n_variants], 2)
+        with pytest.raises(ValueError) as b:
+            dn.check_cluster_inputs(e, o, n_variants, 2)
+        assert str(a.value) == str(b.value)
+        texts.append(str(a.value))
+    assert texts == ["cell offsets must be non-decreasing"] * 2 + ["an entry's variant is not below n_variants",
+                                                                   "the counts of a cell sum to 2^40 or more"]
+    deep["alt"][1 + 2 * 256 - 1] -= 1                                       # every cell one molecule below the bound
+    dn.check_inputs(deep, off_d[1:], geno, 2)
+    used, from_0 = dn.check_cluster_inputs(deep, off_d[1:], 2, 2)
+    assert len(used) == len(deep) - 1 and from_0.tolist() == (off_d[1:] - off_d[1]).tolist()
+
+
+def test_the_generator_over_an_array_is_the_scalar_one():
+    states = [0, 1, (1 << 64) - 1, (1 << 63) - 1, 1 << 63, 0x9E3779B97F4A7C15, (1 << 64) - 0x9E3779B97F4A7C15, (5 << 40) ^ (3 << 32) ^ 77]
+    got = dn.splitmix64(np.array(states, dtype=np.uint64))
+    assert got.dtype == np.uint64 and got.tolist() == [mc.plain_splitmix64(x) for x in states] == [dn.splitmix64(x) for x in states]
+    assert all(type(dn.splitmix64(x)) is int for x in states)
+    assert dn.splitmix64(np.array([[7], [8]], dtype=np.uint64)).shape == (2, 1)
 
 
 # ---------------------------------------------------------------- ties, one donor, thresholds ----
