@@ -59,6 +59,9 @@ GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
 # bdg_allele_rec: a read's windows that carry either allele of a known SNV (bdg_alleles_assign; the rule in badger_amd/alleles.py)
 ALLELE_DTYPE = np.dtype([("read", "<u4"), ("variant", "<u4"), ("ref_hits", "<u4"), ("alt_hits", "<u4")])
 ALLELES_K_DEFAULT, ALLELES_MAX_VARIANTS = 15, 256
+# bdg_site_rec: a selected site of the pileup (bdg_sites_select; the rule in badger_amd/discover.py); ref, alt: codes A 0 .. T 3
+SITE_DTYPE = np.dtype([("site", "<u4"), ("ref", "<u4"), ("alt", "<u4"), ("pad", "<u4"), ("count", "<u4", (4,))])
+SITES_K_DEFAULT, SITES_MAX = 11, 0xFFFFFFFF
 # bdg_iso_rec: the transcripts of its gene a read is compatible with (bdg_iso_assign; the rule in badger_amd/genes.py)
 ISO_DTYPE = np.dtype([("compat", "<u8"), ("feature", "<u4"), ("best", "<u4"), ("second", "<u4"), ("n_gene", "<u4"), ("flags", "<u4"),
                       ("pad", "<u4")])
@@ -122,6 +125,8 @@ EXPORTS = [
     "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
     "bdg_alleles_index_build", "bdg_alleles_index_stats", "bdg_alleles_assign_dev", "bdg_alleles_assign",
     "bdg_alleles_index_values",
+    "bdg_sites_index_build", "bdg_sites_index_stats", "bdg_sites_pileup_dev", "bdg_sites_pileup", "bdg_sites_reset", "bdg_sites_select",
+    "bdg_sites_counts_to_host",
     "bdg_donor_scores", "bdg_donor_scores_dev",
     "bdg_donor_cluster_counts_dev", "bdg_donor_cluster_assign_dev", "bdg_donor_cluster_words_dev", "bdg_donor_cluster",
 ]
@@ -419,6 +424,13 @@ def load():
     L.bdg_alleles_index_values.argtypes = [vp, C.POINTER(u32)]
     L.bdg_alleles_assign_dev.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
     L.bdg_alleles_assign.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
+    L.bdg_sites_index_build.argtypes = [vp, vp, vp, u32, vp, u32]
+    L.bdg_sites_index_stats.argtypes = [vp, vp]
+    L.bdg_sites_pileup_dev.argtypes = [vp, vp, vp, u32, vp]
+    L.bdg_sites_pileup.argtypes = [vp, vp, vp, u32, vp]
+    L.bdg_sites_reset.argtypes = [vp]
+    L.bdg_sites_select.argtypes = [vp, u32, u32, vp, u64, vp]
+    L.bdg_sites_counts_to_host.argtypes = [vp, vp, u64]
     L.bdg_donor_scores.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     L.bdg_donor_scores_dev.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp, vp, vp]
     L.bdg_donor_cluster_counts_dev.argtypes = [vp, vp, vp, u32, vp, u32, u32, vp]
@@ -939,6 +951,71 @@ class Context:
             self._check(rc)
             out = out[:int(counts[0])]
             return out[np.lexsort((out["variant"], out["read"]))], int(counts[1])
+
+    def sites_index_build(self, bases, seq_off, features, k=SITES_K_DEFAULT):
+        """the site table of the transcripts (bases uint8, seq_off uint64 [n + 1], features uint32 [n]) on the device, beside the
+        genes and the allele table and in place of an earlier site table; the counts start at zero (bdg_sites_index_build)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        features = np.ascontiguousarray(features, dtype=np.uint32)
+        if len(seq_off) != len(features) + 1:
+            raise ValueError("seq_off holds one entry more than features")
+        self._check(self.lib.bdg_sites_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data,
+                                                   int(k)))
+        self._sites = int(seq_off[-1])
+
+    def sites_index_stats(self):
+        """-> uint64 [6] as genes_index_stats, of the site table (bdg_sites_index_stats)"""
+        out = np.zeros(6, dtype=np.uint64)
+        self._check(self.lib.bdg_sites_index_stats(self.h, out.ctypes.data))
+        return out
+
+    def sites_pileup_dev(self, d_bases, d_off, n, d_gene_recs):
+        """bdg_sites_pileup_dev: the evidence of the reads over device arrays added to the context's counts, asynchronous"""
+        self._check(self.lib.bdg_sites_pileup_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs)))
+
+    def sites_pileup(self, bases, off, gene_recs):
+        """the evidence of the reads over host arrays added to the context's counts, gene_recs GENE_DTYPE [n] what genes_assign gave
+        for them (bdg_sites_pileup)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        gene_recs = np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
+        n = max(len(off) - 1, 0)
+        if len(gene_recs) != n:
+            raise ValueError("a gene record per read")
+        self._check(self.lib.bdg_sites_pileup(self.h, bases.ctypes.data, off.ctypes.data, n, gene_recs.ctypes.data))
+
+    def sites_reset(self):
+        """every count back to zero (bdg_sites_reset)"""
+        self._check(self.lib.bdg_sites_reset(self.h))
+
+    def sites_select(self, min_alt, ppm, cap=None, retry=True):
+        """the selected sites of the counts as they stand (bdg_sites_select) -> SITE_DTYPE sorted by site.  cap: room for that many
+        records (default 1024); with more the call is made once more with the count the library returned - retry False raises
+        the library's E_CAPACITY instead, its `n_records` the count."""
+        cap = 1024 if cap is None else int(cap)
+        count = C.c_uint64()
+        for attempt in range(2):
+            out = np.zeros(cap, dtype=SITE_DTYPE)
+            rc = self.lib.bdg_sites_select(self.h, int(min_alt), int(ppm), out.ctypes.data if cap else None, cap, C.byref(count))
+            if rc == E_CAPACITY and retry and attempt == 0:
+                cap = int(count.value)
+                continue
+            if rc == E_CAPACITY:
+                err = BadgerHipError(rc, "bdg_sites_select: %d records, room for %d" % (int(count.value), cap))
+                err.n_records = int(count.value)
+                raise err
+            self._check(rc)
+            out = out[:int(count.value)]
+            return out[np.argsort(out["site"], kind="stable")]
+
+    def sites_counts(self, n_sites=None):
+        """-> uint32 [n_sites, 4], the counts as they stand; n_sites: seq_off[-1] of the build (default: of this object's last
+        build) (bdg_sites_counts_to_host)"""
+        n = int(getattr(self, "_sites", 0) if n_sites is None else n_sites)
+        out = np.zeros((n, 4), dtype=np.uint32)
+        self._check(self.lib.bdg_sites_counts_to_host(self.h, out.ctypes.data if n else None, n))
+        return out
 
     def em_tcc(self, classes, prob_off, out_off, eps=EM_EPS_DEFAULT, max_iter=EM_MAX_ITER_DEFAULT, start=None):
         """EM over the compatibility counts of every problem, host arrays (bdg_em_tcc): classes EM_CLASS_DTYPE, problem p the

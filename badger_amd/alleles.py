@@ -386,8 +386,9 @@ def add_allele_options(p):
 
 def check_allele_options(p, a, with_matrix, from_reads=False):
     """the errors of --variants, --allele_k and --allele_min_hits, the same on both command lines; sets a.alleles to None without
-    --variants, else to (path, k, min_hits)"""
-    if (a.allele_k is not None or a.allele_min_hits is not None) and not a.variants:
+    --variants, else to (path, k, min_hits).  (--discover_variants, discover.py, stands in --variants' place: the two values go
+    behind it as well, and it takes them from the namespace itself.)"""
+    if (a.allele_k is not None or a.allele_min_hits is not None) and not a.variants and not getattr(a, "discover_variants", False):
         p.error("--allele_k and --allele_min_hits need --variants")
     if a.variants and not with_matrix:
         p.error("--variants needs --count_matrix and --transcripts: the allele calls go with the gene calls of the matrix")

@@ -9,7 +9,8 @@
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --tagged_reads tagged.fa --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR
                                 [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                 [--umi_per_gene [--gene_umi_dist 0|1 | --gene_umi_dist2]]
-                                [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]
+                                [(--variants variants.tsv | --discover_variants [--discover_k 11] [--discover_min_alt 5] [--discover_min_frac 0.1])
+                                 [--allele_k 15] [--allele_min_hits 1]
                                  [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
                                   [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
 
@@ -53,6 +54,12 @@ too small a lead; donor_summary.tsv counts them (donors.py, which also runs alon
 leave-one-out hard EM over their allele counts, from --donor_restarts random starts of at most --donor_max_iter iterations, and the
 same call follows with the donors cluster0 .. cluster<K-1>; cluster_genotypes.tsv holds the inferred genotypes in the format of
 --donor_genotypes and donor_clusters.tsv the restarts.  Every other file of DIR stays the same bytes.
+--discover_variants (in --variants' place, with --allele_k, --allele_min_hits and the donor options behind it as behind --variants)
+needs no variants file: a third table holds every window of --discover_k bases of the transcripts with its place, two windows of a
+read that lie --discover_k + 1 apart on one diagonal of the read's own gene enclose one base, and the device piles those bases up
+per transcript position; a position where at least --discover_min_alt reads and --discover_min_frac of them show another letter
+than the transcript's becomes a variant.  DIR/discovered_variants.tsv holds them in --variants' format, discovered_sites.tsv their
+counts, and the run goes on as with --variants DIR/discovered_variants.tsv (discover.py).  Not with --matrix_from_reads.
 --matrix_from_reads writes the same DIR from the one pass over the reads: every read's gene (and isoform) call is made on the device
 from its cDNA where it lies in the read, while its chunk is there (genes.py MatrixFromReads).  --tagged_reads is then optional, and
 a tagged file is written as without the flag but not read back; without it the input is read once.  One column differs: the UR of
@@ -81,6 +88,7 @@ from .consensus import ANCHORS, BAND_DEFAULT, MAX_ED_DEFAULT, MIN_READS_DEFAULT,
 from .genes import (K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HITS_DEFAULT, add_gene_options, check_iso_options,
                     check_per_gene_options)
 from .alleles import add_allele_options, check_allele_options, log_counts as log_allele_counts
+from .discover import add_discover_options, check_discover_options, log_counts as log_discover_counts
 from .donors import add_donor_options, check_donor_options, log_counts as log_donor_counts
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
@@ -167,6 +175,7 @@ def parse_args(args):
     add_gene_options(p)
     add_allele_options(p)
     add_donor_options(p)
+    add_discover_options(p)
     a = p.parse_args(args)
     if a.matrix_from_reads and not (a.count_matrix and a.transcripts):
         p.error("--matrix_from_reads needs --count_matrix and --transcripts: it is another way to that matrix")
@@ -179,7 +188,8 @@ def parse_args(args):
     check_iso_options(p, a, bool(a.count_matrix))
     check_per_gene_options(p, a, bool(a.count_matrix))
     check_allele_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
-    check_donor_options(p, a, bool(a.variants))
+    check_discover_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
+    check_donor_options(p, a, bool(a.variants) or a.discover_variants)
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
@@ -359,8 +369,9 @@ def write_count_matrix(args):
     counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
                                     args.gene_min_hits, args.device, args.iso_margin, args.em,
                                     (UMI_LEN[args.data_type], args.gene_umi_dist) if args.umi_per_gene else None, args.alleles,
-                                    args.donors)
+                                    args.donors, args.discover)
     log_counts(counts, args.count_matrix)
+    log_discover_counts(counts, args.count_matrix)
     log_allele_counts(counts, args.count_matrix)
     log_donor_counts(counts, args.count_matrix)
 

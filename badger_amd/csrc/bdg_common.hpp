@@ -167,6 +167,16 @@ struct bdg_ctx {
     uint64_t al_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_alleles_index_stats
     std::vector<uint32_t> al_keys_per_value;       // ... [2 * n_variants]
     int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
+    // ---- site index and pileup (discover_kernels.hip): a third table of the same slots with its own k, the slot's fourth word
+    // the smallest site of its key; replaced by the next bdg_sites_index_build, which touches neither of the other two
+    DevBuf st_table;     // st_slots slots of {u64 key, u32 gene, u32 site}
+    DevBuf st_bases;     // the transcripts' bases as the build got them, u8 [st_sites]: k_sites_select reads the reference letter
+    DevBuf st_counts;    // u32 [st_sites][4]: the pileup, accumulated over the calls since the build or bdg_sites_reset
+    uint64_t st_slots = 0;                   // a power of two; 0: no site index
+    uint64_t st_sites = 0;                   // seq_off[n_seqs] of the build: sites are 0 .. st_sites - 1
+    uint32_t st_k = 0;
+    uint64_t st_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_sites_index_stats
+    int st_pileup_per_cu = 0;                // blocks of k_sites_pileup resident on a compute unit (asked once)
     int em_per_cu = 0;                      // em_kernels.hip: blocks of k_em_tcc resident on a compute unit (asked once)
     int donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
     int cluster_per_cu[3] = { 0, 0, 0 };    // demux_kernels.hip: the same of k_cluster_counts, k_cluster_assign and k_cluster_words

@@ -5,7 +5,8 @@ that every read and molecule is compatible with.
     python -m badger_amd.genes -i tagged.fa -t transcripts.fa[.gz] [--tx2gene map.tsv] -o DIR [--gene_k 21] [--gene_min_hits 3]
                                [--isoforms [--iso_margin 1] [--isoform_em [--em_eps 1e-3] [--em_max_iter 1000] [--em_init uniform|pool]]]
                                [--umi_per_gene --umi_len L [--gene_umi_dist 0|1 | --gene_umi_dist2]]
-                               [--variants variants.tsv [--allele_k 15] [--allele_min_hits 1]
+                               [(--variants variants.tsv | --discover_variants [--discover_k 11] [--discover_min_alt 5] [--discover_min_frac 0.1])
+                                [--allele_k 15] [--allele_min_hits 1]
                                 [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
                                  [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
 
@@ -935,7 +936,7 @@ def device_em(ctx):
 
 
 def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None,
-                           em=None, per_gene=None, variants=None, donors=None):
+                           em=None, per_gene=None, variants=None, donors=None, discover=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
     reads.tsv, with iso_margin (--isoforms) the files of ISO_FILES, and with em = (eps, max_iter, init) (--isoform_em) those of
     EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
@@ -943,8 +944,11 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
     the genes table and the files of alleles.FILES, and with donors = (path, options) (--donor_genotypes, behind variants) the
     donor of every cell from the allele counts on the device (bdg_donor_scores) and the files of donors.FILES; with a
     donors.ClusterOptions in the path's place (--donors) the donors are clusters fitted on the device (bdg_donor_cluster) and the
-    files of donors.CLUSTER_FILES come too -> counts"""
+    files of donors.CLUSTER_FILES come too; with discover = (k, min_alt, ppm, allele k, allele min_hits) (--discover_variants, in
+    variants' place) the variants are found in the reads by the pileup on the device (bdg_sites_pileup), the files of
+    discover.FILES come too and the rest follows as with variants = DIR/discovered_variants.tsv -> counts"""
     from . import _native, alleles
+    from . import discover as discover_step
     from . import donors as donors_step
     ctx = _native.default_context(device)
     names, tx_names, feat = _build_index(ctx, transcripts, tx2gene, k, iso_margin)
@@ -952,7 +956,11 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
         stats = ctx.genes_index_stats()
         caller = alleles.device_caller(ctx, variants[0], transcripts, names, feat, bool(tx2gene), variants[1], variants[2]) \
             if variants else None
-        if donors:
+        if discover:
+            caller = discover_step.device_discoverer(
+                ctx, transcripts, names, feat, bool(tx2gene), *discover,
+                donors_of=(lambda ids: donors_step.device_demux(ctx, donors[0], ids, donors[1])) if donors else None)
+        elif donors:
             caller.donors = donors_step.device_demux(ctx, donors[0], caller.variants.ids, donors[1])
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
                                           (tx_names, feat) if iso_margin else None,
@@ -960,8 +968,10 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
                                           (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None, caller)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         _drop_index(ctx, k)
-        if variants:
+        if variants or discover:
             alleles.drop_index(ctx)
+        if discover:
+            discover_step.drop_index(ctx)
     counts.update(transcripts=len(tx_names), features=len(names), keys=int(stats[1]), ambiguous=int(stats[2]), k=k)
     os.makedirs(out_dir, exist_ok=True)
     for name, data in files.items():
@@ -1210,6 +1220,8 @@ def parse_args(argv):
     add_allele_options(p)
     from .donors import add_donor_options, check_donor_options
     add_donor_options(p)
+    from .discover import add_discover_options, check_discover_options
+    add_discover_options(p)
     p.add_argument("--umi_len", type=gene_umi_len_arg, default=None, metavar="L",
                    help="--umi_per_gene: letters of the library's UMI, 3 .. 12 (a UMI is usable at L - 2 .. L + 2 letters)")
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
@@ -1224,7 +1236,8 @@ def parse_args(argv):
         p.error("--umi_per_gene needs --umi_len: the tagged file does not say how many letters the library's UMI has")
     a.per_gene = (a.umi_len, a.gene_umi_dist) if a.umi_per_gene else None
     check_allele_options(p, a, True)
-    check_donor_options(p, a, bool(a.variants))
+    check_discover_options(p, a, True)
+    check_donor_options(p, a, bool(a.variants) or a.discover_variants)
     return a
 
 
@@ -1234,10 +1247,12 @@ def main(argv):
     if not logger.handlers:
         logger.addHandler(logging.StreamHandler(stream=sys.stdout))
     from .alleles import log_counts as log_allele_counts
+    from .discover import log_counts as log_discover_counts
     from .donors import log_counts as log_donor_counts
     counts = count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
-                                    a.em, a.per_gene, a.alleles, a.donors)
+                                    a.em, a.per_gene, a.alleles, a.donors, a.discover)
     log_counts(counts, a.output)
+    log_discover_counts(counts, a.output)
     log_allele_counts(counts, a.output)
     log_donor_counts(counts, a.output)
 

@@ -1,0 +1,279 @@
+"""The rule of variant discovery (badger_amd/discover.py) on the CPU: the numpy checker against the plain dictionary form, the cases
+derived by hand from the rule's clauses, the selection at its boundaries, the two files to the letter, the command lines, and the
+accuracy condition on the planted pool."""
+import numpy as np
+import pytest
+
+import discover_cases as dc
+from badger_amd import alleles as al
+from badger_amd import badger
+from badger_amd import discover as dv
+from badger_amd import genes as gn
+
+
+# ---------------------------------------------------------------- checker against the plain form ----
+@pytest.mark.parametrize("k", (11, 15, 31))
+def test_checker_against_the_plain_form(k):
+    rng = np.random.default_rng(40 + k)
+    seen = 0
+    for _ in range(12):
+        seqs, feats, reads, recs = dc.small_case(rng, k)
+        idx, plain = dv.build_index(seqs, feats, k), dc.plain_index(seqs, feats, k)
+        n_sites = sum(len(s) for s in seqs)
+        assert idx.n_sites == n_sites and len(idx.keys) == len(plain)
+        keys, values = dc.plain_stats(plain, k)
+        assert (idx.keys == keys).all() and (idx.gene == values).all()
+        by_key = {int(gn.keys_of(w, k)[0]): e[1] for w, e in plain.items()}
+        assert [by_key[int(x)] for x in idx.keys] == idx.site.tolist()
+        want = dc.plain_pileup(plain, n_sites, reads, recs, k)
+        got = dv.pileup(idx, reads, recs)
+        assert got.tolist() == want
+        seen += int(got.sum())
+        # in two calls, into one array
+        half = len(reads) // 2
+        twice = dv.pileup(idx, reads[half:], recs[half:], dv.pileup(idx, reads[:half], recs[:half]))
+        assert (twice == got).all()
+        for min_alt, ppm in ((1, 1), (1, 500000), (2, 1), (1, 1000000)):
+            assert dc.site_tuples(dv.select(idx, got, min_alt, ppm)) == dc.plain_select(idx.bases, want, min_alt, ppm)
+    assert seen > 100
+
+
+@pytest.mark.parametrize("k", (11, 15, 31))
+def test_hand_derived_cases(k):
+    for name, c in dc.hand_cases(k).items():
+        idx = dv.build_index(c["seqs"], c["features"], k)
+        got = dv.pileup(idx, c["reads"], c["recs"])
+        have = {int(s): got[s].tolist() for s in np.flatnonzero(got.sum(axis=1))}
+        assert have == c["want"], (name, k)
+        plain = dc.plain_pileup(dc.plain_index(c["seqs"], c["features"], k), idx.n_sites, c["reads"], c["recs"], k)
+        assert got.tolist() == plain, (name, k)
+
+
+def test_refusals_of_the_checker():
+    with pytest.raises(ValueError, match="k out of range"):
+        dv.build_index([b"ACGT"], [0], 10)
+    with pytest.raises(ValueError, match="k out of range"):
+        dv.build_index([b"ACGT"], [0], 32)
+    with pytest.raises(ValueError, match="feature id reserved"):
+        dv.build_index([b"ACGT"], [gn.AMBIGUOUS], 11)
+    idx = dv.build_index([b"ACGT"], [0], 11)
+    assert len(idx.keys) == 0 and idx.stats() == (0, 0, 0, 64, 0, 0)
+    with pytest.raises(ValueError, match="min_alt"):
+        dv.select(idx, idx.empty_counts(), 0, 1)
+    for ppm in (0, 1000001):
+        with pytest.raises(ValueError, match="ppm"):
+            dv.select(idx, idx.empty_counts(), 1, ppm)
+
+
+# ---------------------------------------------------------------- selection ----
+def _select(bases, rows, min_alt, ppm):
+    idx = dv.SiteIndex(np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0, 11,
+                       np.frombuffer(bases, dtype=np.uint8), np.array([0, len(bases)]))
+    return dc.site_tuples(dv.select(idx, np.array(rows, dtype=np.uint32), min_alt, ppm))
+
+
+def test_selection_boundaries():
+    # min_alt - 1 and min_alt
+    assert _select(b"A", [[10, 4, 0, 0]], 5, 1) == []
+    assert _select(b"A", [[10, 5, 0, 0]], 5, 1) == [(0, 0, 1, (10, 5, 0, 0))]
+    # the fraction at exact equality (3 of 12 is 250,000 ppm) and one count below (3 of 13)
+    assert _select(b"C", [[0, 9, 3, 0]], 1, 250000) == [(0, 1, 2, (0, 9, 3, 0))]
+    assert _select(b"C", [[0, 10, 3, 0]], 1, 250000) == []
+    assert _select(b"C", [[0, 9, 3, 0]], 1, 250001) == []
+    # the whole depth on the other letter, at ppm's maximum; one read of the reference's letter takes it below
+    assert _select(b"G", [[0, 0, 0, 7]], 7, 1000000) == [(0, 2, 3, (0, 0, 0, 7))]
+    assert _select(b"G", [[0, 0, 1, 7]], 7, 1000000) == []
+    # a tie of two other letters: the lowest code; the reference's own count never competes
+    assert _select(b"T", [[0, 6, 6, 50]], 1, 1) == [(0, 3, 1, (0, 6, 6, 50))]
+    assert _select(b"A", [[50, 0, 6, 6]], 1, 1) == [(0, 0, 2, (50, 0, 6, 6))]
+    assert _select(b"C", [[6, 9, 6, 6]], 1, 1) == [(0, 1, 0, (6, 9, 6, 6))]
+    # a transcript base that is no letter, and depth 0
+    assert _select(b"N", [[5, 5, 5, 5]], 1, 1) == []
+    assert _select(b"A", [[0, 0, 0, 0]], 1, 1) == []
+    # only the reference's letter
+    assert _select(b"A", [[9, 0, 0, 0]], 1, 1) == []
+    # 64 bits: 4,000,000,000 * 10^6 against ppm * depth
+    assert _select(b"A", [[4000000000, 4000000000, 0, 0]], 1, 500000) == [(0, 0, 1, (4000000000, 4000000000, 0, 0))]
+    assert _select(b"A", [[4000000001, 4000000000, 0, 0]], 1, 500000) == []
+    # several sites come out by site
+    assert [t[0] for t in _select(b"ACGT", [[0, 1, 0, 0], [0, 1, 0, 0], [1, 0, 1, 0], [0, 0, 2, 0]], 1, 1)] == [0, 2, 3]
+
+
+# ---------------------------------------------------------------- the files ----
+TX_NAMES = ["ENST1", "empty", "ENST2"]
+TX_SEQS = [b"ACGTACGTAC", b"", b"GGGTTTAAAC"]
+
+
+def _recs(rows):
+    out = np.zeros(len(rows), dtype=dv.SITE_DTYPE)
+    for i, (site, ref, alt, count) in enumerate(rows):
+        out[i] = (site, ref, alt, 0, count)
+    return out
+
+
+def test_the_two_files_to_the_letter():
+    recs = _recs([(0, 0, 3, (9, 0, 1, 5)), (9, 1, 0, (7, 2, 0, 0)), (10, 2, 1, (0, 4, 4, 0)), (19, 1, 2, (0, 1, 6, 0))])
+    off = [0, 10, 10, 20]
+    assert dv.variants_text(recs, TX_NAMES, off) == (b"ENST1:1:A>T\tENST1\t1\tA\tT\n" b"ENST1:10:C>A\tENST1\t10\tC\tA\n"
+                                                      b"ENST2:1:G>C\tENST2\t1\tG\tC\n" b"ENST2:10:C>G\tENST2\t10\tC\tG\n")
+    assert dv.sites_text(recs, TX_NAMES, off) == (b"id\tA\tC\tG\tT\tdepth\n" b"ENST1:1:A>T\t9\t0\t1\t5\t15\n" b"ENST1:10:C>A\t7\t2\t0\t0\t9\n"
+                                                   b"ENST2:1:G>C\t0\t4\t4\t0\t8\n" b"ENST2:10:C>G\t0\t1\t6\t0\t7\n")
+    assert dv.variants_text(recs[:0], TX_NAMES, off) == b"" and dv.sites_text(recs[:0], TX_NAMES, off) == b"id\tA\tC\tG\tT\tdepth\n"
+
+
+def test_parse_variants_accepts_the_discovered_file():
+    recs = _recs([(0, 0, 3, (9, 0, 1, 5)), (9, 1, 0, (7, 2, 0, 0)), (10, 2, 1, (0, 4, 4, 0))])
+    text = dv.variants_text(recs, TX_NAMES, [0, 10, 10, 20]).decode()
+    v = al.parse_variants(text.splitlines(True), TX_NAMES, TX_SEQS, np.array([0, 1, 2], dtype=np.uint32))
+    assert v.ids == ["ENST1:1:A>T", "ENST1:10:C>A", "ENST2:1:G>C"] and v.ref == ["A", "C", "G"] and v.alt == ["T", "A", "C"]
+    assert v.gene.tolist() == [0, 0, 2] and v.occ == [(0, 0, 0), (1, 0, 9), (2, 2, 0)]
+
+
+def test_discoverer_finds_writes_and_delegates():
+    """over the checkers: the hook writes its two files, then the four of a Caller over exactly the variants it wrote, with the
+    donors' hook made from their ids; every other file of count_matrix_records is left alone"""
+    k = 11
+    rng = np.random.default_rng(3)
+    t = [dc.gc.rand_seq(rng, 120), dc.gc.rand_seq(rng, 120)]
+    p = 60
+    alt = dc._sub(t[0], p)
+    seqs = [alt.encode()] * 3 + [t[0].encode()] * 2 + [t[1].encode()] * 2
+    recs = dc.gene_recs([0] * 5 + [1] * 2)
+    ids = [b"r%d" % i for i in range(7)]
+    cb = [b"AAAC", b"AAAC", b"AAAG", b"AAAG", b"AAAC", b"AAAG", b"AAAC"]
+    ub = [b"U%d" % i for i in range(7)]
+    names, feat = ["g0", "g1"], np.array([0, 1], dtype=np.uint32)
+    tx_seqs = [x.encode() for x in t]
+    asked = []
+
+    def donors_of(variant_ids):
+        asked.append(list(variant_ids))
+        return lambda cells, ref, alt: ({"donors.tsv": b"x"}, {"donor_cells": len(cells)})
+    hook = dv.checker_discoverer(["t0", "t1"], tx_seqs, feat, names, k, 3, 1, donors_of=donors_of)
+    files, counts = gn.count_matrix_records(ids, cb, ub, None, recs, names, alleles=lambda *a: hook(seqs, *a))
+    name = "t0:%d:%s>%s" % (p + 1, t[0][p], alt[p])
+    assert files["discovered_variants.tsv"] == ("%s\tt0\t%d\t%s\t%s\n" % (name, p + 1, t[0][p], alt[p])).encode()
+    row = [0, 0, 0, 0]
+    row["ACGT".index(t[0][p])], row["ACGT".index(alt[p])] = 2, 3
+    assert files["discovered_sites.tsv"] == ("id\tA\tC\tG\tT\tdepth\n%s\t%d\t%d\t%d\t%d\t5\n" % ((name,) + tuple(row))).encode()
+    assert asked == [[name]] and files["donors.tsv"] == b"x" and counts["discovered"] == 1 and counts["variants"] == 1
+    variants = al.parse_variants(files["discovered_variants.tsv"].decode().splitlines(True), ["t0", "t1"], tx_seqs, feat)
+    want, _ = gn.count_matrix_records(ids, cb, ub, None, recs, names,
+                                      alleles=lambda *a: al.checker_caller(variants, tx_seqs, names)(seqs, *a))
+    plain, _ = gn.count_matrix_records(ids, cb, ub, None, recs, names)
+    for f in al.FILES:
+        assert files[f] == want[f], f
+    for f in plain:
+        assert files[f] == plain[f], f
+    assert b"\t3\n" in files["allele_alt.mtx"] or files["allele_alt.mtx"].count(b"\n") >= 3
+    # nothing found: as --variants on an empty file
+    none = dv.checker_discoverer(["t0", "t1"], tx_seqs, feat, names, k, 4, 1)
+    files, counts = gn.count_matrix_records(ids, cb, ub, None, recs, names, alleles=lambda *a: none(seqs, *a))
+    empty = al.checker_caller(al.parse_variants([], ["t0", "t1"], tx_seqs, feat), tx_seqs, names)
+    want, _ = gn.count_matrix_records(ids, cb, ub, None, recs, names, alleles=lambda *a: empty(seqs, *a))
+    assert files["discovered_variants.tsv"] == b"" and counts["discovered"] == 0
+    for f in al.FILES:
+        assert files[f] == want[f], f
+
+
+# ---------------------------------------------------------------- the command lines ----
+def _refused(capsys, parse, argv):
+    with pytest.raises(SystemExit) as e:
+        parse(argv)
+    assert e.value.code == 2
+    return capsys.readouterr().err
+
+
+GENES_ARGV = ["-i", "tagged.fa", "-t", "tx.fa", "-o", "DIR"]
+STAGE2_ARGV = ["-r", "reads.fastq", "-d", "tenX_v3", "-l", "wl.txt", "-o", "out"]
+MATRIX_ARGV = STAGE2_ARGV + ["--tagged_reads", "t.fa", "--transcripts", "tx.fa", "--count_matrix", "DIR"]
+DEFAULTS = (dv.K_DEFAULT, dv.MIN_ALT_DEFAULT, dv.ppm_of(dv.MIN_FRAC_DEFAULT), al.K_DEFAULT, al.MIN_HITS_DEFAULT)
+NEEDS = "--discover_k, --discover_min_alt and --discover_min_frac need --discover_variants"
+
+
+def _without_new_fields(a):
+    d = dict(vars(a))
+    for f in ("discover_variants", "discover_k", "discover_min_alt", "discover_min_frac", "discover"):
+        d.pop(f)
+    return d
+
+
+@pytest.mark.parametrize("parse, base", ((gn.parse_args, GENES_ARGV), (badger.parse_args, MATRIX_ARGV)))
+def test_command_lines_accept(parse, base):
+    assert DEFAULTS == (11, 5, 100000, 15, 1)
+    a = parse(base)
+    assert a.discover is None and a.discover_variants is False and a.alleles is None and a.donors is None
+    a = parse(base + ["--discover_variants"])
+    assert a.discover == DEFAULTS and a.alleles is None and a.variants is None and a.donors is None
+    # what every other field parses to does not move with the flag
+    assert _without_new_fields(a) == _without_new_fields(parse(base))
+    a = parse(base + ["--discover_variants", "--discover_k", "31", "--discover_min_alt", "2", "--discover_min_frac", "0.25", "--allele_k", "13",
+                      "--allele_min_hits", "2", "--donors", "4", "--donor_seed", "7"])
+    assert a.discover == (31, 2, 250000, 13, 2) and a.alleles is None
+    assert tuple(a.donors[0]) == (4, 8, 50, 7)
+    a = parse(base + ["--discover_variants", "--donor_genotypes", "d.tsv", "--discover_min_frac", "0.000001"])
+    assert a.donors[0] == "d.tsv" and a.discover[2] == 1
+    assert parse(base + ["--discover_variants", "--discover_min_frac", "1"]).discover[2] == 1000000
+    assert parse(base + ["--variants", "v.tsv"]).discover is None and parse(base + ["--variants", "v.tsv"]).alleles == ("v.tsv", 15, 1)
+
+
+@pytest.mark.parametrize("parse, base", ((gn.parse_args, GENES_ARGV), (badger.parse_args, MATRIX_ARGV)))
+def test_command_lines_refuse(capsys, parse, base):
+    for argv, message in (
+            (["--discover_k", "11"], NEEDS), (["--discover_min_alt", "5"], NEEDS), (["--discover_min_frac", "0.1"], NEEDS),
+            (["--variants", "v.tsv", "--discover_k", "11"], NEEDS),
+            (["--discover_variants", "--variants", "v.tsv"], "--discover_variants excludes --variants"),
+            (["--discover_variants", "--discover_k", "10"], "--discover_k takes an integer, 11 .. 31"),
+            (["--discover_variants", "--discover_k", "32"], "--discover_k takes an integer, 11 .. 31"),
+            (["--discover_variants", "--discover_k", "x"], "--discover_k takes an integer, 11 .. 31"),
+            (["--discover_variants", "--discover_min_alt", "0"], "--discover_min_alt takes an integer, at least 1"),
+            (["--discover_variants", "--discover_min_frac", "0"], "--discover_min_frac takes a fraction, 0.000001 .. 1"),
+            (["--discover_variants", "--discover_min_frac", "1.5"], "--discover_min_frac takes a fraction, 0.000001 .. 1"),
+            (["--discover_variants", "--discover_min_frac", "nan"], "--discover_min_frac takes a fraction, 0.000001 .. 1"),
+            (["--discover_variants", "--discover_min_frac", "0.0000001"], "--discover_min_frac takes a fraction, 0.000001 .. 1"),
+            # the old messages, without the flag and with the new options on the line
+            (["--allele_k", "15"], "--allele_k and --allele_min_hits need --variants"),
+            (["--allele_min_hits", "2"], "--allele_k and --allele_min_hits need --variants"),
+            (["--donors", "2"], "--donors needs --variants: the donors are told apart by the allele counts"),
+            (["--donor_genotypes", "d.tsv"], "--donor_genotypes needs --variants: the donors are told apart by the allele counts"),
+            (["--discover_variants", "--allele_k", "10"], "--allele_k takes an integer, 11 .. 31"),
+            (["--discover_variants", "--allele_min_hits", "0"], "--allele_min_hits takes an integer, 1 .. 255"),
+            (["--discover_variants", "--donors", "2", "--donor_genotypes", "d.tsv"], "--donors excludes --donor_genotypes"),
+            (["--discover_variants", "--donor_seed", "3"], "--donor_restarts, --donor_max_iter and --donor_seed need --donors"),
+            (["--discover_variants", "--iso_margin", "2"], "--iso_margin needs --isoforms"),
+            (["--discover_variants", "--gene_k", "10"], "--gene_k takes an integer, 11 .. 31")):
+        assert message in _refused(capsys, parse, base + argv), argv
+
+
+def test_stage2_command_line_refuses(capsys):
+    from_reads = STAGE2_ARGV + ["--transcripts", "tx.fa", "--count_matrix", "DIR", "--matrix_from_reads"]
+    assert badger.parse_args(from_reads).discover is None
+    for argv, message in (
+            (STAGE2_ARGV + ["--discover_variants"], "--discover_variants needs --count_matrix and --transcripts"),
+            (STAGE2_ARGV + ["--tagged_reads", "t.fa", "--discover_variants"], "--discover_variants needs --count_matrix and --transcripts"),
+            (from_reads + ["--discover_variants"],
+             "--discover_variants may not be combined with --matrix_from_reads: the one-pass route does not carry allele calls yet"),
+            (from_reads + ["--variants", "v.tsv"],
+             "--variants may not be combined with --matrix_from_reads: the one-pass route does not carry allele calls yet"),
+            (STAGE2_ARGV + ["--variants", "v.tsv"], "--variants needs --count_matrix and --transcripts"),
+            (STAGE2_ARGV + ["--count_matrix", "DIR", "--discover_variants"], "--count_matrix needs --tagged_reads and --transcripts"),
+            (STAGE2_ARGV + ["--transcripts", "tx.fa", "--discover_variants"],
+             "--transcripts, --tx2gene, --gene_k and --gene_min_hits need --count_matrix")):
+        assert message in _refused(capsys, badger.parse_args, argv), argv
+
+
+# ---------------------------------------------------------------- accuracy ----
+def test_accuracy_on_the_planted_pool():
+    """The condition of DESIGN 4.29 at the defaults (k 11, at least 5 reads, a tenth of the depth) on the pinned seed: 40 random
+    genes of 1,500 bases with 4 sites each, 4 donors, 6,000 3' fragments of 300 .. 1,000 bases with synth's errors.  No false site,
+    and the 71 true ones of 158 polymorphic sites that the checker finds (it is deterministic: pinned exactly).  About a tenth of
+    the reads that cover a site are evidence for it, exp(-0.083 (2k + 1)); random genes say that the rule works, not how well on
+    human data."""
+    model = dc.pool(np.random.default_rng(1))
+    idx = dv.build_index(model["tx_seqs"], np.arange(len(model["tx_seqs"])), dv.K_DEFAULT)
+    counts = dv.pileup(idx, model["reads"], dc.gene_recs(model["gene"]))
+    recs = dv.select(idx, counts, dv.MIN_ALT_DEFAULT, dv.ppm_of(dv.MIN_FRAC_DEFAULT))
+    true, false, polymorphic = dc.score(model, recs)
+    print("true %d, false %d, polymorphic %d" % (true, false, polymorphic))
+    assert false == 0
+    assert (true, polymorphic) == (71, 158)

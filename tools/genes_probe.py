@@ -47,6 +47,15 @@ over its class counts, one JSON line each to --out (and stdout).
     python tools/genes_probe.py --cli --alleles ...
         the command line with --count_matrix --variants against --count_matrix alone (4 sites per transcript), then the pairs
         with --parent as above.
+    python tools/genes_probe.py --device --discover [--reads 1000000] [--tx_bases 4000000] [--reps 10] --out profiles/r31_discover.jsonl
+        the first workload once more: bdg_sites_index_build (k_sites_insert, k_sites_stats, the whole call), then
+        bdg_genes_assign_dev, bdg_alleles_assign_dev (4 sites per transcript), bdg_sites_pileup_dev and bdg_sites_select on the same
+        reads: k_sites_pileup beside k_genes_assign and k_alleles_assign and k_sites_select from the event timers of the same run,
+        the median of --reps runs each; then the pileup alone with every read a fragment of ONE transcript, where every add of
+        the call meets the same few thousand addresses.
+    python tools/genes_probe.py --cli --discover ...
+        the command line with --count_matrix --discover_variants against --count_matrix alone, then the pairs with --parent as
+        above.
 """
 import argparse
 import os
@@ -223,6 +232,85 @@ def device_probe_alleles(args):
             a.free()
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
     ctx.alleles_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0, ak)
+
+
+def device_probe_discover(args):
+    from badger_amd import _native
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    ak, dk, sites_per_tx = 15, args.discover_k, 4
+    for tx_bases in args.tx_bases:
+        n_tx = max(tx_bases // TX_LEN, 1)
+        rng = np.random.default_rng(7)
+        tx = rng.integers(0, 4, (n_tx, TX_LEN), dtype=np.uint8)
+        tx_ascii, tx_off = ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64)
+        feat = np.arange(n_tx, dtype=np.uint32)
+        ctx.genes_index_build(tx_ascii, tx_off, feat, args.k)
+        pos = TX_LEN - 1500 + np.sort(rng.integers(ak, 1500 - ak, (n_tx, sites_per_tx)), axis=1)
+        t_of, p_of = np.repeat(np.arange(n_tx), sites_per_tx), pos.ravel()
+        win = tx[t_of[:, None], p_of[:, None] + np.arange(1 - ak, ak)[None, :]]
+        alt = win.copy()
+        alt[:, ak - 1] = (alt[:, ak - 1] + rng.integers(1, 4, len(alt), dtype=np.uint8)) & 3
+        seqs = ACGT[np.stack([win, alt], axis=1).reshape(-1, 2 * ak - 1)]
+        ctx.alleles_index_build(seqs.ravel(), (np.arange(len(seqs) + 1) * (2 * ak - 1)).astype(np.uint64),
+                                np.arange(2 * len(t_of), dtype=np.uint32), t_of.astype(np.uint32), n_tx, ak)
+        build = lambda: ctx.sites_index_build(tx_ascii, tx_off, feat, dk)  # noqa: E731
+        build()
+        ctx.profile(True)
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        build()
+        build_s = time.perf_counter() - t0
+        build_kt = {k: round(v[1], 4) for k, v in ctx.profile_read().items() if k.startswith("k_sites") and v[0]}
+        ctx.profile(False)
+        stats = [int(x) for x in ctx.sites_index_stats()]
+        for what, reads_of in (("reads of every transcript", tx), ("every read of one transcript", tx[:1])):
+            bases, off = fragments(reads_of, args.reads)
+            n = len(off) - 1
+            d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off)]
+            d_gene = _native.DeviceArray(ctx, n * 6, np.uint32)
+            cap = 8 * n
+            d_out, d_counts = _native.DeviceArray(ctx, cap * 4, np.uint32), _native.DeviceArray(ctx, 2, np.uint64)
+            selected = []
+
+            def call():
+                ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, d_gene)
+                ctx.alleles_assign_dev(d[0], d[1], n, d_gene, d_out, cap, d_counts)
+                ctx.sites_reset()
+                ctx.sites_pileup_dev(d[0], d[1], n, d_gene)
+                selected.append(len(ctx.sites_select(args.discover_min_alt, 100000, cap=1 << 16)))
+            call()
+            ctx.synchronize()
+            per_run = {}
+            ctx.profile(True)
+            for _ in range(args.reps):
+                ctx.profile_reset()
+                call()
+                ctx.synchronize()
+                for k, v in ctx.profile_read().items():
+                    if k in ("k_genes_assign", "k_alleles_assign", "k_sites_pileup", "k_sites_select") and v[0]:
+                        per_run.setdefault(k, []).append(v[1])
+            ctx.profile(False)
+            counts = ctx.sites_counts(n_tx * TX_LEN)
+            gene_recs = d_gene.to_host().view(_native.GENE_DTYPE)
+            med = {k: float(np.median(v)) for k, v in per_run.items()}
+            emit(args.out, {"what": "bdg_sites_index_build, bdg_sites_pileup_dev behind bdg_genes_assign_dev, bdg_sites_select, device-resident: " + what,
+                            "count_layout": args.count_layout, "discover_k": dk, "gene_k": args.k, "allele_k": ak, "transcripts": n_tx,
+                            "transcript_bases": int(n_tx * TX_LEN), "table_bytes": 16 * stats[3], "count_bytes": 16 * int(n_tx * TX_LEN),
+                            "stats": dict(zip(("windows", "keys", "ambiguous", "slots", "longest_run", "wrapped"), stats)),
+                            "build_wall_s": round(build_s, 4), "build_kernel_ms": build_kt, "reads": n, "read_bases": int(off[-1]),
+                            "reads_assigned": int((gene_recs["flags"] & 1 != 0).sum()), "evidence": int(counts.sum(dtype=np.int64)),
+                            "sites_with_evidence": int((counts.sum(axis=1) > 0).sum()), "largest_count": int(counts.max(initial=0)),
+                            "selected": selected[-1], "min_alt": args.discover_min_alt, "ppm": 100000, "reps": args.reps,
+                            "kernel_ms_median": {k: round(v, 4) for k, v in med.items()},
+                            "kernel_ms_runs": {k: [round(x, 4) for x in v] for k, v in per_run.items()},
+                            "pileup_over_genes": round(med["k_sites_pileup"] / med["k_genes_assign"], 4),
+                            "pileup_over_alleles": round(med["k_sites_pileup"] / med["k_alleles_assign"], 4)})
+            for a in d + [d_gene, d_out, d_counts]:
+                a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
+    ctx.alleles_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0, ak)
+    ctx.sites_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), dk)
 
 
 def _variants_of(tx, path, per_tx=4):
@@ -546,7 +634,7 @@ def cli_probe(args):
         r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
-        return time.perf_counter() - t0, [l.split(" - ")[-1].replace(tmp, "TMP") for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l or "Alleles: " in l]
+        return time.perf_counter() - t0, [l.split(" - ")[-1].replace(tmp, "TMP") for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l or "Alleles: " in l or "Discovery: " in l]
 
     def pairs(name_a, a, name_b, b, what):
         walls, said = {name_a: [], name_b: []}, []
@@ -575,6 +663,10 @@ def cli_probe(args):
             matrix = ["--umi_dedup"] + gene + ["--count_matrix", os.path.join(tmp, "matrix")]
             pairs("tagged_route", (ROOT, matrix + ["--tagged_reads", fa]), "from_reads", (ROOT, matrix + ["--matrix_from_reads"]),
                   "stage2 CLI from FASTQ, --umi_dedup --count_matrix%s: --matrix_from_reads against --tagged_reads" % what)
+    elif args.discover:
+        matrix = tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]
+        pairs("count_matrix", (ROOT, matrix), "discover", (ROOT, matrix + ["--discover_variants"]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix: with --discover_variants against without")
     elif args.alleles:
         var = os.path.join(tmp, "variants.tsv")
         _variants_of(tx, var)
@@ -613,6 +705,10 @@ def main():
     p.add_argument("--margin", type=int, default=1)
     p.add_argument("--spans", action="store_true", help="the span kernels beside the forward ones (--device), --matrix_from_reads (--cli) (DESIGN 4.25)")
     p.add_argument("--alleles", action="store_true", help="the allele leg of --device and of --cli (DESIGN 4.26)")
+    p.add_argument("--discover", action="store_true", help="the discovery leg of --device and of --cli (DESIGN 4.29)")
+    p.add_argument("--discover_k", type=int, default=11)
+    p.add_argument("--discover_min_alt", type=int, default=5)
+    p.add_argument("--count_layout", default="[site][4]", help="--discover: what the record says of the library's count layout")
     p.add_argument("--em", action="store_true", help="k_em_tcc alone; with --cli --isoforms the --isoform_em leg (DESIGN 4.21)")
     p.add_argument("--em_problems", type=int, default=1000000)
     p.add_argument("--em_wide", type=int, default=100000)
@@ -625,7 +721,7 @@ def main():
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
-        (device_probe_alleles if args.alleles else device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
+        (device_probe_discover if args.discover else device_probe_alleles if args.alleles else device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
     if args.em and not args.cli:
         em_probe(args)
     if args.cli:
