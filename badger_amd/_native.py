@@ -800,14 +800,26 @@ class Context:
         self._check(self.lib.bdg_consensus_set_band(self.h, int(band)))
         self.consensus_band = int(band)
 
+    def _with_capacity(self, call, cap, name, retry):
+        """a call that emits records into room for cap of them: call(cap) -> (the library's code, the array, the records there
+        are).  With more than cap it is made once more with that count - retry False raises the library's E_CAPACITY instead,
+        its `n_records` the count.  -> the records"""
+        for attempt in range(2):
+            rc, out, n_records = call(cap)
+            if rc == E_CAPACITY and retry and attempt == 0:
+                cap = n_records
+                continue
+            if rc == E_CAPACITY:
+                err = BadgerHipError(rc, "%s: %d records, room for %d" % (name, n_records, cap))
+                err.n_records = n_records
+                raise err
+            self._check(rc)
+            return out[:n_records]
+
     def genes_index_build(self, bases, seq_off, features, k=GENES_K_DEFAULT):
         """the k-mer table of the sequences (bases uint8, seq_off uint64 [n + 1], features uint32 [n]) on the device, held by
         the context in place of an earlier one (bdg_genes_index_build)"""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        features = np.ascontiguousarray(features, dtype=np.uint32)
-        if len(seq_off) != len(features) + 1:
-            raise ValueError("seq_off holds one entry more than features")
+        bases, seq_off, features = _build_seqs(bases, seq_off, features=features)
         self._check(self.lib.bdg_genes_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data, int(k)))
 
     def genes_index_stats(self):
@@ -833,12 +845,7 @@ class Context:
     def genes_index_build_iso(self, bases, seq_off, features, local, k=GENES_K_DEFAULT):
         """genes_index_build plus, per key, the mask of the local indices (uint8 [n], each <= 63) of the sequences that hold
         it (bdg_genes_index_build_iso)"""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        features = np.ascontiguousarray(features, dtype=np.uint32)
-        local = np.ascontiguousarray(local, dtype=np.uint8)
-        if len(seq_off) != len(features) + 1 or len(local) != len(features):
-            raise ValueError("seq_off holds one entry more than features, local as many")
+        bases, seq_off, features, local = _build_seqs(bases, seq_off, features=features, local=local)
         self._check(self.lib.bdg_genes_index_build_iso(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data,
                                                        local.ctypes.data, int(k)))
 
@@ -900,12 +907,8 @@ class Context:
         """the allele table of the allele sequences (bases uint8, seq_off uint64 [n + 1], values uint32 [n]: 2 * variant + allele)
         on the device, beside the genes table and in place of an earlier allele table; genes uint32 [n_variants] the feature id
         of every variant's gene, each < n_features (bdg_alleles_index_build)"""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        values = np.ascontiguousarray(values, dtype=np.uint32)
+        bases, seq_off, values = _build_seqs(bases, seq_off, values=values)
         genes = np.ascontiguousarray(genes, dtype=np.uint32)
-        if len(seq_off) != len(values) + 1:
-            raise ValueError("seq_off holds one entry more than values")
         self._check(self.lib.bdg_alleles_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(values), values.ctypes.data,
                                                      genes.ctypes.data, len(genes), int(n_features), int(k)))
 
@@ -929,37 +932,21 @@ class Context:
         (bdg_alleles_assign) -> (ALLELE_DTYPE sorted by (read, variant), crowded reads).  cap: room for that many records
         (default: one per read); with more the call is made once more with the count the library returned - retry False raises
         the library's E_CAPACITY instead, its `n_records` the count."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        gene_recs = np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
-        n = max(len(off) - 1, 0)
-        if len(gene_recs) != n:
-            raise ValueError("a gene record per read")
-        cap = n if cap is None else int(cap)
+        bases, off, gene_recs, n = _reads_with_genes(bases, off, gene_recs)
         counts = np.zeros(2, dtype=np.uint64)
-        for attempt in range(2):
+
+        def call(cap):
             out = np.zeros(cap, dtype=ALLELE_DTYPE)
             rc = self.lib.bdg_alleles_assign(self.h, bases.ctypes.data, off.ctypes.data, n, gene_recs.ctypes.data,
                                              out.ctypes.data if cap else None, cap, counts.ctypes.data)
-            if rc == E_CAPACITY and retry and attempt == 0:
-                cap = int(counts[0])
-                continue
-            if rc == E_CAPACITY:
-                err = BadgerHipError(rc, "bdg_alleles_assign: %d records, room for %d" % (int(counts[0]), cap))
-                err.n_records = int(counts[0])
-                raise err
-            self._check(rc)
-            out = out[:int(counts[0])]
-            return out[np.lexsort((out["variant"], out["read"]))], int(counts[1])
+            return rc, out, int(counts[0])
+        out = self._with_capacity(call, n if cap is None else int(cap), "bdg_alleles_assign", retry)
+        return out[np.lexsort((out["variant"], out["read"]))], int(counts[1])
 
     def sites_index_build(self, bases, seq_off, features, k=SITES_K_DEFAULT):
         """the site table of the transcripts (bases uint8, seq_off uint64 [n + 1], features uint32 [n]) on the device, beside the
         genes and the allele table and in place of an earlier site table; the counts start at zero (bdg_sites_index_build)"""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        features = np.ascontiguousarray(features, dtype=np.uint32)
-        if len(seq_off) != len(features) + 1:
-            raise ValueError("seq_off holds one entry more than features")
+        bases, seq_off, features = _build_seqs(bases, seq_off, features=features)
         self._check(self.lib.bdg_sites_index_build(self.h, bases.ctypes.data, seq_off.ctypes.data, len(features), features.ctypes.data,
                                                    int(k)))
         self._sites = int(seq_off[-1])
@@ -977,12 +964,7 @@ class Context:
     def sites_pileup(self, bases, off, gene_recs):
         """the evidence of the reads over host arrays added to the context's counts, gene_recs GENE_DTYPE [n] what genes_assign gave
         for them (bdg_sites_pileup)"""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        gene_recs = np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
-        n = max(len(off) - 1, 0)
-        if len(gene_recs) != n:
-            raise ValueError("a gene record per read")
+        bases, off, gene_recs, n = _reads_with_genes(bases, off, gene_recs)
         self._check(self.lib.bdg_sites_pileup(self.h, bases.ctypes.data, off.ctypes.data, n, gene_recs.ctypes.data))
 
     def sites_reset(self):
@@ -993,21 +975,14 @@ class Context:
         """the selected sites of the counts as they stand (bdg_sites_select) -> SITE_DTYPE sorted by site.  cap: room for that many
         records (default 1024); with more the call is made once more with the count the library returned - retry False raises
         the library's E_CAPACITY instead, its `n_records` the count."""
-        cap = 1024 if cap is None else int(cap)
         count = C.c_uint64()
-        for attempt in range(2):
+
+        def call(cap):
             out = np.zeros(cap, dtype=SITE_DTYPE)
             rc = self.lib.bdg_sites_select(self.h, int(min_alt), int(ppm), out.ctypes.data if cap else None, cap, C.byref(count))
-            if rc == E_CAPACITY and retry and attempt == 0:
-                cap = int(count.value)
-                continue
-            if rc == E_CAPACITY:
-                err = BadgerHipError(rc, "bdg_sites_select: %d records, room for %d" % (int(count.value), cap))
-                err.n_records = int(count.value)
-                raise err
-            self._check(rc)
-            out = out[:int(count.value)]
-            return out[np.argsort(out["site"], kind="stable")]
+            return rc, out, int(count.value)
+        out = self._with_capacity(call, 1024 if cap is None else int(cap), "bdg_sites_select", retry)
+        return out[np.argsort(out["site"], kind="stable")]
 
     def sites_counts(self, n_sites=None):
         """-> uint32 [n_sites, 4], the counts as they stand; n_sites: seq_off[-1] of the build (default: of this object's last
@@ -1327,6 +1302,26 @@ def _donor_inputs(entries, cell_off, tables, z0=None):
     ok = n >= 0 and not (n and int(cell_off.max()) > len(entries)) and (z0 is None or (z0.ndim == 2 and z0.shape[1] == n))
     text = "cell_off holds one entry more than there are cells, the entries reach to its highest, ten table values"
     return entries, cell_off, _tables10(tables, ok, text if z0 is None else text + ", z0 is restarts x cells"), n
+
+
+def _build_seqs(bases, seq_off, **per_seq):
+    """the sequences of a table build as the library takes them: bases uint8, seq_off uint64 and the arrays that hold a value per
+    sequence (name=array; uint32, `local` uint8), whose lengths seq_off decides -> (bases, seq_off, arrays ...)"""
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    arrays = [np.ascontiguousarray(a, dtype=np.uint8 if name == "local" else np.uint32) for name, a in per_seq.items()]
+    if any(len(a) != len(seq_off) - 1 for a in arrays):
+        names = list(per_seq)
+        raise ValueError("seq_off holds one entry more than " + ", ".join(names[:1] + [n + " as many" for n in names[1:]]))
+    return (np.ascontiguousarray(bases, dtype=np.uint8), seq_off, *arrays)
+
+
+def _reads_with_genes(bases, off, gene_recs):
+    """reads over host arrays with the gene record genes_assign gave for each -> (bases, off, gene_recs, n)"""
+    off, gene_recs = np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(gene_recs, dtype=GENE_DTYPE)
+    n = max(len(off) - 1, 0)
+    if len(gene_recs) != n:
+        raise ValueError("a gene record per read")
+    return np.ascontiguousarray(bases, dtype=np.uint8), off, gene_recs, n
 
 
 def _ptr(x, byte_offset=0):

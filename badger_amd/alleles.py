@@ -306,12 +306,8 @@ def checker_caller(variants, tx_seqs, names, k=K_DEFAULT, min_hits=MIN_HITS_DEFA
 def device_assign(ctx):
     """assign of a Caller on the device: bdg_alleles_assign over pieces of at most genes.BATCH_BASES bases"""
     def run(seqs, gene_recs):
-        parts, crowded, at, per_read = [], 0, 0, RECORDS_PER_READ
-        while at < len(seqs):
-            end, total = at, 0
-            while end < len(seqs) and (end == at or total + len(seqs[end]) <= genes.BATCH_BASES):
-                total += len(seqs[end])
-                end += 1
+        parts, crowded, per_read = [], 0, RECORDS_PER_READ
+        for at, end in genes.pieces(seqs):
             # room for a few records per read (a read of 1,000 bases covers as many sites as its gene has there); a piece that
             # needs more is run once more with its count, and the pieces behind it start from that rate
             recs, more = ctx.alleles_assign(*genes._flatten(seqs[at:end]), gene_recs[at:end], cap=max(1, int(per_read * (end - at))))
@@ -319,7 +315,6 @@ def device_assign(ctx):
             recs["read"] += np.uint32(at)
             parts.append(recs)
             crowded += more
-            at = end
         return np.concatenate(parts + [np.zeros(0, dtype=REC_DTYPE)]).astype(REC_DTYPE), crowded
     return run
 

@@ -2,14 +2,14 @@
 // badger_amd/alleles.py restates it).  gfx950.
 //
 // A second table of genes_kernels.hip's slots holds the keys that cover each site, once per allele; the slot's fourth word is
-// the feature id of the variant's gene.  The planes, the keys, insert_key and the probe are genes_probe.hpp's, shared with the
-// gene kernels: one wave per sequence, persistent, a lane per window, three ballots per 64 bases.
+// the feature id of the variant's gene.  The planes, the keys, insert_key, the walk, the stats pass and the probe are
+// genes_probe.hpp's, shared with the gene kernels: one wave per sequence, persistent, a lane per window, three ballots per 64
+// bases.
 //
-// k_alleles_insert  insert_key plus the gene word.  All writers of a key that stays unambiguous write the same word (a variant
-//                   has one gene), so it needs no order: a lane looks, and stores only where the word differs.  The word of an
-//                   ambiguous key is whichever writer came last and is never used.  As in k_genes_insert a lane whose left
-//                   neighbour holds the same key does nothing.
-// k_alleles_stats   the six occupancy figures of k_genes_stats, and per value 2 v + a the number of its keys that are not
+// k_alleles_insert  kmer_walk with, per key, insert_key plus the gene word.  All writers of a key that stays unambiguous write
+//                   the same word (a variant has one gene), so it needs no order: a lane looks, and stores only where the word
+//                   differs.  The word of an ambiguous key is whichever writer came last and is never used.
+// k_alleles_stats   kmer_stats, the six occupancy figures, and per value 2 v + a the number of its keys that are not
 //                   ambiguous: one atomicAdd per such slot on the value's own counter (a few dozen keys per value: no hot
 //                   address).
 // k_alleles_assign  a read whose gene record is not ASSIGNED, or whose gene has no variant (a byte per feature), costs its gene
@@ -31,73 +31,42 @@
 
 namespace {
 
-constexpr uint32_t ALLELES_INSERT_WAVES_PER_CU = 16;
 constexpr uint32_t ALLELES_STAGE = 256;                       // records a wave parks before it reserves room for them
 
 static_assert(sizeof(bdg_allele_rec) == 16 && sizeof(uint4) == 16 && ALLELES_STAGE >= BDG_ALLELES_MAX_VARIANTS,
               "a record is one 16-byte store, and a read's records fit the empty staging area");
 
+// what k_alleles_insert does with a key: its left neighbour, where it holds the same key, inserts it for the same value
+struct AllelesInsert {
+    struct Seq { uint32_t v, g; };
+    const uint32_t* __restrict__ values; const uint32_t* __restrict__ genes; GeneSlot* table; uint64_t mask; uint32_t shift;
+    __device__ __forceinline__ Seq seq(uint32_t q) const   // (the host has checked the values and the genes)
+    {
+        const uint32_t v = values[q];
+        return Seq{ v, genes[v >> 1] };
+    }
+    __device__ __forceinline__ void window(Seq of, unsigned long long key, uint64_t) const
+    {
+        if (key == KEY_EMPTY) return;
+        const uint64_t at = insert_key(table, mask, shift, key, of.v);
+        if (__hip_atomic_load(&table[at].pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != of.g)
+            __hip_atomic_store(&table[at].pad, of.g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
 __global__ __launch_bounds__(64)
 void k_alleles_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ values,
                       const uint32_t* __restrict__ genes, uint32_t n_seqs, uint32_t k, GeneSlot* table, uint64_t mask, uint32_t shift)
 {
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
-        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets, values and genes)
-        if (len < k) continue;
-        const uint8_t* s = bases + b;
-        const uint32_t v = values[q], g = genes[v >> 1];
-        Planes A = load_planes(s, len, 0, lane);
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
-            const Planes B = load_planes(s, len, p0 + 64, lane);
-            unsigned long long key = window_key(A, B, lane, kmask);
-            const unsigned long long left = __shfl_up(key, 1);
-            if (lane && left == key) key = KEY_EMPTY;               // its left neighbour inserts the same key for the same value
-            if (key != KEY_EMPTY) {
-                const uint64_t at = insert_key(table, mask, shift, key, v);
-                if (__hip_atomic_load(&table[at].pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g)
-                    __hip_atomic_store(&table[at].pad, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            A = B;
-        }
-    }
+    kmer_walk(bases, seq_off, n_seqs, k, AllelesInsert{ values, genes, table, mask, shift });
 }
 
-// out: distinct keys | ambiguous keys | longest run of occupied slots | keys in front of their home slot; per_value [n_values]
-__global__ __launch_bounds__(256)
+// kmer_stats' four figures, and per_value [n_values]
+__global__ __launch_bounds__(KMER_STATS_THREADS)
 void k_alleles_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t shift, unsigned long long* out, uint32_t* per_value,
                      uint32_t n_values)
 {
-    __shared__ unsigned long long sh[4];
-    if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t mask = slots - 1;
-    unsigned long long distinct = 0, amb = 0, run_max = 0, wrapped = 0;
-    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long key = table[s].key;
-        if (key == KEY_EMPTY) continue;
-        ++distinct;
-        const uint32_t v = table[s].value;
-        amb += v == BDG_GENES_AMBIGUOUS;
-        if (v < n_values) atomicAdd(&per_value[v], 1u);
-        wrapped += home_slot(key, shift) > s;
-        if (table[(s - 1) & mask].key == KEY_EMPTY) {               // a run starts here (there is always an empty slot: it ends)
-            unsigned long long run = 1;
-            for (uint64_t t = (s + 1) & mask; table[t].key != KEY_EMPTY; t = (t + 1) & mask) ++run;
-            run_max = run > run_max ? run : run_max;
-        }
-    }
-    if (distinct) atomicAdd(&sh[0], distinct);
-    if (amb) atomicAdd(&sh[1], amb);
-    if (run_max) atomicMax(&sh[2], run_max);
-    if (wrapped) atomicAdd(&sh[3], wrapped);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (sh[0]) atomicAdd(&out[0], sh[0]);
-        if (sh[1]) atomicAdd(&out[1], sh[1]);
-        if (sh[2]) atomicMax(&out[2], sh[2]);
-        if (sh[3]) atomicAdd(&out[3], sh[3]);
-    }
+    kmer_stats(table, slots, shift, out, [=](uint32_t v) { if (v < n_values) atomicAdd(&per_value[v], 1u); });
 }
 
 // the wave's parked records go out: one add on the call's cursor, then a lane per record; a place at or behind cap is not written
@@ -173,11 +142,7 @@ void k_alleles_assign(const uint8_t* __restrict__ bases, const uint64_t* __restr
     if (lane == 0 && n_crowded) atomicAdd(&counts[1], (unsigned long long)n_crowded);
 }
 
-int alleles_check_assign(bdg_ctx* ctx)
-{
-    if (ctx->al_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "alleles: no index built (bdg_alleles_index_build)");
-    return BDG_OK;
-}
+int alleles_check_assign(bdg_ctx* ctx) { return kmer_check_built(ctx, ctx->al, "alleles: no index built (bdg_alleles_index_build)"); }
 
 // d_counts is set to zero, then the kernel (n > 0)
 int alleles_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes,
@@ -185,20 +150,10 @@ int alleles_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* 
 {
     BDG_HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), ctx->stream));
     if (n == 0) return BDG_OK;
-    return bdg_resident_launch(ctx, k_alleles_assign, ctx->al_assign_per_cu, "k_alleles_assign", n, d_bases, d_off, n, ctx->al_k, d_genes,
-                               static_cast<const uint8_t*>(ctx->al_has.p), ctx->al_features, static_cast<const GeneSlot*>(ctx->al_table.p),
-                               ctx->al_slots - 1, kmer_shift(ctx->al_slots), reinterpret_cast<uint4*>(d_out), cap,
+    return bdg_resident_launch(ctx, k_alleles_assign, ctx->al_assign_per_cu, "k_alleles_assign", n, d_bases, d_off, n, ctx->al.k, d_genes,
+                               static_cast<const uint8_t*>(ctx->al_has.p), ctx->al_features, static_cast<const GeneSlot*>(ctx->al.table.p),
+                               ctx->al.mask(), ctx->al.shift(), reinterpret_cast<uint4*>(d_out), cap,
                                reinterpret_cast<unsigned long long*>(d_counts));
-}
-
-void alleles_drop(bdg_ctx* ctx)
-{
-    ctx->al_table.reset();
-    ctx->al_has.reset();
-    ctx->al_slots = 0;
-    ctx->al_k = 0;
-    ctx->al_features = 0;
-    ctx->al_keys_per_value.clear();
 }
 
 }  // namespace
@@ -209,68 +164,46 @@ int bdg_alleles_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* 
                             const uint32_t* genes, uint32_t n_variants, uint32_t n_features, uint32_t k)
 {
     if (!ctx) return BDG_E_ARG;
-    if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "alleles: k out of range (11 .. 31)");
-    if (!seq_off || (n_seqs && !values) || (n_variants && !genes)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = kmer_check_seqs(ctx, "alleles", bases, seq_off, n_seqs, k)) return rc;
+    if ((n_seqs && !values) || (n_variants && !genes)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (n_variants >= 0x7FFFFFFFu) return bdg_fail(ctx, BDG_E_ARG, "alleles: too many variants");
     for (uint32_t v = 0; v < n_variants; ++v)
         if (genes[v] >= n_features) return bdg_fail(ctx, BDG_E_ARG, "alleles: gene of a variant out of range (>= n_features)");
-    for (uint32_t q = 0; q < n_seqs; ++q) {
-        if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "alleles: sequence offsets must be non-decreasing");
+    for (uint32_t q = 0; q < n_seqs; ++q)
         if (values[q] >= 2u * n_variants) return bdg_fail(ctx, BDG_E_ARG, "alleles: value out of range (>= 2 * n_variants)");
-    }
-    const uint64_t end = seq_off[n_seqs];
-    if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    const uint64_t windows = kmer_windows(bases, seq_off, n_seqs, k), slots = kmer_slots(windows);
-    const uint32_t shift = kmer_shift(slots);
     std::vector<uint8_t> has((size_t)n_features + 1, 0);
     for (uint32_t v = 0; v < n_variants; ++v) has[genes[v]] = 1;
     hipStream_t st = ctx->stream;
     // the sequences, their offsets and values, the variants' genes and the counters live for this call only
     DevBuf d_bases, d_meta;
     const size_t n_values = 2 * (size_t)n_variants;
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), val_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u,
-                 gene_b = (sizeof(uint32_t) * (size_t)n_variants + 7u) & ~(size_t)7u, stat_b = 4 * sizeof(uint64_t),
-                 kpv_b = sizeof(uint32_t) * n_values;
     std::vector<uint32_t> kpv(n_values, 0);
-    auto run = [&](unsigned long long* h_stats) -> int {
+    auto run = [&](const KmerBuild& B) -> int {
+        KmerSeqs S;
         int rc;
-        if ((rc = bdg_reserve(ctx, ctx->al_has, has.size())) || (rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) ||
-            (rc = bdg_reserve(ctx, d_meta, off_b + val_b + gene_b + stat_b + kpv_b + 8)))
+        // the caller's bytes: the keys per value, counted from zero like the four figures, then the variants' genes
+        if ((rc = bdg_reserve(ctx, ctx->al_has, has.size())) ||
+            (rc = kmer_stage_seqs(ctx, d_bases, d_meta, bases, seq_off, n_seqs, values, sizeof(uint32_t) * (n_values + n_variants), S)))
             return rc;
-        char* meta = static_cast<char*>(d_meta.p);
-        auto* d_off = reinterpret_cast<uint64_t*>(meta);
-        auto* d_val = reinterpret_cast<uint32_t*>(meta + off_b);
-        auto* d_gene = reinterpret_cast<uint32_t*>(meta + off_b + val_b);
-        auto* d_stats = reinterpret_cast<unsigned long long*>(meta + off_b + val_b + gene_b);
-        auto* d_kpv = reinterpret_cast<uint32_t*>(meta + off_b + val_b + gene_b + stat_b);
-        if (end > seq_off[0])
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
-        if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_val, values, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
+        auto* d_kpv = static_cast<uint32_t*>(S.d_extra);
+        uint32_t* d_gene = d_kpv + n_values;
         if (n_variants) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_gene, genes, sizeof(uint32_t) * (size_t)n_variants, hipMemcpyHostToDevice, st));
         BDG_HIP_TRY(ctx, hipMemcpyAsync(ctx->al_has.p, has.data(), has.size(), hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, stat_b + kpv_b, st));
-        if (n_seqs) {
-            ScopedKernelTimer tm(ctx, "k_alleles_insert");
-            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * ALLELES_INSERT_WAVES_PER_CU);
-            hipLaunchKernelGGL(k_alleles_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_val, d_gene,
-                               n_seqs, k, static_cast<GeneSlot*>(ctx->al_table.p), slots - 1, shift);
-        }
-        {
-            ScopedKernelTimer tm(ctx, "k_alleles_stats");
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->cus * 8);
-            hipLaunchKernelGGL(k_alleles_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->al_table.p), slots, shift,
-                               d_stats, d_kpv, (uint32_t)n_values);
-        }
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, stat_b, hipMemcpyDeviceToHost, st));
-        if (n_values) BDG_HIP_TRY(ctx, hipMemcpyAsync(kpv.data(), d_kpv, kpv_b, hipMemcpyDeviceToHost, st));
+        if (n_seqs)
+            kmer_insert_launch(ctx, k_alleles_insert, "k_alleles_insert", n_seqs, S.d_bases, S.d_off, S.d_per_seq, static_cast<const uint32_t*>(d_gene),
+                               n_seqs, k, B.table, B.mask(), B.shift);
+        if ((rc = kmer_stats_launch(ctx, k_alleles_stats, "k_alleles_stats", B, S.d_stats, d_kpv, (uint32_t)n_values))) return rc;
+        if (n_values) BDG_HIP_TRY(ctx, hipMemcpyAsync(kpv.data(), d_kpv, sizeof(uint32_t) * n_values, hipMemcpyDeviceToHost, st));
         return BDG_OK;
     };
-    if (int rc = kmer_table_build(ctx, ctx->al_table, windows, slots, ctx->al_stats, [&] { alleles_drop(ctx); }, run)) return rc;
+    auto drop_rest = [&] {
+        ctx->al_has.reset();
+        ctx->al_features = 0;
+        ctx->al_keys_per_value.clear();
+    };
+    if (int rc = kmer_table_build(ctx, ctx->al, bases, seq_off, n_seqs, k, drop_rest, run)) return rc;
     ctx->al_keys_per_value.swap(kpv);
-    ctx->al_k = k;
     ctx->al_features = n_features;
-    ctx->al_slots = slots;
     return BDG_OK;
 }
 
@@ -279,7 +212,7 @@ int bdg_alleles_index_stats(bdg_ctx* ctx, uint64_t out[6], uint32_t* keys_per_va
     if (!ctx) return BDG_E_ARG;
     if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rc = alleles_check_assign(ctx)) return rc;
-    memcpy(out, ctx->al_stats, sizeof(ctx->al_stats));
+    memcpy(out, ctx->al.stats, sizeof(ctx->al.stats));
     if (keys_per_value && !ctx->al_keys_per_value.empty())
         memcpy(keys_per_value, ctx->al_keys_per_value.data(), sizeof(uint32_t) * ctx->al_keys_per_value.size());
     return BDG_OK;
@@ -325,14 +258,7 @@ int bdg_alleles_assign(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, 
     auto* d_out = reinterpret_cast<bdg_allele_rec*>(static_cast<char*>(S.d_out) + cnt_b);
     BDG_HIP_TRY(ctx, hipMemcpyAsync(d_genes, gene_recs, gene_b, hipMemcpyHostToDevice, st));
     if ((rc = alleles_assign_launch(ctx, S.d_bases, S.d_off, n, d_genes, d_out, cap, d_counts))) return rc;
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(counts, d_counts, cnt_b, hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (counts[0] > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "alleles: " + std::to_string(counts[0]) + " records, more than the capacity");
-    if (counts[0]) {
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(bdg_allele_rec) * (size_t)counts[0], hipMemcpyDeviceToHost, st));
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return BDG_OK;
+    return kmer_emit_records(ctx, d_counts, counts, 2, d_out, sizeof(bdg_allele_rec), cap, out, "alleles");
 }
 
 }  // extern "C"

@@ -35,6 +35,22 @@ struct KTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// home_slot's shift for a k-mer table of `slots` slots (a power of two): the top log2(slots) bits of the product
+static inline uint32_t kmer_shift(uint64_t slots) { return 64u - (uint32_t)__builtin_ctzll(slots); }
+
+// A k-mer table a context holds (genes_probe.hpp: its slots, its build, its probe).  kmer_table_build publishes k and slots,
+// which is what makes the index exist; what a table owns besides stays beside it in the context.
+struct KmerTable {
+    DevBuf table;        // `slots` slots of 16 bytes
+    uint64_t slots = 0;  // a power of two; 0: no index
+    uint32_t k = 0;
+    uint64_t stats[6] = { 0, 0, 0, 0, 0, 0 };   // windows | keys | ambiguous keys | slots | longest run | keys in front of their home
+    uint64_t mask() const { return slots - 1; }
+    uint32_t shift() const { return kmer_shift(slots); }
+    bool built() const { return slots != 0; }
+    void drop() { table.reset(); slots = 0; k = 0; }
+};
+
 struct bdg_ctx {
     int device = 0;
     int cus = 0;                            // compute units of the device: bdg_cus() asks on first use
@@ -149,10 +165,7 @@ struct bdg_ctx {
     DevBuf c_trace;      // direction bits, 16 * c_band / 64 bytes per member row and wave in flight
     uint32_t c_band = BDG_CONS_BAND_DEFAULT;   // bdg_consensus_set_band: diagonals of the alignment's band, 64, 128 or 256
     // ---- gene index (genes_kernels.hip): held like the whitelist, replaced by the next bdg_genes_index_build
-    DevBuf gn_table;     // gn_slots slots of {u64 key, u32 value, u32 pad}
-    uint64_t gn_slots = 0;                   // a power of two; 0: no index
-    uint32_t gn_k = 0;
-    uint64_t gn_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_genes_index_stats
+    KmerTable gn;        // slots of {u64 key, u32 value, u32 pad}; its figures: bdg_genes_index_stats
     int gn_assign_per_cu = 0;                // blocks of k_genes_assign resident on a compute unit (asked once)
     DevBuf gn_mask;      // u64 per slot: the transcripts of its gene that hold the slot's key (bdg_genes_index_build_iso only)
     int gn_iso_per_cu = 0;                   // blocks of k_iso_assign resident on a compute unit (asked once)
@@ -160,22 +173,17 @@ struct bdg_ctx {
     DevBuf gn_spans;     // the spans of the chunk bdg_extract_collect computes kept gene records for (grow-only)
     // ---- allele index (alleles_kernels.hip): a second table of the same slots with its own k, replaced by the next
     // bdg_alleles_index_build; building one table does not touch the other
-    DevBuf al_table;     // al_slots slots of {u64 key, u32 value, u32 gene}
+    KmerTable al;        // slots of {u64 key, u32 value, u32 gene}; its figures: bdg_alleles_index_stats
     DevBuf al_has;       // u8 per feature: the gene has a variant
-    uint64_t al_slots = 0;                   // a power of two; 0: no allele index
-    uint32_t al_k = 0, al_features = 0;
-    uint64_t al_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_alleles_index_stats
+    uint32_t al_features = 0;
     std::vector<uint32_t> al_keys_per_value;       // ... [2 * n_variants]
     int al_assign_per_cu = 0;                // blocks of k_alleles_assign resident on a compute unit (asked once)
     // ---- site index and pileup (discover_kernels.hip): a third table of the same slots with its own k, the slot's fourth word
     // the smallest site of its key; replaced by the next bdg_sites_index_build, which touches neither of the other two
-    DevBuf st_table;     // st_slots slots of {u64 key, u32 gene, u32 site}
+    KmerTable st;        // slots of {u64 key, u32 gene, u32 site}; its figures: bdg_sites_index_stats
     DevBuf st_bases;     // the transcripts' bases as the build got them, u8 [st_sites]: k_sites_select reads the reference letter
     DevBuf st_counts;    // u32 [st_sites][4]: the pileup, accumulated over the calls since the build or bdg_sites_reset
-    uint64_t st_slots = 0;                   // a power of two; 0: no site index
     uint64_t st_sites = 0;                   // seq_off[n_seqs] of the build: sites are 0 .. st_sites - 1
-    uint32_t st_k = 0;
-    uint64_t st_stats[6] = { 0, 0, 0, 0, 0, 0 };   // bdg_sites_index_stats
     int st_pileup_per_cu = 0;                // blocks of k_sites_pileup resident on a compute unit (asked once)
     int em_per_cu = 0;                      // em_kernels.hip: blocks of k_em_tcc resident on a compute unit (asked once)
     int donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores

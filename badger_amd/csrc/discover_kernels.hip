@@ -2,13 +2,13 @@
 // bdg_sites_index_build states the rule; badger_amd/discover.py restates it).  gfx950.
 //
 // A third table of genes_kernels.hip's slots holds every window of k bases of the transcripts with its gene and, in the slot's
-// fourth word, the smallest site at which it starts.  The planes, the keys, insert_key and the probe are genes_probe.hpp's, used
-// as they stand: one wave per sequence, persistent, a lane per window, three ballots per 64 bases.
+// fourth word, the smallest site at which it starts.  The planes, the keys, insert_key, the walk, the stats pass and the probe
+// are genes_probe.hpp's, used as they stand: one wave per sequence, persistent, a lane per window, three ballots per 64 bases.
 //
-// k_sites_insert   insert_key plus an unsigned atomicMin of the window's site on the fourth word, which the 0xFF clearing of the
-//                  build leaves at the maximum.  As in k_alleles_insert a lane whose left neighbour holds the same key does nothing:
-//                  the neighbour inserts the same key for the same feature, and its site is the smaller one.
-// k_sites_stats    the six occupancy figures of k_genes_stats.
+// k_sites_insert   kmer_walk with, per key, insert_key plus an unsigned atomicMin of the window's site on the fourth word, which
+//                  the 0xFF clearing of the build leaves at the maximum.  The walk hands no key to a lane whose left neighbour
+//                  holds the same: the neighbour inserts the same key for the same feature, and its site is the smaller one.
+// k_sites_stats    kmer_stats, the six occupancy figures.
 // k_sites_pileup   a read whose gene record is not ASSIGNED costs its gene record and nothing else.  The others are walked like
 //                  k_genes_assign walks them.  A lane holds, for its window of chunk c, the site its key resolves to in the read's
 //                  own gene, or SITE_NONE.  The partner of window w is window w + k + 1: k + 1 <= 32 lanes further on, in chunk c
@@ -29,70 +29,35 @@
 
 namespace {
 
-constexpr uint32_t SITES_INSERT_WAVES_PER_CU = 16;
 constexpr uint32_t SITE_NONE = 0xFFFFFFFFu;
 
 static_assert(sizeof(bdg_site_rec) == 32 && sizeof(uint4) == 16, "a record is two 16-byte stores");
 static_assert(BDG_GENES_K_MAX + 1 <= 32 && 64 * GENES_CHUNKS > 2 * (BDG_GENES_K_MAX + 1),
               "a partner lies in its anchor's chunk or the next, and a step advances");
 
+// what k_sites_insert does with a key: its left neighbour, where it holds the same key, inserts it at a smaller site
+struct SitesInsert {
+    const uint32_t* __restrict__ features; GeneSlot* table; uint64_t mask; uint32_t shift;
+    __device__ __forceinline__ uint32_t seq(uint32_t q) const { return features[q]; }   // (the host has checked the features)
+    __device__ __forceinline__ void window(uint32_t f, unsigned long long key, uint64_t site) const
+    {
+        if (key == KEY_EMPTY) return;
+        const uint64_t at = insert_key(table, mask, shift, key, f);
+        atomicMin(&table[at].pad, (uint32_t)site);
+    }
+};
+
 __global__ __launch_bounds__(64)
 void k_sites_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ features,
                     uint32_t n_seqs, uint32_t k, GeneSlot* table, uint64_t mask, uint32_t shift)
 {
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
-        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets and the features)
-        if (len < k) continue;
-        const uint8_t* s = bases + b;
-        const uint32_t f = features[q];
-        Planes A = load_planes(s, len, 0, lane);
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
-            const Planes B = load_planes(s, len, p0 + 64, lane);
-            unsigned long long key = window_key(A, B, lane, kmask);
-            const unsigned long long left = __shfl_up(key, 1);
-            if (lane && left == key) key = KEY_EMPTY;               // its left neighbour inserts the same key, at a smaller site
-            if (key != KEY_EMPTY) {
-                const uint64_t at = insert_key(table, mask, shift, key, f);
-                atomicMin(&table[at].pad, (uint32_t)(b + p0 + lane));
-            }
-            A = B;
-        }
-    }
+    kmer_walk(bases, seq_off, n_seqs, k, SitesInsert{ features, table, mask, shift });
 }
 
-// out: distinct keys | ambiguous keys | longest run of occupied slots | keys in front of their home slot
-__global__ __launch_bounds__(256)
+__global__ __launch_bounds__(KMER_STATS_THREADS)
 void k_sites_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t shift, unsigned long long* out)
 {
-    __shared__ unsigned long long sh[4];
-    if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t mask = slots - 1;
-    unsigned long long distinct = 0, amb = 0, run_max = 0, wrapped = 0;
-    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long key = table[s].key;
-        if (key == KEY_EMPTY) continue;
-        ++distinct;
-        amb += table[s].value == BDG_GENES_AMBIGUOUS;
-        wrapped += home_slot(key, shift) > s;
-        if (table[(s - 1) & mask].key == KEY_EMPTY) {               // a run starts here (there is always an empty slot: it ends)
-            unsigned long long run = 1;
-            for (uint64_t t = (s + 1) & mask; table[t].key != KEY_EMPTY; t = (t + 1) & mask) ++run;
-            run_max = run > run_max ? run : run_max;
-        }
-    }
-    if (distinct) atomicAdd(&sh[0], distinct);
-    if (amb) atomicAdd(&sh[1], amb);
-    if (run_max) atomicMax(&sh[2], run_max);
-    if (wrapped) atomicAdd(&sh[3], wrapped);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (sh[0]) atomicAdd(&out[0], sh[0]);
-        if (sh[1]) atomicAdd(&out[1], sh[1]);
-        if (sh[2]) atomicMax(&out[2], sh[2]);
-        if (sh[3]) atomicAdd(&out[3], sh[3]);
-    }
+    kmer_stats(table, slots, shift, out, [](uint32_t) {});
 }
 
 // counts: [n_sites][4].  Every add lands on a site in front of a stored one (site(i) + k == site(i + k + 1) - 1 < n_sites).
@@ -172,28 +137,14 @@ void k_sites_select(const uint8_t* __restrict__ bases, const uint4* __restrict__
     }
 }
 
-int sites_check(bdg_ctx* ctx)
-{
-    if (ctx->st_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "sites: no index built (bdg_sites_index_build)");
-    return BDG_OK;
-}
+int sites_check(bdg_ctx* ctx) { return kmer_check_built(ctx, ctx->st, "sites: no index built (bdg_sites_index_build)"); }
 
 int sites_pileup_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes)
 {
     if (n == 0) return BDG_OK;
-    return bdg_resident_launch(ctx, k_sites_pileup, ctx->st_pileup_per_cu, "k_sites_pileup", n, d_bases, d_off, n, ctx->st_k, d_genes,
-                               static_cast<const GeneSlot*>(ctx->st_table.p), ctx->st_slots - 1, kmer_shift(ctx->st_slots),
+    return bdg_resident_launch(ctx, k_sites_pileup, ctx->st_pileup_per_cu, "k_sites_pileup", n, d_bases, d_off, n, ctx->st.k, d_genes,
+                               static_cast<const GeneSlot*>(ctx->st.table.p), ctx->st.mask(), ctx->st.shift(),
                                static_cast<uint32_t*>(ctx->st_counts.p));
-}
-
-void sites_drop(bdg_ctx* ctx)
-{
-    ctx->st_table.reset();
-    ctx->st_bases.reset();
-    ctx->st_counts.reset();
-    ctx->st_slots = 0;
-    ctx->st_sites = 0;
-    ctx->st_k = 0;
 }
 
 }  // namespace
@@ -204,57 +155,31 @@ int bdg_sites_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* se
                           uint32_t k)
 {
     if (!ctx) return BDG_E_ARG;
-    if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "sites: k out of range (11 .. 31)");
-    if (!seq_off || (n_seqs && !features)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    for (uint32_t q = 0; q < n_seqs; ++q) {
-        if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "sites: sequence offsets must be non-decreasing");
+    if (int rc = kmer_check_seqs(ctx, "sites", bases, seq_off, n_seqs, k)) return rc;
+    if (n_seqs && !features) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    for (uint32_t q = 0; q < n_seqs; ++q)
         if (features[q] >= BDG_GENES_AMBIGUOUS) return bdg_fail(ctx, BDG_E_ARG, "sites: feature id reserved or out of range");
-    }
     const uint64_t end = seq_off[n_seqs];
     if (end >= BDG_SITES_MAX) return bdg_fail(ctx, BDG_E_ARG, "sites: 2^32 - 1 bases or more (a site is a uint32)");
-    if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    const uint64_t windows = kmer_windows(bases, seq_off, n_seqs, k), slots = kmer_slots(windows);
-    const uint32_t shift = kmer_shift(slots);
     hipStream_t st = ctx->stream;
-    // the offsets, the features and the counters live for this call only; the bases and the counts stay with the table
-    DevBuf d_meta;
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), feat_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u,
-                 stat_b = 4 * sizeof(uint64_t);
-    auto run = [&](unsigned long long* h_stats) -> int {
+    DevBuf d_meta;   // the offsets, the features and the counters live for this call only; the bases and the counts stay with the table
+    auto run = [&](const KmerBuild& B) -> int {
+        KmerSeqs S;
         int rc;
-        if ((rc = bdg_reserve(ctx, ctx->st_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, ctx->st_counts, 16 * (size_t)end + 16)) ||
-            (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + stat_b + 8)))
-            return rc;
-        char* meta = static_cast<char*>(d_meta.p);
-        auto* d_off = reinterpret_cast<uint64_t*>(meta);
-        auto* d_feat = reinterpret_cast<uint32_t*>(meta + off_b);
-        auto* d_stats = reinterpret_cast<unsigned long long*>(meta + off_b + feat_b);
+        if ((rc = bdg_reserve(ctx, ctx->st_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, ctx->st_counts, 16 * (size_t)end + 16))) return rc;
         BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->st_bases.p, 'N', (size_t)end + 1, st));      // (in front of seq_off[0]: no letter)
         BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->st_counts.p, 0, 16 * (size_t)end + 16, st));
-        if (end > seq_off[0])
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(ctx->st_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
-        if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_feat, features, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, stat_b, st));
-        if (n_seqs) {
-            ScopedKernelTimer tm(ctx, "k_sites_insert");
-            const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * SITES_INSERT_WAVES_PER_CU);
-            hipLaunchKernelGGL(k_sites_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(ctx->st_bases.p), d_off, d_feat,
-                               n_seqs, k, static_cast<GeneSlot*>(ctx->st_table.p), slots - 1, shift);
-        }
-        {
-            ScopedKernelTimer tm(ctx, "k_sites_stats");
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->cus * 8);
-            hipLaunchKernelGGL(k_sites_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->st_table.p), slots, shift,
-                               d_stats);
-        }
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, stat_b, hipMemcpyDeviceToHost, st));
-        return BDG_OK;
+        if ((rc = kmer_stage_seqs(ctx, ctx->st_bases, d_meta, bases, seq_off, n_seqs, features, 0, S))) return rc;
+        if (n_seqs) kmer_insert_launch(ctx, k_sites_insert, "k_sites_insert", n_seqs, S.d_bases, S.d_off, S.d_per_seq, n_seqs, k, B.table, B.mask(), B.shift);
+        return kmer_stats_launch(ctx, k_sites_stats, "k_sites_stats", B, S.d_stats);
     };
-    if (int rc = kmer_table_build(ctx, ctx->st_table, windows, slots, ctx->st_stats, [&] { sites_drop(ctx); }, run)) return rc;
-    ctx->st_k = k;
+    auto drop_rest = [&] {
+        ctx->st_bases.reset();
+        ctx->st_counts.reset();
+        ctx->st_sites = 0;
+    };
+    if (int rc = kmer_table_build(ctx, ctx->st, bases, seq_off, n_seqs, k, drop_rest, run)) return rc;
     ctx->st_sites = end;
-    ctx->st_slots = slots;
     return BDG_OK;
 }
 
@@ -263,7 +188,7 @@ int bdg_sites_index_stats(bdg_ctx* ctx, uint64_t out[6])
     if (!ctx) return BDG_E_ARG;
     if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     if (int rc = sites_check(ctx)) return rc;
-    memcpy(out, ctx->st_stats, sizeof(ctx->st_stats));
+    memcpy(out, ctx->st.stats, sizeof(ctx->st.stats));
     return BDG_OK;
 }
 
@@ -331,14 +256,7 @@ int bdg_sites_select(bdg_ctx* ctx, uint32_t min_alt, uint32_t ppm, bdg_site_rec*
                            static_cast<const uint4*>(ctx->st_counts.p), ctx->st_sites, min_alt, ppm, d_out, cap, d_cursor);
     }
     BDG_HIP_TRY(ctx, hipGetLastError());
-    BDG_HIP_TRY(ctx, hipMemcpyAsync(count, d_cursor, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (*count > cap) return bdg_fail(ctx, BDG_E_CAPACITY, "sites: " + std::to_string(*count) + " records, more than the capacity");
-    if (*count) {
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(bdg_site_rec) * (size_t)*count, hipMemcpyDeviceToHost, st));
-        BDG_HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return BDG_OK;
+    return kmer_emit_records(ctx, d_cursor, count, 1, d_out, sizeof(bdg_site_rec), cap, out, "sites");
 }
 
 int bdg_sites_counts_to_host(bdg_ctx* ctx, uint32_t* out, uint64_t n_sites)

@@ -28,8 +28,9 @@
 //                  reverse-complemented: the same bodies, only the byte a lane loads differs.  k_cdna_spans makes
 //                  the intervals from a chunk's extraction, trim and chimera records.
 //
-// The slot, the planes, the keys, insert_key and the probe macro GENES_PROBE_CHUNKS are in genes_probe.hpp, which
-// alleles_kernels.hip includes too.
+// The slot, the planes, the keys, insert_key, the walk of the insert kernels (kmer_walk), the pass of the stats kernel
+// (kmer_stats) and the probe macro GENES_PROBE_CHUNKS are in genes_probe.hpp, which alleles_kernels.hip and discover_kernels.hip
+// include too.
 #include "bdg_common.hpp"
 #include "bdg_launchers.hpp"
 #include "genes_probe.hpp"
@@ -37,8 +38,6 @@
 #include <algorithm>
 
 namespace {
-
-constexpr uint32_t INSERT_WAVES_PER_CU = 16;                  // (k_genes_assign: as many as the device keeps resident, asked once)
 
 static_assert(sizeof(GeneSlot) == 16 && sizeof(bdg_gene_rec) == 24 && sizeof(bdg_iso_rec) == 32 && sizeof(bdg_cdna_span) == 12,
               "layouts the header states");
@@ -72,60 +71,27 @@ struct Span {
     }
 };
 
+// what k_genes_insert does with a key: its left neighbour, where it holds the same key, inserts it for the same feature
+struct GenesInsert {
+    const uint32_t* __restrict__ features; GeneSlot* table; uint64_t mask; uint32_t shift;
+    __device__ __forceinline__ uint32_t seq(uint32_t q) const { return features[q]; }
+    __device__ __forceinline__ void window(uint32_t f, unsigned long long key, uint64_t) const
+    {
+        if (key != KEY_EMPTY) insert_key(table, mask, shift, key, f);
+    }
+};
+
 __global__ __launch_bounds__(64)
 void k_genes_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ features,
                     uint32_t n_seqs, uint32_t k, GeneSlot* table, uint64_t mask, uint32_t shift)
 {
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
-        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets)
-        if (len < k) continue;
-        const uint8_t* s = bases + b;
-        const uint32_t f = features[q];
-        Planes A = load_planes(s, len, 0, lane);
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
-            const Planes B = load_planes(s, len, p0 + 64, lane);
-            unsigned long long key = window_key(A, B, lane, kmask);
-            const unsigned long long left = __shfl_up(key, 1);
-            if (lane && left == key) key = KEY_EMPTY;               // its left neighbour inserts the same key for the same feature
-            if (key != KEY_EMPTY) insert_key(table, mask, shift, key, f);
-            A = B;
-        }
-    }
+    kmer_walk(bases, seq_off, n_seqs, k, GenesInsert{ features, table, mask, shift });
 }
 
-// out: distinct keys | ambiguous keys | longest run of occupied slots | keys in front of their home slot
-__global__ __launch_bounds__(256)
+__global__ __launch_bounds__(KMER_STATS_THREADS)
 void k_genes_stats(const GeneSlot* __restrict__ table, uint64_t slots, uint32_t shift, unsigned long long* out)
 {
-    __shared__ unsigned long long sh[4];
-    if (threadIdx.x < 4) sh[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t mask = slots - 1;
-    unsigned long long distinct = 0, amb = 0, run_max = 0, wrapped = 0;
-    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long key = table[s].key;
-        if (key == KEY_EMPTY) continue;
-        ++distinct;
-        amb += table[s].value == BDG_GENES_AMBIGUOUS;
-        wrapped += home_slot(key, shift) > s;
-        if (table[(s - 1) & mask].key == KEY_EMPTY) {               // a run starts here (there is always an empty slot: it ends)
-            unsigned long long run = 1;
-            for (uint64_t t = (s + 1) & mask; table[t].key != KEY_EMPTY; t = (t + 1) & mask) ++run;
-            run_max = run > run_max ? run : run_max;
-        }
-    }
-    if (distinct) atomicAdd(&sh[0], distinct);
-    if (amb) atomicAdd(&sh[1], amb);
-    if (run_max) atomicMax(&sh[2], run_max);
-    if (wrapped) atomicAdd(&sh[3], wrapped);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (sh[0]) atomicAdd(&out[0], sh[0]);
-        if (sh[1]) atomicAdd(&out[1], sh[1]);
-        if (sh[2]) atomicMax(&out[2], sh[2]);
-        if (sh[3]) atomicAdd(&out[3], sh[3]);
-    }
+    kmer_stats(table, slots, shift, out, [](uint32_t) {});
 }
 
 // The body of k_genes_assign (READ = Whole) and k_genes_assign_spans (READ = Span), stated once.  A macro and not an inlined
@@ -230,42 +196,37 @@ void k_genes_assign_spans(const uint8_t* __restrict__ bases, const uint64_t* __r
 //                whose value is that gene - all four chunks' gathers before one is used.  Lane t owns cnt[t]; the loop over
 //                the distinct words of a chunk (first live lane's word, ballot of its equals, popcount) adds the count to
 //                every lane whose bit the word has: one round where the read lies in shared exons.  No LDS, no barrier.
+struct IsoInsert {
+    const uint8_t* __restrict__ local; const GeneSlot* table; unsigned long long* tx_mask; uint64_t mask; uint32_t shift;
+    __device__ __forceinline__ unsigned long long seq(uint32_t q) const { return 1ull << (local[q] & 63u); }   // (the host: local[q] <= 63)
+    __device__ __forceinline__ void window(unsigned long long bit, unsigned long long key, uint64_t) const
+    {
+        const uint32_t lane = threadIdx.x;
+        uint64_t at = 0;
+        bool need = false;
+        if (key != KEY_EMPTY) {
+            at = home_slot(key, shift);
+            unsigned long long cur;
+            while ((cur = table[at].key) != key && cur != KEY_EMPTY) at = (at + 1) & mask;   // (k_genes_insert stored it: found)
+            need = cur == key && !(__hip_atomic_load(&tx_mask[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit);
+        }
+        bool lead = false;
+        uint64_t live = __ballot(need);
+        while (live) {                                              // one round per distinct key that still lacks the bit
+            const uint32_t first = __ffsll((unsigned long long)live) - 1;
+            const unsigned long long kk = __shfl(key, first);
+            lead |= lane == first;
+            live &= ~__ballot(need && key == kk);
+        }
+        if (lead) atomicOr(&tx_mask[at], bit);
+    }
+};
+
 __global__ __launch_bounds__(64)
 void k_iso_insert(const uint8_t* __restrict__ bases, const uint64_t* __restrict__ seq_off, const uint8_t* __restrict__ local,
                   uint32_t n_seqs, uint32_t k, const GeneSlot* table, unsigned long long* tx_mask, uint64_t mask, uint32_t shift)
 {
-    const uint32_t lane = threadIdx.x, kmask = (1u << k) - 1u;
-    for (uint32_t q = blockIdx.x; q < n_seqs; q += gridDim.x) {
-        const uint64_t b = seq_off[q], len = seq_off[q + 1] - b;    // (the host has checked the offsets, and local[q] <= 63)
-        if (len < k) continue;
-        const uint8_t* s = bases + b;
-        const unsigned long long bit = 1ull << (local[q] & 63u);
-        Planes A = load_planes(s, len, 0, lane);
-        for (uint64_t p0 = 0; p0 + k <= len; p0 += 64) {
-            const Planes B = load_planes(s, len, p0 + 64, lane);
-            unsigned long long key = window_key(A, B, lane, kmask);
-            const unsigned long long left = __shfl_up(key, 1);
-            if (lane && left == key) key = KEY_EMPTY;
-            uint64_t at = 0;
-            bool need = false;
-            if (key != KEY_EMPTY) {
-                at = home_slot(key, shift);
-                unsigned long long cur;
-                while ((cur = table[at].key) != key && cur != KEY_EMPTY) at = (at + 1) & mask;   // (k_genes_insert stored it: found)
-                need = cur == key && !(__hip_atomic_load(&tx_mask[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit);
-            }
-            bool lead = false;
-            uint64_t live = __ballot(need);
-            while (live) {                                          // one round per distinct key that still lacks the bit
-                const uint32_t first = __ffsll((unsigned long long)live) - 1;
-                const unsigned long long kk = __shfl(key, first);
-                lead |= lane == first;
-                live &= ~__ballot(need && key == kk);
-            }
-            if (lead) atomicOr(&tx_mask[at], bit);
-            A = B;
-        }
-    }
+    kmer_walk(bases, seq_off, n_seqs, k, IsoInsert{ local, table, tx_mask, mask, shift });
 }
 
 // The body of k_iso_assign (READ = Whole) and k_iso_assign_spans (READ = Span), a macro for the same reason.  It names the
@@ -364,16 +325,18 @@ void k_cdna_spans(const uint64_t* __restrict__ off, uint32_t n, const bdg_extrac
     out[i] = sp;
 }
 
+int genes_check_built(bdg_ctx* ctx) { return kmer_check_built(ctx, ctx->gn, "genes: no index built (bdg_genes_index_build)"); }
+
 int genes_check_assign(bdg_ctx* ctx, uint32_t min_hits)
 {
-    if (ctx->gn_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: no index built (bdg_genes_index_build)");
+    if (int rc = genes_check_built(ctx)) return rc;
     if (min_hits == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: min_hits must be at least 1");
     return BDG_OK;
 }
 
 int iso_check_assign(bdg_ctx* ctx, uint32_t margin)
 {
-    if (ctx->gn_slots == 0 || !ctx->gn_mask.p) return bdg_fail(ctx, BDG_E_ARG, "isoforms: no index with masks built (bdg_genes_index_build_iso)");
+    if (!ctx->gn.built() || !ctx->gn_mask.p) return bdg_fail(ctx, BDG_E_ARG, "isoforms: no index with masks built (bdg_genes_index_build_iso)");
     if (margin == 0) return bdg_fail(ctx, BDG_E_ARG, "isoforms: margin must be at least 1");
     return BDG_OK;
 }
@@ -381,32 +344,32 @@ int iso_check_assign(bdg_ctx* ctx, uint32_t margin)
 // The four assign launches: one wave per read as bdg_resident_launch deals them out, each kernel with its own resident figure.
 int genes_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, uint32_t min_hits, bdg_gene_rec* d_out)
 {
-    return bdg_resident_launch(ctx, k_genes_assign, ctx->gn_assign_per_cu, "k_genes_assign", n, d_bases, d_off, n, ctx->gn_k, min_hits,
-                               static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
+    return bdg_resident_launch(ctx, k_genes_assign, ctx->gn_assign_per_cu, "k_genes_assign", n, d_bases, d_off, n, ctx->gn.k, min_hits,
+                               static_cast<const GeneSlot*>(ctx->gn.table.p), ctx->gn.mask(), ctx->gn.shift(), d_out);
 }
 
 int iso_assign_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_gene_rec* d_genes, uint32_t margin,
                       bdg_iso_rec* d_out)
 {
-    return bdg_resident_launch(ctx, k_iso_assign, ctx->gn_iso_per_cu, "k_iso_assign", n, d_bases, d_off, n, ctx->gn_k, d_genes, margin,
-                               static_cast<const GeneSlot*>(ctx->gn_table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
-                               ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
+    return bdg_resident_launch(ctx, k_iso_assign, ctx->gn_iso_per_cu, "k_iso_assign", n, d_bases, d_off, n, ctx->gn.k, d_genes, margin,
+                               static_cast<const GeneSlot*>(ctx->gn.table.p), static_cast<const unsigned long long*>(ctx->gn_mask.p),
+                               ctx->gn.mask(), ctx->gn.shift(), d_out);
 }
 
 int genes_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
                               uint32_t min_hits, bdg_gene_rec* d_out)
 {
     return bdg_resident_launch(ctx, k_genes_assign_spans, ctx->gn_assign_sp_per_cu, "k_genes_assign_spans", n, d_bases, d_off, d_spans, n,
-                               ctx->gn_k, min_hits, static_cast<const GeneSlot*>(ctx->gn_table.p), ctx->gn_slots - 1,
-                               kmer_shift(ctx->gn_slots), d_out);
+                               ctx->gn.k, min_hits, static_cast<const GeneSlot*>(ctx->gn.table.p), ctx->gn.mask(),
+                               ctx->gn.shift(), d_out);
 }
 
 int iso_assign_spans_launch(bdg_ctx* ctx, const uint8_t* d_bases, const uint64_t* d_off, uint32_t n, const bdg_cdna_span* d_spans,
                             const bdg_gene_rec* d_genes, uint32_t margin, bdg_iso_rec* d_out)
 {
     return bdg_resident_launch(ctx, k_iso_assign_spans, ctx->gn_iso_sp_per_cu, "k_iso_assign_spans", n, d_bases, d_off, d_spans, n,
-                               ctx->gn_k, d_genes, margin, static_cast<const GeneSlot*>(ctx->gn_table.p),
-                               static_cast<const unsigned long long*>(ctx->gn_mask.p), ctx->gn_slots - 1, kmer_shift(ctx->gn_slots), d_out);
+                               ctx->gn.k, d_genes, margin, static_cast<const GeneSlot*>(ctx->gn.table.p),
+                               static_cast<const unsigned long long*>(ctx->gn_mask.p), ctx->gn.mask(), ctx->gn.shift(), d_out);
 }
 
 int cdna_spans_launch(bdg_ctx* ctx, const uint64_t* d_off, uint32_t n, const bdg_extract_rec* d_recs, const bdg_trim_rec* d_trim,
@@ -423,69 +386,33 @@ int genes_index_build(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* seq_of
                       const uint8_t* local, bool with_masks, uint32_t k)
 {
     if (!ctx) return BDG_E_ARG;
-    if (k < BDG_GENES_K_MIN || k > BDG_GENES_K_MAX) return bdg_fail(ctx, BDG_E_ARG, "genes: k out of range (11 .. 31)");
-    if (!seq_off || (n_seqs && !features) || (with_masks && n_seqs && !local)) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
+    if (int rc = kmer_check_seqs(ctx, "genes", bases, seq_off, n_seqs, k)) return rc;
+    if (n_seqs && (!features || (with_masks && !local))) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
     for (uint32_t q = 0; q < n_seqs; ++q) {
-        if (seq_off[q + 1] < seq_off[q]) return bdg_fail(ctx, BDG_E_ARG, "genes: sequence offsets must be non-decreasing");
         if (features[q] >= BDG_GENES_AMBIGUOUS) return bdg_fail(ctx, BDG_E_ARG, "genes: feature id reserved (>= 0xFFFFFFFE)");
         if (with_masks && local[q] > BDG_ISO_LOCAL_MAX) return bdg_fail(ctx, BDG_E_ARG, "isoforms: local index above 63");
     }
-    const uint64_t end = seq_off[n_seqs];
-    if (end > seq_off[0] && !bases) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    const uint64_t windows = kmer_windows(bases, seq_off, n_seqs, k), slots = kmer_slots(windows);
-    const uint32_t shift = kmer_shift(slots);
     hipStream_t st = ctx->stream;
-    auto drop = [&] {
-        ctx->gn_table.reset();
-        ctx->gn_mask.reset();
-        ctx->gn_slots = 0;
-        ctx->gn_k = 0;
-    };
-    // the sequences, their offsets and features and the four counters live for this call only
-    DevBuf d_bases, d_meta, d_local;
-    const size_t off_b = sizeof(uint64_t) * ((size_t)n_seqs + 1), feat_b = (sizeof(uint32_t) * (size_t)n_seqs + 7u) & ~(size_t)7u;
-    auto run = [&](unsigned long long* h_stats) -> int {
+    DevBuf d_bases, d_meta, d_local;   // the sequences, their offsets and features and the four counters live for this call only
+    auto run = [&](const KmerBuild& B) -> int {
+        KmerSeqs S;
+        const size_t mask_b = sizeof(uint64_t) * (size_t)B.slots;
         int rc;
-        if ((rc = bdg_reserve(ctx, d_bases, (size_t)end + 1)) || (rc = bdg_reserve(ctx, d_meta, off_b + feat_b + 4 * sizeof(uint64_t)))) return rc;
+        if ((rc = kmer_stage_seqs(ctx, d_bases, d_meta, bases, seq_off, n_seqs, features, 0, S))) return rc;
         // the masks beside the table, and the local indices for this call, only where they are asked for
-        if (with_masks && ((rc = bdg_reserve(ctx, ctx->gn_mask, sizeof(uint64_t) * (size_t)slots)) || (rc = bdg_reserve(ctx, d_local, (size_t)n_seqs + 1))))
-            return rc;
-        auto* d_off = static_cast<uint64_t*>(d_meta.p);
-        auto* d_feat = reinterpret_cast<uint32_t*>(static_cast<char*>(d_meta.p) + off_b);
-        auto* d_stats = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_meta.p) + off_b + feat_b);
-        if (end > seq_off[0])
-            BDG_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(d_bases.p) + seq_off[0], bases + seq_off[0], (size_t)(end - seq_off[0]), hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, off_b, hipMemcpyHostToDevice, st));
-        if (n_seqs) BDG_HIP_TRY(ctx, hipMemcpyAsync(d_feat, features, sizeof(uint32_t) * (size_t)n_seqs, hipMemcpyHostToDevice, st));
-        BDG_HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 4 * sizeof(uint64_t), st));
-        const uint32_t waves = (uint32_t)std::min<uint64_t>(n_seqs, (uint64_t)ctx->cus * INSERT_WAVES_PER_CU);
-        if (n_seqs) {
-            ScopedKernelTimer tm(ctx, "k_genes_insert");
-            hipLaunchKernelGGL(k_genes_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off, d_feat, n_seqs, k,
-                               static_cast<GeneSlot*>(ctx->gn_table.p), slots - 1, shift);
-        }
+        if (with_masks && ((rc = bdg_reserve(ctx, ctx->gn_mask, mask_b)) || (rc = bdg_reserve(ctx, d_local, (size_t)n_seqs + 1)))) return rc;
+        if (n_seqs) kmer_insert_launch(ctx, k_genes_insert, "k_genes_insert", n_seqs, S.d_bases, S.d_off, S.d_per_seq, n_seqs, k, B.table, B.mask(), B.shift);
         if (with_masks) {
-            BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_mask.p, 0, sizeof(uint64_t) * (size_t)slots, st));
+            BDG_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_mask.p, 0, mask_b, st));
             if (n_seqs) {
                 BDG_HIP_TRY(ctx, hipMemcpyAsync(d_local.p, local, (size_t)n_seqs, hipMemcpyHostToDevice, st));
-                ScopedKernelTimer tm(ctx, "k_iso_insert");
-                hipLaunchKernelGGL(k_iso_insert, dim3(waves), dim3(64), 0, st, static_cast<const uint8_t*>(d_bases.p), d_off,
-                                   static_cast<const uint8_t*>(d_local.p), n_seqs, k, static_cast<const GeneSlot*>(ctx->gn_table.p),
-                                   static_cast<unsigned long long*>(ctx->gn_mask.p), slots - 1, shift);
+                kmer_insert_launch(ctx, k_iso_insert, "k_iso_insert", n_seqs, S.d_bases, S.d_off, static_cast<const uint8_t*>(d_local.p), n_seqs, k,
+                                   static_cast<const GeneSlot*>(B.table), static_cast<unsigned long long*>(ctx->gn_mask.p), B.mask(), B.shift);
             }
         }
-        {
-            ScopedKernelTimer tm(ctx, "k_genes_stats");
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>((slots + 255) / 256, (uint64_t)ctx->cus * 8);
-            hipLaunchKernelGGL(k_genes_stats, dim3(blocks), dim3(256), 0, st, static_cast<const GeneSlot*>(ctx->gn_table.p), slots, shift, d_stats);
-        }
-        BDG_HIP_TRY(ctx, hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        return BDG_OK;
+        return kmer_stats_launch(ctx, k_genes_stats, "k_genes_stats", B, S.d_stats);
     };
-    if (int rc = kmer_table_build(ctx, ctx->gn_table, windows, slots, ctx->gn_stats, drop, run)) return rc;
-    ctx->gn_k = k;
-    ctx->gn_slots = slots;
-    return BDG_OK;
+    return kmer_table_build(ctx, ctx->gn, bases, seq_off, n_seqs, k, [&] { ctx->gn_mask.reset(); }, run);
 }
 
 // The host-buffer calls bdg_genes_assign, bdg_iso_assign and bdg_genes_assign_spans: the gene pass, and with_iso the isoform
@@ -605,8 +532,8 @@ int bdg_genes_index_stats(bdg_ctx* ctx, uint64_t out[6])
 {
     if (!ctx) return BDG_E_ARG;
     if (!out) return bdg_fail(ctx, BDG_E_ARG, "null pointer");
-    if (ctx->gn_slots == 0) return bdg_fail(ctx, BDG_E_ARG, "genes: no index built (bdg_genes_index_build)");
-    memcpy(out, ctx->gn_stats, sizeof(ctx->gn_stats));
+    if (int rc = genes_check_built(ctx)) return rc;
+    memcpy(out, ctx->gn.stats, sizeof(ctx->gn.stats));
     return BDG_OK;
 }
 

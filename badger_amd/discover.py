@@ -137,12 +137,7 @@ def pileup(index, reads, gene_recs, counts=None):
     k = index.k
     flags, feature = np.asarray(gene_recs["flags"]), np.asarray(gene_recs["feature"])
     take = [r for r in range(len(reads)) if int(flags[r]) & genes.ASSIGNED and int(feature[r]) < AMBIGUOUS]
-    at = 0
-    while at < len(take):
-        end, total = at, 0
-        while end < len(take) and (end == at or total + len(reads[take[end]]) <= PIECE_BASES):
-            total += len(reads[take[end]]) + 1
-            end += 1
+    for at, end in genes.pieces(take, PIECE_BASES, lambda r: len(reads[r]) + 1):
         # the reads of the piece end to end, behind each a position that is no letter: no window and no pair spans two reads
         code, gene = [], []
         for r in take[at:end]:
@@ -150,7 +145,6 @@ def pileup(index, reads, gene_recs, counts=None):
             code += [c, np.full(1, 4, dtype=np.uint8)]
             gene.append(np.full(len(c) + 1, int(feature[r]), dtype=np.uint32))
         code, gene = np.concatenate(code), np.concatenate(gene)
-        at = end
         key, ok = window_keys(code, k)
         n = len(key) - (k + 1)
         if n <= 0:
@@ -249,14 +243,8 @@ def device_find(ctx, min_alt, ppm):
     bdg_sites_select"""
     def run(seqs, gene_recs):
         ctx.sites_reset()
-        at = 0
-        while at < len(seqs):
-            end, total = at, 0
-            while end < len(seqs) and (end == at or total + len(seqs[end]) <= genes.BATCH_BASES):
-                total += len(seqs[end])
-                end += 1
+        for at, end in genes.pieces(seqs):
             ctx.sites_pileup(*genes._flatten(seqs[at:end]), gene_recs[at:end])
-            at = end
         return ctx.sites_select(min_alt, ppm).astype(SITE_DTYPE)
     return run
 

@@ -898,23 +898,31 @@ def _flatten(seqs):
 
 
 # ---------------------------------------------------------------- the product side ----
+def pieces(seqs, most=BATCH_BASES, length=len):
+    """the device calls over a list of reads: -> (at, end) of consecutive pieces seqs[at:end] whose lengths add up to `most` at
+    most, in order and without a gap; an element longer than that is a piece of its own"""
+    at = 0
+    while at < len(seqs):
+        end, total = at, 0
+        while end < len(seqs) and (end == at or total + length(seqs[end]) <= most):
+            total += length(seqs[end])
+            end += 1
+        yield at, end
+        at = end
+
+
 def device_assign(ctx, min_hits, margin=None):
     """assign of count_matrix_text on the device: bdg_genes_assign over pieces of at most BATCH_BASES bases; with a margin
     bdg_iso_assign, and both records"""
     from . import _native
 
     def run(seqs):
-        out, iso, at = np.zeros(len(seqs), dtype=_native.GENE_DTYPE), np.zeros(len(seqs) if margin else 0, dtype=_native.ISO_DTYPE), 0
-        while at < len(seqs):
-            end, total = at, 0
-            while end < len(seqs) and (end == at or total + len(seqs[end]) <= BATCH_BASES):
-                total += len(seqs[end])
-                end += 1
+        out, iso = np.zeros(len(seqs), dtype=_native.GENE_DTYPE), np.zeros(len(seqs) if margin else 0, dtype=_native.ISO_DTYPE)
+        for at, end in pieces(seqs):
             if margin:
                 out[at:end], iso[at:end] = ctx.iso_assign(*_flatten(seqs[at:end]), min_hits, margin)
             else:
                 out[at:end] = ctx.genes_assign(*_flatten(seqs[at:end]), min_hits)
-            at = end
         return (out, iso) if margin else out
     return run
 

@@ -38,6 +38,24 @@ def test_checker_against_the_plain_form(k):
     assert seen > 100
 
 
+def test_pileup_in_several_pieces(monkeypatch):
+    """the checker looks at PIECE_BASES bases in one go: the counts do not depend on where its pieces end"""
+    k = 11
+    seqs, feats, reads, recs = dc.small_case(np.random.default_rng(77), k)
+    idx = dv.build_index(seqs, feats, k)
+    whole = dv.pileup(idx, reads, recs)
+    assert int(whole.sum()) > 0 and sum(len(r) + 1 for r in reads) < dv.PIECE_BASES
+    spans = []
+    for most in (1, max(len(r) for r in reads) + 1, sum(len(r) + 1 for r in reads) // 3):
+        monkeypatch.setattr(dv, "PIECE_BASES", most)
+        seen = []
+        monkeypatch.setattr(gn, "pieces", lambda *a, _of=gn.pieces, _seen=seen: [_seen.append(p) or p for p in _of(*a)])
+        assert (dv.pileup(idx, reads, recs) == whole).all(), most
+        monkeypatch.undo()
+        spans.append(len(seen))
+    assert spans[0] > spans[1] >= spans[2] > 1
+
+
 @pytest.mark.parametrize("k", (11, 15, 31))
 def test_hand_derived_cases(k):
     for name, c in dc.hand_cases(k).items():

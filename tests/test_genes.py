@@ -100,6 +100,21 @@ def _recs(rows):
     return out
 
 
+def test_pieces():
+    """the (at, end) of the device calls: in order, without a gap, at most `most` a piece unless one element alone is more"""
+    assert list(gn.pieces([])) == [] and list(gn.pieces([], 0)) == []
+    seqs = ["A" * n for n in (3, 4, 3, 11, 2, 8, 5, 5)]
+    assert list(gn.pieces(seqs, 10)) == [(0, 3), (3, 4), (4, 6), (6, 8)]     # 3 + 4 + 3 fits exactly, 11 is alone, 2 + 8 and 5 + 5 fit exactly
+    assert list(gn.pieces(seqs, 9)) == [(0, 2), (2, 3), (3, 4), (4, 5), (5, 6), (6, 7), (7, 8)]
+    assert list(gn.pieces(seqs, 1)) == [(i, i + 1) for i in range(8)]         # every element longer than `most`: alone
+    assert list(gn.pieces(seqs)) == [(0, 8)] and gn.BATCH_BASES >= 41
+    # the hook discover.pileup uses: a position more per read, over indices into the reads
+    take = [0, 2, 5, 7]                                                       # 3 + 1, 3 + 1, 8 + 1, 5 + 1
+    assert list(gn.pieces(take, 8, lambda r: len(seqs[r]) + 1)) == [(0, 2), (2, 3), (3, 4)]
+    assert list(gn.pieces(take, 7, lambda r: len(seqs[r]) + 1)) == [(0, 1), (1, 2), (2, 3), (3, 4)]
+    assert list(gn.pieces(take, 15, lambda r: len(seqs[r]) + 1)) == [(0, 2), (2, 4)]
+
+
 def test_molecule_vote():
     A = gn.ASSIGNED
     cb = [b"AAAC"] * 9 + [b"AAAG"] * 3
