@@ -7,8 +7,9 @@
 // alignment behind align_pattern_ssw (:42-51).
 //
 // Launches per batch, no host round trip in between:
-//   k_scan_reads     persistent waves take tasks of 16 reads and stream them as 16-byte vectors, 63 per step, straight from
-//                    the ASCII buffer (through LDS-DMA, two steps ahead): polyT start of both strands (T-windows of the
+//   k_scan_reads     persistent waves take tasks of 16 reads and stream them as pairs of 16-byte vectors, 63 pairs per step (a
+//                    lane holds two neighbouring vectors of one read), straight from the ASCII buffer (through LDS-DMA, one
+//                    step = two vectors ahead): polyT start of both strands (T-windows of the
 //                    reverse complement are A-windows of the read) and every R1 6-mer hit of both strands (7-mer probe
 //                    table in LDS).  The hits of a vector -
 //                    or of two neighbouring vectors cut through one adapter copy - form one CLUSTER
@@ -127,10 +128,14 @@ __device__ __forceinline__ uint32_t range_mask16(int32_t lo, int32_t hi)
 // Autonomous waves, no block barrier after the probe table is in LDS.  A wave repeatedly takes a TASK
 // of 16 consecutive reads from a sharded counter (the next task is taken, and its offsets are
 // loaded, while the current one is processed).  The task's reads are laid end to end as a stream of
-// 16-byte vectors; each step the wave's lanes take 63 consecutive vectors of that stream (lane 63
-// repeats as lane 0 of the next step: it only feeds lane 62's look-ahead), so short tails of one
-// read and the head of the next share a step.  The vectors reach the wave through LDS
-// (global_load_lds_dwordx4, two steps ahead).  polyT candidates are parked and evaluated 64 at a time.
+// PAIR slots: two neighbouring 16-byte vectors of one read, a and b (a read with an odd number of
+// vectors ends in a pad b, whose bytes belong to the next read or lie behind the batch: it sits at
+// read position >= L and owns nothing).  Each step the wave's lanes take 63 consecutive pair slots of
+// that stream (lane 63 holds the a of lane 0 of the next step: it only feeds the look-ahead of lane
+// 62's b), so short tails of one read and the head of the next share a step, and the address, the
+// slot -> read map and the loop are paid once per 32 bases.  a looks ahead into the lane's own b, b
+// into the next lane's a (DPP).  The vectors reach the wave through LDS (global_load_lds_dwordx4, one
+// load per vector, the next step's pair in flight).  polyT candidates are parked and evaluated 64 at a time.
 // Lane-vectors with hits are staged in a per-wave LDS region and become clusters at the end of the
 // task, written to the global queues with ONE packed 64-bit reservation (A count | B count << 32).
 // ---------------------------------------------------------------------------
@@ -139,16 +144,17 @@ constexpr uint32_t WENT = 256;             // per-wave staging (2 KiB)
 constexpr int TASK_SHARDS = NSH;
 
 struct TaskTab {                           // per wave, double buffered
-    uint4    rd[TASK_READS];               // per read {A, -B, L, L - 5}: vector `slot` of the task lies at byte base + A + 16 * slot
-                                           // (A is relative, modulo 2^32) and starts at read position 16 * slot - B
-    uint32_t pend[TASK_READS];             // vectors of reads 0..j inclusive
+    uint4    rd[TASK_READS];               // per read {A, -B, L, L - 5}: pair `slot` of the task (two neighbouring 16-byte vectors of
+                                           // one read, a and b) lies at byte base + A + 32 * slot (A is relative, modulo 2^32) and
+                                           // its a-vector starts at read position 32 * slot - B
+    uint32_t pend[TASK_READS];             // pair slots of reads 0..j inclusive: ceil(vectors / 2) each (an odd read has a pad b)
     uint32_t base_lo, base_hi;             // byte offset of the task's first vector (0 for a task without vectors)
     uint32_t last_off;                     // offset of the task's last vector from there
 };
 
 __device__ __forceinline__ uint32_t find_read(const TaskTab& t, uint32_t slot)
 {
-    // number of reads whose vectors end at or before `slot` (pend is non-decreasing), at most TASK_READS - 1
+    // number of reads whose pair slots end at or before `slot` (pend is non-decreasing), at most TASK_READS - 1
     uint32_t j = t.pend[7] <= slot ? 8u : 0u;
     j += t.pend[j + 3] <= slot ? 4u : 0u;
     j += t.pend[j + 1] <= slot ? 2u : 0u;
@@ -217,7 +223,7 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
     // All of the block's LDS is one object with the probe table first, i.e. at LDS address 0: a probe's address is its index.
     struct Shared {
         uint8_t  kmer[16384];
-        uint8_t  buf[SCAN_WAVES][2][1024];   // per wave: the vectors of the next two steps (LDS-DMA)
+        uint8_t  buf[SCAN_WAVES][2][1024];   // per wave: the a- and the b-vectors of the next step (LDS-DMA)
         uint2    ent[SCAN_WAVES][WENT];      // per-wave staging of lane-vectors with hits (see emit)
         uint32_t ringr[SCAN_WAVES][32];      // read index of each ring slot
         TaskTab  tab[SCAN_WAVES][2];
@@ -260,7 +266,9 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
         const uint64_t r0 = (uint64_t)task * TASK_READS;
         const uint32_t nr = (uint32_t)(n - r0 < TASK_READS ? n - r0 : TASK_READS);
         uint64_t o = 0;
-        if ((uint32_t)lane <= nr) o = off[r0 + lane];
+        int lo_ = lane;                                 // (a copy the compiler cannot see through: the addresses of the per-task
+        asm volatile("" : "+v"(lo_));                   // loads and stores are made where they are used, not held across the steps)
+        if ((uint32_t)lane <= nr) o = off[r0 + lo_];
         // (lanes 0 .. 16 hold the task's offsets: neighbours, prefix sums and maxima over them go through DPP, not LDS)
         const uint64_t o1 = ((uint64_t)wave_shl1((uint32_t)(o >> 32)) << 32) | wave_shl1((uint32_t)o);
         int64_t L = (uint32_t)lane < nr ? (int64_t)(o1 - o) : 0;
@@ -272,19 +280,21 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
         if (L < 0 || L >= (1ll << 26) || o + (uint64_t)L > total_rounded || o - T0 >= (1ull << 30)) { bad = (uint32_t)lane < nr; L = 0; }
         if (bad) atomicMax(&stat[S_BADREAD], ~(unsigned long long)(r0 + lane));        // corrupt offsets: report, never loop on them
         // every vector of a validated read lies inside [0, total_rounded): no bounds checks on the loads below
-        uint32_t nv = L > 0 ? (uint32_t)(((o & 15ull) + (uint64_t)L + 15ull) >> 4) : 0u;
-        uint32_t incl = nv;
+        const uint32_t nv = L > 0 ? (uint32_t)(((o & 15ull) + (uint64_t)L + 15ull) >> 4) : 0u;
+        const uint32_t np = (nv + 1u) >> 1;                    // pair slots (the b of an odd read's last pair is a pad vector)
+        uint32_t incl = np;
         static_assert(TASK_READS == 16, "the sixteen reads of a task are one DPP row");
 #define BDG_ROW_SHR(x, d) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), 0x110 + (d) /* row_shr:d */, 0xF, 0xF, true))
         incl += BDG_ROW_SHR(incl, 1); incl += BDG_ROW_SHR(incl, 2); incl += BDG_ROW_SHR(incl, 4); incl += BDG_ROW_SHR(incl, 8);
         if (lane < TASK_READS) {
-            const uint32_t excl = incl - nv;
-            const uint32_t A = nv ? (uint32_t)((o & ~15ull) - T0) - 16u * excl : 0u;
-            tb.rd[lane] = make_uint4(A, (uint32_t)(-(int32_t)(16u * excl + (uint32_t)(o & 15ull))), (uint32_t)L, (uint32_t)((int32_t)L - (KMER - 1)));
+            const uint32_t excl = incl - np;
+            const uint32_t A = nv ? (uint32_t)((o & ~15ull) - T0) - 32u * excl : 0u;
+            tb.rd[lane] = make_uint4(A, (uint32_t)(-(int32_t)(32u * excl + (uint32_t)(o & 15ull))), (uint32_t)L, (uint32_t)((int32_t)L - (KMER - 1)));
             tb.pend[lane] = incl;
             if (lane == TASK_READS - 1) { tb.base_lo = incl ? (uint32_t)T0 : 0u; tb.base_hi = incl ? (uint32_t)(T0 >> 32) : 0u; }
         }
-        // offset of the last vector: lanes behind the task's end re-read it (a valid address that costs no select)
+        // offset of the last vector: lanes behind the task's end, and the pad b of a task's last read, re-read it (a valid
+        // address that costs no select)
         uint32_t lastv = lane < TASK_READS && nv ? (uint32_t)((o & ~15ull) - T0) + 16u * (nv - 1u) : 0u;
         lastv = max(lastv, BDG_ROW_SHR(lastv, 1)); lastv = max(lastv, BDG_ROW_SHR(lastv, 2));
         lastv = max(lastv, BDG_ROW_SHR(lastv, 4)); lastv = max(lastv, BDG_ROW_SHR(lastv, 8));
@@ -454,13 +464,14 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
     };
 
     // The vectors of a step reach the wave through LDS: global_load_lds_dwordx4 writes lane l's 16 bytes to buffer + 16 l
-    // without passing through registers, so the loads of the next TWO steps stay in flight while a step is worked on (a load
-    // into registers would have to be copied when the steps rotate, and a copy waits for its load; one step of work does not
-    // cover the memory latency at four waves per SIMD).  The compiler does not see these loads: the waits are placed here.
-    // Loads complete in order, so "at most one younger load outstanding" means the older one has landed.
+    // without passing through registers.  A step takes TWO vectors per lane, a and b, each with a load and a 1 KB half of
+    // the buffer of its own; both loads of the next step are issued as soon as this step's vectors are in registers and
+    // stay in flight while the step is worked on (two vector-times: one does not cover the memory latency at four waves
+    // per SIMD).  The compiler does not see these loads: the waits are placed here.
+    // Loads complete in order, so "at most one younger load outstanding" means the older one, a, has landed.
     const uint32_t buf_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)&s_buf[wv][0][0];
-    auto dma_issue = [&](uint32_t g, const uint8_t* gptr) {            // step g's vector of this lane -> buffer g & 1
-        const uint32_t base = __builtin_amdgcn_readfirstlane(buf_lds + (g & 1u) * 1024u);
+    auto dma_issue = [&](uint32_t half, const uint8_t* gptr) {         // this lane's a (0) / b (1) vector -> that half
+        const uint32_t base = __builtin_amdgcn_readfirstlane(buf_lds + half * 1024u);
         asm volatile("s_waitcnt lgkmcnt(0)\n\t"                       // (the buffer's previous contents have been read)
                      "s_mov_b32 m0, %0\n\t"
                      "s_nop 0\n\t"
@@ -476,8 +487,7 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
     uint32_t tseq = 0;                      // ring slot of read j of the current task: (tseq & 1) * TASK_READS + j
     uint32_t task = grab();
     if (task != 0xFFFFFFFFu) load_tab(task, s_tab[wv][cur]);
-    uint32_t g = 0;                         // steps this wave has done
-    bool have_v = false, have_n = false;    // the loads of step g / g + 1 have been issued
+    bool have_v = false;                    // the loads of the next step to run have been issued
     const uint32_t lane_z = lane < 63 ? 0xFFFFFFFFu : 0u;      // lane 63 only feeds lane 62's look-ahead: it stages no hits
     const uint32_t pt_thr = lane < 63 ? 12u : 99u;             // ... and parks no polyT candidates
     while (task != 0xFFFFFFFFu) {
@@ -491,8 +501,7 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
         const uint32_t nslots = __builtin_amdgcn_readfirstlane(tb.pend[TASK_READS - 1]);
         const uint32_t niter = (nslots + 62u) / 63u;
         const uint32_t nnslots = next_task != 0xFFFFFFFFu ? __builtin_amdgcn_readfirstlane(nt.pend[TASK_READS - 1]) : 0u;
-        const uint32_t nniter = (nnslots + 62u) / 63u;
-        // Read of a slot = number of boundaries (pend[k], k < TASK_READS - 1) at or below it.  The lanes of a step hold 64
+        // Read of a pair slot = number of boundaries (pend[k], k < TASK_READS - 1) at or below it.  The lanes of a step hold 64
         // consecutive slots starting at `lo`, and steps are mapped in order: with kb = number of boundaries at or below lo only
         // the boundaries inside the 64 slots are compared (one per step on average).  Leaves kb = boundaries at or below lo + 63.
         uint32_t kb = 0;
@@ -507,119 +516,135 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
             }
             return jv;
         };
-        // address of this lane's vector in step s of this task (jj = read of the lane's slot) / of the next task; a lane
-        // behind the task's end gets the task's last vector (a valid address that costs no select)
+        // Loads of this lane's pair in step s of this task (jj = read of the lane's slot) / in the first step of the next
+        // task.  A lane behind the task's end gets the task's last vector (a valid address that costs no select), and b is
+        // clamped on its own: the pad b of the task's last read would otherwise lie behind the last vector, which may be the
+        // last one of the buffer.
         const uint32_t last_off = __builtin_amdgcn_readfirstlane(tb.last_off), nlast_off = __builtin_amdgcn_readfirstlane(nt.last_off);
         const uint64_t tbase = tab_base(tb);
         const uint64_t nbase = next_task != 0xFFFFFFFFu ? tab_base(nt) : 0ull;
-        auto addr_cur = [&](uint32_t s, uint32_t jj, uint32_t& negB) -> const uint8_t* {      // (also: -B of the lane's read)
+        auto issue_pair = [&](uint64_t base, uint32_t off_a, uint32_t last) {
+            const uint32_t oa = min(off_a, last), ob = min(oa + 16u, last);
+            dma_issue(0u, bases + base + oa);
+            dma_issue(1u, bases + base + ob);
+        };
+        auto issue_cur = [&](uint32_t s, uint32_t jj, uint32_t& negB) {                        // (also: -B of the lane's read)
             const uint32_t sl = s * 63u + (uint32_t)lane;
             const uint2 ab = *reinterpret_cast<const uint2*>(&tb.rd[jj]);
             negB = ab.y;
-            return bases + tbase + min(ab.x + 16u * sl, last_off);
+            issue_pair(tbase, ab.x + 32u * sl, last_off);
         };
-        auto addr_next = [&](uint32_t s) -> const uint8_t* {
-            const uint32_t sl = s * 63u + (uint32_t)lane;
-            return bases + nbase + min(nt.rd[find_read(nt, sl)].x + 16u * sl, nlast_off);
-        };
+        auto issue_next = [&]() { issue_pair(nbase, nt.rd[find_read(nt, (uint32_t)lane)].x + 32u * (uint32_t)lane, nlast_off); };
         const uint32_t ring0 = (tseq & 1u) * TASK_READS;
         if (lane < 2 * TASK_READS) s_ptmin[wv][ring0 + (lane >> 1)][lane & 1] = 0xFFFFFFFFu;
         if (lane < TASK_READS) { s_ringr[wv][ring0 + lane] = (uint32_t)(r0 + lane); s_ringL[wv][ring0 + lane] = (int32_t)tb.rd[lane].z; }
         __builtin_amdgcn_wave_barrier();
-        uint32_t j = map_step(0u, (uint32_t)lane), jn = map_step(63u, 63u + (uint32_t)lane);
-        uint32_t nb = 0, nbn = 0;               // -B of read j / jn (the vector's position in its read is 16 * slot - B)
-        {
-            const uint8_t* const a0 = addr_cur(0u, j, nb);
-            const uint8_t* const a1 = addr_cur(1u, jn, nbn);
-            if (niter) {                        // (start of the batch, or behind a task without vectors: nothing is in flight)
-                if (!have_v) { dma_issue(g, a0); have_v = true; }
-                if (!have_n) {
-                    if (niter > 1u) { dma_issue(g + 1u, a1); have_n = true; }
-                    else if (nniter) { dma_issue(g + 1u, addr_next(0u)); have_n = true; }
-                }
-            }
-        }
-
-        for (uint32_t it = 0; it < niter; ++it, ++g) {
+        uint32_t j = map_step(0u, (uint32_t)lane), jn = 0;
+        uint32_t nb = tb.rd[j].y, nbn = 0;      // -B of read j / jn (the a-vector's position in its read is 32 * slot - B)
+        if (niter && !have_v) { issue_cur(0u, j, nb); have_v = true; }     // (start of the batch, or behind a task without
+                                                                           // vectors: nothing is in flight)
+        for (uint32_t it = 0; it < niter; ++it) {
             const uint32_t slot_lo = it * 63u;
             const uint32_t slot = slot_lo + (uint32_t)lane;
-            dma_wait(have_n);
+            dma_wait(true);                             // a has landed (b is the younger load)
             __builtin_amdgcn_s_setprio(1);              // (steps before per-task work of other waves: measured, 1.5 %)
-            const uint4 v = *reinterpret_cast<const uint4*>(&s_buf[wv][g & 1u][16 * lane]);
+            const uint4 va = *reinterpret_cast<const uint4*>(&s_buf[wv][0][16 * lane]);
 
             // 2-bit codes.  byte & 6 is a perfect hash of "ACTG" (twice the code: 0, 2, 4, 6); v_perm maps it back to the expected
             // letter, v_dot4 packs four of them into twice a byte of codes.  A byte that is not its expected letter (N, a bad
-            // base, the zero padding behind the last read) sends the whole wave through the exact per-byte path.
-            const uint32_t words[4] = { v.x, v.y, v.z, v.w };
-            uint32_t sel[4], diff = 0;
+            // base, the zero padding behind the last read) sends the whole wave through the exact per-byte path, both vectors.
+            // (The codes are packed before the wave decides: the exact path, which is rare, makes its own from the bytes.)
+            uint32_t diff = 0;
+            auto classify = [&](const uint32_t (&w)[4]) -> uint32_t {
+                uint32_t c[4];
 #pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                sel[d] = words[d] & 0x06060606u;
-                diff = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_perm(0x00470054u, 0x00430041u, sel[d]), words[d], diff, 0xBE);   // (a ^ b) | c
-            }
-            asm volatile("" : "+v"(diff));                          // (one compare of the OR, not four compares)
-            // where the step after next comes from
-            uint32_t jnn = 0, nbnn = 0;
-            const uint8_t* pf = bases;
-            bool have_nn = false;
-            if (it + 2u < niter) { jnn = map_step(slot_lo + 126u, slot + 126u); pf = addr_cur(it + 2u, jnn, nbnn); have_nn = true; }
-            else if (it + 2u - niter < nniter) { pf = addr_next(it + 2u - niter); have_nn = true; }
-            if (have_nn) dma_issue(g, pf);                          // the buffer just read takes it
-            // Position of the vector in its read.  Nothing is clipped to the read here: a 6-mer start is checked against the
+                for (int d = 0; d < 4; ++d) {
+                    const uint32_t sel = w[d] & 0x06060606u;
+                    diff = __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_perm(0x00470054u, 0x00430041u, sel), w[d], diff, 0xBE);   // (a ^ b) | c
+                    c[d] = __builtin_amdgcn_udot4(sel, 0x40100401u, 0u, false);      // 2 * (four codes)
+                }
+                return ((((c[3] << 8) + c[2]) << 8) + c[1]) << 7 | (c[0] >> 1);      // (the doubled bytes do not overlap: bit 0 of each is 0)
+            };
+            const uint32_t wa[4] = { va.x, va.y, va.z, va.w };
+            uint32_t codes_a = classify(wa);
+            dma_wait(false);                            // b has landed
+            const uint4 vb = *reinterpret_cast<const uint4*>(&s_buf[wv][1][16 * lane]);
+            const uint32_t wb[4] = { vb.x, vb.y, vb.z, vb.w };
+            uint32_t codes_b = classify(wb);
+            asm volatile("" : "+v"(diff));                          // (one compare of the OR, not eight compares)
+            // where the next step comes from; both halves of the buffer have just been read and take its loads
+            bool have_n = false;
+            if (it + 1u < niter) { jn = map_step(slot_lo + 63u, slot + 63u); issue_cur(it + 1u, jn, nbn); have_n = true; }
+            else if (nnslots) { issue_next(); have_n = true; }
+            // Position of the vectors in their read.  Nothing is clipped to the read here: a 6-mer start is checked against the
             // read when the item becomes a cluster (to_plain); a polyT window start is valid only if its 16 bases lie inside the
             // read (eval_cands), so flags of bytes outside it never count, and the first 'TTT' behind a valid start lies inside
             // its window (>= 12 T among 16 leave a run of three).  A lane behind the task's last vector sits at p0 >= L of the
-            // last read: it has neither.
-            const int32_t p0 = (int32_t)(slot << 4) + (int32_t)nb;
-            const uint32_t where = ((uint32_t)(p0 + 16) << 5) | (ring0 + j);     // position and ring slot, as staged and parked
-            uint32_t zm = lane_z;                                   // 6-mer starts that may hit, Z form
-            uint32_t codes, bad = 0;
-            uint32_t T_s, A_s;                                      // T = code 2, A = code 0: flags on the even bits
+            // last read, and so does the pad b of an odd read: they have neither.
+            const int32_t p0 = (int32_t)(slot << 5) + (int32_t)nb;               // of a; b starts 16 further on
+            const uint32_t where = ((uint32_t)(p0 + 16) << 5) | (ring0 + j);     // position and ring slot of a, as staged and parked
+            uint32_t zm_a = lane_z, zm_b = lane_z;                  // 6-mer starts that may hit, Z form
+            uint32_t bad = 0;
+            uint32_t TA_a, TA_b;                                   // T = code 2 on the even bits, A = code 0 on the odd bits
             const bool exact = __ballot(diff != 0) != 0;
             if (!exact) {
-                uint32_t c[4];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) c[d] = __builtin_amdgcn_udot4(sel[d], 0x40100401u, 0u, false);      // 2 * (four codes)
-                codes = ((((c[3] << 8) + c[2]) << 8) + c[1]) << 7 | (c[0] >> 1);      // (the doubled bytes do not overlap: bit 0 of each is 0)
-                T_s = (codes >> 1) & ~codes & 0x55555555u;
-                A_s = ~((codes >> 1) | codes) & 0x55555555u;
+                auto flags = [](uint32_t codes) -> uint32_t {
+                    return ((codes >> 1) & ~codes & 0x55555555u) | ((~((codes >> 1) | codes) & 0x55555555u) << 1);
+                };
+                TA_a = flags(codes_a); TA_b = flags(codes_b);
             } else {
-                uint32_t fm = 0x55555555u;                                       // positions whose T / A flag counts
                 const int32_t L = (int32_t)tb.rd[j].z;
-                uint32_t nN = 0, nbad = 0;
-                codes = 0;
+                // Per byte: N / not a base at all (the codes are (byte >> 1) & 3 here too).  Four bytes at a time: bit 7 of
+                // ((x & 0x7F..) + 0x7F..) | x is set iff the byte of x is not zero, and a multiplication gathers the four flags.
+                auto bytes = [](const uint32_t (&w)[4], uint32_t& nN, uint32_t& nbad) {
+                    auto nonzero = [](uint32_t x) -> uint32_t { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; };
+                    auto gather4 = [](uint32_t m) -> uint32_t { return (((m >> 7) * 0x00204081u) >> 21) & 15u; };
+                    nN = 0; nbad = 0;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const uint32_t b = (words[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                    const bool isN = b == 'N';
-                    const bool ok = b == 'A' || b == 'C' || b == 'G' || b == 'T';
-                    nN |= (isN ? 1u : 0u) << k;
-                    nbad |= ((isN || ok) ? 0u : 1u) << k;
-                    codes |= ((b >> 1) & 3u) << (2 * k);
-                }
-                const int32_t lo_t = max(-p0, 0);                                // read bases of this vector: [lo_t, hi)
-                const int32_t hi = min(max(L - p0, 1), 16);
-                const bool same_next = lane < 63 && p0 + 16 < L;                 // the next lane holds the next 16 bases of the same read
-                const uint32_t rm16 = (0xFFFFu >> (16 - hi)) & (0xFFFFu << lo_t);
-                bad = slot < nslots ? nbad & rm16 : 0u;                          // (a lane behind the task's end owns no base)
-                nN = (nN | ~rm16) & 0xFFFFu;                                     // out-of-read behaves like N
-                fm &= ~spread16(nN | nbad);                                      // neither T nor A
-                uint32_t N1 = wave_shl1(nN);
-                if (!same_next) N1 = 0xFFFFu;
-                const uint32_t N32 = nN | (N1 << 16);
-                uint32_t nvm = N32 | (N32 >> 1);
-                nvm |= nvm >> 2;
-                nvm |= N32 >> 4; nvm |= N32 >> 5;
-                zm &= z_from_mask16(~nvm);                                       // 6-mers touching an N never match
-                T_s = (codes >> 1) & ~codes & fm;
-                A_s = ~((codes >> 1) | codes) & fm;
+                    for (int d = 0; d < 4; ++d) {
+                        const uint32_t notN = nonzero(w[d] ^ 0x4E4E4E4Eu);
+                        const uint32_t notbase = nonzero(w[d] ^ __builtin_amdgcn_perm(0x00470054u, 0x00430041u, w[d] & 0x06060606u));
+                        nN |= gather4(notN ^ 0x80808080u) << (4 * d);
+                        nbad |= gather4(notN & notbase) << (4 * d);
+                    }
+                };
+                auto read_mask = [&](int32_t p) -> uint32_t {                    // read bases of a vector at p: [lo_t, hi)
+                    const int32_t lo_t = max(-p, 0);
+                    const int32_t hi = min(max(L - p, 1), 16);
+                    return (0xFFFFu >> (16 - hi)) & (0xFFFFu << lo_t);
+                };
+                auto no_match = [](uint32_t nN, uint32_t N1) -> uint32_t {       // 6-mers touching an N never match
+                    const uint32_t N32 = nN | (N1 << 16);
+                    uint32_t nvm = N32 | (N32 >> 1);
+                    nvm |= nvm >> 2;
+                    nvm |= N32 >> 4; nvm |= N32 >> 5;
+                    return z_from_mask16(~nvm);
+                };
+                uint32_t nN_a, nN_b, nbad_a, nbad_b;
+                bytes(wa, nN_a, nbad_a);
+                bytes(wb, nN_b, nbad_b);
+                const uint32_t rm_a = read_mask(p0), rm_b = read_mask(p0 + 16);
+                // (a lane behind the task's end owns no base; neither does a pad b: read_mask keeps its bit 0)
+                bad = slot < nslots ? (nbad_a & rm_a) | (p0 + 16 < L ? nbad_b & rm_b : 0u) : 0u;
+                nN_a = (nN_a | ~rm_a) & 0xFFFFu;                                 // out-of-read behaves like N
+                nN_b = (nN_b | ~rm_b) & 0xFFFFu;
+                const uint32_t fm_a = 0x55555555u & ~spread16(nN_a | nbad_a);    // positions whose T / A flag counts
+                const uint32_t fm_b = 0x55555555u & ~spread16(nN_b | nbad_b);
+                // the next 16 bases of the same read: a's are the lane's own b, b's the next lane's a
+                uint32_t N1_b = wave_shl1(nN_a);
+                if (!(lane < 63 && p0 + 32 < L)) N1_b = 0xFFFFu;
+                zm_a &= no_match(nN_a, p0 + 16 < L ? nN_b : 0xFFFFu);
+                zm_b &= no_match(nN_b, N1_b);
+                TA_a = ((codes_a >> 1) & ~codes_a & fm_a) | ((~((codes_a >> 1) | codes_a) & fm_a) << 1);
+                TA_b = ((codes_b >> 1) & ~codes_b & fm_b) | ((~((codes_b >> 1) | codes_b) & fm_b) << 1);
             }
 
-            // look-ahead from the next lane (one DPP move each)
-            const uint32_t TA = T_s | (A_s << 1);
-            const uint32_t TA1 = wave_shl1(TA);
-            const uint32_t codes1 = wave_shl1(codes);
+            // b's look-ahead comes from the next lane's a (one DPP move each); a's is the lane's own b
+            const uint32_t TA1_b = wave_shl1(TA_a);
+            const uint32_t codes1_b = wave_shl1(codes_a);
 
+            // One vector: its probes are issued, its polyT candidates parked, and its hit word (Z form, masked) returned.
+            auto scan_vec = [&](uint32_t codes, uint32_t codes1, uint32_t TA, uint32_t TA1, uint32_t zm, uint32_t where) -> uint32_t {
             // R1 6-mer hits of both strands: 8 probes of the 7-mer table, two positions each.  (Issued by hand: the compiler
             // masks every sub-dword LDS load although ds_read_u8 zero-extends.)
             uint32_t e[8];
@@ -640,8 +665,8 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
             {
                 // (lane 63 never parks: its vector is lane 0's of the next step.  A lane behind the task's end may: it sits at
                 // p0 >= L, where eval_cands finds no valid window start.)
-                const bool cT = __popc(T_s) + __popc(TA1 & 0x15555555u) >= pt_thr;
-                const bool cA = __popc(A_s) + __popc(TA1 & 0x2AAAAAAAu) >= pt_thr;
+                const bool cT = __popc(TA & 0x55555555u) + __popc(TA1 & 0x15555555u) >= pt_thr;
+                const bool cA = __popc(TA & 0xAAAAAAAAu) + __popc(TA1 & 0x2AAAAAAAu) >= pt_thr;
                 const unsigned long long bT = __builtin_amdgcn_ballot_w64(cT), bA = __builtin_amdgcn_ballot_w64(cA), bc = bT | bA;
                 if (bc) {
                     // one entry per lane: its flags of both kinds, the kind to evaluate in bit 0 of the info word
@@ -657,29 +682,43 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
                     }
                 }
             }
+            // A table entry holds the forward hits of its two positions in bits 0-1 and the reverse hits in bits 4-5: two
+            // probes make a byte of Z.
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]), "+v"(e[6]), "+v"(e[7]));
+            const uint32_t b0 = e[0] | (e[1] << 2), b1 = e[2] | (e[3] << 2), b2 = e[4] | (e[5] << 2), b3 = e[6] | (e[7] << 2);
+            return ((b0 | (b1 << 8)) | ((b2 | (b3 << 8)) << 16)) & zm;
+            };
+            // (evaluation between the two vectors' parking: at most 63 candidates carried + 126 of one vector are parked)
+            const uint32_t z_a = scan_vec(codes_a, codes_b, TA_a, TA_b, zm_a, where);
+            __builtin_amdgcn_wave_barrier();
+            while (ncand >= 64u) { ncand -= 64u; eval_cands(ncand, 64u); }
+            const uint32_t z_b = scan_vec(codes_b, codes1_b, TA_b, TA1_b, zm_b, where + (16u << 5));
             if (exact && __ballot(bad != 0)) {
                 if (bad != 0) atomicMax(&stat[S_BADREAD], ~(unsigned long long)(r0 + j));
             }
-            // Lanes with hits stage {Z, position, ring slot}; they become queue entries at the next flush.  A table entry holds
-            // the forward hits of its two positions in bits 0-1 and the reverse hits in bits 4-5: two probes make a byte of Z.
+            // Vectors with hits stage {Z, position, ring slot}; they become queue entries at the next flush.  Both vectors
+            // of the step are staged together, a lane's a in front of its b: neighbouring vectors stay neighbours (emit merges
+            // two of them that cut one adapter copy).
             {
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]), "+v"(e[6]), "+v"(e[7]));
-                const uint32_t b0 = e[0] | (e[1] << 2), b1 = e[2] | (e[3] << 2), b2 = e[4] | (e[5] << 2), b3 = e[6] | (e[7] << 2);
-                const uint32_t z = ((b0 | (b1 << 8)) | ((b2 | (b3 << 8)) << 16)) & zm;
-                const unsigned long long bal = __ballot(z != 0);
-                if (bal) {
-                    const uint32_t cnt = (uint32_t)__popcll(bal);
-                    const uint2 item = make_uint2(z, where);
+                const unsigned long long bal_a = __ballot(z_a != 0), bal_b = __ballot(z_b != 0);
+                if (bal_a | bal_b) {
+                    const uint32_t cnt = (uint32_t)__popcll(bal_a) + (uint32_t)__popcll(bal_b);
                     if (nent + cnt <= WENT) {
-                        if (z) ent[nent + lanes_below(bal)] = item;
+                        const uint32_t at = nent + lanes_below(bal_a) + lanes_below(bal_b);
+                        if (z_a) ent[at] = make_uint2(z_a, where);
+                        if (z_b) ent[at + (z_a ? 1u : 0u)] = make_uint2(z_b, where + (16u << 5));
                         nent += cnt;
-                    } else {
-                        emit(false, item, z != 0, 0u, true);       // staging full (pathological reads): straight to queue A
+                    } else {                                       // staging full (pathological reads): straight to queue A
+#pragma unroll 1
+                        for (uint32_t h = 0; h < 2u; ++h) {
+                            const uint32_t z = h ? z_b : z_a;
+                            emit(false, make_uint2(z, where + h * (16u << 5)), z != 0, 0u, true);
+                        }
                     }
                 }
             }
-            j = jn; jn = jnn; nb = nbn; nbn = nbnn;
-            have_v = have_n; have_n = have_nn;
+            j = jn; nb = nbn;
+            have_v = have_n;
             __builtin_amdgcn_wave_barrier();
             while (ncand >= 64u) { ncand -= 64u; eval_cands(ncand, 64u); }
         }
@@ -692,9 +731,11 @@ void k_scan_reads(const uint8_t* __restrict__ bases, uint64_t total_rounded,
             const int32_t pv = pk == 0xFFFFFFFFu ? -1 : (int32_t)((pk >> 5) + (pk & 31u));
             s_pt[wv][ring0 + (lane >> 1)][lane & 1] = pv;
             if ((uint32_t)lane < 2 * nr) {
-                polyt[2 * r0 + lane] = pv;
-                keys[2 * r0 + lane] = 0ull;                              // best relaxed / strict alignment of the read-strand:
-                keys[2ull * n + 2 * r0 + lane] = 0ull;                   // none yet (k_sw_clusters runs after this kernel)
+                int lo_ = lane;
+                asm volatile("" : "+v"(lo_));                            // (as in load_tab)
+                polyt[2 * r0 + lo_] = pv;
+                keys[2 * r0 + lo_] = 0ull;                               // best relaxed / strict alignment of the read-strand:
+                keys[2ull * n + 2 * r0 + lo_] = 0ull;                    // none yet (k_sw_clusters runs after this kernel)
             }
         }
         __builtin_amdgcn_wave_barrier();
