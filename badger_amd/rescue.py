@@ -6,6 +6,9 @@ A read whose row prints "*" (no usable R1 adapter) may still hold its barcode wh
 UMI, the tail.  Per read, with umi_len U, the whitelist and a support s(w) per entry (the run's exact hits, what --bc_correct
 counts):
   eligible    rec.valid == 0, no FLAG_INCOMPLETE, the 3' layout
+  strand text strand_text(read, strand): every byte other than A C G T reads as N (lower case, IUPAC codes, gaps: the ingest
+              folds nothing), the reverse strand is the reversed text with A <-> T, C <-> G and N kept.  The windows and the UMI
+              are taken from it, so a byte outside ACGT kills the windows that hold it and prints as N in the UMI, on both strands.
   candidates  both strand texts s (the read, its reverse complement): p = find_polyt_start(s); with p >= 0, for every offset d
               in -SLACK .. +SLACK the window s[b : b + 16], b = p - U - 16 + d, when 0 <= b, b + 16 <= len(s) and all 16
               letters are ACGT.  At most ten.
@@ -39,6 +42,17 @@ RESCUE_DTYPE = np.dtype([("read", "<u4"), ("entry", "<u4"), ("support", "<u4"), 
 FIELDS = RESCUE_DTYPE.names
 
 
+# the strand text: total over bytes (trim.revcomp is the trim rule's and knows ACGTN only)
+_FORWARD = "".join(chr(c) if chr(c) in "ACGT" else "N" for c in range(256))
+_REVERSE = "".join({"A": "T", "C": "G", "G": "C", "T": "A"}.get(chr(c), "N") for c in range(256))
+
+
+def strand_text(read, strand=1):
+    """the text the rule reads on a strand (+1 the read, -1 its reverse complement): A C G T as they are (complemented on the
+    reverse strand), every other byte N; the complement of N is N"""
+    return read.translate(_FORWARD) if strand > 0 else read[::-1].translate(_REVERSE)
+
+
 def check_params(umi_len, max_ed):
     if not 1 <= umi_len <= UMI_MAX:
         raise ValueError("umi_len %d is outside 1 .. %d" % (umi_len, UMI_MAX))
@@ -48,7 +62,10 @@ def check_params(umi_len, max_ed):
 
 def find_polyt_start(s, window=16, fraction=0.75):
     """the reference's find_polyt_start (barcode_extraction/common.py:10-31): the first window start i in 0 .. len(s) - window - 1
-    whose `window` letters hold at least int(window * fraction) 'T', moved on to the first "TTT" from there; -1 without one"""
+    whose `window` letters hold at least int(window * fraction) 'T', moved on to the first "TTT" from there; -1 without one.
+    s: a strand text, or a raw read standing for its forward strand - it is translated here, which changes nothing in a
+    text that is one already (candidates() hands over strand texts), so only 'T' counts whatever else a read holds"""
+    s = strand_text(s)
     need, n = int(window * fraction), len(s)
     if n < window:
         return -1
@@ -68,7 +85,7 @@ def eligible(rec, layout=LAYOUT_3P):
 def candidates(read, umi_len):
     """[(strand, p, d, b, window)] of a read, strand +1 (the read) / -1 (its reverse complement), whatever its record says"""
     out = []
-    for strand, s in ((1, read), (-1, revcomp(read))):
+    for strand, s in ((1, strand_text(read, 1)), (-1, strand_text(read, -1))):
         p = find_polyt_start(s)
         if p < 0:
             continue
@@ -162,7 +179,7 @@ def rescue_read(read, umi_len, matcher, support, max_ed=MAX_ED_DEFAULT, min_supp
     if status != RESCUED:
         return NONE_IDX, 0, -1, -1, 0, e, 0, status, b""
     strand, p, d, b, _ = cands[i]
-    s = read if strand > 0 else revcomp(read)
+    s = strand_text(read, strand)
     return entry, int(support[entry]), p, b, d, e, strand, status, s[b + 16:p].encode()
 
 
@@ -178,7 +195,7 @@ def rescue_batch(bases, off, recs, umi_len, wl, support, max_ed=MAX_ED_DEFAULT, 
     for i in range(len(off) - 1):
         if not eligible(recs[i], layout):
             continue
-        r = rescue_read(text[off[i]:off[i + 1]].decode("ascii"), umi_len, matcher, support, max_ed, min_support)
+        r = rescue_read(text[off[i]:off[i + 1]].decode("latin-1"), umi_len, matcher, support, max_ed, min_support)
         if r is not None:
             out.append((i,) + r)
     return np.array(out, dtype=RESCUE_DTYPE)

@@ -429,6 +429,10 @@ int  bdg_split_batch(bdg_ctx* ctx, const uint8_t* bases, const uint64_t* off, ui
  * whitelist and a support array s(w) over its entries (uint32 [nw], indexed like the whitelist the caller loaded: what
  * --bc_correct counts, the run's exact hits per entry).  Integers only.
  *   eligible    rec.valid == 0, no BDG_FLAG_INCOMPLETE, the context in BDG_LAYOUT_3P (in BDG_LAYOUT_5P no read is eligible).
+ *   strand text every byte of the read other than 'A' 'C' 'G' 'T' reads as 'N' (lower case, IUPAC codes and gaps included: the
+ *               ingest folds nothing); the reverse strand is the reversed text with A <-> T, C <-> G, and the complement of N
+ *               is N.  Windows and umi are taken from this text on both strands: such a byte kills every window that holds it
+ *               and prints as 'N' in umi.
  *   candidates  both strand texts s of length L: the read and its reverse complement.  p = find_polyt_start(s) with the
  *               reference's defaults (barcode_extraction/common.py:10-31: the first window of 16 letters holding >= 12 'T' among
  *               the window starts 0 .. L - 17, moved on to the first "TTT" from there if there is one; -1 without such a window) -
@@ -467,7 +471,8 @@ typedef struct bdg_rescue_rec {
     int8_t   dist;       /* e */
     int8_t   strand;     /* +1: the read as given, -1: its reverse complement, 0: not rescued */
     uint8_t  status;     /* BDG_RESCUE_* */
-    char     umi[16];    /* s[b + 16 : p], U - d letters (U +- BDG_RESCUE_SLACK), zero-padded */
+    char     umi[16];    /* s[b + 16 : p] of the strand text (A C G T N), U - d letters (U +- BDG_RESCUE_SLACK), zero-padded: no
+                            terminator at 16 letters, empty for U - d <= 0 */
 } bdg_rescue_rec;        /* 40 bytes */
 /* Device-resident: the bases, offsets and records of the bdg_extract_batch_dev call just made (same stream), d_support [nw] on
  * the device, d_out with room for n records.  Runs the three steps - k_rescue_windows (eligible reads compacted into the
