@@ -59,6 +59,10 @@ GENE_ASSIGNED, GENE_LOW, GENE_TIE, GENE_CROWDED = 1, 2, 4, 8
 # bdg_allele_rec: a read's windows that carry either allele of a known SNV (bdg_alleles_assign; the rule in badger_amd/alleles.py)
 ALLELE_DTYPE = np.dtype([("read", "<u4"), ("variant", "<u4"), ("ref_hits", "<u4"), ("alt_hits", "<u4")])
 ALLELES_K_DEFAULT, ALLELES_MAX_VARIANTS = 15, 256
+# bdg_fusion_rec: where along a read the hits of its two best genes lie (bdg_fusion_scan; the rule in badger_amd/fusions.py)
+FUSION_DTYPE = np.dtype([("feat_a", "<u4"), ("hits_a", "<u4"), ("first_a", "<u4"), ("last_a", "<u4"), ("feat_b", "<u4"), ("hits_b", "<u4"),
+                         ("first_b", "<u4"), ("last_b", "<u4"), ("third", "<u4"), ("flags", "<u4")])
+FUSION_SPLIT, FUSION_A_UP, FUSION_SKIPPED, FUSION_INTERLEAVED = 1, 2, 4, 8
 # bdg_site_rec: a selected site of the pileup (bdg_sites_select; the rule in badger_amd/discover.py); ref, alt: codes A 0 .. T 3
 SITE_DTYPE = np.dtype([("site", "<u4"), ("ref", "<u4"), ("alt", "<u4"), ("pad", "<u4"), ("count", "<u4", (4,))])
 SITES_K_DEFAULT, SITES_MAX = 11, 0xFFFFFFFF
@@ -125,6 +129,7 @@ EXPORTS = [
     "bdg_umi_dedup_genes", "bdg_umi_dedup_genes_dev", "bdg_umi_dedup_genes_set_aggregate", "bdg_umi_set_max_dist",
     "bdg_alleles_index_build", "bdg_alleles_index_stats", "bdg_alleles_assign_dev", "bdg_alleles_assign",
     "bdg_alleles_index_values",
+    "bdg_fusion_scan", "bdg_fusion_scan_dev",
     "bdg_sites_index_build", "bdg_sites_index_stats", "bdg_sites_pileup_dev", "bdg_sites_pileup", "bdg_sites_reset", "bdg_sites_select",
     "bdg_sites_counts_to_host",
     "bdg_donor_scores", "bdg_donor_scores_dev",
@@ -424,6 +429,8 @@ def load():
     L.bdg_alleles_index_values.argtypes = [vp, C.POINTER(u32)]
     L.bdg_alleles_assign_dev.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
     L.bdg_alleles_assign.argtypes = [vp, vp, vp, u32, vp, vp, u64, vp]
+    L.bdg_fusion_scan.argtypes = [vp, vp, vp, u32, vp, u32, vp]
+    L.bdg_fusion_scan_dev.argtypes = [vp, vp, vp, u32, vp, u32, vp]
     L.bdg_sites_index_build.argtypes = [vp, vp, vp, u32, vp, u32]
     L.bdg_sites_index_stats.argtypes = [vp, vp]
     L.bdg_sites_pileup_dev.argtypes = [vp, vp, vp, u32, vp]
@@ -942,6 +949,20 @@ class Context:
             return rc, out, int(counts[0])
         out = self._with_capacity(call, n if cap is None else int(cap), "bdg_alleles_assign", retry)
         return out[np.lexsort((out["variant"], out["read"]))], int(counts[1])
+
+    def fusion_scan_dev(self, d_bases, d_off, n, d_gene_recs, min_hits, d_out):
+        """bdg_fusion_scan_dev: the fusion record of every read over device arrays and the gene records of the same reads,
+        asynchronous"""
+        self._check(self.lib.bdg_fusion_scan_dev(self.h, _ptr(d_bases), _ptr(d_off), int(n), _ptr(d_gene_recs), int(min_hits), _ptr(d_out)))
+
+    def fusion_scan(self, bases, off, gene_recs, min_hits):
+        """where along every read the hits of its two best genes lie, over host arrays, gene_recs GENE_DTYPE [n] what genes_assign
+        gave for them (bdg_fusion_scan) -> FUSION_DTYPE [n]"""
+        bases, off, gene_recs, n = _reads_with_genes(bases, off, gene_recs)
+        out = np.zeros(n, dtype=FUSION_DTYPE)
+        self._check(self.lib.bdg_fusion_scan(self.h, bases.ctypes.data, off.ctypes.data, n, gene_recs.ctypes.data, int(min_hits),
+                                             out.ctypes.data))
+        return out
 
     def sites_index_build(self, bases, seq_off, features, k=SITES_K_DEFAULT):
         """the site table of the transcripts (bases uint8, seq_off uint64 [n + 1], features uint32 [n]) on the device, beside the

@@ -13,6 +13,7 @@
                                  [--allele_k 15] [--allele_min_hits 1]
                                  [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
                                   [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
+                                [--fusions [--fusion_min_hits 8] [--fusion_min_molecules 2]]
 
     python -m badger_amd.badger -r reads.fastq -d tenX_v3 ... --transcripts tx.fa [--tx2gene map.tsv] --count_matrix DIR --matrix_from_reads
                                 [--tagged_reads tagged.fa] [the options of --count_matrix]
@@ -60,6 +61,11 @@ read that lie --discover_k + 1 apart on one diagonal of the read's own gene encl
 per transcript position; a position where at least --discover_min_alt reads and --discover_min_frac of them show another letter
 than the transcript's becomes a variant.  DIR/discovered_variants.tsv holds them in --variants' format, discovered_sites.tsv their
 counts, and the run goes on as with --variants DIR/discovered_variants.tsv (discover.py).  Not with --matrix_from_reads.
+--fusions calls gene fusions from the tagged reads whose front belongs to one gene and whose back to another: a pass on the device
+over the reads whose two best genes both have --fusion_min_hits keys says where along the read each gene's keys lie; a read whose two
+stretches do not interleave is split, the vote over the molecules of matrix.mtx follows, and a pair of genes that at least
+--fusion_min_molecules molecules support is reported with its junctions in the transcripts: read_fusions.tsv, fusions.tsv and
+fusion_matrix.mtx in DIR (fusions.py).  Not with --matrix_from_reads: the junctions need the reads' bases.
 --matrix_from_reads writes the same DIR from the one pass over the reads: every read's gene (and isoform) call is made on the device
 from its cDNA where it lies in the read, while its chunk is there (genes.py MatrixFromReads).  --tagged_reads is then optional, and
 a tagged file is written as without the flag but not read back; without it the input is read once.  One column differs: the UR of
@@ -90,6 +96,7 @@ from .genes import (K_DEFAULT as GENE_K_DEFAULT, MIN_HITS_DEFAULT as GENE_MIN_HI
 from .alleles import add_allele_options, check_allele_options, log_counts as log_allele_counts
 from .discover import add_discover_options, check_discover_options, log_counts as log_discover_counts
 from .donors import add_donor_options, check_donor_options, log_counts as log_donor_counts
+from .fusions import add_fusion_options, check_fusion_options, log_counts as log_fusion_counts
 from .barcode_extraction.barcode_callers import context_keeping, context_trimming, contexts_in_layout
 from .extract_raw_barcodes import (BARCODE_CALLING_MODES, _chimera_max_ed, _split_max_ed, check_split_args, split_kwargs, _tso5_max_ed, _tso_min_score, check_5p_args, is_native_input,
                                    trim_5p_values)
@@ -176,6 +183,7 @@ def parse_args(args):
     add_allele_options(p)
     add_donor_options(p)
     add_discover_options(p)
+    add_fusion_options(p)
     a = p.parse_args(args)
     if a.matrix_from_reads and not (a.count_matrix and a.transcripts):
         p.error("--matrix_from_reads needs --count_matrix and --transcripts: it is another way to that matrix")
@@ -190,6 +198,7 @@ def parse_args(args):
     check_allele_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
     check_discover_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
     check_donor_options(p, a, bool(a.variants) or a.discover_variants)
+    check_fusion_options(p, a, bool(a.count_matrix), a.matrix_from_reads)
     if a.umi_dist is not None and not a.umi_dedup:
         p.error("--umi_dist needs --umi_dedup")
     if a.tagged_reads and a.reads.endswith("tsv"):
@@ -369,11 +378,12 @@ def write_count_matrix(args):
     counts = count_matrix_of_tagged(args.tagged_reads, args.transcripts, args.tx2gene, args.count_matrix, args.gene_k,
                                     args.gene_min_hits, args.device, args.iso_margin, args.em,
                                     (UMI_LEN[args.data_type], args.gene_umi_dist) if args.umi_per_gene else None, args.alleles,
-                                    args.donors, args.discover)
+                                    args.donors, args.discover, args.fusion_calls)
     log_counts(counts, args.count_matrix)
     log_discover_counts(counts, args.count_matrix)
     log_allele_counts(counts, args.count_matrix)
     log_donor_counts(counts, args.count_matrix)
+    log_fusion_counts(counts, args.count_matrix)
 
 
 def write_matrix_from_reads(args, matrix, st2, ctx, read_ids):

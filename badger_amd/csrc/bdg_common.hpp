@@ -185,6 +185,7 @@ struct bdg_ctx {
     DevBuf st_counts;    // u32 [st_sites][4]: the pileup, accumulated over the calls since the build or bdg_sites_reset
     uint64_t st_sites = 0;                   // seq_off[n_seqs] of the build: sites are 0 .. st_sites - 1
     int st_pileup_per_cu = 0;                // blocks of k_sites_pileup resident on a compute unit (asked once)
+    int fu_scan_per_cu = 0;                  // fusion_kernels.hip: blocks of k_fusion_scan resident on a compute unit (asked once)
     int em_per_cu = 0;                      // em_kernels.hip: blocks of k_em_tcc resident on a compute unit (asked once)
     int donor_per_cu[4] = { 0, 0, 0, 0 };   // donors_kernels.hip: the same per instantiation of k_donor_scores
     int cluster_per_cu[3] = { 0, 0, 0 };    // demux_kernels.hip: the same of k_cluster_counts, k_cluster_assign and k_cluster_words

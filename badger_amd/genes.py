@@ -9,6 +9,7 @@ that every read and molecule is compatible with.
                                 [--allele_k 15] [--allele_min_hits 1]
                                 [(--donor_genotypes donors.tsv | --donors K [--donor_restarts 8] [--donor_max_iter 50] [--donor_seed 1])
                                  [--donor_error 0.01] [--doublet_rate 0.1] [--donor_min_variants 10] [--donor_min_llr 2.0]]]
+                               [--fusions [--fusion_min_hits 8] [--fusion_min_molecules 2]]
 
 Two things live here.  The CHECKER restates the rule that include/badger_hip.h states at bdg_genes_index_build, in numpy and
 integers only; the tests hold the device against it and it is not on the product path.  The DRIVER (count_matrix_of_tagged) is
@@ -774,7 +775,7 @@ def em_files(names, tx_names, feat, cells, molecules, run, eps=EM_EPS_DEFAULT, m
     return {"isoform_em_matrix.mtx": "".join(rows).encode(), "isoform_em_pool.tsv": "".join(pool_rows).encode()}, counts
 
 
-def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None, alleles=None):
+def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None, alleles=None, fusions=None):
     """the four files of a tagged file's bytes: names the feature ids in first-appearance order of the transcript file,
     assign(list of sequences) -> REC_DTYPE array is assign_reads over an index or the device's equivalent
     -> ({file name: bytes}, counts dict).  With isoforms = (transcript names, their feature ids) assign returns the pair
@@ -784,7 +785,8 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None
     gene from the headers' UR: matrix.mtx and the isoform and EM matrices follow them, gene_molecules.tsv joins the files, the
     other files stay the same bytes.
     With alleles (--variants; an alleles.Caller) the four files of alleles.FILES and their counts join; every other file stays
-    the same bytes."""
+    the same bytes.
+    With fusions (--fusions; a fusions.Caller) the three files of fusions.FILES and their counts join likewise."""
     from .consensus import parse_tagged
     heads, seqs, cb, ub = parse_tagged(text)
     take = [i for i, c in enumerate(cb) if c is not None]
@@ -795,15 +797,18 @@ def count_matrix_text(text, names, assign, isoforms=None, em=None, per_gene=None
     heads = [heads[i] for i in take]
     return count_matrix_records([h.split(b"\t")[0] for h in heads], [cb[i] for i in take], [ub[i] for i in take],
                                 _ur_texts(heads) if per_gene is not None else None, recs, names, iso, isoforms, em, per_gene,
-                                len(cb) - len(take), None if alleles is None else lambda *a: alleles([seqs[i] for i in take], *a))
+                                len(cb) - len(take), None if alleles is None else lambda *a: alleles([seqs[i] for i in take], *a),
+                                fusions=None if fusions is None else lambda *a: fusions([seqs[i] for i in take], *a))
 
 
-def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, em=None, per_gene=None, no_cell=0, alleles=None):
+def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, em=None, per_gene=None, no_cell=0, alleles=None,
+                         fusions=None):
     """what count_matrix_text does behind the parse and the gene calls, for both routes to the matrix.  Per read that has a cell:
     ids its name, cb its cell, ub its molecule or None (all bytes), ur its UMI text or None (looked at with per_gene only), recs
     REC_DTYPE, iso ISO_DTYPE with isoforms; names, isoforms, em, per_gene as for count_matrix_text; no_cell: reads left out for
     want of a cell, for the log; alleles: the hook of --variants, called with (ids, cb, ub, recs, the barcodes, per read its
-    molecule text with per_gene or None) -> ({file name: bytes}, counts dict)"""
+    molecule text with per_gene or None); fusions: the hook of --fusions, called exactly like alleles
+    -> ({file name: bytes}, counts dict)"""
     if per_gene is not None:
         made = molecules_per_gene(cb, ur, recs, per_gene[0], per_gene[1], per_gene[2], iso)
     else:
@@ -828,6 +833,10 @@ def count_matrix_records(ids, cb, ub, ur, recs, names, iso=None, isoforms=None, 
         more, allele_counts = alleles(ids, cb, ub, recs, cells, rows)
         files.update(more)
         counts.update(allele_counts)
+    if fusions is not None:
+        more, fusion_counts = fusions(ids, cb, ub, recs, cells, rows)
+        files.update(more)
+        counts.update(fusion_counts)
     if isoforms is not None:
         more, iso_counts = isoform_files(names, isoforms[0], isoforms[1], ids, cb, ub, iso, cells, molecules)
         files.update(more)
@@ -944,7 +953,7 @@ def device_em(ctx):
 
 
 def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, min_hits=MIN_HITS_DEFAULT, device=0, iso_margin=None,
-                           em=None, per_gene=None, variants=None, donors=None, discover=None):
+                           em=None, per_gene=None, variants=None, donors=None, discover=None, fusions=None):
     """path_in: a tagged FASTA of `badger.py --tagged_reads`; out_dir takes features.tsv, barcodes.tsv, matrix.mtx and
     reads.tsv, with iso_margin (--isoforms) the files of ISO_FILES, and with em = (eps, max_iter, init) (--isoform_em) those of
     EM_FILES, and with per_gene = (umi_len, umi_dist) (--umi_per_gene) the molecules per cell and gene from the device
@@ -954,8 +963,11 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
     donors.ClusterOptions in the path's place (--donors) the donors are clusters fitted on the device (bdg_donor_cluster) and the
     files of donors.CLUSTER_FILES come too; with discover = (k, min_alt, ppm, allele k, allele min_hits) (--discover_variants, in
     variants' place) the variants are found in the reads by the pileup on the device (bdg_sites_pileup), the files of
-    discover.FILES come too and the rest follows as with variants = DIR/discovered_variants.tsv -> counts"""
+    discover.FILES come too and the rest follows as with variants = DIR/discovered_variants.tsv; with fusions = (min_hits,
+    min_molecules) (--fusions) every read's fusion record from the device (bdg_fusion_scan) over the genes table, and the files
+    of fusions.FILES -> counts"""
     from . import _native, alleles
+    from . import fusions as fusions_step
     from . import discover as discover_step
     from . import donors as donors_step
     ctx = _native.default_context(device)
@@ -973,7 +985,8 @@ def count_matrix_of_tagged(path_in, transcripts, tx2gene, out_dir, k=K_DEFAULT, 
         files, counts = count_matrix_text(open(path_in, "rb").read(), names, device_assign(ctx, min_hits, iso_margin),
                                           (tx_names, feat) if iso_margin else None,
                                           (device_em(ctx),) + tuple(em) if iso_margin and em else None,
-                                          (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None, caller)
+                                          (device_dedup_genes(ctx),) + tuple(per_gene) if per_gene else None, caller,
+                                          fusions_step.device_caller(ctx, transcripts, names, feat, k, *fusions) if fusions else None)
     finally:                                   # the context is shared inside the process: the table goes, 64 empty slots stay
         _drop_index(ctx, k)
         if variants or discover:
@@ -1230,6 +1243,8 @@ def parse_args(argv):
     add_donor_options(p)
     from .discover import add_discover_options, check_discover_options
     add_discover_options(p)
+    from .fusions import add_fusion_options, check_fusion_options
+    add_fusion_options(p)
     p.add_argument("--umi_len", type=gene_umi_len_arg, default=None, metavar="L",
                    help="--umi_per_gene: letters of the library's UMI, 3 .. 12 (a UMI is usable at L - 2 .. L + 2 letters)")
     p.add_argument("--device", type=int, default=0, help="MI355X device index")
@@ -1246,6 +1261,7 @@ def parse_args(argv):
     check_allele_options(p, a, True)
     check_discover_options(p, a, True)
     check_donor_options(p, a, bool(a.variants) or a.discover_variants)
+    check_fusion_options(p, a, True)
     return a
 
 
@@ -1258,11 +1274,13 @@ def main(argv):
     from .discover import log_counts as log_discover_counts
     from .donors import log_counts as log_donor_counts
     counts = count_matrix_of_tagged(a.input, a.transcripts, a.tx2gene, a.output, a.gene_k, a.gene_min_hits, a.device, a.iso_margin,
-                                    a.em, a.per_gene, a.alleles, a.donors, a.discover)
+                                    a.em, a.per_gene, a.alleles, a.donors, a.discover, a.fusion_calls)
     log_counts(counts, a.output)
     log_discover_counts(counts, a.output)
     log_allele_counts(counts, a.output)
     log_donor_counts(counts, a.output)
+    from .fusions import log_counts as log_fusion_counts
+    log_fusion_counts(counts, a.output)
 
 
 if __name__ == "__main__":

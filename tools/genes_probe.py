@@ -56,6 +56,13 @@ over its class counts, one JSON line each to --out (and stdout).
     python tools/genes_probe.py --cli --discover ...
         the command line with --count_matrix --discover_variants against --count_matrix alone, then the pairs with --parent as
         above.
+    python tools/genes_probe.py --device --fusions [--reads 1000000] [--tx_bases 4000000] [--reps 10] --out profiles/r32_fusions.jsonl
+        the first workload once more with one read in a hundred a fragment of a planted fusion transcript:
+        bdg_fusion_scan_dev behind bdg_genes_assign_dev on the same reads, k_fusion_scan beside k_genes_assign from the event timers
+        of the same run, the median of --reps runs each; then the worst case, every read a fragment of a planted fusion, so that
+        every read but the random ones passes the gate and the scan walks the windows the gene kernel walks.
+    python tools/genes_probe.py --cli --fusions ...
+        the command line with --count_matrix --fusions against --count_matrix alone, then the pairs with --parent as above.
 """
 import argparse
 import os
@@ -311,6 +318,63 @@ def device_probe_discover(args):
     ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
     ctx.alleles_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), 0, ak)
     ctx.sites_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), dk)
+
+
+def device_probe_fusions(args):
+    from badger_amd import _native
+    from badger_amd import fusions as fu
+    _native.PRELOAD_TORCH = False
+    ctx = _native.default_context(0)
+    for tx_bases in args.tx_bases:
+        n_tx = max(tx_bases // TX_LEN, 1)
+        rng = np.random.default_rng(7)
+        tx = rng.integers(0, 4, (n_tx, TX_LEN), dtype=np.uint8)
+        ctx.genes_index_build(ACGT[tx].ravel(), (np.arange(n_tx + 1) * TX_LEN).astype(np.uint64), np.arange(n_tx, dtype=np.uint32), args.k)
+
+        def fused(cut, n_f=1000):                         # fusion transcripts: the first `cut` bases of one, the rest of another
+            u, d = rng.integers(0, n_tx, n_f), rng.integers(0, n_tx, n_f)
+            return np.concatenate([tx[u, :cut], tx[d, cut:]], axis=1)
+        n_few = args.reads // 100
+        for what, parts in (("one read in a hundred a fragment of a planted fusion, the junction 1,000 bases from the 3' end",
+                             ((tx, args.reads - n_few, 1), (fused(TX_LEN - 1000), n_few, 2))),
+                            ("the worst case: every read a fragment of a planted fusion, the junction 300 bases from the 3' end",
+                             ((fused(TX_LEN - 300), args.reads, 3),))):
+            bases, off = fragments(*parts[0])
+            for part in parts[1:]:
+                more, more_off = fragments(*part)
+                bases, off = np.concatenate([bases, more]), np.concatenate([off, more_off[1:] + off[-1]]).astype(np.uint64)
+            n = len(off) - 1
+            d = [_native.DeviceArray.from_host(ctx, a) for a in (bases, off)]
+            d_gene, d_out = _native.DeviceArray(ctx, n * 6, np.uint32), _native.DeviceArray(ctx, n * 10, np.uint32)
+
+            def call():
+                ctx.genes_assign_dev(d[0], d[1], n, args.min_hits, d_gene)
+                ctx.fusion_scan_dev(d[0], d[1], n, d_gene, args.fusion_min_hits, d_out)
+            call()
+            ctx.synchronize()
+            per_run = {}
+            ctx.profile(True)
+            for _ in range(args.reps):
+                ctx.profile_reset()
+                call()
+                ctx.synchronize()
+                for k, v in ctx.profile_read().items():
+                    if k in ("k_genes_assign", "k_fusion_scan") and v[0]:
+                        per_run.setdefault(k, []).append(v[1])
+            ctx.profile(False)
+            flags = d_out.to_host().view(_native.FUSION_DTYPE)["flags"]
+            med = {k: float(np.median(v)) for k, v in per_run.items()}
+            emit(args.out, {"what": "bdg_fusion_scan_dev behind bdg_genes_assign_dev, device-resident: " + what, "gene_k": args.k,
+                            "gene_min_hits": args.min_hits, "fusion_min_hits": args.fusion_min_hits, "transcripts": n_tx,
+                            "transcript_bases": int(n_tx * TX_LEN), "reads": n, "read_bases": int(off[-1]),
+                            "scanned": int(((flags & fu.SKIPPED) == 0).sum()), "split": int(((flags & fu.SPLIT) != 0).sum()),
+                            "interleaved": int(((flags & fu.INTERLEAVED) != 0).sum()), "reps": args.reps,
+                            "kernel_ms_median": {k: round(v, 4) for k, v in med.items()},
+                            "kernel_ms_runs": {k: [round(x, 4) for x in v] for k, v in per_run.items()},
+                            "fusion_over_genes": round(med["k_fusion_scan"] / med["k_genes_assign"], 4)})
+            for a in d + [d_gene, d_out]:
+                a.free()
+    ctx.genes_index_build(np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, np.uint32), args.k)
 
 
 def _variants_of(tx, path, per_tx=4):
@@ -634,7 +698,7 @@ def cli_probe(args):
         r = subprocess.run([sys.executable] + args_of(out) + extra, cwd=cwd, capture_output=True, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(r.stdout[-2000:] + r.stderr[-2000:])
-        return time.perf_counter() - t0, [l.split(" - ")[-1].replace(tmp, "TMP") for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l or "Alleles: " in l or "Discovery: " in l]
+        return time.perf_counter() - t0, [l.split(" - ")[-1].replace(tmp, "TMP") for l in r.stdout.split("\n") if "Genes: " in l or "Isoforms: " in l or "Isoform EM: " in l or "Alleles: " in l or "Discovery: " in l or "Fusions: " in l]
 
     def pairs(name_a, a, name_b, b, what):
         walls, said = {name_a: [], name_b: []}, []
@@ -663,6 +727,10 @@ def cli_probe(args):
             matrix = ["--umi_dedup"] + gene + ["--count_matrix", os.path.join(tmp, "matrix")]
             pairs("tagged_route", (ROOT, matrix + ["--tagged_reads", fa]), "from_reads", (ROOT, matrix + ["--matrix_from_reads"]),
                   "stage2 CLI from FASTQ, --umi_dedup --count_matrix%s: --matrix_from_reads against --tagged_reads" % what)
+    elif args.fusions:
+        matrix = tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]
+        pairs("count_matrix", (ROOT, matrix), "fusions", (ROOT, matrix + ["--fusions"]),
+              "stage2 CLI from FASTQ, --umi_dedup --tagged_reads --count_matrix: with --fusions against without")
     elif args.discover:
         matrix = tagged + ["--transcripts", tx, "--count_matrix", os.path.join(tmp, "matrix")]
         pairs("count_matrix", (ROOT, matrix), "discover", (ROOT, matrix + ["--discover_variants"]),
@@ -706,6 +774,8 @@ def main():
     p.add_argument("--spans", action="store_true", help="the span kernels beside the forward ones (--device), --matrix_from_reads (--cli) (DESIGN 4.25)")
     p.add_argument("--alleles", action="store_true", help="the allele leg of --device and of --cli (DESIGN 4.26)")
     p.add_argument("--discover", action="store_true", help="the discovery leg of --device and of --cli (DESIGN 4.29)")
+    p.add_argument("--fusions", action="store_true", help="the fusion leg of --device and of --cli (DESIGN 4.31)")
+    p.add_argument("--fusion_min_hits", type=int, default=8)
     p.add_argument("--discover_k", type=int, default=11)
     p.add_argument("--discover_min_alt", type=int, default=5)
     p.add_argument("--count_layout", default="[site][4]", help="--discover: what the record says of the library's count layout")
@@ -721,7 +791,7 @@ def main():
     p.add_argument("--out", default=None)
     args = p.parse_args()
     if args.device:
-        (device_probe_discover if args.discover else device_probe_alleles if args.alleles else device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
+        (device_probe_fusions if args.fusions else device_probe_discover if args.discover else device_probe_alleles if args.alleles else device_probe_spans if args.spans else device_probe_iso if args.isoforms else device_probe)(args)
     if args.em and not args.cli:
         em_probe(args)
     if args.cli:
